@@ -1,6 +1,14 @@
 """bench.py — headline benchmark of the MI355X ray-trace core (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--config 4] [--camera static|orbit] [--form auto|onecall|rccl] [--t01 0.25]
+                    [--full] [--dump-outputs DIR]
+
+A plain run measures the headline only: set-up, W warm-up frames, the K timed frames, the counting replay of those frames that
+`value` is priced on, and the result line.  --full adds everything else (roofline, cpu_baseline, without_statistics,
+moving_camera, frames_in_flight, post_stage / sdr_frame_ms; with --gpus N > 1 the batched job attached as `batched`).
+--dump-outputs DIR writes what the timed path computed in its last step (the frame after TAA and, where the process holds the
+whole frame, that frame's radiance before TAA) as DIR/<buffer>.npy in float32: the whole buffer, or a fixed seeded sample of
+its pixels where the buffers together would exceed 64 MB.
 
 A "step" is one frame of the hot path (ray-gen + per-pixel trace + TAA; with N > 1 also the reassembly of the tiles) over the
 configuration BASELINE.json quotes the metric on: config 4, the Dragon-class mesh (871,200-triangle procedural stand-in for the
@@ -20,7 +28,7 @@ How N GPUs are driven (`--form`):
            this process touches no GPU; it starts N one-process-per-GPU children itself (`python -m torch.distributed.run
            --nproc-per-node N bench.py ... --form resident`, a child process, never an exec), relays rank 0's line, and when the
            children exit non-zero starts the next form in FRESH children: resident -> rccl -> onecall.  `forms_tried` in the line says
-           what ran; `rccl_world` is dist.get_world_size() after a checked all-reduce.  After a resident headline the batched
+           what ran; `rccl_world` is dist.get_world_size() after a checked all-reduce.  With --full, after a resident headline the batched
            launches (--batch 4) run as a second job whose result is attached as `batched` - never the headline: `latency_frames`
            says how many frames lie between a pose and its image.
 `n_gpus` in the line is the number of devices that traced tiles this run (`device_tiles` lists their tile counts), never the flag.
@@ -145,6 +153,30 @@ def timed_twin_work(flat, fbw, fbh, ss, pose, first_frame, frames, device, movin
             "scene_tree_steps": round(tree, 1), "objects_culled_by_their_solid_box": round(d[4, 3], 1), "grids_asked": round(d[4, 4], 1), "grids_entered": round(d[4, 5], 1),
             "cell_steps": round(d[4, 6], 1), "cell_fetches": round(d[4, 7], 1), "light_records": round(lrec, 1), "continuation_rays": round(cont, 1),
             "frames": frames, "what": "per frame, every stage kernel (k_wf_primary, k_wf_trace_p, k_wf_lights, k_wf_shade) of the timed build's counting twin on the timed frames"}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes each per-pixel buffer (H x W [x C]) as out_dir/<name>.npy in float32.  Where the buffers together would exceed `budget`,
+    every one is cut to the same fixed sample of pixels (seed DUMP_SAMPLE_SEED, ascending pixel order): (n, C) instead of (H, W, C)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    idx = None
+    if total > budget:
+        pixels = {a.shape[0] * a.shape[1] for a in arrays.values()}
+        assert len(pixels) == 1, "buffers of different sizes"
+        n_pix = pixels.pop()
+        bytes_per_pixel = total // n_pix
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_pix, budget // bytes_per_pixel, replace=False))
+    for k, a in arrays.items():
+        if idx is not None:
+            a = a.reshape(a.shape[0] * a.shape[1], -1)[idx]
+        np.save(d / f"{k}.npy", a)
 
 
 def orbit_pose(pose, k):
@@ -275,8 +307,8 @@ def launch_ranks(n, argv, chain=FORM_CHAIN, extra=BATCHED_LEG, script=None, time
     env.setdefault("MASTER_ADDR", "127.0.0.1")
     tried, headline = [], None
 
-    def run(name, form_args):
-        cmd = child_command(name, n, free_port(), script) + base + form_args
+    def run(name, form_args, drop=()):
+        cmd = child_command(name, n, free_port(), script) + strip_flag(base, drop) + form_args
         t0 = time.perf_counter()
         proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, start_new_session=True)
         try:
@@ -318,7 +350,7 @@ def launch_ranks(n, argv, chain=FORM_CHAIN, extra=BATCHED_LEG, script=None, time
     if headline is None:
         return None, tried
     if extra and tried[-1]["form"] == "resident":
-        b = run(*extra)
+        b = run(*extra, drop=("--dump-outputs",))          # the outputs dumped are the headline's
         headline["batched"] = ({k: b.get(k) for k in ("value", "unit", "ms_per_step", "n_gpus", "rccl_world", "latency_frames")} | {"parallelism": b["config"]["parallelism"]}) if b else {"failed": tried[-1]["rc"]}
     headline["forms_tried"] = tried
     headline["launched_by"] = "bench.py itself: " + " ".join(child_command(tried[0]["form"], n, "<port>", "bench.py", python="python")) + " ..."
@@ -341,6 +373,9 @@ def main():
     ap.add_argument("--no-post", action="store_true", help="skip the frames WITH the denoise/exposure/tonemap stage (reported apart as post_stage)")
     ap.add_argument("--no-flight", action="store_true", help="skip the frames-in-flight leg (ycge_render_frame_async; reported apart as frames_in_flight)")
     ap.add_argument("--no-moving", action="store_true", help="skip the moving-camera leg (reported apart as moving_camera)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (roofline, CPU baseline, the other legs; "
+                                                        "the --no-* flags above choose among them); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -354,7 +389,7 @@ def main():
             chain = (("resident", ["--form", "resident", "--batch", str(args.batch)]),)
         if force_tiled and args.gpus == 1:
             chain = tuple(f for f in chain if f[0] != "onecall")
-        line, tried = launch_ranks(args.gpus, sys.argv[1:], chain=chain, extra=BATCHED_LEG if args.form == "auto" else None)
+        line, tried = launch_ranks(args.gpus, sys.argv[1:], chain=chain, extra=BATCHED_LEG if (args.form == "auto" and args.full) else None)
         if line is None:
             raise SystemExit("bench.py --gpus %d: no form produced a line: %s" % (args.gpus, json.dumps(tried)))
         print(json.dumps(line))
@@ -583,7 +618,7 @@ def main():
         step(r)
     fence()
     first_frame = args.warmup + 1
-    steps0 = r.timed_steps() if not multi else 0
+    steps0 = r.timed_steps() if (args.full and not multi) else 0
     per_step = []
     if multi and resident:
         rs_timing[0] = True
@@ -596,7 +631,7 @@ def main():
     issue_s = time.perf_counter() - t0          # host time to QUEUE the timed frames (several processes: nothing waits inside the loop)
     fence()
     elapsed = time.perf_counter() - t0
-    timed_lane_steps = (r.timed_steps() - steps0) / args.steps if not multi else None
+    timed_lane_steps = (r.timed_steps() - steps0) / args.steps if (args.full and not multi) else None
     device_tiles = [int(r.stats.device_tiles[i]) for i in range(int(r.stats.n_devices_traced))] if not multi else None
     trace_ms = [p[0] for p in per_step]
     frame_ms = [p[1] for p in per_step]
@@ -618,6 +653,13 @@ def main():
         dist.all_gather(allt, nt)
         device_tiles = [int(t.item()) for t in allt]
     n_gpus_used = sum(1 for t in device_tiles if t > 0)
+    if args.dump_outputs and rank == 0:
+        # the frame of the last timed step as a caller of ycge_render_frame reads it back; the tile-resident form's ranks hold the
+        # resolved frame (all-gathered history) but only their own tiles of the radiance before TAA
+        bufs = {"taa_history": abi.BUF_TAA_HISTORY}
+        if not (multi and resident):
+            bufs["current_hdr"] = abi.BUF_CURRENT_HDR
+        dump_outputs(args.dump_outputs, {k: r.read(v) for k, v in bufs.items()})
 
     # ---- exact work of the timed frames: counting replay (untimed; same frame numbers, same poses)
     rc = make(True)
@@ -648,7 +690,7 @@ def main():
     share = world if multi else 1
     my_alg = algorithmic_bytes({k: v / share for k, v in per_frame.items()}, pixels / share) * launch_frames
     roof = None
-    if mean_trace_ms:
+    if mean_trace_ms and args.full:
         ach = my_alg / (mean_trace_ms * 1e-3) / 1e9
         # which launches trace_ms brackets: the single-launch kernel k_trace with k_trace_fan beside it for the head of the schedule
         # (two streams forked from and joined to the frame's stream: the duration is their makespan; scenes without heavy blocks
@@ -709,7 +751,7 @@ def main():
     # records no timing events - the event between the trace and TAA is a packet of its own that the TAA launch waits behind.  The headline
     # `value` stays the call WITH statistics: its trace duration is what the roofline is priced on.
     no_stats = None
-    if single and not moving:
+    if args.full and single and not moving:
         n = min(args.steps, 200)
         ts = []
         for k in range(n):
@@ -720,7 +762,7 @@ def main():
                 raise abi.YcgeError(rc, "ycge_render_frame without statistics")
         no_stats = {"frames": n, "frame_ms": dist3(ts), "what": "ycge_render_frame(ctx, NULL, NULL): the frame through TAA with no statistics asked for, synchronous"}
     mov = None
-    if not args.no_moving and not moving and not multi:      # the frame the host really drives: the pose changes every frame (RaytraceEntity.cs:221-232)
+    if args.full and not args.no_moving and not moving and not multi:      # the frame the host really drives: the pose changes every frame (RaytraceEntity.cs:221-232)
         n = 64
         rows = []
         resets = 0
@@ -743,7 +785,7 @@ def main():
         r.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
 
     flight = None
-    if single and not moving and not args.no_flight:        # frames in flight (ycge_render_frame_async; no counterpart in the reference): the same frames, queued without waiting
+    if args.full and single and not moving and not args.no_flight:        # frames in flight (ycge_render_frame_async; no counterpart in the reference): the same frames, queued without waiting
         n = min(args.steps, 300)
         for _ in range(args.warmup):
             r.RenderAsync()
@@ -775,7 +817,7 @@ def main():
                           "The headline `value` stays the synchronous call, which is the reference's TryFlipAndBlit; trace_ms here is the launch with TAA running beside it"}
 
     post = None
-    if not args.no_post and not multi:        # the frame the C# wrapper asks for (SDR out); outside the headline metric, which SURVEY 8d times through TAA
+    if args.full and not args.no_post and not multi:        # the frame the C# wrapper asks for (SDR out); outside the headline metric, which SURVEY 8d times through TAA
         ms = []
         for _ in range(12):
             r.TryFlipAndBlit(want_sdr=True, copy=False)
@@ -799,7 +841,7 @@ def main():
         post["waived"] = {"post_ms": round(float(np.median(msw[:, 0])), 4), "frame_ms_with_sdr_readback": round(float(np.median(msw[:, 1])), 4)}
 
     cpu = None
-    if rank == 0 and single and not args.no_cpu_baseline:
+    if args.full and rank == 0 and single and not args.no_cpu_baseline:
         import oracle_binding as ob
         threads = os.cpu_count() or 1
         o = ob.OracleRenderer(scene, fbw, fbh, ss, pose, flat=flat)

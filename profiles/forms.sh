@@ -13,7 +13,7 @@ except Exception as e:
     print("FAILED", e, l[-1][-600:] if l else "")'
 for spec in "auto" "rccl" "resident --batch 3 --steps 51"; do
   echo "== python bench.py --gpus 1 --form $spec   (self-launch, world 1)"
-  YCGE_BENCH_FORCE_TILED=1 timeout 900 python bench.py --gpus 1 --steps 52 --warmup 5 --form $spec --no-cpu-baseline --no-post 2>&1 | grep -v amdgpu.ids | python -c "$show"
+  YCGE_BENCH_FORCE_TILED=1 timeout 900 python bench.py --full --gpus 1 --steps 52 --warmup 5 --form $spec --no-cpu-baseline --no-post 2>&1 | grep -v amdgpu.ids | python -c "$show"
 done
 echo "== the same under an outer launcher (what the task statement's command line does): torch.distributed.run -> bench.py --form auto"
-YCGE_BENCH_FORCE_TILED=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 52 --warmup 5 --no-cpu-baseline --no-post 2>&1 | grep -v amdgpu.ids | python -c "$show"
+YCGE_BENCH_FORCE_TILED=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 52 --warmup 5 --no-cpu-baseline --no-post 2>&1 | grep -v amdgpu.ids | python -c "$show"

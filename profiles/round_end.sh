@@ -12,14 +12,15 @@ bash profiles/run_profiles.sh ${TAG}_c4 > gpurun_out/prof_${TAG}_c4.log 2>&1; ec
 bash profiles/run_profiles.sh ${TAG}_c5 --config 5 > gpurun_out/prof_${TAG}_c5.log 2>&1; echo "profiles c5 rc=$?"; head -12 gpurun_out/prof_${TAG}_c5/summary.txt
 bash profiles/run_profiles.sh ${TAG}_c5lit --config 5 --t01 0.5 > gpurun_out/prof_${TAG}_c5lit.log 2>&1; echo "profiles c5 lit rc=$?"; head -12 gpurun_out/prof_${TAG}_c5lit/summary.txt
 mkdir -p profiles/$RND; for f in gpurun_out/prof_${TAG}_c4/pmc_config4.json gpurun_out/prof_${TAG}_c5/pmc_config5.json gpurun_out/prof_${TAG}_c5lit/pmc_config5_t050.json; do [ -f $f ] && cp $f profiles/$RND/; done
-timeout 600 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err; echo "bench rc=$?"
-for c in 1 2 3 5; do timeout 400 python bench.py --config $c --cpu-seconds 10 2>> gpurun_out/bench_$TAG.err > gpurun_out/bench_${TAG}_cfg$c.json; done
-timeout 500 python bench.py --config 5 --t01 0.5 --cpu-seconds 10 2>> gpurun_out/bench_$TAG.err > gpurun_out/bench_${TAG}_cfg5_t050.json
-timeout 300 python bench.py --camera orbit --no-cpu-baseline > gpurun_out/bench_${TAG}_orbit.json 2>> gpurun_out/bench_$TAG.err
+BENCH_OUT=${BENCH_OUT:-$REPO/bench_out}; mkdir -p $BENCH_OUT          # the JSON lines of bench.py --full (each with every leg beside the headline)
+timeout 600 python bench.py --full > $BENCH_OUT/bench_$TAG.json 2> $BENCH_OUT/bench_$TAG.err; echo "bench rc=$?"
+for c in 1 2 3 5; do timeout 400 python bench.py --full --config $c --cpu-seconds 10 2>> $BENCH_OUT/bench_$TAG.err > $BENCH_OUT/bench_${TAG}_cfg$c.json; done
+timeout 500 python bench.py --full --config 5 --t01 0.5 --cpu-seconds 10 2>> $BENCH_OUT/bench_$TAG.err > $BENCH_OUT/bench_${TAG}_cfg5_t050.json
+timeout 300 python bench.py --full --camera orbit --no-cpu-baseline > $BENCH_OUT/bench_${TAG}_orbit.json 2>> $BENCH_OUT/bench_$TAG.err
 for f in bench_$TAG bench_${TAG}_cfg1 bench_${TAG}_cfg2 bench_${TAG}_cfg3 bench_${TAG}_cfg5 bench_${TAG}_cfg5_t050 bench_${TAG}_orbit; do python - <<PY
 import json
 try:
-    d = json.load(open("gpurun_out/$f.json"))
+    d = json.load(open("$BENCH_OUT/$f.json"))
     fl = d.get("frames_in_flight") or {}
     print("$f", d["value"], "Mrays/s (by the reference's count", d.get("value_reference_ray_count"), ")", d["ms_per_step"], "ms/frame; trace", d.get("trace_ms"), "in flight", fl.get("ms_per_step"), fl.get("value"), "gate", fl.get("gate"), "with sdr", (fl.get("with_sdr") or {}).get("ms_per_step"), "cpu", (d.get("cpu_baseline") or {}).get("value"), "x", d.get("gpu_over_cpu"), "moving", (d.get("moving_camera") or {}).get("trace_ms"), "post", (d.get("post_stage") or {}).get("post_ms"), (d.get("post_stage") or {}).get("frame_ms_with_sdr_readback"), "roofline frac", (d.get("roofline") or {}).get("frac"))
 except Exception as e:
@@ -43,7 +44,7 @@ timeout 300 python profiles/mega_prof.py 4 2>&1 | grep -v amdgpu.ids > gpurun_ou
 echo "== voxel worlds: the walk tree against the scene tree, the light loop beside the trace, walk_phase (lit config 5, same call)"
 for v in "-" "YCGE_NO_WALK_TREE=1" "YCGE_NO_LIGHTS_BESIDE=1" "-"; do
   ( if [ "$v" != "-" ]; then export "$v"; fi; echo -n "$v: "
-    timeout 300 python bench.py --config 5 --t01 0.5 --steps 20 --warmup 3 --no-cpu-baseline --no-post 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'],'ms/frame trace', d['roofline']['mean_launch_ms'], 'moving', d['moving_camera']['trace_ms']['median'], 'in flight', d['frames_in_flight']['ms_per_step'])" )
+    timeout 300 python bench.py --full --config 5 --t01 0.5 --steps 20 --warmup 3 --no-cpu-baseline --no-post 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'],'ms/frame trace', d['roofline']['mean_launch_ms'], 'moving', d['moving_camera']['trace_ms']['median'], 'in flight', d['frames_in_flight']['ms_per_step'])" )
 done
 if [ -f yetanotherconsolegameengine_amd/lib/var_voxstat.so ]; then YCGE_LIB=$REPO/yetanotherconsolegameengine_amd/lib/var_voxstat.so timeout 300 python profiles/vox_stats.py 0.5 2>&1 | grep -v amdgpu.ids; fi
 if [ -f yetanotherconsolegameengine_amd/lib/var_coopstat.so ]; then YCGE_LIB=$REPO/yetanotherconsolegameengine_amd/lib/var_coopstat.so timeout 200 python profiles/coop_stats.py 4 2>&1 | grep -v amdgpu.ids; fi

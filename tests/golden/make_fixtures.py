@@ -4,6 +4,7 @@ Run in the authoring container only (needs /root/reference for the bunny asset):
     python tests/golden/make_fixtures.py bunny      # parse the reference's OBJ asset -> npz (data, not source)
     python tests/golden/make_fixtures.py goldens    # oracle-rendered golden buffers for config 1 (needs oracle/liborc_oracle.so)
     python tests/golden/make_fixtures.py post       # same scene through denoise / exposure / tonemap (frames 1-3)
+    python tests/golden/make_fixtures.py objs DIR   # cow.obj and teapot.obj of the reference's ConsoleGame/assets (DIR) -> obj_meshes.npz
 
 The bunny fixture is the reference's own data file (ConsoleGame/assets/stanford-bunny.obj, the
 Stanford bunny as exported by MeshLab) stored as parsed float32 positions + int32 fan-triangulated
@@ -65,6 +66,21 @@ def post():
         print("post:", {k: np.shape(v) for k, v in out.items()})
 
 
+def objs(assets_dir):
+    """the reference's other two OBJ assets as MeshLoader.cs:23-55 parses them (float32 positions, int32 fan-triangulated faces): what
+    tests/test_host_cpu.py writes back out as OBJ text and parses, beside the bunny fixture"""
+    from yetanotherconsolegameengine_amd import mesh_loader
+    out = {}
+    for name in ("cow", "teapot"):
+        pos, faces = mesh_loader.load_obj(Path(assets_dir) / f"{name}.obj")
+        out[f"{name}_positions"], out[f"{name}_faces"] = pos, faces
+    np.savez_compressed(HERE / "obj_meshes.npz", **out)
+    print("objs:", {k: v.shape for k, v in out.items()})
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["objs"]:
+        objs(sys.argv[2])
+        sys.exit(0)
     for what in sys.argv[1:] or ["bunny", "goldens", "post"]:
         {"bunny": bunny, "goldens": goldens, "post": post}[what]()

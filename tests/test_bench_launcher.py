@@ -103,9 +103,9 @@ def test_forms_fail_soft_in_fresh_children(tmp_path):
     assert line["config"]["form"] == "resident" and line["batched"] == {"failed": tried[-1]["rc"]} and tried[-1]["rc"] != 0
 
 
-def test_plain_gpus_n_never_touches_torch_in_the_parent(tmp_path):
-    """`python bench.py --gpus 2` end to end with the stub in place of the child script: the parent process must not import torch (the
-    driver's rule: nothing that initialises a GPU may precede the start of the ranks) and must print exactly one line."""
+def self_launch(tmp_path, argv):
+    """`python bench.py <argv>` end to end with the stub in place of the child script, in a fresh process that refuses to import torch;
+    returns the one line it printed and the stub's log"""
     stub = tmp_path / "stub_bench.py"
     stub.write_text(STUB)
     code = textwrap.dedent(f'''
@@ -120,7 +120,7 @@ def test_plain_gpus_n_never_touches_torch_in_the_parent(tmp_path):
         import bench
         orig = bench.launch_ranks
         bench.launch_ranks = lambda n, argv, **kw: orig(n, argv, script={str(stub)!r}, log=open("/dev/null", "w"), **kw)
-        sys.argv = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"]
+        sys.argv = ["bench.py"] + {list(argv)!r}
         bench.main()
         assert "torch" not in sys.modules
     ''')
@@ -131,8 +131,25 @@ def test_plain_gpus_n_never_touches_torch_in_the_parent(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [x for x in r.stdout.splitlines() if x.strip()]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    log = tmp_path / "stub.log"
+    return json.loads(lines[0]), [json.loads(x) for x in log.read_text().splitlines()] if log.exists() else []
+
+
+def test_plain_gpus_n_never_touches_torch_in_the_parent(tmp_path):
+    """`python bench.py --gpus 2 --full` end to end with the stub in place of the child script: the parent process must not import torch (the
+    driver's rule: nothing that initialises a GPU may precede the start of the ranks) and must print exactly one line."""
+    d, recs = self_launch(tmp_path, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", str(tmp_path / "dump")])
     assert d["config"]["form"] == "resident" and d["n_gpus"] == 2 and [t["form"] for t in d["forms_tried"]] == ["resident", "resident_batch4"]
+    assert all("--full" in r["argv"] for r in recs)
+    assert all(("--dump-outputs" in r["argv"]) == (r["tag"] == "resident") for r in recs)          # the headline's outputs, not the batched job's
+
+
+def test_a_plain_run_starts_the_headline_job_only(tmp_path):
+    """without --full the batched job is not run: one job, its ranks started once, the caller's --steps forwarded"""
+    d, recs = self_launch(tmp_path, ["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    assert d["config"]["form"] == "resident" and [t["form"] for t in d["forms_tried"]] == ["resident"] and "batched" not in d
+    assert sorted(r["rank"] for r in recs) == [0, 1] and all(r["tag"] == "resident" and "--full" not in r["argv"] for r in recs)
+    assert all(r["argv"][r["argv"].index("--steps") + 1] == "3" for r in recs)
 
 
 def test_build_staleness_is_by_content(tmp_path):

@@ -682,21 +682,33 @@ def test_oracle_parallel_taa_equals_the_serial_loops():
     a.close(); b.close()
 
 
-def test_reference_obj_assets_parse_to_their_triangle_counts():
-    """MeshLoader.cs:23-55 on the reference's own assets (CPU container only: /root/reference does not travel): cow.obj has
-    n-gons that fan out to 5 804 triangles, teapot.obj 6 320, the bunny 69 451 = the committed fixture, vertex for vertex."""
-    assets = Path("/root/reference/ConsoleGame/assets")
-    if not assets.is_dir():
-        pytest.skip("reference assets not present (GPU box)")
-    for name, n_tri in (("cow.obj", 5804), ("teapot.obj", 6320)):
-        pos, faces = mesh_loader.load_obj(assets / name)
+def write_obj(path, pos, faces):
+    """OBJ text as the reference's assets are laid out: comment header, blank line, `v x y z` (9 significant digits: the float32 parse
+    comes back bit for bit), `f a b c` with 1-based indices"""
+    with open(path, "w") as f:
+        f.write("####\n#\n# OBJ File\n#\n####\n\n")
+        f.writelines("v %.9g %.9g %.9g\n" % tuple(float(c) for c in p) for p in pos)
+        f.writelines("f %d %d %d\n" % tuple(int(i) + 1 for i in t) for t in faces)
+
+
+def test_reference_obj_assets_parse_to_their_triangle_counts(tmp_path):
+    """MeshLoader.cs:23-55 on the reference's own assets, as OBJ text written from their parsed arrays (tests/golden/obj_meshes.npz and the
+    bunny fixture, tests/golden/make_fixtures.py): cow.obj fans out to 5 804 triangles, teapot.obj 6 320, the bunny 69 451 = the committed
+    fixture, vertex for vertex."""
+    z = np.load(Path(__file__).resolve().parent / "golden" / "obj_meshes.npz")
+    for name, n_tri in (("cow", 5804), ("teapot", 6320)):
+        write_obj(tmp_path / f"{name}.obj", z[f"{name}_positions"], z[f"{name}_faces"])
+        pos, faces = mesh_loader.load_obj(tmp_path / f"{name}.obj")
         assert faces.shape == (n_tri, 3), (name, faces.shape)
         assert faces.min() >= 0 and faces.max() < len(pos)
+        assert np.array_equal(pos, z[f"{name}_positions"]) and np.array_equal(faces, z[f"{name}_faces"])
         tris = mesh_loader.from_obj_arrays(pos, faces)
         ext = tris.reshape(-1, 3).max(0) - tris.reshape(-1, 3).min(0)
         assert abs(float(ext.max()) - 1.0) < 1e-5                       # normalize: max extent = targetSize
-    pos, faces = mesh_loader.load_obj(assets / "stanford-bunny.obj")
     fpos, ffaces = scenes.load_bunny_arrays()
+    write_obj(tmp_path / "stanford-bunny.obj", fpos, ffaces)
+    pos, faces = mesh_loader.load_obj(tmp_path / "stanford-bunny.obj")
+    assert faces.shape == (69451, 3)
     assert np.array_equal(pos, fpos) and np.array_equal(faces, ffaces)
 
 
