@@ -34,6 +34,10 @@ public sealed class HipRaytraceOptions
 
 public partial class RaytraceEntity
 {
+    /// <summary>Scene.Hit / Scene.Occluded on the GPU's copy of the active scene when the renderer is a HipRaytraceWrapper, else null
+    /// (the host then keeps calling Scene.Hit).  INTEGRATION.md section 6.</summary>
+    internal HipSceneQuery SceneQueries => (renderer as HipRaytraceWrapper)?.SceneQueries;
+
     private sealed unsafe class HipRaytraceWrapper : IConsoleRenderer, IDisposable
     {
         private IntPtr ctx;
@@ -153,6 +157,12 @@ public partial class RaytraceEntity
                 if (frame != IntPtr.Zero) Ycge.Check(ctx, Ycge.ycge_scene_update_texture(ctx, i, frame, (UIntPtr)((ulong)t.width * (ulong)t.height * (ulong)bpp)));
             }
         }
+
+        /// <summary>The native context, for the scene queries (HipSceneQuery): they answer against the scene as the last SyncScene left it.</summary>
+        internal IntPtr NativeContext => ctx;
+        private HipSceneQuery queries;
+        /// <summary>Scene.Hit / Scene.Occluded on the device scene of this wrapper (VolumeScene's camera physics; INTEGRATION.md section 6).</summary>
+        internal HipSceneQuery SceneQueries => queries ??= new HipSceneQuery(() => ctx);
 
         /// <summary>Forces the next frame to upload the scene again (for a host that edits a scene in ways the signature cannot see).</summary>
         public void Invalidate() { forceUpload = true; }

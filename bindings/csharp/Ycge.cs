@@ -174,7 +174,7 @@ namespace ConsoleGame.RayTracing.Native
 
     internal static unsafe class Ycge
     {
-        public const int AbiVersion = 9;
+        public const int AbiVersion = 10;
         public const int MaxDevices = 8;
         private const string Lib = "ycge_hip";       // libycge_hip.so
 
@@ -207,6 +207,9 @@ namespace ConsoleGame.RayTracing.Native
         [DllImport(Lib)] public static extern int ycge_resolve_tiles_resident(IntPtr ctx, IntPtr dHaloRecv, IntPtr dHistorySlab, IntPtr stream, YFrameStats* stats);
         [DllImport(Lib)] public static extern int ycge_unpack_history(IntPtr ctx, IntPtr dAllHistorySlabs, IntPtr stream);
         // tests / tools
+        // scene queries (ABI 10): Scene.Hit / Scene.Occluded for a batch of rays, beside a frame in flight (HipSceneQuery.cs)
+        [DllImport(Lib)] public static extern int ycge_scene_hit(IntPtr ctx, float[] rays, int n, float[] hits, int[] ids);
+        [DllImport(Lib)] public static extern int ycge_scene_occluded(IntPtr ctx, float[] rays, int n, byte[] occluded);
         [DllImport(Lib)] public static extern int ycge_read_buffer(IntPtr ctx, int which, IntPtr dst, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_set_frame_counter(IntPtr ctx, long frameCounter);
         [DllImport(Lib)] public static extern int ycge_read_timed_steps(IntPtr ctx, out ulong laneSteps);

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YCGE_ABI_VERSION 9
+#define YCGE_ABI_VERSION 10
 #define YCGE_MAX_DEVICES 8
 
 typedef enum ycge_status {
@@ -361,7 +361,8 @@ int ycge_render_frame(ycge_ctx *ctx, float *out_top_bottom_sdr, ycge_frame_stats
  * of stage queues) - so a sequence of such calls costs max(trace, TAA + schedule) per frame or less, instead of their sum plus the
  * host's wake-up.  The frames are the ones the same sequence of ycge_render_frame(ctx, NULL, NULL)
  * calls produces, bit for bit.  Single device, no debug captures, no per-frame counters.  Every other entry point (and
- * ycge_wait) first waits for the frames in flight; ycge_set_camera between two calls moves the camera of the next frame. */
+ * ycge_wait) first waits for the frames in flight - except the scene queries ycge_scene_hit / ycge_scene_occluded, which run beside
+ * them; ycge_set_camera between two calls moves the camera of the next frame. */
 int ycge_render_frame_async(ycge_ctx *ctx);
 /* ... with steps 6-8 (denoise, exposure, tonemap + downsample) and the read-back: out_top_bottom_sdr (as for ycge_render_frame) is
  * filled when the frame is complete - after ycge_wait or any other call - so a caller that queues several such frames passes one
@@ -436,6 +437,24 @@ int ycge_unpack_history(ycge_ctx *ctx, const void *d_all_history_slabs, void *hi
  * width * height * frame_bytes_per_pixel of texture `texture_index` of the last ycge_scene_upload.  The host sets
  * ycge_scene.has_dynamic_textures for such scenes (Scene.cs:30), which restarts the TAA history every frame. */
 int ycge_scene_update_texture(ycge_ctx *ctx, int32_t texture_index, const uint8_t *frame, size_t bytes);
+
+/* --- scene queries (ABI 10): the other caller of Scene.Hit in the reference, VolumeScene's camera physics (ground fan, collision
+ * capsule, push-out: Scenes/VolumeScenes.cs), against the scene of the last successful ycge_scene_upload / ycge_scene_update_objects.
+ * A query runs on a stream of its own: it waits for the device work of the last scene change and NOT for frames in flight (a query
+ * between two ycge_render_frame_async calls leaves them in flight), and it changes nothing a frame reads - frame counter, TAA and exposure
+ * state, trace outputs, schedule, timing and statistics.  It returns with the results in the caller's arrays.
+ * Refused with YCGE_ERR_INVALID_ARG (ycge_last_error names the first bad ray; the output arrays are then unspecified): n < 0, a NULL
+ * array when n > 0, a peer context of the one-process multi-device form, a ray with a NaN or inf in its origin, direction or tmin or a NaN
+ * tmax, a ray whose binary32 dx*dx + dy*dy + dz*dz is not finite and > 0.  tmax = +inf, tmax = FLT_MAX and tmin > tmax (a miss) are
+ * accepted.  YCGE_ERR_NO_SCENE before the first upload.  n = 0 with a scene: YCGE_OK. */
+/* Scene.Hit (Scene.cs:71-75) for n rays against the scene of the last successful upload / update_objects.
+ * rays: n x 8 f32 {ox, oy, oz, dx, dy, dz, tmin, tmax}; the direction is normalised as new Ray(o, d) does (Ray.cs:8-12,
+ * Vec3.Normalized) and t is in units of the normalised direction.  Queries behave as screenU = screenV = 0.
+ * hits: n x 10 f32 {t, p xyz, n xyz, albedo rgb} (HitRecord.T/P/N and Mat.Albedo as the hit leaves them - no texture sampling);
+ * ids:  n x 2 i32 {Scene.Objects index, sub} with sub as YCGE_BUF_SUB_ID defines it; a miss is {-1, -1} and ten zeros. */
+int ycge_scene_hit(ycge_ctx *ctx, const float *rays, int32_t n, float *hits, int32_t *ids);
+/* Scene.Occluded / the boolean of Scene.Hit: occluded[i] = 1 when Scene.Hit(ray i, tmin, tmax) would return true, else 0. */
+int ycge_scene_occluded(ycge_ctx *ctx, const float *rays, int32_t n, uint8_t *occluded);
 
 /* tests only */
 int ycge_read_buffer(ycge_ctx *ctx, int32_t which /* ycge_buffer */, void *dst, size_t bytes);

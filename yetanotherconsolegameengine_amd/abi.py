@@ -12,7 +12,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-YCGE_ABI_VERSION = 9
+YCGE_ABI_VERSION = 10
 YCGE_MAX_DEVICES = 8
 
 # ycge_status
@@ -207,6 +207,8 @@ _PROTOTYPES = {
     "ycge_trace_tiles_resident_batch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.c_void_p]),
     "ycge_resolve_tiles_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]),
     "ycge_unpack_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ycge_scene_hit": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "ycge_scene_occluded": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_uint8)]),
     "ycge_read_buffer": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_set_frame_counter": (C.c_int, [C.c_void_p, C.c_int64]),
     "ycge_read_timed_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

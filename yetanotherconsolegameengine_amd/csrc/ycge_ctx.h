@@ -81,6 +81,9 @@ int ycge_launch_pack_slab(const ycge::FrameParams *P, const float *hdr, const fl
 int ycge_launch_push_tiles(const ycge::FrameParams *P, const ycge::PushPlanes *planes, hipStream_t stream);
 int ycge_launch_unpermute(const float *all_slabs, size_t slab_floats_per_rank, int hiW, int hiH, int tiles_x, int n_tiles, int world_size,
                           int slab_floats, float *hdr, float *albedo, float *normal, float *depth, uint8_t *sky, hipStream_t stream);
+uint32_t ycge_launch_query_lanes(int has_grid, int occluded, int compute_units);
+int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
+                      void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
 }
 
 using namespace ycge;
@@ -244,6 +247,8 @@ struct MeshHost {
 
 } // namespace ycge_host
 using namespace ycge_host;
+
+struct QueryState;          // ycge_query.cpp
 
 struct ycge_ctx {
     ycge_config cfg;
@@ -463,6 +468,10 @@ struct ycge_ctx {
     int64_t bvh_device_builds = 0, bvh_host_fallbacks = 0, bvh_host_builds = 0;
     double bvh_last_build_us = 0.0;
     std::vector<MeshHost> meshes;
+    // scene queries (ycge_scene_hit / ycge_scene_occluded, ycge_query.cpp): a stream and buffers of their own, made by the first query;
+    // scene_ev marks the device work of the last scene change on `stream` - a query waits for it and for nothing a frame queued after it
+    struct QueryState *query = nullptr;
+    hipEvent_t scene_ev = nullptr;
 
     int fail(int code, const char *fmt, ...)
     {
@@ -526,5 +535,7 @@ bool frame_is_single_launch(const ycge_ctx *c);
 bool should_reset_history(const ycge_ctx *c, const float pos[3], float yaw, float pitch);
 void fill_frame_params(ycge_ctx *c, ycge::FrameParams &P, int64_t frame, const float pos[3], float yaw, float pitch, float fov_deg);
 int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, bool timed, hipEvent_t launch_begin = nullptr, hipEvent_t launch_end = nullptr, const ResidentTarget *rt = nullptr);
+int query_scene_changed(ycge_ctx *c);       // ycge_query.cpp: record scene_ev behind a scene upload / objects update
+void release_query(ycge_ctx *c);             // ycge_query.cpp: drain the query stream, then free what the queries hold
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
 } // namespace ycge_host

@@ -532,6 +532,7 @@ try {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->taa_stream) (void)hipStreamSynchronize(c->taa_stream);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+    release_query(c);          // (drains the query stream first)
     c->current_hdr.release(); c->g_albedo.release(); c->g_normal.release(); c->g_depth.release(); c->taa_hist.release();
     c->prev_normal.release(); c->prev_depth.release(); c->sky.release(); c->prev_sky.release();
     c->dbg_rays.release(); c->dbg_hit_t.release(); c->dbg_prim.release(); c->dbg_sub.release(); c->dbg_rng.release();
@@ -1287,6 +1288,7 @@ try {
         if (rc != YCGE_OK) c->err = p->err;
     }
     (void)hipSetDevice(c->device);
+    if (rc == YCGE_OK) rc = query_scene_changed(c);
     return rc;
 }
 catch (...) { return ycge_host::abi_catch(c); }
@@ -1414,7 +1416,7 @@ try {
     (void)hipSetDevice(c->device);
     if (rc != YCGE_OK) return rc;
     c->have_scene = true;
-    return YCGE_OK;
+    return query_scene_changed(c);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

@@ -122,6 +122,39 @@ class RaytraceRenderer:
         self._check(self.L.ycge_scene_update_objects(self.ctx, C.cast(f.prims, C.POINTER(abi.Prim)), f.struct.n_prims))
         self.flat = f
 
+    # ---------------------------------------------------------------- scene queries (ycge_scene_hit / ycge_scene_occluded)
+    @staticmethod
+    def _query_rays(origins, dirs, t_min, t_max) -> np.ndarray:
+        """n x 8 f32 {o, d, tmin, tmax}; t_min / t_max may be scalars (broadcast) or length-n arrays."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"origins {o.shape} and dirs {d.shape} differ")
+        rays = np.empty((o.shape[0], 8), dtype=np.float32)
+        rays[:, 0:3], rays[:, 3:6] = o, d
+        rays[:, 6] = np.broadcast_to(np.asarray(t_min, dtype=np.float32), (o.shape[0],))
+        rays[:, 7] = np.broadcast_to(np.asarray(t_max, dtype=np.float32), (o.shape[0],))
+        return rays
+
+    def Hit(self, origins, dirs, t_min=0.001, t_max=np.float32(3.4028234663852886e38)):
+        """Scene.Hit (Scene.cs:71-75) for n rays against the uploaded scene: (hits[n, 10] f32 {t, p xyz, n xyz, albedo rgb},
+        ids[n, 2] i32 {Scene.Objects index, sub}); a miss is ids (-1, -1) and a zero record.  Runs beside frames in flight."""
+        rays = self._query_rays(origins, dirs, t_min, t_max)
+        n = rays.shape[0]
+        hits = np.zeros((n, 10), dtype=np.float32)
+        ids = np.zeros((n, 2), dtype=np.int32)
+        self._check(self.L.ycge_scene_hit(self.ctx, rays.ctypes.data_as(C.POINTER(C.c_float)), n,
+                                          hits.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(C.POINTER(C.c_int32))))
+        return hits, ids
+
+    def Occluded(self, origins, dirs, t_min=0.001, t_max=np.float32(3.4028234663852886e38)) -> np.ndarray:
+        """Scene.Occluded / the boolean of Scene.Hit for n rays: bool[n]."""
+        rays = self._query_rays(origins, dirs, t_min, t_max)
+        n = rays.shape[0]
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self.L.ycge_scene_occluded(self.ctx, rays.ctypes.data_as(C.POINTER(C.c_float)), n, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out.astype(bool)
+
     def scene_bvh_stats(self) -> dict:
         """How ycge_scene_update_objects built the scene BVH so far: on the device (csrc/ycge_bvh_build.hip), on the host after the
         kernel declined, on the host outright; microseconds of the last build + install; how often the current tree took the
