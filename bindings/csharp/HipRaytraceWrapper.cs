@@ -17,6 +17,11 @@
 //   Exchange   - how their tiles come together on Devices[0]: YExchange.PeerPush (xGMI peer writes) or YExchange.Rccl (ONE ncclAllGather of
 //                the tile slabs inside ycge_render_frame - SURVEY 8(e); the library dlopens librccl.so and falls back to PeerPush without it;
 //                ExchangeInUse says which).
+//   DeviceChexelColors - the nearest-of-16 palette search of ChexelColor(Vec3) (Chexel.cs:70-89) runs on the GPU beside the tonemap
+//                (ycge_render_frame_chexels / ycge_render_frame_async_chexels with FrameLate): the frame reads back the SDR array and one
+//                byte a chexel {color_16 of top | of bottom << 4}, and the blit builds each ChexelColor from its byte and its Vec3 - every
+//                field equals the reference's, the host no longer searches.  Needs a library that exports the two calls (INTEGRATION.md
+//                section 7).
 using System;
 using System.Runtime.CompilerServices;
 using ConsoleGame.RayTracing;
@@ -30,6 +35,7 @@ public sealed class HipRaytraceOptions
     public bool FrameLate;
     public int[] Devices;
     public YExchange Exchange = YExchange.PeerPush;
+    public bool DeviceChexelColors;
 }
 
 public partial class RaytraceEntity
@@ -48,6 +54,8 @@ public partial class RaytraceEntity
         private float* sdr;                         // fbW * fbH * {top rgb, bottom rgb}: page-locked memory of the library (ycge_alloc_host_buffer)
         private float* sdrLate;                     // FrameLate: the second array - the frame in flight fills one while the host blits the other
         private readonly bool frameLate;
+        private readonly bool deviceColors;         // DeviceChexelColors: color16 / color16Late hold {color_16 of top | of bottom << 4} per chexel
+        private byte* color16, color16Late;         // (page-locked memory of the library, one per SDR array)
         private bool inFlight;                      // FrameLate: a frame queued by the last TryFlipAndBlit has not been waited for yet
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
         private ulong objectsSignature;
@@ -69,6 +77,7 @@ public partial class RaytraceEntity
                 cfg.MultiDeviceExchange = (int)options.Exchange;
             }
             frameLate = options != null && options.FrameLate && cfg.NDevices <= 1;      // (frames in flight are the single-device form)
+            deviceColors = options != null && options.DeviceChexelColors;
             Ycge.Check(IntPtr.Zero, Ycge.ycge_create(ref cfg, out ctx));
             AllocSdr();
             Upload();                               // the reference ctor ends with scene.RebuildBVH() (RaytraceRenderer.cs:107)
@@ -82,10 +91,23 @@ public partial class RaytraceEntity
             if (sdr != null || sdrLate != null) { Ycge.ycge_wait(ctx); inFlight = false; }
             if (sdr != null) { Ycge.ycge_free_host_buffer((IntPtr)sdr); sdr = null; }
             if (sdrLate != null) { Ycge.ycge_free_host_buffer((IntPtr)sdrLate); sdrLate = null; }
+            FreeColor16();
             UIntPtr bytes = (UIntPtr)((ulong)fbW * (ulong)fbH * 6 * sizeof(float));
             Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(bytes, out IntPtr p));
             sdr = (float*)p;
             if (frameLate) { Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(bytes, out IntPtr q)); sdrLate = (float*)q; }
+            if (deviceColors)
+            {
+                UIntPtr cbytes = (UIntPtr)((ulong)fbW * (ulong)fbH);
+                Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(cbytes, out IntPtr c)); color16 = (byte*)c;
+                if (frameLate) { Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(cbytes, out IntPtr d)); color16Late = (byte*)d; }
+            }
+        }
+
+        private void FreeColor16()
+        {
+            if (color16 != null) { Ycge.ycge_free_host_buffer((IntPtr)color16); color16 = null; }
+            if (color16Late != null) { Ycge.ycge_free_host_buffer((IntPtr)color16Late); color16Late = null; }
         }
 
         // ---- scene: full upload, and what changes between frames (Scene.Update: entities move objects, DayNightCycle.cs:80-89 moves lights and sky)
@@ -191,16 +213,36 @@ public partial class RaytraceEntity
                 // the frame queued by the LAST call is finished first (it ran beside the host's Update in between), then this call's frame is queued
                 // into the other array and the finished one is blitted: one frame late, never torn (the device writes `sdrLate`, the host reads `sdr`)
                 bool have = inFlight;
-                if (inFlight) { Ycge.Check(ctx, Ycge.ycge_wait(ctx)); inFlight = false; float* t = sdr; sdr = sdrLate; sdrLate = t; }
+                if (inFlight)
+                {
+                    Ycge.Check(ctx, Ycge.ycge_wait(ctx)); inFlight = false;
+                    float* t = sdr; sdr = sdrLate; sdrLate = t;
+                    byte* u = color16; color16 = color16Late; color16Late = u;
+                }
                 SyncScene();
-                Ycge.Check(ctx, Ycge.ycge_render_frame_async_sdr(ctx, sdrLate));
+                if (deviceColors) Ycge.Check(ctx, Ycge.ycge_render_frame_async_chexels(ctx, sdrLate, color16Late, null, null));
+                else Ycge.Check(ctx, Ycge.ycge_render_frame_async_sdr(ctx, sdrLate));
                 inFlight = true;
                 if (!have) return;                                             // (the very first call has nothing to show yet: the framebuffer keeps what it had)
             }
             else
             {
                 SyncScene();
-                Ycge.Check(ctx, Ycge.ycge_render_frame(ctx, sdr, null));
+                if (deviceColors) Ycge.Check(ctx, Ycge.ycge_render_frame_chexels(ctx, sdr, color16, null, null, null));
+                else Ycge.Check(ctx, Ycge.ycge_render_frame(ctx, sdr, null));
+            }
+            if (deviceColors)
+            {
+                // the 3-argument ChexelColor applies the same Clamp01 (Chexel.cs:49-53): only the palette search has left the host
+                for (int cy = 0; cy < fbH; cy++)
+                    for (int cx = 0; cx < fbW; cx++)
+                    {
+                        float* c = sdr + ((long)cx + (long)cy * fbW) * 6;
+                        byte b = color16[(long)cx + (long)cy * fbW];
+                        fb.SetChexel(cx, cy, new Chexel('▀', new ChexelColor((ConsoleColor)(b & 15), new Vec3(c[0], c[1], c[2])),
+                                                             new ChexelColor((ConsoleColor)(b >> 4), new Vec3(c[3], c[4], c[5]))));
+                    }
+                return;
             }
             for (int cy = 0; cy < fbH; cy++)
                 for (int cx = 0; cx < fbW; cx++)
@@ -215,6 +257,7 @@ public partial class RaytraceEntity
             if (ctx != IntPtr.Zero) { Ycge.ycge_destroy(ctx); ctx = IntPtr.Zero; }      // (waits for everything in flight)
             if (sdr != null) { Ycge.ycge_free_host_buffer((IntPtr)sdr); sdr = null; }
             if (sdrLate != null) { Ycge.ycge_free_host_buffer((IntPtr)sdrLate); sdrLate = null; }
+            FreeColor16();
             uploaded?.Dispose();
         }
     }

@@ -192,6 +192,9 @@ namespace ConsoleGame.RayTracing.Native
         [DllImport(Lib)] public static extern int ycge_render_frame(IntPtr ctx, float* outTopBottomSdr, YFrameStats* stats);
         [DllImport(Lib)] public static extern int ycge_render_frame_async(IntPtr ctx);
         [DllImport(Lib)] public static extern int ycge_render_frame_async_sdr(IntPtr ctx, float* outTopBottomSdr);
+        // device chexel colours (after ABI 10, found by symbol lookup - AbiVersion is unchanged): the presenters' bytes beside the SDR frame
+        [DllImport(Lib)] public static extern int ycge_render_frame_chexels(IntPtr ctx, float* outTopBottomSdr, byte* outColor16, byte* outAnsi, byte* outRgba, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_render_frame_async_chexels(IntPtr ctx, float* outTopBottomSdr, byte* outColor16, byte* outAnsi, byte* outRgba);
         [DllImport(Lib)] public static extern int ycge_wait(IntPtr ctx);
         [DllImport(Lib)] public static extern int ycge_async_trace_times(IntPtr ctx, float* msOut, int capacity, out int nOut);
         [DllImport(Lib)] public static extern int ycge_flight_query(IntPtr ctx, out YFlightInfo info);

@@ -369,6 +369,24 @@ int ycge_render_frame_async(ycge_ctx *ctx);
  * buffer per frame in flight (page-locked, ycge_pin_host_buffer, or the copy blocks the calling thread).  The post stage of frame N
  * runs beside the traces and TAA of the frames after it; same pixels as ycge_render_frame(ctx, out, NULL) in the same order. */
 int ycge_render_frame_async_sdr(ycge_ctx *ctx, float *out_top_bottom_sdr);
+/* --- device chexel colours: the presenters' colour maps computed beside the tonemap, so that a host reads back the bytes it presents
+ * instead of 24 bytes of f32 a chexel and maps them itself.  Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10 and
+ * ycge_config is unchanged - a host detects these two exports by symbol lookup.  Per chexel (index cx + cy * fbW), from the SDR
+ * {top rgb, bottom rgb} that ycge_render_frame writes, exactly as the reference maps it:
+ *   out_color16  fbW * fbH bytes: color_16 of top | color_16 of bottom << 4 - ChexelColor(Vec3) (Renderer/Chexel.cs:37-41, 70-99),
+ *                the low byte of Win32's MapAttributes(fg = top, bg = bottom)
+ *   out_ansi     fbW * fbH * 2 bytes {top, bottom}: ChexelToAnsi256 (Renderer/ANSITerminalRenderer.cs:246-306)
+ *   out_rgba     fbW * 2 fbH RGBA8 (alpha 255), row 2 cy the top half-cell, row 2 cy + 1 the bottom one: OpenGLTerminalRenderer's
+ *                compose image (:114-145, LinearToSrgb8 :390-400) for a framebuffer that fills the window
+ * Any subset of the four destinations (out_top_bottom_sdr as for ycge_render_frame) may be NULL, not all of them.
+ * The synchronous call is ycge_render_frame with the post stage run whatever the destinations: the same SDR, bit for bit, and the same
+ * frame state (counter, TAA history, exposure) as ycge_render_frame(ctx, sdr, stats) in its place; the one-process multi-device forms
+ * included.  Refused: all destinations NULL, a peer context, the RCCL exchange with lean slabs (config.slab_albedo = 0).
+ * The frames-in-flight call mirrors ycge_render_frame_async_sdr; every destination must be page-locked memory.  No destination of
+ * a refused or failed call is written later. */
+int ycge_render_frame_chexels(ycge_ctx *ctx, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba,
+                              ycge_frame_stats *stats);
+int ycge_render_frame_async_chexels(ycge_ctx *ctx, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba);
 int ycge_wait(ycge_ctx *ctx);
 /* measurement: durations (ms) of the trace launches of the frames queued since the last call, oldest first (at most the last 1024);
  * waits for the frames in flight */

@@ -39,6 +39,12 @@ int ycge_host_band_window_width(int32_t w, int32_t h, int32_t step, int32_t rows
 int ycge_host_halo_layout(int32_t hiW, int32_t hiH, int32_t rank, int32_t world, int64_t *send_counts, int64_t *recv_counts,
                           uint32_t *send_px, uint32_t *recv_px, int64_t capacity);
 
+/* ---- device chexel colours (csrc/ycge_chexel.cpp): LinearToSrgb8's thresholds as the library computed them with the C library's pow -
+ * entry k - 1 the smallest binary32 / binary64 whose byte is >= k (255 each; host only) - and the encode kernel on caller-given SDR
+ * values (w x h chexels of {top rgb, bottom rgb}; NULL outputs are skipped; layouts as ycge_render_frame_chexels) */
+int ycge_host_srgb_thresholds(float *f32_out, double *f64_out);
+int ycge_test_encode_chexels(ycge_ctx *c, const float *sdr, int32_t w, int32_t h, uint8_t *c16, uint8_t *ansi, uint8_t *rgba);
+
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */
 int ycge_debug_device_bvh(const float *bounds, const float *centroids, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *result_out, void *build_out);   /* k_scene_bvh_build alone */

@@ -1,0 +1,277 @@
+// ycge_chexel.cpp - the presenters' colour maps on the device (ycge_render_frame_chexels, ycge_render_frame_async_chexels; kernel:
+// ycge_chexel.hip).
+//
+// A frame of these calls is ycge_render_frame's (or ycge_render_frame_async_sdr's) with the post stage, plus one launch behind the tonemap
+// on the same stream that turns the SDR array into the bytes the caller asked for, and their read-back.  The request lives in the
+// context for the length of one call only (a scope guard clears it, and on an error return every staged destination too): run_post
+// sees no request from any other entry point, so those issue no extra launch, copy or event.
+//
+// LinearToSrgb8 (ANSITerminalRenderer.cs:287-296 = OpenGLTerminalRenderer.cs:390-400) is a monotone step function of its input: the
+// host finds its 255 steps ONCE with the C library's double pow - the function Math.Pow calls - and the kernel counts thresholds.
+// One table for binary32 inputs (the channels), one for binary64 (the luminance, a genuine double).
+#include "ycge_ctx.h"
+
+#include <cmath>
+
+namespace {
+
+// LinearToSrgb8 as the reference writes it: clamp, the sRGB curve in double, Math.Round (half to even: nearbyint in the default
+// rounding mode), the int clamp (NaN: (int)NaN is int.MinValue before .NET 9 and 0 from it - both clamp to 0)
+int linear_to_srgb8(double c)
+{
+    if (c < 0.0) c = 0.0;
+    if (c > 1.0) c = 1.0;
+    const double s = c <= 0.0031308 ? 12.92 * c : 1.055 * std::pow(c, 1.0 / 2.4) - 0.055;
+    const double r = std::nearbyint(s * 255.0);
+    if (!(r >= 0.0)) return 0;
+    return r > 255.0 ? 255 : (int)r;
+}
+
+// the thresholds: entry k - 1 is the smallest non-negative value of the type whose byte is >= k (binary search over the bit patterns,
+// which order non-negative floats); entry 255 is a NaN nobody compares with
+struct SrgbTables {
+    float t32[256];
+    double t64[256];
+    SrgbTables()
+    {
+        for (int k = 1; k <= 255; k++) {
+            uint32_t lo = 0, hi = 0x3f800000u;                 // byte(1.0f) = 255 >= k
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                float x; std::memcpy(&x, &mid, 4);
+                if (linear_to_srgb8((double)x) >= k) hi = mid; else lo = mid + 1;
+            }
+            std::memcpy(&t32[k - 1], &lo, 4);
+            uint64_t lo8 = 0, hi8 = 0x3ff0000000000000ull;
+            while (lo8 < hi8) {
+                const uint64_t mid = lo8 + (hi8 - lo8) / 2;
+                double x; std::memcpy(&x, &mid, 8);
+                if (linear_to_srgb8(x) >= k) hi8 = mid; else lo8 = mid + 1;
+            }
+            std::memcpy(&t64[k - 1], &lo8, 8);
+        }
+        t32[255] = std::nanf("");
+        t64[255] = std::nan("");
+    }
+};
+
+const SrgbTables &srgb_tables()
+{
+    static const SrgbTables t;            // (thread-safe initialisation; no heap)
+    return t;
+}
+
+// offsets of the three outputs in one device buffer of n chexels (aligned for the kernel's 2- and 4-byte stores)
+struct ChexelLayout {
+    size_t n, c16, ansi, rgba, total;
+    explicit ChexelLayout(size_t n_) : n(n_)
+    {
+        c16 = 0;
+        ansi = (n + 255) & ~(size_t)255;
+        rgba = ansi + ((2 * n + 255) & ~(size_t)255);
+        total = rgba + 8 * n;
+    }
+};
+
+} // namespace
+
+// what the chexel calls of one context hold: made by the first call, freed by ycge_destroy (release_chexels)
+struct ChexelState {
+    bool on = false;                                   // a _chexels call is in progress
+    uint8_t *dst[3] = {nullptr, nullptr, nullptr};     // its destinations: c16, ansi, rgba
+    DevBuf<uint8_t> tables;                            // 256 f32 + 256 f64 thresholds
+    DevBuf<uint8_t> out[2];                            // the encoded bytes, per post parity (as d_sdr / d_sdr2)
+    void *stage = nullptr; size_t stage_bytes = 0;     // page-locked staging of pageable destinations (synchronous call only)
+    uint8_t *staged_dst[3] = {nullptr, nullptr, nullptr};
+    size_t staged_off[3] = {0, 0, 0}, staged_bytes[3] = {0, 0, 0};
+    void drop_staged() { for (int k = 0; k < 3; k++) { staged_dst[k] = nullptr; staged_bytes[k] = 0; } }
+};
+
+namespace ycge_host {
+
+static int ensure_tables(ycge_ctx *c, ChexelState &X)
+{
+    if (X.tables.p) return YCGE_OK;
+    const SrgbTables &t = srgb_tables();
+    uint8_t host[3072];
+    std::memcpy(host, t.t32, 1024);
+    std::memcpy(host + 1024, t.t64, 2048);
+    HIP_TRY(c, X.tables.alloc(sizeof host));
+    const hipError_t e = hipMemcpy(X.tables.p, host, sizeof host, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { X.tables.release(); HIP_TRY(c, e); }
+    return YCGE_OK;
+}
+
+int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second)
+{
+    ChexelState *X = c->chexels;
+    if (!X || !X->on || (!X->dst[0] && !X->dst[1] && !X->dst[2])) return YCGE_OK;        // (the SDR alone: nothing to encode)
+    const ChexelLayout L((size_t)c->fbW * c->fbH);
+    DevBuf<uint8_t> &out = X->out[second ? 1 : 0];
+    if (out.cap < L.total) HIP_TRY(c, out.alloc(L.total));
+    if (X->dst[1] || X->dst[2]) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
+    const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, X->dst[0] ? out.p + L.c16 : nullptr, X->dst[1] ? out.p + L.ansi : nullptr,
+                                      X->dst[2] ? out.p + L.rgba : nullptr, c->compute_units, stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed: %s", hipGetErrorString((hipError_t)e));
+    return YCGE_OK;
+}
+
+int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second)
+{
+    ChexelState *X = c->chexels;
+    if (!X || !X->on) return YCGE_OK;
+    const ChexelLayout L((size_t)c->fbW * c->fbH);
+    const size_t off[3] = {L.c16, L.ansi, L.rgba}, bytes[3] = {L.n, 2 * L.n, 8 * L.n};
+    const uint8_t *src = X->out[second ? 1 : 0].p;
+    size_t staged = 0;
+    for (int k = 0; k < 3; k++)
+        if (X->dst[k] && !host_memory_is_page_locked(X->dst[k], bytes[k])) staged = off[k] + bytes[k];
+    if (staged > X->stage_bytes) {
+        if (X->stage) { (void)hipHostFree(X->stage); X->stage = nullptr; X->stage_bytes = 0; }
+        HIP_TRY(c, hipHostMalloc(&X->stage, staged, hipHostMallocDefault));
+        X->stage_bytes = staged;
+    }
+    for (int k = 0; k < 3; k++) {
+        if (!X->dst[k]) continue;
+        uint8_t *target = X->dst[k];
+        if (!host_memory_is_page_locked(X->dst[k], bytes[k])) {        // (synchronous calls only: the frames in flight refuse pageable arrays up front)
+            target = (uint8_t *)X->stage + off[k];
+            X->staged_dst[k] = X->dst[k]; X->staged_off[k] = off[k]; X->staged_bytes[k] = bytes[k];
+        }
+        HIP_TRY(c, hipMemcpyAsync(target, src + off[k], bytes[k], hipMemcpyDeviceToHost, stream));
+    }
+    return YCGE_OK;
+}
+
+void release_chexels(ycge_ctx *c, bool all)
+{
+    ChexelState *X = c->chexels;
+    if (!X) return;
+    X->out[0].release(); X->out[1].release();
+    if (!all) return;
+    X->tables.release();
+    if (X->stage) (void)hipHostFree(X->stage);
+    delete X;
+    c->chexels = nullptr;
+}
+
+} // namespace ycge_host
+
+namespace {
+
+// one _chexels call: sets the request, and clears it on every way out - on an error return also every latched destination (the SDR
+// staging included), so no later call writes into an array of this one
+struct ChexelCall {
+    ycge_ctx *c;
+    bool ok = false;
+    ChexelCall(ycge_ctx *c_, uint8_t *c16, uint8_t *ansi, uint8_t *rgba) : c(c_)
+    {
+        if (!c->chexels) c->chexels = new ChexelState();
+        ChexelState &X = *c->chexels;
+        X.on = true; X.dst[0] = c16; X.dst[1] = ansi; X.dst[2] = rgba;
+        X.drop_staged();
+    }
+    ~ChexelCall()
+    {
+        if (ChexelState *X = c->chexels) {
+            X->on = false; X->dst[0] = X->dst[1] = X->dst[2] = nullptr;
+            X->drop_staged();
+        }
+        if (!ok) { c->staged_sdr_dst = nullptr; c->staged_sdr_bytes = 0; }
+    }
+    // the synchronous call's pageable destinations, once its stream is done
+    void finish()
+    {
+        ChexelState &X = *c->chexels;
+        for (int k = 0; k < 3; k++)
+            if (X.staged_dst[k]) std::memcpy(X.staged_dst[k], (const uint8_t *)X.stage + X.staged_off[k], X.staged_bytes[k]);
+        ok = true;
+    }
+};
+
+int check_chexel_call(ycge_ctx *c, const char *fn, const float *sdr, const uint8_t *c16, const uint8_t *ansi, const uint8_t *rgba)
+{
+    if (!sdr && !c16 && !ansi && !rgba) return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, color16, ansi, rgba)", fn);
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    // (the exchange of the one-process RCCL form packs lean slabs when slab_albedo = 0: no albedo reaches the denoise stage)
+    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
+        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
+    return YCGE_OK;
+}
+
+} // namespace
+
+// =========================================================================== C-ABI
+extern "C" {
+
+int ycge_render_frame_chexels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba, ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    int rc = check_chexel_call(c, "ycge_render_frame_chexels", out_top_bottom_sdr, out_color16, out_ansi, out_rgba);
+    if (rc != YCGE_OK) return rc;
+    ChexelCall call(c, out_color16, out_ansi, out_rgba);
+    rc = render_frame_sync(c, out_top_bottom_sdr, true, st);
+    if (rc == YCGE_OK) call.finish();
+    return rc;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_render_frame_async_chexels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    int rc = check_chexel_call(c, "ycge_render_frame_async_chexels", out_top_bottom_sdr, out_color16, out_ansi, out_rgba);
+    if (rc != YCGE_OK) return rc;
+    const size_t n = (size_t)c->fbW * c->fbH;
+    const void *dst[4] = {out_top_bottom_sdr, out_color16, out_ansi, out_rgba};
+    const size_t bytes[4] = {n * 6 * sizeof(float), n, 2 * n, 8 * n};
+    const char *names[4] = {"sdr", "color16", "ansi", "rgba"};
+    for (int k = 0; k < 4; k++)
+        if (dst[k] && !host_memory_is_page_locked(dst[k], bytes[k]))
+            return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async_chexels fills its arrays while the caller runs on: %s must be page-locked memory "
+                                                 "(ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)", names[k]);
+    ChexelCall call(c, out_color16, out_ansi, out_rgba);
+    rc = render_frame_in_flight(c, out_top_bottom_sdr, true);
+    if (rc == YCGE_OK) call.ok = true;
+    return rc;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: the two threshold tables of LinearToSrgb8 (255 entries each), host only
+int ycge_host_srgb_thresholds(float *f32_out, double *f64_out)
+try {
+    if (!f32_out || !f64_out) return YCGE_ERR_INVALID_ARG;
+    const SrgbTables &t = srgb_tables();
+    std::memcpy(f32_out, t.t32, 255 * sizeof(float));
+    std::memcpy(f64_out, t.t64, 255 * sizeof(double));
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// test hook: k_encode_chexels on caller-given SDR values (w x h chexels of {top rgb, bottom rgb}); any NULL output is skipped.  On the
+// context's device and stream, with buffers of its own; returns with the bytes in the caller's arrays.
+int ycge_test_encode_chexels(ycge_ctx *c, const float *sdr, int32_t w, int32_t h, uint8_t *c16, uint8_t *ansi, uint8_t *rgba)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!sdr || w <= 0 || h <= 0 || (int64_t)w * h > (int64_t)INT32_MAX / 2 || (!c16 && !ansi && !rgba))
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_encode_chexels: bad arguments (w = %d, h = %d)", w, h);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->chexels) c->chexels = new ChexelState();
+    { const int rc = ensure_tables(c, *c->chexels); if (rc != YCGE_OK) return rc; }
+    const ChexelLayout L((size_t)w * h);
+    struct Bufs { DevBuf<float> in; DevBuf<uint8_t> out; ~Bufs() { in.release(); out.release(); } } B;
+    HIP_TRY(c, B.in.alloc(6 * L.n));
+    HIP_TRY(c, B.out.alloc(L.total));
+    HIP_TRY(c, hipMemcpy(B.in.p, sdr, 6 * L.n * sizeof(float), hipMemcpyHostToDevice));
+    const int e = ycge_launch_chexels(B.in.p, w, h, c->chexels->tables.p, c16 ? B.out.p + L.c16 : nullptr, ansi ? B.out.p + L.ansi : nullptr,
+                                      rgba ? B.out.p + L.rgba : nullptr, c->compute_units, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = YCGE_OK;
+    if (c16) rc = copy_out(c, c16, B.out.p + L.c16, L.n);
+    if (ansi && rc == YCGE_OK) rc = copy_out(c, ansi, B.out.p + L.ansi, 2 * L.n);
+    if (rgba && rc == YCGE_OK) rc = copy_out(c, rgba, B.out.p + L.rgba, 8 * L.n);
+    return rc;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+} // extern "C"

@@ -82,6 +82,7 @@ int ycge_launch_push_tiles(const ycge::FrameParams *P, const ycge::PushPlanes *p
 int ycge_launch_unpermute(const float *all_slabs, size_t slab_floats_per_rank, int hiW, int hiH, int tiles_x, int n_tiles, int world_size,
                           int slab_floats, float *hdr, float *albedo, float *normal, float *depth, uint8_t *sky, hipStream_t stream);
 uint32_t ycge_launch_query_lanes(int has_grid, int occluded, int compute_units);
+int ycge_launch_chexels(const float *sdr, int fbW, int fbH, const uint8_t *tables, uint8_t *c16, uint8_t *ansi, uint8_t *rgba, int compute_units, hipStream_t stream);
 int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
 }
@@ -249,6 +250,7 @@ struct MeshHost {
 using namespace ycge_host;
 
 struct QueryState;          // ycge_query.cpp
+struct ChexelState;         // ycge_chexel.cpp
 
 struct ycge_ctx {
     ycge_config cfg;
@@ -472,6 +474,9 @@ struct ycge_ctx {
     // scene_ev marks the device work of the last scene change on `stream` - a query waits for it and for nothing a frame queued after it
     struct QueryState *query = nullptr;
     hipEvent_t scene_ev = nullptr;
+    // device chexel colours (ycge_render_frame_chexels / _async_chexels, ycge_chexel.cpp): the request of the call at hand, the encoded
+    // buffers per post parity, the threshold tables, the staging of pageable destinations; made by the first such call
+    struct ChexelState *chexels = nullptr;
 
     int fail(int code, const char *fmt, ...)
     {
@@ -537,5 +542,10 @@ void fill_frame_params(ycge_ctx *c, ycge::FrameParams &P, int64_t frame, const f
 int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, bool timed, hipEvent_t launch_begin = nullptr, hipEvent_t launch_end = nullptr, const ResidentTarget *rt = nullptr);
 int query_scene_changed(ycge_ctx *c);       // ycge_query.cpp: record scene_ev behind a scene upload / objects update
 void release_query(ycge_ctx *c);             // ycge_query.cpp: drain the query stream, then free what the queries hold
+int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second);   // ycge_chexel.cpp: run_post's encode behind the tonemap (a no-op unless a _chexels call asked)
+int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second);                      // ... and its copies behind the SDR read-back
+void release_chexels(ycge_ctx *c, bool all);                                             // ycge_chexel.cpp: the device buffers (all: and the rest)
+int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *st);     // ycge_frame.cpp: ycge_render_frame, post stage on request
+int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post);                      // ycge_frame.cpp: ycge_render_frame_async(_sdr)
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
 } // namespace ycge_host

@@ -530,10 +530,9 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
-static int render_frame_in_flight(ycge_ctx *c, float *out_sdr);
 int ycge_render_frame_async(ycge_ctx *c)
 try {
-    return c ? render_frame_in_flight(c, nullptr) : YCGE_ERR_INVALID_ARG;
+    return c ? render_frame_in_flight(c, nullptr, false) : YCGE_ERR_INVALID_ARG;
 }
 catch (...) { return ycge_host::abi_catch(c); }
 // ... with steps 6-8 (denoise, exposure, tonemap + downsample) and the read-back into out_top_bottom_sdr, which is filled when the frame
@@ -544,11 +543,14 @@ int ycge_render_frame_async_sdr(ycge_ctx *c, float *out_top_bottom_sdr)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;
     if (!out_top_bottom_sdr) return c->fail(YCGE_ERR_INVALID_ARG, "null SDR buffer");
-    return render_frame_in_flight(c, out_top_bottom_sdr);
+    return render_frame_in_flight(c, out_top_bottom_sdr, true);
 }
 catch (...) { return ycge_host::abi_catch(c); }
+} // extern "C"
 
-static int render_frame_in_flight(ycge_ctx *c, float *out_sdr)
+namespace ycge_host {
+// post: run steps 6-8 (out_sdr, when not NULL, gets the read-back; the chexel calls may ask for their encoded bytes alone)
+int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
 {
     if (c->parent || !c->peers.empty() || c->cfg.world_size != 1)
         return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async is the single-device form (tiled frames overlap through ycge_trace_tiles / ycge_resolve_gathered on two streams)");
@@ -583,7 +585,7 @@ static int render_frame_in_flight(ycge_ctx *c, float *out_sdr)
     // is the one event it waits for.  Only the single-launch kernel (the stage pipeline of voxel worlds shares its queues between frames)
     // and only without refraction stacks.
     const bool overlap_scene = c->knobs.flight_overlap && c->stream2 && c->have_scene && !c->sd.any_transparent &&
-                               (frame_is_single_launch(c) || (!c->knobs.no_flight_stage_overlap && c->n_owned >= 4096 && !out_sdr && !c->post_busy));
+                               (frame_is_single_launch(c) || (!c->knobs.no_flight_stage_overlap && c->n_owned >= 4096 && !post && !c->post_busy));
     // (the stage pipeline: a second set of queues, trace_frame; big frames only - small ones gain nothing from a second stream's hops; and not
     // while a post stage is in flight: its persistent in-place launch needs its band workgroups placed, and behind TWO frames' persistent
     // extend stages they are not - one run in four of `bench.py --config 5` stretched to 0.4 s a frame, profiles/r04/h_voxel_walk_tree.txt)
@@ -670,7 +672,7 @@ static int render_frame_in_flight(ycge_ctx *c, float *out_sdr)
     rc = taa_and_commit(c, c->taa_stream, fs, did_reset, false, false);
     c->in_flight_taa = false;
     if (rc != YCGE_OK) return rc;
-    if (out_sdr) {
+    if (post) {
         for (hipEvent_t *ev : {&c->flight_taa_ev, &c->post_hist_ev, &c->post_done_ev, &c->post_set_ev[0], &c->post_set_ev[1], &c->post_set_ev[2]})
             if (!*ev) HIP_TRY(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
         // Steps 6-8 of this frame.  On the stream of this frame's trace where two traces run at a time (the next trace on that stream is
@@ -699,9 +701,9 @@ static int render_frame_in_flight(ycge_ctx *c, float *out_sdr)
     return YCGE_OK;
 }
 
-int ycge_render_frame(ycge_ctx *c, float *out_sdr, ycge_frame_stats *st)
-try {
-    if (!c) return YCGE_ERR_INVALID_ARG;
+// ycge_render_frame; post: run steps 6-8 (out_sdr, when not NULL, gets the read-back)
+int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *st)
+{
     if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
     { const int jr = join_async(c); if (jr != YCGE_OK) return jr; }
     const bool multi_dev = !c->peers.empty() || c->exchange_mode == YCGE_EXCHANGE_RCCL;
@@ -725,7 +727,7 @@ try {
     if (rc != YCGE_OK) return rc;
     rc = taa_and_commit(c, c->stream, fs, did_reset, timed, c->fuse_done);
     if (rc != YCGE_OK) return rc;
-    if (out_sdr) {      // steps 6-8; with NULL the frame stops after TAA (trace-only callers, benchmarks of the hot path)
+    if (post) {      // steps 6-8; without them the frame stops after TAA (trace-only callers, benchmarks of the hot path)
         rc = run_post(c, c->stream, out_sdr, timed);
         if (rc != YCGE_OK) return rc;
     }
@@ -740,7 +742,7 @@ try {
             st->n_rays += h[0]; st->n_box += h[1]; st->n_tri += h[2]; st->n_prim += h[3]; st->n_vox += h[4]; st->n_rays_dark += h[5];
         }
     if (multi_dev) HIP_TRY(c, hipSetDevice(c->device));
-    if (rc == YCGE_OK && st && out_sdr) {
+    if (rc == YCGE_OK && st && post) {
         float ms = 0.0f;
         HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
         st->post_ms = ms;
@@ -751,6 +753,14 @@ try {
         st->exposure_serial_chunks = (float)n_serial;
     }
     return rc;
+}
+} // namespace ycge_host
+
+extern "C" {
+int ycge_render_frame(ycge_ctx *c, float *out_sdr, ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return render_frame_sync(c, out_sdr, out_sdr != nullptr, st);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

@@ -151,6 +151,7 @@ int set_geometry(ycge_ctx *c, int fbw, int fbh, int ss)
     c->taa_valid = false;                                       // Resize: taaHistoryValid = false (:137), taa.Resize (TemporalAA.cs:34-46)
     c->last_cam[0] = c->last_cam[1] = c->last_cam[2] = NAN; c->last_yaw = c->last_pitch = NAN;
     c->den_a.release(); c->den_b.release(); c->unit_n.release(); c->exp_terms.release(); c->exp_scratch.release(); c->d_sdr.release(); c->d_sdr2.release(); c->atrous_statw.release();     // spatialA / spatialB, :129-130
+    release_chexels(c, false);                                  // (the encoded chexel buffers: sized for the console)
     c->denoised = nullptr;
     c->alt_post.release();
     c->wave_prof.release();                                     // sized for the tile grid
@@ -533,6 +534,7 @@ try {
     if (c->taa_stream) (void)hipStreamSynchronize(c->taa_stream);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     release_query(c);          // (drains the query stream first)
+    release_chexels(c, true);
     c->current_hdr.release(); c->g_albedo.release(); c->g_normal.release(); c->g_depth.release(); c->taa_hist.release();
     c->prev_normal.release(); c->prev_depth.release(); c->sky.release(); c->prev_sky.release();
     c->dbg_rays.release(); c->dbg_hit_t.release(); c->dbg_prim.release(); c->dbg_sub.release(); c->dbg_rng.release();

@@ -3,6 +3,8 @@
 // (Kernels: ycge_post.hip.)
 #include "ycge_ctx.h"
 
+#include <memory>
+
 namespace ycge_host {
 
 // ---- steps 6-8 of TryFlipAndBlit (RaytraceRenderer.cs:221-264): A-trous denoise, auto-exposure, tonemap + downsample
@@ -234,7 +236,9 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
             ycge_ctx::InplaceSchedule *sc = nullptr;
             for (auto *k : c->schedules) if (k->w == w && k->h == h && k->step == step) sc = k;
             if (!sc) {
-                sc = new ycge_ctx::InplaceSchedule();
+                // (cached only once complete: a schedule that failed half-way - an upload, an allocation - is freed, never reused)
+                std::unique_ptr<ycge_ctx::InplaceSchedule> building(new ycge_ctx::InplaceSchedule());
+                sc = building.get();
                 sc->w = w; sc->h = h; sc->step = step;
                 std::vector<uint32_t> px, off, bpx, boff;
                 build_inplace_schedule(w, h, step, px, off);
@@ -273,13 +277,14 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
                 if (sc->levels_per_launch > k_cap) sc->levels_per_launch = k_cap;
                 sc->window_width = sc->levels_per_launch >= 1 && !c->knobs.post_hash
                                        ? band_window_width(bpx, boff, sc->bands, sc->levels, sc->levels_per_launch, rows_per_band, (uint32_t)c->knobs.post_groups, 2048u, sc->split ? &desc : nullptr) : 0u;
-                c->schedules.push_back(sc);
                 HIP_TRY(c, sc->pixels.upload(bpx)); HIP_TRY(c, sc->offsets.upload(boff));
                 std::vector<uint32_t> plevel(bpx.size() / (size_t)c->knobs.post_groups + 1, 0u);       // level of every pass (k_atrous_stream)
                 for (int b = 0; b < sc->bands; b++)
                     for (int t = 0; t < sc->levels; t++)
                         for (uint32_t ps = boff[(size_t)b * (sc->levels + 1) + t]; ps < boff[(size_t)b * (sc->levels + 1) + t + 1]; ps++) plevel[ps] = (uint32_t)t;
                 HIP_TRY(c, sc->pass_level.upload(plevel));
+                c->schedules.push_back(sc);
+                building.release();
             }
             if (sc->split && sc->window_width == 0) return c->fail(YCGE_ERR_DEVICE, "in-place A-trous: the split band layout found no collision-free window (set YCGE_POST_NO_SPLIT=1)");
             const int levels_per_launch = sc->levels_per_launch;
@@ -337,6 +342,7 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
     float *d_sdr = second_sdr ? c->d_sdr2.p : c->d_sdr.p;
     e = ycge_launch_tonemap(cur, w, c->fbW, c->fbH, c->ss, 2.2f, 2.0f, 0.0f, c->tone_state.p, d_sdr, stream);   // toneGamma, toneSaturation, toneVibrance
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "tonemap launch failed: %s", hipGetErrorString((hipError_t)e));
+    { const int rc = chexel_encode(c, stream, d_sdr, second_sdr); if (rc != YCGE_OK) return rc; }      // (only where a _chexels call asked)
     if (timed) HIP_TRY(c, hipEventRecord(c->ev[3], stream));
     if (before_copy) HIP_TRY(c, hipEventRecord(before_copy, stream));
     if (out_sdr_host) {
@@ -350,6 +356,7 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
         }
         HIP_TRY(c, hipMemcpyAsync(target, d_sdr, sdr_bytes, hipMemcpyDeviceToHost, stream));
     }
+    { const int rc = chexel_read_back(c, stream, second_sdr); if (rc != YCGE_OK) return rc; }
     if (history_read) HIP_TRY(c, hipEventRecord(history_read, stream));        // (a single iteration: exposure and tonemap read the history itself)
     return YCGE_OK;
 }

@@ -77,6 +77,7 @@ class RaytraceRenderer:
             self.ctx = C.c_void_p()
         self._drop_sdr_buffer()
         self._drop_sdr_ring()
+        self.__dict__.pop("_chexel_ring", None)          # (the chexel arrays of the frames in flight: after ycge_destroy, as above)
 
     def __enter__(self):
         return self
@@ -191,7 +192,7 @@ class RaytraceRenderer:
         p = (C.c_float * 3)(*self._pos)
         self._check(self.L.ycge_set_camera(self.ctx, p, self._yaw, self._pitch, self._fov))
 
-    def _page_locked_zeros(self, shape):
+    def _page_locked_zeros(self, shape, dtype=np.float32):
         """A zeroed float32 array in page-locked memory OF THE LIBRARY (ycge_alloc_host_buffer: hipHostMalloc): (array, owner).  The
         device writes SDR frames straight into it.  Round 4 registered numpy arrays instead (hipHostRegister) and met GPU memory faults
         at heap addresses: registration is page-granular, and - more to the point - a mapping of process heap lives and dies with the
@@ -200,15 +201,15 @@ class RaytraceRenderer:
         _PageLockedOwner whose finaliser hands the pages back (ycge_free_host_buffer) when the last view of the array dies.  close(),
         Resize() and a change of console size only drop the renderer's own reference (after joining the frames in flight, so the device
         is done with the pages): an array a caller still holds - TryFlipAndBlit(copy=False), RenderAsync(sdr_slot=k) - stays readable."""
-        n = int(np.prod(shape))
+        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p = C.c_void_p()
-        rc = self.L.ycge_alloc_host_buffer(n * 4, C.byref(p))
+        rc = self.L.ycge_alloc_host_buffer(nbytes, C.byref(p))
         if rc != 0 or not p.value:
-            raise abi.YcgeError(rc, f"no page-locked memory for an SDR frame of {n * 4} bytes")
+            raise abi.YcgeError(rc, f"no page-locked memory for an SDR frame of {nbytes} bytes")
         owner = _PageLockedOwner(self.L, p.value)
-        buf = (C.c_float * n).from_address(p.value)
+        buf = (C.c_uint8 * nbytes).from_address(p.value)
         buf._ycge_owner = owner          # (numpy keeps `buf` alive through the buffer protocol; `buf` keeps the owner)
-        a = np.ctypeslib.as_array(buf).reshape(shape)
+        a = np.ctypeslib.as_array(buf).view(dtype).reshape(shape)
         return a, owner
 
     def _free_page_locked(self, handle):
@@ -258,6 +259,46 @@ class RaytraceRenderer:
         a = ring[key][0]
         self._check(self.L.ycge_render_frame_async_sdr(self.ctx, a.ctypes.data_as(C.POINTER(C.c_float))))
         return a
+
+    # ---------------------------------------------------------------- device chexel colours (ycge_render_frame_chexels)
+    CHEXEL_OUTPUTS = ("sdr", "color16", "ansi", "rgba")
+
+    def chexel_shapes(self) -> dict:
+        """What each output of the chexel calls holds: sdr {top rgb, bottom rgb} f32; color16 one byte a chexel (color_16 of top | of
+        bottom << 4); ansi {top, bottom} ANSI-256 indices; rgba the fbW x 2 fbH RGBA8 compose image (row 2 cy = top half-cells)."""
+        return {"sdr": ((self.fbH, self.fbW, 2, 3), np.float32), "color16": ((self.fbH, self.fbW), np.uint8),
+                "ansi": ((self.fbH, self.fbW, 2), np.uint8), "rgba": ((2 * self.fbH, self.fbW, 4), np.uint8)}
+
+    @staticmethod
+    def _chexel_pointers(arrays: dict):
+        f = arrays.get("sdr")
+        u8 = lambda k: arrays[k].ctypes.data_as(C.POINTER(C.c_uint8)) if k in arrays else None
+        return (f.ctypes.data_as(C.POINTER(C.c_float)) if f is not None else None), u8("color16"), u8("ansi"), u8("rgba")
+
+    def TryFlipAndBlitChexels(self, color16: bool = True, ansi: bool = False, rgba: bool = False, sdr: bool = False) -> dict:
+        """One frame (ycge_render_frame_chexels): the post stage runs whatever is asked, and the presenters' colour maps of its SDR
+        array come back from the device - {name: array} for each output asked (shapes: chexel_shapes).  The SDR and the frame state are
+        those of TryFlipAndBlit(want_sdr=True); the frame statistics go to self.stats."""
+        want = {"sdr": sdr, "color16": color16, "ansi": ansi, "rgba": rgba}
+        arrays = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.chexel_shapes().items() if want[k]}
+        self._check(self.L.ycge_render_frame_chexels(self.ctx, *self._chexel_pointers(arrays), C.byref(self.stats)))
+        return arrays
+
+    def RenderAsyncChexels(self, slot: int, color16: bool = True, ansi: bool = False, rgba: bool = False, sdr: bool = False) -> dict:
+        """Frames in flight with the chexel outputs (ycge_render_frame_async_chexels), as RenderAsync(sdr_slot=slot): the wrapper's
+        page-locked arrays of this slot are returned and hold the frame once Wait() has returned - one slot per frame in flight."""
+        want = {"sdr": sdr, "color16": color16, "ansi": ansi, "rgba": rgba}
+        ring = self.__dict__.setdefault("_chexel_ring", {})
+        arrays = {}
+        for k, (shp, dt) in self.chexel_shapes().items():
+            if not want[k]:
+                continue
+            key = (int(slot), k)
+            if key not in ring or ring[key][0].shape != shp:        # (another console size: Resize joined the frames in flight)
+                ring[key] = self._page_locked_zeros(shp, dt)
+            arrays[k] = ring[key][0]
+        self._check(self.L.ycge_render_frame_async_chexels(self.ctx, *self._chexel_pointers(arrays)))
+        return arrays
 
     def Wait(self):
         self._check(self.L.ycge_wait(self.ctx))
