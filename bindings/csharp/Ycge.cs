@@ -149,7 +149,7 @@ namespace ConsoleGame.RayTracing.Native
     public unsafe struct YFrameStats  // ycge_frame_stats
     {
         public long Frame;
-        public int HistoryReset, FanBlocks;
+        public int HistoryReset, FanBlocks;   // FanBlocks: reserved, always 0
         public double TraceMs, TaaMs, PostMs, TotalMs;
         public ulong NRays, NBox, NTri, NPrim, NVox;
         public float Exposure, ExposureSerialChunks;

@@ -262,7 +262,7 @@ typedef enum ycge_exchange { YCGE_EXCHANGE_PEER_PUSH = 0, YCGE_EXCHANGE_RCCL = 1
 typedef struct ycge_frame_stats {
     int64_t frame;               /* frameCounter after the increment            */
     int32_t history_reset;       /* TAA history was (re)initialised this frame  */
-    int32_t fan_blocks;          /* 8x8 blocks of this frame's schedule that went to k_trace_fan (0 = kernel not launched) */
+    int32_t fan_blocks;          /* reserved, always 0 */
     double trace_ms;             /* device time of ray-gen + trace              */
     double taa_ms;
     double post_ms;              /* denoise + exposure + tonemap/downsample     */

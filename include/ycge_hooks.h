@@ -63,7 +63,7 @@ size_t ycge_wf_sizes(int which);
 size_t ycge_post_state_bytes(void);
 size_t ycge_exposure_scratch_bytes(int w, int h, int step);
 size_t ycge_bvh_build_scratch_bytes(int n);
-int ycge_atrous_persist_resident(int groups_per_pass, int split, int level_handover, int profile);
+int ycge_atrous_persist_resident(int groups_per_pass, int split, int profile);
 void ycge_atrous_duo_pad_lds(int bytes);
 void ycge_peer_worker_main(ycge_ctx *c, ycge_ctx *p);                /* a peer device's thread function (started by ycge_create) */
 

@@ -52,7 +52,7 @@ for k in acc:
 # per-FRAME counter summary of the trace kernels (the launches stats.trace_ms brackets), for bench.py's roofline object
 if json_path:
     import json
-    TRACE = ("k_trace", "k_trace_nomesh", "k_trace_fan", "k_trace_refill", "k_wf_primary", "k_wf_extend", "k_wf_trace_p", "k_wf_shade", "k_wf_lights")
+    TRACE = ("k_trace", "k_trace_nomesh", "k_wf_primary", "k_wf_extend", "k_wf_trace_p", "k_wf_shade", "k_wf_lights")
     def is_trace(k):      # the kernels the benchmark times: the NON-counting instances (bench.py's counting replay launches the <true, ...> ones)
         return k.split("<")[0] in TRACE and ("<" not in k or k.split("<")[1].split(",")[0].strip() in ("false", "false>") or k.split("<")[0] == "k_wf_shade")
     # calibration: bytes a copy of known size moves / what the counters say (copycal under the same two PMC passes)
@@ -110,11 +110,11 @@ if json_path:
         # SQ_ACTIVE_INST_VALU counts quad-cycles summed over the SIMDs; SQ_BUSY_CYCLES is summed over the shader engines' SQs:
         # busy fraction of the VALU pipes while the kernels are resident = 4 * active / (SIMD count * launch cycles); the launch
         # cycles come from GRBM_GUI_ACTIVE when that pass exists
-        # GRBM_GUI_ACTIVE comes back summed over the 8 XCDs; concurrent kernels (k_trace_fan beside k_trace) overlap, so the launch's
-        # span is the lead kernel's; the stage kernels of the wavefront pipeline run one after the other, so theirs add up
+        # GRBM_GUI_ACTIVE comes back summed over the 8 XCDs; the stage kernels of the wavefront pipeline run one after the other,
+        # so their spans add up
         span = 0.0
         for k in acc:
-            if is_trace(k) and "GRBM_GUI_ACTIVE" in acc[k] and (k.split("<")[0] != "k_trace_fan"):
+            if is_trace(k) and "GRBM_GUI_ACTIVE" in acc[k]:
                 span += sum(acc[k]["GRBM_GUI_ACTIVE"]) / n_frames["GRBM_GUI_ACTIVE"] / 8.0
         if span > 0:
             d["launch_cycles"] = round(span)

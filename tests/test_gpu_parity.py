@@ -283,12 +283,12 @@ def test_error_codes(product_lib, path):
     product_lib.ycge_destroy(ctx)
 
 
-@pytest.mark.parametrize("case", ["cornell-2", "cornell-2-lean", "bunny-4-fan"])
+@pytest.mark.parametrize("case", ["cornell-2", "cornell-2-lean", "bunny-4"])
 def test_two_rank_tile_split_matches_single_gpu(product_lib, path, case, monkeypatch):
     """world_size 2 (4) emulated on one GPU: the contexts trace their tiles, slabs are concatenated as an
-    all-gather would, all resolve; results equal the single-context frame bit for bit.  The bunny case runs the
-    ranks' heavy blocks through k_trace_fan (the tiled default from 2 ranks up; YCGE_FAN=1 lowers its threshold so that
-    this small frame has such blocks) against a single context that does not."""
+    all-gather would, all resolve; results equal the single-context frame bit for bit.  The bunny case splits config 3
+    over 4 ranks, whose schedules cut the heavy classes into parts (a rank's default split policy), against a single
+    context that does not."""
     lean = case.endswith("lean")             # config.slab_albedo = 0: 8-float slab records, no albedo plane
     floats = tiles.LEAN_SLAB_FLOATS if lean else tiles.SLAB_FLOATS
     if case.startswith("cornell-2"):
@@ -303,7 +303,6 @@ def test_two_rank_tile_split_matches_single_gpu(product_lib, path, case, monkeyp
         r.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
         return r
     single = mk(0, 1)
-    if case == "bunny-4-fan": monkeypatch.setenv("YCGE_FAN", "1")
     ranks = [mk(i, world) for i in range(world)]
     nb = ranks[0].tile_slab_bytes()
     assert nb == ranks[1].tile_slab_bytes() == tiles.slab_floats(world, tiles.tile_grid(single.hiW, single.hiH)[2], floats) * 4
@@ -472,43 +471,11 @@ def test_update_lights_per_frame(product_lib, oracle, path):
     o.close(); g.close()
 
 
-def _experiments_lib():
-    """lib/var_experiments.so: the product's sources with -DYCGE_EXPERIMENTS=1 - the measured-and-rejected kernel forms of csrc/experiments/
-    (k_trace_refill, the group hand-over A-trous) exist in that build only"""
-    from yetanotherconsolegameengine_amd import build
-    return abi.load_library(build.build_variant("experiments"))
-
-
-@pytest.mark.parametrize("cfg_n", [1, 3, 4])
-def test_taa_inside_the_trace_launch_is_bit_exact(oracle, monkeypatch, cfg_n):
-    """csrc/experiments/ycge_taa_in_trace.hip.h (round 6, measured and rejected: slower - profiles/r06/b_taa_in_trace.txt): TemporalBlendWithClamp
-    resolved by the trace launch itself - written-through stores, neighbourhood counters, the last finisher of a 3 x 3 block neighbourhood stages
-    the 10 x 10 window in LDS with device-coherent loads.  Same reads, same arithmetic, same writes as k_taa: history and guide copies equal the
-    oracle's over four frames (the first resets, the others blend), whole blocks and - config 4 at full size, steady state - the parts of split
-    blocks, with a sky / mesh boundary and the image's right and bottom edges in the windows."""
-    monkeypatch.setenv("YCGE_TAA_FUSE", "1")
-    monkeypatch.setenv("YCGE_PATH", "megakernel")
-    lib = _experiments_lib()
-    sc, w, h, ss, pose = scenes.config_scene(cfg_n)
-    if cfg_n == 3: w, h = 323, 91          # a trace grid that is no multiple of the 8 x 8 block: partial blocks on two sides
-    flat = flatten(sc)
-    o = oracle.OracleRenderer(sc, w, h, ss, pose, flat=flat)
-    g = RaytraceRenderer(flat, w, h, pose["fov"], ss, lib=lib)
-    g.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
-    for f in range(4 if cfg_n != 4 else 6):
-        o.render(stages=1, threads=8); g.TryFlipAndBlit()
-        if cfg_n == 4:          # (k_taa takes 33 us at 1080p; two event records back to back are ~5 us apart)
-            assert float(g.stats.taa_ms) < 0.02, "a TAA launch ran: the build or the knob did not take"
-        for b in (abi.BUF_CURRENT_HDR, abi.BUF_TAA_HISTORY, abi.BUF_PREV_NORMAL, abi.BUF_PREV_DEPTH, abi.BUF_PREV_SKY):
-            assert pu.mismatch_count(o.read(b), g.read(b)) == 0, (cfg_n, f, b)
-    o.close(); g.close()
-
-
-def _post_pair(oracle, sc, w, h, ss, pose, frames=3, lib=None):
+def _post_pair(oracle, sc, w, h, ss, pose, frames=3):
     """oracle (stages=2) and product (SDR requested) over `frames` frames; yields per-frame comparison tuples"""
     flat = flatten(sc)
     o = oracle.OracleRenderer(sc, w, h, ss, pose, flat=flat)
-    g = RaytraceRenderer(flat, w, h, pose.get("fov", 45.0), ss, lib=lib)
+    g = RaytraceRenderer(flat, w, h, pose.get("fov", 45.0), ss)
     g.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
     out = []
     for f in range(frames):
@@ -562,17 +529,16 @@ def test_waived_inplace_iteration_against_the_oracle_and_its_distance_to_the_exa
         o.close(); g.close(); e.close()
 
 
-@pytest.mark.parametrize("mode", ["0", "2", "3", "4"])
+@pytest.mark.parametrize("mode", ["0", "2", "3"])
 def test_inplace_atrous_in_every_form_against_the_oracle(product_lib, oracle, monkeypatch, mode):
     """The in-place A-trous iteration as ONE persistent launch with level-granular hand-over between the bands' workgroups (0, the
-    default; 3: bands in block order), as a launch per level group (2) and as a persistent launch with group hand-over (4): the
+    default; 3: bands in block order) and as a launch per level group (2): the
     denoised frame, the exposure and the SDR frame must equal the oracle's on every frame.  Sizes: several bands (the hand-over is
     exercised), an odd size (border clamps), a width that is not a multiple of a cache line's pixels (two bands share lines)."""
     monkeypatch.setenv("YCGE_POST_MODE", mode)
-    lib = _experiments_lib() if mode == "4" else None          # (the group hand-over form lives in csrc/experiments/)
     sc, _, _, _, pose = scenes.config_scene(2)
     for (w, h, ss) in ((192, 54, 1), (131, 37, 1), (64, 20, 2)):
-        for f, (taa, den, expo, sdr, sdr_rms, post_ms) in enumerate(_post_pair(oracle, sc, w, h, ss, pose, frames=3, lib=lib)):
+        for f, (taa, den, expo, sdr, sdr_rms, post_ms) in enumerate(_post_pair(oracle, sc, w, h, ss, pose, frames=3)):
             print(f"mode {mode} {w}x{h} ss{ss} frame {f + 1}: taa {taa} denoised {den} exposure {expo} sdr {sdr}")
             assert taa == 0 and den == 0 and not expo and sdr == 0
 
@@ -636,24 +602,20 @@ def test_update_objects_rebuilds_scene_bvh_only(product_lib, oracle, path):
     o.close(); g.close()
 
 
-@pytest.mark.parametrize("knob", ["YCGE_FAN=1", "YCGE_FAN=1,YCGE_SPLIT=22222220", "YCGE_REFILL=8"])
-def test_query_fan_out_and_refill_kernels_bit_exact(product_lib, oracle, monkeypatch, knob):
-    """k_trace_fan (three wavefronts per heavy block, the default when a frame is tiled over >= 2 GPUs) and k_trace_refill
-    (experiment) trace the same queries as k_trace in another arrangement: every buffer and every counter must still
-    equal the oracle's.  Fan-out needs a schedule, i.e. starts with the second frame; three frames are compared.
-    Scenes: the bunny (heavy blocks, diffuse bounces), the primitive zoo with glass (path items and transmittance
-    segments go through slot 0 one at a time), Cornell (not a flat scene: generic walk under the fan-out)."""
+def test_split_schedule_bit_exact(product_lib, oracle, monkeypatch):
+    """YCGE_SPLIT=22222220: the schedule cuts every block above the lowest policy class into 4 parts of 16 pixels, each a k_trace
+    wavefront of its own - the same queries in another arrangement: every buffer and every counter must still equal the oracle's.
+    Parts need a schedule, i.e. start with the second frame; three frames are compared.  Scenes: the bunny (heavy blocks, diffuse
+    bounces), the primitive zoo with glass (path items and transmittance segments), Cornell (not a flat scene: generic walk)."""
+    knob = "YCGE_SPLIT=22222220"
     monkeypatch.setenv("YCGE_PATH", "megakernel")
-    for kv in knob.split(","):                  # the split variant runs fanned blocks in 4 parts of 16 pixels (the 8-rank default)
-        name, value = kv.split("=")
-        monkeypatch.setenv(name, value)
-    lib = _experiments_lib() if "REFILL" in knob else None          # (k_trace_refill lives in csrc/experiments/)
+    monkeypatch.setenv("YCGE_SPLIT", "22222220")
     sc3, w3, h3, ss3, pose3 = scenes.config_scene(3)
     sc1, w1, h1, ss1, pose1 = scenes.config_scene(1)
     cases = [("bunny", sc3, 320, 90, 1, pose3), ("zoo+glass", _zoo_scene(True), 192, 54, 1, dict(pos=(0.1, 1.2, 1.0), yaw=0.05, pitch=-0.12, fov=50.0)),
              ("cornell", sc1, w1, h1, ss1, pose1)]
     for label, sc, w, h, ss, pose in cases:
-        o, g = pu.run_pair(oracle, sc, w, h, ss, pose, frames=1, lib=lib)
+        o, g = pu.run_pair(oracle, sc, w, h, ss, pose, frames=1)
         _assert_parity(pu.compare_frame(o, g), f"{knob} {label} frame1")
         for f in (2, 3):
             o.render(stages=1, threads=8); g.TryFlipAndBlit()

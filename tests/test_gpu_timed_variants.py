@@ -1,9 +1,8 @@
 """-m gpu: the kernel variants bench.py TIMES, held to the oracle.
 
 Every other oracle comparison runs with config.count_work = 1, i.e. the counting template instances (k_trace<true, .>, the
-COUNT stage kernels).  The benchmark runs the non-counting ones - k_trace<false,true> and k_trace_fan<false,true> with their
-4-wavefronts-per-SIMD register budget (spills), the occupancy-budgeted stage kernels of the voxel world - in their steady state:
-longest-first schedule, cost history over four frames, the head of the schedule fanned out.  Here those binaries run the
+COUNT stage kernels).  The benchmark runs the non-counting ones - k_trace<false,true> with its register budget, the
+occupancy-budgeted stage kernels of the voxel world - in their steady state: longest-first schedule, cost history over four frames.  Here those binaries run the
 BASELINE configs at full size for several frames and every buffer of every frame is compared with the oracle
 (reference order and semantics: Objects/MeshBVH.cs:132-236, RaytraceRenderer.cs:448-620, 274-398).
 """
@@ -29,16 +28,12 @@ def _assert_frame(o, g, label):
         assert st[k + "_rms"] <= pu.RMS_TOL
 
 
-@pytest.mark.parametrize("cfg_n,frames,fan", [(3, 5, None), (4, 6, None), (4, 6, "5")])
-def test_timed_mesh_kernels_full_size_steady_state(product_lib, oracle, monkeypatch, cfg_n, frames, fan):
+@pytest.mark.parametrize("cfg_n,frames", [(3, 5), (4, 6)])
+def test_timed_mesh_kernels_full_size_steady_state(product_lib, oracle, monkeypatch, cfg_n, frames):
     """Configs 3 and 4 at full size, default path (single launch for mesh viewers), NON-counting kernels, capture on: what the
     benchmark launches - k_trace<false,true> with the cooperative walk of its sparse wavefronts (ycge_coop.hip.h), longest first
-    from frame 2 on.  Round 3: a whole frame runs WITHOUT the query fan-out by default (asserted: stats.fan_blocks == 0); the
-    third case switches it on (YCGE_FAN=5, as a rank's share of a tiled frame has it) so that k_trace_fan<false,true>, its three
-    wavefronts walking cooperatively too, meets the oracle at full size as well - asserted through stats.fan_blocks > 0."""
+    from frame 2 on.  stats.fan_blocks is reserved and stays 0 (asserted)."""
     monkeypatch.delenv("YCGE_PATH", raising=False)
-    if fan is not None:
-        monkeypatch.setenv("YCGE_FAN", fan)
     sc, w, h, ss, pose = scenes.config_scene(cfg_n)
     o, g = pu.run_pair(oracle, sc, w, h, ss, pose, frames=1, oracle_threads=64, count=False)
     _assert_frame(o, g, f"cfg{cfg_n} timed variants frame 1")
@@ -47,11 +42,7 @@ def test_timed_mesh_kernels_full_size_steady_state(product_lib, oracle, monkeypa
         o.render(stages=1, threads=64); g.TryFlipAndBlit()
         _assert_frame(o, g, f"cfg{cfg_n} timed variants frame {f}")
         fanned.append(int(g.stats.fan_blocks))
-    if fan is None:
-        assert fanned == [0] * len(fanned), f"fan-out on a whole frame: {fanned}"
-    else:
-        assert fanned[-1] > 0 and fanned[-2] > 0, f"k_trace_fan never launched: {fanned}"
-        assert fanned[-1] <= 200
+    assert fanned == [0] * len(fanned), f"fan_blocks is reserved: {fanned}"
     assert g.timed_steps() > 0
     o.close(); g.close()
 

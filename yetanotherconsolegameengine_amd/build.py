@@ -20,8 +20,7 @@ LIB_DIR = PKG / "lib"
 LIB = LIB_DIR / "libycge_hip.so"
 SOURCES = ["ycge_host.cpp", "ycge_frame.cpp", "ycge_post_host.cpp", "ycge_resident.cpp", "ycge_accel.cpp", "ycge_query.cpp", "ycge_chexel.cpp", "ycge_kernels.hip", "ycge_post.hip", "ycge_bvh_build.hip", "ycge_query.hip",
            "ycge_chexel.hip"]
-HEADERS = ["ycge_ctx.h", "ycge_device.h", "ycge_accel.h", "ycge_math.h", "ycge_rt.hip.h", "ycge_coop.hip.h", "ycge_anyhit.hip.h", "ycge_keysort.h",
-           "experiments/ycge_refill.hip.h", "experiments/ycge_atrous_persist_groups.hip.h", "experiments/ycge_taa_in_trace.hip.h"]
+HEADERS = ["ycge_ctx.h", "ycge_device.h", "ycge_accel.h", "ycge_math.h", "ycge_rt.hip.h", "ycge_coop.hip.h", "ycge_anyhit.hip.h", "ycge_keysort.h"]
 ARCH = "gfx950"
 
 FLAGS = [
@@ -115,9 +114,6 @@ VARIANTS = {
     # the work list of the order-free occlusion queries cut to 112 entries (HIGH = 32): wide rounds are cut back and one-item dives happen
     # on ordinary scenes, so the GPU tests see every mode of the list (csrc/ycge_anyhit.hip.h)
     "bfs112": ["-DYCGE_BFS_LIST=112u"],
-    # the measured-and-rejected kernel forms of csrc/experiments/ (k_trace_refill, the group hand-over A-trous): out of the product build,
-    # kept bit-exact by their parity tests through this one
-    "experiments": ["-DYCGE_EXPERIMENTS=1"],
     # the counting TWIN of the timed stage kernels of voxel worlds: the same non-counting instances with per-lane counters of what they
     # walk (scene-tree steps by kind, cell steps, cell fetches, queue records).  bench.py --config 5 replays its timed frames through it for
     # `roofline.timed_work`; profiles/vox_stats.py reads the per-phase clocks of k_wf_trace_p from it

@@ -34,14 +34,14 @@
 
 extern "C" {
 size_t ycge_wf_sizes(int which);
-int ycge_launch_trace(const ycge::SceneDev *S, const ycge::FrameParams *P, const ycge::TraceOut *O, int count, int flat, int refill_steps,
+int ycge_launch_trace(const ycge::SceneDev *S, const ycge::FrameParams *P, const ycge::TraceOut *O, int count, int flat,
                       hipStream_t stream, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 int ycge_launch_wavefront(const ycge::SceneDev *S, const ycge::FrameParams *P, const ycge::TraceOut *O, void *const bufs[7], int rounds,
                           int has_grid, int flat, int count, int persistent_waves, hipStream_t stream, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join,
                           const ycge::TraceOut *O_side);
 int ycge_launch_trace_batch(const ycge::SceneDev *S, const ycge::FrameParams *P, const ycge::TraceOut *O, int n, int count, int flat, hipStream_t stream);
 int ycge_launch_scene_walk(const void *nodes, int n_inner, const uint32_t *leaf_prims, const void *prims, void *walk, hipStream_t stream);
-int ycge_launch_order_blocks(uint32_t *cost, uint32_t n, uint32_t policy, uint32_t split_top, uint32_t fan_class, uint32_t fan_cap, uint32_t next_slot, uint32_t skip_mask, uint32_t *order_ws,
+int ycge_launch_order_blocks(uint32_t *cost, uint32_t n, uint32_t policy, uint32_t split_top, uint32_t next_slot, uint32_t skip_mask, uint32_t *order_ws,
                              uint32_t *order, hipStream_t stream, int small_groups = 0, uint32_t n_frames = 0, uint32_t *snap = nullptr);
 int ycge_launch_taa_tiles(const ycge::TaaParams *T, const ycge::FrameParams *P, const float *current, const float *normal, const float *depth, const uint8_t *sky,
                           float *hist, float *prev_normal, float *prev_depth, uint8_t *prev_sky, float *slab, hipStream_t stream);
@@ -50,12 +50,10 @@ int ycge_launch_resolve_tiles(const ycge::TaaParams *T, const ycge::FrameParams 
 int ycge_launch_halo(int scatter, float *hdr, uint8_t *sky, const uint32_t *px, uint32_t n, void *records, hipStream_t stream);
 int ycge_launch_pack_history(const ycge::FrameParams *P, const float *hist, float *slab, hipStream_t stream);
 int ycge_launch_unpack_history(const float *all_slabs, size_t slab_floats_per_rank, int hiW, int hiH, int tiles_x, int n_tiles, int world_size, float *hist, hipStream_t stream);
-int ycge_launch_trace_fan(const ycge::SceneDev *S, const ycge::FrameParams *P, const ycge::TraceOut *O, int count, int flat, uint32_t fan_cap,
-                          hipStream_t stream);
 int ycge_launch_taa(const ycge::TaaParams *T, const float *current, const float *normal, const float *depth, const uint8_t *sky,
                     float *hist, float *prev_normal, float *prev_depth, uint8_t *prev_sky, hipStream_t stream, int small_groups = 0, hipEvent_t stop = nullptr);
 size_t ycge_post_state_bytes(void);
-int ycge_atrous_persist_resident(int groups_per_pass, int split, int level_handover, int profile);
+int ycge_atrous_persist_resident(int groups_per_pass, int split, int profile);
 void ycge_atrous_duo_pad_lds(int bytes);
 int ycge_launch_unit_normals(const float *normal, float *unit, size_t n, hipStream_t stream);
 int ycge_launch_atrous(int w, int h, int step, const float phi[4], const float *cur, float *dst, const float *albedo, const float *unit_n,
@@ -66,8 +64,8 @@ int ycge_launch_atrous_inplace(int w, int h, int step, const float phi[4], float
                                const float *depth, const uint8_t *sky, float *statw, const uint32_t *d_pixels, const uint32_t *d_offsets,
                                int n_levels, int n_bands, int K, int groups_per_pass, int rows_per_band, unsigned window_width, hipStream_t stream);
 int ycge_launch_atrous_persist(int w, int h, int step, const float phi[4], float *buf, const uint8_t *sky, float *statw, const uint32_t *d_pixels,
-                               const uint32_t *d_offsets, const uint32_t *d_pass_level, const int32_t *d_band_desc, int n_levels, int n_bands, int K, int groups_per_pass, int rows_per_band, unsigned window_width,
-                               uint32_t *progress, uint32_t epoch, int xcd_local, int level_handover, int profile, uint32_t ticket_base, hipStream_t stream);
+                               const uint32_t *d_offsets, const uint32_t *d_pass_level, const int32_t *d_band_desc, int n_levels, int n_bands, int groups_per_pass, int rows_per_band, unsigned window_width,
+                               uint32_t *progress, uint32_t epoch, int xcd_local, int profile, uint32_t ticket_base, hipStream_t stream);
 size_t ycge_exposure_scratch_bytes(int w, int h, int step);
 size_t ycge_bvh_build_scratch_bytes(int n);
 int ycge_launch_scene_bvh_build(const float *items, int n, void *scratch, void *ref_out, void *gnodes_out, uint32_t *leaf_out, void *result,
@@ -136,17 +134,14 @@ struct Knobs {
     int path_policy = 0;             // YCGE_PATH: 0 auto, 1 wavefront, 2 single launch
     bool xcd_strips = false, generic_walk = false, no_lpt = false, no_refill = false;
     int wave_prof_stage = -1;        // YCGE_WAVE_PROF: -1 off, 0 primary, 1 extend, 2 mega
-    int refill_steps = YCGE_REFILL_STEPS_DEFAULT;
     bool split_set = false; uint32_t split_policy = 0;
     int split_top_lg = 2;                        // YCGE_SPLIT_TOP_LG: log2 of the parts such a block goes in (2 = 4 parts of 16 pixels)
     bool split_top_set = false;                  // YCGE_SPLIT_TOP / YCGE_SPLIT_TOP_LG given: they decide; else schedule_policy picks by the frame's block count
     int split_top = YCGE_SPLIT_TOP_DEFAULT;     // YCGE_SPLIT_TOP: this many blocks at the head of the schedule go in 4 parts of 16 pixels (0 = none)
     int pw_per_cu = 32;
     int post_band_rows = YCGE_POST_BAND_ROWS_DEFAULT, post_k = YCGE_POST_K_DEFAULT, post_groups = YCGE_POST_GROUPS_DEFAULT;
-    int fan_class = -1, fan_cap = -1;   // -1 = default by world size
     bool split_resolve = false;      // YCGE_RES_SPLIT_RESOLVE=1: the tile-resident resolve as round 5's two launches (k_scatter_halo, k_taa_tiles) instead of k_resolve_tiles (A/B)
-    bool taa_fuse = false;           // YCGE_TAA_FUSE=1: the synchronous single-launch frame resolves TAA inside the trace launch - experiment builds only (csrc/experiments/ycge_taa_in_trace.hip.h: bit-exact, slower)
-    int post_mode = 0;               // YCGE_POST_MODE: in-place A-trous: 0 = one persistent launch, level-granular hand-over (k_atrous_stream), 2 = a launch per level group, 3 = as 0 with bands in block order, 4 = persistent with group hand-over (k_atrous_persist)
+    int post_mode = 0;               // YCGE_POST_MODE: in-place A-trous: 0 = one persistent launch, level-granular hand-over (k_atrous_stream), 2 = a launch per level group, 3 = as 0 with bands in block order
     bool post_no_split = false;      // YCGE_POST_NO_SPLIT: whole bands in the persistent in-place A-trous (no row-parity half-bands)
     int post_probe_band = -1;        // YCGE_POST_PROBE_BAND: this band and the next record a per-pass timeline (profiles/post_bands.py)
     int post_assume_resident = 0;    // YCGE_POST_ASSUME_RESIDENT (tests): take this for the runtime's answer - more bands than fit, to exercise the order-of-arrival numbering
@@ -185,7 +180,6 @@ struct Knobs {
         no_walk_tree = getenv("YCGE_NO_WALK_TREE") != nullptr; no_lights_beside = getenv("YCGE_NO_LIGHTS_BESIDE") != nullptr; no_flight_stage_overlap = getenv("YCGE_NO_FLIGHT_STAGE_OVERLAP") != nullptr;
         no_lpt = getenv("YCGE_NO_LPT") != nullptr; no_refill = getenv("YCGE_NO_REFILL") != nullptr;
         if (const char *e = getenv("YCGE_WAVE_PROF")) wave_prof_stage = e[0] == 'e' ? 1 : e[0] == 'm' ? 2 : 0;
-        refill_steps = geti("YCGE_REFILL", YCGE_REFILL_STEPS_DEFAULT);
         if (const char *e = getenv("YCGE_SPLIT")) { split_set = true; split_policy = (uint32_t)strtoul(e, nullptr, 8); }
         split_top_set = getenv("YCGE_SPLIT_TOP") != nullptr || getenv("YCGE_SPLIT_TOP_LG") != nullptr;
         split_top = geti("YCGE_SPLIT_TOP", YCGE_SPLIT_TOP_DEFAULT);
@@ -196,8 +190,6 @@ struct Knobs {
         post_band_rows = geti("YCGE_POST_BAND_ROWS", YCGE_POST_BAND_ROWS_DEFAULT); post_k = geti("YCGE_POST_K", YCGE_POST_K_DEFAULT);
         post_groups = geti("YCGE_POST_GROUPS", YCGE_POST_GROUPS_DEFAULT);
         if (post_groups != 8 && post_groups != 16 && post_groups != 32) post_groups = YCGE_POST_GROUPS_DEFAULT;
-        fan_class = geti("YCGE_FAN", -1); fan_cap = geti("YCGE_FAN_CAP", -1);
-        taa_fuse = YCGE_EXPERIMENTS && geti("YCGE_TAA_FUSE", 0) != 0;
         split_resolve = geti("YCGE_RES_SPLIT_RESOLVE", 0) != 0;
         post_mode = geti("YCGE_POST_MODE", 0);
         post_hash = geti("YCGE_POST_HASH_FORM", 0) != 0;
@@ -223,11 +215,6 @@ struct Knobs {
         scene_bvh_host = getenv("YCGE_SCENE_BVH_HOST") != nullptr;
         bvh_waves = geti("YCGE_BVH_WAVES", 16);
         scene_bvh_device_min = geti("YCGE_SCENE_BVH_DEVICE_MIN", YCGE_BVH_DEV_MIN_ITEMS_DEFAULT);
-#if !YCGE_EXPERIMENTS
-        // the kernel forms of csrc/experiments/ (k_trace_refill, the group hand-over A-trous) are not in this build
-        refill_steps = 0;
-        if (post_mode == 4) post_mode = 0;
-#endif
     }
 };
 
@@ -237,7 +224,6 @@ struct FrameState {
     float pos[3], yaw, pitch, fov;
     bool reset;
     int64_t frame;
-    uint32_t fan_blocks;
     bool scheduled = false;      // the trace ran the single-launch kernel with a longest-first schedule (cost ring in use)
     bool single_launch = false;  // the trace ran the single-launch kernel (its last workgroup stores the placed value), scheduled or not
 };
@@ -281,13 +267,12 @@ struct ycge_ctx {
     hipStream_t last_stream = nullptr;         // the stream the last tiled call ran on (scene updates wait for it too)
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // k_trace runs beside k_trace_fan on a side stream, forked from and joined to the frame's stream
-    hipStream_t fan_stream = nullptr;
-    hipEvent_t fan_ev[2] = {nullptr, nullptr};
+    // a side stream, forked from and joined to the frame's stream: the next frame's schedule, the light loop beside the next round's
+    // trace (stage pipeline), the resident ring's schedules and the static A-trous weights run on it
+    hipStream_t side_stream = nullptr;
+    hipEvent_t side_ev[2] = {nullptr, nullptr};
     hipEvent_t traced_ev = nullptr, order_ev = nullptr;   // the next frame's schedule is built on the side stream, beside TAA
     bool order_pending = false;
-    uint32_t fan_class = 0, fan_cap = 0;       // schedule classes >= fan_class are fanned, at most fan_cap blocks (0 = off)
-    uint32_t *h_n_fan = nullptr;               // pinned: how many entries the last finished schedule gave k_trace_fan (read without waiting)
     char device_name[256] = {0};
     int compute_units = 0;
 
@@ -397,7 +382,7 @@ struct ycge_ctx {
     DevBuf<float> den_a, den_b, unit_n, exp_terms, d_sdr, d_sdr2;      // d_sdr2: SDR frames in flight read back one array while the next frame's tonemap fills the other
     DevBuf<float> atrous_statw;                // [pixel][25 taps][3]: colour-independent weight factors of an in-place A-trous iteration
     DevBuf<uint8_t> exp_scratch;                  // chunk records of the exposure sum (k_exposure_sum)
-    DevBuf<uint32_t> post_progress;               // k_atrous_persist: groups finished per band, one 128-byte line each
+    DevBuf<uint32_t> post_progress;               // k_atrous_stream: levels published per band, one 128-byte line each
     uint32_t post_epoch = 0;                      // ... counted from here in the next launch
     uint32_t post_ticket = 0;                     // k_atrous_stream, bands in order of arrival: numbers drawn so far (the counter lives in post_progress)
     // a second set of everything the denoiser scratches, for the post stages of every other frame in flight: two of them run side by side
@@ -419,11 +404,6 @@ struct ycge_ctx {
     DevBuf<uint32_t> block_cost, block_order, order_ws;   // k_trace scheduling feedback (4 blocks of 8x8 px per tile)
     DevBuf<uint32_t> cost_snap;                    // a schedule built while traces are in flight reads a copy of the cost ring (ycge_launch_order_blocks)
     bool block_order_valid = false;
-    // TemporalBlendWithClamp inside the trace launch (ycge::TaaFuse): neighbourhood counters per 8 x 8 block (monotonic, zeroed when allocated) and
-    // what ycge_render_frame asks of / hears back from trace_frame for the frame at hand
-    DevBuf<uint32_t> taa_block_ctr, taa_part_ctr;
-    bool fuse_request = false, fuse_done = false;
-    ycge::TaaParams fuse_T;
     DevBuf<uint64_t> stack_spill;                 // [YCGE_TRAVERSAL_STACK - 12][persistent lanes]
     bool any_light_lit = false;                   // some light has a contribution (GLight::dark == 0): the timed light loop has shadow rays to trace
     DevBuf<uint64_t> stack_spill_side;            // ... of the stage kernel that runs on the side stream beside another (the light loop beside the next round's trace)

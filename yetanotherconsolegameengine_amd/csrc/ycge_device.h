@@ -18,10 +18,6 @@
 #pragma once
 #include <stdint.h>
 
-#ifndef YCGE_EXPERIMENTS
-#define YCGE_EXPERIMENTS 0          // 1: the measured-and-rejected kernel forms of csrc/experiments/ are compiled in (lib/var_experiments.so; their parity tests load that build)
-#endif
-
 namespace ycge {
 
 // ---- child / stack reference encoding (uint32) ---------------------------
@@ -182,8 +178,6 @@ struct GLight {
 #define YCGE_COST_FRAMES 4          // a block's schedule cost is its largest cost over this many frames
 #endif
 #define YCGE_SCHEDULE_SLACK 2u      // k_trace grid = blocks x this: room for the parts of split blocks
-#define YCGE_FAN_CAP_DEFAULT 2048u   // k_trace_fan: at most this many blocks of the schedule's head
-#define YCGE_REFILL_STEPS_DEFAULT 0
 #define YCGE_POST_BAND_ROWS_DEFAULT 8 // rows per band of the in-place A-trous iteration (at least 2 x step)
 #define YCGE_POST_GROUPS_DEFAULT 16    // pixels per pass of the banded in-place A-trous iteration (workgroup = 32 x this many threads)
 #define YCGE_POST_K_DEFAULT 8         // levels per launch of the banded in-place A-trous iteration
@@ -274,17 +268,6 @@ struct TaaParams {
     int32_t reset;
 };
 
-// TemporalBlendWithClamp INSIDE the trace launch (round 6, measured and rejected: csrc/experiments/ycge_taa_in_trace.hip.h; honoured only by
-// -DYCGE_EXPERIMENTS=1 builds): a block that finishes counts itself in at the blocks of its 3 x 3 neighbourhood, and whoever completes a
-// neighbourhood resolves its centre block.  block_ctr == null - always, in the product: TAA is a launch of its own behind the trace.
-struct TaaFuse {
-    uint32_t *block_ctr;                // [8x8 block of the frame] finished blocks of its neighbourhood, itself included; monotonic: a frame adds the neighbourhood's size
-    uint32_t *part_ctr;                 // [block] finished parts of a split block; the last part puts it back to 0
-    float *hist, *prev_normal, *prev_depth;
-    uint8_t *prev_sky;
-    TaaParams T;
-};
-
 struct TraceOut {
     // full-frame buffers (row-major x + y*hiW); with several GPUs only the owned tiles are written
     float *current_hdr;     // 3 f32 / px
@@ -301,7 +284,7 @@ struct TraceOut {
     // traversal-stack overflow area [level][global lane] and refraction path stack [slot][field][global lane]
     void *stack_spill;                  // uint2 entries {ref, tNear}
     uint32_t stack_lanes;
-    uint32_t lane_base;                 // first column of this launch (k_trace_fan runs beside k_trace)
+    uint32_t lane_base;                 // first column of this launch (0: every launch the library makes starts at column 0)
     float *path_stack;
     // per-wavefront profile of k_wf_primary (COUNT variant; may be null): 4 x u64 {start, end, node iters, leaf phases}
     unsigned long long *wave_prof;
@@ -316,10 +299,8 @@ struct TraceOut {
     // place then, and the next frame's trace (which waits for the value, hipStreamWaitValue32) gets what this launch leaves free
     uint32_t *placed_flag;
     uint32_t placed_value;
-    const uint32_t *n_fan;              // the first *n_fan schedule entries are traced by k_trace_fan (null or 0: none)
     // traversal counters (may be null): rays, box, tri, prim, vox
     unsigned long long *counters;
-    TaaFuse taa;                        // the single-launch kernels only
 };
 
 // planes a peer device copies from its own frame buffers into rank 0's (one process, several GPUs): its tiles only

@@ -17,7 +17,6 @@ void snapshot_frame(ycge_ctx *c, FrameState &fs)
     }
     fs.reset = false;
     fs.frame = ++c->frame_counter;
-    fs.fan_blocks = 0;
 }
 
 // How the longest-first schedule cuts blocks into parts.  policy, octal: digit c = log2(parts) a block of class c
@@ -117,12 +116,12 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
     // an event recorded on the stream is a packet of its own, and the one between the trace and TAA cost every such frame 8 us (round 6)
     // (only ev[1]: with ev[0] as the launch's start event and ev[2] as k_taa's stop event the frames got SLOWER again - config 4 0.5217 -> 0.5289 ms,
     // config 1 0.0845 -> 0.0885; recorded at the frame's two ends they wait behind nothing)
-    const bool kernel_stop = timed && !slab && !rt && !c->in_flight_call && frame_is_single_launch(c) && c->knobs.refill_steps == 0 && c->fan_cap == 0;
+    const bool kernel_stop = timed && !slab && !rt && !c->in_flight_call && frame_is_single_launch(c);
     if (timed) HIP_TRY(c, hipEventRecord(c->ev[0], stream));
     int e;
     O.stack_spill = rt ? rt->set->spill.p : c->spill_override ? c->spill_override : (slab && (fs.frame & 1)) ? c->stack_spill2.p : c->stack_spill.p;
     const uint32_t trace_lanes = (uint32_t)(c->n_owned > 0 ? c->n_owned : 1) * 256u * YCGE_SCHEDULE_SLACK;
-    O.stack_lanes = trace_lanes + c->fan_cap * 192u;
+    O.stack_lanes = trace_lanes;
     O.path_stack = c->path_stack.p;
     const int flat = scene_is_flat(c);
     // Path choice.  Refraction splits need TraceFull's per-pixel LIFO -> single launch.  Otherwise: scenes
@@ -141,7 +140,7 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
             fs.scheduled = O.block_order != nullptr;
             if (c->batch_collect) { c->batch_P.push_back(P); c->batch_O.push_back(O); return YCGE_OK; }      // (ycge_trace_tiles_resident_batch launches the frames of a batch together)
             if (launch_begin) HIP_TRY(c, hipEventRecord(launch_begin, stream));
-            e = ycge_launch_trace(&c->sd, &P, &O, c->cfg.count_work, flat, 0, stream);
+            e = ycge_launch_trace(&c->sd, &P, &O, c->cfg.count_work, flat, stream);
             if (launch_end) HIP_TRY(c, hipEventRecord(launch_end, stream));
             if (e != 0) return c->fail(YCGE_ERR_DEVICE, "trace launch failed: %s", hipGetErrorString((hipError_t)e));
             if (timed) HIP_TRY(c, hipEventRecord(c->ev[1], stream));
@@ -189,63 +188,27 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
         O.block_order = (lpt && c->block_order_valid) ? c->block_order.p : nullptr;
         O.n_order = c->order_ws.p + 16;
         }
-        const bool flight_order = O.block_order != nullptr && O.block_order != c->block_order.p;
-        // the schedule's head (the heaviest blocks of the previous frame) goes to k_trace_fan, launched first and beside k_trace
-        const int refill_steps = c->knobs.refill_steps;   // k_trace_refill: steps between refills (0 = k_trace)
-        // a schedule without fanned blocks (analytic scenes, small frames) skips k_trace_fan and the side stream altogether: the count
-        // comes back through pinned memory and is a frame or two old when read here - either answer traces every block exactly once,
-        // because k_trace is told (n_fan pointer or null) which convention this frame uses
-        const bool fan = O.block_order != nullptr && (!flight_order || deferred) && c->fan_cap > 0 && !(flat && refill_steps > 0) && c->h_n_fan && *(volatile uint32_t *)c->h_n_fan > 0;       // (schedules of ycge_render_frame_async have no fanned head)
         if (launch_begin) HIP_TRY(c, hipEventRecord(launch_begin, stream));       // (behind the wait for the schedule)
-        if (fan) {
-            fs.fan_blocks = *(volatile uint32_t *)c->h_n_fan;      // what the last finished schedule handed to k_trace_fan (this frame's may differ by a few)
-            // k_trace_fan goes FIRST and on the frame's stream, so that its blocks - the frame's longest chains - are resident from
-            // t = 0; the rest of the schedule follows on the side stream (forked before, joined after) and fills in around them
-            O.n_fan = O.n_order + 2;          // (word 18 of the schedule's work space, whichever buffer this frame reads)
-            TraceOut OF = O;
-            OF.lane_base = trace_lanes;
-            HIP_TRY(c, hipEventRecord(c->fan_ev[0], stream));
-            e = ycge_launch_trace_fan(&c->sd, &P, &OF, c->cfg.count_work, flat, c->fan_cap, stream);
-            if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_trace_fan launch failed: %s", hipGetErrorString((hipError_t)e));
-            HIP_TRY(c, hipStreamWaitEvent(c->fan_stream, c->fan_ev[0], 0));
-            e = ycge_launch_trace(&c->sd, &P, &O, c->cfg.count_work, flat, 0, c->fan_stream);
-            HIP_TRY(c, hipEventRecord(c->fan_ev[1], c->fan_stream));
-            HIP_TRY(c, hipStreamWaitEvent(stream, c->fan_ev[1], 0));
-        } else {
-            if (c->fuse_request && !slab && !rt && !c->in_flight_call && refill_steps == 0 && c->cfg.world_size == 1) {
-                const size_t nb = (size_t)c->n_tiles * 4;
-                if (c->taa_block_ctr.n != nb) {
-                    HIP_TRY(c, c->taa_block_ctr.alloc(nb)); HIP_TRY(c, c->taa_part_ctr.alloc(nb));
-                    HIP_TRY(c, hipMemsetAsync(c->taa_block_ctr.p, 0, nb * sizeof(uint32_t), stream)); HIP_TRY(c, hipMemsetAsync(c->taa_part_ctr.p, 0, nb * sizeof(uint32_t), stream));
-                }
-                O.taa.block_ctr = c->taa_block_ctr.p; O.taa.part_ctr = c->taa_part_ctr.p;
-                O.taa.hist = c->taa_hist.p; O.taa.prev_normal = c->prev_normal.p; O.taa.prev_depth = c->prev_depth.p; O.taa.prev_sky = c->prev_sky.p;
-                O.taa.T = c->fuse_T;
-                c->fuse_done = true;
-            }
-            e = ycge_launch_trace(&c->sd, &P, &O, c->cfg.count_work, flat, refill_steps, stream, nullptr, kernel_stop ? c->ev[1] : nullptr);
-        }
+        e = ycge_launch_trace(&c->sd, &P, &O, c->cfg.count_work, flat, stream, nullptr, kernel_stop ? c->ev[1] : nullptr);
         if (launch_end) HIP_TRY(c, hipEventRecord(launch_end, stream));
         if (e == 0 && flight) {
             // (frames in flight: the schedule of frame N + 2 follows this frame's TAA on the second stream, ycge_render_frame_async)
         } else if (e == 0 && deferred) {
             HIP_TRY(c, hipEventRecord(c->traced_ev, stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->fan_stream, c->traced_ev, 0));
-            e = ycge_launch_order_blocks(c->block_cost.p, n_blocks, policy, split_top, c->fan_class, c->fan_cap, (cost_slot + 2u) % YCGE_COST_FRAMES, 1u << ((cost_slot + 1u) % YCGE_COST_FRAMES),
-                                         c->flight_ws[fk].p, c->flight_order[fk].p, c->fan_stream, 0, 0, c->cost_snap.p);          // (the trace of frame N - 1 may still be writing its costs: a copy is read)
-            if (e == 0 && c->h_n_fan && c->fan_cap > 0) HIP_TRY(c, hipMemcpyAsync(c->h_n_fan, c->flight_ws[fk].p + 18, sizeof(uint32_t), hipMemcpyDeviceToHost, c->fan_stream));
-            HIP_TRY(c, hipEventRecord(c->flight_order_ev[fk], c->fan_stream));
+            HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->traced_ev, 0));
+            e = ycge_launch_order_blocks(c->block_cost.p, n_blocks, policy, split_top, (cost_slot + 2u) % YCGE_COST_FRAMES, 1u << ((cost_slot + 1u) % YCGE_COST_FRAMES),
+                                         c->flight_ws[fk].p, c->flight_order[fk].p, c->side_stream, 0, 0, c->cost_snap.p);          // (the trace of frame N - 1 may still be writing its costs: a copy is read)
+            HIP_TRY(c, hipEventRecord(c->flight_order_ev[fk], c->side_stream));
             c->flight_order_frame[fk] = fs.frame + 2;
         } else if (e == 0 && lpt) {
             // the next frame's schedule needs this frame's trace and nothing else: built on the side stream, beside TAA (or the slab
             // pack and all-gather), instead of 25 us in front of it; the next trace waits for it (order_ev)
             HIP_TRY(c, hipEventRecord(c->traced_ev, stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->fan_stream, c->traced_ev, 0));
-            e = ycge_launch_order_blocks(c->block_cost.p, n_blocks, policy, split_top, c->fan_class, c->fan_cap, (cost_slot + 1u) % YCGE_COST_FRAMES, 0u, c->order_ws.p, c->block_order.p, c->fan_stream);
+            HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->traced_ev, 0));
+            e = ycge_launch_order_blocks(c->block_cost.p, n_blocks, policy, split_top, (cost_slot + 1u) % YCGE_COST_FRAMES, 0u, c->order_ws.p, c->block_order.p, c->side_stream);
 
             c->block_order_valid = true;
-            if (e == 0 && c->h_n_fan && c->fan_cap > 0) HIP_TRY(c, hipMemcpyAsync(c->h_n_fan, c->order_ws.p + 18, sizeof(uint32_t), hipMemcpyDeviceToHost, c->fan_stream));
-            HIP_TRY(c, hipEventRecord(c->order_ev, c->fan_stream));
+            HIP_TRY(c, hipEventRecord(c->order_ev, c->side_stream));
             c->order_pending = true;
         }
     } else {
@@ -274,7 +237,7 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
         // the light loop of a round beside the trace of the next (ycge_launch_wavefront): on the side stream, with a spill area of its own
         // (not where the light loop has nothing to trace - every light dark, timed kernels - nor for the small frames of a burst in flight,
         // where the two stream hops cost more than the overlap gives: config 2 in flight 0.053 -> 0.056 ms, config 5 lit 5.12 -> 4.87)
-        const bool beside = !c->knobs.no_lights_beside && c->fan_stream && c->fan_ev[0] && c->fan_ev[1] && c->wf_rounds >= 2 && (c->any_light_lit || c->cfg.count_work) &&
+        const bool beside = !c->knobs.no_lights_beside && c->side_stream && c->side_ev[0] && c->side_ev[1] && c->wf_rounds >= 2 && (c->any_light_lit || c->cfg.count_work) &&
                             (!c->in_flight_call || c->n_owned >= 4096);
         TraceOut O_side = O;
         if (beside) {
@@ -283,7 +246,7 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
             O_side.stack_spill = side.p;
         }
         e = ycge_launch_wavefront(&c->sd, &P, &O, bufs, c->wf_rounds, c->has_grid ? 1 : 0, flat, c->cfg.count_work, pw, stream,
-                                  beside ? c->fan_stream : nullptr, beside ? c->fan_ev[0] : nullptr, beside ? c->fan_ev[1] : nullptr, beside ? &O_side : nullptr);
+                                  beside ? c->side_stream : nullptr, beside ? c->side_ev[0] : nullptr, beside ? c->side_ev[1] : nullptr, beside ? &O_side : nullptr);
         if (launch_end) HIP_TRY(c, hipEventRecord(launch_end, stream));
     }
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "trace launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -308,16 +271,14 @@ void taa_decide(ycge_ctx *c, FrameState &fs, TaaParams &T, bool &did_reset)
     did_reset = !c->taa_valid || fs.reset;                        // :285
     T.reset = did_reset ? 1 : 0;
 }
-// steps 5 and 9: TemporalBlendWithClamp + CommitCamera.  (fused: the trace launch resolved TAA itself - ycge::TaaFuse - and only the commit is left)
-int taa_and_commit(ycge_ctx *c, hipStream_t stream, FrameState &fs, bool &did_reset, bool timed, bool fused)
+// steps 5 and 9: TemporalBlendWithClamp + CommitCamera
+int taa_and_commit(ycge_ctx *c, hipStream_t stream, FrameState &fs, bool &did_reset, bool timed)
 {
     TaaParams T;
     taa_decide(c, fs, T, did_reset);
-    if (!fused) {
-        int e = ycge_launch_taa(&T, c->current_hdr.p, c->g_normal.p, c->g_depth.p, c->sky.p, c->taa_hist.p, c->prev_normal.p, c->prev_depth.p,
-                                c->prev_sky.p, stream, c->in_flight_taa ? 1 : 0);
-        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_taa launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
+    int e = ycge_launch_taa(&T, c->current_hdr.p, c->g_normal.p, c->g_depth.p, c->sky.p, c->taa_hist.p, c->prev_normal.p, c->prev_depth.p,
+                            c->prev_sky.p, stream, c->in_flight_taa ? 1 : 0);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_taa launch failed: %s", hipGetErrorString((hipError_t)e));
     if (timed) HIP_TRY(c, hipEventRecord(c->ev[2], stream));
     c->taa_valid = true;
     c->last_cam[0] = fs.pos[0]; c->last_cam[1] = fs.pos[1]; c->last_cam[2] = fs.pos[2]; c->last_yaw = fs.yaw; c->last_pitch = fs.pitch;   // :266
@@ -330,7 +291,6 @@ int fill_stats(ycge_ctx *c, ycge_frame_stats *st, const FrameState &fs, bool did
     std::memset(st, 0, sizeof *st);
     st->frame = fs.frame;
     st->history_reset = did_reset ? 1 : 0;
-    st->fan_blocks = (int32_t)fs.fan_blocks;
     float ms = 0.0f;
     HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     st->trace_ms = ms;
@@ -431,7 +391,6 @@ static int trace_on_all_devices(ycge_ctx *c, FrameState &fs)
         w.cv.wait(lk, [&] { return w.job == 2; });
         w.job = 0;
         if (w.rc != YCGE_OK && rc == YCGE_OK) { rc = w.rc; c->err = p->err; }
-        fs.fan_blocks += w.fs.fan_blocks;
     }
     if (rc != YCGE_OK) return rc;
     if (rccl) {
@@ -511,7 +470,7 @@ try {
     const bool single_launch = c->have_scene && frame_is_single_launch(c) && !c->sd.any_transparent;
     const bool stage_pair = c->have_scene && !frame_is_single_launch(c) && !c->sd.any_transparent && !c->knobs.no_flight_stage_overlap && c->n_owned >= 4096;      // (the stage pipeline with its second set of queues)
     out->two_trace_streams = (c->knobs.flight_overlap && c->stream2 && (single_launch || stage_pair)) ? 1 : 0;
-    out->placed_gate = (out->two_trace_streams && single_launch && c->knobs.flight_placed_gate && c->knobs.refill_steps == 0) ? 1 : 0;      // (only the single-launch kernels store the value)
+    out->placed_gate = (out->two_trace_streams && single_launch && c->knobs.flight_placed_gate) ? 1 : 0;      // (only the single-launch kernels store the value)
     out->post_gate = c->knobs.flight_post_gate ? 1 : 0;
     out->post_pair = (out->two_trace_streams && c->knobs.flight_post_pair) ? 1 : 0;
     out->frames_outstanding = c->async_outstanding ? 1 : 0;
@@ -596,8 +555,8 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
         // the first frame in flight after synchronous calls.  Whatever they left on the context's stream (a TAA, a post stage that reads
         // the current set) is ahead of this trace in stream order, and the second stream's first TAA waits for this trace.  The
         // synchronous schedule cleared THIS frame's cost slot; the next frame's would have been cleared between the two traces.
-        // ORDER matters here and must not depend on the placed-value gate (it may be off: YCGE_FLIGHT_PLACED_GATE=0, no signal memory,
-        // k_trace_refill): first the synchronous path's schedule still on the side stream (it writes the order buffer and its counters the
+        // ORDER matters here and must not depend on the placed-value gate (it may be off: YCGE_FLIGHT_PLACED_GATE=0, no signal memory):
+        // first the synchronous path's schedule still on the side stream (it writes the order buffer and its counters the
         // second stream's first trace reads), then the cost-slot clears, THEN the fork the second trace stream waits for.
         if (c->order_pending) { HIP_TRY(c, hipStreamWaitEvent(c->stream, c->order_ev, 0)); c->order_pending = false; }
         for (int ahead = 1; ahead <= 2; ahead++)        // (the schedules queued in flight clear the slot of the frame three ahead)
@@ -619,7 +578,7 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
     // ... and (two traces at a time) for the moment the trace before has PLACED its last workgroup: started earlier, this frame's heaviest
     // blocks take wavefront places from that frame's bulk - both frames' longest chains then start late - and started later the machine
     // idles.  The last workgroup of a trace launch stores the frame's sequence number; this stream waits for the value.
-    if (overlap_scene && c->knobs.flight_placed_gate && c->knobs.refill_steps == 0 /* (k_trace_refill stores no value) */) {
+    if (overlap_scene && c->knobs.flight_placed_gate) {
         if (!c->placed_flag) {
             // (a runtime without signal memory: no gate - the frames come out the same, a little later)
             if (hipExtMallocWithFlags((void **)&c->placed_flag, 8, hipMallocSignalMemory) != hipSuccess || hipMemset(c->placed_flag, 0, 8) != hipSuccess) {
@@ -630,7 +589,7 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
             c->placed_expect = 0; c->placed_next = 0;
         }
     }
-    if (overlap_scene && c->knobs.flight_placed_gate && c->knobs.refill_steps == 0 && c->placed_flag) {
+    if (overlap_scene && c->knobs.flight_placed_gate && c->placed_flag) {
         if (c->placed_expect) { HIP_TRY(c, hipStreamWaitValue32(ts, c->placed_flag, c->placed_expect, hipStreamWaitValueGte, 0xffffffffu)); c->placed_waits++; }
         c->placed_next = c->placed_expect + 1u;
         if (c->placed_next == 0u) c->placed_next = 1u;
@@ -661,7 +620,7 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
         const uint32_t in_flight = (1u << ((uint64_t)(fs.frame + 1) % YCGE_COST_FRAMES)) | (1u << ((uint64_t)(fs.frame + 2) % YCGE_COST_FRAMES));
         const uint32_t target = (uint32_t)((uint64_t)(fs.frame + 3) % YCGE_COST_FRAMES);
         const int fk = (int)((uint64_t)fs.frame % 3u);
-        const int e = ycge_launch_order_blocks(c->block_cost.p, n_blocks, policy, split_top, 0u, 0u, target, in_flight, c->flight_ws[fk].p, c->flight_order[fk].p, c->taa_stream, small ? 1 : 0, 0, c->cost_snap.p);       // (the trace of frame N - 1, on the other stream, may still be writing the slot this build reads and clears: a copy is read)
+        const int e = ycge_launch_order_blocks(c->block_cost.p, n_blocks, policy, split_top, target, in_flight, c->flight_ws[fk].p, c->flight_order[fk].p, c->taa_stream, small ? 1 : 0, 0, c->cost_snap.p);       // (the trace of frame N - 1, on the other stream, may still be writing the slot this build reads and clears: a copy is read)
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "schedule launch failed: %s", hipGetErrorString((hipError_t)e));
         c->flight_order_frame[fk] = fs.frame + 3;
         HIP_TRY(c, hipEventRecord(c->flight_order_ev[fk], c->taa_stream));
@@ -669,7 +628,7 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
     if (c->post_hist_pending) { HIP_TRY(c, hipStreamWaitEvent(c->taa_stream, c->post_hist_ev, 0)); c->post_hist_pending = false; }      // the post stage of the frame before reads the history this TAA rewrites
     bool did_reset = false;
     c->in_flight_taa = small;
-    rc = taa_and_commit(c, c->taa_stream, fs, did_reset, false, false);
+    rc = taa_and_commit(c, c->taa_stream, fs, did_reset, false);
     c->in_flight_taa = false;
     if (rc != YCGE_OK) return rc;
     if (post) {
@@ -715,17 +674,12 @@ int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *
     FrameState fs;
     snapshot_frame(c, fs);
     bool did_reset = false;
-    // (experiment builds, YCGE_TAA_FUSE=1: TemporalBlendWithClamp inside the trace launch where the frame is ONE launch on ONE device - ycge::TaaFuse; trace_frame decides and says so)
-    c->fuse_done = false;
-    c->fuse_request = c->knobs.taa_fuse && !multi_dev && c->cfg.taa_clamp_radius == 1;          // (the reference's call, RaytraceRenderer.cs:218: clampRadius 1 - the window the block resolve stages)
-    if (c->fuse_request) taa_decide(c, fs, c->fuse_T, did_reset);
     // (timing events only where the caller asks for statistics: an event between two kernels is a packet of its own that the next launch waits behind -
     // the C# wrapper passes no statistics and gets the frame without them; bench.py asks, its line is measured WITH them)
     const bool timed = st != nullptr;
     int rc = multi_dev ? trace_on_all_devices(c, fs) : trace_frame(c, nullptr, c->stream, fs, timed);
-    c->fuse_request = false;
     if (rc != YCGE_OK) return rc;
-    rc = taa_and_commit(c, c->stream, fs, did_reset, timed, c->fuse_done);
+    rc = taa_and_commit(c, c->stream, fs, did_reset, timed);
     if (rc != YCGE_OK) return rc;
     if (post) {      // steps 6-8; without them the frame stops after TAA (trace-only callers, benchmarks of the hot path)
         rc = run_post(c, c->stream, out_sdr, timed);
@@ -811,7 +765,7 @@ try {
     FrameState fs = c->pending.front();
     c->pending.pop_front();
     bool did_reset = false;
-    int rc = taa_and_commit(c, stream, fs, did_reset, st != nullptr, false);
+    int rc = taa_and_commit(c, stream, fs, did_reset, st != nullptr);
     if (rc != YCGE_OK) return rc;
     if (out_sdr) {
         rc = run_post(c, stream, out_sdr, st != nullptr);

@@ -34,9 +34,9 @@ int alloc_frame_buffers(ycge_ctx *c)
 // queue segments, hit records and stack-spill columns: one 256-entry segment per owned tile
 int alloc_tile_buffers(ycge_ctx *c)
 {
-    if (c->fan_stream) { HIP_TRY(c, hipStreamSynchronize(c->fan_stream)); c->order_pending = false; }      // schedule kernels of the old size
+    if (c->side_stream) { HIP_TRY(c, hipStreamSynchronize(c->side_stream)); c->order_pending = false; }      // schedule kernels of the old size
     const size_t lanes = (size_t)(c->n_owned > 0 ? c->n_owned : 1) * 256;
-    const size_t stack_lanes = lanes * YCGE_SCHEDULE_SLACK + (size_t)c->fan_cap * 192;      // k_trace's grid includes the schedule's slack entries; k_trace_fan's columns follow
+    const size_t stack_lanes = lanes * YCGE_SCHEDULE_SLACK;      // k_trace's grid includes the schedule's slack entries
     HIP_TRY(c, c->wf_q0.alloc(lanes * ycge_wf_sizes(0))); HIP_TRY(c, c->wf_q1.alloc(lanes * ycge_wf_sizes(0)));
     HIP_TRY(c, c->wf_hit.alloc(lanes * ycge_wf_sizes(1))); HIP_TRY(c, c->wf_lq.alloc(lanes * ycge_wf_sizes(2)));
     HIP_TRY(c, c->wf_seg.alloc(4));
@@ -386,7 +386,7 @@ static int create_one(const ycge_config *cfg, ycge_ctx *parent, ycge_ctx **out)
     for (auto &ev : c->ev)
         if (hipEventCreate(&ev) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(YCGE_ERR_DEVICE); }
     {
-        if (hipStreamCreateWithFlags(&c->fan_stream, hipStreamNonBlocking) != hipSuccess) { c->err = "hipStreamCreate failed"; return bail(YCGE_ERR_DEVICE); }
+        if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) { c->err = "hipStreamCreate failed"; return bail(YCGE_ERR_DEVICE); }
         if (c->cfg.world_size == 1 && c->cfg.n_devices <= 1) {
             // The second stream of the frames in flight (ycge_render_frame_async), created HERE, next to the other two: the runtime deals
             // streams onto a few hardware queues in order of creation, and a stream created later - after another context of the process
@@ -399,23 +399,8 @@ static int create_one(const ycge_config *cfg, ycge_ctx *parent, ycge_ctx **out)
                 hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&c->flight_fork_ev, hipEventDisableTiming) != hipSuccess) { c->err = "hipStreamCreate failed"; return bail(YCGE_ERR_DEVICE); }
         }
-        for (hipEvent_t *ev : {&c->fan_ev[0], &c->fan_ev[1], &c->traced_ev, &c->order_ev, &c->pushed_ev})
+        for (hipEvent_t *ev : {&c->side_ev[0], &c->side_ev[1], &c->traced_ev, &c->order_ev, &c->pushed_ev})
             if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(YCGE_ERR_DEVICE); }
-        // Query fan-out (k_trace_fan).  On a rank's share of a tiled frame wavefront slots are plentiful and the rank's time is the
-        // chain of its heaviest blocks: fan the classes >= 384 iterations (>= 256 from 4 ranks up), up to 2048 blocks (per rank on
-        // config 4: 0.565 -> 0.418 ms at 8 ranks, 0.562 -> 0.433 at 4, 0.595 -> 0.493 at 2).  On a whole frame slots are what the
-        // bulk is short of: only the 200 blocks at the head of the schedule (cost = max over four frames), with both kernels at 4
-        // wavefronts per SIMD (0.590 -> 0.569 ms; 400+ blocks or 3 wavefronts per SIMD lose what the shorter chains gain).
-        // Round 3: with the cooperative walk (ycge_coop.hip.h) a block's tail is short enough that on a WHOLE frame the helper wavefronts
-        // cost the bulk more than the shorter chains gain (config 4: 0.514 ms without fan-out, 0.547 with the 200 blocks): off there.
-        // The same holds on a rank's tiles once the heavy classes are split (trace_frame's default policy): per-rank trace on config 4
-        // at 8 ranks 0.359 ms with fan-out + the round-2 split, 0.289 ms with the round-3 split alone; at 4 ranks 0.381 -> 0.351; at 2
-        // ranks 0.485 -> 0.441 (profiles/r03/f_rank_emulation.txt).  k_trace_fan stays behind YCGE_FAN, parity-tested.
-        const uint32_t fan_default = 0u;
-        c->fan_class = c->knobs.fan_class >= 0 ? (uint32_t)c->knobs.fan_class : fan_default;
-        if (hipHostMalloc((void **)&c->h_n_fan, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { c->err = "hipHostMalloc failed"; return bail(YCGE_ERR_DEVICE); }
-        *c->h_n_fan = 0;
-        c->fan_cap = c->fan_class ? (c->knobs.fan_cap >= 0 ? (uint32_t)c->knobs.fan_cap : c->cfg.world_size >= 2 ? YCGE_FAN_CAP_DEFAULT : 200u) : 0u;
     }
     int rc = set_geometry(c, cfg->fb_width, cfg->fb_height, cfg->super_sample);
     if (rc != YCGE_OK) return bail(rc);
@@ -529,7 +514,7 @@ try {
     (void)hipSetDevice(c->device);
     // frames in flight may still be on ANY of the context's streams (TAA, post stage and read-back on taa_stream / stream2): everything
     // is drained before the first buffer goes (not left to hipFree's implicit synchronisation)
-    if (c->fan_stream) (void)hipStreamSynchronize(c->fan_stream);
+    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->taa_stream) (void)hipStreamSynchronize(c->taa_stream);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
@@ -538,7 +523,7 @@ try {
     c->current_hdr.release(); c->g_albedo.release(); c->g_normal.release(); c->g_depth.release(); c->taa_hist.release();
     c->prev_normal.release(); c->prev_depth.release(); c->sky.release(); c->prev_sky.release();
     c->dbg_rays.release(); c->dbg_hit_t.release(); c->dbg_prim.release(); c->dbg_sub.release(); c->dbg_rng.release();
-    c->counters.release(); c->wave_prof.release(); c->own_slab.release(); c->dbg_counters.release(); c->taa_block_ctr.release(); c->taa_part_ctr.release();
+    c->counters.release(); c->wave_prof.release(); c->own_slab.release(); c->dbg_counters.release();
     c->t_hdr.release(); c->t_albedo.release(); c->t_normal.release(); c->t_depth.release(); c->t_sky.release();
     if (c->taa_stream) { (void)hipStreamSynchronize(c->taa_stream); (void)hipStreamDestroy(c->taa_stream); c->taa_stream = nullptr; }
     if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); c->stream2 = nullptr; }
@@ -570,9 +555,8 @@ try {
     if (c->tex_order_ev) (void)hipEventDestroy(c->tex_order_ev);
     if (c->out_stage) { (void)hipHostFree(c->out_stage); c->out_stage = nullptr; c->out_stage_bytes = 0; }
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : {c->fan_ev[0], c->fan_ev[1], c->traced_ev, c->order_ev, c->pushed_ev}) if (ev) (void)hipEventDestroy(ev);
-    if (c->fan_stream) (void)hipStreamDestroy(c->fan_stream);
-    if (c->h_n_fan) (void)hipHostFree(c->h_n_fan);
+    for (hipEvent_t ev : {c->side_ev[0], c->side_ev[1], c->traced_ev, c->order_ev, c->pushed_ev}) if (ev) (void)hipEventDestroy(ev);
+    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

@@ -161,8 +161,6 @@ __device__ __forceinline__ uint32_t block_compact(bool want, uint32_t *s_cnt /* 
 #define YCGE_OUT_NT 1
 #endif
 template <class T> __device__ __forceinline__ void out_st(T *p, T v) { if (YCGE_OUT_NT) __builtin_nontemporal_store(v, p); else *p = v; }
-// ... or written THROUGH (device-coherent, sc1) where the launch itself reads them again on another XCD: the trace kernel's own TAA (TaaFuse)
-template <class T> __device__ __forceinline__ void out_st(T *p, T v, bool through) { if (through) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else out_st(p, v); }
 
 // ---------------------------------------------------------------------------------- k_wf_primary
 // one workgroup per owned 32x8 tile: the hardware dispatcher balances the (very uneven) tiles
@@ -816,47 +814,6 @@ __device__ __forceinline__ void taa_pixel(const TaaParams &T, const int x, const
 #define YCGE_ENT_BLOCK(e) ((e) & 0x3fffffu)
 #define YCGE_ENT_PART(e) (((e) >> 22) & 63u)
 #define YCGE_ENT_LG(e) ((e) >> 28)
-// Query fan-out (k_trace_fan): the heaviest blocks of the previous frame get THREE wavefronts.  The queries a
-// diffuse hit gives rise to - the first shadow segment towards each of the first two lit lights, and the bounce
-// ray - depend on the hit but not on each other (TraceFull only consumes them one after the other,
-// RaytraceRenderer.cs:578-616; the bounce direction is the next draw of the pixel's generator whatever the shadow
-// rays return), so the three wavefronts trace them side by side and wavefront 0 then runs TraceFull's loop over
-// the stored answers in the reference's order: same queries, same answers, same additions in the same order.  A
-// block's chain becomes  primary + max(shadow, shadow, bounce) + max(shadow, shadow)  instead of the sum of the six.
-// Every other query (path items of refractive hits, later transmittance segments, a third light) goes through
-// slot 0 one at a time.  Slots live in LDS; a stage boundary is one workgroup barrier.
-struct FanShared {
-    float o[3][64];             // origin of the lane's posted queries (the queries of one hit share it), xyz, lane
-    float q[3][6][64];          // slot, {d xyz, tmin (< 0: empty), tmax, any-hit flag}, lane
-    float r[3][3][64];          // slot, {t, prim, sub}, lane
-    uint32_t iters[3];          // traversal loop iterations per wavefront (summed into the block's cost)
-    int alive;
-    uint8_t list[192];          // refill mode: the posted queries, compacted (slot * 64 + lane)
-};
-// The same slots for ONE wavefront that traces a PART of a split block (trace_block MODE 3): at most 16 pixel lanes post, the wavefront's
-// 64 lanes answer - lane = slot * (pixels of the part) + pixel.  1.9 KB beside the 10 KB a k_trace wavefront holds anyway.
-struct FanPart {
-    float o[3][16];
-    float q[3][6][16];
-    float r[4][3][16];          // (answer slot 3: the bounce ray's, kept while slot 0 serves the queries that go one at a time)
-};
-template <class FS>
-__device__ __forceinline__ void fan_post(FS *F, int slot, int lane, F3 o, F3 d, float tmin, float tmax, bool anyhit)
-{
-    F->o[0][lane] = o.x; F->o[1][lane] = o.y; F->o[2][lane] = o.z;
-    F->q[slot][0][lane] = d.x; F->q[slot][1][lane] = d.y; F->q[slot][2][lane] = d.z;
-    F->q[slot][3][lane] = tmin; F->q[slot][4][lane] = tmax; F->q[slot][5][lane] = anyhit ? 1.0f : 0.0f;
-}
-template <class FS>
-__device__ __forceinline__ RayQ fan_query(const FS *F, int slot, int lane)
-{
-    RayQ q;
-    q.o = f3(F->o[0][lane], F->o[1][lane], F->o[2][lane]);
-    q.d = f3(F->q[slot][0][lane], F->q[slot][1][lane], F->q[slot][2][lane]);
-    q.tmin = F->q[slot][3][lane]; q.tmax = F->q[slot][4][lane];
-    q.anyhit = F->q[slot][5][lane] != 0.0f;
-    return q;
-}
 __device__ __forceinline__ uint32_t wave_umax(uint32_t v)
 {
     for (int off = 32; off >= 1; off >>= 1) { const uint32_t o2 = (uint32_t)__shfl_xor((int)v, off, 64); v = o2 > v ? o2 : v; }
@@ -882,58 +839,22 @@ __device__ __forceinline__ void shade_ctx_load(uint32_t addr, F3 &p, F3 &n, F3 &
     p = f3(v0.x, v0.y, v0.z); n = f3(v0.w, v1.x, v1.y); alb = f3(v1.z, v1.w, v2.x); wo = f3(v2.y, v2.z, v2.w);
 }
 
-#if YCGE_EXPERIMENTS
-} // namespace ycge
-#include "experiments/ycge_taa_in_trace.hip.h"
-namespace ycge {
-#endif
-#ifndef YCGE_PARTFAN
-// k_trace / k_trace_batch: 0 = round 5's loop (MODE 0), the product.  1 = MODE 3 for every entry, 2 = MODE 3 for the parts of split blocks and
-// MODE 0 for whole blocks (two copies of the loop in one kernel).  Round 6 built MODE 3 - the parts of split blocks fan their queries out over
-// their idle lanes - and measured it (profiles/r06/a_partfan.txt): a rank of 8 / 4 in the tile-resident ring 0.173 -> 0.157 / 0.267 -> 0.231 ms,
-// config 3 at 256 split blocks 0.280 -> 0.275 ms; config 4's whole frame LOSES (0.480 -> 0.499 ms at 32 split blocks, more with more: the
-// machine is within 15 % of full, every part is a wavefront slot, and MODE 3's loop runs whole blocks 4 % slower - 168 registers against 157).
-// And the build with MODE 3 in it dies with a GPU memory fault where two contexts trace on one device (test_one_call_drives_several_devices,
-// 9 of 9 runs; not with the register path alone, -DYCGE_PARTFAN_NOFAN=1, nor with the slots zeroed first, -DYCGE_PARTFAN_ZEROLDS=1): cause
-// not found.  Not in the product; the variants stay buildable for whoever follows it up.
-#define YCGE_PARTFAN 0
-#endif
-#ifndef YCGE_PARTFAN_COST_NUM
-#define YCGE_PARTFAN_COST_NUM 6  // quarters: the iterations a fanned part reports are scaled by this / 4 so that its block keeps its schedule class
-#endif
-// MODE 0: one wavefront per block, queries traced where TraceFull asks for them.
-// MODE 1: k_trace_fan, three wavefronts per block (see above).
-// MODE 2: k_trace_refill, ONE wavefront per block and the same posting of a hit's queries, but stage B is a refill loop:
-//         the block's posted queries (up to 192) form a list, a lane that finishes its query takes the next one whichever
-//         pixel it belongs to, and the walk yields every `refill_steps` steps so that idle lanes can do so.  A block then
-//         costs about max(its longest query, its steps / 64) per stage instead of the sum of the stage's longest lanes.
-// MODE 3: k_trace since round 6.  ONE wavefront per schedule entry as in MODE 0, and the query fan-out of MODE 1 INSIDE that wavefront
-//         where the entry is a PART of a split block (lg >= 2: at most 16 of the 64 lanes hold a pixel): the part's pixels post the
-//         queries of a diffuse hit - first shadow segment towards each of the first two lit lights, the bounce ray - into three slots
-//         and lane = slot * pixels + pixel answers them in ONE pass of the traversal loop, on lanes that idled before.  A part's chain
-//         becomes primary + max(shadow, shadow, bounce) + max(shadow, shadow) with no wavefront slot more than the split already took
-//         (k_trace_fan paid two helper wavefronts a block, which is why it lost on whole frames).  Entries that are whole blocks
-//         (lg < 2) run the same loop with the pixel's own query in registers: stage B traces `q`, stage A consumes - MODE 0's order.
-template <bool COUNT, bool FLAT, int MODE, bool FULLW = true, class FS = FanShared>
-__device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams &P, const TraceOut &O, const uint32_t ent, const uint32_t sched_index,
-                                            FS *F, const int refill_steps)
+// One wavefront per schedule entry; each lane runs TraceFull's work-item loop (RaytraceRenderer.cs:448-616) for its pixel and traces
+// the queries where the loop asks for them, one query a lane per trip, the whole wavefront walking together.  FULLW = false: the
+// instance for scenes without a mesh (no cooperative walk; lanes without a query stay out of it).  The query fan-out forms that once
+// shared this loop (three wavefronts a block, a refill list, the in-wave fan-out of split parts) were measured and retired: DESIGN.md 5.
+template <bool COUNT, bool FLAT, bool FULLW = true>
+__device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams &P, const TraceOut &O, const uint32_t ent, const uint32_t sched_index)
 {
-    constexpr bool FAN = MODE != 0;          // queries are posted to LDS slots and answered in stage B
-    constexpr bool WAVES3 = MODE == 1;
-    constexpr bool INW = MODE == 3;
     const bool DEBUG = O.prim_id != nullptr;
     Work w = {0, 0, 0, 0, 0, 0, 0};
-    StackT<WAVES3 ? 192 : 64> st;
+    StackT<64> st;
     st.init(O.stack_spill, O.stack_lanes, O.lane_base);
     const PathStack pstack = {O.path_stack, O.stack_lanes, O.lane_base};
-    const int lane = (int)(threadIdx.x & 63u), wave = WAVES3 ? (int)(threadIdx.x >> 6) : 0;
+    const int lane = (int)(threadIdx.x & 63u);
     const uint32_t bid = YCGE_ENT_BLOCK(ent), lg = YCGE_ENT_LG(ent);
     const int k = (int)(bid >> 2), wave_in_tile = (int)(bid & 3);
     const int live_lanes = 64 >> lg;
-#ifndef YCGE_PARTFAN_NOFAN
-#define YCGE_PARTFAN_NOFAN 0            // debugging aid: MODE 3's loop with every entry on the register path
-#endif
-    const bool fanrt = !INW || (lg >= 2u && !YCGE_PARTFAN_NOFAN);        // (wave-uniform) MODE 3: this entry fans its queries out over its idle lanes
     const int pix_in_block = (int)YCGE_ENT_PART(ent) * live_lanes + lane;
     int px, py, lx, ly;
     const bool in_image = tile_pixel_wl(P, k, wave_in_tile, pix_in_block & 63, px, py, lx, ly) && lane < live_lanes;
@@ -944,7 +865,7 @@ __device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams
     RayQ q;
     make_primary_ray(P, px, py, q.o, q.d);
     q.tmin = 0.001f; q.tmax = YCGE_FLT_MAX; q.anyhit = false;
-    if (in_image && O.rays && wave == 0) {
+    if (in_image && O.rays) {
         float *r = O.rays + ((size_t)px + (size_t)py * P.hiW) * 6;
         r[0] = q.o.x; r[1] = q.o.y; r[2] = q.o.z; r[3] = q.d.x; r[4] = q.d.y; r[5] = q.d.z;
     }
@@ -960,18 +881,13 @@ __device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams
     // (the pixel index goes through an empty asm at every use: otherwise the compiler computes the six 64-bit store addresses of a
     // pixel once, in the prologue, keeps them live through the whole kernel - and spills them)
     auto pixel_index = [&]() { int x = px, y = py; asm volatile("" : "+v"(x), "+v"(y)); return (size_t)x + (size_t)y * P.hiW; };
-#if YCGE_EXPERIMENTS
-    const bool fuse = !FAN && O.taa.block_ctr != nullptr;          // (wave-uniform) experiments/ycge_taa_in_trace.hip.h: this launch resolves TAA itself, the planes TAA reads are written through
-#else
-    constexpr bool fuse = false;
-#endif
     auto write_gbuffer = [&](F3 g_albedo, F3 g_normal, float g_depth, int g_prim, int g_sub, bool is_sky) {
         const size_t i = pixel_index();
         // (written once, read by TAA / the post stage after the launch: past the caches' keep lists, the tree stays in the L2s)
         out_st(O.g_albedo + 3 * i + 0, g_albedo.x); out_st(O.g_albedo + 3 * i + 1, g_albedo.y); out_st(O.g_albedo + 3 * i + 2, g_albedo.z);
-        out_st(O.g_normal + 3 * i + 0, g_normal.x, fuse); out_st(O.g_normal + 3 * i + 1, g_normal.y, fuse); out_st(O.g_normal + 3 * i + 2, g_normal.z, fuse);
-        out_st(O.g_depth + i, g_depth, fuse);
-        out_st(O.sky + i, (uint8_t)(is_sky ? 1 : 0), fuse);
+        out_st(O.g_normal + 3 * i + 0, g_normal.x); out_st(O.g_normal + 3 * i + 1, g_normal.y); out_st(O.g_normal + 3 * i + 2, g_normal.z);
+        out_st(O.g_depth + i, g_depth);
+        out_st(O.sky + i, (uint8_t)(is_sky ? 1 : 0));
         if (DEBUG) {
             if (O.prim_id) O.prim_id[i] = g_prim;
             if (O.sub_id) O.sub_id[i] = g_sub;
@@ -986,76 +902,28 @@ __device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams
     int light = 0;
     float tr_r = 1.0f, tr_g = 1.0f, tr_b = 1.0f, sh_maxdist = 0.0f;
     int tr_counter = 0;
-    int phase = (in_image && wave == 0) ? PH_PATH : PH_DONE;
-    // fan-out state (FAN only): `want` = where the answer to the pending query q is (slot 0-2, 3 = the bounce answer
-    // held in registers), parked = that answer is still to be traced by the next stage B
-    int want = 0, pre_l1 = -1, pre_l2 = -1, pre_b_prim = -1, pre_b_sub = 0;
-    float pre_b_t = 0.0f;
-    bool parked = FAN, pre_b = false, bounce_in_flight = false;
-    // the block's cost for the next frame's schedule: loop iterations its wavefront(s) spend in traversal = sum over the
-    // query batches of the longest lane's steps.  The same scale whether the block is fanned or not.
+    int phase = in_image ? PH_PATH : PH_DONE;
+    // the block's cost for the next frame's schedule: loop iterations its wavefront spends in traversal = sum over the
+    // query batches of the longest lane's steps
     uint32_t wave_iters = 0;
-    float ans_t = 0.0f;                     // MODE 3, whole-block entries: the answer to the lane's own query, from stage B to stage A
-    int ans_prim = -1, ans_sub = 0;
-#if defined(YCGE_PARTFAN_ZEROLDS)
-    if constexpr (INW) { for (int z = lane; z < (int)(sizeof(FS) / 4); z += 64) ((float *)F)[z] = 0.0f; }
-#endif
-    if (FAN && fanrt) {
-        if (WAVES3) F->q[wave][3][lane] = -1.0f;
-        else if (!INW || lane < live_lanes) { F->q[0][3][lane] = -1.0f; F->q[1][3][lane] = -1.0f; F->q[2][3][lane] = -1.0f; }
-        if (phase != PH_DONE) fan_post(F, 0, lane, q.o, q.d, q.tmin, q.tmax, false);      // the primary query
-    }
 
-    // what a block leaves behind when its last pixel is done (or handed over): the pixels, the schedule feedback, the profile record
-    auto finish_block = [&]() {
-    if (in_image) {                                     // :210-215
-        const size_t i = pixel_index();
-        out_st(O.current_hdr + 3 * i + 0, radiance.x, fuse); out_st(O.current_hdr + 3 * i + 1, radiance.y, fuse); out_st(O.current_hdr + 3 * i + 2, radiance.z, fuse);
-        if (DEBUG && O.rng_state) O.rng_state[i] = rng;
-    }
-#if YCGE_EXPERIMENTS
-    if (fuse) taa_in_trace(P, O, bid, lg, lane);
-#endif
-    // a part of a split block sees fewer lanes, hence fewer iterations than the whole block would: scaled so that the block
-    // stays in its schedule class from frame to frame (x 1.5 for 4 parts, x 2 for 16, x 2.5 for 64: measured ratios are 1.3-2)
-    uint32_t part_iters = wave_iters;
-    if constexpr (WAVES3) part_iters = F->iters[0] + F->iters[1] + F->iters[2];
-    // (MODE 3: a part that fans its queries out walks max(shadow, shadow, bounce) where the block walked their sum: x YCGE_PARTFAN_COST_NUM / 4 on top)
-    const uint32_t part_scaled = part_iters + ((part_iters * lg) >> 2);
-    const uint32_t wave_max_steps = (INW && fanrt) ? (part_scaled * YCGE_PARTFAN_COST_NUM) >> 2 : part_scaled;
-    if (O.block_cost && lane == 0) atomicMax(O.block_cost + bid, wave_max_steps);      // feedback for the next frame's schedule
-    if (prof && lane == 0 && YCGE_ENT_PART(ent) == 0) {
-        unsigned long long *dst = O.wave_prof + ((size_t)k * 4 + wave_in_tile) * 4;
-        dst[0] = t_start; dst[1] = __builtin_amdgcn_s_memrealtime(); dst[2] = sched_index | ((unsigned long long)wave_max_steps << 32);
-        dst[3] = __builtin_amdgcn_s_getreg(((32 - 1) << 11) | (0 << 6) | 20) | ((unsigned long long)(lg | (WAVES3 ? 8u : 0u)) << 32);   // XCC_ID; bit 3 = fanned block
-    }
-    };
-
-  for (;;) {          // FAN: one round = stage A (wavefront 0 consumes answers, posts queries) + stage B (all trace)
-   if (!FAN || wave == 0) {
     for (;;) {
         float t_hit = 0.0f;
         int hit_prim = -1, hit_sub = 0;
-        if (!__any(phase != PH_DONE && !parked)) break;
+        if (!__any(phase != PH_DONE)) break;
         const uint32_t steps_before = w.steps;
-        if (!FAN && !FULLW) {       // (the instance for scenes without a mesh: nothing to walk cooperatively, lanes without a query stay out)
+        if (!FULLW) {               // (the instance for scenes without a mesh: nothing to walk cooperatively, lanes without a query stay out)
             if (phase != PH_DONE) traverse<COUNT, true, FLAT, false>(S, q, st, t_hit, hit_prim, hit_sub, w);
-        } else if (!FAN) {         // every lane of the wavefront enters (the cooperative walk needs them all): finished pixels carry live = false
+        } else {                    // every lane of the wavefront enters (the cooperative walk needs them all): finished pixels carry live = false
             q.live = phase != PH_DONE;
             traverse<COUNT, true, FLAT, true>(S, q, st, t_hit, hit_prim, hit_sub, w);
-        } else if (phase != PH_DONE && !parked) {
-            if (INW && !fanrt) { t_hit = ans_t; hit_prim = ans_prim; hit_sub = ans_sub; }
-            else if (want == 3 && !INW) { t_hit = pre_b_t; hit_prim = pre_b_prim; hit_sub = pre_b_sub; }
-            else { t_hit = F->r[want][0][lane]; hit_prim = __float_as_int(F->r[want][1][lane]); hit_sub = __float_as_int(F->r[want][2][lane]); }
         }
-        if (!FAN) wave_iters += wave_umax(w.steps - steps_before);
-        if (phase == PH_DONE || parked) continue;
+        wave_iters += wave_umax(w.steps - steps_before);
+        if (phase == PH_DONE) continue;
         const bool hit = hit_prim >= 0;
         F3 sh_p, sh_n, sh_alb, sh_wo;
         if (phase != PH_PATH) shade_ctx_load(ctx_addr, sh_p, sh_n, sh_alb, sh_wo);      // a shadow query's answer: back to the hit it belongs to
         else { sh_p = sh_n = sh_alb = sh_wo = f3(0, 0, 0); }
-        int new_kind = 0;       // the next query: 1 = first shadow segment towards `light`, 2 = bounce, 0 = anything else
-        bool fanned = false;
 
         bool go_lights = false, go_next_light = false, go_contrib = false, go_next_item = false;
         if (phase == PH_PATH) {
@@ -1142,31 +1010,6 @@ __device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams
                     shade_ctx_store(ctx_addr, sh_p, sh_n, sh_alb, sh_wo);
                     light = 0;
                     go_lights = true;
-                    if (FAN && fanrt) { // post this hit's independent queries: the expressions of the light loop head and the bounce below
-                        int ns = 0;
-                        pre_l1 = pre_l2 = -1;
-                        pre_b = false;
-                        for (int li = 0; li < S.n_lights && ns < 2; li++) {
-                            const GLight &L = S.lights[li];
-                            F3 to_l = f3(L.pos) - sh_p;
-                            float dist2 = dot(to_l, to_l);
-                            float dist = cs_sqrt(dist2);
-                            F3 ldir = vdiv(to_l, dist);
-                            float n_dot_l = cs_max(0.0f, dot(sh_n, ldir));
-                            if (n_dot_l <= 0.0f) continue;
-                            if (light_is_dark<COUNT>(L, dist2, w)) continue;
-                            fan_post(F, 1 + ns, lane, sh_p + sh_n * P.eps, normalized(ldir), S.is_volume_scene ? 0.001f : 0.0f + P.eps, dist - P.eps, S.is_volume_scene || !S.any_transparent);
-                            if (ns == 0) pre_l1 = li; else pre_l2 = li;
-                            ns++;
-                        }
-                        if (diffuse_depth < P.diffuse_bounces) {
-                            uint64_t rng_peek = rng;        // the draw itself happens at the bounce, below
-                            F3 bounce = cosine_sample_hemisphere(sh_n, rng_peek);
-                            fan_post(F, 0, lane, sh_p + sh_n * P.eps, normalized(bounce), 0.001f, YCGE_FLT_MAX, false);
-                            bounce_in_flight = true;
-                        }
-                        fanned = ns > 0 || bounce_in_flight;
-                    }
                 }
             }
         } else if (phase == PH_SHADOW_OCC) {            // VolumeScene: binary occlusion, :761-765
@@ -1234,7 +1077,6 @@ __device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams
                 if (S.is_volume_scene) { q.tmin = 0.001f; phase = PH_SHADOW_OCC; }
                 else { q.tmin = 0.0f + P.eps; tr_r = tr_g = tr_b = 1.0f; tr_counter = 0; phase = PH_SHADOW_TR; }
                 queued = true;
-                new_kind = 1;
                 break;
             }
             if (!queued) {                              // bounce, :604-616
@@ -1250,7 +1092,6 @@ __device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams
                     beta = f3(beta.x * mult.x, beta.y * mult.y, beta.z * mult.z);
                     diffuse_depth++;
                     phase = PH_PATH;
-                    new_kind = 2;
                 } else {
                     go_next_item = true;
                 }
@@ -1269,120 +1110,23 @@ __device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams
                 phase = PH_PATH;
             }
         }
-
-        if (INW && !fanrt) parked = true;               // (a whole block: the query just set up waits in `q` for stage B)
-        else if (FAN && phase != PH_DONE) {             // where is the answer to the query just set up?
-            if (new_kind == 1 && light == pre_l1) { want = 1; pre_l1 = -1; }
-            else if (new_kind == 1 && light == pre_l2) { want = 2; pre_l2 = -1; }
-            else if (new_kind == 2 && (pre_b || bounce_in_flight)) { want = 3; pre_b = false; }
-            else { fan_post(F, 0, lane, q.o, q.d, q.tmin, q.tmax, q.anyhit); want = 0; parked = true; }
-            if (fanned) parked = true;
-        }
     }
-    if constexpr (WAVES3) { const bool alive = __any(phase != PH_DONE); if (lane == 0) F->alive = alive ? 1 : 0; }
-   }
-   if (!FAN) break;
-   if constexpr (WAVES3) {
-       __syncthreads();
-       if (!F->alive) break;
-       // ---- stage B: wavefront w answers slot w
-       const float f_tmin = F->q[wave][3][lane];
-       const uint32_t steps_before = w.steps;
-       {
-           RayQ fq = fan_query(F, wave, lane);
-           fq.live = f_tmin >= 0.0f;
-           float f_t; int f_prim, f_sub;
-           traverse<COUNT, true, FLAT, true>(S, fq, st, f_t, f_prim, f_sub, w);
-           if (fq.live) {
-           F->r[wave][0][lane] = f_t; F->r[wave][1][lane] = __int_as_float(f_prim); F->r[wave][2][lane] = __int_as_float(f_sub);
-           F->q[wave][3][lane] = -1.0f;
-           }
-       }
-       wave_iters += wave_umax(w.steps - steps_before);
-       __syncthreads();
-   } else if constexpr (INW) {
-       if (!__any(phase != PH_DONE)) break;
-       // ---- stage B inside the one wavefront: lane = slot * pixels + pixel answers that pixel's slot (a part), or its own query (a whole block)
-       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-       __builtin_amdgcn_wave_barrier();
-       const uint32_t steps_before = w.steps;
-       const int b_slot = lane >> (6 - (int)lg), b_src = lane & (live_lanes - 1);
-       const bool b_valid = fanrt && b_slot < 3;
-       // (`q` itself carries the slot's query through the walk - a second ray beside it cost the kernel its last free registers - and the
-       // pixel lanes take their pending query back from its slot afterwards: origin, direction, range, kind; tmin is set anew by whoever walks on)
-       q.live = phase != PH_DONE;
-       if (fanrt) {
-           q = fan_query(F, b_valid ? b_slot : 0, b_src);
-           q.live = b_valid && q.tmin >= 0.0f;
-       }
-       traverse<COUNT, true, FLAT, true>(S, q, st, ans_t, ans_prim, ans_sub, w);
-       if (fanrt) {
-           if (q.live) {
-               F->r[b_slot][0][b_src] = ans_t; F->r[b_slot][1][b_src] = __int_as_float(ans_prim); F->r[b_slot][2][b_src] = __int_as_float(ans_sub);
-               F->q[b_slot][3][b_src] = -1.0f;
-           }
-           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-           __builtin_amdgcn_wave_barrier();
-           if (phase != PH_DONE) q = fan_query(F, want == 3 ? 0 : want, lane);
-       }
-       wave_iters += wave_umax(w.steps - steps_before);
-   } else {
-#if YCGE_EXPERIMENTS
-       if (!__any(phase != PH_DONE)) break;
-       // ---- stage B: the posted queries as one list, lanes refill from it
-       uint32_t n = 0;
-       for (int sl = 0; sl < 3; sl++) {
-           const bool v = F->q[sl][3][lane] >= 0.0f;
-           const unsigned long long m = __ballot(v);
-           if (v) F->list[n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint8_t)(sl * 64 + lane);
-           n += (uint32_t)__popcll(m);
-       }
-       uint32_t next = 0;
-       bool has = false;
-       int id = 0;
-       FlatQuery fq;
-       RayQ rq;
-       rq.o = f3(0, 0, 0); rq.d = f3(0, 0, 1); rq.tmin = 0.0f; rq.tmax = 0.0f;
-       fq.cur = YCGE_REF_NONE_VALUE;
-       for (;;) {
-           const unsigned long long idle = __ballot(!has);
-           if (next < n && idle != 0ull) {
-               const uint32_t my = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-               if (!has && my < n) {
-                   id = (int)F->list[my];
-                   rq = fan_query(F, id >> 6, id & 63);
-                   flat_begin<COUNT>(S, rq, st, fq, w);
-                   has = true;
-               }
-               next += (uint32_t)__popcll(idle);
-           }
-           if (!__any(has)) break;
-           wave_iters += (uint32_t)refill_steps;
-           if (has && flat_advance<COUNT, true>(S, rq, st, fq, w, refill_steps)) {
-               const int sl = id >> 6, ln = id & 63;
-               F->r[sl][0][ln] = fq.closest; F->r[sl][1][ln] = __int_as_float(fq.hit_prim); F->r[sl][2][ln] = __int_as_float(fq.hit_sub);
-               F->q[sl][3][ln] = -1.0f;
-               has = false;
-           }
-       }
-#else
-       break;          // (MODE 2, k_trace_refill, exists in experiment builds only)
-#endif
-   }
-   parked = false;
-   if (bounce_in_flight) {      // slot 0 is needed for the queries that go one at a time: keep the bounce answer in registers (MODE 3: in a fourth answer slot)
-        if constexpr (INW) { F->r[3][0][lane] = F->r[0][0][lane]; F->r[3][1][lane] = F->r[0][1][lane]; F->r[3][2][lane] = F->r[0][2][lane]; }
-        else { pre_b_t = F->r[0][0][lane]; pre_b_prim = __float_as_int(F->r[0][1][lane]); pre_b_sub = __float_as_int(F->r[0][2][lane]); }
-        bounce_in_flight = false; pre_b = true;
-   }
-  }
 
-    if constexpr (WAVES3) {
-        if (lane == 0) F->iters[wave] = wave_iters;
-        __syncthreads();
-        if (wave != 0) { flush_work<COUNT>(w, O.counters); return; }
+    // what the block leaves behind: the pixels, the schedule feedback, the profile record
+    if (in_image) {                                     // :210-215
+        const size_t i = pixel_index();
+        out_st(O.current_hdr + 3 * i + 0, radiance.x); out_st(O.current_hdr + 3 * i + 1, radiance.y); out_st(O.current_hdr + 3 * i + 2, radiance.z);
+        if (DEBUG && O.rng_state) O.rng_state[i] = rng;
     }
-    finish_block();
+    // a part of a split block sees fewer lanes, hence fewer iterations than the whole block would: scaled so that the block
+    // stays in its schedule class from frame to frame (x 1.5 for 4 parts, x 2 for 16, x 2.5 for 64: measured ratios are 1.3-2)
+    const uint32_t wave_max_steps = wave_iters + ((wave_iters * lg) >> 2);
+    if (O.block_cost && lane == 0) atomicMax(O.block_cost + bid, wave_max_steps);      // feedback for the next frame's schedule
+    if (prof && lane == 0 && YCGE_ENT_PART(ent) == 0) {
+        unsigned long long *dst = O.wave_prof + ((size_t)k * 4 + wave_in_tile) * 4;
+        dst[0] = t_start; dst[1] = __builtin_amdgcn_s_memrealtime(); dst[2] = sched_index | ((unsigned long long)wave_max_steps << 32);
+        dst[3] = __builtin_amdgcn_s_getreg(((32 - 1) << 11) | (0 << 6) | 20) | ((unsigned long long)lg << 32);   // XCC_ID
+    }
     flush_work<COUNT>(w, O.counters);
 }
 
@@ -1394,36 +1138,23 @@ __device__ __forceinline__ void trace_block(const SceneDev &S, const FrameParams
 #ifndef YCGE_TRACE_WAVES
 #define YCGE_TRACE_WAVES 3
 #endif
-#ifndef YCGE_FAN_WAVES
-#define YCGE_FAN_WAVES 3        // k_trace_fan: no register cap below its natural ~150 (a fanned block's three wavefronts are latency chains, not throughput)
-#endif
 template <bool COUNT, bool FLAT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FLAT && !COUNT) ? YCGE_TRACE_WAVES : 2, 8))) void k_trace(const SceneDev S, const FrameParams P, const TraceOut O)
 {
     if (O.placed_flag && blockIdx.x == gridDim.x - 1u && threadIdx.x == 0) __hip_atomic_store(O.placed_flag, O.placed_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     uint32_t idx = blockIdx.x, ent = blockIdx.x;
     if (O.block_order) {
-        if (O.n_fan) idx += *O.n_fan;           // the first n_fan entries belong to k_trace_fan
         if (idx >= *O.n_order) return;
         ent = O.block_order[idx];
     } else if (blockIdx.x >= (uint32_t)P.n_owned_tiles * 4u) return;
-#if YCGE_PARTFAN == 2      // parts through MODE 3, whole blocks through round 5's MODE 0: two copies of the loop in one kernel (A/B)
-    __shared__ FanPart F;
-    if (YCGE_ENT_LG(ent) >= 2u) trace_block<COUNT, FLAT, 3, true, FanPart>(S, P, O, ent, idx, &F, 0);
-    else trace_block<COUNT, FLAT, 0>(S, P, O, ent, idx, (FanShared *)nullptr, 0);
-#elif YCGE_PARTFAN
-    __shared__ FanPart F;
-    trace_block<COUNT, FLAT, 3, true, FanPart>(S, P, O, ent, idx, &F, 0);
-#else
-    trace_block<COUNT, FLAT, 0>(S, P, O, ent, idx, (FanShared *)nullptr, 0);
-#endif
+    trace_block<COUNT, FLAT>(S, P, O, ent, idx);
 }
 // SEVERAL frames' blocks in one launch (ycge_trace_tiles_resident_batch: a rank's tiles of n consecutive frames): workgroup b traces
 // schedule entry b / n of frame b % n - the frames share one schedule, so the heaviest blocks of every frame go first - with that frame's
 // parameters and outputs (records in the launch's own arguments, read with scalar loads: the index is wave-uniform).  What one frame's launch leaves
 // idle around its longest chains, the other frames' blocks fill without any help from the queues.  The frames' TraceOut records share ONE
 // spill area n times as wide (the column is the workgroup's index in the launch).
-struct TraceBatch { FrameParams P[YCGE_TRACE_BATCH_MAX]; TraceOut O[YCGE_TRACE_BATCH_MAX]; };        // kernel ARGUMENT (2.7 KB of the 4 KB a launch may carry): nothing to stage, nothing a host that runs ahead could overwrite
+struct TraceBatch { FrameParams P[YCGE_TRACE_BATCH_MAX]; TraceOut O[YCGE_TRACE_BATCH_MAX]; };        // kernel ARGUMENT (8 x (160 + 168) B = 2.6 KB, 2.9 KB with the SceneDev beside it, of the 4 KB a launch may carry): nothing to stage, nothing a host that runs ahead could overwrite
 template <bool COUNT, bool FLAT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FLAT && !COUNT) ? YCGE_TRACE_WAVES : 2, 8))) void k_trace_batch(const SceneDev S, const TraceBatch B, const uint32_t n)
 {
@@ -1435,16 +1166,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FLAT && !CO
         if (idx >= *O.n_order) return;
         ent = O.block_order[idx];
     } else if (i >= (uint32_t)P.n_owned_tiles * 4u) return;
-#if YCGE_PARTFAN == 2      // parts through MODE 3, whole blocks through round 5's MODE 0: two copies of the loop in one kernel (A/B)
-    __shared__ FanPart F;
-    if (YCGE_ENT_LG(ent) >= 2u) trace_block<COUNT, FLAT, 3, true, FanPart>(S, P, O, ent, idx, &F, 0);
-    else trace_block<COUNT, FLAT, 0>(S, P, O, ent, idx, (FanShared *)nullptr, 0);
-#elif YCGE_PARTFAN
-    __shared__ FanPart F;
-    trace_block<COUNT, FLAT, 3, true, FanPart>(S, P, O, ent, idx, &F, 0);
-#else
-    trace_block<COUNT, FLAT, 0>(S, P, O, ent, idx, (FanShared *)nullptr, 0);
-#endif
+    trace_block<COUNT, FLAT>(S, P, O, ent, idx);
 }
 // The same kernel for scenes WITHOUT a mesh (nothing to walk cooperatively: the treelet code is compiled out and, with it, the register
 // peak): 125 registers, 4 wavefronts per SIMD - analytic scenes are throughput, not chains (config 2: 0.082 ms at 3 wavefronts, 0.068 at 4).
@@ -1453,42 +1175,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     if (O.placed_flag && blockIdx.x == gridDim.x - 1u && threadIdx.x == 0) __hip_atomic_store(O.placed_flag, O.placed_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     uint32_t idx = blockIdx.x, ent = blockIdx.x;
     if (O.block_order) {
-        if (O.n_fan) idx += *O.n_fan;
         if (idx >= *O.n_order) return;
         ent = O.block_order[idx];
     } else if (blockIdx.x >= (uint32_t)P.n_owned_tiles * 4u) return;
-    trace_block<false, true, 0, false>(S, P, O, ent, idx, (FanShared *)nullptr, 0);
-}
-#if YCGE_EXPERIMENTS
-template <bool COUNT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(COUNT ? 2 : 3, 8))) void k_trace_refill(const SceneDev S, const FrameParams P, const TraceOut O, const int refill_steps)
-{
-    __shared__ FanShared F;
-    uint32_t idx = blockIdx.x, ent = blockIdx.x;
-    if (O.block_order) {
-        if (idx >= *O.n_order) return;
-        ent = O.block_order[idx];
-    } else if (blockIdx.x >= (uint32_t)P.n_owned_tiles * 4u) return;
-    trace_block<COUNT, true, 2>(S, P, O, ent, idx, &F, refill_steps);
-}
-#endif
-template <bool COUNT, bool FLAT>
-__global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu((FLAT && !COUNT) ? YCGE_FAN_WAVES : 2, 8))) void k_trace_fan(const SceneDev S, const FrameParams P, const TraceOut O)
-{
-    __shared__ FanShared F;
-    if (blockIdx.x >= *O.n_fan) return;
-    trace_block<COUNT, FLAT, 1>(S, P, O, O.block_order[blockIdx.x], blockIdx.x, &F, 0);
+    trace_block<false, true, false>(S, P, O, ent, idx);
 }
 
 // ---------------------------------------------------------------------------------- block schedule (feedback from the previous frame)
 // cost[b] = traversal loop iterations of block b's wavefront(s) (trace_block).  Eight POLICY classes, finer towards the top
-// (class 7 = longest): < 64, < 128, < 192, < 256, < 384, < 512, < 768, more - what the fan-out / split knobs speak of - and 32
+// (class 7 = longest): < 64, < 128, < 192, < 256, < 384, < 512, < 768, more - what the split knob speaks of - and 32
 // ORDER classes nested inside them (order_class), finer towards the bottom too: the schedule is written order class by order class,
 // longest first.  (With eight classes everything below 64 iterations - nine blocks in ten, up to ~90 us each - came in index order,
 // and the frame drained for 0.1 ms behind 100-us blocks that had started last: round 3.)  k_cost_hist counts entries per order class,
 // k_cost_scatter writes the schedule and clears cost[] for the next frame's atomicMax; both batch their global atomics through LDS.
-// ws: [16] total entries (read by k_trace), [18] = entries at the head of the schedule that go to k_trace_fan,
-//     [32..63] entries per order class, [64..95] cursors
+// ws: [16] total entries (read by k_trace), [32..63] entries per order class, [64..95] cursors
 #define YCGE_ORDER_CLASSES 32
 __device__ __forceinline__ int cost_class(uint32_t c)
 {
@@ -1568,7 +1268,7 @@ __device__ __forceinline__ ClassLayout class_layout(const uint32_t *ws, int cls,
 // outside their class's range (holes of stale entries, writes past the list): where traces may still be writing costs while the schedule
 // is built (traces in flight), both kernels read a snapshot of the ring (ycge_launch_order_blocks) and `clear` is the live ring.
 __global__ __launch_bounds__(1024) void k_cost_scatter(const uint32_t *__restrict__ cost, uint32_t *__restrict__ clear, uint32_t n, uint32_t capacity, uint32_t policy, uint32_t split_top,
-                                                       uint32_t fan_class, uint32_t fan_cap, uint32_t next_slot, uint32_t skip_mask, uint32_t n_frames, uint32_t *__restrict__ ws, uint32_t *__restrict__ order)
+                                                       uint32_t next_slot, uint32_t skip_mask, uint32_t n_frames, uint32_t *__restrict__ ws, uint32_t *__restrict__ order)
 {
     __shared__ uint32_t h[YCGE_ORDER_CLASSES], rank0[YCGE_ORDER_CLASSES];
     __shared__ ClassLayout lay[YCGE_ORDER_CLASSES];
@@ -1577,16 +1277,7 @@ __global__ __launch_bounds__(1024) void k_cost_scatter(const uint32_t *__restric
     if (threadIdx.x == 0) {     // every workgroup derives the same decision from the finished histogram
         const ClassLayout all = class_layout(ws, -1, policy, split_top, true);         // (cls = -1: the sums over every class)
         s_split = all.entries_before <= capacity ? 1u : 0u;
-        if (blockIdx.x == 0) {
-            ws[16] = s_split ? all.entries_before : n;
-            uint32_t n_fan = 0;                 // entries of the policy classes >= fan_class, at the head of the schedule
-            if (fan_class > 0) {
-                int lowest = YCGE_ORDER_CLASSES;
-                while (lowest > 0 && policy_class_of_order_class(lowest - 1) >= (int)fan_class) lowest--;
-                if (lowest < YCGE_ORDER_CLASSES) { const ClassLayout f = class_layout(ws, lowest - 1, policy, split_top, s_split != 0); n_fan = f.entries_before; }
-            }
-            ws[18] = n_fan < fan_cap ? n_fan : fan_cap;
-        }
+        if (blockIdx.x == 0) ws[16] = s_split ? all.entries_before : n;
     }
     __syncthreads();
     const bool split = s_split != 0;
@@ -1809,19 +1500,11 @@ size_t ycge_wf_sizes(int which)
 // (start / stop: events that take the KERNEL's own begin and end times - hipExtLaunchKernelGGL hangs it on the dispatch's completion signal, so nothing stands
 // between this launch and the next one on the stream; an event recorded behind the launch is a packet of its own that the next launch waits
 // behind: 8 us of every synchronous frame, round 6)
-int ycge_launch_trace(const ycge::SceneDev *S, const ycge::FrameParams *P, const ycge::TraceOut *O, int count, int flat, int refill_steps,
-                      hipStream_t stream, hipEvent_t start, hipEvent_t stop)
+int ycge_launch_trace(const ycge::SceneDev *S, const ycge::FrameParams *P, const ycge::TraceOut *O, int count, int flat, hipStream_t stream, hipEvent_t start, hipEvent_t stop)
 {
     using namespace ycge;
     if (P->n_owned_tiles <= 0) return 0;
     const dim3 grid((unsigned)P->n_owned_tiles * 4u * YCGE_SCHEDULE_SLACK), block(64);   // schedule capacity; idle entries exit at once
-#if YCGE_EXPERIMENTS
-    if (flat && refill_steps > 0) {
-        if (count) hipLaunchKernelGGL((k_trace_refill<true>), grid, block, 0, stream, *S, *P, *O, refill_steps);
-        else hipLaunchKernelGGL((k_trace_refill<false>), grid, block, 0, stream, *S, *P, *O, refill_steps);
-        return (int)hipGetLastError();
-    }
-#endif
     static const unsigned lds_pad = getenv("YCGE_LDS_PAD") ? (unsigned)atoi(getenv("YCGE_LDS_PAD")) : 0u;   // experiment knob: fewer resident wavefronts
     if (!count && flat && S->tl_offset == 0u) {         // no mesh (or the cooperative walk switched off): the lean instance
         if (stop) hipExtLaunchKernelGGL(k_trace_nomesh, grid, block, lds_pad, stream, start, stop, 0, *S, *P, *O);
@@ -1905,8 +1588,8 @@ int ycge_launch_wavefront(const ycge::SceneDev *S, const ycge::FrameParams *P, c
     return (int)hipGetLastError();
 }
 
-// builds next frame's k_trace schedule from this frame's per-block step counts.  ws: 18 uint32 (see k_cost_hist)
-int ycge_launch_order_blocks(uint32_t *cost, uint32_t n, uint32_t policy, uint32_t split_top, uint32_t fan_class, uint32_t fan_cap, uint32_t next_slot, uint32_t skip_mask,
+// builds next frame's k_trace schedule from this frame's per-block step counts.  ws: 96 uint32 (see k_cost_hist)
+int ycge_launch_order_blocks(uint32_t *cost, uint32_t n, uint32_t policy, uint32_t split_top, uint32_t next_slot, uint32_t skip_mask,
                              uint32_t *ws, uint32_t *order, hipStream_t stream, int small_groups, uint32_t n_frames, uint32_t *snap)
 {
     if (n == 0) return 0;
@@ -1924,23 +1607,11 @@ int ycge_launch_order_blocks(uint32_t *cost, uint32_t n, uint32_t policy, uint32
     // small_groups (frames in flight): a 1024-thread workgroup needs a quarter of a CU cleared before it starts and so waited for the
     // last third of the trace running beside it; four wavefronts find room far sooner (one-wavefront groups were no better)
     const unsigned threads = small_groups ? 256u : 1024u;
-    hipError_t e = hipMemsetAsync(ws, 0, 96 * sizeof(uint32_t), stream);     // ws[16] / ws[18] (entries, n_fan) are rewritten by k_cost_scatter before anyone reads them
+    hipError_t e = hipMemsetAsync(ws, 0, 96 * sizeof(uint32_t), stream);     // ws[16] (entries) is rewritten by k_cost_scatter before anyone reads it
     if (e != hipSuccess) return (int)e;
     const dim3 grid((n + threads - 1u) / threads), block(threads);
     hipLaunchKernelGGL(ycge::k_cost_hist, grid, block, 0, stream, read, n, skip_mask, n_frames, ws);
-    hipLaunchKernelGGL(ycge::k_cost_scatter, grid, block, 0, stream, read, cost, n, n * YCGE_SCHEDULE_SLACK, policy, split_top, fan_class, fan_cap, next_slot, skip_mask, n_frames, ws, order);
-    return (int)hipGetLastError();
-}
-
-// the fanned blocks of the schedule (see k_trace_fan); grid = the cap the schedule was built with
-int ycge_launch_trace_fan(const ycge::SceneDev *S, const ycge::FrameParams *P, const ycge::TraceOut *O, int count, int flat, uint32_t fan_cap,
-                          hipStream_t stream)
-{
-    using namespace ycge;
-    if (P->n_owned_tiles <= 0 || fan_cap == 0) return 0;
-    sel3(count != 0, flat != 0, false, [&](auto C, auto F, auto) {
-        hipLaunchKernelGGL((k_trace_fan<decltype(C)::value, decltype(F)::value>), dim3(fan_cap), dim3(192), 0, stream, *S, *P, *O);
-    });
+    hipLaunchKernelGGL(ycge::k_cost_scatter, grid, block, 0, stream, read, cost, n, n * YCGE_SCHEDULE_SLACK, policy, split_top, next_slot, skip_mask, n_frames, ws, order);
     return (int)hipGetLastError();
 }
 

@@ -392,35 +392,26 @@ __global__ __launch_bounds__(32 * G) void k_atrous_band(const AtrousParams A, fl
     }
 }
 
-// The whole in-place iteration in ONE launch: a workgroup per band walks all of its level groups; before a group it waits for the
-// band above to have finished the same group (progress[band] = epoch + groups finished, one 128-byte line per band), after it the
-// new colours go out and the count goes up.  The launch form pays a kernel boundary per group AND lets a band start a group only a
-// whole launch after its neighbour (8 levels of skew per band where the stencil needs 12 levels of offset anyway: 135 x 8 + 2 581
-// level times); here a band trails its neighbour by what the data needs.  What makes it possible without cache-wide fences
-// (a buffer_wbl2 / buffer_inv pair per group cost more than the launches, round 1): colours are stored write-through and loaded
-// with device-coherent loads (sc1), which cost 25 ns more than plain ones when the line is in L2 (profiles/micro/ldflavour.hip)
-// and are never stale (profiles/micro/xcdvis.hip).  Why the order is right: as in k_atrous_band - a tap in the band above is
-// earlier in scan order and has a smaller level, hence a group <= this one, finished and published before this group starts; a
-// tap in the band below must be read OLD, and that band does not start the group that rewrites it before this band has published
-// the same group.  All bands must be resident at once (one workgroup each; the host checks the count against the chip).
-// xcd_local: band = (block % 8) * per_xcd + block / 8 keeps neighbouring bands on one XCD under round-robin dispatch (their
-// colours then meet in one L2); correctness does not depend on where a workgroup lands.
-#if YCGE_EXPERIMENTS
-} // namespace ycge
-#include "experiments/ycge_atrous_persist_groups.hip.h"
-namespace ycge {
-#endif
-
-// The persistent form with LEVEL-granular hand-over.  In k_atrous_persist a band starts a group when the band above has FINISHED
-// the same group: it trails by a group plus the hand-over, like the launch form.  The data needs far less - a pixel of level T
-// reads the band above up to level T - 1.  Here the LDS window is never cleared (an entry is reused 64 columns = 32 levels
-// later, a tap reaches 8 levels back) and one extra wavefront per workgroup PUBLISHES: after the barrier of pass i it copies the
-// colours that pass wrote from the window to memory (written through), waits for its own stores - off the computing wavefronts'
-// chain, which a write-through acknowledgement (0.4 us) or a device-coherent load of a cold line (1.3 us) would lengthen by a
-// third each (measured with YCGE_POST_DBG) - and raises progress[band] = epoch + (the first level this band has NOT completed).
+// The whole in-place iteration in ONE launch: a workgroup per band walks all of its levels.  The launch form pays a kernel boundary
+// per group AND lets a band start a group only a whole launch after its neighbour (8 levels of skew per band where the stencil needs
+// 12 levels of offset anyway: 135 x 8 + 2 581 level times); here a band trails its neighbour by what the data needs - a pixel of
+// level T reads the band above up to level T - 1.  (Handing over per level GROUP instead trails by a group plus the hand-over, like
+// the launch form: measured and retired, NOTEBOOK.md.)  What makes it possible without cache-wide fences (a buffer_wbl2 / buffer_inv
+// pair per group cost more than the launches, round 1): colours are stored write-through and loaded with device-coherent loads
+// (sc1), which cost 25 ns more than plain ones when the line is in L2 (profiles/micro/ldflavour.hip) and are never stale
+// (profiles/micro/xcdvis.hip).  The LDS window is never cleared (an entry is reused 64 columns = 32 levels later, a tap reaches 8
+// levels back) and one extra wavefront per workgroup PUBLISHES: after the barrier of pass i it copies the colours that pass wrote
+// from the window to memory (written through), waits for its own stores - off the computing wavefronts' chain, which a
+// write-through acknowledgement (0.4 us) or a device-coherent load of a cold line (1.3 us) would lengthen by a third each (measured
+// with YCGE_POST_DBG) - and raises progress[band] = epoch + (the first level this band has NOT completed), one 128-byte line per band.
 // A band fetches the taps of level T (one pass ahead of computing them) once the band above has published >= T; it reads that
 // word one pass ahead as well, so in the steady state nothing waits.  Only the taps ABOVE the band are read device-coherently:
-// what the band rewrote itself comes from the window, everything else it reads is old and right in any cache.
+// what the band rewrote itself comes from the window, everything else it reads is old and right in any cache.  Why the order is
+// right: as in k_atrous_band - a tap in the band above is earlier in scan order and has a smaller level, published before this
+// band fetches it; a tap in the band below must be read OLD, and that band does not compute the level that rewrites it before
+// this band has published that level.  All bands must be resident at once (one workgroup each; the host checks the count against
+// the chip).  xcd_local: band = (block % 8) * per_xcd + block / 8 keeps neighbouring bands on one XCD under round-robin dispatch
+// (their colours then meet in one L2); correctness does not depend on where a workgroup lands.
 template <int G, bool PROF, bool DUO = false>
 __global__ __launch_bounds__(32 * G + 64) void k_atrous_stream(const AtrousParams A, float *__restrict__ buf, const float *__restrict__ statw,
                                                                const uint8_t *__restrict__ sky, const uint32_t *__restrict__ pixels,
@@ -1176,61 +1167,41 @@ int ycge_launch_atrous_inplace(int w, int h, int step, const float phi[4], float
     return (int)hipGetLastError();
 }
 
-// the same iteration as ONE persistent launch (k_atrous_persist).  progress: n_bands x 32 words, zero before the first use; epoch: a
-// value that grows by more than the group count from call to call (the host's running sum)
+// the same iteration as ONE persistent launch (k_atrous_stream).  progress: n_bands x 32 words, zero before the first use; epoch: a
+// value that grows by more than the level count from call to call (the host's running sum)
 // Unused dynamic LDS of the two-set instantiation: the only way to tell the dispatcher "at most N band workgroups on a CU"
 static int g_duo_pad_lds = 0;
 void ycge_atrous_duo_pad_lds(int bytes) { g_duo_pad_lds = bytes > 0 ? bytes : 0; }
 
 int ycge_launch_atrous_persist(int w, int h, int step, const float phi[4], float *buf, const uint8_t *sky, float *statw, const uint32_t *d_pixels,
-                               const uint32_t *d_offsets, const uint32_t *d_pass_level, const int32_t *d_band_desc, int n_levels, int n_bands, int K, int groups_per_pass, int rows_per_band, unsigned window_width,
-                               uint32_t *progress, uint32_t epoch, int xcd_local, int level_handover, int profile, uint32_t ticket_base, hipStream_t stream)
+                               const uint32_t *d_offsets, const uint32_t *d_pass_level, const int32_t *d_band_desc, int n_levels, int n_bands, int groups_per_pass, int rows_per_band, unsigned window_width,
+                               uint32_t *progress, uint32_t epoch, int xcd_local, int profile, uint32_t ticket_base, hipStream_t stream)
 {
     ycge::AtrousParams A = {w, h, step, phi[0], phi[1], phi[2], phi[3]};
     const int per_xcd = (n_bands + 7) / 8;
     const dim3 grid((unsigned)((xcd_local & 1) ? 8 * per_xcd : n_bands));
-    if (level_handover) {       // 8 or 16 pixels a pass: the publishing wavefront is the workgroup's 5th or 9th
-        if (groups_per_pass == 8) hipLaunchKernelGGL((ycge::k_atrous_stream<8, false>), grid, dim3(256 + 64), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
-        else if (groups_per_pass == 16 && d_band_desc && !profile) hipLaunchKernelGGL((ycge::k_atrous_stream<16, false, true>), grid, dim3(512 + 64), (size_t)g_duo_pad_lds, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
-        else if (groups_per_pass == 16 && d_band_desc) hipLaunchKernelGGL((ycge::k_atrous_stream<16, true, true>), grid, dim3(512 + 64), (size_t)g_duo_pad_lds, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
-        else if (groups_per_pass == 16 && !profile) hipLaunchKernelGGL((ycge::k_atrous_stream<16, false>), grid, dim3(512 + 64), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
-        else if (groups_per_pass == 16) hipLaunchKernelGGL((ycge::k_atrous_stream<16, true>), grid, dim3(512 + 64), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
-        else return (int)hipErrorInvalidValue;
-        return (int)hipGetLastError();
-    }
-#if YCGE_EXPERIMENTS
-    if (groups_per_pass == 8)
-        hipLaunchKernelGGL((ycge::k_atrous_persist<8>), grid, dim3(256), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, n_levels, K, n_bands, rows_per_band, window_width, progress, epoch, xcd_local);
-    else if (groups_per_pass == 16)
-        hipLaunchKernelGGL((ycge::k_atrous_persist<16>), grid, dim3(512), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, n_levels, K, n_bands, rows_per_band, window_width, progress, epoch, xcd_local);
-    else
-        hipLaunchKernelGGL((ycge::k_atrous_persist<32>), grid, dim3(1024), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, n_levels, K, n_bands, rows_per_band, window_width, progress, epoch, xcd_local);
+    // 8 or 16 pixels a pass: the publishing wavefront is the workgroup's 5th or 9th
+    if (groups_per_pass == 8) hipLaunchKernelGGL((ycge::k_atrous_stream<8, false>), grid, dim3(256 + 64), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
+    else if (groups_per_pass == 16 && d_band_desc && !profile) hipLaunchKernelGGL((ycge::k_atrous_stream<16, false, true>), grid, dim3(512 + 64), (size_t)g_duo_pad_lds, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
+    else if (groups_per_pass == 16 && d_band_desc) hipLaunchKernelGGL((ycge::k_atrous_stream<16, true, true>), grid, dim3(512 + 64), (size_t)g_duo_pad_lds, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
+    else if (groups_per_pass == 16 && !profile) hipLaunchKernelGGL((ycge::k_atrous_stream<16, false>), grid, dim3(512 + 64), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
+    else if (groups_per_pass == 16) hipLaunchKernelGGL((ycge::k_atrous_stream<16, true>), grid, dim3(512 + 64), 0, stream, A, buf, statw, sky, d_pixels, d_offsets, d_pass_level, d_band_desc, n_levels, n_bands, rows_per_band, window_width, progress, epoch, xcd_local, ticket_base);
+    else return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
-#else
-    return (int)hipErrorInvalidValue;          // (the group hand-over form, YCGE_POST_MODE=4, exists in experiment builds only: the host never asks for it here)
-#endif
 }
 
 // How many band workgroups of the persistent launch one CU holds - asked of the runtime for the very instantiation
 // ycge_launch_atrous_persist would start (they differ: 66 VGPRs and three workgroups for the two-set form, 82 and two for the
 // others).  A band that is not resident while its neighbours spin on its progress word stalls the frame for seconds.
-int ycge_atrous_persist_resident(int groups_per_pass, int split, int level_handover, int profile)
+int ycge_atrous_persist_resident(int groups_per_pass, int split, int profile)
 {
     int n = 0;
     hipError_t e = hipErrorInvalidValue;
-    if (level_handover) {
-        if (groups_per_pass == 8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<8, false>, 256 + 64, 0);
-        else if (groups_per_pass == 16 && split && !profile) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<16, false, true>, 512 + 64, (size_t)g_duo_pad_lds);
-        else if (groups_per_pass == 16 && split) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<16, true, true>, 512 + 64, (size_t)g_duo_pad_lds);
-        else if (groups_per_pass == 16 && !profile) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<16, false>, 512 + 64, 0);
-        else if (groups_per_pass == 16) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<16, true>, 512 + 64, 0);
-    } else {
-#if YCGE_EXPERIMENTS
-        if (groups_per_pass == 8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_persist<8>, 256, 0);
-        else if (groups_per_pass == 16) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_persist<16>, 512, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_persist<32>, 1024, 0);
-#endif
-    }
+    if (groups_per_pass == 8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<8, false>, 256 + 64, 0);
+    else if (groups_per_pass == 16 && split && !profile) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<16, false, true>, 512 + 64, (size_t)g_duo_pad_lds);
+    else if (groups_per_pass == 16 && split) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<16, true, true>, 512 + 64, (size_t)g_duo_pad_lds);
+    else if (groups_per_pass == 16 && !profile) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<16, false>, 512 + 64, 0);
+    else if (groups_per_pass == 16) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ycge::k_atrous_stream<16, true>, 512 + 64, 0);
     return e == hipSuccess ? n : 0;
 }
 

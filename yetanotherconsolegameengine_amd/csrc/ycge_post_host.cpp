@@ -182,7 +182,7 @@ int post_resident_per_cu(ycge_ctx *c, bool split)
 {
     int &q = c->post_resident_seen[split ? 1 : 0];
     ycge_atrous_duo_pad_lds(c->knobs.post_pad_lds);
-    if (q < 0) q = ycge_atrous_persist_resident(c->knobs.post_groups, split ? 1 : 0, c->knobs.post_mode == 4 ? 0 : 1, c->knobs.post_probe_band >= 0 ? 1 : 0);
+    if (q < 0) q = ycge_atrous_persist_resident(c->knobs.post_groups, split ? 1 : 0, c->knobs.post_probe_band >= 0 ? 1 : 0);
     if (c->knobs.post_assume_resident > 0) return c->knobs.post_assume_resident;
     return q < c->knobs.post_resident_per_cu ? q : c->knobs.post_resident_per_cu;
 }
@@ -219,13 +219,13 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
     // The in-place iteration (iteration 1, when there is one) reads colour-independent weight factors that need the G-buffer and the
     // unit normals only: they are computed on the side stream beside iteration 0 (fork here, join in front of the band launches)
     bool static_pending = false;
-    if (iters >= 2 && c->fan_stream && c->cfg.atrous_inplace_exact) {
+    if (iters >= 2 && c->side_stream && c->cfg.atrous_inplace_exact) {
         if (!c->atrous_statw.p) HIP_TRY(c, c->atrous_statw.alloc(n * 75));
-        HIP_TRY(c, hipEventRecord(c->fan_ev[0], stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->fan_stream, c->fan_ev[0], 0));
-        e = ycge_launch_atrous_static(w, h, 2, phi, c->g_albedo.p, c->unit_n.p, c->g_depth.p, c->sky.p, c->atrous_statw.p, c->fan_stream);
+        HIP_TRY(c, hipEventRecord(c->side_ev[0], stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->side_ev[0], 0));
+        e = ycge_launch_atrous_static(w, h, 2, phi, c->g_albedo.p, c->unit_n.p, c->g_depth.p, c->sky.p, c->atrous_statw.p, c->side_stream);
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_atrous_static launch failed: %s", hipGetErrorString((hipError_t)e));
-        HIP_TRY(c, hipEventRecord(c->fan_ev[1], c->fan_stream));
+        HIP_TRY(c, hipEventRecord(c->side_ev[1], c->side_stream));
         static_pending = true;
     }
     for (int it = 0; it < iters; it++) {
@@ -290,21 +290,20 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
             const int levels_per_launch = sc->levels_per_launch;
             if (levels_per_launch < 1) return c->fail(YCGE_ERR_UNSUPPORTED, "in-place A-trous: a level of %u pixels in one band", sc->max_level_pixels);
             if (!c->atrous_statw.p) HIP_TRY(c, c->atrous_statw.alloc(n * 75));
-            if (static_pending && step == 2) { HIP_TRY(c, hipStreamWaitEvent(stream, c->fan_ev[1], 0)); static_pending = false; }
+            if (static_pending && step == 2) { HIP_TRY(c, hipStreamWaitEvent(stream, c->side_ev[1], 0)); static_pending = false; }
             else {
                 e = ycge_launch_atrous_static(w, h, step, phi, c->g_albedo.p, c->unit_n.p, c->g_depth.p, c->sky.p, c->atrous_statw.p, stream);
                 if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_atrous_static launch failed: %s", hipGetErrorString((hipError_t)e));
             }
             // one persistent launch when the window form applies and every band's workgroup is resident at once (it waits for its
             // neighbour inside the kernel); else a launch per level group
-            const bool persist = sc->split || (c->knobs.post_mode != 2 && (c->knobs.post_groups <= 16 || c->knobs.post_mode == 4) && sc->window_width != 0 && (size_t)sc->rows_per_band * sc->window_width <= 2048 &&
+            const bool persist = sc->split || (c->knobs.post_mode != 2 && c->knobs.post_groups <= 16 && sc->window_width != 0 && (size_t)sc->rows_per_band * sc->window_width <= 2048 &&
                                  c->compute_units > 0 && ((sc->bands + 7) / 8) * 8 <= post_resident_per_cu(c, sc->split) * c->compute_units);
             if (persist) {
                 // Bands of one XCD adjacent (their colours meet in one L2) while every band has a CU of its own: 1080p 3.90 against 4.03 ms.
                 // Where two bands must share a CU (a 4K grid: 270 bands) block order is the better one - 14.7 against 15.9 ms, launch
                 // form 16.3: the pairs a CU gets are then far apart in the image and busy at different times.
                 const int xcd_local = c->knobs.post_mode == 3 ? 0 : c->knobs.post_mode == 0 ? (((sc->bands + 7) / 8) * 8 <= c->compute_units ? 1 : 0) : 1;
-                const uint32_t groups = (uint32_t)((sc->levels + levels_per_launch - 1) / levels_per_launch);
                 if (c->post_progress.n < (size_t)sc->bands * 32 + 8000 || c->post_epoch > 0x60000000u) {
                     HIP_TRY(c, c->post_progress.reserve((size_t)sc->bands * 32 + 8000));       // + room for the profiling timeline of two bands
                     HIP_TRY(c, hipMemsetAsync(c->post_progress.p, 0, ((size_t)sc->bands * 32 + 8000) * sizeof(uint32_t), stream));
@@ -314,10 +313,10 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
                 }
                 ycge_atrous_duo_pad_lds(c->knobs.post_pad_lds);
                 e = ycge_launch_atrous_persist(w, h, step, phi, dst, c->sky.p, c->atrous_statw.p, sc->pixels.p, sc->offsets.p, sc->pass_level.p, sc->split ? sc->band_desc.p : nullptr, sc->levels, sc->bands,
-                                               levels_per_launch, c->knobs.post_groups, sc->rows_per_band, sc->window_width, c->post_progress.p, c->post_epoch,
-                                               xcd_local | (c->knobs.post_dbg_free ? 2 : 0), c->knobs.post_mode == 4 ? 0 : 1, c->knobs.post_probe_band >= 0 ? 1 : 0, c->post_ticket, stream);
-                if (!xcd_local && c->knobs.post_mode != 4) c->post_ticket += (uint32_t)sc->bands;      // one number per workgroup of the launch
-                c->post_epoch += (groups > (uint32_t)sc->levels ? groups : (uint32_t)sc->levels) + 1u;
+                                               c->knobs.post_groups, sc->rows_per_band, sc->window_width, c->post_progress.p, c->post_epoch,
+                                               xcd_local | (c->knobs.post_dbg_free ? 2 : 0), c->knobs.post_probe_band >= 0 ? 1 : 0, c->post_ticket, stream);
+                if (!xcd_local) c->post_ticket += (uint32_t)sc->bands;      // one number per workgroup of the launch
+                c->post_epoch += (uint32_t)sc->levels + 1u;
             } else
             e = ycge_launch_atrous_inplace(w, h, step, phi, dst, c->g_albedo.p, c->unit_n.p, c->g_depth.p, c->sky.p, c->atrous_statw.p,
                                            sc->pixels.p, sc->offsets.p, sc->levels, sc->bands, levels_per_launch, c->knobs.post_groups, sc->rows_per_band, sc->window_width, stream);
@@ -330,7 +329,7 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
         // (config.atrous_inplace_exact = 0): plain ping-pong between A and B
         const float *tmp = cur; cur = dst; dst = c->cfg.atrous_inplace_exact ? ((tmp == A) ? B : A) : ((cur == A) ? B : A);
     }
-    if (static_pending) HIP_TRY(c, hipStreamWaitEvent(stream, c->fan_ev[1], 0));
+    if (static_pending) HIP_TRY(c, hipStreamWaitEvent(stream, c->side_ev[1], 0));
     c->denoised = cur;
     const int step = c->ss * 2 > 2 ? c->ss * 2 : 2;            // :226
     const float tone_consts[5] = {1.0f, 0.18f, 0.2f, 0.10f, 1.50f};     // toneExposure, aeKey, aeSpeed, aeMin, aeMax (ToneMapper.cs:8-16)

@@ -133,12 +133,12 @@ try {
         for (int a = 1; a < K; a++) skip |= 1u << ((cost_slot + (uint32_t)a) % RC);
         const int tb = c->res_order_next;
         c->res_order_next = (tb + 1) % 3;
-        HIP_TRY(c, hipStreamWaitEvent(c->fan_stream, rs->traced, 0));
-        if (c->res_order_frame[(size_t)tb] >= 0) HIP_TRY(c, hipStreamWaitEvent(c->fan_stream, c->res_order_read_ev[(size_t)tb], 0));
+        HIP_TRY(c, hipStreamWaitEvent(c->side_stream, rs->traced, 0));
+        if (c->res_order_frame[(size_t)tb] >= 0) HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->res_order_read_ev[(size_t)tb], 0));
         c->res_order_frame[(size_t)tb] = -1;          // (not to be picked while it is being rewritten ...)
-        e = ycge_launch_order_blocks(c->res_cost.p, n_blocks, policy, split_top, 0u, 0u, RC /* the slot nobody reads */, skip, c->res_ws[(size_t)tb]->p, c->res_order[(size_t)tb]->p, c->fan_stream, 0, RC, c->cost_snap.p);      // (traces in flight write their costs meanwhile: a copy is read)
+        e = ycge_launch_order_blocks(c->res_cost.p, n_blocks, policy, split_top, RC /* the slot nobody reads */, skip, c->res_ws[(size_t)tb]->p, c->res_order[(size_t)tb]->p, c->side_stream, 0, RC, c->cost_snap.p);      // (traces in flight write their costs meanwhile: a copy is read)
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "schedule launch failed: %s", hipGetErrorString((hipError_t)e));
-        HIP_TRY(c, hipEventRecord(c->res_order_ev[(size_t)tb], c->fan_stream));
+        HIP_TRY(c, hipEventRecord(c->res_order_ev[(size_t)tb], c->side_stream));
         c->res_order_frame[(size_t)tb] = fs.frame;          // (... and from frame N + K on it is the newest)
     }
     c->pending.push_back(fs);
@@ -273,12 +273,12 @@ try {
         for (int a = 1; a < K; a++) skip |= 1u << ((last_slot + (uint32_t)a) % RC);
         const int tb = c->res_order_next;
         c->res_order_next = (tb + 1) % 3;
-        HIP_TRY(c, hipStreamWaitEvent(c->fan_stream, sets[(size_t)n - 1]->traced, 0));
-        if (c->res_order_frame[(size_t)tb] >= 0) HIP_TRY(c, hipStreamWaitEvent(c->fan_stream, c->res_order_read_ev[(size_t)tb], 0));
+        HIP_TRY(c, hipStreamWaitEvent(c->side_stream, sets[(size_t)n - 1]->traced, 0));
+        if (c->res_order_frame[(size_t)tb] >= 0) HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->res_order_read_ev[(size_t)tb], 0));
         c->res_order_frame[(size_t)tb] = -1;
-        e = ycge_launch_order_blocks(c->res_cost.p, n_blocks, policy, split_top, 0u, 0u, RC, skip, c->res_ws[(size_t)tb]->p, c->res_order[(size_t)tb]->p, c->fan_stream, 0, RC, c->cost_snap.p);      // (traces in flight write their costs meanwhile: a copy is read)
+        e = ycge_launch_order_blocks(c->res_cost.p, n_blocks, policy, split_top, RC, skip, c->res_ws[(size_t)tb]->p, c->res_order[(size_t)tb]->p, c->side_stream, 0, RC, c->cost_snap.p);      // (traces in flight write their costs meanwhile: a copy is read)
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "schedule launch failed: %s", hipGetErrorString((hipError_t)e));
-        HIP_TRY(c, hipEventRecord(c->res_order_ev[(size_t)tb], c->fan_stream));
+        HIP_TRY(c, hipEventRecord(c->res_order_ev[(size_t)tb], c->side_stream));
         c->res_order_frame[(size_t)tb] = fs[(size_t)n - 1].frame;
     }
     return YCGE_OK;

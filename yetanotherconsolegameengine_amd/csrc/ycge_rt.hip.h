@@ -765,7 +765,6 @@ __device__ __forceinline__ bool is_wire_on_face(const GGrid &g, F3 p, int ix, in
 #define YCGE_BLOCK 256
 static __shared__ uint2 g_lds_stack[YCGE_LDS_STACK * YCGE_BLOCK];     // 256-thread workgroups (tile = workgroup)
 static __shared__ __attribute__((aligned(16))) uint2 g_lds_stack64[YCGE_LDS_STACK * 64];           // 64-thread workgroups (8x8 block = workgroup); while the stacks are empty: the work list of mesh_anyhit_bfs
-static __shared__ uint2 g_lds_stack192[YCGE_LDS_STACK * 192];         // 192-thread workgroups (k_trace_fan: a block's three wavefronts)
 
 // The LDS part is accessed with explicit ds_read_b64 / ds_write_b64: written as plain C++ the compiler merges the
 // "LDS or spill" choice into ONE flat_load through a selected generic pointer (seen in the ISA), which puts the
@@ -793,7 +792,7 @@ struct StackT {
     {
         spill = (uint2 *)spill_base + (first_lane + blockIdx.x * BS + threadIdx.x);
         spill_stride = n_lanes;
-        lds_base = (uint32_t)(uintptr_t)(BS == 64 ? (void *)g_lds_stack64 : BS == 192 ? (void *)g_lds_stack192 : (void *)g_lds_stack) + threadIdx.x * 8u;
+        lds_base = (uint32_t)(uintptr_t)(BS == 64 ? (void *)g_lds_stack64 : (void *)g_lds_stack) + threadIdx.x * 8u;
         sp = 0;
     }
     __device__ __forceinline__ void reset() { sp = 0; }
@@ -828,7 +827,7 @@ struct StackT {
     __device__ __forceinline__ uint2 read_early(uint32_t owner, int lvl) const
     {
         const uint32_t l = lvl >= 0 && lvl < YCGE_LDS_STACK ? (uint32_t)lvl : 0u;
-        const uint2 *base = BS == 64 ? g_lds_stack64 : BS == 192 ? g_lds_stack192 : g_lds_stack;
+        const uint2 *base = BS == 64 ? g_lds_stack64 : g_lds_stack;
         return base[l * BS + owner];
     }
     __device__ __forceinline__ void read_at(uint32_t owner, int lvl, uint32_t &ref, float &tnear) const
@@ -1451,12 +1450,6 @@ __device__ __forceinline__ void traverse(const SceneDev &S, RayQ &q, STK &st, fl
         }
     }
 }
-
-#if YCGE_EXPERIMENTS
-} // namespace ycge
-#include "experiments/ycge_refill.hip.h"
-namespace ycge {
-#endif
 
 // ------------------------------------------------------------------ hit attributes
 // Rebuild HitRecord {P, N, Mat} of the winning primitive from (prim, sub, t) with the same
