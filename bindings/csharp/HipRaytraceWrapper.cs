@@ -22,7 +22,12 @@
 //                byte a chexel {color_16 of top | of bottom << 4}, and the blit builds each ChexelColor from its byte and its Vec3 - every
 //                field equals the reference's, the host no longer searches.  Needs a library that exports the two calls (INTEGRATION.md
 //                section 7).
+//   DeviceAnsiStream - with AnsiPresenter (a DeviceAnsiTerminalRenderer in place of ANSITerminalRenderer): the frame is read back as the
+//                bytes ANSITerminalRenderer.Render() would write for the console (ycge_render_frame_ansi), and the presenter writes them to
+//                stdout as they are - the framebuffer is not written and no cell is walked on the host.  Synchronous frames only (FrameLate
+//                is ignored); the raytrace framebuffer is the only one drawn (INTEGRATION.md section 8).
 using System;
+using System.IO;
 using System.Runtime.CompilerServices;
 using ConsoleGame.RayTracing;
 using ConsoleGame.RayTracing.Native;
@@ -36,6 +41,57 @@ public sealed class HipRaytraceOptions
     public int[] Devices;
     public YExchange Exchange = YExchange.PeerPush;
     public bool DeviceChexelColors;
+    public bool DeviceAnsiStream;
+    public DeviceAnsiTerminalRenderer AnsiPresenter;          // DeviceAnsiStream: the presenter the frames' streams go to
+}
+
+/// <summary>ANSITerminalRenderer with the cell walk moved to the GPU (HipRaytraceOptions.DeviceAnsiStream): Render() writes the stream of the
+/// last frame - built by ycge_render_frame_ansi, byte for byte what ANSITerminalRenderer.Render() writes for the same cells - to stdout.
+/// A change of console size is handled as ANSITerminalRenderer does it: onResize(width, height), and the next frame written starts with
+/// ESC[2J ESC[H.  Only the raytrace framebuffer is drawn: AddFrameBuffer / RemoveFrameBuffer keep nothing.</summary>
+public sealed class DeviceAnsiTerminalRenderer : ITerminalRenderer
+{
+    public delegate ReadOnlySpan<byte> FrameSource();
+    private readonly Action<int, int> onResize;
+    private readonly Stream stdout;
+    public int consoleWidth { get; private set; }
+    public int consoleHeight { get; private set; }
+    public readonly ConsoleColor DefaultFg, DefaultBg;
+    internal bool ClearPending;                 // the console changed size: the next stream starts with ESC[2J ESC[H (:100-103)
+    internal FrameSource Source;                // the wrapper's last frame (HipRaytraceWrapper.LastAnsiFrame)
+
+    public DeviceAnsiTerminalRenderer(Action<int, int> onResize)
+    {
+        this.onResize = onResize;
+        consoleWidth = Console.WindowWidth;                                 // ANSITerminalRenderer.cs:31-37
+        consoleHeight = Console.WindowHeight - 1;
+        DefaultFg = Console.ForegroundColor;
+        DefaultBg = Console.BackgroundColor;
+        Console.CursorVisible = false;
+        stdout = Console.OpenStandardOutput();
+        byte[] hide = { 0x1B, (byte)'[', (byte)'?', (byte)'2', (byte)'5', (byte)'l' };      // ESC[?25l (:52-54)
+        stdout.Write(hide, 0, hide.Length);
+        stdout.Flush();
+    }
+
+    public void AddFrameBuffer(Framebuffer fb) { }
+    public void RemoveFrameBuffer(Framebuffer fb) { }
+
+    public void Render()
+    {
+        if (Console.WindowWidth != consoleWidth || Console.WindowHeight - 1 != consoleHeight)
+        {
+            consoleWidth = Console.WindowWidth;                             // :88-96
+            consoleHeight = Console.WindowHeight - 1;
+            onResize?.Invoke(consoleWidth, consoleHeight);
+            ClearPending = true;                                            // (the frame in hand was built for the old size)
+            return;
+        }
+        ReadOnlySpan<byte> s = Source != null ? Source() : ReadOnlySpan<byte>.Empty;
+        if (s.IsEmpty) return;
+        stdout.Write(s);
+        stdout.Flush();
+    }
 }
 
 public partial class RaytraceEntity
@@ -56,6 +112,9 @@ public partial class RaytraceEntity
         private readonly bool frameLate;
         private readonly bool deviceColors;         // DeviceChexelColors: color16 / color16Late hold {color_16 of top | of bottom << 4} per chexel
         private byte* color16, color16Late;         // (page-locked memory of the library, one per SDR array)
+        private readonly DeviceAnsiTerminalRenderer ansi;       // DeviceAnsiStream: the presenter of the streams
+        private byte* ansiBuf;                      // the last frame's stream (page-locked memory of the library, ansiCap bytes)
+        private ulong ansiCap, ansiLen;
         private bool inFlight;                      // FrameLate: a frame queued by the last TryFlipAndBlit has not been waited for yet
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
         private ulong objectsSignature;
@@ -76,11 +135,34 @@ public partial class RaytraceEntity
                 for (int i = 0; i < options.Devices.Length; i++) cfg.Devices[i] = options.Devices[i];
                 cfg.MultiDeviceExchange = (int)options.Exchange;
             }
-            frameLate = options != null && options.FrameLate && cfg.NDevices <= 1;      // (frames in flight are the single-device form)
+            ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
+            frameLate = options != null && options.FrameLate && cfg.NDevices <= 1 && ansi == null;      // (frames in flight are the single-device form; the stream is synchronous)
             deviceColors = options != null && options.DeviceChexelColors;
             Ycge.Check(IntPtr.Zero, Ycge.ycge_create(ref cfg, out ctx));
             AllocSdr();
             Upload();                               // the reference ctor ends with scene.RebuildBVH() (RaytraceRenderer.cs:107)
+            if (ansi != null) ansi.Source = () => LastAnsiFrame;
+        }
+
+        /// <summary>DeviceAnsiStream: the bytes of the last frame, as ANSITerminalRenderer.Render() writes them (valid until the next frame).</summary>
+        public ReadOnlySpan<byte> LastAnsiFrame => ansiBuf == null ? ReadOnlySpan<byte>.Empty : new ReadOnlySpan<byte>(ansiBuf, checked((int)ansiLen));
+
+        // one frame into the stream of the presenter's console (the framebuffer at its viewport), the buffer grown to the stream's bound
+        private void RenderAnsi(Framebuffer fb)
+        {
+            int cw = ansi.consoleWidth, ch = ansi.consoleHeight;
+            Ycge.Check(ctx, Ycge.ycge_ansi_stream_bound(cw, ch, out UIntPtr bound));
+            if ((ulong)bound > ansiCap)
+            {
+                if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; ansiCap = ansiLen = 0; }
+                Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(bound, out IntPtr p));
+                ansiBuf = (byte*)p; ansiCap = (ulong)bound;
+            }
+            UIntPtr len;
+            Ycge.Check(ctx, Ycge.ycge_render_frame_ansi(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
+                                                        ansiBuf, (UIntPtr)ansiCap, &len, null, null));
+            ansiLen = (ulong)len;
+            ansi.ClearPending = false;
         }
 
         /// <summary>What the devices' tiles really travel by (the library falls back to the peer push where librccl.so is missing).</summary>
@@ -208,6 +290,12 @@ public partial class RaytraceEntity
         public void TryFlipAndBlit(Framebuffer fb)
         {
             if (fb.Width != fbW || fb.Height != fbH) Resize(fb, ss);       // RaytraceRenderer.cs:119-120 does the same check
+            if (ansi != null)
+            {
+                SyncScene();
+                RenderAnsi(fb);                                                // (the presenter writes the stream: no chexel reaches the framebuffer)
+                return;
+            }
             if (frameLate)
             {
                 // the frame queued by the LAST call is finished first (it ran beside the host's Update in between), then this call's frame is queued
@@ -258,6 +346,7 @@ public partial class RaytraceEntity
             if (sdr != null) { Ycge.ycge_free_host_buffer((IntPtr)sdr); sdr = null; }
             if (sdrLate != null) { Ycge.ycge_free_host_buffer((IntPtr)sdrLate); sdrLate = null; }
             FreeColor16();
+            if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; }
             uploaded?.Dispose();
         }
     }

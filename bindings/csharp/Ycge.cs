@@ -195,6 +195,11 @@ namespace ConsoleGame.RayTracing.Native
         // device chexel colours (after ABI 10, found by symbol lookup - AbiVersion is unchanged): the presenters' bytes beside the SDR frame
         [DllImport(Lib)] public static extern int ycge_render_frame_chexels(IntPtr ctx, float* outTopBottomSdr, byte* outColor16, byte* outAnsi, byte* outRgba, YFrameStats* stats);
         [DllImport(Lib)] public static extern int ycge_render_frame_async_chexels(IntPtr ctx, float* outTopBottomSdr, byte* outColor16, byte* outAnsi, byte* outRgba);
+        // the ANSI presenter's escape stream built on the device (after ABI 10, found by symbol lookup): ANSITerminalRenderer.Render()'s bytes
+        [DllImport(Lib)] public static extern int ycge_ansi_stream_bound(int consoleW, int consoleH, out UIntPtr bytes);
+        [DllImport(Lib)] public static extern int ycge_render_frame_ansi(IntPtr ctx, int consoleW, int consoleH, int viewportX, int viewportY, int defaultFg16,
+                                                                         int defaultBg16, int clearScreen, byte* outStream, UIntPtr capacity, UIntPtr* outLen,
+                                                                         float* outTopBottomSdr, YFrameStats* stats);
         [DllImport(Lib)] public static extern int ycge_wait(IntPtr ctx);
         [DllImport(Lib)] public static extern int ycge_async_trace_times(IntPtr ctx, float* msOut, int capacity, out int nOut);
         [DllImport(Lib)] public static extern int ycge_flight_query(IntPtr ctx, out YFlightInfo info);

@@ -387,6 +387,22 @@ int ycge_render_frame_async_sdr(ycge_ctx *ctx, float *out_top_bottom_sdr);
 int ycge_render_frame_chexels(ycge_ctx *ctx, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba,
                               ycge_frame_stats *stats);
 int ycge_render_frame_async_chexels(ycge_ctx *ctx, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba);
+/* --- the ANSI presenter's escape stream on the device: the bytes ANSITerminalRenderer.Render() (Renderer/ANSITerminalRenderer.cs:86-153)
+ * writes for a console_w x console_h console whose only framebuffer is this context's fbW x fbH at (viewport_x, viewport_y) - built from
+ * the ANSI pairs of ycge_render_frame_chexels, which stay on the device, by one prefix sum over the cells.  Added after ABI 10 without
+ * changing it: a host detects these exports by symbol lookup.
+ *   [ESC[2J ESC[H when clear_screen], per row ESC[<y+1>;1H, per cell the SGR escape of the indices that differ from the previous cell's
+ *   (ESC[38;5;F;48;5;Bm / ESC[38;5;Fm / ESC[48;5;Bm / none; (-1, -1) before the first cell, rows included) and its character, ESC[0m.
+ *   A covered cell is ('\u2580', ansi(top), ansi(bottom)); any other is (' ', ansi(palette[default_fg16]), ansi(palette[default_bg16])).
+ * ycge_ansi_stream_bound: 7 + 4 + sum over rows of (5 + digits(y + 1)) + 23 console_w console_h bytes - no context, no device.
+ * ycge_render_frame_ansi: the frame state and the optional SDR are ycge_render_frame's, bit for bit; *out_len bytes of out_stream are
+ * written, never a byte past them.  Refused before any device work, the frame state unchanged: NULL out_stream or out_len, a console
+ * that is not positive or whose bound reaches 2^32, defaults outside 0..15, capacity below the bound, a peer context, the RCCL exchange
+ * with lean slabs.  A failed or refused call writes nothing to the caller's arrays, then or later. */
+int ycge_ansi_stream_bound(int32_t console_w, int32_t console_h, size_t *bytes);
+int ycge_render_frame_ansi(ycge_ctx *ctx, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                           int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len,
+                           float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
 int ycge_wait(ycge_ctx *ctx);
 /* measurement: durations (ms) of the trace launches of the frames queued since the last call, oldest first (at most the last 1024);
  * waits for the frames in flight */

@@ -44,6 +44,11 @@ int ycge_host_halo_layout(int32_t hiW, int32_t hiH, int32_t rank, int32_t world,
  * values (w x h chexels of {top rgb, bottom rgb}; NULL outputs are skipped; layouts as ycge_render_frame_chexels) */
 int ycge_host_srgb_thresholds(float *f32_out, double *f64_out);
 int ycge_test_encode_chexels(ycge_ctx *c, const float *sdr, int32_t w, int32_t h, uint8_t *c16, uint8_t *ansi, uint8_t *rgba);
+/* ---- the ANSI escape stream (csrc/ycge_ansi.cpp): its kernels alone on caller-given ANSI pairs (fbW x fbH {fg, bg}, any values 0..255),
+ * with the geometry, defaults, refusals and output of ycge_render_frame_ansi */
+int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,
+                          int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
+                          size_t *out_len);
 
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */

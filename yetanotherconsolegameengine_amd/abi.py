@@ -212,6 +212,9 @@ _PROTOTYPES = {
     "ycge_render_frame_chexels": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                             C.POINTER(FrameStats)]),
     "ycge_render_frame_async_chexels": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "ycge_ansi_stream_bound": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "ycge_render_frame_ansi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
+                                         C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(FrameStats)]),
     "ycge_read_buffer": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_set_frame_counter": (C.c_int, [C.c_void_p, C.c_int64]),
     "ycge_read_timed_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -1,0 +1,235 @@
+// ycge_ansi.cpp - the ANSI presenter's escape stream on the device (ycge_render_frame_ansi, ycge_ansi_stream_bound; kernels:
+// ycge_ansi.hip).
+//
+// A frame of ycge_render_frame_ansi is ycge_render_frame_chexels' with the ANSI pairs alone, kept on the device: behind their encode,
+// on the same stream, three launches turn them into the bytes ANSITerminalRenderer.Render() writes (ANSITerminalRenderer.cs:86-153)
+// for a console over the framebuffer, and the stream's length is copied to a page-locked word.  Once the stream is synchronised, exactly
+// that many bytes are copied to the caller.  The request lives in ChexelState for the length of one call (a scope guard clears it; on an
+// error return also every latched destination), so no other entry point issues a launch or copy of it.
+//
+// The default cell's colours are ansi(palette16[k]): k_encode_chexels run once on the 16 palette colours, so no second formula exists.
+#include "ycge_ctx.h"
+
+namespace {
+
+// Chexel.cs:11-29, the palette entries that ChexelColor(ConsoleColor) holds as color_f32 (the same table as ycge_chexel.hip's)
+const float kPalette16[16][3] = {
+    {0.00f, 0.00f, 0.00f}, {0.00f, 0.00f, 0.50f}, {0.00f, 0.50f, 0.00f}, {0.00f, 0.50f, 0.50f},
+    {0.50f, 0.00f, 0.00f}, {0.50f, 0.00f, 0.50f}, {0.50f, 0.50f, 0.00f}, {0.75f, 0.75f, 0.75f},
+    {0.50f, 0.50f, 0.50f}, {0.00f, 0.00f, 1.00f}, {0.00f, 1.00f, 0.00f}, {0.00f, 1.00f, 1.00f},
+    {1.00f, 0.00f, 0.00f}, {1.00f, 0.00f, 1.00f}, {1.00f, 1.00f, 0.00f}, {1.00f, 1.00f, 1.00f}};
+
+constexpr unsigned long long kOffsetLimit = 0xffffffffull;       // the kernels' offsets are 32-bit
+
+// the stream's upper bound: ESC[2J ESC[H, ESC[0m, each row's ESC[<y+1>;1H, and 23 bytes a cell (the longest escape, 20, and '▀', 3);
+// false when it does not fit a size_t
+bool stream_bound(int32_t cw, int32_t ch, unsigned long long &bytes)
+{
+    unsigned __int128 b = 7 + 4 + (unsigned __int128)23 * (uint64_t)cw * (uint64_t)ch + (unsigned __int128)5 * (uint64_t)ch;
+    for (int64_t lo = 1, d = 1; lo <= ch; lo *= 10, d++)           // the rows numbered lo .. min(ch, 10 lo - 1) have d digits
+        b += (unsigned __int128)d * (uint64_t)((lo * 10 - 1 < ch ? lo * 10 - 1 : ch) - lo + 1);
+    if (b > (unsigned __int128)SIZE_MAX) return false;
+    bytes = (unsigned long long)b;
+    return true;
+}
+
+} // namespace
+
+namespace ycge_host {
+
+// the 16 default indices, on `stream`: k_encode_chexels on the palette as 8 chexels {palette[2 k], palette[2 k + 1]}
+static int ensure_palette(ycge_ctx *c, ChexelState &X, hipStream_t stream)
+{
+    if (X.ansi_palette_ready) return YCGE_OK;
+    { const int rc = ensure_tables(c, X); if (rc != YCGE_OK) return rc; }
+    if (!X.ansi_palette.p) HIP_TRY(c, X.ansi_palette.alloc(48 + 4));
+    HIP_TRY(c, hipMemcpy(X.ansi_palette.p, kPalette16, sizeof kPalette16, hipMemcpyHostToDevice));
+    const int e = ycge_launch_chexels(X.ansi_palette.p, 8, 1, X.tables.p, nullptr, reinterpret_cast<uint8_t *>(X.ansi_palette.p + 48), nullptr,
+                                      c->compute_units, stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed (the default colours): %s", hipGetErrorString((hipError_t)e));
+    X.ansi_palette_ready = true;
+    return YCGE_OK;
+}
+
+// the buffers of a cw x ch stream whose bound is `bound` (kept while large enough) and the default colours
+static int ensure_ansi(ycge_ctx *c, ChexelState &X, int32_t cw, int32_t ch, unsigned long long bound, hipStream_t stream)
+{
+    if (X.ansi_stream.cap < bound) HIP_TRY(c, X.ansi_stream.alloc(bound));
+    const uint32_t tiles = ycge_launch_ansi_tiles((uint32_t)cw * (uint32_t)ch);
+    if (X.ansi_tiles.cap < tiles) HIP_TRY(c, X.ansi_tiles.alloc(tiles));
+    if (!X.ansi_len.p) HIP_TRY(c, X.ansi_len.alloc(1));
+    if (!X.ansi_len_host) {
+        void *p = nullptr;
+        HIP_TRY(c, hipHostMalloc(&p, sizeof(unsigned long long), hipHostMallocDefault));
+        X.ansi_len_host = static_cast<unsigned long long *>(p);
+    }
+    return ensure_palette(c, X, stream);
+}
+
+static int launch_stream(ycge_ctx *c, ChexelState &X, hipStream_t stream, const uint8_t *d_pairs, int fbW, int fbH)
+{
+    const int e = ycge_launch_ansi_stream(d_pairs, fbW, fbH, X.ansi_cw, X.ansi_ch, X.ansi_vx, X.ansi_vy, reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48),
+                                          X.ansi_fg, X.ansi_bg, X.ansi_clear, X.ansi_tiles.p, X.ansi_stream.p, X.ansi_stream.cap, X.ansi_len.p, stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "ANSI stream launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipMemcpyAsync(X.ansi_len_host, X.ansi_len.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    return YCGE_OK;
+}
+
+int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs)
+{
+    ChexelState &X = *c->chexels;
+    { const int rc = ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
+    return launch_stream(c, X, stream, d_pairs, c->fbW, c->fbH);
+}
+
+void release_ansi(ChexelState &X, bool all)
+{
+    X.ansi_stream.release(); X.ansi_tiles.release();
+    if (!all) return;
+    X.ansi_len.release(); X.ansi_palette.release();
+    X.ansi_palette_ready = false;
+    if (X.ansi_len_host) (void)hipHostFree(X.ansi_len_host);
+    X.ansi_len_host = nullptr;
+}
+
+} // namespace ycge_host
+
+namespace {
+
+// one _ansi call: sets the request, and clears it on every way out - on an error return also the SDR staging, so no later call writes
+// into an array of this one
+struct AnsiCall {
+    ycge_ctx *c;
+    bool ok = false;
+    AnsiCall(ycge_ctx *c_, int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear) : c(c_)
+    {
+        if (!c->chexels) c->chexels = new ChexelState();
+        ChexelState &X = *c->chexels;
+        X.on = true; X.dst[0] = X.dst[1] = X.dst[2] = nullptr;
+        X.drop_staged();
+        X.ansi_on = true;
+        X.ansi_cw = cw; X.ansi_ch = ch; X.ansi_vx = vx; X.ansi_vy = vy; X.ansi_fg = fg; X.ansi_bg = bg; X.ansi_clear = clear != 0;
+    }
+    ~AnsiCall()
+    {
+        if (ChexelState *X = c->chexels) {
+            X->on = false; X->ansi_on = false;
+            X->drop_staged();
+        }
+        if (!ok) { c->staged_sdr_dst = nullptr; c->staged_sdr_bytes = 0; }
+    }
+};
+
+// what both entry points refuse; bound: the stream's bound
+int check_stream_args(ycge_ctx *c, const char *fn, int32_t cw, int32_t ch, int32_t fg, int32_t bg, const uint8_t *out, size_t capacity, const size_t *out_len,
+                      unsigned long long &bound)
+{
+    if (!out || !out_len) return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_stream and out_len must not be NULL", fn);
+    if (cw <= 0 || ch <= 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: console %d x %d (both must be positive)", fn, cw, ch);
+    if (fg < 0 || fg > 15 || bg < 0 || bg > 15) return c->fail(YCGE_ERR_INVALID_ARG, "%s: default colours %d, %d (ConsoleColor values 0..15)", fn, fg, bg);
+    if (!stream_bound(cw, ch, bound) || bound > kOffsetLimit)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: the stream of a %d x %d console may reach 2^32 bytes (offsets are 32-bit)", fn, cw, ch);
+    if (capacity < bound)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: capacity %zu bytes is below the stream's bound %llu (ycge_ansi_stream_bound)", fn, capacity, bound);
+    return YCGE_OK;
+}
+
+// exactly len bytes of the device stream into `out` (staged when pageable), on c->stream, synchronously
+int copy_stream(ycge_ctx *c, ChexelState &X, uint8_t *out, size_t len)
+{
+    uint8_t *target = out;
+    const bool staged = !host_memory_is_page_locked(out, len);
+    if (staged) {
+        if (len > X.stage_bytes) {
+            if (X.stage) { (void)hipHostFree(X.stage); X.stage = nullptr; X.stage_bytes = 0; }
+            HIP_TRY(c, hipHostMalloc(&X.stage, len, hipHostMallocDefault));
+            X.stage_bytes = len;
+        }
+        target = static_cast<uint8_t *>(X.stage);
+    }
+    HIP_TRY(c, hipMemcpyAsync(target, X.ansi_stream.p, len, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (staged) std::memcpy(out, X.stage, len);
+    return YCGE_OK;
+}
+
+} // namespace
+
+// =========================================================================== C-ABI
+extern "C" {
+
+int ycge_ansi_stream_bound(int32_t console_w, int32_t console_h, size_t *bytes)
+try {
+    unsigned long long b = 0;
+    if (!bytes || console_w <= 0 || console_h <= 0 || !stream_bound(console_w, console_h, b)) return YCGE_ERR_INVALID_ARG;
+    *bytes = (size_t)b;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+int ycge_render_frame_ansi(ycge_ctx *c, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                           int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr,
+                           ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_render_frame_ansi";
+    unsigned long long bound = 0;
+    int rc = check_stream_args(c, fn, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
+    if (rc != YCGE_OK) return rc;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    // (the exchange of the one-process RCCL form packs lean slabs when slab_albedo = 0: no albedo reaches the denoise stage)
+    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
+        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
+    HIP_TRY(c, hipSetDevice(c->device));
+    AnsiCall call(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    ChexelState &X = *c->chexels;
+    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
+    if (rc != YCGE_OK) return rc;
+    rc = render_frame_sync(c, out_top_bottom_sdr, true, st);          // (its stream synchronisation: the length has arrived)
+    if (rc != YCGE_OK) return rc;
+    const unsigned long long len = *X.ansi_len_host;
+    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
+    rc = copy_stream(c, X, out_stream, (size_t)len);
+    if (rc != YCGE_OK) return rc;
+    *out_len = (size_t)len;
+    call.ok = true;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: the stream kernels alone on caller-given ANSI pairs (fbW x fbH {fg, bg}, any values 0..255), with the geometry, defaults and
+// refusals of ycge_render_frame_ansi; on the context's device and stream, with a pairs buffer of its own
+int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,
+                          int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
+                          size_t *out_len)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_test_ansi_stream";
+    if (!pairs || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (pairs %p, %d x %d)", fn, (const void *)pairs, fbW, fbH);
+    unsigned long long bound = 0;
+    int rc = check_stream_args(c, fn, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->chexels) c->chexels = new ChexelState();
+    ChexelState &X = *c->chexels;
+    X.ansi_cw = console_w; X.ansi_ch = console_h; X.ansi_vx = viewport_x; X.ansi_vy = viewport_y;
+    X.ansi_fg = default_fg16; X.ansi_bg = default_bg16; X.ansi_clear = clear_screen != 0;
+    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
+    if (rc != YCGE_OK) return rc;
+    struct Buf { DevBuf<uint8_t> in; ~Buf() { in.release(); } } B;
+    HIP_TRY(c, B.in.alloc(2 * (size_t)fbW * fbH));
+    HIP_TRY(c, hipMemcpy(B.in.p, pairs, 2 * (size_t)fbW * fbH, hipMemcpyHostToDevice));
+    rc = launch_stream(c, X, c->stream, B.in.p, fbW, fbH);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const unsigned long long len = *X.ansi_len_host;
+    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
+    rc = copy_stream(c, X, out_stream, (size_t)len);
+    if (rc != YCGE_OK) return rc;
+    *out_len = (size_t)len;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+} // extern "C"

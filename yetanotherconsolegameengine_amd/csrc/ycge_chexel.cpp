@@ -75,21 +75,9 @@ struct ChexelLayout {
 
 } // namespace
 
-// what the chexel calls of one context hold: made by the first call, freed by ycge_destroy (release_chexels)
-struct ChexelState {
-    bool on = false;                                   // a _chexels call is in progress
-    uint8_t *dst[3] = {nullptr, nullptr, nullptr};     // its destinations: c16, ansi, rgba
-    DevBuf<uint8_t> tables;                            // 256 f32 + 256 f64 thresholds
-    DevBuf<uint8_t> out[2];                            // the encoded bytes, per post parity (as d_sdr / d_sdr2)
-    void *stage = nullptr; size_t stage_bytes = 0;     // page-locked staging of pageable destinations (synchronous call only)
-    uint8_t *staged_dst[3] = {nullptr, nullptr, nullptr};
-    size_t staged_off[3] = {0, 0, 0}, staged_bytes[3] = {0, 0, 0};
-    void drop_staged() { for (int k = 0; k < 3; k++) { staged_dst[k] = nullptr; staged_bytes[k] = 0; } }
-};
-
 namespace ycge_host {
 
-static int ensure_tables(ycge_ctx *c, ChexelState &X)
+int ensure_tables(ycge_ctx *c, ChexelState &X)
 {
     if (X.tables.p) return YCGE_OK;
     const SrgbTables &t = srgb_tables();
@@ -105,12 +93,13 @@ static int ensure_tables(ycge_ctx *c, ChexelState &X)
 int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second)
 {
     ChexelState *X = c->chexels;
-    if (!X || !X->on || (!X->dst[0] && !X->dst[1] && !X->dst[2])) return YCGE_OK;        // (the SDR alone: nothing to encode)
+    const bool ansi = X && X->ansi_on;                                                   // (ycge_render_frame_ansi: the pairs stay on the device)
+    if (!X || !X->on || (!X->dst[0] && !X->dst[1] && !X->dst[2] && !ansi)) return YCGE_OK;        // (the SDR alone: nothing to encode)
     const ChexelLayout L((size_t)c->fbW * c->fbH);
     DevBuf<uint8_t> &out = X->out[second ? 1 : 0];
     if (out.cap < L.total) HIP_TRY(c, out.alloc(L.total));
-    if (X->dst[1] || X->dst[2]) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
-    const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, X->dst[0] ? out.p + L.c16 : nullptr, X->dst[1] ? out.p + L.ansi : nullptr,
+    if (X->dst[1] || X->dst[2] || ansi) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
+    const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, X->dst[0] ? out.p + L.c16 : nullptr, X->dst[1] || ansi ? out.p + L.ansi : nullptr,
                                       X->dst[2] ? out.p + L.rgba : nullptr, c->compute_units, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed: %s", hipGetErrorString((hipError_t)e));
     return YCGE_OK;
@@ -140,6 +129,7 @@ int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second)
         }
         HIP_TRY(c, hipMemcpyAsync(target, src + off[k], bytes[k], hipMemcpyDeviceToHost, stream));
     }
+    if (X->ansi_on) return ansi_enqueue(c, stream, src + L.ansi);          // (ycge_ansi.cpp: the escape stream from the pairs, and its length)
     return YCGE_OK;
 }
 
@@ -148,6 +138,7 @@ void release_chexels(ycge_ctx *c, bool all)
     ChexelState *X = c->chexels;
     if (!X) return;
     X->out[0].release(); X->out[1].release();
+    release_ansi(*X, all);
     if (!all) return;
     X->tables.release();
     if (X->stage) (void)hipHostFree(X->stage);

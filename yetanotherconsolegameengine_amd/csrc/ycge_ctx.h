@@ -81,6 +81,9 @@ int ycge_launch_unpermute(const float *all_slabs, size_t slab_floats_per_rank, i
                           int slab_floats, float *hdr, float *albedo, float *normal, float *depth, uint8_t *sky, hipStream_t stream);
 uint32_t ycge_launch_query_lanes(int has_grid, int occluded, int compute_units);
 int ycge_launch_chexels(const float *sdr, int fbW, int fbH, const uint8_t *tables, uint8_t *c16, uint8_t *ansi, uint8_t *rgba, int compute_units, hipStream_t stream);
+uint32_t ycge_launch_ansi_tiles(uint32_t cells);
+int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
+                            int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
 int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
 }
@@ -528,4 +531,28 @@ void release_chexels(ycge_ctx *c, bool all);                                    
 int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *st);     // ycge_frame.cpp: ycge_render_frame, post stage on request
 int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post);                      // ycge_frame.cpp: ycge_render_frame_async(_sdr)
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
+int ensure_tables(ycge_ctx *c, ChexelState &X);                                           // ycge_chexel.cpp: LinearToSrgb8's thresholds on the device, once
+int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs);                // ycge_ansi.cpp: the stream kernels behind the encode, and the length's copy
+void release_ansi(ChexelState &X, bool all);                                             // ycge_ansi.cpp: the stream buffers (all: and the rest)
 } // namespace ycge_host
+
+// what the chexel calls of one context hold (ycge_chexel.cpp, ycge_ansi.cpp): made by the first call, freed by ycge_destroy (release_chexels)
+struct ChexelState {
+    bool on = false;                                   // a _chexels or _ansi call is in progress
+    uint8_t *dst[3] = {nullptr, nullptr, nullptr};     // its destinations: c16, ansi, rgba
+    DevBuf<uint8_t> tables;                            // 256 f32 + 256 f64 thresholds
+    DevBuf<uint8_t> out[2];                            // the encoded bytes, per post parity (as d_sdr / d_sdr2)
+    void *stage = nullptr; size_t stage_bytes = 0;     // page-locked staging of pageable destinations (synchronous calls only)
+    uint8_t *staged_dst[3] = {nullptr, nullptr, nullptr};
+    size_t staged_off[3] = {0, 0, 0}, staged_bytes[3] = {0, 0, 0};
+    void drop_staged() { for (int k = 0; k < 3; k++) { staged_dst[k] = nullptr; staged_bytes[k] = 0; } }
+    // ycge_render_frame_ansi: the request of the call at hand (the encode writes the ANSI pairs on the device only) and the stream's buffers
+    bool ansi_on = false;
+    int32_t ansi_cw = 0, ansi_ch = 0, ansi_vx = 0, ansi_vy = 0, ansi_fg = 0, ansi_bg = 0, ansi_clear = 0;
+    DevBuf<uint8_t> ansi_stream;                       // the stream (its bound)
+    DevBuf<uint32_t> ansi_tiles;                       // per-tile byte counts, then offsets
+    DevBuf<unsigned long long> ansi_len;               // the stream's length, as the scan wrote it
+    DevBuf<float> ansi_palette;                        // the 16 palette colours as 8 SDR chexels, then their 16 ANSI indices (bytes at float 48)
+    bool ansi_palette_ready = false;
+    unsigned long long *ansi_len_host = nullptr;       // page-locked word the length is copied to
+};

@@ -78,6 +78,7 @@ class RaytraceRenderer:
         self._drop_sdr_buffer()
         self._drop_sdr_ring()
         self.__dict__.pop("_chexel_ring", None)          # (the chexel arrays of the frames in flight: after ycge_destroy, as above)
+        self.__dict__.pop("_ansi_buf", None)             # (the page-locked stream buffer)
 
     def __enter__(self):
         return self
@@ -299,6 +300,37 @@ class RaytraceRenderer:
             arrays[k] = ring[key][0]
         self._check(self.L.ycge_render_frame_async_chexels(self.ctx, *self._chexel_pointers(arrays)))
         return arrays
+
+    # ---------------------------------------------------------------- the ANSI escape stream (ycge_render_frame_ansi)
+    @staticmethod
+    def ansi_stream_bound(console_width: int, console_height: int, lib=None) -> int:
+        """The most bytes the ANSI stream of a console_width x console_height console can take (ycge_ansi_stream_bound; no GPU needed)."""
+        L = lib if lib is not None else abi.load_library()
+        n = C.c_size_t(0)
+        rc = L.ycge_ansi_stream_bound(int(console_width), int(console_height), C.byref(n))
+        if rc != 0:
+            raise abi.YcgeError(rc, f"no ANSI stream bound for a {console_width} x {console_height} console")
+        return n.value
+
+    def TryFlipAndBlitAnsi(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                           clear_screen: bool = False, sdr: bool = False):
+        """One frame (ycge_render_frame_ansi): the bytes ANSITerminalRenderer.Render() writes for a console over this framebuffer at
+        `viewport`, built on the device - `bytes`, or (bytes, SDR array) with sdr=True.  The SDR and the frame state are those of
+        TryFlipAndBlit(want_sdr=True); the frame statistics go to self.stats.  The stream is read back into one growable page-locked
+        buffer of the renderer, freed by close()."""
+        bound = self.ansi_stream_bound(console_width, console_height, self.L)
+        buf = self.__dict__.get("_ansi_buf")
+        if buf is None or buf[0].size < bound:
+            self.__dict__.pop("_ansi_buf", None)
+            buf = self.__dict__["_ansi_buf"] = self._page_locked_zeros((bound,), np.uint8)
+        out = buf[0]
+        n = C.c_size_t(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._check(self.L.ycge_render_frame_ansi(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
+                                                  int(default_bg), int(bool(clear_screen)), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size,
+                                                  C.byref(n), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
+        stream = out[:n.value].tobytes()
+        return (stream, s) if sdr else stream
 
     def Wait(self):
         self._check(self.L.ycge_wait(self.ctx))
