@@ -27,6 +27,7 @@
 //                stdout as they are - the framebuffer is not written and no cell is walked on the host.  Synchronous frames only (FrameLate
 //                is ignored); the raytrace framebuffer is the only one drawn (INTEGRATION.md section 8).
 using System;
+using System.Collections.Generic;
 using System.IO;
 using System.Runtime.CompilerServices;
 using ConsoleGame.RayTracing;
@@ -231,17 +232,54 @@ public partial class RaytraceEntity
             return true;
         }
 
+        /// <summary>Chunk streaming (WorldManager.LoadChunksAround, WorldManager.cs:289-370): the scene's VolumeGrids that the device does not
+        /// hold yet are attached (ycge_scene_attach_grids: their cells go up once and are encoded on the device).  False when one of them
+        /// needs a material the last upload did not hold.</summary>
+        internal bool SyncVolumeGrids(Scene scene)
+        {
+            var fresh = new List<VolumeGrid>();
+            foreach (Hittable o in scene.Objects) if (o is VolumeGrid g && !uploaded.GridOwners.Contains(g)) fresh.Add(g);
+            if (fresh.Count == 0) return true;
+            using (var scratch = new FlatScene())
+            {
+                var records = new YGrid[fresh.Count];
+                for (int i = 0; i < records.Length; i++) if (!SceneFlattener.FlattenGrid(fresh[i], uploaded, scratch, out records[i])) return false;
+                var index = new int[records.Length];
+                fixed (YGrid* r = records) fixed (int* ix = index) Ycge.Check(ctx, Ycge.ycge_scene_attach_grids(ctx, r, records.Length, ix));
+                for (int i = 0; i < index.Length; i++)
+                {
+                    while (uploaded.GridOwners.Count <= index[i]) uploaded.GridOwners.Add(null);
+                    uploaded.GridOwners[index[i]] = fresh[i];
+                }
+            }
+            return true;
+        }
+
+        /// <summary>... and the grids that left Scene.Objects give their slots back (after ycge_scene_update_objects: nothing refers to them).</summary>
+        private void DetachVolumeGrids()
+        {
+            var live = new HashSet<VolumeGrid>();
+            foreach (Hittable o in scene.Objects) if (o is VolumeGrid g) live.Add(g);
+            var gone = new List<int>();
+            for (int i = 0; i < uploaded.GridOwners.Count; i++) if (uploaded.GridOwners[i] != null && !live.Contains(uploaded.GridOwners[i])) gone.Add(i);
+            if (gone.Count == 0) return;
+            int[] ix = gone.ToArray();
+            fixed (int* p = ix) Ycge.Check(ctx, Ycge.ycge_scene_detach_grids(ctx, p, ix.Length));
+            foreach (int i in gone) uploaded.GridOwners[i] = null;
+        }
+
         private void SyncScene()
         {
             if (forceUpload || ObjectsSignature() != objectsSignature)
             {
-                YPrim[] prims = forceUpload ? null : SceneFlattener.ObjectsAgainst(scene, uploaded);
+                YPrim[] prims = forceUpload || !SyncVolumeGrids(scene) ? null : SceneFlattener.ObjectsAgainst(scene, uploaded);
                 forceUpload = false;
-                if (prims == null) Upload();        // a new mesh, grid or material (chunk streaming): the whole scene again
+                if (prims == null) Upload();        // a new mesh or material: the whole scene again
                 else
                 {
                     fixed (YPrim* p = prims) Ycge.Check(ctx, Ycge.ycge_scene_update_objects(ctx, p, prims.Length));     // only the scene-level BVH is rebuilt, as in the reference
                     uploaded.Prims = prims;
+                    DetachVolumeGrids();
                     objectsSignature = ObjectsSignature();
                 }
             }

@@ -45,7 +45,7 @@ namespace ConsoleGame.RayTracing.Native
         public YLight[] Lights = Array.Empty<YLight>();
         public readonly List<Texture> Textures = new List<Texture>();        // index in YScene.Textures -> the Texture it came from
         public readonly List<Mesh> MeshOwners = new List<Mesh>();            // the Mesh objects behind YScene.Meshes, in order
-        public readonly List<VolumeGrid> GridOwners = new List<VolumeGrid>();  // the VolumeGrid objects behind YScene.Grids, in order
+        public readonly List<VolumeGrid> GridOwners = new List<VolumeGrid>();  // the VolumeGrid objects behind the device's grid indices (upload order, then ycge_scene_attach_grids; null = a free slot)
         public YMaterial[] Materials = Array.Empty<YMaterial>();
         private readonly List<GCHandle> pins = new List<GCHandle>();
         private readonly List<IntPtr> blocks = new List<IntPtr>();
@@ -395,6 +395,18 @@ namespace ConsoleGame.RayTracing.Native
                 return flat;
             }
             catch { flat.Dispose(); throw; }
+        }
+
+        /// <summary>One VolumeGrid as a ycge_grid against the materials of the last upload - for ycge_scene_attach_grids when a chunk enters the
+        /// view (WorldManager.LoadChunksAround, WorldManager.cs:289-370).  `scratch` owns the cells and the lookup table until the call has
+        /// returned.  False when the grid needs a material the last upload did not hold: the caller uploads the scene again.</summary>
+        public static bool FlattenGrid(VolumeGrid g, FlatScene uploaded, FlatScene scratch, out YGrid record)
+        {
+            var mats = new MaterialTable();
+            foreach (YMaterial m in uploaded.Materials) mats.Records.Add(m);
+            mats.Textures.AddRange(uploaded.Textures);
+            record = GridRecord(g, mats, scratch);
+            return mats.Records.Count == uploaded.Materials.Length && mats.Textures.Count == uploaded.Textures.Count;
         }
 
         /// <summary>Only Scene.Objects again, against the materials / meshes / grids of the last upload - for ycge_scene_update_objects after an

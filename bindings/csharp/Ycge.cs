@@ -186,6 +186,9 @@ namespace ConsoleGame.RayTracing.Native
         [DllImport(Lib)] public static extern int ycge_validate_scene(ref YScene scene, byte* msg, UIntPtr msgBytes);
         [DllImport(Lib)] public static extern int ycge_scene_update_lights(IntPtr ctx, YLight* lights, int nLights, YVec3* ambientColor, float ambientIntensity, YVec3* top, YVec3* bottom);
         [DllImport(Lib)] public static extern int ycge_scene_update_objects(IntPtr ctx, YPrim* prims, int nPrims);
+        // chunk streaming (found by symbol lookup, ABI stays 10): grids beside those of the last upload, and their slots given back
+        [DllImport(Lib)] public static extern int ycge_scene_attach_grids(IntPtr ctx, YGrid* grids, int n, int* outGridIndex);
+        [DllImport(Lib)] public static extern int ycge_scene_detach_grids(IntPtr ctx, int* gridIndex, int n);
         [DllImport(Lib)] public static extern int ycge_scene_update_texture(IntPtr ctx, int textureIndex, IntPtr frame, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_resize(IntPtr ctx, int fbWidth, int fbHeight, int superSample);
         [DllImport(Lib)] public static extern int ycge_set_camera(IntPtr ctx, float* pos, float yaw, float pitch, float fovDeg);

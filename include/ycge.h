@@ -332,11 +332,48 @@ int ycge_scene_update_lights(ycge_ctx *ctx, const ycge_light *lights, int32_t n_
 
 /* Scene.Update() -> RebuildBVH() after an entity moved its geometry (Scenes/Scene.cs:122-127; e.g.
  * BobbingSphereEntity.Update, Scenes/TestScenesRandom.cs:708-714): replaces the Scene.Objects records and
- * rebuilds the scene-level BVH only.  `prims` index the materials, meshes and grids of the last
- * ycge_scene_upload (a Mesh keeps its own BVH in the reference too, Mesh.cs:14).  The tree (Objects/BVH.cs:258-459,
+ * rebuilds the scene-level BVH only.  `prims` index the materials and meshes of the last ycge_scene_upload (a Mesh keeps its own
+ * BVH in the reference too, Mesh.cs:14) and the RESIDENT grids: those of the upload and of ycge_scene_attach_grids, less the detached.  The tree (Objects/BVH.cs:258-459,
  * same nodes, numbering and leaf order) is built on the device for up to 2 560 objects - the host only flattens the
  * records and their boxes - and by the host builder above that. */
 int ycge_scene_update_objects(ycge_ctx *ctx, const ycge_prim *prims, int32_t n_prims);
+
+/* --- chunk streaming: VolumeScene.Update calls WorldManager.LoadChunksAround every frame (Scenes/VolumeScenes.cs:63-64): chunks that
+ * entered the view are attached as new VolumeGrids, chunks that left are removed from Scene.Objects and cached (WorldManager.cs:289-370).
+ * Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, ycge_config and ycge_scene are unchanged - a host detects these two
+ * exports by symbol lookup.  One LoadChunksAround tick is: attach what entered, ycge_scene_update_objects with the new object list,
+ * detach what left - or leave it resident and merely unreferenced, which is the reference's chunk cache (CacheChunk /
+ * TryAttachFromCache).  Each of the three steps leaves a complete, renderable scene.
+ *   Same pixels.  After any sequence of attach / update_objects / detach, every frame, every ycge_read_buffer buffer, every scene query,
+ *     the counting instances' ycge_frame_stats counters and ycge_read_timed_steps are what the same context gives when each tick is
+ *     instead one ycge_scene_upload of the equivalent scene (same materials, same Scene.Objects in the same order, the grids they refer
+ *     to) - bit for bit, TAA history and exposure state included.  Grid indices, cell codes and arena offsets are internal and may differ.
+ *   Indices.  A grid of the upload keeps its index.  An attached grid takes the lowest free index (slots are reused); out_grid_index is
+ *     written only on success.  The next ycge_scene_upload forgets all of it.
+ *   Limits are ycge_grid's own (2^30 cells, 2^23 bricks per face, 255 distinct pairs, 4 GiB of voxel bytes RESIDENT), refused with the
+ *     statuses ycge_scene_upload gives.  n = 0 is YCGE_OK.  YCGE_ERR_NO_SCENE before the first upload.  A grid that is wrong in two
+ *     ways - a pair with no material and more than 255 distinct pairs - is refused as the former (YCGE_ERR_INVALID_ARG, the message names
+ *     the lowest such cell in `cells` order), where ycge_scene_upload reports whichever its walk meets first.
+ *   All or nothing.  A refused or failed attach (bad argument, a pair with no material and default_material < 0, a limit, an allocation
+ *     failure) leaves the scene exactly as it was - renderable, no slot taken, out_grid_index untouched.  Stronger than ycge_scene_upload
+ *     (which leaves no scene) on purpose: a streaming host must survive one bad chunk.
+ *   A scene uploaded with no grid may receive grids: the kernel instantiation, the walk tree and the stage-pipeline decision follow at the
+ *     next ycge_scene_update_objects, as after an upload of the equivalent scene - they follow the grids Scene.Objects refer to, so
+ *     grids that stay resident and unreferenced (the chunk cache) change nothing.
+ *   Several devices: the devices of a one-process multi-device context are served one after the other (an attach is serial in their number).
+ *   Frames in flight.  ycge_scene_attach_grids JOINS the frames in flight, like every other scene call: it may move the cell arena, the
+ *     material tables and the grid table, which the frames read (ycge_scene_update_objects, the next step of a tick, joins them anyway).
+ *     ycge_scene_detach_grids changes host state only and joins nothing.  Scene queries see the new grids with the next query.
+ *   One-process multi-device (n_devices >= 2): the root forwards to its peers as ycge_scene_upload does; a peer context refuses.  Tiled
+ *     ranks (world_size > 1) each make the same calls, like every other scene call.
+ * The raw cells go up once through page-locked staging and are encoded on the device (csrc/ycge_grid_encode.hip); a grid whose lookup
+ * table has more than 254 entries takes the host encoder of ycge_scene_upload. */
+/* Make n more grids resident beside those of the last ycge_scene_upload.  No object refers to them yet: the next
+ * ycge_scene_update_objects may (ycge_prim.ref = out_grid_index[k]).  Materials index the materials of the last upload. */
+int ycge_scene_attach_grids(ycge_ctx *ctx, const ycge_grid *grids, int32_t n, int32_t *out_grid_index /* n */);
+/* Give n grids' slots back.  Refused (YCGE_ERR_INVALID_ARG, nothing freed) while the current Scene.Objects refer to one of them,
+ * for an index that is not resident, or for one named twice. */
+int ycge_scene_detach_grids(ycge_ctx *ctx, const int32_t *grid_index, int32_t n);
 
 /* The argument checks of ycge_scene_upload on their own: pure host code, no device and no context needed
  * (every index in range, counts non-negative, pointers present, material kinds known).  Returns YCGE_OK or the

@@ -54,6 +54,9 @@ int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */
 int ycge_debug_device_bvh(const float *bounds, const float *centroids, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *result_out, void *build_out);   /* k_scene_bvh_build alone */
 int ycge_debug_read_walk_tree(ycge_ctx *c, void *gnodes_out, void *walk_out, int32_t capacity_nodes, int32_t *grid_owner_out, int32_t n_grids, uint32_t *root_and_limit_out);
+int ycge_debug_read_grid(ycge_ctx *c, int32_t grid_index, void *record_out /* sizeof GGrid = 112 bytes */, int32_t *materials_out);   /* a resident grid as the device holds it: its record and, per voxel in ycge_grid.cells order, the material of its cell code (-1 = empty) */
+ycge_ctx *ycge_debug_peer_context(ycge_ctx *c, int32_t k);           /* the context of device k + 1 of a one-process multi-device context (NULL: none): the scene calls refuse it */
+int ycge_debug_grid_pool_stats(ycge_ctx *c, int64_t *out12);         /* resident grids, free indices, arena bytes in use, arena capacity, arena growths, slots reused, device encodes, host-fallback encodes; the last attach in us: staging copy, host-to-device copy, encode kernel, read-back */
 int ycge_debug_read_post_progress(ycge_ctx *c, uint32_t *dst, size_t n_words);               /* k_atrous_stream's per-band records (profiles/post_bands.py) */
 int ycge_debug_read_wave_prof(ycge_ctx *c, unsigned long long *dst, size_t n_u64);            /* per-wavefront begin / end / steps of a profiling build (profiles/mega_prof.py) */
 int ycge_debug_read_coop_stats(ycge_ctx *c, uint64_t out[16]);                               /* -DYCGE_DBG_COOPSTAT builds */

@@ -188,6 +188,8 @@ _PROTOTYPES = {
     "ycge_scene_update_lights": (C.c_int, [C.c_void_p, C.POINTER(Light), C.c_int32, C.POINTER(Vec3), C.c_float,
                                            C.POINTER(Vec3), C.POINTER(Vec3)]),
     "ycge_scene_update_objects": (C.c_int, [C.c_void_p, C.POINTER(Prim), C.c_int32]),
+    "ycge_scene_attach_grids": (C.c_int, [C.c_void_p, C.POINTER(Grid), C.c_int32, C.POINTER(C.c_int32)]),
+    "ycge_scene_detach_grids": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "ycge_scene_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ycge_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]),
@@ -230,6 +232,14 @@ _PROTOTYPES = {
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
+# test / profiling hooks of chunk streaming (include/ycge_hooks.h; not part of the boundary)
+GGRID_BYTES = 112
+HOOK_PROTOTYPES = {
+    "ycge_debug_read_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ycge_debug_grid_pool_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ycge_debug_peer_context": (C.c_void_p, [C.c_void_p, C.c_int32]),
+}
+
 _lib = None
 
 
@@ -247,6 +257,11 @@ def bind(lib: C.CDLL, prefix: str = "ycge_", names=None) -> C.CDLL:
         fn = getattr(lib, prefix + name[len("ycge_"):])
         fn.restype = res
         fn.argtypes = args
+    if prefix == "ycge_" and names is None:
+        for name, (res, args) in HOOK_PROTOTYPES.items():
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = res, args
     return lib
 
 

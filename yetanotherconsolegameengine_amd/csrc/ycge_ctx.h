@@ -18,8 +18,10 @@
 #include <cstring>
 #include <deque>
 #include <condition_variable>
+#include <map>
 #include <mutex>
 #include <new>
+#include <set>
 #include <stdexcept>
 #include <system_error>
 #include <thread>
@@ -84,6 +86,7 @@ int ycge_launch_chexels(const float *sdr, int fbW, int fbH, const uint8_t *table
 uint32_t ycge_launch_ansi_tiles(uint32_t cells);
 int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
                             int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
+int ycge_launch_grid_encode(const void *descs, int n_grids, void *results, uint32_t n_workgroups, hipStream_t stream);
 int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
 }
@@ -233,6 +236,26 @@ struct FrameState {
 
 struct MeshHost {
     BuiltTree tree;
+};
+
+// The resident voxel grids of a scene (ycge_grid_encode.cpp): the grids of the last ycge_scene_upload keep their indices and its packing;
+// ycge_scene_attach_grids takes the lowest free index, a block of the cell arena (size-keyed free list, 256-byte alignment, else the end of
+// the arena, which grows geometrically) and a 256-entry region of the LUT; ycge_scene_detach_grids gives index, block and region back.
+// Kept by the root context; every device of a multi-device context holds the same layout.
+struct GridPool {
+    std::vector<GGrid> recs;                 // host mirror of d_grids, one per slot (a free slot: zeros)
+    std::vector<uint8_t> resident;           // per slot: 1 = a grid lives here (a prim may refer to it)
+    std::vector<uint32_t> block_bytes;       // per slot: bytes of its block of the cell arena
+    std::vector<int32_t> lut_region;         // per slot: first entry of its 256-entry LUT region; -1: the upload's packed entries (not given back)
+    std::vector<int32_t> owner;              // per slot: the object of the current Scene.Objects that holds it (-1: none)
+    std::set<int32_t> free_index;            // free slots below recs.size()
+    std::multimap<uint32_t, uint32_t> free_blocks;   // size -> byte offset
+    std::vector<uint32_t> free_luts;
+    uint64_t arena_end = 0, lut_end = 0;     // the first byte / entry never handed out
+    uint64_t arena_in_use = 0;               // bytes of the resident grids' blocks
+    int64_t n_resident = 0, growths = 0, slots_reused = 0, device_encodes = 0, host_encodes = 0;
+    bool streamed = false;                   // an attach or a detach has changed the set since the last upload
+    double last_attach_us[4] = {0, 0, 0, 0};  // the last attach: copy into the staging, host-to-device copy, encode kernel, read-back
 };
 
 } // namespace ycge_host
@@ -428,6 +451,11 @@ struct ycge_ctx {
     DevBuf<GMaterial> d_materials;
     DevBuf<GMesh> d_meshes;
     DevBuf<GGrid> d_grids;
+    GridPool grid_pool;                // (root context)
+    // ycge_scene_attach_grids: the batch's descriptors, results, lookup tables and raw cells in page-locked memory (root) and on this
+    // device; encoded bytes that wait for the arena to grow
+    void *enc_stage = nullptr; size_t enc_stage_bytes = 0;
+    DevBuf<uint8_t> d_enc_in, d_enc_out;
     DevBuf<uint8_t> d_cells;
     DevBuf<int32_t> d_lut;
     DevBuf<uint32_t> d_tex_pixels;             // textures of YCGE_MAT_TEXTURED materials
@@ -523,6 +551,14 @@ bool frame_is_single_launch(const ycge_ctx *c);
 bool should_reset_history(const ycge_ctx *c, const float pos[3], float yaw, float pitch);
 void fill_frame_params(ycge_ctx *c, ycge::FrameParams &P, int64_t frame, const float pos[3], float yaw, float pitch, float fov_deg);
 int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, bool timed, hipEvent_t launch_begin = nullptr, hipEvent_t launch_end = nullptr, const ResidentTarget *rt = nullptr);
+int validate_grid(const ycge_grid &g, int gi, int n_materials, std::string &msg);          // ycge_host.cpp: one grid's argument checks
+void grid_record_init(const ycge_grid &g, GGrid &G);                                       // ... its record from the arguments (clamps, cull_t_limit)
+void grid_record_solid(GGrid &G, const int lo[3], const int hi[3], uint64_t brick_mask);   // ... and from the solid voxels' index box
+std::array<float, 6> grid_world_bounds(const ycge_grid &g);
+int encode_grid_host(ycge_ctx *c, const ycge_grid &g, int gi, int n_materials, const GGrid &G, uint8_t *cells, std::vector<int32_t> &lut, int lo[3], int hi[3],
+                     uint64_t &brick_mask);                                                  // the host encoder (first-seen codes)
+void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_bytes, size_t lut_entries);   // ycge_grid_encode.cpp: after an upload
+void release_grid_pool(ycge_ctx *c);                                                        // ycge_grid_encode.cpp: staging and scratch (ycge_destroy)
 int query_scene_changed(ycge_ctx *c);       // ycge_query.cpp: record scene_ev behind a scene upload / objects update
 void release_query(ycge_ctx *c);             // ycge_query.cpp: drain the query stream, then free what the queries hold
 int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second);   // ycge_chexel.cpp: run_post's encode behind the tonemap (a no-op unless a _chexels call asked)

@@ -520,6 +520,7 @@ try {
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     release_query(c);          // (drains the query stream first)
     release_chexels(c, true);
+    release_grid_pool(c);
     c->current_hdr.release(); c->g_albedo.release(); c->g_normal.release(); c->g_depth.release(); c->taa_hist.release();
     c->prev_normal.release(); c->prev_depth.release(); c->sky.release(); c->prev_sky.release();
     c->dbg_rays.release(); c->dbg_hit_t.release(); c->dbg_prim.release(); c->dbg_sub.release(); c->dbg_rng.release();
@@ -671,6 +672,100 @@ int quiesce(ycge_ctx *c)
     return YCGE_OK;
 }
 
+// ---- one ycge_grid: the argument checks and the host arithmetic of its record, shared by ycge_scene_upload and ycge_scene_attach_grids
+int validate_grid(const ycge_grid &g, int gi, int n_materials, std::string &msg)
+{
+    char buf[256];
+    auto bad = [&](int code, const char *fmt, int a = 0, int b = 0) { std::snprintf(buf, sizeof buf, fmt, a, b); msg = buf; return code; };
+    if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0 || !g.cells) return bad(YCGE_ERR_INVALID_ARG, "grid %d: empty", gi);
+    if ((uint64_t)g.nx * g.ny * g.nz >= (1u << 30)) return bad(YCGE_ERR_UNSUPPORTED, "grid %d: more than 2^30 cells", gi);
+    // (the voxel walk forms brick indices with 24-bit multiplies: ((z >> 3) * bricks_y + (y >> 3)) * bricks_x)
+    if ((uint64_t)((g.nz + 7) >> 3) * (uint64_t)((g.ny + 7) >> 3) >= (1u << 23) || ((g.nx + 7) >> 3) >= (1 << 23))
+        return bad(YCGE_ERR_UNSUPPORTED, "grid %d: more than 2^23 bricks across one face", gi);
+    if (g.n_lookup < 0 || (g.n_lookup > 0 && !g.lookup)) return bad(YCGE_ERR_INVALID_ARG, "grid %d: bad lookup table", gi);
+    for (int k = 0; k < g.n_lookup; k++)
+        if (g.lookup[k].material < 0 || g.lookup[k].material >= n_materials) return bad(YCGE_ERR_INVALID_ARG, "grid %d: lookup entry %d names a material out of range", gi, k);
+    return YCGE_OK;
+}
+
+// the record's fields that come from the arguments alone (VolumeGrid ctor, VolumeGrid.cs:55-93); cell_offset, lut_offset and the solid box follow
+void grid_record_init(const ycge_grid &g, GGrid &G)
+{
+    std::memset(&G, 0, sizeof G);
+    G.nx = g.nx; G.ny = g.ny; G.nz = g.nz;
+    G.nbx = (g.nx + 7) >> 3; G.nby = (g.ny + 7) >> 3; G.nbz = (g.nz + 7) >> 3;
+    G.min_corner[0] = g.min_corner.x; G.min_corner[1] = g.min_corner.y; G.min_corner[2] = g.min_corner.z;
+    G.voxel_size[0] = cs_max(1e-6f, g.voxel_size.x); G.voxel_size[1] = cs_max(1e-6f, g.voxel_size.y); G.voxel_size[2] = cs_max(1e-6f, g.voxel_size.z);
+    G.wireframe = g.wireframe ? 1 : 0;
+    float ww = g.wire_width_fraction; if (ww < 0.0f) ww = 0.0f; if (ww > 0.5f) ww = 0.5f;
+    G.wire_width_frac = ww;
+    float wm = g.wire_max_distance; if (wm < 0.0f) wm = 0.0f;
+    G.wire_max_distance = wm;
+    // How far along a ray the one-voxel margin of the solid box is provably enough.  The reference's walk reaches a cell by repeated
+    // binary32 additions to tMax (VolumeGrid.cs:205-226): after k steps its t is off by at most k * ulp(t) / 2, i.e. the cell path
+    // may drift k * t * 2^-24 world units from the true ray, with k <= nx + ny + nz steps inside one grid.  The cull (and the early
+    // end of a walk at the box's exit) assumes that drift stays below HALF a voxel: t <= voxel * 2^23 / (nx + ny + nz) - 87 000 voxel
+    // lengths for a 32^3 chunk; half of that is what is stored.  Beyond it the timed kernels walk the grid as the reference does.
+    const float vs = cs_min(G.voxel_size[0], cs_min(G.voxel_size[1], G.voxel_size[2]));
+    G.cull_t_limit = vs * 4194304.0f / (float)(G.nx + G.ny + G.nz);
+    G.has_brick_mask = (size_t)G.nbx * G.nby * G.nbz <= 64 ? 1 : 0;
+}
+
+// ... and those that come from the cells: the index box lo..hi of the solid voxels (hi < 0: none) and the brick mask
+void grid_record_solid(GGrid &G, const int lo[3], const int hi[3], uint64_t brick_mask)
+{
+    for (int a = 0; a < 3; a++) {           // one voxel of margin on every side (GGrid::solid_lo / solid_hi)
+        G.solid_lo[a] = hi[a] < 0 ? 1.0f : G.min_corner[a] + (float)(lo[a] - 1) * G.voxel_size[a];
+        G.solid_hi[a] = hi[a] < 0 ? 0.0f : G.min_corner[a] + (float)(hi[a] + 2) * G.voxel_size[a];
+    }
+    G.brick_mask_lo = (uint32_t)brick_mask; G.brick_mask_hi = (uint32_t)(brick_mask >> 32);
+}
+
+std::array<float, 6> grid_world_bounds(const ycge_grid &g)          // VolumeGrid.TryGetBounds, VolumeGrid.cs:95-97
+{
+    const float vs[3] = {cs_max(1e-6f, g.voxel_size.x), cs_max(1e-6f, g.voxel_size.y), cs_max(1e-6f, g.voxel_size.z)};
+    return {{g.min_corner.x, g.min_corner.y, g.min_corner.z, g.min_corner.x + (float)g.nx * vs[0], g.min_corner.y + (float)g.ny * vs[1],
+             g.min_corner.z + (float)g.nz * vs[2]}};
+}
+
+// The host encoder: one byte per voxel = index into a per-grid material table.  `cells` = the grid's nbx * nby * nbz * 512 zeroed bytes,
+// `lut` receives the table (entry 0 = -1: empty; codes 1.. = distinct (matId, metaId) pairs in first-seen order, at most 255).
+int encode_grid_host(ycge_ctx *c, const ycge_grid &g, int gi, int n_materials, const GGrid &G, uint8_t *cells, std::vector<int32_t> &lut, int lo[3], int hi[3],
+                     uint64_t &brick_mask)
+{
+    auto mat_ok = [&](int mi) { return mi >= 0 && mi < n_materials; };
+    std::vector<std::pair<int32_t, int32_t>> seen;
+    lut.push_back(-1);
+    const bool maskable = G.has_brick_mask != 0;
+    brick_mask = 0;
+    lo[0] = g.nx; lo[1] = g.ny; lo[2] = g.nz; hi[0] = hi[1] = hi[2] = -1;          // index box of the solid voxels
+    for (int iz = 0; iz < g.nz; iz++)
+        for (int iy = 0; iy < g.ny; iy++)
+            for (int ix = 0; ix < g.nx; ix++) {
+                const size_t src = ((size_t)ix * g.ny + iy) * g.nz + iz;
+                const int32_t mat = g.cells[2 * src], meta = g.cells[2 * src + 1];
+                if (mat <= 0) continue;
+                int code = -1;
+                for (size_t k = 0; k < seen.size(); k++) if (seen[k].first == mat && seen[k].second == meta) { code = (int)k + 1; break; }
+                if (code < 0) {
+                    if (seen.size() >= 255) return c->fail(YCGE_ERR_UNSUPPORTED, "grid %d: more than 255 distinct (matId, metaId) pairs", gi);
+                    int material = g.default_material;
+                    for (int k = 0; k < g.n_lookup; k++) if (g.lookup[k].mat_id == mat && g.lookup[k].meta_id == meta) { material = g.lookup[k].material; break; }
+                    if (!mat_ok(material)) return c->fail(YCGE_ERR_INVALID_ARG, "grid %d: no material for (matId %d, metaId %d)", gi, mat, meta);
+                    seen.push_back({mat, meta});
+                    lut.push_back(material);
+                    code = (int)seen.size();
+                }
+                const int brick = (((iz >> 3) * G.nby) + (iy >> 3)) * G.nbx + (ix >> 3);
+                cells[(size_t)brick * 512 + morton3(ix & 7, iy & 7, iz & 7)] = (uint8_t)code;
+                if (maskable) brick_mask |= (uint64_t)1 << brick;
+                if (ix < lo[0]) lo[0] = ix; if (ix > hi[0]) hi[0] = ix;
+                if (iy < lo[1]) lo[1] = iy; if (iy > hi[1]) hi[1] = iy;
+                if (iz < lo[2]) lo[2] = iz; if (iz > hi[2]) hi[2] = iz;
+            }
+    return YCGE_OK;
+}
+
 // ---- argument checks of ycge_scene_upload (pure host code; also exported as ycge_validate_scene)
 int validate_scene(const ycge_scene *s, std::string &msg)
 {
@@ -705,15 +800,8 @@ int validate_scene(const ycge_scene *s, std::string &msg)
                 if (!mat_ok(m.tri_material[t])) return bad(YCGE_ERR_INVALID_ARG, "mesh %d: triangle material out of range", mi);
     }
     for (int gi = 0; gi < s->n_grids; gi++) {
-        const ycge_grid &g = s->grids[gi];
-        if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0 || !g.cells) return bad(YCGE_ERR_INVALID_ARG, "grid %d: empty", gi);
-        if ((uint64_t)g.nx * g.ny * g.nz >= (1u << 30)) return bad(YCGE_ERR_UNSUPPORTED, "grid %d: more than 2^30 cells", gi);
-        // (the voxel walk forms brick indices with 24-bit multiplies: ((z >> 3) * bricks_y + (y >> 3)) * bricks_x)
-        if ((uint64_t)((g.nz + 7) >> 3) * (uint64_t)((g.ny + 7) >> 3) >= (1u << 23) || ((g.nx + 7) >> 3) >= (1 << 23))
-            return bad(YCGE_ERR_UNSUPPORTED, "grid %d: more than 2^23 bricks across one face", gi);
-        if (g.n_lookup < 0 || (g.n_lookup > 0 && !g.lookup)) return bad(YCGE_ERR_INVALID_ARG, "grid %d: bad lookup table", gi);
-        for (int k = 0; k < g.n_lookup; k++)
-            if (!mat_ok(g.lookup[k].material)) return bad(YCGE_ERR_INVALID_ARG, "grid %d: lookup entry %d names a material out of range", gi, k);
+        const int rc = validate_grid(s->grids[gi], gi, s->n_materials, msg);
+        if (rc != YCGE_OK) return rc;
     }
     for (int i = 0; i < s->n_prims; i++) {
         const ycge_prim &q = s->prims[i];
@@ -795,7 +883,7 @@ int flatten_objects(ycge_ctx *c, const ycge_prim *prims, int n_prims, ObjectsHos
             break;
         }
         case YCGE_PRIM_VOLUME_GRID:
-            if (q.ref < 0 || q.ref >= (int)c->grid_bounds.size()) return c->fail(YCGE_ERR_INVALID_ARG, "prim %d: grid ref out of range", i);
+            if (q.ref < 0 || q.ref >= (int)c->grid_bounds.size() || !c->grid_pool.resident[(size_t)q.ref]) return c->fail(YCGE_ERR_INVALID_ARG, "prim %d: grid ref out of range", i);
             for (int k = 0; k < 7; k++) g.p[k] = c->grid_solid[q.ref][k];       // box of the grid's solid voxels + how far along a ray it may be trusted (grid_cull in the walk)
             if (oh.grid_owner[(size_t)q.ref] >= 0) oh.grid_owner_unique = false;
             oh.grid_owner[(size_t)q.ref] = i;
@@ -1177,67 +1265,18 @@ try {
     for (int gi = 0; gi < s->n_grids; gi++) {
         const ycge_grid &g = s->grids[gi];
         GGrid &G = ggrids[gi];
-        std::memset(&G, 0, sizeof G);
-        G.nx = g.nx; G.ny = g.ny; G.nz = g.nz;
-        G.nbx = (g.nx + 7) >> 3; G.nby = (g.ny + 7) >> 3; G.nbz = (g.nz + 7) >> 3;
-        G.min_corner[0] = g.min_corner.x; G.min_corner[1] = g.min_corner.y; G.min_corner[2] = g.min_corner.z;
-        G.voxel_size[0] = cs_max(1e-6f, g.voxel_size.x); G.voxel_size[1] = cs_max(1e-6f, g.voxel_size.y); G.voxel_size[2] = cs_max(1e-6f, g.voxel_size.z);
-        G.wireframe = g.wireframe ? 1 : 0;
-        float ww = g.wire_width_fraction; if (ww < 0.0f) ww = 0.0f; if (ww > 0.5f) ww = 0.5f;
-        G.wire_width_frac = ww;
-        float wm = g.wire_max_distance; if (wm < 0.0f) wm = 0.0f;
-        G.wire_max_distance = wm;
+        grid_record_init(g, G);
         const size_t cap = (size_t)G.nbx * G.nby * G.nbz * 512;
         const size_t off = (cells.size() + 255) & ~(size_t)255;
         if (off + cap >= ((size_t)1 << 32)) return c->fail(YCGE_ERR_UNSUPPORTED, "voxel storage exceeds 4 GiB");
         G.cell_offset = (uint32_t)off;
         cells.resize(off + cap, 0);
         G.lut_offset = (uint32_t)lut.size();
-        // code 0 = empty; codes 1.. = distinct (matId, metaId) pairs in first-seen order
-        std::vector<std::pair<int32_t, int32_t>> seen;
-        lut.push_back(-1);
-        const bool maskable = (size_t)G.nbx * G.nby * G.nbz <= 64;
+        int lo[3], hi[3];
         uint64_t brick_mask = 0;
-        int lo[3] = {g.nx, g.ny, g.nz}, hi[3] = {-1, -1, -1};          // index box of the solid voxels
-        for (int iz = 0; iz < g.nz; iz++)
-            for (int iy = 0; iy < g.ny; iy++)
-                for (int ix = 0; ix < g.nx; ix++) {
-                    const size_t src = ((size_t)ix * g.ny + iy) * g.nz + iz;
-                    const int32_t mat = g.cells[2 * src], meta = g.cells[2 * src + 1];
-                    if (mat <= 0) continue;
-                    int code = -1;
-                    for (size_t k = 0; k < seen.size(); k++) if (seen[k].first == mat && seen[k].second == meta) { code = (int)k + 1; break; }
-                    if (code < 0) {
-                        if (seen.size() >= 255) return c->fail(YCGE_ERR_UNSUPPORTED, "grid %d: more than 255 distinct (matId, metaId) pairs", gi);
-                        int material = g.default_material;
-                        for (int k = 0; k < g.n_lookup; k++) if (g.lookup[k].mat_id == mat && g.lookup[k].meta_id == meta) { material = g.lookup[k].material; break; }
-                        if (!mat_ok(material)) return c->fail(YCGE_ERR_INVALID_ARG, "grid %d: no material for (matId %d, metaId %d)", gi, mat, meta);
-                        seen.push_back({mat, meta});
-                        lut.push_back(material);
-                        code = (int)seen.size();
-                    }
-                    const int brick = (((iz >> 3) * G.nby) + (iy >> 3)) * G.nbx + (ix >> 3);
-                    cells[off + (size_t)brick * 512 + morton3(ix & 7, iy & 7, iz & 7)] = (uint8_t)code;
-                    if (maskable) brick_mask |= (uint64_t)1 << brick;
-                    if (ix < lo[0]) lo[0] = ix; if (ix > hi[0]) hi[0] = ix;
-                    if (iy < lo[1]) lo[1] = iy; if (iy > hi[1]) hi[1] = iy;
-                    if (iz < lo[2]) lo[2] = iz; if (iz > hi[2]) hi[2] = iz;
-                }
-        for (int a = 0; a < 3; a++) {           // one voxel of margin on every side (GGrid::solid_lo / solid_hi)
-            G.solid_lo[a] = hi[a] < 0 ? 1.0f : G.min_corner[a] + (float)(lo[a] - 1) * G.voxel_size[a];
-            G.solid_hi[a] = hi[a] < 0 ? 0.0f : G.min_corner[a] + (float)(hi[a] + 2) * G.voxel_size[a];
-        }
-        // How far along a ray the one-voxel margin of that box is provably enough.  The reference's walk reaches a cell by repeated
-        // binary32 additions to tMax (VolumeGrid.cs:205-226): after k steps its t is off by at most k * ulp(t) / 2, i.e. the cell path
-        // may drift k * t * 2^-24 world units from the true ray, with k <= nx + ny + nz steps inside one grid.  The cull (and the early
-        // end of a walk at the box's exit) assumes that drift stays below HALF a voxel: t <= voxel * 2^23 / (nx + ny + nz) - 87 000 voxel
-        // lengths for a 32^3 chunk; half of that is what is stored.  Beyond it the timed kernels walk the grid as the reference does.
-        {
-            const float vs = cs_min(G.voxel_size[0], cs_min(G.voxel_size[1], G.voxel_size[2]));
-            G.cull_t_limit = vs * 4194304.0f / (float)(G.nx + G.ny + G.nz);
-        }
-        G.has_brick_mask = maskable ? 1 : 0;
-        G.brick_mask_lo = (uint32_t)brick_mask; G.brick_mask_hi = (uint32_t)(brick_mask >> 32);
+        const int erc = encode_grid_host(c, g, gi, s->n_materials, G, cells.data() + off, lut, lo, hi, brick_mask);
+        if (erc != YCGE_OK) return erc;
+        grid_record_solid(G, lo, hi, brick_mask);
     }
 
     // ---- what the object / scene-BVH step needs (kept for ycge_scene_update_objects)
@@ -1247,13 +1286,7 @@ try {
     c->materials_can_mirror = false;
     for (int i = 0; i < s->n_materials; i++) if (s->materials[i].reflectivity >= c->cfg.mirror_threshold) c->materials_can_mirror = true;
     c->grid_bounds.assign(s->n_grids, std::array<float, 6>{{0, 0, 0, -1, -1, -1}});
-    for (int gi = 0; gi < s->n_grids; gi++) {                // VolumeGrid.TryGetBounds, VolumeGrid.cs:95-97
-        const ycge_grid &g = s->grids[gi];
-        if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) continue;
-        const float vs[3] = {cs_max(1e-6f, g.voxel_size.x), cs_max(1e-6f, g.voxel_size.y), cs_max(1e-6f, g.voxel_size.z)};
-        c->grid_bounds[gi] = {{g.min_corner.x, g.min_corner.y, g.min_corner.z, g.min_corner.x + (float)g.nx * vs[0],
-                               g.min_corner.y + (float)g.ny * vs[1], g.min_corner.z + (float)g.nz * vs[2]}};
-    }
+    for (int gi = 0; gi < s->n_grids; gi++) c->grid_bounds[gi] = grid_world_bounds(s->grids[gi]);
     c->grid_solid.resize(s->n_grids);
     for (int gi = 0; gi < s->n_grids; gi++)
     {
@@ -1261,6 +1294,7 @@ try {
         c->grid_solid[gi][6] = A.ggrids[gi].cull_t_limit;
     }
     A.has_grid = s->n_grids > 0;
+    grid_pool_reset(c, A.ggrids, cells.size(), lut.size());          // (ycge_grid_encode.cpp: every grid of the upload is resident, nothing is free)
 
     // ---- Scene.Objects + scene BVH, then every device gets the same arrays
     ObjectsHost oh;
@@ -1274,6 +1308,7 @@ try {
         if (rc != YCGE_OK) c->err = p->err;
     }
     (void)hipSetDevice(c->device);
+    if (rc == YCGE_OK) c->grid_pool.owner.swap(oh.grid_owner);
     if (rc == YCGE_OK) rc = query_scene_changed(c);
     return rc;
 }
@@ -1376,6 +1411,10 @@ try {
     for (ycge_ctx *p : c->peers) if (rc == YCGE_OK) rc = quiesce(p);
     if (rc != YCGE_OK) return rc;
     c->have_scene = false;
+    // after an attach or a detach the kernel instantiation follows the grids Scene.Objects refer to, as after an upload of the equivalent
+    // scene (which lists exactly those grids); a set the upload made keeps the upload's answer (its grid TABLE, used or not)
+    if (c->grid_pool.streamed) c->has_grid = oh.any_grid_object;
+    for (ycge_ctx *p : c->peers) p->has_grid = c->has_grid;
     const auto t0 = std::chrono::steady_clock::now();
     if (on_device) {
         rc = install_objects_device_built(c, c, oh, items);
@@ -1401,6 +1440,7 @@ try {
     c->bvh_last_build_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     (void)hipSetDevice(c->device);
     if (rc != YCGE_OK) return rc;
+    c->grid_pool.owner.swap(oh.grid_owner);
     c->have_scene = true;
     return query_scene_changed(c);
 }

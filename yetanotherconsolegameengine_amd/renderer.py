@@ -9,12 +9,13 @@ constructing a renderer without the built library or without an MI355X raises.
 from __future__ import annotations
 
 import ctypes as C
+import time
 from typing import Optional
 
 import numpy as np
 
 from . import abi
-from .scene import FlatScene, Scene, flatten
+from .scene import FlatScene, NeedsUpload, Scene, VolumeGrid, flatten, grid_record
 
 NODE_DTYPE = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"), ("count", "<i4")])
 
@@ -58,6 +59,8 @@ class RaytraceRenderer:
         self._set_dims(fb_width, fb_height, c.super_sample)
         self._pos, self._yaw, self._pitch, self._fov = (0.0, 1.0, 0.0), 0.0, 0.0, fovDeg
         self.flat = None
+        self._streamed = {}          # id -> VolumeGrid attached by AttachGrids and still resident
+        self.stream_call_s = {"attach": 0.0, "update": 0.0, "detach": 0.0}          # seconds inside the last library call of each kind (profiles/stream_rate.py)
         self.stats = abi.FrameStats()
         if scene is not None:
             self.UploadScene(scene)          # the C# ctor ends with scene.RebuildBVH() (:107)
@@ -96,6 +99,7 @@ class RaytraceRenderer:
     def UploadScene(self, scene: Scene | FlatScene):
         """scene.RebuildBVH() + upload (RaytraceRenderer.cs:107, RaytraceEntity.cs:244)."""
         self.flat = scene if hasattr(scene, "byref") else flatten(scene)          # (a FlatScene, or a scene file read back: tools/scene_file.py)
+        self._streamed = {}          # (the next upload forgets every attached grid)
         self._check(self.L.ycge_scene_upload(self.ctx, self.flat.byref()))
 
     def UpdateLights(self, lights, ambient=None, background_top=None, background_bottom=None):
@@ -121,8 +125,86 @@ class RaytraceRenderer:
         """Scene.Update() -> RebuildBVH() after entities moved (Scene.cs:122-127): same materials, meshes and grids
         as the uploaded scene (in the same first-use order), new object records; only the scene BVH is rebuilt."""
         f = scene if isinstance(scene, FlatScene) else flatten(scene, against=self.flat if hasattr(self.flat, "_mat_index") else None)          # (a Scene: numbered against the upload; NeedsUpload if it holds something new)
-        self._check(self.L.ycge_scene_update_objects(self.ctx, C.cast(f.prims, C.POINTER(abi.Prim)), f.struct.n_prims))
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_update_objects(self.ctx, C.cast(f.prims, C.POINTER(abi.Prim)), f.struct.n_prims)
+        self.stream_call_s["update"] = time.perf_counter() - t0
+        self._check(rc)
         self.flat = f
+
+    # ---------------------------------------------------------------- chunk streaming (ycge_scene_attach_grids / ycge_scene_detach_grids)
+    def AttachGrids(self, grids) -> list:
+        """Makes the VolumeGrids resident beside those of the upload and returns their device indices; no object refers to them until
+        the next UpdateObjects / StreamObjects.  Their materials must be materials of the uploaded scene (NeedsUpload otherwise)."""
+        grids = list(grids)
+        if not grids:
+            return []
+        if not hasattr(self.flat, "_mat_index"):
+            raise NeedsUpload("the uploaded scene was not flattened from a Scene: its materials cannot be matched")
+        mat_index = self.flat._mat_index
+
+        def mat_id(m):
+            if id(m) not in mat_index:
+                raise NeedsUpload("a material the uploaded scene does not hold")
+            return mat_index[id(m)]
+
+        keep = []
+        recs = (abi.Grid * len(grids))(*[grid_record(g, mat_id, keep) for g in grids])
+        out = (C.c_int32 * len(grids))()
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_attach_grids(self.ctx, recs, len(grids), out)
+        self.stream_call_s["attach"] = time.perf_counter() - t0          # (the library call alone: what a native host pays)
+        self._check(rc)
+        idx = [int(i) for i in out]
+        for g, i in zip(grids, idx):
+            self.flat._grid_index[id(g)] = i
+            self._streamed[id(g)] = g          # (keeps the object, hence its id, alive while it is resident)
+        return idx
+
+    def DetachGrids(self, indices) -> None:
+        """Gives the grids' slots back; refused while Scene.Objects (as of the last UpdateObjects) refer to one of them."""
+        indices = [int(i) for i in indices]
+        if not indices:
+            return
+        arr = (C.c_int32 * len(indices))(*indices)
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_detach_grids(self.ctx, arr, len(indices))
+        self.stream_call_s["detach"] = time.perf_counter() - t0
+        self._check(rc)
+        gone = set(indices)
+        for key in [k for k, i in self.flat._grid_index.items() if i in gone]:
+            del self.flat._grid_index[key]
+            self._streamed.pop(key, None)
+
+    def StreamObjects(self, scene: Scene, keep_cached: bool = False):
+        """The Scene.Update that follows WorldManager.LoadChunksAround: the scene's VolumeGrid objects (by identity) against the resident
+        ones - attach the new, UpdateObjects with the references mapped to device indices, detach what no longer appears (or keep it
+        resident and unreferenced when keep_cached: the reference's chunk cache).  Returns (attached indices, detached indices)."""
+        resident = self.flat._grid_index
+        self.stream_call_s.update(attach=0.0, update=0.0, detach=0.0)
+        wanted = [o for o in scene.Objects if isinstance(o, VolumeGrid)]
+        attached = self.AttachGrids([o for o in wanted if id(o) not in resident])
+        self.UpdateObjects(scene)
+        detached = []
+        if not keep_cached:
+            live = {id(o) for o in wanted}
+            detached = sorted(i for k, i in resident.items() if k not in live)
+            self.DetachGrids(detached)
+        return attached, detached
+
+    def grid_pool_stats(self) -> dict:
+        """The pool of resident grids (ycge_debug_grid_pool_stats) and the last attach's host-side split in microseconds."""
+        out = (C.c_int64 * 12)()
+        self._check(self.L.ycge_debug_grid_pool_stats(self.ctx, out))
+        keys = ("resident", "free_indices", "arena_in_use", "arena_capacity", "arena_growths", "slots_reused", "device_encodes", "host_encodes",
+                "last_stage_us", "last_h2d_us", "last_kernel_us", "last_readback_us")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def read_grid(self, index: int, shape):
+        """A resident grid as the device holds it (ycge_debug_read_grid): (record bytes, int32 material per voxel [nx, ny, nz], -1 = empty)."""
+        rec = np.zeros(abi.GGRID_BYTES, np.uint8)
+        mats = np.zeros(tuple(shape), np.int32)
+        self._check(self.L.ycge_debug_read_grid(self.ctx, int(index), rec.ctypes.data_as(C.c_void_p), mats.ctypes.data_as(C.c_void_p)))
+        return rec, mats
 
     # ---------------------------------------------------------------- scene queries (ycge_scene_hit / ycge_scene_occluded)
     @staticmethod

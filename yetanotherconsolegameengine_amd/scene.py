@@ -255,6 +255,36 @@ class NeedsUpload(ValueError):
     """flatten(scene, against=uploaded): the objects use a record the uploaded scene does not hold - upload the scene again"""
 
 
+def grid_record(o: "VolumeGrid", mat_id: Callable[[Material], int], keep: list) -> "abi.Grid":
+    """One VolumeGrid as a ycge_grid: its cells as they are, one lookup entry per distinct solid (matId, metaId) pair, the materials
+    numbered by `mat_id`; `keep` receives what the record points to."""
+    cells = np.ascontiguousarray(o.Cells, dtype=np.int32)
+    assert cells.ndim == 4 and cells.shape[3] == 2
+    keep.append(cells)
+    pairs = np.unique(cells.reshape(-1, 2), axis=0)
+    lut = []
+    for mid, meta in pairs:
+        if mid <= 0:
+            continue
+        lut.append((int(mid), int(meta), mat_id(o.MaterialLookup(int(mid), int(meta)))))
+    lut_arr = (abi.VoxelLookup * max(1, len(lut)))()
+    for i, (a, b, c) in enumerate(lut):
+        lut_arr[i].mat_id, lut_arr[i].meta_id, lut_arr[i].material = a, b, c
+    keep.append(lut_arr)
+    g = abi.Grid()
+    g.nx, g.ny, g.nz = cells.shape[0], cells.shape[1], cells.shape[2]
+    g.min_corner = abi.Vec3(*o.MinCorner)
+    g.voxel_size = abi.Vec3(*o.VoxelSize)
+    g.cells = cells.ctypes.data_as(C.POINTER(C.c_int32))
+    g.lookup = C.cast(lut_arr, C.POINTER(abi.VoxelLookup))
+    g.n_lookup = len(lut)
+    g.default_material = -1
+    g.wireframe = 1 if o.EnableWireframe else 0
+    g.wire_width_fraction = float(f32(o.WireWidthFraction))
+    g.wire_max_distance = float(f32(o.WireMaxDistance))
+    return g
+
+
 class FlatScene:
     """A `ycge_scene` plus the ctypes/numpy storage that keeps its pointers alive."""
 
@@ -331,30 +361,7 @@ class FlatScene:
                 meshes.append(m)
             elif isinstance(o, VolumeGrid):
                 self._grid_index[id(o)] = len(grids)
-                cells = np.ascontiguousarray(o.Cells, dtype=np.int32)
-                assert cells.ndim == 4 and cells.shape[3] == 2
-                self._keep.append(cells)
-                pairs = np.unique(cells.reshape(-1, 2), axis=0)
-                lut = []
-                for mid, meta in pairs:
-                    if mid <= 0:
-                        continue
-                    lut.append((int(mid), int(meta), mat_id(o.MaterialLookup(int(mid), int(meta)))))
-                lut_arr = (abi.VoxelLookup * max(1, len(lut)))()
-                for i, (a, b, c) in enumerate(lut):
-                    lut_arr[i].mat_id, lut_arr[i].meta_id, lut_arr[i].material = a, b, c
-                self._keep.append(lut_arr)
-                g = abi.Grid()
-                g.nx, g.ny, g.nz = cells.shape[0], cells.shape[1], cells.shape[2]
-                g.min_corner = abi.Vec3(*o.MinCorner)
-                g.voxel_size = abi.Vec3(*o.VoxelSize)
-                g.cells = cells.ctypes.data_as(C.POINTER(C.c_int32))
-                g.lookup = C.cast(lut_arr, C.POINTER(abi.VoxelLookup))
-                g.n_lookup = len(lut)
-                g.default_material = -1
-                g.wireframe = 1 if o.EnableWireframe else 0
-                g.wire_width_fraction = float(f32(o.WireWidthFraction))
-                g.wire_max_distance = float(f32(o.WireMaxDistance))
+                g = grid_record(o, mat_id, self._keep)
                 prim(abi.PRIM_VOLUME_GRID, -1, [], ref=len(grids))
                 grids.append(g)
             else:

@@ -59,6 +59,14 @@ def read_vg01(path) -> np.ndarray:
     return np.frombuffer(data, dtype="<i4").reshape(nx, ny, nz, 2).copy()
 
 
+def center_column(center, world_min, voxel_size, chunk_size: int) -> Tuple[int, int]:
+    """(cxCenter, czCenter) of BuildDesiredSet / LoadChunksAround (WorldManager.cs:309-312, 376-379), in binary32 as there."""
+    scale_x = f32(f32(voxel_size[0]) * f32(chunk_size))
+    scale_z = f32(f32(voxel_size[2]) * f32(chunk_size))
+    return (int(math.floor(float(f32((f32(center[0]) - f32(world_min[0])) / scale_x)))),
+            int(math.floor(float(f32((f32(center[2]) - f32(world_min[2])) / scale_z)))))
+
+
 def build_desired_set(center, world_min, voxel_size, chunk_size: int, view_distance_chunks: int, chunks_y: int) -> List[Tuple[int, int, int]]:
     """BuildDesiredSet, WorldManager.cs:372-397.  Returned in insertion order (cx, then cz, then cy), which is
     the order EnsureViewLoaded (:634-656) attaches chunks in - and so the order of Scene.Objects."""
@@ -114,3 +122,40 @@ def attach_view(scene: Scene, world: np.ndarray, center, world_min, voxel_size, 
         scene.Objects.append(vg)
         added.append(key)
     return added
+
+
+def stream_view(scene: Scene, world: np.ndarray, center, world_min, voxel_size, chunk_size: int, view_distance_chunks: int,
+                material_lookup: Callable, loaded: dict, chunks_y: Optional[int] = None, cache: Optional[dict] = None):
+    """One LoadChunksAround tick over a preloaded world (WorldManager.cs:289-370): loaded chunks outside the new desired set leave
+    scene.Objects (:341-363; into `cache` when one is given, as CacheChunk does), the desired chunks that are not loaded are attached in
+    the reference's order - radial distance from the centre column, then cy (:313-320; the sort is stable over the desired set's
+    insertion order) - from `cache` when they are there (TryAttachFromCache).  `loaded` (key -> VolumeGrid) persists between calls like
+    loadedChunkMap.  Returns (added keys, removed keys)."""
+    if chunks_y is None:
+        chunks_y = (world.shape[1] + chunk_size - 1) // chunk_size
+    desired = build_desired_set(center, world_min, voxel_size, chunk_size, view_distance_chunks, chunks_y)
+    want = set(desired)
+    removed = [key for key in loaded if key not in want]
+    for key in removed:
+        vg = loaded.pop(key)
+        for i, o in enumerate(scene.Objects):
+            if o is vg:
+                del scene.Objects[i]
+                break
+        if cache is not None:
+            cache[key] = vg
+    cx0, cz0 = center_column(center, world_min, voxel_size, chunk_size)
+    todo = [key for key in desired if key not in loaded]
+    todo.sort(key=lambda k: ((k[0] - cx0) * (k[0] - cx0) + (k[2] - cz0) * (k[2] - cz0), k[1]))
+    added = []
+    for key in todo:
+        vg = cache.pop(key, None) if cache is not None else None
+        if vg is None:
+            cells = slice_chunk(world, *key, chunk_size)
+            if cells is None:
+                continue
+            vg = VolumeGrid(cells, chunk_min_corner(world_min, voxel_size, chunk_size, *key), vec3(*voxel_size), material_lookup)
+        loaded[key] = vg
+        scene.Objects.append(vg)
+        added.append(key)
+    return added, removed
