@@ -62,6 +62,7 @@ int ycge_debug_read_wave_prof(ycge_ctx *c, unsigned long long *dst, size_t n_u64
 int ycge_debug_read_coop_stats(ycge_ctx *c, uint64_t out[16]);                               /* -DYCGE_DBG_COOPSTAT builds */
 int ycge_debug_read_batch_stats(ycge_ctx *c, uint64_t out[64]);
 int ycge_debug_resident_loop(ycge_ctx *c, int32_t frames, double *period_ms, double *issue_ms);   /* a rank's tile-resident ring driven from C (profiles/rank_times.py) */
+int ycge_debug_live_resources(int64_t out[6]);                       /* process-wide, no context and no device needed: {device allocations, device bytes, events, streams, page-locked allocations, page-locked bytes} the library holds right now (csrc/ycge_own.h) */
 int ycge_debug_is_page_locked(const void *p, size_t bytes);          /* the verdict ycge_render_frame takes on a caller's SDR buffer: 1 page-locked over its whole range */
 int ycge_debug_throw(ycge_ctx *c, int32_t kind);                     /* throws INSIDE an export (1 std::bad_alloc, 2 std::runtime_error, 3 an int, 4 std::length_error, 5 std::system_error; 0 nothing): the exception barrier's test */
 int ycge_debug_fail_allocation(int64_t nth);                         /* lib/var_faultinject.so ONLY (-DYCGE_FAULT_INJECTION): the library's n-th allocation from now throws std::bad_alloc */

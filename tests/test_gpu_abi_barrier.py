@@ -26,6 +26,13 @@ def fi_lib(torch_hip_first):
     return L
 
 
+def live(L):
+    """what the library holds through its owning types (ycge_debug_live_resources): device allocations and bytes, events, streams, page-locked allocations and bytes"""
+    out = (C.c_int64 * 6)()
+    assert L.ycge_debug_live_resources(out) == abi.YCGE_OK
+    return tuple(int(v) for v in out)
+
+
 @pytest.mark.parametrize("cfg_n", [1, 3])
 def test_the_nth_allocation_of_a_scene_upload_fails(fi_lib, cfg_n):
     L = fi_lib
@@ -61,12 +68,9 @@ def test_the_nth_allocation_of_a_scene_upload_fails(fi_lib, cfg_n):
     fresh.close(); r.close()
 
 
-def test_the_nth_allocation_of_a_two_device_create_fails(fi_lib):
-    L = fi_lib
-    c = abi.default_config()
-    c.fb_width, c.fb_height, c.super_sample = 96, 27, 1
-    c.n_devices = 2
-    c.devices[0] = c.devices[1] = 0
+def _walk_create(L, c):
+    """every step ends - success (and ycge_destroy) or YCGE_ERR_OUT_OF_MEMORY alike - with the library holding what it held before"""
+    before = live(L)
     failed = 0
     for n in list(range(0, 48)) + list(range(48, 400, 7)):
         ctx = C.c_void_p()
@@ -77,11 +81,28 @@ def test_the_nth_allocation_of_a_two_device_create_fails(fi_lib):
         if rc == abi.YCGE_OK:
             assert ctx.value
             L.ycge_destroy(ctx)
-            if left >= 0:
-                break
         else:
             failed += 1
             assert not ctx.value and b"bad_alloc" in L.ycge_last_error(None), n
+        assert live(L) == before, (n, rc, before, live(L))
+        if rc == abi.YCGE_OK and left >= 0:
+            break
+    return failed
+
+
+def test_the_nth_allocation_of_a_one_device_create_fails(fi_lib):
+    c = abi.default_config()
+    c.fb_width, c.fb_height, c.super_sample = 96, 27, 1
+    assert _walk_create(fi_lib, c) >= 1          # (at least the context itself: allocation 0)
+
+
+def test_the_nth_allocation_of_a_two_device_create_fails(fi_lib):
+    L = fi_lib
+    c = abi.default_config()
+    c.fb_width, c.fb_height, c.super_sample = 96, 27, 1
+    c.n_devices = 2
+    c.devices[0] = c.devices[1] = 0
+    failed = _walk_create(L, c)
     assert failed >= 5, failed
     # the library is still whole: a context made now traces a frame
     sc, w, h, ss, pose = scenes.config_scene(1)

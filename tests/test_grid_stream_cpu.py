@@ -80,4 +80,4 @@ def test_stream_view_reattaches_from_the_cache_the_object_it_cached():
 def test_the_streaming_exports_are_part_of_the_boundary():
     assert "ycge_scene_attach_grids" in abi.EXPORTED_SYMBOLS and "ycge_scene_detach_grids" in abi.EXPORTED_SYMBOLS
     assert abi.YCGE_ABI_VERSION == 10          # found by symbol lookup: the version stays
-    assert set(abi.HOOK_PROTOTYPES) == {"ycge_debug_read_grid", "ycge_debug_grid_pool_stats", "ycge_debug_peer_context"}
+    assert set(abi.HOOK_PROTOTYPES) == {"ycge_debug_read_grid", "ycge_debug_grid_pool_stats", "ycge_debug_peer_context", "ycge_debug_live_resources"}

@@ -827,19 +827,31 @@ def test_no_exception_crosses_the_c_abi(product_lib):
     assert abi.STATUS_NAMES[abi.YCGE_ERR_INTERNAL] == "YCGE_ERR_INTERNAL"
 
 
+def _host_sources_with_exports():
+    """every host .cpp of build.SOURCES that opens an extern "C" block"""
+    from yetanotherconsolegameengine_amd import build
+    csrc = Path(abi.__file__).resolve().parent / "csrc"
+    return [csrc / n for n in build.SOURCES if n.endswith(".cpp") and any(ln.startswith('extern "C" {') for ln in (csrc / n).read_text().split("\n"))]
+
+
 def test_every_export_of_the_host_sources_is_guarded():
-    """The barrier is mechanical: in csrc/ycge_host.cpp, ycge_frame.cpp, ycge_post_host.cpp and ycge_resident.cpp (the translation units with std containers, threads and
-    `new`) every function defined inside an extern "C" block is a function-try-block whose handler calls abi_catch - except the one that
+    """The barrier is mechanical: in every host translation unit with an extern "C" block (csrc/ycge_host.cpp, ycge_frame.cpp, ycge_post_host.cpp,
+    ycge_resident.cpp, ycge_query.cpp, ycge_chexel.cpp, ycge_ansi.cpp, ycge_grid_encode.cpp - std containers, threads and `new` live there)
+    every function defined inside such a block is a function-try-block whose handler calls abi_catch - except the one that
     cannot throw (ycge_last_error returns a pointer)."""
     import re
-    csrc = Path(abi.__file__).resolve().parent / "csrc"
-    for name in ("ycge_host.cpp", "ycge_frame.cpp", "ycge_post_host.cpp", "ycge_resident.cpp"):
-        lines = (csrc / name).read_text().split("\n")
+    sources = _host_sources_with_exports()
+    assert {p.name for p in sources} >= {"ycge_host.cpp", "ycge_frame.cpp", "ycge_post_host.cpp", "ycge_resident.cpp", "ycge_query.cpp", "ycge_chexel.cpp",
+                                         "ycge_ansi.cpp", "ycge_grid_encode.cpp"}, sources
+    least = {"ycge_post_host.cpp": 4, "ycge_query.cpp": 2, "ycge_chexel.cpp": 4, "ycge_ansi.cpp": 3, "ycge_grid_encode.cpp": 5}
+    for path in sources:
+        name = path.name
+        lines = path.read_text().split("\n")
         in_c, n = False, 0
         for i, line in enumerate(lines):
             if line.startswith('extern "C" {'): in_c = True
             if line.startswith('} // extern "C"'): in_c = False
-            m = re.match(r"^(int|size_t|void|const char \*)\s*(ycge_\w+)\(", line) if in_c else None
+            m = re.match(r"^(int|size_t|void|const char \*|ycge_ctx \*)\s*(ycge_\w+)\(", line) if in_c else None
             if not m or line.rstrip().endswith(";"):
                 continue
             if m.group(2) in ("ycge_last_error", "ycge_debug_fail_allocation", "ycge_peer_worker_main"):      # (the last: a thread's main, not an entry point - its body catches for itself)
@@ -851,7 +863,41 @@ def test_every_export_of_the_host_sources_is_guarded():
             while lines[k] != "}": k += 1
             assert lines[k + 1].startswith("catch (...) {") and "abi_catch(" in lines[k + 1], f"{name}:{k + 2} {m.group(2)}"
             n += 1
-        assert n >= (4 if name == "ycge_post_host.cpp" else 10), (name, n)
+        assert n >= least.get(name, 10), (name, n)
+
+
+def test_gpu_resources_are_made_and_freed_by_the_owners_only():
+    """csrc/ycge_own.h is the one place of the host side that creates or frees a device allocation, a page-locked allocation, an event or a
+    stream: no host .cpp and not csrc/ycge_ctx.h names one of those runtime calls - so nothing there can forget to free what it made.
+    The four caller-facing exports that hand page-locked memory to the CALLER (ycge_alloc_host_buffer / ycge_free_host_buffer) or
+    register the caller's own (ycge_pin_host_buffer / ycge_unpin_host_buffer) are the exceptions, and the only ones."""
+    import re
+    from yetanotherconsolegameengine_amd import build
+    csrc = Path(abi.__file__).resolve().parent / "csrc"
+    calls = re.compile(r"hipFree\(|hipHostFree\(|hipEventDestroy\(|hipStreamDestroy\(|hipMalloc\(|hipHostMalloc\(|hipExtMallocWithFlags|hipEventCreate|hipStreamCreate")
+    allowed = ("ycge_alloc_host_buffer", "ycge_free_host_buffer", "ycge_pin_host_buffer", "ycge_unpin_host_buffer")
+    assert "ycge_own.h" in build.HEADERS and calls.search((csrc / "ycge_own.h").read_text())
+    found = []
+    for path in [csrc / n for n in build.SOURCES if n.endswith(".cpp")] + [csrc / "ycge_ctx.h"]:
+        fn = None          # the exported function the line lies in (definitions start in column 0 and end with a "}" there)
+        for i, line in enumerate(path.read_text().split("\n")):
+            m = re.match(r"^(?:int|size_t|void)\s+(ycge_\w+)\(", line)
+            if m: fn = m.group(1)
+            elif line.startswith("}"): fn = None
+            if calls.search(line) and fn not in allowed:
+                found.append(f"{path.name}:{i + 1}: {line.strip()[:120]}")
+    assert not found, "\n".join(found)
+
+
+def test_live_resources_of_a_process_without_a_device(product_lib):
+    """ycge_debug_live_resources needs no context and no GPU: a process that made nothing holds nothing."""
+    import torch
+    out = (C.c_int64 * 6)(*([-1] * 6))
+    assert product_lib.ycge_debug_live_resources(out) == abi.YCGE_OK
+    assert all(v >= 0 for v in out), list(out)
+    if not torch.cuda.is_available():          # (with a GPU, fixtures of the session may hold contexts: tests/test_gpu_resource_ownership.py takes deltas)
+        assert list(out) == [0] * 6
+    assert product_lib.ycge_debug_live_resources(None) == abi.YCGE_ERR_INVALID_ARG
 
 
 def test_the_nth_allocation_fails_inside_host_side_exports():

@@ -238,6 +238,7 @@ HOOK_PROTOTYPES = {
     "ycge_debug_read_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ycge_debug_grid_pool_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ycge_debug_peer_context": (C.c_void_p, [C.c_void_p, C.c_int32]),
+    "ycge_debug_live_resources": (C.c_int, [C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -58,11 +58,7 @@ static int ensure_ansi(ycge_ctx *c, ChexelState &X, int32_t cw, int32_t ch, unsi
     const uint32_t tiles = ycge_launch_ansi_tiles((uint32_t)cw * (uint32_t)ch);
     if (X.ansi_tiles.cap < tiles) HIP_TRY(c, X.ansi_tiles.alloc(tiles));
     if (!X.ansi_len.p) HIP_TRY(c, X.ansi_len.alloc(1));
-    if (!X.ansi_len_host) {
-        void *p = nullptr;
-        HIP_TRY(c, hipHostMalloc(&p, sizeof(unsigned long long), hipHostMallocDefault));
-        X.ansi_len_host = static_cast<unsigned long long *>(p);
-    }
+    HIP_TRY(c, X.ansi_len_host.reserve(sizeof(unsigned long long)));
     return ensure_palette(c, X, stream);
 }
 
@@ -71,40 +67,27 @@ static int launch_stream(ycge_ctx *c, ChexelState &X, hipStream_t stream, const 
     const int e = ycge_launch_ansi_stream(d_pairs, fbW, fbH, X.ansi_cw, X.ansi_ch, X.ansi_vx, X.ansi_vy, reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48),
                                           X.ansi_fg, X.ansi_bg, X.ansi_clear, X.ansi_tiles.p, X.ansi_stream.p, X.ansi_stream.cap, X.ansi_len.p, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "ANSI stream launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(c, hipMemcpyAsync(X.ansi_len_host, X.ansi_len.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(c, hipMemcpyAsync(X.ansi_len_host.p, X.ansi_len.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     return YCGE_OK;
 }
 
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs)
 {
-    ChexelState &X = *c->chexels;
+    ChexelState &X = c->chexels;
     { const int rc = ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
     return launch_stream(c, X, stream, d_pairs, c->fbW, c->fbH);
-}
-
-void release_ansi(ChexelState &X, bool all)
-{
-    X.ansi_stream.release(); X.ansi_tiles.release();
-    if (!all) return;
-    X.ansi_len.release(); X.ansi_palette.release();
-    X.ansi_palette_ready = false;
-    if (X.ansi_len_host) (void)hipHostFree(X.ansi_len_host);
-    X.ansi_len_host = nullptr;
 }
 
 } // namespace ycge_host
 
 namespace {
 
-// one _ansi call: sets the request, and clears it on every way out - on an error return also the SDR staging, so no later call writes
-// into an array of this one
+// one _ansi call: sets the request, and clears it on every way out (the SDR staging: render_frame_sync's own guard)
 struct AnsiCall {
     ycge_ctx *c;
-    bool ok = false;
     AnsiCall(ycge_ctx *c_, int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear) : c(c_)
     {
-        if (!c->chexels) c->chexels = new ChexelState();
-        ChexelState &X = *c->chexels;
+        ChexelState &X = c->chexels;
         X.on = true; X.dst[0] = X.dst[1] = X.dst[2] = nullptr;
         X.drop_staged();
         X.ansi_on = true;
@@ -112,11 +95,9 @@ struct AnsiCall {
     }
     ~AnsiCall()
     {
-        if (ChexelState *X = c->chexels) {
-            X->on = false; X->ansi_on = false;
-            X->drop_staged();
-        }
-        if (!ok) { c->staged_sdr_dst = nullptr; c->staged_sdr_bytes = 0; }
+        ChexelState &X = c->chexels;
+        X.on = false; X.ansi_on = false;
+        X.drop_staged();
     }
 };
 
@@ -140,16 +121,12 @@ int copy_stream(ycge_ctx *c, ChexelState &X, uint8_t *out, size_t len)
     uint8_t *target = out;
     const bool staged = !host_memory_is_page_locked(out, len);
     if (staged) {
-        if (len > X.stage_bytes) {
-            if (X.stage) { (void)hipHostFree(X.stage); X.stage = nullptr; X.stage_bytes = 0; }
-            HIP_TRY(c, hipHostMalloc(&X.stage, len, hipHostMallocDefault));
-            X.stage_bytes = len;
-        }
-        target = static_cast<uint8_t *>(X.stage);
+        HIP_TRY(c, X.stage.reserve(len));
+        target = X.stage.data();
     }
     HIP_TRY(c, hipMemcpyAsync(target, X.ansi_stream.p, len, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (staged) std::memcpy(out, X.stage, len);
+    if (staged) std::memcpy(out, X.stage.p, len);
     return YCGE_OK;
 }
 
@@ -182,17 +159,16 @@ try {
         return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
     HIP_TRY(c, hipSetDevice(c->device));
     AnsiCall call(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
-    ChexelState &X = *c->chexels;
+    ChexelState &X = c->chexels;
     rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
     if (rc != YCGE_OK) return rc;
     rc = render_frame_sync(c, out_top_bottom_sdr, true, st);          // (its stream synchronisation: the length has arrived)
     if (rc != YCGE_OK) return rc;
-    const unsigned long long len = *X.ansi_len_host;
+    const unsigned long long len = *static_cast<const unsigned long long *>(X.ansi_len_host.p);
     if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
     rc = copy_stream(c, X, out_stream, (size_t)len);
     if (rc != YCGE_OK) return rc;
     *out_len = (size_t)len;
-    call.ok = true;
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }
@@ -211,19 +187,18 @@ try {
     int rc = check_stream_args(c, fn, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->chexels) c->chexels = new ChexelState();
-    ChexelState &X = *c->chexels;
+    ChexelState &X = c->chexels;
     X.ansi_cw = console_w; X.ansi_ch = console_h; X.ansi_vx = viewport_x; X.ansi_vy = viewport_y;
     X.ansi_fg = default_fg16; X.ansi_bg = default_bg16; X.ansi_clear = clear_screen != 0;
     rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
     if (rc != YCGE_OK) return rc;
-    struct Buf { DevBuf<uint8_t> in; ~Buf() { in.release(); } } B;
-    HIP_TRY(c, B.in.alloc(2 * (size_t)fbW * fbH));
-    HIP_TRY(c, hipMemcpy(B.in.p, pairs, 2 * (size_t)fbW * fbH, hipMemcpyHostToDevice));
-    rc = launch_stream(c, X, c->stream, B.in.p, fbW, fbH);
+    DevBuf<uint8_t> in;
+    HIP_TRY(c, in.alloc(2 * (size_t)fbW * fbH));
+    HIP_TRY(c, hipMemcpy(in.p, pairs, 2 * (size_t)fbW * fbH, hipMemcpyHostToDevice));
+    rc = launch_stream(c, X, c->stream, in.p, fbW, fbH);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const unsigned long long len = *X.ansi_len_host;
+    const unsigned long long len = *static_cast<const unsigned long long *>(X.ansi_len_host.p);
     if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
     rc = copy_stream(c, X, out_stream, (size_t)len);
     if (rc != YCGE_OK) return rc;

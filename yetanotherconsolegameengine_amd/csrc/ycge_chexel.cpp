@@ -92,9 +92,9 @@ int ensure_tables(ycge_ctx *c, ChexelState &X)
 
 int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second)
 {
-    ChexelState *X = c->chexels;
-    const bool ansi = X && X->ansi_on;                                                   // (ycge_render_frame_ansi: the pairs stay on the device)
-    if (!X || !X->on || (!X->dst[0] && !X->dst[1] && !X->dst[2] && !ansi)) return YCGE_OK;        // (the SDR alone: nothing to encode)
+    ChexelState *X = &c->chexels;
+    const bool ansi = X->ansi_on;                                                        // (ycge_render_frame_ansi: the pairs stay on the device)
+    if (!X->on || (!X->dst[0] && !X->dst[1] && !X->dst[2] && !ansi)) return YCGE_OK;        // (the SDR alone: nothing to encode)
     const ChexelLayout L((size_t)c->fbW * c->fbH);
     DevBuf<uint8_t> &out = X->out[second ? 1 : 0];
     if (out.cap < L.total) HIP_TRY(c, out.alloc(L.total));
@@ -107,24 +107,20 @@ int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool seco
 
 int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second)
 {
-    ChexelState *X = c->chexels;
-    if (!X || !X->on) return YCGE_OK;
+    ChexelState *X = &c->chexels;
+    if (!X->on) return YCGE_OK;
     const ChexelLayout L((size_t)c->fbW * c->fbH);
     const size_t off[3] = {L.c16, L.ansi, L.rgba}, bytes[3] = {L.n, 2 * L.n, 8 * L.n};
     const uint8_t *src = X->out[second ? 1 : 0].p;
     size_t staged = 0;
     for (int k = 0; k < 3; k++)
         if (X->dst[k] && !host_memory_is_page_locked(X->dst[k], bytes[k])) staged = off[k] + bytes[k];
-    if (staged > X->stage_bytes) {
-        if (X->stage) { (void)hipHostFree(X->stage); X->stage = nullptr; X->stage_bytes = 0; }
-        HIP_TRY(c, hipHostMalloc(&X->stage, staged, hipHostMallocDefault));
-        X->stage_bytes = staged;
-    }
+    HIP_TRY(c, X->stage.reserve(staged));
     for (int k = 0; k < 3; k++) {
         if (!X->dst[k]) continue;
         uint8_t *target = X->dst[k];
         if (!host_memory_is_page_locked(X->dst[k], bytes[k])) {        // (synchronous calls only: the frames in flight refuse pageable arrays up front)
-            target = (uint8_t *)X->stage + off[k];
+            target = X->stage.data() + off[k];
             X->staged_dst[k] = X->dst[k]; X->staged_off[k] = off[k]; X->staged_bytes[k] = bytes[k];
         }
         HIP_TRY(c, hipMemcpyAsync(target, src + off[k], bytes[k], hipMemcpyDeviceToHost, stream));
@@ -133,50 +129,32 @@ int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second)
     return YCGE_OK;
 }
 
-void release_chexels(ycge_ctx *c, bool all)
-{
-    ChexelState *X = c->chexels;
-    if (!X) return;
-    X->out[0].release(); X->out[1].release();
-    release_ansi(*X, all);
-    if (!all) return;
-    X->tables.release();
-    if (X->stage) (void)hipHostFree(X->stage);
-    delete X;
-    c->chexels = nullptr;
-}
-
 } // namespace ycge_host
 
 namespace {
 
-// one _chexels call: sets the request, and clears it on every way out - on an error return also every latched destination (the SDR
-// staging included), so no later call writes into an array of this one
+// one _chexels call: sets the request, and clears it and every latched destination on every way out, so no later call writes into an
+// array of this one (the SDR staging: render_frame_sync's own guard)
 struct ChexelCall {
     ycge_ctx *c;
-    bool ok = false;
     ChexelCall(ycge_ctx *c_, uint8_t *c16, uint8_t *ansi, uint8_t *rgba) : c(c_)
     {
-        if (!c->chexels) c->chexels = new ChexelState();
-        ChexelState &X = *c->chexels;
+        ChexelState &X = c->chexels;
         X.on = true; X.dst[0] = c16; X.dst[1] = ansi; X.dst[2] = rgba;
         X.drop_staged();
     }
     ~ChexelCall()
     {
-        if (ChexelState *X = c->chexels) {
-            X->on = false; X->dst[0] = X->dst[1] = X->dst[2] = nullptr;
-            X->drop_staged();
-        }
-        if (!ok) { c->staged_sdr_dst = nullptr; c->staged_sdr_bytes = 0; }
+        ChexelState &X = c->chexels;
+        X.on = false; X.dst[0] = X.dst[1] = X.dst[2] = nullptr;
+        X.drop_staged();
     }
     // the synchronous call's pageable destinations, once its stream is done
     void finish()
     {
-        ChexelState &X = *c->chexels;
+        ChexelState &X = c->chexels;
         for (int k = 0; k < 3; k++)
-            if (X.staged_dst[k]) std::memcpy(X.staged_dst[k], (const uint8_t *)X.stage + X.staged_off[k], X.staged_bytes[k]);
-        ok = true;
+            if (X.staged_dst[k]) std::memcpy(X.staged_dst[k], X.stage.data() + X.staged_off[k], X.staged_bytes[k]);
     }
 };
 
@@ -221,9 +199,7 @@ try {
             return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async_chexels fills its arrays while the caller runs on: %s must be page-locked memory "
                                                  "(ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)", names[k]);
     ChexelCall call(c, out_color16, out_ansi, out_rgba);
-    rc = render_frame_in_flight(c, out_top_bottom_sdr, true);
-    if (rc == YCGE_OK) call.ok = true;
-    return rc;
+    return render_frame_in_flight(c, out_top_bottom_sdr, true);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -246,21 +222,20 @@ try {
     if (!sdr || w <= 0 || h <= 0 || (int64_t)w * h > (int64_t)INT32_MAX / 2 || (!c16 && !ansi && !rgba))
         return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_encode_chexels: bad arguments (w = %d, h = %d)", w, h);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->chexels) c->chexels = new ChexelState();
-    { const int rc = ensure_tables(c, *c->chexels); if (rc != YCGE_OK) return rc; }
+    { const int rc = ensure_tables(c, c->chexels); if (rc != YCGE_OK) return rc; }
     const ChexelLayout L((size_t)w * h);
-    struct Bufs { DevBuf<float> in; DevBuf<uint8_t> out; ~Bufs() { in.release(); out.release(); } } B;
-    HIP_TRY(c, B.in.alloc(6 * L.n));
-    HIP_TRY(c, B.out.alloc(L.total));
-    HIP_TRY(c, hipMemcpy(B.in.p, sdr, 6 * L.n * sizeof(float), hipMemcpyHostToDevice));
-    const int e = ycge_launch_chexels(B.in.p, w, h, c->chexels->tables.p, c16 ? B.out.p + L.c16 : nullptr, ansi ? B.out.p + L.ansi : nullptr,
-                                      rgba ? B.out.p + L.rgba : nullptr, c->compute_units, c->stream);
+    DevBuf<float> in; DevBuf<uint8_t> out;
+    HIP_TRY(c, in.alloc(6 * L.n));
+    HIP_TRY(c, out.alloc(L.total));
+    HIP_TRY(c, hipMemcpy(in.p, sdr, 6 * L.n * sizeof(float), hipMemcpyHostToDevice));
+    const int e = ycge_launch_chexels(in.p, w, h, c->chexels.tables.p, c16 ? out.p + L.c16 : nullptr, ansi ? out.p + L.ansi : nullptr,
+                                      rgba ? out.p + L.rgba : nullptr, c->compute_units, c->stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed: %s", hipGetErrorString((hipError_t)e));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     int rc = YCGE_OK;
-    if (c16) rc = copy_out(c, c16, B.out.p + L.c16, L.n);
-    if (ansi && rc == YCGE_OK) rc = copy_out(c, ansi, B.out.p + L.ansi, 2 * L.n);
-    if (rgba && rc == YCGE_OK) rc = copy_out(c, rgba, B.out.p + L.rgba, 8 * L.n);
+    if (c16) rc = copy_out(c, c16, out.p + L.c16, L.n);
+    if (ansi && rc == YCGE_OK) rc = copy_out(c, ansi, out.p + L.ansi, 2 * L.n);
+    if (rgba && rc == YCGE_OK) rc = copy_out(c, rgba, out.p + L.rgba, 8 * L.n);
     return rc;
 }
 catch (...) { return ycge_host::abi_catch(c); }

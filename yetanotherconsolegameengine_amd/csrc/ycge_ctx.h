@@ -1,9 +1,12 @@
 // ycge_ctx.h - the context of the library (struct ycge_ctx), the launch entry points of the kernel files, and what the host translation
 // units share (internal: the C-ABI is include/ycge.h).
-//   ycge_host.cpp      context, scene flattening and upload, frame orchestration (TryFlipAndBlit steps 1-9), frames in flight, the slab
-//                      form of the tiled frame, the post stage's schedule
+//   ycge_host.cpp      context (creation, teardown order), scene flattening and upload, host buffers, read-outs
+//   ycge_frame.cpp     frame orchestration (TryFlipAndBlit steps 1-5 and 9), frames in flight, the slab form of the tiled frame
+//   ycge_post_host.cpp the post stage (steps 6-8) and its schedules
 //   ycge_resident.cpp  the tile-resident multi-GPU form, its batched launches and emulation loop; read-backs (ycge_read_buffer / _accel)
+//   ycge_query.cpp, ycge_chexel.cpp, ycge_ansi.cpp, ycge_grid_encode.cpp   scene queries, chexel colours, the ANSI stream, streamed grids
 //   ycge_accel.cpp     the bit-faithful BVH builders
+// Every GPU resource is held through an owner of ycge_own.h: members free themselves, ycge_ctx::~ycge_ctx orders only what has an order.
 // All device work is in the .hip files; there is no CPU implementation of any per-pixel stage.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +22,7 @@
 #include <deque>
 #include <condition_variable>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <set>
@@ -33,6 +37,7 @@
 #include "ycge_accel.h"
 #include "ycge_device.h"
 #include "ycge_math.h"
+#include "ycge_own.h"
 
 extern "C" {
 size_t ycge_wf_sizes(int which);
@@ -101,39 +106,6 @@ inline std::string g_create_error;          // (one per library: C++17 inline va
 // into the P/Invoke frame of the CLR host ("no exceptions/longjmp across the ABI").  Called INSIDE a catch (...) handler:
 // rethrows to classify.  std::bad_alloc -> YCGE_ERR_OUT_OF_MEMORY, anything else -> YCGE_ERR_INTERNAL; the text goes to ycge_last_error.
 int abi_catch(const ycge_ctx *c) noexcept;
-
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0, cap = 0;          // elements in use / elements allocated
-    void release() { if (p) { (void)hipFree(p); p = nullptr; } n = cap = 0; }
-    hipError_t alloc(size_t count)
-    {
-        release();
-        if (count == 0) return hipSuccess;
-        const hipError_t e = hipMalloc((void **)&p, count * sizeof(T) + 64);     // records are read with whole 64- / 72-byte fetches: room for the over-read past the last record
-        if (e != hipSuccess) { p = nullptr; return e; }
-        n = cap = count;
-        return hipSuccess;
-    }
-    // room for `count` elements, contents undefined; the allocation is kept when it is large enough
-    hipError_t reserve(size_t count)
-    {
-        if (count > cap || cap == 0) { const hipError_t e = alloc(count > 0 ? count : 1); if (e != hipSuccess) return e; }
-        n = count;
-        return hipSuccess;
-    }
-    // per-frame callers (lights, moved objects) reuse the allocation when the new contents fit
-    hipError_t upload(const std::vector<T> &v)
-    {
-        if (v.size() > cap || (v.empty() && cap == 0)) {
-            const hipError_t e = alloc(v.size());
-            if (e != hipSuccess) return e;
-        }
-        n = v.size();
-        if (v.empty()) return hipSuccess;
-        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
 
 // Experiment knobs (none changes a pixel): read ONCE, when the context is created.
 struct Knobs {
@@ -261,8 +233,37 @@ struct GridPool {
 } // namespace ycge_host
 using namespace ycge_host;
 
-struct QueryState;          // ycge_query.cpp
-struct ChexelState;         // ycge_chexel.cpp
+// what the scene queries of one context hold (ycge_query.cpp): a stream and buffers of their own, made by the first query, grow-only
+struct QueryState {
+    Stream stream;
+    DevBuf<float> rays, hits;
+    DevBuf<int32_t> ids;
+    DevBuf<uint8_t> occluded;
+    DevBuf<uint32_t> first_bad;
+    DevBuf<uint64_t> spill;            // [spill levels][resident lanes]
+    uint32_t lanes[4] = {0, 0, 0, 0};  // resident lanes of k_query<has_grid, occluded>
+    PinnedBuf in_stage, out_stage;
+};
+// what the chexel calls of one context hold (ycge_chexel.cpp, ycge_ansi.cpp): filled by the first call
+struct ChexelState {
+    bool on = false;                                   // a _chexels or _ansi call is in progress
+    uint8_t *dst[3] = {nullptr, nullptr, nullptr};     // its destinations: c16, ansi, rgba
+    DevBuf<uint8_t> tables;                            // 256 f32 + 256 f64 thresholds
+    DevBuf<uint8_t> out[2];                            // the encoded bytes, per post parity (as d_sdr / d_sdr2)
+    PinnedBuf stage;                                   // page-locked staging of pageable destinations (synchronous calls only)
+    uint8_t *staged_dst[3] = {nullptr, nullptr, nullptr};
+    size_t staged_off[3] = {0, 0, 0}, staged_bytes[3] = {0, 0, 0};
+    void drop_staged() { for (int k = 0; k < 3; k++) { staged_dst[k] = nullptr; staged_bytes[k] = 0; } }
+    // ycge_render_frame_ansi: the request of the call at hand (the encode writes the ANSI pairs on the device only) and the stream's buffers
+    bool ansi_on = false;
+    int32_t ansi_cw = 0, ansi_ch = 0, ansi_vx = 0, ansi_vy = 0, ansi_fg = 0, ansi_bg = 0, ansi_clear = 0;
+    DevBuf<uint8_t> ansi_stream;                       // the stream (its bound)
+    DevBuf<uint32_t> ansi_tiles;                       // per-tile byte counts, then offsets
+    DevBuf<unsigned long long> ansi_len;               // the stream's length, as the scan wrote it
+    DevBuf<float> ansi_palette;                        // the 16 palette colours as 8 SDR chexels, then their 16 ANSI indices (bytes at float 48)
+    bool ansi_palette_ready = false;
+    PinnedBuf ansi_len_host;                           // page-locked word the length is copied to
+};
 
 struct ycge_ctx {
     ycge_config cfg;
@@ -272,7 +273,7 @@ struct ycge_ctx {
     // one process, several GPUs (config.n_devices >= 2): this context is rank 0 and owns one context per further device
     std::vector<ycge_ctx *> peers;
     ycge_ctx *parent = nullptr;
-    hipEvent_t pushed_ev = nullptr;            // a peer's tiles have arrived in the parent's frame buffers
+    Event pushed_ev;                           // a peer's tiles have arrived in the parent's frame buffers
     // config.multi_device_exchange = YCGE_EXCHANGE_RCCL (root only): the in-process communicators (ncclCommInitAll over devices[]), rank r's
     // on device r's stream; exchange_mode says what the frames really use (0 = peer push: not asked for, or librccl.so / its symbols absent)
     int exchange_mode = 0;
@@ -288,16 +289,17 @@ struct ycge_ctx {
         int job = 0;                           // 0 idle, 1 frame posted, 2 done, -1 quit
         FrameState fs{};
         int rc = 0;
-    } *worker = nullptr;
+    };
+    std::unique_ptr<PeerWorker> worker;
     std::deque<FrameState> pending;            // frames traced by ycge_trace_tiles and not yet resolved (pipelined callers)
     hipStream_t last_stream = nullptr;         // the stream the last tiled call ran on (scene updates wait for it too)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Stream stream;
+    Event ev[4];
     // a side stream, forked from and joined to the frame's stream: the next frame's schedule, the light loop beside the next round's
     // trace (stage pipeline), the resident ring's schedules and the static A-trous weights run on it
-    hipStream_t side_stream = nullptr;
-    hipEvent_t side_ev[2] = {nullptr, nullptr};
-    hipEvent_t traced_ev = nullptr, order_ev = nullptr;   // the next frame's schedule is built on the side stream, beside TAA
+    Stream side_stream;
+    Event side_ev[2];
+    Event traced_ev, order_ev;   // the next frame's schedule is built on the side stream, beside TAA
     bool order_pending = false;
     char device_name[256] = {0};
     int compute_units = 0;
@@ -330,19 +332,19 @@ struct ycge_ctx {
     DevBuf<float> alt2_hdr, alt2_albedo, alt2_normal, alt2_depth;      // (three sets: the trace of frame N + 1 must not wait for the TAA of frame N - 1, which finds
     DevBuf<uint8_t> alt2_sky;                                          //  its places among frame N's wavefronts late; it waits for TAA of frame N - 2)
     int set_id[3] = {0, 1, 2};                     // which of the three sets the names current / alt / alt2 hold
-    hipStream_t taa_stream = nullptr, stream2 = nullptr;      // stream2: the traces of odd frames in flight (two traces may overlap: the tail of one, the bulk of the next)
+    Stream taa_stream, stream2;      // stream2: the traces of odd frames in flight (two traces may overlap: the tail of one, the bulk of the next)
     DevBuf<uint64_t> stack_spill2;                 // ... which then need a traversal-stack spill area of their own
     uint64_t *spill_override = nullptr;            // set around trace_frame by ycge_render_frame_async
-    hipEvent_t flight_fork_ev = nullptr;
-    uint32_t *placed_flag = nullptr;               // signal memory: the number of the newest frame in flight whose trace has placed its last workgroup
+    Event flight_fork_ev;
+    SignalWord placed_flag;                        // signal memory: the number of the newest frame in flight whose trace has placed its last workgroup
     uint32_t placed_expect = 0, placed_next = 0;   // what the next trace waits for (0: nothing) / the value the next trace stores
     uint64_t placed_waits = 0;                     // traces queued behind a placed value so far (ycge_flight_query)
     // frames in flight WITH the post stage (ycge_render_frame_async_sdr): post of frame N beside the traces and TAA of the frames after it
-    hipEvent_t flight_taa_ev = nullptr, post_hist_ev = nullptr, post_done_ev = nullptr, post_set_ev[3] = {nullptr, nullptr, nullptr};
+    Event flight_taa_ev, post_hist_ev, post_done_ev, post_set_ev[3];
     bool post_hist_pending = false, post_busy = false, post_set_pending[3] = {false, false, false};
-    hipEvent_t tile_trace_ev[2] = {nullptr, nullptr};      // tiled frames: the trace (and slab pack) of the newest frame of each parity is done
+    Event tile_trace_ev[2];      // tiled frames: the trace (and slab pack) of the newest frame of each parity is done
     bool tile_trace_used[2] = {false, false};
-    hipEvent_t set_resolved_ev[3] = {nullptr, nullptr, nullptr};
+    Event set_resolved_ev[3];
     bool set_read[3] = {false, false, false};             // a TAA launch on taa_stream has read this set: the next trace into it waits for set_resolved_ev
     int out_set = 0;                               // which set the names above hold
     bool async_outstanding = false;
@@ -350,11 +352,11 @@ struct ycge_ctx {
     // staler than the synchronous path's, which builds it between the two traces), into the buffers frame N is not reading
     DevBuf<uint32_t> flight_order[3], flight_ws[3];         // (frames in flight use all three, by frame number mod 3; tiled frames two, by parity)
     int64_t flight_order_frame[3] = {-1, -1, -1};  // the frame number each buffer's schedule was built for (-1: none)
-    hipEvent_t flight_order_ev[3] = {nullptr, nullptr, nullptr};     // the schedule in each buffer is complete (side stream)
+    Event flight_order_ev[3];     // the schedule in each buffer is complete (side stream)
     int64_t last_frame_deferred = -2;              // the newest tiled frame whose trace was followed by a deferred schedule
     bool in_flight_taa = false;                    // taa_and_commit is called by ycge_render_frame_async with two traces overlapping: one-wavefront workgroups
     bool in_flight_call = false;                   // trace_frame is called by ycge_render_frame_async
-    std::vector<hipEvent_t> flight_ev;             // begin / end of the trace launches of the frames in flight, a ring (ycge_async_trace_times)
+    std::vector<Event> flight_ev;             // begin / end of the trace launches of the frames in flight, a ring (ycge_async_trace_times)
     uint64_t flight_frames = 0;                    // queued since the last ycge_async_trace_times
     // ---- tile-resident form (one process per GPU; ycge_trace_tiles_resident / ycge_resolve_tiles_resident): TAA on this rank's own tiles
     // with a one-pixel halo of {hdr, sky} exchanged between the ranks, the history never leaves its rank; a ring of K frame sets so that K
@@ -363,10 +365,10 @@ struct ycge_ctx {
         DevBuf<float> hdr, normal, depth;
         DevBuf<uint8_t> sky;
         DevBuf<uint64_t> spill;
-        hipEvent_t traced = nullptr, resolved = nullptr;
+        Event traced, resolved;
         bool traced_used = false, resolved_used = false;
     };
-    std::vector<ResidentSet *> rsets;
+    std::vector<ResidentSet> rsets;
     // ycge_trace_tiles_resident_batch: the frames of a batch leave their launch parameters here instead of launching (trace_frame), one
     // launch traces them all (the records travel as its arguments)
     bool batch_collect = false;
@@ -375,17 +377,17 @@ struct ycge_ctx {
     static constexpr int kBatchMax = YCGE_TRACE_BATCH_MAX;
     DevBuf<uint64_t> batch_spill[2];               // a spill area as wide as the batch's frames together, per batch parity: two batches may run at a time
     uint64_t batch_count = 0;
-    hipEvent_t batch_done[2] = {nullptr, nullptr}; // a batch's launch: the batch after the next may scratch its spill area after it
+    Event batch_done[2];                           // a batch's launch: the batch after the next may scratch its spill area after it
     bool batch_spill_used[2] = {false, false};
     static constexpr uint32_t kResCostFrames = 16; // the resident ring's own cost ring: K - 1 slots are being written, one is cleared, the rest are read
     DevBuf<uint32_t> res_cost;
     // three schedule buffers taken in turn: one is built behind the trace of every R-th frame M (R = the ring's depth; YCGE_RES_SCHED_EVERY) and
     // serves the frames from M + K on - a trace never waits for a trace younger than frame N - K - until a newer one does
-    std::vector<DevBuf<uint32_t> *> res_order, res_ws;
-    std::vector<hipEvent_t> res_order_ev, res_order_read_ev;
+    std::vector<DevBuf<uint32_t>> res_order, res_ws;
+    std::vector<Event> res_order_ev, res_order_read_ev;
     std::vector<int64_t> res_order_frame;          // per buffer: the frame M its schedule was built behind (-1: none)
     int res_order_next = 0;                        // the buffer the next build writes
-    hipEvent_t res_last_traced = nullptr;          // stage-pipeline scenes share their queues between frames: their traces follow each other
+    Event res_last_traced;          // stage-pipeline scenes share their queues between frames: their traces follow each other
     bool res_last_traced_used = false;
     std::vector<int64_t> halo_send_counts, halo_recv_counts;          // records (4 floats) per peer rank
     DevBuf<uint32_t> d_halo_send_px, d_halo_recv_px;
@@ -417,8 +419,8 @@ struct ycge_ctx {
                      void release() { den_a.release(); den_b.release(); unit_n.release(); exp_terms.release(); atrous_statw.release(); exp_scratch.release(); post_progress.release(); post_epoch = post_ticket = 0; } } alt_post;
     int post_resident_seen[2] = {-1, -1};         // post_resident_per_cu: the runtime's answer for the whole-band / split-band instantiation (-1: not asked yet)
     DevBuf<uint8_t> tone_state;                   // ToneMapper state; lives as long as the context (not reset by Resize)
-    struct InplaceSchedule { ~InplaceSchedule() { pixels.release(); offsets.release(); pass_level.release(); band_desc.release(); } int w = 0, h = 0, step = 0, levels = 0, bands = 0, rows_per_band = 0, levels_per_launch = 0; uint32_t max_level_pixels = 0, window_width = 0; bool split = false; DevBuf<uint32_t> pixels, offsets, pass_level; DevBuf<int32_t> band_desc; };
-    std::vector<InplaceSchedule *> schedules;     // level schedules of the in-place A-trous iterations, by (w, h, step)
+    struct InplaceSchedule { int w = 0, h = 0, step = 0, levels = 0, bands = 0, rows_per_band = 0, levels_per_launch = 0; uint32_t max_level_pixels = 0, window_width = 0; bool split = false; DevBuf<uint32_t> pixels, offsets, pass_level; DevBuf<int32_t> band_desc; };
+    std::vector<std::unique_ptr<InplaceSchedule>> schedules; // level schedules of the in-place A-trous iterations, by (w, h, step)
     // what ycge_scene_update_objects needs from the last full upload
     std::vector<GMesh> gmeshes_host;
     std::vector<std::array<float, 6>> grid_bounds;   // VolumeGrid.TryGetBounds per grid; max < min marks an empty grid
@@ -454,20 +456,19 @@ struct ycge_ctx {
     GridPool grid_pool;                // (root context)
     // ycge_scene_attach_grids: the batch's descriptors, results, lookup tables and raw cells in page-locked memory (root) and on this
     // device; encoded bytes that wait for the arena to grow
-    void *enc_stage = nullptr; size_t enc_stage_bytes = 0;
+    PinnedBuf enc_stage;
     DevBuf<uint8_t> d_enc_in, d_enc_out;
     DevBuf<uint8_t> d_cells;
     DevBuf<int32_t> d_lut;
     DevBuf<uint32_t> d_tex_pixels;             // textures of YCGE_MAT_TEXTURED materials
     // a live texture's next frame travels through page-locked staging (two buffers taken in turn) and a stream-ordered copy on the
     // context's stream: behind the traces that still read the old frame, ahead of the ones queued after the call
-    uint8_t *tex_stage[2] = {nullptr, nullptr};
-    size_t tex_stage_bytes[2] = {0, 0};
-    hipEvent_t tex_stage_ev[2] = {nullptr, nullptr};
+    PinnedBuf tex_stage[2];
+    Event tex_stage_ev[2];
     // GPU -> host copies never target memory whose mapping the library does not control (copy_out below): page-locked staging of its own
-    void *out_stage = nullptr; size_t out_stage_bytes = 0;
+    PinnedBuf out_stage;
     float *staged_sdr_dst = nullptr; size_t staged_sdr_bytes = 0;       // a synchronous frame's SDR read-back into a pageable caller array: finished on the host after the stream
-    hipEvent_t tex_order_ev = nullptr;         // "everything queued on the second trace stream so far": a live texture's copy waits for it
+    Event tex_order_ev;         // "everything queued on the second trace stream so far": a live texture's copy waits for it
     bool tex_stage_busy[2] = {false, false};
     int tex_stage_next = 0;
     DevBuf<int32_t> d_tex_info;
@@ -483,11 +484,18 @@ struct ycge_ctx {
     std::vector<MeshHost> meshes;
     // scene queries (ycge_scene_hit / ycge_scene_occluded, ycge_query.cpp): a stream and buffers of their own, made by the first query;
     // scene_ev marks the device work of the last scene change on `stream` - a query waits for it and for nothing a frame queued after it
-    struct QueryState *query = nullptr;
-    hipEvent_t scene_ev = nullptr;
+    std::unique_ptr<QueryState> query;
+    Event scene_ev;
     // device chexel colours (ycge_render_frame_chexels / _async_chexels, ycge_chexel.cpp): the request of the call at hand, the encoded
-    // buffers per post parity, the threshold tables, the staging of pageable destinations; made by the first such call
-    struct ChexelState *chexels = nullptr;
+    // buffers per post parity, the threshold tables, the staging of pageable destinations
+    ChexelState chexels;
+
+    ycge_ctx() = default;
+    ycge_ctx(const ycge_ctx &) = delete;
+    ycge_ctx &operator=(const ycge_ctx &) = delete;
+    ~ycge_ctx();                 // ycge_host.cpp: what has an ORDER (worker, communicators, peers, the streams' drain); the members free themselves
+    void stop_worker();          // a peer's issuing thread: told to quit and joined
+    void drain();                // waits for every stream of this context, with its device current
 
     int fail(int code, const char *fmt, ...)
     {
@@ -534,8 +542,15 @@ struct RcclApi {
 const RcclApi &load_rccl();
 size_t slab_floats(const ycge_ctx *c);
 bool host_memory_is_page_locked(const void *p, size_t bytes);
-int ensure_out_stage(ycge_ctx *c, size_t bytes);
 void finish_staged_sdr(ycge_ctx *c);
+// run_post latches a pageable SDR destination on the context (staged_sdr_dst) for the caller to finish behind its stream.  Every entry
+// point that may reach run_post holds one of these: whatever way it leaves, no later call finds a pointer of this one.
+struct StagedSdrGuard {
+    ycge_ctx *c;
+    explicit StagedSdrGuard(ycge_ctx *c_) : c(c_) {}
+    StagedSdrGuard(const StagedSdrGuard &) = delete;
+    ~StagedSdrGuard() { c->staged_sdr_dst = nullptr; c->staged_sdr_bytes = 0; }
+};
 int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, hipEvent_t history_read = nullptr /* recorded once the TAA history has been read for the last time */,
              hipEvent_t before_copy = nullptr /* recorded in front of the read-back: the exposure state is this frame's */, bool second_sdr = false,
              hipEvent_t tone_wait = nullptr /* the frame before has left its exposure state: waited for in front of this frame's exposure step */, bool second_set = false);
@@ -558,37 +573,12 @@ std::array<float, 6> grid_world_bounds(const ycge_grid &g);
 int encode_grid_host(ycge_ctx *c, const ycge_grid &g, int gi, int n_materials, const GGrid &G, uint8_t *cells, std::vector<int32_t> &lut, int lo[3], int hi[3],
                      uint64_t &brick_mask);                                                  // the host encoder (first-seen codes)
 void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_bytes, size_t lut_entries);   // ycge_grid_encode.cpp: after an upload
-void release_grid_pool(ycge_ctx *c);                                                        // ycge_grid_encode.cpp: staging and scratch (ycge_destroy)
 int query_scene_changed(ycge_ctx *c);       // ycge_query.cpp: record scene_ev behind a scene upload / objects update
-void release_query(ycge_ctx *c);             // ycge_query.cpp: drain the query stream, then free what the queries hold
 int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second);   // ycge_chexel.cpp: run_post's encode behind the tonemap (a no-op unless a _chexels call asked)
 int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second);                      // ... and its copies behind the SDR read-back
-void release_chexels(ycge_ctx *c, bool all);                                             // ycge_chexel.cpp: the device buffers (all: and the rest)
 int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *st);     // ycge_frame.cpp: ycge_render_frame, post stage on request
 int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post);                      // ycge_frame.cpp: ycge_render_frame_async(_sdr)
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
 int ensure_tables(ycge_ctx *c, ChexelState &X);                                           // ycge_chexel.cpp: LinearToSrgb8's thresholds on the device, once
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs);                // ycge_ansi.cpp: the stream kernels behind the encode, and the length's copy
-void release_ansi(ChexelState &X, bool all);                                             // ycge_ansi.cpp: the stream buffers (all: and the rest)
 } // namespace ycge_host
-
-// what the chexel calls of one context hold (ycge_chexel.cpp, ycge_ansi.cpp): made by the first call, freed by ycge_destroy (release_chexels)
-struct ChexelState {
-    bool on = false;                                   // a _chexels or _ansi call is in progress
-    uint8_t *dst[3] = {nullptr, nullptr, nullptr};     // its destinations: c16, ansi, rgba
-    DevBuf<uint8_t> tables;                            // 256 f32 + 256 f64 thresholds
-    DevBuf<uint8_t> out[2];                            // the encoded bytes, per post parity (as d_sdr / d_sdr2)
-    void *stage = nullptr; size_t stage_bytes = 0;     // page-locked staging of pageable destinations (synchronous calls only)
-    uint8_t *staged_dst[3] = {nullptr, nullptr, nullptr};
-    size_t staged_off[3] = {0, 0, 0}, staged_bytes[3] = {0, 0, 0};
-    void drop_staged() { for (int k = 0; k < 3; k++) { staged_dst[k] = nullptr; staged_bytes[k] = 0; } }
-    // ycge_render_frame_ansi: the request of the call at hand (the encode writes the ANSI pairs on the device only) and the stream's buffers
-    bool ansi_on = false;
-    int32_t ansi_cw = 0, ansi_ch = 0, ansi_vx = 0, ansi_vy = 0, ansi_fg = 0, ansi_bg = 0, ansi_clear = 0;
-    DevBuf<uint8_t> ansi_stream;                       // the stream (its bound)
-    DevBuf<uint32_t> ansi_tiles;                       // per-tile byte counts, then offsets
-    DevBuf<unsigned long long> ansi_len;               // the stream's length, as the scan wrote it
-    DevBuf<float> ansi_palette;                        // the 16 palette colours as 8 SDR chexels, then their 16 ANSI indices (bytes at float 48)
-    bool ansi_palette_ready = false;
-    unsigned long long *ansi_len_host = nullptr;       // page-locked word the length is copied to
-};

@@ -90,7 +90,7 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
         // area), every tiled trace first waits for the trace of frame N - 2, whatever streams the caller uses, and a scene whose trace
         // shares more than that between frames (stage pipeline queues, refraction stacks) also for frame N - 1.
         const int par = (int)(fs.frame & 1);
-        for (int k = 0; k < 2; k++) if (!c->tile_trace_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->tile_trace_ev[k], hipEventDisableTiming));
+        for (int k = 0; k < 2; k++) HIP_TRY(c, c->tile_trace_ev[k].ensure());
         if (par) {
             if (!c->alt_hdr.p) {
                 HIP_TRY(c, c->alt_hdr.alloc(3 * npx)); HIP_TRY(c, c->alt_albedo.alloc(3 * npx)); HIP_TRY(c, c->alt_normal.alloc(3 * npx));
@@ -110,7 +110,7 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
     if (debug) { O.rays = c->dbg_rays.p; O.prim_id = c->dbg_prim.p; O.sub_id = c->dbg_sub.p; O.hit_t = c->dbg_hit_t.p; O.rng_state = c->dbg_rng.p; }
     if (c->knobs.wave_prof_stage >= 0) { if (!c->wave_prof.p) HIP_TRY(c, c->wave_prof.alloc((size_t)c->n_tiles * 16)); O.wave_prof = c->wave_prof.p; O.wave_prof_stage = c->knobs.wave_prof_stage; }
     O.counters = c->counters.p;
-    if (c->in_flight_call && c->placed_flag && c->placed_next) { O.placed_flag = c->placed_flag; O.placed_value = c->placed_next; }
+    if (c->in_flight_call && c->placed_flag.p && c->placed_next) { O.placed_flag = c->placed_flag.p; O.placed_value = c->placed_next; }
     if (c->cfg.count_work) HIP_TRY(c, hipMemsetAsync(c->counters.p, 0, 6 * sizeof(unsigned long long), stream));
     // A timed synchronous frame that is ONE plain launch: ev[1] rides on the launch itself (the kernel's own end time, ycge_launch_trace) -
     // an event recorded on the stream is a packet of its own, and the one between the trace and TAA cost every such frame 8 us (round 6)
@@ -170,7 +170,7 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
         if (deferred) {
             for (int k = 0; k < 2; k++) {
                 if (!c->flight_order[k].p) { HIP_TRY(c, c->flight_order[k].alloc((size_t)n_blocks * YCGE_SCHEDULE_SLACK)); HIP_TRY(c, c->flight_ws[k].alloc(96)); HIP_TRY(c, hipMemset(c->flight_ws[k].p, 0, 96 * sizeof(uint32_t))); }
-                if (!c->flight_order_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->flight_order_ev[k], hipEventDisableTiming));
+                HIP_TRY(c, c->flight_order_ev[k].ensure());
             }
             if (c->last_frame_deferred != fs.frame - 1)      // the frame before was not a tiled one: nobody has cleared the NEXT frame's cost slot
                 HIP_TRY(c, hipMemsetAsync(c->block_cost.p + (size_t)((cost_slot + 1u) % YCGE_COST_FRAMES) * n_blocks, 0, (size_t)n_blocks * sizeof(uint32_t), stream));
@@ -518,11 +518,11 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
     if (out_sdr && !host_memory_is_page_locked(out_sdr, (size_t)c->fbW * c->fbH * 6 * sizeof(float)))
         return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async_sdr fills its array while the caller runs on: it must be page-locked memory (ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)");
     if (!c->taa_stream) return c->fail(YCGE_ERR_INVALID_ARG, "no second stream: frames in flight need a single-device context");
-    for (int k = 0; k < 3; k++) if (!c->set_resolved_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->set_resolved_ev[k], hipEventDisableTiming));
-    for (int k = 0; k < 3; k++) if (!c->flight_order_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->flight_order_ev[k], hipEventDisableTiming));
+    for (int k = 0; k < 3; k++) HIP_TRY(c, c->set_resolved_ev[k].ensure());
+    for (int k = 0; k < 3; k++) HIP_TRY(c, c->flight_order_ev[k].ensure());
     if (c->flight_ev.empty()) {
-        c->flight_ev.resize(2 * YCGE_FLIGHT_RING, nullptr);
-        for (hipEvent_t &ev : c->flight_ev) HIP_TRY(c, hipEventCreate(&ev));
+        c->flight_ev.resize(2 * YCGE_FLIGHT_RING);
+        for (Event &ev : c->flight_ev) HIP_TRY(c, ev.ensure(hipEventDefault));
     }
     const size_t npx = (size_t)c->hiW * c->hiH;
     if (!c->alt_hdr.p) {
@@ -579,18 +579,17 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
     // blocks take wavefront places from that frame's bulk - both frames' longest chains then start late - and started later the machine
     // idles.  The last workgroup of a trace launch stores the frame's sequence number; this stream waits for the value.
     if (overlap_scene && c->knobs.flight_placed_gate) {
-        if (!c->placed_flag) {
+        if (!c->placed_flag.p) {
             // (a runtime without signal memory: no gate - the frames come out the same, a little later)
-            if (hipExtMallocWithFlags((void **)&c->placed_flag, 8, hipMallocSignalMemory) != hipSuccess || hipMemset(c->placed_flag, 0, 8) != hipSuccess) {
+            if (c->placed_flag.alloc() != hipSuccess) {
                 (void)hipGetLastError();
-                if (c->placed_flag) { (void)hipFree(c->placed_flag); c->placed_flag = nullptr; }
                 c->knobs.flight_placed_gate = false;
             }
             c->placed_expect = 0; c->placed_next = 0;
         }
     }
-    if (overlap_scene && c->knobs.flight_placed_gate && c->placed_flag) {
-        if (c->placed_expect) { HIP_TRY(c, hipStreamWaitValue32(ts, c->placed_flag, c->placed_expect, hipStreamWaitValueGte, 0xffffffffu)); c->placed_waits++; }
+    if (overlap_scene && c->knobs.flight_placed_gate && c->placed_flag.p) {
+        if (c->placed_expect) { HIP_TRY(c, hipStreamWaitValue32(ts, c->placed_flag.p, c->placed_expect, hipStreamWaitValueGte, 0xffffffffu)); c->placed_waits++; }
         c->placed_next = c->placed_expect + 1u;
         if (c->placed_next == 0u) c->placed_next = 1u;
     } else c->placed_next = 0;
@@ -632,8 +631,8 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
     c->in_flight_taa = false;
     if (rc != YCGE_OK) return rc;
     if (post) {
-        for (hipEvent_t *ev : {&c->flight_taa_ev, &c->post_hist_ev, &c->post_done_ev, &c->post_set_ev[0], &c->post_set_ev[1], &c->post_set_ev[2]})
-            if (!*ev) HIP_TRY(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        for (Event *ev : {&c->flight_taa_ev, &c->post_hist_ev, &c->post_done_ev, &c->post_set_ev[0], &c->post_set_ev[1], &c->post_set_ev[2]})
+            HIP_TRY(c, ev->ensure());
         // Steps 6-8 of this frame.  On the stream of this frame's trace where two traces run at a time (the next trace on that stream is
         // frame N + 2's, which must wait for this post stage anyway: it overwrites the G-buffer set the denoiser reads); on the second
         // trace stream where all traces share one (stage pipeline).  Post stages follow each other (one set of denoise buffers, one
@@ -670,6 +669,7 @@ int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *
         return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame is the one-process entry: set config.n_devices / devices[] to drive several GPUs from it, "
                                              "or use ycge_trace_tiles + ycge_resolve_gathered with one process per GPU (rank / world_size)");
     HIP_TRY(c, hipSetDevice(c->device));
+    StagedSdrGuard staged(c);
     auto t0 = std::chrono::steady_clock::now();
     FrameState fs;
     snapshot_frame(c, fs);
@@ -753,6 +753,7 @@ try {
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
     c->last_stream = stream;
+    StagedSdrGuard staged(c);
     auto t0 = std::chrono::steady_clock::now();
     if (out_sdr && !c->cfg.slab_albedo) return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
     const size_t per_rank = (size_t)c->tiles_per_rank_padded * 256 * slab_floats(c);

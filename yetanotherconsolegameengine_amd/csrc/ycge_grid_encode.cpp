@@ -44,12 +44,6 @@ void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_b
     c->grid_pool = std::move(P);
 }
 
-void release_grid_pool(ycge_ctx *c)
-{
-    if (c->enc_stage) { (void)hipHostFree(c->enc_stage); c->enc_stage = nullptr; c->enc_stage_bytes = 0; }
-    c->d_enc_in.release(); c->d_enc_out.release();
-}
-
 namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
@@ -68,10 +62,9 @@ template <class T> hipError_t grow_preserve(DevBuf<T> &b, size_t need, size_t ke
     if (e != hipSuccess) return e;
     if (keep && b.p) {
         e = hipMemcpy(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) { nb.release(); return e; }
+        if (e != hipSuccess) return e;
     }
-    b.release();
-    b = nb;
+    b = std::move(nb);
     return hipSuccess;
 }
 
@@ -95,15 +88,6 @@ struct Planned {
     std::vector<int32_t> host_lut;
 };
 
-int ensure_stage(ycge_ctx *c, size_t bytes)
-{
-    if (c->enc_stage_bytes >= bytes) return YCGE_OK;
-    if (c->enc_stage) { (void)hipHostFree(c->enc_stage); c->enc_stage = nullptr; c->enc_stage_bytes = 0; }
-    HIP_TRY(c, hipHostMalloc(&c->enc_stage, bytes, hipHostMallocPortable));
-    c->enc_stage_bytes = bytes;
-    return YCGE_OK;
-}
-
 double us_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
 
 // one group of device-encoded grids: stage, copy, launch, read back (every device of the context; the root's results are returned)
@@ -118,9 +102,8 @@ int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &p
     at = align_up(at, 256);
     for (int k : group) { plan[k].cells_off = at; at = align_up(at + (size_t)grids[k].nx * grids[k].ny * grids[k].nz * 8, 256); }
     const size_t off_back = at, total = at + m * sizeof(GridEncResult);
-    int rc = ensure_stage(root, total);
-    if (rc != YCGE_OK) return rc;
-    uint8_t *st = (uint8_t *)root->enc_stage;
+    HIP_TRY(root, root->enc_stage.reserve(total, hipHostMallocPortable));      // (every device of the context copies from it)
+    uint8_t *st = root->enc_stage.data();
     auto t0 = std::chrono::steady_clock::now();
     GridEncResult *init = (GridEncResult *)(st + off_res);
     uint32_t n_wg = 0;
@@ -339,16 +322,13 @@ try {
             if (e == hipSuccess) e = larger[i].alloc(want);
             if (e == hipSuccess && x->d_cells.p && x->d_cells.n) e = hipMemcpy(larger[i].p, x->d_cells.p, x->d_cells.n, hipMemcpyDeviceToDevice);
         }
-        if (e != hipSuccess) {
-            for (size_t i = 0; i < ctxs.size(); i++) { (void)hipSetDevice(ctxs[i]->device); larger[i].release(); }
-            HIP_TRY(c, e);
-        }
+        if (e != hipSuccess) (void)hipSetDevice(c->device);          // (the larger arenas made so far go with `larger`: a free takes any device's memory, whichever is current)
+        HIP_TRY(c, e);
         for (size_t i = 0; i < ctxs.size(); i++) {
             ycge_ctx *x = ctxs[i];
             (void)hipSetDevice(x->device);
             const size_t used = x->d_cells.n;
-            x->d_cells.release();
-            x->d_cells = larger[i];
+            x->d_cells = std::move(larger[i]);
             x->d_cells.n = used;
             x->sd.grid_cells = x->d_cells.p;
         }
@@ -475,4 +455,4 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
-}  // extern "C"
+} // extern "C"

@@ -1,5 +1,6 @@
-// ycge_host.cpp - host side of the C-ABI in include/ycge.h: context, scene flattening and upload, frame orchestration (TryFlipAndBlit
-// steps 1-9), frames in flight, the slab form of the tiled frame.  (The tile-resident multi-GPU form and the read-backs: ycge_resident.cpp.)
+// ycge_host.cpp - host side of the C-ABI in include/ycge.h: the context (creation, geometry, the order of its teardown), scene flattening
+// and upload, scene updates, host buffers, host-only test hooks.  (Frame orchestration, frames in flight, the slab form of the tiled frame:
+// ycge_frame.cpp.  The post stage: ycge_post_host.cpp.  The tile-resident multi-GPU form and the read-backs: ycge_resident.cpp.)
 #include "ycge_ctx.h"
 #include <dlfcn.h>
 
@@ -118,18 +119,13 @@ void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &se
         }
     }
 }
+// the ring of the tile-resident form, its schedules and halo lists: all per size (callers have quiesced the device)
 void release_resident(ycge_ctx *c)
 {
-    for (auto *rs : c->rsets) { if (rs->traced) (void)hipEventDestroy(rs->traced); if (rs->resolved) (void)hipEventDestroy(rs->resolved); delete rs; }
     c->rsets.clear();
-    for (auto *b : c->res_order) delete b;
-    for (auto *b : c->res_ws) delete b;
     c->res_order.clear(); c->res_ws.clear();
-    for (hipEvent_t ev : c->res_order_ev) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : c->res_order_read_ev) if (ev) (void)hipEventDestroy(ev);
     c->res_order_ev.clear(); c->res_order_read_ev.clear(); c->res_order_frame.clear();
-    if (c->res_last_traced) { (void)hipEventDestroy(c->res_last_traced); c->res_last_traced = nullptr; }
-    c->res_last_traced_used = false;
+    c->res_last_traced.release(); c->res_last_traced_used = false;
     c->res_cost.release(); c->d_halo_send_px.release(); c->d_halo_recv_px.release(); c->d_halo_index.release();
     c->halo_send_counts.clear(); c->halo_recv_counts.clear(); c->halo_ready = false;
 }
@@ -151,7 +147,7 @@ int set_geometry(ycge_ctx *c, int fbw, int fbh, int ss)
     c->taa_valid = false;                                       // Resize: taaHistoryValid = false (:137), taa.Resize (TemporalAA.cs:34-46)
     c->last_cam[0] = c->last_cam[1] = c->last_cam[2] = NAN; c->last_yaw = c->last_pitch = NAN;
     c->den_a.release(); c->den_b.release(); c->unit_n.release(); c->exp_terms.release(); c->exp_scratch.release(); c->d_sdr.release(); c->d_sdr2.release(); c->atrous_statw.release();     // spatialA / spatialB, :129-130
-    release_chexels(c, false);                                  // (the encoded chexel buffers: sized for the console)
+    c->chexels.out[0].release(); c->chexels.out[1].release(); c->chexels.ansi_stream.release(); c->chexels.ansi_tiles.release();      // (the encoded chexels and their stream: sized for the console)
     c->denoised = nullptr;
     c->alt_post.release();
     c->wave_prof.release();                                     // sized for the tile grid
@@ -162,8 +158,7 @@ int set_geometry(ycge_ctx *c, int fbw, int fbh, int ss)
     c->set_read[0] = c->set_read[1] = c->set_read[2] = false; c->out_set = 0; c->async_outstanding = false;
     c->tile_trace_used[0] = c->tile_trace_used[1] = false;
     release_resident(c);                                        // the ring of the tile-resident form and its halo lists are per size
-    for (auto *sc : c->schedules) delete sc;      // level schedules are per size: rebuilt on demand (the destructor frees the device lists)
-    c->schedules.clear();
+    c->schedules.clear();                         // level schedules are per size: rebuilt on demand
     int rc = alloc_frame_buffers(c);
     if (rc != YCGE_OK) return rc;
     rc = alloc_tile_buffers(c);
@@ -364,29 +359,28 @@ static int create_one(const ycge_config *cfg, ycge_ctx *parent, ycge_ctx **out)
         return YCGE_ERR_NO_DEVICE_CODE;
     }
     if (cfg->device < 0 || cfg->device >= n_dev) { g_create_error = "device ordinal out of range"; return YCGE_ERR_INVALID_ARG; }
-    struct Owner { ycge_ctx *p; ~Owner() { if (p) ycge_destroy(p); } } owner{new ycge_ctx()};      // (an exception on the way out of this function must not leak the context and its streams)
-    ycge_ctx *c = owner.p;
+    std::unique_ptr<ycge_ctx> c(new ycge_ctx());      // (whatever way out of this function, an exception included, takes the context and its streams with it)
     c->err.reserve(320);
     c->cfg = *cfg;
     c->device = cfg->device;
     c->fov_deg = cfg->fov_deg;
     c->parent = parent;
     c->knobs.read();                // every YCGE_* knob is read here, once
-    auto bail = [&](int code) { g_create_error = c->err; owner.p = nullptr; ycge_destroy(c); return code; };
-    if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(YCGE_ERR_DEVICE); }
+    auto bail = [&](int code, const char *what = nullptr) { if (what) c->err = what; g_create_error = c->err; return code; };
+    if (hipSetDevice(c->device) != hipSuccess) return bail(YCGE_ERR_DEVICE, "hipSetDevice failed");
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) { c->err = "hipGetDeviceProperties failed"; return bail(YCGE_ERR_DEVICE); }
+    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return bail(YCGE_ERR_DEVICE, "hipGetDeviceProperties failed");
     std::snprintf(c->device_name, sizeof c->device_name, "%s (%s)", prop.name, prop.gcnArchName);
     c->compute_units = prop.multiProcessorCount;
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
         c->err = std::string("device is ") + prop.gcnArchName + "; this library carries gfx950 code only";
         return bail(YCGE_ERR_NO_DEVICE_CODE);
     }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { c->err = "hipStreamCreate failed"; return bail(YCGE_ERR_DEVICE); }
-    for (auto &ev : c->ev)
-        if (hipEventCreate(&ev) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(YCGE_ERR_DEVICE); }
+    if (c->stream.ensure() != hipSuccess) return bail(YCGE_ERR_DEVICE, "stream creation failed");
+    for (Event &ev : c->ev)
+        if (ev.ensure(hipEventDefault) != hipSuccess) return bail(YCGE_ERR_DEVICE, "event creation failed");
     {
-        if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) { c->err = "hipStreamCreate failed"; return bail(YCGE_ERR_DEVICE); }
+        if (c->side_stream.ensure() != hipSuccess) return bail(YCGE_ERR_DEVICE, "stream creation failed");
         if (c->cfg.world_size == 1 && c->cfg.n_devices <= 1) {
             // The second stream of the frames in flight (ycge_render_frame_async), created HERE, next to the other two: the runtime deals
             // streams onto a few hardware queues in order of creation, and a stream created later - after another context of the process
@@ -395,17 +389,16 @@ static int create_one(const ycge_config *cfg, ycge_ctx *parent, ycge_ctx **out)
             // next - yield to the running trace's workgroups (measured neutral: 0.548 against 0.551 ms at normal priority)
             int lo = 0, hi = 0;
             if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess ||
-                hipStreamCreateWithPriority(&c->taa_stream, hipStreamNonBlocking, c->knobs.flight_priority > 0 ? hi : c->knobs.flight_priority < 0 ? lo : 0) != hipSuccess ||
-                hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&c->flight_fork_ev, hipEventDisableTiming) != hipSuccess) { c->err = "hipStreamCreate failed"; return bail(YCGE_ERR_DEVICE); }
+                c->taa_stream.ensure_with_priority(c->knobs.flight_priority > 0 ? hi : c->knobs.flight_priority < 0 ? lo : 0) != hipSuccess ||
+                c->stream2.ensure() != hipSuccess ||
+                c->flight_fork_ev.ensure() != hipSuccess) return bail(YCGE_ERR_DEVICE, "stream creation failed");
         }
-        for (hipEvent_t *ev : {&c->side_ev[0], &c->side_ev[1], &c->traced_ev, &c->order_ev, &c->pushed_ev})
-            if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(YCGE_ERR_DEVICE); }
+        for (Event *ev : {&c->side_ev[0], &c->side_ev[1], &c->traced_ev, &c->order_ev, &c->pushed_ev})
+            if (ev->ensure() != hipSuccess) return bail(YCGE_ERR_DEVICE, "event creation failed");
     }
-    int rc = set_geometry(c, cfg->fb_width, cfg->fb_height, cfg->super_sample);
+    int rc = set_geometry(c.get(), cfg->fb_width, cfg->fb_height, cfg->super_sample);
     if (rc != YCGE_OK) return bail(rc);
-    owner.p = nullptr;
-    *out = c;
+    *out = c.release();
     return YCGE_OK;
 }
 
@@ -446,7 +439,7 @@ try {
     int rc = create_one(&base, nullptr, &root);
     if (rc != YCGE_OK) return rc;
     // (whatever throws below - a vector that grows, a thread that cannot start - takes the root, its peers and their threads with it)
-    struct Owner { ycge_ctx *root, *peer; ~Owner() { if (peer) ycge_destroy(peer); if (root) ycge_destroy(root); } } owner{root, nullptr};
+    std::unique_ptr<ycge_ctx> owner(root);
     root->cfg.n_devices = cfg->n_devices;
     root->peers.reserve((size_t)cfg->n_devices);
     for (int r = 1; r < cfg->n_devices; r++) {
@@ -455,9 +448,7 @@ try {
         ycge_ctx *peer = nullptr;
         rc = create_one(&pc, root, &peer);
         if (rc != YCGE_OK) return rc;
-        owner.peer = peer;
-        root->peers.push_back(peer);
-        owner.peer = nullptr;
+        root->peers.push_back(peer);              // (room was reserved: the root owns it from here)
         if (peer->device != root->device) {        // the peer's kernels write into the root's frame buffers over xGMI
             int can = 0;
             if (hipDeviceCanAccessPeer(&can, peer->device, root->device) != hipSuccess || !can) {
@@ -483,85 +474,67 @@ try {
         (void)hipSetDevice(root->device);
     }
     for (ycge_ctx *peer : root->peers) {        // each peer's share of a frame is issued by its own thread (trace_on_all_devices)
-        peer->worker = new ycge_ctx::PeerWorker;
+        peer->worker.reset(new ycge_ctx::PeerWorker);
         peer->worker->th = std::thread(ycge_peer_worker_main, root, peer);
     }
     (void)hipSetDevice(root->device);
-    owner.root = nullptr;
-    *out = root;
+    *out = owner.release();
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(nullptr); }
 
 void ycge_destroy(ycge_ctx *c)
 try {
-    if (!c) return;
-    if (c->worker) {
-        { std::lock_guard<std::mutex> g(c->worker->m); c->worker->job = -1; }
-        c->worker->cv.notify_all();
-        if (c->worker->th.joinable()) c->worker->th.join();
-        delete c->worker;
-        c->worker = nullptr;
-    }
-    for (ycge_ctx *p : c->peers) ycge_destroy(p);
-    c->peers.clear();
-    if (!c->nccl_comms.empty()) {
-        const RcclApi &R = load_rccl();
-        for (void *cm : c->nccl_comms) if (cm && R.CommDestroy) (void)R.CommDestroy(cm);
-        c->nccl_comms.clear();
-    }
-    c->all_slabs.release();
-    (void)hipSetDevice(c->device);
-    // frames in flight may still be on ANY of the context's streams (TAA, post stage and read-back on taa_stream / stream2): everything
-    // is drained before the first buffer goes (not left to hipFree's implicit synchronisation)
-    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->taa_stream) (void)hipStreamSynchronize(c->taa_stream);
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    release_query(c);          // (drains the query stream first)
-    release_chexels(c, true);
-    release_grid_pool(c);
-    c->current_hdr.release(); c->g_albedo.release(); c->g_normal.release(); c->g_depth.release(); c->taa_hist.release();
-    c->prev_normal.release(); c->prev_depth.release(); c->sky.release(); c->prev_sky.release();
-    c->dbg_rays.release(); c->dbg_hit_t.release(); c->dbg_prim.release(); c->dbg_sub.release(); c->dbg_rng.release();
-    c->counters.release(); c->wave_prof.release(); c->own_slab.release(); c->dbg_counters.release();
-    c->t_hdr.release(); c->t_albedo.release(); c->t_normal.release(); c->t_depth.release(); c->t_sky.release();
-    if (c->taa_stream) { (void)hipStreamSynchronize(c->taa_stream); (void)hipStreamDestroy(c->taa_stream); c->taa_stream = nullptr; }
-    if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); c->stream2 = nullptr; }
-    if (c->flight_fork_ev) (void)hipEventDestroy(c->flight_fork_ev);
-    if (c->placed_flag) (void)hipFree(c->placed_flag);
-    for (int k = 0; k < 2; k++) if (c->tile_trace_ev[k]) (void)hipEventDestroy(c->tile_trace_ev[k]);
-    for (hipEvent_t ev : {c->flight_taa_ev, c->post_hist_ev, c->post_done_ev, c->post_set_ev[0], c->post_set_ev[1], c->post_set_ev[2]}) if (ev) (void)hipEventDestroy(ev);
-    c->stack_spill2.release(); c->stack_spill_side.release(); c->stack_spill_side2.release();
-    c->wf2_q0.release(); c->wf2_q1.release(); c->wf2_hit.release(); c->wf2_lq.release(); c->wf2_seg.release(); c->wf2_counts.release();
-    release_resident(c);
-    c->batch_spill[0].release(); c->batch_spill[1].release();
-    for (int k = 0; k < 2; k++) if (c->batch_done[k]) { (void)hipEventDestroy(c->batch_done[k]); c->batch_done[k] = nullptr; }
-    for (int k = 0; k < 3; k++) if (c->set_resolved_ev[k]) (void)hipEventDestroy(c->set_resolved_ev[k]);
-    for (int k = 0; k < 3; k++) { c->flight_order[k].release(); c->flight_ws[k].release(); if (c->flight_order_ev[k]) (void)hipEventDestroy(c->flight_order_ev[k]); }
-    for (hipEvent_t ev : c->flight_ev) (void)hipEventDestroy(ev);
-    c->flight_ev.clear();
-    c->alt_hdr.release(); c->alt_albedo.release(); c->alt_normal.release(); c->alt_depth.release(); c->alt_sky.release();
-    c->alt2_hdr.release(); c->alt2_albedo.release(); c->alt2_normal.release(); c->alt2_depth.release(); c->alt2_sky.release();
-    c->den_a.release(); c->den_b.release(); c->unit_n.release(); c->exp_terms.release(); c->exp_scratch.release(); c->d_sdr.release(); c->d_sdr2.release(); c->atrous_statw.release(); c->tone_state.release();
-    for (auto *sc : c->schedules) delete sc;
-    c->schedules.clear();
-    c->post_progress.release();
-    c->alt_post.release();
-    c->wf_q0.release(); c->wf_q1.release(); c->wf_hit.release(); c->wf_lq.release(); c->wf_seg.release(); c->wf_counts.release(); c->tile_order.release(); c->block_cost.release(); c->cost_snap.release(); c->block_order.release(); c->order_ws.release(); c->stack_spill.release(); c->path_stack.release();
-    c->d_scene_nodes.release(); c->d_walk_nodes.release(); c->d_grid_owner.release(); c->d_mesh_arena.release(); c->d_scene_leaf.release(); c->d_prims.release();
-    c->d_bvh_items.release(); c->d_bvh_scratch.release(); c->d_bvh_ref.release(); c->d_bvh_res.release();
-    c->d_materials.release(); c->d_meshes.release(); c->d_grids.release(); c->d_cells.release(); c->d_lut.release(); c->d_lights.release(); c->d_tex_pixels.release(); c->d_tex_info.release();
-    for (int k = 0; k < 2; k++) { if (c->tex_stage[k]) (void)hipHostFree(c->tex_stage[k]); if (c->tex_stage_ev[k]) (void)hipEventDestroy(c->tex_stage_ev[k]); }
-    if (c->tex_order_ev) (void)hipEventDestroy(c->tex_order_ev);
-    if (c->out_stage) { (void)hipHostFree(c->out_stage); c->out_stage = nullptr; c->out_stage_bytes = 0; }
-    for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : {c->side_ev[0], c->side_ev[1], c->traced_ev, c->order_ev, c->pushed_ev}) if (ev) (void)hipEventDestroy(ev);
-    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c) delete c;
 }
 catch (...) { (void)ycge_host::abi_catch(nullptr); }
+
+} // extern "C"
+
+void ycge_ctx::stop_worker()
+{
+    if (!worker) return;
+    { std::lock_guard<std::mutex> g(worker->m); worker->job = -1; }
+    worker->cv.notify_all();
+    if (worker->th.joinable()) worker->th.join();
+    worker.reset();
+}
+
+// frames in flight may still be on ANY of the context's streams (TAA, post stage and read-back on taa_stream / stream2; a query on its own)
+void ycge_ctx::drain()
+{
+    (void)hipSetDevice(device);
+    for (hipStream_t s : {(hipStream_t)side_stream, (hipStream_t)stream, (hipStream_t)taa_stream, (hipStream_t)stream2, query ? (hipStream_t)query->stream : nullptr})
+        if (s) (void)hipStreamSynchronize(s);
+}
+
+// The body holds what has an ORDER; everything else goes with the members, each through its owner.  Nothing here relies on the order the
+// members are declared in: when the body is done no thread issues work for this context, no communicator exists and every stream of every
+// rank is idle, so buffers, events and streams may go in any order (and a member added tomorrow needs no line here).
+//   1. the thread that issues a peer's share of a frame is stopped before anything it uses goes;
+//   2. a root, with each rank's device current, waits for EVERY rank's streams, then destroys the communicators, then the peers: no
+//      communicator outlives a stream it was used on, no all_slabs is freed under a running all-gather;
+//   3. this context's own streams are waited for (not left to the implicit synchronisation of a free).
+ycge_ctx::~ycge_ctx()
+{
+    try {
+        stop_worker();
+        for (ycge_ctx *p : peers) p->stop_worker();
+        for (ycge_ctx *p : peers) p->drain();
+        drain();
+        if (!nccl_comms.empty()) {
+            const RcclApi &R = load_rccl();
+            for (void *cm : nccl_comms) if (cm && R.CommDestroy) (void)R.CommDestroy(cm);
+            nccl_comms.clear();
+        }
+        for (ycge_ctx *p : peers) delete p;
+        peers.clear();
+        (void)hipSetDevice(device);
+    }
+    catch (...) { }
+}
+
+extern "C" {
 
 const char *ycge_last_error(const ycge_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 
@@ -627,27 +600,18 @@ bool host_memory_is_page_locked(const void *p, size_t bytes)
     if (!locked((const uint8_t *)p + (bytes - 1), a1)) return false;
     return a0.devicePointer && a1.devicePointer && (const uint8_t *)a1.devicePointer - (const uint8_t *)a0.devicePointer == (ptrdiff_t)(bytes - 1);
 }
-int ensure_out_stage(ycge_ctx *c, size_t bytes)
-{
-    if (c->out_stage_bytes >= bytes) return YCGE_OK;
-    if (c->out_stage) { (void)hipHostFree(c->out_stage); c->out_stage = nullptr; c->out_stage_bytes = 0; }
-    HIP_TRY(c, hipHostMalloc(&c->out_stage, bytes, hipHostMallocDefault));
-    c->out_stage_bytes = bytes;
-    return YCGE_OK;
-}
 // synchronous copy of `bytes` from device memory of the current device to `dst`; nothing of this context may be in flight on other streams
 int copy_out(ycge_ctx *c, void *dst, const void *src, size_t bytes)
 {
     if (bytes == 0) return YCGE_OK;
     if (host_memory_is_page_locked(dst, bytes)) { HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return YCGE_OK; }
     const size_t chunk = (size_t)32 << 20;
-    const int rc = ensure_out_stage(c, bytes < chunk ? bytes : chunk);
-    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, c->out_stage.reserve(bytes < chunk ? bytes : chunk));
     for (size_t off = 0; off < bytes; off += chunk) {
         const size_t n = bytes - off < chunk ? bytes - off : chunk;
-        HIP_TRY(c, hipMemcpyAsync(c->out_stage, (const uint8_t *)src + off, n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->out_stage.p, (const uint8_t *)src + off, n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::memcpy((uint8_t *)dst + off, c->out_stage, n);
+        std::memcpy((uint8_t *)dst + off, c->out_stage.p, n);
     }
     return YCGE_OK;
 }
@@ -655,7 +619,7 @@ int copy_out(ycge_ctx *c, void *dst, const void *src, size_t bytes)
 void finish_staged_sdr(ycge_ctx *c)
 {
     if (!c->staged_sdr_dst) return;
-    std::memcpy(c->staged_sdr_dst, c->out_stage, c->staged_sdr_bytes);
+    std::memcpy(c->staged_sdr_dst, c->out_stage.p, c->staged_sdr_bytes);
     c->staged_sdr_dst = nullptr; c->staged_sdr_bytes = 0;
 }
 
@@ -1356,20 +1320,16 @@ try {
         // The caller's array is its own again when this returns: the frame is staged in page-locked memory first.
         HIP_TRY(c, hipSetDevice(c->device));
         if (c->stream2) {
-            if (!c->tex_order_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->tex_order_ev, hipEventDisableTiming));
+            HIP_TRY(c, c->tex_order_ev.ensure());
             HIP_TRY(c, hipEventRecord(c->tex_order_ev, c->stream2));
             HIP_TRY(c, hipStreamWaitEvent(c->stream, c->tex_order_ev, 0));
         }
         const int k = c->tex_stage_next; c->tex_stage_next ^= 1;
         if (c->tex_stage_busy[k]) { HIP_TRY(c, hipEventSynchronize(c->tex_stage_ev[k])); c->tex_stage_busy[k] = false; }      // (the copy of two updates ago)
-        if (c->tex_stage_bytes[k] < bytes) {
-            if (c->tex_stage[k]) { (void)hipHostFree(c->tex_stage[k]); c->tex_stage[k] = nullptr; c->tex_stage_bytes[k] = 0; }
-            HIP_TRY(c, hipHostMalloc((void **)&c->tex_stage[k], bytes, hipHostMallocDefault));
-            c->tex_stage_bytes[k] = bytes;
-        }
-        if (!c->tex_stage_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->tex_stage_ev[k], hipEventDisableTiming));
-        std::memcpy(c->tex_stage[k], frame, bytes);
-        HIP_TRY(c, hipMemcpyAsync(c->d_tex_pixels.p + info[0], c->tex_stage[k], bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, c->tex_stage[k].reserve(bytes));
+        HIP_TRY(c, c->tex_stage_ev[k].ensure());
+        std::memcpy(c->tex_stage[k].p, frame, bytes);
+        HIP_TRY(c, hipMemcpyAsync(c->d_tex_pixels.p + info[0], c->tex_stage[k].p, bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipEventRecord(c->tex_stage_ev[k], c->stream));
         if (c->stream2) HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->tex_stage_ev[k], 0));
         c->tex_stage_busy[k] = true;
@@ -1733,6 +1693,16 @@ try {
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }
+
+// tests: what the process holds through the owners of ycge_own.h right now - {device allocations, device bytes, events, streams, page-locked
+// allocations, page-locked bytes}.  Needs no context and no device.
+int ycge_debug_live_resources(int64_t out[6])
+try {
+    if (!out) return YCGE_ERR_INVALID_ARG;
+    for (int k = 0; k < LIVE_KINDS; k++) out[k] = g_live[k].load(std::memory_order_relaxed);
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
 
 #if YCGE_FAULT_INJECTION
 // lib/var_faultinject.so only (tests/test_gpu_abi_barrier.py): the n-th allocation from now fails.  The replaced operators serve this

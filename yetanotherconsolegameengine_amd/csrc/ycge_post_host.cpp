@@ -234,7 +234,7 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
             if (w > 65535 || h > 65535 || n * 300 >= ((size_t)1 << 32))
                 return c->fail(YCGE_ERR_UNSUPPORTED, "in-place A-trous: trace grid above 65535 pixels a side or 14.3 M pixels (32-bit offsets into the weight table)");
             ycge_ctx::InplaceSchedule *sc = nullptr;
-            for (auto *k : c->schedules) if (k->w == w && k->h == h && k->step == step) sc = k;
+            for (auto &k : c->schedules) if (k->w == w && k->h == h && k->step == step) sc = k.get();
             if (!sc) {
                 // (cached only once complete: a schedule that failed half-way - an upload, an allocation - is freed, never reused)
                 std::unique_ptr<ycge_ctx::InplaceSchedule> building(new ycge_ctx::InplaceSchedule());
@@ -283,8 +283,7 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
                     for (int t = 0; t < sc->levels; t++)
                         for (uint32_t ps = boff[(size_t)b * (sc->levels + 1) + t]; ps < boff[(size_t)b * (sc->levels + 1) + t + 1]; ps++) plevel[ps] = (uint32_t)t;
                 HIP_TRY(c, sc->pass_level.upload(plevel));
-                c->schedules.push_back(sc);
-                building.release();
+                c->schedules.push_back(std::move(building));
             }
             if (sc->split && sc->window_width == 0) return c->fail(YCGE_ERR_DEVICE, "in-place A-trous: the split band layout found no collision-free window (set YCGE_POST_NO_SPLIT=1)");
             const int levels_per_launch = sc->levels_per_launch;
@@ -348,9 +347,8 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
         const size_t sdr_bytes = (size_t)c->fbW * c->fbH * 6 * sizeof(float);
         float *target = out_sdr_host;
         if (!host_memory_is_page_locked(out_sdr_host, sdr_bytes)) {        // (synchronous callers only: the frames in flight refuse a pageable array up front)
-            const int rs = ensure_out_stage(c, sdr_bytes);
-            if (rs != YCGE_OK) return rs;
-            target = (float *)c->out_stage;
+            HIP_TRY(c, c->out_stage.reserve(sdr_bytes));
+            target = (float *)c->out_stage.p;
             c->staged_sdr_dst = out_sdr_host; c->staged_sdr_bytes = sdr_bytes;
         }
         HIP_TRY(c, hipMemcpyAsync(target, d_sdr, sdr_bytes, hipMemcpyDeviceToHost, stream));

@@ -8,52 +8,16 @@
 // buffers are read-only while a query runs.
 #include "ycge_ctx.h"
 
-// what the queries of one context hold: made by the first query, grow-only, freed by ycge_destroy (release_query)
-struct QueryState {
-    hipStream_t stream = nullptr;
-    DevBuf<float> rays, hits;
-    DevBuf<int32_t> ids;
-    DevBuf<uint8_t> occluded;
-    DevBuf<uint32_t> first_bad;
-    DevBuf<uint64_t> spill;            // [spill levels][resident lanes]
-    uint32_t lanes[4] = {0, 0, 0, 0};  // resident lanes of k_query<has_grid, occluded>
-    void *in_stage = nullptr, *out_stage = nullptr;
-    size_t in_bytes = 0, out_bytes = 0;
-};
-
 namespace ycge_host {
 
 int query_scene_changed(ycge_ctx *c)
 {
-    if (!c->scene_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->scene_ev, hipEventDisableTiming));
+    HIP_TRY(c, c->scene_ev.ensure());
     HIP_TRY(c, hipEventRecord(c->scene_ev, c->stream));
     return YCGE_OK;
 }
 
-void release_query(ycge_ctx *c)
-{
-    if (QueryState *q = c->query) {
-        if (q->stream) (void)hipStreamSynchronize(q->stream);
-        q->rays.release(); q->hits.release(); q->ids.release(); q->occluded.release(); q->first_bad.release(); q->spill.release();
-        if (q->in_stage) (void)hipHostFree(q->in_stage);
-        if (q->out_stage) (void)hipHostFree(q->out_stage);
-        if (q->stream) (void)hipStreamDestroy(q->stream);
-        delete q;
-        c->query = nullptr;
-    }
-    if (c->scene_ev) { (void)hipEventDestroy(c->scene_ev); c->scene_ev = nullptr; }
-}
-
 namespace {
-
-int ensure_pinned(ycge_ctx *c, void *&p, size_t &have, size_t bytes)
-{
-    if (have >= bytes) return YCGE_OK;
-    if (p) { (void)hipHostFree(p); p = nullptr; have = 0; }
-    HIP_TRY(c, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    have = bytes;
-    return YCGE_OK;
-}
 
 // why ray i was refused (the device reported its index; the reason is recomputed here for that one ray)
 int refuse_ray(ycge_ctx *c, const char *fn, const float *rays, uint32_t i)
@@ -78,9 +42,9 @@ int run_query(ycge_ctx *c, const char *fn, const float *rays, int32_t n, float *
     if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "Scene BVH not built; call ycge_scene_upload first (Scene.cs:73)");
     if (n == 0) return YCGE_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->query) c->query = new QueryState();
+    if (!c->query) c->query.reset(new QueryState());
     QueryState &Q = *c->query;
-    if (!Q.stream) HIP_TRY(c, hipStreamCreateWithFlags(&Q.stream, hipStreamNonBlocking));
+    HIP_TRY(c, Q.stream.ensure());
     const int has_grid = c->has_grid ? 1 : 0, occl = occluded ? 1 : 0;
     uint32_t &lanes = Q.lanes[has_grid * 2 + occl];
     if (!lanes) lanes = ycge_launch_query_lanes(has_grid, occl, c->compute_units);
@@ -91,16 +55,14 @@ int run_query(ycge_ctx *c, const char *fn, const float *rays, int32_t n, float *
     if (occl) HIP_TRY(c, Q.occluded.reserve(un));
     else { HIP_TRY(c, Q.hits.reserve(10 * un)); HIP_TRY(c, Q.ids.reserve(2 * un)); }
     const size_t in_bytes = 32 * un, out_bytes = 64 + (occl ? un : 48 * un);       // out: {first bad ray, pad} then the records
-    int rc = ensure_pinned(c, Q.in_stage, Q.in_bytes, in_bytes);
-    if (rc == YCGE_OK) rc = ensure_pinned(c, Q.out_stage, Q.out_bytes, out_bytes);
-    if (rc != YCGE_OK) return rc;
-    std::memcpy(Q.in_stage, rays, in_bytes);
-    HIP_TRY(c, hipMemcpyAsync(Q.rays.p, Q.in_stage, in_bytes, hipMemcpyHostToDevice, Q.stream));
+    HIP_TRY(c, Q.in_stage.reserve(in_bytes)); HIP_TRY(c, Q.out_stage.reserve(out_bytes));
+    std::memcpy(Q.in_stage.p, rays, in_bytes);
+    HIP_TRY(c, hipMemcpyAsync(Q.rays.p, Q.in_stage.p, in_bytes, hipMemcpyHostToDevice, Q.stream));
     if (c->scene_ev) HIP_TRY(c, hipStreamWaitEvent(Q.stream, c->scene_ev, 0));
     HIP_TRY(c, hipMemsetAsync(Q.first_bad.p, 0xff, sizeof(uint32_t), Q.stream));
     const int e = ycge_launch_query(&c->sd, Q.rays.p, (uint32_t)n, Q.hits.p, Q.ids.p, occl ? Q.occluded.p : nullptr, Q.first_bad.p, Q.spill.p, lanes, has_grid, Q.stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "%s: k_query launch failed: %s", fn, hipGetErrorString((hipError_t)e));
-    uint8_t *out = (uint8_t *)Q.out_stage;
+    uint8_t *out = Q.out_stage.data();
     HIP_TRY(c, hipMemcpyAsync(out, Q.first_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, Q.stream));
     if (occl) HIP_TRY(c, hipMemcpyAsync(out + 64, Q.occluded.p, un, hipMemcpyDeviceToHost, Q.stream));
     else {

@@ -31,27 +31,25 @@ static int ensure_resident(ycge_ctx *c)
             c->halo_ready = true;
         }
         const size_t n = (size_t)c->hiW * c->hiH;
-        for (int k = 0; k < K; k++) {
-            auto *rs = new ycge_ctx::ResidentSet();
-            c->rsets.push_back(rs);
-            HIP_TRY(c, rs->hdr.alloc(3 * n)); HIP_TRY(c, rs->normal.alloc(3 * n)); HIP_TRY(c, rs->depth.alloc(n)); HIP_TRY(c, rs->sky.alloc(n));
-            HIP_TRY(c, rs->spill.alloc(c->stack_spill.n));
-            HIP_TRY(c, hipEventCreateWithFlags(&rs->traced, hipEventDisableTiming)); HIP_TRY(c, hipEventCreateWithFlags(&rs->resolved, hipEventDisableTiming));
+        std::vector<ycge_ctx::ResidentSet> sets((size_t)K);
+        for (ycge_ctx::ResidentSet &rs : sets) {
+            HIP_TRY(c, rs.hdr.alloc(3 * n)); HIP_TRY(c, rs.normal.alloc(3 * n)); HIP_TRY(c, rs.depth.alloc(n)); HIP_TRY(c, rs.sky.alloc(n));
+            HIP_TRY(c, rs.spill.alloc(c->stack_spill.n));
+            HIP_TRY(c, rs.traced.ensure()); HIP_TRY(c, rs.resolved.ensure());
         }
         const size_t nb = (size_t)(c->n_owned > 0 ? c->n_owned : 1) * 4;
         HIP_TRY(c, c->res_cost.alloc(nb * (ycge_ctx::kResCostFrames + 1)));          // (+ one slot nobody reads: what a schedule build "clears for the next frame")
         HIP_TRY(c, hipMemset(c->res_cost.p, 0, nb * (ycge_ctx::kResCostFrames + 1) * sizeof(uint32_t)));
         c->res_order_next = 0;
+        c->res_order.resize(3); c->res_ws.resize(3); c->res_order_ev.resize(3); c->res_order_read_ev.resize(3);
+        c->res_order_frame.assign(3, -1);
         for (int k = 0; k < 3; k++) {
-            auto *o = new DevBuf<uint32_t>(); auto *w = new DevBuf<uint32_t>();
-            c->res_order.push_back(o); c->res_ws.push_back(w);
-            HIP_TRY(c, o->alloc(nb * YCGE_SCHEDULE_SLACK)); HIP_TRY(c, w->alloc(96)); HIP_TRY(c, hipMemset(w->p, 0, 96 * sizeof(uint32_t)));
-            hipEvent_t e1 = nullptr, e2 = nullptr;
-            HIP_TRY(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming)); HIP_TRY(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-            c->res_order_ev.push_back(e1); c->res_order_read_ev.push_back(e2);
-            c->res_order_frame.push_back(-1);
+            DevBuf<uint32_t> &o = c->res_order[(size_t)k], &w = c->res_ws[(size_t)k];
+            HIP_TRY(c, o.alloc(nb * YCGE_SCHEDULE_SLACK)); HIP_TRY(c, w.alloc(96)); HIP_TRY(c, hipMemset(w.p, 0, 96 * sizeof(uint32_t)));
+            HIP_TRY(c, c->res_order_ev[(size_t)k].ensure()); HIP_TRY(c, c->res_order_read_ev[(size_t)k].ensure());
         }
-        HIP_TRY(c, hipEventCreateWithFlags(&c->res_last_traced, hipEventDisableTiming));
+        HIP_TRY(c, c->res_last_traced.ensure());
+        c->rsets = std::move(sets);          // (the ring exists only once all of it does: a call that failed above is tried again from the start)
     }
     return YCGE_OK;
 }
@@ -93,7 +91,7 @@ try {
     auto t0 = std::chrono::steady_clock::now();
     FrameState fs;
     snapshot_frame(c, fs);
-    ycge_ctx::ResidentSet *rs = c->rsets[(size_t)((uint64_t)fs.frame % (uint64_t)K)];
+    ycge_ctx::ResidentSet *rs = &c->rsets[(size_t)((uint64_t)fs.frame % (uint64_t)K)];
     if (rs->resolved_used) HIP_TRY(c, hipStreamWaitEvent(stream, rs->resolved, 0));        // TAA of frame N - K has read this set
     if (rs->traced_used) HIP_TRY(c, hipStreamWaitEvent(stream, rs->traced, 0));            // (its spill area: the trace of frame N - K, on whatever stream)
     const bool single = frame_is_single_launch(c);
@@ -110,7 +108,7 @@ try {
         for (int b = 0; b < 3; b++)
             if (c->res_order_frame[(size_t)b] >= 0 && c->res_order_frame[(size_t)b] + K <= fs.frame && (ob < 0 || c->res_order_frame[(size_t)b] > c->res_order_frame[(size_t)ob])) ob = b;
     if (ob >= 0) {
-        rt.order = c->res_order[(size_t)ob]->p; rt.n_order = c->res_ws[(size_t)ob]->p + 16;
+        rt.order = c->res_order[(size_t)ob].p; rt.n_order = c->res_ws[(size_t)ob].p + 16;
         HIP_TRY(c, hipStreamWaitEvent(stream, c->res_order_ev[(size_t)ob], 0));
     }
     if (lpt) HIP_TRY(c, hipMemsetAsync(rt.cost, 0, (size_t)n_blocks * sizeof(uint32_t), stream));          // this frame's cost slot (the kernel's atomicMax needs zeros)
@@ -136,7 +134,7 @@ try {
         HIP_TRY(c, hipStreamWaitEvent(c->side_stream, rs->traced, 0));
         if (c->res_order_frame[(size_t)tb] >= 0) HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->res_order_read_ev[(size_t)tb], 0));
         c->res_order_frame[(size_t)tb] = -1;          // (not to be picked while it is being rewritten ...)
-        e = ycge_launch_order_blocks(c->res_cost.p, n_blocks, policy, split_top, RC /* the slot nobody reads */, skip, c->res_ws[(size_t)tb]->p, c->res_order[(size_t)tb]->p, c->side_stream, 0, RC, c->cost_snap.p);      // (traces in flight write their costs meanwhile: a copy is read)
+        e = ycge_launch_order_blocks(c->res_cost.p, n_blocks, policy, split_top, RC /* the slot nobody reads */, skip, c->res_ws[(size_t)tb].p, c->res_order[(size_t)tb].p, c->side_stream, 0, RC, c->cost_snap.p);      // (traces in flight write their costs meanwhile: a copy is read)
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "schedule launch failed: %s", hipGetErrorString((hipError_t)e));
         HIP_TRY(c, hipEventRecord(c->res_order_ev[(size_t)tb], c->side_stream));
         c->res_order_frame[(size_t)tb] = fs.frame;          // (... and from frame N + K on it is the newest)
@@ -216,7 +214,7 @@ try {
     for (int k = 0; k < n; k++) {
         set_pose(k);
         snapshot_frame(c, fs[(size_t)k]);
-        ycge_ctx::ResidentSet *rs = sets[(size_t)k] = c->rsets[(size_t)((uint64_t)fs[(size_t)k].frame % (uint64_t)K)];
+        ycge_ctx::ResidentSet *rs = sets[(size_t)k] = &c->rsets[(size_t)((uint64_t)fs[(size_t)k].frame % (uint64_t)K)];
         if (rs->resolved_used) HIP_TRY(c, hipStreamWaitEvent(stream, rs->resolved, 0));
         if (rs->traced_used) HIP_TRY(c, hipStreamWaitEvent(stream, rs->traced, 0));
         const uint32_t cost_slot = (uint32_t)((uint64_t)fs[(size_t)k].frame % RC);
@@ -229,7 +227,7 @@ try {
                 if (c->res_order_frame[(size_t)b] >= 0 && c->res_order_frame[(size_t)b] + K <= fs[0].frame && (ob < 0 || c->res_order_frame[(size_t)b] > c->res_order_frame[(size_t)ob])) ob = b;
             if (ob >= 0) HIP_TRY(c, hipStreamWaitEvent(stream, c->res_order_ev[(size_t)ob], 0));
         }
-        if (ob >= 0) { rt.order = c->res_order[(size_t)ob]->p; rt.n_order = c->res_ws[(size_t)ob]->p + 16; }
+        if (ob >= 0) { rt.order = c->res_order[(size_t)ob].p; rt.n_order = c->res_ws[(size_t)ob].p + 16; }
         if (lpt) HIP_TRY(c, hipMemsetAsync(rt.cost, 0, (size_t)n_blocks * sizeof(uint32_t), stream));
         c->batch_collect = true;
         rc = trace_frame(c, nullptr, stream, fs[(size_t)k], false, nullptr, nullptr, &rt);
@@ -251,7 +249,7 @@ try {
     if (c->batch_spill_used[bp]) HIP_TRY(c, hipStreamWaitEvent(stream, c->batch_done[bp], 0));          // (the batch before the last scratched this area)
     int e = ycge_launch_trace_batch(&c->sd, c->batch_P.data(), c->batch_O.data(), n, 0, scene_is_flat(c), stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_trace_batch launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (!c->batch_done[bp]) HIP_TRY(c, hipEventCreateWithFlags(&c->batch_done[bp], hipEventDisableTiming));
+    HIP_TRY(c, c->batch_done[bp].ensure());
     HIP_TRY(c, hipEventRecord(c->batch_done[bp], stream)); c->batch_spill_used[bp] = true;
     if (ob >= 0) HIP_TRY(c, hipEventRecord(c->res_order_read_ev[(size_t)ob], stream));
     for (int k = 0; k < n; k++) {
@@ -276,7 +274,7 @@ try {
         HIP_TRY(c, hipStreamWaitEvent(c->side_stream, sets[(size_t)n - 1]->traced, 0));
         if (c->res_order_frame[(size_t)tb] >= 0) HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->res_order_read_ev[(size_t)tb], 0));
         c->res_order_frame[(size_t)tb] = -1;
-        e = ycge_launch_order_blocks(c->res_cost.p, n_blocks, policy, split_top, RC, skip, c->res_ws[(size_t)tb]->p, c->res_order[(size_t)tb]->p, c->side_stream, 0, RC, c->cost_snap.p);      // (traces in flight write their costs meanwhile: a copy is read)
+        e = ycge_launch_order_blocks(c->res_cost.p, n_blocks, policy, split_top, RC, skip, c->res_ws[(size_t)tb].p, c->res_order[(size_t)tb].p, c->side_stream, 0, RC, c->cost_snap.p);      // (traces in flight write their costs meanwhile: a copy is read)
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "schedule launch failed: %s", hipGetErrorString((hipError_t)e));
         HIP_TRY(c, hipEventRecord(c->res_order_ev[(size_t)tb], c->side_stream));
         c->res_order_frame[(size_t)tb] = fs[(size_t)n - 1].frame;
@@ -302,7 +300,7 @@ try {
     FrameState fs = c->pending.front();
     c->pending.pop_front();
     const int K = (int)c->rsets.size();
-    ycge_ctx::ResidentSet *rs = c->rsets[(size_t)((uint64_t)fs.frame % (uint64_t)K)];
+    ycge_ctx::ResidentSet *rs = &c->rsets[(size_t)((uint64_t)fs.frame % (uint64_t)K)];
     HIP_TRY(c, hipStreamWaitEvent(stream, rs->traced, 0));         // (the caller's exchange already follows the trace; this holds whatever streams it uses)
     if (st) HIP_TRY(c, hipEventRecord(c->ev[1], stream));
     int e = 0;
@@ -374,29 +372,31 @@ try {
     for (int64_t v : c->halo_send_counts) ns += (size_t)v;
     for (int64_t v : c->halo_recv_counts) nr += (size_t)v;
     const size_t sb = (ns ? ns : 1) * 16, rb = (nr ? nr : 1) * 16, hb = (size_t)c->tiles_per_rank_padded * 256 * 3 * sizeof(float);
-    std::vector<hipStream_t> st((size_t)K, nullptr);
-    std::vector<hipEvent_t> evt((size_t)K, nullptr), evr((size_t)K, nullptr);
-    std::vector<void *> send((size_t)K, nullptr), recv((size_t)K, nullptr), hist((size_t)K, nullptr);
-    hipStream_t comm = nullptr;
-    auto cleanup = [&]() {
-        (void)hipDeviceSynchronize();
-        for (int k = 0; k < K; k++) { if (st[k]) (void)hipStreamDestroy(st[k]); if (evt[k]) (void)hipEventDestroy(evt[k]); if (evr[k]) (void)hipEventDestroy(evr[k]);
-                                      if (send[k]) (void)hipFree(send[k]); if (recv[k]) (void)hipFree(recv[k]); if (hist[k]) (void)hipFree(hist[k]); }
-        if (comm) (void)hipStreamDestroy(comm);
-    };
-#define LOOP_TRY(call) do { if ((call) != hipSuccess) { cleanup(); return c->fail(YCGE_ERR_DEVICE, "%s failed", #call); } } while (0)
+    // what the loop makes goes with these owners on every way out; the destructor's body runs before any member goes: the device is idle first
+    struct Loop {
+        std::vector<Stream> st;
+        std::vector<Event> evt, evr, tl_b, tl_e;
+        std::vector<DevBuf<uint8_t>> send, recv, hist;
+        Stream comm;
+        explicit Loop(size_t k) : st(k), evt(k), evr(k), send(k), recv(k), hist(k) {}
+        ~Loop() { (void)hipDeviceSynchronize(); }
+    } loop((size_t)K);
+    auto &st = loop.st; auto &evt = loop.evt; auto &evr = loop.evr; auto &tl_b = loop.tl_b; auto &tl_e = loop.tl_e;
+    auto &send = loop.send; auto &recv = loop.recv; auto &hist = loop.hist; Stream &comm = loop.comm;
+    auto mark_on = [](std::vector<Event> &tl, hipStream_t s) { Event e; if (e.ensure(hipEventDefault) != hipSuccess || hipEventRecord(e, s) != hipSuccess) return false; tl.push_back(std::move(e)); return true; };
+#define LOOP_TRY(call) do { if ((call) != hipSuccess) return c->fail(YCGE_ERR_DEVICE, "%s failed", #call); } while (0)
     {   // the exchange + resolve stream at the highest priority (YCGE_RES_LOOP_PRIO=0: plain): its small kernels must not queue behind a
         // trace that happens to share its hardware queue - a resolve held up that way holds up the trace K frames later
         int lo = 0, hi = 0;
         const char *pe = getenv("YCGE_RES_LOOP_PRIO");
-        if ((!pe || atoi(pe) != 0) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo) LOOP_TRY(hipStreamCreateWithPriority(&comm, hipStreamNonBlocking, hi));
-        else LOOP_TRY(hipStreamCreateWithFlags(&comm, hipStreamNonBlocking));
+        if ((!pe || atoi(pe) != 0) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo) LOOP_TRY(comm.ensure_with_priority(hi));
+        else LOOP_TRY(comm.ensure());
     }
     for (int k = 0; k < K; k++) {
-        LOOP_TRY(hipStreamCreateWithFlags(&st[k], hipStreamNonBlocking));
-        LOOP_TRY(hipEventCreateWithFlags(&evt[k], hipEventDisableTiming)); LOOP_TRY(hipEventCreateWithFlags(&evr[k], hipEventDisableTiming));
-        LOOP_TRY(hipMalloc(&send[k], sb)); LOOP_TRY(hipMalloc(&recv[k], rb)); LOOP_TRY(hipMalloc(&hist[k], hb));
-        LOOP_TRY(hipMemset(send[k], 0, sb)); LOOP_TRY(hipMemset(recv[k], 0, rb));
+        LOOP_TRY(st[k].ensure());
+        LOOP_TRY(evt[k].ensure()); LOOP_TRY(evr[k].ensure());
+        LOOP_TRY(send[k].alloc(sb)); LOOP_TRY(recv[k].alloc(rb)); LOOP_TRY(hist[k].alloc(hb));
+        LOOP_TRY(hipMemset(send[k].p, 0, sb)); LOOP_TRY(hipMemset(recv[k].p, 0, rb));
     }
     std::deque<int> issued;
     // YCGE_RES_LOOP_COMM=slot: exchange and resolve of a frame on the stream of ITS ring slot (the next trace there waits for that resolve
@@ -406,8 +406,8 @@ try {
     auto resolve = [&](int k) -> int {
         hipStream_t cs = comm_on_slot ? st[k] : comm;
         if (!comm_on_slot && hipStreamWaitEvent(cs, evt[k], 0) != hipSuccess) return YCGE_ERR_DEVICE;
-        if (hipMemcpyAsync(recv[k], send[k], sb < rb ? sb : rb, hipMemcpyDeviceToDevice, cs) != hipSuccess) return YCGE_ERR_DEVICE;      // stands in for the all-to-all
-        const int r2 = ycge_resolve_tiles_resident(c, recv[k], hist[k], cs, nullptr);
+        if (hipMemcpyAsync(recv[k].p, send[k].p, sb < rb ? sb : rb, hipMemcpyDeviceToDevice, cs) != hipSuccess) return YCGE_ERR_DEVICE;      // stands in for the all-to-all
+        const int r2 = ycge_resolve_tiles_resident(c, recv[k].p, hist[k].p, cs, nullptr);
         if (r2 != YCGE_OK) return r2;
         return hipEventRecord(evr[k], cs) == hipSuccess ? YCGE_OK : YCGE_ERR_DEVICE;
     };
@@ -415,7 +415,6 @@ try {
     // YCGE_RES_LOOP_TIMELINE=1: timing events around the last 16 frames' traces (begin: behind the stream's waits; end: behind the halo
     // gather), printed relative to the first - how the K traces in flight really lie to each other
     const bool timeline = getenv("YCGE_RES_LOOP_TIMELINE") != nullptr;
-    std::vector<hipEvent_t> tl_b, tl_e;
     // YCGE_RES_LOOP_EAGER=0: a frame's exchange + resolve are queued only when its ring slot is needed again (round 4's loop).  Default: queued
     // right behind its trace (they wait for the trace's event on their own stream) - the trace that takes the slot K frames later then finds
     // the resolve done instead of waiting for one that was queued a moment ago and runs starved beside the traces in flight
@@ -426,11 +425,11 @@ try {
         if ((int)issued.size() == K) { const int r2 = resolve(issued.front()); issued.pop_front(); if (r2 != YCGE_OK) return r2; }
         if (hipStreamWaitEvent(st[k], evr[k], 0) != hipSuccess) return YCGE_ERR_DEVICE;
         const bool mark = timeline && i > 12 + (int64_t)frames - 16;
-        if (mark) { hipEvent_t eb = nullptr; if (hipEventCreate(&eb) != hipSuccess || hipEventRecord(eb, st[k]) != hipSuccess) return YCGE_ERR_DEVICE; tl_b.push_back(eb); }
-        const int r2 = ycge_trace_tiles_resident(c, send[k], st[k], nullptr);
+        if (mark && !mark_on(tl_b, st[k])) return YCGE_ERR_DEVICE;
+        const int r2 = ycge_trace_tiles_resident(c, send[k].p, st[k], nullptr);
         if (r2 != YCGE_OK) return r2;
         issued.push_back(k);
-        if (mark) { hipEvent_t ee2 = nullptr; if (hipEventCreate(&ee2) != hipSuccess || hipEventRecord(ee2, st[k]) != hipSuccess) return YCGE_ERR_DEVICE; tl_e.push_back(ee2); }
+        if (mark && !mark_on(tl_e, st[k])) return YCGE_ERR_DEVICE;
         if (hipEventRecord(evt[k], st[k]) != hipSuccess) return YCGE_ERR_DEVICE;
         if (eager) { const int r3 = resolve(issued.front()); issued.pop_front(); if (r3 != YCGE_OK) return r3; }
         return YCGE_OK;
@@ -439,7 +438,7 @@ try {
     // YCGE_RES_LOOP_BATCH=n: the frames n at a time in one launch (ycge_trace_tiles_resident_batch), consecutive batches on two streams
     const int nb = getenv("YCGE_RES_LOOP_BATCH") ? atoi(getenv("YCGE_RES_LOOP_BATCH")) : 0;
     if (nb > 1) {
-        if (nb > K || nb > ycge_ctx::kBatchMax) { cleanup(); return c->fail(YCGE_ERR_INVALID_ARG, "YCGE_RES_LOOP_BATCH=%d needs a ring of at least that many sets (and <= %d)", nb, ycge_ctx::kBatchMax); }
+        if (nb > K || nb > ycge_ctx::kBatchMax) { return c->fail(YCGE_ERR_INVALID_ARG, "YCGE_RES_LOOP_BATCH=%d needs a ring of at least that many sets (and <= %d)", nb, ycge_ctx::kBatchMax); }
         float pose[6 * ycge_ctx::kBatchMax];
         { std::lock_guard<std::mutex> g(c->cam_lock); for (int k = 0; k < nb; k++) { pose[6 * k] = c->cam_pos[0]; pose[6 * k + 1] = c->cam_pos[1]; pose[6 * k + 2] = c->cam_pos[2]; pose[6 * k + 3] = c->yaw; pose[6 * k + 4] = c->pitch; pose[6 * k + 5] = c->fov_deg; } }
         int64_t batches = 0;
@@ -448,12 +447,12 @@ try {
             hipStream_t bs = st[(size_t)((batches++ & 1) * (K >= 3 ? 2 : 1))];          // (streams 0 and 2 of the loop: neighbours share a hardware queue on this runtime - 4 queues, round robin)
             void *sends[ycge_ctx::kBatchMax];
             int slots[ycge_ctx::kBatchMax];
-            for (int k = 0; k < nb; k++) { slots[k] = (int)(i++ % K); sends[k] = send[(size_t)slots[k]]; if (hipStreamWaitEvent(bs, evr[(size_t)slots[k]], 0) != hipSuccess) return YCGE_ERR_DEVICE; }
+            for (int k = 0; k < nb; k++) { slots[k] = (int)(i++ % K); sends[k] = send[(size_t)slots[k]].p; if (hipStreamWaitEvent(bs, evr[(size_t)slots[k]], 0) != hipSuccess) return YCGE_ERR_DEVICE; }
             const bool mark = timeline && batches > 4 + (int64_t)((frames + nb - 1) / nb) - 10;
-            if (mark) { hipEvent_t eb = nullptr; if (hipEventCreate(&eb) != hipSuccess || hipEventRecord(eb, bs) != hipSuccess) return YCGE_ERR_DEVICE; tl_b.push_back(eb); }
+            if (mark && !mark_on(tl_b, bs)) return YCGE_ERR_DEVICE;
             const int r2 = ycge_trace_tiles_resident_batch(c, nb, pose, sends, bs);
             if (r2 != YCGE_OK) return r2;
-            if (mark) { hipEvent_t ee2 = nullptr; if (hipEventCreate(&ee2) != hipSuccess || hipEventRecord(ee2, bs) != hipSuccess) return YCGE_ERR_DEVICE; tl_e.push_back(ee2); }
+            if (mark && !mark_on(tl_e, bs)) return YCGE_ERR_DEVICE;
             for (int k = 0; k < nb; k++) { issued.push_back(slots[k]); if (hipEventRecord(evt[(size_t)slots[k]], bs) != hipSuccess) return YCGE_ERR_DEVICE; }
             // the frames of the batch before the last are resolved NOW (they run beside the launches in flight, starved: a batch that re-uses
             // their sets should find them done - a ring of three batches' sets lets consecutive launches lie side by side)
@@ -463,13 +462,13 @@ try {
         const int nbat = (frames + nb - 1) / nb;
         for (int w = 0; w < 4 && rc == YCGE_OK; w++) rc = batch();
         if (rc == YCGE_OK) rc = drain();
-        if (rc != YCGE_OK) { cleanup(); return rc; }
+        if (rc != YCGE_OK) return rc;
         LOOP_TRY(hipDeviceSynchronize());
         const auto b0 = std::chrono::steady_clock::now();
         for (int f = 0; f < nbat && rc == YCGE_OK; f++) rc = batch();
         if (rc == YCGE_OK) rc = drain();
         const auto b1 = std::chrono::steady_clock::now();
-        if (rc != YCGE_OK) { cleanup(); return rc; }
+        if (rc != YCGE_OK) return rc;
         LOOP_TRY(hipDeviceSynchronize());
         const auto b2 = std::chrono::steady_clock::now();
         *issue_ms = std::chrono::duration<double, std::milli>(b1 - b0).count() / (nbat * nb);
@@ -479,20 +478,17 @@ try {
             (void)hipEventElapsedTime(&b, tl_b[0], tl_b[q]); (void)hipEventElapsedTime(&e2, tl_b[0], tl_e[q]);
             fprintf(stderr, "  batch %2zu: begin %7.3f ms  end %7.3f ms  duration %6.3f\n", q, b, e2, e2 - b);
         }
-        for (hipEvent_t ev : tl_b) (void)hipEventDestroy(ev);
-        for (hipEvent_t ev : tl_e) (void)hipEventDestroy(ev);
-        cleanup();
         return YCGE_OK;
     }
     for (int w = 0; w < 12 && rc == YCGE_OK; w++) rc = frame();
     if (rc == YCGE_OK) rc = drain();
-    if (rc != YCGE_OK) { cleanup(); return rc; }
+    if (rc != YCGE_OK) return rc;
     LOOP_TRY(hipDeviceSynchronize());
     const auto t0 = std::chrono::steady_clock::now();
     for (int f = 0; f < frames && rc == YCGE_OK; f++) rc = frame();
     if (rc == YCGE_OK) rc = drain();
     const auto t1 = std::chrono::steady_clock::now();
-    if (rc != YCGE_OK) { cleanup(); return rc; }
+    if (rc != YCGE_OK) return rc;
     LOOP_TRY(hipDeviceSynchronize());
     const auto t2 = std::chrono::steady_clock::now();
 #undef LOOP_TRY
@@ -503,9 +499,6 @@ try {
         (void)hipEventElapsedTime(&b, tl_b[0], tl_b[q]); (void)hipEventElapsedTime(&e2, tl_b[0], tl_e[q]);
         fprintf(stderr, "  trace %2zu (slot %zu): begin %7.3f ms  end %7.3f ms  duration %6.3f\n", q, q % (size_t)K, b, e2, e2 - b);
     }
-    for (hipEvent_t ev : tl_b) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : tl_e) (void)hipEventDestroy(ev);
-    cleanup();
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }
