@@ -49,6 +49,16 @@ int ycge_test_encode_chexels(ycge_ctx *c, const float *sdr, int32_t w, int32_t h
 int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,
                           int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
                           size_t *out_len);
+/* ---- the post stage (csrc/ycge_post_host.cpp, csrc/ycge_post.hip) on caller-given inputs.  state_out = 6 words: {aeExposure, effective exposure} as
+ * binary32, the chunks k_exposure_sum added one by one, 0, the frame's logSum as binary32, its counted samples.
+ * ycge_test_post_stage: hist / albedo / normal hiW*hiH*3 f32, depth hiW*hiH f32, sky hiW*hiH u8 are copied over the context's TAA history and
+ * G-buffer, ae_in over its exposure state, and the frames' own run_post runs on them (knobs, schedules, side stream as in a frame);
+ * denoised_out hiW*hiH*3 (may be NULL), sdr_out fbW*fbH*6.  It dirties those buffers and the exposure state.  Refused, the context left as it
+ * was: frames in flight, a peer or multi-device context, a rank of several.
+ * ycge_test_exposure: the exposure sum kernels alone on n terms (0 = a skipped sample), serial != 0 the one-lane form; touches no context state */
+int ycge_test_post_stage(ycge_ctx *c, const float *hist, const float *albedo, const float *normal, const float *depth, const uint8_t *sky, float ae_in,
+                         float *denoised_out, float *sdr_out, uint32_t *state_out);
+int ycge_test_exposure(ycge_ctx *c, const float *terms, int64_t n, float ae_in, int32_t serial, uint32_t *state_out);
 
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */

@@ -342,6 +342,8 @@ struct ToneMapper {
     float ae_key = 0.18f, ae_speed = 0.2f, ae_exposure = 1.0f, ae_min = 0.10f, ae_max = 1.50f;
     float effective = 1.0f;
     float saturation = 2.0f, vibrance = 0.0f;
+    float last_log_sum = 0.0f;          /* logSum and cnt of the last UpdateExposure (locals there): read by the probes only */
+    int last_cnt = 0;
 
     void update_exposure(const V3 *hdr, const uint8_t *sky, int w, int h, int sample_step)   /* ToneMapper.cs:49-91 */
     {
@@ -355,6 +357,11 @@ struct ToneMapper {
                 float lum = 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z;
                 if (lum > 0.0f) { log_sum += m_log(1e-6f + lum); cnt++; }
             }
+        finish_exposure(log_sum, cnt);
+    }
+    void finish_exposure(float log_sum, int cnt)                                             /* ToneMapper.cs:81-90 */
+    {
+        last_log_sum = log_sum; last_cnt = cnt;
         float avg_log = cnt > 0 ? log_sum / (float)(cnt > 1 ? cnt : 1) : 0.0f;
         float avg_lum = m_exp(avg_log);
         float target = cnt > 0 ? ae_key / cs_max(1e-6f, avg_lum) : ae_exposure;
@@ -938,14 +945,15 @@ int orc_scene_hit_many(void *ctx, const float *od /* n x 6 */, int n, float t_mi
 /* probe for known-answer tests of steps 6-8 (denoise, exposure, downsample + tonemap) on caller-supplied buffers:
  * hdr / albedo / normal = hiW*hiH*3 f32, depth = hiW*hiH f32, sky = hiW*hiH u8; denoised_out = hiW*hiH*3,
  * sdr_out = fbW*fbH*6; exposure_io = {aeExposure before -> after, effective exposure after} */
-int orc_post_probe(int fb_w, int fb_h, int ss, const float *hdr, const float *albedo, const float *normal, const float *depth,
-                   const uint8_t *sky, int iterations, const float phi[4], float *denoised_out, float *exposure_io, float *sdr_out)
+static int post_probe(int fb_w, int fb_h, int ss, const float *hdr, const float *albedo, const float *normal, const float *depth,
+                      const uint8_t *sky, int iterations, int inplace_exact, const float phi[4], float *denoised_out, float *exposure_io, float *sdr_out,
+                      float *log_sum_out, int *cnt_out)
 {
     if (fb_w <= 0 || fb_h <= 0 || !hdr || !albedo || !normal || !depth || !sky || !phi || !denoised_out || !exposure_io || !sdr_out) return YCGE_ERR_INVALID_ARG;
     Renderer r;
     ycge_config cfg{};
     cfg.atrous_iterations = iterations; cfg.atrous_c_phi = phi[0]; cfg.atrous_n_phi = phi[1]; cfg.atrous_z_phi = phi[2]; cfg.atrous_a_phi = phi[3];
-    cfg.atrous_inplace_exact = 1;        /* the reference's buffer walk (RaytraceRenderer.cs:718) */
+    cfg.atrous_inplace_exact = inplace_exact;        /* 1: the reference's buffer walk (RaytraceRenderer.cs:718) */
     r.cfg = cfg;
     r.resize(fb_w, fb_h, ss);
     size_t n = (size_t)r.hiW * r.hiH;
@@ -956,6 +964,8 @@ int orc_post_probe(int fb_w, int fb_h, int ss, const float *hdr, const float *al
     r.tone.ae_exposure = exposure_io[0];
     r.tone.update_exposure(den, r.sky.data(), r.hiW, r.hiH, (r.ss * 2 > 2) ? r.ss * 2 : 2);
     exposure_io[0] = r.tone.ae_exposure; exposure_io[1] = r.tone.effective;
+    if (log_sum_out) *log_sum_out = r.tone.last_log_sum;
+    if (cnt_out) *cnt_out = r.tone.last_cnt;
     for (int cy = 0; cy < r.fbH; cy++) {
         int y_top0 = cy * 2 * r.ss, y_bot0 = (cy * 2 + 1) * r.ss;
         for (int cx = 0; cx < r.fbW; cx++) {
@@ -974,6 +984,36 @@ int orc_post_probe(int fb_w, int fb_h, int ss, const float *hdr, const float *al
         }
     }
     return YCGE_OK;
+}
+int orc_post_probe(int fb_w, int fb_h, int ss, const float *hdr, const float *albedo, const float *normal, const float *depth,
+                   const uint8_t *sky, int iterations, const float phi[4], float *denoised_out, float *exposure_io, float *sdr_out)
+{
+    return post_probe(fb_w, fb_h, ss, hdr, albedo, normal, depth, sky, iterations, 1, phi, denoised_out, exposure_io, sdr_out, nullptr, nullptr);
+}
+/* ... the same with config.atrous_inplace_exact given (0: the waived ping-pong) and UpdateExposure's logSum and cnt returned */
+int orc_post_probe_sums(int fb_w, int fb_h, int ss, const float *hdr, const float *albedo, const float *normal, const float *depth,
+                        const uint8_t *sky, int iterations, int inplace_exact, const float phi[4], float *denoised_out, float *exposure_io, float *sdr_out,
+                        float *log_sum_out, int *cnt_out)
+{
+    if (!log_sum_out || !cnt_out) return YCGE_ERR_INVALID_ARG;
+    return post_probe(fb_w, fb_h, ss, hdr, albedo, normal, depth, sky, iterations, inplace_exact, phi, denoised_out, exposure_io, sdr_out, log_sum_out, cnt_out);
+}
+/* ToneMapper.UpdateExposure's serial loop from the log terms onward (ToneMapper.cs:63-90): logSum += term in order, a zero term being a
+ * sample the loop skipped (cnt = the others).  state_io = {aeExposure before -> after, effective after, logSum}; returns cnt or < 0 */
+int orc_exposure_probe(const float *terms, int64_t n, float *state_io)
+{
+    if (!terms || n < 0 || !state_io) return YCGE_ERR_INVALID_ARG;
+    orc::ToneMapper tone;
+    tone.ae_exposure = state_io[0];
+    float log_sum = 0.0f;
+    int cnt = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (terms[i] == 0.0f) continue;
+        log_sum += terms[i]; cnt++;
+    }
+    tone.finish_exposure(log_sum, cnt);
+    state_io[0] = tone.ae_exposure; state_io[1] = tone.effective; state_io[2] = log_sum;
+    return cnt;
 }
 /* analysis aid: re-trace the last rendered frame and report, per pixel, the traversal steps of each of its first
  * `per_pixel` Scene.Hit calls in call order (primary, shadow rays of vertex 1, bounce, shadow rays of vertex 2, ...) */

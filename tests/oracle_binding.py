@@ -73,6 +73,10 @@ def lib() -> C.CDLL:
         L.orc_scene_hit_bruteforce.restype = C.c_int
         L.orc_scene_hit_bruteforce.argtypes = L.orc_scene_hit.argtypes
         L.orc_morton3.restype = C.c_int; L.orc_morton3.argtypes = [C.c_int] * 3
+        L.orc_post_probe_sums.restype = C.c_int
+        L.orc_post_probe_sums.argtypes = [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.orc_exposure_probe.restype = C.c_int
+        L.orc_exposure_probe.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -81,6 +85,31 @@ def _check(L, ctx, rc):
     if rc != 0:
         msg = L.orc_last_error(ctx) if ctx else b""
         raise abi.YcgeError(rc, (msg or b"").decode())
+
+
+def post_probe(fbw, fbh, ss, hdr, alb, nrm, dep, sky, iterations=3, phi=(3.0, 0.35, 2.0, 0.20), ae_in=1.0, inplace_exact=1):
+    """Steps 6-8 of TryFlipAndBlit (orc_post_probe_sums) on hiH x hiW arrays: (denoised, sdr, state) with state = {ae_exposure, effective,
+    log_sum, count} - the shape RaytraceRenderer.post_probe returns."""
+    L = lib()
+    W, H = fbw * ss, fbh * 2 * ss
+    arrs = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((hdr, np.float32), (alb, np.float32), (nrm, np.float32), (dep, np.float32), (sky, np.uint8))]
+    assert [a.size for a in arrs] == [3 * W * H] * 3 + [W * H] * 2, ([a.size for a in arrs], W, H)
+    phi_a = np.array(phi, np.float32)
+    den = np.zeros((H, W, 3), np.float32); sdr = np.zeros((fbh, fbw, 2, 3), np.float32)
+    expo = np.array([ae_in, 0.0], np.float32); log_sum = np.zeros(1, np.float32); cnt = np.zeros(1, np.int32)
+    _check(L, None, L.orc_post_probe_sums(fbw, fbh, ss, *[a.ctypes.data for a in arrs], int(iterations), int(inplace_exact), phi_a.ctypes.data,
+                                          den.ctypes.data, expo.ctypes.data, sdr.ctypes.data, log_sum.ctypes.data, cnt.ctypes.data))
+    return den, sdr, dict(ae_exposure=expo[0], effective=expo[1], log_sum=log_sum[0], count=int(cnt[0]))
+
+
+def exposure_probe(terms, ae_in=1.0):
+    """ToneMapper.UpdateExposure's serial loop from the log terms onward (orc_exposure_probe), 0 = a skipped sample."""
+    L = lib()
+    t = np.ascontiguousarray(terms, dtype=np.float32).ravel()
+    st = np.array([ae_in, 0.0, 0.0], np.float32)
+    cnt = L.orc_exposure_probe(t.ctypes.data, t.size, st.ctypes.data)
+    assert cnt >= 0, cnt
+    return dict(ae_exposure=st[0], effective=st[1], log_sum=st[2], count=int(cnt))
 
 
 NODE_DTYPE = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"), ("count", "<i4")])

@@ -876,9 +876,10 @@ def nan_aware_mismatches(a, b):
     return int(np.count_nonzero(na != nb) + np.count_nonzero((a.view(np.uint32) != b.view(np.uint32)) & ~na & ~nb))
 
 
-def run_poisoned(oracle, seed, values, what, log=print):
+def run_poisoned(oracle, seed, values, what, log=print, stages=1):
     """A drawn scene with a few poisoned values (random_scenes.poison), two frames.  Returns (differences, frames rendered): the library must take
-    the scene and finish its frames whatever the values; what of it must EQUAL the oracle's is the callers' business."""
+    the scene and finish its frames whatever the values; what of it must EQUAL the oracle's is the callers' business.  stages=2: the frames run
+    the post stage too, and the denoised image, the exposure and the SDR array are compared as well (NaN for NaN)."""
     s, pose = random_scene(seed, n_range=(20, 120))
     tags = poison(s, pose, seed, values, what)
     flat = flatten(s)
@@ -887,8 +888,17 @@ def run_poisoned(oracle, seed, values, what, log=print):
     g.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
     found = []
     for f in range(2):
-        o.render(stages=1, threads=8); g.TryFlipAndBlit()
+        if stages >= 2:
+            so = o.render(stages=2, threads=8, want_sdr=True); sg = g.TryFlipAndBlit(want_sdr=True)
+        else:
+            o.render(stages=1, threads=8); g.TryFlipAndBlit()
         bad = {}
+        if stages >= 2:
+            n = nan_aware_mismatches(o.read(abi.BUF_DENOISED), g.read(abi.BUF_DENOISED))
+            if n: bad["denoised"] = n
+            n = nan_aware_mismatches(so, sg)
+            if n: bad["sdr"] = n
+            if nan_aware_mismatches(np.float32([o.stats.exposure]), np.float32([g.stats.exposure])): bad["exposure"] = (float(o.stats.exposure), float(g.stats.exposure))
         for name, which in (("rays", abi.BUF_RAYS), ("prim_id", abi.BUF_PRIM_ID), ("sub_id", abi.BUF_SUB_ID), ("hit_t", abi.BUF_HIT_T), ("rng_state", abi.BUF_RNG_STATE),
                             ("current_hdr", abi.BUF_CURRENT_HDR), ("g_albedo", abi.BUF_G_ALBEDO), ("g_normal", abi.BUF_G_NORMAL), ("g_depth", abi.BUF_G_DEPTH),
                             ("sky", abi.BUF_SKY_MASK), ("taa_history", abi.BUF_TAA_HISTORY)):
@@ -907,9 +917,10 @@ def run_poisoned(oracle, seed, values, what, log=print):
 def test_poisoned_lights_materials_and_tame_geometry_equal_the_oracle(product_lib, oracle, path, values, what):
     """What IS held bit for bit (NaN for NaN) beyond sane scenes: lights and materials with NaN, +-inf, 1e30, FLT_MAX, denormals, -0.0 in them -
     an intensity, a position, an albedo, an index of refraction of 0 or below, transparency / reflectivity out of range - and GEOMETRY with
-    denormal, signed-zero and 1e9 coordinates."""
+    denormal, signed-zero and 1e9 coordinates.  Through the post stage as well: the denoised image, the exposure and the SDR array of the same
+    frames (whatever radiance TAA left, NaN included) equal the oracle's."""
     for seed in range(12):
-        found, _ = run_poisoned(oracle, seed, values, what)
+        found, _ = run_poisoned(oracle, seed, values, what, stages=2)
         assert not found, found
 
 
@@ -919,7 +930,10 @@ def test_wild_geometry_is_survived(product_lib, oracle, path):
     `t` that the reference's comparisons then ACCEPT as the closest hit, and from there every `t < closest` goes the way the C# happens to be
     written; the kernels' fast forms (hardware min / max in the slab test of a ray with finite reciprocals, ycge_rt.hip.h: box_scene) assume finite
     boxes.  A measured 25-70 % of such frames differ somewhere (profiles/r06/g_fuzz_scenes.txt).  What the library owes such a scene: it takes
-    it, renders, returns - no fault, no hang, no error - and rays and RNG state, which no geometry touches, still equal the oracle's."""
+    it, renders, returns - no fault, no hang, no error - and rays and RNG state, which no geometry touches, still equal the oracle's.
+    The post stage IS held on these frames, whatever the trace made of them: fed the oracle's own TAA history and G-buffer of the second
+    frame (ycge_test_post_stage), it gives the oracle's denoised image, logSum, cnt, exposure and SDR array, NaN for NaN."""
+    import post_probe_inputs as ppi
     n_diff = 0
     for seed in range(24):
         s, pose = random_scene(seed, n_range=(20, 120))
@@ -934,5 +948,10 @@ def test_wild_geometry_is_survived(product_lib, oracle, path):
             n_diff += bool(nan_aware_mismatches(o.read(abi.BUF_CURRENT_HDR), g.read(abi.BUF_CURRENT_HDR)))
         sdr = g.TryFlipAndBlit(want_sdr=True)          # ... and the post stage finishes on whatever TAA left (NaN radiance included)
         assert sdr.shape == (31, 97, 2, 3)
+        ins = [o.read(w) for w in (abi.BUF_TAA_HISTORY, abi.BUF_G_ALBEDO, abi.BUF_G_NORMAL, abi.BUF_G_DEPTH, abi.BUF_SKY_MASK)]
+        den_g, sdr_g, st_g = g.post_probe(*ins, 1.0)          # (the last use of this context: the probe overwrites its history)
+        den_o, sdr_o, st_o = oracle.post_probe(97, 31, 1, *ins, ae_in=1.0)
+        assert nan_aware_mismatches(den_o, den_g) == 0 and nan_aware_mismatches(sdr_o, sdr_g) == 0, seed
+        assert st_g["count"] == st_o["count"] and all(ppi.same_f32(st_g[k], st_o[k]) for k in ("log_sum", "ae_exposure", "effective")), (seed, st_g, st_o)
         o.close(); g.close()
     print(f"wild geometry: radiance differs somewhere in {n_diff} of 48 frames")

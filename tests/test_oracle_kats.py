@@ -263,7 +263,25 @@ def test_committed_golden_buffers_cornell():
 # ToneMapper.UpdateExposure (ToneMapper.cs:49-91), the box average of :229-264 and ToneMapAndEncode (:204-260).
 # exp / log / pow are the oracle's own scalar kernels (pinned against libm above): everything ELSE - loop order,
 # clamping, buffer aliasing, the serial sum, the tone curve - is written again here from the C# text.
-def _py_post(L, fbw, fbh, ss, hdr, alb, nrm, dep, sky, iters, phi, ae0):
+# MathF.Max / MathF.Min (.NET Core 3.0 and later): a NaN operand is returned, +0 is above -0.  The C# text uses them for SOME clamps and plain
+# comparisons (which let a NaN through unchanged) for others - each is restated below as the line it stands for is written.
+def _cs_max(a, b):
+    a, b = f32(a), f32(b)
+    if a != a: return a
+    if b != b: return b
+    if a == b: return a if np.signbit(b) else b
+    return a if a > b else b
+
+
+def _cs_min(a, b):
+    a, b = f32(a), f32(b)
+    if a != a: return a
+    if b != b: return b
+    if a == b: return a if np.signbit(a) else b
+    return a if a < b else b
+
+
+def _py_post(L, fbw, fbh, ss, hdr, alb, nrm, dep, sky, iters, phi, ae0, inplace_exact=1):
     ex = lambda v: f32(L.orc_exp(float(v)))
     W, H = fbw * ss, fbh * 2 * ss
     k = [f32(1) / f32(16), f32(1) / f32(4), f32(3) / f32(8), f32(1) / f32(4), f32(1) / f32(16)]
@@ -280,90 +298,104 @@ def _py_post(L, fbw, fbh, ss, hdr, alb, nrm, dep, sky, iters, phi, ae0):
 
     src = hdr.copy(); A = np.zeros_like(hdr); B = np.zeros_like(hdr)
     cur, dst = src, A
-    phis = [max(f32(1e-6), f32(p)) for p in phi]
-    for it in range(max(1, iters)):
-        step = 1 << it
-        for y in range(H):
-            for x in range(W):
-                if sky[y, x]:
-                    dst[y, x] = cur[y, x]; continue
-                c0 = cur[y, x].copy(); a0 = alb[y, x]; n0 = normalized(nrm[y, x]); z0 = dep[y, x]
-                wsum = f32(0); acc = np.zeros(3, f32)
-                for ky in range(-2, 3):
-                    sy = min(max(y + ky * step, 0), H - 1)
-                    for kx in range(-2, 3):
-                        sx = min(max(x + kx * step, 0), W - 1)
-                        if sky[sy, sx] != sky[y, x]:
-                            continue
-                        wb = f32(k[kx + 2] * k[ky + 2])
-                        c = cur[sy, sx]; a = alb[sy, sx]; n = normalized(nrm[sy, sx]); z = dep[sy, sx]
-                        dl = abs(f32(luma(c) - luma(c0)))
-                        dot = f32(f32(f32(n0[0] * n[0]) + f32(n0[1] * n[1])) + f32(n0[2] * n[2]))
-                        dn = max(f32(0), f32(f32(1) - dot))
-                        dz = abs(f32(z - z0))
-                        da = f32(f32(abs(f32(a[0] - a0[0])) + abs(f32(a[1] - a0[1]))) + abs(f32(a[2] - a0[2])))
-                        w = f32(f32(f32(f32(wb * ex(f32(-dl / phis[0]))) * ex(f32(-dn / phis[1]))) * ex(f32(-dz / phis[2]))) * ex(f32(-da / phis[3])))
-                        acc = np.array([f32(acc[0] + f32(c[0] * w)), f32(acc[1] + f32(c[1] * w)), f32(acc[2] + f32(c[2] * w))], f32)
-                        wsum = f32(wsum + w)
-                if wsum > f32(1e-8):
-                    inv = f32(1) / wsum
-                    dst[y, x] = [acc[0] * inv, acc[1] * inv, acc[2] * inv]
-                else:
-                    dst[y, x] = c0
-        tmp = cur; cur = dst; dst = B if tmp is A else A            # `var tmp = cur; cur = dst; dst = (tmp == scratchA) ? scratchB : scratchA`
-    den = cur
-    # UpdateExposure (serial overload)
-    st = max(2, ss * 2)
-    log_sum = f32(0); cnt = 0
-    for py in range(0, H, st):
-        for px in range(0, W, st):
-            if sky[py, px]:
-                continue
-            lum = luma(den[py, px])
-            if lum > 0:
-                log_sum = f32(log_sum + f32(L.orc_log(float(f32(f32(1e-6) + lum))))); cnt += 1
-    avg_log = f32(log_sum / f32(max(1, cnt))) if cnt > 0 else f32(0)
-    avg_lum = ex(avg_log)
-    target = f32(f32(0.18) / max(f32(1e-6), avg_lum)) if cnt > 0 else f32(ae0)
-    target = min(max(target, f32(0.10)), f32(1.50))
-    s = f32(f32(1) - ex(f32(-0.2)))
-    ae = f32(f32(ae0) + f32(f32(target - f32(ae0)) * s))
-    eff = f32(f32(1.0) * ae)
+    phis = [_cs_max(f32(1e-6), f32(p)) for p in phi]                      # MathF.Max(1e-6f, cPhi), :694-697
+    with np.errstate(all="ignore"):
+        for it in range(max(1, iters)):
+            step = 1 << it
+            for y in range(H):
+                for x in range(W):
+                    if sky[y, x]:
+                        dst[y, x] = cur[y, x]; continue
+                    c0 = cur[y, x].copy(); a0 = alb[y, x]; n0 = normalized(nrm[y, x]); z0 = dep[y, x]
+                    wsum = f32(0); acc = np.zeros(3, f32)
+                    for ky in range(-2, 3):
+                        sy = y + ky * step
+                        sy = 0 if sy < 0 else H - 1 if sy >= H else sy          # integer comparisons, :672
+                        for kx in range(-2, 3):
+                            sx = x + kx * step
+                            sx = 0 if sx < 0 else W - 1 if sx >= W else sx
+                            if sky[sy, sx] != sky[y, x]:
+                                continue
+                            wb = f32(k[kx + 2] * k[ky + 2])
+                            c = cur[sy, sx]; a = alb[sy, sx]; n = normalized(nrm[sy, sx]); z = dep[sy, sx]
+                            dl = f32(abs(f32(luma(c) - luma(c0))))                # MathF.Abs
+                            dot = f32(f32(f32(n0[0] * n[0]) + f32(n0[1] * n[1])) + f32(n0[2] * n[2]))
+                            dn = _cs_max(f32(0), f32(f32(1) - dot))                # MathF.Max(0.0f, 1.0f - n0.Dot(n)), :690
+                            dz = f32(abs(f32(z - z0)))
+                            da = f32(f32(f32(abs(f32(a[0] - a0[0]))) + f32(abs(f32(a[1] - a0[1])))) + f32(abs(f32(a[2] - a0[2]))))
+                            w = f32(f32(f32(f32(wb * ex(f32(-dl / phis[0]))) * ex(f32(-dn / phis[1]))) * ex(f32(-dz / phis[2]))) * ex(f32(-da / phis[3])))
+                            acc = np.array([f32(acc[0] + f32(c[0] * w)), f32(acc[1] + f32(c[1] * w)), f32(acc[2] + f32(c[2] * w))], f32)
+                            wsum = f32(wsum + w)
+                    if wsum > f32(1e-8):                                           # a comparison: a NaN sum takes the else branch, :705
+                        inv = f32(1) / wsum
+                        dst[y, x] = [acc[0] * inv, acc[1] * inv, acc[2] * inv]
+                    else:
+                        dst[y, x] = c0
+            tmp = cur; cur = dst            # `var tmp = cur; cur = dst; dst = (tmp == scratchA) ? scratchB : scratchA`
+            dst = (B if tmp is A else A) if inplace_exact else (B if cur is A else A)      # (0: the waived ping-pong of include/ycge.h)
+        den = cur
+        # UpdateExposure (serial overload)
+        st = max(2, ss * 2)
+        log_sum = f32(0); cnt = 0
+        for py in range(0, H, st):
+            for px in range(0, W, st):
+                if sky[py, px]:
+                    continue
+                lum = luma(den[py, px])
+                if lum > 0:
+                    log_sum = f32(log_sum + f32(L.orc_log(float(f32(f32(1e-6) + lum))))); cnt += 1
+        avg_log = f32(log_sum / f32(max(1, cnt))) if cnt > 0 else f32(0)          # Math.Max(1, cnt): integers
+        avg_lum = ex(avg_log)
+        target = f32(f32(0.18) / _cs_max(f32(1e-6), avg_lum)) if cnt > 0 else f32(ae0)      # MathF.Max(1e-6f, avgLum), ToneMapper.cs:83
+        if target < f32(0.10): target = f32(0.10)                                  # comparisons, :84-85: a NaN target stays
+        if target > f32(1.50): target = f32(1.50)
+        s = f32(f32(1) - ex(f32(-0.2)))
+        ae = f32(f32(ae0) + f32(f32(target - f32(ae0)) * s))
+        eff = f32(f32(1.0) * ae)
 
-    def aces(xv):
-        num = f32(xv * f32(f32(f32(2.51) * xv) + f32(0.03)))
-        dn_ = f32(f32(xv * f32(f32(f32(2.43) * xv) + f32(0.59))) + f32(0.14))
-        yv = f32(num / dn_) if dn_ > 0 else f32(0)
-        return min(max(yv, f32(0)), f32(1))
+        def sat01(v):                                                               # Saturate01, ToneMapper.cs:240-245: comparisons
+            return f32(0) if v < 0 else f32(1) if v > 1 else f32(v)
 
-    def map_pixel(c):
-        inv_g = f32(f32(1) / max(f32(0.1), f32(2.2)))
-        v = []
-        for ch in range(3):
-            t = aces(f32(max(f32(0), c[ch]) * eff))
-            t = min(max(t, f32(0)), f32(1))
-            v.append(min(max(f32(L.orc_pow(float(t), float(inv_g))), f32(0)), f32(1)))
-        r, g, b = v
-        yv = luma(np.array([r, g, b], f32))
-        chroma = f32(max(r, max(g, b)) - min(r, min(g, b)))
-        fsat = f32(f32(2.0) * f32(f32(1) + f32(f32(0.0) * f32(f32(1) - chroma))))
-        return [min(max(f32(yv + f32(f32(ch_ - yv) * fsat)), f32(0)), f32(1)) for ch_ in (r, g, b)]
+        def aces(xv):
+            num = f32(xv * f32(f32(f32(2.51) * xv) + f32(0.03)))
+            dn_ = f32(f32(xv * f32(f32(f32(2.43) * xv) + f32(0.59))) + f32(0.14))
+            yv = f32(num / dn_) if dn_ > 0 else f32(0)
+            if yv < 0: yv = f32(0)                                                  # comparisons, :257-258
+            if yv > 1: yv = f32(1)
+            return yv
 
-    sdr = np.zeros((fbh, fbw, 2, 3), f32)
-    inv = f32(f32(1) / f32(ss * ss))
-    for cy in range(fbh):
-        for cx in range(fbw):
-            for half, y0 in ((0, cy * 2 * ss), (1, (cy * 2 + 1) * ss)):
-                sm = np.zeros(3, f32)
-                for sy in range(ss):
-                    for sx in range(ss):
-                        sm = (sm + den[y0 + sy, cx * ss + sx]).astype(f32)
-                sdr[cy, cx, half] = map_pixel((sm * inv).astype(f32))
-    return den, ae, eff, sdr
+        def map_pixel(c):
+            inv_g = f32(f32(1) / _cs_max(f32(0.1), f32(2.2)))
+            v = []
+            for ch in range(3):
+                t = aces(f32(_cs_max(f32(0), c[ch]) * eff))                         # MathF.Max(0.0f, hdr.X) * exposure, :206
+                v.append(sat01(f32(L.orc_pow(float(sat01(t)), float(inv_g)))))
+            r, g, b = v
+            yv = luma(np.array([r, g, b], f32))
+            chroma = f32(_cs_max(r, _cs_max(g, b)) - _cs_min(r, _cs_min(g, b)))     # MathF.Max / MathF.Min, :229-230
+            fsat = f32(f32(2.0) * f32(f32(1) + f32(f32(0.0) * f32(f32(1) - chroma))))
+            return [sat01(f32(yv + f32(f32(ch_ - yv) * fsat))) for ch_ in (r, g, b)]
+
+        sdr = np.zeros((fbh, fbw, 2, 3), f32)
+        inv = f32(f32(1) / f32(ss * ss))
+        for cy in range(fbh):
+            for cx in range(fbw):
+                for half, y0 in ((0, cy * 2 * ss), (1, (cy * 2 + 1) * ss)):
+                    sm = np.zeros(3, f32)
+                    for sy in range(ss):
+                        for sx in range(ss):
+                            sm = (sm + den[y0 + sy, cx * ss + sx]).astype(f32)
+                    sdr[cy, cx, half] = map_pixel((sm * inv).astype(f32))
+    return den, ae, eff, sdr, log_sum, cnt
 
 
 @pytest.mark.parametrize("fbw,fbh,ss,iters", [(7, 4, 1, 3), (5, 3, 2, 3), (6, 3, 1, 2)])
 def test_post_stage_against_python_restatement(fbw, fbh, ss, iters):
+    """orc_post_probe and orc_post_probe_sums against _py_post: the tame data of the first version, then every family of
+    tests/post_probe_inputs.py - sky layouts, constant images, phi of 0 / below 0 / 1e-6, zero / non-unit / overflowing normals, infinite
+    and equal depths, NaN, +-inf, FLT_MAX, 1e30, denormals, -0.0 and negative radiance and albedo in every placement, all luminances <= 0 -
+    with exposures starting at 1, 0.1, 1.5 and NaN.  Bit for bit, NaN counted equal to NaN; logSum and cnt included."""
+    import post_probe_inputs as ppi
     L = ob.lib()
     L.orc_post_probe.restype = C.c_int
     L.orc_post_probe.argtypes = [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -379,13 +411,54 @@ def test_post_stage_against_python_restatement(fbw, fbh, ss, iters):
     den_o = np.zeros_like(hdr); sdr_o = np.zeros((fbh, fbw, 2, 3), f32); expo = np.array([1.0, 0.0], f32)
     assert L.orc_post_probe(fbw, fbh, ss, hdr.ctypes.data, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data, sky.ctypes.data, iters,
                             phi.ctypes.data, den_o.ctypes.data, expo.ctypes.data, sdr_o.ctypes.data) == 0
-    den_p, ae, eff, sdr_p = _py_post(L, fbw, fbh, ss, hdr, alb, nrm, dep, sky, iters, phi, 1.0)
+    den_p, ae, eff, sdr_p, log_sum_p, cnt_p = _py_post(L, fbw, fbh, ss, hdr, alb, nrm, dep, sky, iters, phi, 1.0)
     assert np.array_equal(den_o.view(np.uint32), np.ascontiguousarray(den_p, f32).view(np.uint32))
     assert bits(expo[0]) == bits(ae) and bits(expo[1]) == bits(eff)
     assert np.array_equal(sdr_o.view(np.uint32), sdr_p.view(np.uint32))
     # the in-place iteration is not a ping-pong: redoing iteration 1 out of place must give a different image
     if iters >= 2:
         assert not np.array_equal(den_p, hdr)
+        den_w = _py_post(L, fbw, fbh, ss, hdr, alb, nrm, dep, sky, iters, phi, 1.0, inplace_exact=0)[0]
+        assert not np.array_equal(den_w, den_p)
+    # ---- the families no frame produces
+    n_nan_sdr = 0
+    for k, family in enumerate(ppi.FAMILIES):
+        d = ppi.make_inputs(family, W, H, seed=fbw)
+        ae0 = [1.0, 0.1, 1.5, float("nan")][k % 4]
+        exact = 0 if (k % 5 == 4 and iters >= 2) else 1
+        den_o, sdr_o, st = ob.post_probe(fbw, fbh, ss, d["hdr"], d["alb"], d["nrm"], d["dep"], d["sky"], iters, d["phi"], ae0, exact)
+        den_p, ae, eff, sdr_p, log_sum_p, cnt_p = _py_post(L, fbw, fbh, ss, d["hdr"], d["alb"], d["nrm"], d["dep"], d["sky"], iters, d["phi"], ae0, exact)
+        what = (family, fbw, fbh, ss, iters, ae0, exact)
+        assert ppi.nan_aware_mismatches(den_o, den_p) == 0, what
+        assert st["count"] == cnt_p and ppi.same_f32(st["log_sum"], log_sum_p), (what, st, log_sum_p, cnt_p)
+        assert ppi.same_f32(st["ae_exposure"], ae) and ppi.same_f32(st["effective"], eff), (what, st, ae, eff)
+        assert ppi.nan_aware_mismatches(sdr_o, sdr_p) == 0, what
+        n_nan_sdr += int(np.isnan(sdr_o).any())
+        if family == "all_dark": assert cnt_p == 0
+    assert n_nan_sdr > 0          # (the poisoned families do reach the tone curve: MathF.Max(0, NaN) is NaN)
+
+
+def test_exposure_probe_against_a_numpy_serial_loop():
+    """orc_exposure_probe: logSum and cnt are the plain binary32 loop's; the update's tail equals orc_post_probe_sums' on an image whose sampled
+    luminances give those terms."""
+    rng = np.random.default_rng(11)
+    for n, ae0 in ((1, 1.0), (37, 0.1), (600, 1.5), (2000, float("nan"))):
+        terms = np.log(f32(1e-6) + rng.random(n).astype(f32) ** f32(3)).astype(f32)
+        terms[rng.random(n) < 0.25] = 0
+        if n == 600: terms[17] = f32(np.inf)
+        ref = f32(0)
+        with np.errstate(all="ignore"):
+            for t in terms: ref = f32(ref + t)
+        st = ob.exposure_probe(terms, ae0)
+        assert st["count"] == int(np.count_nonzero(terms)) and bits(st["log_sum"]) == bits(ref), (n, st, ref)
+    st = ob.exposure_probe(np.zeros(9, f32), 0.7)
+    assert st["count"] == 0 and bits(st["ae_exposure"]) == bits(f32(0.7)) and bits(st["effective"]) == bits(f32(0.7))
+    # the tail: a 2-pixel image (one sampled pixel) whose term is known
+    hdr = np.zeros((2, 1, 3), f32); hdr[0, 0] = 0.25
+    z3 = np.zeros((2, 1, 3), f32)
+    _, _, st_img = ob.post_probe(1, 1, 1, hdr, z3, z3, np.ones((2, 1), f32), np.zeros((2, 1), np.uint8), 1, ae_in=0.9)
+    st_t = ob.exposure_probe(np.array([st_img["log_sum"]], f32), 0.9)
+    assert st_img["count"] == 1 and bits(st_t["ae_exposure"]) == bits(st_img["ae_exposure"]) and bits(st_t["effective"]) == bits(st_img["effective"])
 
 
 def test_committed_golden_post_stage_cornell():

@@ -240,6 +240,13 @@ HOOK_PROTOTYPES = {
     "ycge_debug_peer_context": (C.c_void_p, [C.c_void_p, C.c_int32]),
     "ycge_debug_live_resources": (C.c_int, [C.POINTER(C.c_int64)]),
 }
+# test hooks of the post stage on caller-given inputs (csrc/ycge_post_host.cpp), bound where they are used (RaytraceRenderer.post_probe /
+# exposure_probe); state_out: POST_STATE_WORDS uint32
+POST_HOOK_PROTOTYPES = {
+    "ycge_test_post_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ycge_test_exposure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
+}
+POST_STATE_WORDS = 6
 
 _lib = None
 

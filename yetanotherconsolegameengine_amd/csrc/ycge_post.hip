@@ -26,8 +26,10 @@ struct AtrousParams {
 struct ToneState {                          // ToneMapper fields that change (ToneMapper.cs:13,17)
     float ae_exposure;
     float effective;
-    uint32_t count;                         // scratch: sampled pixels with lum > 0 this frame
+    uint32_t count;                         // diagnostics: chunks k_exposure_sum added one by one this frame (0 from the serial form)
     uint32_t pad;
+    float log_sum;                          // the frame's logSum and cnt (ToneMapper.cs:63-77) as the sum kernels left them: read by the
+    uint32_t samples;                       // test hooks only (ycge_test_post_stage / ycge_test_exposure), nothing on the device reads them
 };
 
 __device__ __forceinline__ F3 ld3(const float *p, size_t i) { return f3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
@@ -797,6 +799,8 @@ __global__ __launch_bounds__(64) void k_exposure_sum_serial(const float *__restr
     state->ae_exposure = ae;
     state->effective = K.tone_exposure * ae;
     state->count = 0;
+    state->log_sum = log_sum;
+    state->samples = total_cnt;
 }
 
 // part 2, the default: the SAME serial fp32 sum, evaluated exactly without being serial.
@@ -1049,6 +1053,8 @@ __global__ __launch_bounds__(1024) void k_exposure_sum(const float *__restrict__
     state->ae_exposure = ae;
     state->effective = K.tone_exposure * ae;
     state->count = (uint32_t)s_serial;          // diagnostics: chunks that took the serial path this frame
+    state->log_sum = log_sum;
+    state->samples = s_total_cnt;
 }
 
 // ToneMapper.ToneMapAndEncode + ApplySaturation, ToneMapper.cs:204-260
@@ -1212,14 +1218,22 @@ size_t ycge_exposure_scratch_bytes(int w, int h, int step)
     return ((n_chunks * sizeof(double) + 63) & ~(size_t)63) + n_chunks * sizeof(ycge::ExpoRec) + 64;
 }
 
+int ycge_launch_exposure_sums(const float *terms, int n, void *state, const float consts[5], void *scratch, int serial, hipStream_t stream);
 int ycge_launch_exposure(const float *hdr, const uint8_t *sky, int w, int h, int step, float *terms, void *state, const float consts[5],
                          void *scratch, int serial, hipStream_t stream)
 {
     const int nsx = (w + step - 1) / step, nsy = (h + step - 1) / step;
     const int n = nsx * nsy;
-    ycge::ToneConsts K = {consts[0], consts[1], consts[2], consts[3], consts[4]};
     hipLaunchKernelGGL(ycge::k_exposure_terms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hdr, sky, w, h, step, nsx, nsy, terms,
                        (ycge::ToneState *)state);
+    return ycge_launch_exposure_sums(terms, n, state, consts, scratch, serial, stream);
+}
+
+// part 2 alone: terms[0 .. n) followed by one count word per 256 terms, as k_exposure_terms leaves them (run_post through
+// ycge_launch_exposure; the ycge_test_exposure hook with terms of the caller's)
+int ycge_launch_exposure_sums(const float *terms, int n, void *state, const float consts[5], void *scratch, int serial, hipStream_t stream)
+{
+    ycge::ToneConsts K = {consts[0], consts[1], consts[2], consts[3], consts[4]};
     if (serial || !scratch) {       // YCGE_EXPOSURE_SERIAL: the one-lane chain (A/B and cross-check of the chunked evaluation)
         hipLaunchKernelGGL(ycge::k_exposure_sum_serial, dim3(1), dim3(64), 0, stream, terms, n, K, (ycge::ToneState *)state);
         return (int)hipGetLastError();

@@ -360,7 +360,92 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
 
 } // namespace ycge_host
 
+namespace {
+// who may be probed: a context that renders whole frames by itself, with nothing queued on it
+int check_post_probe(ycge_ctx *c, const char *fn)
+{
+    if (c->parent || !c->peers.empty() || c->exchange_mode == YCGE_EXCHANGE_RCCL) return c->fail(YCGE_ERR_INVALID_ARG, "%s: a one-device context only (this one is a peer or drives peers)", fn);
+    if (c->cfg.world_size != 1) return c->fail(YCGE_ERR_INVALID_ARG, "%s: a one-device context only (this one is rank %d of %d)", fn, c->cfg.rank, c->cfg.world_size);
+    if (c->async_outstanding || !c->pending.empty()) return c->fail(YCGE_ERR_INVALID_ARG, "%s: frames are in flight on this context (ycge_wait first)", fn);
+    return YCGE_OK;
+}
+} // namespace
+
 extern "C" {
+
+// test hook: steps 6-8 on caller-given inputs, through run_post itself.  The arrays replace the context's own taa_hist, g_albedo, g_normal, g_depth
+// and sky (hiW x hiH of the size ycge_create / ycge_resize set), ae_in its exposure state; knobs, schedule cache, side stream and the
+// persistent launch's bookkeeping are the context's, as in a frame.  DIRTIES: those five buffers, the tone state, the denoise buffers and what
+// ycge_read_buffer(YCGE_BUF_DENOISED) returns - a frame rendered afterwards blends into the probe's history unless the caller resets it
+// (ycge_resize to the same size does) and continues from the probe's exposure (a probe of an all-sky image counts no sample and so leaves
+// the state at its ae_in: that is how a caller puts a value back).
+// denoised_out: hiW*hiH*3 (may be NULL); sdr_out: fbW*fbH*6; state_out: {aeExposure, effective exposure, chunks added one by one, 0, logSum, cnt}.
+int ycge_test_post_stage(ycge_ctx *c, const float *hist, const float *albedo, const float *normal, const float *depth, const uint8_t *sky, float ae_in,
+                         float *denoised_out, float *sdr_out, uint32_t *state_out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!hist || !albedo || !normal || !depth || !sky || !sdr_out || !state_out) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_post_stage: a NULL array");
+    { const int rc = check_post_probe(c, "ycge_test_post_stage"); if (rc != YCGE_OK) return rc; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->hiW * c->hiH;
+    if (!c->taa_hist.p || !c->g_albedo.p || !c->g_normal.p || !c->g_depth.p || !c->sky.p || c->taa_hist.n < 3 * n || c->g_albedo.n < 3 * n || c->g_normal.n < 3 * n || c->g_depth.n < n || c->sky.n < n)
+        return c->fail(YCGE_ERR_INTERNAL, "ycge_test_post_stage: the context holds no frame buffers of %d x %d", c->hiW, c->hiH);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(c->taa_hist.p, hist, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->g_albedo.p, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->g_normal.p, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->g_depth.p, depth, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->sky.p, sky, n, hipMemcpyHostToDevice));
+    if (!c->tone_state.p) HIP_TRY(c, c->tone_state.alloc(ycge_post_state_bytes()));
+    {
+        uint32_t init[6] = {0, 0, 0, 0, 0, 0};
+        static_assert(sizeof(float) == 4, "binary32");
+        if (ycge_post_state_bytes() != sizeof init) return c->fail(YCGE_ERR_INTERNAL, "ycge_test_post_stage: the tone state is %zu bytes, not %zu", ycge_post_state_bytes(), sizeof init);
+        std::memcpy(&init[0], &ae_in, 4); std::memcpy(&init[1], &ae_in, 4);        // (effective = toneExposure * aeExposure, toneExposure = 1)
+        HIP_TRY(c, hipMemcpy(c->tone_state.p, init, sizeof init, hipMemcpyHostToDevice));
+    }
+    StagedSdrGuard staged(c);
+    const int rc = run_post(c, c->stream, sdr_out, false);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (rc != YCGE_OK) return rc;
+    finish_staged_sdr(c);
+    if (denoised_out) { const int cr = copy_out(c, denoised_out, c->denoised, 3 * n * sizeof(float)); if (cr != YCGE_OK) return cr; }
+    return copy_out(c, state_out, c->tone_state.p, 6 * sizeof(uint32_t));
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: the exposure sum kernels alone (serial != 0: k_exposure_sum_serial, else the chunked form) on n caller-given terms, a zero term
+// being a skipped sample (cnt = the terms that are not zero).  Buffers of its own on the context's device and stream: the context's state
+// is not touched.  state_out as ycge_test_post_stage.
+int ycge_test_exposure(ycge_ctx *c, const float *terms, int64_t n, float ae_in, int32_t serial, uint32_t *state_out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!terms || !state_out || n <= 0 || n > ((int64_t)1 << 26)) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_exposure: bad arguments (n = %lld)", (long long)n);
+    { const int rc = check_post_probe(c, "ycge_test_exposure"); if (rc != YCGE_OK) return rc; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_blocks = ((size_t)n + 255) / 256;
+    std::vector<float> host((size_t)n + n_blocks);          // the terms, then k_exposure_terms' count word per 256 of them
+    std::memcpy(host.data(), terms, (size_t)n * sizeof(float));
+    for (size_t b = 0; b < n_blocks; b++) {
+        uint32_t cnt = 0;
+        for (size_t i = b * 256; i < (b + 1) * 256 && i < (size_t)n; i++) cnt += !(terms[i] == 0.0f);
+        std::memcpy(&host[(size_t)n + b], &cnt, 4);
+    }
+    DevBuf<float> d_terms; DevBuf<uint8_t> d_state, d_scratch;
+    HIP_TRY(c, d_terms.upload(host));
+    HIP_TRY(c, d_state.alloc(ycge_post_state_bytes()));
+    HIP_TRY(c, d_scratch.alloc(ycge_exposure_scratch_bytes((int)n, 1, 1)));
+    uint32_t init[6] = {0, 0, 0, 0, 0, 0};
+    if (ycge_post_state_bytes() != sizeof init) return c->fail(YCGE_ERR_INTERNAL, "ycge_test_exposure: the tone state is %zu bytes, not %zu", ycge_post_state_bytes(), sizeof init);
+    std::memcpy(&init[0], &ae_in, 4); std::memcpy(&init[1], &ae_in, 4);
+    HIP_TRY(c, hipMemcpy(d_state.p, init, sizeof init, hipMemcpyHostToDevice));
+    const float tone_consts[5] = {1.0f, 0.18f, 0.2f, 0.10f, 1.50f};     // as run_post
+    const int e = ycge_launch_exposure_sums(d_terms.p, (int)n, d_state.p, tone_consts, d_scratch.p, serial ? 1 : 0, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "exposure launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return copy_out(c, state_out, d_state.p, sizeof init);
+}
+catch (...) { return ycge_host::abi_catch(c); }
 
 // Level schedule of an in-place A-trous iteration (host only).  pixels_out: w*h uint32, offsets_out: capacity
 // uint32.  Returns the number of levels (offsets_out holds levels + 1 entries) or <0.

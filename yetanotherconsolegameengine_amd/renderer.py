@@ -490,6 +490,40 @@ class RaytraceRenderer:
         self._check(self.L.ycge_read_timed_steps(self.ctx, C.byref(n)))
         return int(n.value)
 
+    def _post_hook(self, name: str):
+        fn = getattr(self.L, name)
+        fn.restype, fn.argtypes = abi.POST_HOOK_PROTOTYPES[name]
+        return fn
+
+    @staticmethod
+    def _post_state(words: np.ndarray) -> dict:
+        f = words.view(np.float32)
+        return dict(ae_exposure=f[0], effective=f[1], serial_chunks=int(words[2]), log_sum=f[4], count=int(words[5]))
+
+    def post_probe(self, hist, albedo, normal, depth, sky, ae_in: float = 1.0):
+        """Steps 6-8 of TryFlipAndBlit on caller-given hiH x hiW arrays (ycge_test_post_stage): the frames' own post stage, with this
+        renderer's config and knobs.  Returns (denoised, sdr, state) with state = {ae_exposure, effective, serial_chunks, log_sum, count}.
+        Overwrites the TAA history, the G-buffer and the exposure state of the context."""
+        n = self.hiH * self.hiW
+        arrs = []
+        for a, dt, k in ((hist, np.float32, 3 * n), (albedo, np.float32, 3 * n), (normal, np.float32, 3 * n), (depth, np.float32, n), (sky, np.uint8, n)):
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != k:
+                raise ValueError(f"post_probe: an array of {a.size} elements where the {self.hiW} x {self.hiH} trace grid needs {k}")
+            arrs.append(a)
+        den = np.zeros((self.hiH, self.hiW, 3), np.float32)
+        sdr = np.zeros((self.fbH, self.fbW, 2, 3), np.float32)
+        st = np.zeros(abi.POST_STATE_WORDS, np.uint32)
+        self._check(self._post_hook("ycge_test_post_stage")(self.ctx, *[a.ctypes.data for a in arrs], float(ae_in), den.ctypes.data, sdr.ctypes.data, st.ctypes.data))
+        return den, sdr, self._post_state(st)
+
+    def exposure_probe(self, terms, ae_in: float = 1.0, serial: bool = False) -> dict:
+        """The exposure sum kernels alone (ycge_test_exposure) on a vector of log terms, 0 = a skipped sample; the state as post_probe's."""
+        t = np.ascontiguousarray(terms, dtype=np.float32).ravel()
+        st = np.zeros(abi.POST_STATE_WORDS, np.uint32)
+        self._check(self._post_hook("ycge_test_exposure")(self.ctx, t.ctypes.data, t.size, float(ae_in), int(bool(serial)), st.ctypes.data))
+        return self._post_state(st)
+
     def read(self, which: int) -> np.ndarray:
         dt, n = abi.BUFFER_LAYOUT[which]
         shape = (self.hiH, self.hiW, n) if n > 1 else (self.hiH, self.hiW)
