@@ -203,6 +203,12 @@ namespace ConsoleGame.RayTracing.Native
         [DllImport(Lib)] public static extern int ycge_render_frame_ansi(IntPtr ctx, int consoleW, int consoleH, int viewportX, int viewportY, int defaultFg16,
                                                                          int defaultBg16, int clearScreen, byte* outStream, UIntPtr capacity, UIntPtr* outLen,
                                                                          float* outTopBottomSdr, YFrameStats* stats);
+        // Video mode (after ABI 10, found by symbol lookup): VideoRenderer.TryFlipAndBlit of the frame IFrameReader.GetCurrentFramePtr() shows
+        [DllImport(Lib)] public static extern int ycge_video_blit(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, float* outTopBottomSdr, byte* outColor16,
+                                                                  byte* outAnsi, byte* outRgba);
+        [DllImport(Lib)] public static extern int ycge_video_blit_ansi(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int consoleW, int consoleH, int viewportX,
+                                                                       int viewportY, int defaultFg16, int defaultBg16, int clearScreen, byte* outStream, UIntPtr capacity,
+                                                                       UIntPtr* outLen, float* outTopBottomSdr);
         [DllImport(Lib)] public static extern int ycge_wait(IntPtr ctx);
         [DllImport(Lib)] public static extern int ycge_async_trace_times(IntPtr ctx, float* msOut, int capacity, out int nOut);
         [DllImport(Lib)] public static extern int ycge_flight_query(IntPtr ctx, out YFlightInfo info);

@@ -440,6 +440,36 @@ int ycge_ansi_stream_bound(int32_t console_w, int32_t console_h, size_t *bytes);
 int ycge_render_frame_ansi(ycge_ctx *ctx, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
                            int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len,
                            float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+/* --- Video mode: the other renderer behind the reference's IConsoleRenderer seam (RaytraceEntity.cs:12-50, VideoWrapper -> VideoRenderer),
+ * for a host that presents through the device encoders and must not fall back to CPU threads when the user switches to a camera or a
+ * video.  Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no struct changes; a host detects these exports by symbol lookup.
+ * ycge_video_blit is VideoRenderer.TryFlipAndBlit (Renderer/VideoRenderer.cs:68-148) for the frame IFrameReader.GetCurrentFramePtr() shows:
+ * src_w x src_h pixels of bytes_per_pixel = 3 (BGR) or 4 (BGRA, the 4th byte ignored), row-major, no row padding - letterboxed into the
+ * context's hi-res grid (fbW, fbH, ss of ycge_create / ycge_resize: hiW = fbW*ss, hiH = fbH*2*ss), each hi-res sample a 6 x 6 Lanczos-3
+ * resample, ss*ss samples averaged per half-cell.
+ *   Same pixels: out_top_bottom_sdr is, bit for bit, the {topAvg, botAvg} that VideoRenderer.cs:127-128 passes to new Chexel('\u2580', ...), in
+ *   the layout of ycge_render_frame.  out_color16 / out_ansi / out_rgba are what ycge_render_frame_chexels gives for those values, and the
+ *   stream of ycge_video_blit_ansi is what ycge_render_frame_ansi gives for those pairs (arguments, bound, refusals and output as there).
+ *   The weights come from the C library's sinf (MathF.Sin).  The reference's bilinear fallback (:215: a weight sum <= 0) is not implemented:
+ *   no geometry is known to reach it, and one that did fails with YCGE_ERR_INTERNAL instead of showing other pixels.
+ *   No scene needed: a context that never saw ycge_scene_upload blits.
+ *   Frame state untouched: a blit changes nothing a ray-traced frame reads - frame counter, TAA history, exposure state, trace outputs,
+ *   schedule, statistics.  It first waits for the frames in flight, like every entry point except the scene queries, and returns with the
+ *   destinations filled; `frame` is the caller's own again then.  There is no frames-in-flight form of the blit (deliberately: a video
+ *   frame is a copy and one short launch, there is nothing to overlap it with).
+ *   Geometry follows ycge_resize (VideoWrapper.Resize makes a new VideoRenderer).
+ *   A pageable `frame` goes up through page-locked staging of the library; a page-locked one (ycge_alloc_host_buffer, ycge_pin_host_buffer)
+ *   goes up directly.  Destinations as for ycge_render_frame_chexels: any subset may be NULL, not all of them.
+ *   Refused before any device work with YCGE_ERR_INVALID_ARG, nothing written then or later, the context usable: NULL frame, src_w or
+ *   src_h < 1, bytes_per_pixel not 3 or 4, src_w*src_h*bytes_per_pixel >= 2^31, all destinations NULL, a peer context of the one-process
+ *   multi-device form (its root blits on devices[0]); for the stream form also NULL out_stream or out_len, a console that is not positive
+ *   or whose bound reaches 2^32, defaults outside 0..15, capacity below ycge_ansi_stream_bound. */
+int ycge_video_blit(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                    float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba);
+int ycge_video_blit_ansi(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                         int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
+                         int32_t default_fg16, int32_t default_bg16, int32_t clear_screen,
+                         uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr /* may be NULL */);
 int ycge_wait(ycge_ctx *ctx);
 /* measurement: durations (ms) of the trace launches of the frames queued since the last call, oldest first (at most the last 1024);
  * waits for the frames in flight */

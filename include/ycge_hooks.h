@@ -49,6 +49,14 @@ int ycge_test_encode_chexels(ycge_ctx *c, const float *sdr, int32_t w, int32_t h
 int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,
                           int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
                           size_t *out_len);
+/* ---- Video mode (csrc/ycge_video.cpp).  ycge_host_video_tables: host only, no device - for src_w x src_h -> fbW x fbH ss the tables
+ * k_video_blit reads, as the library computed them with the C library's sinf: per hi-res column x0 (hiW = fbW*ss entries) and its six
+ * normalised weights (6 hiW), per hi-res row y0 (hiH = fbH*2*ss) and weights (6 hiH), and {scale, offX, offY} (VideoRenderer.cs:75-81).
+ * ycge_test_video_blit: the kernel alone on a caller-given geometry, whatever the context's framebuffer is; sdr_out fbW*fbH*6 f32 */
+int ycge_host_video_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0_out, float *wx_out, int32_t *y0_out,
+                           float *wy_out, float *geometry_out);
+int ycge_test_video_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t fbW, int32_t fbH, int32_t ss,
+                         float *sdr_out);
 /* ---- the post stage (csrc/ycge_post_host.cpp, csrc/ycge_post.hip) on caller-given inputs.  state_out = 6 words: {aeExposure, effective exposure} as
  * binary32, the chunks k_exposure_sum added one by one, 0, the frame's logSum as binary32, its counted samples.
  * ycge_test_post_stage: hist / albedo / normal hiW*hiH*3 f32, depth hiW*hiH f32, sky hiW*hiH u8 are copied over the context's TAA history and

@@ -217,6 +217,10 @@ _PROTOTYPES = {
     "ycge_ansi_stream_bound": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "ycge_render_frame_ansi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
                                          C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(FrameStats)]),
+    "ycge_video_blit": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint8),
+                                  C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "ycge_video_blit_ansi": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
     "ycge_read_buffer": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_set_frame_counter": (C.c_int, [C.c_void_p, C.c_int64]),
     "ycge_read_timed_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -247,6 +251,11 @@ POST_HOOK_PROTOTYPES = {
     "ycge_test_exposure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
 }
 POST_STATE_WORDS = 6
+# test hooks of Video mode (csrc/ycge_video.cpp), bound where they are used (renderer.video_tables / VideoRenderer.blit_probe)
+VIDEO_HOOK_PROTOTYPES = {
+    "ycge_host_video_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ycge_test_video_blit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+}
 
 _lib = None
 

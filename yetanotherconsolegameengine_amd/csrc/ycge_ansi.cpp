@@ -173,6 +173,41 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// Video mode (ycge_video.cpp): the stream of VideoRenderer.TryFlipAndBlit's chexels for the frame the host's IFrameReader shows
+int ycge_video_blit_ansi(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t console_w, int32_t console_h,
+                         int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
+                         size_t *out_len, float *out_top_bottom_sdr)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_video_blit_ansi";
+    unsigned long long bound = 0;
+    int rc = video_check_frame(c, fn, frame, src_w, src_h, bytes_per_pixel);
+    if (rc == YCGE_OK) rc = check_stream_args(c, fn, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
+    if (rc != YCGE_OK) return rc;
+    rc = join_async(c);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    AnsiCall call(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    StagedSdrGuard staged(c);
+    ChexelState &X = c->chexels;
+    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
+    const float *d_sdr = nullptr;
+    if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
+    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, d_sdr, false);
+    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out_top_bottom_sdr);
+    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, false);          // (the stream kernels and the length's copy)
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const unsigned long long len = *static_cast<const unsigned long long *>(X.ansi_len_host.p);
+    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
+    rc = copy_stream(c, X, out_stream, (size_t)len);
+    if (rc != YCGE_OK) return rc;
+    finish_staged_sdr(c);
+    *out_len = (size_t)len;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 // test hook: the stream kernels alone on caller-given ANSI pairs (fbW x fbH {fg, bg}, any values 0..255), with the geometry, defaults and
 // refusals of ycge_render_frame_ansi; on the context's device and stream, with a pairs buffer of its own
 int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,

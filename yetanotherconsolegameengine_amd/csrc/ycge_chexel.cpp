@@ -203,6 +203,51 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// Video mode (ycge_video.cpp): VideoRenderer.TryFlipAndBlit of the frame the host's IFrameReader shows, into the destinations of
+// ycge_render_frame_chexels.  Upload and k_video_blit, then this file's encode and read-back on the same stream, then one synchronisation.
+int ycge_video_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, float *out_top_bottom_sdr, uint8_t *out_color16,
+                    uint8_t *out_ansi, uint8_t *out_rgba)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_video_blit";
+    int rc = video_check_frame(c, fn, frame, src_w, src_h, bytes_per_pixel);
+    if (rc != YCGE_OK) return rc;
+    if (!out_top_bottom_sdr && !out_color16 && !out_ansi && !out_rgba)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, color16, ansi, rgba)", fn);
+    rc = join_async(c);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ChexelCall call(c, out_color16, out_ansi, out_rgba);
+    StagedSdrGuard staged(c);
+    const float *d_sdr = nullptr;
+    rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
+    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, d_sdr, false);
+    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out_top_bottom_sdr);
+    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, false);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }          // (nothing of this call is queued when its staging is let go)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    finish_staged_sdr(c);
+    call.finish();
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: the column and row tables of a video geometry as the library computes them (host only; ycge_video.cpp)
+int ycge_host_video_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0_out, float *wx_out, int32_t *y0_out, float *wy_out,
+                           float *geometry_out)
+try {
+    return video_host_tables(src_w, src_h, fbW, fbH, ss, x0_out, wx_out, y0_out, wy_out, geometry_out);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// test hook: k_video_blit alone on a caller-given geometry, whatever the context's framebuffer is; returns with the SDR in the caller's array
+int ycge_test_video_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return video_test_blit(c, frame, src_w, src_h, bytes_per_pixel, fbW, fbH, ss, sdr_out);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 // test hook: the two threshold tables of LinearToSrgb8 (255 entries each), host only
 int ycge_host_srgb_thresholds(float *f32_out, double *f64_out)
 try {

@@ -92,6 +92,7 @@ int ycge_launch_chexels(const float *sdr, int fbW, int fbH, const uint8_t *table
 uint32_t ycge_launch_ansi_tiles(uint32_t cells);
 int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
                             int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
+int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
 int ycge_launch_grid_encode(const void *descs, int n_grids, void *results, uint32_t n_workgroups, hipStream_t stream);
 int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
@@ -264,6 +265,15 @@ struct ChexelState {
     DevBuf<float> ansi_palette;                        // the 16 palette colours as 8 SDR chexels, then their 16 ANSI indices (bytes at float 48)
     bool ansi_palette_ready = false;
     PinnedBuf ansi_len_host;                           // page-locked word the length is copied to
+};
+// what the video blits of one context hold (ycge_video.cpp): made by the first blit, grow-only; nothing a ray-traced frame reads
+struct VideoState {
+    int32_t key[5] = {0, 0, 0, 0, 0};                  // {src_w, src_h, fbW, fbH, ss} the tables were made for
+    DevBuf<uint8_t> tables;                            // int32 x0[hiW], f32 wx[hiW][6], int32 y0[hiH], f32 wy[hiH][6]
+    DevBuf<uint8_t> frame;                             // the source frame
+    DevBuf<float> sdr;                                 // its chexels {top rgb, bottom rgb}
+    PinnedBuf stage;                                   // page-locked staging of a pageable source frame
+    int64_t table_builds = 0;
 };
 
 struct ycge_ctx {
@@ -490,6 +500,7 @@ struct ycge_ctx {
     // device chexel colours (ycge_render_frame_chexels / _async_chexels, ycge_chexel.cpp): the request of the call at hand, the encoded
     // buffers per post parity, the threshold tables, the staging of pageable destinations
     ChexelState chexels;
+    VideoState video;            // Video mode (ycge_video_blit, ycge_video.cpp)
 
     ycge_ctx() = default;
     ycge_ctx(const ycge_ctx &) = delete;
@@ -582,4 +593,11 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post);             
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
 int ensure_tables(ycge_ctx *c, ChexelState &X);                                           // ycge_chexel.cpp: LinearToSrgb8's thresholds on the device, once
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs);                // ycge_ansi.cpp: the stream kernels behind the encode, and the length's copy
+// ycge_video.cpp: Video mode.  The refusals of a source frame; upload + k_video_blit on `stream` for a geometry (*d_sdr: its SDR array);
+// the SDR read-back (a pageable array: staged as run_post does it, finish_staged_sdr behind the stream); the test hooks' bodies
+int video_check_frame(ycge_ctx *c, const char *fn, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp);
+int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const float **d_sdr);
+int video_read_sdr(ycge_ctx *c, hipStream_t stream, const float *d_sdr, float *out_sdr);
+int video_host_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0, float *wx, int32_t *y0, float *wy, float *geom3);
+int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out);
 } // namespace ycge_host

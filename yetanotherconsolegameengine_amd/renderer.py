@@ -545,3 +545,106 @@ class RaytraceRenderer:
         cu = C.c_int32()
         self._check(self.L.ycge_device_info(self.ctx, name, 256, C.byref(cu)))
         return name.value.decode(), cu.value
+
+
+def video_tables(src_width: int, src_height: int, fb_width: int, fb_height: int, superSample: int = 1, lib=None):
+    """The tables k_video_blit reads for a src_width x src_height frame on a fb_width x fb_height console (ycge_host_video_tables; host
+    only, no GPU needed): (x0 int32[hiW], wx f32[hiW, 6], y0 int32[hiH], wy f32[hiH, 6], (scale, offX, offY))."""
+    L = lib if lib is not None else abi.load_library()
+    fn = L.ycge_host_video_tables
+    fn.restype, fn.argtypes = abi.VIDEO_HOOK_PROTOTYPES["ycge_host_video_tables"]
+    ss = max(1, int(superSample))
+    hiW, hiH = fb_width * ss, fb_height * 2 * ss
+    x0, wx = np.zeros(hiW, np.int32), np.zeros((hiW, 6), np.float32)
+    y0, wy = np.zeros(hiH, np.int32), np.zeros((hiH, 6), np.float32)
+    geom = np.zeros(3, np.float32)
+    rc = fn(int(src_width), int(src_height), int(fb_width), int(fb_height), ss, x0.ctypes.data, wx.ctypes.data, y0.ctypes.data, wy.ctypes.data, geom.ctypes.data)
+    if rc != 0:
+        raise abi.YcgeError(rc, (L.ycge_last_error(None) or b"").decode())
+    return x0, wx, y0, wy, tuple(geom)
+
+
+class VideoRenderer:
+    """Host-side mirror of the reference's other renderer behind the IConsoleRenderer seam (Renderer/VideoRenderer.cs; VideoWrapper,
+    RaytraceEntity.cs:38-50): TryFlipAndBlit resamples the frame a reader shows (Lanczos-3, letterboxed) into the console's chexels, on the
+    device (ycge_video_blit).  Built over a RaytraceRenderer's context - the mode switch of RaytraceEntity: both renderers of one console -
+    or over a context of its own, which needs no scene.  The readers (ffmpeg, camera) stay on the host: a frame is a numpy uint8 array of
+    shape (height, width, 3) BGR or (height, width, 4) BGRA, what IFrameReader.GetCurrentFramePtr() points at."""
+
+    def __init__(self, fb_width: int = 0, fb_height: int = 0, superSample: int = 1, *, renderer: Optional[RaytraceRenderer] = None, lib=None, device: int = 0):
+        self._own = renderer is None
+        self._r = renderer if renderer is not None else RaytraceRenderer(None, fb_width, fb_height, superSample=superSample, lib=lib, device=device)
+        self.L = self._r.L
+
+    fbW = property(lambda self: self._r.fbW)
+    fbH = property(lambda self: self._r.fbH)
+    ss = property(lambda self: self._r.ss)
+    ctx = property(lambda self: self._r.ctx)
+
+    def close(self):
+        if self._own:
+            self._r.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def SetCamera(self, pos, yaw: float, pitch: float):          # VideoWrapper.SetCamera / SetFov: no-ops (RaytraceEntity.cs:44-45)
+        return None
+
+    def SetFov(self, fovDeg: float):
+        return None
+
+    def Resize(self, fb_width: int, fb_height: int, superSample: int):
+        """VideoWrapper.Resize makes a new VideoRenderer for the new console: the context's geometry follows (ycge_resize)."""
+        self._r.Resize(fb_width, fb_height, superSample)
+
+    @staticmethod
+    def _frame_args(frame):
+        f = np.asarray(frame)
+        if f.dtype != np.uint8 or f.ndim != 3 or not f.flags.c_contiguous:
+            raise ValueError("a video frame is a C-contiguous uint8 array of shape (height, width, 3 or 4)")
+        return f, f.ctypes.data_as(C.POINTER(C.c_uint8)), int(f.shape[1]), int(f.shape[0]), int(f.shape[2])
+
+    def TryFlipAndBlit(self, frame, color16: bool = True, ansi: bool = False, rgba: bool = False, sdr: bool = False, out: Optional[dict] = None) -> dict:
+        """VideoRenderer.TryFlipAndBlit for `frame`: {name: array} for each output asked (shapes: RaytraceRenderer.chexel_shapes) - the SDR
+        {topAvg, botAvg} of VideoRenderer.cs:127-128 bit for bit, and the presenters' colour maps of it.  `out` = caller's arrays to fill
+        instead (any of sdr / color16 / ansi / rgba; pageable or page-locked)."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        if out is None:
+            want = {"sdr": sdr, "color16": color16, "ansi": ansi, "rgba": rgba}
+            out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self._r.chexel_shapes().items() if want[k]}
+        self._r._check(self.L.ycge_video_blit(self.ctx, ptr, w, h, bpp, *RaytraceRenderer._chexel_pointers(out)))
+        return out
+
+    def TryFlipAndBlitAnsi(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                           clear_screen: bool = False, sdr: bool = False):
+        """The bytes ANSITerminalRenderer.Render() writes for a console over this framebuffer showing `frame` (ycge_video_blit_ansi):
+        `bytes`, or (bytes, SDR array) with sdr=True.  The stream buffer is the RaytraceRenderer's (page-locked, growable)."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        r = self._r
+        bound = RaytraceRenderer.ansi_stream_bound(console_width, console_height, self.L)
+        buf = r.__dict__.get("_ansi_buf")
+        if buf is None or buf[0].size < bound:
+            r.__dict__.pop("_ansi_buf", None)
+            buf = r.__dict__["_ansi_buf"] = r._page_locked_zeros((bound,), np.uint8)
+        o = buf[0]
+        n = C.c_size_t(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        r._check(self.L.ycge_video_blit_ansi(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
+                                             int(default_bg), int(bool(clear_screen)), o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size, C.byref(n),
+                                             s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
+        stream = o[:n.value].tobytes()
+        return (stream, s) if sdr else stream
+
+    # ---------------------------------------------------------------- tests only
+    def blit_probe(self, frame, fb_width: int, fb_height: int, superSample: int = 1) -> np.ndarray:
+        """k_video_blit alone on a caller-given geometry (ycge_test_video_blit), whatever this console's size: the SDR array."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        fn = self.L.ycge_test_video_blit
+        fn.restype, fn.argtypes = abi.VIDEO_HOOK_PROTOTYPES["ycge_test_video_blit"]
+        s = np.zeros((fb_height, fb_width, 2, 3), np.float32)
+        self._r._check(fn(self.ctx, f.ctypes.data, w, h, bpp, int(fb_width), int(fb_height), int(superSample), s.ctypes.data))
+        return s
