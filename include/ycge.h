@@ -323,7 +323,10 @@ const char *ycge_last_error(const ycge_ctx *ctx);
 
 /* scene.RebuildBVH()   RaytraceRenderer.cs:107, RaytraceEntity.cs:244, Scene.cs:122-127.
  * Builds the scene BVH (Objects/BVH.cs:258-459) and every mesh BVH
- * (Objects/MeshBVH.cs:371-576) bit-faithfully and uploads them. */
+ * (Objects/MeshBVH.cs:371-576) and uploads them.  A mesh BVH is built
+ * bit-faithfully, on the device from N triangles on
+ * (N = YCGE_MESH_BVH_DEVICE_MIN, default 4 000: the measured crossover,
+ * profiles/mesh_build_rate.json) and on the host below. */
 int ycge_scene_upload(ycge_ctx *ctx, const ycge_scene *scene);
 /* per-frame entity animation of lights / sky (Scenes/DayNightCycle.cs:80-89) */
 int ycge_scene_update_lights(ycge_ctx *ctx, const ycge_light *lights, int32_t n_lights,

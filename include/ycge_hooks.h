@@ -71,6 +71,8 @@ int ycge_test_exposure(ycge_ctx *c, const float *terms, int64_t n, float ae_in, 
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */
 int ycge_debug_device_bvh(const float *bounds, const float *centroids, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *result_out, void *build_out);   /* k_scene_bvh_build alone */
+int ycge_debug_mesh_bvh_stats(ycge_ctx *c, int64_t *out8);           /* how ycge_scene_upload built the mesh BVHs: device builds, host builds, host builds after the device builder declined, us of the last device build; of the last upload: Array.Sort cases, deepest tree, wide nodes, subtree workgroups.  c = NULL: YCGE_ERR_INVALID_ARG and out8[0..2] = YCGE_MESH_BVH_HOST, _DEVICE_MIN, _WIDE_MIN as parsed now (no device) */
+int ycge_debug_device_mesh_bvh(const float *tris9, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *res16);   /* the device-side mesh BVH builder alone (csrc/ycge_mesh_bvh_build.hip), no context; what it declines the host builds.  res16: depth, Array.Sort cases, wide nodes, subtree workgroups, fallback reason (0: built on the device), built on the device, wide levels, us.  Returns the node count; YCGE_ERR_NO_DEVICE_CODE without a device */
 int ycge_debug_read_walk_tree(ycge_ctx *c, void *gnodes_out, void *walk_out, int32_t capacity_nodes, int32_t *grid_owner_out, int32_t n_grids, uint32_t *root_and_limit_out);
 int ycge_debug_read_grid(ycge_ctx *c, int32_t grid_index, void *record_out /* sizeof GGrid = 112 bytes */, int32_t *materials_out);   /* a resident grid as the device holds it: its record and, per voxel in ycge_grid.cells order, the material of its cell code (-1 = empty) */
 ycge_ctx *ycge_debug_peer_context(ycge_ctx *c, int32_t k);           /* the context of device k + 1 of a one-process multi-device context (NULL: none): the scene calls refuse it */
@@ -90,6 +92,7 @@ size_t ycge_wf_sizes(int which);
 size_t ycge_post_state_bytes(void);
 size_t ycge_exposure_scratch_bytes(int w, int h, int step);
 size_t ycge_bvh_build_scratch_bytes(int n);
+size_t ycge_mesh_bvh_sizes(int which);
 int ycge_atrous_persist_resident(int groups_per_pass, int split, int profile);
 void ycge_atrous_duo_pad_lds(int bytes);
 void ycge_peer_worker_main(ycge_ctx *c, ycge_ctx *p);                /* a peer device's thread function (started by ycge_create) */

@@ -256,6 +256,15 @@ VIDEO_HOOK_PROTOTYPES = {
     "ycge_host_video_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ycge_test_video_blit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }
+# test / profiling hooks of the device-side mesh BVH build (csrc/ycge_mesh_bvh.cpp), bound where they are used (RaytraceRenderer.mesh_bvh_stats,
+# device_mesh_bvh below); res16: MESH_BVH_RES_WORDS uint32, the fallback reasons as the library names them
+MESH_BVH_HOOK_PROTOTYPES = {
+    "ycge_debug_device_mesh_bvh": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ycge_debug_mesh_bvh_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+MESH_BVH_RES_WORDS = 16
+MESH_BVH_STATS = ("device_builds", "host_builds", "host_fallbacks", "last_device_build_us", "sort_fallbacks", "max_depth", "wide_nodes", "subtree_workgroups")
+MESH_BVH_BUILT, MESH_BVH_SORT_NO_SPLIT, MESH_BVH_SORT_EMPTY_SIDE, MESH_BVH_TOP_OVERFLOW, MESH_BVH_TOO_DEEP, MESH_BVH_NON_FINITE = range(6)
 
 _lib = None
 

@@ -77,6 +77,15 @@ size_t ycge_exposure_scratch_bytes(int w, int h, int step);
 size_t ycge_bvh_build_scratch_bytes(int n);
 int ycge_launch_scene_bvh_build(const float *items, int n, void *scratch, void *ref_out, void *gnodes_out, uint32_t *leaf_out, void *result,
                                 int active_waves, hipStream_t stream);
+size_t ycge_mesh_bvh_sizes(int which);
+int ycge_launch_mesh_items(const float *tris9, int n, float *items, uint32_t *hdr, hipStream_t stream);
+int ycge_launch_mesh_init(int n, int wide, uint32_t *ord, int32_t *node_of, void *top, int32_t *level0, int32_t *jobs, uint32_t *hdr, hipStream_t stream);
+int ycge_launch_mesh_wide_level(const float *items, int n, int n_cur, int wide_min, int next_slot, uint32_t *ord, uint32_t *ord2, int32_t *node_of, const int32_t *level,
+                                int32_t *level_next, int32_t *jobs, void *top, int top_cap, void *acc, uint8_t *flag, uint32_t *lpref, uint32_t *blk, uint32_t *blk_excl,
+                                uint32_t *back_l, uint32_t *hdr, hipStream_t stream);
+int ycge_launch_mesh_subtrees(const float *items, int n, const uint32_t *ord, float *items_pos, const int32_t *jobs, int n_jobs, void *top, void *sub_nodes,
+                              uint32_t *leaf_out, uint32_t *hdr, hipStream_t stream);
+int ycge_launch_mesh_assemble(void *top, int n_top, int n_levels, const int32_t *jobs, int n_jobs, const void *sub_nodes, void *nodes_out, uint32_t *hdr, hipStream_t stream);
 int ycge_launch_exposure(const float *hdr, const uint8_t *sky, int w, int h, int step, float *terms, void *state, const float consts[5],
                          void *scratch, int serial, hipStream_t stream);
 int ycge_launch_exposure_sums(const float *terms, int n, void *state, const float consts[5], void *scratch, int serial, hipStream_t stream);
@@ -139,6 +148,9 @@ struct Knobs {
     int bvh_waves = 16;              // YCGE_BVH_WAVES: wavefronts of k_scene_bvh_build that take nodes (tests: the order nodes are split in must not matter)
     bool scene_bvh_host = false;     // YCGE_SCENE_BVH_HOST: ycge_scene_update_objects builds the scene BVH on the host, not on the device
     int scene_bvh_device_min = YCGE_BVH_DEV_MIN_ITEMS_DEFAULT;   // YCGE_SCENE_BVH_DEVICE_MIN: fewer objects than this are built on the host (measured crossover, profiles/r02/f2_update_objects_timing.txt)
+    bool mesh_bvh_host = false;      // YCGE_MESH_BVH_HOST: ycge_scene_upload builds every mesh BVH on the host
+    int mesh_bvh_device_min = YCGE_MESH_BVH_DEV_MIN_TRIS_DEFAULT;   // YCGE_MESH_BVH_DEVICE_MIN: meshes of fewer triangles are built on the host (measured crossover of the whole upload, profiles/mesh_build_rate.json)
+    int mesh_bvh_wide_min = YCGE_BVH_DEV_MAX_ITEMS;   // YCGE_MESH_BVH_WIDE_MIN: nodes of more items take the several-workgroup path of ycge_mesh_bvh_build.hip (9 .. the one-workgroup capacity; tests: many wide levels on small meshes)
     int res_sched_every = 0;         // YCGE_RES_SCHED_EVERY: the tile-resident ring builds a new schedule behind every n-th frame (0 = the ring's depth)
     int bfs_rays = 0;                // YCGE_BFS=<n>: a wavefront's occlusion queries against a mesh go breadth-first from one shared work list when at most n of its lanes ask (mesh_anyhit_bfs; 0 = never, 64 = always)
     bool no_flight_stage_overlap = false;   // YCGE_NO_FLIGHT_STAGE_OVERLAP: frames in flight of the stage pipeline (voxel worlds) one trace at a time (A/B)
@@ -195,6 +207,11 @@ struct Knobs {
         scene_bvh_host = getenv("YCGE_SCENE_BVH_HOST") != nullptr;
         bvh_waves = geti("YCGE_BVH_WAVES", 16);
         scene_bvh_device_min = geti("YCGE_SCENE_BVH_DEVICE_MIN", YCGE_BVH_DEV_MIN_ITEMS_DEFAULT);
+        mesh_bvh_host = getenv("YCGE_MESH_BVH_HOST") != nullptr;
+        mesh_bvh_device_min = geti("YCGE_MESH_BVH_DEVICE_MIN", YCGE_MESH_BVH_DEV_MIN_TRIS_DEFAULT);
+        mesh_bvh_wide_min = geti("YCGE_MESH_BVH_WIDE_MIN", YCGE_BVH_DEV_MAX_ITEMS);
+        if (mesh_bvh_wide_min < 9) mesh_bvh_wide_min = 9;
+        if (mesh_bvh_wide_min > YCGE_BVH_DEV_MAX_ITEMS) mesh_bvh_wide_min = YCGE_BVH_DEV_MAX_ITEMS;
     }
 };
 
@@ -211,6 +228,31 @@ struct FrameState {
 struct MeshHost {
     BuiltTree tree;
 };
+
+// The device-side mesh BVH build (ycge_mesh_bvh.cpp drives the kernels of ycge_mesh_bvh_build.hip): its scratch, kept from mesh to mesh of
+// one upload and given back when the upload ends, and what it reports about one build.
+struct MeshBvhScratch {
+    DevBuf<float> tris, items, items_pos;
+    DevBuf<uint32_t> ord, ord2, lpref, blk, blk_excl, back_l, hdr, leaf;
+    DevBuf<int32_t> node_of, level[2], jobs;
+    DevBuf<uint8_t> flag, top, acc, sub_nodes, nodes;
+    PinnedBuf stage;
+    void release()
+    {
+        tris.release(); items.release(); items_pos.release(); ord.release(); ord2.release(); lpref.release(); blk.release(); blk_excl.release(); back_l.release();
+        hdr.release(); leaf.release(); node_of.release(); level[0].release(); level[1].release(); jobs.release(); flag.release(); top.release(); acc.release();
+        sub_nodes.release(); nodes.release(); stage.release();
+    }
+};
+enum { MESH_BVH_BUILT = 0, MESH_BVH_SORT_NO_SPLIT = 1, MESH_BVH_SORT_EMPTY_SIDE = 2, MESH_BVH_TOP_OVERFLOW = 3, MESH_BVH_TOO_DEEP = 4, MESH_BVH_NON_FINITE = 5 };
+struct MeshBvhReport {
+    int fallback = MESH_BVH_BUILT;     // why the host builds this mesh instead (MESH_BVH_*); Array.Sort at a wide node and a non-finite coordinate are the expected ones
+    int wide_nodes = 0, levels = 0, jobs = 0;
+    double us = 0.0;                   // items kernel to the tree in host memory
+    hipError_t error = hipSuccess;
+};
+// YCGE_OK: `out` is build_tree(triangle_items(tris9), TreeFlavour::Mesh); 1: not built, rep.fallback says why; YCGE_ERR_*: rep.error
+int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int wide_min, hipStream_t stream, BuiltTree &out, MeshBvhReport &rep);
 
 // The resident voxel grids of a scene (ycge_grid_encode.cpp): the grids of the last ycge_scene_upload keep their indices and its packing;
 // ycge_scene_attach_grids takes the lowest free index, a block of the cell arena (size-keyed free list, 256-byte alignment, else the end of
@@ -493,6 +535,10 @@ struct ycge_ctx {
     int64_t bvh_device_builds = 0, bvh_host_fallbacks = 0, bvh_host_builds = 0;
     double bvh_last_build_us = 0.0;
     std::vector<MeshHost> meshes;
+    MeshBvhScratch mesh_bvh;                   // device-side mesh BVH builds of the upload at hand
+    int64_t mesh_bvh_device_builds = 0, mesh_bvh_host_builds = 0, mesh_bvh_host_fallbacks = 0;       // since the context was made
+    int64_t mesh_bvh_sorts = 0, mesh_bvh_depth = 0, mesh_bvh_wide_nodes = 0, mesh_bvh_jobs = 0;       // of the last upload: summed / deepest over its meshes
+    double mesh_bvh_last_us = 0.0;
     // scene queries (ycge_scene_hit / ycge_scene_occluded, ycge_query.cpp): a stream and buffers of their own, made by the first query;
     // scene_ev marks the device work of the last scene change on `stream` - a query waits for it and for nothing a frame queued after it
     std::unique_ptr<QueryState> query;

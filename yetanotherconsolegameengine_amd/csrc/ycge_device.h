@@ -42,6 +42,7 @@ enum : uint32_t {
 #define YCGE_TRACE_BATCH_MAX 8          // frames in one launch of k_trace_batch: their parameter and output records ride in the kernel arguments
 #define YCGE_WALK_LEAF_NODES 6          // walk tree: entries set aside per leaf child (a leaf holds at most 7 objects: 6 nodes)
 #define YCGE_BVH_DEV_MAX_ITEMS 2560     // one workgroup keeps the item order and its node queue in LDS
+#define YCGE_MESH_BVH_DEV_MIN_TRIS_DEFAULT 4000     // ycge_scene_upload builds a mesh BVH on the device from this many triangles on: the smallest measured count at which the device upload is no slower (1 000: 1.09 against 0.52 ms; 4 000: 1.67 against 2.27; config 4: 214 against 652 - profiles/mesh_build_rate.json)
 #define YCGE_BVH_DEV_MIN_ITEMS_DEFAULT 1400     // below this ycge_scene_update_objects builds on the host: the measured crossover of the two builders
 struct BvhBuildResult {
     uint32_t root_ref;

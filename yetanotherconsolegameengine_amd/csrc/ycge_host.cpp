@@ -1201,12 +1201,30 @@ try {
     std::vector<GMesh> &gmeshes = A.gmeshes;
     gmeshes.assign(s->n_meshes, GMesh{});
     int max_mesh_depth = 0;
+    c->mesh_bvh_sorts = c->mesh_bvh_depth = c->mesh_bvh_wide_nodes = c->mesh_bvh_jobs = 0;
+    struct ScratchOfThisUpload { MeshBvhScratch &s; ~ScratchOfThisUpload() { s.release(); } } scratch_of_this_upload{c->mesh_bvh};      // kept from mesh to mesh, given back however the upload ends
     for (int mi = 0; mi < s->n_meshes; mi++) {
         const ycge_mesh &m = s->meshes[mi];
-        BoundsSoA items;
-        triangle_items(m.triangles, m.n_triangles, items);
         BuiltTree &t = c->meshes[mi].tree;
-        build_tree(items, TreeFlavour::Mesh, t);
+        // the tree is built on the device (ycge_mesh_bvh_build.hip, the same tree byte for byte) from YCGE_MESH_BVH_DEVICE_MIN triangles on - on the
+        // host below that, under YCGE_MESH_BVH_HOST, and for what the device builder declines: Array.Sort at a node wider than one workgroup, a
+        // non-finite coordinate, a tree deeper than the reference's stack (the host builder words that error)
+        bool on_device = !c->knobs.mesh_bvh_host && m.n_triangles >= 1 && m.n_triangles >= c->knobs.mesh_bvh_device_min;
+        if (on_device) {
+            MeshBvhReport rep;
+            const int brc = mesh_bvh_build_device(c->mesh_bvh, m.triangles, m.n_triangles, c->knobs.mesh_bvh_wide_min, c->stream, t, rep);
+            if (brc < 0) return c->fail(brc, "mesh %d: device-side BVH build failed: %s", mi, hipGetErrorString(rep.error));
+            if (brc == 1) { on_device = false; c->mesh_bvh_host_fallbacks++; }
+            else { c->mesh_bvh_device_builds++; c->mesh_bvh_last_us = rep.us; c->mesh_bvh_wide_nodes += rep.wide_nodes; c->mesh_bvh_jobs += rep.jobs; }
+        }
+        if (!on_device) {
+            BoundsSoA items;
+            triangle_items(m.triangles, m.n_triangles, items);
+            build_tree(items, TreeFlavour::Mesh, t);
+            c->mesh_bvh_host_builds++;
+        }
+        c->mesh_bvh_sorts += t.sort_fallbacks;
+        if (t.max_depth > c->mesh_bvh_depth) c->mesh_bvh_depth = t.max_depth;
         if (t.max_depth > 64) return c->fail(YCGE_ERR_STACK_DEPTH, "mesh %d: BVH depth %d exceeds the reference's 64-entry stack (MeshBVH.cs:150)", mi, t.max_depth);
         if (t.max_depth > max_mesh_depth) max_mesh_depth = t.max_depth;
         GMesh &gm = gmeshes[mi];
@@ -1422,6 +1440,56 @@ try {
     if (!c || !out6) return YCGE_ERR_INVALID_ARG;
     out6[0] = c->bvh_device_builds; out6[1] = c->bvh_host_fallbacks; out6[2] = c->bvh_host_builds; out6[3] = (int64_t)c->bvh_last_build_us;
     out6[4] = c->scene_tree.sort_fallbacks; out6[5] = c->scene_tree.max_depth;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook, no context: the builder alone on the current device, with ycge_scene_upload's answer to what it declines (the host builds
+// the mesh).  nodes_out: 2 n records of 40 bytes, leaf_out: n.  res16: {depth, Array.Sort cases, wide nodes, subtree workgroups, fallback
+// reason (MESH_BVH_*, 0 = built on the device), 1 = built on the device, wide levels, microseconds of the device build}.  Returns the node
+// count; YCGE_ERR_NO_DEVICE_CODE without a device, nothing written.  YCGE_MESH_BVH_WIDE_MIN is read at every call.
+int ycge_debug_device_mesh_bvh(const float *tris9, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *res16)
+try {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { (void)hipGetLastError(); return YCGE_ERR_NO_DEVICE_CODE; }
+    if (n < 0 || !res16 || (n > 0 && (!tris9 || !nodes_out || !leaf_out))) return YCGE_ERR_INVALID_ARG;
+    Knobs knobs;
+    knobs.read();
+    MeshBvhScratch scratch;
+    MeshBvhReport rep;
+    BuiltTree t;
+    const int rc = mesh_bvh_build_device(scratch, tris9, n, knobs.mesh_bvh_wide_min, nullptr, t, rep);
+    if (rc < 0) return rc;
+    if (rc == 1) {
+        BoundsSoA items;
+        triangle_items(tris9, n, items);
+        build_tree(items, TreeFlavour::Mesh, t);
+    }
+    if (!t.nodes.empty()) std::memcpy(nodes_out, t.nodes.data(), t.nodes.size() * sizeof(RefNode));
+    if (!t.leaf_index.empty()) std::memcpy(leaf_out, t.leaf_index.data(), t.leaf_index.size() * 4);
+    for (int k = 0; k < 16; k++) res16[k] = 0u;
+    res16[0] = (uint32_t)t.max_depth; res16[1] = (uint32_t)t.sort_fallbacks; res16[2] = (uint32_t)rep.wide_nodes; res16[3] = (uint32_t)rep.jobs;
+    res16[4] = (uint32_t)rep.fallback; res16[5] = rc == YCGE_OK ? 1u : 0u; res16[6] = (uint32_t)rep.levels; res16[7] = (uint32_t)rep.us;
+    return (int)t.nodes.size();
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// test / profiling hook: how ycge_scene_upload built the mesh BVHs - {device builds, host builds, host builds after the device builder
+// declined (counted in host builds too), microseconds of the last device build (items kernel to the tree in host memory), and of the last
+// upload: Array.Sort cases, deepest tree, wide nodes, subtree workgroups}.  Without a context: YCGE_ERR_INVALID_ARG, and out8[0..2] = the
+// three knobs as the environment gives them now (YCGE_MESH_BVH_HOST, _DEVICE_MIN, _WIDE_MIN after its clamp) - host only, no device.
+int ycge_debug_mesh_bvh_stats(ycge_ctx *c, int64_t *out8)
+try {
+    if (!out8) return YCGE_ERR_INVALID_ARG;
+    if (!c) {
+        Knobs knobs;
+        knobs.read();
+        for (int k = 0; k < 8; k++) out8[k] = 0;
+        out8[0] = knobs.mesh_bvh_host ? 1 : 0; out8[1] = knobs.mesh_bvh_device_min; out8[2] = knobs.mesh_bvh_wide_min;
+        return YCGE_ERR_INVALID_ARG;
+    }
+    out8[0] = c->mesh_bvh_device_builds; out8[1] = c->mesh_bvh_host_builds; out8[2] = c->mesh_bvh_host_fallbacks; out8[3] = (int64_t)c->mesh_bvh_last_us;
+    out8[4] = c->mesh_bvh_sorts; out8[5] = c->mesh_bvh_depth; out8[6] = c->mesh_bvh_wide_nodes; out8[7] = c->mesh_bvh_jobs;
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }

@@ -250,6 +250,16 @@ class RaytraceRenderer:
         return dict(device_builds=int(out[0]), host_fallbacks=int(out[1]), host_builds=int(out[2]), last_build_us=int(out[3]),
                     sort_fallbacks=int(out[4]), max_depth=int(out[5]))
 
+    def mesh_bvh_stats(self) -> dict:
+        """How ycge_scene_upload built the mesh BVHs: on the device (csrc/ycge_mesh_bvh_build.hip), on the host, on the host after the device
+        builder declined (counted as host builds too) - since the context was made; microseconds of the last device build (items kernel to
+        the tree in host memory); and of the last upload: Array.Sort cases, deepest tree, wide nodes, subtree workgroups."""
+        out = (C.c_int64 * 8)()
+        fn = self.L.ycge_debug_mesh_bvh_stats
+        fn.restype, fn.argtypes = abi.MESH_BVH_HOOK_PROTOTYPES["ycge_debug_mesh_bvh_stats"]
+        self._check(fn(self.ctx, out))
+        return {k: int(v) for k, v in zip(abi.MESH_BVH_STATS, out)}
+
     def Resize(self, fb_width: int, fb_height: int, superSample: int):
         self._check(self.L.ycge_resize(self.ctx, fb_width, fb_height, superSample))          # (joins the frames in flight: nothing writes the old arrays any more)
         self._set_dims(fb_width, fb_height, max(1, superSample))
