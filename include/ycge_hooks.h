@@ -73,6 +73,10 @@ int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge
 int ycge_debug_device_bvh(const float *bounds, const float *centroids, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *result_out, void *build_out);   /* k_scene_bvh_build alone */
 int ycge_debug_mesh_bvh_stats(ycge_ctx *c, int64_t *out8);           /* how ycge_scene_upload built the mesh BVHs: device builds, host builds, host builds after the device builder declined, us of the last device build; of the last upload: Array.Sort cases, deepest tree, wide nodes, subtree workgroups.  c = NULL: YCGE_ERR_INVALID_ARG and out8[0..2] = YCGE_MESH_BVH_HOST, _DEVICE_MIN, _WIDE_MIN as parsed now (no device) */
 int ycge_debug_device_mesh_bvh(const float *tris9, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *res16);   /* the device-side mesh BVH builder alone (csrc/ycge_mesh_bvh_build.hip), no context; what it declines the host builds.  res16: depth, Array.Sort cases, wide nodes, subtree workgroups, fallback reason (0: built on the device), built on the device, wide levels, us.  Returns the node count; YCGE_ERR_NO_DEVICE_CODE without a device */
+int ycge_debug_device_mesh_arena(const float *tris9, int32_t n, void *out, int64_t capacity_bytes, uint32_t *root_ref_out, uint32_t *tl_offset_out, uint32_t *res8);   /* the twin of ycge_host_mesh_arena_treelets on the device, no context: the tree (device builder, or the host's tree uploaded when it declines), then records and treelets by csrc/ycge_mesh_emit.hip.  res8: tree built on the device, nodes, record units, us of layout / records / treelets, 0, 0.  Returns the arena's bytes; YCGE_ERR_NO_DEVICE_CODE without a device */
+int ycge_debug_read_mesh_arena(ycge_ctx *c, void *dst, int64_t capacity_bytes, uint32_t *tl_offset_out);   /* the context's resident mesh arena (records, then the treelet region at *tl_offset_out, 0 = none), whichever side wrote it; returns its bytes */
+int ycge_debug_read_meshes(ycge_ctx *c, void *dst, int32_t capacity_meshes);   /* the GMesh records the device holds (32 bytes each: root box, root reference); returns how many */
+int ycge_debug_mesh_emit_stats(ycge_ctx *c, int64_t *out4);          /* who wrote the arena of the last upload: meshes emitted on the device, on the host, us of the last device layout + records + treelets, arena bytes.  c = NULL: YCGE_ERR_INVALID_ARG and out4[0..1] = YCGE_MESH_EMIT_HOST, _DEVICE_MIN as parsed now (no device) */
 int ycge_debug_read_walk_tree(ycge_ctx *c, void *gnodes_out, void *walk_out, int32_t capacity_nodes, int32_t *grid_owner_out, int32_t n_grids, uint32_t *root_and_limit_out);
 int ycge_debug_read_grid(ycge_ctx *c, int32_t grid_index, void *record_out /* sizeof GGrid = 112 bytes */, int32_t *materials_out);   /* a resident grid as the device holds it: its record and, per voxel in ycge_grid.cells order, the material of its cell code (-1 = empty) */
 ycge_ctx *ycge_debug_peer_context(ycge_ctx *c, int32_t k);           /* the context of device k + 1 of a one-process multi-device context (NULL: none): the scene calls refuse it */

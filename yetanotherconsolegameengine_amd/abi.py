@@ -265,6 +265,17 @@ MESH_BVH_HOOK_PROTOTYPES = {
 MESH_BVH_RES_WORDS = 16
 MESH_BVH_STATS = ("device_builds", "host_builds", "host_fallbacks", "last_device_build_us", "sort_fallbacks", "max_depth", "wide_nodes", "subtree_workgroups")
 MESH_BVH_BUILT, MESH_BVH_SORT_NO_SPLIT, MESH_BVH_SORT_EMPTY_SIDE, MESH_BVH_TOP_OVERFLOW, MESH_BVH_TOO_DEEP, MESH_BVH_NON_FINITE = range(6)
+# test / profiling hooks of the arena assembled on the device (csrc/ycge_mesh_emit.hip), bound where they are used (RaytraceRenderer.mesh_emit_stats /
+# read_mesh_arena, device_mesh_arena in the tests); res8: MESH_EMIT_RES_WORDS uint32
+MESH_EMIT_HOOK_PROTOTYPES = {
+    "ycge_debug_device_mesh_arena": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ycge_debug_read_mesh_arena": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ycge_debug_read_meshes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "ycge_debug_mesh_emit_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+MESH_EMIT_RES_WORDS = 8
+MESH_EMIT_RES = ("tree_built_on_device", "nodes", "record_units", "layout_us", "records_us", "treelets_us")
+MESH_EMIT_STATS = ("device_meshes", "host_meshes", "last_device_emit_us", "arena_bytes")
 
 _lib = None
 

@@ -86,6 +86,11 @@ int ycge_launch_mesh_wide_level(const float *items, int n, int n_cur, int wide_m
 int ycge_launch_mesh_subtrees(const float *items, int n, const uint32_t *ord, float *items_pos, const int32_t *jobs, int n_jobs, void *top, void *sub_nodes,
                               uint32_t *leaf_out, uint32_t *hdr, hipStream_t stream);
 int ycge_launch_mesh_assemble(void *top, int n_top, int n_levels, const int32_t *jobs, int n_jobs, const void *sub_nodes, void *nodes_out, uint32_t *hdr, hipStream_t stream);
+uint32_t ycge_launch_mesh_emit_tiles(uint32_t n_nodes);
+int ycge_launch_mesh_emit_layout(const void *nodes, uint32_t n_nodes, uint32_t mesh, uint32_t *tiles, uint32_t *refs, uint32_t *hdr, hipStream_t stream);
+int ycge_launch_mesh_emit_records(const void *nodes, uint32_t n_nodes, uint32_t n_tris, uint32_t mesh, const uint32_t *refs, const uint32_t *leaf, const float *tris9,
+                                  const int32_t *tri_material, int32_t material, int32_t n_materials, uint8_t *arena, uint32_t arena_units, uint32_t *hdr, hipStream_t stream);
+int ycge_launch_mesh_emit_treelets(const uint32_t *refs, uint32_t n_nodes, uint8_t *arena, uint32_t tl_offset, hipStream_t stream);
 int ycge_launch_exposure(const float *hdr, const uint8_t *sky, int w, int h, int step, float *terms, void *state, const float consts[5],
                          void *scratch, int serial, hipStream_t stream);
 int ycge_launch_exposure_sums(const float *terms, int n, void *state, const float consts[5], void *scratch, int serial, hipStream_t stream);
@@ -108,6 +113,11 @@ int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, fl
 }
 
 using namespace ycge;
+
+// ycge_scene_upload assembles the arena on the device when a tree built there has this many triangles: the smallest measured count from which
+// on that upload is no slower than the same upload with the host's emit (4 000: 1.53 against 1.44 ms; 16 000: 2.37 against 2.82; config 4:
+// 11.7 against 198 - profiles/mesh_build_rate.json).  Below it the emit's own allocations and two read-backs outweigh the host's loops.
+#define YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT 16000
 
 namespace ycge_host {
 
@@ -159,6 +169,8 @@ struct Knobs {
     int persist_min_tiles = -1;      // YCGE_PERSIST_MIN_TILES: frames of fewer tiles take k_wf_extend instead of the persistent extend stage (-1: a quarter of the persistent wavefronts)
     bool no_analytic_walk = false;   // YCGE_NO_ANALYTIC_WALK: scenes of analytic objects only are walked by tree_phase's general loop (A/B of analytic_walk; same pixels)
     bool no_walk_tree = false;       // YCGE_NO_WALK_TREE: voxel worlds are walked down the scene tree, leaves and object steps and all (A/B of SceneDev::walk_nodes)
+    bool mesh_emit_host = false;     // YCGE_MESH_EMIT_HOST: ycge_scene_upload writes every mesh's records and the treelets on the host, whoever built the trees
+    int mesh_emit_device_min = YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT;   // YCGE_MESH_EMIT_DEVICE_MIN: ... and also when no tree built on the device has this many triangles (measured crossover of the whole upload, profiles/mesh_build_rate.json)
     bool no_coop = false;            // YCGE_NO_COOP: no treelets are built, sparse wavefronts keep the regular walk (A/B of the cooperative walk)
     bool exposure_serial = false;    // YCGE_EXPOSURE_SERIAL: the one-lane chain instead of the chunked exact evaluation
     void read()
@@ -208,6 +220,8 @@ struct Knobs {
         bvh_waves = geti("YCGE_BVH_WAVES", 16);
         scene_bvh_device_min = geti("YCGE_SCENE_BVH_DEVICE_MIN", YCGE_BVH_DEV_MIN_ITEMS_DEFAULT);
         mesh_bvh_host = getenv("YCGE_MESH_BVH_HOST") != nullptr;
+        mesh_emit_host = getenv("YCGE_MESH_EMIT_HOST") != nullptr;
+        mesh_emit_device_min = geti("YCGE_MESH_EMIT_DEVICE_MIN", YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT);
         mesh_bvh_device_min = geti("YCGE_MESH_BVH_DEVICE_MIN", YCGE_MESH_BVH_DEV_MIN_TRIS_DEFAULT);
         mesh_bvh_wide_min = geti("YCGE_MESH_BVH_WIDE_MIN", YCGE_BVH_DEV_MAX_ITEMS);
         if (mesh_bvh_wide_min < 9) mesh_bvh_wide_min = 9;
@@ -253,6 +267,34 @@ struct MeshBvhReport {
 };
 // YCGE_OK: `out` is build_tree(triangle_items(tris9), TreeFlavour::Mesh); 1: not built, rep.fallback says why; YCGE_ERR_*: rep.error
 int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int wide_min, hipStream_t stream, BuiltTree &out, MeshBvhReport &rep);
+
+// The arena of an upload assembled on the device (ycge_mesh_bvh.cpp drives the kernels of ycge_mesh_emit.hip): per mesh what the kernels read -
+// the buffers of the device-side build taken over from its scratch, or a host-built tree uploaded - and the references of all meshes' nodes.
+// Given back when the upload ends, with the builder's scratch.
+struct MeshEmit {
+    struct Input {
+        DevBuf<float> tris;
+        DevBuf<uint8_t> nodes;           // RefNode records in pre-order
+        DevBuf<uint32_t> leaf;
+        DevBuf<int32_t> tri_material;    // empty: `material` for every triangle
+        uint32_t n_nodes = 0, n_tris = 0, first_ref = 0;      // first_ref: where its nodes' references start in `refs`
+        int32_t material = 0, root_count = 0;                 // root_count: triangles of a leaf root (0: the root is a node)
+        bool ready = false;
+    };
+    std::vector<Input> in;               // one per mesh of the upload (n_nodes == 0: a mesh without triangles)
+    DevBuf<uint32_t> refs, tiles, hdr;
+    std::vector<uint32_t> hdr_host;      // the last read-back of hdr: [0] units, then per mesh {units, a leaf above 15 triangles, a material out of range, 0}
+    uint32_t n_refs = 0;
+    double us[3] = {0.0, 0.0, 0.0};      // layout, records, treelets - separated only when asked (mesh_emit_write's `timed`)
+    void release() { in.clear(); refs.release(); tiles.release(); hdr.release(); hdr_host.clear(); n_refs = 0; }
+};
+// mesh `mi` of the upload: built == true takes S.tris / S.nodes / S.leaf of the build that has just made `t`, else `t`, its leaf order and the triangles are uploaded
+hipError_t mesh_emit_add(MeshEmit &E, size_t mi, bool built, MeshBvhScratch &S, const BuiltTree &t, const float *tris9, int32_t n_tris, const int32_t *tri_material, int32_t material);
+hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t stream);            // every mesh's layout; hdr_host on return (stage: the builder's page-locked staging)
+// the gap behind the rec_units units of records and the treelet region zeroed, every mesh's records, the treelets (tl_offset != 0); hdr_host on return
+hipError_t mesh_emit_write(MeshEmit &E, uint8_t *arena, uint32_t rec_units, size_t total_bytes, uint32_t tl_offset, int32_t n_materials, bool timed, PinnedBuf &stage, hipStream_t stream);
+// where the treelet region of an arena of rec_bytes of records starts (0: none, append_treelets' conditions) and where the arena then ends
+uint32_t mesh_arena_treelet_offset(size_t rec_bytes, bool any_root_is_a_node, size_t &total_bytes);
 
 // The resident voxel grids of a scene (ycge_grid_encode.cpp): the grids of the last ycge_scene_upload keep their indices and its packing;
 // ycge_scene_attach_grids takes the lowest free index, a block of the cell arena (size-keyed free list, 256-byte alignment, else the end of
@@ -536,6 +578,9 @@ struct ycge_ctx {
     double bvh_last_build_us = 0.0;
     std::vector<MeshHost> meshes;
     MeshBvhScratch mesh_bvh;                   // device-side mesh BVH builds of the upload at hand
+    MeshEmit mesh_emit;                        // ... and its arena, when that is assembled on the device
+    int64_t mesh_emit_dev_meshes = 0, mesh_emit_host_meshes = 0, mesh_emit_arena_bytes = 0;       // of the last upload: meshes whose records the device / the host wrote
+    double mesh_emit_last_us = 0.0;            // the last device emit: layout, records, treelets, their two read-backs
     int64_t mesh_bvh_device_builds = 0, mesh_bvh_host_builds = 0, mesh_bvh_host_fallbacks = 0;       // since the context was made
     int64_t mesh_bvh_sorts = 0, mesh_bvh_depth = 0, mesh_bvh_wide_nodes = 0, mesh_bvh_jobs = 0;       // of the last upload: summed / deepest over its meshes
     double mesh_bvh_last_us = 0.0;

@@ -1004,13 +1004,21 @@ struct SceneArrays {
     std::vector<uint32_t> tex_pixels;
     std::vector<int32_t> tex_info;          // per texture {first word, width, height, 0 | live-frame flags}
     uint32_t tl_offset = 0;          // treelet region of the arena (append_treelets), 0 = none
+    const ycge_ctx *arena_on = nullptr;     // the arena was assembled on this context's device (its d_mesh_arena holds it, `arena` is empty): the others copy it from there
 };
 
 int install_scene(ycge_ctx *c, const SceneArrays &A, const ObjectsHost &oh, const ycge_scene *s)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     c->have_scene = false;
-    HIP_TRY(c, c->d_materials.upload(A.mats)); HIP_TRY(c, c->d_mesh_arena.upload(A.arena));
+    HIP_TRY(c, c->d_materials.upload(A.mats));
+    if (!A.arena_on) HIP_TRY(c, c->d_mesh_arena.upload(A.arena));
+    else if (c != A.arena_on) {
+        const DevBuf<uint8_t> &src = A.arena_on->d_mesh_arena;
+        HIP_TRY(c, c->d_mesh_arena.alloc(src.n));
+        if (c->device == A.arena_on->device) HIP_TRY(c, hipMemcpy(c->d_mesh_arena.p, src.p, src.n, hipMemcpyDeviceToDevice));
+        else HIP_TRY(c, hipMemcpyPeer(c->d_mesh_arena.p, c->device, src.p, A.arena_on->device, src.n));
+    }
     HIP_TRY(c, c->d_meshes.upload(A.gmeshes)); HIP_TRY(c, c->d_grids.upload(A.ggrids)); HIP_TRY(c, c->d_cells.upload(A.cells));
     HIP_TRY(c, c->d_lut.upload(A.lut));
     HIP_TRY(c, c->d_tex_pixels.upload(A.tex_pixels)); HIP_TRY(c, c->d_tex_info.upload(A.tex_info));
@@ -1096,13 +1104,11 @@ static uint32_t emit_mesh_records(const BuiltTree &t, const float *tris9, const 
 // Returns the region's byte offset, 0 when there is nothing to build or 32-bit offsets would not reach its end.
 static uint32_t append_treelets(std::vector<uint8_t> &arena, const std::vector<GMesh> &gmeshes)
 {
-    const size_t n_units = arena.size() / 32;
-    const size_t t0 = (arena.size() + 511) & ~(size_t)511;
-    const size_t total = t0 + n_units * YCGE_TL_BYTES_PER_UNIT;
-    if (n_units == 0 || total + 4096 >= (1ull << 32)) return 0;
     bool any = false;
     for (const GMesh &m : gmeshes) any |= YCGE_REF_KIND(m.root_ref) == REF_MESH_NODE && m.root_ref != YCGE_REF_NONE_VALUE;
-    if (!any) return 0;
+    size_t total = 0;
+    const size_t t0 = mesh_arena_treelet_offset(arena.size(), any, total);          // (shared with the arena assembled on the device: the same answer)
+    if (t0 == 0) return 0;
     arena.resize(total, 0);
     auto node_at = [&](uint32_t ref) { GNode g; std::memcpy(&g, arena.data() + (size_t)((ref & 0x1ffffff0u) >> 4) * 32, sizeof g); return g; };
     std::vector<uint32_t> todo;
@@ -1129,6 +1135,47 @@ static uint32_t append_treelets(std::vector<uint8_t> &arena, const std::vector<G
         if (YCGE_REF_KIND(g.rref) == REF_MESH_NODE) todo.push_back(g.rref);
     }
     return (uint32_t)t0;
+}
+
+// The arena of the meshes E holds, assembled on the device: layout, the refusals emit_mesh_records and ycge_scene_upload word (text: theirs,
+// for `fail`), the allocation at its exact size, records, treelets.  root_refs: one per mesh.  YCGE_OK or the error (text in msg).
+static int emit_arena_on_device(MeshEmit &E, PinnedBuf &stage, DevBuf<uint8_t> &d_arena, int n_materials, bool no_coop, bool timed, hipStream_t stream, std::vector<uint32_t> &root_refs,
+                                uint32_t &tl_offset, std::string &msg)
+{
+    char buf[256];
+    auto bad = [&](int code, const char *fmt, int a = 0) { std::snprintf(buf, sizeof buf, fmt, a); msg = buf; return code; };
+    auto hip_bad = [&](const char *what, hipError_t e) {
+        (void)hipGetLastError();
+        std::snprintf(buf, sizeof buf, "%s failed: %s", what, hipGetErrorString(e)); msg = buf;
+        return e == hipErrorOutOfMemory ? YCGE_ERR_OUT_OF_MEMORY : YCGE_ERR_DEVICE;
+    };
+    hipError_t e = mesh_emit_layout(E, stage, stream);
+    if (e != hipSuccess) return hip_bad("the mesh record layout", e);
+    const size_t n = E.in.size();
+    root_refs.assign(n, YCGE_REF_NONE_VALUE);
+    uint64_t units = 0;
+    bool any_node_root = false;
+    for (size_t mi = 0; mi < n; mi++) {
+        const MeshEmit::Input &I = E.in[mi];
+        const uint32_t *h = E.hdr_host.data() + 4 + 4 * mi;          // {units, a leaf above 15 triangles, a material out of range, 0}
+        if (h[1]) return bad(YCGE_ERR_UNSUPPORTED, "mesh %d: a leaf of more than 15 triangles", (int)mi);
+        if (I.n_nodes != 0) {
+            if (units < (1u << 25)) root_refs[mi] = I.root_count > 0 ? YCGE_REF(REF_MESH_LEAF, ((uint32_t)units << 4) | (uint32_t)I.root_count) : YCGE_REF(REF_MESH_NODE, (uint32_t)units << 4);
+            any_node_root |= I.root_count == 0;
+        }
+        units += h[0];
+        if (units >= (1u << 25)) return bad(YCGE_ERR_UNSUPPORTED, "mesh records exceed the 1 GB arena");
+    }
+    if (units != E.hdr_host[0]) return bad(YCGE_ERR_INTERNAL, "the mesh record layout disagrees with its own total");
+    size_t total = 0;
+    tl_offset = no_coop ? 0u : mesh_arena_treelet_offset((size_t)units * 32, any_node_root, total);
+    if (tl_offset == 0) total = (size_t)units * 32;
+    if ((e = d_arena.alloc(total)) != hipSuccess) return hip_bad("the mesh arena's allocation", e);
+    if (total == 0) return YCGE_OK;
+    if ((e = mesh_emit_write(E, d_arena.p, (uint32_t)units, total, tl_offset, n_materials, timed, stage, stream)) != hipSuccess) return hip_bad("the mesh records on the device", e);
+    for (size_t mi = 0; mi < n; mi++)
+        if (E.hdr_host[4 + 4 * mi + 2]) return bad(YCGE_ERR_INVALID_ARG, "mesh %d: triangle material out of range", (int)mi);
+    return YCGE_OK;
 }
 
 int ycge_validate_scene(const ycge_scene *scene, char *msg, size_t msg_bytes)
@@ -1202,7 +1249,30 @@ try {
     gmeshes.assign(s->n_meshes, GMesh{});
     int max_mesh_depth = 0;
     c->mesh_bvh_sorts = c->mesh_bvh_depth = c->mesh_bvh_wide_nodes = c->mesh_bvh_jobs = 0;
-    struct ScratchOfThisUpload { MeshBvhScratch &s; ~ScratchOfThisUpload() { s.release(); } } scratch_of_this_upload{c->mesh_bvh};      // kept from mesh to mesh, given back however the upload ends
+    struct ScratchOfThisUpload { MeshBvhScratch &s; MeshEmit &e; ~ScratchOfThisUpload() { s.release(); e.release(); } } scratch_of_this_upload{c->mesh_bvh, c->mesh_emit};      // kept from mesh to mesh, given back however the upload ends
+    // The arena is assembled on the device (ycge_mesh_emit.hip) when at least one tree of this upload was built there, of a mesh of
+    // YCGE_MESH_EMIT_DEVICE_MIN triangles or more: until the last tree exists the upload only keeps what the kernels will read, and emits
+    // afterwards - on the device, or, when the builder declined every such mesh, here as before.  An upload that offers the builder no such
+    // mesh (and YCGE_MESH_EMIT_HOST) emits mesh by mesh as before.
+    auto worth_the_device_emit = [&](const ycge_mesh &m) { return m.n_triangles >= 1 && m.n_triangles >= c->knobs.mesh_bvh_device_min && m.n_triangles >= c->knobs.mesh_emit_device_min; };
+    bool emit_later = false;
+    if (!c->knobs.mesh_emit_host && !c->knobs.mesh_bvh_host)
+        for (int mi = 0; mi < s->n_meshes; mi++) emit_later |= worth_the_device_emit(s->meshes[mi]);
+    std::vector<uint8_t> built_on_device((size_t)s->n_meshes, 0);
+    int n_built_on_device = 0;
+    c->mesh_emit_dev_meshes = c->mesh_emit_host_meshes = c->mesh_emit_arena_bytes = 0; c->mesh_emit_last_us = 0.0;
+    auto emit_on_host = [&](int mi) -> int {
+        const ycge_mesh &m = s->meshes[mi];
+        const BuiltTree &t = c->meshes[mi].tree;
+        GMesh &gm = gmeshes[mi];
+        bool bad_material = false, bad_leaf = false;
+        gm.root_ref = emit_mesh_records(t, m.triangles, m.tri_material, m.material, s->n_materials, arena, bad_leaf, bad_material);
+        if (bad_leaf) return c->fail(YCGE_ERR_UNSUPPORTED, "mesh %d: a leaf of more than 15 triangles", mi);
+        if (bad_material) return c->fail(YCGE_ERR_INVALID_ARG, "mesh %d: triangle material out of range", mi);
+        if (arena.size() / 32 >= (1u << 25)) return c->fail(YCGE_ERR_UNSUPPORTED, "mesh records exceed the 1 GB arena");
+        c->mesh_emit_host_meshes++;
+        return YCGE_OK;
+    };
     for (int mi = 0; mi < s->n_meshes; mi++) {
         const ycge_mesh &m = s->meshes[mi];
         BuiltTree &t = c->meshes[mi].tree;
@@ -1229,15 +1299,35 @@ try {
         if (t.max_depth > max_mesh_depth) max_mesh_depth = t.max_depth;
         GMesh &gm = gmeshes[mi];
         std::memset(&gm, 0, sizeof gm);
-        bool bad_material = false, bad_leaf = false;
-        gm.root_ref = emit_mesh_records(t, m.triangles, m.tri_material, m.material, s->n_materials, arena, bad_leaf, bad_material);
         if (t.root >= 0) for (int a = 0; a < 3; a++) { gm.root_min[a] = t.nodes[t.root].mn[a]; gm.root_max[a] = t.nodes[t.root].mx[a]; }
-        if (bad_leaf) return c->fail(YCGE_ERR_UNSUPPORTED, "mesh %d: a leaf of more than 15 triangles", mi);
-        if (bad_material) return c->fail(YCGE_ERR_INVALID_ARG, "mesh %d: triangle material out of range", mi);
-        if (arena.size() / 32 >= (1u << 25)) return c->fail(YCGE_ERR_UNSUPPORTED, "mesh records exceed the 1 GB arena");
+        if (!emit_later) { const int erc = emit_on_host(mi); if (erc != YCGE_OK) return erc; }
+        else if (on_device) {          // its triangles, nodes and leaf order are on the device: kept, before the next build takes the scratch
+            built_on_device[(size_t)mi] = 1; n_built_on_device += worth_the_device_emit(m) ? 1 : 0;
+            HIP_TRY(c, mesh_emit_add(c->mesh_emit, (size_t)mi, true, c->mesh_bvh, t, m.triangles, m.n_triangles, m.tri_material, m.material));
+        }
     }
 
-    A.tl_offset = c->knobs.no_coop ? 0u : append_treelets(arena, gmeshes);
+    if (emit_later && n_built_on_device == 0) {
+        for (int mi = 0; mi < s->n_meshes; mi++) { const int erc = emit_on_host(mi); if (erc != YCGE_OK) return erc; }
+        emit_later = false;
+    }
+    if (!emit_later) A.tl_offset = c->knobs.no_coop ? 0u : append_treelets(arena, gmeshes);
+    else {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int mi = 0; mi < s->n_meshes; mi++) {
+            const ycge_mesh &m = s->meshes[mi];
+            if (!built_on_device[(size_t)mi]) HIP_TRY(c, mesh_emit_add(c->mesh_emit, (size_t)mi, false, c->mesh_bvh, c->meshes[mi].tree, m.triangles, m.n_triangles, m.tri_material, m.material));
+        }
+        std::vector<uint32_t> root_refs;
+        std::string msg;
+        const int erc = emit_arena_on_device(c->mesh_emit, c->mesh_bvh.stage, c->d_mesh_arena, s->n_materials, c->knobs.no_coop, false, c->stream, root_refs, A.tl_offset, msg);
+        if (erc != YCGE_OK) return c->fail(erc, "%s", msg.c_str());
+        for (int mi = 0; mi < s->n_meshes; mi++) gmeshes[mi].root_ref = root_refs[(size_t)mi];
+        A.arena_on = c;
+        c->mesh_emit_dev_meshes = s->n_meshes;
+        c->mesh_emit_last_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+    c->mesh_emit_arena_bytes = A.arena_on ? (int64_t)c->d_mesh_arena.n : (int64_t)arena.size();
 
     // ---- voxel grids: VolumeGrid ctor (VolumeGrid.cs:55-93), one byte per voxel = index into a per-grid material table
     std::vector<GGrid> &ggrids = A.ggrids;
@@ -1490,6 +1580,108 @@ try {
     }
     out8[0] = c->mesh_bvh_device_builds; out8[1] = c->mesh_bvh_host_builds; out8[2] = c->mesh_bvh_host_fallbacks; out8[3] = (int64_t)c->mesh_bvh_last_us;
     out8[4] = c->mesh_bvh_sorts; out8[5] = c->mesh_bvh_depth; out8[6] = c->mesh_bvh_wide_nodes; out8[7] = c->mesh_bvh_jobs;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hook, no context: the twin of ycge_host_mesh_arena_treelets on the current device - the tree (the device builder, or the
+// host's tree uploaded when that declines), then the kernels of ycge_mesh_emit.hip; single material 0.  Returns the arena's size, the bytes
+// in `out` when they fit.  res8: {1 = tree built on the device, nodes, units of records, us of the layout, of the records, of the treelets
+// (each with its wait), 0, 0}.  YCGE_ERR_NO_DEVICE_CODE without a device, nothing written.  YCGE_MESH_BVH_WIDE_MIN and YCGE_NO_COOP are read at every call.
+int ycge_debug_device_mesh_arena(const float *tris9, int32_t n, void *out, int64_t capacity_bytes, uint32_t *root_ref_out, uint32_t *tl_offset_out, uint32_t *res8)
+try {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { (void)hipGetLastError(); return YCGE_ERR_NO_DEVICE_CODE; }
+    if (n < 0 || (n > 0 && !tris9) || !root_ref_out || !tl_offset_out) return YCGE_ERR_INVALID_ARG;
+    Knobs knobs;
+    knobs.read();
+    MeshBvhScratch scratch;
+    MeshEmit E;
+    MeshBvhReport rep;
+    BuiltTree t;
+    const int rc = mesh_bvh_build_device(scratch, tris9, n, knobs.mesh_bvh_wide_min, nullptr, t, rep);
+    if (rc < 0) return rc;
+    if (rc == 1) {
+        BoundsSoA items;
+        triangle_items(tris9, n, items);
+        build_tree(items, TreeFlavour::Mesh, t);
+    }
+    if (mesh_emit_add(E, 0, rc == YCGE_OK && n > 0, scratch, t, tris9, n, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); return YCGE_ERR_DEVICE; }
+    DevBuf<uint8_t> d_arena;
+    std::vector<uint32_t> root_refs;
+    std::string msg;
+    *tl_offset_out = 0;
+    const int erc = emit_arena_on_device(E, scratch.stage, d_arena, 1, knobs.no_coop, true, nullptr, root_refs, *tl_offset_out, msg);
+    if (erc != YCGE_OK) return erc == YCGE_ERR_INVALID_ARG ? YCGE_ERR_UNSUPPORTED : erc;          // (as the host twin answers a bad leaf or material)
+    *root_ref_out = root_refs[0];
+    if (d_arena.n > (size_t)0x7fffffff) return YCGE_ERR_UNSUPPORTED;
+    if (out && (int64_t)d_arena.n <= capacity_bytes && d_arena.n) {
+        PinnedBuf stage;
+        const size_t piece = (size_t)4 << 20;
+        if (stage.reserve(d_arena.n < piece ? d_arena.n : piece) != hipSuccess) { (void)hipGetLastError(); return YCGE_ERR_OUT_OF_MEMORY; }
+        for (size_t at = 0; at < d_arena.n; at += stage.bytes) {          // (through page-locked staging: the device writes no caller memory)
+            const size_t len = d_arena.n - at < stage.bytes ? d_arena.n - at : stage.bytes;
+            if (hipMemcpy(stage.p, d_arena.p + at, len, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return YCGE_ERR_DEVICE; }
+            std::memcpy((uint8_t *)out + at, stage.p, len);
+        }
+    }
+    if (res8) {
+        for (int k = 0; k < 8; k++) res8[k] = 0u;
+        res8[0] = rc == YCGE_OK && n > 0 ? 1u : 0u; res8[1] = (uint32_t)t.nodes.size(); res8[2] = E.hdr_host.empty() ? 0u : E.hdr_host[0];
+        res8[3] = (uint32_t)E.us[0]; res8[4] = (uint32_t)E.us[1]; res8[5] = (uint32_t)E.us[2];
+    }
+    return (int)d_arena.n;
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// test hook: the arena the context's device holds (records, then the treelet region at *tl_offset_out, 0 = none), whichever side wrote it.
+// Returns its size; the bytes go to dst when they fit.
+int ycge_debug_read_mesh_arena(ycge_ctx *c, void *dst, int64_t capacity_bytes, uint32_t *tl_offset_out)
+try {
+    if (!c || !tl_offset_out) return YCGE_ERR_INVALID_ARG;
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    HIP_TRY(c, hipSetDevice(c->device));
+    *tl_offset_out = c->sd.tl_offset;
+    const size_t bytes = c->d_mesh_arena.p ? c->d_mesh_arena.n : 0;
+    if (bytes > (size_t)0x7fffffff) return c->fail(YCGE_ERR_UNSUPPORTED, "the arena is larger than this hook returns");
+    if (dst && (int64_t)bytes <= capacity_bytes && bytes) {
+        HIP_TRY(c, hipDeviceSynchronize());
+        const int rc = copy_out(c, dst, c->d_mesh_arena.p, bytes);
+        if (rc != YCGE_OK) return rc;
+    }
+    return (int)bytes;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: the GMesh records (32 bytes each: root box, root reference) the context's device holds; returns how many
+int ycge_debug_read_meshes(ycge_ctx *c, void *dst, int32_t capacity_meshes)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = c->d_meshes.p ? c->d_meshes.n : 0;
+    if (dst && n && n <= (size_t)(capacity_meshes > 0 ? capacity_meshes : 0)) {
+        HIP_TRY(c, hipDeviceSynchronize());
+        const int rc = copy_out(c, dst, c->d_meshes.p, n * sizeof(GMesh));
+        if (rc != YCGE_OK) return rc;
+    }
+    return (int)n;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hook: who wrote the arena of the last upload - {meshes whose records the device wrote, meshes whose records the host
+// wrote, microseconds of the device's layout + records + treelets (0: the host wrote them), the arena's bytes}.  Without a context:
+// YCGE_ERR_INVALID_ARG, and out4[0..1] = YCGE_MESH_EMIT_HOST and YCGE_MESH_EMIT_DEVICE_MIN as the environment gives them now (host only).
+int ycge_debug_mesh_emit_stats(ycge_ctx *c, int64_t *out4)
+try {
+    if (!out4) return YCGE_ERR_INVALID_ARG;
+    if (!c) {
+        Knobs knobs;
+        knobs.read();
+        out4[0] = knobs.mesh_emit_host ? 1 : 0; out4[1] = knobs.mesh_emit_device_min; out4[2] = out4[3] = 0;
+        return YCGE_ERR_INVALID_ARG;
+    }
+    out4[0] = c->mesh_emit_dev_meshes; out4[1] = c->mesh_emit_host_meshes; out4[2] = (int64_t)c->mesh_emit_last_us; out4[3] = c->mesh_emit_arena_bytes;
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }

@@ -1,5 +1,5 @@
 // ycge_mesh_bvh.cpp - the host side of the device-side mesh BVH build (kernels: ycge_mesh_bvh_build.hip): scratch, the level loop over
-// the wide nodes, the read-back of the tree into a BuiltTree.  ycge_scene_upload (ycge_host.cpp)
+// the wide nodes, the read-back of the tree into a BuiltTree - and of the arena assembled on the device behind it (kernels: ycge_mesh_emit.hip).  ycge_scene_upload (ycge_host.cpp)
 // picks the builder per mesh, and the two hooks tests and profiles hold the builder by live there too; whatever this builder declines - Array.Sort at a wide node, a non-finite coordinate, a tree
 // deeper than the reference accepts - the host builder of ycge_accel.cpp builds, and it is the one that words the errors.
 #include "ycge_ctx.h"
@@ -89,6 +89,99 @@ int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int 
     out.sort_fallbacks = (int32_t)hdr[MH_SORTS];
     rep.us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     return YCGE_OK;
+}
+
+// ---- the arena on the device (ycge_mesh_emit.hip) ----------------------------------------------------------------------------------
+
+namespace {
+enum { EH_UNITS = 0, EH_MESH0 = 4, EH_MESH_WORDS = 4 };      // = ycge_mesh_emit.hip
+}
+
+uint32_t mesh_arena_treelet_offset(size_t rec_bytes, bool any_root_is_a_node, size_t &total_bytes)
+{
+    const size_t n_units = rec_bytes / 32;
+    const size_t t0 = (rec_bytes + 511) & ~(size_t)511;
+    const size_t total = t0 + n_units * YCGE_TL_BYTES_PER_UNIT;
+    total_bytes = rec_bytes;
+    if (n_units == 0 || total + 4096 >= (1ull << 32) || !any_root_is_a_node) return 0;
+    total_bytes = total;
+    return (uint32_t)t0;
+}
+
+hipError_t mesh_emit_add(MeshEmit &E, size_t mi, bool built, MeshBvhScratch &S, const BuiltTree &t, const float *tris9, int32_t n_tris, const int32_t *tri_material, int32_t material)
+{
+    if (E.in.size() <= mi) E.in.resize(mi + 1);
+    MeshEmit::Input &I = E.in[mi];
+    I.ready = true;
+    I.material = material;
+    I.n_nodes = (uint32_t)t.nodes.size();
+    I.n_tris = n_tris > 0 ? (uint32_t)n_tris : 0u;
+    if (t.root < 0 || I.n_nodes == 0 || I.n_tris == 0) { I.n_nodes = 0; return hipSuccess; }
+    I.root_count = t.nodes[0].count > 0 ? t.nodes[0].count : 0;
+    const size_t N = I.n_tris;
+    hipError_t e = hipSuccess;
+    if (built) { I.tris = std::move(S.tris); I.nodes = std::move(S.nodes); I.leaf = std::move(S.leaf); }       // (the next build reserves its own)
+    else {
+        if ((e = I.tris.reserve(9 * N)) != hipSuccess || (e = I.nodes.reserve((size_t)I.n_nodes * sizeof(RefNode))) != hipSuccess || (e = I.leaf.reserve(N)) != hipSuccess) return e;
+        if ((e = hipMemcpy(I.tris.p, tris9, 9 * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return e;
+        if ((e = hipMemcpy(I.nodes.p, t.nodes.data(), (size_t)I.n_nodes * sizeof(RefNode), hipMemcpyHostToDevice)) != hipSuccess) return e;
+        if ((e = hipMemcpy(I.leaf.p, t.leaf_index.data(), N * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
+    }
+    if (tri_material) {
+        if ((e = I.tri_material.reserve(N)) != hipSuccess) return e;
+        e = hipMemcpy(I.tri_material.p, tri_material, N * 4, hipMemcpyHostToDevice);
+    }
+    return e;
+}
+
+hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t stream)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_hdr = EH_MESH0 + EH_MESH_WORDS * E.in.size();
+    uint64_t n_refs = 0;
+    uint32_t max_nodes = 1;
+    for (MeshEmit::Input &I : E.in) {
+        I.first_ref = (uint32_t)n_refs;
+        n_refs += I.n_nodes;
+        if (I.n_nodes > max_nodes) max_nodes = I.n_nodes;
+    }
+    if (n_refs > 0x0fffffffu) return hipErrorInvalidValue;          // (2^28 nodes: their records are far past the arena's 2^25 units)
+    E.n_refs = (uint32_t)n_refs;
+    hipError_t e = hipSuccess;
+    if ((e = E.refs.reserve(n_refs ? n_refs : 1)) != hipSuccess || (e = E.tiles.reserve(ycge_launch_mesh_emit_tiles(max_nodes))) != hipSuccess || (e = E.hdr.reserve(n_hdr)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(E.hdr.p, 0, n_hdr * 4, stream)) != hipSuccess) return e;
+    for (size_t mi = 0; mi < E.in.size(); mi++) {
+        const MeshEmit::Input &I = E.in[mi];
+        if (I.n_nodes == 0) continue;
+        if ((e = (hipError_t)ycge_launch_mesh_emit_layout(I.nodes.p, I.n_nodes, (uint32_t)mi, E.tiles.p, E.refs.p + I.first_ref, E.hdr.p, stream)) != hipSuccess) return e;
+    }
+    E.hdr_host.assign(n_hdr, 0u);
+    e = staged_read(stage, E.hdr_host.data(), E.hdr.p, n_hdr * 4, stream);
+    E.us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    return e;
+}
+
+hipError_t mesh_emit_write(MeshEmit &E, uint8_t *arena, uint32_t rec_units, size_t total_bytes, uint32_t tl_offset, int32_t n_materials, bool timed, PinnedBuf &stage, hipStream_t stream)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](double &us) { const auto t1 = std::chrono::steady_clock::now(); us = std::chrono::duration<double, std::micro>(t1 - t0).count(); t0 = t1; };
+    const size_t rec_bytes = (size_t)rec_units * 32, n_hdr = EH_MESH0 + EH_MESH_WORDS * E.in.size();
+    hipError_t e = hipSuccess;
+    if (total_bytes > rec_bytes && (e = hipMemsetAsync(arena + rec_bytes, 0, total_bytes - rec_bytes, stream)) != hipSuccess) return e;
+    for (size_t mi = 0; mi < E.in.size(); mi++) {
+        const MeshEmit::Input &I = E.in[mi];
+        if (I.n_nodes == 0) continue;
+        e = (hipError_t)ycge_launch_mesh_emit_records(I.nodes.p, I.n_nodes, I.n_tris, (uint32_t)mi, E.refs.p + I.first_ref, I.leaf.p, I.tris.p, I.tri_material.p, I.material, n_materials,
+                                                      arena, rec_units, E.hdr.p, stream);
+        if (e != hipSuccess) return e;
+    }
+    if (timed) { if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e; lap(E.us[1]); }
+    if (tl_offset != 0 && E.n_refs != 0 && (e = (hipError_t)ycge_launch_mesh_emit_treelets(E.refs.p, E.n_refs, arena, tl_offset, stream)) != hipSuccess) return e;
+    E.hdr_host.assign(n_hdr, 0u);
+    e = staged_read(stage, E.hdr_host.data(), E.hdr.p, n_hdr * 4, stream);
+    lap(E.us[timed ? 2 : 1]);
+    if (!timed) E.us[2] = 0.0;
+    return e;
 }
 
 } // namespace ycge_host

@@ -260,6 +260,37 @@ class RaytraceRenderer:
         self._check(fn(self.ctx, out))
         return {k: int(v) for k, v in zip(abi.MESH_BVH_STATS, out)}
 
+    def mesh_emit_stats(self) -> dict:
+        """Who wrote the mesh arena of the last ycge_scene_upload: meshes whose records the device wrote (csrc/ycge_mesh_emit.hip: an upload with
+        at least one tree built on the device), meshes whose records the host wrote, microseconds of the device's layout + records + treelets,
+        the arena's bytes."""
+        out = (C.c_int64 * 4)()
+        fn = self.L.ycge_debug_mesh_emit_stats
+        fn.restype, fn.argtypes = abi.MESH_EMIT_HOOK_PROTOTYPES["ycge_debug_mesh_emit_stats"]
+        self._check(fn(self.ctx, out))
+        return {k: int(v) for k, v in zip(abi.MESH_EMIT_STATS, out)}
+
+    def read_mesh_arena(self):
+        """(bytes, tl_offset): the mesh arena the device holds - records, then the treelet region (0: none) - whichever side wrote it."""
+        fn = self.L.ycge_debug_read_mesh_arena
+        fn.restype, fn.argtypes = abi.MESH_EMIT_HOOK_PROTOTYPES["ycge_debug_read_mesh_arena"]
+        tl = C.c_uint32(0)
+        n = fn(self.ctx, None, 0, C.byref(tl))
+        self._check(min(n, 0))
+        out = np.zeros(max(n, 1), np.uint8)
+        self._check(min(fn(self.ctx, out.ctypes.data, n, C.byref(tl)), 0))
+        return out[:n], int(tl.value)
+
+    def read_meshes(self) -> np.ndarray:
+        """The GMesh records the device holds, [n, 8] uint32: root box (min xyz, max xyz), root reference, padding."""
+        fn = self.L.ycge_debug_read_meshes
+        fn.restype, fn.argtypes = abi.MESH_EMIT_HOOK_PROTOTYPES["ycge_debug_read_meshes"]
+        n = fn(self.ctx, None, 0)
+        self._check(min(n, 0))
+        out = np.zeros((max(n, 1), 8), np.uint32)
+        self._check(min(fn(self.ctx, out.ctypes.data, n), 0))
+        return out[:n]
+
     def Resize(self, fb_width: int, fb_height: int, superSample: int):
         self._check(self.L.ycge_resize(self.ctx, fb_width, fb_height, superSample))          # (joins the frames in flight: nothing writes the old arrays any more)
         self._set_dims(fb_width, fb_height, max(1, superSample))
