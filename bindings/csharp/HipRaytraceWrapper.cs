@@ -44,6 +44,21 @@ public sealed class HipRaytraceOptions
     public bool DeviceChexelColors;
     public bool DeviceAnsiStream;
     public DeviceAnsiTerminalRenderer AnsiPresenter;          // DeviceAnsiStream: the presenter the frames' streams go to
+    public HipGeneratedWorld GeneratedWorld;                  // chunks that come from the generator are made on the device (ycge_scene_generate_grids)
+}
+
+/// <summary>The chunks of a voxel world that no world file holds (WorldManager.AttachChunkFromGenerator, WorldManager.cs:754-793), for a host
+/// that lets the device generate them: the host keeps `Desired` at the chunk keys of its view that come from the generator (LoadChunksAround's
+/// desired set less the chunks it attaches from a file or its cache as VolumeGrids) and does NOT call WorldGenerator.GenerateChunkCells for
+/// them; HipRaytraceWrapper.SyncVolumeGrids generates and attaches the keys that are new, shows them as Scene.Objects' last entries and gives
+/// back the slots of the keys that left.  A chunk of nothing but Air takes no slot (index -1, WorldManager.cs:759).</summary>
+public sealed class HipGeneratedWorld
+{
+    public YWorld World;                                      // WorldConfig: ChunkSize, ChunksY, WorldSeed, WorldMin, VoxelSize
+    public Func<int, int, Material> MaterialLookup;           // VolumeGrid's materialLookup: its materials must be materials of the uploaded scene
+    public bool Wireframe = true;                             // VolumeGrid ctor defaults
+    public float WireWidthFraction = 0.06f, WireMaxDistance = 16.0f;
+    public readonly HashSet<(int cx, int cy, int cz)> Desired = new HashSet<(int cx, int cy, int cz)>();
 }
 
 /// <summary>ANSITerminalRenderer with the cell walk moved to the GPU (HipRaytraceOptions.DeviceAnsiStream): Render() writes the stream of the
@@ -120,6 +135,8 @@ public partial class RaytraceEntity
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
         private ulong objectsSignature;
         private bool forceUpload;
+        private readonly HipGeneratedWorld generated;                   // HipRaytraceOptions.GeneratedWorld (null: every chunk is a VolumeGrid of the host)
+        private readonly Dictionary<(int, int, int), int> generatedIndex = new Dictionary<(int, int, int), int>();   // key -> device grid index, -1: all Air
         private YLight[] lightsSent = Array.Empty<YLight>();
         private YVec3 ambientSent, topSent, bottomSent; private float ambientIntensitySent;
 
@@ -139,6 +156,7 @@ public partial class RaytraceEntity
             ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
             frameLate = options != null && options.FrameLate && cfg.NDevices <= 1 && ansi == null;      // (frames in flight are the single-device form; the stream is synchronous)
             deviceColors = options != null && options.DeviceChexelColors;
+            generated = options?.GeneratedWorld;
             Ycge.Check(IntPtr.Zero, Ycge.ycge_create(ref cfg, out ctx));
             AllocSdr();
             Upload();                               // the reference ctor ends with scene.RebuildBVH() (RaytraceRenderer.cs:107)
@@ -255,6 +273,45 @@ public partial class RaytraceEntity
             return true;
         }
 
+        /// <summary>Chunks that came from the generator (HipGeneratedWorld): the desired keys the device does not hold yet are generated ON
+        /// THE DEVICE and attached in one call (ycge_scene_generate_grids: keys in, device indices back, -1 for a chunk of nothing but Air,
+        /// which gets no object); no cells are made or sent by the host.  False when the lookup needs a material the last upload did not hold.</summary>
+        private bool SyncGeneratedChunks()
+        {
+            if (generated == null) return true;
+            var fresh = new List<(int, int, int)>();
+            foreach (var key in generated.Desired) if (!generatedIndex.ContainsKey(key)) fresh.Add(key);
+            if (fresh.Count == 0) return true;
+            using (var scratch = new FlatScene())
+            {
+                if (!SceneFlattener.GeneratorProto(generated, uploaded, scratch, out YGrid proto)) return false;
+                var keys = new int[3 * fresh.Count];
+                for (int i = 0; i < fresh.Count; i++) { keys[3 * i] = fresh[i].Item1; keys[3 * i + 1] = fresh[i].Item2; keys[3 * i + 2] = fresh[i].Item3; }
+                var index = new int[fresh.Count];
+                YWorld world = generated.World;
+                fixed (int* k = keys) fixed (int* ix = index) Ycge.Check(ctx, Ycge.ycge_scene_generate_grids(ctx, ref world, k, fresh.Count, &proto, ix, null));
+                for (int i = 0; i < index.Length; i++) generatedIndex[fresh[i]] = index[i];
+            }
+            return true;
+        }
+        private bool GeneratedChanged()
+        {
+            if (generated == null) return false;
+            if (generated.Desired.Count != generatedIndex.Count) return true;
+            foreach (var key in generated.Desired) if (!generatedIndex.ContainsKey(key)) return true;
+            return false;
+        }
+        /// <summary>Scene.Objects' records followed by one VolumeGrid record per resident generated chunk that is still desired (they have no
+        /// host object: the reference would have scene.Add'ed their VolumeGrids last, WorldManager.cs:775).</summary>
+        private YPrim[] WithGenerated(YPrim[] prims)
+        {
+            if (generated == null || prims == null) return prims;
+            var all = new List<YPrim>(prims);
+            foreach (var kv in generatedIndex)
+                if (kv.Value >= 0 && generated.Desired.Contains(kv.Key)) all.Add(new YPrim { Type = (int)YPrimType.VolumeGrid, Ref = kv.Value });
+            return all.ToArray();
+        }
+
         /// <summary>... and the grids that left Scene.Objects give their slots back (after ycge_scene_update_objects: nothing refers to them).</summary>
         private void DetachVolumeGrids()
         {
@@ -262,19 +319,36 @@ public partial class RaytraceEntity
             foreach (Hittable o in scene.Objects) if (o is VolumeGrid g) live.Add(g);
             var gone = new List<int>();
             for (int i = 0; i < uploaded.GridOwners.Count; i++) if (uploaded.GridOwners[i] != null && !live.Contains(uploaded.GridOwners[i])) gone.Add(i);
+            if (generated != null)          // generated chunks that left the view: their slots go back too (a -1 held none)
+            {
+                var left = new List<(int, int, int)>();
+                foreach (var kv in generatedIndex) if (!generated.Desired.Contains(kv.Key)) { left.Add(kv.Key); if (kv.Value >= 0) gone.Add(kv.Value); }
+                foreach (var key in left) generatedIndex.Remove(key);
+            }
             if (gone.Count == 0) return;
             int[] ix = gone.ToArray();
             fixed (int* p = ix) Ycge.Check(ctx, Ycge.ycge_scene_detach_grids(ctx, p, ix.Length));
-            foreach (int i in gone) uploaded.GridOwners[i] = null;
+            foreach (int i in gone) if (i < uploaded.GridOwners.Count) uploaded.GridOwners[i] = null;
         }
 
         private void SyncScene()
         {
-            if (forceUpload || ObjectsSignature() != objectsSignature)
+            if (forceUpload || ObjectsSignature() != objectsSignature || GeneratedChanged())
             {
-                YPrim[] prims = forceUpload || !SyncVolumeGrids(scene) ? null : SceneFlattener.ObjectsAgainst(scene, uploaded);
+                YPrim[] prims = forceUpload || !SyncVolumeGrids(scene) || !SyncGeneratedChunks() ? null : WithGenerated(SceneFlattener.ObjectsAgainst(scene, uploaded));
                 forceUpload = false;
-                if (prims == null) Upload();        // a new mesh or material: the whole scene again
+                if (prims == null)
+                {
+                    Upload();                       // a new mesh or material: the whole scene again
+                    generatedIndex.Clear();         // (an upload forgets every attached grid; the generated chunks are made again)
+                    if (generated != null && generated.Desired.Count > 0)
+                    {
+                        if (!SyncGeneratedChunks()) throw new InvalidOperationException("HipGeneratedWorld.MaterialLookup returns a material the scene does not hold");
+                        prims = WithGenerated(uploaded.Prims);
+                        fixed (YPrim* p = prims) Ycge.Check(ctx, Ycge.ycge_scene_update_objects(ctx, p, prims.Length));
+                        uploaded.Prims = prims;
+                    }
+                }
                 else
                 {
                     fixed (YPrim* p = prims) Ycge.Check(ctx, Ycge.ycge_scene_update_objects(ctx, p, prims.Length));     // only the scene-level BVH is rebuilt, as in the reference

@@ -409,6 +409,27 @@ namespace ConsoleGame.RayTracing.Native
             return mats.Records.Count == uploaded.Materials.Length && mats.Textures.Count == uploaded.Textures.Count;
         }
 
+        /// <summary>The `proto` of ycge_scene_generate_grids for a HipGeneratedWorld: a lookup entry for every (matId, metaId) pair
+        /// WorldGenerator.GenerateChunkCells can write (Stone with metas 0..2, StrataMap.cs:8-19; Dirt, Grass, Water, Sand, Wood, Leaves, Snow
+        /// with meta 0, WorldGenSettings.cs:8-22), materials numbered against the last upload.  False when the lookup returns one it did not hold.</summary>
+        public static bool GeneratorProto(HipGeneratedWorld w, FlatScene uploaded, FlatScene scratch, out YGrid proto)
+        {
+            var mats = new MaterialTable();
+            foreach (YMaterial m in uploaded.Materials) mats.Records.Add(m);
+            mats.Textures.AddRange(uploaded.Textures);
+            var table = new List<YVoxelLookup>();
+            for (int meta = 0; meta <= 2; meta++) table.Add(new YVoxelLookup { MatId = 1, MetaId = meta, Material = mats.Add(w.MaterialLookup(1, meta)) });
+            for (int mat = 2; mat <= 8; mat++) table.Add(new YVoxelLookup { MatId = mat, MetaId = 0, Material = mats.Add(w.MaterialLookup(mat, 0)) });
+            YVoxelLookup[] lut = table.ToArray();
+            proto = new YGrid
+            {
+                Nx = w.World.ChunkSize, Ny = w.World.ChunkSize, Nz = w.World.ChunkSize, VoxelSize = w.World.VoxelSize,
+                Cells = IntPtr.Zero, Lookup = scratch.Pin(lut), NLookup = lut.Length, DefaultMaterial = -1,
+                Wireframe = w.Wireframe ? 1 : 0, WireWidthFraction = w.WireWidthFraction, WireMaxDistance = w.WireMaxDistance,
+            };
+            return mats.Records.Count == uploaded.Materials.Length && mats.Textures.Count == uploaded.Textures.Count;
+        }
+
         /// <summary>Only Scene.Objects again, against the materials / meshes / grids of the last upload - for ycge_scene_update_objects after an
         /// entity moved (Scene.cs:122-127).  Returns null when the objects need a record the last upload did not hold (a new material, mesh or
         /// grid): the caller uploads the scene again.</summary>

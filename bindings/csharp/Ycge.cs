@@ -189,6 +189,10 @@ namespace ConsoleGame.RayTracing.Native
         // chunk streaming (found by symbol lookup, ABI stays 10): grids beside those of the last upload, and their slots given back
         [DllImport(Lib)] public static extern int ycge_scene_attach_grids(IntPtr ctx, YGrid* grids, int n, int* outGridIndex);
         [DllImport(Lib)] public static extern int ycge_scene_detach_grids(IntPtr ctx, int* gridIndex, int n);
+        // chunk generation (found by symbol lookup, ABI stays 10): WorldGenerator.GenerateChunkCells on the host / on the device + attach
+        // (YWorld: bindings/csharp/YcgeWorld.cs)
+        [DllImport(Lib)] public static extern int ycge_worldgen_chunk_cells(ref YWorld world, int cx, int cy, int cz, int* cellsOut, int* anySolidOut);
+        [DllImport(Lib)] public static extern int ycge_scene_generate_grids(IntPtr ctx, ref YWorld world, int* keys, int n, YGrid* proto, int* outGridIndex, int* cellsOut);
         [DllImport(Lib)] public static extern int ycge_scene_update_texture(IntPtr ctx, int textureIndex, IntPtr frame, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_resize(IntPtr ctx, int fbWidth, int fbHeight, int superSample);
         [DllImport(Lib)] public static extern int ycge_set_camera(IntPtr ctx, float* pos, float yaw, float pitch, float fovDeg);

@@ -378,6 +378,41 @@ int ycge_scene_attach_grids(ycge_ctx *ctx, const ycge_grid *grids, int32_t n, in
  * for an index that is not resident, or for one named twice. */
 int ycge_scene_detach_grids(ycge_ctx *ctx, const int32_t *grid_index, int32_t n);
 
+/* --- chunk generation: the chunks ycge_scene_attach_grids receives come from WorldGenerator.GenerateChunkCells on the host's worker threads
+ * (WorldManager.cs:754-793, 914; 2 312 calls before the first frame when there is no world file, VolumeScenes.cs:617-624).  The function is
+ * pure - (cx, cy, cz, WorldConfig) in, the (int,int)[S,S,S] of ycge_grid.cells out - so a chunk can be made where it will be traced.
+ * Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no existing struct changes; a host detects these exports by symbol lookup.
+ * The generator is the per-chunk one (WorldGenerator.cs:95-203: TerrainNoise, RiverNetwork.ComputeForChunk, BiomeMap, Layering, StrataMap,
+ * FloraPlacer.PlaceTreesInChunk) with IslandSettings and WorldGenSettings at the reference's values; the whole-world pregen path
+ * (GenerateAndSaveWorld) is a different function and is not offered.  MathF.Pow is csrc/ycge_math.h's m_pow (within 1 ulp of a faithful
+ * libm), as everywhere in this library. */
+typedef struct ycge_world {      /* WorldConfig (WorldConfig.cs:19-34), the fields a chunk depends on */
+    int32_t chunk_size;          /* ChunkSize, 4..64                                          */
+    int32_t chunks_y;            /* ChunksY >= 1: WorldHeight = chunks_y * chunk_size; WaterLevel and SnowLevel follow as :32-33 */
+    int32_t world_seed;          /* WorldSeed                                                 */
+    ycge_vec3 world_min;         /* WorldMin: chunk (cx, cy, cz) has min_corner world_min + c * chunk_size * voxel_size (WorldManager.cs:761-768) */
+    ycge_vec3 voxel_size;        /* VoxelSize                                                 */
+} ycge_world;
+/* GenerateChunkCells on the host, one thread: pure host code, no context and no device.  cells_out: 2 * chunk_size^3 int32 in
+ * ycge_grid.cells order; *any_solid_out = 1 when a cell is not Air, else 0.  YCGE_ERR_INVALID_ARG: a NULL pointer, chunk_size outside
+ * 4..64, chunks_y < 1 or a world higher than 2^20, a key outside +-2^24 blocks (|c| * chunk_size: block coordinates must be exact in
+ * binary32) - the same checks ycge_scene_generate_grids makes. */
+int ycge_worldgen_chunk_cells(const ycge_world *world, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t *any_solid_out);
+/* Generate n chunks ON THE DEVICE (csrc/ycge_worldgen.hip) and make them resident: what ycge_scene_attach_grids gives when it is handed,
+ * for the same keys in the same order, the cells ycge_worldgen_chunk_cells returns - the same pixels, indices, limits and statuses, all or
+ * nothing, joining the frames in flight, forwarded to the devices of a one-process multi-device context, as documented there.
+ *   keys = n x {cx, cy, cz}; a key may appear more than once (each takes a grid).
+ *   proto: a ycge_grid whose `cells` is ignored; its lookup table, default_material and wireframe settings serve every chunk; nx, ny, nz
+ *     and min_corner are overwritten per chunk (chunk_size; WorldManager.cs:761-769), voxel_size is the world's.
+ *   A chunk with no cell other than Air takes no slot and reports index -1 (WorldManager.cs:759).
+ *   The keys are worked through in internal sub-batches bounded by the staging area; a failure in any of them leaves the scene as it was
+ *     and out_grid_index untouched.
+ *   cells_out, when not NULL, receives the raw cells of every chunk (n * 2 * chunk_size^3 int32) - the only bulk read-back; a host leaves
+ *     it NULL.  It may have been written when the call is refused later.
+ *   YCGE_WORLDGEN_HOST in the environment at ycge_create: the cells are made by the host generator and go up as an attach's. */
+int ycge_scene_generate_grids(ycge_ctx *ctx, const ycge_world *world, const int32_t *keys /* 3 n */, int32_t n, const ycge_grid *proto,
+                              int32_t *out_grid_index /* n */, int32_t *cells_out /* NULL, or n * 2 * chunk_size^3 */);
+
 /* The argument checks of ycge_scene_upload on their own: pure host code, no device and no context needed
  * (every index in range, counts non-negative, pointers present, material kinds known).  Returns YCGE_OK or the
  * status ycge_scene_upload would return; `msg` (may be NULL) receives the reason. */

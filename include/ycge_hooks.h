@@ -18,7 +18,7 @@ extern "C" {
 #endif
 
 /* ---- layout probe: sizeof the C structs as the library was compiled (0 ycge_vec3, 1 material, 2 prim, 3 mesh, 4 voxel_lookup, 5 grid,
- * 6 light, 7 scene, 8 config, 9 frame_stats, 10 flight_info) - the ctypes and C# mirrors are held to it */
+ * 6 light, 7 scene, 8 config, 9 frame_stats, 10 flight_info, 11 world) - the ctypes and C# mirrors are held to it */
 size_t ycge_abi_sizeof(int32_t which);
 
 /* ---- host-side builders and schedules, no GPU needed (tests/test_host_cpu.py: against the oracle, bit for bit) */
@@ -81,6 +81,12 @@ int ycge_debug_read_walk_tree(ycge_ctx *c, void *gnodes_out, void *walk_out, int
 int ycge_debug_read_grid(ycge_ctx *c, int32_t grid_index, void *record_out /* sizeof GGrid = 112 bytes */, int32_t *materials_out);   /* a resident grid as the device holds it: its record and, per voxel in ycge_grid.cells order, the material of its cell code (-1 = empty) */
 ycge_ctx *ycge_debug_peer_context(ycge_ctx *c, int32_t k);           /* the context of device k + 1 of a one-process multi-device context (NULL: none): the scene calls refuse it */
 int ycge_debug_grid_pool_stats(ycge_ctx *c, int64_t *out12);         /* resident grids, free indices, arena bytes in use, arena capacity, arena growths, slots reused, device encodes, host-fallback encodes; the last attach in us: staging copy, host-to-device copy, encode kernel, read-back */
+/* chunk generation, host only (csrc/ycge_worldgen.cpp over csrc/ycge_worldgen.h; tests/test_worldgen_hooks_cpu.py against tests/worldgen_restatement.py) */
+int ycge_host_worldgen_noise(int32_t n, const int32_t *ix, const int32_t *iz, const float *x, const float *z, int32_t seed, uint32_t *hash_out, float *noise_out);   /* FastHash(ix, 0, iz, seed) and GradientNoise2D(x, z, seed) */
+int ycge_host_worldgen_height(const ycge_world *world, int32_t n, const int32_t *gx, const int32_t *gz, int32_t *height_out);                                      /* TerrainNoise.HeightY */
+int ycge_host_worldgen_river(const int32_t *tile /* (size + 2)^2 */, int32_t size, int32_t sea, int32_t *dir_out, float *accum_out, int32_t *carved_out, int32_t *river_water_out);   /* RiverNetwork.ComputeForChunk on a caller's height tile: D8 code (dx + 1) * 3 + (dz + 1), accum, carved ground, river surface */
+int ycge_host_worldgen_carve(float accum, int32_t ground, int32_t sea, int32_t *carved_out, int32_t *river_water_out);                                               /* the carve and river-surface formulas at a given accumulation */
+int ycge_debug_worldgen_stats(ycge_ctx *c, int64_t *out4);           /* ycge_scene_generate_grids: chunks made on the device, chunks made on the host, the last call's column kernel and fill + tree kernels in us (root device) */
 int ycge_debug_read_post_progress(ycge_ctx *c, uint32_t *dst, size_t n_words);               /* k_atrous_stream's per-band records (profiles/post_bands.py) */
 int ycge_debug_read_wave_prof(ycge_ctx *c, unsigned long long *dst, size_t n_u64);            /* per-wavefront begin / end / steps of a profiling build (profiles/mega_prof.py) */
 int ycge_debug_read_coop_stats(ycge_ctx *c, uint64_t out[16]);                               /* -DYCGE_DBG_COOPSTAT builds */

@@ -101,6 +101,11 @@ class Grid(C.Structure):
     ]
 
 
+class World(C.Structure):
+    """ycge_world: WorldConfig as a chunk depends on it (ycge_worldgen_chunk_cells / ycge_scene_generate_grids)."""
+    _fields_ = [("chunk_size", C.c_int32), ("chunks_y", C.c_int32), ("world_seed", C.c_int32), ("world_min", Vec3), ("voxel_size", Vec3)]
+
+
 class Light(C.Structure):
     _fields_ = [("position", Vec3), ("color", Vec3), ("intensity", C.c_float)]
 
@@ -190,6 +195,9 @@ _PROTOTYPES = {
     "ycge_scene_update_objects": (C.c_int, [C.c_void_p, C.POINTER(Prim), C.c_int32]),
     "ycge_scene_attach_grids": (C.c_int, [C.c_void_p, C.POINTER(Grid), C.c_int32, C.POINTER(C.c_int32)]),
     "ycge_scene_detach_grids": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
+    # (world: a ycge_world, passed with C.byref(abi.World))
+    "ycge_worldgen_chunk_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ycge_scene_generate_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(Grid), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ycge_scene_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ycge_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]),
@@ -243,6 +251,10 @@ HOOK_PROTOTYPES = {
     "ycge_debug_grid_pool_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ycge_debug_peer_context": (C.c_void_p, [C.c_void_p, C.c_int32]),
     "ycge_debug_live_resources": (C.c_int, [C.POINTER(C.c_int64)]),
+}
+# test / profiling hook of chunk generation (csrc/ycge_grid_encode.cpp), bound where it is used (RaytraceRenderer.worldgen_stats)
+WORLDGEN_HOOK_PROTOTYPES = {
+    "ycge_debug_worldgen_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
 }
 # test hooks of the post stage on caller-given inputs (csrc/ycge_post_host.cpp), bound where they are used (RaytraceRenderer.post_probe /
 # exposure_probe); state_out: POST_STATE_WORDS uint32

@@ -20,10 +20,13 @@
 // FRAMES IN FLIGHT: an attach joins them (quiesce), as every other scene change does - it may move the arena, the LUT and the grid table,
 // which the frames read.  A detach changes host state only and joins nothing.
 #include <algorithm>
+#include <climits>
+#include <map>
 #include <unordered_set>
 
 #include "ycge_ctx.h"
 #include "ycge_grid_encode.h"
+#include "ycge_worldgen_host.h"
 
 namespace ycge_host {
 
@@ -90,19 +93,41 @@ struct Planned {
 
 double us_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
 
-// one group of device-encoded grids: stage, copy, launch, read back (every device of the context; the root's results are returned)
-int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &plan, const std::vector<int> &group, std::vector<GridEncResult> &res, double us[4])
+// ycge_scene_generate_grids: where the cells of grid k come from when no caller brought them
+struct GenSource {
+    wg::World W;
+    bool host = false;                               // YCGE_WORLDGEN_HOST: ycge_worldgen.cpp fills the staging, the rest is an attach
+    std::vector<std::array<int32_t, 3>> keys;        // per grid
+    std::vector<int32_t> col;                        // per grid: its chunk column among the column records
+    std::vector<wg::ColRec> host_cols;               // host: n_cols x S * S (device: every context's d_wg_cols)
+    std::vector<int32_t *> cells_out;                // per grid, or empty
+    size_t chunk_bytes() const { return (size_t)W.size * W.size * W.size * 8; }
+};
+constexpr size_t kGenGroupMax = 32768;               // chunks in one fill launch (gridDim.y)
+
+// one group of device-encoded grids: stage, copy, launch, read back (every device of the context; the root's results are returned).
+// With a device GenSource nothing but descriptors and lookup tables is staged: k_wg_fill / k_wg_trees write the cells where k_grid_encode reads them.
+int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &plan, const std::vector<int> &group, std::vector<GridEncResult> &res, double us[4],
+                 const GenSource *gen)
 {
     const DeviceGuard guard(root->device);
     const size_t m = group.size();
+    const bool gen_dev = gen && !gen->host;
     size_t at = align_up(m * sizeof(GridEncDesc), 256);
     const size_t off_res = at;
     at = align_up(at + m * sizeof(GridEncResult), 256);
+    const size_t off_chunks = at;
+    if (gen_dev) at = align_up(at + m * sizeof(WgChunk), 256);
+    const size_t off_any = at;
+    if (gen_dev) at = align_up(at + m * sizeof(uint32_t), 256);
     for (int k : group) { plan[k].lookup_off = at; at = align_up(at + (size_t)grids[k].n_lookup * sizeof(ycge_voxel_lookup), 16); }
     at = align_up(at, 256);
+    const size_t off_cells = at;
     for (int k : group) { plan[k].cells_off = at; at = align_up(at + (size_t)grids[k].nx * grids[k].ny * grids[k].nz * 8, 256); }
-    const size_t off_back = at, total = at + m * sizeof(GridEncResult);
-    HIP_TRY(root, root->enc_stage.reserve(total, hipHostMallocPortable));      // (every device of the context copies from it)
+    const size_t dev_total = at;                                                    // what the device holds
+    const size_t up_bytes = gen_dev ? off_cells : at;                               // what goes up
+    const size_t off_back = up_bytes, back_bytes = m * sizeof(GridEncResult) + (gen_dev ? m * sizeof(uint32_t) : 0);   // (staging only)
+    HIP_TRY(root, root->enc_stage.reserve(off_back + back_bytes, hipHostMallocPortable));      // (every device of the context copies from it)
     uint8_t *st = root->enc_stage.data();
     auto t0 = std::chrono::steady_clock::now();
     GridEncResult *init = (GridEncResult *)(st + off_res);
@@ -116,7 +141,15 @@ int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &p
         r.lo[0] = g.nx; r.lo[1] = g.ny; r.lo[2] = g.nz; r.hi[0] = r.hi[1] = r.hi[2] = -1; r.bad_cell = 0xffffffffu;
         init[j] = r;
         if (g.n_lookup > 0) std::memcpy(st + pl.lookup_off, g.lookup, (size_t)g.n_lookup * sizeof(ycge_voxel_lookup));
-        std::memcpy(st + pl.cells_off, g.cells, (size_t)g.nx * g.ny * g.nz * 8);
+        if (!gen) std::memcpy(st + pl.cells_off, g.cells, (size_t)g.nx * g.ny * g.nz * 8);
+        else if (gen->host) {
+            const size_t k = (size_t)group[j];
+            int32_t any = 0;
+            worldgen_fill_host(gen->W, gen->host_cols.data() + (size_t)gen->col[k] * gen->W.size * gen->W.size, gen->keys[k][0], gen->keys[k][1], gen->keys[k][2],
+                               (int32_t *)(st + pl.cells_off), &any);
+            if (!any) return root->fail(YCGE_ERR_INTERNAL, "ycge_scene_generate_grids: chunk (%d, %d, %d) came out empty", gen->keys[k][0], gen->keys[k][1], gen->keys[k][2]);
+            if (!gen->cells_out.empty()) std::memcpy(gen->cells_out[k], st + pl.cells_off, gen->chunk_bytes());
+        } else ((uint32_t *)(st + off_any))[j] = 0u;
         first_wg[j] = n_wg;
         const uint64_t wgs = (uint64_t)pl.rec.nbx * pl.rec.nby * (((uint64_t)pl.rec.nbz + YCGE_ENC_RUN - 1) / YCGE_ENC_RUN);
         if (n_wg + wgs >= 0x7fffffffull) return root->fail(YCGE_ERR_UNSUPPORTED, "ycge_scene_attach_grids: more bricks in one batch than one launch takes");
@@ -127,7 +160,7 @@ int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &p
     ctxs.insert(ctxs.end(), root->peers.begin(), root->peers.end());
     for (ycge_ctx *c : ctxs) {
         HIP_TRY(root, hipSetDevice(c->device));
-        if (c->d_enc_in.cap < total) HIP_TRY(root, c->d_enc_in.alloc(total));
+        if (c->d_enc_in.cap < dev_total) HIP_TRY(root, c->d_enc_in.alloc(dev_total));
         GridEncDesc *descs = (GridEncDesc *)st;
         for (size_t j = 0; j < m; j++) {
             const ycge_grid &g = grids[group[j]];
@@ -144,22 +177,62 @@ int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &p
             d.first_wg = first_wg[j];
             d.maskable = pl.rec.has_brick_mask ? 1u : 0u;
             descs[j] = d;
+            if (gen_dev) {
+                const size_t k = (size_t)group[j];
+                WgChunk w;
+                w.cx = gen->keys[k][0]; w.cy = gen->keys[k][1]; w.cz = gen->keys[k][2]; w.col = gen->col[k];
+                w.cells = (int32_t *)(c->d_enc_in.p + pl.cells_off);
+                ((WgChunk *)(st + off_chunks))[j] = w;
+            }
         }
         t0 = std::chrono::steady_clock::now();
-        HIP_TRY(root, hipMemcpyAsync(c->d_enc_in.p, st, off_back, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(root, hipMemcpyAsync(c->d_enc_in.p, st, up_bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(root, hipStreamSynchronize(c->stream));
         if (c == root) us[1] += us_since(t0);
         t0 = std::chrono::steady_clock::now();
+        if (gen_dev) {
+            const int ge = ycge_launch_worldgen_fill((const WgChunk *)(c->d_enc_in.p + off_chunks), (int)m, &gen->W, (const wg::ColRec *)c->d_wg_cols.p,
+                                                     (uint32_t *)(c->d_enc_in.p + off_any), c->stream);
+            if (ge != 0) return root->fail(YCGE_ERR_DEVICE, "k_wg_fill launch failed: %s", hipGetErrorString((hipError_t)ge));
+            if (c == root) { HIP_TRY(root, hipStreamSynchronize(c->stream)); root->worldgen_last_us[1] += us_since(t0); t0 = std::chrono::steady_clock::now(); }
+        }
         const int e = ycge_launch_grid_encode(c->d_enc_in.p, (int)m, c->d_enc_in.p + off_res, n_wg, c->stream);
         if (e != 0) return root->fail(YCGE_ERR_DEVICE, "k_grid_encode launch failed: %s", hipGetErrorString((hipError_t)e));
         HIP_TRY(root, hipStreamSynchronize(c->stream));
         if (c == root) us[2] += us_since(t0);
         t0 = std::chrono::steady_clock::now();
         HIP_TRY(root, hipMemcpyAsync(st + off_back, c->d_enc_in.p + off_res, m * sizeof(GridEncResult), hipMemcpyDeviceToHost, c->stream));
+        if (gen_dev) HIP_TRY(root, hipMemcpyAsync(st + off_back + m * sizeof(GridEncResult), c->d_enc_in.p + off_any, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(root, hipStreamSynchronize(c->stream));
         if (c == root) {
             us[3] += us_since(t0);
             for (size_t j = 0; j < m; j++) std::memcpy(&res[(size_t)group[j]], st + off_back + j * sizeof(GridEncResult), sizeof(GridEncResult));
+        }
+        if (gen_dev && c == root) {
+            const uint32_t *any = (const uint32_t *)(st + off_back + m * sizeof(GridEncResult));
+            for (size_t j = 0; j < m; j++) {
+                const size_t k = (size_t)group[j];
+                if (!any[j]) return root->fail(YCGE_ERR_INTERNAL, "ycge_scene_generate_grids: chunk (%d, %d, %d) came out empty", gen->keys[k][0], gen->keys[k][1], gen->keys[k][2]);
+                if (!gen->cells_out.empty()) {
+                    const int rc = copy_out(root, gen->cells_out[k], c->d_enc_in.p + plan[k].cells_off, gen->chunk_bytes());
+                    if (rc != YCGE_OK) return rc;
+                }
+            }
+        }
+    }
+    if (gen) {          // a pair with no material: named here, while the group's cells are still where they were made
+        for (size_t j = 0; j < m; j++) {
+            const size_t k = (size_t)group[j];
+            const GridEncResult &r = res[k];
+            if (r.bad_cell == 0xffffffffu) continue;
+            int32_t pair[2] = {0, 0};
+            if (gen->host) std::memcpy(pair, st + plan[k].cells_off + (size_t)r.bad_cell * 8, 8);
+            else {
+                HIP_TRY(root, hipSetDevice(root->device));
+                const int rc = copy_out(root, pair, root->d_enc_in.p + plan[k].cells_off + (size_t)r.bad_cell * 8, 8);
+                if (rc != YCGE_OK) return rc;
+            }
+            return root->fail(YCGE_ERR_INVALID_ARG, "grid %d: no material for (matId %d, metaId %d)", (int)k, pair[0], pair[1]);
         }
     }
     (void)hipSetDevice(root->device);
@@ -184,18 +257,10 @@ bool too_many_pairs(const ycge_grid &g)
 
 extern "C" {
 
-int ycge_scene_attach_grids(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *out_grid_index)
-try {
-    if (!c) return YCGE_ERR_INVALID_ARG;
-    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
-    if (n < 0 || (n > 0 && (!grids || !out_grid_index))) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_attach_grids: bad array (n = %d)", n);
-    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
-    if (n == 0) return YCGE_OK;
-    for (int k = 0; k < n; k++) {
-        std::string m;
-        const int vrc = validate_grid(grids[k], k, c->n_materials, m);
-        if (vrc != YCGE_OK) return c->fail(vrc, "%s", m.c_str());
-    }
+// the body of ycge_scene_attach_grids (gen == NULL: the caller's cells) and of ycge_scene_generate_grids (the cells of grids[k] are made
+// from gen->keys[k]; grids[k].cells is not read).  Arguments are checked by the callers; n >= 1.
+static int attach_common(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *out_grid_index, const GenSource *gen)
+{
     int rc = quiesce(c);
     for (ycge_ctx *p : c->peers) if (rc == YCGE_OK) rc = quiesce(p);
     if (rc != YCGE_OK) return rc;
@@ -272,11 +337,12 @@ try {
         for (int k = 0; k <= n; k++) {
             const size_t bytes = k < n ? (size_t)grids[k].nx * grids[k].ny * grids[k].nz * 8 : 0;
             if (!group.empty() && (k == n || group_bytes + bytes > budget)) {
-                rc = encode_group(c, grids, plan, group, res, us);
+                rc = encode_group(c, grids, plan, group, res, us, gen);
                 if (rc != YCGE_OK) return rc;
                 group.clear(); group_bytes = 0;
             }
             if (k < n && plan[(size_t)k].device) { group.push_back(k); group_bytes += bytes; }
+            if (gen && group.size() >= kGenGroupMax) group_bytes = budget;          // (a full fill launch: the next grid opens a new group)
         }
     }
     // ---- verdicts, records, the host encoder for the rest
@@ -287,15 +353,27 @@ try {
         uint64_t mask = 0;
         if (pl.device) {
             const GridEncResult &r = res[(size_t)k];
-            if (r.bad_cell != 0xffffffffu)
+            if (r.bad_cell != 0xffffffffu)          // (generated grids: encode_group has named it already)
                 return c->fail(YCGE_ERR_INVALID_ARG, "grid %d: no material for (matId %d, metaId %d)", k, g.cells[2 * (size_t)r.bad_cell], g.cells[2 * (size_t)r.bad_cell + 1]);
-            if (r.any_miss && too_many_pairs(g)) return c->fail(YCGE_ERR_UNSUPPORTED, "grid %d: more than 255 distinct (matId, metaId) pairs", k);
+            // (the generator writes a dozen distinct pairs at most: never asked for its grids)
+            if (!gen && r.any_miss && too_many_pairs(g)) return c->fail(YCGE_ERR_UNSUPPORTED, "grid %d: more than 255 distinct (matId, metaId) pairs", k);
             for (int a = 0; a < 3; a++) { lo[a] = r.lo[a]; hi[a] = r.hi[a]; }
             mask = pl.rec.has_brick_mask ? ((uint64_t)r.mask_hi << 32) | r.mask_lo : 0;
             P.device_encodes++;
         } else {
             pl.host_bytes.assign(pl.cap, 0);
-            rc = encode_grid_host(c, g, k, c->n_materials, pl.rec, pl.host_bytes.data(), pl.host_lut, lo, hi, mask);
+            ycge_grid gh = g;
+            std::vector<int32_t> made;
+            if (gen) {          // a lookup table too large for k_grid_encode: this chunk's cells are made here, whoever makes the others
+                std::vector<wg::ColRec> cols((size_t)gen->W.size * gen->W.size);
+                int32_t any = 0;
+                made.resize(gen->chunk_bytes() / 4);
+                worldgen_columns_host(gen->W, gen->keys[(size_t)k][0], gen->keys[(size_t)k][2], cols.data());
+                worldgen_fill_host(gen->W, cols.data(), gen->keys[(size_t)k][0], gen->keys[(size_t)k][1], gen->keys[(size_t)k][2], made.data(), &any);
+                if (!gen->cells_out.empty()) std::memcpy(gen->cells_out[(size_t)k], made.data(), gen->chunk_bytes());
+                gh.cells = made.data();
+            }
+            rc = encode_grid_host(c, gh, k, c->n_materials, pl.rec, pl.host_bytes.data(), pl.host_lut, lo, hi, mask);
             if (rc != YCGE_OK) return rc;
             pl.host_lut.resize(YCGE_ENC_LUT_ENTRIES, -1);
             P.host_encodes++;
@@ -358,6 +436,178 @@ try {
     c->grid_solid.swap(solid);
     for (int k = 0; k < n; k++) out_grid_index[k] = plan[(size_t)k].index;
     return query_scene_changed(c);
+}
+
+int ycge_scene_attach_grids(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *out_grid_index)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    if (n < 0 || (n > 0 && (!grids || !out_grid_index))) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_attach_grids: bad array (n = %d)", n);
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    if (n == 0) return YCGE_OK;
+    for (int k = 0; k < n; k++) {
+        std::string m;
+        const int vrc = validate_grid(grids[k], k, c->n_materials, m);
+        if (vrc != YCGE_OK) return c->fail(vrc, "%s", m.c_str());
+    }
+    return attach_common(c, grids, n, out_grid_index, nullptr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ycge_scene_generate_grids: the chunk columns first (every 2-D field of WorldGenerator.GenerateChunkCells, once per distinct (cx, cz)) -
+// their tops say which chunks hold anything, and only those take part in the attach; then attach_common with a GenSource, whose groups are
+// the sub-batches.  Everything before attach_common changes scratch buffers only, and attach_common is all or nothing.
+int ycge_scene_generate_grids(ycge_ctx *c, const ycge_world *world, const int32_t *keys, int32_t n, const ycge_grid *proto, int32_t *out_grid_index, int32_t *cells_out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    const char *why = nullptr;
+    if (worldgen_check(world, &why) != YCGE_OK) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_generate_grids: %s", why);
+    if (n < 0 || (n > 0 && (!keys || !out_grid_index)) || !proto) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_generate_grids: bad array (n = %d)", n);
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    if (n == 0) return YCGE_OK;
+    const int S = world->chunk_size;
+    static const int32_t no_cells[2] = {0, 0};          // (validate_grid wants a pointer; a generated grid's cells are never read through it)
+    ycge_grid g0 = *proto;
+    g0.nx = g0.ny = g0.nz = S; g0.voxel_size = world->voxel_size; g0.cells = no_cells;
+    {
+        std::string m;
+        const int vrc = validate_grid(g0, 0, c->n_materials, m);
+        if (vrc != YCGE_OK) return c->fail(vrc, "%s", m.c_str());
+    }
+    for (int k = 0; k < n; k++)
+        if (worldgen_key_check(world, keys[3 * k], keys[3 * k + 1], keys[3 * k + 2]) != YCGE_OK)          // (block coordinates stay exact in binary32, as the generator assumes)
+            return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_generate_grids: key %d is outside +-2^24 blocks", k);
+    int rc = quiesce(c);
+    for (ycge_ctx *p : c->peers) if (rc == YCGE_OK) rc = quiesce(p);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const DeviceGuard guard(c->device);
+
+    GenSource all;          // every key; `gen` below keeps the ones that hold something
+    all.W = wg::make_world(S, world->chunks_y, world->world_seed);
+    all.host = c->knobs.worldgen_host;
+    const size_t S2 = (size_t)S * S, chunk_i32 = 2 * S2 * S;
+    std::vector<std::array<int32_t, 2>> col_keys;
+    {
+        std::map<std::pair<int32_t, int32_t>, int32_t> seen;
+        for (int k = 0; k < n; k++) {
+            const auto ins = seen.insert({{keys[3 * k], keys[3 * k + 2]}, (int32_t)col_keys.size()});
+            if (ins.second) col_keys.push_back({{keys[3 * k], keys[3 * k + 2]}});
+            all.keys.push_back({{keys[3 * k], keys[3 * k + 1], keys[3 * k + 2]}});
+            all.col.push_back(ins.first->second);
+        }
+    }
+    const size_t n_cols = col_keys.size();
+    std::vector<int32_t> col_top(n_cols);
+    c->worldgen_last_us[0] = c->worldgen_last_us[1] = 0;
+    std::vector<ycge_ctx *> ctxs{c};
+    ctxs.insert(ctxs.end(), c->peers.begin(), c->peers.end());
+    const size_t cols_bytes = align_up(n_cols * S2 * sizeof(wg::ColRec), 256), keys_bytes = align_up(n_cols * 8, 256);
+    if (all.host) {
+        all.host_cols.resize(n_cols * S2);
+        for (size_t j = 0; j < n_cols; j++) {
+            worldgen_columns_host(all.W, col_keys[j][0], col_keys[j][1], all.host_cols.data() + j * S2);
+            int32_t top = INT32_MIN;
+            for (size_t i = 0; i < S2; i++) { const wg::ColRec &R = all.host_cols[j * S2 + i]; top = std::max(top, std::max(R.ground, R.water)); }
+            col_top[j] = top;
+        }
+    } else {
+        for (ycge_ctx *x : ctxs) {
+            HIP_TRY(c, hipSetDevice(x->device));
+            const size_t need = cols_bytes + keys_bytes + n_cols * 4;
+            if (x->d_wg_cols.cap < need) HIP_TRY(c, x->d_wg_cols.alloc(need));
+            uint8_t *d_keys = x->d_wg_cols.p + cols_bytes, *d_top = d_keys + keys_bytes;
+            const auto t0 = std::chrono::steady_clock::now();
+            HIP_TRY(c, hipMemcpyAsync(d_keys, col_keys.data(), n_cols * 8, hipMemcpyHostToDevice, x->stream));
+            const int e = ycge_launch_worldgen_columns((const int32_t *)d_keys, (int)n_cols, &all.W, (wg::ColRec *)x->d_wg_cols.p, (int32_t *)d_top, x->stream);
+            if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wg_columns launch failed: %s", hipGetErrorString((hipError_t)e));
+            HIP_TRY(c, hipStreamSynchronize(x->stream));
+            if (x == c) {
+                c->worldgen_last_us[0] = us_since(t0);
+                rc = copy_out(c, col_top.data(), d_top, n_cols * 4);
+                if (rc != YCGE_OK) return rc;
+            }
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+    }
+    // a chunk holds something exactly when a column reaches into or above it: Water up to localWater, ground below (trees stand on ground of their own chunk)
+    GenSource gen;
+    gen.W = all.W; gen.host = all.host; gen.host_cols.swap(all.host_cols);
+    std::vector<int> solid_k, air_k;
+    for (int k = 0; k < n; k++) (col_top[(size_t)all.col[(size_t)k]] >= all.keys[(size_t)k][1] * S ? solid_k : air_k).push_back(k);
+    std::vector<ycge_grid> grids;
+    for (int k : solid_k) {
+        ycge_grid g = g0;
+        const auto &key = all.keys[(size_t)k];
+        g.min_corner.x = world->world_min.x + (float)(key[0] * S) * world->voxel_size.x;          // WorldManager.cs:761-768
+        g.min_corner.y = world->world_min.y + (float)(key[1] * S) * world->voxel_size.y;
+        g.min_corner.z = world->world_min.z + (float)(key[2] * S) * world->voxel_size.z;
+        grids.push_back(g);
+        gen.keys.push_back(key); gen.col.push_back(all.col[(size_t)k]);
+        if (cells_out) gen.cells_out.push_back(cells_out + (size_t)k * chunk_i32);
+    }
+    // the empty chunks' cells, when asked for: made like the others (and found empty), in launches of their own
+    if (cells_out && !air_k.empty()) {
+        if (gen.host) {
+            for (int k : air_k) {
+                int32_t any = 0;
+                const auto &key = all.keys[(size_t)k];
+                worldgen_fill_host(gen.W, gen.host_cols.data() + (size_t)all.col[(size_t)k] * S2, key[0], key[1], key[2], cells_out + (size_t)k * chunk_i32, &any);
+                if (any) return c->fail(YCGE_ERR_INTERNAL, "ycge_scene_generate_grids: chunk (%d, %d, %d) holds cells above its column's top", key[0], key[1], key[2]);
+            }
+        } else {
+            const size_t slot = align_up(chunk_i32 * 4, 256), per = std::max<size_t>(1, std::min<size_t>(kGenGroupMax, ((size_t)64 << 20) / slot));
+            for (size_t first = 0; first < air_k.size(); first += per) {
+                const size_t m = std::min(per, air_k.size() - first);
+                const size_t off_any = align_up(m * sizeof(WgChunk), 256), off_cells = align_up(off_any + m * 4, 256), total = off_cells + m * slot;
+                if (c->d_enc_in.cap < total) HIP_TRY(c, c->d_enc_in.alloc(total));
+                std::vector<uint8_t> head(off_cells, 0);
+                for (size_t j = 0; j < m; j++) {
+                    const int k = air_k[first + j];
+                    WgChunk w;
+                    w.cx = all.keys[(size_t)k][0]; w.cy = all.keys[(size_t)k][1]; w.cz = all.keys[(size_t)k][2]; w.col = all.col[(size_t)k];
+                    w.cells = (int32_t *)(c->d_enc_in.p + off_cells + j * slot);
+                    std::memcpy(head.data() + j * sizeof(WgChunk), &w, sizeof w);
+                }
+                HIP_TRY(c, hipMemcpy(c->d_enc_in.p, head.data(), off_cells, hipMemcpyHostToDevice));
+                const int e = ycge_launch_worldgen_fill((const WgChunk *)c->d_enc_in.p, (int)m, &gen.W, (const wg::ColRec *)c->d_wg_cols.p, (uint32_t *)(c->d_enc_in.p + off_any), c->stream);
+                if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wg_fill launch failed: %s", hipGetErrorString((hipError_t)e));
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+                std::vector<uint32_t> any(m);
+                rc = copy_out(c, any.data(), c->d_enc_in.p + off_any, m * 4);
+                for (size_t j = 0; j < m && rc == YCGE_OK; j++) {
+                    const int k = air_k[first + j];
+                    if (any[j]) return c->fail(YCGE_ERR_INTERNAL, "ycge_scene_generate_grids: chunk (%d, %d, %d) holds cells above its column's top", all.keys[(size_t)k][0], all.keys[(size_t)k][1], all.keys[(size_t)k][2]);
+                    rc = copy_out(c, cells_out + (size_t)k * chunk_i32, c->d_enc_in.p + off_cells + j * slot, chunk_i32 * 4);
+                }
+                if (rc != YCGE_OK) return rc;
+            }
+        }
+    }
+    std::vector<int32_t> idx(solid_k.size(), -1);
+    if (!solid_k.empty()) {
+        rc = attach_common(c, grids.data(), (int32_t)grids.size(), idx.data(), &gen);
+        if (rc != YCGE_OK) return rc;
+    }
+    {          // who made the cells: the kernels, or the host generator (the knob; a lookup table too large for k_grid_encode).  An empty chunk's cells are made only when cells_out asks.
+        const bool solid_on_host = gen.host || proto->n_lookup > YCGE_ENC_MAX_LOOKUP;
+        const int64_t n_air = cells_out ? (int64_t)air_k.size() : 0, n_solid = (int64_t)solid_k.size();
+        c->worldgen_host_chunks += (solid_on_host ? n_solid : 0) + (gen.host ? n_air : 0);
+        c->worldgen_device_chunks += (solid_on_host ? 0 : n_solid) + (gen.host ? 0 : n_air);
+    }
+    for (int k : air_k) out_grid_index[k] = -1;
+    for (size_t j = 0; j < solid_k.size(); j++) out_grid_index[solid_k[j]] = idx[j];
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hook: {chunks made on the device, chunks made on the host, the last call's column kernel and fill + tree kernels in microseconds (root device)}
+int ycge_debug_worldgen_stats(ycge_ctx *c, int64_t *out4)
+try {
+    if (!c || !out4) return YCGE_ERR_INVALID_ARG;
+    out4[0] = c->worldgen_device_chunks; out4[1] = c->worldgen_host_chunks; out4[2] = (int64_t)c->worldgen_last_us[0]; out4[3] = (int64_t)c->worldgen_last_us[1];
+    return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

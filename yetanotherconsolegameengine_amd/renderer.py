@@ -160,6 +160,28 @@ class RaytraceRenderer:
             self._streamed[id(g)] = g          # (keeps the object, hence its id, alive while it is resident)
         return idx
 
+    def GenerateGrids(self, world: abi.World, keys, proto: abi.Grid, want_cells: bool = False):
+        """ycge_scene_generate_grids: WorldGenerator.GenerateChunkCells for the chunk keys [(cx, cy, cz), ...] on the device, attached like
+        AttachGrids' grids.  `proto` supplies the lookup table, default material and wireframe settings (its materials index the uploaded
+        scene's).  Returns the device indices (-1: an all-air chunk, no slot) and, with want_cells, the raw cells [n, S, S, S, 2] int32."""
+        keys = np.ascontiguousarray(np.asarray(keys, np.int32).reshape(-1, 3))
+        n, S = keys.shape[0], int(world.chunk_size)
+        out = (C.c_int32 * max(1, n))(*([-7] * max(1, n)))
+        cells = np.zeros((n, S, S, S, 2), np.int32) if want_cells else None
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_generate_grids(self.ctx, C.byref(world), keys.ctypes.data_as(C.POINTER(C.c_int32)), n, C.byref(proto), out,
+                                              cells.ctypes.data_as(C.POINTER(C.c_int32)) if want_cells else None)
+        self.stream_call_s["generate"] = time.perf_counter() - t0
+        self._check(rc)
+        idx = [int(out[k]) for k in range(n)]
+        return (idx, cells) if want_cells else idx
+
+    def worldgen_stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self.L.ycge_debug_worldgen_stats.restype, self.L.ycge_debug_worldgen_stats.argtypes = abi.WORLDGEN_HOOK_PROTOTYPES["ycge_debug_worldgen_stats"]
+        self._check(self.L.ycge_debug_worldgen_stats(self.ctx, out))
+        return dict(zip(("device_chunks", "host_chunks", "last_columns_us", "last_fill_us"), (int(v) for v in out)))
+
     def DetachGrids(self, indices) -> None:
         """Gives the grids' slots back; refused while Scene.Objects (as of the last UpdateObjects) refer to one of them."""
         indices = [int(i) for i in indices]

@@ -159,3 +159,24 @@ def stream_view(scene: Scene, world: np.ndarray, center, world_min, voxel_size, 
         scene.Objects.append(vg)
         added.append(key)
     return added, removed
+
+
+def stream_generated(renderer, world, proto, center, view_distance_chunks: int, loaded: dict):
+    """One LoadChunksAround tick with no world file behind it (WorldManager.cs:289-370 with AttachChunkFromGenerator, :754-793): the
+    desired chunks that are not loaded are GENERATED ON THE DEVICE and attached (RaytraceRenderer.GenerateGrids, ycge_scene_generate_grids)
+    in the reference's order; the keys that left the view are returned for the caller to drop from its object list and detach.  `world`
+    is an abi.World, `proto` the abi.Grid whose lookup serves every chunk; `loaded` (key -> device grid index, -1 for an all-air chunk)
+    persists between calls.  Returns (added keys, removed keys, indices of the removed resident grids)."""
+    wmin = (world.world_min.x, world.world_min.y, world.world_min.z)
+    vox = (world.voxel_size.x, world.voxel_size.y, world.voxel_size.z)
+    desired = build_desired_set(center, wmin, vox, world.chunk_size, view_distance_chunks, world.chunks_y)
+    want = set(desired)
+    removed = [key for key in loaded if key not in want]
+    gone = [loaded.pop(key) for key in removed]
+    cx0, cz0 = center_column(center, wmin, vox, world.chunk_size)
+    todo = [key for key in desired if key not in loaded]
+    todo.sort(key=lambda k: ((k[0] - cx0) * (k[0] - cx0) + (k[2] - cz0) * (k[2] - cz0), k[1]))
+    if todo:
+        for key, i in zip(todo, renderer.GenerateGrids(world, todo, proto)):
+            loaded[key] = i
+    return todo, removed, [i for i in gone if i >= 0]
