@@ -193,6 +193,9 @@ namespace ConsoleGame.RayTracing.Native
         // (YWorld: bindings/csharp/YcgeWorld.cs)
         [DllImport(Lib)] public static extern int ycge_worldgen_chunk_cells(ref YWorld world, int cx, int cy, int cz, int* cellsOut, int* anySolidOut);
         [DllImport(Lib)] public static extern int ycge_scene_generate_grids(IntPtr ctx, ref YWorld world, int* keys, int n, YGrid* proto, int* outGridIndex, int* cellsOut);
+        // the pregenerated world (WorldManager.GenerateAndSaveWorld) on the host / on the device + attach; HipPregenWorld in YcgeWorld.cs
+        [DllImport(Lib)] public static extern int ycge_worldgen_world_cells(ref YWorld world, int chunksX, int chunksZ, int originBx, int originBz, int* cellsOut);
+        [DllImport(Lib)] public static extern int ycge_scene_generate_world(IntPtr ctx, ref YWorld world, int chunksX, int chunksZ, int originBx, int originBz, YGrid* proto, int* outGridIndex, int* cellsOut);
         [DllImport(Lib)] public static extern int ycge_scene_update_texture(IntPtr ctx, int textureIndex, IntPtr frame, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_resize(IntPtr ctx, int fbWidth, int fbHeight, int superSample);
         [DllImport(Lib)] public static extern int ycge_set_camera(IntPtr ctx, float* pos, float yaw, float pitch, float fovDeg);

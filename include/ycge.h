@@ -384,8 +384,8 @@ int ycge_scene_detach_grids(ycge_ctx *ctx, const int32_t *grid_index, int32_t n)
  * Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no existing struct changes; a host detects these exports by symbol lookup.
  * The generator is the per-chunk one (WorldGenerator.cs:95-203: TerrainNoise, RiverNetwork.ComputeForChunk, BiomeMap, Layering, StrataMap,
  * FloraPlacer.PlaceTreesInChunk) with IslandSettings and WorldGenSettings at the reference's values; the whole-world pregen path
- * (GenerateAndSaveWorld) is a different function and is not offered.  MathF.Pow is csrc/ycge_math.h's m_pow (within 1 ulp of a faithful
- * libm), as everywhere in this library. */
+ * (GenerateAndSaveWorld) is a different function: ycge_worldgen_world_cells / ycge_scene_generate_world below.  MathF.Pow is
+ * csrc/ycge_math.h's m_pow (within 1 ulp of a faithful libm), as everywhere in this library. */
 typedef struct ycge_world {      /* WorldConfig (WorldConfig.cs:19-34), the fields a chunk depends on */
     int32_t chunk_size;          /* ChunkSize, 4..64                                          */
     int32_t chunks_y;            /* ChunksY >= 1: WorldHeight = chunks_y * chunk_size; WaterLevel and SnowLevel follow as :32-33 */
@@ -412,6 +412,34 @@ int ycge_worldgen_chunk_cells(const ycge_world *world, int32_t cx, int32_t cy, i
  *   YCGE_WORLDGEN_HOST in the environment at ycge_create: the cells are made by the host generator and go up as an attach's. */
 int ycge_scene_generate_grids(ycge_ctx *ctx, const ycge_world *world, const int32_t *keys /* 3 n */, int32_t n, const ycge_grid *proto,
                               int32_t *out_grid_index /* n */, int32_t *cells_out /* NULL, or n * 2 * chunk_size^3 */);
+
+/* --- the pregenerated world: VolumeScenes.BuildMinecraftLike with a file name never calls the per-chunk generator; it builds the whole
+ * world with WorldManager.GenerateAndSaveWorld (WorldManager.cs:510-631), reads the file back and attaches every chunk
+ * (VolumeScenes.cs:608-616).  That function differs from GenerateChunkCells: rivers over the whole map (RiverNetworkGlobal: a cell with no
+ * lower neighbour adds nothing), slope / D8 / flora clamped at the WORLD's edge, the bank rule (wY - gY) <= 3.5f, and
+ * FloraPlacer.PlaceTreesGlobal (trees cross chunk borders, another trunk clip, no slope test, cacti and (Stone, 1) rock piles in deserts).
+ * Found by symbol lookup as the two above; YCGE_ABI_VERSION stays 10.
+ *   The WINDOW: chunks_x x chunks_y x chunks_z chunks of chunk_size; nx = chunks_x * S, ny = chunks_y * S, nz = chunks_z * S.  Column
+ *     (x, z) of the window is block (origin_bx + x, origin_bz + z) in every noise, hash and strata call; every edge clamp and bound is the
+ *     window's.  origin (0, 0) is the reference's world, bit for bit.
+ *   YCGE_ERR_INVALID_ARG, nothing written: what ycge_worldgen_chunk_cells refuses of `world`, chunks_x or chunks_z < 1, a window whose block
+ *     coordinates leave +-2^24, nx * ny * nz >= 2^30, a NULL cells_out.
+ * ycge_worldgen_world_cells: GenerateAndSaveWorld's worldCells on the host, one thread, no context and no device.  cells_out: 2*nx*ny*nz
+ * int32 in the VG01 payload order (x, then y, then z; {mat, meta}) - what bw.Write emits at :616-628. */
+int ycge_worldgen_world_cells(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *cells_out);
+/* The same world made ON THE DEVICE (csrc/ycge_worldpregen.hip) and made resident: what ycge_scene_attach_grids gives when handed, chunk by
+ * chunk in (cx, cy, cz) order with cx outermost, the S^3 slices of ycge_worldgen_world_cells' result - the same pixels, indices, limits and
+ * statuses, all or nothing, joining the frames in flight, forwarded to the devices of a one-process multi-device context.
+ *   Chunk (cx, cy, cz) gets min_corner = world_min + c * S * voxel_size.  A chunk none of whose cells is other than Air - after the flora
+ *     pass, whose trees cross chunk borders - takes no slot and reports -1 (AttachChunkFromPreloaded, WorldManager.cs:704-720).
+ *   out_grid_index: chunks_x * chunks_y * chunks_z, in that order; untouched when the call is refused.
+ *   proto: as for ycge_scene_generate_grids.  The chunks are worked through in sub-batches bounded by the staging area.
+ *   cells_out: NULL, or the whole world as ycge_worldgen_world_cells writes it (the only bulk read-back).  Untouched by an argument
+ *     refusal (the list above, a bad proto, no scene); it may have been written when the call is refused later.
+ *   YCGE_WORLDGEN_HOST at ycge_create (or a lookup table k_grid_encode does not take): ycge_worldgen_world_cells makes the cells and they
+ *     go up as an attach's. */
+int ycge_scene_generate_world(ycge_ctx *ctx, const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz,
+                              const ycge_grid *proto, int32_t *out_grid_index /* chunks_x*chunks_y*chunks_z */, int32_t *cells_out /* NULL, or 2*nx*ny*nz */);
 
 /* The argument checks of ycge_scene_upload on their own: pure host code, no device and no context needed
  * (every index in range, counts non-negative, pointers present, material kinds known).  Returns YCGE_OK or the

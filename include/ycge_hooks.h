@@ -86,6 +86,19 @@ int ycge_host_worldgen_noise(int32_t n, const int32_t *ix, const int32_t *iz, co
 int ycge_host_worldgen_height(const ycge_world *world, int32_t n, const int32_t *gx, const int32_t *gz, int32_t *height_out);                                      /* TerrainNoise.HeightY */
 int ycge_host_worldgen_river(const int32_t *tile /* (size + 2)^2 */, int32_t size, int32_t sea, int32_t *dir_out, float *accum_out, int32_t *carved_out, int32_t *river_water_out);   /* RiverNetwork.ComputeForChunk on a caller's height tile: D8 code (dx + 1) * 3 + (dz + 1), accum, carved ground, river surface */
 int ycge_host_worldgen_carve(float accum, int32_t ground, int32_t sea, int32_t *carved_out, int32_t *river_water_out);                                               /* the carve and river-surface formulas at a given accumulation */
+/* the pregenerated world, host only (tests/test_worldpregen_cpu.py against tests/worldpregen_restatement.py).  world_fields: the 2-D fields of a window as
+ * ycge_worldgen_world_cells computes them, each nx * nz in x * nz + z order, NULL = skipped: ground before and after the river pass, D8 code, accum, slope, biome,
+ * localWater, feature descriptor (csrc/ycge_worldgen.h), BiomeMap's dryness verdict alone (Forest / Desert whatever the height), StrataMap's noise verdict.
+ * world_from_fields: the voxel fill and PlaceTreesGlobal on CALLER-GIVEN fields of nx x nz columns (feature NULL: the descriptors are made from the fields, origin (0, 0)) - gather = 0 the serial loops, != 0 the kernels' scheme on the
+ * host (anyLeaves flags to a fixed point, then one gather per cell); *passes_out = 0 or the gather's passes */
+int ycge_host_worldgen_world_fields(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *ground0_out,
+                                    int32_t *ground_out, int32_t *dir_out, float *accum_out, float *slope_out, int32_t *biome_out, int32_t *water_out,
+                                    uint32_t *feature_out, int32_t *climate_out, int32_t *rock_out);
+int ycge_host_worldgen_river_global(const int32_t *ground /* nx * nz */, int32_t nx, int32_t nz, int32_t sea, int32_t *dir_out, float *accum_out, int32_t *carved_out,
+                                    int32_t *river_water_out);       /* RiverNetworkGlobal.Compute on a caller's heights: D8 code, accum (the in-degree), carved ground, river surface */
+int ycge_host_worldgen_world_from_fields(const ycge_world *world, int32_t nx, int32_t nz, const int32_t *ground, const int32_t *water, const float *slope,
+                                         const int32_t *biome, const int32_t *rock, const uint32_t *feature, int32_t gather, int32_t *cells_out, int32_t *passes_out);
+int ycge_debug_worldpregen_stats(ycge_ctx *c, int64_t *out5);        /* the last call of ycge_scene_generate_world, on the root device: anyLeaves passes (the last flips nothing); us of the 2-D field kernels, of the anyLeaves pass loop (wall time: a launch, a stream synchronise and a 4-byte read-back per pass), of the occupancy kernel and its read-back, of the fill kernels */
 int ycge_debug_worldgen_stats(ycge_ctx *c, int64_t *out4);           /* ycge_scene_generate_grids: chunks made on the device, chunks made on the host, the last call's column kernel and fill + tree kernels in us (root device) */
 int ycge_debug_read_post_progress(ycge_ctx *c, uint32_t *dst, size_t n_words);               /* k_atrous_stream's per-band records (profiles/post_bands.py) */
 int ycge_debug_read_wave_prof(ycge_ctx *c, unsigned long long *dst, size_t n_u64);            /* per-wavefront begin / end / steps of a profiling build (profiles/mega_prof.py) */

@@ -198,6 +198,8 @@ _PROTOTYPES = {
     # (world: a ycge_world, passed with C.byref(abi.World))
     "ycge_worldgen_chunk_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ycge_scene_generate_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(Grid), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ycge_worldgen_world_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "ycge_scene_generate_world": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Grid), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ycge_scene_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ycge_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]),
@@ -255,6 +257,10 @@ HOOK_PROTOTYPES = {
 # test / profiling hook of chunk generation (csrc/ycge_grid_encode.cpp), bound where it is used (RaytraceRenderer.worldgen_stats)
 WORLDGEN_HOOK_PROTOTYPES = {
     "ycge_debug_worldgen_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ycge_debug_worldpregen_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ycge_host_worldgen_world_fields": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
+    "ycge_host_worldgen_river_global": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "ycge_host_worldgen_world_from_fields": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
 }
 # test hooks of the post stage on caller-given inputs (csrc/ycge_post_host.cpp), bound where they are used (RaytraceRenderer.post_probe /
 # exposure_probe); state_out: POST_STATE_WORDS uint32

@@ -172,6 +172,7 @@ struct Knobs {
     bool mesh_emit_host = false;     // YCGE_MESH_EMIT_HOST: ycge_scene_upload writes every mesh's records and the treelets on the host, whoever built the trees
     int mesh_emit_device_min = YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT;   // YCGE_MESH_EMIT_DEVICE_MIN: ... and also when no tree built on the device has this many triangles (measured crossover of the whole upload, profiles/mesh_build_rate.json)
     bool no_coop = false;            // YCGE_NO_COOP: no treelets are built, sparse wavefronts keep the regular walk (A/B of the cooperative walk)
+    size_t enc_group_bytes = (size_t)256 << 20;   // YCGE_ENC_GROUP_BYTES: raw cells staged per encode group (attach / generate sub-batches); a larger grid is a group of its own
     bool worldgen_host = false;      // YCGE_WORLDGEN_HOST: ycge_scene_generate_grids makes the cells with the host generator (ycge_worldgen.cpp) and sends them up as an attach does
     bool exposure_serial = false;    // YCGE_EXPOSURE_SERIAL: the one-lane chain instead of the chunked exact evaluation
     void read()
@@ -222,6 +223,7 @@ struct Knobs {
         scene_bvh_device_min = geti("YCGE_SCENE_BVH_DEVICE_MIN", YCGE_BVH_DEV_MIN_ITEMS_DEFAULT);
         mesh_bvh_host = getenv("YCGE_MESH_BVH_HOST") != nullptr;
         worldgen_host = getenv("YCGE_WORLDGEN_HOST") != nullptr;
+        if (const char *e = getenv("YCGE_ENC_GROUP_BYTES")) { const long long v = atoll(e); if (v > 0) enc_group_bytes = (size_t)v; }
         mesh_emit_host = getenv("YCGE_MESH_EMIT_HOST") != nullptr;
         mesh_emit_device_min = geti("YCGE_MESH_EMIT_DEVICE_MIN", YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT);
         mesh_bvh_device_min = geti("YCGE_MESH_BVH_DEVICE_MIN", YCGE_MESH_BVH_DEV_MIN_TRIS_DEFAULT);
@@ -558,6 +560,8 @@ struct ycge_ctx {
     // ycge_scene_generate_grids: the column records of the batch's distinct (cx, cz) on this device, then their keys and tops
     DevBuf<uint8_t> d_wg_cols;
     int64_t worldgen_device_chunks = 0, worldgen_host_chunks = 0;          // since the context was made (root)
+    int worldpregen_last_passes = 0;                                      // ycge_scene_generate_world's last call on the root: anyLeaves passes,
+    double worldpregen_last_us[4] = {0, 0, 0, 0};                         // ... field kernels, anyLeaves passes, tops, fill kernels
     double worldgen_last_us[2] = {0, 0};                                  // the last call on the root: column kernel, fill + tree kernels
     DevBuf<uint8_t> d_cells;
     DevBuf<int32_t> d_lut;

@@ -101,8 +101,47 @@ struct GenSource {
     std::vector<int32_t> col;                        // per grid: its chunk column among the column records
     std::vector<wg::ColRec> host_cols;               // host: n_cols x S * S (device: every context's d_wg_cols)
     std::vector<int32_t *> cells_out;                // per grid, or empty
+    // ycge_scene_generate_world: keys are chunk coordinates in the window; the cells come from the window's fields on every device
+    // (k_wp_fill), or are slices of host_world
+    bool world = false;
+    wg::Window N{};
+    const int32_t *host_world = nullptr;             // host: the whole world's cells, VG01 order
+    int32_t *world_out = nullptr;                    // device: the caller's cells_out (whole world), or NULL
     size_t chunk_bytes() const { return (size_t)W.size * W.size * W.size * 8; }
 };
+// chunk `key` of a world in VG01 order <-> its S^3 cells in ycge_grid.cells order (rows of S cells along z)
+void world_slice(const GenSource &g, const std::array<int32_t, 3> &key, const int32_t *world, int32_t *chunk)
+{
+    const size_t S = (size_t)g.W.size, ny = (size_t)g.W.height, nz = (size_t)g.N.nz;
+    for (size_t lx = 0; lx < S; lx++)
+        for (size_t ly = 0; ly < S; ly++)
+            std::memcpy(chunk + 2 * (lx * S + ly) * S, world + 2 * (((key[0] * S + lx) * ny + key[1] * S + ly) * nz + key[2] * S), S * 8);
+}
+void world_scatter(const GenSource &g, const std::array<int32_t, 3> &key, const int32_t *chunk, int32_t *world)
+{
+    const size_t S = (size_t)g.W.size, ny = (size_t)g.W.height, nz = (size_t)g.N.nz;
+    for (size_t lx = 0; lx < S; lx++)
+        for (size_t ly = 0; ly < S; ly++)
+            std::memcpy(world + 2 * (((key[0] * S + lx) * ny + key[1] * S + ly) * nz + key[2] * S), chunk + 2 * (lx * S + ly) * S, S * 8);
+}
+// where the fields of a window of n columns (and the occupancy words of its n_chunks chunks, last: nothing else moves with their number)
+// lie in a context's d_wg_cols
+size_t wp_layout(uint8_t *base, size_t n, size_t n_chunks, WpFields *F)
+{
+    size_t at = 0;
+    auto take = [&](size_t bytes) { uint8_t *p = base ? base + at : nullptr; at = align_up(at + bytes, 256); return p; };
+    WpFields f;
+    f.rec = (wg::ColRec *)take(n * sizeof(wg::ColRec));
+    f.ground0 = (int32_t *)take(n * 4); f.ground = (int32_t *)take(n * 4); f.river_water = (int32_t *)take(n * 4);
+    f.feat = (uint32_t *)take(n * 4); f.reach = (int32_t *)take(n * 4);
+    f.dir = take(n); f.fallback = take(n);
+    (void)take(n);          // the other flag buffer of the anyLeaves passes (wp_next_flags)
+    f.changed = (uint32_t *)take(256);
+    f.occupied = (uint32_t *)take(n_chunks * 4);
+    if (F) *F = f;
+    return at;
+}
+uint8_t *wp_next_flags(const WpFields &F, size_t n) { return F.fallback + align_up(n, 256); }
 constexpr size_t kGenGroupMax = 32768;               // chunks in one fill launch (gridDim.y)
 
 // one group of device-encoded grids: stage, copy, launch, read back (every device of the context; the root's results are returned).
@@ -142,7 +181,10 @@ int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &p
         init[j] = r;
         if (g.n_lookup > 0) std::memcpy(st + pl.lookup_off, g.lookup, (size_t)g.n_lookup * sizeof(ycge_voxel_lookup));
         if (!gen) std::memcpy(st + pl.cells_off, g.cells, (size_t)g.nx * g.ny * g.nz * 8);
-        else if (gen->host) {
+        else if (gen->world && gen->host) {
+            const size_t k = (size_t)group[j];
+            world_slice(*gen, gen->keys[k], gen->host_world, (int32_t *)(st + pl.cells_off));
+        } else if (gen->host) {
             const size_t k = (size_t)group[j];
             int32_t any = 0;
             worldgen_fill_host(gen->W, gen->host_cols.data() + (size_t)gen->col[k] * gen->W.size * gen->W.size, gen->keys[k][0], gen->keys[k][1], gen->keys[k][2],
@@ -191,9 +233,15 @@ int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &p
         if (c == root) us[1] += us_since(t0);
         t0 = std::chrono::steady_clock::now();
         if (gen_dev) {
-            const int ge = ycge_launch_worldgen_fill((const WgChunk *)(c->d_enc_in.p + off_chunks), (int)m, &gen->W, (const wg::ColRec *)c->d_wg_cols.p,
-                                                     (uint32_t *)(c->d_enc_in.p + off_any), c->stream);
-            if (ge != 0) return root->fail(YCGE_ERR_DEVICE, "k_wg_fill launch failed: %s", hipGetErrorString((hipError_t)ge));
+            int ge;
+            if (gen->world) {
+                WpFields F;
+                wp_layout(c->d_wg_cols.p, (size_t)gen->N.nx * gen->N.nz, 0, &F);
+                ge = ycge_launch_worldpregen_fill((const WgChunk *)(c->d_enc_in.p + off_chunks), (int)m, &gen->W, &gen->N, &F, (uint32_t *)(c->d_enc_in.p + off_any), c->stream);
+            } else
+                ge = ycge_launch_worldgen_fill((const WgChunk *)(c->d_enc_in.p + off_chunks), (int)m, &gen->W, (const wg::ColRec *)c->d_wg_cols.p,
+                                               (uint32_t *)(c->d_enc_in.p + off_any), c->stream);
+            if (ge != 0) return root->fail(YCGE_ERR_DEVICE, "%s launch failed: %s", gen->world ? "k_wp_fill" : "k_wg_fill", hipGetErrorString((hipError_t)ge));
             if (c == root) { HIP_TRY(root, hipStreamSynchronize(c->stream)); root->worldgen_last_us[1] += us_since(t0); t0 = std::chrono::steady_clock::now(); }
         }
         const int e = ycge_launch_grid_encode(c->d_enc_in.p, (int)m, c->d_enc_in.p + off_res, n_wg, c->stream);
@@ -210,9 +258,17 @@ int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &p
         }
         if (gen_dev && c == root) {
             const uint32_t *any = (const uint32_t *)(st + off_back + m * sizeof(GridEncResult));
+            std::vector<uint8_t> made;          // ycge_scene_generate_world with cells_out: the group's cell area in ONE copy, scattered below
+            if (gen->world && gen->world_out) {
+                made.resize(dev_total - off_cells);
+                const int rc = copy_out(root, made.data(), c->d_enc_in.p + off_cells, made.size());
+                if (rc != YCGE_OK) return rc;
+            }
             for (size_t j = 0; j < m; j++) {
                 const size_t k = (size_t)group[j];
-                if (!any[j]) return root->fail(YCGE_ERR_INTERNAL, "ycge_scene_generate_grids: chunk (%d, %d, %d) came out empty", gen->keys[k][0], gen->keys[k][1], gen->keys[k][2]);
+                if (!any[j]) return root->fail(YCGE_ERR_INTERNAL, "%s: chunk (%d, %d, %d) came out empty", gen->world ? "ycge_scene_generate_world" : "ycge_scene_generate_grids",
+                                               gen->keys[k][0], gen->keys[k][1], gen->keys[k][2]);
+                if (!made.empty()) world_scatter(*gen, gen->keys[k], (const int32_t *)(made.data() + (plan[k].cells_off - off_cells)), gen->world_out);
                 if (!gen->cells_out.empty()) {
                     const int rc = copy_out(root, gen->cells_out[k], c->d_enc_in.p + plan[k].cells_off, gen->chunk_bytes());
                     if (rc != YCGE_OK) return rc;
@@ -333,7 +389,7 @@ static int attach_common(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t
     {
         std::vector<int> group;
         size_t group_bytes = 0;
-        const size_t budget = (size_t)256 << 20;
+        const size_t budget = c->knobs.enc_group_bytes;          // (256 MiB; YCGE_ENC_GROUP_BYTES)
         for (int k = 0; k <= n; k++) {
             const size_t bytes = k < n ? (size_t)grids[k].nx * grids[k].ny * grids[k].nz * 8 : 0;
             if (!group.empty() && (k == n || group_bytes + bytes > budget)) {
@@ -364,7 +420,11 @@ static int attach_common(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t
             pl.host_bytes.assign(pl.cap, 0);
             ycge_grid gh = g;
             std::vector<int32_t> made;
-            if (gen) {          // a lookup table too large for k_grid_encode: this chunk's cells are made here, whoever makes the others
+            if (gen && gen->world) {          // (ycge_scene_generate_world takes the host generator for such a table: the world is there)
+                made.resize(gen->chunk_bytes() / 4);
+                world_slice(*gen, gen->keys[(size_t)k], gen->host_world, made.data());
+                gh.cells = made.data();
+            } else if (gen) {          // a lookup table too large for k_grid_encode: this chunk's cells are made here, whoever makes the others
                 std::vector<wg::ColRec> cols((size_t)gen->W.size * gen->W.size);
                 int32_t any = 0;
                 made.resize(gen->chunk_bytes() / 4);
@@ -598,6 +658,149 @@ try {
     }
     for (int k : air_k) out_grid_index[k] = -1;
     for (size_t j = 0; j < solid_k.size(); j++) out_grid_index[solid_k[j]] = idx[j];
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ycge_scene_generate_world: the 2-D fields of the window first (on every device), the anyLeaves flags to their fixed point, then one
+// word per chunk - does it hold anything (AttachChunkFromPreloaded, WorldManager.cs:704-720: any cell not Air, trees from other chunks
+// included; EXACT, chunk by chunk: between a column's ground and a neighbour's canopy above it a whole small chunk can be Air) - then attach_common with a GenSource of the chunks that do, whose groups are the sub-batches k_wp_fill fills.  Everything
+// before attach_common changes scratch buffers only, and attach_common is all or nothing.
+int ycge_scene_generate_world(ycge_ctx *c, const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, const ycge_grid *proto,
+                              int32_t *out_grid_index, int32_t *cells_out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    const char *why = nullptr;
+    if (worldgen_check(world, &why) != YCGE_OK || worldgen_window_check(world, chunks_x, chunks_z, origin_bx, origin_bz, &why) != YCGE_OK)
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_generate_world: %s", why);
+    if (!out_grid_index || !proto) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_generate_world: null argument");
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    const int S = world->chunk_size, chunks_y = world->chunks_y;
+    static const int32_t no_cells[2] = {0, 0};
+    ycge_grid g0 = *proto;
+    g0.nx = g0.ny = g0.nz = S; g0.voxel_size = world->voxel_size; g0.cells = no_cells;
+    {
+        std::string m;
+        const int vrc = validate_grid(g0, 0, c->n_materials, m);
+        if (vrc != YCGE_OK) return c->fail(vrc, "%s", m.c_str());
+    }
+    int rc = quiesce(c);
+    for (ycge_ctx *p : c->peers) if (rc == YCGE_OK) rc = quiesce(p);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const DeviceGuard guard(c->device);
+
+    GenSource gen;
+    gen.world = true;
+    gen.W = wg::make_world(S, chunks_y, world->world_seed);
+    gen.N = wg::Window{chunks_x * S, chunks_z * S, origin_bx, origin_bz};
+    gen.host = c->knobs.worldgen_host || proto->n_lookup > YCGE_ENC_MAX_LOOKUP;          // (a table k_grid_encode does not take: every chunk is encoded on the host, from the host's cells)
+    const size_t n_cols = (size_t)gen.N.nx * gen.N.nz, ny = (size_t)gen.W.height, n_chunks = (size_t)chunks_x * chunks_y * chunks_z;
+    const size_t world_i32 = 2 * n_cols * ny;
+    std::vector<uint8_t> occupied(n_chunks, 0);          // per chunk, (cx, cy, cz) with cx outermost
+    std::vector<int32_t> host_world;
+    for (double &u : c->worldpregen_last_us) u = 0;
+    c->worldpregen_last_passes = 0;
+    if (gen.host) {
+        int32_t *w = cells_out;
+        if (!w) { host_world.resize(world_i32); w = host_world.data(); }
+        world_cells_host(world, chunks_x, chunks_z, origin_bx, origin_bz, w);
+        gen.host_world = w;
+        for (size_t x = 0; x < (size_t)gen.N.nx; x++)
+            for (size_t y = 0; y < ny; y++) {
+                const int32_t *row = w + 2 * ((x * ny + y) * gen.N.nz);
+                for (size_t z = 0; z < (size_t)gen.N.nz; z++)
+                    if (row[2 * z] != 0) occupied[((x / S) * chunks_y + y / S) * chunks_z + z / S] = 1;
+            }
+    } else {
+        std::vector<ycge_ctx *> ctxs{c};
+        ctxs.insert(ctxs.end(), c->peers.begin(), c->peers.end());
+        std::vector<uint32_t> occ_words(n_chunks);
+        int root_passes = 0;
+        for (ycge_ctx *x : ctxs) {          // (the root first: a peer repeats its passes without reading anything back)
+            HIP_TRY(c, hipSetDevice(x->device));
+            const size_t need = wp_layout(nullptr, n_cols, n_chunks, nullptr);
+            if (x->d_wg_cols.cap < need) HIP_TRY(c, x->d_wg_cols.alloc(need));
+            WpFields F;
+            wp_layout(x->d_wg_cols.p, n_cols, n_chunks, &F);
+            uint8_t *flags[2] = {F.fallback, wp_next_flags(F, n_cols)};
+            auto t0 = std::chrono::steady_clock::now();
+            int e = ycge_launch_worldpregen_fields(&gen.W, &gen.N, &F, x->stream);
+            if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wp_* launch failed: %s", hipGetErrorString((hipError_t)e));
+            HIP_TRY(c, hipStreamSynchronize(x->stream));
+            if (x == c) c->worldpregen_last_us[0] = us_since(t0);
+            t0 = std::chrono::steady_clock::now();
+            int passes = 0, cur = 0;
+            for (;;) {          // anyLeaves: from flags[cur] into flags[1 - cur] until a pass flips nothing (then both hold the fixed point)
+                F.fallback = flags[cur];
+                e = ycge_launch_worldpregen_any_leaves(&gen.W, &gen.N, &F, flags[1 - cur], x->stream);
+                if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wp_any_leaves launch failed: %s", hipGetErrorString((hipError_t)e));
+                passes++;
+                if (x != c) { if (passes == root_passes) break; cur = 1 - cur; continue; }
+                HIP_TRY(c, hipStreamSynchronize(x->stream));
+                uint32_t changed = 0;
+                rc = copy_out(c, &changed, F.changed, sizeof changed);
+                if (rc != YCGE_OK) return rc;
+                if (!changed) break;
+                if ((size_t)passes > n_cols + 1) return c->fail(YCGE_ERR_INTERNAL, "ycge_scene_generate_world: the anyLeaves passes do not settle");
+                cur = 1 - cur;
+            }
+            F.fallback = flags[0];          // (the last pass flipped nothing: both buffers hold the fixed point, and wp_layout names this one)
+            if (x == c) { root_passes = c->worldpregen_last_passes = passes; c->worldpregen_last_us[1] = us_since(t0); }
+            t0 = std::chrono::steady_clock::now();
+            if (x == c) {
+                e = ycge_launch_worldpregen_occupied(&gen.W, &gen.N, &F, chunks_y, chunks_z, n_chunks, x->stream);
+                if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wp_occupied launch failed: %s", hipGetErrorString((hipError_t)e));
+            }
+            HIP_TRY(c, hipStreamSynchronize(x->stream));
+            if (x == c) {
+                rc = copy_out(c, occ_words.data(), F.occupied, n_chunks * 4);
+                if (rc != YCGE_OK) return rc;
+                c->worldpregen_last_us[2] = us_since(t0);
+            }
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        for (size_t k = 0; k < n_chunks; k++) occupied[k] = occ_words[k] != 0;
+        if (cells_out) { std::memset(cells_out, 0, world_i32 * 4); gen.world_out = cells_out; }          // (a chunk that holds nothing is (Air, 0) throughout)
+    }
+    std::vector<ycge_grid> grids;
+    std::vector<size_t> solid_k;
+    for (int cx = 0; cx < chunks_x; cx++)
+        for (int cy = 0; cy < chunks_y; cy++)
+            for (int cz = 0; cz < chunks_z; cz++) {
+                const size_t k = ((size_t)cx * chunks_y + cy) * chunks_z + cz;
+                if (!occupied[k]) continue;
+                ycge_grid g = g0;
+                g.min_corner.x = world->world_min.x + (float)(cx * S) * world->voxel_size.x;          // WorldManager.cs:722-726
+                g.min_corner.y = world->world_min.y + (float)(cy * S) * world->voxel_size.y;
+                g.min_corner.z = world->world_min.z + (float)(cz * S) * world->voxel_size.z;
+                grids.push_back(g);
+                gen.keys.push_back({{cx, cy, cz}}); gen.col.push_back(0);
+                solid_k.push_back(k);
+            }
+    std::vector<int32_t> idx(solid_k.size(), -1);
+    if (!solid_k.empty()) {
+        c->worldgen_last_us[1] = 0;
+        rc = attach_common(c, grids.data(), (int32_t)grids.size(), idx.data(), &gen);
+        if (rc != YCGE_OK) return rc;
+        c->worldpregen_last_us[3] = c->worldgen_last_us[1];
+    }
+    (gen.host ? c->worldgen_host_chunks : c->worldgen_device_chunks) += (int64_t)n_chunks;
+    for (size_t k = 0; k < n_chunks; k++) out_grid_index[k] = -1;
+    for (size_t j = 0; j < solid_k.size(); j++) out_grid_index[solid_k[j]] = idx[j];
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hook: the last ycge_scene_generate_world on the root device - {anyLeaves passes (the last flips nothing), us of the
+// 2-D field kernels, of the anyLeaves pass loop (WALL time: each pass is a launch, a stream synchronise and a 4-byte read-back), of the
+// occupancy kernel and its read-back, of the fill kernels}
+int ycge_debug_worldpregen_stats(ycge_ctx *c, int64_t *out5)
+try {
+    if (!c || !out5) return YCGE_ERR_INVALID_ARG;
+    out5[0] = c->worldpregen_last_passes;
+    for (int a = 0; a < 4; a++) out5[1 + a] = (int64_t)c->worldpregen_last_us[a];
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }

@@ -1,6 +1,7 @@
 // ycge_worldgen.cpp - the host generator: WorldGenerator.GenerateChunkCells (Scenes/WorldGeneration/WorldGenerator.cs:95-203) on one
 // thread, loop for loop, from the restatement in ycge_worldgen.h.  It is the yardstick the device generator (ycge_worldgen.hip) is held
 // to, and what ycge_scene_generate_grids runs under YCGE_WORLDGEN_HOST.  ycge_worldgen_chunk_cells needs no context and no device.
+// Below it, WorldManager.GenerateAndSaveWorld (WorldManager.cs:510-631) the same way: ycge_worldgen_world_cells.
 #include <cstring>
 #include <new>
 #include <vector>
@@ -114,6 +115,166 @@ void worldgen_fill_host(const wg::World &W, const wg::ColRec *cols, int cx, int 
     *any_solid_out = any_solid ? 1 : 0;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------- GenerateAndSaveWorld
+int worldgen_window_check(const ycge_world *w, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, const char **why)
+{
+    if (chunks_x < 1 || chunks_z < 1) { *why = "chunks_x or chunks_z < 1"; return YCGE_ERR_INVALID_ARG; }
+    const int64_t S = w->chunk_size, lim = 1 << 24;
+    const int64_t nx = chunks_x * S, nz = chunks_z * S, ny = (int64_t)w->chunks_y * S;
+    if (origin_bx < -lim || origin_bz < -lim || origin_bx + nx - 1 > lim || origin_bz + nz - 1 > lim) { *why = "the window leaves +-2^24 blocks"; return YCGE_ERR_INVALID_ARG; }
+    if (nx * ny >= ((int64_t)1 << 30) || nx * ny * nz >= ((int64_t)1 << 30)) { *why = "nx * ny * nz >= 2^30"; return YCGE_ERR_INVALID_ARG; }          // (nx, nz <= 2^25 + 1, ny <= 2^20)
+    return YCGE_OK;
+}
+
+// WorldManager.cs:521-560 and the feature descriptors, loop for loop
+void world_fields_host(const wg::World &W, const wg::Window &N, WorldFields &F)
+{
+    const int nx = N.nx, nz = N.nz;
+    const size_t n = (size_t)nx * nz;
+    F.ground0.resize(n); F.ground.resize(n); F.river_water.resize(n); F.dir.resize(n); F.accum.resize(n); F.rec.resize(n); F.feat.resize(n);
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++) F.ground0[(size_t)x * nz + z] = wg::height_y(N.ox + x, N.oz + z, W);
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++) F.dir[(size_t)x * nz + z] = (uint8_t)wg::d8_global(F.ground0.data(), nx, nz, x, z);
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++) {
+            const size_t i = (size_t)x * nz + z;
+            F.accum[i] = wg::river_accum_global(F.dir.data(), nx, nz, x, z);
+            F.ground[i] = wg::river_carve(F.accum[i], F.ground0[i], W.sea, &F.river_water[i]);
+        }
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++) {
+            const size_t i = (size_t)x * nz + z;
+            F.rec[i] = wg::column_record_global(F.ground.data(), N, x, z, F.river_water[i], W);
+            F.feat[i] = wg::feature_at(F.rec[i], N.ox + x, N.oz + z, W);
+        }
+}
+
+// WorldManager.cs:562-606: the voxel fill, then FloraPlacer.PlaceTreesGlobal (FloraPlacer.cs:137-254) as the serial loops it is, from the
+// feature descriptors.  cells: the VG01 payload, (x * ny + y) * nz + z.
+void world_serial_host(const wg::World &W, const wg::Window &N, const wg::ColRec *rec, const uint32_t *feat, int32_t *cells)
+{
+    const int nx = N.nx, nz = N.nz, ny = W.height;
+    auto at = [&](int x, int y, int z) { return cells + 2 * (((size_t)x * ny + y) * nz + z); };
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++) {
+            const wg::ColRec &R = rec[(size_t)x * nz + z];
+            for (int y = 0; y < ny; y++) { int32_t *c = at(x, y, z); int mat, meta; wg::cell_at_global(R, y, W, &mat, &meta); c[0] = mat; c[1] = meta; }
+        }
+    for (int gx = 0; gx < nx; gx++) {
+        for (int gz = 0; gz < nz; gz++) {
+            const uint32_t d = feat[(size_t)gx * nz + gz];
+            if (wg::feat_kind(d) != wg::kFeatTree) continue;
+            const wg::Tree T = wg::feat_tree(d, rec[(size_t)gx * nz + gz].ground);
+            for (int t = 0; t < T.trunk_h; t++) {          // :171-176
+                const int y = T.trunk_base + t;
+                if (y < 0 || y >= ny) break;
+                int32_t *c = at(gx, y, gz);
+                if (wg::tree_may_replace(c[0])) { c[0] = wg::kWood; c[1] = 0; }
+            }
+            bool any_leaves = false;          // :179-195
+            for (int dy = wg::tree_dy_min(T); dy <= 2; dy++) {
+                const int y = T.canopy_base + dy;
+                if (y < 0 || y >= ny) continue;
+                const int radius = wg::tree_radius(T, dy);
+                for (int rx = -radius; rx <= radius; rx++) {
+                    const int x2 = gx + rx;
+                    if (x2 < 0 || x2 >= nx) continue;
+                    for (int rz = -radius; rz <= radius; rz++) {
+                        const int z2 = gz + rz;
+                        if (z2 < 0 || z2 >= nz) continue;
+                        int32_t *c = at(x2, y, z2);
+                        if (wg::tree_may_replace(c[0])) { c[0] = wg::kLeaves; c[1] = 0; any_leaves = true; }
+                    }
+                }
+            }
+            if (!any_leaves) {          // :196-211
+                const int y = T.trunk_base + T.trunk_h - 1;
+                if (y >= 0 && y < ny)
+                    for (int rx = -1; rx <= 1; rx++) {
+                        const int x2 = gx + rx;
+                        if (x2 < 0 || x2 >= nx) continue;
+                        for (int rz = -1; rz <= 1; rz++) {
+                            const int z2 = gz + rz;
+                            if (z2 < 0 || z2 >= nz) continue;
+                            int32_t *c = at(x2, y, z2);
+                            if (c[0] == wg::kAir) { c[0] = wg::kLeaves; c[1] = 0; }
+                        }
+                    }
+            }
+        }
+        for (int gz = 0; gz < nz; gz++) {          // :214-252, after the trees of this x
+            const uint32_t d = feat[(size_t)gx * nz + gz];
+            const int gY = rec[(size_t)gx * nz + gz].ground;
+            if (wg::feat_kind(d) == wg::kFeatCactus) {
+                const int height = wg::feat_cactus_h(d);
+                for (int t = 1; t <= height; t++) {
+                    const int y = gY + t;
+                    if (y >= ny) break;
+                    int32_t *c = at(gx, y, gz);
+                    if (c[0] == wg::kAir) { c[0] = wg::kWood; c[1] = 0; }
+                }
+            } else if (wg::feat_kind(d) == wg::kFeatRock) {
+                const int y = gY + 1;
+                if (y >= ny) continue;
+                for (int rx = -1; rx <= 1; rx++) {
+                    const int x2 = gx + rx;
+                    if (x2 < 0 || x2 >= nx) continue;
+                    for (int rz = -1; rz <= 1; rz++) {
+                        const int z2 = gz + rz;
+                        if (z2 < 0 || z2 >= nz) continue;
+                        if ((rx < 0 ? -rx : rx) + (rz < 0 ? -rz : rz) > 1) continue;
+                        int32_t *c = at(x2, y, z2);
+                        if (c[0] == wg::kAir) { c[0] = wg::kStone; c[1] = 1; }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The same cells the way the kernels make them (ycge_worldpregen.hip), on the host: the fallback flags to their fixed point, then every
+// cell by wg::world_cell.  Returns the number of passes over the trees (the last one changes nothing).
+int world_gather_host(const wg::World &W, const wg::Window &N, const wg::ColRec *rec, const uint32_t *feat, int32_t *cells)
+{
+    const int nx = N.nx, nz = N.nz, ny = W.height;
+    std::vector<uint8_t> fallback((size_t)nx * nz, 0);
+    int passes = 0;
+    for (bool changed = true; changed;) {
+        changed = false;
+        passes++;
+        std::vector<uint8_t> next = fallback;
+        for (int x = 0; x < nx; x++)
+            for (int z = 0; z < nz; z++) {
+                const size_t i = (size_t)x * nz + z;
+                if (wg::feat_kind(feat[i]) != wg::kFeatTree) continue;
+                const uint8_t f = wg::tree_any_leaves(rec, feat, fallback.data(), N, W, x, z) ? 0 : 1;
+                if (f != fallback[i]) { next[i] = f; changed = true; }
+            }
+        fallback.swap(next);
+    }
+    for (int x = 0; x < nx; x++)
+        for (int y = 0; y < ny; y++)
+            for (int z = 0; z < nz; z++) {
+                int mat, meta;
+                wg::world_cell(rec, feat, fallback.data(), N, W, x, y, z, &mat, &meta);
+                int32_t *c = cells + 2 * (((size_t)x * ny + y) * nz + z);
+                c[0] = mat; c[1] = meta;
+            }
+    return passes;
+}
+
+int world_cells_host(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *cells_out)
+{
+    const wg::World W = wg::make_world(world->chunk_size, world->chunks_y, world->world_seed);
+    const wg::Window N = {chunks_x * W.size, chunks_z * W.size, origin_bx, origin_bz};
+    WorldFields F;
+    world_fields_host(W, N, F);
+    world_serial_host(W, N, F.rec.data(), F.feat.data(), cells_out);
+    return YCGE_OK;
+}
+
 }  // namespace ycge_host
 
 extern "C" int ycge_worldgen_chunk_cells(const ycge_world *world, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t *any_solid_out)
@@ -175,4 +336,96 @@ try {
     *carved_out = wg::river_carve(accum, ground, sea, river_water_out);
     return YCGE_OK;
 }
+catch (...) { return YCGE_ERR_INTERNAL; }
+
+// ---- GenerateAndSaveWorld
+extern "C" int ycge_worldgen_world_cells(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *cells_out)
+try {
+    const char *why = nullptr;
+    int rc = ycge_host::worldgen_check(world, &why);
+    if (rc == YCGE_OK) rc = ycge_host::worldgen_window_check(world, chunks_x, chunks_z, origin_bx, origin_bz, &why);
+    if (rc != YCGE_OK) return rc;
+    if (!cells_out) return YCGE_ERR_INVALID_ARG;
+    return ycge_host::world_cells_host(world, chunks_x, chunks_z, origin_bx, origin_bz, cells_out);
+}
+catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
+catch (...) { return YCGE_ERR_INTERNAL; }
+
+// test hook: the 2-D fields of a window from the host code, each nx * nz in x * nz + z order (NULL: skipped).  climate: BiomeMap's
+// dryness verdict alone (Forest or Desert, whatever the height); rock: StrataMap's noise verdict.
+extern "C" int ycge_host_worldgen_world_fields(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *ground0_out,
+                                               int32_t *ground_out, int32_t *dir_out, float *accum_out, float *slope_out, int32_t *biome_out, int32_t *water_out,
+                                               uint32_t *feature_out, int32_t *climate_out, int32_t *rock_out)
+try {
+    const char *why = nullptr;
+    int rc = ycge_host::worldgen_check(world, &why);
+    if (rc == YCGE_OK) rc = ycge_host::worldgen_window_check(world, chunks_x, chunks_z, origin_bx, origin_bz, &why);
+    if (rc != YCGE_OK) return rc;
+    const wg::World W = wg::make_world(world->chunk_size, world->chunks_y, world->world_seed);
+    const wg::Window N = {chunks_x * W.size, chunks_z * W.size, origin_bx, origin_bz};
+    ycge_host::WorldFields F;
+    ycge_host::world_fields_host(W, N, F);
+    const size_t n = (size_t)N.nx * N.nz;
+    for (size_t i = 0; i < n; i++) {
+        if (ground0_out) ground0_out[i] = F.ground0[i];
+        if (ground_out) ground_out[i] = F.ground[i];
+        if (dir_out) dir_out[i] = F.dir[i];
+        if (accum_out) accum_out[i] = F.accum[i];
+        if (slope_out) slope_out[i] = F.rec[i].slope;
+        if (biome_out) biome_out[i] = F.rec[i].biome_rock & 0xff;
+        if (water_out) water_out[i] = F.rec[i].water;
+        if (feature_out) feature_out[i] = F.feat[i];
+        if (climate_out) climate_out[i] = wg::biome_evaluate(N.ox + (int)(i / N.nz), N.oz + (int)(i % N.nz), W.sea + wg::kBeachBuffer + 1, W.sea, W);
+        if (rock_out) rock_out[i] = F.rec[i].biome_rock >> 8;
+    }
+    return YCGE_OK;
+}
+catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
+catch (...) { return YCGE_ERR_INTERNAL; }
+
+// test hook: RiverNetworkGlobal.Compute (and WorldManager.cs:536) on a caller's nx * nz heights: D8 code, accum, carved ground, river surface
+extern "C" int ycge_host_worldgen_river_global(const int32_t *ground, int32_t nx, int32_t nz, int32_t sea, int32_t *dir_out, float *accum_out, int32_t *carved_out,
+                                               int32_t *river_water_out)
+try {
+    if (!ground || nx < 1 || nz < 1 || (int64_t)nx * nz > (1 << 24) || !dir_out || !accum_out || !carved_out || !river_water_out) return YCGE_ERR_INVALID_ARG;
+    std::vector<uint8_t> dir((size_t)nx * nz);
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++) dir_out[x * nz + z] = dir[(size_t)x * nz + z] = (uint8_t)wg::d8_global(ground, nx, nz, x, z);
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++) {
+            const int i = x * nz + z;
+            accum_out[i] = wg::river_accum_global(dir.data(), nx, nz, x, z);
+            carved_out[i] = wg::river_carve(accum_out[i], ground[i], sea, &river_water_out[i]);
+        }
+    return YCGE_OK;
+}
+catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
+catch (...) { return YCGE_ERR_INTERNAL; }
+
+// test hook: the voxel fill and the flora pass on CALLER-GIVEN fields of nx x nz columns (any sizes >= 1; ground in 0..height-1; biome a
+// Biome value; rock 0..2; feature a descriptor of ycge_worldgen.h, or NULL: wg::feature_at of the given fields with origin (0, 0)) - gather == 0: the serial loops of ycge_worldgen_world_cells, != 0: the
+// kernels' scheme on the host (fallback flags to a fixed point, then wg::world_cell per cell).  passes_out: 0, or the gather's passes.
+extern "C" int ycge_host_worldgen_world_from_fields(const ycge_world *world, int32_t nx, int32_t nz, const int32_t *ground, const int32_t *water, const float *slope,
+                                                    const int32_t *biome, const int32_t *rock, const uint32_t *feature, int32_t gather, int32_t *cells_out,
+                                                    int32_t *passes_out)
+try {
+    const char *why = nullptr;
+    if (ycge_host::worldgen_check(world, &why) != YCGE_OK || nx < 1 || nz < 1 || !ground || !water || !slope || !biome || !rock || !cells_out || !passes_out)
+        return YCGE_ERR_INVALID_ARG;
+    const wg::World W = wg::make_world(world->chunk_size, world->chunks_y, world->world_seed);
+    if ((int64_t)nx * nz * W.height >= ((int64_t)1 << 30)) return YCGE_ERR_INVALID_ARG;
+    const wg::Window N = {nx, nz, 0, 0};
+    std::vector<wg::ColRec> rec((size_t)nx * nz);
+    for (size_t i = 0; i < rec.size(); i++) {
+        if (ground[i] < 0 || ground[i] >= W.height) return YCGE_ERR_INVALID_ARG;
+        rec[i].ground = ground[i]; rec[i].water = water[i]; rec[i].slope = slope[i]; rec[i].biome_rock = (biome[i] & 0xff) | ((rock[i] & 3) << 8);
+    }
+    std::vector<uint32_t> feat(rec.size());
+    for (size_t i = 0; i < rec.size(); i++) feat[i] = feature ? feature[i] : wg::feature_at(rec[i], (int)(i / (size_t)nz), (int)(i % (size_t)nz), W);
+    *passes_out = 0;
+    if (gather) *passes_out = ycge_host::world_gather_host(W, N, rec.data(), feat.data(), cells_out);
+    else ycge_host::world_serial_host(W, N, rec.data(), feat.data(), cells_out);
+    return YCGE_OK;
+}
+catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
 catch (...) { return YCGE_ERR_INTERNAL; }

@@ -1,12 +1,12 @@
-// ycge_worldgen.h - WorldGenerator.GenerateChunkCells restated for host and gfx950 (Scenes/WorldGeneration/*.cs of the reference).
+// ycge_worldgen.h - WorldGenerator.GenerateChunkCells and WorldManager.GenerateAndSaveWorld restated for host and gfx950
+// (Scenes/WorldGeneration/*.cs of the reference).
 //
 // One chunk of the voxel world is a pure function of (cx, cy, cz, WorldConfig): integer hashing and fp32 + - * / sqrt floor round, plus
 // one MathF.Pow.  Everything here obeys ycge_math.h's contract (no contraction, correctly rounded divide and sqrt, m_pow for the power), so
 // the host generator (ycge_worldgen.cpp) and the kernels (ycge_worldgen.hip) give the same cells, bit for bit.
 //
 // IslandSettings (IslandSettings.cs:5-54) and the WorldGenSettings fields the generator reads (WorldGenSettings.cs) are compile-time
-// constants at the reference's values.  Not restated: the whole-world pregen path (RiverNetworkGlobal, PlaceTreesGlobal), the dead
-// FBM3D / GradientNoise3D / GetBlockAt, SimpleEntityPlacer.
+// constants at the reference's values.  Not restated: the dead FBM3D / GradientNoise3D / GetBlockAt, SimpleEntityPlacer.
 //
 // The work is cut where the data flow cuts it:
 //   height_y            TerrainNoise.HeightY: once per cell of the (S + 2)^2 tile around a chunk column (cx, cz)
@@ -16,6 +16,12 @@
 //   column_record       WorldGenerator.cs:125-154 + StrataMap's noise verdict: what every cy of the column shares
 //   cell_at             WorldGenerator.cs:156-199, one cell from its column's record
 //   tree_at + the tree_* helpers   FloraPlacer.cs:27-69; the placement loops (:71-131) are the callers'
+// and, for the whole-world pregen (WorldManager.cs:510-631; the second half of this file):
+//   d8_global, river_accum_global   RiverNetworkGlobal.cs:17-63 over the window
+//   column_record_global            WorldManager.cs:543-559
+//   cell_at_global                  WorldManager.cs:569-598
+//   feature_at, feature_write       FloraPlacer.PlaceTreesGlobal (:137-254) as one descriptor per column and its write set
+//   world_cell_before, world_cell, tree_any_leaves   the serial placement as a gather
 #pragma once
 #include "ycge_math.h"
 
@@ -409,6 +415,223 @@ YCGE_HD int tree_radius(const Tree &T, int dy)                                //
     return T.canopy_r - (dy == 2 ? 1 : 0);
 }
 YCGE_HD bool tree_may_replace(int mat) { return mat == kAir || mat == kTallGrass; }          // :76, :101
+
+// ================================================================================================================ the whole-world pregen
+// WorldManager.GenerateAndSaveWorld over a window of nx x nz columns whose column (x, z) is block (ox + x, oz + z) of the world in every
+// noise, hash and strata call; every clamp and bound is the window's.  ox = oz = 0 is the reference.  Fields are indexed x * nz + z.
+struct Window {
+    int nx, nz;          // ChunksX * ChunkSize, ChunksZ * ChunkSize
+    int ox, oz;
+};
+constexpr float kRiverBankSand = 1.5f;          // IslandSettings.cs:54
+constexpr int kFeatReach = 3;                   // a feature writes at most 3 columns from its root (a broadleaf canopy of radius 3)
+
+// RiverNetworkGlobal.cs:17-40 - as d8_direction, but a neighbour outside the window is skipped (:29)
+YCGE_HD int d8_global(const int *ground, int nx, int nz, int x, int z)
+{
+    const int h0 = ground[x * nz + z];
+    int best_dx = 0, best_dz = 0, best_drop = 0;
+    for (int oz = -1; oz <= 1; oz++)
+        for (int ox = -1; ox <= 1; ox++) {
+            if (ox == 0 && oz == 0) continue;
+            const int x2 = x + ox, z2 = z + oz;
+            if (x2 < 0 || x2 >= nx || z2 < 0 || z2 >= nz) continue;
+            const int drop = h0 - ground[x2 * nz + z2];
+            if (drop > best_drop) { best_drop = drop; best_dx = ox; best_dz = oz; }
+        }
+    return (best_dx + 1) * 3 + (best_dz + 1);
+}
+// RiverNetworkGlobal.cs:42-63.  The argument of river_accum carries over: cells are visited by height ASCENDING, a cell drains into a
+// STRICTLY lower cell (bestDrop > 0), which the order has already passed, so when a cell is visited nothing has reached it yet: a is 0,
+// is raised to 1 (:55), and every draining cell adds exactly 1 to its target.  Array.Sort's order among equal heights cannot matter (equal
+// cells never drain into each other).  Unlike the per-chunk pass, a cell with no lower neighbour adds nothing (:58), and a D8 target is in
+// the window by construction.  accum is therefore the number of neighbours whose D8 points at the cell: at most 8, far from the
+// threshold of 50 - nothing is ever carved, and the river surface is the sea everywhere.
+YCGE_HD float river_accum_global(const uint8_t *dir, int nx, int nz, int x, int z)
+{
+    int n = 0;
+    for (int ox = -1; ox <= 1; ox++)
+        for (int oz = -1; oz <= 1; oz++) {
+            if (ox == 0 && oz == 0) continue;
+            const int x2 = x + ox, z2 = z + oz;
+            if (x2 < 0 || x2 >= nx || z2 < 0 || z2 >= nz) continue;
+            if (dir[x2 * nz + z2] == (1 - ox) * 3 + (1 - oz)) n++;
+        }
+    return (float)n;
+}
+// RiverNetworkGlobal.cs:65-83 with WorldManager.cs:536 is river_carve: Math.Max(0, ground - floor(carve)) is ground where floor(carve) is 0.
+
+// WorldManager.cs:543-559 for column (x, z).  `carved`: the ground after the river pass.
+YCGE_HD ColRec column_record_global(const int *carved, const Window &N, int x, int z, int river_water, const World &W)
+{
+    const int nx = N.nx, nz = N.nz;
+    const int x0 = x - 1 > 0 ? x - 1 : 0, x1 = x + 1 < nx - 1 ? x + 1 : nx - 1;          // clamped at the window's edges, :547-548
+    const int z0 = z - 1 > 0 ? z - 1 : 0, z1 = z + 1 < nz - 1 ? z + 1 : nz - 1;
+    const float dx = (float)(carved[x1 * nz + z] - carved[x0 * nz + z]) * 0.5f;
+    const float dz = (float)(carved[x * nz + z1] - carved[x * nz + z0]) * 0.5f;
+    const float g = cs_sqrt(dx * dx + dz * dz);
+    const int gx = N.ox + x, gz = N.oz + z;
+    ColRec R;
+    R.slope = clamp01(g / kSlopeNormalize);
+    R.ground = carved[x * nz + z];
+    int biome = biome_evaluate(gx, gz, R.ground, W.sea, W);
+    const int inland = local_water_y(gx, gz, W, R.ground, R.slope);
+    R.water = inland > river_water ? inland : river_water;
+    if (R.water > W.sea && R.ground <= R.water) biome = kLakes;
+    R.biome_rock = biome | (rock_verdict(gx, gz, W) << 8);
+    return R;
+}
+// WorldManager.cs:569-598, one cell: cell_at with the bank rule of :580, an int compared with 3.5f
+YCGE_HD void cell_at_global(const ColRec &R, int gy, const World &W, int *mat, int *meta)
+{
+    const int gY = R.ground, wY = R.water, biome = R.biome_rock & 0xff;
+    *meta = 0;
+    if (gy > gY) *mat = gy <= wY ? kWater : kAir;
+    else if (gy == gY) {
+        if (wY > W.sea && (float)(wY - gY) <= (float)kBeachBuffer + kRiverBankSand) *mat = kSand;
+        else *mat = choose_surface_block(biome, gY, W.sea, W.snow, R.slope);
+    }
+    else if (gy >= gY - kTerrainDirtDepth) *mat = choose_subsurface_block(biome, gy, gY, W.sea);
+    else { *mat = kStone; *meta = rock_meta(R.biome_rock >> 8, gy); }
+}
+
+// ---- FloraPlacer.PlaceTreesGlobal as data.  Forest and Desert exclude each other, so a column roots at most one feature:
+//   bits 0-1   kind: 0 none, 1 tree, 2 cactus, 3 rock pile
+//   tree:      bit 2 conifer, bits 3-7 trunkH after the clip at the world's top (:168-169; <= 13), bits 8-9 canopyR
+//   cactus:    bits 3-5 height (2..5)
+// A feature stands on its column's ground (trunkBase = gY + 1), which the column's record holds.
+enum : uint32_t { kFeatNone = 0, kFeatTree = 1, kFeatCactus = 2, kFeatRock = 3 };
+YCGE_HD uint32_t feature_at(const ColRec &R, int gx, int gz, const World &W)
+{
+    const int gY = R.ground, wY = R.water, b = R.biome_rock & 0xff, ny = W.height;
+    if (b == kForest) {          // :150-169 (density is 0 for every other biome; no slope test here)
+        if (gY <= wY || gY >= W.snow - 2) return kFeatNone;
+        const uint32_t h = flora_hash(gx, gz, W.seed + 90001);
+        const float r = (float)(h & 0xFFFFu) / 65535.0f;
+        if (r > 0.03f) return kFeatNone;
+        const bool conifer = ((h >> 16) & 3u) == 0u;
+        const int trunk_base = gY + 1;
+        int trunk_h = conifer ? 6 + (int)((h >> 2) & 7u) : 4 + (int)((h >> 3) & 5u);
+        const int canopy_r = conifer ? 2 : 2 + (int)((h >> 6) & 1u);
+        if (trunk_base + trunk_h + 2 >= ny) trunk_h = ny - trunk_base - 2 > 3 ? ny - trunk_base - 2 : 3;
+        return kFeatTree | (conifer ? 4u : 0u) | ((uint32_t)trunk_h << 3) | ((uint32_t)canopy_r << 8);
+    }
+    if (b == kDesert) {          // :216-225
+        if (gY <= wY) return kFeatNone;
+        if (R.slope > 0.25f) return kFeatNone;
+        const uint32_t ux = (uint32_t)gx, uz = (uint32_t)gz;          // (C# int products wrap; so do these)
+        const uint32_t h = flora_hash((int)((ux * 73856093u) ^ (uz * 19349663u)), (int)((uz * 83492791u) ^ (ux * 297121507u)), W.seed + 1234567);
+        const float r = (float)(h & 0xFFFFu) / 65535.0f;
+        if (r < 0.70f) return kFeatNone;
+        if (r < 0.85f) return kFeatCactus | ((2u + ((h >> 16) & 3u)) << 3);
+        return kFeatRock;
+    }
+    return kFeatNone;
+}
+YCGE_HD int feat_kind(uint32_t d) { return (int)(d & 3u); }
+YCGE_HD int feat_trunk_h(uint32_t d) { return (int)((d >> 3) & 31u); }
+YCGE_HD int feat_cactus_h(uint32_t d) { return (int)((d >> 3) & 7u); }
+YCGE_HD Tree feat_tree(uint32_t d, int gY)          // (lx, lz unused; canopy_base as :178)
+{
+    Tree T;
+    T.lx = T.lz = 0;
+    T.conifer = (d >> 2) & 1u; T.trunk_h = feat_trunk_h(d); T.canopy_r = (int)((d >> 8) & 3u);
+    T.trunk_base = gY + 1;
+    T.canopy_base = T.trunk_base + T.trunk_h - (T.conifer ? 2 : 1);
+    return T;
+}
+// the highest y a feature may write (trunk top and canopy top; a crown lies at the trunk top), for the fill's early out
+YCGE_HD int feat_top(uint32_t d, int gY)
+{
+    switch (feat_kind(d)) {
+    case kFeatTree: return feat_tree(d, gY).canopy_base + 2;
+    case kFeatCactus: return gY + feat_cactus_h(d);
+    case kFeatRock: return gY + 1;
+    default: return gY;
+    }
+}
+// One feature's turn at the cell (dx, y, dz) from its root, whose material so far is *mat: trunk, then canopy, then the fallback crown
+// (:171-211), or the cactus (:229-234), or the rock pile (:239-250), each with its own rule for what it may replace.  The cell lies in
+// the window and below the world's top, so the x2 / z2 / y bounds of the C# hold (trunkBase >= 1: y < 0 never happens; the trunk's and
+// the cactus' `break` at the top ends a loop whose later y are higher still).
+YCGE_HD void feature_write(uint32_t d, int gY, bool fallback, int dx, int y, int dz, int *mat, int *meta)
+{
+    const int adx = dx < 0 ? -dx : dx, adz = dz < 0 ? -dz : dz;
+    switch (feat_kind(d)) {
+    case kFeatTree: {
+        const Tree T = feat_tree(d, gY);
+        if (adx == 0 && adz == 0 && y >= T.trunk_base && y < T.trunk_base + T.trunk_h && tree_may_replace(*mat)) { *mat = kWood; *meta = 0; }
+        const int dy = y - T.canopy_base;
+        if (dy >= tree_dy_min(T) && dy <= 2) {
+            const int radius = tree_radius(T, dy);
+            if (adx <= radius && adz <= radius && tree_may_replace(*mat)) { *mat = kLeaves; *meta = 0; }
+        }
+        if (fallback && y == T.trunk_base + T.trunk_h - 1 && adx <= 1 && adz <= 1 && *mat == kAir) { *mat = kLeaves; *meta = 0; }
+        break;
+    }
+    case kFeatCactus:
+        if (adx == 0 && adz == 0 && y > gY && y <= gY + feat_cactus_h(d) && *mat == kAir) { *mat = kWood; *meta = 0; }
+        break;
+    case kFeatRock:
+        if (y == gY + 1 && adx + adz <= 1 && *mat == kAir) { *mat = kStone; *meta = 1; }
+        break;
+    default: break;
+    }
+}
+// The cell (x, y, z) as PlaceTreesGlobal has left it just BEFORE the canopy of the tree rooted at (lim_x, lim_z): the base cell, then the
+// features rooted within kFeatReach columns in the serial order - x-row by x-row, a row's trees in z order, then that row's desert
+// features in z order - up to and excluding that tree (its own row's desert pass comes after it).  Every write leaves the cell neither Air
+// nor TallGrass, which no feature replaces, so the scan ends at the first one.  `fallback`: one flag per column, read for trees only.
+YCGE_HD void world_cell_before(const ColRec *rec, const uint32_t *feat, const uint8_t *fallback, const Window &N, const World &W, int x, int y, int z,
+                               int lim_x, int lim_z, int *mat, int *meta)
+{
+    cell_at_global(rec[x * N.nz + z], y, W, mat, meta);
+    if (!tree_may_replace(*mat)) return;
+    const int fx0 = x - kFeatReach > 0 ? x - kFeatReach : 0, fx_hi = x + kFeatReach < N.nx - 1 ? x + kFeatReach : N.nx - 1, fx1 = fx_hi < lim_x ? fx_hi : lim_x;
+    const int fz0 = z - kFeatReach > 0 ? z - kFeatReach : 0, fz1 = z + kFeatReach < N.nz - 1 ? z + kFeatReach : N.nz - 1;
+    for (int fx = fx0; fx <= fx1; fx++) {
+        for (int pass = 0; pass < 2; pass++) {          // 0: the row's trees, 1: its desert features
+            if (pass == 1 && fx == lim_x) break;
+            for (int fz = fz0; fz <= fz1; fz++) {
+                if (pass == 0 && fx == lim_x && fz >= lim_z) break;
+                const uint32_t d = feat[fx * N.nz + fz];
+                if (d == kFeatNone || (feat_kind(d) == kFeatTree) != (pass == 0)) continue;
+                feature_write(d, rec[fx * N.nz + fz].ground, fallback[fx * N.nz + fz] != 0, x - fx, y, z - fz, mat, meta);
+                if (!tree_may_replace(*mat)) return;
+            }
+        }
+    }
+}
+// the finished cell: no limit
+YCGE_HD void world_cell(const ColRec *rec, const uint32_t *feat, const uint8_t *fallback, const Window &N, const World &W, int x, int y, int z, int *mat, int *meta)
+{
+    world_cell_before(rec, feat, fallback, N, W, x, y, z, 0x7fffffff, 0, mat, meta);
+}
+// anyLeaves of the tree rooted at (x, z) (:179-195): did its canopy loop find a cell it could take?  The cell as the earlier features and
+// the tree's own trunk left it.  Depends on the fallback flags of EARLIER trees only.
+YCGE_HD bool tree_any_leaves(const ColRec *rec, const uint32_t *feat, const uint8_t *fallback, const Window &N, const World &W, int x, int z)
+{
+    const uint32_t d = feat[x * N.nz + z];
+    const Tree T = feat_tree(d, rec[x * N.nz + z].ground);
+    for (int dy = tree_dy_min(T); dy <= 2; dy++) {
+        const int y = T.canopy_base + dy;
+        if (y < 0 || y >= W.height) continue;
+        const int radius = tree_radius(T, dy);
+        for (int rx = -radius; rx <= radius; rx++) {
+            const int x2 = x + rx;
+            if (x2 < 0 || x2 >= N.nx) continue;
+            for (int rz = -radius; rz <= radius; rz++) {
+                const int z2 = z + rz;
+                if (z2 < 0 || z2 >= N.nz) continue;
+                int mat, meta;
+                world_cell_before(rec, feat, fallback, N, W, x2, y, z2, x, z, &mat, &meta);
+                if (rx == 0 && rz == 0 && y >= T.trunk_base && y < T.trunk_base + T.trunk_h && tree_may_replace(mat)) mat = kWood;
+                if (tree_may_replace(mat)) return true;
+            }
+        }
+    }
+    return false;
+}
 
 }  // namespace wg
 }  // namespace ycge

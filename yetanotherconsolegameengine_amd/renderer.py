@@ -176,6 +176,32 @@ class RaytraceRenderer:
         idx = [int(out[k]) for k in range(n)]
         return (idx, cells) if want_cells else idx
 
+    def GenerateWorld(self, world: abi.World, chunks_x: int, chunks_z: int, proto: abi.Grid, origin=(0, 0), want_cells: bool = False):
+        """ycge_scene_generate_world: WorldManager.GenerateAndSaveWorld for a window of chunks_x x world.chunks_y x chunks_z chunks whose column
+        (0, 0) is block `origin` - the reference's pregenerated world at origin (0, 0) - made on the device and attached like AttachGrids'
+        grids, chunk (cx, cy, cz) at world_min + c * S * voxel_size.  Returns the device indices as int32 [chunks_x, chunks_y, chunks_z] (-1: a
+        chunk of nothing but Air, no slot) and, with want_cells, the whole world's cells [nx, ny, nz, 2] int32 (the VG01 payload)."""
+        S, cy = int(world.chunk_size), int(world.chunks_y)
+        n = chunks_x * cy * chunks_z
+        out = np.full(max(1, n), -7, np.int32)
+        cells = np.zeros((chunks_x * S, cy * S, chunks_z * S, 2), np.int32) if want_cells else None
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_generate_world(self.ctx, C.byref(world), chunks_x, chunks_z, int(origin[0]), int(origin[1]), C.byref(proto),
+                                              out.ctypes.data_as(C.POINTER(C.c_int32)), cells.ctypes.data_as(C.POINTER(C.c_int32)) if want_cells else None)
+        self.stream_call_s["generate_world"] = time.perf_counter() - t0
+        self._check(rc)
+        idx = out[:n].reshape(chunks_x, cy, chunks_z)
+        return (idx, cells) if want_cells else idx
+
+    def worldpregen_stats(self) -> dict:
+        """The last GenerateWorld on the root device: anyLeaves passes (the last flips nothing) and, in microseconds, the field kernels, the
+        anyLeaves pass loop (wall time: a launch, a stream synchronise and a 4-byte read-back per pass), the occupancy kernel with its read-back, the fill kernels."""
+        out = (C.c_int64 * 5)()
+        fn = self.L.ycge_debug_worldpregen_stats
+        fn.restype, fn.argtypes = abi.WORLDGEN_HOOK_PROTOTYPES["ycge_debug_worldpregen_stats"]
+        self._check(fn(self.ctx, out))
+        return dict(zip(("any_leaves_passes", "fields_us", "any_leaves_us", "occupied_us", "fill_us"), (int(v) for v in out)))
+
     def worldgen_stats(self) -> dict:
         out = (C.c_int64 * 4)()
         self.L.ycge_debug_worldgen_stats.restype, self.L.ycge_debug_worldgen_stats.argtypes = abi.WORLDGEN_HOOK_PROTOTYPES["ycge_debug_worldgen_stats"]

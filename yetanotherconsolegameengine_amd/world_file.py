@@ -59,6 +59,20 @@ def read_vg01(path) -> np.ndarray:
     return np.frombuffer(data, dtype="<i4").reshape(nx, ny, nz, 2).copy()
 
 
+def pregen_world(lib, world, chunks_x: int, chunks_z: int, path=None, origin=(0, 0)) -> np.ndarray:
+    """GenerateAndSaveWorld (WorldManager.cs:510-631) by the library's host generator (ycge_worldgen_world_cells; `lib` the loaded
+    library, `world` an abi.World): the cells [nx, ny, nz, 2] of the window, written as a VG01 file when `path` is given."""
+    import ctypes as C
+    S = int(world.chunk_size)
+    cells = np.zeros((chunks_x * S, int(world.chunks_y) * S, chunks_z * S, 2), np.int32)
+    rc = lib.ycge_worldgen_world_cells(C.byref(world), chunks_x, chunks_z, int(origin[0]), int(origin[1]), cells.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise ValueError(f"ycge_worldgen_world_cells refused the window (status {rc})")
+    if path is not None:
+        write_vg01(path, cells)
+    return cells
+
+
 def center_column(center, world_min, voxel_size, chunk_size: int) -> Tuple[int, int]:
     """(cxCenter, czCenter) of BuildDesiredSet / LoadChunksAround (WorldManager.cs:309-312, 376-379), in binary32 as there."""
     scale_x = f32(f32(voxel_size[0]) * f32(chunk_size))
