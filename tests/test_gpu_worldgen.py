@@ -1,4 +1,4 @@
-"""-m gpu: ycge_scene_generate_grids (csrc/ycge_worldgen.hip behind csrc/ycge_grid_encode.cpp) against the host generator
+"""-m gpu: ycge_scene_generate_grids (csrc/ycge_worldgen_scene.cpp over csrc/ycge_worldgen.hip) against the host generator
 (ycge_worldgen_chunk_cells) - raw cells byte for byte, indices, and frames and queries bit for bit against a twin context that attaches the
 host generator's cells with ycge_scene_attach_grids.  The chunk set is tests/test_worldgen_cpu.py's, which asserts what it covers."""
 import ctypes as C
@@ -223,3 +223,106 @@ def test_the_host_knob_gives_the_same_cells_and_frames(product_lib, host_set):
         for w, (p, q) in enumerate(zip(x, y)):
             _same(np.asarray(p), np.asarray(q), f"frame / query {f}, buffer {w}")
     H.close(); D.close()
+
+
+# ---- chunks of 8 (seed 3): three that hold something and one of nothing but Air, the paths of the export the chosen set does not take
+SMALL = dict(size=8, chunks_y=8, seed=3)
+SMALL_SOLID = [(100, 2, -100), (100, 3, -100), (0, 1, 0)]
+SMALL_KEYS = SMALL_SOLID + [(-56, 7, 0)]          # (this world's ground lies in its top chunks: few columns leave cy = 7 empty)
+BIG_PAIRS = ALL_PAIRS + [(100 + i, 0) for i in range(280)]          # 304 entries: more than k_grid_encode takes, every grid goes to the host encoder
+
+
+def _two_frames_and_queries(r, idx, pos):
+    r._check(r.L.ycge_scene_update_objects(r.ctx, _prims(idx), len(idx)))
+    out = []
+    r.SetCamera(pos, 0.0, -1.2)
+    for f in range(2):
+        r.TryFlipAndBlit(want_sdr=True)
+        out.append([r.read(which) for which in FRAME_BUFFERS])
+    rng = np.random.default_rng(9)
+    o = np.tile(np.asarray(pos, np.float32), (256, 1))
+    d = rng.normal(size=(256, 3)).astype(np.float32); d[:, 1] = -np.abs(d[:, 1]) - 0.3
+    out.append(list(r.Hit(o, d)) + [r.Occluded(o, d)])
+    return out
+
+
+SMALL_POSE = (WORLD_MIN[0] + 100 * 8 + 4.0, 34.0, WORLD_MIN[2] - 100 * 8 + 4.0)          # just above chunk column (100, -100)
+
+
+def test_a_lookup_table_too_large_for_the_kernel_takes_the_host_encoder(product_lib):
+    """n_lookup > YCGE_ENC_MAX_LOOKUP: the chunks that hold something are made by the host generator and encoded by the host encoder, the
+    all-Air one is still made on the device; cells, indices, counters, and frames and queries against an attach of the host's cells."""
+    w = _world(**SMALL)
+    host = _host_cells(product_lib, w, SMALL_KEYS)
+    solid = [bool((c[..., 0] != 0).any()) for c in host]
+    assert solid == [True, True, True, False]
+    n_solid, n_air = 3, 1
+    proto, keep = _proto(BIG_PAIRS)
+    A = RaytraceRenderer(_anchor(), 96, 27, 60.0)
+    B = RaytraceRenderer(_anchor(), 96, 27, 60.0)
+    idx, cells = A.GenerateGrids(w, SMALL_KEYS, proto, want_cells=True)
+    assert cells.tobytes() == host.tobytes()
+    assert idx == [0, 1, 2, -1]
+    st, wg = A.grid_pool_stats(), A.worldgen_stats()
+    assert st["host_encodes"] == n_solid and st["device_encodes"] == 0 and st["resident"] == n_solid
+    assert wg["host_chunks"] == n_solid and wg["device_chunks"] == n_air
+    ib = _attach_host(B, product_lib, w, SMALL_SOLID, proto)
+    assert ib == idx[:3] and B.grid_pool_stats()["host_encodes"] == n_solid
+    fa, fb = _two_frames_and_queries(A, idx[:3], SMALL_POSE), _two_frames_and_queries(B, ib, SMALL_POSE)
+    for f, (x, y) in enumerate(zip(fa, fb)):
+        for k, (p, q) in enumerate(zip(x, y)):
+            _same(np.asarray(p), np.asarray(q), f"frame / query {f}, buffer {k}")
+    assert (np.asarray(fa[2][1])[:, 0] >= 0).any() and np.asarray(fa[2][2]).any()          # (the downward rays do meet the chunks)
+    A.close(); B.close()
+
+
+def test_two_devices_give_the_indices_and_frames_of_one(product_lib):
+    """A context that drives two devices (both own tiles at 160 x 90): every device gets the columns, the fill and the encode; a peer
+    context handed to the export is refused."""
+    w = _world(**SMALL)
+    proto, keep = _proto(ALL_PAIRS)
+
+    def run(devices):
+        r = RaytraceRenderer(_anchor(), 160, 90, devices=devices)
+        idx = r.GenerateGrids(w, SMALL_KEYS, proto)
+        out = _two_frames_and_queries(r, idx[:3], SMALL_POSE)[:2]
+        r.close()
+        return idx, out
+
+    (i1, one), (i2, two) = run(None), run([0, 0])
+    assert i1 == i2 == [0, 1, 2, -1]
+    for f, (x, y) in enumerate(zip(one, two)):
+        for k, (p, q) in enumerate(zip(x, y)):
+            _same(np.asarray(p), np.asarray(q), f"two devices: frame {f}, buffer {k}")
+    r = RaytraceRenderer(_anchor(), 160, 90, devices=[0, 0])
+    peer = C.c_void_p(r.L.ycge_debug_peer_context(r.ctx, 0))
+    assert peer.value
+    before = r.grid_pool_stats()
+    karr = np.ascontiguousarray(np.asarray(SMALL_KEYS, np.int32))
+    out = (C.c_int32 * 4)(-7, -7, -7, -7)
+    assert r.L.ycge_scene_generate_grids(peer, C.byref(w), karr.ctypes.data_as(C.POINTER(C.c_int32)), 4, C.byref(proto), out, None) == abi.YCGE_ERR_INVALID_ARG
+    assert b"driven by their root" in r.L.ycge_last_error(peer)
+    assert list(out) == [-7] * 4 and r.grid_pool_stats() == before
+    r.close()
+
+
+def test_air_chunks_beside_solid_ones_in_two_groups(product_lib):
+    """A key list that is mostly Air with want_cells: the Air chunks' cells are made and found empty in launches of their own, the two
+    solid chunks fall into two encode groups (YCGE_ENC_GROUP_BYTES below two chunks' raw cells)."""
+    w = _world(**SMALL)
+    keys = [(-56, 7, 0), (-56, 7, 1), (100, 2, -100), (-55, 7, 2), (-57, 7, 5), (-58, 7, -4), (0, 1, 0), (-55, 7, 5), (-56, 7, -4)]
+    host = _host_cells(product_lib, w, keys)
+    solid = [bool((c[..., 0] != 0).any()) for c in host]
+    assert [k for k, s in zip(keys, solid) if s] == [(100, 2, -100), (0, 1, 0)]
+    os.environ["YCGE_ENC_GROUP_BYTES"] = str(8 * 8 * 8 * 8 + 1000)
+    try:
+        r = RaytraceRenderer(_anchor(), 32, 16)          # (knobs are read when the context is made)
+    finally:
+        del os.environ["YCGE_ENC_GROUP_BYTES"]
+    proto, keep = _proto(ALL_PAIRS)
+    idx, cells = r.GenerateGrids(w, keys, proto, want_cells=True)
+    assert cells.tobytes() == host.tobytes()
+    assert idx == [-1, -1, 0, -1, -1, -1, 1, -1, -1]
+    st, wg = r.grid_pool_stats(), r.worldgen_stats()
+    assert st["device_encodes"] == 2 and wg["device_chunks"] == len(keys) and wg["host_chunks"] == 0
+    r.close()

@@ -1,4 +1,4 @@
-"""-m gpu: ycge_scene_generate_world (csrc/ycge_worldpregen.hip behind csrc/ycge_grid_encode.cpp) against the host generator
+"""-m gpu: ycge_scene_generate_world (csrc/ycge_worldgen_scene.cpp over csrc/ycge_worldpregen.hip) against the host generator
 (ycge_worldgen_world_cells) - the whole world's cells byte for byte, the indices, and frames and queries bit for bit against a twin
 context that attaches the host generator's chunks with ycge_scene_attach_grids.  The windows are tests/test_worldpregen_cpu.py's, which
 asserts what they cover and holds the host generator to the restatement."""
@@ -219,3 +219,59 @@ def test_the_host_knob_gives_the_same_cells_and_frames(product_lib):
     fd = _frames_and_queries(D, [int(i) for i in id_.ravel() if i >= 0])
     _all_same(fh, fd, "host knob against device")
     H.close(); D.close()
+
+
+def test_a_lookup_table_too_large_for_the_kernel_takes_the_host_world(product_lib):
+    """n_lookup > YCGE_ENC_MAX_LOOKUP: the whole world is made by the host generator and every occupied chunk goes through the host
+    encoder; cells, indices, counters, and frames and queries against an attach of the host's chunks."""
+    name = "small"
+    S, cy, cx, cz, seed, ox, oz = WINDOWS[name]
+    world, host = _world(name), host_cells(product_lib, name)
+    proto, keep = _proto(ALL_PAIRS + [(100 + i, 0) for i in range(280)])
+    A = RaytraceRenderer(_anchor(), 96, 27, 60.0)
+    B = RaytraceRenderer(_anchor(), 96, 27, 60.0)
+    idx, cells = A.GenerateWorld(world, cx, cz, proto, origin=(ox, oz), want_cells=True)
+    assert cells.shape == host.shape and cells.tobytes() == host.tobytes()
+    want = expected_indices(host, S)
+    assert (idx == want).all()
+    n_occ = int((want >= 0).sum())
+    st, wg = A.grid_pool_stats(), A.worldgen_stats()
+    assert st["host_encodes"] == n_occ and st["device_encodes"] == 0 and st["resident"] == n_occ
+    assert wg["host_chunks"] == cx * cy * cz and wg["device_chunks"] == 0
+    ia = [int(i) for i in idx.ravel() if i >= 0]
+    ib = _attach_host(B, world, host, S, proto)
+    assert ia == ib
+    fa, fb = _frames_and_queries(A, ia), _frames_and_queries(B, ib)
+    _all_same(fa, fb, "generated against attached")
+    assert (np.asarray(fa[2][1])[:, 0] >= 0).any() and np.asarray(fa[2][2]).any()          # (the downward rays do meet the chunks)
+    A.close(); B.close()
+
+
+def test_two_devices_give_the_indices_and_frames_of_one(product_lib):
+    """A context that drives two devices (both own tiles at 160 x 90) on the window whose anyLeaves passes number two at least: the peer
+    repeats the root's passes without reading anything back.  A peer context handed to the export is refused."""
+    name = "fallback"
+    S, cy, cx, cz, seed, ox, oz = WINDOWS[name]
+    world = _world(name)
+    proto, keep = _proto(ALL_PAIRS)
+
+    def run(devices):
+        r = RaytraceRenderer(_anchor(), 160, 90, devices=devices)
+        idx = r.GenerateWorld(world, cx, cz, proto, origin=(ox, oz))
+        assert r.worldpregen_stats()["any_leaves_passes"] >= 2
+        out = _frames_and_queries(r, [int(i) for i in idx.ravel() if i >= 0])[:2]
+        r.close()
+        return idx, out
+
+    (i1, one), (i2, two) = run(None), run([0, 0])
+    assert (i1 == i2).all() and (i1 == expected_indices(host_cells(product_lib, name), S)).all()
+    _all_same(one, two, "two devices against one")
+    r = RaytraceRenderer(_anchor(), 160, 90, devices=[0, 0])
+    peer = C.c_void_p(r.L.ycge_debug_peer_context(r.ctx, 0))
+    assert peer.value
+    before = r.grid_pool_stats()
+    out = np.full(cx * cy * cz, -7, np.int32)
+    assert r.L.ycge_scene_generate_world(peer, C.byref(world), cx, cz, ox, oz, C.byref(proto), out.ctypes.data_as(C.POINTER(C.c_int32)), None) == abi.YCGE_ERR_INVALID_ARG
+    assert b"driven by their root" in r.L.ycge_last_error(peer)
+    assert (out == -7).all() and r.grid_pool_stats() == before
+    r.close()

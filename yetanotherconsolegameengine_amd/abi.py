@@ -254,7 +254,7 @@ HOOK_PROTOTYPES = {
     "ycge_debug_peer_context": (C.c_void_p, [C.c_void_p, C.c_int32]),
     "ycge_debug_live_resources": (C.c_int, [C.POINTER(C.c_int64)]),
 }
-# test / profiling hook of chunk generation (csrc/ycge_grid_encode.cpp), bound where it is used (RaytraceRenderer.worldgen_stats)
+# test / profiling hook of chunk generation (csrc/ycge_worldgen_scene.cpp), bound where it is used (RaytraceRenderer.worldgen_stats)
 WORLDGEN_HOOK_PROTOTYPES = {
     "ycge_debug_worldgen_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ycge_debug_worldpregen_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

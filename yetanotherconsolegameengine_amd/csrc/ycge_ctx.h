@@ -4,7 +4,7 @@
 //   ycge_frame.cpp     frame orchestration (TryFlipAndBlit steps 1-5 and 9), frames in flight, the slab form of the tiled frame
 //   ycge_post_host.cpp the post stage (steps 6-8) and its schedules
 //   ycge_resident.cpp  the tile-resident multi-GPU form, its batched launches and emulation loop; read-backs (ycge_read_buffer / _accel)
-//   ycge_query.cpp, ycge_chexel.cpp, ycge_ansi.cpp, ycge_grid_encode.cpp   scene queries, chexel colours, the ANSI stream, streamed grids
+//   ycge_query.cpp, ycge_chexel.cpp, ycge_ansi.cpp, ycge_grid_encode.cpp, ycge_worldgen_scene.cpp   scene queries, chexel colours, the ANSI stream, streamed grids, generated chunks
 //   ycge_accel.cpp     the bit-faithful BVH builders
 // Every GPU resource is held through an owner of ycge_own.h: members free themselves, ycge_ctx::~ycge_ctx orders only what has an order.
 // All device work is in the .hip files; there is no CPU implementation of any per-pixel stage.
@@ -557,7 +557,7 @@ struct ycge_ctx {
     // device; encoded bytes that wait for the arena to grow
     PinnedBuf enc_stage;
     DevBuf<uint8_t> d_enc_in, d_enc_out;
-    // ycge_scene_generate_grids: the column records of the batch's distinct (cx, cz) on this device, then their keys and tops
+    // ycge_scene_generate_grids (ycge_worldgen_scene.cpp): the column records of the batch's distinct (cx, cz) on this device, then their keys and tops
     DevBuf<uint8_t> d_wg_cols;
     int64_t worldgen_device_chunks = 0, worldgen_host_chunks = 0;          // since the context was made (root)
     int worldpregen_last_passes = 0;                                      // ycge_scene_generate_world's last call on the root: anyLeaves passes,
@@ -671,6 +671,12 @@ int join_async(ycge_ctx *c);
 int copy_out(ycge_ctx *c, void *dst, const void *src, size_t bytes);
 int fill_stats(ycge_ctx *c, ycge_frame_stats *st, const FrameState &fs, bool did_reset, bool have_taa, double wall_ms);
 int quiesce(ycge_ctx *c);
+inline std::vector<ycge_ctx *> contexts_of(ycge_ctx *c) { std::vector<ycge_ctx *> v{c}; v.insert(v.end(), c->peers.begin(), c->peers.end()); return v; }          // root, then peers
+inline int quiesce_all(ycge_ctx *c) { for (ycge_ctx *x : contexts_of(c)) { const int rc = quiesce(x); if (rc != YCGE_OK) return rc; } return YCGE_OK; }
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+inline double us_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+// the calling thread's current device goes back to the root's on every way out (a failed step on a peer's device included)
+struct DeviceGuard { int device; explicit DeviceGuard(int d) : device(d) {} ~DeviceGuard() { (void)hipSetDevice(device); } };
 void release_resident(ycge_ctx *c);
 void snapshot_frame(ycge_ctx *c, FrameState &fs);
 void schedule_policy(const ycge_ctx *c, uint32_t &policy, uint32_t &split_top, int resident_ring = 0, bool batched = false);
@@ -686,6 +692,21 @@ std::array<float, 6> grid_world_bounds(const ycge_grid &g);
 int encode_grid_host(ycge_ctx *c, const ycge_grid &g, int gi, int n_materials, const GGrid &G, uint8_t *cells, std::vector<int32_t> &lut, int lo[3], int hi[3],
                      uint64_t &brick_mask);                                                  // the host encoder (first-seen codes)
 void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_bytes, size_t lut_entries);   // ycge_grid_encode.cpp: after an upload
+// Where the raw cells of an attach's grids come from (attach_grids_from, ycge_grid_encode.cpp: the body of ycge_scene_attach_grids for any source; arguments checked by the callers, n >= 1, all or
+// nothing).  Host-made cells are written into the staging of their group and go up with it; device-made cells are written on every device where k_grid_encode reads them: only descriptors and tables go up.
+struct CellSource {
+    bool on_device = false;          // the cells are made by fill(), not by write()
+    bool caller_cells = false;       // ycge_grid.cells are the cells, readable throughout the call (else: never read; a pair with no material is named when its group ends)
+    size_t group_max = SIZE_MAX;     // grids in one group
+    virtual ~CellSource() = default;
+    // the cells of grid k, 2 * nx * ny * nz int32 in ycge_grid.cells order: into its group's staging, or for the host encoder (a lookup table k_grid_encode does not take)
+    virtual int write(ycge_ctx *root, size_t k, const ycge_grid &g, int32_t *cells) = 0;
+    // device-made: the bytes of launch records the source wants on the device ahead of the cells of a group of m grids (at d_head), and the launch on x's
+    // stream that writes the cells of grid group[j] to d_cells[j].  x == root: waits, refuses what came out wrong and hands the cells to the caller if asked
+    virtual size_t head_bytes(size_t /* m */) const { return 0; }
+    virtual int fill(ycge_ctx * /* root */, ycge_ctx * /* x */, const std::vector<int> & /* group */, uint8_t * /* d_head */, const std::vector<int32_t *> & /* d_cells */) { return YCGE_OK; }
+};
+int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *out_grid_index, CellSource &src);
 int query_scene_changed(ycge_ctx *c);       // ycge_query.cpp: record scene_ev behind a scene upload / objects update
 int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second);   // ycge_chexel.cpp: run_post's encode behind the tonemap (a no-op unless a _chexels call asked)
 int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second);                      // ... and its copies behind the SDR read-back

@@ -1196,8 +1196,7 @@ try {
         const int vrc = validate_scene(s, m);
         if (vrc != YCGE_OK) return c->fail(vrc, "%s", m.c_str());
     }
-    int qrc = quiesce(c);
-    for (ycge_ctx *p : c->peers) if (qrc == YCGE_OK) qrc = quiesce(p);
+    const int qrc = quiesce_all(c);
     if (qrc != YCGE_OK) return qrc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->have_scene = false;
@@ -1475,8 +1474,7 @@ try {
     // against 105; config 5's 976: 559 against 354; 2 300: 687 against 1 533 - profiles/r02/f2_update_objects_timing.txt)
     bool on_device = !c->knobs.scene_bvh_host && n_prims >= 1 && n_prims >= c->knobs.scene_bvh_device_min && n_prims <= YCGE_BVH_DEV_MAX_ITEMS;
     if (!on_device) { rc = build_scene_tree_host(c, items, oh); if (rc != YCGE_OK) return rc; }
-    rc = quiesce(c);
-    for (ycge_ctx *p : c->peers) if (rc == YCGE_OK) rc = quiesce(p);
+    rc = quiesce_all(c);
     if (rc != YCGE_OK) return rc;
     c->have_scene = false;
     // after an attach or a detach the kernel instantiation follows the grids Scene.Objects refer to, as after an upload of the equivalent
@@ -1824,9 +1822,7 @@ int ycge_read_timed_steps(ycge_ctx *c, uint64_t *lane_steps)
 try {
     if (!c || !lane_steps) return YCGE_ERR_INVALID_ARG;
     unsigned long long total = 0;
-    std::vector<ycge_ctx *> all{c};
-    all.insert(all.end(), c->peers.begin(), c->peers.end());
-    for (ycge_ctx *d : all) {
+    for (ycge_ctx *d : contexts_of(c)) {
         std::vector<unsigned long long> v(YCGE_COUNTER_WORDS);
         if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
             copy_out(d, v.data(), d->counters.p, v.size() * sizeof(unsigned long long)) != YCGE_OK) { (void)hipSetDevice(c->device); return c->fail(YCGE_ERR_DEVICE, "timed-step read-back failed on device %d", d->device); }

@@ -10,10 +10,12 @@
 #include "ycge_worldgen.h"
 #include "ycge_worldgen_host.h"
 
+struct ycge_ctx;
 using namespace ycge;
 
 namespace ycge_host {
 
+int abi_catch(const ycge_ctx *c) noexcept;          // ycge_host.cpp: the exception barrier of the C-ABI (no context here: NULL)
 int worldgen_check(const ycge_world *w, const char **why)
 {
     if (!w) { *why = "null world"; return YCGE_ERR_INVALID_ARG; }
@@ -277,7 +279,8 @@ int world_cells_host(const ycge_world *world, int32_t chunks_x, int32_t chunks_z
 
 }  // namespace ycge_host
 
-extern "C" int ycge_worldgen_chunk_cells(const ycge_world *world, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t *any_solid_out)
+extern "C" {
+int ycge_worldgen_chunk_cells(const ycge_world *world, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t *any_solid_out)
 try {
     const char *why = nullptr;
     const int rc = ycge_host::worldgen_check(world, &why);
@@ -290,20 +293,19 @@ try {
     ycge_host::worldgen_fill_host(W, cols.data(), cx, cy, cz, cells_out, any_solid_out);
     return YCGE_OK;
 }
-catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
 
 // ---- test hooks (include/ycge_hooks.h): the restatement's pieces on a caller's inputs, host only
 // GenMath: hash_out[i] = FastHash(ix[i], 0, iz[i], seed); noise_out[i] = GradientNoise2D(x[i], z[i], seed)
-extern "C" int ycge_host_worldgen_noise(int32_t n, const int32_t *ix, const int32_t *iz, const float *x, const float *z, int32_t seed, uint32_t *hash_out, float *noise_out)
+int ycge_host_worldgen_noise(int32_t n, const int32_t *ix, const int32_t *iz, const float *x, const float *z, int32_t seed, uint32_t *hash_out, float *noise_out)
 try {
     if (n < 0 || (n > 0 && (!ix || !iz || !x || !z || !hash_out || !noise_out))) return YCGE_ERR_INVALID_ARG;
     for (int i = 0; i < n; i++) { hash_out[i] = wg::fast_hash(ix[i], 0, iz[i], seed); noise_out[i] = wg::gradient_noise2(x[i], z[i], seed); }
     return YCGE_OK;
 }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
 // TerrainNoise.HeightY at n points
-extern "C" int ycge_host_worldgen_height(const ycge_world *world, int32_t n, const int32_t *gx, const int32_t *gz, int32_t *height_out)
+int ycge_host_worldgen_height(const ycge_world *world, int32_t n, const int32_t *gx, const int32_t *gz, int32_t *height_out)
 try {
     const char *why = nullptr;
     if (ycge_host::worldgen_check(world, &why) != YCGE_OK || n < 0 || (n > 0 && (!gx || !gz || !height_out))) return YCGE_ERR_INVALID_ARG;
@@ -311,10 +313,10 @@ try {
     for (int i = 0; i < n; i++) height_out[i] = wg::height_y(gx[i], gz[i], W);
     return YCGE_OK;
 }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
 // RiverNetwork.ComputeForChunk on a caller's (size + 2)^2 height tile (index (lx + 1) * (size + 2) + (lz + 1)):
 // per chunk cell (index lx * size + lz) the D8 code, accum, carved ground, river surface
-extern "C" int ycge_host_worldgen_river(const int32_t *tile, int32_t size, int32_t sea, int32_t *dir_out, float *accum_out, int32_t *carved_out, int32_t *river_water_out)
+int ycge_host_worldgen_river(const int32_t *tile, int32_t size, int32_t sea, int32_t *dir_out, float *accum_out, int32_t *carved_out, int32_t *river_water_out)
 try {
     if (!tile || size < 1 || size > 64 || !dir_out || !accum_out || !carved_out || !river_water_out) return YCGE_ERR_INVALID_ARG;
     std::vector<uint8_t> dir((size_t)size * size);
@@ -328,18 +330,18 @@ try {
         }
     return YCGE_OK;
 }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
 // river_carve alone at a given accumulation (the formulas behind the threshold, which no chunk reaches)
-extern "C" int ycge_host_worldgen_carve(float accum, int32_t ground, int32_t sea, int32_t *carved_out, int32_t *river_water_out)
+int ycge_host_worldgen_carve(float accum, int32_t ground, int32_t sea, int32_t *carved_out, int32_t *river_water_out)
 try {
     if (!carved_out || !river_water_out) return YCGE_ERR_INVALID_ARG;
     *carved_out = wg::river_carve(accum, ground, sea, river_water_out);
     return YCGE_OK;
 }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
 
 // ---- GenerateAndSaveWorld
-extern "C" int ycge_worldgen_world_cells(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *cells_out)
+int ycge_worldgen_world_cells(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *cells_out)
 try {
     const char *why = nullptr;
     int rc = ycge_host::worldgen_check(world, &why);
@@ -348,12 +350,11 @@ try {
     if (!cells_out) return YCGE_ERR_INVALID_ARG;
     return ycge_host::world_cells_host(world, chunks_x, chunks_z, origin_bx, origin_bz, cells_out);
 }
-catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
 
 // test hook: the 2-D fields of a window from the host code, each nx * nz in x * nz + z order (NULL: skipped).  climate: BiomeMap's
 // dryness verdict alone (Forest or Desert, whatever the height); rock: StrataMap's noise verdict.
-extern "C" int ycge_host_worldgen_world_fields(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *ground0_out,
+int ycge_host_worldgen_world_fields(const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t *ground0_out,
                                                int32_t *ground_out, int32_t *dir_out, float *accum_out, float *slope_out, int32_t *biome_out, int32_t *water_out,
                                                uint32_t *feature_out, int32_t *climate_out, int32_t *rock_out)
 try {
@@ -380,11 +381,10 @@ try {
     }
     return YCGE_OK;
 }
-catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
 
 // test hook: RiverNetworkGlobal.Compute (and WorldManager.cs:536) on a caller's nx * nz heights: D8 code, accum, carved ground, river surface
-extern "C" int ycge_host_worldgen_river_global(const int32_t *ground, int32_t nx, int32_t nz, int32_t sea, int32_t *dir_out, float *accum_out, int32_t *carved_out,
+int ycge_host_worldgen_river_global(const int32_t *ground, int32_t nx, int32_t nz, int32_t sea, int32_t *dir_out, float *accum_out, int32_t *carved_out,
                                                int32_t *river_water_out)
 try {
     if (!ground || nx < 1 || nz < 1 || (int64_t)nx * nz > (1 << 24) || !dir_out || !accum_out || !carved_out || !river_water_out) return YCGE_ERR_INVALID_ARG;
@@ -399,13 +399,12 @@ try {
         }
     return YCGE_OK;
 }
-catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
 
 // test hook: the voxel fill and the flora pass on CALLER-GIVEN fields of nx x nz columns (any sizes >= 1; ground in 0..height-1; biome a
 // Biome value; rock 0..2; feature a descriptor of ycge_worldgen.h, or NULL: wg::feature_at of the given fields with origin (0, 0)) - gather == 0: the serial loops of ycge_worldgen_world_cells, != 0: the
 // kernels' scheme on the host (fallback flags to a fixed point, then wg::world_cell per cell).  passes_out: 0, or the gather's passes.
-extern "C" int ycge_host_worldgen_world_from_fields(const ycge_world *world, int32_t nx, int32_t nz, const int32_t *ground, const int32_t *water, const float *slope,
+int ycge_host_worldgen_world_from_fields(const ycge_world *world, int32_t nx, int32_t nz, const int32_t *ground, const int32_t *water, const float *slope,
                                                     const int32_t *biome, const int32_t *rock, const uint32_t *feature, int32_t gather, int32_t *cells_out,
                                                     int32_t *passes_out)
 try {
@@ -427,5 +426,5 @@ try {
     else ycge_host::world_serial_host(W, N, rec.data(), feat.data(), cells_out);
     return YCGE_OK;
 }
-catch (const std::bad_alloc &) { return YCGE_ERR_OUT_OF_MEMORY; }
-catch (...) { return YCGE_ERR_INTERNAL; }
+catch (...) { return ycge_host::abi_catch(nullptr); }
+} // extern "C"

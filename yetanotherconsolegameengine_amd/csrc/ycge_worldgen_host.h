@@ -1,5 +1,5 @@
 // ycge_worldgen_host.h - what ycge_worldgen.cpp (host generator) and ycge_worldgen.hip / ycge_worldpregen.hip (device generators) offer
-// ycge_scene_generate_grids and ycge_scene_generate_world (ycge_grid_encode.cpp).
+// ycge_scene_generate_grids and ycge_scene_generate_world (ycge_worldgen_scene.cpp).
 #pragma once
 #include <stdint.h>
 
