@@ -51,14 +51,14 @@ int ycge_launch_scene_walk(const void *nodes, int n_inner, const uint32_t *leaf_
 int ycge_launch_order_blocks(uint32_t *cost, uint32_t n, uint32_t policy, uint32_t split_top, uint32_t next_slot, uint32_t skip_mask, uint32_t *order_ws,
                              uint32_t *order, hipStream_t stream, int small_groups = 0, uint32_t n_frames = 0, uint32_t *snap = nullptr);
 int ycge_launch_taa_tiles(const ycge::TaaParams *T, const ycge::FrameParams *P, const float *current, const float *normal, const float *depth, const uint8_t *sky,
-                          float *hist, float *prev_normal, float *prev_depth, uint8_t *prev_sky, float *slab, hipStream_t stream);
+                          float *hist, const ycge::TaaGuides *prev_in, const ycge::TaaGuidesOut *prev_out /* null: no guide store */, float *slab, hipStream_t stream);
 int ycge_launch_resolve_tiles(const ycge::TaaParams *T, const ycge::FrameParams *P, const float *current, const float *normal, const float *depth, const uint8_t *sky,
-                              const void *records, const uint32_t *halo_index, float *hist, float *prev_normal, float *prev_depth, uint8_t *prev_sky, float *slab, hipStream_t stream);
+                              const void *records, const uint32_t *halo_index, float *hist, const ycge::TaaGuides *prev_in, const ycge::TaaGuidesOut *prev_out /* null: no guide store */, float *slab, hipStream_t stream);
 int ycge_launch_halo(int scatter, float *hdr, uint8_t *sky, const uint32_t *px, uint32_t n, void *records, hipStream_t stream);
 int ycge_launch_pack_history(const ycge::FrameParams *P, const float *hist, float *slab, hipStream_t stream);
 int ycge_launch_unpack_history(const float *all_slabs, size_t slab_floats_per_rank, int hiW, int hiH, int tiles_x, int n_tiles, int world_size, float *hist, hipStream_t stream);
 int ycge_launch_taa(const ycge::TaaParams *T, const float *current, const float *normal, const float *depth, const uint8_t *sky,
-                    float *hist, float *prev_normal, float *prev_depth, uint8_t *prev_sky, hipStream_t stream, int small_groups = 0, hipEvent_t stop = nullptr);
+                    float *hist, const ycge::TaaGuides *prev_in, const ycge::TaaGuidesOut *prev_out, hipStream_t stream, int small_groups = 0, hipEvent_t stop = nullptr);
 size_t ycge_post_state_bytes(void);
 int ycge_atrous_persist_resident(int groups_per_pass, int split, int profile);
 void ycge_atrous_duo_pad_lds(int bytes);
@@ -139,6 +139,8 @@ struct Knobs {
     int split_top = YCGE_SPLIT_TOP_DEFAULT;     // YCGE_SPLIT_TOP: this many blocks at the head of the schedule go in 4 parts of 16 pixels (0 = none)
     int pw_per_cu = 32;
     int post_band_rows = YCGE_POST_BAND_ROWS_DEFAULT, post_k = YCGE_POST_K_DEFAULT, post_groups = YCGE_POST_GROUPS_DEFAULT;
+    bool traced_packet = false;      // YCGE_TRACED_PACKET=1: the synchronous frame records an event between the trace and TAA for the side stream's schedule, as before (A/B)
+    bool taa_copy_guides = false;    // YCGE_TAA_COPY_GUIDES=1: the synchronous single-device frame copies TAA's guide planes as every other form does (A/B; same pixels)
     bool split_resolve = false;      // YCGE_RES_SPLIT_RESOLVE=1: the tile-resident resolve as round 5's two launches (k_scatter_halo, k_taa_tiles) instead of k_resolve_tiles (A/B)
     int post_mode = 0;               // YCGE_POST_MODE: in-place A-trous: 0 = one persistent launch, level-granular hand-over (k_atrous_stream), 2 = a launch per level group, 3 = as 0 with bands in block order
     bool post_no_split = false;      // YCGE_POST_NO_SPLIT: whole bands in the persistent in-place A-trous (no row-parity half-bands)
@@ -197,6 +199,8 @@ struct Knobs {
         post_groups = geti("YCGE_POST_GROUPS", YCGE_POST_GROUPS_DEFAULT);
         if (post_groups != 8 && post_groups != 16 && post_groups != 32) post_groups = YCGE_POST_GROUPS_DEFAULT;
         split_resolve = geti("YCGE_RES_SPLIT_RESOLVE", 0) != 0;
+        taa_copy_guides = geti("YCGE_TAA_COPY_GUIDES", 0) != 0;
+        traced_packet = geti("YCGE_TRACED_PACKET", 0) != 0;
         post_mode = geti("YCGE_POST_MODE", 0);
         post_hash = geti("YCGE_POST_HASH_FORM", 0) != 0;
         post_no_split = getenv("YCGE_POST_NO_SPLIT") != nullptr;
@@ -420,6 +424,17 @@ struct ycge_ctx {
     // per-pixel buffers in HBM (row-major, x + y*hiW)
     DevBuf<float> current_hdr, g_albedo, g_normal, g_depth, taa_hist, prev_normal, prev_depth;
     DevBuf<uint8_t> sky, prev_sky;
+    // TAA's guide planes are the last resolved frame's normal, depth and sky flag.  The synchronous single-device frame does not copy them
+    // (17 of the 87 bytes TAA moved per pixel): it keeps the planes the trace wrote and traces the next frame into a second set (g2_*: swapped
+    // with g_normal / g_depth / sky before that trace, so those names are always the newest frame's).  guide_prev_*: the planes that hold
+    // the last resolved frame's guides - a frame's own planes after such a frame, null = prev_normal / prev_depth / prev_sky after a frame
+    // of the copying forms (frames in flight, tiled and tile-resident frames, multi-device frames; YCGE_TAA_COPY_GUIDES=1), which
+    // are the only users of prev_* and allocate them (guides_copying).  Nothing may write the planes guide_prev_* name before the TAA that
+    // reads them has run: whoever writes g_normal / g_depth / sky first calls guides_keep.
+    DevBuf<float> g2_normal, g2_depth;
+    DevBuf<uint8_t> g2_sky;
+    const float *guide_prev_normal = nullptr, *guide_prev_depth = nullptr;
+    const uint8_t *guide_prev_sky = nullptr;
     // tiled frame: the trace writes its tiles here (same full-frame indexing), ycge_resolve_gathered writes the buffers above -
     // so the trace of frame N+1 may run beside the all-gather and resolve of frame N (two streams, caller-ordered)
     DevBuf<float> t_hdr, t_albedo, t_normal, t_depth;
@@ -668,6 +683,11 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
              hipEvent_t before_copy = nullptr /* recorded in front of the read-back: the exposure state is this frame's */, bool second_sdr = false,
              hipEvent_t tone_wait = nullptr /* the frame before has left its exposure state: waited for in front of this frame's exposure step */, bool second_set = false);
 int join_async(ycge_ctx *c);
+int guides_keep(ycge_ctx *c, bool *swapped = nullptr);       // in front of anything that writes g_normal / g_depth / sky: the last resolved frame's guides are not among them afterwards
+void guides_unkeep(ycge_ctx *c);              // ... undone: the frame failed, the names stay with the last frame that was rendered
+int guides_copying(ycge_ctx *c, ycge::TaaGuides &in, ycge::TaaGuidesOut &out);       // the guide arguments of a TAA launch of the copying forms (call guides_copied behind the launch)
+inline void guides_copied(ycge_ctx *c) { c->guide_prev_normal = c->guide_prev_depth = nullptr; c->guide_prev_sky = nullptr; }
+void guides_forget(ycge_ctx *c);              // new frame size: no guides, no planes
 int copy_out(ycge_ctx *c, void *dst, const void *src, size_t bytes);
 int fill_stats(ycge_ctx *c, ycge_frame_stats *st, const FrameState &fs, bool did_reset, bool have_taa, double wall_ms);
 int quiesce(ycge_ctx *c);

@@ -268,6 +268,10 @@ struct TaaParams {
     float pad_lum;
     int32_t reset;
 };
+// the guide planes of TAA: the last resolved frame's normal, depth and sky flag (read), and where this frame's go for the next (written; a
+// launcher given no TaaGuidesOut stores none - the caller keeps the planes the trace wrote instead)
+struct TaaGuides { const float *normal; const float *depth; const uint8_t *sky; };
+struct TaaGuidesOut { float *normal; float *depth; uint8_t *sky; };
 
 struct TraceOut {
     // full-frame buffers (row-major x + y*hiW); with several GPUs only the owned tiles are written

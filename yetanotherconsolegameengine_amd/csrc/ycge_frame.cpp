@@ -189,7 +189,11 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
         O.n_order = c->order_ws.p + 16;
         }
         if (launch_begin) HIP_TRY(c, hipEventRecord(launch_begin, stream));       // (behind the wait for the schedule)
-        e = ycge_launch_trace(&c->sd, &P, &O, c->cfg.count_work, flat, stream, nullptr, kernel_stop ? c->ev[1] : nullptr);
+        // The synchronous frame's schedule for the next frame waits on the side stream for this launch's OWN end (its stop event: ev[1] where the
+        // frame is timed, traced_ev where not) - an event recorded behind the launch is a packet between the trace and TAA (YCGE_TRACED_PACKET=1: A/B)
+        const bool sync_lpt = lpt && !flight && !deferred;
+        const hipEvent_t trace_end = kernel_stop ? (hipEvent_t)c->ev[1] : (sync_lpt && !c->knobs.traced_packet) ? (hipEvent_t)c->traced_ev : nullptr;
+        e = ycge_launch_trace(&c->sd, &P, &O, c->cfg.count_work, flat, stream, nullptr, trace_end);
         if (launch_end) HIP_TRY(c, hipEventRecord(launch_end, stream));
         if (e == 0 && flight) {
             // (frames in flight: the schedule of frame N + 2 follows this frame's TAA on the second stream, ycge_render_frame_async)
@@ -203,8 +207,8 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
         } else if (e == 0 && lpt) {
             // the next frame's schedule needs this frame's trace and nothing else: built on the side stream, beside TAA (or the slab
             // pack and all-gather), instead of 25 us in front of it; the next trace waits for it (order_ev)
-            HIP_TRY(c, hipEventRecord(c->traced_ev, stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->traced_ev, 0));
+            if (c->knobs.traced_packet || !trace_end) { HIP_TRY(c, hipEventRecord(c->traced_ev, stream)); HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->traced_ev, 0)); }
+            else HIP_TRY(c, hipStreamWaitEvent(c->side_stream, trace_end, 0));
             e = ycge_launch_order_blocks(c->block_cost.p, n_blocks, policy, split_top, (cost_slot + 1u) % YCGE_COST_FRAMES, 0u, c->order_ws.p, c->block_order.p, c->side_stream);
 
             c->block_order_valid = true;
@@ -271,14 +275,54 @@ void taa_decide(ycge_ctx *c, FrameState &fs, TaaParams &T, bool &did_reset)
     did_reset = !c->taa_valid || fs.reset;                        // :285
     T.reset = did_reset ? 1 : 0;
 }
+// TAA's guide planes (ycge_ctx.h: guide_prev_*).  guides_keep: the planes named g_normal / g_depth / sky are about to be written - if they
+// hold the last resolved frame's guides, the second set takes the names (a swap of names: nothing is copied).
+// swapped (optional): whether the names changed - a caller whose frame then fails swaps them back (guides_unkeep), so that the names stay
+// with the last frame that was rendered.
+int guides_keep(ycge_ctx *c, bool *swapped)
+{
+    if (swapped) *swapped = false;
+    if (!c->guide_prev_normal || c->guide_prev_normal != c->g_normal.p) return YCGE_OK;
+    const size_t n = (size_t)c->hiW * c->hiH;
+    if (!c->g2_normal.p) { HIP_TRY(c, c->g2_normal.alloc(3 * n)); HIP_TRY(c, c->g2_depth.alloc(n)); HIP_TRY(c, c->g2_sky.alloc(n)); }
+    guides_unkeep(c);
+    if (swapped) *swapped = true;
+    return YCGE_OK;
+}
+void guides_unkeep(ycge_ctx *c) { std::swap(c->g_normal, c->g2_normal); std::swap(c->g_depth, c->g2_depth); std::swap(c->sky, c->g2_sky); }
+// the copying forms: TAA reads the guides where they are and writes this frame's into prev_* (allocated here: only these forms use them)
+int guides_copying(ycge_ctx *c, TaaGuides &in, TaaGuidesOut &out)
+{
+    const size_t n = (size_t)c->hiW * c->hiH;
+    if (!c->prev_normal.p) { HIP_TRY(c, c->prev_normal.alloc(3 * n)); HIP_TRY(c, c->prev_depth.alloc(n)); HIP_TRY(c, c->prev_sky.alloc(n)); }
+    out = TaaGuidesOut{c->prev_normal.p, c->prev_depth.p, c->prev_sky.p};
+    in = c->guide_prev_normal ? TaaGuides{c->guide_prev_normal, c->guide_prev_depth, c->guide_prev_sky} : TaaGuides{c->prev_normal.p, c->prev_depth.p, c->prev_sky.p};
+    return YCGE_OK;
+}
+void guides_forget(ycge_ctx *c)
+{
+    guides_copied(c);
+    c->prev_normal.release(); c->prev_depth.release(); c->prev_sky.release();
+    c->g2_normal.release(); c->g2_depth.release(); c->g2_sky.release();
+}
+
 // steps 5 and 9: TemporalBlendWithClamp + CommitCamera
-int taa_and_commit(ycge_ctx *c, hipStream_t stream, FrameState &fs, bool &did_reset, bool timed)
+// keep_planes (the synchronous single-device frame, whose caller has called guides_keep in front of the trace): no guide copies - the planes the
+// trace has just written ARE the next frame's guides
+int taa_and_commit(ycge_ctx *c, hipStream_t stream, FrameState &fs, bool &did_reset, bool timed, bool keep_planes)
 {
     TaaParams T;
     taa_decide(c, fs, T, did_reset);
-    int e = ycge_launch_taa(&T, c->current_hdr.p, c->g_normal.p, c->g_depth.p, c->sky.p, c->taa_hist.p, c->prev_normal.p, c->prev_depth.p,
-                            c->prev_sky.p, stream, c->in_flight_taa ? 1 : 0);
+    TaaGuides prev_in; TaaGuidesOut prev_out;
+    if (keep_planes) prev_in = c->guide_prev_normal ? TaaGuides{c->guide_prev_normal, c->guide_prev_depth, c->guide_prev_sky}
+                                                    : TaaGuides{c->prev_normal.p, c->prev_depth.p, c->prev_sky.p};      // (null planes: no frame has been resolved at this size, T.reset - nothing is read)
+    else { const int rc = guides_copying(c, prev_in, prev_out); if (rc != YCGE_OK) return rc; }
+    if (keep_planes && !T.reset && (!prev_in.normal || prev_in.normal == c->g_normal.p)) return c->fail(YCGE_ERR_INTERNAL, "TAA's guide planes are the planes this frame was traced into");
+    int e = ycge_launch_taa(&T, c->current_hdr.p, c->g_normal.p, c->g_depth.p, c->sky.p, c->taa_hist.p, &prev_in, keep_planes ? nullptr : &prev_out,
+                            stream, c->in_flight_taa ? 1 : 0);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_taa launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (keep_planes) { c->guide_prev_normal = c->g_normal.p; c->guide_prev_depth = c->g_depth.p; c->guide_prev_sky = c->sky.p; }
+    else guides_copied(c);
     if (timed) HIP_TRY(c, hipEventRecord(c->ev[2], stream));
     c->taa_valid = true;
     c->last_cam[0] = fs.pos[0]; c->last_cam[1] = fs.pos[1]; c->last_cam[2] = fs.pos[2]; c->last_yaw = fs.yaw; c->last_pitch = fs.pitch;   // :266
@@ -627,9 +671,13 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
     if (c->post_hist_pending) { HIP_TRY(c, hipStreamWaitEvent(c->taa_stream, c->post_hist_ev, 0)); c->post_hist_pending = false; }      // the post stage of the frame before reads the history this TAA rewrites
     bool did_reset = false;
     c->in_flight_taa = small;
-    rc = taa_and_commit(c, c->taa_stream, fs, did_reset, false);
+    // (the first frame in flight behind a synchronous frame: its TAA reads that frame's planes as its guides - the set now named alt - and the
+    // trace of frame N + 2, which writes that set, waits for it as it waits for every TAA that has read the set it writes)
+    const bool guides_in_alt = c->guide_prev_normal != nullptr && c->guide_prev_normal == c->alt_normal.p;
+    rc = taa_and_commit(c, c->taa_stream, fs, did_reset, false, false);
     c->in_flight_taa = false;
     if (rc != YCGE_OK) return rc;
+    if (guides_in_alt) { HIP_TRY(c, hipEventRecord(c->set_resolved_ev[c->set_id[1]], c->taa_stream)); c->set_read[c->set_id[1]] = true; }
     if (post) {
         for (Event *ev : {&c->flight_taa_ev, &c->post_hist_ev, &c->post_done_ev, &c->post_set_ev[0], &c->post_set_ev[1], &c->post_set_ev[2]})
             HIP_TRY(c, ev->ensure());
@@ -677,10 +725,17 @@ int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *
     // (timing events only where the caller asks for statistics: an event between two kernels is a packet of its own that the next launch waits behind -
     // the C# wrapper passes no statistics and gets the frame without them; bench.py asks, its line is measured WITH them)
     const bool timed = st != nullptr;
-    int rc = multi_dev ? trace_on_all_devices(c, fs) : trace_frame(c, nullptr, c->stream, fs, timed);
+    // the single-device frame keeps the planes it traces into as the next frame's TAA guides instead of copying them (ycge_ctx.h: guide_prev_*)
+    const bool keep_planes = !multi_dev && !c->knobs.taa_copy_guides;
+    bool swapped = false;
+    int rc = guides_keep(c, &swapped);    // this frame's trace does not write the last resolved frame's guides
     if (rc != YCGE_OK) return rc;
-    rc = taa_and_commit(c, c->stream, fs, did_reset, timed);
-    if (rc != YCGE_OK) return rc;
+    rc = multi_dev ? trace_on_all_devices(c, fs) : trace_frame(c, nullptr, c->stream, fs, timed);
+    if (rc == YCGE_OK) rc = taa_and_commit(c, c->stream, fs, did_reset, timed, keep_planes);
+    if (rc != YCGE_OK) {          // (no scene, a failed launch: YCGE_BUF_G_NORMAL / G_DEPTH / SKY_MASK go on naming the last frame that was rendered)
+        if (swapped) { (void)hipStreamSynchronize(c->stream); guides_unkeep(c); }
+        return rc;
+    }
     if (post) {      // steps 6-8; without them the frame stops after TAA (trace-only callers, benchmarks of the hot path)
         rc = run_post(c, c->stream, out_sdr, timed);
         if (rc != YCGE_OK) return rc;
@@ -758,6 +813,7 @@ try {
     if (out_sdr && !c->cfg.slab_albedo) return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
     const size_t per_rank = (size_t)c->tiles_per_rank_padded * 256 * slab_floats(c);
     if (st) HIP_TRY(c, hipEventRecord(c->ev[1], stream));
+    { const int rc = guides_keep(c); if (rc != YCGE_OK) return rc; }       // (a synchronous frame's planes may hold the guides: the gathered frame goes into the other set)
     int e = ycge_launch_unpermute((const float *)d_all_slabs, per_rank, c->hiW, c->hiH, c->tiles_x, c->n_tiles, c->cfg.world_size,
                                   (int)slab_floats(c), c->current_hdr.p, c->g_albedo.p, c->g_normal.p, c->g_depth.p, c->sky.p, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_unpermute launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -766,7 +822,7 @@ try {
     FrameState fs = c->pending.front();
     c->pending.pop_front();
     bool did_reset = false;
-    int rc = taa_and_commit(c, stream, fs, did_reset, st != nullptr);
+    int rc = taa_and_commit(c, stream, fs, did_reset, st != nullptr, false);
     if (rc != YCGE_OK) return rc;
     if (out_sdr) {
         rc = run_post(c, stream, out_sdr, st != nullptr);

@@ -20,8 +20,8 @@ int alloc_frame_buffers(ycge_ctx *c)
     const size_t n = (size_t)c->hiW * c->hiH;
     HIP_TRY(c, c->current_hdr.alloc(3 * n)); HIP_TRY(c, c->g_albedo.alloc(3 * n)); HIP_TRY(c, c->g_normal.alloc(3 * n));
     HIP_TRY(c, c->g_depth.alloc(n)); HIP_TRY(c, c->sky.alloc(n));
-    HIP_TRY(c, c->taa_hist.alloc(3 * n)); HIP_TRY(c, c->prev_normal.alloc(3 * n)); HIP_TRY(c, c->prev_depth.alloc(n));
-    HIP_TRY(c, c->prev_sky.alloc(n));
+    HIP_TRY(c, c->taa_hist.alloc(3 * n));
+    guides_forget(c);           // (prev_* and the second set of guide planes: allocated by the frame forms that use them)
     HIP_TRY(c, hipMemset(c->taa_hist.p, 0, 3 * n * sizeof(float)));
     if (c->cfg.capture_debug) {
         HIP_TRY(c, c->dbg_rays.alloc(6 * n)); HIP_TRY(c, c->dbg_prim.alloc(n)); HIP_TRY(c, c->dbg_sub.alloc(n));

@@ -689,22 +689,33 @@ __device__ __forceinline__ float luma(float r, float g, float b) { return 0.2126
 // before the next trace (or while it runs: frames in flight).  The 3 x 3 colour taps stay ordinary loads, they are shared.
 template <class T> __device__ __forceinline__ T taa_ld(const T *p) { return YCGE_TAA_NT ? __builtin_nontemporal_load(p) : *p; }
 template <class T> __device__ __forceinline__ void taa_st(T *p, T v) { if (YCGE_TAA_NT) __builtin_nontemporal_store(v, p); else *p = v; }
+// The guide planes of the NEXT frame's blend are this frame's normal, depth and sky flag, value for value.  A caller that keeps the planes
+// the trace wrote until then passes no prev_out (null) and nothing is stored: 17 of the 87 bytes a pixel moved.  prev_in and prev_out may
+// be the same planes (the copying callers): each pixel is read before it is written, by its own thread - hence no __restrict__ on them.
+__device__ __forceinline__ void taa_store_guides(const size_t i, const float nx, const float ny, const float nz, const float z_now, const uint8_t sky_now,
+                                                 float *prev_out_normal, float *prev_out_depth, uint8_t *prev_out_sky)
+{
+    if (!prev_out_normal) return;
+    taa_st(prev_out_normal + 3 * i, nx); taa_st(prev_out_normal + 3 * i + 1, ny); taa_st(prev_out_normal + 3 * i + 2, nz);
+    taa_st(prev_out_depth + i, z_now);
+    taa_st(prev_out_sky + i, sky_now);
+}
 // TemporalBlendWithClamp, RaytraceRenderer.cs:274-398.  One thread per pixel; the history and
 // guide updates touch only the thread's own pixel, so the serial loops of the C# fuse into one pass.
 // taa_blend: everything behind the pixel's own values of this frame and the luminance range of its window - the reset copy (:285-300), the
 // per-pixel alpha (:318-340), the clamp of the history's luminance (:362-378), the blend and the guide copies (:380-396).
 __device__ __forceinline__ void taa_blend(const TaaParams &T, const size_t i, const float cr, const float cg, const float cb, const float nx, const float ny, const float nz,
                                           const float z_now, const uint8_t sky_now, const float min_l, const float max_l, float *__restrict__ hist,
-                                          float *__restrict__ prev_normal, float *__restrict__ prev_depth, uint8_t *__restrict__ prev_sky)
+                                          const float *prev_in_normal, const float *prev_in_depth, const uint8_t *prev_in_sky, float *prev_out_normal, float *prev_out_depth, uint8_t *prev_out_sky)
 {
     float pr = taa_ld(hist + 3 * i), pg = taa_ld(hist + 3 * i + 1), pb = taa_ld(hist + 3 * i + 2);
     float local_alpha = T.alpha;
-    if ((sky_now != 0) != (taa_ld(prev_sky + i) != 0)) {
+    if ((sky_now != 0) != (taa_ld(prev_in_sky + i) != 0)) {
         local_alpha = 1.0f;
     } else {
-        const float z_prev = taa_ld(prev_depth + i);
+        const float z_prev = taa_ld(prev_in_depth + i);
         F3 n_now = normalized(f3(nx, ny, nz));
-        F3 n_prev = normalized(f3(taa_ld(prev_normal + 3 * i), taa_ld(prev_normal + 3 * i + 1), taa_ld(prev_normal + 3 * i + 2)));
+        F3 n_prev = normalized(f3(taa_ld(prev_in_normal + 3 * i), taa_ld(prev_in_normal + 3 * i + 1), taa_ld(prev_in_normal + 3 * i + 2)));
         if (!cs_isfinite(z_now) || !cs_isfinite(z_prev)) {
             local_alpha = 1.0f;
         } else {
@@ -728,17 +739,13 @@ __device__ __forceinline__ void taa_blend(const TaaParams &T, const size_t i, co
     taa_st(hist + 3 * i, pr * (1.0f - local_alpha) + cr * local_alpha);
     taa_st(hist + 3 * i + 1, pg * (1.0f - local_alpha) + cg * local_alpha);
     taa_st(hist + 3 * i + 2, pb * (1.0f - local_alpha) + cb * local_alpha);
-    taa_st(prev_normal + 3 * i, nx); taa_st(prev_normal + 3 * i + 1, ny); taa_st(prev_normal + 3 * i + 2, nz);
-    taa_st(prev_depth + i, z_now);
-    taa_st(prev_sky + i, sky_now);
+    taa_store_guides(i, nx, ny, nz, z_now, sky_now, prev_out_normal, prev_out_depth, prev_out_sky);
 }
 __device__ __forceinline__ void taa_reset(const size_t i, const float cr, const float cg, const float cb, const float nx, const float ny, const float nz, const float z_now,
-                                          const uint8_t sky_now, float *__restrict__ hist, float *__restrict__ prev_normal, float *__restrict__ prev_depth, uint8_t *__restrict__ prev_sky)
+                                          const uint8_t sky_now, float *__restrict__ hist, const float *prev_in_normal, const float *prev_in_depth, const uint8_t *prev_in_sky, float *prev_out_normal, float *prev_out_depth, uint8_t *prev_out_sky)
 {
     taa_st(hist + 3 * i, cr); taa_st(hist + 3 * i + 1, cg); taa_st(hist + 3 * i + 2, cb);
-    taa_st(prev_normal + 3 * i, nx); taa_st(prev_normal + 3 * i + 1, ny); taa_st(prev_normal + 3 * i + 2, nz);
-    taa_st(prev_depth + i, z_now);
-    taa_st(prev_sky + i, sky_now);
+    taa_store_guides(i, nx, ny, nz, z_now, sky_now, prev_out_normal, prev_out_depth, prev_out_sky);
 }
 // (TAP: where this frame's colour and sky flag of a window pixel come from - the frame's planes (PlaneTap: k_taa, k_taa_tiles) or, for the
 // pixels other ranks own, the halo records as they arrived (HaloTap: k_resolve_tiles))
@@ -753,7 +760,7 @@ struct PlaneTap {
 template <class TAP>
 __device__ __forceinline__ void taa_pixel_t(const TaaParams &T, const int x, const int y, const TAP &tap, const float *__restrict__ normal,
                                             const float *__restrict__ depth, float *__restrict__ hist,
-                                            float *__restrict__ prev_normal, float *__restrict__ prev_depth, uint8_t *__restrict__ prev_sky)
+                                            const float *prev_in_normal, const float *prev_in_depth, const uint8_t *prev_in_sky, float *prev_out_normal, float *prev_out_depth, uint8_t *prev_out_sky)
 {
     if (x >= T.w || y >= T.h) return;
     const size_t i = (size_t)x + (size_t)y * T.w;
@@ -762,7 +769,7 @@ __device__ __forceinline__ void taa_pixel_t(const TaaParams &T, const int x, con
     tap(x, y, cr, cg, cb, sky_now);
     const float nx = taa_ld(normal + 3 * i), ny = taa_ld(normal + 3 * i + 1), nz = taa_ld(normal + 3 * i + 2);
     const float z_now = taa_ld(depth + i);
-    if (T.reset) { taa_reset(i, cr, cg, cb, nx, ny, nz, z_now, sky_now, hist, prev_normal, prev_depth, prev_sky); return; }
+    if (T.reset) { taa_reset(i, cr, cg, cb, nx, ny, nz, z_now, sky_now, hist, prev_in_normal, prev_in_depth, prev_in_sky, prev_out_normal, prev_out_depth, prev_out_sky); return; }
     float min_l = YCGE_INF, max_l = -YCGE_INF;
     const int r = T.radius;
     if (r == 1) {       // the default window: all nine taps fetched before any is looked at (the loop below waits for a tap's sky flag
@@ -795,14 +802,14 @@ __device__ __forceinline__ void taa_pixel_t(const TaaParams &T, const int x, con
             if (l > max_l) max_l = l;
         }
     }
-    taa_blend(T, i, cr, cg, cb, nx, ny, nz, z_now, sky_now, min_l, max_l, hist, prev_normal, prev_depth, prev_sky);
+    taa_blend(T, i, cr, cg, cb, nx, ny, nz, z_now, sky_now, min_l, max_l, hist, prev_in_normal, prev_in_depth, prev_in_sky, prev_out_normal, prev_out_depth, prev_out_sky);
 }
 __device__ __forceinline__ void taa_pixel(const TaaParams &T, const int x, const int y, const float *__restrict__ current, const float *__restrict__ normal,
                                              const float *__restrict__ depth, const uint8_t *__restrict__ sky, float *__restrict__ hist,
-                                             float *__restrict__ prev_normal, float *__restrict__ prev_depth, uint8_t *__restrict__ prev_sky)
+                                             const float *prev_in_normal, const float *prev_in_depth, const uint8_t *prev_in_sky, float *prev_out_normal, float *prev_out_depth, uint8_t *prev_out_sky)
 {
     const PlaneTap tap = {current, sky, T.w};
-    taa_pixel_t(T, x, y, tap, normal, depth, hist, prev_normal, prev_depth, prev_sky);
+    taa_pixel_t(T, x, y, tap, normal, depth, hist, prev_in_normal, prev_in_depth, prev_in_sky, prev_out_normal, prev_out_depth, prev_out_sky);
 }
 
 // One 64-thread workgroup per schedule entry, listed longest first (k_cost_scatter).  An entry is an 8x8 pixel block
@@ -814,10 +821,25 @@ __device__ __forceinline__ void taa_pixel(const TaaParams &T, const int x, const
 #define YCGE_ENT_BLOCK(e) ((e) & 0x3fffffu)
 #define YCGE_ENT_PART(e) (((e) >> 22) & 63u)
 #define YCGE_ENT_LG(e) ((e) >> 28)
+// the maximum of v over the 64 lanes of a wavefront whose lanes are ALL active (trace_block's trip loop), the same value in every lane.  Once per
+// trip, for the schedule's cost feedback alone: a scan within the rows of 16 lanes and two row broadcasts, all in the vector ALU's own lane
+// crossbar - six __shfl_xor steps were six round trips through the LDS.  (A lane that a step gives no partner takes 0, the identity.)
+// (-DYCGE_UMAX_DPP=0: the shuffles, A/B)
+#ifndef YCGE_UMAX_DPP
+#define YCGE_UMAX_DPP 1
+#endif
 __device__ __forceinline__ uint32_t wave_umax(uint32_t v)
 {
+#if !YCGE_UMAX_DPP
     for (int off = 32; off >= 1; off >>= 1) { const uint32_t o2 = (uint32_t)__shfl_xor((int)v, off, 64); v = o2 > v ? o2 : v; }
     return v;
+#endif
+#define YCGE_UMAX_STEP(ctrl, rows) { const uint32_t o2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xf, false); v = o2 > v ? o2 : v; }
+    YCGE_UMAX_STEP(0x111, 0xf) YCGE_UMAX_STEP(0x112, 0xf) YCGE_UMAX_STEP(0x114, 0xf) YCGE_UMAX_STEP(0x118, 0xf)     // row_shr:1, 2, 4, 8: lane 15 of a row holds the row's
+    YCGE_UMAX_STEP(0x142, 0xa)      // row_bcast:15 into rows 1 and 3: lanes 31 and 63 hold their half's
+    YCGE_UMAX_STEP(0x143, 0xc)      // row_bcast:31 into rows 2 and 3: lane 63 holds the wavefront's
+#undef YCGE_UMAX_STEP
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
 // The shading context of a diffuse hit (position, normal, albedo, direction to the eye) between the hit and the light-loop / bounce
@@ -838,7 +860,6 @@ __device__ __forceinline__ void shade_ctx_load(uint32_t addr, F3 &p, F3 &n, F3 &
                  : "=&v"(v0), "=&v"(v1), "=&v"(v2) : "v"(addr) : "memory");
     p = f3(v0.x, v0.y, v0.z); n = f3(v0.w, v1.x, v1.y); alb = f3(v1.z, v1.w, v2.x); wo = f3(v2.y, v2.z, v2.w);
 }
-
 // One wavefront per schedule entry; each lane runs TraceFull's work-item loop (RaytraceRenderer.cs:448-616) for its pixel and traces
 // the queries where the loop asks for them, one query a lane per trip, the whole wavefront walking together.  FULLW = false: the
 // instance for scenes without a mesh (no cooperative walk; lanes without a query stay out of it).  The query fan-out forms that once
@@ -1306,11 +1327,11 @@ __global__ __launch_bounds__(1024) void k_cost_scatter(const uint32_t *__restric
 // ---------------------------------------------------------------------------------- K_taa (taa_pixel: above, in front of trace_block)
 __global__ __launch_bounds__(256) void k_taa(const TaaParams T, const float *__restrict__ current, const float *__restrict__ normal,
                                              const float *__restrict__ depth, const uint8_t *__restrict__ sky, float *__restrict__ hist,
-                                             float *__restrict__ prev_normal, float *__restrict__ prev_depth, uint8_t *__restrict__ prev_sky)
+                                             const float *prev_in_normal, const float *prev_in_depth, const uint8_t *prev_in_sky, float *prev_out_normal, float *prev_out_depth, uint8_t *prev_out_sky)
 {
     // 32 x 8 pixels a workgroup; 32 x 2 (one wavefront) for the frames in flight: such a workgroup takes the place of ONE retiring
     // wavefront of the trace that runs beside it, a four-wavefront one waits until four places are free on one CU
-    taa_pixel(T, blockIdx.x * 32 + (threadIdx.x & 31), blockIdx.y * (int)(blockDim.x >> 5) + (threadIdx.x >> 5), current, normal, depth, sky, hist, prev_normal, prev_depth, prev_sky);
+    taa_pixel(T, blockIdx.x * 32 + (threadIdx.x & 31), blockIdx.y * (int)(blockDim.x >> 5) + (threadIdx.x >> 5), current, normal, depth, sky, hist, prev_in_normal, prev_in_depth, prev_in_sky, prev_out_normal, prev_out_depth, prev_out_sky);
 }
 
 // ---------------------------------------------------------------------------------- tile-resident TAA (multi-GPU, one process per GPU)
@@ -1322,13 +1343,13 @@ __global__ __launch_bounds__(256) void k_taa(const TaaParams T, const float *__r
 // profiles/r05: the resolve that the next launch on the same ring slots waits for); a single wavefront takes any slot that frees.
 __global__ __launch_bounds__(64) void k_taa_tiles(const TaaParams T, const FrameParams P, const float *__restrict__ current, const float *__restrict__ normal,
                                                   const float *__restrict__ depth, const uint8_t *__restrict__ sky, float *__restrict__ hist,
-                                                  float *__restrict__ prev_normal, float *__restrict__ prev_depth, uint8_t *__restrict__ prev_sky,
+                                                  const float *prev_in_normal, const float *prev_in_depth, const uint8_t *prev_in_sky, float *prev_out_normal, float *prev_out_depth, uint8_t *prev_out_sky,
                                                   float *__restrict__ slab /* or null: the resolved history of the rank's tiles, k_pack_history's layout - one launch less in the resolve chain */)
 {
     int px, py, lx, ly;
     const int k = (int)(blockIdx.x >> 2);
     if (!tile_pixel_wl(P, k, (int)(blockIdx.x & 3u), (int)threadIdx.x, px, py, lx, ly)) return;
-    taa_pixel(T, px, py, current, normal, depth, sky, hist, prev_normal, prev_depth, prev_sky);
+    taa_pixel(T, px, py, current, normal, depth, sky, hist, prev_in_normal, prev_in_depth, prev_in_sky, prev_out_normal, prev_out_depth, prev_out_sky);
     if (slab) {         // (this thread's own stores, read back in program order)
         const size_t i = (size_t)px + (size_t)py * P.hiW;
         float *s = slab + ((size_t)k * 256 + (size_t)(ly * YCGE_TILE_W + lx)) * 3;
@@ -1352,14 +1373,15 @@ struct HaloTap {
 };
 __global__ __launch_bounds__(64) void k_resolve_tiles(const TaaParams T, const FrameParams P, const float *__restrict__ current, const float *__restrict__ normal,
                                                       const float *__restrict__ depth, const uint8_t *__restrict__ sky, const float4 *__restrict__ records,
-                                                      const uint32_t *__restrict__ halo_index, float *__restrict__ hist, float *__restrict__ prev_normal,
-                                                      float *__restrict__ prev_depth, uint8_t *__restrict__ prev_sky, float *__restrict__ slab)
+                                                      const uint32_t *__restrict__ halo_index, float *__restrict__ hist, const float *prev_in_normal,
+                                                      const float *prev_in_depth, const uint8_t *prev_in_sky, float *prev_out_normal, float *prev_out_depth, uint8_t *prev_out_sky,
+                                                      float *__restrict__ slab)
 {
     int px, py, lx, ly;
     const int k = (int)(blockIdx.x >> 2);
     if (!tile_pixel_wl(P, k, (int)(blockIdx.x & 3u), (int)threadIdx.x, px, py, lx, ly)) return;
     const HaloTap tap = {current, sky, records, halo_index, P.hiW, P.tiles_x, P.rank, P.world_size};
-    taa_pixel_t(T, px, py, tap, normal, depth, hist, prev_normal, prev_depth, prev_sky);
+    taa_pixel_t(T, px, py, tap, normal, depth, hist, prev_in_normal, prev_in_depth, prev_in_sky, prev_out_normal, prev_out_depth, prev_out_sky);
     if (slab) {
         const size_t i = (size_t)px + (size_t)py * P.hiW;
         float *s = slab + ((size_t)k * 256 + (size_t)(ly * YCGE_TILE_W + lx)) * 3;
@@ -1616,29 +1638,32 @@ int ycge_launch_order_blocks(uint32_t *cost, uint32_t n, uint32_t policy, uint32
 }
 
 int ycge_launch_taa(const ycge::TaaParams *T, const float *current, const float *normal, const float *depth, const uint8_t *sky,
-                    float *hist, float *prev_normal, float *prev_depth, uint8_t *prev_sky, hipStream_t stream, int small_groups, hipEvent_t stop)
+                    float *hist, const ycge::TaaGuides *prev_in, const ycge::TaaGuidesOut *prev_out, hipStream_t stream, int small_groups, hipEvent_t stop)
 {
     // small_groups (frames in flight): one-wavefront workgroups take the place of a single retiring wavefront of the trace running beside them
     const unsigned rows = small_groups ? 2u : 8u;
     dim3 grid((unsigned)((T->w + 31) / 32), (unsigned)((T->h + (int)rows - 1) / (int)rows)), block(32u * rows);
-    if (stop) hipExtLaunchKernelGGL(ycge::k_taa, grid, block, 0, stream, nullptr, stop, 0, *T, current, normal, depth, sky, hist, prev_normal, prev_depth, prev_sky);
-    else hipLaunchKernelGGL(ycge::k_taa, grid, block, 0, stream, *T, current, normal, depth, sky, hist, prev_normal, prev_depth, prev_sky);
+    const ycge::TaaGuidesOut po = prev_out ? *prev_out : ycge::TaaGuidesOut{nullptr, nullptr, nullptr};       // (null: the caller keeps the frame's own planes as the guides)
+    if (stop) hipExtLaunchKernelGGL(ycge::k_taa, grid, block, 0, stream, nullptr, stop, 0, *T, current, normal, depth, sky, hist, prev_in->normal, prev_in->depth, prev_in->sky, po.normal, po.depth, po.sky);
+    else hipLaunchKernelGGL(ycge::k_taa, grid, block, 0, stream, *T, current, normal, depth, sky, hist, prev_in->normal, prev_in->depth, prev_in->sky, po.normal, po.depth, po.sky);
     return (int)hipGetLastError();
 }
 
 int ycge_launch_taa_tiles(const ycge::TaaParams *T, const ycge::FrameParams *P, const float *current, const float *normal, const float *depth, const uint8_t *sky,
-                          float *hist, float *prev_normal, float *prev_depth, uint8_t *prev_sky, float *slab, hipStream_t stream)
+                          float *hist, const ycge::TaaGuides *prev_in, const ycge::TaaGuidesOut *prev_out, float *slab, hipStream_t stream)
 {
     if (P->n_owned_tiles <= 0) return 0;
-    hipLaunchKernelGGL(ycge::k_taa_tiles, dim3((unsigned)P->n_owned_tiles * 4u), dim3(64), 0, stream, *T, *P, current, normal, depth, sky, hist, prev_normal, prev_depth, prev_sky, slab);
+    const ycge::TaaGuidesOut po = prev_out ? *prev_out : ycge::TaaGuidesOut{nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(ycge::k_taa_tiles, dim3((unsigned)P->n_owned_tiles * 4u), dim3(64), 0, stream, *T, *P, current, normal, depth, sky, hist, prev_in->normal, prev_in->depth, prev_in->sky, po.normal, po.depth, po.sky, slab);
     return (int)hipGetLastError();
 }
 int ycge_launch_resolve_tiles(const ycge::TaaParams *T, const ycge::FrameParams *P, const float *current, const float *normal, const float *depth, const uint8_t *sky,
-                              const void *records, const uint32_t *halo_index, float *hist, float *prev_normal, float *prev_depth, uint8_t *prev_sky, float *slab, hipStream_t stream)
+                              const void *records, const uint32_t *halo_index, float *hist, const ycge::TaaGuides *prev_in, const ycge::TaaGuidesOut *prev_out, float *slab, hipStream_t stream)
 {
     if (P->n_owned_tiles <= 0) return 0;
+    const ycge::TaaGuidesOut po = prev_out ? *prev_out : ycge::TaaGuidesOut{nullptr, nullptr, nullptr};
     hipLaunchKernelGGL(ycge::k_resolve_tiles, dim3((unsigned)P->n_owned_tiles * 4u), dim3(64), 0, stream, *T, *P, current, normal, depth, sky, (const float4 *)records, halo_index,
-                       hist, prev_normal, prev_depth, prev_sky, slab);
+                       hist, prev_in->normal, prev_in->depth, prev_in->sky, po.normal, po.depth, po.sky, slab);
     return (int)hipGetLastError();
 }
 int ycge_launch_halo(int scatter, float *hdr, uint8_t *sky, const uint32_t *px, uint32_t n, void *records, hipStream_t stream)

@@ -391,6 +391,7 @@ try {
     if (!c->taa_hist.p || !c->g_albedo.p || !c->g_normal.p || !c->g_depth.p || !c->sky.p || c->taa_hist.n < 3 * n || c->g_albedo.n < 3 * n || c->g_normal.n < 3 * n || c->g_depth.n < n || c->sky.n < n)
         return c->fail(YCGE_ERR_INTERNAL, "ycge_test_post_stage: the context holds no frame buffers of %d x %d", c->hiW, c->hiH);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    { const int rc = guides_keep(c); if (rc != YCGE_OK) return rc; }       // (the probe's planes do not become TAA's guides: as when they were a copy)
     HIP_TRY(c, hipMemcpy(c->taa_hist.p, hist, 3 * n * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->g_albedo.p, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->g_normal.p, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice));

@@ -318,12 +318,15 @@ try {
     T.reset = did_reset ? 1 : 0;
     FrameParams P;
     fill_frame_params(c, P, fs.frame, fs.pos, fs.yaw, fs.pitch, fs.fov);
+    TaaGuides prev_in; TaaGuidesOut prev_out;
+    { const int rc = guides_copying(c, prev_in, prev_out); if (rc != YCGE_OK) return rc; }
     // ONE launch: the halo taps read from the records where the exchange left them, TAA on this rank's tiles, the resolved history packed (k_resolve_tiles)
     if (c->knobs.split_resolve)
-        e = ycge_launch_taa_tiles(&T, &P, rs->hdr.p, rs->normal.p, rs->depth.p, rs->sky.p, c->taa_hist.p, c->prev_normal.p, c->prev_depth.p, c->prev_sky.p, (float *)d_history_slab /* packed by the same launch */, stream);
+        e = ycge_launch_taa_tiles(&T, &P, rs->hdr.p, rs->normal.p, rs->depth.p, rs->sky.p, c->taa_hist.p, &prev_in, &prev_out, (float *)d_history_slab /* packed by the same launch */, stream);
     else
-        e = ycge_launch_resolve_tiles(&T, &P, rs->hdr.p, rs->normal.p, rs->depth.p, rs->sky.p, d_halo_recv, c->d_halo_index.p, c->taa_hist.p, c->prev_normal.p, c->prev_depth.p, c->prev_sky.p, (float *)d_history_slab, stream);
+        e = ycge_launch_resolve_tiles(&T, &P, rs->hdr.p, rs->normal.p, rs->depth.p, rs->sky.p, d_halo_recv, c->d_halo_index.p, c->taa_hist.p, &prev_in, &prev_out, (float *)d_history_slab, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "resolve launch failed: %s", hipGetErrorString((hipError_t)e));
+    guides_copied(c);
     if (st) HIP_TRY(c, hipEventRecord(c->ev[2], stream));
     c->taa_valid = true;
     c->last_cam[0] = fs.pos[0]; c->last_cam[1] = fs.pos[1]; c->last_cam[2] = fs.pos[2]; c->last_yaw = fs.yaw; c->last_pitch = fs.pitch;
@@ -535,9 +538,14 @@ try {
     case YCGE_BUF_G_DEPTH: src = c->g_depth.p; want = n * 4; break;
     case YCGE_BUF_SKY_MASK: src = c->sky.p; want = n; break;
     case YCGE_BUF_TAA_HISTORY: src = c->taa_hist.p; want = n * 12; break;
-    case YCGE_BUF_PREV_NORMAL: src = c->prev_normal.p; want = n * 12; break;
-    case YCGE_BUF_PREV_DEPTH: src = c->prev_depth.p; want = n * 4; break;
-    case YCGE_BUF_PREV_SKY: src = c->prev_sky.p; want = n; break;
+    // (TAA's guides: wherever the last resolved frame left them - the frame's own planes after a synchronous single-device frame)
+    case YCGE_BUF_PREV_NORMAL: case YCGE_BUF_PREV_DEPTH: case YCGE_BUF_PREV_SKY: {
+        TaaGuides g; TaaGuidesOut unused;
+        if (c->guide_prev_normal) g = TaaGuides{c->guide_prev_normal, c->guide_prev_depth, c->guide_prev_sky};
+        else { const int rc = guides_copying(c, g, unused); if (rc != YCGE_OK) return rc; }
+        if (which == YCGE_BUF_PREV_NORMAL) { src = g.normal; want = n * 12; } else if (which == YCGE_BUF_PREV_DEPTH) { src = g.depth; want = n * 4; } else { src = g.sky; want = n; }
+        break;
+    }
     case YCGE_BUF_DENOISED:
         if (!c->denoised) return c->fail(YCGE_ERR_INVALID_ARG, "no denoised frame yet: render with an SDR output buffer first");
         src = c->denoised; want = n * 12; break;
