@@ -165,6 +165,14 @@ namespace ConsoleGame.RayTracing.Native
         public ulong PlacedWaits;
     }
 
+    // ycge_obj_info (an out parameter only, never embedded: C#'s default struct layout is the sequential one the C side has)
+    public struct YObjInfo
+    {
+        public int NPositions, NTriangles;
+        public long NLines;
+        public int OnDevice, Reserved;
+    }
+
     public enum YStatus { Ok = 0, InvalidArg = -1, NoScene = -2, Device = -3, Unsupported = -4, OutOfMemory = -5, StackDepth = -6, NoDeviceCode = -7, Internal = -8 }
     public enum YMaterialKind { Constant = 0, Checker = 1, Textured = 2 }
     public enum YExchange { PeerPush = 0, Rccl = 1 }
@@ -216,6 +224,12 @@ namespace ConsoleGame.RayTracing.Native
         [DllImport(Lib)] public static extern int ycge_video_blit_ansi(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int consoleW, int consoleH, int viewportX,
                                                                        int viewportY, int defaultFg16, int defaultBg16, int clearScreen, byte* outStream, UIntPtr capacity,
                                                                        UIntPtr* outLen, float* outTopBottomSdr);
+        // OBJ meshes from file bytes (MeshLoader.FromObj on the device; HipObjLoader.cs).  info: a YObjInfo
+        [DllImport(Lib)] public static extern int ycge_obj_parse_host(byte* text, UIntPtr bytes, float* positions, int* faces, out YObjInfo info, byte* msg, UIntPtr msgBytes);
+        [DllImport(Lib)] public static extern int ycge_obj_parse(IntPtr ctx, byte* text, UIntPtr bytes, out YObjInfo info);
+        [DllImport(Lib)] public static extern int ycge_obj_read(IntPtr ctx, float* positions, int* faces);
+        [DllImport(Lib)] public static extern int ycge_obj_triangles(IntPtr ctx, int normalize, float targetSize, float scale, float* translate, float* outTriangles, float* outBounds);
+        [DllImport(Lib)] public static extern int ycge_obj_release(IntPtr ctx);
         [DllImport(Lib)] public static extern int ycge_wait(IntPtr ctx);
         [DllImport(Lib)] public static extern int ycge_async_trace_times(IntPtr ctx, float* msOut, int capacity, out int nOut);
         [DllImport(Lib)] public static extern int ycge_flight_query(IntPtr ctx, out YFlightInfo info);

@@ -536,6 +536,54 @@ int ycge_video_blit_ansi(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int
                          int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
                          int32_t default_fg16, int32_t default_bg16, int32_t clear_screen,
                          uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr /* may be NULL */);
+/* --- OBJ meshes from file bytes: MeshLoader.FromObj (RayTracing/MeshLoader.cs:12-149) up to the float soup ycge_mesh.triangles takes, parsed
+ * on the device.  Added after ABI 10 without changing it (YCGE_ABI_VERSION stays 10, no struct changes; detect by symbol lookup).
+ *   The contract, byte by byte ("the reference's loader" restated correctly; tests/obj_restatement.py is its yardstick):
+ *   Lines    StreamReader.ReadLine: a line ends at \n, \r\n or a lone \r, the last one needs no terminator; a UTF-8 byte-order mark at
+ *            offset 0 is skipped; lines count from 1.  An empty line or one whose first byte is '#' is skipped (" # x" is not).
+ *   Tokens   split at char.IsWhiteSpace: in ASCII, inside a line, space, \t, \v, \f - 0x1C..0x1F are not separators.
+ *   v lines  first token exactly v and at least 4 tokens: tokens 1..3 are parsed, the rest never looked at; fewer tokens add nothing.
+ *   f lines  first token exactly f and at least 4 tokens: every token is cut at its first '/' and read by ParseIndex - empty gives 0,
+ *            i > 0 gives i - 1, else count + i with count the positions read so far at this line - and a fan of tokens - 3 triangles
+ *            (v0, v[k-1], v[k]) is added.  An index may name a vertex a later line defines: 0 <= index < the final count is checked last.
+ *   Floats   [+-]? (digits [. digits?] | . digits) ([eE] [+-]? digits)?, correctly rounded to binary32 (nearest, ties to even; -0 stays
+ *            -0; overflow gives +-inf, underflow a subnormal or zero) as .NET's float.Parse rounds - not by way of binary64.  Thousands
+ *            separators, Infinity, NaN and surrounding blanks are refused.  Integers: [+-]? digits within int32.
+ *   Refused  with YCGE_ERR_INVALID_ARG and a message, nothing held, the context usable - in this order: a NULL or empty text, 2^31 bytes
+ *            or more; the first line in file order with a malformed float or integer token or (YCGE_ERR_UNSUPPORTED: it would need
+ *            .NET's Unicode separators) a byte >= 0x80 outside a comment - the message names the 1-based line; more than 2^28 triangles;
+ *            no position or no triangle (InvalidDataException); an index out of range - the message names the lowest triangle, counted
+ *            from 0 in file order.
+ *   Tail     (MeshLoader.cs:57-96, 107-148; binary32 operation by operation, no contraction) the box over the vertices any face uses;
+ *            c = (min + max) * 0.5f; maxExtent by the three compares, 1 if <= 0; s = target_size / maxExtent; every vertex becomes
+ *            (p - c) * s (skipped, as there, when a bound is infinite); then p * scale + t only when scale != 1 or t != 0; triangles are
+ *            gathered in face order; the bounds are min / max over their corners.  Extremes do not depend on order except for the sign
+ *            of a zero extreme, which in the reference follows HashSet enumeration order: here -0 orders below +0.  NaN is never an extreme.
+ * ycge_obj_parse_host is pure host code - no context, no device: the yardstick and the fallback.  positions (3 * n_positions floats) and
+ *   faces (3 * n_triangles int32) may be NULL (counts only); msg (may be NULL) receives the refusal's text, cut to msg_bytes.
+ * ycge_obj_parse reads the text on the device and HOLDS the result in the context - one parsed OBJ at a time: the next parse,
+ *   ycge_obj_release or ycge_destroy lets go of it.  No scene needed, none touched; frame counter, TAA history, exposure, schedule and
+ *   statistics stay as they are.  It first waits for the frames in flight.  Pageable text goes up through page-locked staging of the
+ *   library, page-locked text directly.  A peer context of the one-process multi-device form is refused; the root parses on devices[0].
+ *   The host parser takes the whole file instead, with the same results and refusals, when the context was created with YCGE_OBJ_HOST in
+ *   the environment, when the file has fewer than YCGE_OBJ_DEVICE_MIN bytes (default 0: the crossover is not yet measured), or when the
+ *   kernels decline it: a float token outside their exact domain (more than 15 significant digits, or a decimal exponent beyond +-22 once
+ *   the fraction digits are counted in), a line that is no comment longer than 1024 bytes.  info->on_device says who parsed.
+ * ycge_obj_read copies the held positions / faces out (either may be NULL) - e.g. for MeshScenes.TryReadObjBoundsNormalized's union-find
+ *   tail, which stays on the host.  ycge_obj_triangles is the tail above for the held OBJ, any number of times: out_triangles 9 *
+ *   n_triangles floats, out_bounds (may be NULL) min xyz, max xyz; translate NULL = (0, 0, 0).  Both and ycge_obj_release without a held
+ *   OBJ: YCGE_ERR_INVALID_ARG (release of nothing: YCGE_OK). */
+typedef struct ycge_obj_info {
+    int32_t n_positions, n_triangles;
+    int64_t n_lines;
+    int32_t on_device;           /* 1: the kernels parsed; 0: the host parser did */
+    int32_t reserved;
+} ycge_obj_info;
+int ycge_obj_parse_host(const uint8_t *text, size_t bytes, float *positions, int32_t *faces, ycge_obj_info *info, char *msg, size_t msg_bytes);
+int ycge_obj_parse(ycge_ctx *ctx, const uint8_t *text, size_t bytes, ycge_obj_info *info);
+int ycge_obj_read(ycge_ctx *ctx, float *positions /* or NULL */, int32_t *faces /* or NULL */);
+int ycge_obj_triangles(ycge_ctx *ctx, int32_t normalize, float target_size, float scale, const float translate[3], float *out_triangles, float out_bounds[6]);
+int ycge_obj_release(ycge_ctx *ctx);
 int ycge_wait(ycge_ctx *ctx);
 /* measurement: durations (ms) of the trace launches of the frames queued since the last call, oldest first (at most the last 1024);
  * waits for the frames in flight */

@@ -100,6 +100,7 @@ int ycge_host_worldgen_world_from_fields(const ycge_world *world, int32_t nx, in
                                          const int32_t *biome, const int32_t *rock, const uint32_t *feature, int32_t gather, int32_t *cells_out, int32_t *passes_out);
 int ycge_debug_worldpregen_stats(ycge_ctx *c, int64_t *out5);        /* the last call of ycge_scene_generate_world, on the root device: anyLeaves passes (the last flips nothing); us of the 2-D field kernels, of the anyLeaves pass loop (wall time: a launch, a stream synchronise and a 4-byte read-back per pass), of the occupancy kernel and its read-back, of the fill kernels */
 int ycge_debug_worldgen_stats(ycge_ctx *c, int64_t *out4);           /* ycge_scene_generate_grids: chunks made on the device, chunks made on the host, the last call's column kernel and fill + tree kernels in us (root device) */
+int ycge_debug_obj_stats(ycge_ctx *c, int64_t *out6);               /* ycge_obj_parse: files the kernels parsed, files the host parser took, why the last one went to the host (0: it did not; 1 a float token outside the exact domain, 2 a line over the cap, 4 YCGE_OBJ_HOST, 8 below YCGE_OBJ_DEVICE_MIN), then wall us of the last parse's line marking + line walk + scans, of its token parsing + used / range / bounds pass, and of the last ycge_obj_triangles' pass.  c = NULL: YCGE_ERR_INVALID_ARG and out6[0..4] = the mark kernel's tile in bytes, the lines a workgroup of the line kernels takes, the line cap in bytes, YCGE_OBJ_DEVICE_MIN and YCGE_OBJ_HOST as parsed now (no device) */
 int ycge_debug_read_post_progress(ycge_ctx *c, uint32_t *dst, size_t n_words);               /* k_atrous_stream's per-band records (profiles/post_bands.py) */
 int ycge_debug_read_wave_prof(ycge_ctx *c, unsigned long long *dst, size_t n_u64);            /* per-wavefront begin / end / steps of a profiling build (profiles/mega_prof.py) */
 int ycge_debug_read_coop_stats(ycge_ctx *c, uint64_t out[16]);                               /* -DYCGE_DBG_COOPSTAT builds */

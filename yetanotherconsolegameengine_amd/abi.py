@@ -151,6 +151,11 @@ class FrameStats(C.Structure):
     ]
 
 
+class ObjInfo(C.Structure):
+    """ycge_obj_info: what ycge_obj_parse / ycge_obj_parse_host found (passed with C.byref)."""
+    _fields_ = [("n_positions", C.c_int32), ("n_triangles", C.c_int32), ("n_lines", C.c_int64), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FlightInfo(C.Structure):
     _fields_ = [("two_trace_streams", C.c_int32), ("placed_gate", C.c_int32), ("post_gate", C.c_int32), ("post_pair", C.c_int32),
                 ("frames_outstanding", C.c_int32), ("stage_pipeline", C.c_int32), ("placed_waits", C.c_uint64)]
@@ -231,6 +236,12 @@ _PROTOTYPES = {
                                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "ycge_video_blit_ansi": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
+    "ycge_obj_parse_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "ycge_obj_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ycge_obj_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ycge_obj_triangles": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "ycge_obj_release": (C.c_int, [C.c_void_p]),
     "ycge_read_buffer": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_set_frame_counter": (C.c_int, [C.c_void_p, C.c_int64]),
     "ycge_read_timed_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -295,6 +306,13 @@ MESH_EMIT_RES_WORDS = 8
 MESH_EMIT_RES = ("tree_built_on_device", "nodes", "record_units", "layout_us", "records_us", "treelets_us")
 MESH_EMIT_STATS = ("device_meshes", "host_meshes", "last_device_emit_us", "arena_bytes")
 
+# test / profiling hook of the OBJ parse (csrc/ycge_obj.cpp), bound where it is used (RaytraceRenderer.obj_stats, obj_geometry below)
+OBJ_HOOK_PROTOTYPES = {
+    "ycge_debug_obj_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+}
+OBJ_STATS = ("device_parses", "host_parses", "last_decline", "lines_us", "parse_us", "triangles_us")
+OBJ_DECLINE_FLOAT_DOMAIN, OBJ_DECLINE_LINE_CAP, OBJ_DECLINE_ENV_HOST, OBJ_DECLINE_BELOW_MIN = 1, 2, 4, 8
+
 _lib = None
 
 
@@ -334,3 +352,33 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if path is None:
         _lib = lib
     return lib
+
+
+def obj_parse_host(data: bytes, lib: C.CDLL | None = None):
+    """ycge_obj_parse_host: the library's host parser alone (no context, no device) -> (positions f32 [nv, 3], faces i32 [nt, 3], ObjInfo).
+    Raises YcgeError with the refusal's text."""
+    import numpy as np
+    L = lib if lib is not None else load_library()
+    fn = L.ycge_obj_parse_host
+    fn.restype, fn.argtypes = _PROTOTYPES["ycge_obj_parse_host"]
+    data = bytes(data)
+    info, msg = ObjInfo(), C.create_string_buffer(256)
+    rc = fn(data, len(data), None, None, C.byref(info), msg, len(msg))
+    if rc != 0:
+        raise YcgeError(rc, msg.value.decode())
+    pos = np.empty((info.n_positions, 3), np.float32)
+    faces = np.empty((info.n_triangles, 3), np.int32)
+    rc = fn(data, len(data), pos.ctypes.data, faces.ctypes.data, C.byref(info), msg, len(msg))
+    if rc != 0:
+        raise YcgeError(rc, msg.value.decode())
+    return pos, faces, info
+
+
+def obj_geometry(lib: C.CDLL | None = None) -> dict:
+    """the OBJ kernels' geometry and the environment's knobs as the library reads them now (no device)"""
+    L = lib if lib is not None else load_library()
+    fn = L.ycge_debug_obj_stats
+    fn.restype, fn.argtypes = OBJ_HOOK_PROTOTYPES["ycge_debug_obj_stats"]
+    out = (C.c_int64 * 6)()
+    fn(None, out)
+    return dict(zip(("tile_bytes", "lines_per_workgroup", "line_cap", "device_min", "env_host"), (int(v) for v in out)))

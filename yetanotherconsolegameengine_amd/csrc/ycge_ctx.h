@@ -107,6 +107,15 @@ uint32_t ycge_launch_ansi_tiles(uint32_t cells);
 int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
                             int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
+size_t ycge_launch_obj_sizes(int which);
+int ycge_launch_obj_count_lines(const uint8_t *text, uint32_t n, uint32_t first, uint32_t *tiles, void *header, hipStream_t stream);
+int ycge_launch_obj_classify(const uint8_t *text, uint32_t n, uint32_t first, const uint32_t *tiles, uint32_t *line_start, uint32_t n_lines, uint32_t *add,
+                             uint32_t *block_pos, uint32_t *block_tri, void *header, hipStream_t stream);
+int ycge_launch_obj_parse(const uint8_t *text, uint32_t n, const uint32_t *line_start, uint32_t n_lines, const uint32_t *add, const uint32_t *block_pos,
+                          const uint32_t *block_tri, float *positions, int32_t *faces, uint32_t n_positions, uint32_t n_triangles, void *header, hipStream_t stream);
+int ycge_launch_obj_used_bounds(const float *positions, const int32_t *faces, uint32_t n_positions, uint32_t n_triangles, uint8_t *used, void *header, hipStream_t stream);
+int ycge_launch_obj_triangles(const float *positions, const int32_t *faces, uint32_t n_triangles, int normalize, const float c[3], float s, int transform,
+                              float scale, const float t[3], float *out, void *header, hipStream_t stream);
 int ycge_launch_grid_encode(const void *descs, int n_grids, void *results, uint32_t n_workgroups, hipStream_t stream);
 int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
@@ -118,6 +127,10 @@ using namespace ycge;
 // on that upload is no slower than the same upload with the host's emit (4 000: 1.53 against 1.44 ms; 16 000: 2.37 against 2.82; config 4:
 // 11.7 against 198 - profiles/mesh_build_rate.json).  Below it the emit's own allocations and two read-backs outweigh the host's loops.
 #define YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT 16000
+
+// ycge_obj_parse hands a file of fewer bytes than this to the host parser: the crossover between ycge_obj_parse_host and the device path
+// (profiles/obj_rate.py) is NOT YET MEASURED, so every file goes to the device.
+#define YCGE_OBJ_DEVICE_MIN_DEFAULT 0
 
 namespace ycge_host {
 
@@ -176,6 +189,8 @@ struct Knobs {
     bool no_coop = false;            // YCGE_NO_COOP: no treelets are built, sparse wavefronts keep the regular walk (A/B of the cooperative walk)
     size_t enc_group_bytes = (size_t)256 << 20;   // YCGE_ENC_GROUP_BYTES: raw cells staged per encode group (attach / generate sub-batches); a larger grid is a group of its own
     bool worldgen_host = false;      // YCGE_WORLDGEN_HOST: ycge_scene_generate_grids makes the cells with the host generator (ycge_worldgen.cpp) and sends them up as an attach does
+    bool obj_host = false;           // YCGE_OBJ_HOST: ycge_obj_parse reads every file with the host parser (ycge_obj_parse_host's)
+    long long obj_device_min = YCGE_OBJ_DEVICE_MIN_DEFAULT;   // YCGE_OBJ_DEVICE_MIN: ... and files of fewer bytes than this (crossover not yet measured)
     bool exposure_serial = false;    // YCGE_EXPOSURE_SERIAL: the one-lane chain instead of the chunked exact evaluation
     void read()
     {
@@ -218,6 +233,8 @@ struct Knobs {
         flight_no_begin = geti("YCGE_FLIGHT_NO_BEGIN", 0) != 0;
         post_dbg_free = geti("YCGE_POST_DBG_FREE", 0) != 0;
         exposure_serial = getenv("YCGE_EXPOSURE_SERIAL") != nullptr;
+        obj_host = getenv("YCGE_OBJ_HOST") != nullptr;
+        if (const char *e = getenv("YCGE_OBJ_DEVICE_MIN")) obj_device_min = atoll(e);
         no_coop = getenv("YCGE_NO_COOP") != nullptr;
         res_sched_every = geti("YCGE_RES_SCHED_EVERY", 0);
         bfs_rays = geti("YCGE_BFS", 0);
@@ -366,6 +383,19 @@ struct VideoState {
     DevBuf<float> sdr;                                 // its chexels {top rgb, bottom rgb}
     PinnedBuf stage;                                   // page-locked staging of a pageable source frame
     int64_t table_builds = 0;
+};
+// the OBJ a context holds (ycge_obj_parse, ycge_obj.cpp): one at a time, whoever parsed it; nothing a frame reads
+struct ObjState {
+    bool held = false;
+    int32_t n_positions = 0, n_triangles = 0, on_device = 0;
+    int64_t n_lines = 0;
+    DevBuf<float> positions, triangles;                // 3 per vertex; the last ycge_obj_triangles' soup, 9 per triangle
+    DevBuf<int32_t> faces;                             // 3 per triangle
+    DevBuf<uint8_t> header;                            // what the kernels report (ObjHeader, ycge_obj.hip)
+    PinnedBuf stage;                                   // page-locked staging of a pageable text, one chunk at a time
+    float used_min[3] = {0, 0, 0}, used_max[3] = {0, 0, 0};   // the box of the vertices any face uses
+    int64_t device_parses = 0, host_parses = 0, last_decline = 0;
+    double last_us[3] = {0, 0, 0};                     // lines + classify + scans; token parsing + used / range / bounds; the last triangle pass
 };
 
 struct ycge_ctx {
@@ -617,6 +647,7 @@ struct ycge_ctx {
     // buffers per post parity, the threshold tables, the staging of pageable destinations
     ChexelState chexels;
     VideoState video;            // Video mode (ycge_video_blit, ycge_video.cpp)
+    ObjState obj;                // the parsed OBJ (ycge_obj_parse, ycge_obj.cpp)
 
     ycge_ctx() = default;
     ycge_ctx(const ycge_ctx &) = delete;
@@ -742,4 +773,11 @@ int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src
 int video_read_sdr(ycge_ctx *c, hipStream_t stream, const float *d_sdr, float *out_sdr);
 int video_host_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0, float *wx, int32_t *y0, float *wy, float *geom3);
 int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out);
+// ycge_obj.cpp: MeshLoader.FromObj from file bytes - the bodies of ycge_obj_parse_host (no context), ycge_obj_parse / _read / _triangles / _release and ycge_debug_obj_stats
+int obj_parse_host(const uint8_t *text, size_t bytes, float *positions, int32_t *faces, ycge_obj_info *info, char *msg, size_t msg_bytes);
+int obj_parse(ycge_ctx *c, const uint8_t *text, size_t bytes, ycge_obj_info *info);
+int obj_read(ycge_ctx *c, float *positions, int32_t *faces);
+int obj_triangles(ycge_ctx *c, int32_t normalize, float target_size, float scale, const float translate[3], float *out_triangles, float out_bounds[6]);
+int obj_release(ycge_ctx *c);
+int obj_stats(ycge_ctx *c, int64_t *out6);
 } // namespace ycge_host

@@ -1684,6 +1684,51 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// OBJ meshes from file bytes (ycge_obj.cpp): MeshLoader.FromObj up to the triangles ycge_mesh.triangles takes.  The host parser alone ...
+int ycge_obj_parse_host(const uint8_t *text, size_t bytes, float *positions, int32_t *faces, ycge_obj_info *info, char *msg, size_t msg_bytes)
+try {
+    return obj_parse_host(text, bytes, positions, faces, info, msg, msg_bytes);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// ... the parse on the device, held by the context ...
+int ycge_obj_parse(ycge_ctx *c, const uint8_t *text, size_t bytes, ycge_obj_info *info)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return obj_parse(c, text, bytes, info);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ... its positions and faces ...
+int ycge_obj_read(ycge_ctx *c, float *positions, int32_t *faces)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return obj_read(c, positions, faces);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ... FromObj's tail: normalise, scale / translate, gather, bounds ...
+int ycge_obj_triangles(ycge_ctx *c, int32_t normalize, float target_size, float scale, const float translate[3], float *out_triangles, float out_bounds[6])
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return obj_triangles(c, normalize, target_size, scale, translate, out_triangles, out_bounds);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_obj_release(ycge_ctx *c)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return obj_release(c);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hook: who parsed, why, and the last parse's phases (include/ycge_hooks.h)
+int ycge_debug_obj_stats(ycge_ctx *c, int64_t *out6)
+try {
+    return obj_stats(c, out6);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 int ycge_resize(ycge_ctx *c, int32_t fbw, int32_t fbh, int32_t ss)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;

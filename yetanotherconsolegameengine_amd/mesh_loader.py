@@ -151,3 +151,24 @@ def add_mesh_auto_ground(pos: np.ndarray, faces: np.ndarray, scale: float, targe
     y_translate = f32(target_pos[1]) - min_y_norm * f32(scale) + f32(0.01)
     translate = (f32(target_pos[0]), y_translate, f32(target_pos[2]))
     return from_obj_arrays(pos, faces, scale=scale, translate=translate, normalize=True, target_size=1.0)
+
+
+def from_obj_device(renderer, data, scale: float = 1.0, translate=(0.0, 0.0, 0.0), normalize: bool = True, target_size: float = 1.0) -> np.ndarray:
+    """MeshLoader.FromObj with the file read on the device (RaytraceRenderer.ParseObj / ObjTriangles): `data` is the file's bytes or a
+    path; returns float32 triangles [nt, 3, 3].  The renderer holds the parsed OBJ afterwards."""
+    renderer.ParseObj(data)
+    return renderer.ObjTriangles(scale=scale, translate=translate, normalize=normalize, target_size=target_size)[0]
+
+
+def add_mesh_auto_ground_device(renderer, data, scale: float, target_pos) -> np.ndarray:
+    """MeshScenes.AddMeshAutoGround with ONE parse, on the device: the positions and faces come back once for the union-find tail of
+    TryReadObjBoundsNormalized (which stays on the host), the placed triangles are made on the device."""
+    renderer.ParseObj(data)
+    pos, faces = renderer.ReadObj()
+    b = read_obj_bounds_normalized(pos, faces)
+    if b is None:
+        raise FileNotFoundError("OBJ not found or empty")
+    min_y_norm = b[0][1]
+    y_translate = f32(target_pos[1]) - min_y_norm * f32(scale) + f32(0.01)
+    translate = (f32(target_pos[0]), y_translate, f32(target_pos[2]))
+    return renderer.ObjTriangles(scale=scale, translate=translate, normalize=True, target_size=1.0)[0]

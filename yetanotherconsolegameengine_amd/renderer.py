@@ -208,6 +208,49 @@ class RaytraceRenderer:
         self._check(self.L.ycge_debug_worldgen_stats(self.ctx, out))
         return dict(zip(("device_chunks", "host_chunks", "last_columns_us", "last_fill_us"), (int(v) for v in out)))
 
+    # ---------------------------------------------------------------- OBJ meshes from file bytes (MeshLoader.FromObj on the device)
+    def ParseObj(self, data) -> abi.ObjInfo:
+        """ycge_obj_parse: `data` is the file's bytes or a path.  The context holds the parsed OBJ until the next ParseObj, ReleaseObj or close."""
+        if not isinstance(data, (bytes, bytearray, memoryview)):
+            with open(data, "rb") as fh:
+                data = fh.read()
+        data = bytes(data)
+        info = abi.ObjInfo()
+        self._check(self.L.ycge_obj_parse(self.ctx, data, len(data), C.byref(info)))
+        self._obj_info = info
+        return info
+
+    def ReadObj(self):
+        """ycge_obj_read -> (positions f32 [nv, 3], faces i32 [nt, 3]) of the held OBJ"""
+        info = getattr(self, "_obj_info", None)
+        pos = np.empty((info.n_positions if info else 0, 3), np.float32)
+        faces = np.empty((info.n_triangles if info else 0, 3), np.int32)
+        self._check(self.L.ycge_obj_read(self.ctx, pos.ctypes.data if info else None, faces.ctypes.data if info else None))
+        return pos, faces
+
+    def ObjTriangles(self, scale: float = 1.0, translate=(0.0, 0.0, 0.0), normalize: bool = True, target_size: float = 1.0):
+        """ycge_obj_triangles: MeshLoader.FromObj's tail for the held OBJ -> (triangles f32 [nt, 3, 3], bounds f32 [6] = min xyz, max xyz)"""
+        info = getattr(self, "_obj_info", None)
+        tris = np.empty((info.n_triangles if info else 0, 3, 3), np.float32)
+        bounds = np.empty(6, np.float32)
+        t = (C.c_float * 3)(*[float(np.float32(v)) for v in translate])
+        self._check(self.L.ycge_obj_triangles(self.ctx, int(bool(normalize)), float(np.float32(target_size)), float(np.float32(scale)), t,
+                                               tris.ctypes.data if info else None, bounds.ctypes.data))
+        return tris, bounds
+
+    def ReleaseObj(self) -> None:
+        self._obj_info = None
+        self._check(self.L.ycge_obj_release(self.ctx))
+
+    def obj_stats(self) -> dict:
+        """Who parsed: files the kernels parsed, files the host parser took, why the last one went to the host (abi.OBJ_DECLINE_*; 0: it did
+        not), wall microseconds of the last parse's line passes, of its token and index passes, of the last ObjTriangles' pass."""
+        out = (C.c_int64 * 6)()
+        fn = self.L.ycge_debug_obj_stats
+        fn.restype, fn.argtypes = abi.OBJ_HOOK_PROTOTYPES["ycge_debug_obj_stats"]
+        self._check(fn(self.ctx, out))
+        return dict(zip(abi.OBJ_STATS, (int(v) for v in out)))
+
     def DetachGrids(self, indices) -> None:
         """Gives the grids' slots back; refused while Scene.Objects (as of the last UpdateObjects) refer to one of them."""
         indices = [int(i) for i in indices]
