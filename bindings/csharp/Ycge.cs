@@ -173,6 +173,17 @@ namespace ConsoleGame.RayTracing.Native
         public int OnDevice, Reserved;
     }
 
+    // ycge_obj_ground_info, 64 bytes (an out parameter only, as above)
+    public struct YObjGroundInfo
+    {
+        public float MinX, MinY, MinZ, MaxX, MaxY, MaxZ;
+        public float CentroidX, CentroidY, CentroidZ;
+        public float Extent;
+        public int NComponents;
+        public int ComponentFaces, ComponentVertices, FirstFace;
+        public int OnDevice, Reserved;
+    }
+
     public enum YStatus { Ok = 0, InvalidArg = -1, NoScene = -2, Device = -3, Unsupported = -4, OutOfMemory = -5, StackDepth = -6, NoDeviceCode = -7, Internal = -8 }
     public enum YMaterialKind { Constant = 0, Checker = 1, Textured = 2 }
     public enum YExchange { PeerPush = 0, Rccl = 1 }
@@ -230,6 +241,10 @@ namespace ConsoleGame.RayTracing.Native
         [DllImport(Lib)] public static extern int ycge_obj_read(IntPtr ctx, float* positions, int* faces);
         [DllImport(Lib)] public static extern int ycge_obj_triangles(IntPtr ctx, int normalize, float targetSize, float scale, float* translate, float* outTriangles, float* outBounds);
         [DllImport(Lib)] public static extern int ycge_obj_release(IntPtr ctx);
+        // MeshScenes.AddMeshAutoGround on the held OBJ (largest component, centroid, bounds on the device).  info: a YObjGroundInfo; outInfo may be null
+        [DllImport(Lib)] public static extern int ycge_obj_ground_host(float* positions, int nPositions, int* faces, int nTriangles, out YObjGroundInfo info);
+        [DllImport(Lib)] public static extern int ycge_obj_ground(IntPtr ctx, out YObjGroundInfo info);
+        [DllImport(Lib)] public static extern int ycge_obj_triangles_auto_ground(IntPtr ctx, float scale, float* target, float* outTriangles, float* outBounds, YObjGroundInfo* outInfo);
         [DllImport(Lib)] public static extern int ycge_wait(IntPtr ctx);
         [DllImport(Lib)] public static extern int ycge_async_trace_times(IntPtr ctx, float* msOut, int capacity, out int nOut);
         [DllImport(Lib)] public static extern int ycge_flight_query(IntPtr ctx, out YFlightInfo info);

@@ -569,10 +569,10 @@ int ycge_video_blit_ansi(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int
  *   the environment, when the file has fewer than YCGE_OBJ_DEVICE_MIN bytes (default 0: the crossover is not yet measured), or when the
  *   kernels decline it: a float token outside their exact domain (more than 15 significant digits, or a decimal exponent beyond +-22 once
  *   the fraction digits are counted in), a line that is no comment longer than 1024 bytes.  info->on_device says who parsed.
- * ycge_obj_read copies the held positions / faces out (either may be NULL) - e.g. for MeshScenes.TryReadObjBoundsNormalized's union-find
- *   tail, which stays on the host.  ycge_obj_triangles is the tail above for the held OBJ, any number of times: out_triangles 9 *
- *   n_triangles floats, out_bounds (may be NULL) min xyz, max xyz; translate NULL = (0, 0, 0).  Both and ycge_obj_release without a held
- *   OBJ: YCGE_ERR_INVALID_ARG (release of nothing: YCGE_OK). */
+ * ycge_obj_read copies the held positions / faces out (either may be NULL); MeshScenes.TryReadObjBoundsNormalized's union-find tail no
+ *   longer needs them: ycge_obj_ground, below, runs it on the device.  ycge_obj_triangles is the tail above for the held OBJ, any number
+ *   of times: out_triangles 9 * n_triangles floats, out_bounds (may be NULL) min xyz, max xyz; translate NULL = (0, 0, 0).  Both and
+ *   ycge_obj_release without a held OBJ: YCGE_ERR_INVALID_ARG (release of nothing: YCGE_OK). */
 typedef struct ycge_obj_info {
     int32_t n_positions, n_triangles;
     int64_t n_lines;
@@ -584,6 +584,43 @@ int ycge_obj_parse(ycge_ctx *ctx, const uint8_t *text, size_t bytes, ycge_obj_in
 int ycge_obj_read(ycge_ctx *ctx, float *positions /* or NULL */, int32_t *faces /* or NULL */);
 int ycge_obj_triangles(ycge_ctx *ctx, int32_t normalize, float target_size, float scale, const float translate[3], float *out_triangles, float out_bounds[6]);
 int ycge_obj_release(ycge_ctx *ctx);
+/* --- MeshScenes.AddMeshAutoGround (Scenes/MeshScenes.cs:173-184) on the held OBJ: what TryReadObjBoundsNormalized (:233-330) does behind its
+ * parse - every mesh scene of the reference goes through it - and the placed triangles, with no geometry coming back before them.  Added
+ * after ABI 10 without changing it (detect by symbol lookup).  The contract, bit for bit (tests/obj_ground_restatement.py is its yardstick):
+ *   Components  vertices are joined by the edges (a, b) and (b, c) of every face; vertices no face names do not matter.
+ *   The chosen  component: the one with the most faces; among equal counts the one whose first face comes first in file order (the
+ *               reference's Dictionary enumerates in insertion order and compares with a strict >).  NOT the one with the lowest vertex.
+ *   Centroid    cx = 0; for the kept faces in file order cx += ((A.x + B.x) + C.x) * (1 / 3f), every operation a rounded binary32 one, the
+ *               product rounded before it is added; then cx *= 1 / (float)kept_faces.  y, z alike.  The order of the sum is part of the result.
+ *   Bounds      over the vertices of the kept faces, of pos - centroid; min / max start at +inf / -inf, NaN never replaces an extreme, and
+ *               -0 orders below +0 (as in ycge_obj_triangles' bounds; the reference's sign of a zero extreme follows HashSet order and
+ *               cannot reach AddMeshAutoGround's result).
+ *   Normalise   extent = rx; if (ry > extent) extent = ry; if (rz > extent) extent = rz; if (extent <= 0) extent = 1; s = 1 / extent;
+ *               min = rMin * s, max = rMax * s.  A NaN extent passes every compare and stays NaN; infinite positions (the host parser's
+ *               1e39) flow through as plain binary32 arithmetic.
+ *   Placement   yTranslate = (target.y - min.y * scale) + 0.01f; then ycge_obj_triangles with normalize = 1, target_size = 1, scale and
+ *               translate = (target.x, yTranslate, target.z).
+ * ycge_obj_ground_host is pure host code - no context, no device: the yardstick and the fallback.  NULL arrays, counts <= 0 and an index
+ *   out of range: YCGE_ERR_INVALID_ARG.
+ * ycge_obj_ground works on the held OBJ, any number of times, with the same answer each time; towards frames in flight, peer contexts and
+ *   a missing OBJ it behaves as ycge_obj_triangles does, and it touches nothing a frame reads.  The kernels (csrc/ycge_obj_ground.hip)
+ *   label the components with a lock-free union-find, count faces per component, write one centroid term per face and add them in file
+ *   order with one lane per axis; info->on_device says who ran the tail.  The host tail runs instead (on the held arrays, read back) when
+ *   YCGE_OBJ_GROUND_HOST is set, for OBJs of fewer triangles than YCGE_OBJ_GROUND_DEVICE_MIN (both read once, at ycge_create), and
+ *   when a kernel passes one of its loop bounds.
+ * ycge_obj_triangles_auto_ground does all of it in one call: out_triangles 9 * n_triangles floats, out_bounds (may be NULL) min xyz, max
+ *   xyz of the placed triangles, out_info (may be NULL) what ycge_obj_ground found. */
+typedef struct ycge_obj_ground_info {      /* 64 bytes */
+    float min[3], max[3];                  /* TryReadObjBoundsNormalized's out min / max */
+    float centroid[3];                     /* cx, cy, cz after *= invT */
+    float extent;                          /* after the <= 0 rule */
+    int32_t n_components;                  /* components that own at least one face */
+    int32_t component_faces, component_vertices, first_face;   /* of the chosen one */
+    int32_t on_device, reserved;           /* 1: the kernels ran the tail; 0: the host tail did */
+} ycge_obj_ground_info;
+int ycge_obj_ground_host(const float *positions, int32_t n_positions, const int32_t *faces, int32_t n_triangles, ycge_obj_ground_info *out);
+int ycge_obj_ground(ycge_ctx *ctx, ycge_obj_ground_info *out);
+int ycge_obj_triangles_auto_ground(ycge_ctx *ctx, float scale, const float target[3], float *out_triangles, float out_bounds[6], ycge_obj_ground_info *out_info /* or NULL */);
 int ycge_wait(ycge_ctx *ctx);
 /* measurement: durations (ms) of the trace launches of the frames queued since the last call, oldest first (at most the last 1024);
  * waits for the frames in flight */

@@ -156,6 +156,12 @@ class ObjInfo(C.Structure):
     _fields_ = [("n_positions", C.c_int32), ("n_triangles", C.c_int32), ("n_lines", C.c_int64), ("on_device", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ObjGroundInfo(C.Structure):
+    """ycge_obj_ground_info, 64 bytes: what ycge_obj_ground / ycge_obj_ground_host found (passed with C.byref)."""
+    _fields_ = [("min", C.c_float * 3), ("max", C.c_float * 3), ("centroid", C.c_float * 3), ("extent", C.c_float), ("n_components", C.c_int32),
+                ("component_faces", C.c_int32), ("component_vertices", C.c_int32), ("first_face", C.c_int32), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FlightInfo(C.Structure):
     _fields_ = [("two_trace_streams", C.c_int32), ("placed_gate", C.c_int32), ("post_gate", C.c_int32), ("post_pair", C.c_int32),
                 ("frames_outstanding", C.c_int32), ("stage_pipeline", C.c_int32), ("placed_waits", C.c_uint64)]
@@ -242,6 +248,10 @@ _PROTOTYPES = {
     "ycge_obj_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ycge_obj_triangles": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "ycge_obj_release": (C.c_int, [C.c_void_p]),
+    # (out / out_info: a ycge_obj_ground_info, passed with C.byref(abi.ObjGroundInfo); out_info may be None)
+    "ycge_obj_ground_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ycge_obj_ground": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ycge_obj_triangles_auto_ground": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ycge_read_buffer": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_set_frame_counter": (C.c_int, [C.c_void_p, C.c_int64]),
     "ycge_read_timed_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -312,6 +322,14 @@ OBJ_HOOK_PROTOTYPES = {
 }
 OBJ_STATS = ("device_parses", "host_parses", "last_decline", "lines_us", "parse_us", "triangles_us")
 OBJ_DECLINE_FLOAT_DOMAIN, OBJ_DECLINE_LINE_CAP, OBJ_DECLINE_ENV_HOST, OBJ_DECLINE_BELOW_MIN = 1, 2, 4, 8
+# ... and of the auto-ground tail (csrc/ycge_obj_ground.hip), bound where they are used (RaytraceRenderer.obj_ground_stats, obj_ground_geometry below)
+OBJ_GROUND_HOOK_PROTOTYPES = {
+    "ycge_debug_obj_ground_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ycge_debug_obj_ground_phases": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+}
+OBJ_GROUND_STATS = ("device_tails", "host_tails", "last_decline", "rounds", "serial_sums", "last_us")
+OBJ_GROUND_PHASES = ("label_us", "select_us", "terms_us", "sums_us", "bounds_us")
+OBJ_GROUND_DECLINE_FIND_BOUND, OBJ_GROUND_DECLINE_ROUND_CAP, OBJ_GROUND_DECLINE_ENV_HOST, OBJ_GROUND_DECLINE_BELOW_MIN = 1, 2, 4, 8
 
 _lib = None
 
@@ -382,3 +400,29 @@ def obj_geometry(lib: C.CDLL | None = None) -> dict:
     out = (C.c_int64 * 6)()
     fn(None, out)
     return dict(zip(("tile_bytes", "lines_per_workgroup", "line_cap", "device_min", "env_host"), (int(v) for v in out)))
+
+
+def obj_ground_host(pos, faces, lib: C.CDLL | None = None) -> ObjGroundInfo:
+    """ycge_obj_ground_host: the library's host tail alone (no context, no device) on positions f32 [nv, 3] and faces i32 [nt, 3].
+    Raises YcgeError when it refuses the arrays."""
+    import numpy as np
+    L = lib if lib is not None else load_library()
+    fn = L.ycge_obj_ground_host
+    fn.restype, fn.argtypes = _PROTOTYPES["ycge_obj_ground_host"]
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    info = ObjGroundInfo()
+    rc = fn(pos.ctypes.data, len(pos), faces.ctypes.data, len(faces), C.byref(info))
+    if rc != 0:
+        raise YcgeError(rc, "ycge_obj_ground_host refused the arrays")
+    return info
+
+
+def obj_ground_geometry(lib: C.CDLL | None = None) -> dict:
+    """the auto-ground kernels' geometry and the environment's knobs as the library reads them now (no device)"""
+    L = lib if lib is not None else load_library()
+    fn = L.ycge_debug_obj_ground_stats
+    fn.restype, fn.argtypes = OBJ_GROUND_HOOK_PROTOTYPES["ycge_debug_obj_ground_stats"]
+    out = (C.c_int64 * 6)()
+    fn(None, out)
+    return dict(zip(("sum_chunk", "round_cap", "device_min_default", "device_min", "env_host"), (int(v) for v in out)))

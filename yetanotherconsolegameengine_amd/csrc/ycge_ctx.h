@@ -116,6 +116,14 @@ int ycge_launch_obj_parse(const uint8_t *text, uint32_t n, const uint32_t *line_
 int ycge_launch_obj_used_bounds(const float *positions, const int32_t *faces, uint32_t n_positions, uint32_t n_triangles, uint8_t *used, void *header, hipStream_t stream);
 int ycge_launch_obj_triangles(const float *positions, const int32_t *faces, uint32_t n_triangles, int normalize, const float c[3], float s, int transform,
                               float scale, const float t[3], float *out, void *header, hipStream_t stream);
+size_t ycge_launch_obj_ground_sizes(int which);
+int ycge_launch_obj_ground_round(const int32_t *faces, uint32_t n_triangles, uint32_t n_positions, uint32_t *parent, int first, void *header, hipStream_t stream);
+int ycge_launch_obj_ground_select(const int32_t *faces, uint32_t n_triangles, uint32_t n_positions, const uint32_t *parent, uint32_t *count, uint32_t *first, void *header,
+                                  hipStream_t stream);
+int ycge_launch_obj_ground_terms(const float *positions, const int32_t *faces, uint32_t n_triangles, uint32_t n_positions, const uint32_t *parent, float *terms, uint32_t padded,
+                                 uint8_t *used, void *header, hipStream_t stream);
+int ycge_launch_obj_ground_sum(const float *terms, uint32_t padded, void *header, hipStream_t stream);
+int ycge_launch_obj_ground_bounds(const float *positions, uint32_t n_positions, const uint8_t *used, void *header, hipStream_t stream);
 int ycge_launch_grid_encode(const void *descs, int n_grids, void *results, uint32_t n_workgroups, hipStream_t stream);
 int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
@@ -131,6 +139,12 @@ using namespace ycge;
 // ycge_obj_parse hands a file of fewer bytes than this to the host parser: the crossover between ycge_obj_parse_host and the device path
 // (profiles/obj_rate.py) is NOT YET MEASURED, so every file goes to the device.
 #define YCGE_OBJ_DEVICE_MIN_DEFAULT 0
+
+// ycge_obj_ground hands an OBJ of fewer triangles than this to the host tail (ycge_obj_ground_host): the measured crossover between
+// ycge_obj_read + the host tail and the kernels of ycge_obj_ground.hip (profiles/obj_ground_rate.json: at 131 081 triangles 0.95 ms against
+// 1.05, at 871 209 3.4 against 9.3; at 16 009 the host side wins, 0.16 against 0.24: the tail's launches and two read-backs cost 0.14 ms
+// before any work is done).
+#define YCGE_OBJ_GROUND_DEVICE_MIN_DEFAULT 131081
 
 namespace ycge_host {
 
@@ -191,6 +205,9 @@ struct Knobs {
     bool worldgen_host = false;      // YCGE_WORLDGEN_HOST: ycge_scene_generate_grids makes the cells with the host generator (ycge_worldgen.cpp) and sends them up as an attach does
     bool obj_host = false;           // YCGE_OBJ_HOST: ycge_obj_parse reads every file with the host parser (ycge_obj_parse_host's)
     long long obj_device_min = YCGE_OBJ_DEVICE_MIN_DEFAULT;   // YCGE_OBJ_DEVICE_MIN: ... and files of fewer bytes than this (crossover not yet measured)
+    bool obj_ground_host = false;    // YCGE_OBJ_GROUND_HOST: ycge_obj_ground takes every held OBJ through the host tail (ycge_obj_ground_host's)
+    long long obj_ground_device_min = YCGE_OBJ_GROUND_DEVICE_MIN_DEFAULT;   // YCGE_OBJ_GROUND_DEVICE_MIN: ... and OBJs of fewer triangles than this
+    bool obj_ground_phases = false;  // YCGE_OBJ_GROUND_PHASES: a stream synchronise behind every phase of the device tail (ycge_debug_obj_ground_phases: what each costs)
     bool exposure_serial = false;    // YCGE_EXPOSURE_SERIAL: the one-lane chain instead of the chunked exact evaluation
     void read()
     {
@@ -235,6 +252,9 @@ struct Knobs {
         exposure_serial = getenv("YCGE_EXPOSURE_SERIAL") != nullptr;
         obj_host = getenv("YCGE_OBJ_HOST") != nullptr;
         if (const char *e = getenv("YCGE_OBJ_DEVICE_MIN")) obj_device_min = atoll(e);
+        obj_ground_host = getenv("YCGE_OBJ_GROUND_HOST") != nullptr;
+        if (const char *e = getenv("YCGE_OBJ_GROUND_DEVICE_MIN")) obj_ground_device_min = atoll(e);
+        obj_ground_phases = getenv("YCGE_OBJ_GROUND_PHASES") != nullptr;
         no_coop = getenv("YCGE_NO_COOP") != nullptr;
         res_sched_every = geti("YCGE_RES_SCHED_EVERY", 0);
         bfs_rays = geti("YCGE_BFS", 0);
@@ -396,6 +416,13 @@ struct ObjState {
     float used_min[3] = {0, 0, 0}, used_max[3] = {0, 0, 0};   // the box of the vertices any face uses
     int64_t device_parses = 0, host_parses = 0, last_decline = 0;
     double last_us[3] = {0, 0, 0};                     // lines + classify + scans; token parsing + used / range / bounds; the last triangle pass
+    // ycge_obj_ground (ycge_obj_ground.hip): union-find parents, faces and first face per root, the three term planes, the chosen component's vertices
+    DevBuf<uint32_t> ground_parent, ground_count, ground_first;
+    DevBuf<float> ground_terms;
+    DevBuf<uint8_t> ground_used, ground_header;
+    int64_t ground_device_tails = 0, ground_host_tails = 0, ground_last_decline = 0, ground_rounds = 0;
+    double ground_last_us = 0;
+    double ground_phase_us[5] = {0, 0, 0, 0, 0};       // YCGE_OBJ_GROUND_PHASES: labelling, count + winner, terms, the three sums, bounds + read-back
 };
 
 struct ycge_ctx {
@@ -780,4 +807,10 @@ int obj_read(ycge_ctx *c, float *positions, int32_t *faces);
 int obj_triangles(ycge_ctx *c, int32_t normalize, float target_size, float scale, const float translate[3], float *out_triangles, float out_bounds[6]);
 int obj_release(ycge_ctx *c);
 int obj_stats(ycge_ctx *c, int64_t *out6);
+// ... and MeshScenes.AddMeshAutoGround on the held OBJ: the bodies of ycge_obj_ground_host (no context), ycge_obj_ground, ycge_obj_triangles_auto_ground and their hooks
+int obj_ground_host(const float *positions, int32_t n_positions, const int32_t *faces, int32_t n_triangles, ycge_obj_ground_info *out);
+int obj_ground(ycge_ctx *c, ycge_obj_ground_info *out);
+int obj_triangles_auto_ground(ycge_ctx *c, float scale, const float target[3], float *out_triangles, float out_bounds[6], ycge_obj_ground_info *out_info);
+int obj_ground_stats(ycge_ctx *c, int64_t *out6);
+int obj_ground_phases(ycge_ctx *c, int64_t *out5);
 } // namespace ycge_host

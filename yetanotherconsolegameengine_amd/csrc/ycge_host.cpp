@@ -1715,6 +1715,29 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// ... MeshScenes.TryReadObjBoundsNormalized behind its parse: the host tail alone ...
+int ycge_obj_ground_host(const float *positions, int32_t n_positions, const int32_t *faces, int32_t n_triangles, ycge_obj_ground_info *out)
+try {
+    return obj_ground_host(positions, n_positions, faces, n_triangles, out);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// ... the same on the held OBJ, on the device ...
+int ycge_obj_ground(ycge_ctx *c, ycge_obj_ground_info *out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return obj_ground(c, out);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ... and AddMeshAutoGround's placed triangles in one call
+int ycge_obj_triangles_auto_ground(ycge_ctx *c, float scale, const float target[3], float *out_triangles, float out_bounds[6], ycge_obj_ground_info *out_info)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return obj_triangles_auto_ground(c, scale, target, out_triangles, out_bounds, out_info);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 int ycge_obj_release(ycge_ctx *c)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;
@@ -1726,6 +1749,19 @@ catch (...) { return ycge_host::abi_catch(c); }
 int ycge_debug_obj_stats(ycge_ctx *c, int64_t *out6)
 try {
     return obj_stats(c, out6);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hooks: who took the auto-ground tail, why, its rounds and time; with YCGE_OBJ_GROUND_PHASES, what each phase cost (include/ycge_hooks.h)
+int ycge_debug_obj_ground_stats(ycge_ctx *c, int64_t *out6)
+try {
+    return obj_ground_stats(c, out6);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_debug_obj_ground_phases(ycge_ctx *c, int64_t *out5)
+try {
+    return obj_ground_phases(c, out5);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

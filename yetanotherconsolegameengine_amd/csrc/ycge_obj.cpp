@@ -1,6 +1,8 @@
 // ycge_obj.cpp - OBJ meshes from file bytes: MeshLoader.FromObj (RayTracing/MeshLoader.cs:12-149) up to the float soup ycge_mesh.triangles
 // takes (ycge_obj_parse_host, ycge_obj_parse, _read, _triangles, _release; kernels: ycge_obj.hip; the reading rules, the token routines
-// and the host parser: ycge_obj.h).  The entry points themselves stand in ycge_host.cpp, beside ycge_scene_upload.
+// and the host parser: ycge_obj.h), and MeshScenes.AddMeshAutoGround on the held OBJ (ycge_obj_ground_host, ycge_obj_ground,
+// ycge_obj_triangles_auto_ground; kernels: ycge_obj_ground.hip; the contract and the host tail: ycge_obj.h).  The entry points themselves
+// stand in ycge_host.cpp, beside ycge_scene_upload.
 //
 // A parse is: the text up (through page-locked staging when the caller's array is pageable), the lines marked and counted, one read-back
 // of the line count; the line table, each line's kind, two scans, one read-back of the position and triangle counts; the tokens parsed
@@ -18,6 +20,16 @@ struct ObjHeaderHost {
     uint32_t decline, n_lines, n_positions, n_triangles;
     uint32_t used_box[6], tri_box[6];
 };
+
+// GroundHeader of ycge_obj_ground.hip, as the host reads it back
+struct GroundHeaderHost {
+    unsigned long long best;
+    uint32_t decline, changed, n_components, n_used;
+    uint32_t box[6];
+    float sum[3], centroid[3];
+    uint32_t pad[2];
+};
+static_assert(sizeof(ycge_obj_ground_info) == 64 && sizeof(ycge_obj::GroundInfo) == sizeof(ycge_obj_ground_info), "ycge_obj_ground_info is 64 bytes, and ycge_obj.h mirrors it");
 
 float unordered(uint32_t o)
 {
@@ -68,6 +80,7 @@ static void obj_drop(ycge_ctx *c)
     O.held = false;
     O.n_positions = O.n_triangles = O.on_device = 0; O.n_lines = 0;
     O.positions.release(); O.faces.release(); O.triangles.release(); O.header.release(); O.stage.release();
+    O.ground_parent.release(); O.ground_count.release(); O.ground_first.release(); O.ground_terms.release(); O.ground_used.release(); O.ground_header.release();
 }
 
 static int read_header(ycge_ctx *c, ObjHeaderHost &h)
@@ -282,6 +295,150 @@ int obj_stats(ycge_ctx *c, int64_t *out6)
     const ObjState &O = c->obj;
     out6[0] = O.device_parses; out6[1] = O.host_parses; out6[2] = O.last_decline;
     for (int a = 0; a < 3; a++) out6[3 + a] = (int64_t)O.last_us[a];
+    return YCGE_OK;
+}
+
+int obj_ground_host(const float *positions, int32_t n_positions, const int32_t *faces, int32_t n_triangles, ycge_obj_ground_info *out)
+{
+    if (!out) return YCGE_ERR_INVALID_ARG;
+    ycge_obj::GroundInfo g;
+    const int rc = ycge_obj::ground_host(positions, n_positions, faces, n_triangles, g);
+    std::memcpy(out, &g, sizeof g);
+    return rc;
+}
+
+// The kernels' tail.  YCGE_OK with *declined = 0: *out is filled; *declined != 0: the host tail's OBJ; a status: failed.
+static int ground_on_device(ycge_ctx *c, ycge_obj_ground_info *out, int *declined)
+{
+    ObjState &O = c->obj;
+    *declined = 0;
+    const uint32_t nv = (uint32_t)O.n_positions, nf = (uint32_t)O.n_triangles;
+    const uint32_t chunk = (uint32_t)ycge_launch_obj_ground_sizes(1), padded = (nf + chunk - 1u) / chunk * chunk;
+    const int round_cap = (int)ycge_launch_obj_ground_sizes(2);
+    const bool phases = c->knobs.obj_ground_phases;          // a stream synchronise behind every phase: what each one costs
+    for (double &u : O.ground_phase_us) u = 0.0;
+    HIP_TRY(c, O.ground_header.reserve(ycge_launch_obj_ground_sizes(0)));
+    HIP_TRY(c, O.ground_parent.reserve(nv));
+    HIP_TRY(c, O.ground_count.reserve(nv));
+    HIP_TRY(c, O.ground_first.reserve(nv));
+    HIP_TRY(c, O.ground_used.reserve(nv));
+    HIP_TRY(c, O.ground_terms.reserve((size_t)3 * padded));
+    GroundHeaderHost h;
+    auto read_back = [&]() -> int {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return copy_out(c, &h, O.ground_header.p, sizeof h);
+    };
+    auto t0 = std::chrono::steady_clock::now();
+    auto phase_done = [&](int k) -> int {
+        if (!phases) return YCGE_OK;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        O.ground_phase_us[k] = us_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        return YCGE_OK;
+    };
+    // labelling: the first round does the work, every later one checks it across a launch boundary; the round that hooks nothing ends it
+    int rounds = 0;
+    for (;;) {
+        const int e = ycge_launch_obj_ground_round(O.faces.p, nf, nv, O.ground_parent.p, rounds == 0 ? 1 : 0, O.ground_header.p, c->stream);
+        if (e != 0) return launch_failed(c, "k_ground_hook", e);
+        if (++rounds == 1) continue;
+        { const int rc = read_back(); if (rc != YCGE_OK) return rc; }
+        if (h.decline) break;
+        if (!h.changed) break;
+        if (rounds >= round_cap) { h.decline = (uint32_t)ycge_obj::GROUND_DECLINE_ROUND_CAP; break; }
+    }
+    O.ground_rounds = rounds;
+    if (h.decline) { *declined = (int)h.decline; return YCGE_OK; }
+    { const int rc = phase_done(0); if (rc != YCGE_OK) return rc; }
+    int e = ycge_launch_obj_ground_select(O.faces.p, nf, nv, O.ground_parent.p, O.ground_count.p, O.ground_first.p, O.ground_header.p, c->stream);
+    if (e != 0) return launch_failed(c, "k_ground_count", e);
+    { const int rc = phase_done(1); if (rc != YCGE_OK) return rc; }
+    e = ycge_launch_obj_ground_terms(O.positions.p, O.faces.p, nf, nv, O.ground_parent.p, O.ground_terms.p, padded, O.ground_used.p, O.ground_header.p, c->stream);
+    if (e != 0) return launch_failed(c, "k_ground_terms", e);
+    { const int rc = phase_done(2); if (rc != YCGE_OK) return rc; }
+    e = ycge_launch_obj_ground_sum(O.ground_terms.p, padded, O.ground_header.p, c->stream);
+    if (e != 0) return launch_failed(c, "k_ground_sum", e);
+    { const int rc = phase_done(3); if (rc != YCGE_OK) return rc; }
+    e = ycge_launch_obj_ground_bounds(O.positions.p, nv, O.ground_used.p, O.ground_header.p, c->stream);
+    if (e != 0) return launch_failed(c, "k_ground_bounds", e);
+    { const int rc = read_back(); if (rc != YCGE_OK) return rc; }
+    if (phases) O.ground_phase_us[4] = us_since(t0);
+    ycge_obj::GroundInfo g;
+    std::memset(&g, 0, sizeof g);
+    float rmin[3], rmax[3];
+    decode_box(h.box, rmin, rmax);
+    for (int a = 0; a < 3; a++) g.centroid[a] = h.centroid[a];
+    ycge_obj::ground_normalise(rmin, rmax, g);
+    g.n_components = (int32_t)h.n_components; g.component_faces = (int32_t)(h.best >> 32); g.component_vertices = (int32_t)h.n_used;
+    g.first_face = (int32_t)~(uint32_t)h.best; g.on_device = 1;
+    std::memcpy(out, &g, sizeof g);
+    return YCGE_OK;
+}
+
+int obj_ground(ycge_ctx *c, ycge_obj_ground_info *out)
+{
+    if (out) std::memset(out, 0, sizeof *out);
+    { const int rc = obj_held(c, "ycge_obj_ground"); if (rc != YCGE_OK) return rc; }
+    if (!out) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_obj_ground: out is NULL");
+    ObjState &O = c->obj;
+    const auto t0 = std::chrono::steady_clock::now();
+    int declined = c->knobs.obj_ground_host ? (int)ycge_obj::GROUND_DECLINE_ENV_HOST : (long long)O.n_triangles < c->knobs.obj_ground_device_min ? (int)ycge_obj::GROUND_DECLINE_BELOW_MIN : 0;
+    O.ground_rounds = 0;
+    if (!declined) {
+        const int rc = ground_on_device(c, out, &declined);
+        if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    }
+    if (declined) {          // the host tail, on the held arrays
+        std::vector<float> pos((size_t)3 * O.n_positions);
+        std::vector<int32_t> fc((size_t)3 * O.n_triangles);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        { const int rc = copy_out(c, pos.data(), O.positions.p, pos.size() * sizeof(float)); if (rc != YCGE_OK) return rc; }
+        { const int rc = copy_out(c, fc.data(), O.faces.p, fc.size() * sizeof(int32_t)); if (rc != YCGE_OK) return rc; }
+        const int rc = obj_ground_host(pos.data(), O.n_positions, fc.data(), O.n_triangles, out);
+        if (rc != YCGE_OK) return c->fail(rc, "ycge_obj_ground: the host tail refused the held OBJ");
+    }
+    O.ground_last_decline = declined;
+    (declined ? O.ground_host_tails : O.ground_device_tails)++;
+    O.ground_last_us = us_since(t0);
+    return YCGE_OK;
+}
+
+int obj_triangles_auto_ground(ycge_ctx *c, float scale, const float target[3], float *out_triangles, float out_bounds[6], ycge_obj_ground_info *out_info)
+{
+    if (out_info) std::memset(out_info, 0, sizeof *out_info);
+    { const int rc = obj_held(c, "ycge_obj_triangles_auto_ground"); if (rc != YCGE_OK) return rc; }
+    if (!out_triangles || !target) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_obj_triangles_auto_ground: %s is NULL", out_triangles ? "target" : "out_triangles");
+    ycge_obj_ground_info g;
+    { const int rc = obj_ground(c, &g); if (rc != YCGE_OK) return rc; }
+    if (out_info) *out_info = g;
+    // AddMeshAutoGround (MeshScenes.cs:180-183): each operation rounded to binary32 (this file is compiled without contraction)
+    const float lifted = g.min[1] * scale;
+    const float y_translate = (target[1] - lifted) + 0.01f;
+    const float translate[3] = {target[0], y_translate, target[2]};
+    return obj_triangles(c, 1, 1.0f, scale, translate, out_triangles, out_bounds);
+}
+
+int obj_ground_stats(ycge_ctx *c, int64_t *out6)
+{
+    if (!out6) return YCGE_ERR_INVALID_ARG;
+    if (!c) {
+        Knobs knobs;
+        knobs.read();
+        out6[0] = (int64_t)ycge_launch_obj_ground_sizes(1); out6[1] = (int64_t)ycge_launch_obj_ground_sizes(2); out6[2] = YCGE_OBJ_GROUND_DEVICE_MIN_DEFAULT;
+        out6[3] = knobs.obj_ground_device_min; out6[4] = knobs.obj_ground_host ? 1 : 0; out6[5] = 0;
+        return YCGE_ERR_INVALID_ARG;
+    }
+    const ObjState &O = c->obj;
+    out6[0] = O.ground_device_tails; out6[1] = O.ground_host_tails; out6[2] = O.ground_last_decline; out6[3] = O.ground_rounds;
+    out6[4] = 0;          // (no chunked sum is built: nothing falls back)
+    out6[5] = (int64_t)O.ground_last_us;
+    return YCGE_OK;
+}
+
+int obj_ground_phases(ycge_ctx *c, int64_t *out5)
+{
+    if (!c || !out5) return YCGE_ERR_INVALID_ARG;
+    for (int a = 0; a < 5; a++) out5[a] = (int64_t)c->obj.ground_phase_us[a];
     return YCGE_OK;
 }
 

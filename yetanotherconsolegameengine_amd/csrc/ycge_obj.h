@@ -265,3 +265,106 @@ inline int parse_host(const uint8_t *text, size_t bytes, std::vector<float> &pos
 }
 
 } // namespace ycge_obj
+
+// ---------------------------------------------------------------------------------------------------------------- the auto-ground tail
+// MeshScenes.TryReadObjBoundsNormalized behind its parse (Scenes/MeshScenes.cs:233-330) on parsed arrays: ycge_obj_ground_host, the
+// yardstick of the kernels of ycge_obj_ground.hip and their fallback.  THE CONTRACT (tests/obj_ground_restatement.py states it again):
+//   components  vertices joined by the edges (a, b) and (b, c) of every face; which vertex is a root never reaches the result
+//   the chosen  the component with the most faces; among equal counts the one whose first face comes first in file order
+//   centroid    cx = 0; per kept face in file order cx += ((A.x + B.x) + C.x) * (1 / 3f), every operation rounded to binary32 (no contracted
+//               multiply-add: compile without contraction); then cx *= 1 / (float)kept.  y and z alike
+//   bounds      over the vertices of the kept faces, of pos - centroid; NaN never replaces an extreme; -0 orders below +0
+//   normalise   extent = rx; if (ry > extent); if (rz > extent); if (extent <= 0) extent = 1; s = 1 / extent; min = rMin * s; max = rMax * s
+namespace ycge_obj {
+
+// ycge_obj_ground_info of include/ycge.h, field for field (this header stands alone; ycge_obj.cpp asserts the size)
+struct GroundInfo {
+    float min[3], max[3], centroid[3], extent;
+    int32_t n_components, component_faces, component_vertices, first_face, on_device, reserved;
+};
+// why the kernels did not take the tail (ycge_debug_obj_ground_stats, out6[2]); the kernels set the first two
+enum { GROUND_DECLINE_FIND_BOUND = 1, GROUND_DECLINE_ROUND_CAP = 2, GROUND_DECLINE_ENV_HOST = 4, GROUND_DECLINE_BELOW_MIN = 8 };
+constexpr int kGroundRoundCap = 64;                  // labelling rounds before the host tail takes the OBJ
+
+// a float as an unsigned integer of the same order (-0 below +0): the order the kernels' min / max use
+inline uint32_t ground_ordered(float f)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// steps 5 of the contract: raw extremes about the centroid -> out.extent, out.min, out.max
+inline void ground_normalise(const float rmin[3], const float rmax[3], GroundInfo &out)
+{
+    const float rx = rmax[0] - rmin[0], ry = rmax[1] - rmin[1], rz = rmax[2] - rmin[2];
+    float extent = rx;
+    if (ry > extent) extent = ry;
+    if (rz > extent) extent = rz;
+    if (extent <= 0.0f) extent = 1.0f;
+    const float s = 1.0f / extent;
+    out.extent = extent;
+    for (int a = 0; a < 3; a++) { out.min[a] = rmin[a] * s; out.max[a] = rmax[a] * s; }
+}
+
+// 0 or ST_INVALID_ARG (NULL arrays, counts <= 0, an index out of range)
+inline int ground_host(const float *positions, int32_t n_positions, const int32_t *faces, int32_t n_triangles, GroundInfo &out)
+{
+    std::memset(&out, 0, sizeof out);
+    if (!positions || !faces || n_positions <= 0 || n_triangles <= 0) return ST_INVALID_ARG;
+    const size_t nv = (size_t)n_positions, nf = (size_t)n_triangles;
+    for (size_t k = 0; k < 3 * nf; k++)
+        if (faces[k] < 0 || faces[k] >= n_positions) return ST_INVALID_ARG;
+    // union-find, the larger root under the smaller (no rank: the root's identity is not part of the result), path halving
+    std::vector<int32_t> parent(nv);
+    for (size_t v = 0; v < nv; v++) parent[v] = (int32_t)v;
+    auto find = [&](int32_t x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
+    auto join = [&](int32_t x, int32_t y) { const int32_t a = find(x), b = find(y); if (a < b) parent[b] = a; else if (b < a) parent[a] = b; };
+    for (size_t f = 0; f < nf; f++) { join(faces[3 * f], faces[3 * f + 1]); join(faces[3 * f + 1], faces[3 * f + 2]); }
+    // faces per root; the winner: strictly more faces in order of first appearance (the Dictionary's insertion order)
+    std::vector<int32_t> count(nv, 0), root_of(nf);
+    int32_t best = -1, best_first = 0, n_components = 0;
+    for (size_t f = 0; f < nf; f++) { const int32_t r = find(faces[3 * f]); root_of[f] = r; if (count[r]++ == 0) n_components++; }
+    {
+        std::vector<uint8_t> seen(nv, 0);
+        for (size_t f = 0; f < nf; f++) {
+            const int32_t r = root_of[f];
+            if (seen[r]) continue;
+            seen[r] = 1;
+            if (best < 0 || count[r] > count[best]) { best = r; best_first = (int32_t)f; }
+        }
+    }
+    const float third = 1.0f / 3.0f;
+    float c[3] = {0.0f, 0.0f, 0.0f};
+    std::vector<uint8_t> used(nv, 0);
+    for (size_t f = 0; f < nf; f++) {
+        if (root_of[f] != best) continue;
+        const size_t ia = (size_t)faces[3 * f], ib = (size_t)faces[3 * f + 1], ic = (size_t)faces[3 * f + 2];
+        used[ia] = used[ib] = used[ic] = 1;
+        for (int a = 0; a < 3; a++) {
+            const float sum = (positions[3 * ia + a] + positions[3 * ib + a]) + positions[3 * ic + a];
+            const float term = sum * third;          // (rounded before it is added)
+            c[a] = c[a] + term;
+        }
+    }
+    const float inv = 1.0f / (float)count[best];
+    for (int a = 0; a < 3; a++) c[a] = c[a] * inv;
+    float rmin[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, rmax[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    int32_t n_used = 0;
+    for (size_t v = 0; v < nv; v++) {
+        if (!used[v]) continue;
+        n_used++;
+        for (int a = 0; a < 3; a++) {
+            const float x = positions[3 * v + a] - c[a];
+            if (x != x) continue;
+            if (ground_ordered(x) < ground_ordered(rmin[a])) rmin[a] = x;
+            if (ground_ordered(x) > ground_ordered(rmax[a])) rmax[a] = x;
+        }
+    }
+    for (int a = 0; a < 3; a++) out.centroid[a] = c[a];
+    ground_normalise(rmin, rmax, out);
+    out.n_components = n_components; out.component_faces = count[best]; out.component_vertices = n_used; out.first_face = best_first;
+    return ST_OK;
+}
+
+} // namespace ycge_obj

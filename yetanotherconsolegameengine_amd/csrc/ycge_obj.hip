@@ -11,6 +11,7 @@
 //   k_obj_used         faces mark used[]; an index out of range reports the lowest triangle through a second error word
 //   k_obj_bounds       min / max over the used vertices: per workgroup in LDS, then one ordered-integer atomic per workgroup and component
 //   k_obj_triangles    one lane, one triangle: gather, normalise, scale / translate, store; its bounds by the same two-stage reduction
+//                      (ycge_obj_box.hip.h, shared with ycge_obj_ground.hip)
 // Float min / max are exact, so the order of arrival cannot change a bit; -0 orders below +0 here (the reference's sign of a zero extreme
 // depends on HashSet enumeration order), NaN never replaces an extreme (the reference's compares are false for it).
 // No workgroup waits on another's flag.  Lanes take lines of different lengths, so the walk diverges: accepted for this first form (nothing
@@ -20,6 +21,7 @@
 #include <cstdint>
 
 #include "ycge_obj.h"
+#include "ycge_obj_box.hip.h"
 
 namespace {
 
@@ -61,13 +63,6 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *w
     }
     __syncthreads();                      // (wsum may be reused)
     return before + inc - v;
-}
-
-// a float as an unsigned integer of the same order (-0 below +0); and back
-__device__ __forceinline__ uint32_t ordered(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // bit k: byte base + k of the text starts a line.  first: 0, or 3 behind a byte-order mark.  The text buffer is readable up to the next
@@ -213,29 +208,6 @@ __global__ __launch_bounds__(kObjBlock) void k_obj_used(const int32_t *__restric
         else used[v] = 1;
     }
     if (bad) atomicMin(&H->bad_face, (unsigned long long)f);
-}
-
-// this lane's box (ordered integers; lo > hi: nothing) into the workgroup's in LDS, then into box[6] by one atomic per component
-__device__ __forceinline__ void reduce_box(const uint32_t lo[3], const uint32_t hi[3], uint32_t *__restrict__ box)
-{
-    __shared__ uint32_t sbox[6];
-    if (threadIdx.x < 3) { sbox[threadIdx.x] = 0xffffffffu; sbox[3 + threadIdx.x] = 0u; }
-    __syncthreads();
-    for (int a = 0; a < 3; a++) {
-        if (lo[a] <= hi[a]) { atomicMin(&sbox[a], lo[a]); atomicMax(&sbox[3 + a], hi[a]); }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) { if (sbox[threadIdx.x] <= sbox[3 + threadIdx.x]) { atomicMin(&box[threadIdx.x], sbox[threadIdx.x]); atomicMax(&box[3 + threadIdx.x], sbox[3 + threadIdx.x]); } }
-}
-
-__device__ __forceinline__ void grow(uint32_t lo[3], uint32_t hi[3], const float p[3])
-{
-    for (int a = 0; a < 3; a++) {
-        if (p[a] != p[a]) continue;
-        const uint32_t o = ordered(p[a]);
-        lo[a] = o < lo[a] ? o : lo[a];
-        hi[a] = o > hi[a] ? o : hi[a];
-    }
 }
 
 __global__ __launch_bounds__(kObjBlock) void k_obj_bounds(const float *__restrict__ positions, uint32_t n_positions, const uint8_t *__restrict__ used, ObjHeader *__restrict__ H)

@@ -161,14 +161,7 @@ def from_obj_device(renderer, data, scale: float = 1.0, translate=(0.0, 0.0, 0.0
 
 
 def add_mesh_auto_ground_device(renderer, data, scale: float, target_pos) -> np.ndarray:
-    """MeshScenes.AddMeshAutoGround with ONE parse, on the device: the positions and faces come back once for the union-find tail of
-    TryReadObjBoundsNormalized (which stays on the host), the placed triangles are made on the device."""
+    """MeshScenes.AddMeshAutoGround with ONE parse, on the device: ParseObj, then one call (RaytraceRenderer.ObjTrianglesAutoGround) that finds
+    the largest component, its centroid and bounds against the held OBJ and places the triangles - no geometry comes back before them."""
     renderer.ParseObj(data)
-    pos, faces = renderer.ReadObj()
-    b = read_obj_bounds_normalized(pos, faces)
-    if b is None:
-        raise FileNotFoundError("OBJ not found or empty")
-    min_y_norm = b[0][1]
-    y_translate = f32(target_pos[1]) - min_y_norm * f32(scale) + f32(0.01)
-    translate = (f32(target_pos[0]), y_translate, f32(target_pos[2]))
-    return renderer.ObjTriangles(scale=scale, translate=translate, normalize=True, target_size=1.0)[0]
+    return renderer.ObjTrianglesAutoGround(scale, target_pos)[0]

@@ -238,6 +238,24 @@ class RaytraceRenderer:
                                                tris.ctypes.data if info else None, bounds.ctypes.data))
         return tris, bounds
 
+    def ObjGround(self) -> abi.ObjGroundInfo:
+        """ycge_obj_ground: MeshScenes.TryReadObjBoundsNormalized behind its parse, for the held OBJ - the component with the most faces, its
+        centroid, the normalised bounds of its vertices about it; info.on_device says whether the kernels ran it."""
+        info = abi.ObjGroundInfo()
+        self._check(self.L.ycge_obj_ground(self.ctx, C.byref(info)))
+        return info
+
+    def ObjTrianglesAutoGround(self, scale: float, target_pos):
+        """ycge_obj_triangles_auto_ground: MeshScenes.AddMeshAutoGround for the held OBJ in one call -> (triangles f32 [nt, 3, 3], bounds f32
+        [6] = min xyz, max xyz, ObjGroundInfo)"""
+        info = getattr(self, "_obj_info", None)
+        tris = np.empty((info.n_triangles if info else 0, 3, 3), np.float32)
+        bounds = np.empty(6, np.float32)
+        ground = abi.ObjGroundInfo()
+        t = (C.c_float * 3)(*[float(np.float32(v)) for v in target_pos])
+        self._check(self.L.ycge_obj_triangles_auto_ground(self.ctx, float(np.float32(scale)), t, tris.ctypes.data if info else None, bounds.ctypes.data, C.byref(ground)))
+        return tris, bounds, ground
+
     def ReleaseObj(self) -> None:
         self._obj_info = None
         self._check(self.L.ycge_obj_release(self.ctx))
@@ -250,6 +268,22 @@ class RaytraceRenderer:
         fn.restype, fn.argtypes = abi.OBJ_HOOK_PROTOTYPES["ycge_debug_obj_stats"]
         self._check(fn(self.ctx, out))
         return dict(zip(abi.OBJ_STATS, (int(v) for v in out)))
+
+    def obj_ground_stats(self) -> dict:
+        """Who ran the auto-ground tail: tails the kernels ran, tails the host ran, why the last one went to the host (abi.OBJ_GROUND_DECLINE_*;
+        0: it did not), the labelling rounds of the last device tail, sums that fell back to a serial path (no chunked sum is built: 0), wall
+        microseconds of the last tail; with YCGE_OBJ_GROUND_PHASES set at creation also the last device tail's phases (abi.OBJ_GROUND_PHASES)."""
+        out = (C.c_int64 * 6)()
+        fn = self.L.ycge_debug_obj_ground_stats
+        fn.restype, fn.argtypes = abi.OBJ_GROUND_HOOK_PROTOTYPES["ycge_debug_obj_ground_stats"]
+        self._check(fn(self.ctx, out))
+        d = dict(zip(abi.OBJ_GROUND_STATS, (int(v) for v in out)))
+        ph = (C.c_int64 * 5)()
+        fn = self.L.ycge_debug_obj_ground_phases
+        fn.restype, fn.argtypes = abi.OBJ_GROUND_HOOK_PROTOTYPES["ycge_debug_obj_ground_phases"]
+        self._check(fn(self.ctx, ph))
+        d.update(zip(abi.OBJ_GROUND_PHASES, (int(v) for v in ph)))
+        return d
 
     def DetachGrids(self, indices) -> None:
         """Gives the grids' slots back; refused while Scene.Objects (as of the last UpdateObjects) refer to one of them."""
