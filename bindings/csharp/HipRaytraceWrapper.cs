@@ -26,6 +26,11 @@
 //                bytes ANSITerminalRenderer.Render() would write for the console (ycge_render_frame_ansi), and the presenter writes them to
 //                stdout as they are - the framebuffer is not written and no cell is walked on the host.  Synchronous frames only (FrameLate
 //                is ignored); the raytrace framebuffer is the only one drawn (INTEGRATION.md section 8).
+//   DeviceAnsiDelta - with DeviceAnsiStream: a frame's bytes are the delta stream (ycge_render_frame_ansi_delta) - only the cells whose
+//                ANSI pair changed since the last frame written, each run behind a cursor move, and always the console's last cell, so the
+//                cursor ends where Render() leaves it for Terminal.Start's HUD.  The first frame, a frame after a console resize
+//                (ClearPending) and a frame after a switch of geometry are keyframes: the full stream.  AnsiMergeGap: unchanged cells between
+//                two changed ones of a row that are rewritten rather than jumped over (0..8).
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -44,6 +49,10 @@ public sealed class HipRaytraceOptions
     public bool DeviceChexelColors;
     public bool DeviceAnsiStream;
     public DeviceAnsiTerminalRenderer AnsiPresenter;          // DeviceAnsiStream: the presenter the frames' streams go to
+    public bool DeviceAnsiDelta;                              // DeviceAnsiStream: delta streams between keyframes
+    // The default is the gap with the fewest total bytes over the resting sequence of profiles/ansi_delta_rate.json (config 4, 1921 x 541,
+    // frames 1..60): 3, with 1 117 018 bytes in 59 deltas; gaps 2..5 lie within 0.4 % of it, gap 0 is 2.6 % above.
+    public int AnsiMergeGap = 3;
     public HipGeneratedWorld GeneratedWorld;                  // chunks that come from the generator are made on the device (ycge_scene_generate_grids)
 }
 
@@ -62,7 +71,10 @@ public sealed class HipGeneratedWorld
 }
 
 /// <summary>ANSITerminalRenderer with the cell walk moved to the GPU (HipRaytraceOptions.DeviceAnsiStream): Render() writes the stream of the
-/// last frame - built by ycge_render_frame_ansi, byte for byte what ANSITerminalRenderer.Render() writes for the same cells - to stdout.
+/// last frame to stdout.  A frame's bytes are built by ycge_render_frame_ansi: byte for byte what ANSITerminalRenderer.Render() writes for the
+/// same cells.  With HipRaytraceOptions.DeviceAnsiDelta they are built by ycge_render_frame_ansi_delta: that same stream for a keyframe (the
+/// first frame, after a resize, after another geometry), otherwise only the cells that changed since the frame before, which leave the
+/// terminal - cells, cursor and colours - as the full stream would.  Every frame handed over must be written, in order: Render() does.
 /// A change of console size is handled as ANSITerminalRenderer does it: onResize(width, height), and the next frame written starts with
 /// ESC[2J ESC[H.  Only the raytrace framebuffer is drawn: AddFrameBuffer / RemoveFrameBuffer keep nothing.</summary>
 public sealed class DeviceAnsiTerminalRenderer : ITerminalRenderer
@@ -131,6 +143,8 @@ public partial class RaytraceEntity
         private readonly DeviceAnsiTerminalRenderer ansi;       // DeviceAnsiStream: the presenter of the streams
         private byte* ansiBuf;                      // the last frame's stream (page-locked memory of the library, ansiCap bytes)
         private ulong ansiCap, ansiLen;
+        private readonly bool ansiDelta;            // DeviceAnsiDelta: delta streams between keyframes
+        private readonly int ansiMergeGap;
         private bool inFlight;                      // FrameLate: a frame queued by the last TryFlipAndBlit has not been waited for yet
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
         private ulong objectsSignature;
@@ -154,6 +168,7 @@ public partial class RaytraceEntity
                 cfg.MultiDeviceExchange = (int)options.Exchange;
             }
             ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
+            ansiDelta = ansi != null && options.DeviceAnsiDelta; ansiMergeGap = options != null ? options.AnsiMergeGap : 3;
             frameLate = options != null && options.FrameLate && cfg.NDevices <= 1 && ansi == null;      // (frames in flight are the single-device form; the stream is synchronous)
             deviceColors = options != null && options.DeviceChexelColors;
             generated = options?.GeneratedWorld;
@@ -178,8 +193,12 @@ public partial class RaytraceEntity
                 ansiBuf = (byte*)p; ansiCap = (ulong)bound;
             }
             UIntPtr len;
-            Ycge.Check(ctx, Ycge.ycge_render_frame_ansi(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
-                                                        ansiBuf, (UIntPtr)ansiCap, &len, null, null));
+            if (ansiDelta)
+                Ycge.Check(ctx, Ycge.ycge_render_frame_ansi_delta(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
+                                                                  ansiMergeGap, 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null, null));
+            else
+                Ycge.Check(ctx, Ycge.ycge_render_frame_ansi(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
+                                                            ansiBuf, (UIntPtr)ansiCap, &len, null, null));
             ansiLen = (ulong)len;
             ansi.ClearPending = false;
         }

@@ -33,6 +33,8 @@ public partial class RaytraceEntity
         private readonly DeviceAnsiTerminalRenderer ansi;
         private byte* ansiBuf;
         private ulong ansiCap, ansiLen;
+        private readonly bool ansiDelta;            // HipRaytraceOptions.DeviceAnsiDelta: delta streams, on the delta state the context shares with the ray-traced frames
+        private readonly int ansiMergeGap;
 
         /// <summary>sharedContext: the context of the raytrace wrapper of the same console, whose geometry must be fb's and superSample's
         /// (IntPtr.Zero: a context of this wrapper's own).</summary>
@@ -42,6 +44,7 @@ public partial class RaytraceEntity
             useRGBA = requestRGBA;
             fbW = fb.Width; fbH = fb.Height; ss = Math.Max(1, superSample);         // VideoRenderer.cs:33-37
             ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
+            ansiDelta = ansi != null && options.DeviceAnsiDelta; ansiMergeGap = options != null ? options.AnsiMergeGap : 3;
             deviceColors = options != null && options.DeviceChexelColors;
             if (sharedContext != IntPtr.Zero)
             {
@@ -104,8 +107,12 @@ public partial class RaytraceEntity
                     ansiBuf = (byte*)p; ansiCap = (ulong)bound;
                 }
                 UIntPtr len;
-                Ycge.Check(ctx, Ycge.ycge_video_blit_ansi(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
-                                                          ansi.ClearPending ? 1 : 0, ansiBuf, (UIntPtr)ansiCap, &len, null));
+                if (ansiDelta)
+                    Ycge.Check(ctx, Ycge.ycge_video_blit_ansi_delta(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
+                                                                    ansi.ClearPending ? 1 : 0, ansiMergeGap, 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null));
+                else
+                    Ycge.Check(ctx, Ycge.ycge_video_blit_ansi(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
+                                                              ansi.ClearPending ? 1 : 0, ansiBuf, (UIntPtr)ansiCap, &len, null));
                 ansiLen = (ulong)len;
                 ansi.ClearPending = false;
                 return;                                                        // (the presenter writes the stream: the framebuffer is not walked)

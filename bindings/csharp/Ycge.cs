@@ -235,6 +235,15 @@ namespace ConsoleGame.RayTracing.Native
         [DllImport(Lib)] public static extern int ycge_video_blit_ansi(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int consoleW, int consoleH, int viewportX,
                                                                        int viewportY, int defaultFg16, int defaultBg16, int clearScreen, byte* outStream, UIntPtr capacity,
                                                                        UIntPtr* outLen, float* outTopBottomSdr);
+        // the delta ANSI stream (after ABI 10, found by symbol lookup): only the cells that changed since the last stream of the context; a
+        // keyframe is the full stream.  outInfo: 4 words {keyframe returned, changed cells, emitted cells, run starts} or null
+        [DllImport(Lib)] public static extern int ycge_render_frame_ansi_delta(IntPtr ctx, int consoleW, int consoleH, int viewportX, int viewportY, int defaultFg16,
+                                                                               int defaultBg16, int clearScreen, int mergeGap, int keyframe, byte* outStream,
+                                                                               UIntPtr capacity, UIntPtr* outLen, uint* outInfo, float* outTopBottomSdr, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_video_blit_ansi_delta(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int consoleW, int consoleH,
+                                                                             int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, int mergeGap,
+                                                                             int keyframe, byte* outStream, UIntPtr capacity, UIntPtr* outLen, uint* outInfo,
+                                                                             float* outTopBottomSdr);
         // OBJ meshes from file bytes (MeshLoader.FromObj on the device; HipObjLoader.cs).  info: a YObjInfo
         [DllImport(Lib)] public static extern int ycge_obj_parse_host(byte* text, UIntPtr bytes, float* positions, int* faces, out YObjInfo info, byte* msg, UIntPtr msgBytes);
         [DllImport(Lib)] public static extern int ycge_obj_parse(IntPtr ctx, byte* text, UIntPtr bytes, out YObjInfo info);

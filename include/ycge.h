@@ -536,6 +536,45 @@ int ycge_video_blit_ansi(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int
                          int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
                          int32_t default_fg16, int32_t default_bg16, int32_t clear_screen,
                          uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr /* may be NULL */);
+/* --- The delta ANSI stream: only the cells that changed since the last stream this context handed out.  The reference has no delta
+ * presenter, so these rules define the bytes; they are tied to Render() in two ways: a keyframe IS the stream of ycge_render_frame_ansi, and
+ * a delta applied to a terminal that shows the previous stream leaves it showing what the full stream of the new frame would, with the
+ * cursor and the SGR state where the full stream leaves them (Terminal.Start writes its HUD right behind Render()).  Added after ABI 10
+ * without changing it: a host detects these exports by symbol lookup.
+ *   Geometry, covered cells and default cells are those of ycge_render_frame_ansi.  `prev` is the pair array of the last stream this
+ *   context handed out successfully through either export below, `cur` this frame's.
+ *   Keyframe: the stream of ycge_render_frame_ansi (ycge_video_blit_ansi) for the same arguments, byte for byte.  Returned when there is no
+ *   valid prev, when the geometry key {console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, fbW, fbH} differs from
+ *   that of prev, when clear_screen != 0 or when keyframe != 0.
+ *   Delta, with merge_gap = G in 0..8:
+ *     changed(x, y): the cell is covered and its pair differs from prev in either byte.
+ *     emitted(x, y): changed(x, y); or the cell lies in the same row strictly between two changed cells a < x < b with b - a - 1 <= G; or
+ *       it is the console's last cell (console_w - 1, console_h - 1), covered or not - so the cursor ends exactly where the full stream
+ *       leaves it, pending wrap included.
+ *     Emitted cells are written in raster order.  An emitted cell is a run start when x == 0 or (x - 1, y) is not emitted: it writes
+ *     ESC[<y+1>;<x+1>H, then ESC[38;5;<fg>;48;5;<bg>m unconditionally (Render()'s first branch against (-1, -1)).  Any other emitted cell
+ *     writes the escape of Render()'s three branches (ANSITerminalRenderer.cs:120-143) against the pair of (x - 1, y).  Then the cell's
+ *     character: '\u2580' in UTF-8 when covered, ' ' otherwise.  The stream ends with ESC[0m.  No clear prefix, no per-row ;1H moves.
+ *   A delta never exceeds ycge_ansi_stream_bound, which stays the capacity to pass (the proof: csrc/ycge_ansi_delta.hip).
+ *   out_info (4 words, or NULL): {keyframe returned (0 / 1), changed cells, emitted cells, run starts}; the three counts are 0 on a keyframe.
+ *   State: prev advances only when one of these two calls returns YCGE_OK (two pair buffers are swapped, nothing is copied).  The next call
+ *   is a keyframe after: a failure behind the call's refusals, ycge_resize, a change of the framebuffer size, a call to
+ *   ycge_render_frame_ansi or ycge_video_blit_ansi on the context (the host has then shown something else).  A refusal of the call's
+ *   arguments leaves the state as it was.  Both exports share the one delta state of the context: one terminal, whichever renderer the
+ *   host shows on it (the mode switch of RaytraceEntity).
+ *   The frame state, the SDR, the statistics and the refusals are those of ycge_render_frame_ansi / ycge_video_blit_ansi, and one more:
+ *   merge_gap outside 0..8 is YCGE_ERR_INVALID_ARG, the message names the value.
+ *   The host: write every stream it is handed to the terminal, in order and whole; pass keyframe = 1 (or clear_screen) after anything
+ *   else wrote to the terminal's cells - a HUD line over the console area, another program, a redraw after a suspend. */
+int ycge_render_frame_ansi_delta(ycge_ctx *ctx, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                                 int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t keyframe, uint8_t *out_stream,
+                                 size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */,
+                                 float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+int ycge_video_blit_ansi_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                               int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
+                               int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t keyframe,
+                               uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */,
+                               float *out_top_bottom_sdr /* may be NULL */);
 /* --- OBJ meshes from file bytes: MeshLoader.FromObj (RayTracing/MeshLoader.cs:12-149) up to the float soup ycge_mesh.triangles takes, parsed
  * on the device.  Added after ABI 10 without changing it (YCGE_ABI_VERSION stays 10, no struct changes; detect by symbol lookup).
  *   The contract, byte by byte ("the reference's loader" restated correctly; tests/obj_restatement.py is its yardstick):

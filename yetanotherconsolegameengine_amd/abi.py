@@ -242,6 +242,13 @@ _PROTOTYPES = {
                                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "ycge_video_blit_ansi": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    # (out_info: 4 uint32 {keyframe returned, changed cells, emitted cells, run starts}, or None)
+    "ycge_render_frame_ansi_delta": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                               C.POINTER(FrameStats)]),
+    "ycge_video_blit_ansi_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
     "ycge_obj_parse_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "ycge_obj_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -294,6 +301,11 @@ POST_STATE_WORDS = 6
 VIDEO_HOOK_PROTOTYPES = {
     "ycge_host_video_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ycge_test_video_blit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+}
+# test hook of the delta ANSI stream (csrc/ycge_ansi.cpp), bound where it is used (tests/test_gpu_ansi_delta.py)
+ANSI_DELTA_HOOK_PROTOTYPES = {
+    "ycge_test_ansi_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)] + [C.c_int32] * 10 +
+                             [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
 }
 # test / profiling hooks of the device-side mesh BVH build (csrc/ycge_mesh_bvh.cpp), bound where they are used (RaytraceRenderer.mesh_bvh_stats,
 # device_mesh_bvh below); res16: MESH_BVH_RES_WORDS uint32, the fallback reasons as the library names them

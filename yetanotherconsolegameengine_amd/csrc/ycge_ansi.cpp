@@ -7,6 +7,11 @@
 // that many bytes are copied to the caller.  The request lives in ChexelState for the length of one call (a scope guard clears it; on an
 // error return also every latched destination), so no other entry point issues a launch or copy of it.
 //
+// The delta form (ycge_render_frame_ansi_delta, ycge_video_blit_ansi_delta; kernels: ycge_ansi_delta.hip) keeps the pairs of the last
+// stream it handed out in one of two buffers of ChexelState and writes only the cells that changed since; the contract is in
+// include/ycge.h.  Its encode writes into the other buffer and a successful call flips the two: nothing is copied.  A keyframe runs the
+// full stream's kernels on those pairs, so its bytes are ycge_render_frame_ansi's.
+//
 // The default cell's colours are ansi(palette16[k]): k_encode_chexels run once on the 16 palette colours, so no second formula exists.
 #include "ycge_ctx.h"
 
@@ -56,7 +61,7 @@ static int ensure_ansi(ycge_ctx *c, ChexelState &X, int32_t cw, int32_t ch, unsi
 {
     if (X.ansi_stream.cap < bound) HIP_TRY(c, X.ansi_stream.alloc(bound));
     const uint32_t tiles = ycge_launch_ansi_tiles((uint32_t)cw * (uint32_t)ch);
-    if (X.ansi_tiles.cap < tiles) HIP_TRY(c, X.ansi_tiles.alloc(tiles));
+    if (X.ansi_tiles.cap < 4 * (size_t)tiles) HIP_TRY(c, X.ansi_tiles.alloc(4 * (size_t)tiles));          // (the delta kernels keep four words a tile)
     if (!X.ansi_len.p) HIP_TRY(c, X.ansi_len.alloc(1));
     HIP_TRY(c, X.ansi_len_host.reserve(sizeof(unsigned long long)));
     return ensure_palette(c, X, stream);
@@ -71,10 +76,23 @@ static int launch_stream(ycge_ctx *c, ChexelState &X, hipStream_t stream, const 
     return YCGE_OK;
 }
 
+// the delta stream of d_pairs against d_prev for the request in X, and the copy of {length, changed, emitted, run starts}
+static int launch_delta(ycge_ctx *c, ChexelState &X, hipStream_t stream, const uint8_t *d_pairs, const uint8_t *d_prev, int fbW, int fbH)
+{
+    if (!X.delta_res.p) HIP_TRY(c, X.delta_res.alloc(4));
+    HIP_TRY(c, X.delta_res_host.reserve(4 * sizeof(unsigned long long)));
+    const int e = ycge_launch_ansi_delta(d_pairs, d_prev, fbW, fbH, X.ansi_cw, X.ansi_ch, X.ansi_vx, X.ansi_vy, reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48),
+                                         X.ansi_fg, X.ansi_bg, X.delta_gap, X.ansi_tiles.p, X.ansi_stream.p, X.ansi_stream.cap, X.delta_res.p, stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "ANSI delta stream launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipMemcpyAsync(X.delta_res_host.p, X.delta_res.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    return YCGE_OK;
+}
+
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs)
 {
     ChexelState &X = c->chexels;
     { const int rc = ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
+    if (X.delta_on && !X.delta_full) return launch_delta(c, X, stream, d_pairs, X.delta_pairs[X.delta_prev].p, c->fbW, c->fbH);
     return launch_stream(c, X, stream, d_pairs, c->fbW, c->fbH);
 }
 
@@ -130,6 +148,57 @@ int copy_stream(ycge_ctx *c, ChexelState &X, uint8_t *out, size_t len)
     return YCGE_OK;
 }
 
+// one _delta call behind an AnsiCall: decides keyframe or delta, and on every way out but commit() makes the next call a keyframe
+struct DeltaCall {
+    ycge_ctx *c;
+    int32_t key[8];
+    bool done = false;
+    DeltaCall(ycge_ctx *c_, int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear, int32_t gap, int32_t keyframe)
+        : c(c_), key{cw, ch, vx, vy, fg, bg, c_->fbW, c_->fbH}
+    {
+        ChexelState &X = c->chexels;
+        X.delta_on = true; X.delta_gap = gap;
+        X.delta_full = !X.delta_valid || !X.delta_pairs[X.delta_prev].p || std::memcmp(key, X.delta_key, sizeof key) != 0 || clear != 0 || keyframe != 0;
+    }
+    ~DeltaCall()
+    {
+        ChexelState &X = c->chexels;
+        X.delta_on = false;
+        if (!done) X.delta_valid = false;
+    }
+    // the stream is with the caller: this frame's pairs are `prev` from now on
+    void commit()
+    {
+        ChexelState &X = c->chexels;
+        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true;
+        std::memcpy(X.delta_key, key, sizeof key);
+        done = true;
+    }
+};
+
+int check_merge_gap(ycge_ctx *c, const char *fn, int32_t gap)
+{
+    if (gap < 0 || gap > 8) return c->fail(YCGE_ERR_INVALID_ARG, "%s: merge_gap %d (0..8)", fn, gap);
+    return YCGE_OK;
+}
+
+// behind the stream's synchronisation: the length and the counters the device wrote (full: a keyframe, whose length the full stream's scan
+// wrote), the bound check, the stream's copy; then the caller's words
+int deliver_delta(ycge_ctx *c, ChexelState &X, const char *fn, bool full, unsigned long long bound, uint8_t *out_stream, size_t *out_len, uint32_t *out_info)
+{
+    const unsigned long long *res = static_cast<const unsigned long long *>(full ? X.ansi_len_host.p : X.delta_res_host.p);
+    const unsigned long long len = res[0];
+    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
+    const int rc = copy_stream(c, X, out_stream, (size_t)len);
+    if (rc != YCGE_OK) return rc;
+    *out_len = (size_t)len;
+    if (out_info) {
+        out_info[0] = full ? 1u : 0u;
+        for (int k = 1; k < 4; k++) out_info[k] = full ? 0u : (uint32_t)res[k];
+    }
+    return YCGE_OK;
+}
+
 } // namespace
 
 // =========================================================================== C-ABI
@@ -160,6 +229,7 @@ try {
     HIP_TRY(c, hipSetDevice(c->device));
     AnsiCall call(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
     ChexelState &X = c->chexels;
+    X.delta_valid = false;                                            // (the terminal shows this stream next: a later _delta call returns a keyframe)
     rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
     if (rc != YCGE_OK) return rc;
     rc = render_frame_sync(c, out_top_bottom_sdr, true, st);          // (its stream synchronisation: the length has arrived)
@@ -190,6 +260,7 @@ try {
     AnsiCall call(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
     StagedSdrGuard staged(c);
     ChexelState &X = c->chexels;
+    X.delta_valid = false;                                            // (as in ycge_render_frame_ansi)
     rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
     const float *d_sdr = nullptr;
     if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
@@ -204,6 +275,71 @@ try {
     if (rc != YCGE_OK) return rc;
     finish_staged_sdr(c);
     *out_len = (size_t)len;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// The delta form of ycge_render_frame_ansi (the contract: include/ycge.h): a keyframe is that call's stream, a delta writes the cells that
+// changed since the last stream this context handed out
+int ycge_render_frame_ansi_delta(ycge_ctx *c, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                                 int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t keyframe, uint8_t *out_stream, size_t capacity,
+                                 size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr, ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_render_frame_ansi_delta";
+    unsigned long long bound = 0;
+    int rc = check_stream_args(c, fn, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
+    if (rc == YCGE_OK) rc = check_merge_gap(c, fn, merge_gap);
+    if (rc != YCGE_OK) return rc;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
+        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
+    HIP_TRY(c, hipSetDevice(c->device));
+    AnsiCall call(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    DeltaCall delta(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, merge_gap, keyframe);
+    ChexelState &X = c->chexels;
+    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
+    if (rc != YCGE_OK) return rc;
+    rc = render_frame_sync(c, out_top_bottom_sdr, true, st);          // (its stream synchronisation: the length and the counters have arrived)
+    if (rc != YCGE_OK) return rc;
+    rc = deliver_delta(c, X, fn, X.delta_full, bound, out_stream, out_len, out_info);
+    if (rc != YCGE_OK) return rc;
+    delta.commit();
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ... and of ycge_video_blit_ansi, on the same delta state: one terminal, whichever renderer the host shows on it
+int ycge_video_blit_ansi_delta(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t console_w, int32_t console_h,
+                               int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
+                               int32_t keyframe, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_video_blit_ansi_delta";
+    unsigned long long bound = 0;
+    int rc = video_check_frame(c, fn, frame, src_w, src_h, bytes_per_pixel);
+    if (rc == YCGE_OK) rc = check_stream_args(c, fn, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
+    if (rc == YCGE_OK) rc = check_merge_gap(c, fn, merge_gap);
+    if (rc != YCGE_OK) return rc;
+    rc = join_async(c);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    AnsiCall call(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    DeltaCall delta(c, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, merge_gap, keyframe);
+    StagedSdrGuard staged(c);
+    ChexelState &X = c->chexels;
+    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
+    const float *d_sdr = nullptr;
+    if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
+    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, d_sdr, false);
+    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out_top_bottom_sdr);
+    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, false);          // (the stream kernels and the copy of what they report)
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rc = deliver_delta(c, X, fn, X.delta_full, bound, out_stream, out_len, out_info);
+    if (rc != YCGE_OK) return rc;
+    finish_staged_sdr(c);
+    delta.commit();
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }
@@ -239,6 +375,43 @@ try {
     if (rc != YCGE_OK) return rc;
     *out_len = (size_t)len;
     return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: the delta kernels alone on caller-given pairs, prev_pairs and pairs both fbW x fbH {fg, bg}; a NULL prev_pairs or a
+// clear_screen gives the keyframe (ycge_test_ansi_stream's bytes).  Stateless: pair buffers of its own, the context's delta state untouched.
+int ycge_test_ansi_delta(ycge_ctx *c, const uint8_t *prev_pairs, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h,
+                         int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
+                         uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_test_ansi_delta";
+    if (!pairs || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (pairs %p, %d x %d)", fn, (const void *)pairs, fbW, fbH);
+    unsigned long long bound = 0;
+    int rc = check_stream_args(c, fn, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
+    if (rc == YCGE_OK) rc = check_merge_gap(c, fn, merge_gap);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ChexelState &X = c->chexels;
+    X.ansi_cw = console_w; X.ansi_ch = console_h; X.ansi_vx = viewport_x; X.ansi_vy = viewport_y;
+    X.ansi_fg = default_fg16; X.ansi_bg = default_bg16; X.ansi_clear = clear_screen != 0;
+    X.delta_gap = merge_gap;
+    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
+    if (rc != YCGE_OK) return rc;
+    const bool full = !prev_pairs || clear_screen != 0;
+    const size_t bytes = 2 * (size_t)fbW * fbH;
+    DevBuf<uint8_t> in, prev;
+    HIP_TRY(c, in.alloc(bytes));
+    HIP_TRY(c, hipMemcpy(in.p, pairs, bytes, hipMemcpyHostToDevice));
+    if (!full) {
+        HIP_TRY(c, prev.alloc(bytes));
+        HIP_TRY(c, hipMemcpy(prev.p, prev_pairs, bytes, hipMemcpyHostToDevice));
+    }
+    rc = full ? launch_stream(c, X, c->stream, in.p, fbW, fbH) : launch_delta(c, X, c->stream, in.p, prev.p, fbW, fbH);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return deliver_delta(c, X, fn, full, bound, out_stream, out_len, out_info);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

@@ -99,7 +99,13 @@ int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool seco
     DevBuf<uint8_t> &out = X->out[second ? 1 : 0];
     if (out.cap < L.total) HIP_TRY(c, out.alloc(L.total));
     if (X->dst[1] || X->dst[2] || ansi) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
-    const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, X->dst[0] ? out.p + L.c16 : nullptr, X->dst[1] || ansi ? out.p + L.ansi : nullptr,
+    uint8_t *pairs = out.p + L.ansi;
+    if (X->delta_on) {                                                                   // (a _delta call: the pairs go where the next call finds them)
+        DevBuf<uint8_t> &next = X->delta_pairs[1 - X->delta_prev];
+        if (next.cap < 2 * L.n) HIP_TRY(c, next.alloc(2 * L.n));
+        pairs = next.p;
+    }
+    const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, X->dst[0] ? out.p + L.c16 : nullptr, X->dst[1] || ansi ? pairs : nullptr,
                                       X->dst[2] ? out.p + L.rgba : nullptr, c->compute_units, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed: %s", hipGetErrorString((hipError_t)e));
     return YCGE_OK;
@@ -125,7 +131,8 @@ int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second)
         }
         HIP_TRY(c, hipMemcpyAsync(target, src + off[k], bytes[k], hipMemcpyDeviceToHost, stream));
     }
-    if (X->ansi_on) return ansi_enqueue(c, stream, src + L.ansi);          // (ycge_ansi.cpp: the escape stream from the pairs, and its length)
+    if (X->ansi_on)                                                        // (ycge_ansi.cpp: the escape stream from the pairs, and its length)
+        return ansi_enqueue(c, stream, X->delta_on ? X->delta_pairs[1 - X->delta_prev].p : src + L.ansi);
     return YCGE_OK;
 }
 

@@ -106,6 +106,8 @@ int ycge_launch_chexels(const float *sdr, int fbW, int fbH, const uint8_t *table
 uint32_t ycge_launch_ansi_tiles(uint32_t cells);
 int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
                             int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
+int ycge_launch_ansi_delta(const uint8_t *pairs, const uint8_t *prev, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
+                           int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream);
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
 size_t ycge_launch_obj_sizes(int which);
 int ycge_launch_obj_count_lines(const uint8_t *text, uint32_t n, uint32_t first, uint32_t *tiles, void *header, hipStream_t stream);
@@ -394,6 +396,17 @@ struct ChexelState {
     DevBuf<float> ansi_palette;                        // the 16 palette colours as 8 SDR chexels, then their 16 ANSI indices (bytes at float 48)
     bool ansi_palette_ready = false;
     PinnedBuf ansi_len_host;                           // page-locked word the length is copied to
+    // ycge_render_frame_ansi_delta / ycge_video_blit_ansi_delta: the encode of such a call writes its pairs into delta_pairs[1 - delta_prev];
+    // delta_pairs[delta_prev] holds those of the last stream handed out while delta_valid, for the geometry delta_key.  A successful call
+    // flips delta_prev - nothing is copied.  Whatever shows the terminal something else (a plain _ansi call, ycge_resize, a failure) clears delta_valid.
+    bool delta_on = false, delta_full = false;         // a _delta call is in progress; it returns a keyframe (the full stream's kernels)
+    int32_t delta_gap = 0;
+    DevBuf<uint8_t> delta_pairs[2];
+    int delta_prev = 0;
+    bool delta_valid = false;
+    int32_t delta_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // {cw, ch, vx, vy, dfg, dbg, fbW, fbH}
+    DevBuf<unsigned long long> delta_res;              // {length, changed, emitted, run starts}, as the delta scan wrote them
+    PinnedBuf delta_res_host;
 };
 // what the video blits of one context hold (ycge_video.cpp): made by the first blit, grow-only; nothing a ray-traced frame reads
 struct VideoState {

@@ -560,18 +560,22 @@ class RaytraceRenderer:
             raise abi.YcgeError(rc, f"no ANSI stream bound for a {console_width} x {console_height} console")
         return n.value
 
+    def _ansi_out(self, console_width: int, console_height: int):
+        """the renderer's growable page-locked stream buffer, at least the bound of this console"""
+        bound = self.ansi_stream_bound(console_width, console_height, self.L)
+        buf = self.__dict__.get("_ansi_buf")
+        if buf is None or buf[0].size < bound:
+            self.__dict__.pop("_ansi_buf", None)
+            buf = self.__dict__["_ansi_buf"] = self._page_locked_zeros((bound,), np.uint8)
+        return buf[0]
+
     def TryFlipAndBlitAnsi(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                            clear_screen: bool = False, sdr: bool = False):
         """One frame (ycge_render_frame_ansi): the bytes ANSITerminalRenderer.Render() writes for a console over this framebuffer at
         `viewport`, built on the device - `bytes`, or (bytes, SDR array) with sdr=True.  The SDR and the frame state are those of
         TryFlipAndBlit(want_sdr=True); the frame statistics go to self.stats.  The stream is read back into one growable page-locked
         buffer of the renderer, freed by close()."""
-        bound = self.ansi_stream_bound(console_width, console_height, self.L)
-        buf = self.__dict__.get("_ansi_buf")
-        if buf is None or buf[0].size < bound:
-            self.__dict__.pop("_ansi_buf", None)
-            buf = self.__dict__["_ansi_buf"] = self._page_locked_zeros((bound,), np.uint8)
-        out = buf[0]
+        out = self._ansi_out(console_width, console_height)
         n = C.c_size_t(0)
         s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
         self._check(self.L.ycge_render_frame_ansi(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
@@ -579,6 +583,24 @@ class RaytraceRenderer:
                                                   C.byref(n), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
         stream = out[:n.value].tobytes()
         return (stream, s) if sdr else stream
+
+    DELTA_INFO = ("keyframe", "changed", "emitted", "runs")
+
+    def TryFlipAndBlitAnsiDelta(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                                clear_screen: bool = False, merge_gap: int = 3, keyframe: bool = False, sdr: bool = False):
+        """One frame (ycge_render_frame_ansi_delta): the bytes that bring a terminal showing this context's last stream to this frame -
+        only the cells that changed, or the whole stream of TryFlipAndBlitAnsi when a keyframe is due (the first call, another
+        geometry, clear_screen, keyframe, after Resize or a plain TryFlipAndBlitAnsi).  Returns (bytes, info) or (bytes, info, SDR
+        array) with sdr=True; info = {"keyframe", "changed", "emitted", "runs"}.  The frame state is TryFlipAndBlit's."""
+        out = self._ansi_out(console_width, console_height)
+        n, info = C.c_size_t(0), (C.c_uint32 * 4)()
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._check(self.L.ycge_render_frame_ansi_delta(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
+                                                        int(default_bg), int(bool(clear_screen)), int(merge_gap), int(bool(keyframe)),
+                                                        out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, C.byref(n), info,
+                                                        s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
+        stream, info = out[:n.value].tobytes(), dict(zip(self.DELTA_INFO, (int(v) for v in info)))
+        return (stream, info, s) if sdr else (stream, info)
 
     def Wait(self):
         self._check(self.L.ycge_wait(self.ctx))
@@ -791,12 +813,7 @@ class VideoRenderer:
         `bytes`, or (bytes, SDR array) with sdr=True.  The stream buffer is the RaytraceRenderer's (page-locked, growable)."""
         f, ptr, w, h, bpp = self._frame_args(frame)
         r = self._r
-        bound = RaytraceRenderer.ansi_stream_bound(console_width, console_height, self.L)
-        buf = r.__dict__.get("_ansi_buf")
-        if buf is None or buf[0].size < bound:
-            r.__dict__.pop("_ansi_buf", None)
-            buf = r.__dict__["_ansi_buf"] = r._page_locked_zeros((bound,), np.uint8)
-        o = buf[0]
+        o = r._ansi_out(console_width, console_height)
         n = C.c_size_t(0)
         s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
         r._check(self.L.ycge_video_blit_ansi(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
@@ -804,6 +821,22 @@ class VideoRenderer:
                                              s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
         stream = o[:n.value].tobytes()
         return (stream, s) if sdr else stream
+
+    def TryFlipAndBlitAnsiDelta(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                                clear_screen: bool = False, merge_gap: int = 3, keyframe: bool = False, sdr: bool = False):
+        """The delta form of TryFlipAndBlitAnsi (ycge_video_blit_ansi_delta), on the delta state this context shares with
+        RaytraceRenderer.TryFlipAndBlitAnsiDelta: (bytes, info) or (bytes, info, SDR array) with sdr=True."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        r = self._r
+        o = r._ansi_out(console_width, console_height)
+        n, info = C.c_size_t(0), (C.c_uint32 * 4)()
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        r._check(self.L.ycge_video_blit_ansi_delta(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]),
+                                                   int(default_fg), int(default_bg), int(bool(clear_screen)), int(merge_gap), int(bool(keyframe)),
+                                                   o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size, C.byref(n), info,
+                                                   s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
+        stream, info = o[:n.value].tobytes(), dict(zip(RaytraceRenderer.DELTA_INFO, (int(v) for v in info)))
+        return (stream, info, s) if sdr else (stream, info)
 
     # ---------------------------------------------------------------- tests only
     def blit_probe(self, frame, fb_width: int, fb_height: int, superSample: int = 1) -> np.ndarray:
