@@ -31,6 +31,10 @@
 //                cursor ends where Render() leaves it for Terminal.Start's HUD.  The first frame, a frame after a console resize
 //                (ClearPending) and a frame after a switch of geometry are keyframes: the full stream.  AnsiMergeGap: unchanged cells between
 //                two changed ones of a row that are rewritten rather than jumped over (0..8).
+//   AnsiTrueColor - with DeviceAnsiStream: the streams carry 24-bit colour (ycge_render_frame_ansi_rgb / _rgb_delta): ESC[38;2;R;G;Bm of the
+//                sRGB8 triples OpenGLTerminalRenderer shows, not the 240 colours of ChexelToAnsi256.  With DeviceAnsiDelta a cell is rewritten
+//                when a channel is more than AnsiRgbTolerance (0..255) away from what the terminal shows for it; 0 is the exact form.  The
+//                library keeps one terminal state per context: a switch of colour form is a keyframe (INTEGRATION.md section 8.2).
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -53,6 +57,9 @@ public sealed class HipRaytraceOptions
     // The default is the gap with the fewest total bytes over the resting sequence of profiles/ansi_delta_rate.json (config 4, 1921 x 541,
     // frames 1..60): 3, with 1 117 018 bytes in 59 deltas; gaps 2..5 lie within 0.4 % of it, gap 0 is 2.6 % above.
     public int AnsiMergeGap = 3;
+    public bool AnsiTrueColor = false;                        // DeviceAnsiStream: 24-bit colour streams
+    // 0 is the exact form and stays the default until profiles/ansi_rgb_rate.json has numbers that argue otherwise (INTEGRATION.md 8.2).
+    public int AnsiRgbTolerance = 0;
     public HipGeneratedWorld GeneratedWorld;                  // chunks that come from the generator are made on the device (ycge_scene_generate_grids)
 }
 
@@ -75,6 +82,8 @@ public sealed class HipGeneratedWorld
 /// same cells.  With HipRaytraceOptions.DeviceAnsiDelta they are built by ycge_render_frame_ansi_delta: that same stream for a keyframe (the
 /// first frame, after a resize, after another geometry), otherwise only the cells that changed since the frame before, which leave the
 /// terminal - cells, cursor and colours - as the full stream would.  Every frame handed over must be written, in order: Render() does.
+/// With HipRaytraceOptions.AnsiTrueColor the same streams carry 24-bit colour (ycge_render_frame_ansi_rgb / _rgb_delta); the presenter writes
+/// them as they are, and a wrapper of the other colour form on the same context starts with a keyframe - the library sees to that.
 /// A change of console size is handled as ANSITerminalRenderer does it: onResize(width, height), and the next frame written starts with
 /// ESC[2J ESC[H.  Only the raytrace framebuffer is drawn: AddFrameBuffer / RemoveFrameBuffer keep nothing.</summary>
 public sealed class DeviceAnsiTerminalRenderer : ITerminalRenderer
@@ -145,6 +154,8 @@ public partial class RaytraceEntity
         private ulong ansiCap, ansiLen;
         private readonly bool ansiDelta;            // DeviceAnsiDelta: delta streams between keyframes
         private readonly int ansiMergeGap;
+        private readonly bool ansiRgb;              // AnsiTrueColor: the 24-bit colour forms of the two calls
+        private readonly int ansiTolerance;
         private bool inFlight;                      // FrameLate: a frame queued by the last TryFlipAndBlit has not been waited for yet
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
         private ulong objectsSignature;
@@ -169,6 +180,7 @@ public partial class RaytraceEntity
             }
             ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
             ansiDelta = ansi != null && options.DeviceAnsiDelta; ansiMergeGap = options != null ? options.AnsiMergeGap : 3;
+            ansiRgb = ansi != null && options.AnsiTrueColor; ansiTolerance = options != null ? options.AnsiRgbTolerance : 0;
             frameLate = options != null && options.FrameLate && cfg.NDevices <= 1 && ansi == null;      // (frames in flight are the single-device form; the stream is synchronous)
             deviceColors = options != null && options.DeviceChexelColors;
             generated = options?.GeneratedWorld;
@@ -185,7 +197,9 @@ public partial class RaytraceEntity
         private void RenderAnsi(Framebuffer fb)
         {
             int cw = ansi.consoleWidth, ch = ansi.consoleHeight;
-            Ycge.Check(ctx, Ycge.ycge_ansi_stream_bound(cw, ch, out UIntPtr bound));
+            UIntPtr bound;
+            if (ansiRgb) Ycge.Check(ctx, Ycge.ycge_ansi_rgb_stream_bound(cw, ch, out bound));
+            else Ycge.Check(ctx, Ycge.ycge_ansi_stream_bound(cw, ch, out bound));
             if ((ulong)bound > ansiCap)
             {
                 if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; ansiCap = ansiLen = 0; }
@@ -193,7 +207,13 @@ public partial class RaytraceEntity
                 ansiBuf = (byte*)p; ansiCap = (ulong)bound;
             }
             UIntPtr len;
-            if (ansiDelta)
+            if (ansiRgb && ansiDelta)
+                Ycge.Check(ctx, Ycge.ycge_render_frame_ansi_rgb_delta(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
+                                                                      ansiMergeGap, ansiTolerance, 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null, null));
+            else if (ansiRgb)
+                Ycge.Check(ctx, Ycge.ycge_render_frame_ansi_rgb(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
+                                                                ansiBuf, (UIntPtr)ansiCap, &len, null, null));
+            else if (ansiDelta)
                 Ycge.Check(ctx, Ycge.ycge_render_frame_ansi_delta(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
                                                                   ansiMergeGap, 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null, null));
             else

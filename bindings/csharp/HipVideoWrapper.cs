@@ -35,6 +35,8 @@ public partial class RaytraceEntity
         private ulong ansiCap, ansiLen;
         private readonly bool ansiDelta;            // HipRaytraceOptions.DeviceAnsiDelta: delta streams, on the delta state the context shares with the ray-traced frames
         private readonly int ansiMergeGap;
+        private readonly bool ansiRgb;              // HipRaytraceOptions.AnsiTrueColor: the 24-bit colour forms
+        private readonly int ansiTolerance;
 
         /// <summary>sharedContext: the context of the raytrace wrapper of the same console, whose geometry must be fb's and superSample's
         /// (IntPtr.Zero: a context of this wrapper's own).</summary>
@@ -45,6 +47,7 @@ public partial class RaytraceEntity
             fbW = fb.Width; fbH = fb.Height; ss = Math.Max(1, superSample);         // VideoRenderer.cs:33-37
             ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
             ansiDelta = ansi != null && options.DeviceAnsiDelta; ansiMergeGap = options != null ? options.AnsiMergeGap : 3;
+            ansiRgb = ansi != null && options.AnsiTrueColor; ansiTolerance = options != null ? options.AnsiRgbTolerance : 0;
             deviceColors = options != null && options.DeviceChexelColors;
             if (sharedContext != IntPtr.Zero)
             {
@@ -99,7 +102,9 @@ public partial class RaytraceEntity
             if (ansi != null)
             {
                 int cw = ansi.consoleWidth, ch = ansi.consoleHeight;
-                Ycge.Check(ctx, Ycge.ycge_ansi_stream_bound(cw, ch, out UIntPtr bound));
+                UIntPtr bound;
+                if (ansiRgb) Ycge.Check(ctx, Ycge.ycge_ansi_rgb_stream_bound(cw, ch, out bound));
+                else Ycge.Check(ctx, Ycge.ycge_ansi_stream_bound(cw, ch, out bound));
                 if ((ulong)bound > ansiCap)
                 {
                     if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; ansiCap = ansiLen = 0; }
@@ -107,7 +112,13 @@ public partial class RaytraceEntity
                     ansiBuf = (byte*)p; ansiCap = (ulong)bound;
                 }
                 UIntPtr len;
-                if (ansiDelta)
+                if (ansiRgb && ansiDelta)
+                    Ycge.Check(ctx, Ycge.ycge_video_blit_ansi_rgb_delta(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
+                                                                        ansi.ClearPending ? 1 : 0, ansiMergeGap, ansiTolerance, 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null));
+                else if (ansiRgb)
+                    Ycge.Check(ctx, Ycge.ycge_video_blit_ansi_rgb(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
+                                                                  ansi.ClearPending ? 1 : 0, ansiBuf, (UIntPtr)ansiCap, &len, null));
+                else if (ansiDelta)
                     Ycge.Check(ctx, Ycge.ycge_video_blit_ansi_delta(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
                                                                     ansi.ClearPending ? 1 : 0, ansiMergeGap, 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null));
                 else

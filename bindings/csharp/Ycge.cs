@@ -244,6 +244,23 @@ namespace ConsoleGame.RayTracing.Native
                                                                              int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, int mergeGap,
                                                                              int keyframe, byte* outStream, UIntPtr capacity, UIntPtr* outLen, uint* outInfo,
                                                                              float* outTopBottomSdr);
+        // 24-bit colour ANSI streams (after ABI 10, found by symbol lookup): the five calls above on sRGB8 triples (ESC[38;2;R;G;Bm); the
+        // delta forms take a tolerance 0..255 behind mergeGap and compare against what the terminal shows
+        [DllImport(Lib)] public static extern int ycge_ansi_rgb_stream_bound(int consoleW, int consoleH, out UIntPtr bytes);
+        [DllImport(Lib)] public static extern int ycge_render_frame_ansi_rgb(IntPtr ctx, int consoleW, int consoleH, int viewportX, int viewportY, int defaultFg16,
+                                                                             int defaultBg16, int clearScreen, byte* outStream, UIntPtr capacity, UIntPtr* outLen,
+                                                                             float* outTopBottomSdr, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_render_frame_ansi_rgb_delta(IntPtr ctx, int consoleW, int consoleH, int viewportX, int viewportY, int defaultFg16,
+                                                                                   int defaultBg16, int clearScreen, int mergeGap, int tolerance, int keyframe,
+                                                                                   byte* outStream, UIntPtr capacity, UIntPtr* outLen, uint* outInfo,
+                                                                                   float* outTopBottomSdr, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_video_blit_ansi_rgb(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int consoleW, int consoleH,
+                                                                           int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, byte* outStream,
+                                                                           UIntPtr capacity, UIntPtr* outLen, float* outTopBottomSdr);
+        [DllImport(Lib)] public static extern int ycge_video_blit_ansi_rgb_delta(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int consoleW, int consoleH,
+                                                                                 int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, int mergeGap,
+                                                                                 int tolerance, int keyframe, byte* outStream, UIntPtr capacity, UIntPtr* outLen,
+                                                                                 uint* outInfo, float* outTopBottomSdr);
         // OBJ meshes from file bytes (MeshLoader.FromObj on the device; HipObjLoader.cs).  info: a YObjInfo
         [DllImport(Lib)] public static extern int ycge_obj_parse_host(byte* text, UIntPtr bytes, float* positions, int* faces, out YObjInfo info, byte* msg, UIntPtr msgBytes);
         [DllImport(Lib)] public static extern int ycge_obj_parse(IntPtr ctx, byte* text, UIntPtr bytes, out YObjInfo info);

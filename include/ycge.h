@@ -575,6 +575,62 @@ int ycge_video_blit_ansi_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t src_
                                int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t keyframe,
                                uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */,
                                float *out_top_bottom_sdr /* may be NULL */);
+/* --- 24-bit colour ANSI streams: the full, delta and video forms above on sRGB8 triples instead of palette indices, for terminals that take
+ * ESC[38;2;R;G;Bm / ESC[48;2;R;G;Bm.  The reference has no 24-bit presenter, so these rules define the bytes; they are Render()'s
+ * (ANSITerminalRenderer.cs:86-153) - the same walk, the same three branches, the same trailer - with "index" replaced by "sRGB8 triple".
+ * Added after ABI 10 without changing it: a host detects these exports by symbol lookup.
+ *   Colours.  A covered cell is ('▀', fg = RGB8(top), bg = RGB8(bottom)), RGB8 the three bytes ycge_render_frame_chexels writes for that
+ *   half-cell into out_rgba (row 2 cy the top, row 2 cy + 1 the bottom).  Any other cell is (' ', RGB8(palette[default_fg16]),
+ *   RGB8(palette[default_bg16])), from the same encoder run on the 16 palette colours.  Two colours are equal when all three bytes are.
+ *   Full stream.  [ESC[2J ESC[H when clear_screen], per row ESC[<y+1>;1H, per cell against the previous cell in raster order (nothing before
+ *   the first cell, rows included):
+ *       both differ   ESC[38;2;R;G;B;48;2;R;G;Bm      fg only   ESC[38;2;R;G;Bm      bg only   ESC[48;2;R;G;Bm      neither   nothing
+ *   then the character, and ESC[0m at the end.  Numbers as AppendInt writes them.
+ *   Bound.  The longest escape is 7 + 11 + 6 + 11 + 1 = 36 bytes, a cell at most 36 + 3 = 39:
+ *   ycge_ansi_rgb_stream_bound = 7 + 4 + sum over rows of (5 + digits(y + 1)) + 39 console_w console_h - no context, no device, refused as
+ *   ycge_ansi_stream_bound refuses.  A console whose bound reaches 2^32 is refused by every stream call (offsets are 32-bit).
+ *   Delta, with merge_gap = G in 0..8, keyframe as in ycge_render_frame_ansi_delta, and tolerance = T in 0..255:
+ *     shown(x, y): the fg / bg pair of triples the terminal displays for a covered cell, according to the streams this context handed out
+ *       through the two _rgb_delta exports.
+ *     changed(x, y): the cell is covered and the largest |cur - shown| over its six channels exceeds T (T = 0: "differs").
+ *     emitted, run starts and cursor moves are ycge_render_frame_ansi_delta's: gap merge inside a row only, the console's last cell always
+ *       emitted, a run start writes ESC[<y+1>;<x+1>H and then the both-differ escape unconditionally; no clear prefix, no per-row moves;
+ *       the trailer ESC[0m.  Any other emitted cell writes the three-branch escape against cur(x - 1, y): its left neighbour is emitted, so
+ *       that is what the terminal holds there.
+ *     After a successful call shown = cur for every emitted covered cell and is unchanged for every other; after a keyframe shown = cur.
+ *     Guarantee: a terminal that shows the previous streams, fed this delta, ends with the cursor (pending wrap included) and the SGR state
+ *       where the full stream of this frame leaves them, every cell's character the full stream's and every channel within T of the full
+ *       stream's - identical when T = 0.  The error never accumulates: the comparison is against shown, not against the previous frame.
+ *     (Why a tolerance: the 240-colour palette hid the +-1 flicker that TAA's running blend leaves in a resting picture; at 24 bits it would
+ *     mark nearly every cell changed on every frame.)
+ *   Keyframe: the full 24-bit stream for the same arguments, byte for byte - when there is no valid shown, when the geometry key
+ *   {console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, fbW, fbH} differs, when clear_screen or keyframe is set.
+ *   out_info as in ycge_render_frame_ansi_delta.  A delta never exceeds ycge_ansi_rgb_stream_bound (the proof: csrc/ycge_ansi_rgb.hip; the
+ *   2 x 1 console with both cells changed and every channel three-digit reaches the bound less 7).
+ *   State.  One terminal per context: the 24-bit delta state and the 256-colour delta state invalidate each other.  The next delta call of
+ *   EITHER family is a keyframe after: any full stream of either family and either renderer, a delta of the other family, ycge_resize, a
+ *   change of the framebuffer size, a failure behind the argument checks.  An argument refusal leaves the state untouched.  The ray-traced
+ *   and the video 24-bit deltas share one state.  tolerance outside 0..255 is YCGE_ERR_INVALID_ARG, the message names the value.
+ *   Everything else - the frame state, the SDR, the statistics, the refusals (peer context, RCCL with lean slabs, NULLs, capacity below the
+ *   bound, defaults outside 0..15), "nothing written by a refused or failed call" - is the corresponding _ansi / _ansi_delta call's.  The
+ *   RGBA plane stays on the device. */
+int ycge_ansi_rgb_stream_bound(int32_t console_w, int32_t console_h, size_t *bytes);
+int ycge_render_frame_ansi_rgb(ycge_ctx *ctx, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                               int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len,
+                               float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+int ycge_render_frame_ansi_rgb_delta(ycge_ctx *ctx, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                                     int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance, int32_t keyframe,
+                                     uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */,
+                                     float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+int ycge_video_blit_ansi_rgb(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                             int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
+                             int32_t default_fg16, int32_t default_bg16, int32_t clear_screen,
+                             uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr /* may be NULL */);
+int ycge_video_blit_ansi_rgb_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                                   int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
+                                   int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance,
+                                   int32_t keyframe, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */,
+                                   float *out_top_bottom_sdr /* may be NULL */);
 /* --- OBJ meshes from file bytes: MeshLoader.FromObj (RayTracing/MeshLoader.cs:12-149) up to the float soup ycge_mesh.triangles takes, parsed
  * on the device.  Added after ABI 10 without changing it (YCGE_ABI_VERSION stays 10, no struct changes; detect by symbol lookup).
  *   The contract, byte by byte ("the reference's loader" restated correctly; tests/obj_restatement.py is its yardstick):

@@ -56,6 +56,18 @@ int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_
 int ycge_test_ansi_delta(ycge_ctx *c, const uint8_t *prev_pairs, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h,
                          int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
                          uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info);
+/* ---- the 24-bit colour streams (csrc/ycge_ansi.cpp, kernels csrc/ycge_ansi_rgb.hip): the stream kernels alone on a caller-given colour
+ * image in the layout they read in the product - out_rgba's, fbW x 2 fbH RGBA8, row 2 cy the top half-cell, the fourth byte ignored - with
+ * the geometry, defaults and refusals of ycge_render_frame_ansi_rgb / _rgb_delta.  The delta hook is stateless: shown (NULL or
+ * clear_screen != 0: the keyframe, ycge_test_ansi_rgb_stream's bytes) and cur are the caller's, and out_shown (or NULL) receives the next
+ * shown in the same layout with every fourth byte 255 - cur after a keyframe, otherwise cur where a covered cell was emitted and shown
+ * everywhere else - so a test chains frames without a scene */
+int ycge_test_ansi_rgb_stream(ycge_ctx *c, const uint8_t *rgba, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,
+                              int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
+                              size_t *out_len);
+int ycge_test_ansi_rgb_delta(ycge_ctx *c, const uint8_t *shown, const uint8_t *cur, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h,
+                             int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
+                             int32_t tolerance, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, uint8_t *out_shown);
 /* ---- Video mode (csrc/ycge_video.cpp).  ycge_host_video_tables: host only, no device - for src_w x src_h -> fbW x fbH ss the tables
  * k_video_blit reads, as the library computed them with the C library's sinf: per hi-res column x0 (hiW = fbW*ss entries) and its six
  * normalised weights (6 hiW), per hi-res row y0 (hiH = fbH*2*ss) and weights (6 hiH), and {scale, offX, offY} (VideoRenderer.cs:75-81).

@@ -249,6 +249,18 @@ _PROTOTYPES = {
     "ycge_video_blit_ansi_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t),
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    # the 24-bit colour forms of the five above (the _delta ones take `tolerance` behind merge_gap)
+    "ycge_ansi_rgb_stream_bound": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "ycge_render_frame_ansi_rgb": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
+                                             C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(FrameStats)]),
+    "ycge_render_frame_ansi_rgb_delta": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                                   C.POINTER(FrameStats)]),
+    "ycge_video_blit_ansi_rgb": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    "ycge_video_blit_ansi_rgb_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
+                                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
     "ycge_obj_parse_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "ycge_obj_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -306,6 +318,13 @@ VIDEO_HOOK_PROTOTYPES = {
 ANSI_DELTA_HOOK_PROTOTYPES = {
     "ycge_test_ansi_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)] + [C.c_int32] * 10 +
                              [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+}
+# test hooks of the 24-bit colour streams (csrc/ycge_ansi.cpp), bound where they are used (tests/test_gpu_ansi_rgb.py): the planes are
+# fbW x 2 fbH RGBA8; the delta hook's last argument is out_shown (or None)
+ANSI_RGB_HOOK_PROTOTYPES = {
+    "ycge_test_ansi_rgb_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)] + [C.c_int32] * 9 + [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ycge_test_ansi_rgb_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)] + [C.c_int32] * 11 +
+                                 [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
 }
 # test / profiling hooks of the device-side mesh BVH build (csrc/ycge_mesh_bvh.cpp), bound where they are used (RaytraceRenderer.mesh_bvh_stats,
 # device_mesh_bvh below); res16: MESH_BVH_RES_WORDS uint32, the fallback reasons as the library names them

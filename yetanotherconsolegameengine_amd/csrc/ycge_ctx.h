@@ -108,6 +108,11 @@ int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int 
                             int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
 int ycge_launch_ansi_delta(const uint8_t *pairs, const uint8_t *prev, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
                            int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream);
+int ycge_launch_ansi_rgb_stream(const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
+                                int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
+int ycge_launch_ansi_rgb_delta(const uint8_t *rgba, const uint8_t *shown, uint8_t *next, int fbW, int fbH, int cw, int ch, int vx, int vy,
+                               const uint8_t *palette, int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap,
+                               unsigned long long *res, hipStream_t stream);
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
 size_t ycge_launch_obj_sizes(int which);
 int ycge_launch_obj_count_lines(const uint8_t *text, uint32_t n, uint32_t first, uint32_t *tiles, void *header, hipStream_t stream);
@@ -407,6 +412,17 @@ struct ChexelState {
     int32_t delta_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // {cw, ch, vx, vy, dfg, dbg, fbW, fbH}
     DevBuf<unsigned long long> delta_res;              // {length, changed, emitted, run starts}, as the delta scan wrote them
     PinnedBuf delta_res_host;
+    // the 24-bit colour forms (ycge_render_frame_ansi_rgb and its kin; kernels: ycge_ansi_rgb.hip): ansi_rgb marks the call at hand as one.
+    // Its encode keeps the RGBA plane on the device.  The delta state above is the one terminal's, whichever family drew it: delta_rgb says
+    // which family delta_valid speaks of, and a call of the other family finds no valid state.  delta_shown[delta_prev] is what the terminal
+    // displays (the plane's layout); a keyframe's encode writes the plane into delta_shown[1 - delta_prev], a delta's write kernel writes
+    // emitted ? cur : shown there, and a successful call flips delta_prev.
+    bool ansi_rgb = false;
+    int32_t delta_tol = 0;
+    bool delta_rgb = false;
+    DevBuf<uint8_t> delta_shown[2];
+    DevBuf<uint8_t> rgb_palette;                       // RGB8 of the 16 palette colours: the encoder's 8 x 2 RGBA plane of ansi_palette's chexels
+    bool rgb_palette_ready = false;
 };
 // what the video blits of one context hold (ycge_video.cpp): made by the first blit, grow-only; nothing a ray-traced frame reads
 struct VideoState {

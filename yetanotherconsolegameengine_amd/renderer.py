@@ -602,6 +602,54 @@ class RaytraceRenderer:
         stream, info = out[:n.value].tobytes(), dict(zip(self.DELTA_INFO, (int(v) for v in info)))
         return (stream, info, s) if sdr else (stream, info)
 
+    # ---------------------------------------------------------------- the 24-bit colour forms (ycge_render_frame_ansi_rgb / _rgb_delta)
+    @staticmethod
+    def ansi_rgb_stream_bound(console_width: int, console_height: int, lib=None) -> int:
+        """The most bytes a 24-bit colour stream of a console_width x console_height console can take (ycge_ansi_rgb_stream_bound; no GPU needed)."""
+        L = lib if lib is not None else abi.load_library()
+        n = C.c_size_t(0)
+        rc = L.ycge_ansi_rgb_stream_bound(int(console_width), int(console_height), C.byref(n))
+        if rc != 0:
+            raise abi.YcgeError(rc, f"no 24-bit ANSI stream bound for a {console_width} x {console_height} console")
+        return n.value
+
+    def _ansi_rgb_out(self, console_width: int, console_height: int):
+        """the renderer's growable page-locked stream buffer (_ansi_out's), at least the 24-bit bound of this console"""
+        bound = self.ansi_rgb_stream_bound(console_width, console_height, self.L)
+        buf = self.__dict__.get("_ansi_buf")
+        if buf is None or buf[0].size < bound:
+            self.__dict__.pop("_ansi_buf", None)
+            buf = self.__dict__["_ansi_buf"] = self._page_locked_zeros((bound,), np.uint8)
+        return buf[0]
+
+    def TryFlipAndBlitAnsiRgb(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                              clear_screen: bool = False, sdr: bool = False):
+        """TryFlipAndBlitAnsi in 24-bit colour (ycge_render_frame_ansi_rgb): the same walk with ESC[38;2;R;G;Bm / ESC[48;2;R;G;Bm of the
+        sRGB8 triples TryFlipAndBlit(rgba=True) gives - `bytes`, or (bytes, SDR array) with sdr=True."""
+        out = self._ansi_rgb_out(console_width, console_height)
+        n = C.c_size_t(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._check(self.L.ycge_render_frame_ansi_rgb(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
+                                                      int(default_bg), int(bool(clear_screen)), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size,
+                                                      C.byref(n), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
+        stream = out[:n.value].tobytes()
+        return (stream, s) if sdr else stream
+
+    def TryFlipAndBlitAnsiRgbDelta(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                                   clear_screen: bool = False, merge_gap: int = 3, tolerance: int = 0, keyframe: bool = False, sdr: bool = False):
+        """TryFlipAndBlitAnsiDelta in 24-bit colour (ycge_render_frame_ansi_rgb_delta): a cell is rewritten when a channel is more than
+        `tolerance` (0..255; 0 = exact) away from what the terminal shows for it.  One terminal per context: a stream of the other colour
+        form makes the next call a keyframe.  Returns (bytes, info) or (bytes, info, SDR array) with sdr=True."""
+        out = self._ansi_rgb_out(console_width, console_height)
+        n, info = C.c_size_t(0), (C.c_uint32 * 4)()
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._check(self.L.ycge_render_frame_ansi_rgb_delta(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]),
+                                                            int(default_fg), int(default_bg), int(bool(clear_screen)), int(merge_gap), int(tolerance),
+                                                            int(bool(keyframe)), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, C.byref(n), info,
+                                                            s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
+        stream, info = out[:n.value].tobytes(), dict(zip(self.DELTA_INFO, (int(v) for v in info)))
+        return (stream, info, s) if sdr else (stream, info)
+
     def Wait(self):
         self._check(self.L.ycge_wait(self.ctx))
 
@@ -835,6 +883,36 @@ class VideoRenderer:
                                                    int(default_fg), int(default_bg), int(bool(clear_screen)), int(merge_gap), int(bool(keyframe)),
                                                    o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size, C.byref(n), info,
                                                    s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
+        stream, info = o[:n.value].tobytes(), dict(zip(RaytraceRenderer.DELTA_INFO, (int(v) for v in info)))
+        return (stream, info, s) if sdr else (stream, info)
+
+    def TryFlipAndBlitAnsiRgb(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                              clear_screen: bool = False, sdr: bool = False):
+        """TryFlipAndBlitAnsi in 24-bit colour (ycge_video_blit_ansi_rgb): `bytes`, or (bytes, SDR array) with sdr=True."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        r = self._r
+        o = r._ansi_rgb_out(console_width, console_height)
+        n = C.c_size_t(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        r._check(self.L.ycge_video_blit_ansi_rgb(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]),
+                                                 int(default_fg), int(default_bg), int(bool(clear_screen)), o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size,
+                                                 C.byref(n), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
+        stream = o[:n.value].tobytes()
+        return (stream, s) if sdr else stream
+
+    def TryFlipAndBlitAnsiRgbDelta(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                                   clear_screen: bool = False, merge_gap: int = 3, tolerance: int = 0, keyframe: bool = False, sdr: bool = False):
+        """The delta form of TryFlipAndBlitAnsiRgb (ycge_video_blit_ansi_rgb_delta), on the delta state this context shares with
+        RaytraceRenderer.TryFlipAndBlitAnsiRgbDelta: (bytes, info) or (bytes, info, SDR array) with sdr=True."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        r = self._r
+        o = r._ansi_rgb_out(console_width, console_height)
+        n, info = C.c_size_t(0), (C.c_uint32 * 4)()
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        r._check(self.L.ycge_video_blit_ansi_rgb_delta(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]),
+                                                       int(default_fg), int(default_bg), int(bool(clear_screen)), int(merge_gap), int(tolerance),
+                                                       int(bool(keyframe)), o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size, C.byref(n), info,
+                                                       s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
         stream, info = o[:n.value].tobytes(), dict(zip(RaytraceRenderer.DELTA_INFO, (int(v) for v in info)))
         return (stream, info, s) if sdr else (stream, info)
 
