@@ -555,7 +555,7 @@ int ycge_video_blit_ansi(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int
  *     ESC[<y+1>;<x+1>H, then ESC[38;5;<fg>;48;5;<bg>m unconditionally (Render()'s first branch against (-1, -1)).  Any other emitted cell
  *     writes the escape of Render()'s three branches (ANSITerminalRenderer.cs:120-143) against the pair of (x - 1, y).  Then the cell's
  *     character: '\u2580' in UTF-8 when covered, ' ' otherwise.  The stream ends with ESC[0m.  No clear prefix, no per-row ;1H moves.
- *   A delta never exceeds ycge_ansi_stream_bound, which stays the capacity to pass (the proof: csrc/ycge_ansi_delta.hip).
+ *   A delta never exceeds ycge_ansi_stream_bound, which stays the capacity to pass (the proof: csrc/ycge_ansi_cells.hip.h).
  *   out_info (4 words, or NULL): {keyframe returned (0 / 1), changed cells, emitted cells, run starts}; the three counts are 0 on a keyframe.
  *   State: prev advances only when one of these two calls returns YCGE_OK (two pair buffers are swapped, nothing is copied).  The next call
  *   is a keyframe after: a failure behind the call's refusals, ycge_resize, a change of the framebuffer size, a call to
@@ -605,7 +605,7 @@ int ycge_video_blit_ansi_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t src_
  *     mark nearly every cell changed on every frame.)
  *   Keyframe: the full 24-bit stream for the same arguments, byte for byte - when there is no valid shown, when the geometry key
  *   {console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, fbW, fbH} differs, when clear_screen or keyframe is set.
- *   out_info as in ycge_render_frame_ansi_delta.  A delta never exceeds ycge_ansi_rgb_stream_bound (the proof: csrc/ycge_ansi_rgb.hip; the
+ *   out_info as in ycge_render_frame_ansi_delta.  A delta never exceeds ycge_ansi_rgb_stream_bound (the same proof, with 39 for 23; the
  *   2 x 1 console with both cells changed and every channel three-digit reaches the bound less 7).
  *   State.  One terminal per context: the 24-bit delta state and the 256-colour delta state invalidate each other.  The next delta call of
  *   EITHER family is a keyframe after: any full stream of either family and either renderer, a delta of the other family, ycge_resize, a

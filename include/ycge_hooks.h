@@ -49,7 +49,7 @@ int ycge_test_encode_chexels(ycge_ctx *c, const float *sdr, int32_t w, int32_t h
 int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,
                           int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
                           size_t *out_len);
-/* ---- the delta ANSI stream (csrc/ycge_ansi.cpp, kernels csrc/ycge_ansi_delta.hip): the delta kernels alone on caller-given pair arrays,
+/* ---- the delta ANSI stream (csrc/ycge_ansi.cpp, kernels csrc/ycge_ansi.hip): the delta kernels alone on caller-given pair arrays,
  * prev_pairs and pairs both fbW x fbH {fg, bg}, with the rules, refusals and out_info of ycge_render_frame_ansi_delta.  A NULL prev_pairs
  * (or clear_screen != 0) gives the keyframe, the bytes of ycge_test_ansi_stream.  Stateless: pair buffers of its own, the context's delta
  * state untouched */

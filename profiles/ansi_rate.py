@@ -111,7 +111,7 @@ def part_kernel(out: Path):
     g.close()
 
 
-KERNELS = ("k_ansi_count", "k_ansi_scan", "k_ansi_write", "k_encode_chexels", "k_tonemap")
+KERNELS = ("k_count", "k_scan", "k_write", "k_encode_chexels", "k_tonemap")      # (ycge_ansi_cells.hip.h's full-stream kernels, whichever colour form)
 
 
 def kernel_rows(path):

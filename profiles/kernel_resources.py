@@ -33,6 +33,6 @@ if not rows:
     sys.exit("no kernels found (did the compile fail?)\n" + r.stderr[-2000:])
 dem = subprocess.run(["c++filt"] + [r_["name"] for r_ in rows], capture_output=True, text=True).stdout.splitlines()
 for r_, d in zip(rows, dem):
-    d = d.replace("ycge::", "").split("(")[0].replace("void ", "")
+    d = d.replace("ycge::", "").replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
     print(f"{d:46s} VGPR={r_.get('VGPRs','?'):>4s} SGPR={r_.get('TotalSGPRs','?'):>4s} scratch={r_.get('ScratchSize [bytes/lane]','?'):>5s} "
           f"LDS={r_.get('LDS Size [bytes/block]','?'):>6s} occ={r_.get('Occupancy [waves/SIMD]','?')}")

@@ -155,12 +155,18 @@ def test_the_new_exports_are_declared_everywhere():
 
 
 def test_the_kernels_live_in_their_own_unit_with_the_bound_proved():
+    """the 256-colour unit instantiates the shared header, which carries the scheme of both colour forms once, the proof of the bound in
+    its head; the delta stream has no unit of its own any more"""
     from yetanotherconsolegameengine_amd import build
-    assert {"ycge_ansi.hip", "ycge_ansi_delta.hip"} <= set(build.SOURCES) and "ycge_ansi_cells.hip.h" in build.HEADERS
-    src = (Path(abi.__file__).resolve().parent / "csrc" / "ycge_ansi_delta.hip").read_text()
+    csrc = Path(abi.__file__).resolve().parent / "csrc"
+    assert "ycge_ansi.hip" in build.SOURCES and "ycge_ansi_cells.hip.h" in build.HEADERS
+    assert "ycge_ansi_delta.hip" not in build.SOURCES and not (csrc / "ycge_ansi_delta.hip").exists()
+    src = (csrc / "ycge_ansi_cells.hip.h").read_text()
     assert "The bound." in src.split("#include")[0]
-    for k in ("k_delta_count", "k_delta_scan", "k_delta_write"):
+    for k in ("void k_delta_count(", "void k_scan(", "void k_delta_write("):
         assert k in src
+    unit = (csrc / "ycge_ansi.hip").read_text()
+    assert '#include "ycge_ansi_cells.hip.h"' in unit and "launch_delta<" in unit
 
 
 def test_the_default_merge_gap_is_the_measured_one():

@@ -1,22 +1,21 @@
-// ycge_ansi.cpp - the ANSI presenter's escape stream on the device (ycge_render_frame_ansi, ycge_ansi_stream_bound; kernels:
-// ycge_ansi.hip).
+// ycge_ansi.cpp - the ANSI presenter's escape streams on the device (ycge_render_frame_ansi and its kin, ycge_ansi_stream_bound; kernels:
+// ycge_ansi.hip and ycge_ansi_rgb.hip over ycge_ansi_cells.hip.h).
 //
 // A frame of ycge_render_frame_ansi is ycge_render_frame_chexels' with the ANSI pairs alone, kept on the device: behind their encode,
 // on the same stream, three launches turn them into the bytes ANSITerminalRenderer.Render() writes (ANSITerminalRenderer.cs:86-153)
 // for a console over the framebuffer, and the stream's length is copied to a page-locked word.  Once the stream is synchronised, exactly
-// that many bytes are copied to the caller.  The request lives in ChexelState for the length of one call (a scope guard clears it; on an
-// error return also every latched destination), so no other entry point issues a launch or copy of it.
+// that many bytes are copied to the caller.  The request (AnsiRequest) lives in ChexelState for the length of one call (a scope guard
+// clears it; on an error return also every latched destination), so no other entry point issues a launch or copy of it.
 //
-// The delta form (ycge_render_frame_ansi_delta, ycge_video_blit_ansi_delta; kernels: ycge_ansi_delta.hip) keeps the pairs of the last
-// stream it handed out in one of two buffers of ChexelState and writes only the cells that changed since; the contract is in
-// include/ycge.h.  Its encode writes into the other buffer and a successful call flips the two: nothing is copied.  A keyframe runs the
-// full stream's kernels on those pairs, so its bytes are ycge_render_frame_ansi's.
+// The delta form (ycge_render_frame_ansi_delta, ycge_video_blit_ansi_delta) keeps the pairs of the last stream it handed out in one of two
+// buffers of ChexelState and writes only the cells that changed since; the contract is in include/ycge.h.  Its encode writes into the
+// other buffer and a successful call flips the two: nothing is copied.  A keyframe runs the full stream's kernels on those pairs, so its
+// bytes are ycge_render_frame_ansi's.
 //
-// The 24-bit colour forms (ycge_render_frame_ansi_rgb, ycge_render_frame_ansi_rgb_delta and the two video calls; kernels:
-// ycge_ansi_rgb.hip) are the same calls with `rgb` set: the encode keeps the RGBA plane instead of the pairs, the bound counts 39 bytes a
-// cell, and the delta compares against what the terminal shows (ChexelState::delta_shown) under a tolerance.  One request guard, one delta
-// state machine and one delivery serve both families; the state belongs to the one terminal, so a stream of either family invalidates it
-// for both.
+// The 24-bit colour forms (ycge_render_frame_ansi_rgb, ycge_render_frame_ansi_rgb_delta and the two video calls) are the same calls with
+// `rgb` set in the request: the encode keeps the RGBA plane instead of the pairs, the bound counts 39 bytes a cell, and the delta compares
+// against what the terminal shows under a tolerance.  One request, one launch, one guard and one delivery serve every form; the delta
+// state belongs to the one terminal, so a stream of either family invalidates it for both.
 //
 // The default cell's colours are ansi(palette16[k]): k_encode_chexels run once on the 16 palette colours, so no second formula exists.
 #include "ycge_ctx.h"
@@ -74,114 +73,113 @@ static int ensure_rgb_palette(ycge_ctx *c, ChexelState &X, hipStream_t stream)
     return YCGE_OK;
 }
 
-// the buffers of a cw x ch stream whose bound is `bound` (kept while large enough) and the default colours (rgb: their triples too)
-static int ensure_ansi(ycge_ctx *c, ChexelState &X, int32_t cw, int32_t ch, unsigned long long bound, hipStream_t stream, bool rgb = false)
+// the buffers of r's stream, whose bound is `bound` (kept while large enough), and the default colours (rgb: their triples too)
+static int ensure_ansi(ycge_ctx *c, ChexelState &X, const AnsiRequest &r, unsigned long long bound, hipStream_t stream)
 {
     if (X.ansi_stream.cap < bound) HIP_TRY(c, X.ansi_stream.alloc(bound));
-    const uint32_t tiles = ycge_launch_ansi_tiles((uint32_t)cw * (uint32_t)ch);
+    const uint32_t tiles = ycge_launch_ansi_tiles((uint32_t)r.cw * (uint32_t)r.ch);
     if (X.ansi_tiles.cap < 4 * (size_t)tiles) HIP_TRY(c, X.ansi_tiles.alloc(4 * (size_t)tiles));          // (the delta kernels keep four words a tile)
-    if (!X.ansi_len.p) HIP_TRY(c, X.ansi_len.alloc(1));
-    HIP_TRY(c, X.ansi_len_host.reserve(sizeof(unsigned long long)));
-    return rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream);
+    if (!X.ansi_res.p) HIP_TRY(c, X.ansi_res.alloc(4));
+    HIP_TRY(c, X.ansi_res_host.reserve(4 * sizeof(unsigned long long)));
+    return r.rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream);
 }
 
-static int launch_stream(ycge_ctx *c, ChexelState &X, hipStream_t stream, const uint8_t *d_pairs, int fbW, int fbH)
+// r's stream of the fbW x fbH plane d_plane (the pairs; rgb: the RGBA plane), and the copy of what the scan reports.  delta: against d_prev
+// - rgb: what the terminal displays, d_next the plane that receives the next such - with the copy of {length, changed, emitted, run starts};
+// otherwise the full stream and its length alone
+static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiRequest &r, bool delta, const uint8_t *d_plane, const uint8_t *d_prev, uint8_t *d_next,
+                  int fbW, int fbH)
 {
-    const int e = ycge_launch_ansi_stream(d_pairs, fbW, fbH, X.ansi_cw, X.ansi_ch, X.ansi_vx, X.ansi_vy, reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48),
-                                          X.ansi_fg, X.ansi_bg, X.ansi_clear, X.ansi_tiles.p, X.ansi_stream.p, X.ansi_stream.cap, X.ansi_len.p, stream);
-    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "ANSI stream launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(c, hipMemcpyAsync(X.ansi_len_host.p, X.ansi_len.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    return YCGE_OK;
-}
-
-// the delta stream of d_pairs against d_prev for the request in X, and the copy of {length, changed, emitted, run starts}
-static int launch_delta(ycge_ctx *c, ChexelState &X, hipStream_t stream, const uint8_t *d_pairs, const uint8_t *d_prev, int fbW, int fbH)
-{
-    if (!X.delta_res.p) HIP_TRY(c, X.delta_res.alloc(4));
-    HIP_TRY(c, X.delta_res_host.reserve(4 * sizeof(unsigned long long)));
-    const int e = ycge_launch_ansi_delta(d_pairs, d_prev, fbW, fbH, X.ansi_cw, X.ansi_ch, X.ansi_vx, X.ansi_vy, reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48),
-                                         X.ansi_fg, X.ansi_bg, X.delta_gap, X.ansi_tiles.p, X.ansi_stream.p, X.ansi_stream.cap, X.delta_res.p, stream);
-    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "ANSI delta stream launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(c, hipMemcpyAsync(X.delta_res_host.p, X.delta_res.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    return YCGE_OK;
-}
-
-// the 24-bit forms of the two: d_rgba the frame's RGBA plane; d_shown what the terminal displays, d_next the plane that receives the next `shown`
-static int launch_rgb_stream(ycge_ctx *c, ChexelState &X, hipStream_t stream, const uint8_t *d_rgba, int fbW, int fbH)
-{
-    const int e = ycge_launch_ansi_rgb_stream(d_rgba, fbW, fbH, X.ansi_cw, X.ansi_ch, X.ansi_vx, X.ansi_vy, X.rgb_palette.p, X.ansi_fg, X.ansi_bg, X.ansi_clear,
-                                              X.ansi_tiles.p, X.ansi_stream.p, X.ansi_stream.cap, X.ansi_len.p, stream);
-    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "24-bit ANSI stream launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(c, hipMemcpyAsync(X.ansi_len_host.p, X.ansi_len.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    return YCGE_OK;
-}
-
-static int launch_rgb_delta(ycge_ctx *c, ChexelState &X, hipStream_t stream, const uint8_t *d_rgba, const uint8_t *d_shown, uint8_t *d_next, int fbW, int fbH)
-{
-    if (!X.delta_res.p) HIP_TRY(c, X.delta_res.alloc(4));
-    HIP_TRY(c, X.delta_res_host.reserve(4 * sizeof(unsigned long long)));
-    const int e = ycge_launch_ansi_rgb_delta(d_rgba, d_shown, d_next, fbW, fbH, X.ansi_cw, X.ansi_ch, X.ansi_vx, X.ansi_vy, X.rgb_palette.p, X.ansi_fg, X.ansi_bg,
-                                             X.delta_gap, X.delta_tol, X.ansi_tiles.p, X.ansi_stream.p, X.ansi_stream.cap, X.delta_res.p, stream);
-    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "24-bit ANSI delta stream launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(c, hipMemcpyAsync(X.delta_res_host.p, X.delta_res.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    const uint8_t *palette = r.rgb ? X.rgb_palette.p : reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48);
+    uint8_t *out = X.ansi_stream.p;
+    const size_t cap = X.ansi_stream.cap;
+    int e;
+    if (!delta)
+        e = (r.rgb ? ycge_launch_ansi_rgb_stream : ycge_launch_ansi_stream)(d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.clear, X.ansi_tiles.p, out,
+                                                                          cap, X.ansi_res.p, stream);
+    else if (r.rgb)
+        e = ycge_launch_ansi_rgb_delta(d_plane, d_prev, d_next, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, r.tolerance, X.ansi_tiles.p, out, cap,
+                                       X.ansi_res.p, stream);
+    else
+        e = ycge_launch_ansi_delta(d_plane, d_prev, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
+    if (e != 0)
+        return c->fail(YCGE_ERR_DEVICE, "%sANSI %sstream launch failed: %s", r.rgb ? "24-bit " : "", delta ? "delta " : "", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipMemcpyAsync(X.ansi_res_host.p, X.ansi_res.p, (delta ? 4 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     return YCGE_OK;
 }
 
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs)
 {
     ChexelState &X = c->chexels;
-    if (X.ansi_rgb) {                                                 // (d_pairs: the RGBA plane)
-        { const int rc = ensure_rgb_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
-        if (X.delta_on && !X.delta_full)
-            return launch_rgb_delta(c, X, stream, d_pairs, X.delta_shown[X.delta_prev].p, X.delta_shown[1 - X.delta_prev].p, c->fbW, c->fbH);
-        return launch_rgb_stream(c, X, stream, d_pairs, c->fbW, c->fbH);
-    }
-    { const int rc = ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
-    if (X.delta_on && !X.delta_full) return launch_delta(c, X, stream, d_pairs, X.delta_pairs[X.delta_prev].p, c->fbW, c->fbH);
-    return launch_stream(c, X, stream, d_pairs, c->fbW, c->fbH);
+    { const int rc = X.ansi.rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
+    return launch(c, X, stream, X.ansi, X.delta_on && !X.delta_full, d_pairs, X.delta_held[X.delta_prev].p, X.delta_held[1 - X.delta_prev].p, c->fbW, c->fbH);
 }
 
 } // namespace ycge_host
 
 namespace {
 
-// one _ansi call: sets the request, and clears it on every way out (the SDR staging: render_frame_sync's own guard)
+// one _ansi call: sets the request, and clears it on every way out (the SDR staging: render_frame_sync's own guard).  A _delta call
+// (r.delta) decides keyframe or delta, and on every way out but commit() makes the next call a keyframe; any other call shows the terminal
+// its own stream next, so a later _delta call returns a keyframe
 struct AnsiCall {
     ycge_ctx *c;
-    AnsiCall(ycge_ctx *c_, bool rgb, int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear) : c(c_)
+    int32_t key[8];
+    bool done = false;
+    AnsiCall(ycge_ctx *c_, const AnsiRequest &r) : c(c_), key{r.cw, r.ch, r.vx, r.vy, r.fg, r.bg, c_->fbW, c_->fbH}
     {
         ChexelState &X = c->chexels;
         X.on = true; X.dst[0] = X.dst[1] = X.dst[2] = nullptr;
         X.drop_staged();
-        X.ansi_on = true; X.ansi_rgb = rgb;
-        X.ansi_cw = cw; X.ansi_ch = ch; X.ansi_vx = vx; X.ansi_vy = vy; X.ansi_fg = fg; X.ansi_bg = bg; X.ansi_clear = clear != 0;
+        X.ansi_on = true; X.ansi = r;
+        X.delta_on = r.delta;
+        if (r.delta)
+            X.delta_full = !X.delta_valid || X.delta_rgb != r.rgb || !X.delta_held[X.delta_prev].p || std::memcmp(key, X.delta_key, sizeof key) != 0 || r.clear || r.keyframe;
+        else
+            X.delta_valid = false;
     }
     ~AnsiCall()
     {
         ChexelState &X = c->chexels;
-        X.on = false; X.ansi_on = false; X.ansi_rgb = false;
+        if (!done) X.delta_valid = false;
+        X.on = false; X.ansi_on = false; X.delta_on = false; X.ansi = AnsiRequest();
         X.drop_staged();
+    }
+    // a _delta call's stream is with the caller: this frame's pairs are `prev` from now on
+    void commit()
+    {
+        ChexelState &X = c->chexels;
+        if (!X.ansi.delta) return;
+        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = X.ansi.rgb;
+        std::memcpy(X.delta_key, key, sizeof key);
+        done = true;
     }
 };
 
 // what every entry point refuses; bound: the stream's bound in the call's colour form
-int check_stream_args(ycge_ctx *c, const char *fn, bool rgb, int32_t cw, int32_t ch, int32_t fg, int32_t bg, const uint8_t *out, size_t capacity,
-                      const size_t *out_len, unsigned long long &bound)
+int check_stream_args(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t *out, size_t capacity, const size_t *out_len, unsigned long long &bound)
 {
     if (!out || !out_len) return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_stream and out_len must not be NULL", fn);
-    if (cw <= 0 || ch <= 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: console %d x %d (both must be positive)", fn, cw, ch);
-    if (fg < 0 || fg > 15 || bg < 0 || bg > 15) return c->fail(YCGE_ERR_INVALID_ARG, "%s: default colours %d, %d (ConsoleColor values 0..15)", fn, fg, bg);
-    if (!stream_bound(cw, ch, rgb, bound) || bound > kOffsetLimit)
-        return c->fail(YCGE_ERR_INVALID_ARG, "%s: the stream of a %d x %d console may reach 2^32 bytes (offsets are 32-bit)", fn, cw, ch);
+    if (r.cw <= 0 || r.ch <= 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: console %d x %d (both must be positive)", fn, r.cw, r.ch);
+    if (r.fg < 0 || r.fg > 15 || r.bg < 0 || r.bg > 15) return c->fail(YCGE_ERR_INVALID_ARG, "%s: default colours %d, %d (ConsoleColor values 0..15)", fn, r.fg, r.bg);
+    if (!stream_bound(r.cw, r.ch, r.rgb, bound) || bound > kOffsetLimit)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: the stream of a %d x %d console may reach 2^32 bytes (offsets are 32-bit)", fn, r.cw, r.ch);
     if (capacity < bound)
         return c->fail(YCGE_ERR_INVALID_ARG, "%s: capacity %zu bytes is below the stream's bound %llu (%s)", fn, capacity, bound,
-                       rgb ? "ycge_ansi_rgb_stream_bound" : "ycge_ansi_stream_bound");
+                       r.rgb ? "ycge_ansi_rgb_stream_bound" : "ycge_ansi_stream_bound");
+    if (r.delta && (r.gap < 0 || r.gap > 8)) return c->fail(YCGE_ERR_INVALID_ARG, "%s: merge_gap %d (0..8)", fn, r.gap);
+    if (r.delta && r.rgb && (r.tolerance < 0 || r.tolerance > 255)) return c->fail(YCGE_ERR_INVALID_ARG, "%s: tolerance %d (0..255)", fn, r.tolerance);
     return YCGE_OK;
 }
 
-// exactly len bytes of the device stream into `out` (staged when pageable), on c->stream, synchronously
-int copy_stream(ycge_ctx *c, ChexelState &X, uint8_t *out, size_t len)
+// behind the stream's synchronisation: the length the device wrote, the bound check, exactly that many bytes of the device stream into
+// `out` (staged when pageable; on c->stream, synchronously); then the caller's words - out_info (a _delta call's, or NULL): {keyframe,
+// changed, emitted, run starts}, the counters zero for a keyframe (full: the full stream's scan wrote the length alone)
+int deliver(ycge_ctx *c, ChexelState &X, const char *fn, bool full, unsigned long long bound, uint8_t *out, size_t *out_len, uint32_t *out_info)
 {
+    const unsigned long long *res = static_cast<const unsigned long long *>(X.ansi_res_host.p);
+    const size_t len = (size_t)res[0];
+    if (res[0] > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, res[0], bound);
     uint8_t *target = out;
     const bool staged = !host_memory_is_page_locked(out, len);
     if (staged) {
@@ -191,62 +189,7 @@ int copy_stream(ycge_ctx *c, ChexelState &X, uint8_t *out, size_t len)
     HIP_TRY(c, hipMemcpyAsync(target, X.ansi_stream.p, len, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (staged) std::memcpy(out, X.stage.p, len);
-    return YCGE_OK;
-}
-
-// one _delta call behind an AnsiCall: decides keyframe or delta, and on every way out but commit() makes the next call a keyframe
-struct DeltaCall {
-    ycge_ctx *c;
-    int32_t key[8];
-    bool done = false;
-    bool rgb;
-    DeltaCall(ycge_ctx *c_, bool rgb_, int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear, int32_t gap, int32_t tol,
-              int32_t keyframe)
-        : c(c_), key{cw, ch, vx, vy, fg, bg, c_->fbW, c_->fbH}, rgb(rgb_)
-    {
-        ChexelState &X = c->chexels;
-        X.delta_on = true; X.delta_gap = gap; X.delta_tol = tol;
-        const DevBuf<uint8_t> &held = rgb ? X.delta_shown[X.delta_prev] : X.delta_pairs[X.delta_prev];
-        X.delta_full = !X.delta_valid || X.delta_rgb != rgb || !held.p || std::memcmp(key, X.delta_key, sizeof key) != 0 || clear != 0 || keyframe != 0;
-    }
-    ~DeltaCall()
-    {
-        ChexelState &X = c->chexels;
-        X.delta_on = false;
-        if (!done) X.delta_valid = false;
-    }
-    // the stream is with the caller: this frame's pairs are `prev` from now on
-    void commit()
-    {
-        ChexelState &X = c->chexels;
-        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = rgb;
-        std::memcpy(X.delta_key, key, sizeof key);
-        done = true;
-    }
-};
-
-int check_merge_gap(ycge_ctx *c, const char *fn, int32_t gap)
-{
-    if (gap < 0 || gap > 8) return c->fail(YCGE_ERR_INVALID_ARG, "%s: merge_gap %d (0..8)", fn, gap);
-    return YCGE_OK;
-}
-
-int check_tolerance(ycge_ctx *c, const char *fn, int32_t tol)
-{
-    if (tol < 0 || tol > 255) return c->fail(YCGE_ERR_INVALID_ARG, "%s: tolerance %d (0..255)", fn, tol);
-    return YCGE_OK;
-}
-
-// behind the stream's synchronisation: the length and the counters the device wrote (full: a keyframe, whose length the full stream's scan
-// wrote), the bound check, the stream's copy; then the caller's words
-int deliver_delta(ycge_ctx *c, ChexelState &X, const char *fn, bool full, unsigned long long bound, uint8_t *out_stream, size_t *out_len, uint32_t *out_info)
-{
-    const unsigned long long *res = static_cast<const unsigned long long *>(full ? X.ansi_len_host.p : X.delta_res_host.p);
-    const unsigned long long len = res[0];
-    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
-    const int rc = copy_stream(c, X, out_stream, (size_t)len);
-    if (rc != YCGE_OK) return rc;
-    *out_len = (size_t)len;
+    *out_len = len;
     if (out_info) {
         out_info[0] = full ? 1u : 0u;
         for (int k = 1; k < 4; k++) out_info[k] = full ? 0u : (uint32_t)res[k];
@@ -254,118 +197,49 @@ int deliver_delta(ycge_ctx *c, ChexelState &X, const char *fn, bool full, unsign
     return YCGE_OK;
 }
 
-// ycge_render_frame_ansi (rgb: ycge_render_frame_ansi_rgb)
-int frame_ansi(ycge_ctx *c, const char *fn, bool rgb, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
-               int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr, ycge_frame_stats *st)
+// ycge_render_frame_ansi and its three kin.  The delta forms (the contract: include/ycge.h): a keyframe is the plain call's stream, a delta
+// writes the cells that changed since the last stream this context handed out; out_info is theirs alone
+int frame(ycge_ctx *c, const char *fn, const AnsiRequest &r, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr,
+          ycge_frame_stats *st)
 {
     if (!c) return YCGE_ERR_INVALID_ARG;
     unsigned long long bound = 0;
-    int rc = check_stream_args(c, fn, rgb, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
+    int rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
     if (rc != YCGE_OK) return rc;
     if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
     // (the exchange of the one-process RCCL form packs lean slabs when slab_albedo = 0: no albedo reaches the denoise stage)
     if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
         return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
     HIP_TRY(c, hipSetDevice(c->device));
-    AnsiCall call(c, rgb, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    AnsiCall call(c, r);
     ChexelState &X = c->chexels;
-    X.delta_valid = false;                                            // (the terminal shows this stream next: a later _delta call returns a keyframe)
-    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream, rgb);
-    if (rc != YCGE_OK) return rc;
-    rc = render_frame_sync(c, out_top_bottom_sdr, true, st);          // (its stream synchronisation: the length has arrived)
-    if (rc != YCGE_OK) return rc;
-    const unsigned long long len = *static_cast<const unsigned long long *>(X.ansi_len_host.p);
-    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
-    rc = copy_stream(c, X, out_stream, (size_t)len);
-    if (rc != YCGE_OK) return rc;
-    *out_len = (size_t)len;
-    return YCGE_OK;
-}
-
-// Video mode (ycge_video.cpp): the stream of VideoRenderer.TryFlipAndBlit's chexels for the frame the host's IFrameReader shows
-int video_ansi(ycge_ctx *c, const char *fn, bool rgb, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t console_w,
-               int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream,
-               size_t capacity, size_t *out_len, float *out_top_bottom_sdr)
-{
-    if (!c) return YCGE_ERR_INVALID_ARG;
-    unsigned long long bound = 0;
-    int rc = video_check_frame(c, fn, frame, src_w, src_h, bytes_per_pixel);
-    if (rc == YCGE_OK) rc = check_stream_args(c, fn, rgb, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
-    if (rc != YCGE_OK) return rc;
-    rc = join_async(c);
-    if (rc != YCGE_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    AnsiCall call(c, rgb, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
-    StagedSdrGuard staged(c);
-    ChexelState &X = c->chexels;
-    X.delta_valid = false;                                            // (as in ycge_render_frame_ansi)
-    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream, rgb);
-    const float *d_sdr = nullptr;
-    if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
-    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, d_sdr, false);
-    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out_top_bottom_sdr);
-    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, false);          // (the stream kernels and the length's copy)
-    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const unsigned long long len = *static_cast<const unsigned long long *>(X.ansi_len_host.p);
-    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
-    rc = copy_stream(c, X, out_stream, (size_t)len);
-    if (rc != YCGE_OK) return rc;
-    finish_staged_sdr(c);
-    *out_len = (size_t)len;
-    return YCGE_OK;
-}
-
-// The delta form of ycge_render_frame_ansi (the contract: include/ycge.h): a keyframe is that call's stream, a delta writes the cells that
-// changed since the last stream this context handed out
-// (rgb: ycge_render_frame_ansi_rgb_delta, which alone reads `tolerance`)
-int frame_ansi_delta(ycge_ctx *c, const char *fn, bool rgb, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
-                     int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance, int32_t keyframe, uint8_t *out_stream, size_t capacity,
-                     size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr, ycge_frame_stats *st)
-{
-    if (!c) return YCGE_ERR_INVALID_ARG;
-    unsigned long long bound = 0;
-    int rc = check_stream_args(c, fn, rgb, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
-    if (rc == YCGE_OK) rc = check_merge_gap(c, fn, merge_gap);
-    if (rc == YCGE_OK && rgb) rc = check_tolerance(c, fn, tolerance);
-    if (rc != YCGE_OK) return rc;
-    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
-    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
-        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
-    HIP_TRY(c, hipSetDevice(c->device));
-    AnsiCall call(c, rgb, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
-    DeltaCall delta(c, rgb, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, merge_gap, tolerance, keyframe);
-    ChexelState &X = c->chexels;
-    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream, rgb);
+    rc = ensure_ansi(c, X, r, bound, c->stream);
     if (rc != YCGE_OK) return rc;
     rc = render_frame_sync(c, out_top_bottom_sdr, true, st);          // (its stream synchronisation: the length and the counters have arrived)
     if (rc != YCGE_OK) return rc;
-    rc = deliver_delta(c, X, fn, X.delta_full, bound, out_stream, out_len, out_info);
+    rc = deliver(c, X, fn, !r.delta || X.delta_full, bound, out_stream, out_len, r.delta ? out_info : nullptr);
     if (rc != YCGE_OK) return rc;
-    delta.commit();
+    call.commit();
     return YCGE_OK;
 }
 
-// ... and of ycge_video_blit_ansi, on the same delta state: one terminal, whichever renderer the host shows on it
-int video_ansi_delta(ycge_ctx *c, const char *fn, bool rgb, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t console_w,
-                     int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
-                     int32_t tolerance, int32_t keyframe, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr)
+// Video mode (ycge_video.cpp): the stream of VideoRenderer.TryFlipAndBlit's chexels for the frame the host's IFrameReader shows; the
+// delta forms on the same delta state: one terminal, whichever renderer the host shows on it
+int video(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, uint8_t *out_stream,
+          size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr)
 {
     if (!c) return YCGE_ERR_INVALID_ARG;
     unsigned long long bound = 0;
     int rc = video_check_frame(c, fn, frame, src_w, src_h, bytes_per_pixel);
-    if (rc == YCGE_OK) rc = check_stream_args(c, fn, rgb, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
-    if (rc == YCGE_OK) rc = check_merge_gap(c, fn, merge_gap);
-    if (rc == YCGE_OK && rgb) rc = check_tolerance(c, fn, tolerance);
+    if (rc == YCGE_OK) rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
     if (rc != YCGE_OK) return rc;
     rc = join_async(c);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    AnsiCall call(c, rgb, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
-    DeltaCall delta(c, rgb, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, merge_gap, tolerance, keyframe);
+    AnsiCall call(c, r);
     StagedSdrGuard staged(c);
     ChexelState &X = c->chexels;
-    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream, rgb);
+    rc = ensure_ansi(c, X, r, bound, c->stream);
     const float *d_sdr = nullptr;
     if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
     if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, d_sdr, false);
@@ -373,10 +247,74 @@ int video_ansi_delta(ycge_ctx *c, const char *fn, bool rgb, const uint8_t *frame
     if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, false);          // (the stream kernels and the copy of what they report)
     if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    rc = deliver_delta(c, X, fn, X.delta_full, bound, out_stream, out_len, out_info);
+    rc = deliver(c, X, fn, !r.delta || X.delta_full, bound, out_stream, out_len, r.delta ? out_info : nullptr);
     if (rc != YCGE_OK) return rc;
     finish_staged_sdr(c);
-    delta.commit();
+    call.commit();
+    return YCGE_OK;
+}
+
+// The four test hooks: r's stream kernels alone on caller-given planes of the fbW x fbH framebuffer (`what` names cur in the refusal), with
+// the geometry, defaults and refusals of the frame call; on the context's device and stream.  A delta (r.delta) runs against prev; a NULL
+// prev or a clear_screen gives the keyframe.  Stateless: plane buffers of its own, the context's request and delta state untouched.
+// out_shown (24-bit delta, or NULL): the next `shown` - cur after a keyframe, otherwise cur where a covered cell was emitted and prev
+// elsewhere - with every fourth byte 255
+int test_stream(ycge_ctx *c, const char *fn, const char *what, const AnsiRequest &r, const uint8_t *prev, const uint8_t *cur, int32_t fbW, int32_t fbH,
+                uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, uint8_t *out_shown)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!cur || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (%s %p, %d x %d)", fn, what, (const void *)cur, fbW, fbH);
+    unsigned long long bound = 0;
+    int rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ChexelState &X = c->chexels;
+    rc = ensure_ansi(c, X, r, bound, c->stream);
+    if (rc != YCGE_OK) return rc;
+    const bool full = !r.delta || !prev || r.clear;
+    const size_t bytes = (r.rgb ? 8 : 2) * (size_t)fbW * fbH;
+    DevBuf<uint8_t> in, held, next;
+    HIP_TRY(c, in.alloc(bytes));
+    HIP_TRY(c, hipMemcpy(in.p, cur, bytes, hipMemcpyHostToDevice));
+    if (!full) {
+        HIP_TRY(c, held.alloc(bytes));
+        HIP_TRY(c, hipMemcpy(held.p, prev, bytes, hipMemcpyHostToDevice));
+    }
+    if (!full && r.rgb) {
+        HIP_TRY(c, next.alloc(bytes));
+        HIP_TRY(c, hipMemcpy(next.p, held.p, bytes, hipMemcpyDeviceToDevice));      // (framebuffer cells off the console keep what they held)
+    }
+    rc = launch(c, X, c->stream, r, !full, in.p, held.p, next.p, fbW, fbH);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rc = deliver(c, X, fn, full, bound, out_stream, out_len, out_info);
+    if (rc != YCGE_OK || !out_shown) return rc;
+    rc = copy_out(c, out_shown, full ? in.p : next.p, bytes);
+    if (rc != YCGE_OK) return rc;
+    for (size_t k = 3; k < bytes; k += 4) out_shown[k] = 255;
+    return YCGE_OK;
+}
+
+// a call's arguments as its request
+AnsiRequest request(bool rgb, int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear)
+{
+    AnsiRequest r;
+    r.rgb = rgb; r.cw = cw; r.ch = ch; r.vx = vx; r.vy = vy; r.fg = fg; r.bg = bg; r.clear = clear != 0;
+    return r;
+}
+
+AnsiRequest with_delta(AnsiRequest r, int32_t merge_gap, int32_t tolerance, int32_t keyframe)
+{
+    r.delta = true; r.gap = merge_gap; r.tolerance = tolerance; r.keyframe = keyframe != 0;
+    return r;
+}
+
+int bound_call(int32_t console_w, int32_t console_h, bool rgb, size_t *bytes)
+{
+    unsigned long long b = 0;
+    if (!bytes || console_w <= 0 || console_h <= 0 || !stream_bound(console_w, console_h, rgb, b)) return YCGE_ERR_INVALID_ARG;
+    *bytes = (size_t)b;
     return YCGE_OK;
 }
 
@@ -387,10 +325,7 @@ extern "C" {
 
 int ycge_ansi_stream_bound(int32_t console_w, int32_t console_h, size_t *bytes)
 try {
-    unsigned long long b = 0;
-    if (!bytes || console_w <= 0 || console_h <= 0 || !stream_bound(console_w, console_h, false, b)) return YCGE_ERR_INVALID_ARG;
-    *bytes = (size_t)b;
-    return YCGE_OK;
+    return bound_call(console_w, console_h, false, bytes);
 }
 catch (...) { return ycge_host::abi_catch(nullptr); }
 
@@ -398,8 +333,8 @@ int ycge_render_frame_ansi(ycge_ctx *c, int32_t console_w, int32_t console_h, in
                            int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr,
                            ycge_frame_stats *st)
 try {
-    return frame_ansi(c, "ycge_render_frame_ansi", false, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, out_stream, capacity,
-                      out_len, out_top_bottom_sdr, st);
+    return frame(c, "ycge_render_frame_ansi", request(false, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen), out_stream,
+                 capacity, out_len, nullptr, out_top_bottom_sdr, st);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -407,8 +342,8 @@ int ycge_video_blit_ansi(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32
                          int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
                          size_t *out_len, float *out_top_bottom_sdr)
 try {
-    return video_ansi(c, "ycge_video_blit_ansi", false, frame, src_w, src_h, bytes_per_pixel, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16,
-                      clear_screen, out_stream, capacity, out_len, out_top_bottom_sdr);
+    return video(c, "ycge_video_blit_ansi", request(false, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen), frame, src_w, src_h,
+                 bytes_per_pixel, out_stream, capacity, out_len, nullptr, out_top_bottom_sdr);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -416,8 +351,8 @@ int ycge_render_frame_ansi_delta(ycge_ctx *c, int32_t console_w, int32_t console
                                  int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t keyframe, uint8_t *out_stream, size_t capacity,
                                  size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr, ycge_frame_stats *st)
 try {
-    return frame_ansi_delta(c, "ycge_render_frame_ansi_delta", false, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, merge_gap,
-                            0, keyframe, out_stream, capacity, out_len, out_info, out_top_bottom_sdr, st);
+    const AnsiRequest r = request(false, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    return frame(c, "ycge_render_frame_ansi_delta", with_delta(r, merge_gap, 0, keyframe), out_stream, capacity, out_len, out_info, out_top_bottom_sdr, st);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -425,18 +360,16 @@ int ycge_video_blit_ansi_delta(ycge_ctx *c, const uint8_t *frame, int32_t src_w,
                                int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
                                int32_t keyframe, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr)
 try {
-    return video_ansi_delta(c, "ycge_video_blit_ansi_delta", false, frame, src_w, src_h, bytes_per_pixel, console_w, console_h, viewport_x, viewport_y, default_fg16,
-                            default_bg16, clear_screen, merge_gap, 0, keyframe, out_stream, capacity, out_len, out_info, out_top_bottom_sdr);
+    const AnsiRequest r = request(false, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    return video(c, "ycge_video_blit_ansi_delta", with_delta(r, merge_gap, 0, keyframe), frame, src_w, src_h, bytes_per_pixel, out_stream, capacity, out_len, out_info,
+                 out_top_bottom_sdr);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
 // The 24-bit colour forms (the contract: include/ycge.h): the same four calls on sRGB8 triples, the delta with a tolerance
 int ycge_ansi_rgb_stream_bound(int32_t console_w, int32_t console_h, size_t *bytes)
 try {
-    unsigned long long b = 0;
-    if (!bytes || console_w <= 0 || console_h <= 0 || !stream_bound(console_w, console_h, true, b)) return YCGE_ERR_INVALID_ARG;
-    *bytes = (size_t)b;
-    return YCGE_OK;
+    return bound_call(console_w, console_h, true, bytes);
 }
 catch (...) { return ycge_host::abi_catch(nullptr); }
 
@@ -444,8 +377,8 @@ int ycge_render_frame_ansi_rgb(ycge_ctx *c, int32_t console_w, int32_t console_h
                                int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr,
                                ycge_frame_stats *st)
 try {
-    return frame_ansi(c, "ycge_render_frame_ansi_rgb", true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, out_stream,
-                      capacity, out_len, out_top_bottom_sdr, st);
+    return frame(c, "ycge_render_frame_ansi_rgb", request(true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen), out_stream,
+                 capacity, out_len, nullptr, out_top_bottom_sdr, st);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -453,8 +386,8 @@ int ycge_video_blit_ansi_rgb(ycge_ctx *c, const uint8_t *frame, int32_t src_w, i
                              int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream,
                              size_t capacity, size_t *out_len, float *out_top_bottom_sdr)
 try {
-    return video_ansi(c, "ycge_video_blit_ansi_rgb", true, frame, src_w, src_h, bytes_per_pixel, console_w, console_h, viewport_x, viewport_y, default_fg16,
-                      default_bg16, clear_screen, out_stream, capacity, out_len, out_top_bottom_sdr);
+    return video(c, "ycge_video_blit_ansi_rgb", request(true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen), frame, src_w,
+                 src_h, bytes_per_pixel, out_stream, capacity, out_len, nullptr, out_top_bottom_sdr);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -462,8 +395,8 @@ int ycge_render_frame_ansi_rgb_delta(ycge_ctx *c, int32_t console_w, int32_t con
                                      int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance, int32_t keyframe, uint8_t *out_stream,
                                      size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr, ycge_frame_stats *st)
 try {
-    return frame_ansi_delta(c, "ycge_render_frame_ansi_rgb_delta", true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen,
-                            merge_gap, tolerance, keyframe, out_stream, capacity, out_len, out_info, out_top_bottom_sdr, st);
+    const AnsiRequest r = request(true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    return frame(c, "ycge_render_frame_ansi_rgb_delta", with_delta(r, merge_gap, tolerance, keyframe), out_stream, capacity, out_len, out_info, out_top_bottom_sdr, st);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -472,156 +405,54 @@ int ycge_video_blit_ansi_rgb_delta(ycge_ctx *c, const uint8_t *frame, int32_t sr
                                    int32_t tolerance, int32_t keyframe, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
                                    float *out_top_bottom_sdr)
 try {
-    return video_ansi_delta(c, "ycge_video_blit_ansi_rgb_delta", true, frame, src_w, src_h, bytes_per_pixel, console_w, console_h, viewport_x, viewport_y,
-                            default_fg16, default_bg16, clear_screen, merge_gap, tolerance, keyframe, out_stream, capacity, out_len, out_info, out_top_bottom_sdr);
+    const AnsiRequest r = request(true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    return video(c, "ycge_video_blit_ansi_rgb_delta", with_delta(r, merge_gap, tolerance, keyframe), frame, src_w, src_h, bytes_per_pixel, out_stream, capacity, out_len,
+                 out_info, out_top_bottom_sdr);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
 // test hook: the stream kernels alone on caller-given ANSI pairs (fbW x fbH {fg, bg}, any values 0..255), with the geometry, defaults and
-// refusals of ycge_render_frame_ansi; on the context's device and stream, with a pairs buffer of its own
+// refusals of ycge_render_frame_ansi (test_stream above)
 int ycge_test_ansi_stream(ycge_ctx *c, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,
                           int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
                           size_t *out_len)
 try {
-    if (!c) return YCGE_ERR_INVALID_ARG;
-    static const char fn[] = "ycge_test_ansi_stream";
-    if (!pairs || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
-        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (pairs %p, %d x %d)", fn, (const void *)pairs, fbW, fbH);
-    unsigned long long bound = 0;
-    int rc = check_stream_args(c, fn, false, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
-    if (rc != YCGE_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ChexelState &X = c->chexels;
-    X.ansi_cw = console_w; X.ansi_ch = console_h; X.ansi_vx = viewport_x; X.ansi_vy = viewport_y;
-    X.ansi_fg = default_fg16; X.ansi_bg = default_bg16; X.ansi_clear = clear_screen != 0;
-    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
-    if (rc != YCGE_OK) return rc;
-    DevBuf<uint8_t> in;
-    HIP_TRY(c, in.alloc(2 * (size_t)fbW * fbH));
-    HIP_TRY(c, hipMemcpy(in.p, pairs, 2 * (size_t)fbW * fbH, hipMemcpyHostToDevice));
-    rc = launch_stream(c, X, c->stream, in.p, fbW, fbH);
-    if (rc != YCGE_OK) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const unsigned long long len = *static_cast<const unsigned long long *>(X.ansi_len_host.p);
-    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
-    rc = copy_stream(c, X, out_stream, (size_t)len);
-    if (rc != YCGE_OK) return rc;
-    *out_len = (size_t)len;
-    return YCGE_OK;
+    const AnsiRequest r = request(false, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    return test_stream(c, "ycge_test_ansi_stream", "pairs", r, nullptr, pairs, fbW, fbH, out_stream, capacity, out_len, nullptr, nullptr);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
 // test hook: the delta kernels alone on caller-given pairs, prev_pairs and pairs both fbW x fbH {fg, bg}; a NULL prev_pairs or a
-// clear_screen gives the keyframe (ycge_test_ansi_stream's bytes).  Stateless: pair buffers of its own, the context's delta state untouched.
+// clear_screen gives the keyframe (ycge_test_ansi_stream's bytes)
 int ycge_test_ansi_delta(ycge_ctx *c, const uint8_t *prev_pairs, const uint8_t *pairs, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h,
                          int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
                          uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info)
 try {
-    if (!c) return YCGE_ERR_INVALID_ARG;
-    static const char fn[] = "ycge_test_ansi_delta";
-    if (!pairs || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
-        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (pairs %p, %d x %d)", fn, (const void *)pairs, fbW, fbH);
-    unsigned long long bound = 0;
-    int rc = check_stream_args(c, fn, false, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
-    if (rc == YCGE_OK) rc = check_merge_gap(c, fn, merge_gap);
-    if (rc != YCGE_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ChexelState &X = c->chexels;
-    X.ansi_cw = console_w; X.ansi_ch = console_h; X.ansi_vx = viewport_x; X.ansi_vy = viewport_y;
-    X.ansi_fg = default_fg16; X.ansi_bg = default_bg16; X.ansi_clear = clear_screen != 0;
-    X.delta_gap = merge_gap;
-    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream);
-    if (rc != YCGE_OK) return rc;
-    const bool full = !prev_pairs || clear_screen != 0;
-    const size_t bytes = 2 * (size_t)fbW * fbH;
-    DevBuf<uint8_t> in, prev;
-    HIP_TRY(c, in.alloc(bytes));
-    HIP_TRY(c, hipMemcpy(in.p, pairs, bytes, hipMemcpyHostToDevice));
-    if (!full) {
-        HIP_TRY(c, prev.alloc(bytes));
-        HIP_TRY(c, hipMemcpy(prev.p, prev_pairs, bytes, hipMemcpyHostToDevice));
-    }
-    rc = full ? launch_stream(c, X, c->stream, in.p, fbW, fbH) : launch_delta(c, X, c->stream, in.p, prev.p, fbW, fbH);
-    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return deliver_delta(c, X, fn, full, bound, out_stream, out_len, out_info);
+    const AnsiRequest r = request(false, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    return test_stream(c, "ycge_test_ansi_delta", "pairs", with_delta(r, merge_gap, 0, 0), prev_pairs, pairs, fbW, fbH, out_stream, capacity, out_len, out_info, nullptr);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
 // test hook: the 24-bit stream kernels alone on a caller-given RGBA plane (fbW x 2 fbH RGBA8, row 2 cy the top half-cell, the fourth byte
-// ignored), with the geometry, defaults and refusals of ycge_render_frame_ansi_rgb; a plane buffer of its own
+// ignored), with the geometry, defaults and refusals of ycge_render_frame_ansi_rgb
 int ycge_test_ansi_rgb_stream(ycge_ctx *c, const uint8_t *rgba, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x,
                               int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream, size_t capacity,
                               size_t *out_len)
 try {
-    if (!c) return YCGE_ERR_INVALID_ARG;
-    static const char fn[] = "ycge_test_ansi_rgb_stream";
-    if (!rgba || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
-        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (rgba %p, %d x %d)", fn, (const void *)rgba, fbW, fbH);
-    unsigned long long bound = 0;
-    int rc = check_stream_args(c, fn, true, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
-    if (rc != YCGE_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ChexelState &X = c->chexels;
-    X.ansi_cw = console_w; X.ansi_ch = console_h; X.ansi_vx = viewport_x; X.ansi_vy = viewport_y;
-    X.ansi_fg = default_fg16; X.ansi_bg = default_bg16; X.ansi_clear = clear_screen != 0;
-    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream, true);
-    if (rc != YCGE_OK) return rc;
-    const size_t bytes = 8 * (size_t)fbW * fbH;
-    DevBuf<uint8_t> in;
-    HIP_TRY(c, in.alloc(bytes));
-    HIP_TRY(c, hipMemcpy(in.p, rgba, bytes, hipMemcpyHostToDevice));
-    rc = launch_rgb_stream(c, X, c->stream, in.p, fbW, fbH);
-    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return deliver_delta(c, X, fn, true, bound, out_stream, out_len, nullptr);
+    const AnsiRequest r = request(true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    return test_stream(c, "ycge_test_ansi_rgb_stream", "rgba", r, nullptr, rgba, fbW, fbH, out_stream, capacity, out_len, nullptr, nullptr);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
 // test hook: the 24-bit delta kernels alone on caller-given planes, shown and cur both fbW x 2 fbH RGBA8 (the fourth byte ignored); a NULL
-// shown or a clear_screen gives the keyframe (ycge_test_ansi_rgb_stream's bytes).  out_shown (or NULL): the next `shown` - cur after a
-// keyframe, otherwise cur where a covered cell was emitted and shown elsewhere - with every fourth byte 255.  Stateless: planes of its own,
-// the context's delta state untouched.
+// shown or a clear_screen gives the keyframe (ycge_test_ansi_rgb_stream's bytes).  out_shown (or NULL): the next `shown`
 int ycge_test_ansi_rgb_delta(ycge_ctx *c, const uint8_t *shown, const uint8_t *cur, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h,
                              int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
                              int32_t tolerance, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, uint8_t *out_shown)
 try {
-    if (!c) return YCGE_ERR_INVALID_ARG;
-    static const char fn[] = "ycge_test_ansi_rgb_delta";
-    if (!cur || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
-        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (cur %p, %d x %d)", fn, (const void *)cur, fbW, fbH);
-    unsigned long long bound = 0;
-    int rc = check_stream_args(c, fn, true, console_w, console_h, default_fg16, default_bg16, out_stream, capacity, out_len, bound);
-    if (rc == YCGE_OK) rc = check_merge_gap(c, fn, merge_gap);
-    if (rc == YCGE_OK) rc = check_tolerance(c, fn, tolerance);
-    if (rc != YCGE_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ChexelState &X = c->chexels;
-    X.ansi_cw = console_w; X.ansi_ch = console_h; X.ansi_vx = viewport_x; X.ansi_vy = viewport_y;
-    X.ansi_fg = default_fg16; X.ansi_bg = default_bg16; X.ansi_clear = clear_screen != 0;
-    X.delta_gap = merge_gap; X.delta_tol = tolerance;
-    rc = ensure_ansi(c, X, console_w, console_h, bound, c->stream, true);
-    if (rc != YCGE_OK) return rc;
-    const bool full = !shown || clear_screen != 0;
-    const size_t bytes = 8 * (size_t)fbW * fbH;
-    DevBuf<uint8_t> in, prev, next;
-    HIP_TRY(c, in.alloc(bytes));
-    HIP_TRY(c, hipMemcpy(in.p, cur, bytes, hipMemcpyHostToDevice));
-    if (!full) {
-        HIP_TRY(c, prev.alloc(bytes));
-        HIP_TRY(c, next.alloc(bytes));
-        HIP_TRY(c, hipMemcpy(prev.p, shown, bytes, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(next.p, prev.p, bytes, hipMemcpyDeviceToDevice));      // (framebuffer cells off the console keep what they held)
-    }
-    rc = full ? launch_rgb_stream(c, X, c->stream, in.p, fbW, fbH) : launch_rgb_delta(c, X, c->stream, in.p, prev.p, next.p, fbW, fbH);
-    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    rc = deliver_delta(c, X, fn, full, bound, out_stream, out_len, out_info);
-    if (rc != YCGE_OK || !out_shown) return rc;
-    rc = copy_out(c, out_shown, full ? in.p : next.p, bytes);
-    if (rc != YCGE_OK) return rc;
-    for (size_t k = 3; k < bytes; k += 4) out_shown[k] = 255;
-    return YCGE_OK;
+    const AnsiRequest r = request(true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    return test_stream(c, "ycge_test_ansi_rgb_delta", "cur", with_delta(r, merge_gap, tolerance, 0), shown, cur, fbW, fbH, out_stream, capacity, out_len, out_info,
+                       out_shown);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

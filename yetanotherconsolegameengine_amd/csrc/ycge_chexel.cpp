@@ -99,17 +99,14 @@ int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool seco
     DevBuf<uint8_t> &out = X->out[second ? 1 : 0];
     if (out.cap < L.total) HIP_TRY(c, out.alloc(L.total));
     if (X->dst[1] || X->dst[2] || ansi) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
-    const bool rgb = ansi && X->ansi_rgb;                                                // (a 24-bit stream: the RGBA plane stays on the device instead)
+    const bool rgb = ansi && X->ansi.rgb;                                                // (a 24-bit stream: the RGBA plane stays on the device instead)
     uint8_t *pairs = out.p + L.ansi, *rgba = out.p + L.rgba;
-    if (X->delta_on && !rgb) {                                                           // (a _delta call: the pairs go where the next call finds them)
-        DevBuf<uint8_t> &next = X->delta_pairs[1 - X->delta_prev];
-        if (next.cap < 2 * L.n) HIP_TRY(c, next.alloc(2 * L.n));
-        pairs = next.p;
-    }
-    if (X->delta_on && rgb) {                                                            // (a keyframe's plane is the next `shown`; a delta's write kernel fills it)
-        DevBuf<uint8_t> &next = X->delta_shown[1 - X->delta_prev];
-        if (next.cap < 8 * L.n) HIP_TRY(c, next.alloc(8 * L.n));
-        if (X->delta_full) rgba = next.p;
+    if (X->delta_on) {                                                                   // (a _delta call: the pairs go where the next call finds them;
+        DevBuf<uint8_t> &next = X->delta_held[1 - X->delta_prev];                        //  24-bit: a keyframe's plane is the next `shown`, a delta's write kernel fills it)
+        const size_t bytes = (rgb ? 8 : 2) * L.n;
+        if (next.cap < bytes) HIP_TRY(c, next.alloc(bytes));
+        if (!rgb) pairs = next.p;
+        else if (X->delta_full) rgba = next.p;
     }
     const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, X->dst[0] ? out.p + L.c16 : nullptr, X->dst[1] || (ansi && !rgb) ? pairs : nullptr,
                                       X->dst[2] || rgb ? rgba : nullptr, c->compute_units, stream);
@@ -137,11 +134,10 @@ int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second)
         }
         HIP_TRY(c, hipMemcpyAsync(target, src + off[k], bytes[k], hipMemcpyDeviceToHost, stream));
     }
-    if (X->ansi_on && X->ansi_rgb)                                         // (ycge_ansi.cpp: the 24-bit stream from the RGBA plane, where chexel_encode put it)
-        return ansi_enqueue(c, stream, X->delta_on && X->delta_full ? X->delta_shown[1 - X->delta_prev].p : src + L.rgba);
-    if (X->ansi_on)                                                        // (... the escape stream from the pairs, and its length)
-        return ansi_enqueue(c, stream, X->delta_on ? X->delta_pairs[1 - X->delta_prev].p : src + L.ansi);
-    return YCGE_OK;
+    if (!X->ansi_on) return YCGE_OK;
+    // (ycge_ansi.cpp: the escape stream and its length from the pairs - 24-bit: the RGBA plane - where chexel_encode put them)
+    const bool held = X->delta_on && (X->delta_full || !X->ansi.rgb);
+    return ansi_enqueue(c, stream, held ? X->delta_held[1 - X->delta_prev].p : src + (X->ansi.rgb ? L.rgba : L.ansi));
 }
 
 } // namespace ycge_host

@@ -382,6 +382,15 @@ struct QueryState {
     uint32_t lanes[4] = {0, 0, 0, 0};  // resident lanes of k_query<has_grid, occluded>
     PinnedBuf in_stage, out_stage;
 };
+// one ANSI stream call (ycge_ansi.cpp): the colour form, the console, the viewport, the default colours, the clear-screen prefix; delta: a
+// _delta call, which alone reads gap, tolerance (24-bit colour only) and keyframe
+struct AnsiRequest {
+    bool rgb = false;
+    int32_t cw = 0, ch = 0, vx = 0, vy = 0, fg = 0, bg = 0;
+    bool clear = false, delta = false;
+    int32_t gap = 0, tolerance = 0;
+    bool keyframe = false;
+};
 // what the chexel calls of one context hold (ycge_chexel.cpp, ycge_ansi.cpp): filled by the first call
 struct ChexelState {
     bool on = false;                                   // a _chexels or _ansi call is in progress
@@ -392,35 +401,26 @@ struct ChexelState {
     uint8_t *staged_dst[3] = {nullptr, nullptr, nullptr};
     size_t staged_off[3] = {0, 0, 0}, staged_bytes[3] = {0, 0, 0};
     void drop_staged() { for (int k = 0; k < 3; k++) { staged_dst[k] = nullptr; staged_bytes[k] = 0; } }
-    // ycge_render_frame_ansi: the request of the call at hand (the encode writes the ANSI pairs on the device only) and the stream's buffers
+    // the ANSI stream calls (ycge_ansi.cpp; kernels: ycge_ansi.hip, ycge_ansi_rgb.hip): the request of the call at hand - its encode keeps the
+    // ANSI pairs (24-bit colour: the RGBA plane) on the device only - and the stream's buffers
     bool ansi_on = false;
-    int32_t ansi_cw = 0, ansi_ch = 0, ansi_vx = 0, ansi_vy = 0, ansi_fg = 0, ansi_bg = 0, ansi_clear = 0;
+    AnsiRequest ansi;
     DevBuf<uint8_t> ansi_stream;                       // the stream (its bound)
-    DevBuf<uint32_t> ansi_tiles;                       // per-tile byte counts, then offsets
-    DevBuf<unsigned long long> ansi_len;               // the stream's length, as the scan wrote it
+    DevBuf<uint32_t> ansi_tiles;                       // per-tile byte counts, then offsets (a delta: four words a tile)
+    DevBuf<unsigned long long> ansi_res;               // {length, changed, emitted, run starts}, as the scan wrote them (the full stream: the length alone)
     DevBuf<float> ansi_palette;                        // the 16 palette colours as 8 SDR chexels, then their 16 ANSI indices (bytes at float 48)
     bool ansi_palette_ready = false;
-    PinnedBuf ansi_len_host;                           // page-locked word the length is copied to
-    // ycge_render_frame_ansi_delta / ycge_video_blit_ansi_delta: the encode of such a call writes its pairs into delta_pairs[1 - delta_prev];
-    // delta_pairs[delta_prev] holds those of the last stream handed out while delta_valid, for the geometry delta_key.  A successful call
-    // flips delta_prev - nothing is copied.  Whatever shows the terminal something else (a plain _ansi call, ycge_resize, a failure) clears delta_valid.
+    PinnedBuf ansi_res_host;                           // page-locked words ansi_res is copied to
+    // The _delta calls: delta_held[delta_prev] holds what the last stream handed out left on the terminal while delta_valid, for the geometry
+    // delta_key and the colour form delta_rgb - the frame's pairs, or in 24-bit colour the plane the terminal displays; a call of the other
+    // form finds no valid state.  The encode of a 256-colour _delta call writes its pairs into delta_held[1 - delta_prev]; in 24-bit colour a
+    // keyframe's encode writes the plane there and a delta's write kernel writes emitted ? cur : shown.  A successful call flips delta_prev -
+    // nothing is copied.  Whatever shows the terminal something else (a plain _ansi call, ycge_resize, a failure) clears delta_valid.
     bool delta_on = false, delta_full = false;         // a _delta call is in progress; it returns a keyframe (the full stream's kernels)
-    int32_t delta_gap = 0;
-    DevBuf<uint8_t> delta_pairs[2];
+    DevBuf<uint8_t> delta_held[2];
     int delta_prev = 0;
-    bool delta_valid = false;
+    bool delta_valid = false, delta_rgb = false;
     int32_t delta_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // {cw, ch, vx, vy, dfg, dbg, fbW, fbH}
-    DevBuf<unsigned long long> delta_res;              // {length, changed, emitted, run starts}, as the delta scan wrote them
-    PinnedBuf delta_res_host;
-    // the 24-bit colour forms (ycge_render_frame_ansi_rgb and its kin; kernels: ycge_ansi_rgb.hip): ansi_rgb marks the call at hand as one.
-    // Its encode keeps the RGBA plane on the device.  The delta state above is the one terminal's, whichever family drew it: delta_rgb says
-    // which family delta_valid speaks of, and a call of the other family finds no valid state.  delta_shown[delta_prev] is what the terminal
-    // displays (the plane's layout); a keyframe's encode writes the plane into delta_shown[1 - delta_prev], a delta's write kernel writes
-    // emitted ? cur : shown there, and a successful call flips delta_prev.
-    bool ansi_rgb = false;
-    int32_t delta_tol = 0;
-    bool delta_rgb = false;
-    DevBuf<uint8_t> delta_shown[2];
     DevBuf<uint8_t> rgb_palette;                       // RGB8 of the 16 palette colours: the encoder's 8 x 2 RGBA plane of ansi_palette's chexels
     bool rgb_palette_ready = false;
 };

@@ -148,8 +148,7 @@ int set_geometry(ycge_ctx *c, int fbw, int fbh, int ss)
     c->last_cam[0] = c->last_cam[1] = c->last_cam[2] = NAN; c->last_yaw = c->last_pitch = NAN;
     c->den_a.release(); c->den_b.release(); c->unit_n.release(); c->exp_terms.release(); c->exp_scratch.release(); c->d_sdr.release(); c->d_sdr2.release(); c->atrous_statw.release();     // spatialA / spatialB, :129-130
     c->chexels.out[0].release(); c->chexels.out[1].release(); c->chexels.ansi_stream.release(); c->chexels.ansi_tiles.release();      // (the encoded chexels and their stream: sized for the console)
-    c->chexels.delta_pairs[0].release(); c->chexels.delta_pairs[1].release(); c->chexels.delta_valid = false;      // (the next delta call returns a keyframe)
-    c->chexels.delta_shown[0].release(); c->chexels.delta_shown[1].release();                                      // (of either colour form)
+    c->chexels.delta_held[0].release(); c->chexels.delta_held[1].release(); c->chexels.delta_valid = false;      // (the next delta call, of either colour form, returns a keyframe)
     c->denoised = nullptr;
     c->alt_post.release();
     c->wave_prof.release();                                     // sized for the tile grid

@@ -553,21 +553,46 @@ class RaytraceRenderer:
     @staticmethod
     def ansi_stream_bound(console_width: int, console_height: int, lib=None) -> int:
         """The most bytes the ANSI stream of a console_width x console_height console can take (ycge_ansi_stream_bound; no GPU needed)."""
+        return RaytraceRenderer._ansi_bound(console_width, console_height, False, lib)
+
+    @staticmethod
+    def _ansi_bound(console_width: int, console_height: int, rgb: bool, lib=None) -> int:
+        """ycge_ansi_stream_bound, or with rgb ycge_ansi_rgb_stream_bound"""
         L = lib if lib is not None else abi.load_library()
         n = C.c_size_t(0)
-        rc = L.ycge_ansi_stream_bound(int(console_width), int(console_height), C.byref(n))
+        rc = (L.ycge_ansi_rgb_stream_bound if rgb else L.ycge_ansi_stream_bound)(int(console_width), int(console_height), C.byref(n))
         if rc != 0:
-            raise abi.YcgeError(rc, f"no ANSI stream bound for a {console_width} x {console_height} console")
+            raise abi.YcgeError(rc, f"no {'24-bit ' if rgb else ''}ANSI stream bound for a {console_width} x {console_height} console")
         return n.value
 
-    def _ansi_out(self, console_width: int, console_height: int):
-        """the renderer's growable page-locked stream buffer, at least the bound of this console"""
-        bound = self.ansi_stream_bound(console_width, console_height, self.L)
+    def _ansi_out(self, console_width: int, console_height: int, rgb: bool = False):
+        """the renderer's growable page-locked stream buffer, at least the bound of this console in the colour form asked"""
+        bound = self._ansi_bound(console_width, console_height, rgb, self.L)
         buf = self.__dict__.get("_ansi_buf")
         if buf is None or buf[0].size < bound:
             self.__dict__.pop("_ansi_buf", None)
             buf = self.__dict__["_ansi_buf"] = self._page_locked_zeros((bound,), np.uint8)
         return buf[0]
+
+    def _ansi_call(self, export, head, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr, rgb=False, delta=None, stats=True):
+        """One stream call on this context: export(ctx, *head, the console, viewport, defaults and clear_screen, *delta, the stream buffer,
+        its capacity and length[, info], the SDR array or NULL[, the frame statistics]).  head: a video call's frame arguments; delta: a
+        _delta call's (merge_gap[, tolerance], keyframe), or None.  A plain call returns bytes or (bytes, SDR array), a _delta call
+        (bytes, info) or (bytes, info, SDR array)."""
+        out = self._ansi_out(console_width, console_height, rgb)
+        n = C.c_size_t(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        console = (int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg), int(default_bg), int(bool(clear_screen)))
+        buf = (out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, C.byref(n))
+        tail = (s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None,) + ((C.byref(self.stats),) if stats else ())
+        if delta is None:
+            self._check(export(self.ctx, *head, *console, *buf, *tail))
+            stream = out[:n.value].tobytes()
+            return (stream, s) if sdr else stream
+        info = (C.c_uint32 * 4)()
+        self._check(export(self.ctx, *head, *console, *(int(v) for v in delta), *buf, info, *tail))
+        stream, info = out[:n.value].tobytes(), dict(zip(self.DELTA_INFO, (int(v) for v in info)))
+        return (stream, info, s) if sdr else (stream, info)
 
     def TryFlipAndBlitAnsi(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                            clear_screen: bool = False, sdr: bool = False):
@@ -575,14 +600,7 @@ class RaytraceRenderer:
         `viewport`, built on the device - `bytes`, or (bytes, SDR array) with sdr=True.  The SDR and the frame state are those of
         TryFlipAndBlit(want_sdr=True); the frame statistics go to self.stats.  The stream is read back into one growable page-locked
         buffer of the renderer, freed by close()."""
-        out = self._ansi_out(console_width, console_height)
-        n = C.c_size_t(0)
-        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
-        self._check(self.L.ycge_render_frame_ansi(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
-                                                  int(default_bg), int(bool(clear_screen)), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size,
-                                                  C.byref(n), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
-        stream = out[:n.value].tobytes()
-        return (stream, s) if sdr else stream
+        return self._ansi_call(self.L.ycge_render_frame_ansi, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr)
 
     DELTA_INFO = ("keyframe", "changed", "emitted", "runs")
 
@@ -592,63 +610,28 @@ class RaytraceRenderer:
         only the cells that changed, or the whole stream of TryFlipAndBlitAnsi when a keyframe is due (the first call, another
         geometry, clear_screen, keyframe, after Resize or a plain TryFlipAndBlitAnsi).  Returns (bytes, info) or (bytes, info, SDR
         array) with sdr=True; info = {"keyframe", "changed", "emitted", "runs"}.  The frame state is TryFlipAndBlit's."""
-        out = self._ansi_out(console_width, console_height)
-        n, info = C.c_size_t(0), (C.c_uint32 * 4)()
-        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
-        self._check(self.L.ycge_render_frame_ansi_delta(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
-                                                        int(default_bg), int(bool(clear_screen)), int(merge_gap), int(bool(keyframe)),
-                                                        out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, C.byref(n), info,
-                                                        s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
-        stream, info = out[:n.value].tobytes(), dict(zip(self.DELTA_INFO, (int(v) for v in info)))
-        return (stream, info, s) if sdr else (stream, info)
+        return self._ansi_call(self.L.ycge_render_frame_ansi_delta, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
+                               delta=(merge_gap, bool(keyframe)))
 
     # ---------------------------------------------------------------- the 24-bit colour forms (ycge_render_frame_ansi_rgb / _rgb_delta)
     @staticmethod
     def ansi_rgb_stream_bound(console_width: int, console_height: int, lib=None) -> int:
         """The most bytes a 24-bit colour stream of a console_width x console_height console can take (ycge_ansi_rgb_stream_bound; no GPU needed)."""
-        L = lib if lib is not None else abi.load_library()
-        n = C.c_size_t(0)
-        rc = L.ycge_ansi_rgb_stream_bound(int(console_width), int(console_height), C.byref(n))
-        if rc != 0:
-            raise abi.YcgeError(rc, f"no 24-bit ANSI stream bound for a {console_width} x {console_height} console")
-        return n.value
-
-    def _ansi_rgb_out(self, console_width: int, console_height: int):
-        """the renderer's growable page-locked stream buffer (_ansi_out's), at least the 24-bit bound of this console"""
-        bound = self.ansi_rgb_stream_bound(console_width, console_height, self.L)
-        buf = self.__dict__.get("_ansi_buf")
-        if buf is None or buf[0].size < bound:
-            self.__dict__.pop("_ansi_buf", None)
-            buf = self.__dict__["_ansi_buf"] = self._page_locked_zeros((bound,), np.uint8)
-        return buf[0]
+        return RaytraceRenderer._ansi_bound(console_width, console_height, True, lib)
 
     def TryFlipAndBlitAnsiRgb(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                               clear_screen: bool = False, sdr: bool = False):
         """TryFlipAndBlitAnsi in 24-bit colour (ycge_render_frame_ansi_rgb): the same walk with ESC[38;2;R;G;Bm / ESC[48;2;R;G;Bm of the
         sRGB8 triples TryFlipAndBlit(rgba=True) gives - `bytes`, or (bytes, SDR array) with sdr=True."""
-        out = self._ansi_rgb_out(console_width, console_height)
-        n = C.c_size_t(0)
-        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
-        self._check(self.L.ycge_render_frame_ansi_rgb(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
-                                                      int(default_bg), int(bool(clear_screen)), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size,
-                                                      C.byref(n), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
-        stream = out[:n.value].tobytes()
-        return (stream, s) if sdr else stream
+        return self._ansi_call(self.L.ycge_render_frame_ansi_rgb, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr, rgb=True)
 
     def TryFlipAndBlitAnsiRgbDelta(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                                    clear_screen: bool = False, merge_gap: int = 3, tolerance: int = 0, keyframe: bool = False, sdr: bool = False):
         """TryFlipAndBlitAnsiDelta in 24-bit colour (ycge_render_frame_ansi_rgb_delta): a cell is rewritten when a channel is more than
         `tolerance` (0..255; 0 = exact) away from what the terminal shows for it.  One terminal per context: a stream of the other colour
         form makes the next call a keyframe.  Returns (bytes, info) or (bytes, info, SDR array) with sdr=True."""
-        out = self._ansi_rgb_out(console_width, console_height)
-        n, info = C.c_size_t(0), (C.c_uint32 * 4)()
-        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
-        self._check(self.L.ycge_render_frame_ansi_rgb_delta(self.ctx, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]),
-                                                            int(default_fg), int(default_bg), int(bool(clear_screen)), int(merge_gap), int(tolerance),
-                                                            int(bool(keyframe)), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, C.byref(n), info,
-                                                            s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
-        stream, info = out[:n.value].tobytes(), dict(zip(self.DELTA_INFO, (int(v) for v in info)))
-        return (stream, info, s) if sdr else (stream, info)
+        return self._ansi_call(self.L.ycge_render_frame_ansi_rgb_delta, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
+                               rgb=True, delta=(merge_gap, tolerance, bool(keyframe)))
 
     def Wait(self):
         self._check(self.L.ycge_wait(self.ctx))
@@ -855,66 +838,35 @@ class VideoRenderer:
         self._r._check(self.L.ycge_video_blit(self.ctx, ptr, w, h, bpp, *RaytraceRenderer._chexel_pointers(out)))
         return out
 
+    def _ansi_call(self, export, frame, *args, **kwargs):
+        """RaytraceRenderer._ansi_call on this context with `frame` ahead of the console: a video call carries no frame statistics"""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        return self._r._ansi_call(export, (ptr, w, h, bpp), *args, stats=False, **kwargs)
+
     def TryFlipAndBlitAnsi(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                            clear_screen: bool = False, sdr: bool = False):
         """The bytes ANSITerminalRenderer.Render() writes for a console over this framebuffer showing `frame` (ycge_video_blit_ansi):
         `bytes`, or (bytes, SDR array) with sdr=True.  The stream buffer is the RaytraceRenderer's (page-locked, growable)."""
-        f, ptr, w, h, bpp = self._frame_args(frame)
-        r = self._r
-        o = r._ansi_out(console_width, console_height)
-        n = C.c_size_t(0)
-        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
-        r._check(self.L.ycge_video_blit_ansi(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg),
-                                             int(default_bg), int(bool(clear_screen)), o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size, C.byref(n),
-                                             s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
-        stream = o[:n.value].tobytes()
-        return (stream, s) if sdr else stream
+        return self._ansi_call(self.L.ycge_video_blit_ansi, frame, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr)
 
     def TryFlipAndBlitAnsiDelta(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                                 clear_screen: bool = False, merge_gap: int = 3, keyframe: bool = False, sdr: bool = False):
         """The delta form of TryFlipAndBlitAnsi (ycge_video_blit_ansi_delta), on the delta state this context shares with
         RaytraceRenderer.TryFlipAndBlitAnsiDelta: (bytes, info) or (bytes, info, SDR array) with sdr=True."""
-        f, ptr, w, h, bpp = self._frame_args(frame)
-        r = self._r
-        o = r._ansi_out(console_width, console_height)
-        n, info = C.c_size_t(0), (C.c_uint32 * 4)()
-        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
-        r._check(self.L.ycge_video_blit_ansi_delta(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]),
-                                                   int(default_fg), int(default_bg), int(bool(clear_screen)), int(merge_gap), int(bool(keyframe)),
-                                                   o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size, C.byref(n), info,
-                                                   s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
-        stream, info = o[:n.value].tobytes(), dict(zip(RaytraceRenderer.DELTA_INFO, (int(v) for v in info)))
-        return (stream, info, s) if sdr else (stream, info)
+        return self._ansi_call(self.L.ycge_video_blit_ansi_delta, frame, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
+                               delta=(merge_gap, bool(keyframe)))
 
     def TryFlipAndBlitAnsiRgb(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                               clear_screen: bool = False, sdr: bool = False):
         """TryFlipAndBlitAnsi in 24-bit colour (ycge_video_blit_ansi_rgb): `bytes`, or (bytes, SDR array) with sdr=True."""
-        f, ptr, w, h, bpp = self._frame_args(frame)
-        r = self._r
-        o = r._ansi_rgb_out(console_width, console_height)
-        n = C.c_size_t(0)
-        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
-        r._check(self.L.ycge_video_blit_ansi_rgb(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]),
-                                                 int(default_fg), int(default_bg), int(bool(clear_screen)), o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size,
-                                                 C.byref(n), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
-        stream = o[:n.value].tobytes()
-        return (stream, s) if sdr else stream
+        return self._ansi_call(self.L.ycge_video_blit_ansi_rgb, frame, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr, rgb=True)
 
     def TryFlipAndBlitAnsiRgbDelta(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                                    clear_screen: bool = False, merge_gap: int = 3, tolerance: int = 0, keyframe: bool = False, sdr: bool = False):
         """The delta form of TryFlipAndBlitAnsiRgb (ycge_video_blit_ansi_rgb_delta), on the delta state this context shares with
         RaytraceRenderer.TryFlipAndBlitAnsiRgbDelta: (bytes, info) or (bytes, info, SDR array) with sdr=True."""
-        f, ptr, w, h, bpp = self._frame_args(frame)
-        r = self._r
-        o = r._ansi_rgb_out(console_width, console_height)
-        n, info = C.c_size_t(0), (C.c_uint32 * 4)()
-        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
-        r._check(self.L.ycge_video_blit_ansi_rgb_delta(self.ctx, ptr, w, h, bpp, int(console_width), int(console_height), int(viewport[0]), int(viewport[1]),
-                                                       int(default_fg), int(default_bg), int(bool(clear_screen)), int(merge_gap), int(tolerance),
-                                                       int(bool(keyframe)), o.ctypes.data_as(C.POINTER(C.c_uint8)), o.size, C.byref(n), info,
-                                                       s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
-        stream, info = o[:n.value].tobytes(), dict(zip(RaytraceRenderer.DELTA_INFO, (int(v) for v in info)))
-        return (stream, info, s) if sdr else (stream, info)
+        return self._ansi_call(self.L.ycge_video_blit_ansi_rgb_delta, frame, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
+                               rgb=True, delta=(merge_gap, tolerance, bool(keyframe)))
 
     # ---------------------------------------------------------------- tests only
     def blit_probe(self, frame, fb_width: int, fb_height: int, superSample: int = 1) -> np.ndarray:
