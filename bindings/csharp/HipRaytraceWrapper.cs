@@ -25,7 +25,8 @@
 //   DeviceAnsiStream - with AnsiPresenter (a DeviceAnsiTerminalRenderer in place of ANSITerminalRenderer): the frame is read back as the
 //                bytes ANSITerminalRenderer.Render() would write for the console (ycge_render_frame_ansi), and the presenter writes them to
 //                stdout as they are - the framebuffer is not written and no cell is walked on the host.  Synchronous frames only (FrameLate
-//                is ignored); the raytrace framebuffer is the only one drawn (INTEGRATION.md section 8).
+//                is ignored).  The presenter's other framebuffers - Terminal's entity framebuffer, a menu, a text entity - are composed on the
+//                device as GetChexelForPoint composes them (ycge_console_set_layers, sent before every frame; INTEGRATION.md section 8).
 //   DeviceAnsiDelta - with DeviceAnsiStream: a frame's bytes are the delta stream (ycge_render_frame_ansi_delta) - only the cells whose
 //                ANSI pair changed since the last frame written, each run behind a cursor move, and always the console's last cell, so the
 //                cursor ends where Render() leaves it for Terminal.Start's HUD.  The first frame, a frame after a console resize
@@ -85,7 +86,8 @@ public sealed class HipGeneratedWorld
 /// With HipRaytraceOptions.AnsiTrueColor the same streams carry 24-bit colour (ycge_render_frame_ansi_rgb / _rgb_delta); the presenter writes
 /// them as they are, and a wrapper of the other colour form on the same context starts with a keyframe - the library sees to that.
 /// A change of console size is handled as ANSITerminalRenderer does it: onResize(width, height), and the next frame written starts with
-/// ESC[2J ESC[H.  Only the raytrace framebuffer is drawn: AddFrameBuffer / RemoveFrameBuffer keep nothing.</summary>
+/// ESC[2J ESC[H.  AddFrameBuffer / RemoveFrameBuffer keep the list as ANSITerminalRenderer does (:56-65); the wrapper that draws a frame hands
+/// the framebuffers beside its own to the library (HipConsoleLayers), which composes them as GetChexelForPoint does.</summary>
 public sealed class DeviceAnsiTerminalRenderer : ITerminalRenderer
 {
     public delegate ReadOnlySpan<byte> FrameSource();
@@ -111,8 +113,10 @@ public sealed class DeviceAnsiTerminalRenderer : ITerminalRenderer
         stdout.Flush();
     }
 
-    public void AddFrameBuffer(Framebuffer fb) { }
-    public void RemoveFrameBuffer(Framebuffer fb) { }
+    internal readonly List<Framebuffer> FrameBuffers = new List<Framebuffer>();      // frameBuffers (:21), bottom first
+
+    public void AddFrameBuffer(Framebuffer fb) { FrameBuffers.Add(fb); }
+    public void RemoveFrameBuffer(Framebuffer fb) { FrameBuffers.Remove(fb); }
 
     public void Render()
     {
@@ -206,6 +210,7 @@ public partial class RaytraceEntity
                 Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(bound, out IntPtr p));
                 ansiBuf = (byte*)p; ansiCap = (ulong)bound;
             }
+            HipConsoleLayers.Set(ctx, ansi.FrameBuffers, fb);                   // (the other framebuffers as they stand now; fb is this wrapper's own)
             UIntPtr len;
             if (ansiRgb && ansiDelta)
                 Ycge.Check(ctx, Ycge.ycge_render_frame_ansi_rgb_delta(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,

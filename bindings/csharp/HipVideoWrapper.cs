@@ -111,6 +111,7 @@ public partial class RaytraceEntity
                     Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(bound, out IntPtr p));
                     ansiBuf = (byte*)p; ansiCap = (ulong)bound;
                 }
+                HipConsoleLayers.Set(ctx, ansi.FrameBuffers, fb);               // (the presenter's other framebuffers, composed on the device)
                 UIntPtr len;
                 if (ansiRgb && ansiDelta)
                     Ycge.Check(ctx, Ycge.ycge_video_blit_ansi_rgb_delta(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,

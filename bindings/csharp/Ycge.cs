@@ -261,6 +261,9 @@ namespace ConsoleGame.RayTracing.Native
                                                                                  int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, int mergeGap,
                                                                                  int tolerance, int keyframe, byte* outStream, UIntPtr capacity, UIntPtr* outLen,
                                                                                  uint* outInfo, float* outTopBottomSdr);
+        // the console's other framebuffers for every stream call above (found by symbol lookup, ABI stays 10); YConsoleLayer, YChexel and
+        // HipConsoleLayers: bindings/csharp/YcgeConsole.cs
+        [DllImport(Lib)] public static extern int ycge_console_set_layers(IntPtr ctx, YConsoleLayer* layers, int n, int raytraceAt);
         // OBJ meshes from file bytes (MeshLoader.FromObj on the device; HipObjLoader.cs).  info: a YObjInfo
         [DllImport(Lib)] public static extern int ycge_obj_parse_host(byte* text, UIntPtr bytes, float* positions, int* faces, out YObjInfo info, byte* msg, UIntPtr msgBytes);
         [DllImport(Lib)] public static extern int ycge_obj_parse(IntPtr ctx, byte* text, UIntPtr bytes, out YObjInfo info);

@@ -631,6 +631,42 @@ int ycge_video_blit_ansi_rgb_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t 
                                    int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance,
                                    int32_t keyframe, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */,
                                    float *out_top_bottom_sdr /* may be NULL */);
+/* --- The console's other framebuffers in the device streams: layers, any glyph.  Terminal registers a console-sized entity framebuffer
+ * first (Renderer/Terminal.cs:53-55), RaytraceEntity adds its own on top (RaytraceEntity.cs:297-298), any entity may add more, and
+ * ANSITerminalRenderer.GetChexelForPoint (:67-84) composes them: the topmost framebuffer whose chexel at the point has Char != ' ' wins,
+ * else the default cell.  Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no existing struct or prototype changes; a
+ * host detects the export by symbol lookup.
+ *   ycge_chexel: Chexel.Char as its UTF-16 code unit, ForegroundColor.color_f32, BackgroundColor.color_f32 (28 bytes; pad is ignored).
+ *   ycge_console_layer: a Framebuffer - ViewportX, ViewportY, Width, Height - and its cells row by row: cell (x, y) at cells[y * w + x].
+ *   ycge_console_set_layers: layers[0..n) are the console's OTHER framebuffers in frameBuffers order, bottom first; raytrace_at in 0..n says
+ *   how many of them lie below the raytrace framebuffer, which keeps coming from the stream call's own viewport_x, viewport_y and the
+ *   context's size.  From this call on every one of the eight stream calls of the context (ycge_render_frame_ansi, ycge_video_blit_ansi, their
+ *   _delta, _rgb and _rgb_delta forms) writes the bytes Render() writes for that list:
+ *     GetChexelForPoint taken literally - a layer cell with ch == ' ' is transparent whatever its colours; raytrace chexels are '▀' and
+ *     opaque; ch == 0 is a character; nothing covering a point gives ' ' in the default colours.  Layers may hang off any edge of the console
+ *     or lie wholly outside it.
+ *     A cell's character is its code unit as AppendCharUtf8 (:204-224) writes it: 1 byte below 0x80, 2 below 0x800, else 3 - a lone surrogate
+ *     in its 3-byte form.  No character is longer than '▀', so ycge_ansi_stream_bound and ycge_ansi_rgb_stream_bound stand as they are.
+ *     A layer's colours are encoded once, by the encoder the frames use (the one behind ycge_render_frame_chexels, on the layer's colours as
+ *     top / bottom): ansi(fg), ansi(bg) for the 256-colour streams, RGB8(fg), RGB8(bg) for the 24-bit ones.
+ *   The call copies the cells (the host may reuse its arrays), costs the upload and encode of the layers' cells only, and joins frames in
+ *   flight like every scene call.  n == 0 removes all layers: the streams are then byte for byte what they are without this call.  The layers
+ *   survive ycge_resize and ycge_scene_upload.
+ *   All or nothing: a refused call leaves the previous layers in force.  YCGE_ERR_INVALID_ARG, the message naming the value: n outside
+ *   0..YCGE_CONSOLE_MAX_LAYERS, raytrace_at outside 0..n, a NULL layers with n > 0, a NULL cells, w or h <= 0, more than 2^26 cells over all
+ *   layers; a peer context refuses as the stream calls do.
+ *   The delta contract with layers in force (beside the rules at ycge_render_frame_ansi_delta and ycge_render_frame_ansi_rgb_delta):
+ *     What the terminal shows is a console-wide composite of {character, colours}; prev / shown is the composite the last _delta stream left.
+ *     changed(x, y) holds for ANY console cell whose character differs from what was last handed out, or whose colours differ - in 256
+ *     colours either index, in 24-bit colour the largest channel difference exceeding tolerance.  emitted, run starts, the last-cell rule,
+ *     merge_gap and out_info are as without layers; after a 24-bit delta shown = cur for every emitted cell, and its character always is cur's.
+ *     A ycge_console_set_layers call that keeps n > 0 never forces a keyframe: moved, resized or edited layers resend only the cells whose
+ *     composite changed.  Keyframes are the causes listed at the _delta calls, plus the first _delta call after the layers went from none
+ *     to some or back. */
+typedef struct ycge_chexel { uint16_t ch; uint16_t pad; float fg[3]; float bg[3]; } ycge_chexel;   /* 28 bytes */
+typedef struct ycge_console_layer { int32_t x, y, w, h; const ycge_chexel *cells; } ycge_console_layer;
+#define YCGE_CONSOLE_MAX_LAYERS 16
+int ycge_console_set_layers(ycge_ctx *ctx, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at);
 /* --- OBJ meshes from file bytes: MeshLoader.FromObj (RayTracing/MeshLoader.cs:12-149) up to the float soup ycge_mesh.triangles takes, parsed
  * on the device.  Added after ABI 10 without changing it (YCGE_ABI_VERSION stays 10, no struct changes; detect by symbol lookup).
  *   The contract, byte by byte ("the reference's loader" restated correctly; tests/obj_restatement.py is its yardstick):

@@ -68,6 +68,18 @@ int ycge_test_ansi_rgb_stream(ycge_ctx *c, const uint8_t *rgba, int32_t fbW, int
 int ycge_test_ansi_rgb_delta(ycge_ctx *c, const uint8_t *shown, const uint8_t *cur, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h,
                              int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
                              int32_t tolerance, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, uint8_t *out_shown);
+/* ---- the layered streams (csrc/ycge_ansi.cpp, kernels csrc/ycge_ansi_cells.hip.h): the compose kernel and the stream kernels alone on a
+ * caller-given framebuffer plane (rgb == 0: fbW x fbH pairs; else the fbW x 2 fbH RGBA plane), n >= 1 layers as ycge_console_set_layers
+ * takes them, and an optional previous composite - prev_colours in the plane's own form for a console_w x console_h framebuffer, prev_glyphs
+ * console_w * console_h code units.  delta == 0: the full stream (out_info untouched).  delta != 0: the rules and out_info of the _delta
+ * calls; a NULL prev_colours / prev_glyphs or clear_screen != 0 gives the keyframe.  tolerance is read when rgb != 0 alone.  out_colours /
+ * out_glyphs (or NULL) receive the next composite in the same forms: this call's, and in a 24-bit delta cur where a cell was emitted and
+ * prev elsewhere (every fourth byte 255).  Stateless: the context's own layers, request and delta state are untouched */
+int ycge_test_ansi_layers(ycge_ctx *c, int32_t rgb, const uint8_t *plane, int32_t fbW, int32_t fbH, const ycge_console_layer *layers, int32_t n,
+                          int32_t raytrace_at, const uint8_t *prev_colours, const uint16_t *prev_glyphs, int32_t console_w, int32_t console_h,
+                          int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t delta,
+                          int32_t merge_gap, int32_t tolerance, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
+                          uint8_t *out_colours, uint16_t *out_glyphs);
 /* ---- Video mode (csrc/ycge_video.cpp).  ycge_host_video_tables: host only, no device - for src_w x src_h -> fbW x fbH ss the tables
  * k_video_blit reads, as the library computed them with the C library's sinf: per hi-res column x0 (hiW = fbW*ss entries) and its six
  * normalised weights (6 hiW), per hi-res row y0 (hiH = fbH*2*ss) and weights (6 hiH), and {scale, offX, offY} (VideoRenderer.cs:75-81).

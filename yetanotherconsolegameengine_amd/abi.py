@@ -162,6 +162,19 @@ class ObjGroundInfo(C.Structure):
                 ("component_faces", C.c_int32), ("component_vertices", C.c_int32), ("first_face", C.c_int32), ("on_device", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Chexel(C.Structure):
+    """ycge_chexel, 28 bytes: Chexel.Char as its UTF-16 code unit, ForegroundColor.color_f32, BackgroundColor.color_f32."""
+    _fields_ = [("ch", C.c_uint16), ("pad", C.c_uint16), ("fg", C.c_float * 3), ("bg", C.c_float * 3)]
+
+
+class ConsoleLayer(C.Structure):
+    """ycge_console_layer: a Framebuffer's ViewportX, ViewportY, Width, Height and its cells row by row (cell (x, y) at y * w + x)."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("cells", C.POINTER(Chexel))]
+
+
+CONSOLE_MAX_LAYERS = 16
+
+
 class FlightInfo(C.Structure):
     _fields_ = [("two_trace_streams", C.c_int32), ("placed_gate", C.c_int32), ("post_gate", C.c_int32), ("post_pair", C.c_int32),
                 ("frames_outstanding", C.c_int32), ("stage_pipeline", C.c_int32), ("placed_waits", C.c_uint64)]
@@ -261,6 +274,8 @@ _PROTOTYPES = {
     "ycge_video_blit_ansi_rgb_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
                                                  C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    # (layers: an array of abi.ConsoleLayer, or None with n = 0)
+    "ycge_console_set_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
     "ycge_obj_parse_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "ycge_obj_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -325,6 +340,14 @@ ANSI_RGB_HOOK_PROTOTYPES = {
     "ycge_test_ansi_rgb_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)] + [C.c_int32] * 9 + [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "ycge_test_ansi_rgb_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)] + [C.c_int32] * 11 +
                                  [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
+}
+# test hook of the layered streams (csrc/ycge_ansi.cpp), bound where it is used (tests/test_gpu_ansi_layers.py): rgb, the framebuffer plane,
+# fbW, fbH, the layers (an array of abi.ConsoleLayer), n, raytrace_at, the previous composite's colours and glyphs (or None), the console,
+# viewport, defaults and clear_screen, delta, merge_gap, tolerance, the stream's four arguments, the next composite's colours and glyphs (or None)
+ANSI_LAYERS_HOOK_PROTOTYPES = {
+    "ycge_test_ansi_layers": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
+                                        C.POINTER(C.c_uint16)] + [C.c_int32] * 10 +
+                              [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)]),
 }
 # test / profiling hooks of the device-side mesh BVH build (csrc/ycge_mesh_bvh.cpp), bound where they are used (RaytraceRenderer.mesh_bvh_stats,
 # device_mesh_bvh below); res16: MESH_BVH_RES_WORDS uint32, the fallback reasons as the library names them

@@ -17,6 +17,10 @@
 // against what the terminal shows under a tolerance.  One request, one launch, one guard and one delivery serve every form; the delta
 // state belongs to the one terminal, so a stream of either family invalidates it for both.
 //
+// Layers (ycge_console_set_layers): the console's other framebuffers, kept in ChexelState::layers with their colours encoded once by
+// k_encode_chexels.  While any are set, launch() runs the compose pass in front of the stream kernels, which then walk the console-wide
+// composite; the delta forms keep the last composite's colour and glyph planes in comp_held / glyph_held, flipped with delta_held.
+//
 // The default cell's colours are ansi(palette16[k]): k_encode_chexels run once on the 16 palette colours, so no second formula exists.
 #include "ycge_ctx.h"
 
@@ -87,14 +91,23 @@ static int ensure_ansi(ycge_ctx *c, ChexelState &X, const AnsiRequest &r, unsign
 // r's stream of the fbW x fbH plane d_plane (the pairs; rgb: the RGBA plane), and the copy of what the scan reports.  delta: against d_prev
 // - rgb: what the terminal displays, d_next the plane that receives the next such - with the copy of {length, changed, emitted, run starts};
 // otherwise the full stream and its length alone
+// L (or NULL: no layers): the console's other framebuffers and the composite's planes, the compose pass in front; d_prev and d_next are then L's
 static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiRequest &r, bool delta, const uint8_t *d_plane, const uint8_t *d_prev, uint8_t *d_next,
-                  int fbW, int fbH)
+                  int fbW, int fbH, const ycge_ansi::LayersRun *L)
 {
     const uint8_t *palette = r.rgb ? X.rgb_palette.p : reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48);
     uint8_t *out = X.ansi_stream.p;
     const size_t cap = X.ansi_stream.cap;
     int e;
-    if (!delta)
+    if (L && !delta)
+        e = (r.rgb ? ycge_launch_ansi_rgb_layers_stream : ycge_launch_ansi_layers_stream)(L, d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.clear,
+                                                                                        X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
+    else if (L && r.rgb)
+        e = ycge_launch_ansi_rgb_layers_delta(L, d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, r.tolerance, X.ansi_tiles.p, out, cap, X.ansi_res.p,
+                                              stream);
+    else if (L)
+        e = ycge_launch_ansi_layers_delta(L, d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
+    else if (!delta)
         e = (r.rgb ? ycge_launch_ansi_rgb_stream : ycge_launch_ansi_stream)(d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.clear, X.ansi_tiles.p, out,
                                                                           cap, X.ansi_res.p, stream);
     else if (r.rgb)
@@ -108,11 +121,43 @@ static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiReq
     return YCGE_OK;
 }
 
+// S's layers in the colour form rgb; the composite's planes are the caller's to set
+static ycge_ansi::LayersRun layers_run(const LayerStore &S, bool rgb)
+{
+    ycge_ansi::LayersRun L{};
+    L.n = S.n; L.raytrace_at = S.raytrace_at; L.cells = S.cells;
+    L.colours = rgb ? S.rgba.p : S.pairs.p; L.glyphs = S.glyphs.p;
+    for (int k = 0; k < S.n; k++) L.rect[k] = S.rect[k];
+    return L;
+}
+
+// the composite's planes of r's console (kept while large enough): both held pairs, and for a 24-bit delta the third colour plane
+static int ensure_composite(ycge_ctx *c, ChexelState &X, const AnsiRequest &r)
+{
+    const size_t cells = (size_t)r.cw * (size_t)r.ch, bytes = (r.rgb ? 8 : 2) * cells;
+    for (int k = 0; k < 2; k++) {
+        if (X.comp_held[k].cap < bytes) HIP_TRY(c, X.comp_held[k].alloc(bytes));
+        if (X.glyph_held[k].cap < cells) HIP_TRY(c, X.glyph_held[k].alloc(cells));
+    }
+    if (r.rgb && r.delta && X.comp_cur.cap < bytes) HIP_TRY(c, X.comp_cur.alloc(bytes));
+    return YCGE_OK;
+}
+
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs)
 {
     ChexelState &X = c->chexels;
     { const int rc = X.ansi.rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
-    return launch(c, X, stream, X.ansi, X.delta_on && !X.delta_full, d_pairs, X.delta_held[X.delta_prev].p, X.delta_held[1 - X.delta_prev].p, c->fbW, c->fbH);
+    const bool delta = X.delta_on && !X.delta_full;
+    if (X.layers.n == 0)
+        return launch(c, X, stream, X.ansi, delta, d_pairs, X.delta_held[X.delta_prev].p, X.delta_held[1 - X.delta_prev].p, c->fbW, c->fbH, nullptr);
+    // (layers: this call's composite goes where the next _delta call finds it; a 24-bit delta's write kernel fills that plane instead)
+    ycge_ansi::LayersRun L = layers_run(X.layers, X.ansi.rgb);
+    const int held = X.delta_prev, next = 1 - X.delta_prev;
+    L.comp = delta && X.ansi.rgb ? X.comp_cur.p : X.comp_held[next].p;
+    L.comp_glyph = X.glyph_held[next].p;
+    L.prev = X.comp_held[held].p; L.prev_glyph = X.glyph_held[held].p;
+    L.next = X.comp_held[next].p;
+    return launch(c, X, stream, X.ansi, delta, d_pairs, nullptr, nullptr, c->fbW, c->fbH, &L);
 }
 
 } // namespace ycge_host
@@ -134,7 +179,8 @@ struct AnsiCall {
         X.ansi_on = true; X.ansi = r;
         X.delta_on = r.delta;
         if (r.delta)
-            X.delta_full = !X.delta_valid || X.delta_rgb != r.rgb || !X.delta_held[X.delta_prev].p || std::memcmp(key, X.delta_key, sizeof key) != 0 || r.clear || r.keyframe;
+            X.delta_full = !X.delta_valid || X.delta_rgb != r.rgb || !X.delta_held[X.delta_prev].p || std::memcmp(key, X.delta_key, sizeof key) != 0 || r.clear || r.keyframe ||
+                           X.delta_layered != (X.layers.n > 0) || (X.layers.n > 0 && (!X.comp_held[X.delta_prev].p || !X.glyph_held[X.delta_prev].p));
         else
             X.delta_valid = false;
     }
@@ -150,7 +196,7 @@ struct AnsiCall {
     {
         ChexelState &X = c->chexels;
         if (!X.ansi.delta) return;
-        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = X.ansi.rgb;
+        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = X.ansi.rgb; X.delta_layered = X.layers.n > 0;
         std::memcpy(X.delta_key, key, sizeof key);
         done = true;
     }
@@ -214,6 +260,7 @@ int frame(ycge_ctx *c, const char *fn, const AnsiRequest &r, uint8_t *out_stream
     AnsiCall call(c, r);
     ChexelState &X = c->chexels;
     rc = ensure_ansi(c, X, r, bound, c->stream);
+    if (rc == YCGE_OK && X.layers.n > 0) rc = ensure_composite(c, X, r);
     if (rc != YCGE_OK) return rc;
     rc = render_frame_sync(c, out_top_bottom_sdr, true, st);          // (its stream synchronisation: the length and the counters have arrived)
     if (rc != YCGE_OK) return rc;
@@ -240,6 +287,7 @@ int video(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t *fram
     StagedSdrGuard staged(c);
     ChexelState &X = c->chexels;
     rc = ensure_ansi(c, X, r, bound, c->stream);
+    if (rc == YCGE_OK && X.layers.n > 0) rc = ensure_composite(c, X, r);
     const float *d_sdr = nullptr;
     if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
     if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, d_sdr, false);
@@ -285,7 +333,7 @@ int test_stream(ycge_ctx *c, const char *fn, const char *what, const AnsiRequest
         HIP_TRY(c, next.alloc(bytes));
         HIP_TRY(c, hipMemcpy(next.p, held.p, bytes, hipMemcpyDeviceToDevice));      // (framebuffer cells off the console keep what they held)
     }
-    rc = launch(c, X, c->stream, r, !full, in.p, held.p, next.p, fbW, fbH);
+    rc = launch(c, X, c->stream, r, !full, in.p, held.p, next.p, fbW, fbH, nullptr);
     if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     rc = deliver(c, X, fn, full, bound, out_stream, out_len, out_info);
@@ -294,6 +342,126 @@ int test_stream(ycge_ctx *c, const char *fn, const char *what, const AnsiRequest
     if (rc != YCGE_OK) return rc;
     for (size_t k = 3; k < bytes; k += 4) out_shown[k] = 255;
     return YCGE_OK;
+}
+
+constexpr uint64_t kLayerCellsMax = 1ull << 26;
+
+// what ycge_console_set_layers refuses in its arguments; cells: the layers' cells in all
+int check_layers(ycge_ctx *c, const char *fn, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at, uint64_t &cells)
+{
+    if (n < 0 || n > YCGE_CONSOLE_MAX_LAYERS) return c->fail(YCGE_ERR_INVALID_ARG, "%s: n = %d (0..%d layers)", fn, n, YCGE_CONSOLE_MAX_LAYERS);
+    if (raytrace_at < 0 || raytrace_at > n) return c->fail(YCGE_ERR_INVALID_ARG, "%s: raytrace_at = %d (0..n = %d)", fn, raytrace_at, n);
+    if (n > 0 && !layers) return c->fail(YCGE_ERR_INVALID_ARG, "%s: layers is NULL with n = %d", fn, n);
+    cells = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (!layers[k].cells) return c->fail(YCGE_ERR_INVALID_ARG, "%s: layers[%d].cells is NULL", fn, k);
+        if (layers[k].w <= 0 || layers[k].h <= 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: layers[%d] is %d x %d (both must be positive)", fn, k, layers[k].w, layers[k].h);
+        cells += (uint64_t)layers[k].w * (uint64_t)layers[k].h;
+        if (cells > kLayerCellsMax) return c->fail(YCGE_ERR_INVALID_ARG, "%s: more than 2^26 cells over all layers (%llu by layers[%d])", fn, (unsigned long long)cells, k);
+    }
+    return YCGE_OK;
+}
+
+// checked layers into S: the cells' code units and colours uploaded, the colours encoded by k_encode_chexels as a cells x 1 framebuffer
+// {top = foreground, bottom = background} into the pairs and the RGBA plane.  Synchronous on c->stream; the host's arrays are free on return
+int build_layers(ycge_ctx *c, ChexelState &X, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at, uint64_t cells, LayerStore &S)
+{
+    { const int rc = ensure_tables(c, X); if (rc != YCGE_OK) return rc; }
+    std::vector<uint16_t> glyphs((size_t)cells);
+    std::vector<float> sdr(6 * (size_t)cells);
+    size_t at = 0;
+    for (int32_t k = 0; k < n; k++) {
+        const ycge_console_layer &l = layers[k];
+        S.rect[k] = ycge_ansi::LayerRect{l.x, l.y, l.w, l.h, (uint32_t)at};
+        const size_t count = (size_t)l.w * (size_t)l.h;
+        for (size_t j = 0; j < count; j++, at++) {
+            const ycge_chexel &x = l.cells[j];
+            glyphs[at] = x.ch;
+            for (int q = 0; q < 3; q++) { sdr[6 * at + q] = x.fg[q]; sdr[6 * at + 3 + q] = x.bg[q]; }
+        }
+    }
+    S.n = n; S.raytrace_at = raytrace_at; S.cells = (uint32_t)cells;
+    DevBuf<float> d_sdr;
+    HIP_TRY(c, d_sdr.upload(sdr));
+    HIP_TRY(c, S.glyphs.upload(glyphs));
+    HIP_TRY(c, S.pairs.alloc(2 * (size_t)cells));
+    HIP_TRY(c, S.rgba.alloc(8 * (size_t)cells));
+    const int e = ycge_launch_chexels(d_sdr.p, (int)cells, 1, X.tables.p, nullptr, S.pairs.p, S.rgba.p, c->compute_units, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed (the layers' colours): %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return YCGE_OK;
+}
+
+// ycge_console_set_layers: all or nothing - the new store is complete before it replaces the old one
+int set_layers(ycge_ctx *c, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    const char *fn = "ycge_console_set_layers";
+    uint64_t cells = 0;
+    int rc = check_layers(c, fn, layers, n, raytrace_at, cells);
+    if (rc != YCGE_OK) return rc;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    rc = join_async(c);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    LayerStore S;
+    if (n > 0) {
+        rc = build_layers(c, c->chexels, layers, n, raytrace_at, cells, S);
+        if (rc != YCGE_OK) return rc;
+    }
+    c->chexels.layers = std::move(S);
+    return YCGE_OK;
+}
+
+// The layered test hook: compose and stream kernels alone on a caller-given framebuffer plane (rgb: the RGBA plane, else the pairs), layers
+// and previous composite, with the geometry, defaults and refusals of the frame calls.  delta: a _delta call's rules - a NULL previous
+// composite or a clear_screen gives the keyframe.  Stateless: layer store and planes of its own; the context's layers, request and delta
+// state are untouched.  out_colours / out_glyphs (or NULL): the next composite - this call's, in a 24-bit delta emitted ? cur : shown
+int test_layers(ycge_ctx *c, const AnsiRequest &r, const uint8_t *plane, int32_t fbW, int32_t fbH, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at,
+                const uint8_t *prev_colours, const uint16_t *prev_glyphs, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
+                uint8_t *out_colours, uint16_t *out_glyphs)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    const char *fn = "ycge_test_ansi_layers";
+    if (!plane || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (plane %p, %d x %d)", fn, (const void *)plane, fbW, fbH);
+    unsigned long long bound = 0;
+    uint64_t cells = 0;
+    int rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
+    if (rc == YCGE_OK) rc = check_layers(c, fn, layers, n, raytrace_at, cells);
+    if (rc != YCGE_OK) return rc;
+    if (n == 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: n = 0 (the unlayered streams have hooks of their own)", fn);
+    HIP_TRY(c, hipSetDevice(c->device));
+    ChexelState &X = c->chexels;
+    rc = ensure_ansi(c, X, r, bound, c->stream);
+    if (rc != YCGE_OK) return rc;
+    LayerStore S;
+    rc = build_layers(c, X, layers, n, raytrace_at, cells, S);
+    if (rc != YCGE_OK) return rc;
+    const bool full = !r.delta || !prev_colours || !prev_glyphs || r.clear;
+    const size_t console = (size_t)r.cw * (size_t)r.ch, bytes = (r.rgb ? 8 : 2) * console, fb_bytes = (r.rgb ? 8 : 2) * (size_t)fbW * fbH;
+    DevBuf<uint8_t> in, comp, held, next;
+    DevBuf<uint16_t> comp_glyph, held_glyph;
+    HIP_TRY(c, in.alloc(fb_bytes));
+    HIP_TRY(c, hipMemcpy(in.p, plane, fb_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(c, comp.alloc(bytes));
+    HIP_TRY(c, comp_glyph.alloc(console));
+    if (!full) {
+        HIP_TRY(c, held.alloc(bytes));
+        HIP_TRY(c, hipMemcpy(held.p, prev_colours, bytes, hipMemcpyHostToDevice));
+        HIP_TRY(c, held_glyph.alloc(console));
+        HIP_TRY(c, hipMemcpy(held_glyph.p, prev_glyphs, console * sizeof(uint16_t), hipMemcpyHostToDevice));
+        if (r.rgb) HIP_TRY(c, next.alloc(bytes));
+    }
+    ycge_ansi::LayersRun L = layers_run(S, r.rgb);
+    L.comp = comp.p; L.comp_glyph = comp_glyph.p; L.prev = held.p; L.prev_glyph = held_glyph.p; L.next = next.p;
+    rc = launch(c, X, c->stream, r, !full, in.p, nullptr, nullptr, fbW, fbH, &L);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rc = deliver(c, X, fn, full, bound, out_stream, out_len, r.delta ? out_info : nullptr);
+    if (rc == YCGE_OK && out_colours) rc = copy_out(c, out_colours, !full && r.rgb ? next.p : comp.p, bytes);
+    if (rc == YCGE_OK && out_glyphs) rc = copy_out(c, out_glyphs, comp_glyph.p, console * sizeof(uint16_t));
+    return rc;
 }
 
 // a call's arguments as its request
@@ -453,6 +621,26 @@ try {
     const AnsiRequest r = request(true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
     return test_stream(c, "ycge_test_ansi_rgb_delta", "cur", with_delta(r, merge_gap, tolerance, 0), shown, cur, fbW, fbH, out_stream, capacity, out_len, out_info,
                        out_shown);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// The console's other framebuffers (the contract: include/ycge.h): from this call on every stream call of the context writes the bytes
+// Render() writes for the whole list
+int ycge_console_set_layers(ycge_ctx *c, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at)
+try {
+    return set_layers(c, layers, n, raytrace_at);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: the compose and stream kernels alone on a caller-given framebuffer plane, layers and previous composite (test_layers above)
+int ycge_test_ansi_layers(ycge_ctx *c, int32_t rgb, const uint8_t *plane, int32_t fbW, int32_t fbH, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at,
+                          const uint8_t *prev_colours, const uint16_t *prev_glyphs, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
+                          int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t delta, int32_t merge_gap, int32_t tolerance, uint8_t *out_stream,
+                          size_t capacity, size_t *out_len, uint32_t *out_info, uint8_t *out_colours, uint16_t *out_glyphs)
+try {
+    AnsiRequest r = request(rgb != 0, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
+    if (delta) r = with_delta(r, merge_gap, rgb ? tolerance : 0, 0);
+    return test_layers(c, r, plane, fbW, fbH, layers, n, raytrace_at, prev_colours, prev_glyphs, out_stream, capacity, out_len, out_info, out_colours, out_glyphs);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

@@ -19,12 +19,16 @@ struct Indexed {
     using Plane = uint8_t;                // fbW x fbH {fg = ansi(top), bg = ansi(bottom)}; the palette: ansi(palette16[k]) at byte k
     using Args = StreamArgs<Plane>;
     using Delta = DeltaArgs<Plane>;
+    using Glyph = FixedGlyph;
     static constexpr uint32_t kNone = 256u;
     static constexpr int kEscMax = 7 + 3 + 6 + 3 + 1;               // 20
 
     static __device__ __forceinline__ size_t offset(const Args &a, size_t fx, size_t fy) { return 2 * (fy * (uint32_t)a.fbW + fx); }
     static __device__ __forceinline__ void load(const Plane *p, const Args &, uint32_t &fg, uint32_t &bg) { fg = p[0]; bg = p[1]; }
     static __device__ __forceinline__ void load_default(const Args &a, uint32_t &fg, uint32_t &bg) { fg = a.palette[a.dfg]; bg = a.palette[a.dbg]; }
+    static __device__ __forceinline__ void store(Plane *p, const Args &, uint32_t fg, uint32_t bg) { p[0] = (uint8_t)fg; p[1] = (uint8_t)bg; }
+    // layer cell k of the pairs the encoder wrote for the layers' cells
+    static __device__ __forceinline__ void layer_load(const Plane *lc, uint32_t, uint32_t k, uint32_t &fg, uint32_t &bg) { fg = lc[2 * (size_t)k]; bg = lc[2 * (size_t)k + 1]; }
 
     static __device__ __forceinline__ uint32_t both_bytes(uint32_t fg, uint32_t bg) { return 14u + digits(fg) + digits(bg); }
 
@@ -72,4 +76,22 @@ extern "C" int ycge_launch_ansi_delta(const uint8_t *pairs, const uint8_t *prev,
                                       hipStream_t stream)
 {
     return launch_delta<Indexed>(Indexed::Delta{}, pairs, prev, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream);
+}
+
+// the two above with the console's other framebuffers (ycge_ansi_layers.h): the compose pass into L->comp / L->comp_glyph - 2 cw ch bytes
+// and cw ch code units - then the stream of that composite; the delta against L->prev / L->prev_glyph.  Four launches on `stream`.
+extern "C" int ycge_launch_ansi_layers_stream(const LayersRun *L, const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                                              int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len,
+                                              hipStream_t stream)
+{
+    if (!L) return (int)hipErrorInvalidValue;
+    return launch_layered_stream<Indexed>(*L, pairs, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, clear, tiles, out, cap, out_len, stream);
+}
+
+extern "C" int ycge_launch_ansi_layers_delta(const LayersRun *L, const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                                             int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
+                                             hipStream_t stream)
+{
+    if (!L) return (int)hipErrorInvalidValue;
+    return launch_layered_delta<Indexed>(Indexed::Delta{}, *L, pairs, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream);
 }

@@ -41,6 +41,20 @@
 //     bound reaches 2^32, so cw ch < 2^32 / (E + 3) and digits(ch) + digits(cw) <= digits(cw ch) + 1 <= 10.
 //   - The trailer is the bound's 4.  So the delta is at most the bound less the 7 bytes of the clear prefix, which it never writes; the
 //     2 x 1 console with both cells changed (and, in 24-bit colour, every channel three-digit) reaches exactly that.
+//   - A layered stream (below) writes any UTF-16 code unit as a cell's character.  AppendCharUtf8 (:204-224) writes a code unit below
+//     0x80 as 1 byte, below 0x800 as 2 and any other as 3 - a lone surrogate too, in its 3-byte form - so no character is longer than
+//     the 3 bytes of '▀' that E + 3 counts, and every line above holds as it stands.
+//
+// Layers.  With the console's other framebuffers set (ycge_console_set_layers; LayersRun in ycge_ansi_layers.h) a stream is two steps:
+//   k_compose<C>      one lane per console cell: GetChexelForPoint (:67-84) over the at most 17 sources, topmost first - a layer cell whose
+//                     code unit is not ' ' wins, the raytrace framebuffer's chexels are '▀' and always win, nothing gives ' ' in the default
+//                     colours - into a console-sized colour plane in C's own form and a uint16_t glyph plane beside it
+//   the kernels above, instantiated with Layered<C>: the composite is a framebuffer that fills the console (every cell covered, viewport
+//                     0, 0), the character comes from the glyph plane (PlaneGlyph) and is 1, 2 or 3 bytes; changed(x, y) also holds where the
+//                     code unit differs from the previous composite's.  A differing glyph is always emitted, so the next glyph plane is this
+//                     call's as it stands; the colour planes follow C::store_next as before.
+// The unlayered instances (FixedGlyph) load no glyph and launch no compose pass; the LDS stages keep their sizes, a character being at most
+// the 3 bytes they already count.
 //
 // LDS.  A cell is at most (5 + 10) + E + 3 bytes in the full stream and (4 + 10 + 10) + E + 3 in a delta, which sizes the stage of a
 // tile's 1024 cells (4 a lane): 38 912 and 48 128 B for 256 colours; 55 296 and 64 512 B for 24-bit colour, two workgroups a CU of the
@@ -58,10 +72,14 @@
 //   both_bytes(fg, bg)             the length of the both-differ escape, which a run start writes unconditionally
 //   changed(d, o)                  changed, for the covered cell at offset o
 //   store_next(d, o, emitted)      what k_delta_write leaves for the next call at offset o
+//   Glyph                          FixedGlyph ('▀' where covered, ' ' elsewhere); Layered<C> has PlaneGlyph
+//   store(p, a, fg, bg)            load's inverse, and layer_load(lc, cells, k, fg, bg): the colours of layer cell k (k_compose alone)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "ycge_ansi_layers.h"
 
 namespace ycge_ansi {
 
@@ -79,6 +97,7 @@ struct StreamArgs {
     const T *palette;                     // that encoder on the 16 palette colours (C::load_default)
     int32_t fbW, fbH, cw, vx, vy, dfg, dbg;
     uint32_t n;                           // console cells, cw * ch
+    const uint16_t *glyph;                // PlaneGlyph alone: the composite's code units, n of them (the plane is then cw x ch at 0, 0)
 };
 
 template <typename T>
@@ -86,17 +105,29 @@ struct DeltaArgs {
     StreamArgs<T> a;                      // a.plane: this frame's
     const T *prev;                        // what the last stream handed out left on the terminal, same shape
     int32_t gap;                          // merge_gap, 0..kGapMax
+    const uint16_t *prev_glyph;           // PlaneGlyph alone: prev's code units
 };
 
 struct Cell {
     uint32_t x, y, fg, bg;
+    uint32_t ch;                          // PlaneGlyph alone: the cell's UTF-16 code unit
     bool covered;                         // a framebuffer chexel ('▀'); otherwise the default cell (' ')
 };
+
+// The glyph policy.  FixedGlyph: the character is a compile-time function of `covered`, no plane is read.  PlaneGlyph: the composite of a
+// layered console, whose every cell is covered and whose character is the glyph plane's code unit.
+struct FixedGlyph { static constexpr bool kPlane = false; };
+struct PlaneGlyph { static constexpr bool kPlane = true; };
+
+// a colour policy over the composite of a layered console
+template <class C>
+struct Layered : C { using Glyph = PlaneGlyph; };
 
 // console cell (x, y) lies on the framebuffer; o: where its colours start in a plane
 template <class C>
 __device__ __forceinline__ bool covered_at(const StreamArgs<typename C::Plane> &a, uint32_t x, uint32_t y, size_t &o)
 {
+    if (C::Glyph::kPlane) { o = C::offset(a, x, y); return true; }
     const int64_t fx = (int64_t)x - a.vx, fy = (int64_t)y - a.vy;
     if (!(fx >= 0 && fx < a.fbW && fy >= 0 && fy < a.fbH)) return false;
     o = C::offset(a, (size_t)fx, (size_t)fy);
@@ -104,12 +135,20 @@ __device__ __forceinline__ bool covered_at(const StreamArgs<typename C::Plane> &
 }
 
 // GetChexelForPoint (:67-84) with the raytrace framebuffer alone: its chexels are '▀', never ' ', so no layer below shows through
+// (PlaneGlyph: the composite's cell, which k_compose made by that lookup over every source)
 template <class C>
 __device__ __forceinline__ Cell cell_at(const StreamArgs<typename C::Plane> &a, uint32_t i)
 {
     Cell c;
     c.y = i / (uint32_t)a.cw;
     c.x = i - c.y * (uint32_t)a.cw;
+    c.ch = 0;
+    if (C::Glyph::kPlane) {
+        c.covered = true;
+        c.ch = a.glyph[i];
+        C::load(a.plane + C::offset(a, c.x, c.y), a, c.fg, c.bg);
+        return c;
+    }
     const int64_t fx = (int64_t)c.x - a.vx, fy = (int64_t)c.y - a.vy;
     c.covered = fx >= 0 && fx < a.fbW && fy >= 0 && fy < a.fbH;
     if (c.covered) C::load(a.plane + C::offset(a, (size_t)fx, (size_t)fy), a, c.fg, c.bg);
@@ -145,6 +184,25 @@ __device__ __forceinline__ uint32_t put_char(uint8_t *s, uint32_t p, bool covere
     return p + 1;
 }
 
+// the bytes of a cell's character.  PlaneGlyph: AppendCharUtf8 (:204-224) on the code unit - 1 byte below 0x80, 2 below 0x800, else 3
+template <class G>
+__device__ __forceinline__ uint32_t glyph_bytes(const Cell &c)
+{
+    if (G::kPlane) return 1u + (c.ch >= 0x80u) + (c.ch >= 0x800u);
+    return c.covered ? 3u : 1u;
+}
+
+template <class G>
+__device__ __forceinline__ uint32_t put_glyph(uint8_t *s, uint32_t p, const Cell &c)
+{
+    if (!G::kPlane) return put_char(s, p, c.covered);
+    const uint32_t u = c.ch;
+    if (u < 0x80u) { s[p] = (uint8_t)u; return p + 1; }
+    if (u < 0x800u) { s[p] = (uint8_t)(0xc0u | u >> 6); s[p + 1] = (uint8_t)(0x80u | (u & 0x3fu)); return p + 2; }
+    s[p] = (uint8_t)(0xe0u | u >> 12); s[p + 1] = (uint8_t)(0x80u | (u >> 6 & 0x3fu)); s[p + 2] = (uint8_t)(0x80u | (u & 0x3fu));
+    return p + 3;
+}
+
 // exclusive scan of one value per lane over the workgroup (wave prefix by __shfl_up, the wave totals through LDS); total: the sum
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *wsum, uint32_t &total)
 {
@@ -176,14 +234,14 @@ template <class C>
 __device__ __forceinline__ uint32_t cell_bytes(const Cell &c, uint32_t pfg, uint32_t pbg)
 {
     const uint32_t len = c.x == 0 ? 5u + digits(c.y + 1u) : 0u;      // ESC [ y+1 ; 1 H
-    return len + C::esc_bytes(c.fg, c.bg, pfg, pbg) + (c.covered ? 3u : 1u);
+    return len + C::esc_bytes(c.fg, c.bg, pfg, pbg) + glyph_bytes<typename C::Glyph>(c);
 }
 
 template <class C>
 __device__ __forceinline__ uint32_t put_cell(uint8_t *s, uint32_t p, const Cell &c, uint32_t pfg, uint32_t pbg)
 {
     if (c.x == 0) { p = put_ascii(s, p, "\x1b["); p = put_int(s, p, c.y + 1u); p = put_ascii(s, p, ";1H"); }
-    return put_char(s, C::put_esc(s, p, c.fg, c.bg, pfg, pbg), c.covered);
+    return put_glyph<typename C::Glyph>(s, C::put_esc(s, p, c.fg, c.bg, pfg, pbg), c);
 }
 
 // the byte counts of this lane's kAnsiPerLane cells (a lane past the end counts 0)
@@ -296,6 +354,7 @@ __device__ __forceinline__ bool changed_at(const typename C::Delta &d, uint32_t 
     const uint32_t y = i / (uint32_t)d.a.cw, x = i - y * (uint32_t)d.a.cw;
     size_t o;
     if (!covered_at<C>(d.a, x, y, o)) return false;
+    if (C::Glyph::kPlane && d.a.glyph[i] != d.prev_glyph[i]) return true;
     return C::changed(d, o);
 }
 
@@ -369,7 +428,7 @@ __device__ __forceinline__ void lane_delta(const typename C::Delta &d, const uin
                 L.pfg[k] = p.fg; L.pbg[k] = p.bg;
                 len = C::esc_bytes(c.fg, c.bg, p.fg, p.bg);
             }
-            L.len[k] = len + (c.covered ? 3u : 1u);
+            L.len[k] = len + glyph_bytes<typename C::Glyph>(c);
             L.counts[1]++;
             L.counts[2] += L.start[k];
         }
@@ -420,12 +479,59 @@ __global__ __launch_bounds__(kAnsiBlock) void k_delta_write(typename C::Delta d,
         if (L.start[k]) {
             p = put_ascii(stage, p, "\x1b["); p = put_int(stage, p, c.y + 1u); stage[p++] = ';'; p = put_int(stage, p, c.x + 1u); stage[p++] = 'H';
         }
-        p = put_char(stage, C::put_esc(stage, p, c.fg, c.bg, L.pfg[k], L.pbg[k]), c.covered);      // (a run start: against kNone, kNone - both colours)
+        p = put_glyph<typename C::Glyph>(stage, C::put_esc(stage, p, c.fg, c.bg, L.pfg[k], L.pbg[k]), c);      // (a run start: against kNone, kNone - both colours)
     }
     __syncthreads();
     const uint32_t off = tiles[blockIdx.x * (uint32_t)kTileWords];
     for (uint32_t j = threadIdx.x; j < total; j += kAnsiBlock)
         if (off + j < cap) out[off + j] = stage[j];
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the composite
+
+template <typename T>
+struct ComposeArgs {
+    StreamArgs<T> a;                      // the raytrace framebuffer's plane, its geometry on the console, the default colours
+    const T *layer_colours;               // LayersRun::colours
+    const uint16_t *layer_glyphs;
+    uint32_t layer_cells;
+    int32_t n_layers, raytrace_at;
+    T *out;                               // the composite's colour plane: a cw x ch framebuffer's
+    uint16_t *out_glyph;                  // ... and its code units
+    LayerRect rect[kMaxLayers];
+};
+
+// GetChexelForPoint (:67-84) for console cell i over every source.  Source s of 0..n_layers, bottom first: layer s below the raytrace
+// framebuffer (s < raytrace_at), the raytrace framebuffer (s == raytrace_at), layer s - 1 above it.  Every index is checked against its
+// rectangle before the load; the rectangles and `first` are the host's, within layer_cells.
+template <class C>
+__global__ __launch_bounds__(kAnsiBlock) void k_compose(ComposeArgs<typename C::Plane> g)
+{
+    const uint32_t i = blockIdx.x * (uint32_t)kAnsiBlock + threadIdx.x;
+    if (i >= g.a.n) return;
+    const uint32_t y = i / (uint32_t)g.a.cw, x = i - y * (uint32_t)g.a.cw;
+    uint32_t fg = 0, bg = 0, ch = ' ';
+    bool found = false;
+    for (int s = g.n_layers; s >= 0 && !found; s--) {
+        if (s == g.raytrace_at) {
+            size_t o;
+            if (covered_at<C>(g.a, x, y, o)) { C::load(g.a.plane + o, g.a, fg, bg); ch = 0x2580u; found = true; }
+            continue;
+        }
+        const LayerRect &r = g.rect[s < g.raytrace_at ? s : s - 1];
+        const int64_t lx = (int64_t)x - r.x, ly = (int64_t)y - r.y;
+        if (!(lx >= 0 && lx < r.w && ly >= 0 && ly < r.h)) continue;
+        const uint32_t k = r.first + (uint32_t)ly * (uint32_t)r.w + (uint32_t)lx;
+        const uint32_t u = g.layer_glyphs[k];
+        if (u == (uint32_t)' ') continue;                            // (transparent whatever its colours)
+        C::layer_load(g.layer_colours, g.layer_cells, k, fg, bg);
+        ch = u; found = true;
+    }
+    if (!found) C::load_default(g.a, fg, bg);
+    StreamArgs<typename C::Plane> full = g.a;                         // the composite as a framebuffer: cw wide
+    full.fbW = g.a.cw;
+    C::store(g.out + C::offset(full, x, y), full, fg, bg);
+    g.out_glyph[i] = (uint16_t)ch;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the launches
@@ -442,6 +548,7 @@ bool fill_args(StreamArgs<T> &a, const uint8_t *plane, int fbW, int fbH, int cw,
     a.plane = reinterpret_cast<const T *>(plane); a.palette = reinterpret_cast<const T *>(palette);
     a.fbW = fbW; a.fbH = fbH; a.cw = cw; a.vx = vx; a.vy = vy; a.dfg = dfg; a.dbg = dbg;
     a.n = (uint32_t)cw * (uint32_t)ch;
+    a.glyph = nullptr;
     return true;
 }
 
@@ -472,11 +579,84 @@ int launch_delta(typename C::Delta d, const uint8_t *plane, const uint8_t *prev,
     if (!fill_args(d.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !prev || (uintptr_t)prev % alignof(T) || gap < 0 || gap > kGapMax || !tiles ||
         !out || !res || cap > 0xffffffffull)
         return (int)hipErrorInvalidValue;
-    d.prev = reinterpret_cast<const T *>(prev); d.gap = gap;
+    d.prev = reinterpret_cast<const T *>(prev); d.gap = gap; d.prev_glyph = nullptr;
     const uint32_t n_tiles = tiles_of(d.a.n);
     hipLaunchKernelGGL(k_delta_count<C>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, d, tiles);
     hipLaunchKernelGGL(k_scan<true>, dim3(1), dim3(kAnsiBlock), 0, stream, tiles, n_tiles, 0, out, (uint32_t)cap, res);
     hipLaunchKernelGGL(k_delta_write<C>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, d, (const uint32_t *)tiles, out, (uint32_t)cap);
+    return (int)hipGetLastError();
+}
+
+// the layered forms: the compose pass into L.comp / L.comp_glyph, then the kernels above over the composite.  false: a LayersRun no kernel may see
+template <typename T>
+bool fill_compose(ComposeArgs<T> &g, const LayersRun &L, int ch, bool delta)
+{
+    if (L.n <= 0 || L.n > kMaxLayers || L.raytrace_at < 0 || L.raytrace_at > L.n || !L.colours || !L.glyphs || !L.comp || !L.comp_glyph ||
+        (uintptr_t)L.colours % alignof(T) || (uintptr_t)L.comp % alignof(T) || (delta && (!L.prev || !L.prev_glyph || (uintptr_t)L.prev % alignof(T))))
+        return false;
+    for (int k = 0; k < L.n; k++) {
+        const LayerRect &r = L.rect[k];
+        if (r.w <= 0 || r.h <= 0 || (uint64_t)r.first + (uint64_t)r.w * (uint64_t)r.h > (uint64_t)L.cells) return false;
+        g.rect[k] = r;
+    }
+    for (int k = L.n; k < kMaxLayers; k++) g.rect[k] = LayerRect{0, 0, 0, 0, 0};
+    g.layer_colours = reinterpret_cast<const T *>(L.colours); g.layer_glyphs = L.glyphs; g.layer_cells = L.cells;
+    g.n_layers = L.n; g.raytrace_at = L.raytrace_at;
+    g.out = reinterpret_cast<T *>(L.comp); g.out_glyph = L.comp_glyph;
+    return true;
+}
+
+template <class C>
+void launch_compose(ComposeArgs<typename C::Plane> &g, hipStream_t stream)
+{
+    g.a.glyph = nullptr;
+    hipLaunchKernelGGL(k_compose<C>, dim3((g.a.n + (uint32_t)kAnsiBlock - 1u) / (uint32_t)kAnsiBlock), dim3(kAnsiBlock), 0, stream, g);
+}
+
+// the composite as the stream kernels' framebuffer
+template <typename T>
+void composite_args(StreamArgs<T> &a, const ComposeArgs<T> &g, int ch)
+{
+    a = g.a;
+    a.plane = g.out; a.fbW = g.a.cw; a.fbH = ch; a.vx = 0; a.vy = 0; a.glyph = g.out_glyph;
+}
+
+// launch_stream's arguments and the layers: four launches on `stream`
+template <class C>
+int launch_layered_stream(const LayersRun &L, const uint8_t *plane, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg, int clear,
+                          uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream)
+{
+    using T = typename C::Plane;
+    ComposeArgs<T> g;
+    if (!fill_args(g.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !fill_compose(g, L, ch, false) || !tiles || !out || !out_len || cap > 0xffffffffull)
+        return (int)hipErrorInvalidValue;
+    launch_compose<C>(g, stream);
+    StreamArgs<T> a;
+    composite_args(a, g, ch);
+    const uint32_t n_tiles = tiles_of(a.n);
+    hipLaunchKernelGGL(k_count<Layered<C>>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, a, tiles);
+    hipLaunchKernelGGL(k_scan<false>, dim3(1), dim3(kAnsiBlock), 0, stream, tiles, n_tiles, clear, out, (uint32_t)cap, out_len);
+    hipLaunchKernelGGL(k_write<Layered<C>>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, a, (const uint32_t *)tiles, out, (uint32_t)cap);
+    return (int)hipGetLastError();
+}
+
+// launch_delta's arguments and the layers: the composite against L.prev / L.prev_glyph.  Four launches on `stream`
+template <class C>
+int launch_layered_delta(typename C::Delta d, const LayersRun &L, const uint8_t *plane, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                         int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream)
+{
+    using T = typename C::Plane;
+    ComposeArgs<T> g;
+    if (!fill_args(g.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !fill_compose(g, L, ch, true) || gap < 0 || gap > kGapMax || !tiles || !out || !res ||
+        cap > 0xffffffffull)
+        return (int)hipErrorInvalidValue;
+    launch_compose<C>(g, stream);
+    composite_args(d.a, g, ch);
+    d.prev = reinterpret_cast<const T *>(L.prev); d.prev_glyph = L.prev_glyph; d.gap = gap;
+    const uint32_t n_tiles = tiles_of(d.a.n);
+    hipLaunchKernelGGL(k_delta_count<Layered<C>>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, d, tiles);
+    hipLaunchKernelGGL(k_scan<true>, dim3(1), dim3(kAnsiBlock), 0, stream, tiles, n_tiles, 0, out, (uint32_t)cap, res);
+    hipLaunchKernelGGL(k_delta_write<Layered<C>>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, d, (const uint32_t *)tiles, out, (uint32_t)cap);
     return (int)hipGetLastError();
 }
 

@@ -53,6 +53,7 @@ struct Rgb {
         Plane *next;                      // the next `shown`, same shape; written by k_delta_write for every covered cell
         int32_t tol;                      // tolerance 0..255
     };
+    using Glyph = FixedGlyph;
     static constexpr uint32_t kNone = 0xffffffffu;                 // no triple equals it
     static constexpr int kEscMax = 7 + 11 + 6 + 11 + 1;            // 36
 
@@ -61,6 +62,12 @@ struct Rgb {
     // RGB8(palette[k]): chexel k / 2 of the 8 x 2 plane, top row for an even k
     static __device__ __forceinline__ uint32_t palette_rgb(const Args &a, int k) { return a.palette[(k & 1) * 8 + (k >> 1)] & kRgbMask; }
     static __device__ __forceinline__ void load_default(const Args &a, uint32_t &fg, uint32_t &bg) { fg = palette_rgb(a, a.dfg); bg = palette_rgb(a, a.dbg); }
+    static __device__ __forceinline__ void store(Plane *p, const Args &a, uint32_t fg, uint32_t bg) { p[0] = fg | 0xff000000u; p[a.fbW] = bg | 0xff000000u; }
+    // layer cell k of the plane the encoder wrote for the layers' cells as a cells x 1 framebuffer: the top row, then the bottom row
+    static __device__ __forceinline__ void layer_load(const Plane *lc, uint32_t cells, uint32_t k, uint32_t &fg, uint32_t &bg)
+    {
+        fg = lc[k] & kRgbMask; bg = lc[(size_t)cells + k] & kRgbMask;
+    }
 
     static __device__ __forceinline__ uint32_t both_bytes(uint32_t fg, uint32_t bg) { return 14u + triple_bytes(fg) + triple_bytes(bg); }
 
@@ -119,4 +126,25 @@ extern "C" int ycge_launch_ansi_rgb_delta(const uint8_t *rgba, const uint8_t *sh
     Rgb::Delta d{};
     d.next = reinterpret_cast<uint32_t *>(next); d.tol = tol;
     return launch_delta<Rgb>(d, rgba, shown, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream);
+}
+
+// the two above with the console's other framebuffers (ycge_ansi_layers.h): the compose pass into L->comp / L->comp_glyph - a cw x 2 ch
+// RGBA plane and cw ch code units - then the stream of that composite; the delta against L->prev (`shown`, same shape) / L->prev_glyph,
+// with L->next, distinct from both, receiving emitted ? cur : shown for every console cell.  Four launches on `stream`.
+extern "C" int ycge_launch_ansi_rgb_layers_stream(const LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                                                  int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len,
+                                                  hipStream_t stream)
+{
+    if (!L) return (int)hipErrorInvalidValue;
+    return launch_layered_stream<Rgb>(*L, rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, clear, tiles, out, cap, out_len, stream);
+}
+
+extern "C" int ycge_launch_ansi_rgb_layers_delta(const LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                                                 int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
+                                                 hipStream_t stream)
+{
+    if (!L || !L->next || L->next == L->prev || L->next == L->comp || ((uintptr_t)L->next & 3u) || tol < 0 || tol > 255) return (int)hipErrorInvalidValue;
+    Rgb::Delta d{};
+    d.next = reinterpret_cast<uint32_t *>(L->next); d.tol = tol;
+    return launch_layered_delta<Rgb>(d, *L, rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream);
 }

@@ -35,6 +35,7 @@
 
 #include "../../include/ycge.h"
 #include "ycge_accel.h"
+#include "ycge_ansi_layers.h"
 #include "ycge_device.h"
 #include "ycge_math.h"
 #include "ycge_own.h"
@@ -113,6 +114,15 @@ int ycge_launch_ansi_rgb_stream(const uint8_t *rgba, int fbW, int fbH, int cw, i
 int ycge_launch_ansi_rgb_delta(const uint8_t *rgba, const uint8_t *shown, uint8_t *next, int fbW, int fbH, int cw, int ch, int vx, int vy,
                                const uint8_t *palette, int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap,
                                unsigned long long *res, hipStream_t stream);
+int ycge_launch_ansi_layers_stream(const ycge_ansi::LayersRun *L, const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                                   int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
+int ycge_launch_ansi_layers_delta(const ycge_ansi::LayersRun *L, const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                                  int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream);
+int ycge_launch_ansi_rgb_layers_stream(const ycge_ansi::LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                                       int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
+int ycge_launch_ansi_rgb_layers_delta(const ycge_ansi::LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
+                                      int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
+                                      hipStream_t stream);
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
 size_t ycge_launch_obj_sizes(int which);
 int ycge_launch_obj_count_lines(const uint8_t *text, uint32_t n, uint32_t first, uint32_t *tiles, void *header, hipStream_t stream);
@@ -391,6 +401,15 @@ struct AnsiRequest {
     int32_t gap = 0, tolerance = 0;
     bool keyframe = false;
 };
+// the console's other framebuffers as the device holds them (ycge_console_set_layers, ycge_ansi.cpp): rect[0..n) bottom first, their cells
+// one behind the other - code units, and the colours as k_encode_chexels wrote them for the cells as a cells x 1 framebuffer, in both forms
+struct LayerStore {
+    int32_t n = 0, raytrace_at = 0;
+    uint32_t cells = 0;
+    ycge_ansi::LayerRect rect[ycge_ansi::kMaxLayers] = {};
+    DevBuf<uint16_t> glyphs;
+    DevBuf<uint8_t> pairs, rgba;                       // 2 bytes a cell; 2 * cells RGBA words, the foregrounds then the backgrounds
+};
 // what the chexel calls of one context hold (ycge_chexel.cpp, ycge_ansi.cpp): filled by the first call
 struct ChexelState {
     bool on = false;                                   // a _chexels or _ansi call is in progress
@@ -423,6 +442,14 @@ struct ChexelState {
     int32_t delta_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // {cw, ch, vx, vy, dfg, dbg, fbW, fbH}
     DevBuf<uint8_t> rgb_palette;                       // RGB8 of the 16 palette colours: the encoder's 8 x 2 RGBA plane of ansi_palette's chexels
     bool rgb_palette_ready = false;
+    // Layers (ycge_console_set_layers): while layers.n > 0 every stream is that of the console-wide composite.  comp_held / glyph_held
+    // [delta_prev] hold the composite the last _delta stream left on the terminal (delta_layered: that stream was a layered one), the call at
+    // hand composes into [1 - delta_prev] and a successful _delta call flips them with delta_held.  A 24-bit delta composes into comp_cur
+    // instead, and its write kernel fills comp_held[1 - delta_prev] with emitted ? cur : shown.  Kept across ycge_resize and ycge_scene_upload.
+    LayerStore layers;
+    DevBuf<uint8_t> comp_held[2], comp_cur;
+    DevBuf<uint16_t> glyph_held[2];
+    bool delta_layered = false;
 };
 // what the video blits of one context hold (ycge_video.cpp): made by the first blit, grow-only; nothing a ray-traced frame reads
 struct VideoState {

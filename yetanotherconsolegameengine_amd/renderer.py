@@ -35,6 +35,36 @@ class _PageLockedOwner:
             pass
 
 
+CHEXEL_DTYPE = np.dtype([("ch", "<u2"), ("pad", "<u2"), ("fg", "<f4", 3), ("bg", "<f4", 3)])          # abi.Chexel as a numpy record, 28 bytes
+
+
+class ConsoleLayer:
+    """A Framebuffer of the console beside the raytrace one (Renderer/Framebuffer.cs) as ycge_console_set_layers takes it: `chars` (h, w)
+    UTF-16 code units - or h strings of w BMP characters - with `fg` and `bg` (h, w, 3) float32 colours (one colour broadcasts), at
+    console position (x, y).  A cell whose character is ' ' is transparent."""
+
+    def __init__(self, chars, fg=(0.75, 0.75, 0.75), bg=(0.0, 0.0, 0.0), x: int = 0, y: int = 0):
+        if len(chars) and isinstance(chars[0], str):
+            chars = [[ord(ch) for ch in row] for row in chars]
+        self.chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        if self.chars.ndim != 2 or self.chars.size == 0:
+            raise ValueError("a layer's characters are an (h, w) array, both positive")
+        self.h, self.w = self.chars.shape
+        self.fg = np.ascontiguousarray(np.broadcast_to(np.asarray(fg, np.float32), (self.h, self.w, 3)))
+        self.bg = np.ascontiguousarray(np.broadcast_to(np.asarray(bg, np.float32), (self.h, self.w, 3)))
+        self.x, self.y = int(x), int(y)
+
+    def cells(self) -> np.ndarray:
+        """the layer's ycge_chexel array, row by row"""
+        c = np.zeros(self.h * self.w, CHEXEL_DTYPE)
+        c["ch"], c["fg"], c["bg"] = self.chars.ravel(), self.fg.reshape(-1, 3), self.bg.reshape(-1, 3)
+        return c
+
+    def as_struct(self) -> "abi.ConsoleLayer":
+        self._cells = self.cells()          # (kept alive for the length of the call that reads it)
+        return abi.ConsoleLayer(self.x, self.y, self.w, self.h, self._cells.ctypes.data_as(C.POINTER(abi.Chexel)))
+
+
 class RaytraceRenderer:
     def __init__(self, scene: Scene | FlatScene, fb_width: int, fb_height: int, fovDeg: float = 45.0, superSample: int = 1, *,
                  cfg: Optional[abi.Config] = None, capture_debug: bool = False, count_work: bool = False, device: int = 0,
@@ -633,6 +663,18 @@ class RaytraceRenderer:
         return self._ansi_call(self.L.ycge_render_frame_ansi_rgb_delta, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
                                rgb=True, delta=(merge_gap, tolerance, bool(keyframe)))
 
+    # ---------------------------------------------------------------- the console's other framebuffers (ycge_console_set_layers)
+    def SetConsoleLayers(self, layers=(), raytrace_at: int = 0):
+        """The console's OTHER framebuffers for every TryFlipAndBlitAnsi* call of this context from now on (ycge_console_set_layers): a
+        sequence of ConsoleLayer in frameBuffers order, bottom first, of which `raytrace_at` lie below the raytrace framebuffer.  The
+        streams are then Render()'s for the whole list - GetChexelForPoint over every framebuffer, any character.  An empty sequence
+        removes the layers.  The cells are copied; a refused call (abi.YcgeError) leaves the previous layers in force."""
+        layers = list(layers)
+        arr = (abi.ConsoleLayer * max(1, len(layers)))()
+        for k, l in enumerate(layers):
+            arr[k] = l.as_struct()
+        self._check(self.L.ycge_console_set_layers(self.ctx, arr if layers else None, len(layers), int(raytrace_at)))
+
     def Wait(self):
         self._check(self.L.ycge_wait(self.ctx))
 
@@ -837,6 +879,10 @@ class VideoRenderer:
             out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self._r.chexel_shapes().items() if want[k]}
         self._r._check(self.L.ycge_video_blit(self.ctx, ptr, w, h, bpp, *RaytraceRenderer._chexel_pointers(out)))
         return out
+
+    def SetConsoleLayers(self, layers=(), raytrace_at: int = 0):
+        """RaytraceRenderer.SetConsoleLayers on the shared context: one console, whichever renderer shows on it"""
+        self._r.SetConsoleLayers(layers, raytrace_at)
 
     def _ansi_call(self, export, frame, *args, **kwargs):
         """RaytraceRenderer._ansi_call on this context with `frame` ahead of the console: a video call carries no frame statistics"""
