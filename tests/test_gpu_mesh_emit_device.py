@@ -236,15 +236,21 @@ def _upload(flat, monkeypatch, emit_host, env=()):
     return out
 
 
-def _same_upload(flat, monkeypatch, env, label):
-    da, dtl, dm, dst, dbvh = _upload(flat, monkeypatch, False, env)
-    ha, htl, hm, hst, hbvh = _upload(flat, monkeypatch, True, env)
-    assert hst["device_meshes"] == 0 and hst["host_meshes"] == 4 and hst["last_device_emit_us"] == 0, hst
-    assert dst["device_meshes"] == 4 and dst["host_meshes"] == 0, dst
+def _same_arena(d, h, label):
+    """two uploads (_upload's tuples) hold the same arena: size, treelet offset, GMesh records, every byte"""
+    (da, dtl, dm, dst, _), (ha, htl, hm, hst, _) = d, h
     assert dst["arena_bytes"] == hst["arena_bytes"] == len(ha) == len(da), (label, dst, hst)
     assert dtl == htl, f"{label}: treelets at {dtl}, host {htl}"
     assert np.array_equal(dm, hm), f"{label}: GMesh records differ"
     assert np.array_equal(da, ha), f"{label}: {int((da != ha).sum())} bytes of the arena differ, the first at {int(np.flatnonzero(da != ha)[0])}"
+
+
+def _same_upload(flat, monkeypatch, env, label):
+    d, h = _upload(flat, monkeypatch, False, env), _upload(flat, monkeypatch, True, env)
+    (da, dtl, dm, dst, dbvh), hst = d, h[3]
+    assert hst["device_meshes"] == 0 and hst["host_meshes"] == 4 and hst["last_device_emit_us"] == 0, hst
+    assert dst["device_meshes"] == 4 and dst["host_meshes"] == 0, dst
+    _same_arena(d, h, label)
     return da, dtl, dm, dbvh
 
 
@@ -262,6 +268,51 @@ def test_host_built_and_device_built_trees_in_one_device_arena(product_lib, monk
     flat = _four_mesh_flat()
     arena, tl, meshes, bvh = _same_upload(flat, monkeypatch, (("YCGE_MESH_BVH_DEVICE_MIN", "1000"),), "DEVICE_MIN 1000")
     assert bvh["device_builds"] == 1 and bvh["host_builds"] == 3, bvh
+
+
+def _declined_flat(with_a_built_mesh):
+    """Mesh 0: 40 identical triangles, which the device builder declines under YCGE_MESH_BVH_WIDE_MIN=9 (Array.Sort at a wide node:
+    MESH_BVH_SORT_NO_SPLIT, test_gpu_mesh_bvh_device_build.py); mesh 1, on request: 500 drawn triangles, which it builds."""
+    rng = np.random.default_rng(4)
+    s = Scene()
+    s.Ambient = AmbientLight(vec3(1, 1, 1), 0.3)
+    same40 = np.tile(f32([[[1, 2, 3], [2, 2, 3], [1, 3, 3]]]), (40, 1, 1))
+    s.Add(Mesh(same40, Material(vec3(0.8, 0.3, 0.2), 0.1, 0.0, ZERO)))
+    if with_a_built_mesh:
+        s.Add(Mesh(_tris(rng.uniform((-2.5, 0.2, -6), (-0.5, 2, -4), (500, 3)), 0.1, rng), Material(vec3(0.2, 0.5, 0.8), 0.1, 0.0, ZERO)))
+    s.Add(Box(vec3(-6, -0.2, -9), vec3(6, 0.0, 0), Solid(vec3(0.6, 0.6, 0.6)), 0.1, 0.0))
+    s.Lights.append(PointLight(vec3(0, 5, -2), vec3(1, 1, 1), 80.0))
+    s.BackgroundTop, s.BackgroundBottom = vec3(0.5, 0.7, 1.0), vec3(0.9, 0.95, 1.0)
+    return flatten(s), same40
+
+
+DECLINING = (("YCGE_MESH_BVH_DEVICE_MIN", "1"), ("YCGE_MESH_BVH_WIDE_MIN", "9"))
+
+
+def test_a_tree_the_builder_declined_in_a_device_made_arena(product_lib, monkeypatch):
+    """The builder declines mesh 0 inside an upload and builds mesh 1: the host's tree of mesh 0 is uploaded and joins the arena the
+    device writes (mesh_emit_add, built = false) - the bytes of the same upload under YCGE_MESH_EMIT_HOST=1."""
+    flat, _ = _declined_flat(True)
+    d, h = _upload(flat, monkeypatch, False, DECLINING), _upload(flat, monkeypatch, True, DECLINING)
+    print("device emit:", d[3], d[4], "host emit:", h[3], h[4])
+    assert d[4]["device_builds"] == 1 and d[4]["host_fallbacks"] == 1, d[4]
+    assert d[3]["device_meshes"] == 2 and d[3]["host_meshes"] == 0, d[3]
+    assert h[3]["device_meshes"] == 0 and h[3]["host_meshes"] == 2 and h[3]["last_device_emit_us"] == 0, h[3]
+    _same_arena(d, h, "a declined tree beside a built one")
+
+
+def test_every_mesh_worth_the_device_emit_declined(product_lib, monkeypatch):
+    """The builder declines the only mesh: no tree of the upload is on the device, the host writes the whole arena - what it writes
+    under YCGE_MESH_EMIT_HOST=1, and what ycge_host_mesh_arena_treelets lays out for the same triangles."""
+    flat, same40 = _declined_flat(False)
+    assert flat.meshes[0].material == 0          # (the hook below emits material 0)
+    d, h = _upload(flat, monkeypatch, False, DECLINING), _upload(flat, monkeypatch, True, DECLINING)
+    print("device emit:", d[3], d[4], "host emit:", h[3], h[4])
+    assert d[4]["host_fallbacks"] == 1 and d[4]["device_builds"] == 0, d[4]
+    assert d[3]["device_meshes"] == 0 and d[3]["host_meshes"] == 1 and d[3]["last_device_emit_us"] == 0, d[3]
+    _same_arena(d, h, "the only mesh declined")
+    hb, hroot, htl = _host(product_lib, same40)
+    assert d[1] == htl and np.array_equal(d[0], hb) and d[2][0, 6] == hroot, "the upload's arena against the hook's"
 
 
 def test_no_treelets_without_the_cooperative_walk(product_lib, monkeypatch):

@@ -521,7 +521,7 @@ def test_tables_that_no_object_uses(product_lib, oracle, path, debug):
     """Found by the drawn call sequences (round 6, seed 2204: `Memory access fault by GPU` in the timed k_trace): every mesh and voxel entity LEFT
     Scene.Objects (ycge_scene_update_objects with analytic objects only) while the scene's tables - the last upload's - still list three meshes and
     a grid.  The objects were then `analytic_only`, the context still `has_grid`, and a walk tree installed beside that flag sent the non-counting
-    kernel out of bounds (install_walk_tree, csrc/ycge_host.cpp: now only with a grid OBJECT).  Here: the entities leave, come back, leave again;
+    kernel out of bounds (install_walk_tree, csrc/ycge_scene.cpp: now only with a grid OBJECT).  Here: the entities leave, come back, leave again;
     and a scene is UPLOADED whose tables list a mesh and a grid nothing uses - on the timed instances (debug False) and the counting ones."""
     s, pose = random_scene(3)          # three meshes, a voxel volume, 230 analytic objects
     assert sum(isinstance(o_, Mesh) for o_ in s.Objects) == 3 and sum(isinstance(o_, VolumeGrid) for o_ in s.Objects) == 1

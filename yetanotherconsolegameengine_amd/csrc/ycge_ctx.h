@@ -1,6 +1,8 @@
 // ycge_ctx.h - the context of the library (struct ycge_ctx), the launch entry points of the kernel files, and what the host translation
 // units share (internal: the C-ABI is include/ycge.h).
-//   ycge_host.cpp      context (creation, teardown order), scene flattening and upload, host buffers, read-outs
+//   ycge_host.cpp      context (creation, teardown order), geometry, copy_out / quiesce, the exception barrier, host buffers, general hooks
+//   ycge_scene.cpp     scene flattening and upload as named steps, scene updates, the object installs
+//   ycge_mesh_bvh.cpp  mesh trees (device builder or host builder) and the mesh arena (device emit or host emit), their hooks
 //   ycge_frame.cpp     frame orchestration (TryFlipAndBlit steps 1-5 and 9), frames in flight, the slab form of the tiled frame
 //   ycge_post_host.cpp the post stage (steps 6-8) and its schedules
 //   ycge_resident.cpp  the tile-resident multi-GPU form, its batched launches and emulation loop; read-backs (ycge_read_buffer / _accel)
@@ -327,8 +329,6 @@ struct MeshBvhReport {
     double us = 0.0;                   // items kernel to the tree in host memory
     hipError_t error = hipSuccess;
 };
-// YCGE_OK: `out` is build_tree(triangle_items(tris9), TreeFlavour::Mesh); 1: not built, rep.fallback says why; YCGE_ERR_*: rep.error
-int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int wide_min, hipStream_t stream, BuiltTree &out, MeshBvhReport &rep);
 
 // The arena of an upload assembled on the device (ycge_mesh_bvh.cpp drives the kernels of ycge_mesh_emit.hip): per mesh what the kernels read -
 // the buffers of the device-side build taken over from its scratch, or a host-built tree uploaded - and the references of all meshes' nodes.
@@ -352,11 +352,17 @@ struct MeshEmit {
 };
 // mesh `mi` of the upload: built == true takes S.tris / S.nodes / S.leaf of the build that has just made `t`, else `t`, its leaf order and the triangles are uploaded
 hipError_t mesh_emit_add(MeshEmit &E, size_t mi, bool built, MeshBvhScratch &S, const BuiltTree &t, const float *tris9, int32_t n_tris, const int32_t *tri_material, int32_t material);
-hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t stream);            // every mesh's layout; hdr_host on return (stage: the builder's page-locked staging)
-// the gap behind the rec_units units of records and the treelet region zeroed, every mesh's records, the treelets (tl_offset != 0); hdr_host on return
-hipError_t mesh_emit_write(MeshEmit &E, uint8_t *arena, uint32_t rec_units, size_t total_bytes, uint32_t tl_offset, int32_t n_materials, bool timed, PinnedBuf &stage, hipStream_t stream);
-// where the treelet region of an arena of rec_bytes of records starts (0: none, append_treelets' conditions) and where the arena then ends
-uint32_t mesh_arena_treelet_offset(size_t rec_bytes, bool any_root_is_a_node, size_t &total_bytes);
+// the builder's scratch and the emit's inputs of ONE upload: kept from mesh to mesh, given back however the upload ends
+struct MeshUploadScratch { MeshBvhScratch &s; MeshEmit &e; ~MeshUploadScratch() { s.release(); e.release(); } };
+// One mesh's tree by the builder ycge_scene_upload picks: the device's (the same tree byte for byte) from YCGE_MESH_BVH_DEVICE_MIN triangles on - or always, when asked -
+// and the host's below that, under YCGE_MESH_BVH_HOST and for what the device builder declines (rep.fallback).  on_device: S holds the tree's triangles, nodes and leaf order.
+int build_mesh_tree(const Knobs &knobs, bool always_try_device, MeshBvhScratch &S, const float *tris9, int32_t n, hipStream_t stream, BuiltTree &t, bool &on_device, MeshBvhReport &rep);
+// The arena of an upload's meshes - records in mesh order, then the treelets unless no_coop - written by the host from the trees (gmeshes[].root_ref), or by the device from
+// E's inputs into d_arena at its exact size (root_refs).  YCGE_OK or the error, its text in msg; the three refusals both share are worded in mesh_refusal alone.
+int emit_arena_on_host(const std::vector<MeshHost> &trees, const ycge_mesh *meshes, int n_materials, bool no_coop, std::vector<uint8_t> &arena, std::vector<GMesh> &gmeshes, uint32_t &tl_offset, std::string &msg);
+int emit_arena_on_device(MeshEmit &E, PinnedBuf &stage, DevBuf<uint8_t> &d_arena, int n_materials, bool no_coop, bool timed, hipStream_t stream, std::vector<uint32_t> &root_refs, uint32_t &tl_offset, std::string &msg);
+enum MeshRefusal { MESH_LEAF_ABOVE_15 = 0, MESH_TRI_MATERIAL = 1, MESH_ARENA_FULL = 2 };
+int mesh_refusal(MeshRefusal why, int mesh, std::string &msg);          // the refusal's code, its text into msg
 
 // The resident voxel grids of a scene (ycge_grid_encode.cpp): the grids of the last ycge_scene_upload keep their indices and its packing;
 // ycge_scene_attach_grids takes the lowest free index, a block of the cell arena (size-keyed free list, 256-byte alignment, else the end of
@@ -761,8 +767,11 @@ struct ycge_ctx {
 #define YCGE_FLIGHT_RING 1024u       // frames in flight whose trace launches keep their timing events (ycge_async_trace_times)
 
 extern "C" void ycge_peer_worker_main(ycge_ctx *root, ycge_ctx *peer);      // ycge_frame.cpp: a peer device's thread (ycge_create starts it)
-// ---- what the other translation units of the library call in ycge_host.cpp (defined there, in this namespace)
+// ---- what the other translation units of the library call in ycge_host.cpp and ycge_scene.cpp (defined there, in this namespace)
 namespace ycge_host {
+struct H3 { float x, y, z; };
+H3 h_norm(H3 a);                // ycge_host.cpp: a / |a| (a zero vector stays)
+int morton3(int x, int y, int z);          // ycge_host.cpp: a voxel's place in its 8 x 8 x 8 brick (VolumeGrid.cs:246-252)
 // where a trace of the tile-resident form writes and which schedule it follows (trace_frame's last argument)
 struct ResidentTarget {
     ycge_ctx::ResidentSet *set;
@@ -807,11 +816,19 @@ int fill_stats(ycge_ctx *c, ycge_frame_stats *st, const FrameState &fs, bool did
 int quiesce(ycge_ctx *c);
 inline std::vector<ycge_ctx *> contexts_of(ycge_ctx *c) { std::vector<ycge_ctx *> v{c}; v.insert(v.end(), c->peers.begin(), c->peers.end()); return v; }          // root, then peers
 inline int quiesce_all(ycge_ctx *c) { for (ycge_ctx *x : contexts_of(c)) { const int rc = quiesce(x); if (rc != YCGE_OK) return rc; } return YCGE_OK; }
+// one step on the root, then on each peer: stops at the first failure, and a peer's error text is the root's (the caller reads it there)
+template <class Step> int on_root_then_peers(ycge_ctx *c, Step step)
+{
+    int rc = step(c);
+    for (ycge_ctx *p : c->peers) { if (rc != YCGE_OK) break; rc = step(p); if (rc != YCGE_OK) c->err = p->err; }
+    return rc;
+}
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 inline double us_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
 // the calling thread's current device goes back to the root's on every way out (a failed step on a peer's device included)
 struct DeviceGuard { int device; explicit DeviceGuard(int d) : device(d) {} ~DeviceGuard() { (void)hipSetDevice(device); } };
 void release_resident(ycge_ctx *c);
+int alloc_tile_buffers(ycge_ctx *c);          // ycge_host.cpp: queue segments, hit records, spill columns (for c->spill_levels) and schedules of the owned tiles
 void snapshot_frame(ycge_ctx *c, FrameState &fs);
 void schedule_policy(const ycge_ctx *c, uint32_t &policy, uint32_t &split_top, int resident_ring = 0, bool batched = false);
 int scene_is_flat(const ycge_ctx *c);
@@ -819,7 +836,7 @@ bool frame_is_single_launch(const ycge_ctx *c);
 bool should_reset_history(const ycge_ctx *c, const float pos[3], float yaw, float pitch);
 void fill_frame_params(ycge_ctx *c, ycge::FrameParams &P, int64_t frame, const float pos[3], float yaw, float pitch, float fov_deg);
 int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, bool timed, hipEvent_t launch_begin = nullptr, hipEvent_t launch_end = nullptr, const ResidentTarget *rt = nullptr);
-int validate_grid(const ycge_grid &g, int gi, int n_materials, std::string &msg);          // ycge_host.cpp: one grid's argument checks
+int validate_grid(const ycge_grid &g, int gi, int n_materials, std::string &msg);          // ycge_scene.cpp: one grid's argument checks
 void grid_record_init(const ycge_grid &g, GGrid &G);                                       // ... its record from the arguments (clamps, cull_t_limit)
 void grid_record_solid(GGrid &G, const int lo[3], const int hi[3], uint64_t brick_mask);   // ... and from the solid voxels' index box
 std::array<float, 6> grid_world_bounds(const ycge_grid &g);

@@ -1,6 +1,6 @@
 // ycge_frame.cpp - frame orchestration behind the C-ABI (include/ycge.h): TryFlipAndBlit steps 1-5 and 9 (RaytraceRenderer.cs:159-218, 266) as
 // trace_frame / taa_and_commit, the one-process multi-device frame (peer push or the RCCL all-gather), frames in flight, the slab form of the tiled frame.
-// (Context, scene flattening and upload: ycge_host.cpp.  Steps 6-8 - the post stage - and its schedules: ycge_post_host.cpp.  The tile-resident form: ycge_resident.cpp.)
+// (Context: ycge_host.cpp.  Scene flattening and upload: ycge_scene.cpp.  Steps 6-8 - the post stage - and its schedules: ycge_post_host.cpp.  The tile-resident form: ycge_resident.cpp.)
 #include "ycge_ctx.h"
 
 namespace ycge_host {

@@ -1,7 +1,9 @@
 // ycge_mesh_bvh.cpp - the host side of the device-side mesh BVH build (kernels: ycge_mesh_bvh_build.hip): scratch, the level loop over
-// the wide nodes, the read-back of the tree into a BuiltTree - and of the arena assembled on the device behind it (kernels: ycge_mesh_emit.hip).  ycge_scene_upload (ycge_host.cpp)
-// picks the builder per mesh, and the two hooks tests and profiles hold the builder by live there too; whatever this builder declines - Array.Sort at a wide node, a non-finite coordinate, a tree
-// deeper than the reference accepts - the host builder of ycge_accel.cpp builds, and it is the one that words the errors.
+// the wide nodes, the read-back of the tree into a BuiltTree - and of the arena assembled on the device behind it (kernels: ycge_mesh_emit.hip),
+// with the host's emit beside it (emit_mesh_records, append_treelets).  build_mesh_tree is the choice of builder ycge_scene_upload
+// (ycge_scene.cpp) makes per mesh: whatever the device builder declines - Array.Sort at a wide node, a non-finite coordinate, a tree deeper
+// than the reference accepts - the host builder of ycge_accel.cpp builds, and it is the one that words the errors.  The hooks tests and
+// profiles hold the builders and the two emits by live at the end of the file.
 #include "ycge_ctx.h"
 
 namespace ycge_host {
@@ -26,7 +28,8 @@ hipError_t staged_read(PinnedBuf &stage, void *dst, const void *src, size_t byte
 
 } // namespace
 
-int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int wide_min, hipStream_t stream, BuiltTree &out, MeshBvhReport &rep)
+// YCGE_OK: `out` is the host builder's tree of tris9, byte for byte; 1: not built, rep.fallback says why; YCGE_ERR_*: rep.error
+static int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int wide_min, hipStream_t stream, BuiltTree &out, MeshBvhReport &rep)
 {
     out = BuiltTree{};
     rep = MeshBvhReport{};
@@ -91,13 +94,44 @@ int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int 
     return YCGE_OK;
 }
 
+// the host builder (MeshBVH ctor, MeshBVH.cs:41-130; ycge_accel.cpp)
+static void host_mesh_tree(const float *tris9, int32_t n, BuiltTree &t)
+{
+    BoundsSoA items;
+    triangle_items(tris9, n, items);
+    build_tree(items, TreeFlavour::Mesh, t);
+}
+
+int build_mesh_tree(const Knobs &knobs, bool always_try_device, MeshBvhScratch &S, const float *tris9, int32_t n, hipStream_t stream, BuiltTree &t, bool &on_device, MeshBvhReport &rep)
+{
+    rep = MeshBvhReport{};
+    on_device = always_try_device || (!knobs.mesh_bvh_host && n >= 1 && n >= knobs.mesh_bvh_device_min);
+    if (on_device) {
+        const int rc = mesh_bvh_build_device(S, tris9, n, knobs.mesh_bvh_wide_min, stream, t, rep);
+        if (rc < 0) return rc;
+        on_device = rc == YCGE_OK;
+    }
+    if (!on_device) host_mesh_tree(tris9, n, t);
+    return YCGE_OK;
+}
+
+// a tree into a hook's arrays (nodes_out: 2 n records of 40 bytes, leaf_out: n, stats_out: {root, depth, Array.Sort cases} or null); the node count
+static int tree_out(const BuiltTree &t, void *nodes_out, int32_t *leaf_out, int32_t *stats_out)
+{
+    if (!t.nodes.empty()) std::memcpy(nodes_out, t.nodes.data(), t.nodes.size() * sizeof(RefNode));
+    if (!t.leaf_index.empty()) std::memcpy(leaf_out, t.leaf_index.data(), t.leaf_index.size() * 4);
+    if (stats_out) { stats_out[0] = t.root; stats_out[1] = t.max_depth; stats_out[2] = t.sort_fallbacks; }
+    return (int)t.nodes.size();
+}
+
 // ---- the arena on the device (ycge_mesh_emit.hip) ----------------------------------------------------------------------------------
 
 namespace {
 enum { EH_UNITS = 0, EH_MESH0 = 4, EH_MESH_WORDS = 4 };      // = ycge_mesh_emit.hip
 }
 
-uint32_t mesh_arena_treelet_offset(size_t rec_bytes, bool any_root_is_a_node, size_t &total_bytes)
+// where the treelet region of an arena of rec_bytes of records starts (0: none, append_treelets' conditions) and where the arena then ends
+static uint32_t mesh_arena_treelet_offset(size_t rec_bytes, bool any_root_is_a_node, size_t &total_bytes)
 {
     const size_t n_units = rec_bytes / 32;
     const size_t t0 = (rec_bytes + 511) & ~(size_t)511;
@@ -134,7 +168,8 @@ hipError_t mesh_emit_add(MeshEmit &E, size_t mi, bool built, MeshBvhScratch &S, 
     return e;
 }
 
-hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t stream)
+// every mesh's layout; hdr_host on return (stage: the builder's page-locked staging)
+static hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t stream)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_hdr = EH_MESH0 + EH_MESH_WORDS * E.in.size();
@@ -161,7 +196,8 @@ hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t stream)
     return e;
 }
 
-hipError_t mesh_emit_write(MeshEmit &E, uint8_t *arena, uint32_t rec_units, size_t total_bytes, uint32_t tl_offset, int32_t n_materials, bool timed, PinnedBuf &stage, hipStream_t stream)
+// the gap behind the rec_units units of records and the treelet region zeroed, every mesh's records, the treelets (tl_offset != 0); hdr_host on return
+static hipError_t mesh_emit_write(MeshEmit &E, uint8_t *arena, uint32_t rec_units, size_t total_bytes, uint32_t tl_offset, int32_t n_materials, bool timed, PinnedBuf &stage, hipStream_t stream)
 {
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](double &us) { const auto t1 = std::chrono::steady_clock::now(); us = std::chrono::duration<double, std::micro>(t1 - t0).count(); t0 = t1; };
@@ -184,4 +220,363 @@ hipError_t mesh_emit_write(MeshEmit &E, uint8_t *arena, uint32_t rec_units, size
     return e;
 }
 
+// ---- the arena of an upload: the host's emit, the device's, and what both refuse ----------------------------------------------------
+
+int mesh_refusal(MeshRefusal why, int mesh, std::string &msg)
+{
+    static const struct { int code; const char *text; } refusals[] = {{YCGE_ERR_UNSUPPORTED, "mesh %d: a leaf of more than 15 triangles"},
+                                                                      {YCGE_ERR_INVALID_ARG, "mesh %d: triangle material out of range"},
+                                                                      {YCGE_ERR_UNSUPPORTED, "mesh records exceed the 1 GB arena"}};
+    char buf[96];
+    std::snprintf(buf, sizeof buf, refusals[why].text, mesh);
+    msg = buf;
+    return refusals[why].code;
+}
+
+// A mesh's device records appended to the arena (32-byte units): depth-first - an internal node (GNode, both child boxes),
+// then its left child's records (a leaf's triangle pair records or the whole left subtree), then the right child's - so a
+// walk's next fetch is usually the next cache line.  Returns the root reference (ycge_device.h).
+static uint32_t emit_mesh_records(const BuiltTree &t, const float *tris9, const int32_t *tri_material, int32_t material, int n_materials,
+                                  std::vector<uint8_t> &arena, bool &bad_leaf, bool &bad_material)
+{
+    if (t.root < 0) return YCGE_REF_NONE_VALUE;
+    std::function<uint32_t(int32_t)> emit = [&](int32_t ni) -> uint32_t {
+        const RefNode &nd = t.nodes[(size_t)ni];
+        const uint32_t unit = (uint32_t)(arena.size() / 32);
+        if (nd.count > 0) {
+            if (nd.count > 15) { bad_leaf = true; return YCGE_REF_NONE_VALUE; }
+            const uint32_t n_rec = ((uint32_t)nd.count + 1u) / 2u;
+            arena.resize(arena.size() + (size_t)n_rec * sizeof(GTriPair), 0);        // an odd leaf's last slot stays all zeros
+            for (int32_t k = 0; k < nd.count; k++) {
+                const int32_t ti = t.leaf_index[(size_t)(nd.start + k)];
+                const float *v = tris9 + 9 * (size_t)ti;
+                uint8_t *rec = arena.data() + (size_t)unit * 32 + (size_t)(k / 2) * sizeof(GTriPair);
+                GTriPair g;
+                std::memcpy(&g, rec, sizeof g);
+                const int sl = k & 1;
+                g.ax[sl] = v[0]; g.ay[sl] = v[1]; g.az[sl] = v[2];
+                g.e1x[sl] = v[3] - v[0]; g.e1y[sl] = v[4] - v[1]; g.e1z[sl] = v[5] - v[2];        // MeshBVH.cs:87-91
+                g.e2x[sl] = v[6] - v[0]; g.e2y[sl] = v[7] - v[1]; g.e2z[sl] = v[8] - v[2];
+                g.orig[sl] = ti;
+                g.material[sl] = tri_material ? tri_material[ti] : material;
+                if (g.material[sl] < 0 || g.material[sl] >= n_materials) bad_material = true;
+                std::memcpy(rec, &g, sizeof g);
+            }
+            return YCGE_REF(REF_MESH_LEAF, (unit << 4) | (uint32_t)nd.count);
+        }
+        arena.resize(arena.size() + sizeof(GNode), 0);
+        GNode g;
+        std::memset(&g, 0, sizeof g);
+        const RefNode &L = t.nodes[(size_t)nd.left];
+        const RefNode &R = t.nodes[(size_t)nd.right];
+        g.lmin_x = L.mn[0]; g.lmin_y = L.mn[1]; g.lmin_z = L.mn[2]; g.lmax_x = L.mx[0]; g.lmax_y = L.mx[1]; g.lmax_z = L.mx[2];
+        g.rmin_x = R.mn[0]; g.rmin_y = R.mn[1]; g.rmin_z = R.mn[2]; g.rmax_x = R.mx[0]; g.rmax_y = R.mx[1]; g.rmax_z = R.mx[2];
+        g.lref = emit(nd.left);
+        g.rref = emit(nd.right);
+        std::memcpy(arena.data() + (size_t)unit * 32, &g, sizeof g);
+        return YCGE_REF(REF_MESH_NODE, unit << 4);
+    };
+    return emit(t.root);
+}
+
+
+// Treelets of every internal mesh node (GTreeSlot, ycge_device.h), appended to the arena: a pure function of the records above.
+// Returns the region's byte offset, 0 when there is nothing to build or 32-bit offsets would not reach its end.
+static uint32_t append_treelets(std::vector<uint8_t> &arena, const std::vector<GMesh> &gmeshes)
+{
+    bool any = false;
+    for (const GMesh &m : gmeshes) any |= YCGE_REF_KIND(m.root_ref) == REF_MESH_NODE && m.root_ref != YCGE_REF_NONE_VALUE;
+    size_t total = 0;
+    const size_t t0 = mesh_arena_treelet_offset(arena.size(), any, total);          // (shared with the arena assembled on the device: the same answer)
+    if (t0 == 0) return 0;
+    arena.resize(total, 0);
+    auto node_at = [&](uint32_t ref) { GNode g; std::memcpy(&g, arena.data() + (size_t)((ref & 0x1ffffff0u) >> 4) * 32, sizeof g); return g; };
+    std::vector<uint32_t> todo;
+    for (const GMesh &m : gmeshes) if (m.root_ref != YCGE_REF_NONE_VALUE && YCGE_REF_KIND(m.root_ref) == REF_MESH_NODE) todo.push_back(m.root_ref);
+    while (!todo.empty()) {
+        const uint32_t ref = todo.back(); todo.pop_back();
+        const uint32_t unit = (ref & 0x1ffffff0u) >> 4;
+        GTreeSlot slots[YCGE_TL_SLOTS];
+        std::memset(slots, 0, sizeof slots);
+        // fill(b, parent record): slots 2b+2 / 2b+3 from the record of the node in slot b (b = -1: the treelet's own node)
+        std::function<void(int, const GNode &, int)> fill = [&](int b, const GNode &g, int depth) {
+            const int l = 2 * b + 2, r = l + 1;
+            slots[l].mn[0] = g.lmin_x; slots[l].mn[1] = g.lmin_y; slots[l].mn[2] = g.lmin_z; slots[l].mx_x = g.lmax_x; slots[l].mx_y = g.lmax_y; slots[l].mx_z = g.lmax_z;
+            slots[r].mn[0] = g.rmin_x; slots[r].mn[1] = g.rmin_y; slots[r].mn[2] = g.rmin_z; slots[r].mx_x = g.rmax_x; slots[r].mx_y = g.rmax_y; slots[r].mx_z = g.rmax_z;
+            slots[l].ref = g.lref; slots[r].ref = g.rref; slots[l].valid = slots[r].valid = 1;
+            if (depth < 3)
+                for (int c : {l, r})
+                    if (YCGE_REF_KIND(slots[c].ref) == REF_MESH_NODE) fill(c, node_at(slots[c].ref), depth + 1);
+        };
+        const GNode g = node_at(ref);
+        fill(-1, g, 1);
+        std::memcpy(arena.data() + t0 + (size_t)unit * YCGE_TL_BYTES_PER_UNIT, slots, sizeof slots);
+        if (YCGE_REF_KIND(g.lref) == REF_MESH_NODE) todo.push_back(g.lref);
+        if (YCGE_REF_KIND(g.rref) == REF_MESH_NODE) todo.push_back(g.rref);
+    }
+    return (uint32_t)t0;
+}
+
+// The host writes the arena: every mesh's records in mesh order, then the treelets
+int emit_arena_on_host(const std::vector<MeshHost> &trees, const ycge_mesh *meshes, int n_materials, bool no_coop, std::vector<uint8_t> &arena, std::vector<GMesh> &gmeshes,
+                       uint32_t &tl_offset, std::string &msg)
+{
+    for (size_t mi = 0; mi < trees.size(); mi++) {
+        const ycge_mesh &m = meshes[mi];
+        bool bad_material = false, bad_leaf = false;
+        gmeshes[mi].root_ref = emit_mesh_records(trees[mi].tree, m.triangles, m.tri_material, m.material, n_materials, arena, bad_leaf, bad_material);
+        if (bad_leaf) return mesh_refusal(MESH_LEAF_ABOVE_15, (int)mi, msg);
+        if (bad_material) return mesh_refusal(MESH_TRI_MATERIAL, (int)mi, msg);
+        if (arena.size() / 32 >= (1u << 25)) return mesh_refusal(MESH_ARENA_FULL, (int)mi, msg);
+    }
+    tl_offset = no_coop ? 0u : append_treelets(arena, gmeshes);
+    return YCGE_OK;
+}
+
+// The arena of the meshes E holds, assembled on the device: layout, the refusals of the host's emit, the allocation at its exact size,
+// records, treelets
+int emit_arena_on_device(MeshEmit &E, PinnedBuf &stage, DevBuf<uint8_t> &d_arena, int n_materials, bool no_coop, bool timed, hipStream_t stream, std::vector<uint32_t> &root_refs,
+                         uint32_t &tl_offset, std::string &msg)
+{
+    char buf[256];
+    auto hip_bad = [&](const char *what, hipError_t e) {
+        (void)hipGetLastError();
+        std::snprintf(buf, sizeof buf, "%s failed: %s", what, hipGetErrorString(e)); msg = buf;
+        return e == hipErrorOutOfMemory ? YCGE_ERR_OUT_OF_MEMORY : YCGE_ERR_DEVICE;
+    };
+    hipError_t e = mesh_emit_layout(E, stage, stream);
+    if (e != hipSuccess) return hip_bad("the mesh record layout", e);
+    const size_t n = E.in.size();
+    root_refs.assign(n, YCGE_REF_NONE_VALUE);
+    uint64_t units = 0;
+    bool any_node_root = false;
+    for (size_t mi = 0; mi < n; mi++) {
+        const MeshEmit::Input &I = E.in[mi];
+        const uint32_t *h = E.hdr_host.data() + 4 + 4 * mi;          // {units, a leaf above 15 triangles, a material out of range, 0}
+        if (h[1]) return mesh_refusal(MESH_LEAF_ABOVE_15, (int)mi, msg);
+        if (I.n_nodes != 0) {
+            if (units < (1u << 25)) root_refs[mi] = I.root_count > 0 ? YCGE_REF(REF_MESH_LEAF, ((uint32_t)units << 4) | (uint32_t)I.root_count) : YCGE_REF(REF_MESH_NODE, (uint32_t)units << 4);
+            any_node_root |= I.root_count == 0;
+        }
+        units += h[0];
+        if (units >= (1u << 25)) return mesh_refusal(MESH_ARENA_FULL, (int)mi, msg);
+    }
+    if (units != E.hdr_host[0]) { msg = "the mesh record layout disagrees with its own total"; return YCGE_ERR_INTERNAL; }
+    size_t total = 0;
+    tl_offset = no_coop ? 0u : mesh_arena_treelet_offset((size_t)units * 32, any_node_root, total);
+    if (tl_offset == 0) total = (size_t)units * 32;
+    if ((e = d_arena.alloc(total)) != hipSuccess) return hip_bad("the mesh arena's allocation", e);
+    if (total == 0) return YCGE_OK;
+    if ((e = mesh_emit_write(E, d_arena.p, (uint32_t)units, total, tl_offset, n_materials, timed, stage, stream)) != hipSuccess) return hip_bad("the mesh records on the device", e);
+    for (size_t mi = 0; mi < n; mi++)
+        if (E.hdr_host[4 + 4 * mi + 2]) return mesh_refusal(MESH_TRI_MATERIAL, (int)mi, msg);
+    return YCGE_OK;
+}
+
+// a hook's read of what c's device holds at src, into dst (null: nothing to read) once the device is idle
+static int read_idle_device(ycge_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!dst || bytes == 0) return YCGE_OK;
+    HIP_TRY(c, hipDeviceSynchronize());
+    return copy_out(c, dst, src, bytes);
+}
+
+// one mesh (single material 0) through the host builder and the host's emit, treelets on request; the arena's size, its bytes when they fit
+static int host_arena_of_one_mesh(const float *tris9, int32_t n, bool treelets, void *out, int64_t capacity_bytes, uint32_t *root_ref_out, uint32_t *tl_offset_out)
+{
+    std::vector<MeshHost> trees(1);
+    host_mesh_tree(tris9, n, trees[0].tree);
+    ycge_mesh m;
+    std::memset(&m, 0, sizeof m);
+    m.triangles = tris9; m.n_triangles = n;
+    std::vector<uint8_t> arena;
+    std::vector<GMesh> gmeshes(1, GMesh{});
+    std::string msg;
+    uint32_t tl_offset = 0;
+    const int rc = emit_arena_on_host(trees, &m, 1, !treelets, arena, gmeshes, tl_offset, msg);
+    *root_ref_out = gmeshes[0].root_ref;
+    if (rc != YCGE_OK) return YCGE_ERR_UNSUPPORTED;
+    if (tl_offset_out) *tl_offset_out = tl_offset;
+    if (out && (int64_t)arena.size() <= capacity_bytes && !arena.empty()) std::memcpy(out, arena.data(), arena.size());
+    return (int)arena.size();
+}
+
 } // namespace ycge_host
+
+// ---- the hooks of the mesh path (tests and profiles hold the builders and the two emits by them) ------------------------------------------
+extern "C" {
+
+// test hook, no context: the builder alone on the current device, with ycge_scene_upload's answer to what it declines (the host builds
+// the mesh).  nodes_out: 2 n records of 40 bytes, leaf_out: n.  res16: {depth, Array.Sort cases, wide nodes, subtree workgroups, fallback
+// reason (MESH_BVH_*, 0 = built on the device), 1 = built on the device, wide levels, microseconds of the device build}.  Returns the node
+// count; YCGE_ERR_NO_DEVICE_CODE without a device, nothing written.  YCGE_MESH_BVH_WIDE_MIN is read at every call.
+int ycge_debug_device_mesh_bvh(const float *tris9, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *res16)
+try {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { (void)hipGetLastError(); return YCGE_ERR_NO_DEVICE_CODE; }
+    if (n < 0 || !res16 || (n > 0 && (!tris9 || !nodes_out || !leaf_out))) return YCGE_ERR_INVALID_ARG;
+    Knobs knobs;
+    knobs.read();
+    MeshBvhScratch scratch;
+    MeshBvhReport rep;
+    BuiltTree t;
+    bool on_device = false;
+    const int rc = build_mesh_tree(knobs, true, scratch, tris9, n, nullptr, t, on_device, rep);
+    if (rc < 0) return rc;
+    for (int k = 0; k < 16; k++) res16[k] = 0u;
+    res16[0] = (uint32_t)t.max_depth; res16[1] = (uint32_t)t.sort_fallbacks; res16[2] = (uint32_t)rep.wide_nodes; res16[3] = (uint32_t)rep.jobs;
+    res16[4] = (uint32_t)rep.fallback; res16[5] = on_device ? 1u : 0u; res16[6] = (uint32_t)rep.levels; res16[7] = (uint32_t)rep.us;
+    return tree_out(t, nodes_out, leaf_out, nullptr);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// test / profiling hook: how ycge_scene_upload built the mesh BVHs - {device builds, host builds, host builds after the device builder
+// declined (counted in host builds too), microseconds of the last device build (items kernel to the tree in host memory), and of the last
+// upload: Array.Sort cases, deepest tree, wide nodes, subtree workgroups}.  Without a context: YCGE_ERR_INVALID_ARG, and out8[0..2] = the
+// three knobs as the environment gives them now (YCGE_MESH_BVH_HOST, _DEVICE_MIN, _WIDE_MIN after its clamp) - host only, no device.
+int ycge_debug_mesh_bvh_stats(ycge_ctx *c, int64_t *out8)
+try {
+    if (!out8) return YCGE_ERR_INVALID_ARG;
+    if (!c) {
+        Knobs knobs;
+        knobs.read();
+        for (int k = 0; k < 8; k++) out8[k] = 0;
+        out8[0] = knobs.mesh_bvh_host ? 1 : 0; out8[1] = knobs.mesh_bvh_device_min; out8[2] = knobs.mesh_bvh_wide_min;
+        return YCGE_ERR_INVALID_ARG;
+    }
+    out8[0] = c->mesh_bvh_device_builds; out8[1] = c->mesh_bvh_host_builds; out8[2] = c->mesh_bvh_host_fallbacks; out8[3] = (int64_t)c->mesh_bvh_last_us;
+    out8[4] = c->mesh_bvh_sorts; out8[5] = c->mesh_bvh_depth; out8[6] = c->mesh_bvh_wide_nodes; out8[7] = c->mesh_bvh_jobs;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hook, no context: the twin of ycge_host_mesh_arena_treelets on the current device - the tree (the device builder, or the
+// host's tree uploaded when that declines), then the kernels of ycge_mesh_emit.hip; single material 0.  Returns the arena's size, the bytes
+// in `out` when they fit.  res8: {1 = tree built on the device, nodes, units of records, us of the layout, of the records, of the treelets
+// (each with its wait), 0, 0}.  YCGE_ERR_NO_DEVICE_CODE without a device, nothing written.  YCGE_MESH_BVH_WIDE_MIN and YCGE_NO_COOP are read at every call.
+int ycge_debug_device_mesh_arena(const float *tris9, int32_t n, void *out, int64_t capacity_bytes, uint32_t *root_ref_out, uint32_t *tl_offset_out, uint32_t *res8)
+try {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { (void)hipGetLastError(); return YCGE_ERR_NO_DEVICE_CODE; }
+    if (n < 0 || (n > 0 && !tris9) || !root_ref_out || !tl_offset_out) return YCGE_ERR_INVALID_ARG;
+    Knobs knobs;
+    knobs.read();
+    MeshBvhScratch scratch;
+    MeshEmit E;
+    MeshBvhReport rep;
+    BuiltTree t;
+    bool on_device = false;
+    const int rc = build_mesh_tree(knobs, true, scratch, tris9, n, nullptr, t, on_device, rep);
+    if (rc < 0) return rc;
+    on_device = on_device && n > 0;
+    if (mesh_emit_add(E, 0, on_device, scratch, t, tris9, n, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); return YCGE_ERR_DEVICE; }
+    DevBuf<uint8_t> d_arena;
+    std::vector<uint32_t> root_refs;
+    std::string msg;
+    *tl_offset_out = 0;
+    const int erc = emit_arena_on_device(E, scratch.stage, d_arena, 1, knobs.no_coop, true, nullptr, root_refs, *tl_offset_out, msg);
+    if (erc != YCGE_OK) return erc == YCGE_ERR_INVALID_ARG ? YCGE_ERR_UNSUPPORTED : erc;          // (as the host twin answers a bad leaf or material)
+    *root_ref_out = root_refs[0];
+    if (d_arena.n > (size_t)0x7fffffff) return YCGE_ERR_UNSUPPORTED;
+    if (out && (int64_t)d_arena.n <= capacity_bytes && d_arena.n) {          // (through page-locked staging: the device writes no caller memory)
+        const hipError_t e = staged_read(scratch.stage, out, d_arena.p, d_arena.n, nullptr);
+        if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? YCGE_ERR_OUT_OF_MEMORY : YCGE_ERR_DEVICE; }
+    }
+    if (res8) {
+        for (int k = 0; k < 8; k++) res8[k] = 0u;
+        res8[0] = on_device ? 1u : 0u; res8[1] = (uint32_t)t.nodes.size(); res8[2] = E.hdr_host.empty() ? 0u : E.hdr_host[0];
+        res8[3] = (uint32_t)E.us[0]; res8[4] = (uint32_t)E.us[1]; res8[5] = (uint32_t)E.us[2];
+    }
+    return (int)d_arena.n;
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// test hook: the arena the context's device holds (records, then the treelet region at *tl_offset_out, 0 = none), whichever side wrote it.
+// Returns its size; the bytes go to dst when they fit.
+int ycge_debug_read_mesh_arena(ycge_ctx *c, void *dst, int64_t capacity_bytes, uint32_t *tl_offset_out)
+try {
+    if (!c || !tl_offset_out) return YCGE_ERR_INVALID_ARG;
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    *tl_offset_out = c->sd.tl_offset;
+    const size_t bytes = c->d_mesh_arena.p ? c->d_mesh_arena.n : 0;
+    if (bytes > (size_t)0x7fffffff) return c->fail(YCGE_ERR_UNSUPPORTED, "the arena is larger than this hook returns");
+    const int rc = read_idle_device(c, (int64_t)bytes <= capacity_bytes ? dst : nullptr, c->d_mesh_arena.p, bytes);
+    return rc != YCGE_OK ? rc : (int)bytes;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: the GMesh records (32 bytes each: root box, root reference) the context's device holds; returns how many
+int ycge_debug_read_meshes(ycge_ctx *c, void *dst, int32_t capacity_meshes)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    const size_t n = c->d_meshes.p ? c->d_meshes.n : 0;
+    const int rc = read_idle_device(c, n <= (size_t)(capacity_meshes > 0 ? capacity_meshes : 0) ? dst : nullptr, c->d_meshes.p, n * sizeof(GMesh));
+    return rc != YCGE_OK ? rc : (int)n;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hook: who wrote the arena of the last upload - {meshes whose records the device wrote, meshes whose records the host
+// wrote, microseconds of the device's layout + records + treelets (0: the host wrote them), the arena's bytes}.  Without a context:
+// YCGE_ERR_INVALID_ARG, and out4[0..1] = YCGE_MESH_EMIT_HOST and YCGE_MESH_EMIT_DEVICE_MIN as the environment gives them now (host only).
+int ycge_debug_mesh_emit_stats(ycge_ctx *c, int64_t *out4)
+try {
+    if (!out4) return YCGE_ERR_INVALID_ARG;
+    if (!c) {
+        Knobs knobs;
+        knobs.read();
+        out4[0] = knobs.mesh_emit_host ? 1 : 0; out4[1] = knobs.mesh_emit_device_min; out4[2] = out4[3] = 0;
+        return YCGE_ERR_INVALID_ARG;
+    }
+    out4[0] = c->mesh_emit_dev_meshes; out4[1] = c->mesh_emit_host_meshes; out4[2] = (int64_t)c->mesh_emit_last_us; out4[3] = c->mesh_emit_arena_bytes;
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ---- host-only helpers exported for the `-m "not gpu"` tests (no device needed) -------------
+// Build a tree over caller-supplied boxes with the product builder: bounds = n*6 (min xyz, max xyz),
+// centroids = n*3.  flavour 0 = scene, 1 = mesh.  Outputs are malloc'ed by the caller:
+// nodes_out must hold 2*n records of 10 x 4 B, leaf_out n int32.  Returns node count or <0.
+int ycge_host_build_tree(const float *bounds, const float *centroids, int32_t n, int32_t flavour, void *nodes_out, int32_t *leaf_out,
+                         int32_t *stats_out /* [root, max_depth, sort_fallbacks] */)
+try {
+    if (n < 0 || (n > 0 && (!bounds || !centroids || !nodes_out || !leaf_out))) return YCGE_ERR_INVALID_ARG;
+    BoundsSoA it;
+    it.resize(n);
+    for (int i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++) { it.mn[a][i] = bounds[6 * i + a]; it.mx[a][i] = bounds[6 * i + 3 + a]; it.c[a][i] = centroids[3 * i + a]; }
+    BuiltTree t;
+    build_tree(it, flavour == 0 ? TreeFlavour::Scene : TreeFlavour::Mesh, t);
+    return tree_out(t, nodes_out, leaf_out, stats_out);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// Same for a triangle soup (MeshBVH ctor path incl. TryComputeBounds).
+int ycge_host_build_mesh(const float *tris9, int32_t n, void *nodes_out, int32_t *leaf_out, int32_t *stats_out)
+try {
+    if (n < 0 || (n > 0 && (!tris9 || !nodes_out || !leaf_out))) return YCGE_ERR_INVALID_ARG;
+    BuiltTree t;
+    host_mesh_tree(tris9, n, t);
+    return tree_out(t, nodes_out, leaf_out, stats_out);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// test hook: the device records of one mesh (single material 0) as emit_mesh_records lays them out
+int ycge_host_mesh_arena(const float *tris9, int32_t n, void *out, int64_t capacity_bytes, uint32_t *root_ref_out)
+try {
+    if (n < 0 || (n > 0 && !tris9) || !root_ref_out) return YCGE_ERR_INVALID_ARG;
+    return host_arena_of_one_mesh(tris9, n, false, out, capacity_bytes, root_ref_out, nullptr);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// ... with the treelet region of the cooperative walk appended (append_treelets): returns the total size, *tl_offset_out = where it starts
+int ycge_host_mesh_arena_treelets(const float *tris9, int32_t n, void *out, int64_t capacity_bytes, uint32_t *root_ref_out, uint32_t *tl_offset_out)
+try {
+    if (n < 0 || (n > 0 && !tris9) || !root_ref_out || !tl_offset_out) return YCGE_ERR_INVALID_ARG;
+    return host_arena_of_one_mesh(tris9, n, true, out, capacity_bytes, root_ref_out, tl_offset_out);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+} // extern "C"
+

@@ -1,6 +1,6 @@
 // ycge_mesh_emit.hip - a mesh's device records and the cooperative walk's treelets, written on the device (host side: ycge_mesh_bvh.cpp).
 //
-// ycge_scene_upload's emit_mesh_records (ycge_host.cpp) is a depth-first recursion over a tree whose nodes are numbered in pre-order, left
+// The host's emit_mesh_records (ycge_mesh_bvh.cpp) is a depth-first recursion over a tree whose nodes are numbered in pre-order, left
 // before right: the record of node i lies behind the records of the nodes 0 .. i - 1.  With a record's size in 32-byte units - 2 for an
 // internal node (GNode), 3 * ((count + 1) / 2) for a leaf (GTriPair records) - a node's unit is the arena's units before the mesh plus the
 // exclusive prefix sum of the sizes, and every record is a function of its own node, its two children and the leaf's triangles.  Per mesh,

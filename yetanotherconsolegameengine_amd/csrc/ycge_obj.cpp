@@ -2,7 +2,7 @@
 // takes (ycge_obj_parse_host, ycge_obj_parse, _read, _triangles, _release; kernels: ycge_obj.hip; the reading rules, the token routines
 // and the host parser: ycge_obj.h), and MeshScenes.AddMeshAutoGround on the held OBJ (ycge_obj_ground_host, ycge_obj_ground,
 // ycge_obj_triangles_auto_ground; kernels: ycge_obj_ground.hip; the contract and the host tail: ycge_obj.h).  The entry points themselves
-// stand in ycge_host.cpp, beside ycge_scene_upload.
+// stand in ycge_host.cpp, thin wrappers behind the exception barrier.
 //
 // A parse is: the text up (through page-locked staging when the caller's array is pageable), the lines marked and counted, one read-back
 // of the line count; the line table, each line's kind, two scans, one read-back of the position and triangle counts; the tokens parsed
