@@ -98,6 +98,22 @@ int ycge_test_video_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32
 int ycge_test_post_stage(ycge_ctx *c, const float *hist, const float *albedo, const float *normal, const float *depth, const uint8_t *sky, float ae_in,
                          float *denoised_out, float *sdr_out, uint32_t *state_out);
 int ycge_test_exposure(ycge_ctx *c, const float *terms, int64_t n, float ae_in, int32_t serial, uint32_t *state_out);
+/* ---- TemporalBlendWithClamp (csrc/ycge_resident.cpp, kernels csrc/ycge_kernels.hip) on caller-given planes of w x h pixels: current / normal /
+ * hist_in / prev_normal 3 f32 a pixel, depth / prev_depth f32, sky / prev_sky u8 holding 0 or 1; taa_alpha, taa_clamp_radius, taa_luminance_pad the
+ * raw config values (TaaParams is derived as for a frame); reset != 0 the history restart.  form: 0 k_taa with guide outputs of their own, 1 the
+ * guide inputs are the outputs, 2 no guide outputs (normal_out / depth_out / sky_out: the given normal / depth / sky as the device holds them),
+ * 3 form 0 in the one-wavefront workgroups of frames in flight, 4 k_scatter_halo + k_taa_tiles, 5 k_resolve_tiles.  Forms 0-3: any w x h, a
+ * one-device context, slab_out unused (may be NULL).  Forms 4-5: the context's own hiW x hiH as its rank of world_size, taa_clamp_radius <= 1;
+ * the halo records are gathered from the caller's full frame over this rank's receive list, then every pixel of another rank is poisoned in
+ * the planes TAA reads; outputs hold the inputs wherever this rank owns nothing; slab_out: the bytes of a history slab, zeros where no pixel is.
+ * Buffers of its own: the context's history, guides, planes, taa_valid and committed camera are untouched, and so is what an existing ring
+ * of the tile-resident form holds - but forms 4-5 CREATE that ring and the halo lists on a context that has none yet, as its first
+ * tile-resident call would (a device synchronise, the ring's allocations, cleared cost and schedule words).  Refused:
+ * frames in flight, a peer or multi-device context, and for forms 0-3 a rank of several */
+int ycge_test_taa(ycge_ctx *c, int32_t form, int32_t reset, int32_t w, int32_t h, const float *current, const float *normal, const float *depth,
+                  const uint8_t *sky, const float *hist_in, const float *prev_normal, const float *prev_depth, const uint8_t *prev_sky, float taa_alpha,
+                  int32_t taa_clamp_radius, float taa_luminance_pad, float *hist_out, float *normal_out, float *depth_out, uint8_t *sky_out,
+                  float *slab_out);
 
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */

@@ -1015,6 +1015,33 @@ int orc_exposure_probe(const float *terms, int64_t n, float *state_io)
     state_io[0] = tone.ae_exposure; state_io[1] = tone.effective; state_io[2] = log_sum;
     return cnt;
 }
+/* probe of step 5 on caller-supplied buffers: Renderer::temporal_blend itself on a renderer of w x h trace pixels (given directly: hiH of a
+ * real renderer is always even).  current / normal / hist_in / prev_normal = w*h*3 f32, depth / prev_depth = w*h f32, sky / prev_sky = w*h u8;
+ * the three config values raw; out: the history and the guides after the call */
+int orc_taa_probe(int w, int h, int reset, const float *current, const float *normal, const float *depth, const uint8_t *sky, const float *hist_in,
+                  const float *prev_normal, const float *prev_depth, const uint8_t *prev_sky, float taa_alpha, int taa_clamp_radius, float taa_luminance_pad,
+                  float *hist_out, float *normal_out, float *depth_out, uint8_t *sky_out)
+{
+    if (w <= 0 || h <= 0 || !current || !normal || !depth || !sky || !hist_in || !prev_normal || !prev_depth || !prev_sky || !hist_out || !normal_out ||
+        !depth_out || !sky_out) return YCGE_ERR_INVALID_ARG;
+    Renderer r;
+    ycge_config cfg{};
+    cfg.taa_alpha = taa_alpha; cfg.taa_clamp_radius = taa_clamp_radius; cfg.taa_luminance_pad = taa_luminance_pad;
+    r.cfg = cfg;
+    r.hiW = w; r.hiH = h;
+    const size_t n = (size_t)w * h;
+    r.current.resize(n); r.g_normal.resize(n); r.taa_hist.resize(n); r.prev_normal.resize(n);
+    r.g_depth.resize(n); r.prev_depth.resize(n); r.sky.resize(n); r.prev_sky.resize(n);
+    static_assert(sizeof(orc::V3) == 12, "three binary32");
+    std::memcpy(r.current.data(), current, n * 12); std::memcpy(r.g_normal.data(), normal, n * 12); std::memcpy(r.g_depth.data(), depth, n * 4);
+    std::memcpy(r.sky.data(), sky, n); std::memcpy(r.taa_hist.data(), hist_in, n * 12); std::memcpy(r.prev_normal.data(), prev_normal, n * 12);
+    std::memcpy(r.prev_depth.data(), prev_depth, n * 4); std::memcpy(r.prev_sky.data(), prev_sky, n);
+    r.taa_valid = true;
+    (void)r.temporal_blend(reset != 0);
+    std::memcpy(hist_out, r.taa_hist.data(), n * 12); std::memcpy(normal_out, r.prev_normal.data(), n * 12);
+    std::memcpy(depth_out, r.prev_depth.data(), n * 4); std::memcpy(sky_out, r.prev_sky.data(), n);
+    return YCGE_OK;
+}
 /* analysis aid: re-trace the last rendered frame and report, per pixel, the traversal steps of each of its first
  * `per_pixel` Scene.Hit calls in call order (primary, shadow rays of vertex 1, bounce, shadow rays of vertex 2, ...) */
 int orc_query_profile2(void *ctx, uint32_t *out, uint32_t *out2, int per_pixel);

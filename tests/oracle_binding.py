@@ -77,6 +77,8 @@ def lib() -> C.CDLL:
         L.orc_post_probe_sums.argtypes = [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6
         L.orc_exposure_probe.restype = C.c_int
         L.orc_exposure_probe.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.orc_taa_probe.restype = C.c_int
+        L.orc_taa_probe.argtypes = [C.c_int] * 3 + [C.c_void_p] * 8 + [C.c_float, C.c_int, C.c_float] + [C.c_void_p] * 4
         _lib = L
     return _lib
 
@@ -110,6 +112,21 @@ def exposure_probe(terms, ae_in=1.0):
     cnt = L.orc_exposure_probe(t.ctypes.data, t.size, st.ctypes.data)
     assert cnt >= 0, cnt
     return dict(ae_exposure=st[0], effective=st[1], log_sum=st[2], count=int(cnt))
+
+
+def taa_probe(reset, current, normal, depth, sky, hist_in, prev_normal, prev_depth, prev_sky, taa_alpha=0.01, taa_clamp_radius=1, taa_luminance_pad=0.10):
+    """Step 5 of TryFlipAndBlit (orc_taa_probe: Renderer::temporal_blend) on h x w planes, the size read off `depth`, with the raw config values:
+    dict(hist, prev_normal, prev_depth, prev_sky) after the call - the shape RaytraceRenderer.taa_probe returns."""
+    L = lib()
+    h, w = np.shape(depth)
+    n = h * w
+    arrs = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((current, np.float32), (normal, np.float32), (depth, np.float32), (sky, np.uint8), (hist_in, np.float32),
+                                                            (prev_normal, np.float32), (prev_depth, np.float32), (prev_sky, np.uint8))]
+    assert [a.size for a in arrs] == [3 * n, 3 * n, n, n, 3 * n, 3 * n, n, n], ([a.size for a in arrs], w, h)
+    out = dict(hist=np.zeros((h, w, 3), np.float32), prev_normal=np.zeros((h, w, 3), np.float32), prev_depth=np.zeros((h, w), np.float32), prev_sky=np.zeros((h, w), np.uint8))
+    _check(L, None, L.orc_taa_probe(w, h, int(bool(reset)), *[a.ctypes.data for a in arrs], float(taa_alpha), int(taa_clamp_radius), float(taa_luminance_pad),
+                                    *[out[k].ctypes.data for k in ("hist", "prev_normal", "prev_depth", "prev_sky")]))
+    return out
 
 
 NODE_DTYPE = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"), ("count", "<i4")])

@@ -604,48 +604,63 @@ def render_frame(L, scene, hiW, hiH, pose, frame, salt=0x9E3779B97F4A7C15):
 def luma(c): return f32(f32(f32(f32(0.2126) * c[0]) + f32(f32(0.7152) * c[1])) + f32(f32(0.0722) * c[2]))
 
 
-def temporal_blend(state, cur, normal, depth, sky, force_reset, alpha=0.01, radius=1, pad=0.10):
-    """TemporalBlendWithClamp, RaytraceRenderer.cs:274-398.  state: dict with hist / prev_normal / prev_depth / prev_sky or empty."""
+TAA_ALPHA_KEPT, TAA_ALPHA_SKY, TAA_ALPHA_DEPTH_NONFINITE, TAA_ALPHA_REL, TAA_ALPHA_NDOT = range(5)
+TAA_CLAMP_NONE, TAA_CLAMP_ABOVE, TAA_CLAMP_BELOW = range(3)
+
+
+def temporal_blend(state, cur, normal, depth, sky, force_reset, alpha=0.01, radius=1, pad=0.10, branches=None):
+    """TemporalBlendWithClamp, RaytraceRenderer.cs:274-398.  state: dict with hist / prev_normal / prev_depth / prev_sky or empty.
+    alpha, radius, pad: the raw config values.  branches (a dict, optional) receives per pixel which way the call went: `alpha` = why the
+    local alpha is what it is (TAA_ALPHA_*: the sky flags differ, a non-finite depth, rel, ndot alone, or the configured alpha was kept), `clamp`
+    (TAA_CLAMP_*: the history's luminance left alone, scaled down from above l_max, scaled up from below l_min), `taps` = the window's
+    taps with the pixel's own sky flag (clamped taps counted as often as the loop meets them).  A reset leaves it empty."""
     H, W = depth.shape
     if not state or force_reset:
         state.update(hist=cur.copy(), prev_normal=normal.copy(), prev_depth=depth.copy(), prev_sky=sky.copy())
         return state["hist"]
     alpha = fmax(f32(0), fmin(f32(1), f32(alpha)))
+    radius = radius if radius > 0 else 0
     hist = state["hist"]
+    if branches is not None:
+        branches.update(alpha=np.zeros((H, W), np.int8), clamp=np.zeros((H, W), np.int8), taps=np.zeros((H, W), np.int32))
     for y in range(H):
         for x in range(W):
             c, prev = cur[y, x], hist[y, x].copy()
-            la = alpha
+            la, why = alpha, TAA_ALPHA_KEPT
             if bool(sky[y, x]) != bool(state["prev_sky"][y, x]):
-                la = f32(1)
+                la, why = f32(1), TAA_ALPHA_SKY
             else:
                 zn, zp = depth[y, x], state["prev_depth"][y, x]
                 nn, npv = V(*normal[y, x]).normalized(), V(*state["prev_normal"][y, x]).normalized()
                 if not np.isfinite(zn) or not np.isfinite(zp):
-                    la = f32(1)
+                    la, why = f32(1), TAA_ALPHA_DEPTH_NONFINITE
                 else:
                     rel = f32(f32(abs(f32(zn - zp))) / fmax(f32(1e-4), fmin(zn, zp)))
                     if rel > f32(0.05) or nn.dot(npv) < f32(0.8):
-                        la = f32(1)
-            mn_l, mx_l = f32(np.inf), f32(-np.inf)
+                        la, why = f32(1), (TAA_ALPHA_REL if rel > f32(0.05) else TAA_ALPHA_NDOT)
+            mn_l, mx_l, taps = f32(np.inf), f32(-np.inf), 0
             for oy in range(-radius, radius + 1):
                 sy = min(max(y + oy, 0), H - 1)
                 for ox_ in range(-radius, radius + 1):
                     sx = min(max(x + ox_, 0), W - 1)
                     if sky[sy, sx] != sky[y, x]:
                         continue
+                    taps += 1
                     l = luma(cur[sy, sx])
                     if l < mn_l: mn_l = l
                     if l > mx_l: mx_l = l
             rng_ = f32(mx_l - mn_l)
             l_min, l_max = f32(mn_l - f32(rng_ * f32(pad))), f32(mx_l + f32(rng_ * f32(pad)))
             pl = luma(prev)
+            clamp = TAA_CLAMP_NONE
             if pl > l_max:
-                sc = f32(l_max / fmax(f32(1e-6), pl)); prev = np.array([prev[0] * sc, prev[1] * sc, prev[2] * sc], f32)
+                sc = f32(l_max / fmax(f32(1e-6), pl)); prev = np.array([prev[0] * sc, prev[1] * sc, prev[2] * sc], f32); clamp = TAA_CLAMP_ABOVE
             elif pl < l_min:
-                sc = f32(l_min / fmax(f32(1e-6), pl)); prev = np.array([prev[0] * sc, prev[1] * sc, prev[2] * sc], f32)
+                sc = f32(l_min / fmax(f32(1e-6), pl)); prev = np.array([prev[0] * sc, prev[1] * sc, prev[2] * sc], f32); clamp = TAA_CLAMP_BELOW
             ia = f32(f32(1.0) - la)
             hist[y, x] = [f32(f32(prev[0] * ia) + f32(c[0] * la)), f32(f32(prev[1] * ia) + f32(c[1] * la)), f32(f32(prev[2] * ia) + f32(c[2] * la))]
+            if branches is not None:
+                branches["alpha"][y, x], branches["clamp"][y, x], branches["taps"][y, x] = why, clamp, taps
     state.update(prev_normal=normal.copy(), prev_depth=depth.copy(), prev_sky=sky.copy())
     return hist
 

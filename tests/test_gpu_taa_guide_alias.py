@@ -6,6 +6,7 @@ guide_prev_*).  Every other frame form still copies, and a context may change fo
 per trace path - go through sequences of frames that change form, size, scene, frame counter and pose, and after EVERY frame the TAA
 history, the guides (YCGE_BUF_PREV_*) and the frame's own planes (YCGE_BUF_G_NORMAL / G_DEPTH / SKY_MASK) are compared with the oracle bit
 for bit.  YCGE_TAA_COPY_GUIDES=1 (the copying path, kept for A/B) must give the same bits.
+(These sequences hold the guide HANDLING; the value edges of the blend itself - thresholds, non-finite and degenerate inputs - are held by the TAA probe, tests/test_gpu_taa_probe.py.)
 
 Shapes: the smallest at which this can go wrong - frames that are no whole number of 32 x 8 tiles, more than one tile in both directions.
 """

@@ -324,6 +324,12 @@ POST_HOOK_PROTOTYPES = {
     "ycge_test_exposure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
 }
 POST_STATE_WORDS = 6
+# test hook of TemporalBlendWithClamp on caller-given planes (csrc/ycge_resident.cpp), bound where it is used (RaytraceRenderer.taa_probe): form, reset,
+# w, h, the eight input planes, taa_alpha, taa_clamp_radius, taa_luminance_pad, history / normal / depth / sky out, the history slab (tile forms) or None
+TAA_HOOK_PROTOTYPES = {
+    "ycge_test_taa": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 8 + [C.c_float, C.c_int32, C.c_float] + [C.c_void_p] * 5),
+}
+TAA_FORM_PLANES, TAA_FORM_IN_PLACE, TAA_FORM_KEEP_PLANES, TAA_FORM_IN_FLIGHT, TAA_FORM_SCATTER_TILES, TAA_FORM_RESOLVE_TILES = range(6)
 # test hooks of Video mode (csrc/ycge_video.cpp), bound where they are used (renderer.video_tables / VideoRenderer.blit_probe)
 VIDEO_HOOK_PROTOTYPES = {
     "ycge_host_video_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

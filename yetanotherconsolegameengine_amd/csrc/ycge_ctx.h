@@ -806,6 +806,19 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
              hipEvent_t before_copy = nullptr /* recorded in front of the read-back: the exposure state is this frame's */, bool second_sdr = false,
              hipEvent_t tone_wait = nullptr /* the frame before has left its exposure state: waited for in front of this frame's exposure step */, bool second_set = false);
 int join_async(ycge_ctx *c);
+// TemporalBlendWithClamp's parameters from the raw config values (RaytraceRenderer.cs:218, :305): every TAA launch - the frames', the
+// tile-resident resolve's, ycge_test_taa's - is handed what this makes
+inline ycge::TaaParams taa_params(int w, int h, float taa_alpha, int taa_clamp_radius, float taa_luminance_pad, bool reset)
+{
+    ycge::TaaParams T;
+    T.w = w; T.h = h;
+    T.alpha = cs_max(0.0f, cs_min(1.0f, taa_alpha));      // :305
+    T.radius = taa_clamp_radius > 0 ? taa_clamp_radius : 0;
+    T.pad_lum = taa_luminance_pad;
+    T.reset = reset ? 1 : 0;
+    return T;
+}
+int check_post_probe(ycge_ctx *c, const char *fn, bool any_rank = false);       // ycge_post_host.cpp: who may be probed (any_rank: a rank of several too)
 int guides_keep(ycge_ctx *c, bool *swapped = nullptr);       // in front of anything that writes g_normal / g_depth / sky: the last resolved frame's guides are not among them afterwards
 void guides_unkeep(ycge_ctx *c);              // ... undone: the frame failed, the names stay with the last frame that was rendered
 int guides_copying(ycge_ctx *c, ycge::TaaGuides &in, ycge::TaaGuidesOut &out);       // the guide arguments of a TAA launch of the copying forms (call guides_copied behind the launch)

@@ -268,12 +268,8 @@ int trace_frame(ycge_ctx *c, float *d_slab, hipStream_t stream, FrameState &fs, 
 void taa_decide(ycge_ctx *c, FrameState &fs, TaaParams &T, bool &did_reset)
 {
     fs.reset = should_reset_history(c, fs.pos, fs.yaw, fs.pitch) || c->has_dynamic_textures;      // step 2 (:171): this frame's pose against the last committed one; a scene with live textures restarts every frame
-    T.w = c->hiW; T.h = c->hiH;
-    T.alpha = cs_max(0.0f, cs_min(1.0f, c->cfg.taa_alpha));      // :305
-    T.radius = c->cfg.taa_clamp_radius > 0 ? c->cfg.taa_clamp_radius : 0;
-    T.pad_lum = c->cfg.taa_luminance_pad;
     did_reset = !c->taa_valid || fs.reset;                        // :285
-    T.reset = did_reset ? 1 : 0;
+    T = taa_params(c->hiW, c->hiH, c->cfg.taa_alpha, c->cfg.taa_clamp_radius, c->cfg.taa_luminance_pad, did_reset);
 }
 // TAA's guide planes (ycge_ctx.h: guide_prev_*).  guides_keep: the planes named g_normal / g_depth / sky are about to be written - if they
 // hold the last resolved frame's guides, the second set takes the names (a swap of names: nothing is copied).

@@ -358,18 +358,17 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
     return YCGE_OK;
 }
 
-} // namespace ycge_host
-
-namespace {
-// who may be probed: a context that renders whole frames by itself, with nothing queued on it
-int check_post_probe(ycge_ctx *c, const char *fn)
+// who may be probed: a context that renders whole frames by itself, with nothing queued on it (any_rank: or its own tiles of them -
+// ycge_test_taa's tile forms)
+int check_post_probe(ycge_ctx *c, const char *fn, bool any_rank)
 {
     if (c->parent || !c->peers.empty() || c->exchange_mode == YCGE_EXCHANGE_RCCL) return c->fail(YCGE_ERR_INVALID_ARG, "%s: a one-device context only (this one is a peer or drives peers)", fn);
-    if (c->cfg.world_size != 1) return c->fail(YCGE_ERR_INVALID_ARG, "%s: a one-device context only (this one is rank %d of %d)", fn, c->cfg.rank, c->cfg.world_size);
+    if (!any_rank && c->cfg.world_size != 1) return c->fail(YCGE_ERR_INVALID_ARG, "%s: a one-device context only (this one is rank %d of %d)", fn, c->cfg.rank, c->cfg.world_size);
     if (c->async_outstanding || !c->pending.empty()) return c->fail(YCGE_ERR_INVALID_ARG, "%s: frames are in flight on this context (ycge_wait first)", fn);
     return YCGE_OK;
 }
-} // namespace
+
+} // namespace ycge_host
 
 extern "C" {
 

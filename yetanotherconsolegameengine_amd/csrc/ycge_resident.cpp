@@ -309,13 +309,8 @@ try {
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_scatter_halo launch failed: %s", hipGetErrorString((hipError_t)e));
     }
     fs.reset = should_reset_history(c, fs.pos, fs.yaw, fs.pitch) || c->has_dynamic_textures;
-    TaaParams T;
-    T.w = c->hiW; T.h = c->hiH;
-    T.alpha = cs_max(0.0f, cs_min(1.0f, c->cfg.taa_alpha));
-    T.radius = c->cfg.taa_clamp_radius > 0 ? c->cfg.taa_clamp_radius : 0;
-    T.pad_lum = c->cfg.taa_luminance_pad;
     const bool did_reset = !c->taa_valid || fs.reset;
-    T.reset = did_reset ? 1 : 0;
+    const TaaParams T = taa_params(c->hiW, c->hiH, c->cfg.taa_alpha, c->cfg.taa_clamp_radius, c->cfg.taa_luminance_pad, did_reset);
     FrameParams P;
     fill_frame_params(c, P, fs.frame, fs.pos, fs.yaw, fs.pitch, fs.fov);
     TaaGuides prev_in; TaaGuidesOut prev_out;
@@ -357,6 +352,103 @@ try {
     const int e = ycge_launch_unpack_history((const float *)d_all_history_slabs, (size_t)c->tiles_per_rank_padded * 256 * 3, c->hiW, c->hiH, c->tiles_x, c->n_tiles, c->cfg.world_size, c->taa_hist.p, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_unpack_history launch failed: %s", hipGetErrorString((hipError_t)e));
     return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: TemporalBlendWithClamp's kernels alone on caller-given planes (w x h; current / normal / hist_in / prev_normal 3 f32 a pixel, depth /
+// prev_depth f32, sky / prev_sky u8 of 0 or 1), through the launchers and the TaaParams derivation the frames use.  form: 0 k_taa with
+// guide outputs of their own, 1 with the guide inputs as outputs, 2 with none (normal / depth / sky come back: the planes a keep-planes frame
+// reads next), 3 form 0 in one-wavefront workgroups, 4 k_scatter_halo + k_taa_tiles, 5 k_resolve_tiles.  Forms 0-3: any w x h, a one-device
+// context.  Forms 4-5: this context's own hiW x hiH as its rank of world_size, guides in place, slab_out (ycge_history_slab_bytes; zeros where
+// no pixel is) - the records are gathered by k_gather_halo over this rank's receive list from the caller's full frame, and every pixel
+// of another rank is then poisoned in what TAA reads (sky flag inverted, colour 1e30): a tap that reads the plane where it should read a
+// record shows.  Stateless: buffers of its own on the context's device and stream; history, guides, planes, ring contents, taa_valid and
+// the committed camera stay as they are (forms 4-5 make the context's halo lists and ring exist, as any tile-resident call does).
+int ycge_test_taa(ycge_ctx *c, int32_t form, int32_t reset, int32_t w, int32_t h, const float *current, const float *normal, const float *depth, const uint8_t *sky,
+                  const float *hist_in, const float *prev_normal, const float *prev_depth, const uint8_t *prev_sky, float taa_alpha, int32_t taa_clamp_radius,
+                  float taa_luminance_pad, float *hist_out, float *normal_out, float *depth_out, uint8_t *sky_out, float *slab_out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!current || !normal || !depth || !sky || !hist_in || !prev_normal || !prev_depth || !prev_sky || !hist_out || !normal_out || !depth_out || !sky_out)
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_taa: a NULL array");
+    if (form < 0 || form > 5) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_taa: unknown form %d (0..5)", form);
+    if (w < 1 || h < 1 || (int64_t)w * h > ((int64_t)1 << 26)) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_taa: bad size %d x %d", w, h);
+    const bool tiles = form >= 4;
+    { const int rc = check_post_probe(c, "ycge_test_taa", tiles); if (rc != YCGE_OK) return rc; }
+    if (tiles) {
+        if (w != c->hiW || h != c->hiH) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_taa: form %d runs on the context's own %d x %d trace grid, not %d x %d", form, c->hiW, c->hiH, w, h);
+        if (taa_clamp_radius > 1) return c->fail(YCGE_ERR_UNSUPPORTED, "the tile-resident form exchanges a one-pixel halo: taa_clamp_radius %d needs ycge_resolve_gathered", taa_clamp_radius);
+        if (!slab_out) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_taa: a NULL array");
+        const int rc = ensure_resident(c);
+        if (rc != YCGE_OK) return rc;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)w * h;
+    const TaaParams T = taa_params(w, h, taa_alpha, taa_clamp_radius, taa_luminance_pad, reset != 0);
+    DevBuf<float> d_cur, d_nrm, d_dep, d_hist, d_pn, d_pd, d_on, d_od, d_full_cur, d_slab;
+    DevBuf<uint8_t> d_sky, d_ps, d_os, d_full_sky, d_rec;
+    auto up = [&](auto &buf, const auto *src, size_t count) -> hipError_t {
+        const hipError_t e = buf.alloc(count);
+        return e != hipSuccess ? e : hipMemcpy(buf.p, src, count * sizeof *src, hipMemcpyHostToDevice);
+    };
+    HIP_TRY(c, up(d_nrm, normal, 3 * n)); HIP_TRY(c, up(d_dep, depth, n)); HIP_TRY(c, up(d_hist, hist_in, 3 * n));
+    HIP_TRY(c, up(d_pn, prev_normal, 3 * n)); HIP_TRY(c, up(d_pd, prev_depth, n)); HIP_TRY(c, up(d_ps, prev_sky, n));
+    const TaaGuides prev_in{d_pn.p, d_pd.p, d_ps.p};
+    TaaGuidesOut prev_out{d_pn.p, d_pd.p, d_ps.p};          // (forms 1, 4, 5: in place)
+    int e = 0;
+    if (!tiles) {
+        HIP_TRY(c, up(d_cur, current, 3 * n)); HIP_TRY(c, up(d_sky, sky, n));
+        if (form == 0 || form == 3) {
+            HIP_TRY(c, d_on.alloc(3 * n)); HIP_TRY(c, d_od.alloc(n)); HIP_TRY(c, d_os.alloc(n));
+            // (on the launch's own stream: a memset on the null stream is not ordered against it and may land behind the kernel's stores)
+            HIP_TRY(c, hipMemsetAsync(d_on.p, 0, 3 * n * sizeof(float), c->stream)); HIP_TRY(c, hipMemsetAsync(d_od.p, 0, n * sizeof(float), c->stream));
+            HIP_TRY(c, hipMemsetAsync(d_os.p, 0, n, c->stream));
+            prev_out = TaaGuidesOut{d_on.p, d_od.p, d_os.p};
+        }
+        e = ycge_launch_taa(&T, d_cur.p, d_nrm.p, d_dep.p, d_sky.p, d_hist.p, &prev_in, form == 2 ? nullptr : &prev_out, c->stream, form == 3 ? 1 : 0);
+        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_taa launch failed: %s", hipGetErrorString((hipError_t)e));
+    } else {
+        size_t n_recv = 0;
+        for (int64_t v : c->halo_recv_counts) n_recv += (size_t)v;
+        const size_t slab_n = (size_t)c->tiles_per_rank_padded * 256 * 3;
+        HIP_TRY(c, up(d_full_cur, current, 3 * n)); HIP_TRY(c, up(d_full_sky, sky, n));
+        HIP_TRY(c, d_rec.alloc((n_recv ? n_recv : 1) * 16));
+        HIP_TRY(c, d_slab.alloc(slab_n)); HIP_TRY(c, hipMemsetAsync(d_slab.p, 0, slab_n * sizeof(float), c->stream));
+        // the records the owners would have sent, in this rank's receive order
+        e = ycge_launch_halo(0, d_full_cur.p, d_full_sky.p, c->d_halo_recv_px.p, (uint32_t)n_recv, d_rec.p, c->stream);
+        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_gather_halo launch failed: %s", hipGetErrorString((hipError_t)e));
+        {   // what TAA reads: this rank's own pixels, everything else poisoned
+            std::vector<float> cur(current, current + 3 * n);
+            std::vector<uint8_t> sk(sky, sky + n);
+            for (size_t i = 0; i < n; i++) {
+                const int x = (int)(i % (size_t)w), y = (int)(i / (size_t)w);
+                if (((y / YCGE_TILE_H) * c->tiles_x + x / YCGE_TILE_W) % c->cfg.world_size == c->cfg.rank) continue;
+                cur[3 * i] = cur[3 * i + 1] = cur[3 * i + 2] = 1e30f;
+                sk[i] = sk[i] ? (uint8_t)0 : (uint8_t)1;
+            }
+            HIP_TRY(c, up(d_cur, cur.data(), 3 * n)); HIP_TRY(c, up(d_sky, sk.data(), n));
+        }
+        FrameParams P;
+        const float origin[3] = {0.0f, 0.0f, 0.0f};
+        fill_frame_params(c, P, 0, origin, 0.0f, 0.0f, 45.0f);          // (the tile partition is all the TAA kernels read of it)
+        if (form == 4) {
+            e = ycge_launch_halo(1, d_cur.p, d_sky.p, c->d_halo_recv_px.p, (uint32_t)n_recv, d_rec.p, c->stream);
+            if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_scatter_halo launch failed: %s", hipGetErrorString((hipError_t)e));
+            e = ycge_launch_taa_tiles(&T, &P, d_cur.p, d_nrm.p, d_dep.p, d_sky.p, d_hist.p, &prev_in, &prev_out, d_slab.p, c->stream);
+        } else
+            e = ycge_launch_resolve_tiles(&T, &P, d_cur.p, d_nrm.p, d_dep.p, d_sky.p, d_rec.p, c->d_halo_index.p, d_hist.p, &prev_in, &prev_out, d_slab.p, c->stream);
+        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "resolve launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const float *gn = form == 2 ? d_nrm.p : prev_out.normal, *gd = form == 2 ? d_dep.p : prev_out.depth;
+    const uint8_t *gs = form == 2 ? d_sky.p : prev_out.sky;
+    int rc = copy_out(c, hist_out, d_hist.p, 3 * n * sizeof(float));
+    if (rc == YCGE_OK) rc = copy_out(c, normal_out, gn, 3 * n * sizeof(float));
+    if (rc == YCGE_OK) rc = copy_out(c, depth_out, gd, n * sizeof(float));
+    if (rc == YCGE_OK) rc = copy_out(c, sky_out, gs, n);
+    if (rc == YCGE_OK && tiles) rc = copy_out(c, slab_out, d_slab.p, d_slab.n * sizeof(float));
+    return rc;
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

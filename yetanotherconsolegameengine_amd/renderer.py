@@ -785,6 +785,35 @@ class RaytraceRenderer:
         self._check(self._post_hook("ycge_test_exposure")(self.ctx, t.ctypes.data, t.size, float(ae_in), int(bool(serial)), st.ctypes.data))
         return self._post_state(st)
 
+    def taa_probe(self, form: int, reset: bool, current, normal, depth, sky, hist_in, prev_normal, prev_depth, prev_sky,
+                  taa_alpha: float = 0.01, taa_clamp_radius: int = 1, taa_luminance_pad: float = 0.10) -> dict:
+        """TemporalBlendWithClamp's kernels alone (ycge_test_taa) on caller-given h x w planes, the size read off `depth`; form: abi.TAA_FORM_*.
+        The three last arguments are the raw config values.  Returns dict(hist, prev_normal, prev_depth, prev_sky) after the launch and, for
+        the tile forms (which run at this context's own trace grid, as its rank of world_size), slab.  Works in buffers of its own; the tile forms create the context's tile-resident ring if it has none."""
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if depth.ndim != 2:
+            raise ValueError("taa_probe: depth is an h x w plane")
+        h, w = depth.shape
+        n = h * w
+        arrs = [None] * 8
+        for k, (a, dt, per) in enumerate(((current, np.float32, 3), (normal, np.float32, 3), (depth, np.float32, 1), (sky, np.uint8, 1), (hist_in, np.float32, 3),
+                                          (prev_normal, np.float32, 3), (prev_depth, np.float32, 1), (prev_sky, np.uint8, 1))):
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != per * n:
+                raise ValueError(f"taa_probe: an array of {a.size} elements where the {w} x {h} planes need {per * n}")
+            arrs[k] = a
+        out = dict(hist=np.zeros((h, w, 3), np.float32), prev_normal=np.zeros((h, w, 3), np.float32), prev_depth=np.zeros((h, w), np.float32),
+                   prev_sky=np.zeros((h, w), np.uint8))
+        slab = np.zeros(self.history_slab_bytes() // 4, np.float32) if form >= abi.TAA_FORM_SCATTER_TILES else None
+        fn = self.L.ycge_test_taa
+        fn.restype, fn.argtypes = abi.TAA_HOOK_PROTOTYPES["ycge_test_taa"]
+        self._check(fn(self.ctx, int(form), int(bool(reset)), w, h, *[a.ctypes.data for a in arrs], float(taa_alpha), int(taa_clamp_radius), float(taa_luminance_pad),
+                       out["hist"].ctypes.data, out["prev_normal"].ctypes.data, out["prev_depth"].ctypes.data, out["prev_sky"].ctypes.data,
+                       slab.ctypes.data if slab is not None else None))
+        if slab is not None:
+            out["slab"] = slab
+        return out
+
     def read(self, which: int) -> np.ndarray:
         dt, n = abi.BUFFER_LAYOUT[which]
         shape = (self.hiH, self.hiW, n) if n > 1 else (self.hiH, self.hiW)
