@@ -215,6 +215,12 @@ namespace ConsoleGame.RayTracing.Native
         // the pregenerated world (WorldManager.GenerateAndSaveWorld) on the host / on the device + attach; HipPregenWorld in YcgeWorld.cs
         [DllImport(Lib)] public static extern int ycge_worldgen_world_cells(ref YWorld world, int chunksX, int chunksZ, int originBx, int originBz, int* cellsOut);
         [DllImport(Lib)] public static extern int ycge_scene_generate_world(IntPtr ctx, ref YWorld world, int chunksX, int chunksZ, int originBx, int originBz, YGrid* proto, int* outGridIndex, int* cellsOut);
+        // the world store (found by symbol lookup, ABI stays 10): a VG01 payload resident on the device, its chunks attached by key; HipWorldStore in YcgeWorld.cs
+        [DllImport(Lib)] public static extern int ycge_world_file_info(byte* bytes, UIntPtr nBytes, int* dimsOut, UIntPtr* payloadOffsetOut, byte* msg, UIntPtr msgBytes);
+        [DllImport(Lib)] public static extern int ycge_world_store_load(IntPtr ctx, int* cells, int nx, int ny, int nz, int chunkSize);
+        [DllImport(Lib)] public static extern int ycge_world_store_info(IntPtr ctx, int* dimsOut, int* chunkSizeOut, byte* occupiedOut, UIntPtr capacity);
+        [DllImport(Lib)] public static extern int ycge_scene_attach_world_chunks(IntPtr ctx, int* keys, int n, YGrid* proto, int* outGridIndex);
+        [DllImport(Lib)] public static extern int ycge_world_store_release(IntPtr ctx);
         [DllImport(Lib)] public static extern int ycge_scene_update_texture(IntPtr ctx, int textureIndex, IntPtr frame, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_resize(IntPtr ctx, int fbWidth, int fbHeight, int superSample);
         [DllImport(Lib)] public static extern int ycge_set_camera(IntPtr ctx, float* pos, float yaw, float pitch, float fovDeg);

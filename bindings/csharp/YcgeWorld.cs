@@ -49,4 +49,49 @@ namespace ConsoleGame.RayTracing.Native
             return cells;
         }
     }
+
+    /// <summary>A host that HAS a world file (WorldManager.ReloadFromExistingFile) hands its payload over once and then streams by chunk key:
+    /// Load makes the cells resident on the device (the header checked as :414-424 checks it), Attach is AttachChunkFromPreloaded for a list
+    /// of keys - the slices are cut on the device, no cell crosses the bus again - and returns the device grid per key, -1 for a key outside
+    /// the world and for a chunk with no cell of mat != 0 (the reference attaches none).  proto.MinCorner is WorldMin and proto.VoxelSize
+    /// is VoxelSize.  The store outlives scene uploads; Release (or ycge_destroy) frees it, and the grids attached from it stay.</summary>
+    public sealed unsafe class HipWorldStore
+    {
+        public int Nx, Ny, Nz, ChunkSize;
+        public int ChunksX => (Nx + ChunkSize - 1) / ChunkSize;
+        public int ChunksY => (Ny + ChunkSize - 1) / ChunkSize;
+        public int ChunksZ => (Nz + ChunkSize - 1) / ChunkSize;
+
+        /// <summary>`file`: the whole VG01 file (a mapped view will do; it is not read after the call).</summary>
+        public void Load(IntPtr ctx, byte* file, ulong bytes, int chunkSize)
+        {
+            int* dims = stackalloc int[3];
+            byte* msg = stackalloc byte[256];
+            UIntPtr offset;
+            if (Ycge.ycge_world_file_info(file, (UIntPtr)bytes, dims, &offset, msg, (UIntPtr)256) != 0)
+                throw new System.IO.InvalidDataException(Marshal.PtrToStringAnsi((IntPtr)msg));
+            Ycge.Check(ctx, Ycge.ycge_world_store_load(ctx, (int*)(file + (ulong)offset), dims[0], dims[1], dims[2], chunkSize));
+            Nx = dims[0]; Ny = dims[1]; Nz = dims[2]; ChunkSize = chunkSize;
+        }
+
+        /// <summary>One byte per chunk, [ChunksX, ChunksY, ChunksZ]: 1 when a cell of the chunk has mat != 0 (AttachChunkFromPreloaded's anySolid).</summary>
+        public byte[,,] Occupied(IntPtr ctx)
+        {
+            var flat = new byte[ChunksX * ChunksY * ChunksZ];
+            fixed (byte* o = flat) Ycge.Check(ctx, Ycge.ycge_world_store_info(ctx, null, null, o, (UIntPtr)(ulong)flat.Length));
+            var occ = new byte[ChunksX, ChunksY, ChunksZ];
+            Buffer.BlockCopy(flat, 0, occ, 0, flat.Length);
+            return occ;
+        }
+
+        /// <summary>keys: {cx, cy, cz} per chunk, in the order the host wants the grids taken (the LoadChunksAround tick: radial, then cy).</summary>
+        public int[] Attach(IntPtr ctx, int[] keys, YGrid proto)
+        {
+            var index = new int[keys.Length / 3];
+            fixed (int* k = keys) fixed (int* ix = index) Ycge.Check(ctx, Ycge.ycge_scene_attach_world_chunks(ctx, k, index.Length, &proto, ix));
+            return index;
+        }
+
+        public void Release(IntPtr ctx) { Ycge.Check(ctx, Ycge.ycge_world_store_release(ctx)); Nx = Ny = Nz = 0; }
+    }
 }

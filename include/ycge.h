@@ -441,6 +441,47 @@ int ycge_worldgen_world_cells(const ycge_world *world, int32_t chunks_x, int32_t
 int ycge_scene_generate_world(ycge_ctx *ctx, const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz,
                               const ycge_grid *proto, int32_t *out_grid_index /* chunks_x*chunks_y*chunks_z */, int32_t *cells_out /* NULL, or 2*nx*ny*nz */);
 
+/* --- the world store: a host that HAS a VG01 world file reads it into preloadedWorld once (WorldManager.ReloadFromExistingFile,
+ * WorldManager.cs:399-508), and from then on every chunk that enters the view is a slice of that array (AttachChunkFromPreloaded, :696-752,
+ * from EnsureViewLoaded, EnsureAllChunksLoaded and the LoadChunksAround tick).  Here the payload goes up ONCE and stays resident on the
+ * device; chunks are attached from it by key and no cell crosses the bus again (csrc/ycge_world_store.cpp, kernels in
+ * csrc/ycge_world_store.hip).  Found by symbol lookup as the exports above; YCGE_ABI_VERSION stays 10.
+ *   The store belongs to the context, not to the scene: ycge_scene_upload keeps it, ycge_world_store_release and ycge_destroy free it, a
+ *     second ycge_world_store_load replaces it - once the new one is complete: a refused or failed load leaves the old store as it was.  Grids
+ *     attached from a store are encoded copies and stay resident when it goes.  A load touches no scene and joins no frame in flight.
+ *   One-process multi-device: every device holds the payload; a peer context is refused by all of these.
+ *   YCGE_WORLD_STORE_SLAB_BYTES at ycge_create (default 64 MiB): the payload goes up in slabs of whole x-planes (one at least) through two
+ *     page-locked staging buffers of that size, the copy of one slab beside the occupancy kernel on the one before; a `cells` range that is
+ *     page-locked already (ycge_alloc_host_buffer, ycge_pin_host_buffer) is copied from directly.
+ *   YCGE_WORLD_STORE_HOST at ycge_create: the store is a host copy, chunks are sliced by a host loop and go up as an attach's cells do. */
+/* The header of a VG01 file as ReloadFromExistingFile checks it (:414-424): 'V','G','0','1', little-endian int32 nx, ny, nz, the payload at
+ * offset 16.  Pure host code, no context and no device.  YCGE_ERR_INVALID_ARG with the reference's text in msg (may be NULL):
+ * "Unsupported world file header. Expected 'VG01'.", "Invalid world dimensions.", "Unable to read beyond the end of the stream." (n_bytes
+ * below 16 or below 16 + 8 * nx * ny * nz); also refused: nx * ny * nz >= 2^30 (ycge_scene_generate_world's limit), a NULL bytes or dims_out. */
+int ycge_world_file_info(const uint8_t *bytes, size_t n_bytes, int32_t dims_out[3], size_t *payload_offset_out /* may be NULL */, char *msg, size_t msg_bytes);
+/* Make the payload resident.  cells: 2 * nx * ny * nz int32, x, then y, then z fastest, {mat, meta} - it may point into a mapped file and is
+ * not read after the call.  Per chunk of chunk_size, clipped at the far faces (:698-700), the load finds whether any cell has mat != 0 (:716).
+ * YCGE_ERR_INVALID_ARG: a NULL pointer, a dimension < 1, nx * ny * nz >= 2^30, chunk_size outside 1..1024, more than 2^24 chunks, a peer
+ * context.  An allocation failure is YCGE_ERR_OUT_OF_MEMORY, as for ycge_scene_attach_grids. */
+int ycge_world_store_load(ycge_ctx *ctx, const int32_t *cells, int32_t nx, int32_t ny, int32_t nz, int32_t chunk_size);
+/* The store's dimensions, chunk size (either may be NULL) and, when occupied_out is not NULL, one byte per chunk in (cx, cy, cz) order with
+ * cx outermost (ceil(n / chunk_size) chunks per axis): 1 when a cell of the chunk has mat != 0.  YCGE_ERR_INVALID_ARG with a message:
+ * no store, or capacity below the number of chunks. */
+int ycge_world_store_info(ycge_ctx *ctx, int32_t dims_out[3], int32_t *chunk_size_out, uint8_t *occupied_out, size_t capacity);
+/* Attach n chunks of the store by key: what ycge_scene_attach_grids gives when it is handed, for the same keys in the same order, the cells
+ * AttachChunkFromPreloaded slices - the same pixels, indices, limits and statuses, all or nothing, joining the frames in flight, forwarded
+ * to the devices of a one-process multi-device context, as documented there.
+ *   proto: as for ycge_scene_generate_grids, but proto->min_corner is WorldMin and proto->voxel_size is VoxelSize: chunk (cx, cy, cz) gets
+ *     nx, ny, nz = its clipped sizes and min_corner = WorldMin + (float)(c * chunk_size) * VoxelSize in binary32 (:720-724).
+ *   No slot, index -1: a key with a negative component or at or beyond the chunk counts (the reference indexes out of range there, and
+ *     EnsureViewLoaded swallows it), and a chunk with no cell of mat != 0.  A chunk whose only non-zero ids are negative DOES take a slot:
+ *     the reference attaches it (!= 0) although VolumeGrid draws nothing of it (matId > 0).  A key may repeat; each occurrence takes a grid.
+ *   YCGE_ERR_NO_SCENE before the first upload; YCGE_ERR_INVALID_ARG with a message when there is no store.  A pair with no material and
+ *     default_material < 0 is refused as the attach refuses it; the message names the chunk key and the cell in the chunk. */
+int ycge_scene_attach_world_chunks(ycge_ctx *ctx, const int32_t *keys /* 3 n */, int32_t n, const ycge_grid *proto, int32_t *out_grid_index /* n */);
+/* Free the store on every device (YCGE_OK when there is none). */
+int ycge_world_store_release(ycge_ctx *ctx);
+
 /* The argument checks of ycge_scene_upload on their own: pure host code, no device and no context needed
  * (every index in range, counts non-negative, pointers present, material kinds known).  Returns YCGE_OK or the
  * status ycge_scene_upload would return; `msg` (may be NULL) receives the reason. */

@@ -224,6 +224,12 @@ _PROTOTYPES = {
     "ycge_scene_generate_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(Grid), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ycge_worldgen_world_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ycge_scene_generate_world": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Grid), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # the world store: a VG01 payload resident on the device, chunks attached by key (keys: int32 [n, 3]; occupied_out: uint8 per chunk or None)
+    "ycge_world_file_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
+    "ycge_world_store_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ycge_world_store_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_size_t]),
+    "ycge_scene_attach_world_chunks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(Grid), C.POINTER(C.c_int32)]),
+    "ycge_world_store_release": (C.c_int, [C.c_void_p]),
     "ycge_scene_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ycge_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]),
@@ -317,6 +323,12 @@ WORLDGEN_HOOK_PROTOTYPES = {
     "ycge_host_worldgen_river_global": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     "ycge_host_worldgen_world_from_fields": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
 }
+# test / profiling hooks of the world store (csrc/ycge_world_store.cpp), bound where they are used (RaytraceRenderer.world_store_chunk / world_store_stats)
+WORLD_STORE_HOOK_PROTOTYPES = {
+    "ycge_debug_world_store_chunk": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "ycge_debug_world_store_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+}
+WORLD_STORE_STATS = ("store_bytes", "slabs", "load_stage_us", "load_h2d_us", "load_occupied_us", "last_slice_us", "device_chunks", "host_chunks")
 # test hooks of the post stage on caller-given inputs (csrc/ycge_post_host.cpp), bound where they are used (RaytraceRenderer.post_probe /
 # exposure_probe); state_out: POST_STATE_WORDS uint32
 POST_HOOK_PROTOTYPES = {
@@ -430,6 +442,21 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if path is None:
         _lib = lib
     return lib
+
+
+def world_file_info(data, lib: C.CDLL | None = None):
+    """ycge_world_file_info: the header of a VG01 file's bytes (no context, no device) -> ((nx, ny, nz), payload offset).  Raises YcgeError
+    with the reference's text for what ReloadFromExistingFile refuses."""
+    L = lib if lib is not None else load_library()
+    fn = L.ycge_world_file_info
+    fn.restype, fn.argtypes = _PROTOTYPES["ycge_world_file_info"]
+    import numpy as np
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data
+    dims, off, msg = (C.c_int32 * 3)(), C.c_size_t(0), C.create_string_buffer(256)
+    rc = fn(buf.ctypes.data if buf.size else C.addressof(msg), buf.size, dims, C.byref(off), msg, len(msg))          # (an empty file is a short one, not a NULL argument)
+    if rc != 0:
+        raise YcgeError(rc, msg.value.decode())
+    return tuple(int(v) for v in dims), int(off.value)
 
 
 def obj_parse_host(data: bytes, lib: C.CDLL | None = None):

@@ -7,6 +7,7 @@
 //   ycge_post_host.cpp the post stage (steps 6-8) and its schedules
 //   ycge_resident.cpp  the tile-resident multi-GPU form, its batched launches and emulation loop; read-backs (ycge_read_buffer / _accel)
 //   ycge_query.cpp, ycge_chexel.cpp, ycge_ansi.cpp, ycge_grid_encode.cpp, ycge_worldgen_scene.cpp   scene queries, chexel colours, the ANSI stream, streamed grids, generated chunks
+//   ycge_world_store.cpp   a VG01 world resident on the device, its chunks attached by key
 //   ycge_accel.cpp     the bit-faithful BVH builders
 // Every GPU resource is held through an owner of ycge_own.h: members free themselves, ycge_ctx::~ycge_ctx orders only what has an order.
 // All device work is in the .hip files; there is no CPU implementation of any per-pixel stage.
@@ -41,6 +42,7 @@
 #include "ycge_device.h"
 #include "ycge_math.h"
 #include "ycge_own.h"
+#include "ycge_world_store.h"
 
 extern "C" {
 size_t ycge_wf_sizes(int which);
@@ -228,6 +230,8 @@ struct Knobs {
     long long obj_ground_device_min = YCGE_OBJ_GROUND_DEVICE_MIN_DEFAULT;   // YCGE_OBJ_GROUND_DEVICE_MIN: ... and OBJs of fewer triangles than this
     bool obj_ground_phases = false;  // YCGE_OBJ_GROUND_PHASES: a stream synchronise behind every phase of the device tail (ycge_debug_obj_ground_phases: what each costs)
     bool exposure_serial = false;    // YCGE_EXPOSURE_SERIAL: the one-lane chain instead of the chunked exact evaluation
+    bool world_store_host = false;   // YCGE_WORLD_STORE_HOST: ycge_world_store_load keeps the world in host memory; its chunks are sliced by a host loop and go up as an attach's cells do
+    size_t world_store_slab_bytes = YCGE_WORLD_STORE_SLAB_BYTES_DEFAULT;   // YCGE_WORLD_STORE_SLAB_BYTES: bytes of whole x-planes staged per slab of a load (one plane at least)
     void read()
     {
         auto geti = [](const char *n, int dflt) { const char *e = getenv(n); return e ? atoi(e) : dflt; };
@@ -283,6 +287,8 @@ struct Knobs {
         scene_bvh_device_min = geti("YCGE_SCENE_BVH_DEVICE_MIN", YCGE_BVH_DEV_MIN_ITEMS_DEFAULT);
         mesh_bvh_host = getenv("YCGE_MESH_BVH_HOST") != nullptr;
         worldgen_host = getenv("YCGE_WORLDGEN_HOST") != nullptr;
+        world_store_host = getenv("YCGE_WORLD_STORE_HOST") != nullptr;
+        if (const char *e = getenv("YCGE_WORLD_STORE_SLAB_BYTES")) { const long long v = atoll(e); if (v > 0) world_store_slab_bytes = (size_t)v; }
         if (const char *e = getenv("YCGE_ENC_GROUP_BYTES")) { const long long v = atoll(e); if (v > 0) enc_group_bytes = (size_t)v; }
         mesh_emit_host = getenv("YCGE_MESH_EMIT_HOST") != nullptr;
         mesh_emit_device_min = geti("YCGE_MESH_EMIT_DEVICE_MIN", YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT);
@@ -485,6 +491,21 @@ struct ObjState {
     int64_t ground_device_tails = 0, ground_host_tails = 0, ground_last_decline = 0, ground_rounds = 0;
     double ground_last_us = 0;
     double ground_phase_us[5] = {0, 0, 0, 0, 0};       // YCGE_OBJ_GROUND_PHASES: labelling, count + winner, terms, the three sums, bounds + read-back
+};
+
+// the VG01 world a context holds (ycge_world_store_load, ycge_world_store.cpp): one at a time, not scene state - ycge_scene_upload keeps it.
+// Every device of a multi-device context holds the cells; the rest is the root's.
+struct WorldStore {
+    bool held = false, on_host = false;                // on_host: YCGE_WORLD_STORE_HOST, the cells are host_cells
+    ycge::WsShape shape{};
+    DevBuf<int32_t> d_cells;                           // the payload in VG01 order, on this context's device
+    std::vector<int32_t> host_cells;
+    std::vector<uint8_t> occupied;                     // per chunk, (cx, cy, cz) with cx outermost: 1 when a cell has mat != 0
+    int64_t bytes = 0, slabs = 0;                      // of the last load
+    double load_us[3] = {0, 0, 0};                     // ... its copies into the staging (wall), its host-to-device copies and occupancy kernels (stream time, root device)
+    std::vector<Event> slice_ev;                       // begin / end of the last attach's slice launches on the root's stream, a pair per group (kept from attach to attach)
+    size_t slice_ev_used = 0;
+    int64_t device_chunks = 0, host_chunks = 0;        // chunks sliced by k_ws_slice / by the host, since the context was made
 };
 
 struct ycge_ctx {
@@ -737,6 +758,7 @@ struct ycge_ctx {
     ChexelState chexels;
     VideoState video;            // Video mode (ycge_video_blit, ycge_video.cpp)
     ObjState obj;                // the parsed OBJ (ycge_obj_parse, ycge_obj.cpp)
+    WorldStore world_store;      // the resident VG01 world (ycge_world_store_load, ycge_world_store.cpp)
 
     ycge_ctx() = default;
     ycge_ctx(const ycge_ctx &) = delete;
@@ -861,6 +883,7 @@ void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_b
 struct CellSource {
     bool on_device = false;          // the cells are made by fill(), not by write()
     bool caller_cells = false;       // ycge_grid.cells are the cells, readable throughout the call (else: never read; a pair with no material is named when its group ends)
+    bool foreign_cells = false;      // not the caller's, yet arbitrary (a world file's): a grid whose cells missed the lookup table has its distinct pairs counted, as the caller's are
     size_t group_max = SIZE_MAX;     // grids in one group
     virtual ~CellSource() = default;
     // the cells of grid k, 2 * nx * ny * nz int32 in ycge_grid.cells order: into its group's staging, or for the host encoder (a lookup table k_grid_encode does not take)
@@ -868,6 +891,9 @@ struct CellSource {
     // device-made: the bytes of launch records the source wants on the device ahead of the cells of a group of m grids (at d_head), and the launch on x's
     // stream that writes the cells of grid group[j] to d_cells[j].  x == root: waits, refuses what came out wrong and hands the cells to the caller if asked
     virtual size_t head_bytes(size_t /* m */) const { return 0; }
+    // how a refusal names cell `cell` (ycge_grid.cells order; kNoCell: the grid as a whole) of grid k when the cells are not the caller's
+    static constexpr uint32_t kNoCell = 0xffffffffu;
+    virtual std::string where(size_t k, uint32_t /* cell */) const { return "grid " + std::to_string(k); }
     virtual int fill(ycge_ctx * /* root */, ycge_ctx * /* x */, const std::vector<int> & /* group */, uint8_t * /* d_head */, const std::vector<int32_t *> & /* d_cells */) { return YCGE_OK; }
 };
 int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *out_grid_index, CellSource &src);
@@ -899,4 +925,12 @@ int obj_ground(ycge_ctx *c, ycge_obj_ground_info *out);
 int obj_triangles_auto_ground(ycge_ctx *c, float scale, const float target[3], float *out_triangles, float out_bounds[6], ycge_obj_ground_info *out_info);
 int obj_ground_stats(ycge_ctx *c, int64_t *out6);
 int obj_ground_phases(ycge_ctx *c, int64_t *out5);
+// ycge_world_store.cpp: the bodies of ycge_world_file_info (no context), ycge_world_store_load / _info / _release, ycge_scene_attach_world_chunks and the hooks
+int world_file_info(const uint8_t *bytes, size_t n_bytes, int32_t dims_out[3], size_t *payload_offset_out, char *msg, size_t msg_bytes);
+int world_store_load(ycge_ctx *c, const int32_t *cells, int32_t nx, int32_t ny, int32_t nz, int32_t chunk_size);
+int world_store_info(ycge_ctx *c, int32_t dims_out[3], int32_t *chunk_size_out, uint8_t *occupied_out, size_t capacity);
+int world_store_release(ycge_ctx *c);
+int world_store_attach(ycge_ctx *c, const int32_t *keys, int32_t n, const ycge_grid *proto, int32_t *out_grid_index);
+int world_store_chunk(ycge_ctx *c, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t dims_out[3]);
+int world_store_stats(ycge_ctx *c, int64_t *out8);
 } // namespace ycge_host

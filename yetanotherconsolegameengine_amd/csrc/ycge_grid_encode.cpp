@@ -175,7 +175,7 @@ int encode_group(ycge_ctx *root, const ycge_grid *grids, std::vector<Planned> &p
                 const int rc = copy_out(root, pair, root->d_enc_in.p + plan[k].cells_off + (size_t)r.bad_cell * 8, 8);
                 if (rc != YCGE_OK) return rc;
             }
-            return root->fail(YCGE_ERR_INVALID_ARG, "grid %d: no material for (matId %d, metaId %d)", (int)k, pair[0], pair[1]);
+            return root->fail(YCGE_ERR_INVALID_ARG, "%s: no material for (matId %d, metaId %d)", src.where(k, r.bad_cell).c_str(), pair[0], pair[1]);
         }
     }
     (void)hipSetDevice(root->device);
@@ -291,6 +291,14 @@ int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *o
             if (r.bad_cell != 0xffffffffu)          // (cells that are not the caller's: encode_group has named it already)
                 return c->fail(YCGE_ERR_INVALID_ARG, "grid %d: no material for (matId %d, metaId %d)", k, g.cells[2 * (size_t)r.bad_cell], g.cells[2 * (size_t)r.bad_cell + 1]);
             if (src.caller_cells && r.any_miss && too_many_pairs(g)) return c->fail(YCGE_ERR_UNSUPPORTED, "grid %d: more than 255 distinct (matId, metaId) pairs", k);
+            if (src.foreign_cells && r.any_miss) {          // cells nobody has vetted (a world file's): the same limit, counted on a copy of the grid's cells
+                std::vector<int32_t> made(2 * (size_t)g.nx * g.ny * g.nz);
+                rc = src.write(c, (size_t)k, g, made.data());
+                if (rc != YCGE_OK) return rc;
+                ycge_grid gm = g;
+                gm.cells = made.data();
+                if (too_many_pairs(gm)) return c->fail(YCGE_ERR_UNSUPPORTED, "%s: more than 255 distinct (matId, metaId) pairs", src.where((size_t)k, CellSource::kNoCell).c_str());
+            }
             for (int a = 0; a < 3; a++) { lo[a] = r.lo[a]; hi[a] = r.hi[a]; }
             mask = pl.rec.has_brick_mask ? ((uint64_t)r.mask_hi << 32) | r.mask_lo : 0;
             P.device_encodes++;
@@ -305,7 +313,11 @@ int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *o
                 gh.cells = made.data();
             }
             rc = encode_grid_host(c, gh, k, c->n_materials, pl.rec, pl.host_bytes.data(), pl.host_lut, lo, hi, mask);
-            if (rc != YCGE_OK) return rc;
+            if (rc != YCGE_OK) {          // (its refusals begin "grid k": cells that are not the caller's are named as their source names them)
+                const std::string head = "grid " + std::to_string(k);
+                if (!src.caller_cells && c->err.compare(0, head.size(), head) == 0) c->err = src.where((size_t)k, CellSource::kNoCell) + c->err.substr(head.size());
+                return rc;
+            }
             pl.host_lut.resize(YCGE_ENC_LUT_ENTRIES, -1);
             P.host_encodes++;
         }

@@ -670,6 +670,52 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// a VG01 world file's header (ycge_world_store.cpp: pure host code, no context and no device) ...
+int ycge_world_file_info(const uint8_t *bytes, size_t n_bytes, int32_t dims_out[3], size_t *payload_offset_out, char *msg, size_t msg_bytes)
+try {
+    return world_file_info(bytes, n_bytes, dims_out, payload_offset_out, msg, msg_bytes);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// ... its payload made resident on every device of the context, what the context holds of it, given back ...
+int ycge_world_store_load(ycge_ctx *c, const int32_t *cells, int32_t nx, int32_t ny, int32_t nz, int32_t chunk_size)
+try {
+    return world_store_load(c, cells, nx, ny, nz, chunk_size);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_world_store_info(ycge_ctx *c, int32_t dims_out[3], int32_t *chunk_size_out, uint8_t *occupied_out, size_t capacity)
+try {
+    return world_store_info(c, dims_out, chunk_size_out, occupied_out, capacity);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_world_store_release(ycge_ctx *c)
+try {
+    return world_store_release(c);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ... and its chunks attached by key (AttachChunkFromPreloaded)
+int ycge_scene_attach_world_chunks(ycge_ctx *c, const int32_t *keys, int32_t n, const ycge_grid *proto, int32_t *out_grid_index)
+try {
+    return world_store_attach(c, keys, n, proto, out_grid_index);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hooks: one chunk's raw cells as the slice writes them (no attach); the store's size, the last load's and attach's split (include/ycge_hooks.h)
+int ycge_debug_world_store_chunk(ycge_ctx *c, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t dims_out[3])
+try {
+    return world_store_chunk(c, cx, cy, cz, cells_out, dims_out);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_debug_world_store_stats(ycge_ctx *c, int64_t *out8)
+try {
+    return world_store_stats(c, out8);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 int ycge_resize(ycge_ctx *c, int32_t fbw, int32_t fbh, int32_t ss)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;

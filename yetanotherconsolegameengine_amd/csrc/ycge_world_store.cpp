@@ -1,0 +1,363 @@
+// ycge_world_store.cpp - a VG01 world resident on the device, and its chunks attached by key: the bodies of ycge_world_file_info,
+// ycge_world_store_load / _info / _release, ycge_scene_attach_world_chunks and their hooks (the exports are in ycge_host.cpp).
+//
+// The reference reads a world file into preloadedWorld once (WorldManager.ReloadFromExistingFile, WorldManager.cs:399-508) and from then on
+// every chunk that enters the view is a slice of that array (AttachChunkFromPreloaded, :696-752).  Here the payload goes up once and stays:
+// the "world store", one allocation per device in VG01 order (x, then y, then z fastest, {mat, meta}).  An attach by key slices the chunks
+// out of it on the device (k_ws_slice, ycge_world_store.hip) into the area k_grid_encode reads - a third CellSource behind attach_grids_from
+// (ycge_grid_encode.cpp), beside the caller's cells and the generators' - so no cell crosses the bus again.
+//
+// LOAD: in x-slabs (a run of whole x-planes is contiguous in VG01 order) of YCGE_WORLD_STORE_SLAB_BYTES through two page-locked staging
+// buffers, each slab staged once for all devices; a caller's range that is page-locked already is copied from directly.  Copies and the
+// occupancy kernel run on two streams of the load's own, so the copy of slab k + 1 overlaps k_ws_occupied on slab k, and no stream of a
+// frame is touched: a load joins no frame in flight.  The occupancy words come back once, after the last slab: which keys of an attach
+// take part is decided on the host with no read-back.  The new store replaces the old one in a last step that cannot fail.
+//
+// YCGE_WORLD_STORE_HOST at ycge_create: the store is a host copy of the payload, the slice is a host loop and the cells go up as an
+// attach's cells do - the yardstick and the fallback.
+#include <algorithm>
+
+#include "ycge_ctx.h"
+#include "ycge_grid_encode.h"
+
+namespace ycge_host {
+namespace {
+
+const char *const kNoStore = "no world store loaded (ycge_world_store_load)";
+
+size_t chunk_of(const WsShape &W, int cx, int cy, int cz) { return ((size_t)cx * W.ncy + cy) * W.ncz + cz; }
+void clipped(const WsShape &W, int cx, int cy, int cz, int s[3])
+{
+    s[0] = std::min(W.S, W.nx - cx * W.S); s[1] = std::min(W.S, W.ny - cy * W.S); s[2] = std::min(W.S, W.nz - cz * W.S);          // WorldManager.cs:698-700
+}
+size_t first_cell(const WsShape &W, int cx, int cy, int cz) { return (((size_t)cx * W.S) * W.ny + (size_t)cy * W.S) * W.nz + (size_t)cz * W.S; }
+
+// chunk `key` of a host world in VG01 order into `out`, ycge_grid.cells order (AttachChunkFromPreloaded's loop, :704-714)
+void slice_host(const WsShape &W, const int32_t *world, const std::array<int32_t, 3> &key, int32_t *out)
+{
+    int s[3];
+    clipped(W, key[0], key[1], key[2], s);
+    const int32_t *base = world + 2 * first_cell(W, key[0], key[1], key[2]);
+    for (size_t lx = 0; lx < (size_t)s[0]; lx++)
+        for (size_t ly = 0; ly < (size_t)s[1]; ly++)
+            std::memcpy(out + 2 * (lx * s[1] + ly) * s[2], base + 2 * ((lx * W.ny + ly) * W.nz), (size_t)s[2] * 8);
+}
+
+// chunk `key` of the root's device store into host memory: one k_ws_slice into a buffer of its own, one copy.  Nothing of the context may be in flight (copy_out).
+int slice_to_host(ycge_ctx *c, const WorldStore &st, const std::array<int32_t, 3> &key, int32_t *out)
+{
+    const WsShape &W = st.shape;
+    int s[3];
+    clipped(W, key[0], key[1], key[2], s);
+    const size_t n_cells = (size_t)s[0] * s[1] * s[2];
+    const DeviceGuard guard(c->device);
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<uint8_t> d;
+    HIP_TRY(c, d.alloc(256 + n_cells * 8));
+    WsChunk r{};
+    r.src = first_cell(W, key[0], key[1], key[2]); r.sx = s[0]; r.sy = s[1]; r.sz = s[2]; r.dst = (int32_t *)(d.p + 256);
+    HIP_TRY(c, hipMemcpy(d.p, &r, sizeof r, hipMemcpyHostToDevice));
+    const int e = ycge_launch_world_store_slice(st.d_cells.p, &W, (const WsChunk *)d.p, 1, n_cells, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ws_slice launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return copy_out(c, out, d.p + 256, n_cells * 8);
+}
+
+// the chunks of one ycge_scene_attach_world_chunks: grid k of the attach is chunk keys[k]
+struct StoreCells : CellSource {
+    WorldStore &store;                     // the root's
+    std::vector<std::array<int32_t, 3>> keys;
+    explicit StoreCells(WorldStore &s) : store(s) { on_device = !s.on_host; foreign_cells = true; group_max = 32768; }          // (gridDim.y of a slice launch)
+    size_t head_bytes(size_t m) const override { return align_up(m * sizeof(WsChunk), 256); }
+    std::string where(size_t k, uint32_t cell) const override
+    {
+        int s[3];
+        clipped(store.shape, keys[k][0], keys[k][1], keys[k][2], s);
+        char buf[160];
+        int n = std::snprintf(buf, sizeof buf, "ycge_scene_attach_world_chunks: chunk (%d, %d, %d)", keys[k][0], keys[k][1], keys[k][2]);
+        if (cell != kNoCell) std::snprintf(buf + n, sizeof buf - (size_t)n, ", cell (%u, %u, %u)", cell / (uint32_t)(s[1] * s[2]), cell / (uint32_t)s[2] % (uint32_t)s[1], cell % (uint32_t)s[2]);
+        return buf;
+    }
+    // the host store's slice; or, for the host encoder (a lookup table k_grid_encode does not take) and the count of distinct pairs, the chunk sliced out of the device store
+    int write(ycge_ctx *root, size_t k, const ycge_grid &, int32_t *cells) override
+    {
+        if (store.on_host) { slice_host(store.shape, store.host_cells.data(), keys[k], cells); return YCGE_OK; }
+        return slice_to_host(root, store, keys[k], cells);
+    }
+    int fill(ycge_ctx *root, ycge_ctx *x, const std::vector<int> &group, uint8_t *d_head, const std::vector<int32_t *> &d_cells) override
+    {
+        const WsShape &W = store.shape;
+        std::vector<WsChunk> recs(group.size());
+        size_t max_cells = 0;
+        for (size_t j = 0; j < group.size(); j++) {
+            const auto &key = keys[(size_t)group[j]];
+            WsChunk r{};
+            r.src = first_cell(W, key[0], key[1], key[2]);
+            int s[3];
+            clipped(W, key[0], key[1], key[2], s);
+            r.sx = s[0]; r.sy = s[1]; r.sz = s[2]; r.dst = d_cells[j];
+            max_cells = std::max(max_cells, (size_t)s[0] * s[1] * s[2]);
+            recs[j] = r;
+        }
+        HIP_TRY(root, hipMemcpy(d_head, recs.data(), recs.size() * sizeof(WsChunk), hipMemcpyHostToDevice));
+        // the encode launch follows on the same stream: nothing waits here.  The root's launch lies between two events the stats hook reads later.
+        Event *ev = nullptr;
+        if (x == root) {
+            if (store.slice_ev.size() < store.slice_ev_used + 2) store.slice_ev.resize(store.slice_ev_used + 2);
+            ev = &store.slice_ev[store.slice_ev_used];
+            HIP_TRY(root, ev[0].ensure(hipEventDefault)); HIP_TRY(root, ev[1].ensure(hipEventDefault));
+            HIP_TRY(root, hipEventRecord(ev[0], x->stream));
+        }
+        const int e = ycge_launch_world_store_slice(x->world_store.d_cells.p, &W, (const WsChunk *)d_head, (int)recs.size(), max_cells, x->stream);
+        if (e != 0) return root->fail(YCGE_ERR_DEVICE, "k_ws_slice launch failed: %s", hipGetErrorString((hipError_t)e));
+        if (ev) { HIP_TRY(root, hipEventRecord(ev[1], x->stream)); store.slice_ev_used += 2; }
+        return YCGE_OK;
+    }
+};
+
+int need_root(ycge_ctx *c)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    return YCGE_OK;
+}
+
+}  // namespace
+
+int world_file_info(const uint8_t *bytes, size_t n_bytes, int32_t dims_out[3], size_t *payload_offset_out, char *msg, size_t msg_bytes)
+{
+    auto refuse = [&](const char *why) { if (msg && msg_bytes) std::snprintf(msg, msg_bytes, "%s", why); return (int)YCGE_ERR_INVALID_ARG; };
+    if (msg && msg_bytes) msg[0] = 0;
+    if (!bytes || !dims_out) return refuse("ycge_world_file_info: null argument");
+    const char *const eof = "Unable to read beyond the end of the stream.";
+    // ReloadFromExistingFile, :414-424: four ReadChar, THEN the compare, then three ReadInt32 - a read that runs out of bytes throws
+    if (n_bytes < 4) return refuse(eof);
+    if (std::memcmp(bytes, "VG01", 4) != 0) return refuse("Unsupported world file header. Expected 'VG01'.");
+    if (n_bytes < 16) return refuse(eof);
+    int32_t d[3];
+    for (int a = 0; a < 3; a++) {
+        const uint8_t *p = bytes + 4 + 4 * a;
+        d[a] = (int32_t)((uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24);
+    }
+    if (d[0] <= 0 || d[1] <= 0 || d[2] <= 0) return refuse("Invalid world dimensions.");
+    const uint64_t cells = (uint64_t)d[0] * (uint64_t)d[1] * (uint64_t)d[2];          // (< 2^93 in exact arithmetic: compare before it can wrap)
+    if ((uint64_t)d[0] * (uint64_t)d[1] >= ((uint64_t)1 << 30) || cells >= ((uint64_t)1 << 30)) return refuse("ycge_world_file_info: nx * ny * nz >= 2^30");
+    if (n_bytes - 16 < 8 * cells) return refuse(eof);
+    for (int a = 0; a < 3; a++) dims_out[a] = d[a];
+    if (payload_offset_out) *payload_offset_out = 16;
+    return YCGE_OK;
+}
+
+int world_store_load(ycge_ctx *c, const int32_t *cells, int32_t nx, int32_t ny, int32_t nz, int32_t chunk_size)
+{
+    int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    if (!cells) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_load: null cells");
+    if (nx <= 0 || ny <= 0 || nz <= 0) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_load: dimensions %d x %d x %d", nx, ny, nz);
+    if ((uint64_t)nx * (uint64_t)ny >= ((uint64_t)1 << 30) || (uint64_t)nx * (uint64_t)ny * (uint64_t)nz >= ((uint64_t)1 << 30))
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_load: nx * ny * nz >= 2^30");
+    if (chunk_size < 1 || chunk_size > YCGE_WORLD_STORE_MAX_CHUNK) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_load: chunk_size %d is outside 1..%d", chunk_size, YCGE_WORLD_STORE_MAX_CHUNK);
+    WsShape W{};
+    W.nx = nx; W.ny = ny; W.nz = nz; W.S = chunk_size;
+    W.ncx = (nx + chunk_size - 1) / chunk_size; W.ncy = (ny + chunk_size - 1) / chunk_size; W.ncz = (nz + chunk_size - 1) / chunk_size;
+    const uint64_t n_chunks64 = (uint64_t)W.ncx * (uint64_t)W.ncy * (uint64_t)W.ncz;
+    if (n_chunks64 > (uint64_t)YCGE_WORLD_STORE_MAX_CHUNKS) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_load: more than 2^24 chunks");
+    const size_t n_chunks = (size_t)n_chunks64, plane_cells = (size_t)ny * nz, n_i32 = 2 * (size_t)nx * plane_cells, total = n_i32 * 4;
+
+    const std::vector<ycge_ctx *> ctxs = contexts_of(c);
+    std::vector<WorldStore> made(ctxs.size());          // every device's new store, complete before any context takes its own
+    WorldStore &R = made[0];
+    for (WorldStore &s : made) { s.held = true; s.shape = W; }
+    R.occupied.assign(n_chunks, 0);
+    R.bytes = (int64_t)total;
+    if (c->knobs.world_store_host) {
+        R.on_host = true;
+        const auto t0 = std::chrono::steady_clock::now();
+        R.host_cells.assign(cells, cells + n_i32);
+        for (size_t x = 0; x < (size_t)nx; x++)
+            for (size_t y = 0; y < (size_t)ny; y++) {
+                const int32_t *row = cells + 2 * ((x * ny + y) * nz);
+                uint8_t *occ = R.occupied.data() + chunk_of(W, (int)(x / chunk_size), (int)(y / chunk_size), 0);
+                for (size_t z = 0; z < (size_t)nz; z++)
+                    if (row[2 * z] != 0) occ[z / chunk_size] = 1;          // Item1 != 0, :716
+            }
+        R.load_us[0] = us_since(t0);
+        for (size_t i = 1; i < made.size(); i++) made[i].on_host = true;
+    } else {
+        const DeviceGuard guard(c->device);
+        const size_t plane_bytes = plane_cells * 8;
+        const size_t planes = std::max<size_t>(1, std::min<size_t>((size_t)nx, c->knobs.world_store_slab_bytes / plane_bytes));          // per slab
+        const bool direct = host_memory_is_page_locked(cells, total);
+        PinnedBuf stage[2], occ_back;
+        Stream copy_s[YCGE_MAX_DEVICES], kern_s;
+        Event copied[YCGE_MAX_DEVICES][2], c_begin[2], k_begin[2], k_end[2];
+        DevBuf<uint32_t> d_occ;
+        if (ctxs.size() > YCGE_MAX_DEVICES) return c->fail(YCGE_ERR_INTERNAL, "ycge_world_store_load: %d devices", (int)ctxs.size());
+        for (size_t i = 0; i < ctxs.size(); i++) {
+            HIP_TRY(c, hipSetDevice(ctxs[i]->device));
+            HIP_TRY(c, made[i].d_cells.alloc(n_i32));
+            HIP_TRY(c, copy_s[i].ensure());
+            for (int b = 0; b < 2; b++) HIP_TRY(c, copied[i][b].ensure(hipEventDefault));
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, kern_s.ensure());
+        for (int b = 0; b < 2; b++) { HIP_TRY(c, c_begin[b].ensure(hipEventDefault)); HIP_TRY(c, k_begin[b].ensure(hipEventDefault)); HIP_TRY(c, k_end[b].ensure(hipEventDefault)); }
+        HIP_TRY(c, d_occ.alloc(n_chunks));
+        HIP_TRY(c, hipMemsetAsync(d_occ.p, 0, n_chunks * 4, kern_s));
+        HIP_TRY(c, occ_back.reserve(n_chunks * 4));
+        if (!direct) for (int b = 0; b < (planes < (size_t)nx ? 2 : 1); b++) HIP_TRY(c, stage[b].reserve(planes * plane_bytes, hipHostMallocPortable));          // (every device copies from it; one slab: one buffer)
+        // slab k - 2, which went through buffer b, is done with: its copies on every device, its kernel; the root's times taken
+        auto collect = [&](int b) -> int {
+            for (size_t i = 1; i < ctxs.size(); i++) HIP_TRY(c, hipEventSynchronize(copied[i][b]));
+            HIP_TRY(c, hipEventSynchronize(k_end[b]));
+            float ms = 0;
+            HIP_TRY(c, hipEventElapsedTime(&ms, c_begin[b], copied[0][b])); R.load_us[1] += 1000.0 * ms;
+            HIP_TRY(c, hipEventElapsedTime(&ms, k_begin[b], k_end[b])); R.load_us[2] += 1000.0 * ms;
+            return YCGE_OK;
+        };
+        size_t k = 0;
+        for (size_t x0 = 0; x0 < (size_t)nx; x0 += planes, k++) {
+            const int b = (int)(k & 1);
+            const size_t px = std::min(planes, (size_t)nx - x0), off_i32 = 2 * x0 * plane_cells, bytes = px * plane_bytes;
+            if (k >= 2) { rc = collect(b); if (rc != YCGE_OK) return rc; }
+            const int32_t *from = cells + off_i32;
+            if (!direct) {
+                const auto t0 = std::chrono::steady_clock::now();
+                std::memcpy(stage[b].p, from, bytes);
+                R.load_us[0] += us_since(t0);
+                from = (const int32_t *)stage[b].p;
+            }
+            for (size_t i = 0; i < ctxs.size(); i++) {
+                HIP_TRY(c, hipSetDevice(ctxs[i]->device));
+                if (i == 0) HIP_TRY(c, hipEventRecord(c_begin[b], copy_s[0]));
+                HIP_TRY(c, hipMemcpyAsync(made[i].d_cells.p + off_i32, from, bytes, hipMemcpyHostToDevice, copy_s[i]));
+                HIP_TRY(c, hipEventRecord(copied[i][b], copy_s[i]));
+            }
+            HIP_TRY(c, hipSetDevice(c->device));
+            HIP_TRY(c, hipStreamWaitEvent(kern_s, copied[0][b], 0));
+            HIP_TRY(c, hipEventRecord(k_begin[b], kern_s));
+            const int e = ycge_launch_world_store_occupied(R.d_cells.p, &W, (int32_t)x0, (int32_t)px, d_occ.p, kern_s);
+            if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ws_occupied launch failed: %s", hipGetErrorString((hipError_t)e));
+            HIP_TRY(c, hipEventRecord(k_end[b], kern_s));
+        }
+        R.slabs = (int64_t)k;
+        for (size_t j = (k >= 2 ? k - 2 : 0); j < k; j++) { rc = collect((int)(j & 1)); if (rc != YCGE_OK) return rc; }
+        HIP_TRY(c, hipMemcpyAsync(occ_back.p, d_occ.p, n_chunks * 4, hipMemcpyDeviceToHost, kern_s));
+        HIP_TRY(c, hipStreamSynchronize(kern_s));
+        for (size_t i = 0; i < ctxs.size(); i++) { HIP_TRY(c, hipSetDevice(ctxs[i]->device)); HIP_TRY(c, hipStreamSynchronize(copy_s[i])); }
+        const uint32_t *words = (const uint32_t *)occ_back.p;
+        for (size_t i = 0; i < n_chunks; i++) R.occupied[i] = words[i] != 0;
+    }
+    // ---- nothing below fails: the new store replaces the old one (whose memory goes with it); the counters go on
+    R.device_chunks = c->world_store.device_chunks; R.host_chunks = c->world_store.host_chunks;
+    for (size_t i = 0; i < ctxs.size(); i++) {
+        (void)hipSetDevice(ctxs[i]->device);
+        ctxs[i]->world_store = std::move(made[i]);
+    }
+    (void)hipSetDevice(c->device);
+    return YCGE_OK;
+}
+
+int world_store_info(ycge_ctx *c, int32_t dims_out[3], int32_t *chunk_size_out, uint8_t *occupied_out, size_t capacity)
+{
+    const int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    const WorldStore &st = c->world_store;
+    if (!st.held) return c->fail(YCGE_ERR_INVALID_ARG, "%s", kNoStore);
+    if (occupied_out && capacity < st.occupied.size()) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_info: %zu chunks, room for %zu", st.occupied.size(), capacity);
+    if (dims_out) { dims_out[0] = st.shape.nx; dims_out[1] = st.shape.ny; dims_out[2] = st.shape.nz; }
+    if (chunk_size_out) *chunk_size_out = st.shape.S;
+    if (occupied_out) std::memcpy(occupied_out, st.occupied.data(), st.occupied.size());
+    return YCGE_OK;
+}
+
+int world_store_release(ycge_ctx *c)
+{
+    const int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    const int64_t dev = c->world_store.device_chunks, host = c->world_store.host_chunks;
+    for (ycge_ctx *x : contexts_of(c)) { (void)hipSetDevice(x->device); x->world_store = WorldStore{}; }
+    (void)hipSetDevice(c->device);
+    c->world_store.device_chunks = dev; c->world_store.host_chunks = host;
+    return YCGE_OK;
+}
+
+int world_store_attach(ycge_ctx *c, const int32_t *keys, int32_t n, const ycge_grid *proto, int32_t *out_grid_index)
+{
+    int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    if (n < 0 || (n > 0 && (!keys || !out_grid_index)) || !proto) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_attach_world_chunks: bad array (n = %d)", n);
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    WorldStore &st = c->world_store;
+    if (!st.held) return c->fail(YCGE_ERR_INVALID_ARG, "%s", kNoStore);
+    if (n == 0) return YCGE_OK;
+    const WsShape &W = st.shape;
+    static const int32_t no_cells[2] = {0, 0};          // (validate_grid wants a pointer; these grids' cells are never read through it)
+    ycge_grid g0 = *proto;
+    g0.nx = std::min(W.S, W.nx); g0.ny = std::min(W.S, W.ny); g0.nz = std::min(W.S, W.nz); g0.cells = no_cells;          // (the largest chunk)
+    std::string m;
+    const int vrc = validate_grid(g0, 0, c->n_materials, m);
+    if (vrc != YCGE_OK) return c->fail(vrc, "%s", m.c_str());
+    // which keys take a grid: inside the chunk counts (the reference's index exception otherwise, swallowed in EnsureViewLoaded) and occupied (:716-718)
+    StoreCells src(st);
+    std::vector<ycge_grid> grids;
+    std::vector<int> which;
+    for (int k = 0; k < n; k++) {
+        const int32_t cx = keys[3 * k], cy = keys[3 * k + 1], cz = keys[3 * k + 2];
+        if (cx < 0 || cy < 0 || cz < 0 || cx >= W.ncx || cy >= W.ncy || cz >= W.ncz || !st.occupied[chunk_of(W, cx, cy, cz)]) continue;
+        int s[3];
+        clipped(W, cx, cy, cz, s);
+        ycge_grid g = g0;
+        g.nx = s[0]; g.ny = s[1]; g.nz = s[2];
+        g.min_corner.x = proto->min_corner.x + (float)(cx * W.S) * proto->voxel_size.x;          // :720-724, as chunk_grid (ycge_worldgen_scene.cpp)
+        g.min_corner.y = proto->min_corner.y + (float)(cy * W.S) * proto->voxel_size.y;
+        g.min_corner.z = proto->min_corner.z + (float)(cz * W.S) * proto->voxel_size.z;
+        grids.push_back(g); which.push_back(k); src.keys.push_back({{cx, cy, cz}});
+    }
+    std::vector<int32_t> idx(grids.size(), -1);
+    st.slice_ev_used = 0;
+    rc = grids.empty() ? YCGE_OK : attach_grids_from(c, grids.data(), (int32_t)grids.size(), idx.data(), src);
+    if (rc != YCGE_OK) return rc;
+    std::fill(out_grid_index, out_grid_index + n, -1);
+    for (size_t j = 0; j < which.size(); j++) out_grid_index[which[j]] = idx[j];
+    // who sliced: the kernel, or the host (the knob; the device store's rows for the host encoder, a lookup table k_grid_encode does not take)
+    (src.on_device && proto->n_lookup <= YCGE_ENC_MAX_LOOKUP ? st.device_chunks : st.host_chunks) += (int64_t)grids.size();
+    return YCGE_OK;
+}
+
+int world_store_chunk(ycge_ctx *c, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t dims_out[3])
+{
+    int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    const WorldStore &st = c->world_store;
+    if (!st.held) return c->fail(YCGE_ERR_INVALID_ARG, "%s", kNoStore);
+    const WsShape &W = st.shape;
+    if (cx < 0 || cy < 0 || cz < 0 || cx >= W.ncx || cy >= W.ncy || cz >= W.ncz) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_debug_world_store_chunk: no chunk (%d, %d, %d)", cx, cy, cz);
+    int s[3];
+    clipped(W, cx, cy, cz, s);
+    if (dims_out) for (int a = 0; a < 3; a++) dims_out[a] = s[a];
+    if (!cells_out) return YCGE_OK;
+    if (st.on_host) { slice_host(W, st.host_cells.data(), {{cx, cy, cz}}, cells_out); return YCGE_OK; }
+    rc = quiesce(c);          // (copy_out's staging is the frames' too)
+    if (rc != YCGE_OK) return rc;
+    return slice_to_host(c, st, {{cx, cy, cz}}, cells_out);
+}
+
+int world_store_stats(ycge_ctx *c, int64_t *out8)
+{
+    if (!c || !out8) return YCGE_ERR_INVALID_ARG;
+    const WorldStore &st = c->world_store;
+    out8[0] = st.held ? st.bytes : 0; out8[1] = st.slabs;
+    for (int a = 0; a < 3; a++) out8[2 + a] = (int64_t)st.load_us[a];
+    double slice_us = 0;          // the last attach's slice launches, a pair of events per group (the attach has ended: they are all recorded and complete)
+    for (size_t i = 0; i + 1 < st.slice_ev_used; i += 2) {
+        float ms = 0;
+        HIP_TRY(c, hipEventSynchronize(st.slice_ev[i + 1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms, st.slice_ev[i], st.slice_ev[i + 1]));
+        slice_us += 1000.0 * ms;
+    }
+    out8[5] = (int64_t)slice_us; out8[6] = st.device_chunks; out8[7] = st.host_chunks;
+    return YCGE_OK;
+}
+
+}  // namespace ycge_host

@@ -1,0 +1,33 @@
+// ycge_world_store.h - what ycge_world_store.cpp hands the kernels of ycge_world_store.hip: the shape of a resident VG01 world and one
+// launch record per chunk of a slice.
+#pragma once
+#include <stdint.h>
+
+namespace ycge {
+
+#define YCGE_WORLD_STORE_SLAB_BYTES_DEFAULT ((size_t)64 << 20)   // staged per slab of a load: two such page-locked buffers are held while it runs (crossover not yet measured)
+#define YCGE_WORLD_STORE_MAX_CHUNK 1024
+#define YCGE_WORLD_STORE_MAX_CHUNKS (1 << 24)
+
+struct WsShape {                        // the world (cells in VG01 order: x, then y, then z fastest) and its chunks
+    int32_t nx, ny, nz, S;
+    int32_t ncx, ncy, ncz, pad;         // chunks per axis: ceil(n / S); the last one of an axis is clipped
+};
+
+struct WsChunk {
+    uint64_t src;                       // the chunk's first cell in the store, in cells: ((cx * S) * ny + cy * S) * nz + cz * S
+    int32_t sx, sy, sz;                 // its clipped sizes
+    int32_t pad;
+    int32_t *dst;                       // sx * sy * sz cells in ycge_grid.cells order
+};
+static_assert(sizeof(WsChunk) == 32, "WsChunk must be 32 B");
+
+}  // namespace ycge
+
+extern "C" {
+// k_ws_occupied over the x-planes [x0, x0 + planes) of the store at `cells` (the whole store's base): occupied[(cx * ncy + cy) * ncz + cz] |= 1 for
+// every chunk with a cell of mat != 0 in those planes.  The words are the caller's to zero, once, before the first slab.
+int ycge_launch_world_store_occupied(const int32_t *cells, const ycge::WsShape *shape, int32_t x0, int32_t planes, uint32_t *occupied, void *stream);
+// k_ws_slice: chunk k of the m records at `chunks` (device memory) from the store at `cells` into its dst; max_cells: the largest sx * sy * sz among them
+int ycge_launch_world_store_slice(const int32_t *cells, const ycge::WsShape *shape, const ycge::WsChunk *chunks, int m, size_t max_cells, void *stream);
+}

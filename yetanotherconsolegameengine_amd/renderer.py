@@ -238,6 +238,72 @@ class RaytraceRenderer:
         self._check(self.L.ycge_debug_worldgen_stats(self.ctx, out))
         return dict(zip(("device_chunks", "host_chunks", "last_columns_us", "last_fill_us"), (int(v) for v in out)))
 
+    # ---------------------------------------------------------------- the world store (ycge_world_store_load / ycge_scene_attach_world_chunks)
+    def LoadWorld(self, cells_or_path, chunk_size: int):
+        """ycge_world_store_load: a VG01 world made resident on the device, once.  `cells_or_path` is the cells int32 [nx, ny, nz, 2] or the
+        path of a VG01 file, which is mapped and handed over without a copy (its header checked by ycge_world_file_info).  Replaces a store
+        the renderer holds; the scene is not touched.  Returns (nx, ny, nz)."""
+        if isinstance(cells_or_path, np.ndarray):
+            cells = np.ascontiguousarray(cells_or_path, np.int32)
+            if cells.ndim != 4 or cells.shape[3] != 2:
+                raise ValueError("cells must be [nx, ny, nz, 2]")
+            dims = cells.shape[:3]
+        else:
+            if cells_or_path is None or str(cells_or_path).strip() == "":
+                raise ValueError("filename is null or empty.")
+            data = np.memmap(cells_or_path, np.uint8, "r")
+            dims, off = abi.world_file_info(data, self.L)
+            cells = data[off:off + 8 * dims[0] * dims[1] * dims[2]].view("<i4")
+        t0 = time.perf_counter()
+        rc = self.L.ycge_world_store_load(self.ctx, cells.ctypes.data, int(dims[0]), int(dims[1]), int(dims[2]), int(chunk_size))
+        self.stream_call_s["load_world"] = time.perf_counter() - t0
+        self._check(rc)
+        return tuple(int(v) for v in dims)
+
+    def WorldInfo(self):
+        """ycge_world_store_info -> ((nx, ny, nz), chunk_size, occupied uint8 [chunks_x, chunks_y, chunks_z]: 1 where a cell has mat != 0)"""
+        dims, S = (C.c_int32 * 3)(), C.c_int32(0)
+        self._check(self.L.ycge_world_store_info(self.ctx, dims, C.byref(S), None, 0))
+        counts = tuple(-(-int(d) // S.value) for d in dims)
+        occ = np.zeros(counts, np.uint8)
+        self._check(self.L.ycge_world_store_info(self.ctx, dims, C.byref(S), occ.ctypes.data, occ.size))
+        return tuple(int(d) for d in dims), int(S.value), occ
+
+    def AttachWorldChunks(self, keys, proto: abi.Grid) -> list:
+        """ycge_scene_attach_world_chunks: the chunks [(cx, cy, cz), ...] of the store attached like AttachGrids' grids, sliced on the device.
+        proto.min_corner is WorldMin and proto.voxel_size VoxelSize; its lookup table, default material and wireframe settings serve every
+        chunk.  Returns the device indices; -1 for a key outside the world and for a chunk with no cell of mat != 0 (no slot)."""
+        keys = np.ascontiguousarray(np.asarray(keys, np.int32).reshape(-1, 3))
+        n = keys.shape[0]
+        out = (C.c_int32 * max(1, n))(*([-7] * max(1, n)))
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_attach_world_chunks(self.ctx, keys.ctypes.data_as(C.POINTER(C.c_int32)), n, C.byref(proto), out)
+        self.stream_call_s["attach_world"] = time.perf_counter() - t0
+        self._check(rc)
+        return [int(out[k]) for k in range(n)]
+
+    def ReleaseWorld(self) -> None:
+        self._check(self.L.ycge_world_store_release(self.ctx))
+
+    def world_store_chunk(self, cx: int, cy: int, cz: int) -> np.ndarray:
+        """One chunk's raw cells [sx, sy, sz, 2] as the slice writes them (ycge_debug_world_store_chunk); no attach."""
+        fn = self.L.ycge_debug_world_store_chunk
+        fn.restype, fn.argtypes = abi.WORLD_STORE_HOOK_PROTOTYPES["ycge_debug_world_store_chunk"]
+        dims = (C.c_int32 * 3)()
+        self._check(fn(self.ctx, cx, cy, cz, None, dims))
+        cells = np.zeros((dims[0], dims[1], dims[2], 2), np.int32)
+        self._check(fn(self.ctx, cx, cy, cz, cells.ctypes.data, dims))
+        return cells
+
+    def world_store_stats(self) -> dict:
+        """The store's bytes, the last load's slabs and split in microseconds (copies into the staging: wall; host-to-device copies and
+        occupancy kernels: stream time, they overlap), the last AttachWorldChunks' slice kernels, chunks sliced on the device / the host."""
+        fn = self.L.ycge_debug_world_store_stats
+        fn.restype, fn.argtypes = abi.WORLD_STORE_HOOK_PROTOTYPES["ycge_debug_world_store_stats"]
+        out = (C.c_int64 * 8)()
+        self._check(fn(self.ctx, out))
+        return dict(zip(abi.WORLD_STORE_STATS, (int(v) for v in out)))
+
     # ---------------------------------------------------------------- OBJ meshes from file bytes (MeshLoader.FromObj on the device)
     def ParseObj(self, data) -> abi.ObjInfo:
         """ycge_obj_parse: `data` is the file's bytes or a path.  The context holds the parsed OBJ until the next ParseObj, ReleaseObj or close."""

@@ -194,3 +194,52 @@ def stream_generated(renderer, world, proto, center, view_distance_chunks: int, 
         for key, i in zip(todo, renderer.GenerateGrids(world, todo, proto)):
             loaded[key] = i
     return todo, removed, [i for i in gone if i >= 0]
+
+
+def stream_resident(renderer, proto, center, chunk_size: int, view_distance_chunks: int, chunks_y: int, loaded: dict):
+    """One LoadChunksAround tick over a world that is RESIDENT ON THE DEVICE (RaytraceRenderer.LoadWorld): stream_view's tick - the same
+    desired set, the same radial-then-cy order - with AttachChunkFromPreloaded done by the device (RaytraceRenderer.AttachWorldChunks,
+    ycge_scene_attach_world_chunks): no cell is sliced or sent by the host.  `proto` is the abi.Grid whose min_corner is WorldMin, whose
+    voxel_size is VoxelSize and whose lookup serves every chunk; `loaded` (key -> device grid index, -1 for a chunk that took no slot: all
+    air, or outside the world) persists between calls.  Returns (added keys, removed keys, indices of the removed resident grids), as
+    stream_generated does, for the caller to update its objects and detach."""
+    wmin = (proto.min_corner.x, proto.min_corner.y, proto.min_corner.z)
+    vox = (proto.voxel_size.x, proto.voxel_size.y, proto.voxel_size.z)
+    desired = build_desired_set(center, wmin, vox, chunk_size, view_distance_chunks, chunks_y)
+    want = set(desired)
+    removed = [key for key in loaded if key not in want]
+    gone = [loaded.pop(key) for key in removed]
+    cx0, cz0 = center_column(center, wmin, vox, chunk_size)
+    todo = [key for key in desired if key not in loaded]
+    todo.sort(key=lambda k: ((k[0] - cx0) * (k[0] - cx0) + (k[2] - cz0) * (k[2] - cz0), k[1]))
+    if todo:
+        for key, i in zip(todo, renderer.AttachWorldChunks(todo, proto)):
+            loaded[key] = i
+    return todo, removed, [i for i in gone if i >= 0]
+
+
+def load_all_order(dims, chunk_size: int, center, world_min, voxel_size) -> List[Tuple[int, int, int]]:
+    """The keys of every chunk of a world of `dims` cells in the order ReloadFromExistingFile queues them (WorldManager.cs:447-480): by
+    squared distance of (cx, cz) from the centre column - clamped into the world, :465-468 - then cy.  The C# sort is not stable and starts
+    from a HashSet's order, so keys that tie are in no defined order there; here they keep (cx, cy, cz) order."""
+    counts = [(int(d) + chunk_size - 1) // chunk_size for d in dims]
+    cx0 = int(math.floor(float(f32((float(center[0]) - float(world_min[0])) / (float(voxel_size[0]) * chunk_size)))))
+    cz0 = int(math.floor(float(f32((float(center[2]) - float(world_min[2])) / (float(voxel_size[2]) * chunk_size)))))
+    cx0, cz0 = min(max(cx0, 0), counts[0] - 1), min(max(cz0, 0), counts[2] - 1)
+    keys = [(cx, cy, cz) for cx in range(counts[0]) for cy in range(counts[1]) for cz in range(counts[2])]
+    keys.sort(key=lambda k: ((k[0] - cx0) * (k[0] - cx0) + (k[2] - cz0) * (k[2] - cz0), k[1]))
+    return keys
+
+
+def load_all_resident(renderer, proto, center, loaded: Optional[dict] = None):
+    """ReloadFromExistingFile's attach of the whole file (:447-508) over the renderer's resident world: every chunk in load_all_order's
+    order, one AttachWorldChunks call.  Returns (keys in that order, their device indices: -1 for an all-air chunk); `loaded`, when given,
+    receives key -> index as stream_resident keeps it."""
+    dims, chunk_size, _ = renderer.WorldInfo()
+    wmin = (proto.min_corner.x, proto.min_corner.y, proto.min_corner.z)
+    vox = (proto.voxel_size.x, proto.voxel_size.y, proto.voxel_size.z)
+    keys = load_all_order(dims, chunk_size, center, wmin, vox)
+    idx = renderer.AttachWorldChunks(keys, proto)
+    if loaded is not None:
+        loaded.update(zip(keys, idx))
+    return keys, idx
