@@ -195,6 +195,8 @@ namespace ConsoleGame.RayTracing.Native
     {
         public const int AbiVersion = 10;
         public const int MaxDevices = 8;
+        public const int WorldStoreFields = 0;          // YCGE_WORLD_STORE_FIELDS: the window's 2-D fields stay resident
+        public const int WorldStoreCells = 1;           // YCGE_WORLD_STORE_CELLS: the ordinary cell store, written on the device
         private const string Lib = "ycge_hip";       // libycge_hip.so
 
         [DllImport(Lib)] public static extern int ycge_config_default(ref YConfig cfg);
@@ -221,6 +223,9 @@ namespace ConsoleGame.RayTracing.Native
         [DllImport(Lib)] public static extern int ycge_world_store_info(IntPtr ctx, int* dimsOut, int* chunkSizeOut, byte* occupiedOut, UIntPtr capacity);
         [DllImport(Lib)] public static extern int ycge_scene_attach_world_chunks(IntPtr ctx, int* keys, int n, YGrid* proto, int* outGridIndex);
         [DllImport(Lib)] public static extern int ycge_world_store_release(IntPtr ctx);
+        // the store made by the generator on the device (form: WorldStoreFields / WorldStoreCells) and its x-planes read back, VG01 payload order
+        [DllImport(Lib)] public static extern int ycge_world_store_generate(IntPtr ctx, ref YWorld world, int chunksX, int chunksZ, int originBx, int originBz, int form);
+        [DllImport(Lib)] public static extern int ycge_world_store_read(IntPtr ctx, int x0, int planes, int* cellsOut);
         [DllImport(Lib)] public static extern int ycge_scene_update_texture(IntPtr ctx, int textureIndex, IntPtr frame, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_resize(IntPtr ctx, int fbWidth, int fbHeight, int superSample);
         [DllImport(Lib)] public static extern int ycge_set_camera(IntPtr ctx, float* pos, float yaw, float pitch, float fovDeg);

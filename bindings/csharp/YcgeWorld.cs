@@ -50,7 +50,8 @@ namespace ConsoleGame.RayTracing.Native
         }
     }
 
-    /// <summary>A host that HAS a world file (WorldManager.ReloadFromExistingFile) hands its payload over once and then streams by chunk key:
+    /// <summary>A host that HAS a world file (WorldManager.ReloadFromExistingFile) hands its payload over once - or lets the device make the world
+    /// (Generate) and writes the file from it (Save) - and then streams by chunk key:
     /// Load makes the cells resident on the device (the header checked as :414-424 checks it), Attach is AttachChunkFromPreloaded for a list
     /// of keys - the slices are cut on the device, no cell crosses the bus again - and returns the device grid per key, -1 for a key outside
     /// the world and for a chunk with no cell of mat != 0 (the reference attaches none).  proto.MinCorner is WorldMin and proto.VoxelSize
@@ -72,6 +73,41 @@ namespace ConsoleGame.RayTracing.Native
                 throw new System.IO.InvalidDataException(Marshal.PtrToStringAnsi((IntPtr)msg));
             Ycge.Check(ctx, Ycge.ycge_world_store_load(ctx, (int*)(file + (ulong)offset), dims[0], dims[1], dims[2], chunkSize));
             Nx = dims[0]; Ny = dims[1]; Nz = dims[2]; ChunkSize = chunkSize;
+        }
+
+        /// <summary>A host that has NO file yet (VolumeScenes.BuildMinecraftLike with a file name that does not exist: GenerateAndSaveWorld, then
+        /// ReloadFromExistingFile): the window of chunksX x world.ChunksY x chunksZ chunks at block (0, 0) is made on the device and IS the store -
+        /// no cell crosses the bus.  form Ycge.WorldStoreFields keeps the window's 2-D fields (tens of bytes a column) and makes a chunk's cells
+        /// when Attach names it; Ycge.WorldStoreCells writes the ordinary cell store on the device.  Attach, Occupied and Release work as after Load.</summary>
+        public void Generate(IntPtr ctx, YWorld world, int chunksX, int chunksZ, int form = Ycge.WorldStoreFields)
+        {
+            Ycge.Check(ctx, Ycge.ycge_world_store_generate(ctx, ref world, chunksX, chunksZ, 0, 0, form));
+            ChunkSize = world.ChunkSize;
+            Nx = chunksX * ChunkSize; Ny = world.ChunksY * ChunkSize; Nz = chunksZ * ChunkSize;
+        }
+
+        /// <summary>The store as a VG01 file (WorldManager.cs:612-629): the header, then the payload in slabs of whole x-planes read back from the
+        /// device (at most slabBytes each, one plane at least), so the world never exists in host memory in one piece.</summary>
+        public void Save(IntPtr ctx, string path, long slabBytes = 64L << 20)
+        {
+            long planeInts = 2L * Ny * Nz;
+            int per = (int)Math.Max(1, Math.Min(Nx, slabBytes / (planeInts * sizeof(int))));
+            var slab = new int[per * planeInts];
+            var bytes = new byte[slab.Length * sizeof(int)];
+            using (var fs = new System.IO.FileStream(path, System.IO.FileMode.Create, System.IO.FileAccess.Write))
+            using (var bw = new System.IO.BinaryWriter(fs))
+            {
+                bw.Write((byte)'V'); bw.Write((byte)'G'); bw.Write((byte)'0'); bw.Write((byte)'1');
+                bw.Write(Nx); bw.Write(Ny); bw.Write(Nz);
+                for (int x0 = 0; x0 < Nx; x0 += per)
+                {
+                    int planes = Math.Min(per, Nx - x0);
+                    fixed (int* c = slab) Ycge.Check(ctx, Ycge.ycge_world_store_read(ctx, x0, planes, c));
+                    int n = (int)(planes * planeInts * sizeof(int));
+                    Buffer.BlockCopy(slab, 0, bytes, 0, n);
+                    bw.Write(bytes, 0, n);
+                }
+            }
         }
 
         /// <summary>One byte per chunk, [ChunksX, ChunksY, ChunksZ]: 1 when a cell of the chunk has mat != 0 (AttachChunkFromPreloaded's anySolid).</summary>

@@ -481,6 +481,31 @@ int ycge_world_store_info(ycge_ctx *ctx, int32_t dims_out[3], int32_t *chunk_siz
 int ycge_scene_attach_world_chunks(ycge_ctx *ctx, const int32_t *keys /* 3 n */, int32_t n, const ycge_grid *proto, int32_t *out_grid_index /* n */);
 /* Free the store on every device (YCGE_OK when there is none). */
 int ycge_world_store_release(ycge_ctx *ctx);
+/* Make the window of ycge_scene_generate_world the context's world store, ON THE DEVICE: the reference's start-up path is
+ * GenerateAndSaveWorld, ReloadFromExistingFile, LoadChunksAround - here generate, (ycge_world_store_read to save,) and attach by key, with
+ * no cell of the world on the bus.  world, chunks_x, chunks_z, origin_bx, origin_bz: as for ycge_scene_generate_world, with its limits and
+ * refusals; the store's dimensions are chunks * chunk_size per axis and its chunk size is world->chunk_size.  The store's rules above hold:
+ * it belongs to the context, the call touches no scene and joins no frame in flight, it replaces an older store (loaded or generated) only
+ * once it is complete, a refused or failed call leaves the old store as it was, a peer context is refused, every device of a one-process
+ * multi-device context makes its own copy.  Found by symbol lookup; YCGE_ABI_VERSION stays 10.
+ *   form = YCGE_WORLD_STORE_FIELDS: what stays resident is the 2-D fields of the window - column records, feature descriptors, the settled
+ *     anyLeaves fallback flags, the features' reach: tens of bytes a column, where a cell store takes 8 bytes a cell - and the chunk
+ *     occupancy.  No 3-D array of the world exists anywhere; ycge_scene_attach_world_chunks makes each chunk's cells from the fields when its
+ *     key is attached (k_wp_fill), under the same contract word for word, and ycge_world_store_read makes planes (k_wp_planes).
+ *   form = YCGE_WORLD_STORE_CELLS: the ordinary device cell store, its payload written on the device by k_wp_planes in slabs of
+ *     YCGE_WORLD_STORE_SLAB_BYTES; afterwards indistinguishable from ycge_world_store_load of ycge_worldgen_world_cells' result.
+ *   Any other form: YCGE_ERR_INVALID_ARG.
+ *   YCGE_WORLDGEN_HOST or YCGE_WORLD_STORE_HOST at ycge_create: ycge_worldgen_world_cells makes the cells on the host and the store is what
+ *     ycge_world_store_load makes of them (with YCGE_WORLD_STORE_HOST: a host copy), whatever the form. */
+#define YCGE_WORLD_STORE_FIELDS 0
+#define YCGE_WORLD_STORE_CELLS 1
+int ycge_world_store_generate(ycge_ctx *ctx, const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t form);
+/* The x-planes [x0, x0 + planes) of the store in VG01 payload order - x, then y, then z fastest, {mat, meta}: what bw.Write emits at
+ * WorldManager.cs:616-628 - so a host writes the 16 header bytes and then the payload slab by slab.  Any store: a host copy is copied, a
+ * device cell store is copied through page-locked staging (directly into a page-locked cells_out), a fields store makes the planes in a
+ * device slab first.  It may wait for the frames in flight and changes no later frame.  YCGE_ERR_INVALID_ARG with a message: no store,
+ * planes < 1, a range outside 0..nx, a NULL cells_out, a peer context; nothing is written then.  Found by symbol lookup. */
+int ycge_world_store_read(ycge_ctx *ctx, int32_t x0, int32_t planes, int32_t *cells_out /* 2 * planes * ny * nz */);
 
 /* The argument checks of ycge_scene_upload on their own: pure host code, no device and no context needed
  * (every index in range, counts non-negative, pointers present, material kinds known).  Returns YCGE_OK or the

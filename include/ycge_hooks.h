@@ -151,7 +151,8 @@ int ycge_debug_obj_stats(ycge_ctx *c, int64_t *out6);               /* ycge_obj_
 int ycge_debug_obj_ground_stats(ycge_ctx *c, int64_t *out6);        /* ycge_obj_ground: tails the kernels ran, tails the host ran, why the last one went to the host (0: it did not; 1 a walk or a hook passed its bound of n_positions steps, 2 the round cap, 4 YCGE_OBJ_GROUND_HOST, 8 below YCGE_OBJ_GROUND_DEVICE_MIN), the labelling rounds of the last device tail (hook + flatten launches; the last one hooks nothing: 2 on a clean run), the sums of the last tail that fell back to a serial path (0: no chunked sum is built, every sum is the serial chain), wall us of the last tail.  c = NULL: YCGE_ERR_INVALID_ARG and out6[0..4] = the terms one trip of the sum takes, the round cap, YCGE_OBJ_GROUND_DEVICE_MIN_DEFAULT, YCGE_OBJ_GROUND_DEVICE_MIN and YCGE_OBJ_GROUND_HOST as parsed now (no device) */
 int ycge_debug_obj_ground_phases(ycge_ctx *c, int64_t *out5);       /* contexts made with YCGE_OBJ_GROUND_PHASES (a stream synchronise behind every phase): wall us of the last device tail's labelling rounds, count + winner, terms, the three sums, bounds + read-back; zeros otherwise */
 int ycge_debug_world_store_chunk(ycge_ctx *c, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t dims_out[3]);   /* the raw cells of one chunk of the world store as k_ws_slice writes them (a host store: as the host loop does), ycge_grid.cells order, and its clipped sizes; runs no attach.  cells_out = NULL: the sizes alone.  YCGE_ERR_INVALID_ARG: no store, no such chunk */
-int ycge_debug_world_store_stats(ycge_ctx *c, int64_t *out8);       /* the world store: its bytes (0: none), the slabs of the last load, us of that load's copies into the staging (wall), its host-to-device copies and its occupancy kernels (stream time, root device: they overlap each other), us of the last ycge_scene_attach_world_chunks' slice kernels (root device), chunks sliced on the device and on the host since the context was made */
+int ycge_debug_world_store_stats(ycge_ctx *c, int64_t *out8);       /* the world store: the bytes it actually holds (0: none; a fields store: its 2-D fields), the slabs of the last load, us of that load's copies into the staging (wall), its host-to-device copies and its occupancy kernels (stream time, root device: they overlap each other), us of the last ycge_scene_attach_world_chunks' slice kernels (root device), chunks sliced on the device and on the host since the context was made */
+int ycge_debug_world_store_generate_stats(ycge_ctx *c, int64_t *out9);       /* the last ycge_world_store_generate on the root device: the form asked for (-1: none yet), 1 when the host generator made the cells (YCGE_WORLDGEN_HOST / YCGE_WORLD_STORE_HOST), the anyLeaves passes (the last flips nothing), the slabs of k_wp_planes (CELLS form), then us: the 2-D field kernels, the anyLeaves pass loop (WALL time: each pass is a launch, a stream synchronise and a 4-byte read-back), the occupancy kernel and its read-back, the k_wp_planes and k_ws_occupied launches (stream time), the host generator */
 int ycge_debug_read_post_progress(ycge_ctx *c, uint32_t *dst, size_t n_words);               /* k_atrous_stream's per-band records (profiles/post_bands.py) */
 int ycge_debug_read_wave_prof(ycge_ctx *c, unsigned long long *dst, size_t n_u64);            /* per-wavefront begin / end / steps of a profiling build (profiles/mega_prof.py) */
 int ycge_debug_read_coop_stats(ycge_ctx *c, uint64_t out[16]);                               /* -DYCGE_DBG_COOPSTAT builds */

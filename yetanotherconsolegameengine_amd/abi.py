@@ -230,6 +230,9 @@ _PROTOTYPES = {
     "ycge_world_store_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_size_t]),
     "ycge_scene_attach_world_chunks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(Grid), C.POINTER(C.c_int32)]),
     "ycge_world_store_release": (C.c_int, [C.c_void_p]),
+    # the store made by the generator on the device (world: C.byref(abi.World); form: WORLD_STORE_FIELDS / WORLD_STORE_CELLS) and its x-planes read back (cells_out: int32 [planes, ny, nz, 2])
+    "ycge_world_store_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ycge_world_store_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "ycge_scene_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ycge_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]),
@@ -327,7 +330,11 @@ WORLDGEN_HOOK_PROTOTYPES = {
 WORLD_STORE_HOOK_PROTOTYPES = {
     "ycge_debug_world_store_chunk": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "ycge_debug_world_store_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ycge_debug_world_store_generate_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
 }
+WORLD_STORE_FIELDS, WORLD_STORE_CELLS = 0, 1          # ycge_world_store_generate's form (YCGE_WORLD_STORE_FIELDS / _CELLS)
+WORLD_STORE_FORMS = {"fields": WORLD_STORE_FIELDS, "cells": WORLD_STORE_CELLS}
+WORLD_STORE_GENERATE_STATS = ("form", "on_host", "any_leaves_passes", "plane_slabs", "fields_us", "any_leaves_us", "occupied_us", "planes_us", "host_generator_us")
 WORLD_STORE_STATS = ("store_bytes", "slabs", "load_stage_us", "load_h2d_us", "load_occupied_us", "last_slice_us", "device_chunks", "host_chunks")
 # test hooks of the post stage on caller-given inputs (csrc/ycge_post_host.cpp), bound where they are used (RaytraceRenderer.post_probe /
 # exposure_probe); state_out: POST_STATE_WORDS uint32

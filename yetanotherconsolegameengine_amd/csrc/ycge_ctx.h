@@ -7,7 +7,7 @@
 //   ycge_post_host.cpp the post stage (steps 6-8) and its schedules
 //   ycge_resident.cpp  the tile-resident multi-GPU form, its batched launches and emulation loop; read-backs (ycge_read_buffer / _accel)
 //   ycge_query.cpp, ycge_chexel.cpp, ycge_ansi.cpp, ycge_grid_encode.cpp, ycge_worldgen_scene.cpp   scene queries, chexel colours, the ANSI stream, streamed grids, generated chunks
-//   ycge_world_store.cpp   a VG01 world resident on the device, its chunks attached by key
+//   ycge_world_store.cpp   a VG01 world resident on the device - loaded, or generated there - its chunks attached by key, its planes read back
 //   ycge_accel.cpp     the bit-faithful BVH builders
 // Every GPU resource is held through an owner of ycge_own.h: members free themselves, ycge_ctx::~ycge_ctx orders only what has an order.
 // All device work is in the .hip files; there is no CPU implementation of any per-pixel stage.
@@ -43,6 +43,7 @@
 #include "ycge_math.h"
 #include "ycge_own.h"
 #include "ycge_world_store.h"
+#include "ycge_worldgen.h"
 
 extern "C" {
 size_t ycge_wf_sizes(int which);
@@ -505,7 +506,18 @@ struct WorldStore {
     double load_us[3] = {0, 0, 0};                     // ... its copies into the staging (wall), its host-to-device copies and occupancy kernels (stream time, root device)
     std::vector<Event> slice_ev;                       // begin / end of the last attach's slice launches on the root's stream, a pair per group (kept from attach to attach)
     size_t slice_ev_used = 0;
-    int64_t device_chunks = 0, host_chunks = 0;        // chunks sliced by k_ws_slice / by the host, since the context was made
+    int64_t device_chunks = 0, host_chunks = 0;        // chunks sliced by k_ws_slice (made by k_wp_fill, a fields store) / by the host, since the context was made
+    // ycge_world_store_generate, YCGE_WORLD_STORE_FIELDS: no cells anywhere - d_fields holds the WpFields of the window (wp_layout,
+    // ycge_worldgen_cells.h) with the anyLeaves flags settled, and a chunk or a plane is made from them when it is asked for
+    bool fields = false;
+    DevBuf<uint8_t> d_fields;                          // on this context's device
+    ycge::wg::World gen_world{};
+    ycge::wg::Window gen_window{};
+    double last_fill_us = 0;                           // the last attach's k_wp_fill launches on the root (wall: launch to stream idle)
+    // the last generate (root): form asked for, 1 when the host generator made it (the knobs), anyLeaves passes, plane slabs, then
+    // microseconds: field kernels, anyLeaves pass loop, occupancy + read-back, plane kernels (CELLS form; stream time), the host generator
+    int64_t gen_form = -1, gen_on_host = 0, gen_passes = 0, gen_slabs = 0;
+    double gen_us[5] = {0, 0, 0, 0, 0};
 };
 
 struct ycge_ctx {
@@ -933,4 +945,8 @@ int world_store_release(ycge_ctx *c);
 int world_store_attach(ycge_ctx *c, const int32_t *keys, int32_t n, const ycge_grid *proto, int32_t *out_grid_index);
 int world_store_chunk(ycge_ctx *c, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t dims_out[3]);
 int world_store_stats(ycge_ctx *c, int64_t *out8);
+// ... and of ycge_world_store_generate (the generator as the store's source), ycge_world_store_read and ycge_debug_world_store_generate_stats
+int world_store_generate(ycge_ctx *c, const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t form);
+int world_store_read(ycge_ctx *c, int32_t x0, int32_t planes, int32_t *cells_out);
+int world_store_generate_stats(ycge_ctx *c, int64_t *out9);
 } // namespace ycge_host

@@ -341,7 +341,9 @@ int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *o
             ycge_ctx *x = ctxs[i];
             e = hipSetDevice(x->device);
             if (e == hipSuccess) e = larger[i].alloc(want);
-            if (e == hipSuccess && x->d_cells.p && x->d_cells.n) e = hipMemcpy(larger[i].p, x->d_cells.p, x->d_cells.n, hipMemcpyDeviceToDevice);
+            // (the resident bytes AND this call's grids that still fitted the old arena: those were encoded in place, beyond d_cells.n)
+            const size_t keep = x->d_cells.p ? std::max(x->d_cells.n, std::min<size_t>(x->d_cells.cap, (size_t)P.arena_end)) : 0;
+            if (e == hipSuccess && keep) e = hipMemcpy(larger[i].p, x->d_cells.p, keep, hipMemcpyDeviceToDevice);
         }
         if (e != hipSuccess) (void)hipSetDevice(c->device);          // (the larger arenas made so far go with `larger`: a free takes any device's memory, whichever is current)
         HIP_TRY(c, e);

@@ -703,6 +703,25 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// ... the store made by the generator on the device instead of loaded, and its payload read back in x-planes (a VG01 file, slab by slab)
+int ycge_world_store_generate(ycge_ctx *c, const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t form)
+try {
+    return world_store_generate(c, world, chunks_x, chunks_z, origin_bx, origin_bz, form);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_world_store_read(ycge_ctx *c, int32_t x0, int32_t planes, int32_t *cells_out)
+try {
+    return world_store_read(c, x0, planes, cells_out);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_debug_world_store_generate_stats(ycge_ctx *c, int64_t *out9)
+try {
+    return world_store_generate_stats(c, out9);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 // test / profiling hooks: one chunk's raw cells as the slice writes them (no attach); the store's size, the last load's and attach's split (include/ycge_hooks.h)
 int ycge_debug_world_store_chunk(ycge_ctx *c, int32_t cx, int32_t cy, int32_t cz, int32_t *cells_out, int32_t dims_out[3])
 try {

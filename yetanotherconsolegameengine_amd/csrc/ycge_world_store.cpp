@@ -15,10 +15,16 @@
 //
 // YCGE_WORLD_STORE_HOST at ycge_create: the store is a host copy of the payload, the slice is a host loop and the cells go up as an
 // attach's cells do - the yardstick and the fallback.
+//
+// GENERATE (ycge_world_store_generate): the store's source is the generator.  The reference makes the world once (GenerateAndSaveWorld),
+// keeps it (ReloadFromExistingFile) and streams it (LoadChunksAround); here the window's 2-D fields are made on every device by the
+// kernels of ycge_scene_generate_world (wp_make_fields, ycge_worldgen_cells.h) on streams of the call's own, and either STAY - the FIELDS
+// form: tens of bytes a column, a chunk is made by k_wp_fill when its key is attached (FieldCells, WindowCells with the store's fields)
+// - or are turned into the ordinary cell store by k_wp_planes, slab by slab, and freed (the CELLS form).  ycge_world_store_read hands
+// the payload back in x-planes, whatever the store is made of: the way to a VG01 file that never holds the world in one piece.
 #include <algorithm>
 
-#include "ycge_ctx.h"
-#include "ycge_grid_encode.h"
+#include "ycge_worldgen_cells.h"
 
 namespace ycge_host {
 namespace {
@@ -63,21 +69,54 @@ int slice_to_host(ycge_ctx *c, const WorldStore &st, const std::array<int32_t, 3
     return copy_out(c, out, d.p + 256, n_cells * 8);
 }
 
+// how a refusal names chunk `key` of the store, and cell `cell` of it (CellSource::where)
+std::string chunk_where(const WsShape &W, const std::array<int32_t, 3> &key, uint32_t cell)
+{
+    int s[3];
+    clipped(W, key[0], key[1], key[2], s);
+    char buf[160];
+    int n = std::snprintf(buf, sizeof buf, "ycge_scene_attach_world_chunks: chunk (%d, %d, %d)", key[0], key[1], key[2]);
+    if (cell != CellSource::kNoCell) std::snprintf(buf + n, sizeof buf - (size_t)n, ", cell (%u, %u, %u)", cell / (uint32_t)(s[1] * s[2]), cell / (uint32_t)s[2] % (uint32_t)s[1], cell % (uint32_t)s[2]);
+    return buf;
+}
+
+// chunk `key` of the root's fields store into host memory: one k_wp_fill into a buffer of its own, one copy.  Nothing of the context may be in flight (copy_out).
+int fields_chunk_to_host(ycge_ctx *c, const WorldStore &st, const std::array<int32_t, 3> &key, int32_t *out)
+{
+    const size_t S = (size_t)st.shape.S, bytes = S * S * S * 8;
+    const DeviceGuard guard(c->device);
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<uint8_t> d;
+    HIP_TRY(c, d.alloc(512 + bytes));
+    uint8_t head[512] = {0};          // the chunk's record; at 256 its `any` word, zeroed
+    const WgChunk r{key[0], key[1], key[2], 0, (int32_t *)(d.p + 512)};
+    std::memcpy(head, &r, sizeof r);
+    HIP_TRY(c, hipMemcpy(d.p, head, sizeof head, hipMemcpyHostToDevice));
+    WpFields F;
+    wp_layout(st.d_fields.p, (size_t)st.gen_window.nx * st.gen_window.nz, 0, &F);
+    const int e = ycge_launch_worldpregen_fill((const WgChunk *)d.p, 1, &st.gen_world, &st.gen_window, &F, (uint32_t *)(d.p + 256), c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wp_fill launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return copy_out(c, out, d.p + 512, bytes);
+}
+
+// the chunks of one ycge_scene_attach_world_chunks on a fields store: ycge_scene_generate_world's source, filling from the fields the store keeps
+struct FieldCells : WindowCells {
+    WorldStore &store;                     // the root's
+    explicit FieldCells(WorldStore &s) : WindowCells("ycge_scene_attach_world_chunks", s.gen_world, true, s.gen_window), store(s) {}
+    uint8_t *fields_of(ycge_ctx *x) const override { return x->world_store.d_fields.p; }
+    std::string where(size_t k, uint32_t cell) const override { return chunk_where(store.shape, keys[k], cell); }
+    // for the host encoder (a lookup table k_grid_encode does not take)
+    int write(ycge_ctx *root, size_t k, const ycge_grid &, int32_t *cells) override { return fields_chunk_to_host(root, store, keys[k], cells); }
+};
+
 // the chunks of one ycge_scene_attach_world_chunks: grid k of the attach is chunk keys[k]
 struct StoreCells : CellSource {
     WorldStore &store;                     // the root's
     std::vector<std::array<int32_t, 3>> keys;
     explicit StoreCells(WorldStore &s) : store(s) { on_device = !s.on_host; foreign_cells = true; group_max = 32768; }          // (gridDim.y of a slice launch)
     size_t head_bytes(size_t m) const override { return align_up(m * sizeof(WsChunk), 256); }
-    std::string where(size_t k, uint32_t cell) const override
-    {
-        int s[3];
-        clipped(store.shape, keys[k][0], keys[k][1], keys[k][2], s);
-        char buf[160];
-        int n = std::snprintf(buf, sizeof buf, "ycge_scene_attach_world_chunks: chunk (%d, %d, %d)", keys[k][0], keys[k][1], keys[k][2]);
-        if (cell != kNoCell) std::snprintf(buf + n, sizeof buf - (size_t)n, ", cell (%u, %u, %u)", cell / (uint32_t)(s[1] * s[2]), cell / (uint32_t)s[2] % (uint32_t)s[1], cell % (uint32_t)s[2]);
-        return buf;
-    }
+    std::string where(size_t k, uint32_t cell) const override { return chunk_where(store.shape, keys[k], cell); }
     // the host store's slice; or, for the host encoder (a lookup table k_grid_encode does not take) and the count of distinct pairs, the chunk sliced out of the device store
     int write(ycge_ctx *root, size_t k, const ycge_grid &, int32_t *cells) override
     {
@@ -299,7 +338,10 @@ int world_store_attach(ycge_ctx *c, const int32_t *keys, int32_t n, const ycge_g
     const int vrc = validate_grid(g0, 0, c->n_materials, m);
     if (vrc != YCGE_OK) return c->fail(vrc, "%s", m.c_str());
     // which keys take a grid: inside the chunk counts (the reference's index exception otherwise, swallowed in EnsureViewLoaded) and occupied (:716-718)
-    StoreCells src(st);
+    StoreCells store_src(st);
+    FieldCells field_src(st);          // (a fields store: the generator's source, filling from the resident fields)
+    CellSource &src = st.fields ? (CellSource &)field_src : (CellSource &)store_src;
+    std::vector<std::array<int32_t, 3>> &src_keys = st.fields ? field_src.keys : store_src.keys;
     std::vector<ycge_grid> grids;
     std::vector<int> which;
     for (int k = 0; k < n; k++) {
@@ -312,11 +354,13 @@ int world_store_attach(ycge_ctx *c, const int32_t *keys, int32_t n, const ycge_g
         g.min_corner.x = proto->min_corner.x + (float)(cx * W.S) * proto->voxel_size.x;          // :720-724, as chunk_grid (ycge_worldgen_scene.cpp)
         g.min_corner.y = proto->min_corner.y + (float)(cy * W.S) * proto->voxel_size.y;
         g.min_corner.z = proto->min_corner.z + (float)(cz * W.S) * proto->voxel_size.z;
-        grids.push_back(g); which.push_back(k); src.keys.push_back({{cx, cy, cz}});
+        grids.push_back(g); which.push_back(k); src_keys.push_back({{cx, cy, cz}});
     }
     std::vector<int32_t> idx(grids.size(), -1);
-    st.slice_ev_used = 0;
+    field_src.col.assign(src_keys.size(), 0);
+    st.slice_ev_used = 0; st.last_fill_us = 0;
     rc = grids.empty() ? YCGE_OK : attach_grids_from(c, grids.data(), (int32_t)grids.size(), idx.data(), src);
+    st.last_fill_us = field_src.fill_us;
     if (rc != YCGE_OK) return rc;
     std::fill(out_grid_index, out_grid_index + n, -1);
     for (size_t j = 0; j < which.size(); j++) out_grid_index[which[j]] = idx[j];
@@ -340,6 +384,7 @@ int world_store_chunk(ycge_ctx *c, int32_t cx, int32_t cy, int32_t cz, int32_t *
     if (st.on_host) { slice_host(W, st.host_cells.data(), {{cx, cy, cz}}, cells_out); return YCGE_OK; }
     rc = quiesce(c);          // (copy_out's staging is the frames' too)
     if (rc != YCGE_OK) return rc;
+    if (st.fields) return fields_chunk_to_host(c, st, {{cx, cy, cz}}, cells_out);
     return slice_to_host(c, st, {{cx, cy, cz}}, cells_out);
 }
 
@@ -356,7 +401,167 @@ int world_store_stats(ycge_ctx *c, int64_t *out8)
         HIP_TRY(c, hipEventElapsedTime(&ms, st.slice_ev[i], st.slice_ev[i + 1]));
         slice_us += 1000.0 * ms;
     }
+    if (st.held && st.fields) slice_us = st.last_fill_us;          // (a fields store slices nothing: its chunks are made by k_wp_fill)
     out8[5] = (int64_t)slice_us; out8[6] = st.device_chunks; out8[7] = st.host_chunks;
+    return YCGE_OK;
+}
+
+int world_store_generate(ycge_ctx *c, const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t form)
+{
+    int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    const char *why = nullptr;
+    if (worldgen_check(world, &why) != YCGE_OK || worldgen_window_check(world, chunks_x, chunks_z, origin_bx, origin_bz, &why) != YCGE_OK)
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_generate: %s", why);
+    if (form != YCGE_WORLD_STORE_FIELDS && form != YCGE_WORLD_STORE_CELLS) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_generate: form %d", form);
+    const int S = world->chunk_size, chunks_y = world->chunks_y;
+    const wg::World gW = wg::make_world(S, chunks_y, world->world_seed);
+    const wg::Window gN{chunks_x * S, chunks_z * S, origin_bx, origin_bz};
+    WsShape W{};
+    W.nx = gN.nx; W.ny = gW.height; W.nz = gN.nz; W.S = S; W.ncx = chunks_x; W.ncy = chunks_y; W.ncz = chunks_z;
+    const size_t n_cols = (size_t)W.nx * W.nz, n_chunks = (size_t)chunks_x * chunks_y * chunks_z, plane_cells = (size_t)W.ny * W.nz, n_i32 = 2 * n_cols * (size_t)W.ny;
+    if (n_chunks > (size_t)YCGE_WORLD_STORE_MAX_CHUNKS) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_generate: more than 2^24 chunks");
+
+    if (c->knobs.worldgen_host || c->knobs.world_store_host) {          // the host generator's cells, loaded as any payload is: the fallback and a second yardstick
+        std::vector<int32_t> cells(n_i32);
+        const auto t0 = std::chrono::steady_clock::now();
+        world_cells_host(world, chunks_x, chunks_z, origin_bx, origin_bz, cells.data());
+        const double host_us = us_since(t0);
+        rc = world_store_load(c, cells.data(), W.nx, W.ny, W.nz, S);
+        if (rc != YCGE_OK) return rc;
+        WorldStore &st = c->world_store;
+        st.gen_form = form; st.gen_on_host = 1; st.gen_passes = 0; st.gen_slabs = st.slabs;
+        for (double &u : st.gen_us) u = 0;
+        st.gen_us[4] = host_us;
+        return YCGE_OK;
+    }
+
+    const DeviceGuard guard(c->device);
+    const std::vector<ycge_ctx *> ctxs = contexts_of(c);
+    if (ctxs.size() > YCGE_MAX_DEVICES) return c->fail(YCGE_ERR_INTERNAL, "ycge_world_store_generate: %d devices", (int)ctxs.size());
+    std::vector<WorldStore> made(ctxs.size());          // every device's new store, complete before any context takes its own
+    WorldStore &R = made[0];
+    for (WorldStore &s : made) { s.held = true; s.shape = W; s.gen_world = gW; s.gen_window = gN; }
+    const size_t fields_bytes = wp_layout(nullptr, n_cols, n_chunks, nullptr);
+    Stream gen_s[YCGE_MAX_DEVICES];          // the call's own: no stream of a frame is touched
+    PinnedBuf back;                          // the flip counts and the occupancy words come back through it
+    HIP_TRY(c, back.reserve(std::max<size_t>(256, n_chunks * 4)));
+    std::vector<uint32_t> words(n_chunks, 0);
+    int passes = 0;
+    for (size_t i = 0; i < ctxs.size(); i++) {          // (the root first: a peer repeats its passes without reading anything back)
+        HIP_TRY(c, hipSetDevice(ctxs[i]->device));
+        HIP_TRY(c, made[i].d_fields.alloc(fields_bytes));
+        HIP_TRY(c, gen_s[i].ensure());
+        const hipStream_t s = gen_s[i];
+        const WpReadBack read_back = [&](void *dst, const void *from, size_t bytes) -> int {
+            HIP_TRY(c, hipMemcpyAsync(back.p, from, bytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            std::memcpy(dst, back.p, bytes);
+            return YCGE_OK;
+        };
+        rc = wp_make_fields(c, "ycge_world_store_generate", i == 0, made[i].d_fields.p, gW, gN, chunks_y, chunks_z, s, read_back, passes, R.gen_us, words.data());
+        if (rc != YCGE_OK) return rc;
+    }
+    R.occupied.assign(n_chunks, 0);
+    for (size_t k = 0; k < n_chunks; k++) R.occupied[k] = words[k] != 0;
+    R.gen_form = form; R.gen_passes = passes;
+    if (form == YCGE_WORLD_STORE_FIELDS) {
+        for (WorldStore &s : made) s.fields = true;
+        R.bytes = (int64_t)fields_bytes;
+    } else {
+        // the cell store, written where it will lie: x-slabs of k_wp_planes on every device, and on the root k_ws_occupied behind each slab -
+        // the loaded store's occupancy kernel on the generated cells, which must find what k_wp_occupied found in the fields
+        const size_t plane_bytes = plane_cells * 8;
+        const size_t planes = std::max<size_t>(1, std::min<size_t>((size_t)W.nx, c->knobs.world_store_slab_bytes / plane_bytes));          // per slab
+        DevBuf<uint32_t> d_occ;
+        Event k_begin, k_end;
+        size_t slabs = 0;
+        for (size_t i = 0; i < ctxs.size(); i++) {
+            HIP_TRY(c, hipSetDevice(ctxs[i]->device));
+            HIP_TRY(c, made[i].d_cells.alloc(n_i32));
+            WpFields F;
+            wp_layout(made[i].d_fields.p, n_cols, n_chunks, &F);
+            if (i == 0) {
+                HIP_TRY(c, d_occ.alloc(n_chunks));
+                HIP_TRY(c, hipMemsetAsync(d_occ.p, 0, n_chunks * 4, gen_s[0]));
+                HIP_TRY(c, k_begin.ensure(hipEventDefault)); HIP_TRY(c, k_end.ensure(hipEventDefault));
+                HIP_TRY(c, hipEventRecord(k_begin, gen_s[0]));
+            }
+            for (size_t x0 = 0; x0 < (size_t)W.nx; x0 += planes) {
+                const size_t px = std::min(planes, (size_t)W.nx - x0);
+                int e = ycge_launch_worldpregen_planes(&gW, &gN, &F, (int32_t)x0, (int32_t)px, made[i].d_cells.p + 2 * x0 * plane_cells, gen_s[i]);
+                if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wp_planes launch failed: %s", hipGetErrorString((hipError_t)e));
+                if (i != 0) continue;
+                slabs++;
+                e = ycge_launch_world_store_occupied(R.d_cells.p, &W, (int32_t)x0, (int32_t)px, d_occ.p, gen_s[0]);
+                if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ws_occupied launch failed: %s", hipGetErrorString((hipError_t)e));
+            }
+            if (i == 0) HIP_TRY(c, hipEventRecord(k_end, gen_s[0]));
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipMemcpyAsync(back.p, d_occ.p, n_chunks * 4, hipMemcpyDeviceToHost, gen_s[0]));
+        for (size_t i = 0; i < ctxs.size(); i++) { HIP_TRY(c, hipSetDevice(ctxs[i]->device)); HIP_TRY(c, hipStreamSynchronize(gen_s[i])); }
+        HIP_TRY(c, hipSetDevice(c->device));
+        float ms = 0;
+        HIP_TRY(c, hipEventElapsedTime(&ms, k_begin, k_end));
+        R.gen_us[3] = 1000.0 * ms;
+        const uint32_t *seen = (const uint32_t *)back.p;
+        for (size_t k = 0; k < n_chunks; k++)
+            if ((seen[k] != 0) != (R.occupied[k] != 0))
+                return c->fail(YCGE_ERR_INTERNAL, "ycge_world_store_generate: k_wp_occupied and k_ws_occupied disagree on chunk (%d, %d, %d)", (int)(k / ((size_t)chunks_y * chunks_z)),
+                               (int)(k / (size_t)chunks_z % (size_t)chunks_y), (int)(k % (size_t)chunks_z));
+        for (WorldStore &s : made) s.d_fields.release();          // (the cells are the store: the fields have done their work)
+        R.bytes = (int64_t)(n_i32 * 4); R.slabs = R.gen_slabs = (int64_t)slabs;
+    }
+    // ---- nothing below fails: the new store replaces the old one (whose memory goes with it); the counters go on
+    R.device_chunks = c->world_store.device_chunks; R.host_chunks = c->world_store.host_chunks;
+    for (size_t i = 0; i < ctxs.size(); i++) {
+        (void)hipSetDevice(ctxs[i]->device);
+        ctxs[i]->world_store = std::move(made[i]);
+    }
+    (void)hipSetDevice(c->device);
+    return YCGE_OK;
+}
+
+int world_store_read(ycge_ctx *c, int32_t x0, int32_t planes, int32_t *cells_out)
+{
+    int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    const WorldStore &st = c->world_store;
+    if (!st.held) return c->fail(YCGE_ERR_INVALID_ARG, "%s", kNoStore);
+    const WsShape &W = st.shape;
+    if (planes < 1 || x0 < 0 || x0 > W.nx - planes) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_read: planes [%d, %d + %d) of a world of %d", x0, x0, planes, W.nx);
+    if (!cells_out) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_world_store_read: null cells_out");
+    const size_t plane_cells = (size_t)W.ny * W.nz, plane_bytes = plane_cells * 8;
+    if (st.on_host) { std::memcpy(cells_out, st.host_cells.data() + 2 * (size_t)x0 * plane_cells, (size_t)planes * plane_bytes); return YCGE_OK; }
+    rc = quiesce(c);          // (copy_out's staging is the frames' too)
+    if (rc != YCGE_OK) return rc;
+    const DeviceGuard guard(c->device);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!st.fields) return copy_out(c, cells_out, st.d_cells.p + 2 * (size_t)x0 * plane_cells, (size_t)planes * plane_bytes);
+    // a fields store: the planes are made in a device slab of their own, slab by slab, and copied out
+    const size_t per = std::max<size_t>(1, std::min<size_t>((size_t)planes, c->knobs.world_store_slab_bytes / plane_bytes));
+    DevBuf<int32_t> slab;
+    HIP_TRY(c, slab.alloc(2 * per * plane_cells));
+    WpFields F;
+    wp_layout(st.d_fields.p, (size_t)W.nx * W.nz, 0, &F);
+    for (size_t done = 0; done < (size_t)planes; done += per) {
+        const size_t px = std::min(per, (size_t)planes - done);
+        const int e = ycge_launch_worldpregen_planes(&st.gen_world, &st.gen_window, &F, (int32_t)((size_t)x0 + done), (int32_t)px, slab.p, c->stream);
+        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wp_planes launch failed: %s", hipGetErrorString((hipError_t)e));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        rc = copy_out(c, cells_out + 2 * done * plane_cells, slab.p, px * plane_bytes);
+        if (rc != YCGE_OK) return rc;
+    }
+    return YCGE_OK;
+}
+
+int world_store_generate_stats(ycge_ctx *c, int64_t *out9)
+{
+    if (!c || !out9) return YCGE_ERR_INVALID_ARG;
+    const WorldStore &st = c->world_store;
+    out9[0] = st.gen_form; out9[1] = st.gen_on_host; out9[2] = st.gen_passes; out9[3] = st.gen_slabs;
+    for (int a = 0; a < 5; a++) out9[4 + a] = (int64_t)st.gen_us[a];
     return YCGE_OK;
 }
 

@@ -63,4 +63,6 @@ int ycge_launch_worldpregen_occupied(const ycge::wg::World *W, const ycge::wg::W
 // ... and the cells of chunks (cx, cy, cz = chunk coordinates in the window; col is not read), any_solid[k] (zeroed by the caller) per chunk
 int ycge_launch_worldpregen_fill(const ycge::WgChunk *chunks, int n_chunks, const ycge::wg::World *W, const ycge::wg::Window *N, const ycge::WpFields *F, uint32_t *any_solid,
                                  void *stream);
+// ... or the x-planes [x0, x0 + planes) of the finished world in VG01 order (k_wp_planes) to `cells`, 2 * planes * ny * nz int32: plane x0's first cell
+int ycge_launch_worldpregen_planes(const ycge::wg::World *W, const ycge::wg::Window *N, const ycge::WpFields *F, int32_t x0, int32_t planes, int32_t *cells, void *stream);
 }

@@ -20,6 +20,9 @@
 //                    exact chunk by chunk: a small chunk between the ground and a neighbouring tree's canopy can be all Air
 //   k_wp_fill        as k_wg_fill: each lane owns pairs of consecutive cells of a chunk and writes them as one 16-byte store into the area
 //                    k_grid_encode reads; the cell is the base cell, or, at or below the column's reach, the gather
+//   k_wp_planes      the same cells as whole x-planes in VG01 order, one lane per column walking a run of y: the payload of a world file, slab by
+//                    slab (ycge_world_store_read on a fields store), or a device cell store (ycge_world_store_generate, CELLS form).  No LDS,
+//                    no atomics, no scratch (profiles/world_store_generate_resources.txt)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -138,6 +141,32 @@ __global__ __launch_bounds__(kBlock) void k_wp_fill(const WgChunk *__restrict__ 
     if (__syncthreads_or(solid) && threadIdx.x == 0) atomicOr(&any_solid[blockIdx.y], 1u);
 }
 
+// Whole x-planes of the finished world in VG01 order (x, then y, then z fastest).  One lane per column (x, z) and run of y_seg cells along
+// y (blockIdx.y), consecutive lanes along z: the lane loads its record and reach once and walks its run, and per y a wavefront stores one
+// contiguous run of 64 cells (512 bytes) of the row (x, y, .).  The runs along y are there for the lanes' number alone: a slab of 64 MiB
+// of the reference's world is 32 planes of 1024 columns, half a wavefront per SIMD when a lane walks the whole column (the 32 slabs of
+// the 2 GiB world, each followed by k_ws_occupied: 15.4 ms that way, 9.6 ms with runs of 16 - NOTEBOOK.md).  8-byte stores: nz is odd whenever S and chunks_z
+// are, and then no row pair starts 16-byte aligned.  blockIdx.x counts (plane, block of kBlock columns along z).  `cells`: the first
+// cell of plane x0.
+__global__ __launch_bounds__(kBlock) void k_wp_planes(wg::World W, wg::Window N, int x0, int z_blocks, int y_seg, const wg::ColRec *__restrict__ rec,
+                                                      const uint32_t *__restrict__ feat, const uint8_t *__restrict__ fallback, const int32_t *__restrict__ reach,
+                                                      int2 *__restrict__ cells)
+{
+    const int px = (int)(blockIdx.x / (unsigned)z_blocks), z = (int)(blockIdx.x % (unsigned)z_blocks) * kBlock + (int)threadIdx.x;
+    if (z >= N.nz) return;
+    const int x = x0 + px, col = x * N.nz + z, ny = W.height;
+    const int y_begin = (int)blockIdx.y * y_seg, y_end = min(ny, y_begin + y_seg);
+    const wg::ColRec R = rec[col];
+    const int hi = reach[col];
+    int2 *out = cells + (size_t)px * (size_t)ny * (size_t)N.nz + (size_t)z;
+    for (int y = y_begin; y < y_end; y++) {
+        int mat, meta;
+        if (y > hi) wg::cell_at_global(R, y, W, &mat, &meta);
+        else wg::world_cell(rec, feat, fallback, N, W, x, y, z, &mat, &meta);
+        out[(size_t)y * (size_t)N.nz] = make_int2(mat, meta);
+    }
+}
+
 inline unsigned blocks_for(const wg::Window *N) { return (unsigned)(((size_t)N->nx * N->nz + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -169,6 +198,17 @@ extern "C" int ycge_launch_worldpregen_occupied(const wg::World *W, const wg::Wi
     const hipError_t e = hipMemsetAsync(F->occupied, 0, n_chunks * sizeof(uint32_t), s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_wp_occupied, dim3(blocks_for(N)), dim3(kBlock), 0, s, *W, *N, chunks_y, chunks_z, F->rec, F->feat, F->fallback, F->reach, F->occupied);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ycge_launch_worldpregen_planes(const wg::World *W, const wg::Window *N, const WpFields *F, int32_t x0, int32_t planes, int32_t *cells, void *stream)
+{
+    const uint64_t z_blocks = ((uint64_t)N->nz + kBlock - 1) / kBlock, blocks = (uint64_t)(planes > 0 ? planes : 0) * z_blocks;
+    const int y_seg = W->height <= 16 * 65535 ? 16 : 32;          // (gridDim.y; the height is 2^20 at most)
+    const unsigned y_segs = (unsigned)((W->height + y_seg - 1) / y_seg);
+    if (x0 < 0 || planes <= 0 || (int64_t)x0 + planes > N->nx || !cells || blocks > 0x7fffffffull || y_segs == 0 || y_segs > 65535u) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_wp_planes, dim3((unsigned)blocks, y_segs), dim3(kBlock), 0, (hipStream_t)stream, *W, *N, x0, (int)z_blocks, y_seg, F->rec, F->feat, F->fallback, F->reach,
+                       (int2 *)cells);
     return (int)hipGetLastError();
 }
 

@@ -260,6 +260,50 @@ class RaytraceRenderer:
         self._check(rc)
         return tuple(int(v) for v in dims)
 
+    def GenerateWorldStore(self, world: abi.World, chunks_x: int, chunks_z: int, origin=(0, 0), form="fields"):
+        """ycge_world_store_generate: the window of GenerateWorld made the renderer's world store on the device - GenerateAndSaveWorld and
+        ReloadFromExistingFile in one call, with no cell on the bus.  form "fields": the window's 2-D fields stay resident and a chunk's cells
+        are made when its key is attached; "cells": the ordinary cell store, written on the device.  Replaces a store the renderer holds;
+        the scene is not touched.  Returns (nx, ny, nz)."""
+        if form not in abi.WORLD_STORE_FORMS and not isinstance(form, int):
+            raise ValueError("form must be 'fields' or 'cells'")
+        t0 = time.perf_counter()
+        rc = self.L.ycge_world_store_generate(self.ctx, C.byref(world) if world is not None else None, int(chunks_x), int(chunks_z), int(origin[0]), int(origin[1]),
+                                              abi.WORLD_STORE_FORMS.get(form, form))
+        self.stream_call_s["generate_world_store"] = time.perf_counter() - t0
+        self._check(rc)
+        S = int(world.chunk_size)
+        return (chunks_x * S, int(world.chunks_y) * S, chunks_z * S)
+
+    def ReadWorldCells(self, x0: int = 0, planes=None, out: np.ndarray | None = None) -> np.ndarray:
+        """ycge_world_store_read: the x-planes [x0, x0 + planes) of the store (planes None: to the end) as int32 [planes, ny, nz, 2], VG01
+        payload order - whatever the store is made of.  `out`, when given, is a C-contiguous int32 array of that size that receives them
+        (a page-locked one is copied into directly)."""
+        dims, S = (C.c_int32 * 3)(), C.c_int32(0)
+        self._check(self.L.ycge_world_store_info(self.ctx, dims, C.byref(S), None, 0))
+        if planes is None:
+            planes = int(dims[0]) - int(x0)
+        shape = (max(int(planes), 0), int(dims[1]), int(dims[2]), 2)
+        if out is None:
+            out = np.empty(shape, np.int32)
+        elif out.dtype != np.int32 or not out.flags.c_contiguous or out.size != int(np.prod(shape)):
+            raise ValueError("out must be C-contiguous int32 of planes * ny * nz * 2 elements")
+        t0 = time.perf_counter()
+        rc = self.L.ycge_world_store_read(self.ctx, int(x0), int(planes), out.ctypes.data)
+        self.stream_call_s["read_world"] = time.perf_counter() - t0
+        self._check(rc)
+        return out.reshape(shape)
+
+    def world_store_generate_stats(self) -> dict:
+        """The last GenerateWorldStore on the root device: the form asked for, whether the host generator made the cells (the knobs), the
+        anyLeaves passes (the last flips nothing), the slabs of k_wp_planes and, in microseconds, the field kernels, the anyLeaves pass loop
+        (wall time), the occupancy kernel with its read-back, the plane kernels (stream time), the host generator."""
+        fn = self.L.ycge_debug_world_store_generate_stats
+        fn.restype, fn.argtypes = abi.WORLD_STORE_HOOK_PROTOTYPES["ycge_debug_world_store_generate_stats"]
+        out = (C.c_int64 * 9)()
+        self._check(fn(self.ctx, out))
+        return dict(zip(abi.WORLD_STORE_GENERATE_STATS, (int(v) for v in out)))
+
     def WorldInfo(self):
         """ycge_world_store_info -> ((nx, ny, nz), chunk_size, occupied uint8 [chunks_x, chunks_y, chunks_z]: 1 where a cell has mat != 0)"""
         dims, S = (C.c_int32 * 3)(), C.c_int32(0)

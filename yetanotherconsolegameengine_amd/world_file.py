@@ -73,6 +73,35 @@ def pregen_world(lib, world, chunks_x: int, chunks_z: int, path=None, origin=(0,
     return cells
 
 
+SAVE_SLAB_BYTES = 64 << 20          # save_resident's default slab: the payload a host holds at one time
+
+
+def save_resident(renderer, path, slab_planes: Optional[int] = None) -> Tuple[int, int, int]:
+    """The renderer's resident world (LoadWorld or GenerateWorldStore) written as a VG01 file (WorldManager.cs:612-629): the header, then the
+    payload in slabs of `slab_planes` x-planes read back by RaytraceRenderer.ReadWorldCells (ycge_world_store_read) - by default what
+    SAVE_SLAB_BYTES holds, one plane at least - so a 2 GB world never exists in host memory in one piece.  Returns (nx, ny, nz)."""
+    (nx, ny, nz), _, _ = renderer.WorldInfo()
+    if slab_planes is None:
+        slab_planes = SAVE_SLAB_BYTES // (8 * ny * nz)
+    slab_planes = max(1, min(int(slab_planes), nx))
+    with open(path, "wb") as fh:
+        fh.write(MAGIC)
+        fh.write(struct.pack("<iii", nx, ny, nz))
+        for x0 in range(0, nx, slab_planes):
+            fh.write(np.ascontiguousarray(renderer.ReadWorldCells(x0, min(slab_planes, nx - x0)), dtype="<i4").data)
+    return nx, ny, nz
+
+
+def pregen_resident(renderer, world, chunks_x: int, chunks_z: int, path=None, origin=(0, 0), form="fields") -> Tuple[int, int, int]:
+    """pregen_world's counterpart on the device: GenerateAndSaveWorld (WorldManager.cs:510-631) as RaytraceRenderer.GenerateWorldStore - the
+    window becomes the renderer's resident world, ready for stream_resident / load_all_resident - written as a VG01 file slab by slab
+    (save_resident) when `path` is given.  No array of the world is made on the host.  Returns (nx, ny, nz)."""
+    dims = renderer.GenerateWorldStore(world, chunks_x, chunks_z, origin=origin, form=form)
+    if path is not None:
+        save_resident(renderer, path)
+    return dims
+
+
 def center_column(center, world_min, voxel_size, chunk_size: int) -> Tuple[int, int]:
     """(cxCenter, czCenter) of BuildDesiredSet / LoadChunksAround (WorldManager.cs:309-312, 376-379), in binary32 as there."""
     scale_x = f32(f32(voxel_size[0]) * f32(chunk_size))
