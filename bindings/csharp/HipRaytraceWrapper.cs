@@ -24,8 +24,9 @@
 //                section 7).
 //   DeviceAnsiStream - with AnsiPresenter (a DeviceAnsiTerminalRenderer in place of ANSITerminalRenderer): the frame is read back as the
 //                bytes ANSITerminalRenderer.Render() would write for the console (ycge_render_frame_ansi), and the presenter writes them to
-//                stdout as they are - the framebuffer is not written and no cell is walked on the host.  Synchronous frames only (FrameLate
-//                is ignored).  The presenter's other framebuffers - Terminal's entity framebuffer, a menu, a text entity - are composed on the
+//                stdout as they are - the framebuffer is not written and no cell is walked on the host.  With FrameLate the frame is queued
+//                (ycge_render_frame_async_ansi, all four colour / delta combinations): two page-locked stream buffers and records rotate, the
+//                device copies the exact length into one while the presenter writes the other, one frame late.  The presenter's other framebuffers - Terminal's entity framebuffer, a menu, a text entity - are composed on the
 //                device as GetChexelForPoint composes them (ycge_console_set_layers, sent before every frame; INTEGRATION.md section 8).
 //   DeviceAnsiDelta - with DeviceAnsiStream: a frame's bytes are the delta stream (ycge_render_frame_ansi_delta) - only the cells whose
 //                ANSI pair changed since the last frame written, each run behind a cursor move, and always the console's last cell, so the
@@ -156,6 +157,9 @@ public partial class RaytraceEntity
         private readonly DeviceAnsiTerminalRenderer ansi;       // DeviceAnsiStream: the presenter of the streams
         private byte* ansiBuf;                      // the last frame's stream (page-locked memory of the library, ansiCap bytes)
         private ulong ansiCap, ansiLen;
+        private byte* ansiBufLate;                  // FrameLate: the second stream buffer - the frame in flight fills one while the presenter writes the other
+        private ulong ansiCapLate;
+        private YAnsiAsyncResult* ansiRec, ansiRecLate;   // FrameLate: the records of the two (page-locked memory of the library)
         private readonly bool ansiDelta;            // DeviceAnsiDelta: delta streams between keyframes
         private readonly int ansiMergeGap;
         private readonly bool ansiRgb;              // AnsiTrueColor: the 24-bit colour forms of the two calls
@@ -185,7 +189,7 @@ public partial class RaytraceEntity
             ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
             ansiDelta = ansi != null && options.DeviceAnsiDelta; ansiMergeGap = options != null ? options.AnsiMergeGap : 3;
             ansiRgb = ansi != null && options.AnsiTrueColor; ansiTolerance = options != null ? options.AnsiRgbTolerance : 0;
-            frameLate = options != null && options.FrameLate && cfg.NDevices <= 1 && ansi == null;      // (frames in flight are the single-device form; the stream is synchronous)
+            frameLate = options != null && options.FrameLate && cfg.NDevices <= 1;      // (frames in flight are the single-device form)
             deviceColors = options != null && options.DeviceChexelColors;
             generated = options?.GeneratedWorld;
             Ycge.Check(IntPtr.Zero, Ycge.ycge_create(ref cfg, out ctx));
@@ -197,6 +201,41 @@ public partial class RaytraceEntity
         /// <summary>DeviceAnsiStream: the bytes of the last frame, as ANSITerminalRenderer.Render() writes them (valid until the next frame).</summary>
         public ReadOnlySpan<byte> LastAnsiFrame => ansiBuf == null ? ReadOnlySpan<byte>.Empty : new ReadOnlySpan<byte>(ansiBuf, checked((int)ansiLen));
 
+        // FrameLate: the stream queued by the last call is finished first and becomes LastAnsiFrame; the other buffer and record are free again
+        private void FinishAnsiInFlight()
+        {
+            if (!inFlight) return;
+            Ycge.Check(ctx, Ycge.ycge_wait(ctx)); inFlight = false;
+            byte* b = ansiBuf; ansiBuf = ansiBufLate; ansiBufLate = b;
+            ulong cap = ansiCap; ansiCap = ansiCapLate; ansiCapLate = cap;
+            YAnsiAsyncResult* r = ansiRec; ansiRec = ansiRecLate; ansiRecLate = r;
+            if (ansiRec->Status != 0) throw new InvalidOperationException("the device ANSI stream exceeded its buffer; nothing was copied");
+            ansiLen = ansiRec->Length;
+        }
+
+        // FrameLate: this call's frame queued into the second buffer (grown to the stream's bound: nothing is in flight), one frame late
+        private void QueueAnsi(Framebuffer fb, int cw, int ch, UIntPtr bound)
+        {
+            if ((ulong)bound > ansiCapLate)
+            {
+                if (ansiBufLate != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBufLate); ansiBufLate = null; ansiCapLate = 0; }
+                Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(bound, out IntPtr p));
+                ansiBufLate = (byte*)p; ansiCapLate = (ulong)bound;
+            }
+            if (ansiRec == null)
+            {
+                Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer((UIntPtr)sizeof(YAnsiAsyncResult), out IntPtr r0)); ansiRec = (YAnsiAsyncResult*)r0;
+                Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer((UIntPtr)sizeof(YAnsiAsyncResult), out IntPtr r1)); ansiRecLate = (YAnsiAsyncResult*)r1;
+            }
+            if (ansi.ClearPending) ansiLen = 0;                                 // (the frame in hand was built for the old console; a keyframe follows)
+            var req = new YAnsiAsync { ConsoleW = cw, ConsoleH = ch, ViewportX = fb.ViewportX, ViewportY = fb.ViewportY, DefaultFg16 = (int)ansi.DefaultFg,
+                                       DefaultBg16 = (int)ansi.DefaultBg, ClearScreen = ansi.ClearPending ? 1 : 0, Rgb = ansiRgb ? 1 : 0, Delta = ansiDelta ? 1 : 0,
+                                       MergeGap = ansiDelta ? ansiMergeGap : 0, Tolerance = ansiDelta && ansiRgb ? ansiTolerance : 0, Keyframe = 0 };
+            Ycge.Check(ctx, Ycge.ycge_render_frame_async_ansi(ctx, &req, ansiBufLate, (UIntPtr)ansiCapLate, ansiRecLate, null));
+            inFlight = true;
+            ansi.ClearPending = false;
+        }
+
         // one frame into the stream of the presenter's console (the framebuffer at its viewport), the buffer grown to the stream's bound
         private void RenderAnsi(Framebuffer fb)
         {
@@ -204,6 +243,12 @@ public partial class RaytraceEntity
             UIntPtr bound;
             if (ansiRgb) Ycge.Check(ctx, Ycge.ycge_ansi_rgb_stream_bound(cw, ch, out bound));
             else Ycge.Check(ctx, Ycge.ycge_ansi_stream_bound(cw, ch, out bound));
+            if (frameLate)
+            {
+                HipConsoleLayers.Set(ctx, ansi.FrameBuffers, fb);               // (joins: TryFlipAndBlit has waited for the frame in flight already)
+                QueueAnsi(fb, cw, ch, bound);
+                return;
+            }
             if ((ulong)bound > ansiCap)
             {
                 if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; ansiCap = ansiLen = 0; }
@@ -233,7 +278,7 @@ public partial class RaytraceEntity
 
         private void AllocSdr()
         {
-            if (sdr != null || sdrLate != null) { Ycge.ycge_wait(ctx); inFlight = false; }
+            if (sdr != null || sdrLate != null) { Ycge.ycge_wait(ctx); if (inFlight && ansi != null) ansiLen = 0; inFlight = false; }      // (a queued stream nobody wrote: the next one is a keyframe, ycge_resize sees to that)
             if (sdr != null) { Ycge.ycge_free_host_buffer((IntPtr)sdr); sdr = null; }
             if (sdrLate != null) { Ycge.ycge_free_host_buffer((IntPtr)sdrLate); sdrLate = null; }
             FreeColor16();
@@ -448,6 +493,7 @@ public partial class RaytraceEntity
             if (fb.Width != fbW || fb.Height != fbH) Resize(fb, ss);       // RaytraceRenderer.cs:119-120 does the same check
             if (ansi != null)
             {
+                if (frameLate) FinishAnsiInFlight();                           // (it ran beside the host's Update and the presenter's write in between)
                 SyncScene();
                 RenderAnsi(fb);                                                // (the presenter writes the stream: no chexel reaches the framebuffer)
                 return;
@@ -503,6 +549,9 @@ public partial class RaytraceEntity
             if (sdrLate != null) { Ycge.ycge_free_host_buffer((IntPtr)sdrLate); sdrLate = null; }
             FreeColor16();
             if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; }
+            if (ansiBufLate != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBufLate); ansiBufLate = null; }
+            if (ansiRec != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiRec); ansiRec = null; }
+            if (ansiRecLate != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiRecLate); ansiRecLate = null; }
             uploaded?.Dispose();
         }
     }

@@ -184,6 +184,23 @@ namespace ConsoleGame.RayTracing.Native
         public int OnDevice, Reserved;
     }
 
+    // ycge_ansi_async, 48 bytes: the request of ycge_render_frame_async_ansi (passed by address only, as above)
+    public struct YAnsiAsync
+    {
+        public int ConsoleW, ConsoleH, ViewportX, ViewportY, DefaultFg16, DefaultBg16, ClearScreen;
+        public int Rgb;               // 0: 38;5 / 48;5 indices, 1: 24-bit triples
+        public int Delta;             // 0: the full stream, 1: the delta stream
+        public int MergeGap, Tolerance, Keyframe;   // delta only; Tolerance with Rgb only; otherwise 0
+    }
+
+    // ycge_ansi_async_result, 32 bytes: the record the device fills, in page-locked memory of the library (ycge_alloc_host_buffer)
+    public unsafe struct YAnsiAsyncResult
+    {
+        public ulong Length;
+        public fixed uint Info[4];    // {keyframe returned, changed, emitted, run starts}
+        public uint Status, Reserved; // Status 1: the device stream exceeded the capacity, nothing was copied
+    }
+
     public enum YStatus { Ok = 0, InvalidArg = -1, NoScene = -2, Device = -3, Unsupported = -4, OutOfMemory = -5, StackDepth = -6, NoDeviceCode = -7, Internal = -8 }
     public enum YMaterialKind { Constant = 0, Checker = 1, Textured = 2 }
     public enum YExchange { PeerPush = 0, Rccl = 1 }
@@ -275,6 +292,10 @@ namespace ConsoleGame.RayTracing.Native
         // the console's other framebuffers for every stream call above (found by symbol lookup, ABI stays 10); YConsoleLayer, YChexel and
         // HipConsoleLayers: bindings/csharp/YcgeConsole.cs
         [DllImport(Lib)] public static extern int ycge_console_set_layers(IntPtr ctx, YConsoleLayer* layers, int n, int raytraceAt);
+        // the four frame forms of the streams with frames in flight (found by symbol lookup, ABI stays 10): outStream (16-byte aligned) and outResult
+        // in page-locked memory, both the caller's to read after ycge_wait
+        [DllImport(Lib)] public static extern int ycge_render_frame_async_ansi(IntPtr ctx, YAnsiAsync* req, byte* outStream, UIntPtr capacity, YAnsiAsyncResult* outResult,
+                                                                               float* outTopBottomSdr);
         // OBJ meshes from file bytes (MeshLoader.FromObj on the device; HipObjLoader.cs).  info: a YObjInfo
         [DllImport(Lib)] public static extern int ycge_obj_parse_host(byte* text, UIntPtr bytes, float* positions, int* faces, out YObjInfo info, byte* msg, UIntPtr msgBytes);
         [DllImport(Lib)] public static extern int ycge_obj_parse(IntPtr ctx, byte* text, UIntPtr bytes, out YObjInfo info);

@@ -733,6 +733,44 @@ typedef struct ycge_chexel { uint16_t ch; uint16_t pad; float fg[3]; float bg[3]
 typedef struct ycge_console_layer { int32_t x, y, w, h; const ycge_chexel *cells; } ycge_console_layer;
 #define YCGE_CONSOLE_MAX_LAYERS 16
 int ycge_console_set_layers(ycge_ctx *ctx, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at);
+/* --- ANSI streams with frames in flight: the four frame forms above - ycge_render_frame_ansi, _ansi_delta, _ansi_rgb, _ansi_rgb_delta - queued
+ * as ycge_render_frame_async_sdr queues a frame.  The synchronous calls read the stream's length on the host and copy exactly that many
+ * bytes, which takes a synchronisation inside the call; here a kernel behind the stream's kernels (k_ansi_deliver, csrc/ycge_ansi_flight.hip)
+ * copies exactly `length` bytes into the caller's page-locked buffer and fills the caller's record, and the call returns at once.  Added
+ * after ABI 10 without changing it: YCGE_ABI_VERSION stays 10; a host detects the export by symbol lookup.  Video blits stay synchronous.
+ *   req: the console, viewport, defaults and clear_screen of the synchronous calls; rgb picks the colour form, delta the stream; merge_gap,
+ *   tolerance and keyframe are the _delta calls' (tolerance the 24-bit one's) and must be 0 where the form does not read them.
+ *   Bytes.  The bytes, the length and info are those the synchronous export of the same form would have returned, for the same sequence of
+ *   calls on the same context, frame for frame; layers in force are included.  Exactly `length` bytes of out_stream are written, never a
+ *   byte at or past them.  The frame state and the optional SDR are ycge_render_frame_async_sdr's.
+ *   When.  out_stream, out_result and the SDR array are the caller's to read after ycge_wait, or any other call on the context - they all
+ *   join first.  There is no polling contract.  A caller with several frames in flight passes a buffer and a record per frame.
+ *   Delta state.  A queued call counts as handed out when it is queued: the keyframe decision and the flip of the held planes happen then,
+ *   and the rules at the _delta calls hold with "call" read as "queued call".  A synchronous delta behind queued deltas is a delta against
+ *   the last queued frame.  A call that fails behind its argument checks makes the next one a keyframe; a call refused for its arguments
+ *   leaves the state untouched.  The host writes the streams whole and in queue order.
+ *   Refused with YCGE_ERR_INVALID_ARG, the message naming the parameter or value, nothing written then or later: a NULL req, out_stream or
+ *   out_result; out_stream not page-locked over all of [out_stream, out_stream + capacity) or not 16-byte aligned; out_result not page-locked
+ *   or not 8-byte aligned; an SDR array that is not page-locked; capacity below the form's bound; merge_gap outside 0..8, tolerance outside
+ *   0..255; non-zero delta fields on a full stream, a tolerance without rgb; a console that is not positive or whose bound reaches 2^32,
+ *   defaults outside 0..15; and whatever the other frames in flight refuse - peer and multi-device contexts, config.capture_debug,
+ *   config.count_work, the RCCL exchange with lean slabs.
+ *   status.  0; or 1: the device stream exceeded `capacity` (the capacity check above makes that a fault of the library), nothing was copied.
+ *   The call that joins such a frame - ycge_wait or any other - fails once with YCGE_ERR_DEVICE, and the next delta is a keyframe. */
+typedef struct ycge_ansi_async {      /* 48 bytes */
+    int32_t console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen;
+    int32_t rgb;        /* 0: 38;5 / 48;5 indices, 1: 24-bit triples */
+    int32_t delta;      /* 0: the full stream, 1: the delta stream */
+    int32_t merge_gap, tolerance, keyframe;   /* delta only; tolerance with rgb only; otherwise must be 0 */
+} ycge_ansi_async;
+typedef struct ycge_ansi_async_result {   /* 32 bytes, page-locked, 8-byte aligned */
+    uint64_t length;
+    uint32_t info[4];   /* {keyframe returned, changed, emitted, run starts}; a full stream: {1, 0, 0, 0} */
+    uint32_t status;    /* 0, or 1: the device stream exceeded capacity, nothing was copied */
+    uint32_t reserved;
+} ycge_ansi_async_result;
+int ycge_render_frame_async_ansi(ycge_ctx *ctx, const ycge_ansi_async *req, uint8_t *out_stream, size_t capacity,
+                                 ycge_ansi_async_result *out_result, float *out_top_bottom_sdr /* may be NULL */);
 /* --- OBJ meshes from file bytes: MeshLoader.FromObj (RayTracing/MeshLoader.cs:12-149) up to the float soup ycge_mesh.triangles takes, parsed
  * on the device.  Added after ABI 10 without changing it (YCGE_ABI_VERSION stays 10, no struct changes; detect by symbol lookup).
  *   The contract, byte by byte ("the reference's loader" restated correctly; tests/obj_restatement.py is its yardstick):

@@ -80,6 +80,15 @@ int ycge_test_ansi_layers(ycge_ctx *c, int32_t rgb, const uint8_t *plane, int32_
                           int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t delta,
                           int32_t merge_gap, int32_t tolerance, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
                           uint8_t *out_colours, uint16_t *out_glyphs);
+/* ---- the delivery of a stream with frames in flight (csrc/ycge_ansi.cpp, kernel csrc/ycge_ansi_flight.hip): k_ansi_deliver alone.  src
+ * (n_src bytes) is uploaded as the device stream and {length, counts[0..3)} as the words the scan writes; the kernel then copies into
+ * out_stream (capacity bytes, page-locked, 16-byte aligned) and fills out_result (page-locked, 8-byte aligned), and the call synchronises.
+ * keyframe != 0: the record of a full stream, {1, 0, 0, 0}, whatever the counts.  groups > 0: that many workgroups, so that the
+ * grid-stride wrap is reached at small sizes; 0: the product's grid.  length > capacity: nothing is copied, status = 1, and the next call
+ * on the context that joins (ycge_wait) fails once with YCGE_ERR_DEVICE.  Refused: frames in flight on the context, a length within the
+ * capacity but above n_src, what ycge_render_frame_async_ansi refuses of the two buffers */
+int ycge_test_ansi_deliver(ycge_ctx *c, const uint8_t *src, size_t n_src, uint64_t length, size_t capacity, int32_t keyframe, const uint32_t *counts,
+                           int32_t groups, uint8_t *out_stream, ycge_ansi_async_result *out_result);
 /* ---- Video mode (csrc/ycge_video.cpp).  ycge_host_video_tables: host only, no device - for src_w x src_h -> fbW x fbH ss the tables
  * k_video_blit reads, as the library computed them with the C library's sinf: per hi-res column x0 (hiW = fbW*ss entries) and its six
  * normalised weights (6 hiW), per hi-res row y0 (hiH = fbH*2*ss) and weights (6 hiH), and {scale, offX, offY} (VideoRenderer.cs:75-81).

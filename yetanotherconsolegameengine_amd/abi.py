@@ -180,6 +180,21 @@ class FlightInfo(C.Structure):
                 ("frames_outstanding", C.c_int32), ("stage_pipeline", C.c_int32), ("placed_waits", C.c_uint64)]
 
 
+class AnsiAsync(C.Structure):
+    """ycge_ansi_async: the request of ycge_render_frame_async_ansi (ycge_abi_sizeof(12))."""
+    _fields_ = [("console_w", C.c_int32), ("console_h", C.c_int32), ("viewport_x", C.c_int32), ("viewport_y", C.c_int32),
+                ("default_fg16", C.c_int32), ("default_bg16", C.c_int32), ("clear_screen", C.c_int32), ("rgb", C.c_int32), ("delta", C.c_int32),
+                ("merge_gap", C.c_int32), ("tolerance", C.c_int32), ("keyframe", C.c_int32)]
+
+
+class AnsiAsyncResult(C.Structure):
+    """ycge_ansi_async_result: the record k_ansi_deliver fills, in page-locked memory (ycge_abi_sizeof(13))."""
+    _fields_ = [("length", C.c_uint64), ("info", C.c_uint32 * 4), ("status", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ABI_SIZEOF_ANSI_ASYNC, ABI_SIZEOF_ANSI_ASYNC_RESULT = 12, 13
+
+
 def default_config() -> Config:
     """Reference defaults (RaytraceRenderer.cs:31-43,65,218-224) — pure data, no library needed."""
     c = Config()
@@ -285,6 +300,8 @@ _PROTOTYPES = {
                                                  C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     # (layers: an array of abi.ConsoleLayer, or None with n = 0)
     "ycge_console_set_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    # (req: C.byref(abi.AnsiAsync); out_result: the address of an abi.AnsiAsyncResult in page-locked memory)
+    "ycge_render_frame_async_ansi": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
     "ycge_obj_parse_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "ycge_obj_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -373,6 +390,12 @@ ANSI_LAYERS_HOOK_PROTOTYPES = {
     "ycge_test_ansi_layers": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
                                         C.POINTER(C.c_uint16)] + [C.c_int32] * 10 +
                               [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)]),
+}
+# test hook of the delivery of a stream with frames in flight (csrc/ycge_ansi.cpp), bound where it is used (tests/test_gpu_ansi_flight.py): src,
+# n_src, length, capacity, keyframe, counts (3 uint32), groups, out_stream, out_result (an abi.AnsiAsyncResult in page-locked memory)
+ANSI_FLIGHT_HOOK_PROTOTYPES = {
+    "ycge_test_ansi_deliver": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_size_t, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.c_void_p,
+                                         C.c_void_p]),
 }
 # test / profiling hooks of the device-side mesh BVH build (csrc/ycge_mesh_bvh.cpp), bound where they are used (RaytraceRenderer.mesh_bvh_stats,
 # device_mesh_bvh below); res16: MESH_BVH_RES_WORDS uint32, the fallback reasons as the library names them

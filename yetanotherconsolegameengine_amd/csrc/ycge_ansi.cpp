@@ -117,7 +117,20 @@ static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiReq
         e = ycge_launch_ansi_delta(d_plane, d_prev, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
     if (e != 0)
         return c->fail(YCGE_ERR_DEVICE, "%sANSI %sstream launch failed: %s", r.rgb ? "24-bit " : "", delta ? "delta " : "", hipGetErrorString((hipError_t)e));
-    HIP_TRY(c, hipMemcpyAsync(X.ansi_res_host.p, X.ansi_res.p, (delta ? 4 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    if (!X.flight_out) {
+        HIP_TRY(c, hipMemcpyAsync(X.ansi_res_host.p, X.ansi_res.p, (delta ? 4 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        return YCGE_OK;
+    }
+    // a frame in flight (ycge_render_frame_async_ansi): the exact-length copy and the caller's record by k_ansi_deliver, one workgroup a CU,
+    // and behind it the event the next such frame's encode waits for
+    void *d_sticky = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer(&d_sticky, X.flight_sticky.p, 0));
+    // (a length above the device stream's own size is refused as one above the caller's capacity is: no load passes the allocation)
+    e = ycge_launch_ansi_deliver(out, X.ansi_res.p, X.flight_cap < cap ? X.flight_cap : cap, delta ? 0 : 1, X.flight_out, X.flight_rec, static_cast<uint32_t *>(d_sticky), c->compute_units, stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ansi_deliver launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, X.flight_ev.ensure());
+    HIP_TRY(c, hipEventRecord(X.flight_ev, stream));
+    X.flight_stream = stream; X.flight_pending = true;
     return YCGE_OK;
 }
 
@@ -189,6 +202,7 @@ struct AnsiCall {
         ChexelState &X = c->chexels;
         if (!done) X.delta_valid = false;
         X.on = false; X.ansi_on = false; X.delta_on = false; X.ansi = AnsiRequest();
+        X.flight_out = nullptr; X.flight_rec = nullptr; X.flight_cap = 0;
         X.drop_staged();
     }
     // a _delta call's stream is with the caller: this frame's pairs are `prev` from now on
@@ -267,6 +281,127 @@ int frame(ycge_ctx *c, const char *fn, const AnsiRequest &r, uint8_t *out_stream
     rc = deliver(c, X, fn, !r.delta || X.delta_full, bound, out_stream, out_len, r.delta ? out_info : nullptr);
     if (rc != YCGE_OK) return rc;
     call.commit();
+    return YCGE_OK;
+}
+
+// ---- frames in flight (ycge_render_frame_async_ansi; the contract: include/ycge.h).  The call is frame() without deliver(): the stream's
+// launches end in k_ansi_deliver (launch() above), which copies the exact length into the caller's page-locked buffer and fills the record,
+// so nothing is waited for.  The delta state moves at queue time: AnsiCall decides keyframe or delta, commit() flips the held planes.
+
+// what k_ansi_deliver is given: a 16-byte aligned stream buffer, page-locked over all of its capacity, and an 8-byte aligned page-locked record
+int check_flight_buffers(ycge_ctx *c, const char *fn, const uint8_t *out, size_t capacity, const void *rec)
+{
+    if (((uintptr_t)out & 15u) != 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_stream %p is not 16-byte aligned", fn, (const void *)out);
+    if (((uintptr_t)rec & 7u) != 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_result %p is not 8-byte aligned", fn, rec);
+    if (!host_memory_is_page_locked(out, capacity))
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_stream must be page-locked memory over all of its capacity, %zu bytes (ycge_alloc_host_buffer, or whole pages "
+                                             "registered with ycge_pin_host_buffer): the device fills it while the caller runs on", fn, capacity);
+    if (!host_memory_is_page_locked(rec, sizeof(ycge_ansi_async_result)))
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_result must be page-locked memory (ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)", fn);
+    return YCGE_OK;
+}
+
+// the sticky word of the library (join_async looks at it)
+int ensure_flight(ycge_ctx *c, ChexelState &X)
+{
+    if (X.flight_sticky.p) return YCGE_OK;
+    HIP_TRY(c, X.flight_sticky.reserve(64));
+    std::memset(X.flight_sticky.p, 0, 64);
+    return YCGE_OK;
+}
+
+// whether r's queued frame finds every buffer it names as it is: one that has to grow is freed under the frames in flight that read it
+bool flight_buffers_ready(const ycge_ctx *c, const ChexelState &X, const AnsiRequest &r, unsigned long long bound)
+{
+    const size_t tiles = ycge_launch_ansi_tiles((uint32_t)r.cw * (uint32_t)r.ch), cells = (size_t)r.cw * (size_t)r.ch, px = r.rgb ? 8 : 2;
+    if (X.ansi_stream.cap < bound || X.ansi_tiles.cap < 4 * tiles || !X.ansi_res.p || !X.flight_sticky.p) return false;
+    if (r.rgb ? !X.rgb_palette_ready : !X.ansi_palette_ready) return false;
+    if (r.delta && X.delta_held[1 - X.delta_prev].cap < px * (size_t)c->fbW * c->fbH) return false;
+    if (X.layers.n == 0) return true;
+    for (int k = 0; k < 2; k++)
+        if (X.comp_held[k].cap < px * cells || X.glyph_held[k].cap < cells) return false;
+    return !(r.rgb && r.delta && X.comp_cur.cap < px * cells);
+}
+
+AnsiRequest request(bool rgb, int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear);
+AnsiRequest with_delta(AnsiRequest r, int32_t merge_gap, int32_t tolerance, int32_t keyframe);
+
+int frame_async(ycge_ctx *c, const ycge_ansi_async *q, uint8_t *out_stream, size_t capacity, ycge_ansi_async_result *out_result, float *out_top_bottom_sdr)
+{
+    static const char fn[] = "ycge_render_frame_async_ansi";
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!q) return c->fail(YCGE_ERR_INVALID_ARG, "%s: req must not be NULL", fn);
+    if (!out_stream || !out_result) return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_stream and out_result must not be NULL", fn);
+    AnsiRequest r = request(q->rgb != 0, q->console_w, q->console_h, q->viewport_x, q->viewport_y, q->default_fg16, q->default_bg16, q->clear_screen);
+    if (!q->delta && (q->merge_gap || q->tolerance || q->keyframe))
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: merge_gap %d, tolerance %d, keyframe %d on a full stream (delta = 0: all three must be 0)", fn, q->merge_gap, q->tolerance, q->keyframe);
+    if (q->delta && !q->rgb && q->tolerance) return c->fail(YCGE_ERR_INVALID_ARG, "%s: tolerance %d without rgb (must be 0)", fn, q->tolerance);
+    if (q->delta) r = with_delta(r, q->merge_gap, q->tolerance, q->keyframe);
+    unsigned long long bound = 0;
+    size_t unused = 0;
+    int rc = check_stream_args(c, fn, r, out_stream, capacity, &unused, bound);
+    if (rc == YCGE_OK) rc = check_flight_buffers(c, fn, out_stream, capacity, out_result);
+    if (rc != YCGE_OK) return rc;
+    if (out_top_bottom_sdr && !host_memory_is_page_locked(out_top_bottom_sdr, (size_t)c->fbW * c->fbH * 6 * sizeof(float)))
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_top_bottom_sdr must be page-locked memory (ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)", fn);
+    rc = check_in_flight(c);
+    if (rc != YCGE_OK) return rc;
+    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
+        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
+    if (!c->taa_stream) return c->fail(YCGE_ERR_INVALID_ARG, "no second stream: frames in flight need a single-device context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    AnsiCall call(c, r);
+    ChexelState &X = c->chexels;
+    if (!flight_buffers_ready(c, X, r, bound)) {
+        // (the first call of a form or a size: the frames in flight are joined, and what the buffers' makers queued on c->stream is waited for)
+        rc = join_async(c);
+        if (rc == YCGE_OK) rc = ensure_ansi(c, X, r, bound, c->stream);
+        if (rc == YCGE_OK && X.layers.n > 0) rc = ensure_composite(c, X, r);
+        if (rc == YCGE_OK) rc = ensure_flight(c, X);
+        if (rc != YCGE_OK) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    void *d_out = nullptr, *d_rec = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer(&d_out, out_stream, 0));
+    HIP_TRY(c, hipHostGetDevicePointer(&d_rec, out_result, 0));
+    X.flight_out = static_cast<uint8_t *>(d_out); X.flight_rec = d_rec; X.flight_cap = capacity;
+    rc = render_frame_in_flight(c, out_top_bottom_sdr, true);
+    if (rc != YCGE_OK) return rc;
+    call.commit();
+    return YCGE_OK;
+}
+
+// The delivery's test hook: k_ansi_deliver alone on a caller-given device stream and result words, synchronised.  groups: its workgroups
+// (0: the product's grid, one a CU).  Stateless but for the context's stream buffer, which holds src afterwards
+int test_deliver(ycge_ctx *c, const uint8_t *src, size_t n_src, unsigned long long length, size_t capacity, int32_t keyframe, const uint32_t *counts, int32_t groups,
+                 uint8_t *out_stream, ycge_ansi_async_result *out_result)
+{
+    static const char fn[] = "ycge_test_ansi_deliver";
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!out_stream || !out_result || !counts || (n_src > 0 && !src) || groups < 0 || groups > 65536)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad arguments (src %p, n_src %zu, counts %p, groups %d, out_stream %p, out_result %p)", fn, (const void *)src, n_src,
+                       (const void *)counts, groups, (const void *)out_stream, (const void *)out_result);
+    if (length <= capacity && length > n_src) return c->fail(YCGE_ERR_INVALID_ARG, "%s: length %llu is above n_src %zu (the copy would read past the source)", fn, length, n_src);
+    if (c->async_outstanding) return c->fail(YCGE_ERR_INVALID_ARG, "%s: frames are in flight on this context (ycge_wait first)", fn);
+    int rc = check_flight_buffers(c, fn, out_stream, capacity, out_result);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ChexelState &X = c->chexels;
+    if (X.ansi_stream.cap < n_src || !X.ansi_stream.p) HIP_TRY(c, X.ansi_stream.alloc(n_src > 16 ? n_src : 16));
+    if (!X.ansi_res.p) HIP_TRY(c, X.ansi_res.alloc(4));
+    rc = ensure_flight(c, X);
+    if (rc != YCGE_OK) return rc;
+    if (n_src > 0) HIP_TRY(c, hipMemcpy(X.ansi_stream.p, src, n_src, hipMemcpyHostToDevice));
+    const unsigned long long words[4] = {length, counts[0], counts[1], counts[2]};
+    HIP_TRY(c, hipMemcpy(X.ansi_res.p, words, sizeof words, hipMemcpyHostToDevice));
+    void *d_out = nullptr, *d_rec = nullptr, *d_sticky = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer(&d_out, out_stream, 0));
+    HIP_TRY(c, hipHostGetDevicePointer(&d_rec, out_result, 0));
+    HIP_TRY(c, hipHostGetDevicePointer(&d_sticky, X.flight_sticky.p, 0));
+    const int e = ycge_launch_ansi_deliver(X.ansi_stream.p, X.ansi_res.p, capacity, keyframe ? 1 : 0, static_cast<uint8_t *>(d_out), d_rec, static_cast<uint32_t *>(d_sticky),
+                                           groups > 0 ? groups : c->compute_units, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ansi_deliver launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return YCGE_OK;
 }
 
@@ -576,6 +711,22 @@ try {
     const AnsiRequest r = request(true, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
     return video(c, "ycge_video_blit_ansi_rgb_delta", with_delta(r, merge_gap, tolerance, keyframe), frame, src_w, src_h, bytes_per_pixel, out_stream, capacity, out_len,
                  out_info, out_top_bottom_sdr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// The four frame forms with frames in flight (the contract: include/ycge.h): queued, delivered on the device, the caller's after ycge_wait
+int ycge_render_frame_async_ansi(ycge_ctx *c, const ycge_ansi_async *req, uint8_t *out_stream, size_t capacity, ycge_ansi_async_result *out_result,
+                                 float *out_top_bottom_sdr)
+try {
+    return frame_async(c, req, out_stream, capacity, out_result, out_top_bottom_sdr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: k_ansi_deliver alone on a caller-given device stream and result words (test_deliver above)
+int ycge_test_ansi_deliver(ycge_ctx *c, const uint8_t *src, size_t n_src, uint64_t length, size_t capacity, int32_t keyframe, const uint32_t *counts,
+                           int32_t groups, uint8_t *out_stream, ycge_ansi_async_result *out_result)
+try {
+    return test_deliver(c, src, n_src, length, capacity, keyframe, counts, groups, out_stream, out_result);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

@@ -95,6 +95,8 @@ int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool seco
     ChexelState *X = &c->chexels;
     const bool ansi = X->ansi_on;                                                        // (ycge_render_frame_ansi: the pairs stay on the device)
     if (!X->on || (!X->dst[0] && !X->dst[1] && !X->dst[2] && !ansi)) return YCGE_OK;        // (the SDR alone: nothing to encode)
+    // (frames in flight: the stream buffers are one set per context - this frame's encode .. deliver follows the deliver of the frame before)
+    if (ansi && X->flight_pending && X->flight_stream != stream) HIP_TRY(c, hipStreamWaitEvent(stream, X->flight_ev, 0));
     const ChexelLayout L((size_t)c->fbW * c->fbH);
     DevBuf<uint8_t> &out = X->out[second ? 1 : 0];
     if (out.cap < L.total) HIP_TRY(c, out.alloc(L.total));

@@ -128,6 +128,8 @@ int ycge_launch_ansi_rgb_layers_stream(const ycge_ansi::LayersRun *L, const uint
 int ycge_launch_ansi_rgb_layers_delta(const ycge_ansi::LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
                                       int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
                                       hipStream_t stream);
+int ycge_launch_ansi_deliver(const uint8_t *src, const unsigned long long *res, unsigned long long capacity, int full, uint8_t *dst, void *record, uint32_t *sticky,
+                             int groups, hipStream_t stream);
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
 size_t ycge_launch_obj_sizes(int which);
 int ycge_launch_obj_count_lines(const uint8_t *text, uint32_t n, uint32_t first, uint32_t *tiles, void *header, hipStream_t stream);
@@ -463,6 +465,18 @@ struct ChexelState {
     DevBuf<uint8_t> comp_held[2], comp_cur;
     DevBuf<uint16_t> glyph_held[2];
     bool delta_layered = false;
+    // Frames in flight (ycge_render_frame_async_ansi): flight_out / flight_rec are the device aliases of the call at hand's page-locked stream
+    // buffer (flight_cap bytes) and result record - while set, the stream is delivered by k_ansi_deliver instead of the copy of ansi_res.
+    // The stream buffers are one set per context, so a frame's encode .. deliver follows the deliver of the frame before: flight_ev is
+    // recorded behind every such deliver, on flight_stream, and waited for in front of the next encode on another stream while
+    // flight_pending (join_async clears it).  flight_sticky: the word a deliver sets when the stream exceeds the capacity (join_async).
+    uint8_t *flight_out = nullptr;
+    void *flight_rec = nullptr;
+    size_t flight_cap = 0;
+    Event flight_ev;
+    hipStream_t flight_stream = nullptr;
+    bool flight_pending = false;
+    PinnedBuf flight_sticky;
 };
 // what the video blits of one context hold (ycge_video.cpp): made by the first blit, grow-only; nothing a ray-traced frame reads
 struct VideoState {
@@ -913,6 +927,7 @@ int query_scene_changed(ycge_ctx *c);       // ycge_query.cpp: record scene_ev b
 int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second);   // ycge_chexel.cpp: run_post's encode behind the tonemap (a no-op unless a _chexels call asked)
 int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second);                      // ... and its copies behind the SDR read-back
 int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *st);     // ycge_frame.cpp: ycge_render_frame, post stage on request
+int check_in_flight(ycge_ctx *c);                                                        // ycge_frame.cpp: the contexts and configurations the frames in flight refuse
 int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post);                      // ycge_frame.cpp: ycge_render_frame_async(_sdr)
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
 int ensure_tables(ycge_ctx *c, ChexelState &X);                                           // ycge_chexel.cpp: LinearToSrgb8's thresholds on the device, once

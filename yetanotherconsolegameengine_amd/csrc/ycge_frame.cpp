@@ -352,9 +352,19 @@ int fill_stats(ycge_ctx *c, ycge_frame_stats *st, const FrameState &fs, bool did
 
 namespace ycge_host {
 // every other entry point first waits for what ycge_render_frame_async left in flight (the frames-in-flight machinery is below)
+// ... and then looks at the word a k_ansi_deliver sets when a stream exceeded its capacity (ycge_render_frame_async_ansi; ycge_ansi_flight.hip):
+// the in-flight counterpart of deliver()'s "above its bound" refusal.  Reported once: the word is cleared, and the next delta is a keyframe.
+static int ansi_flight_overflow(ycge_ctx *c)
+{
+    volatile uint32_t *word = static_cast<volatile uint32_t *>(c->chexels.flight_sticky.p);
+    if (!word || !*word) return YCGE_OK;
+    *word = 0u;
+    c->chexels.delta_valid = false;
+    return c->fail(YCGE_ERR_DEVICE, "ycge_render_frame_async_ansi: the device wrote a stream above the capacity of its buffer; nothing of it was copied (status = 1 in its record)");
+}
 int join_async(ycge_ctx *c)
 {
-    if (!c->async_outstanding) return YCGE_OK;
+    if (!c->async_outstanding) return ansi_flight_overflow(c);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->stream2) HIP_TRY(c, hipStreamSynchronize(c->stream2));
@@ -362,7 +372,8 @@ int join_async(ycge_ctx *c)
     c->async_outstanding = false;
     c->set_read[0] = c->set_read[1] = c->set_read[2] = false;
     c->post_hist_pending = c->post_busy = c->post_set_pending[0] = c->post_set_pending[1] = c->post_set_pending[2] = false;
-    return YCGE_OK;
+    c->chexels.flight_pending = false;
+    return ansi_flight_overflow(c);
 }
 } // namespace ycge_host
 
@@ -548,12 +559,18 @@ catch (...) { return ycge_host::abi_catch(c); }
 } // extern "C"
 
 namespace ycge_host {
-// post: run steps 6-8 (out_sdr, when not NULL, gets the read-back; the chexel calls may ask for their encoded bytes alone)
-int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
+// the contexts and configurations no frame in flight is queued on (ycge_render_frame_async_ansi asks before it touches its delta state)
+int check_in_flight(ycge_ctx *c)
 {
     if (c->parent || !c->peers.empty() || c->cfg.world_size != 1)
         return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async is the single-device form (tiled frames overlap through ycge_trace_tiles / ycge_resolve_gathered on two streams)");
     if (c->cfg.capture_debug || c->cfg.count_work) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async keeps neither debug captures nor per-frame counters: use ycge_render_frame");
+    return YCGE_OK;
+}
+// post: run steps 6-8 (out_sdr, when not NULL, gets the read-back; the chexel calls may ask for their encoded bytes alone)
+int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
+{
+    { const int rc = check_in_flight(c); if (rc != YCGE_OK) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     if (out_sdr && !host_memory_is_page_locked(out_sdr, (size_t)c->fbW * c->fbH * 6 * sizeof(float)))
         return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async_sdr fills its array while the caller runs on: it must be page-locked memory (ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)");

@@ -875,7 +875,7 @@ try {
     case 0: return sizeof(ycge_vec3); case 1: return sizeof(ycge_material); case 2: return sizeof(ycge_prim); case 3: return sizeof(ycge_mesh);
     case 4: return sizeof(ycge_voxel_lookup); case 5: return sizeof(ycge_grid); case 6: return sizeof(ycge_light); case 7: return sizeof(ycge_scene);
     case 8: return sizeof(ycge_config); case 9: return sizeof(ycge_frame_stats); case 10: return sizeof(ycge_flight_info);
-    case 11: return sizeof(ycge_world);
+    case 11: return sizeof(ycge_world); case 12: return sizeof(ycge_ansi_async); case 13: return sizeof(ycge_ansi_async_result);
     }
     return 0;
 }

@@ -112,6 +112,7 @@ class RaytraceRenderer:
         self._drop_sdr_ring()
         self.__dict__.pop("_chexel_ring", None)          # (the chexel arrays of the frames in flight: after ycge_destroy, as above)
         self.__dict__.pop("_ansi_buf", None)             # (the page-locked stream buffer)
+        self.__dict__.pop("_ansi_ring", None)            # (the stream buffers and records of the frames in flight)
 
     def __enter__(self):
         return self
@@ -772,6 +773,44 @@ class RaytraceRenderer:
         form makes the next call a keyframe.  Returns (bytes, info) or (bytes, info, SDR array) with sdr=True."""
         return self._ansi_call(self.L.ycge_render_frame_ansi_rgb_delta, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
                                rgb=True, delta=(merge_gap, tolerance, bool(keyframe)))
+
+    # ---------------------------------------------------------------- ANSI streams with frames in flight (ycge_render_frame_async_ansi)
+    def RenderAsyncAnsi(self, slot: int, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                        clear_screen: bool = False, rgb: bool = False, delta: bool = False, merge_gap: int = 3, tolerance: int = 0,
+                        keyframe: bool = False, sdr: bool = False) -> None:
+        """Frames in flight with the ANSI stream (ycge_render_frame_async_ansi), as RenderAsyncChexels: queues the frame and returns.  The
+        four forms of TryFlipAndBlitAnsi / AnsiDelta / AnsiRgb / AnsiRgbDelta by `rgb` and `delta`; merge_gap and keyframe are read with
+        delta alone, tolerance with rgb and delta.  The stream is delivered on the device into the wrapper's page-locked buffer of this
+        slot - one slot per frame in flight - and AsyncAnsiResult(slot) hands it out once Wait() has returned.  The bytes are those the
+        synchronous call of the same form would have returned in its place; a queued delta counts as handed out when it is queued."""
+        bound = self._ansi_bound(console_width, console_height, rgb, self.L)
+        ring = self.__dict__.setdefault("_ansi_ring", {})
+        key = int(slot)
+        if key not in ring or ring[key]["stream"].size < bound:            # (the first frame of a larger console: nothing of this slot may be in flight)
+            if key in ring:
+                self.Wait()
+            ring[key] = {"stream": self._page_locked_zeros((bound,), np.uint8)[0], "record": self._page_locked_zeros((C.sizeof(abi.AnsiAsyncResult),), np.uint8)[0]}
+        entry = ring[key]
+        shape = (self.fbH, self.fbW, 2, 3)
+        if sdr and (entry.get("sdr") is None or entry["sdr"].shape != shape):
+            entry["sdr"] = self._page_locked_zeros(shape)[0]
+        entry["want_sdr"] = bool(sdr)
+        req = abi.AnsiAsync(int(console_width), int(console_height), int(viewport[0]), int(viewport[1]), int(default_fg), int(default_bg), int(bool(clear_screen)),
+                            int(bool(rgb)), int(bool(delta)), int(merge_gap) if delta else 0, int(tolerance) if (delta and rgb) else 0, int(bool(keyframe)) if delta else 0)
+        out = entry["stream"]
+        self._check(self.L.ycge_render_frame_async_ansi(self.ctx, C.byref(req), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, entry["record"].ctypes.data,
+                                                        entry["sdr"].ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
+
+    def AsyncAnsiResult(self, slot: int):
+        """What the frame queued last into `slot` delivered - valid after Wait(): (bytes, info) or, when it was queued with sdr=True,
+        (bytes, info, SDR array), info as TryFlipAndBlitAnsiDelta's (a full stream: keyframe 1, the counts 0).  Raises when the record's
+        status is not 0 (the device stream exceeded the buffer; nothing was copied)."""
+        entry = self.__dict__.get("_ansi_ring", {})[int(slot)]
+        rec = abi.AnsiAsyncResult.from_buffer_copy(entry["record"].tobytes())
+        if rec.status != 0:
+            raise abi.YcgeError(abi.YCGE_ERR_DEVICE, f"the ANSI stream of slot {slot} was not delivered (status {rec.status}, length {rec.length})")
+        stream, info = entry["stream"][:rec.length].tobytes(), dict(zip(self.DELTA_INFO, (int(v) for v in rec.info)))
+        return (stream, info, entry["sdr"]) if entry["want_sdr"] else (stream, info)
 
     # ---------------------------------------------------------------- the console's other framebuffers (ycge_console_set_layers)
     def SetConsoleLayers(self, layers=(), raytrace_at: int = 0):
