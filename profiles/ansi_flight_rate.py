@@ -2,7 +2,7 @@
 synchronous export of each form and against ycge_render_frame_async_chexels with the ANSI pairs alone (the same frame work and a 2.1 MB
 read-back), in one process on one GPU.  The method of profiles/ansi_rgb_rate.py.
 
-    python profiles/ansi_flight_rate.py --part rate --out DIR [--rounds 8 --frames 20]   the periods, at rest and moving
+    python profiles/ansi_flight_rate.py --part rate --out DIR [--rounds 8 --frames 20 --parent-lib PATH]   the periods, at rest and moving
     python profiles/ansi_flight_rate.py --part kernel --out DIR       frames in flight and k_ansi_deliver through its hook (for rocprofv3 --kernel-trace)
     python profiles/ansi_flight_rate.py --part copies --out DIR       the synchronous forms (for a rocprofv3 --memory-copy-trace run of its own)
     python profiles/ansi_flight_rate.py --part merge --out DIR [--kernel-trace CSV --copy-trace CSV]     -> profiles/ansi_flight_rate.json
@@ -16,6 +16,10 @@ Two expectations are written down with the numbers, not tuned for: the in-flight
 the same run by more than that form's round-to-round spread (max - min), and within the async-chexels leg's own spread of that leg.
 The kernel part runs k_ansi_deliver through ycge_test_ansi_deliver at one, two and four workgroups a CU for a full 256-colour stream's
 size and a resting delta's, the three grids alternating launch by launch; the merge names the trace's launches by their order.
+With --parent-lib, the parent commit's library (built elsewhere from the parent's sources) is loaded beside the product's, and two legs of
+the parent and one of the product alternate round by round: in the first round the same frames at rest on each - the second call of each
+synchronous form and of the delta in flight, its length and sha256 (`streams`) - and in every round the five legs in flight at rest
+(`against_parent`, parent_check below).
 Not measured: the terminal that consumes the bytes, and the C# wrapper (never compiled here).
 """
 from __future__ import annotations
@@ -42,12 +46,12 @@ FULL_BYTES, DELTA_BYTES = 3_100_000, 17_000          # a full 256-colour stream 
 TRACED, SETTLE_TRACED, HOOK_LAUNCHES = 20, 30, 12     # frames a traced leg runs, frames at rest before them, launches per hook setting
 
 
-def renderer():
+def renderer(lib=None):
     from yetanotherconsolegameengine_amd import scenes
     from yetanotherconsolegameengine_amd.renderer import RaytraceRenderer
     from yetanotherconsolegameengine_amd.scene import flatten
     sc, w, h, ss, pose = scenes.config_scene(4)
-    g = RaytraceRenderer(flatten(sc), w, h, pose.get("fov", 45.0), ss)
+    g = RaytraceRenderer(flatten(sc), w, h, pose.get("fov", 45.0), ss, lib=lib)
     g.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
     return g, pose
 
@@ -137,7 +141,68 @@ def rounds_of(g, pose, moving, rounds, frames):
     return res
 
 
-def part_rate(out: Path, rounds: int, frames: int, settle: int):
+def parent_check(per):
+    """per: (leg, form) -> [ms a frame of each round], the legs "parent A", "branch", "parent B" (two of the parent's, as
+    profiles/ansi_layers_rate.py has them: what differs between two legs of ONE build is part of the noise) -> form -> the parent's median
+    and spread (max - min) over the rounds of both its legs, each leg's median, and whether the branch's lies at or below the parent's
+    median plus its spread.  Every round of a leg runs on a context of its own, the only one alive: a context's place among the live
+    contexts of a process changes its period whichever library made it (of three, the second ran its frames in flight 0.25 ms slower
+    and the third its synchronous frames 0.2 ms slower)"""
+    res = {}
+    for f in dict.fromkeys(f for _, f in per):
+        p, b = per[("parent A", f)] + per[("parent B", f)], per[("branch", f)]
+        res[f] = {"parent_median_ms": float(np.median(p)), "parent_spread_ms": float(np.max(p) - np.min(p)), "branch_median_ms": float(np.median(b)),
+                  "branch_spread_ms": float(np.max(b) - np.min(b)), "parent_A_median_ms": float(np.median(per[("parent A", f)])),
+                  "parent_B_median_ms": float(np.median(per[("parent B", f)]))}
+        res[f]["within_allowance"] = bool(res[f]["branch_median_ms"] <= res[f]["parent_median_ms"] + res[f]["parent_spread_ms"])
+    return res
+
+
+def streams_at_rest(g):
+    """on a context converged at rest: the second call of each synchronous form (behind another form the first delta is a keyframe), then of
+    the delta in flight -> {form: [length, sha256]}"""
+    import hashlib
+    cw, ch = g.fbW + 1, g.fbH + 1
+    res = {}
+    for form in FORMS:
+        sync_call(g, form)
+        n = sync_call(g, form)
+        res[f"synchronous {form}"] = [n, hashlib.sha256(g._ansi_out(cw, ch, True)[:n].tobytes()).hexdigest()]
+    for slot in (0, 1):
+        g.RenderAsyncAnsi(slot, cw, ch, delta=True, merge_gap=GAP)
+        g.Wait()
+    data = bytes(g.AsyncAnsiResult(1)[0])
+    res["in flight ansi delta"] = [len(data), hashlib.sha256(data).hexdigest()]
+    return res
+
+
+def against_parent(parent_lib, rounds: int, frames: int, settle: int):
+    from yetanotherconsolegameengine_amd import abi
+    P = abi.load_library(parent_lib)
+    libs = {"parent A": P, "branch": None, "parent B": P}
+    flight = [leg for leg in LEGS if leg.startswith("in flight")]
+    per, streams = {(b, leg): [] for b in libs for leg in flight}, {}
+    for r in range(rounds):
+        for b in (list(libs) if r % 2 == 0 else list(libs)[::-1]):
+            g, pose = renderer(libs[b])
+            for _ in range(settle):
+                sync_call(g, "ansi delta")
+            if r == 0:
+                streams[b] = streams_at_rest(g)
+            fns = legs(g, pose, False)
+            for leg in flight:
+                fns[leg](4)
+            for leg in flight:
+                if "delta" in leg:
+                    fns[leg](1)          # (behind another form the first delta is a keyframe: not timed)
+                t0 = time.perf_counter()
+                fns[leg](frames)
+                per[(b, leg)].append((time.perf_counter() - t0) * 1e3 / frames)
+            g.close()
+    return {"streams": dict(streams, equal_on_both_builds=streams["parent A"] == streams["branch"] == streams["parent B"]), "at_rest": parent_check(per)}
+
+
+def part_rate(out: Path, rounds: int, frames: int, settle: int, parent_lib=None):
     g, pose = renderer()
     for _ in range(settle):              # the camera rests: TAA converges
         sync_call(g, "ansi delta")
@@ -146,6 +211,8 @@ def part_rate(out: Path, rounds: int, frames: int, settle: int):
     res["moving"] = rounds_of(g, pose, True, rounds, frames)
     res["device"] = str(g.device_info())
     g.close()
+    if parent_lib:
+        res["against_parent"] = against_parent(parent_lib, rounds, frames, settle)
     print(json.dumps(res), flush=True)
     (out / "rate.json").write_text(json.dumps(res, indent=1))
 
@@ -264,9 +331,10 @@ if __name__ == "__main__":
     ap.add_argument("--settle", type=int, default=60)
     ap.add_argument("--kernel-trace", default=None)
     ap.add_argument("--copy-trace", default=None)
+    ap.add_argument("--parent-lib", default=None, help="rate: the parent commit's library, measured beside the product's")
     a = ap.parse_args()
     out = Path(a.out); out.mkdir(parents=True, exist_ok=True)
-    if a.part == "rate": part_rate(out, a.rounds, a.frames, a.settle)
+    if a.part == "rate": part_rate(out, a.rounds, a.frames, a.settle, a.parent_lib)
     elif a.part == "kernel": part_kernel(out)
     elif a.part == "copies": part_copies(out)
     else: part_merge(out, a.kernel_trace, a.copy_trace)

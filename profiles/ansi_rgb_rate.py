@@ -2,7 +2,7 @@
 stream takes per tolerance and per merge_gap, with the camera at rest and with it moving every frame, and what a synchronous frame of each
 form costs against the 256-colour forms in the same process.  One GPU, one process; the method of profiles/ansi_delta_rate.py.
 
-    python profiles/ansi_rgb_rate.py [--frames 60 --rounds 8 --frames-per-round 20]     -> profiles/ansi_rgb_rate.json
+    python profiles/ansi_rgb_rate.py [--frames 60 --rounds 8 --frames-per-round 20 --parent-lib PATH]     -> profiles/ansi_rgb_rate.json
 
 Config 4 at 1920 x 540 under a 1921 x 541 console.  Bytes: for each tolerance in {0, 1, 2, 4, 8} at the default merge_gap 3, and for each
 merge_gap in {0, 1, 3, 8} at tolerance 2, a fresh context renders frames 1..60, the first a keyframe, once with the camera where the
@@ -12,7 +12,9 @@ length and the last frame's out_info.  The 256-colour delta at merge_gap 3 runs 
 context that has converged at rest, every destination page-locked memory of the library, the host clock around the call, the median of
 the rounds.  The check: the median of `_ansi_rgb_delta` lies within max - min of `_ansi_delta`'s rounds of `_ansi_delta`'s median, plus
 the copy time of the extra bytes priced from the two full streams ((ms_rgb - ms_256) / (bytes_rgb - bytes_256): kernels' stores and the
-copy together, so an upper price).  Nothing here measures the terminal that consumes the bytes.
+copy together, so an upper price).  With --parent-lib, the parent commit's library (built elsewhere from the parent's sources) is loaded
+beside the product's: two legs of the parent and one of the product run the five forms, alternated round by round (`rate_against_parent`,
+parent_check below).  Nothing here measures the terminal that consumes the bytes.
 """
 from __future__ import annotations
 
@@ -35,12 +37,12 @@ TOLERANCES, GAPS, DEFAULT_GAP, GAP_TOLERANCE = (0, 1, 2, 4, 8), (0, 1, 3, 8), 3,
 FORMS = ("ansi rgb delta T=0", "ansi rgb delta T=2", "ansi delta", "ansi rgb stream", "ansi stream")
 
 
-def renderer():
+def renderer(lib=None):
     from yetanotherconsolegameengine_amd import scenes
     from yetanotherconsolegameengine_amd.renderer import RaytraceRenderer
     from yetanotherconsolegameengine_amd.scene import flatten
     sc, w, h, ss, pose = scenes.config_scene(4)
-    g = RaytraceRenderer(flatten(sc), w, h, pose.get("fov", 45.0), ss)
+    g = RaytraceRenderer(flatten(sc), w, h, pose.get("fov", 45.0), ss, lib=lib)
     g.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
     return g, pose
 
@@ -88,13 +90,58 @@ def sequence(frames: int, moving: bool, gap: int, tol):
             "delta_bytes_last": deltas[-1][0], "last_frame": dict(zip(("bytes", "keyframe", "changed", "emitted", "runs"), rows[-1]))}
 
 
-def rate(rounds: int, frames: int, settle: int):
-    g, _ = renderer()
+def form_fns(g, settle: int):
+    """the five forms on g, converged at rest"""
     rgb_delta, delta, rgb_stream, stream = frame_fns(g)
-    fns = {"ansi rgb delta T=0": lambda: rgb_delta(DEFAULT_GAP, 0), "ansi rgb delta T=2": lambda: rgb_delta(DEFAULT_GAP, 2), "ansi delta": lambda: delta(DEFAULT_GAP),
-           "ansi rgb stream": rgb_stream, "ansi stream": stream}
     for _ in range(settle):              # the camera rests: TAA converges
         delta(DEFAULT_GAP)
+    return {"ansi rgb delta T=0": lambda: rgb_delta(DEFAULT_GAP, 0), "ansi rgb delta T=2": lambda: rgb_delta(DEFAULT_GAP, 2), "ansi delta": lambda: delta(DEFAULT_GAP),
+            "ansi rgb stream": rgb_stream, "ansi stream": stream}
+
+
+def parent_check(per):
+    """per: (leg, form) -> [ms a frame of each round], the legs "parent A", "branch", "parent B" (two of the parent's, as
+    profiles/ansi_layers_rate.py has them: what differs between two legs of ONE build is part of the noise) -> form -> the parent's median
+    and spread (max - min) over the rounds of both its legs, each leg's median, and whether the branch's lies at or below the parent's
+    median plus its spread.  Every round of a leg runs on a context of its own, the only one alive: a context's place among the live
+    contexts of a process changes its period whichever library made it (of three, the second ran its frames in flight 0.25 ms slower
+    and the third its synchronous frames 0.2 ms slower)"""
+    res = {}
+    for f in dict.fromkeys(f for _, f in per):
+        p, b = per[("parent A", f)] + per[("parent B", f)], per[("branch", f)]
+        res[f] = {"parent_median_ms": float(np.median(p)), "parent_spread_ms": float(np.max(p) - np.min(p)), "branch_median_ms": float(np.median(b)),
+                  "branch_spread_ms": float(np.max(b) - np.min(b)), "parent_A_median_ms": float(np.median(per[("parent A", f)])),
+                  "parent_B_median_ms": float(np.median(per[("parent B", f)]))}
+        res[f]["within_allowance"] = bool(res[f]["branch_median_ms"] <= res[f]["parent_median_ms"] + res[f]["parent_spread_ms"])
+    return res
+
+
+def rate_against_parent(parent_lib, rounds: int, frames: int, settle: int):
+    from yetanotherconsolegameengine_amd import abi
+    P = abi.load_library(parent_lib)
+    libs = {"parent A": P, "branch": None, "parent B": P}
+    per = {(b, f): [] for b in libs for f in FORMS}
+    for r in range(rounds):
+        for b in (list(libs) if r % 2 == 0 else list(libs)[::-1]):
+            g, _ = renderer(libs[b])
+            fns = form_fns(g, settle)
+            for f in FORMS:
+                for _ in range(5):
+                    fns[f]()
+            for f in FORMS:
+                if "delta" in f:
+                    fns[f]()             # (behind another form the first delta call is a keyframe: not timed)
+                t0 = time.perf_counter()
+                for _ in range(frames):
+                    fns[f]()
+                per[(b, f)].append((time.perf_counter() - t0) * 1e3 / frames)
+            g.close()
+    return dict(parent_check(per), rounds=rounds, frames_per_round=frames, frames_at_rest_before=settle)
+
+
+def rate(rounds: int, frames: int, settle: int):
+    g, _ = renderer()
+    fns = form_fns(g, settle)
     for f in FORMS:
         for _ in range(5):
             fns[f]()
@@ -128,6 +175,7 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--frames-per-round", type=int, default=20)
+    ap.add_argument("--parent-lib", default=None, help="the parent commit's library, measured beside the product's")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "ansi_rgb_rate.json"))
     a = ap.parse_args()
     m = {"what": "the 24-bit colour ANSI streams on the device (ycge_render_frame_ansi_rgb / _rgb_delta) on one MI355X; profiles/ansi_rgb_rate.py",
@@ -147,4 +195,7 @@ if __name__ == "__main__":
               "256-colour", m[name]["ansi_delta_256"]["delta_bytes_median"], flush=True)
     m["rate"] = rate(a.rounds, a.frames_per_round, a.frames)
     print(json.dumps(m["rate"]), flush=True)
+    if a.parent_lib:
+        m["rate_against_parent"] = rate_against_parent(a.parent_lib, a.rounds, a.frames_per_round, a.frames)
+        print(json.dumps(m["rate_against_parent"]), flush=True)
     Path(a.out).write_text(json.dumps(m, indent=1) + "\n")

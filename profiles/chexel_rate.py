@@ -1,7 +1,7 @@
 """Device chexel colours (ycge_render_frame_chexels): what a frame costs when the host asks for presenter bytes instead of, or beside,
 the f32 SDR array.  Config 4 (1920 x 540 console), one GPU, one process, the forms alternated round by round.
 
-    python profiles/chexel_rate.py --part rate   --out DIR [--rounds R --frames K]   ms/frame of each form -> DIR/rate.json
+    python profiles/chexel_rate.py --part rate   --out DIR [--rounds R --frames K --parent-lib PATH]   ms/frame of each form -> DIR/rate.json
     python profiles/chexel_rate.py --part kernel --out DIR                           a short run of the all-outputs form (for rocprofv3)
     python profiles/chexel_rate.py --part merge  --out DIR [--kernel-stats FILE] [--bench-logs LOG ...]   -> profiles/chexel_rate.json
 
@@ -9,6 +9,8 @@ Forms: `sdr` is ycge_render_frame(sdr) - today's frame; the others are ycge_rend
 destination is page-locked memory of the library (as the C# wrapper's), so the read-back is a plain DMA.  A frame's time is the host
 clock around the call, which returns with the frame in the caller's arrays.  The kernel time of k_encode_chexels comes from a separate
 `rocprofv3 --kernel-trace --stats -- python profiles/chexel_rate.py --part kernel` run, whose rocpd database (or kernel_stats.csv) the merge reads.
+With --parent-lib, the parent commit's library (built elsewhere from the parent's sources) is loaded beside the product's: two legs of
+the parent and one of the product run every form, alternated round by round, and rate.json gets `against_parent` (parent_check below).
 """
 from __future__ import annotations
 
@@ -30,14 +32,31 @@ FORMS = {"sdr": ("sdr",), "color16": ("color16",), "rgba": ("rgba",), "sdr+color
          "all four": ("sdr", "color16", "ansi", "rgba")}
 
 
-def renderer():
+def renderer(lib=None):
     from yetanotherconsolegameengine_amd import scenes
     from yetanotherconsolegameengine_amd.renderer import RaytraceRenderer
     from yetanotherconsolegameengine_amd.scene import flatten
     sc, w, h, ss, pose = scenes.config_scene(4)
-    g = RaytraceRenderer(flatten(sc), w, h, pose.get("fov", 45.0), ss)
+    g = RaytraceRenderer(flatten(sc), w, h, pose.get("fov", 45.0), ss, lib=lib)
     g.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
     return g
+
+
+def parent_check(per):
+    """per: (leg, form) -> [ms a frame of each round], the legs "parent A", "branch", "parent B" (two of the parent's, as
+    profiles/ansi_layers_rate.py has them: what differs between two legs of ONE build is part of the noise) -> form -> the parent's median
+    and spread (max - min) over the rounds of both its legs, each leg's median, and whether the branch's lies at or below the parent's
+    median plus its spread.  Every round of a leg runs on a context of its own, the only one alive: a context's place among the live
+    contexts of a process changes its period whichever library made it (of three, the second ran its frames in flight 0.25 ms slower
+    and the third its synchronous frames 0.2 ms slower)"""
+    res = {}
+    for f in dict.fromkeys(f for _, f in per):
+        p, b = per[("parent A", f)] + per[("parent B", f)], per[("branch", f)]
+        res[f] = {"parent_median_ms": float(np.median(p)), "parent_spread_ms": float(np.max(p) - np.min(p)), "branch_median_ms": float(np.median(b)),
+                  "branch_spread_ms": float(np.max(b) - np.min(b)), "parent_A_median_ms": float(np.median(per[("parent A", f)])),
+                  "parent_B_median_ms": float(np.median(per[("parent B", f)]))}
+        res[f]["within_allowance"] = bool(res[f]["branch_median_ms"] <= res[f]["parent_median_ms"] + res[f]["parent_spread_ms"])
+    return res
 
 
 def frame_fn(g, form):
@@ -50,7 +69,28 @@ def frame_fn(g, form):
     return lambda: g._check(g.L.ycge_render_frame_chexels(g.ctx, *ptrs, None)), arrays
 
 
-def part_rate(out: Path, rounds: int, frames: int):
+def against_parent(parent_lib, rounds: int, frames: int):
+    from yetanotherconsolegameengine_amd import abi
+    P = abi.load_library(parent_lib)
+    libs = {"parent A": P, "branch": None, "parent B": P}
+    per = {(b, f): [] for b in libs for f in FORMS}
+    for r in range(rounds):
+        for b in (list(libs) if r % 2 == 0 else list(libs)[::-1]):
+            g = renderer(libs[b])
+            fns = {f: frame_fn(g, f)[0] for f in FORMS}
+            for f in FORMS:
+                for _ in range(5):
+                    fns[f]()
+            for f in FORMS:
+                t0 = time.perf_counter()
+                for _ in range(frames):
+                    fns[f]()
+                per[(b, f)].append((time.perf_counter() - t0) * 1e3 / frames)
+            g.close()
+    return parent_check(per)
+
+
+def part_rate(out: Path, rounds: int, frames: int, parent_lib=None):
     g = renderer()
     fns = {f: frame_fn(g, f)[0] for f in FORMS}
     for f in FORMS:                      # warm-up: code objects, buffers, schedules
@@ -69,6 +109,8 @@ def part_rate(out: Path, rounds: int, frames: int):
            "bytes_read_back": {f: sum({"sdr": 24, "color16": 1, "ansi": 2, "rgba": 8}[k] * n for k in FORMS[f]) for f in FORMS},
            "ms_per_frame": {f: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))} for f, v in per.items()}}
     g.close()
+    if parent_lib:
+        res["against_parent"] = against_parent(parent_lib, rounds, frames)
     print(json.dumps(res), flush=True)
     (out / "rate.json").write_text(json.dumps(res, indent=1))
 
@@ -136,9 +178,10 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("--parent-lib", default=None, help="rate: the parent commit's library, measured beside the product's")
     ap.add_argument("--bench-logs", nargs="*", default=(), help="merge: bench_parent_*.log / bench_branch_*.log of the same job")
     a = ap.parse_args()
     out = Path(a.out); out.mkdir(parents=True, exist_ok=True)
-    if a.part == "rate": part_rate(out, a.rounds, a.frames)
+    if a.part == "rate": part_rate(out, a.rounds, a.frames, a.parent_lib)
     elif a.part == "kernel": part_kernel(out)
     else: part_merge(out, a.kernel_stats, a.bench_logs)

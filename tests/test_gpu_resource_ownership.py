@@ -194,13 +194,14 @@ def test_the_resident_loop_hook_frees_what_it_makes(product_lib):
     r.close()
 
 
-@pytest.mark.parametrize("entry", ["ycge_render_frame", "ycge_render_frame_chexels"])
+@pytest.mark.parametrize("entry", ["ycge_render_frame", "ycge_render_frame_chexels", "ycge_render_frame_ansi"])
 def test_a_failed_frame_leaves_no_latched_sdr_destination(entry):
-    """lib/var_faultinject.so: the n-th host allocation of a context's FIRST frame with the post stage, into a PAGEABLE SDR array, fails.  After every step that
-    returned an error the array is filled with a pattern and one successful frame is rendered with out_sdr = NULL: the pattern is intact
-    (no pointer of the failed call stayed latched on the context), that frame - no post stage - changed no counter, and the context's
-    destruction gives everything back.  Reading the code, the walk cannot fail BEHIND the latch (run_post sets it in front of HIP calls
-    only, none of which allocates host memory): the guarantee there is the one scope guard of render_frame_sync, by construction."""
+    """lib/var_faultinject.so: the n-th host allocation of a context's FIRST frame with the post stage, into PAGEABLE arrays - the SDR array, and
+    with it a console-16 array (_chexels) or an out_stream of ycge_ansi_stream_bound bytes (_ansi) - fails.  After every step that returned an
+    error the arrays are filled with a pattern and one successful frame is rendered with out_sdr = NULL: the patterns are intact (no pointer of
+    the failed call outlived it), that frame - no post stage - changed no counter, and the context's destruction gives everything back.  The
+    guarantee is structural: a call's destinations, staged ones included, are a value on its entry point's stack that is passed down to the post
+    stage, and the context has no member that could hold one - the walk checks that nothing else took the place of the latch it once had."""
     L = abi.load_library(build.build_variant("faultinject"))
     L.ycge_debug_fail_allocation.restype = C.c_int
     L.ycge_debug_fail_allocation.argtypes = [C.c_int64]
@@ -213,14 +214,18 @@ def test_a_failed_frame_leaves_no_latched_sdr_destination(entry):
         try:
             g.SetCamera(pose["pos"], pose["yaw"], pose["pitch"])
             sdr = np.zeros((g.fbH, g.fbW, 2, 3), np.float32)
-            c16 = np.zeros((g.fbH, g.fbW), np.uint8)
-            p_sdr = sdr.ctypes.data_as(C.POINTER(C.c_float))
+            bound = C.c_size_t(0)
+            assert L.ycge_ansi_stream_bound(g.fbW, g.fbH, C.byref(bound)) == abi.YCGE_OK
+            c16 = np.zeros(bound.value if entry == "ycge_render_frame_ansi" else (g.fbH, g.fbW), np.uint8)          # (_ansi: the stream's bytes)
+            p_sdr, p_c16 = sdr.ctypes.data_as(C.POINTER(C.c_float)), c16.ctypes.data_as(C.POINTER(C.c_uint8))
             assert L.ycge_render_frame(g.ctx, None, None) == abi.YCGE_OK          # (what a trace-only frame makes on first use exists from here on)
             L.ycge_debug_fail_allocation(n)
             if entry == "ycge_render_frame":
                 rc = L.ycge_render_frame(g.ctx, p_sdr, None)
+            elif entry == "ycge_render_frame_chexels":
+                rc = L.ycge_render_frame_chexels(g.ctx, p_sdr, p_c16, None, None, None)
             else:
-                rc = L.ycge_render_frame_chexels(g.ctx, p_sdr, c16.ctypes.data_as(C.POINTER(C.c_uint8)), None, None, None)
+                rc = L.ycge_render_frame_ansi(g.ctx, g.fbW, g.fbH, 0, 0, 7, 0, 0, p_c16, bound.value, C.byref(C.c_size_t(0)), p_sdr, None)
             left = L.ycge_debug_fail_allocation(-1)
             assert rc in (abi.YCGE_OK, abi.YCGE_ERR_OUT_OF_MEMORY), (n, rc, L.ycge_last_error(g.ctx))
             if rc == abi.YCGE_ERR_OUT_OF_MEMORY:
@@ -238,5 +243,5 @@ def test_a_failed_frame_leaves_no_latched_sdr_destination(entry):
         if rc == abi.YCGE_OK and left >= 0:
             break
         n += 1 if n < 40 else max(1, n // 3)
-    print(f"{entry}: {failed} of the walk's steps failed (up to n = {n}), all of them in front of the latch")
+    print(f"{entry}: {failed} of the walk's steps failed (up to n = {n})")
     assert failed >= 1, failed

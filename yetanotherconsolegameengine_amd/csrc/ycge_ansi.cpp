@@ -4,8 +4,8 @@
 // A frame of ycge_render_frame_ansi is ycge_render_frame_chexels' with the ANSI pairs alone, kept on the device: behind their encode,
 // on the same stream, three launches turn them into the bytes ANSITerminalRenderer.Render() writes (ANSITerminalRenderer.cs:86-153)
 // for a console over the framebuffer, and the stream's length is copied to a page-locked word.  Once the stream is synchronised, exactly
-// that many bytes are copied to the caller.  The request (AnsiRequest) lives in ChexelState for the length of one call (a scope guard
-// clears it; on an error return also every latched destination), so no other entry point issues a launch or copy of it.
+// that many bytes are copied to the caller.  The request (AnsiRequest) travels in the entry point's FrameOutputs (ycge_ctx.h) down to
+// chexel_encode, chexel_read_back and ansi_enqueue: a frame whose outputs name no request issues no launch or copy of it.
 //
 // The delta form (ycge_render_frame_ansi_delta, ycge_video_blit_ansi_delta) keeps the pairs of the last stream it handed out in one of two
 // buffers of ChexelState and writes only the cells that changed since; the contract is in include/ycge.h.  Its encode writes into the
@@ -14,8 +14,8 @@
 //
 // The 24-bit colour forms (ycge_render_frame_ansi_rgb, ycge_render_frame_ansi_rgb_delta and the two video calls) are the same calls with
 // `rgb` set in the request: the encode keeps the RGBA plane instead of the pairs, the bound counts 39 bytes a cell, and the delta compares
-// against what the terminal shows under a tolerance.  One request, one launch, one guard and one delivery serve every form; the delta
-// state belongs to the one terminal, so a stream of either family invalidates it for both.
+// against what the terminal shows under a tolerance.  One request, one launch, one delta transaction (DeltaCall) and one delivery serve
+// every form; the delta state belongs to the one terminal, so a stream of either family invalidates it for both.
 //
 // Layers (ycge_console_set_layers): the console's other framebuffers, kept in ChexelState::layers with their colours encoded once by
 // k_encode_chexels.  While any are set, launch() runs the compose pass in front of the stream kernels, which then walk the console-wide
@@ -92,8 +92,9 @@ static int ensure_ansi(ycge_ctx *c, ChexelState &X, const AnsiRequest &r, unsign
 // - rgb: what the terminal displays, d_next the plane that receives the next such - with the copy of {length, changed, emitted, run starts};
 // otherwise the full stream and its length alone
 // L (or NULL: no layers): the console's other framebuffers and the composite's planes, the compose pass in front; d_prev and d_next are then L's
+// flight (or NULL): the frame in flight whose stream buffer and record k_ansi_deliver fills instead of that copy
 static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiRequest &r, bool delta, const uint8_t *d_plane, const uint8_t *d_prev, uint8_t *d_next,
-                  int fbW, int fbH, const ycge_ansi::LayersRun *L)
+                  int fbW, int fbH, const ycge_ansi::LayersRun *L, const FrameOutputs *flight = nullptr)
 {
     const uint8_t *palette = r.rgb ? X.rgb_palette.p : reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48);
     uint8_t *out = X.ansi_stream.p;
@@ -117,7 +118,7 @@ static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiReq
         e = ycge_launch_ansi_delta(d_plane, d_prev, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
     if (e != 0)
         return c->fail(YCGE_ERR_DEVICE, "%sANSI %sstream launch failed: %s", r.rgb ? "24-bit " : "", delta ? "delta " : "", hipGetErrorString((hipError_t)e));
-    if (!X.flight_out) {
+    if (!flight) {
         HIP_TRY(c, hipMemcpyAsync(X.ansi_res_host.p, X.ansi_res.p, (delta ? 4 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
         return YCGE_OK;
     }
@@ -126,7 +127,7 @@ static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiReq
     void *d_sticky = nullptr;
     HIP_TRY(c, hipHostGetDevicePointer(&d_sticky, X.flight_sticky.p, 0));
     // (a length above the device stream's own size is refused as one above the caller's capacity is: no load passes the allocation)
-    e = ycge_launch_ansi_deliver(out, X.ansi_res.p, X.flight_cap < cap ? X.flight_cap : cap, delta ? 0 : 1, X.flight_out, X.flight_rec, static_cast<uint32_t *>(d_sticky), c->compute_units, stream);
+    e = ycge_launch_ansi_deliver(out, X.ansi_res.p, flight->dev_capacity < cap ? flight->dev_capacity : cap, delta ? 0 : 1, flight->dev_stream, flight->dev_record, static_cast<uint32_t *>(d_sticky), c->compute_units, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ansi_deliver launch failed: %s", hipGetErrorString((hipError_t)e));
     HIP_TRY(c, X.flight_ev.ensure());
     HIP_TRY(c, hipEventRecord(X.flight_ev, stream));
@@ -156,61 +157,64 @@ static int ensure_composite(ycge_ctx *c, ChexelState &X, const AnsiRequest &r)
     return YCGE_OK;
 }
 
-int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs)
+// what a frame's stream call makes before it queues anything: r's buffers and, while layers are set, the composite's planes
+static int ensure_frame_buffers(ycge_ctx *c, ChexelState &X, const AnsiRequest &r, unsigned long long bound, hipStream_t stream)
+{
+    const int rc = ensure_ansi(c, X, r, bound, stream);
+    return rc == YCGE_OK && X.layers.n > 0 ? ensure_composite(c, X, r) : rc;
+}
+
+int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_pairs)
 {
     ChexelState &X = c->chexels;
-    { const int rc = X.ansi.rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
-    const bool delta = X.delta_on && !X.delta_full;
+    const AnsiRequest &r = *out.ansi;
+    { const int rc = r.rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
+    const bool delta = !out.keyframe;
+    const FrameOutputs *flight = out.dev_stream ? &out : nullptr;
     if (X.layers.n == 0)
-        return launch(c, X, stream, X.ansi, delta, d_pairs, X.delta_held[X.delta_prev].p, X.delta_held[1 - X.delta_prev].p, c->fbW, c->fbH, nullptr);
+        return launch(c, X, stream, r, delta, d_pairs, X.delta_held[X.delta_prev].p, X.delta_held[1 - X.delta_prev].p, c->fbW, c->fbH, nullptr, flight);
     // (layers: this call's composite goes where the next _delta call finds it; a 24-bit delta's write kernel fills that plane instead)
-    ycge_ansi::LayersRun L = layers_run(X.layers, X.ansi.rgb);
+    ycge_ansi::LayersRun L = layers_run(X.layers, r.rgb);
     const int held = X.delta_prev, next = 1 - X.delta_prev;
-    L.comp = delta && X.ansi.rgb ? X.comp_cur.p : X.comp_held[next].p;
+    L.comp = delta && r.rgb ? X.comp_cur.p : X.comp_held[next].p;
     L.comp_glyph = X.glyph_held[next].p;
     L.prev = X.comp_held[held].p; L.prev_glyph = X.glyph_held[held].p;
     L.next = X.comp_held[next].p;
-    return launch(c, X, stream, X.ansi, delta, d_pairs, nullptr, nullptr, c->fbW, c->fbH, &L);
+    return launch(c, X, stream, r, delta, d_pairs, nullptr, nullptr, c->fbW, c->fbH, &L, flight);
 }
 
 } // namespace ycge_host
 
 namespace {
 
-// one _ansi call: sets the request, and clears it on every way out (the SDR staging: render_frame_sync's own guard).  A _delta call
-// (r.delta) decides keyframe or delta, and on every way out but commit() makes the next call a keyframe; any other call shows the terminal
-// its own stream next, so a later _delta call returns a keyframe
-struct AnsiCall {
-    ycge_ctx *c;
+// one _ansi call's transaction on the context's delta state.  A _delta call (r.delta) decides keyframe or delta, and on every way out but
+// commit() makes the next call a keyframe; any other call shows the terminal its own stream next, so a later _delta call returns a keyframe
+struct DeltaCall {
+    ChexelState &X;
+    const AnsiRequest &r;
     int32_t key[8];
-    bool done = false;
-    AnsiCall(ycge_ctx *c_, const AnsiRequest &r) : c(c_), key{r.cw, r.ch, r.vx, r.vy, r.fg, r.bg, c_->fbW, c_->fbH}
+    bool keyframe = true, done = false;
+    DeltaCall(ycge_ctx *c, const AnsiRequest &r_) : X(c->chexels), r(r_), key{r_.cw, r_.ch, r_.vx, r_.vy, r_.fg, r_.bg, c->fbW, c->fbH}
     {
-        ChexelState &X = c->chexels;
-        X.on = true; X.dst[0] = X.dst[1] = X.dst[2] = nullptr;
-        X.drop_staged();
-        X.ansi_on = true; X.ansi = r;
-        X.delta_on = r.delta;
         if (r.delta)
-            X.delta_full = !X.delta_valid || X.delta_rgb != r.rgb || !X.delta_held[X.delta_prev].p || std::memcmp(key, X.delta_key, sizeof key) != 0 || r.clear || r.keyframe ||
-                           X.delta_layered != (X.layers.n > 0) || (X.layers.n > 0 && (!X.comp_held[X.delta_prev].p || !X.glyph_held[X.delta_prev].p));
+            keyframe = !X.delta_valid || X.delta_rgb != r.rgb || !X.delta_held[X.delta_prev].p || std::memcmp(key, X.delta_key, sizeof key) != 0 || r.clear || r.keyframe ||
+                       X.delta_layered != (X.layers.n > 0) || (X.layers.n > 0 && (!X.comp_held[X.delta_prev].p || !X.glyph_held[X.delta_prev].p));
         else
             X.delta_valid = false;
     }
-    ~AnsiCall()
+    ~DeltaCall() { if (!done) X.delta_valid = false; }
+    // what the call's frame hands out: r's stream, a keyframe or not as decided here, and the SDR array
+    FrameOutputs outputs(float *sdr) const
     {
-        ChexelState &X = c->chexels;
-        if (!done) X.delta_valid = false;
-        X.on = false; X.ansi_on = false; X.delta_on = false; X.ansi = AnsiRequest();
-        X.flight_out = nullptr; X.flight_rec = nullptr; X.flight_cap = 0;
-        X.drop_staged();
+        FrameOutputs out(sdr);
+        out.ansi = &r; out.keyframe = keyframe;
+        return out;
     }
     // a _delta call's stream is with the caller: this frame's pairs are `prev` from now on
     void commit()
     {
-        ChexelState &X = c->chexels;
-        if (!X.ansi.delta) return;
-        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = X.ansi.rgb; X.delta_layered = X.layers.n > 0;
+        if (!r.delta) return;
+        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = r.rgb; X.delta_layered = X.layers.n > 0;
         std::memcpy(X.delta_key, key, sizeof key);
         done = true;
     }
@@ -265,20 +269,17 @@ int frame(ycge_ctx *c, const char *fn, const AnsiRequest &r, uint8_t *out_stream
     if (!c) return YCGE_ERR_INVALID_ARG;
     unsigned long long bound = 0;
     int rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
+    if (rc == YCGE_OK) rc = check_post_frame(c);
     if (rc != YCGE_OK) return rc;
-    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
-    // (the exchange of the one-process RCCL form packs lean slabs when slab_albedo = 0: no albedo reaches the denoise stage)
-    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
-        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
     HIP_TRY(c, hipSetDevice(c->device));
-    AnsiCall call(c, r);
+    DeltaCall call(c, r);
+    FrameOutputs out = call.outputs(out_top_bottom_sdr);
     ChexelState &X = c->chexels;
-    rc = ensure_ansi(c, X, r, bound, c->stream);
-    if (rc == YCGE_OK && X.layers.n > 0) rc = ensure_composite(c, X, r);
+    rc = ensure_frame_buffers(c, X, r, bound, c->stream);
     if (rc != YCGE_OK) return rc;
-    rc = render_frame_sync(c, out_top_bottom_sdr, true, st);          // (its stream synchronisation: the length and the counters have arrived)
+    rc = render_frame_sync(c, &out, st);          // (its stream synchronisation: the length and the counters have arrived)
     if (rc != YCGE_OK) return rc;
-    rc = deliver(c, X, fn, !r.delta || X.delta_full, bound, out_stream, out_len, r.delta ? out_info : nullptr);
+    rc = deliver(c, X, fn, call.keyframe, bound, out_stream, out_len, r.delta ? out_info : nullptr);
     if (rc != YCGE_OK) return rc;
     call.commit();
     return YCGE_OK;
@@ -286,7 +287,7 @@ int frame(ycge_ctx *c, const char *fn, const AnsiRequest &r, uint8_t *out_stream
 
 // ---- frames in flight (ycge_render_frame_async_ansi; the contract: include/ycge.h).  The call is frame() without deliver(): the stream's
 // launches end in k_ansi_deliver (launch() above), which copies the exact length into the caller's page-locked buffer and fills the record,
-// so nothing is waited for.  The delta state moves at queue time: AnsiCall decides keyframe or delta, commit() flips the held planes.
+// so nothing is waited for.  The delta state moves at queue time: DeltaCall decides keyframe or delta, commit() flips the held planes.
 
 // what k_ansi_deliver is given: a 16-byte aligned stream buffer, page-locked over all of its capacity, and an 8-byte aligned page-locked record
 int check_flight_buffers(ycge_ctx *c, const char *fn, const uint8_t *out, size_t capacity, const void *rec)
@@ -345,18 +346,17 @@ int frame_async(ycge_ctx *c, const ycge_ansi_async *q, uint8_t *out_stream, size
     if (out_top_bottom_sdr && !host_memory_is_page_locked(out_top_bottom_sdr, (size_t)c->fbW * c->fbH * 6 * sizeof(float)))
         return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_top_bottom_sdr must be page-locked memory (ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)", fn);
     rc = check_in_flight(c);
+    if (rc == YCGE_OK) rc = check_post_frame(c);
     if (rc != YCGE_OK) return rc;
-    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
-        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
     if (!c->taa_stream) return c->fail(YCGE_ERR_INVALID_ARG, "no second stream: frames in flight need a single-device context");
     HIP_TRY(c, hipSetDevice(c->device));
-    AnsiCall call(c, r);
+    DeltaCall call(c, r);
+    FrameOutputs out = call.outputs(out_top_bottom_sdr);
     ChexelState &X = c->chexels;
     if (!flight_buffers_ready(c, X, r, bound)) {
         // (the first call of a form or a size: the frames in flight are joined, and what the buffers' makers queued on c->stream is waited for)
         rc = join_async(c);
-        if (rc == YCGE_OK) rc = ensure_ansi(c, X, r, bound, c->stream);
-        if (rc == YCGE_OK && X.layers.n > 0) rc = ensure_composite(c, X, r);
+        if (rc == YCGE_OK) rc = ensure_frame_buffers(c, X, r, bound, c->stream);
         if (rc == YCGE_OK) rc = ensure_flight(c, X);
         if (rc != YCGE_OK) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -364,8 +364,8 @@ int frame_async(ycge_ctx *c, const ycge_ansi_async *q, uint8_t *out_stream, size
     void *d_out = nullptr, *d_rec = nullptr;
     HIP_TRY(c, hipHostGetDevicePointer(&d_out, out_stream, 0));
     HIP_TRY(c, hipHostGetDevicePointer(&d_rec, out_result, 0));
-    X.flight_out = static_cast<uint8_t *>(d_out); X.flight_rec = d_rec; X.flight_cap = capacity;
-    rc = render_frame_in_flight(c, out_top_bottom_sdr, true);
+    out.dev_stream = static_cast<uint8_t *>(d_out); out.dev_record = d_rec; out.dev_capacity = capacity;
+    rc = render_frame_in_flight(c, &out);
     if (rc != YCGE_OK) return rc;
     call.commit();
     return YCGE_OK;
@@ -418,21 +418,20 @@ int video(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t *fram
     rc = join_async(c);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    AnsiCall call(c, r);
-    StagedSdrGuard staged(c);
+    DeltaCall call(c, r);
+    FrameOutputs out = call.outputs(out_top_bottom_sdr);
     ChexelState &X = c->chexels;
-    rc = ensure_ansi(c, X, r, bound, c->stream);
-    if (rc == YCGE_OK && X.layers.n > 0) rc = ensure_composite(c, X, r);
+    rc = ensure_frame_buffers(c, X, r, bound, c->stream);
     const float *d_sdr = nullptr;
     if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
-    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, d_sdr, false);
-    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out_top_bottom_sdr);
-    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, false);          // (the stream kernels and the copy of what they report)
+    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, out, d_sdr, false);
+    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out);
+    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, out, false);          // (the stream kernels and the copy of what they report)
     if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    rc = deliver(c, X, fn, !r.delta || X.delta_full, bound, out_stream, out_len, r.delta ? out_info : nullptr);
+    rc = deliver(c, X, fn, call.keyframe, bound, out_stream, out_len, r.delta ? out_info : nullptr);
     if (rc != YCGE_OK) return rc;
-    finish_staged_sdr(c);
+    out.finish();
     call.commit();
     return YCGE_OK;
 }

@@ -2,9 +2,9 @@
 // ycge_chexel.hip).
 //
 // A frame of these calls is ycge_render_frame's (or ycge_render_frame_async_sdr's) with the post stage, plus one launch behind the tonemap
-// on the same stream that turns the SDR array into the bytes the caller asked for, and their read-back.  The request lives in the
-// context for the length of one call only (a scope guard clears it, and on an error return every staged destination too): run_post
-// sees no request from any other entry point, so those issue no extra launch, copy or event.
+// on the same stream that turns the SDR array into the bytes the caller asked for, and their read-back.  What the caller asked for is
+// the entry point's FrameOutputs (ycge_ctx.h), handed down to run_post and from there to this file: an entry point that asks for no
+// chexels hands down a value that names none, and issues no extra launch, copy or event.
 //
 // LinearToSrgb8 (ANSITerminalRenderer.cs:287-296 = OpenGLTerminalRenderer.cs:390-400) is a monotone step function of its input: the
 // host finds its 255 steps ONCE with the C library's double pow - the function Math.Pow calls - and the kernel counts thresholds.
@@ -90,94 +90,66 @@ int ensure_tables(ycge_ctx *c, ChexelState &X)
     return YCGE_OK;
 }
 
-int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second)
+int chexel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked, const float *d_sdr, bool second)
 {
     ChexelState *X = &c->chexels;
-    const bool ansi = X->ansi_on;                                                        // (ycge_render_frame_ansi: the pairs stay on the device)
-    if (!X->on || (!X->dst[0] && !X->dst[1] && !X->dst[2] && !ansi)) return YCGE_OK;        // (the SDR alone: nothing to encode)
+    uint8_t *const *dst = asked.chexels;
+    const bool ansi = asked.ansi != nullptr;                                             // (ycge_render_frame_ansi: the pairs stay on the device)
+    if (!dst[0] && !dst[1] && !dst[2] && !ansi) return YCGE_OK;                          // (the SDR alone: nothing to encode)
     // (frames in flight: the stream buffers are one set per context - this frame's encode .. deliver follows the deliver of the frame before)
     if (ansi && X->flight_pending && X->flight_stream != stream) HIP_TRY(c, hipStreamWaitEvent(stream, X->flight_ev, 0));
     const ChexelLayout L((size_t)c->fbW * c->fbH);
     DevBuf<uint8_t> &out = X->out[second ? 1 : 0];
     if (out.cap < L.total) HIP_TRY(c, out.alloc(L.total));
-    if (X->dst[1] || X->dst[2] || ansi) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
-    const bool rgb = ansi && X->ansi.rgb;                                                // (a 24-bit stream: the RGBA plane stays on the device instead)
+    if (dst[1] || dst[2] || ansi) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
+    const bool rgb = ansi && asked.ansi->rgb;                                            // (a 24-bit stream: the RGBA plane stays on the device instead)
     uint8_t *pairs = out.p + L.ansi, *rgba = out.p + L.rgba;
-    if (X->delta_on) {                                                                   // (a _delta call: the pairs go where the next call finds them;
+    if (ansi && asked.ansi->delta) {                                                     // (a _delta call: the pairs go where the next call finds them;
         DevBuf<uint8_t> &next = X->delta_held[1 - X->delta_prev];                        //  24-bit: a keyframe's plane is the next `shown`, a delta's write kernel fills it)
         const size_t bytes = (rgb ? 8 : 2) * L.n;
         if (next.cap < bytes) HIP_TRY(c, next.alloc(bytes));
         if (!rgb) pairs = next.p;
-        else if (X->delta_full) rgba = next.p;
+        else if (asked.keyframe) rgba = next.p;
     }
-    const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, X->dst[0] ? out.p + L.c16 : nullptr, X->dst[1] || (ansi && !rgb) ? pairs : nullptr,
-                                      X->dst[2] || rgb ? rgba : nullptr, c->compute_units, stream);
+    const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, dst[0] ? out.p + L.c16 : nullptr, dst[1] || (ansi && !rgb) ? pairs : nullptr,
+                                      dst[2] || rgb ? rgba : nullptr, c->compute_units, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed: %s", hipGetErrorString((hipError_t)e));
     return YCGE_OK;
 }
 
-int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second)
+int chexel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, bool second)
 {
     ChexelState *X = &c->chexels;
-    if (!X->on) return YCGE_OK;
+    uint8_t *const *dst = out.chexels;
+    if (!dst[0] && !dst[1] && !dst[2] && !out.ansi) return YCGE_OK;
     const ChexelLayout L((size_t)c->fbW * c->fbH);
     const size_t off[3] = {L.c16, L.ansi, L.rgba}, bytes[3] = {L.n, 2 * L.n, 8 * L.n};
     const uint8_t *src = X->out[second ? 1 : 0].p;
     size_t staged = 0;
     for (int k = 0; k < 3; k++)
-        if (X->dst[k] && !host_memory_is_page_locked(X->dst[k], bytes[k])) staged = off[k] + bytes[k];
+        if (dst[k] && !host_memory_is_page_locked(dst[k], bytes[k])) staged = off[k] + bytes[k];
     HIP_TRY(c, X->stage.reserve(staged));
     for (int k = 0; k < 3; k++) {
-        if (!X->dst[k]) continue;
-        uint8_t *target = X->dst[k];
-        if (!host_memory_is_page_locked(X->dst[k], bytes[k])) {        // (synchronous calls only: the frames in flight refuse pageable arrays up front)
-            target = X->stage.data() + off[k];
-            X->staged_dst[k] = X->dst[k]; X->staged_off[k] = off[k]; X->staged_bytes[k] = bytes[k];
-        }
+        if (!dst[k]) continue;
+        uint8_t *target = dst[k];
+        if (!host_memory_is_page_locked(dst[k], bytes[k]))             // (synchronous calls only: the frames in flight refuse pageable arrays up front)
+            target = out.redirect(dst[k], X->stage.data() + off[k], bytes[k]);
         HIP_TRY(c, hipMemcpyAsync(target, src + off[k], bytes[k], hipMemcpyDeviceToHost, stream));
     }
-    if (!X->ansi_on) return YCGE_OK;
+    if (!out.ansi) return YCGE_OK;
     // (ycge_ansi.cpp: the escape stream and its length from the pairs - 24-bit: the RGBA plane - where chexel_encode put them)
-    const bool held = X->delta_on && (X->delta_full || !X->ansi.rgb);
-    return ansi_enqueue(c, stream, held ? X->delta_held[1 - X->delta_prev].p : src + (X->ansi.rgb ? L.rgba : L.ansi));
+    const bool held = out.ansi->delta && (out.keyframe || !out.ansi->rgb);
+    return ansi_enqueue(c, stream, out, held ? X->delta_held[1 - X->delta_prev].p : src + (out.ansi->rgb ? L.rgba : L.ansi));
 }
 
 } // namespace ycge_host
 
 namespace {
 
-// one _chexels call: sets the request, and clears it and every latched destination on every way out, so no later call writes into an
-// array of this one (the SDR staging: render_frame_sync's own guard)
-struct ChexelCall {
-    ycge_ctx *c;
-    ChexelCall(ycge_ctx *c_, uint8_t *c16, uint8_t *ansi, uint8_t *rgba) : c(c_)
-    {
-        ChexelState &X = c->chexels;
-        X.on = true; X.dst[0] = c16; X.dst[1] = ansi; X.dst[2] = rgba;
-        X.drop_staged();
-    }
-    ~ChexelCall()
-    {
-        ChexelState &X = c->chexels;
-        X.on = false; X.dst[0] = X.dst[1] = X.dst[2] = nullptr;
-        X.drop_staged();
-    }
-    // the synchronous call's pageable destinations, once its stream is done
-    void finish()
-    {
-        ChexelState &X = c->chexels;
-        for (int k = 0; k < 3; k++)
-            if (X.staged_dst[k]) std::memcpy(X.staged_dst[k], X.stage.data() + X.staged_off[k], X.staged_bytes[k]);
-    }
-};
-
-int check_chexel_call(ycge_ctx *c, const char *fn, const float *sdr, const uint8_t *c16, const uint8_t *ansi, const uint8_t *rgba)
+int check_chexel_call(ycge_ctx *c, const char *fn, const FrameOutputs &out)
 {
-    if (!sdr && !c16 && !ansi && !rgba) return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, color16, ansi, rgba)", fn);
-    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
-    // (the exchange of the one-process RCCL form packs lean slabs when slab_albedo = 0: no albedo reaches the denoise stage)
-    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
-        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
+    if (!out.sdr && !out.chexels[0] && !out.chexels[1] && !out.chexels[2])
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, color16, ansi, rgba)", fn);
     return YCGE_OK;
 }
 
@@ -189,19 +161,19 @@ extern "C" {
 int ycge_render_frame_chexels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba, ycge_frame_stats *st)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;
-    int rc = check_chexel_call(c, "ycge_render_frame_chexels", out_top_bottom_sdr, out_color16, out_ansi, out_rgba);
-    if (rc != YCGE_OK) return rc;
-    ChexelCall call(c, out_color16, out_ansi, out_rgba);
-    rc = render_frame_sync(c, out_top_bottom_sdr, true, st);
-    if (rc == YCGE_OK) call.finish();
-    return rc;
+    FrameOutputs out(out_top_bottom_sdr, out_color16, out_ansi, out_rgba);
+    int rc = check_chexel_call(c, "ycge_render_frame_chexels", out);
+    if (rc == YCGE_OK) rc = check_post_frame(c);
+    return rc == YCGE_OK ? render_frame_sync(c, &out, st) : rc;
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
 int ycge_render_frame_async_chexels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;
-    int rc = check_chexel_call(c, "ycge_render_frame_async_chexels", out_top_bottom_sdr, out_color16, out_ansi, out_rgba);
+    FrameOutputs out(out_top_bottom_sdr, out_color16, out_ansi, out_rgba);
+    int rc = check_chexel_call(c, "ycge_render_frame_async_chexels", out);
+    if (rc == YCGE_OK) rc = check_post_frame(c);
     if (rc != YCGE_OK) return rc;
     const size_t n = (size_t)c->fbW * c->fbH;
     const void *dst[4] = {out_top_bottom_sdr, out_color16, out_ansi, out_rgba};
@@ -211,8 +183,7 @@ try {
         if (dst[k] && !host_memory_is_page_locked(dst[k], bytes[k]))
             return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async_chexels fills its arrays while the caller runs on: %s must be page-locked memory "
                                                  "(ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)", names[k]);
-    ChexelCall call(c, out_color16, out_ansi, out_rgba);
-    return render_frame_in_flight(c, out_top_bottom_sdr, true);
+    return render_frame_in_flight(c, &out);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -224,23 +195,20 @@ try {
     if (!c) return YCGE_ERR_INVALID_ARG;
     static const char fn[] = "ycge_video_blit";
     int rc = video_check_frame(c, fn, frame, src_w, src_h, bytes_per_pixel);
+    FrameOutputs out(out_top_bottom_sdr, out_color16, out_ansi, out_rgba);
+    if (rc == YCGE_OK) rc = check_chexel_call(c, fn, out);
     if (rc != YCGE_OK) return rc;
-    if (!out_top_bottom_sdr && !out_color16 && !out_ansi && !out_rgba)
-        return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, color16, ansi, rgba)", fn);
     rc = join_async(c);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    ChexelCall call(c, out_color16, out_ansi, out_rgba);
-    StagedSdrGuard staged(c);
     const float *d_sdr = nullptr;
     rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
-    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, d_sdr, false);
-    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out_top_bottom_sdr);
-    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, false);
-    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }          // (nothing of this call is queued when its staging is let go)
+    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, out, d_sdr, false);
+    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out);
+    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, out, false);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }          // (nothing of this call is queued when it returns)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    finish_staged_sdr(c);
-    call.finish();
+    out.finish();
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }

@@ -425,20 +425,34 @@ struct LayerStore {
     DevBuf<uint16_t> glyphs;
     DevBuf<uint8_t> pairs, rgba;                       // 2 bytes a cell; 2 * cells RGBA words, the foregrounds then the backgrounds
 };
-// what the chexel calls of one context hold (ycge_chexel.cpp, ycge_ansi.cpp): filled by the first call
+// What one frame hands out: the argument of render_frame_sync / render_frame_in_flight and of everything below them (run_post, chexel_encode,
+// chexel_read_back, ansi_enqueue, video_read_sdr).  A value on the entry point's stack, holding borrowed pointers only.  Default-constructed: a
+// post stage with no output - nothing to encode, nothing to copy; a NULL pointer to it: no post stage.
+// A pageable destination of a SYNCHRONOUS call is redirected into the context's page-locked staging (ycge_ctx::out_stage, ChexelState::stage)
+// and noted here; the caller that synchronises the stream calls finish().  The asynchronous entry points refuse pageable destinations ahead
+// of their first enqueue, so their value never holds a staged entry: it may leave scope with copies still queued, and its stack lifetime suffices.
+struct FrameOutputs {
+    float *sdr = nullptr;                              // the caller's destinations: the SDR array ...
+    uint8_t *chexels[3] = {nullptr, nullptr, nullptr}; // ... c16, ansi pairs, rgba
+    const AnsiRequest *ansi = nullptr;                 // the ANSI stream asked for (its encode keeps the pairs - 24-bit colour: the RGBA plane - on the device only)
+    bool keyframe = true;                              // ... runs the full stream's kernels (a _delta call: what its DeltaCall decided)
+    uint8_t *dev_stream = nullptr;                     // a frame in flight: the device aliases of the caller's page-locked stream buffer (dev_capacity bytes)
+    void *dev_record = nullptr;                        // ... and result record - the stream is delivered by k_ansi_deliver instead of the copy of ansi_res
+    size_t dev_capacity = 0;
+    struct Staged { void *dst; const void *stage; size_t bytes; } staged[4] = {};
+    int n_staged = 0;
+    explicit FrameOutputs(float *sdr_ = nullptr, uint8_t *c16 = nullptr, uint8_t *pairs = nullptr, uint8_t *rgba = nullptr) : sdr(sdr_), chexels{c16, pairs, rgba} {}
+    // `stage` stands in for the pageable dst in a queued copy
+    template <class T> T *redirect(T *dst, void *stage, size_t bytes) { staged[n_staged++] = Staged{dst, stage, bytes}; return static_cast<T *>(stage); }
+    // the stream of those copies has been waited for
+    void finish() { for (int k = 0; k < n_staged; k++) std::memcpy(staged[k].dst, staged[k].stage, staged[k].bytes); n_staged = 0; }
+};
+// what the chexel calls of one context hold (ycge_chexel.cpp, ycge_ansi.cpp): filled by the first call.  Nothing of the call at hand: that is its FrameOutputs
 struct ChexelState {
-    bool on = false;                                   // a _chexels or _ansi call is in progress
-    uint8_t *dst[3] = {nullptr, nullptr, nullptr};     // its destinations: c16, ansi, rgba
     DevBuf<uint8_t> tables;                            // 256 f32 + 256 f64 thresholds
     DevBuf<uint8_t> out[2];                            // the encoded bytes, per post parity (as d_sdr / d_sdr2)
     PinnedBuf stage;                                   // page-locked staging of pageable destinations (synchronous calls only)
-    uint8_t *staged_dst[3] = {nullptr, nullptr, nullptr};
-    size_t staged_off[3] = {0, 0, 0}, staged_bytes[3] = {0, 0, 0};
-    void drop_staged() { for (int k = 0; k < 3; k++) { staged_dst[k] = nullptr; staged_bytes[k] = 0; } }
-    // the ANSI stream calls (ycge_ansi.cpp; kernels: ycge_ansi.hip, ycge_ansi_rgb.hip): the request of the call at hand - its encode keeps the
-    // ANSI pairs (24-bit colour: the RGBA plane) on the device only - and the stream's buffers
-    bool ansi_on = false;
-    AnsiRequest ansi;
+    // the ANSI stream calls (ycge_ansi.cpp; kernels: ycge_ansi.hip, ycge_ansi_rgb.hip): the stream's buffers
     DevBuf<uint8_t> ansi_stream;                       // the stream (its bound)
     DevBuf<uint32_t> ansi_tiles;                       // per-tile byte counts, then offsets (a delta: four words a tile)
     DevBuf<unsigned long long> ansi_res;               // {length, changed, emitted, run starts}, as the scan wrote them (the full stream: the length alone)
@@ -450,7 +464,6 @@ struct ChexelState {
     // form finds no valid state.  The encode of a 256-colour _delta call writes its pairs into delta_held[1 - delta_prev]; in 24-bit colour a
     // keyframe's encode writes the plane there and a delta's write kernel writes emitted ? cur : shown.  A successful call flips delta_prev -
     // nothing is copied.  Whatever shows the terminal something else (a plain _ansi call, ycge_resize, a failure) clears delta_valid.
-    bool delta_on = false, delta_full = false;         // a _delta call is in progress; it returns a keyframe (the full stream's kernels)
     DevBuf<uint8_t> delta_held[2];
     int delta_prev = 0;
     bool delta_valid = false, delta_rgb = false;
@@ -465,14 +478,10 @@ struct ChexelState {
     DevBuf<uint8_t> comp_held[2], comp_cur;
     DevBuf<uint16_t> glyph_held[2];
     bool delta_layered = false;
-    // Frames in flight (ycge_render_frame_async_ansi): flight_out / flight_rec are the device aliases of the call at hand's page-locked stream
-    // buffer (flight_cap bytes) and result record - while set, the stream is delivered by k_ansi_deliver instead of the copy of ansi_res.
-    // The stream buffers are one set per context, so a frame's encode .. deliver follows the deliver of the frame before: flight_ev is
-    // recorded behind every such deliver, on flight_stream, and waited for in front of the next encode on another stream while
-    // flight_pending (join_async clears it).  flight_sticky: the word a deliver sets when the stream exceeds the capacity (join_async).
-    uint8_t *flight_out = nullptr;
-    void *flight_rec = nullptr;
-    size_t flight_cap = 0;
+    // Frames in flight (ycge_render_frame_async_ansi): the stream buffers are one set per context, so a frame's encode .. deliver follows the
+    // deliver of the frame before: flight_ev is recorded behind every k_ansi_deliver, on flight_stream, and waited for in front of the next
+    // encode on another stream while flight_pending (join_async clears it).  flight_sticky: the word a deliver sets when the stream exceeds
+    // the capacity (join_async).
     Event flight_ev;
     hipStream_t flight_stream = nullptr;
     bool flight_pending = false;
@@ -753,7 +762,6 @@ struct ycge_ctx {
     Event tex_stage_ev[2];
     // GPU -> host copies never target memory whose mapping the library does not control (copy_out below): page-locked staging of its own
     PinnedBuf out_stage;
-    float *staged_sdr_dst = nullptr; size_t staged_sdr_bytes = 0;       // a synchronous frame's SDR read-back into a pageable caller array: finished on the host after the stream
     Event tex_order_ev;         // "everything queued on the second trace stream so far": a live texture's copy waits for it
     bool tex_stage_busy[2] = {false, false};
     int tex_stage_next = 0;
@@ -779,8 +787,8 @@ struct ycge_ctx {
     // scene_ev marks the device work of the last scene change on `stream` - a query waits for it and for nothing a frame queued after it
     std::unique_ptr<QueryState> query;
     Event scene_ev;
-    // device chexel colours (ycge_render_frame_chexels / _async_chexels, ycge_chexel.cpp): the request of the call at hand, the encoded
-    // buffers per post parity, the threshold tables, the staging of pageable destinations
+    // device chexel colours (ycge_render_frame_chexels / _async_chexels, ycge_chexel.cpp): the encoded buffers per post parity, the
+    // threshold tables, the staging of pageable destinations
     ChexelState chexels;
     VideoState video;            // Video mode (ycge_video_blit, ycge_video.cpp)
     ObjState obj;                // the parsed OBJ (ycge_obj_parse, ycge_obj.cpp)
@@ -841,18 +849,16 @@ struct RcclApi {
 const RcclApi &load_rccl();
 size_t slab_floats(const ycge_ctx *c);
 bool host_memory_is_page_locked(const void *p, size_t bytes);
-void finish_staged_sdr(ycge_ctx *c);
-// run_post latches a pageable SDR destination on the context (staged_sdr_dst) for the caller to finish behind its stream.  Every entry
-// point that may reach run_post holds one of these: whatever way it leaves, no later call finds a pointer of this one.
-struct StagedSdrGuard {
-    ycge_ctx *c;
-    explicit StagedSdrGuard(ycge_ctx *c_) : c(c_) {}
-    StagedSdrGuard(const StagedSdrGuard &) = delete;
-    ~StagedSdrGuard() { c->staged_sdr_dst = nullptr; c->staged_sdr_bytes = 0; }
+// how one post stage runs (run_post's last argument; the defaults: a synchronous frame nobody times)
+struct PostRun {
+    bool timed = false;                  // ev[3] is recorded behind the encode (the caller asked for statistics)
+    hipEvent_t history_read = nullptr;   // recorded once the TAA history has been read for the last time
+    hipEvent_t before_copy = nullptr;    // recorded in front of the read-back: the exposure state is this frame's
+    hipEvent_t tone_wait = nullptr;      // the frame before has left its exposure state: waited for in front of this frame's exposure step
+    bool second_sdr = false;             // into the second device SDR array and set of encoded bytes (frames in flight, by parity)
+    bool second_set = false;             // on the second set of denoise buffers (post stages side by side)
 };
-int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, hipEvent_t history_read = nullptr /* recorded once the TAA history has been read for the last time */,
-             hipEvent_t before_copy = nullptr /* recorded in front of the read-back: the exposure state is this frame's */, bool second_sdr = false,
-             hipEvent_t tone_wait = nullptr /* the frame before has left its exposure state: waited for in front of this frame's exposure step */, bool second_set = false);
+int run_post(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, const PostRun &run);     // ycge_post_host.cpp: steps 6-8, the encode and the read-backs `out` asks for
 int join_async(ycge_ctx *c);
 // TemporalBlendWithClamp's parameters from the raw config values (RaytraceRenderer.cs:218, :305): every TAA launch - the frames', the
 // tile-resident resolve's, ycge_test_taa's - is handed what this makes
@@ -924,19 +930,20 @@ struct CellSource {
 };
 int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *out_grid_index, CellSource &src);
 int query_scene_changed(ycge_ctx *c);       // ycge_query.cpp: record scene_ev behind a scene upload / objects update
-int chexel_encode(ycge_ctx *c, hipStream_t stream, const float *d_sdr, bool second);   // ycge_chexel.cpp: run_post's encode behind the tonemap (a no-op unless a _chexels call asked)
-int chexel_read_back(ycge_ctx *c, hipStream_t stream, bool second);                      // ... and its copies behind the SDR read-back
-int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *st);     // ycge_frame.cpp: ycge_render_frame, post stage on request
+int chexel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked, const float *d_sdr, bool second);   // ycge_chexel.cpp: run_post's encode behind the tonemap (a no-op unless chexels or a stream are asked for)
+int chexel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, bool second);   // ... and its copies behind the SDR read-back
+int render_frame_sync(ycge_ctx *c, FrameOutputs *out, ycge_frame_stats *st);             // ycge_frame.cpp: ycge_render_frame (out NULL: no post stage; finished when it returns)
 int check_in_flight(ycge_ctx *c);                                                        // ycge_frame.cpp: the contexts and configurations the frames in flight refuse
-int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post);                      // ycge_frame.cpp: ycge_render_frame_async(_sdr)
+int check_post_frame(ycge_ctx *c);                                                       // ycge_frame.cpp: ... and a presenter's frame with the post stage
+int render_frame_in_flight(ycge_ctx *c, FrameOutputs *out);                              // ycge_frame.cpp: ycge_render_frame_async(_sdr)
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
 int ensure_tables(ycge_ctx *c, ChexelState &X);                                           // ycge_chexel.cpp: LinearToSrgb8's thresholds on the device, once
-int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *d_pairs);                // ycge_ansi.cpp: the stream kernels behind the encode, and the length's copy
+int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_pairs);   // ycge_ansi.cpp: out.ansi's stream kernels behind the encode, and the length's copy
 // ycge_video.cpp: Video mode.  The refusals of a source frame; upload + k_video_blit on `stream` for a geometry (*d_sdr: its SDR array);
-// the SDR read-back (a pageable array: staged as run_post does it, finish_staged_sdr behind the stream); the test hooks' bodies
+// the SDR read-back (a pageable array: staged as run_post does it); the test hooks' bodies
 int video_check_frame(ycge_ctx *c, const char *fn, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp);
 int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const float **d_sdr);
-int video_read_sdr(ycge_ctx *c, hipStream_t stream, const float *d_sdr, float *out_sdr);
+int video_read_sdr(ycge_ctx *c, hipStream_t stream, const float *d_sdr, FrameOutputs &out);
 int video_host_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0, float *wx, int32_t *y0, float *wy, float *geom3);
 int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out);
 // ycge_obj.cpp: MeshLoader.FromObj from file bytes - the bodies of ycge_obj_parse_host (no context), ycge_obj_parse / _read / _triangles / _release and ycge_debug_obj_stats

@@ -542,7 +542,7 @@ catch (...) { return ycge_host::abi_catch(c); }
 
 int ycge_render_frame_async(ycge_ctx *c)
 try {
-    return c ? render_frame_in_flight(c, nullptr, false) : YCGE_ERR_INVALID_ARG;
+    return c ? render_frame_in_flight(c, nullptr) : YCGE_ERR_INVALID_ARG;
 }
 catch (...) { return ycge_host::abi_catch(c); }
 // ... with steps 6-8 (denoise, exposure, tonemap + downsample) and the read-back into out_top_bottom_sdr, which is filled when the frame
@@ -553,7 +553,8 @@ int ycge_render_frame_async_sdr(ycge_ctx *c, float *out_top_bottom_sdr)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;
     if (!out_top_bottom_sdr) return c->fail(YCGE_ERR_INVALID_ARG, "null SDR buffer");
-    return render_frame_in_flight(c, out_top_bottom_sdr, true);
+    FrameOutputs out(out_top_bottom_sdr);
+    return render_frame_in_flight(c, &out);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 } // extern "C"
@@ -567,12 +568,22 @@ int check_in_flight(ycge_ctx *c)
     if (c->cfg.capture_debug || c->cfg.count_work) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async keeps neither debug captures nor per-frame counters: use ycge_render_frame");
     return YCGE_OK;
 }
-// post: run steps 6-8 (out_sdr, when not NULL, gets the read-back; the chexel calls may ask for their encoded bytes alone)
-int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
+// ... and every presenter's frame with the post stage: ycge_render_frame_chexels, _ansi and their kin, synchronous or in flight
+int check_post_frame(ycge_ctx *c)
+{
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    // (the exchange of the one-process RCCL form packs lean slabs when slab_albedo = 0: no albedo reaches the denoise stage)
+    if (c->exchange_mode == YCGE_EXCHANGE_RCCL && !c->cfg.slab_albedo)
+        return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
+    return YCGE_OK;
+}
+// out (or NULL: the frame stops after TAA): steps 6-8 run and hand out what it names - the SDR read-back, the chexel calls' encoded bytes, an ANSI stream
+int render_frame_in_flight(ycge_ctx *c, FrameOutputs *out)
 {
     { const int rc = check_in_flight(c); if (rc != YCGE_OK) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (out_sdr && !host_memory_is_page_locked(out_sdr, (size_t)c->fbW * c->fbH * 6 * sizeof(float)))
+    const bool post = out != nullptr;
+    if (post && out->sdr && !host_memory_is_page_locked(out->sdr, (size_t)c->fbW * c->fbH * 6 * sizeof(float)))
         return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame_async_sdr fills its array while the caller runs on: it must be page-locked memory (ycge_alloc_host_buffer, or whole pages registered with ycge_pin_host_buffer)");
     if (!c->taa_stream) return c->fail(YCGE_ERR_INVALID_ARG, "no second stream: frames in flight need a single-device context");
     for (int k = 0; k < 3; k++) HIP_TRY(c, c->set_resolved_ev[k].ensure());
@@ -707,8 +718,13 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
         // Elsewhere the post stages follow each other.
         const bool side_by_side = overlap_scene && c->knobs.flight_post_pair;
         if (c->post_busy && !side_by_side) HIP_TRY(c, hipStreamWaitEvent(ps, c->post_done_ev, 0));
-        rc = run_post(c, ps, out_sdr, false, c->post_hist_ev, overlap_scene ? c->post_done_ev : nullptr, overlap_scene && par == 1,
-                      (side_by_side && c->post_busy) ? c->post_done_ev : nullptr, side_by_side && par == 1);
+        PostRun run;
+        run.history_read = c->post_hist_ev;
+        run.before_copy = overlap_scene ? c->post_done_ev : nullptr;
+        run.tone_wait = (side_by_side && c->post_busy) ? c->post_done_ev : nullptr;
+        run.second_sdr = overlap_scene && par == 1;
+        run.second_set = side_by_side && par == 1;
+        rc = run_post(c, ps, *out, run);
         if (rc != YCGE_OK) return rc;
         if (!overlap_scene) HIP_TRY(c, hipEventRecord(c->post_done_ev, ps));
         HIP_TRY(c, hipEventRecord(c->post_set_ev[k], ps));
@@ -720,9 +736,10 @@ int render_frame_in_flight(ycge_ctx *c, float *out_sdr, bool post)
     return YCGE_OK;
 }
 
-// ycge_render_frame; post: run steps 6-8 (out_sdr, when not NULL, gets the read-back)
-int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *st)
+// ycge_render_frame; out (or NULL: the frame stops after TAA): steps 6-8 run and hand out what it names, finished when this returns
+int render_frame_sync(ycge_ctx *c, FrameOutputs *out, ycge_frame_stats *st)
 {
+    const bool post = out != nullptr;
     if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
     { const int jr = join_async(c); if (jr != YCGE_OK) return jr; }
     const bool multi_dev = !c->peers.empty() || c->exchange_mode == YCGE_EXCHANGE_RCCL;
@@ -730,7 +747,6 @@ int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *
         return c->fail(YCGE_ERR_INVALID_ARG, "ycge_render_frame is the one-process entry: set config.n_devices / devices[] to drive several GPUs from it, "
                                              "or use ycge_trace_tiles + ycge_resolve_gathered with one process per GPU (rank / world_size)");
     HIP_TRY(c, hipSetDevice(c->device));
-    StagedSdrGuard staged(c);
     auto t0 = std::chrono::steady_clock::now();
     FrameState fs;
     snapshot_frame(c, fs);
@@ -750,11 +766,12 @@ int render_frame_sync(ycge_ctx *c, float *out_sdr, bool post, ycge_frame_stats *
         return rc;
     }
     if (post) {      // steps 6-8; without them the frame stops after TAA (trace-only callers, benchmarks of the hot path)
-        rc = run_post(c, c->stream, out_sdr, timed);
+        PostRun run; run.timed = timed;
+        rc = run_post(c, c->stream, *out, run);
         if (rc != YCGE_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    finish_staged_sdr(c);
+    if (post) out->finish();
     double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     rc = fill_stats(c, st, fs, did_reset, true, wall);
     if (rc == YCGE_OK && st && c->cfg.count_work)
@@ -782,7 +799,8 @@ extern "C" {
 int ycge_render_frame(ycge_ctx *c, float *out_sdr, ycge_frame_stats *st)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;
-    return render_frame_sync(c, out_sdr, out_sdr != nullptr, st);
+    FrameOutputs out(out_sdr);
+    return render_frame_sync(c, out_sdr ? &out : nullptr, st);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -821,7 +839,7 @@ try {
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
     c->last_stream = stream;
-    StagedSdrGuard staged(c);
+    FrameOutputs out(out_sdr);
     auto t0 = std::chrono::steady_clock::now();
     if (out_sdr && !c->cfg.slab_albedo) return c->fail(YCGE_ERR_INVALID_ARG, "lean slabs (config.slab_albedo = 0) carry no albedo: the denoise stage cannot run");
     const size_t per_rank = (size_t)c->tiles_per_rank_padded * 256 * slab_floats(c);
@@ -838,13 +856,14 @@ try {
     int rc = taa_and_commit(c, stream, fs, did_reset, st != nullptr, false);
     if (rc != YCGE_OK) return rc;
     if (out_sdr) {
-        rc = run_post(c, stream, out_sdr, st != nullptr);
+        PostRun run; run.timed = st != nullptr;
+        rc = run_post(c, stream, out, run);
         if (rc != YCGE_OK) return rc;
-        if (!st) { HIP_TRY(c, hipStreamSynchronize(stream)); finish_staged_sdr(c); }      // the caller's host buffer is filled when the call returns
+        if (!st) { HIP_TRY(c, hipStreamSynchronize(stream)); out.finish(); }      // the caller's host buffer is filled when the call returns
     }
     if (st) {
         HIP_TRY(c, hipStreamSynchronize(stream));
-        finish_staged_sdr(c);
+        out.finish();
         std::memset(st, 0, sizeof *st);
         st->frame = fs.frame; st->history_reset = did_reset ? 1 : 0;
         float ms = 0.0f;

@@ -556,13 +556,6 @@ int copy_out(ycge_ctx *c, void *dst, const void *src, size_t bytes)
     }
     return YCGE_OK;
 }
-// the SDR frame of a SYNCHRONOUS call into a pageable array: the copy was queued into the staging buffer (run_post); the stream has been waited for
-void finish_staged_sdr(ycge_ctx *c)
-{
-    if (!c->staged_sdr_dst) return;
-    std::memcpy(c->staged_sdr_dst, c->out_stage.p, c->staged_sdr_bytes);
-    c->staged_sdr_dst = nullptr; c->staged_sdr_bytes = 0;
-}
 
 // every stream a frame of this context may still be running on
 int quiesce(ycge_ctx *c)

@@ -187,15 +187,17 @@ int post_resident_per_cu(ycge_ctx *c, bool split)
     return q < c->knobs.post_resident_per_cu ? q : c->knobs.post_resident_per_cu;
 }
 
-int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, hipEvent_t history_read, hipEvent_t before_copy, bool second_sdr, hipEvent_t tone_wait, bool second_set)      // (defaults and what the events mean: ycge_ctx.h)
+int run_post(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, const PostRun &run)      // (what the fields mean: ycge_ctx.h)
 {
+    const bool second_sdr = run.second_sdr;
+    hipEvent_t history_read = run.history_read;
     // (every other frame in flight: the names below stand for the second set of denoise buffers while this call queues its kernels)
     struct SwapPost { ycge_ctx *c; bool on;
         void swap() { std::swap(c->den_a, c->alt_post.den_a); std::swap(c->den_b, c->alt_post.den_b); std::swap(c->unit_n, c->alt_post.unit_n); std::swap(c->exp_terms, c->alt_post.exp_terms);
                       std::swap(c->atrous_statw, c->alt_post.atrous_statw); std::swap(c->exp_scratch, c->alt_post.exp_scratch); std::swap(c->post_progress, c->alt_post.post_progress);
                       std::swap(c->post_epoch, c->alt_post.post_epoch); std::swap(c->post_ticket, c->alt_post.post_ticket); }
         SwapPost(ycge_ctx *c_, bool on_) : c(c_), on(on_) { if (on) swap(); }
-        ~SwapPost() { if (on) swap(); } } swap_post(c, second_set);
+        ~SwapPost() { if (on) swap(); } } swap_post(c, run.second_set);
     const int w = c->hiW, h = c->hiH;
     const size_t n = (size_t)w * h;
     if (!c->den_a.p) {
@@ -333,27 +335,26 @@ int run_post(ycge_ctx *c, hipStream_t stream, float *out_sdr_host, bool timed, h
     const int step = c->ss * 2 > 2 ? c->ss * 2 : 2;            // :226
     const float tone_consts[5] = {1.0f, 0.18f, 0.2f, 0.10f, 1.50f};     // toneExposure, aeKey, aeSpeed, aeMin, aeMax (ToneMapper.cs:8-16)
     if (!c->exp_scratch.p) HIP_TRY(c, c->exp_scratch.alloc(ycge_exposure_scratch_bytes(w, h, step)));
-    if (tone_wait) HIP_TRY(c, hipStreamWaitEvent(stream, tone_wait, 0));
+    if (run.tone_wait) HIP_TRY(c, hipStreamWaitEvent(stream, run.tone_wait, 0));
     e = ycge_launch_exposure(cur, c->sky.p, w, h, step, c->exp_terms.p, c->tone_state.p, tone_consts, c->exp_scratch.p, c->knobs.exposure_serial ? 1 : 0, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "exposure launch failed: %s", hipGetErrorString((hipError_t)e));
     if (second_sdr && !c->d_sdr2.p) HIP_TRY(c, c->d_sdr2.alloc((size_t)c->fbW * c->fbH * 6));
     float *d_sdr = second_sdr ? c->d_sdr2.p : c->d_sdr.p;
     e = ycge_launch_tonemap(cur, w, c->fbW, c->fbH, c->ss, 2.2f, 2.0f, 0.0f, c->tone_state.p, d_sdr, stream);   // toneGamma, toneSaturation, toneVibrance
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "tonemap launch failed: %s", hipGetErrorString((hipError_t)e));
-    { const int rc = chexel_encode(c, stream, d_sdr, second_sdr); if (rc != YCGE_OK) return rc; }      // (only where a _chexels call asked)
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev[3], stream));
-    if (before_copy) HIP_TRY(c, hipEventRecord(before_copy, stream));
-    if (out_sdr_host) {
+    { const int rc = chexel_encode(c, stream, out, d_sdr, second_sdr); if (rc != YCGE_OK) return rc; }      // (only where `out` asks for chexels or a stream)
+    if (run.timed) HIP_TRY(c, hipEventRecord(c->ev[3], stream));
+    if (run.before_copy) HIP_TRY(c, hipEventRecord(run.before_copy, stream));
+    if (out.sdr) {
         const size_t sdr_bytes = (size_t)c->fbW * c->fbH * 6 * sizeof(float);
-        float *target = out_sdr_host;
-        if (!host_memory_is_page_locked(out_sdr_host, sdr_bytes)) {        // (synchronous callers only: the frames in flight refuse a pageable array up front)
+        float *target = out.sdr;
+        if (!host_memory_is_page_locked(out.sdr, sdr_bytes)) {        // (synchronous callers only: the frames in flight refuse a pageable array up front)
             HIP_TRY(c, c->out_stage.reserve(sdr_bytes));
-            target = (float *)c->out_stage.p;
-            c->staged_sdr_dst = out_sdr_host; c->staged_sdr_bytes = sdr_bytes;
+            target = out.redirect(out.sdr, c->out_stage.p, sdr_bytes);
         }
         HIP_TRY(c, hipMemcpyAsync(target, d_sdr, sdr_bytes, hipMemcpyDeviceToHost, stream));
     }
-    { const int rc = chexel_read_back(c, stream, second_sdr); if (rc != YCGE_OK) return rc; }
+    { const int rc = chexel_read_back(c, stream, out, second_sdr); if (rc != YCGE_OK) return rc; }
     if (history_read) HIP_TRY(c, hipEventRecord(history_read, stream));        // (a single iteration: exposure and tonemap read the history itself)
     return YCGE_OK;
 }
@@ -404,11 +405,11 @@ try {
         std::memcpy(&init[0], &ae_in, 4); std::memcpy(&init[1], &ae_in, 4);        // (effective = toneExposure * aeExposure, toneExposure = 1)
         HIP_TRY(c, hipMemcpy(c->tone_state.p, init, sizeof init, hipMemcpyHostToDevice));
     }
-    StagedSdrGuard staged(c);
-    const int rc = run_post(c, c->stream, sdr_out, false);
+    FrameOutputs out(sdr_out);
+    const int rc = run_post(c, c->stream, out, PostRun());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (rc != YCGE_OK) return rc;
-    finish_staged_sdr(c);
+    out.finish();
     if (denoised_out) { const int cr = copy_out(c, denoised_out, c->denoised, 3 * n * sizeof(float)); if (cr != YCGE_OK) return cr; }
     return copy_out(c, state_out, c->tone_state.p, 6 * sizeof(uint32_t));
 }

@@ -146,15 +146,14 @@ int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src
     return YCGE_OK;
 }
 
-int video_read_sdr(ycge_ctx *c, hipStream_t stream, const float *d_sdr, float *out_sdr)
+int video_read_sdr(ycge_ctx *c, hipStream_t stream, const float *d_sdr, FrameOutputs &out)
 {
-    if (!out_sdr) return YCGE_OK;
+    if (!out.sdr) return YCGE_OK;
     const size_t sdr_bytes = (size_t)c->fbW * c->fbH * 6 * sizeof(float);
-    float *target = out_sdr;
-    if (!host_memory_is_page_locked(out_sdr, sdr_bytes)) {          // (finished on the host behind the stream: finish_staged_sdr)
+    float *target = out.sdr;
+    if (!host_memory_is_page_locked(out.sdr, sdr_bytes)) {          // (finished on the host behind the stream: out.finish())
         HIP_TRY(c, c->out_stage.reserve(sdr_bytes));
-        target = (float *)c->out_stage.p;
-        c->staged_sdr_dst = out_sdr; c->staged_sdr_bytes = sdr_bytes;
+        target = out.redirect(out.sdr, c->out_stage.p, sdr_bytes);
     }
     HIP_TRY(c, hipMemcpyAsync(target, d_sdr, sdr_bytes, hipMemcpyDeviceToHost, stream));
     return YCGE_OK;
