@@ -96,7 +96,11 @@ def scene_box(g):
 
 
 def random_rays(seed, lo, hi, n=4096):
-    """origins inside and around the bounds; direction lengths 1e-3 .. 1e3, axis-aligned directions, +-0 components; the drawn intervals"""
+    """origins inside and around the bounds; direction lengths 1e-3 .. 1e3, axis-aligned directions, +-0 components; the drawn intervals.
+    What these rays do not reach: drawn from a continuous distribution, no origin lies in the plane of a box (so a zero direction component
+    never meets a 0 * inf slab product), no ray passes exactly through an edge, rim or vertex two primitives share, none ends on its hit to
+    the ulp, no denominator lands beside its cut-off, no voxel walk ties.  Those rays are tests/seam_rays.py, held to the oracle by
+    tests/test_gpu_seam_rays.py."""
     rng = np.random.default_rng(seed)
     ext = hi - lo
     o = (lo - 0.2 * ext + rng.random((n, 3)) * 1.4 * ext).astype(F32)
