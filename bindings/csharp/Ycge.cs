@@ -173,6 +173,15 @@ namespace ConsoleGame.RayTracing.Native
         public int OnDevice, Reserved;
     }
 
+    // ycge_voxel_edit, 36 bytes: every cell of the inclusive box Lo..Hi becomes (MatId, MetaId) (passed by address only, as above)
+    public unsafe struct YVoxelEdit
+    {
+        public int GridIndex;         // resident grid; 0 for ycge_world_store_edit
+        public fixed int Lo[3];
+        public fixed int Hi[3];
+        public int MatId, MetaId;
+    }
+
     // ycge_obj_ground_info, 64 bytes (an out parameter only, as above)
     public struct YObjGroundInfo
     {
@@ -243,6 +252,9 @@ namespace ConsoleGame.RayTracing.Native
         // the store made by the generator on the device (form: WorldStoreFields / WorldStoreCells) and its x-planes read back, VG01 payload order
         [DllImport(Lib)] public static extern int ycge_world_store_generate(IntPtr ctx, ref YWorld world, int chunksX, int chunksZ, int originBx, int originBz, int form);
         [DllImport(Lib)] public static extern int ycge_world_store_read(IntPtr ctx, int x0, int planes, int* cellsOut);
+        // voxel edits of resident grids and of the world store (found by symbol lookup, ABI stays 10); HipVoxelEdits in YcgeWorld.cs
+        [DllImport(Lib)] public static extern int ycge_scene_edit_voxels(IntPtr ctx, YVoxelEdit* ops, int n, uint* outInfo);
+        [DllImport(Lib)] public static extern int ycge_world_store_edit(IntPtr ctx, YVoxelEdit* ops, int n);
         [DllImport(Lib)] public static extern int ycge_scene_update_texture(IntPtr ctx, int textureIndex, IntPtr frame, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_resize(IntPtr ctx, int fbWidth, int fbHeight, int superSample);
         [DllImport(Lib)] public static extern int ycge_set_camera(IntPtr ctx, float* pos, float yaw, float pitch, float fovDeg);

@@ -130,4 +130,42 @@ namespace ConsoleGame.RayTracing.Native
 
         public void Release(IntPtr ctx) { Ycge.Check(ctx, Ycge.ycge_world_store_release(ctx)); Nx = Ny = Nz = 0; }
     }
+
+    /// <summary>A host's SetBlock: boxes of one (matId, metaId) pair written into resident grids (ycge_scene_edit_voxels) and into the world
+    /// store (ycge_world_store_edit) where they lie - no cell of the world has to exist in host memory.  Ops apply in list order; where
+    /// boxes overlap the later op wins.  A refused list changes nothing (Ycge.Check throws with the message, which names the op).  On a grid
+    /// the host encoded (a grid of the upload; a lookup table above 254 entries) a 256th distinct pair is refused with YCGE_ERR_UNSUPPORTED:
+    /// codes are not reclaimed, detach the grid and attach it again.</summary>
+    public sealed unsafe class HipVoxelEdits
+    {
+        readonly System.Collections.Generic.List<YVoxelEdit> ops = new System.Collections.Generic.List<YVoxelEdit>();
+        public int Count => ops.Count;
+        public void Clear() { ops.Clear(); }
+
+        /// <summary>gridIndex: the device grid (0 for a store edit); the box is inclusive, in the grid's - or the store's - cell indices.</summary>
+        public void Box(int gridIndex, int x0, int y0, int z0, int x1, int y1, int z1, int matId, int metaId)
+        {
+            var e = new YVoxelEdit { GridIndex = gridIndex, MatId = matId, MetaId = metaId };
+            e.Lo[0] = x0; e.Lo[1] = y0; e.Lo[2] = z0; e.Hi[0] = x1; e.Hi[1] = y1; e.Hi[2] = z1;
+            ops.Add(e);
+        }
+        public void Cell(int gridIndex, int x, int y, int z, int matId, int metaId) { Box(gridIndex, x, y, z, x, y, z, matId, metaId); }
+
+        /// <summary>{cells whose code changed, bricks written, grids whose record changed, objects installed again (0 or 1)}.  The scene is
+        /// complete afterwards: no ycge_scene_update_objects has to follow.</summary>
+        public uint[] ApplyToScene(IntPtr ctx)
+        {
+            var info = new uint[4];
+            var list = ops.ToArray();
+            fixed (YVoxelEdit* o = list) fixed (uint* i = info) Ycge.Check(ctx, Ycge.ycge_scene_edit_voxels(ctx, o, list.Length, i));
+            return info;
+        }
+
+        /// <summary>The same list, in store cell coordinates, into the context's world store (every GridIndex 0).</summary>
+        public void ApplyToStore(IntPtr ctx)
+        {
+            var list = ops.ToArray();
+            fixed (YVoxelEdit* o = list) Ycge.Check(ctx, Ycge.ycge_world_store_edit(ctx, o, list.Length));
+        }
+    }
 }

@@ -507,6 +507,58 @@ int ycge_world_store_generate(ycge_ctx *ctx, const ycge_world *world, int32_t ch
  * planes < 1, a range outside 0..nx, a NULL cells_out, a peer context; nothing is written then.  Found by symbol lookup. */
 int ycge_world_store_read(ycge_ctx *ctx, int32_t x0, int32_t planes, int32_t *cells_out /* 2 * planes * ny * nz */);
 
+/* --- voxel edits: a host that digs or places a block changes cells of a grid that is resident, and of the world store, where they lie.
+ * Without these two calls the route is a host copy of every chunk's raw cells, a detach, an attach of the whole chunk and an objects
+ * update - and the store has no route at all.  The reference has no block editing: the existing paths define the result.  Added after
+ * ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no existing struct changes; a host detects both exports by symbol lookup.
+ * An op sets every cell of an inclusive index box to one (mat_id, meta_id) pair.  Ops apply in list order: where boxes overlap, the
+ * later op wins. */
+typedef struct ycge_voxel_edit {   /* 9 int32, 36 bytes */
+    int32_t grid_index;            /* resident grid; must be 0 for ycge_world_store_edit */
+    int32_t lo[3], hi[3];          /* inclusive index box; one cell is lo == hi          */
+    int32_t mat_id, meta_id;       /* the pair every cell of the box becomes             */
+} ycge_voxel_edit;
+#define YCGE_VOXEL_EDIT_MAX_OPS (1 << 20)
+/* Edit cells of resident grids (those of the upload and attached ones alike), on the device, in place.
+ *   Same pixels.  After the call every frame, every ycge_read_buffer buffer, every scene query, the counting instances' counters and
+ *     ycge_read_timed_steps are what the same context gives after one ycge_scene_upload of the equivalent scene instead - the same
+ *     materials, the same Scene.Objects in the same order, the grids with the ops applied to their cells - bit for bit, TAA history and
+ *     exposure state included.  Cell codes and offsets are internal and may differ.
+ *   Complete scene.  The call leaves a complete, renderable scene on its own; no ycge_scene_update_objects has to follow.  An object
+ *     record carries its grid's solid box and the walk tree is derived from it, so whenever an edit changes the record of a grid that an
+ *     object holds (its solid box or its brick mask), the call installs the objects again as ycge_scene_update_objects does, from the
+ *     context's own copy of the last object list ycge_scene_upload or ycge_scene_update_objects accepted.  An edit that leaves every
+ *     record as it was - the common dig or place inside the box - only touches bytes.
+ *   out_info (4 words, or NULL): cells whose code differs from before the call, bricks that hold such a cell, grids whose record
+ *     changed, objects installed again (0 or 1).  Written only on success.
+ *   Codes.  A cell is one byte, a code into the grid's material table.  mat_id <= 0 is air with any meta_id.  A grid that the device
+ *     encoded (an attached grid whose lookup table has at most 254 entries) is coded by its lookup table: 1 + the first matching entry,
+ *     or the code of default_material for a pair the table lacks - such a grid has NO limit of distinct pairs under edits.  A grid that
+ *     the host encoded (the grids of an upload; an attached grid with a larger lookup table) numbers its pairs as they first appear: a
+ *     new pair takes the next free code and its table entry is written; a 256th code is refused with YCGE_ERR_UNSUPPORTED.  Codes of
+ *     pairs no cell holds any more are not reclaimed (the message says so): detaching the grid and attaching it again is the way out.
+ *   Refusals are decided on the host before any device work and are all or nothing: nothing is written, scene and pool stay as they
+ *     were.  YCGE_ERR_INVALID_ARG with a message that names the op: NULL ops with n > 0, n < 0, n > YCGE_VOXEL_EDIT_MAX_OPS, a grid that is
+ *     not resident, lo > hi on an axis, a box that leaves the grid, a solid pair with no material (the lookup table lacks it and
+ *     default_material < 0; the message names the pair too).  YCGE_ERR_INVALID_ARG for a peer context, YCGE_ERR_NO_SCENE before the
+ *     first upload.  n = 0 is YCGE_OK.
+ *   Frames in flight are joined (they read the cells).  Scene queries see the edit with the next query.
+ *   One-process multi-device: the root forwards to every device, as an attach does; a peer context refuses.  Tiled ranks each make the
+ *     same call.
+ * The host turns every op into a code byte and lists the bricks the boxes touch; one workgroup per brick rewrites the bytes, a second
+ * kernel reduces the edited grids' solid boxes and brick masks, one small read-back follows (csrc/ycge_grid_edit.hip). */
+int ycge_scene_edit_voxels(ycge_ctx *ctx, const ycge_voxel_edit *ops, int32_t n, uint32_t *out_info /* 4 words or NULL */);
+/* Edit cells of the world store.  Boxes are in store cell coordinates - x, y, z of the VG01 payload - and grid_index must be 0.  The
+ * raw pairs are written as given, with any values.  The occupancy of every chunk an op touches is found again (mat != 0), the clipped
+ * chunks of the far faces included: a chunk may become empty - an attach of its key then reports -1 - or occupied.  Afterwards the
+ * store is what ycge_world_store_load of the edited cells gives, to ycge_world_store_read, ycge_world_store_info and
+ * ycge_scene_attach_world_chunks alike.  A device cell store is edited by kernels, a YCGE_WORLD_STORE_HOST store by a host loop; a
+ * YCGE_WORLD_STORE_FIELDS store holds no cells and refuses with YCGE_ERR_UNSUPPORTED (generate with YCGE_WORLD_STORE_CELLS instead).
+ * No scene is touched: grids attached earlier are encoded copies and keep their cells (edit those with ycge_scene_edit_voxels).  The
+ * call waits for frames in flight only where ycge_world_store_read would.  Every device of a multi-device context edits its own copy.
+ * Refusals as above, all or nothing, the message names the op; in addition: no store, grid_index != 0, a box that leaves the store. */
+int ycge_world_store_edit(ycge_ctx *ctx, const ycge_voxel_edit *ops, int32_t n);
+
 /* The argument checks of ycge_scene_upload on their own: pure host code, no device and no context needed
  * (every index in range, counts non-negative, pointers present, material kinds known).  Returns YCGE_OK or the
  * status ycge_scene_upload would return; `msg` (may be NULL) receives the reason. */

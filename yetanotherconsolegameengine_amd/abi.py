@@ -101,6 +101,16 @@ class Grid(C.Structure):
     ]
 
 
+class VoxelEdit(C.Structure):
+    """ycge_voxel_edit (36 bytes): every cell of the inclusive index box lo..hi of a resident grid - or, for ycge_world_store_edit, of the
+    store, with grid_index 0 - becomes (mat_id, meta_id)."""
+    _fields_ = [("grid_index", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("mat_id", C.c_int32), ("meta_id", C.c_int32)]
+
+
+VOXEL_EDIT_MAX_OPS = 1 << 20
+VOXEL_EDIT_INFO = ("cells_changed", "bricks_written", "records_changed", "objects_installed")
+
+
 class World(C.Structure):
     """ycge_world: WorldConfig as a chunk depends on it (ycge_worldgen_chunk_cells / ycge_scene_generate_grids)."""
     _fields_ = [("chunk_size", C.c_int32), ("chunks_y", C.c_int32), ("world_seed", C.c_int32), ("world_min", Vec3), ("voxel_size", Vec3)]
@@ -248,6 +258,9 @@ _PROTOTYPES = {
     # the store made by the generator on the device (world: C.byref(abi.World); form: WORLD_STORE_FIELDS / WORLD_STORE_CELLS) and its x-planes read back (cells_out: int32 [planes, ny, nz, 2])
     "ycge_world_store_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "ycge_world_store_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    # voxel edits of resident grids and of the world store (ops: an array of abi.VoxelEdit; out_info: uint32 [4] or None)
+    "ycge_scene_edit_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]),
+    "ycge_world_store_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "ycge_scene_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ycge_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]),

@@ -7,6 +7,7 @@
 //   ycge_post_host.cpp the post stage (steps 6-8) and its schedules
 //   ycge_resident.cpp  the tile-resident multi-GPU form, its batched launches and emulation loop; read-backs (ycge_read_buffer / _accel)
 //   ycge_query.cpp, ycge_chexel.cpp, ycge_ansi.cpp, ycge_grid_encode.cpp, ycge_worldgen_scene.cpp   scene queries, chexel colours, the ANSI stream, streamed grids, generated chunks
+//   ycge_grid_edit.cpp     voxel edits of resident grids (ycge_scene_edit_voxels): pair -> code, the brick work list, the records that follow
 //   ycge_world_store.cpp   a VG01 world resident on the device - loaded, or generated there - its chunks attached by key, its planes read back
 //   ycge_accel.cpp     the bit-faithful BVH builders
 // Every GPU resource is held through an owner of ycge_own.h: members free themselves, ycge_ctx::~ycge_ctx orders only what has an order.
@@ -149,6 +150,8 @@ int ycge_launch_obj_ground_terms(const float *positions, const int32_t *faces, u
 int ycge_launch_obj_ground_sum(const float *terms, uint32_t padded, void *header, hipStream_t stream);
 int ycge_launch_obj_ground_bounds(const float *positions, uint32_t n_positions, const uint8_t *used, void *header, hipStream_t stream);
 int ycge_launch_grid_encode(const void *descs, int n_grids, void *results, uint32_t n_workgroups, hipStream_t stream);
+int ycge_launch_grid_edit(uint8_t *arena, const void *records, uint32_t n_records, const void *ops, uint32_t *counters, hipStream_t stream);
+int ycge_launch_grid_solid(const uint8_t *arena, const void *descs, int n_grids, void *results, uint32_t n_workgroups, hipStream_t stream);
 int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
 }
@@ -377,8 +380,22 @@ int mesh_refusal(MeshRefusal why, int mesh, std::string &msg);          // the r
 // ycge_scene_attach_grids takes the lowest free index, a block of the cell arena (size-keyed free list, 256-byte alignment, else the end of
 // the arena, which grows geometrically) and a 256-entry region of the LUT; ycge_scene_detach_grids gives index, block and region back.
 // Kept by the root context; every device of a multi-device context holds the same layout.
+// What a slot needs on the host to turn a (matId, metaId) pair into a cell code (ycge_scene_edit_voxels, ycge_grid_edit.cpp).  A slot
+// the device encoded is coded by its lookup table (1 + the first matching entry, n_lookup + 1 for a miss that falls to default_material);
+// a slot the host encoded numbers its pairs as they first appeared.  Identical lookup tables are interned (intern_lookup): a world of
+// thousands of chunks holds one host copy.
+struct LookupTable { std::vector<ycge_voxel_lookup> e; };
+struct SlotCodes {
+    std::shared_ptr<const LookupTable> lookup;
+    int32_t default_material = -1;           // a material of the upload, or -1: a lookup miss has no material
+    bool host_encoded = false;
+    std::vector<std::pair<int32_t, int32_t>> seen;   // host-encoded: the pairs in code order (code = 1 + index) ...
+    std::vector<int32_t> lut;                        // ... and the table that goes with them (entry 0 = -1: empty)
+};
+
 struct GridPool {
     std::vector<GGrid> recs;                 // host mirror of d_grids, one per slot (a free slot: zeros)
+    std::vector<SlotCodes> codes;            // per slot: how an edit codes a pair (a free slot: empty)
     std::vector<uint8_t> resident;           // per slot: 1 = a grid lives here (a prim may refer to it)
     std::vector<uint32_t> block_bytes;       // per slot: bytes of its block of the cell arena
     std::vector<int32_t> lut_region;         // per slot: first entry of its 256-entry LUT region; -1: the upload's packed entries (not given back)
@@ -743,6 +760,8 @@ struct ycge_ctx {
     DevBuf<GMesh> d_meshes;
     DevBuf<GGrid> d_grids;
     GridPool grid_pool;                // (root context)
+    std::map<std::string, std::weak_ptr<const LookupTable>> lookup_tables;   // (root) the interned lookup tables of the resident grids, by their bytes
+    std::vector<ycge_prim> last_prims;  // (root) the object list the last ycge_scene_upload / ycge_scene_update_objects accepted: an edit that changes a held grid's record installs it again
     // ycge_scene_attach_grids: the batch's descriptors, results, lookup tables and raw cells in page-locked memory (root) and on this
     // device; encoded bytes that wait for the arena to grow
     PinnedBuf enc_stage;
@@ -891,6 +910,20 @@ template <class Step> int on_root_then_peers(ycge_ctx *c, Step step)
     return rc;
 }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+// room for `need` elements with the first `keep` preserved (device to device): the one place that copies resident bytes (the grid pool's tables)
+template <class T> hipError_t grow_preserve(DevBuf<T> &b, size_t need, size_t keep)
+{
+    if (need <= b.cap) { if (b.n < need) b.n = need; return hipSuccess; }
+    DevBuf<T> nb;
+    hipError_t e = nb.alloc(need);
+    if (e != hipSuccess) return e;
+    if (keep && b.p) {
+        e = hipMemcpy(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) return e;
+    }
+    b = std::move(nb);
+    return hipSuccess;
+}
 inline double us_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
 // the calling thread's current device goes back to the root's on every way out (a failed step on a peer's device included)
 struct DeviceGuard { int device; explicit DeviceGuard(int d) : device(d) {} ~DeviceGuard() { (void)hipSetDevice(device); } };
@@ -908,8 +941,14 @@ void grid_record_init(const ycge_grid &g, GGrid &G);                            
 void grid_record_solid(GGrid &G, const int lo[3], const int hi[3], uint64_t brick_mask);   // ... and from the solid voxels' index box
 std::array<float, 6> grid_world_bounds(const ycge_grid &g);
 int encode_grid_host(ycge_ctx *c, const ycge_grid &g, int gi, int n_materials, const GGrid &G, uint8_t *cells, std::vector<int32_t> &lut, int lo[3], int hi[3],
-                     uint64_t &brick_mask);                                                  // the host encoder (first-seen codes)
-void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_bytes, size_t lut_entries);   // ycge_grid_encode.cpp: after an upload
+                     uint64_t &brick_mask, std::vector<std::pair<int32_t, int32_t>> *seen_out = nullptr);   // the host encoder (first-seen codes; seen_out: the pairs in code order)
+void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_bytes, size_t lut_entries, std::vector<SlotCodes> codes = {});   // ycge_grid_encode.cpp: after an upload
+// ycge_grid_edit.cpp: how edits code the pairs of grid g (a grid of `root`'s scene; lut: a host-encoded grid's table, entry 0 first), the interned copy of a lookup table,
+// and the bodies of ycge_scene_edit_voxels / ycge_world_store_edit's argument checks
+SlotCodes slot_codes_of(ycge_ctx *root, const ycge_grid &g, int n_materials, const std::vector<std::pair<int32_t, int32_t>> *seen, const int32_t *lut);
+std::shared_ptr<const LookupTable> intern_lookup(ycge_ctx *root, const ycge_voxel_lookup *lookup, int32_t n);
+int scene_edit_voxels(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n, uint32_t *out_info);
+int update_objects(ycge_ctx *c, const ycge_prim *prims, int32_t n_prims);          // ycge_scene.cpp: the body of ycge_scene_update_objects (arguments checked)
 // Where the raw cells of an attach's grids come from (attach_grids_from, ycge_grid_encode.cpp: the body of ycge_scene_attach_grids for any source; arguments checked by the callers, n >= 1, all or
 // nothing).  Host-made cells are written into the staging of their group and go up with it; device-made cells are written on every device where k_grid_encode reads them: only descriptors and tables go up.
 struct CellSource {
@@ -971,4 +1010,5 @@ int world_store_stats(ycge_ctx *c, int64_t *out8);
 int world_store_generate(ycge_ctx *c, const ycge_world *world, int32_t chunks_x, int32_t chunks_z, int32_t origin_bx, int32_t origin_bz, int32_t form);
 int world_store_read(ycge_ctx *c, int32_t x0, int32_t planes, int32_t *cells_out);
 int world_store_generate_stats(ycge_ctx *c, int64_t *out9);
+int world_store_edit(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n);          // ... and of ycge_world_store_edit
 } // namespace ycge_host

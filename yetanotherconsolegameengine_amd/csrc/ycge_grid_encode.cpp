@@ -27,11 +27,13 @@
 
 namespace ycge_host {
 
-void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_bytes, size_t lut_entries)
+void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_bytes, size_t lut_entries, std::vector<SlotCodes> codes)
 {
     GridPool P;
     const size_t n = recs.size();
     P.recs = recs;
+    P.codes = std::move(codes);
+    P.codes.resize(n);
     P.resident.assign(n, 1);
     P.block_bytes.assign(n, 0);
     P.lut_region.assign(n, -1);
@@ -49,21 +51,6 @@ namespace {
 int morton3_host(int x, int y, int z)
 {
     return ((x & 1) << 0) | ((y & 1) << 1) | ((z & 1) << 2) | ((x & 2) << 2) | ((y & 2) << 3) | ((z & 2) << 4) | ((x & 4) << 4) | ((y & 4) << 5) | ((z & 4) << 6);
-}
-
-// room for `need` elements with the first `keep` preserved (device to device): the one place that copies resident bytes
-template <class T> hipError_t grow_preserve(DevBuf<T> &b, size_t need, size_t keep)
-{
-    if (need <= b.cap) { if (b.n < need) b.n = need; return hipSuccess; }
-    DevBuf<T> nb;
-    hipError_t e = nb.alloc(need);
-    if (e != hipSuccess) return e;
-    if (keep && b.p) {
-        e = hipMemcpy(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) return e;
-    }
-    b = std::move(nb);
-    return hipSuccess;
 }
 
 struct Planned {
@@ -219,7 +206,7 @@ int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *o
         if (!P.free_index.empty()) { pl.index = *P.free_index.begin(); P.free_index.erase(P.free_index.begin()); P.slots_reused++; }
         else {
             pl.index = (int32_t)P.recs.size();
-            P.recs.push_back(GGrid{}); P.resident.push_back(0); P.block_bytes.push_back(0); P.lut_region.push_back(-1);
+            P.recs.push_back(GGrid{}); P.codes.push_back(SlotCodes{}); P.resident.push_back(0); P.block_bytes.push_back(0); P.lut_region.push_back(-1);
             bounds.push_back(std::array<float, 6>{{0, 0, 0, -1, -1, -1}}); solid.push_back(std::array<float, 7>{});
         }
         pl.cap = (uint32_t)((size_t)pl.rec.nbx * pl.rec.nby * pl.rec.nbz * 512);
@@ -301,6 +288,7 @@ int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *o
             }
             for (int a = 0; a < 3; a++) { lo[a] = r.lo[a]; hi[a] = r.hi[a]; }
             mask = pl.rec.has_brick_mask ? ((uint64_t)r.mask_hi << 32) | r.mask_lo : 0;
+            P.codes[(size_t)pl.index] = slot_codes_of(c, g, c->n_materials, nullptr, nullptr);
             P.device_encodes++;
         } else {
             pl.host_bytes.assign(pl.cap, 0);
@@ -312,12 +300,14 @@ int attach_grids_from(ycge_ctx *c, const ycge_grid *grids, int32_t n, int32_t *o
                 if (rc != YCGE_OK) return rc;
                 gh.cells = made.data();
             }
-            rc = encode_grid_host(c, gh, k, c->n_materials, pl.rec, pl.host_bytes.data(), pl.host_lut, lo, hi, mask);
+            std::vector<std::pair<int32_t, int32_t>> seen;
+            rc = encode_grid_host(c, gh, k, c->n_materials, pl.rec, pl.host_bytes.data(), pl.host_lut, lo, hi, mask, &seen);
             if (rc != YCGE_OK) {          // (its refusals begin "grid k": cells that are not the caller's are named as their source names them)
                 const std::string head = "grid " + std::to_string(k);
                 if (!src.caller_cells && c->err.compare(0, head.size(), head) == 0) c->err = src.where((size_t)k, CellSource::kNoCell) + c->err.substr(head.size());
                 return rc;
             }
+            P.codes[(size_t)pl.index] = slot_codes_of(c, g, c->n_materials, &seen, pl.host_lut.data());
             pl.host_lut.resize(YCGE_ENC_LUT_ENTRIES, -1);
             P.host_encodes++;
         }
@@ -429,12 +419,13 @@ try {
         P.arena_in_use -= P.block_bytes[i]; P.n_resident--;
         P.block_bytes[i] = 0; P.lut_region[i] = -1;
         std::memset(&P.recs[i], 0, sizeof(GGrid));
+        P.codes[i] = SlotCodes{};
         bounds[i] = std::array<float, 6>{{0, 0, 0, -1, -1, -1}};
         solid[i] = std::array<float, 7>{};
     }
     while (!P.recs.empty() && !P.resident.back()) {          // the tables follow the resident set: free slots at the end go
         P.free_index.erase((int32_t)P.recs.size() - 1);
-        P.recs.pop_back(); P.resident.pop_back(); P.block_bytes.pop_back(); P.lut_region.pop_back();
+        P.recs.pop_back(); P.codes.pop_back(); P.resident.pop_back(); P.block_bytes.pop_back(); P.lut_region.pop_back();
         bounds.pop_back(); solid.pop_back();
     }
     if (P.owner.size() > P.recs.size()) P.owner.resize(P.recs.size());

@@ -709,6 +709,19 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// voxel edits: cells of resident grids (ycge_grid_edit.cpp) and of the world store (ycge_world_store.cpp) changed where they lie
+int ycge_scene_edit_voxels(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n, uint32_t *out_info)
+try {
+    return scene_edit_voxels(c, ops, n, out_info);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_world_store_edit(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n)
+try {
+    return world_store_edit(c, ops, n);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 int ycge_debug_world_store_generate_stats(ycge_ctx *c, int64_t *out9)
 try {
     return world_store_generate_stats(c, out9);

@@ -126,10 +126,12 @@ std::array<float, 6> grid_world_bounds(const ycge_grid &g)          // VolumeGri
 // The host encoder: one byte per voxel = index into a per-grid material table.  `cells` = the grid's nbx * nby * nbz * 512 zeroed bytes,
 // `lut` receives the table (entry 0 = -1: empty; codes 1.. = distinct (matId, metaId) pairs in first-seen order, at most 255).
 int encode_grid_host(ycge_ctx *c, const ycge_grid &g, int gi, int n_materials, const GGrid &G, uint8_t *cells, std::vector<int32_t> &lut, int lo[3], int hi[3],
-                     uint64_t &brick_mask)
+                     uint64_t &brick_mask, std::vector<std::pair<int32_t, int32_t>> *seen_out)
 {
     auto mat_ok = [&](int mi) { return mi >= 0 && mi < n_materials; };
-    std::vector<std::pair<int32_t, int32_t>> seen;
+    std::vector<std::pair<int32_t, int32_t>> own;
+    std::vector<std::pair<int32_t, int32_t>> &seen = seen_out ? *seen_out : own;
+    seen.clear();
     lut.push_back(-1);
     const bool maskable = G.has_brick_mask != 0;
     brick_mask = 0;
@@ -429,6 +431,7 @@ struct SceneArrays {
     std::vector<GMesh> gmeshes;
     std::vector<GGrid> ggrids;
     std::vector<int32_t> lut;
+    std::vector<SlotCodes> codes;           // per grid, for the grid pool
     bool any_transparent = false, has_grid = false, any_textured = false;
     std::vector<uint32_t> tex_pixels;
     std::vector<int32_t> tex_info;          // per texture {first word, width, height, 0 | live-frame flags}
@@ -614,9 +617,11 @@ int encode_grids(ycge_ctx *c, const ycge_scene *s, SceneArrays &A)
         G.lut_offset = (uint32_t)lut.size();
         int lo[3], hi[3];
         uint64_t brick_mask = 0;
-        const int erc = encode_grid_host(c, g, gi, s->n_materials, G, cells.data() + off, lut, lo, hi, brick_mask);
+        std::vector<std::pair<int32_t, int32_t>> seen;
+        const int erc = encode_grid_host(c, g, gi, s->n_materials, G, cells.data() + off, lut, lo, hi, brick_mask, &seen);
         if (erc != YCGE_OK) return erc;
         grid_record_solid(G, lo, hi, brick_mask);
+        A.codes.push_back(slot_codes_of(c, g, s->n_materials, &seen, lut.data() + G.lut_offset));          // (what a later edit of this grid codes its pairs by)
     }
     return YCGE_OK;
 }
@@ -638,7 +643,7 @@ int remember_for_updates(ycge_ctx *c, const ycge_scene *s, SceneArrays &A)
         c->grid_solid[gi][6] = A.ggrids[gi].cull_t_limit;
     }
     A.has_grid = s->n_grids > 0;
-    grid_pool_reset(c, A.ggrids, A.cells.size(), A.lut.size());          // (ycge_grid_encode.cpp: every grid of the upload is resident, nothing is free)
+    grid_pool_reset(c, A.ggrids, A.cells.size(), A.lut.size(), std::move(A.codes));          // (ycge_grid_encode.cpp: every grid of the upload is resident, nothing is free)
     return YCGE_OK;
 }
 
@@ -667,6 +672,7 @@ try {
     c->have_scene = false;
     SceneArrays A;          // built once, by the steps in this order ...
     ObjectsHost oh;
+    std::vector<ycge_prim> kept(s->prims, s->prims + s->n_prims);          // (what a later voxel edit installs again; made while a failure still leaves no scene)
     rc = flatten_materials(s, A);
     if (rc == YCGE_OK) rc = flatten_textures(s, A);
     if (rc == YCGE_OK) rc = build_mesh_arena(c, s, A);
@@ -680,6 +686,7 @@ try {
     });
     (void)hipSetDevice(c->device);
     if (rc == YCGE_OK) c->grid_pool.owner.swap(oh.grid_owner);
+    if (rc == YCGE_OK) c->last_prims.swap(kept);
     if (rc == YCGE_OK) rc = query_scene_changed(c);
     return rc;
 }
@@ -764,6 +771,18 @@ try {
     if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
     if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
     if (n_prims < 0 || (n_prims > 0 && !prims)) return c->fail(YCGE_ERR_INVALID_ARG, "bad object array");
+    std::vector<ycge_prim> kept(prims, prims + n_prims);          // (what a later voxel edit installs again)
+    const int rc = ycge_host::update_objects(c, prims, n_prims);
+    if (rc == YCGE_OK) c->last_prims.swap(kept);
+    return rc;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+} // extern "C"
+
+// the body of ycge_scene_update_objects, also what ycge_scene_edit_voxels ends with when a held grid's record changed (with the kept list)
+int ycge_host::update_objects(ycge_ctx *c, const ycge_prim *prims, int32_t n_prims)
+{
     ObjectsHost oh;
     BoundsSoA items;
     int rc = flatten_objects(c, prims, n_prims, oh, items);       // host work first: the devices keep rendering the old objects meanwhile
@@ -803,7 +822,8 @@ try {
     c->have_scene = true;
     return query_scene_changed(c);
 }
-catch (...) { return ycge_host::abi_catch(c); }
+
+extern "C" {
 
 // test / profiling hook: {device builds, host rebuilds after the kernel declined (a tree deeper than the reference's stack), host builds,
 // microseconds of the last update's build + install, Array.Sort cases in the current tree (BVH.cs:389,419), depth of the current tree}

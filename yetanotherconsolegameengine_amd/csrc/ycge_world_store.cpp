@@ -556,6 +556,117 @@ int world_store_read(ycge_ctx *c, int32_t x0, int32_t planes, int32_t *cells_out
     return YCGE_OK;
 }
 
+// ycge_world_store_edit: boxes of raw pairs written into the store where it lies, the later op winning; then the occupancy of the chunks
+// the boxes touch, found again.  A device store: k_ws_edit on every device, launches of at most YCGE_WS_EDIT_OPS_PER_LAUNCH ops in list
+// order on one stream (within a launch a lane leaves a cell to the last op that covers it); on the root the touched chunks' words are
+// zeroed - the others keep what the store knows - and k_ws_occupied runs over the x-planes of every run of touched chunk columns.  A
+// host store: two host loops.  Every refusal is decided before the first cell is written.
+int world_store_edit(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n)
+{
+    static const char *const fn = "ycge_world_store_edit";
+    int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    if (n < 0 || n > YCGE_VOXEL_EDIT_MAX_OPS || (n > 0 && !ops)) return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad op array (n = %d; at most %d ops)", fn, n, YCGE_VOXEL_EDIT_MAX_OPS);
+    WorldStore &st = c->world_store;
+    if (!st.held) return c->fail(YCGE_ERR_INVALID_ARG, "%s", kNoStore);
+    if (st.fields)
+        return c->fail(YCGE_ERR_UNSUPPORTED, "%s: a fields store holds no cells to edit; generate the store with YCGE_WORLD_STORE_CELLS", fn);
+    const WsShape &W = st.shape;
+    const int dims[3] = {W.nx, W.ny, W.nz};
+    std::vector<WsEditOp> list((size_t)n);
+    std::vector<uint8_t> touched(st.occupied.size(), 0);
+    for (int k = 0; k < n; k++) {
+        const ycge_voxel_edit &e = ops[k];
+        if (e.grid_index != 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: op %d: grid_index %d (must be 0)", fn, k, e.grid_index);
+        for (int a = 0; a < 3; a++) {
+            if (e.lo[a] > e.hi[a]) return c->fail(YCGE_ERR_INVALID_ARG, "%s: op %d: lo %d > hi %d on axis %d", fn, k, e.lo[a], e.hi[a], a);
+            if (e.lo[a] < 0 || e.hi[a] >= dims[a]) return c->fail(YCGE_ERR_INVALID_ARG, "%s: op %d: the box leaves the store (%d x %d x %d) on axis %d", fn, k, W.nx, W.ny, W.nz, a);
+        }
+        WsEditOp &o = list[(size_t)k];
+        for (int a = 0; a < 3; a++) { o.lo[a] = e.lo[a]; o.hi[a] = e.hi[a]; }
+        o.mat = e.mat_id; o.meta = e.meta_id;
+        for (int cx = e.lo[0] / W.S; cx <= e.hi[0] / W.S; cx++)
+            for (int cy = e.lo[1] / W.S; cy <= e.hi[1] / W.S; cy++)
+                for (int cz = e.lo[2] / W.S; cz <= e.hi[2] / W.S; cz++) touched[chunk_of(W, cx, cy, cz)] = 1;
+    }
+    if (n == 0) return YCGE_OK;
+    std::vector<uint8_t> occupied = st.occupied;          // (takes the store's place in a last step that cannot fail)
+    const size_t per_cx = (size_t)W.ncy * W.ncz;
+
+    if (st.on_host) {
+        int32_t *cells = st.host_cells.data();
+        for (const WsEditOp &o : list)
+            for (size_t x = (size_t)o.lo[0]; x <= (size_t)o.hi[0]; x++)
+                for (size_t y = (size_t)o.lo[1]; y <= (size_t)o.hi[1]; y++) {
+                    int32_t *row = cells + 2 * ((x * W.ny + y) * W.nz);
+                    for (size_t z = (size_t)o.lo[2]; z <= (size_t)o.hi[2]; z++) { row[2 * z] = o.mat; row[2 * z + 1] = o.meta; }
+                }
+        for (int cx = 0; cx < W.ncx; cx++)
+            for (int cy = 0; cy < W.ncy; cy++)
+                for (int cz = 0; cz < W.ncz; cz++) {
+                    const size_t ci = chunk_of(W, cx, cy, cz);
+                    if (!touched[ci]) continue;
+                    int s[3];
+                    clipped(W, cx, cy, cz, s);
+                    const int32_t *base = cells + 2 * first_cell(W, cx, cy, cz);
+                    uint8_t any = 0;
+                    for (size_t lx = 0; lx < (size_t)s[0] && !any; lx++)
+                        for (size_t ly = 0; ly < (size_t)s[1] && !any; ly++) {
+                            const int32_t *row = base + 2 * ((lx * W.ny + ly) * W.nz);
+                            for (size_t lz = 0; lz < (size_t)s[2]; lz++) if (row[2 * lz] != 0) { any = 1; break; }          // Item1 != 0, :716
+                        }
+                    occupied[ci] = any;
+                }
+        st.occupied.swap(occupied);
+        return YCGE_OK;
+    }
+
+    rc = quiesce(c);          // (copy_out's staging is the frames' too)
+    if (rc != YCGE_OK) return rc;
+    const DeviceGuard guard(c->device);
+    for (ycge_ctx *x : contexts_of(c)) {
+        HIP_TRY(c, hipSetDevice(x->device));
+        DevBuf<uint8_t> d_ops;
+        HIP_TRY(c, d_ops.alloc((size_t)n * sizeof(WsEditOp)));
+        HIP_TRY(c, hipMemcpy(d_ops.p, list.data(), (size_t)n * sizeof(WsEditOp), hipMemcpyHostToDevice));
+        for (size_t first = 0; first < (size_t)n; first += YCGE_WS_EDIT_OPS_PER_LAUNCH) {
+            const size_t m = std::min<size_t>(YCGE_WS_EDIT_OPS_PER_LAUNCH, (size_t)n - first);
+            uint64_t max_cells = 0;
+            for (size_t k = first; k < first + m; k++) {
+                const WsEditOp &o = list[k];
+                max_cells = std::max(max_cells, (uint64_t)(o.hi[0] - o.lo[0] + 1) * (uint64_t)(o.hi[1] - o.lo[1] + 1) * (uint64_t)(o.hi[2] - o.lo[2] + 1));
+            }
+            const int e = ycge_launch_world_store_edit(x->world_store.d_cells.p, &W, (const WsEditOp *)d_ops.p + first, (int)m, max_cells, x->stream);
+            if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ws_edit launch failed: %s", hipGetErrorString((hipError_t)e));
+        }
+        HIP_TRY(c, hipStreamSynchronize(x->stream));          // (d_ops goes when this scope ends)
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the occupancy, on the root: a word per chunk of the touched chunk columns cx0..cx1, run by run
+    for (int cx0 = 0; cx0 < W.ncx;) {
+        auto column_touched = [&](int cx) { return std::find(touched.begin() + (ptrdiff_t)(cx * per_cx), touched.begin() + (ptrdiff_t)((cx + 1) * per_cx), (uint8_t)1) != touched.begin() + (ptrdiff_t)((cx + 1) * per_cx); };
+        if (!column_touched(cx0)) { cx0++; continue; }
+        int cx1 = cx0;
+        while (cx1 + 1 < W.ncx && column_touched(cx1 + 1)) cx1++;
+        const size_t first = (size_t)cx0 * per_cx, count = (size_t)(cx1 - cx0 + 1) * per_cx;
+        std::vector<uint32_t> words(count);
+        for (size_t i = 0; i < count; i++) words[i] = touched[first + i] ? 0u : (uint32_t)(occupied[first + i] != 0);
+        DevBuf<uint32_t> d_occ;          // (as long as the whole store's: k_ws_occupied indexes it by the chunk's number)
+        HIP_TRY(c, d_occ.alloc(st.occupied.size()));
+        HIP_TRY(c, hipMemcpy(d_occ.p + first, words.data(), count * 4, hipMemcpyHostToDevice));
+        const int x0 = cx0 * W.S, x1 = std::min(W.nx, (cx1 + 1) * W.S);
+        const int e = ycge_launch_world_store_occupied(st.d_cells.p, &W, x0, x1 - x0, d_occ.p, c->stream);
+        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ws_occupied launch failed: %s", hipGetErrorString((hipError_t)e));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        rc = copy_out(c, words.data(), d_occ.p + first, count * 4);
+        if (rc != YCGE_OK) return rc;
+        for (size_t i = 0; i < count; i++) occupied[first + i] = words[i] != 0;
+        cx0 = cx1 + 1;
+    }
+    st.occupied.swap(occupied);
+    return YCGE_OK;
+}
+
 int world_store_generate_stats(ycge_ctx *c, int64_t *out9)
 {
     if (!c || !out9) return YCGE_ERR_INVALID_ARG;

@@ -22,9 +22,20 @@ struct WsChunk {
 };
 static_assert(sizeof(WsChunk) == 32, "WsChunk must be 32 B");
 
+#define YCGE_WS_EDIT_OPS_PER_LAUNCH 32768   // ops of one k_ws_edit launch (its gridDim.y)
+
+struct WsEditOp {                       // one op of ycge_world_store_edit: every cell of the inclusive box, in store cell coordinates, becomes {mat, meta}
+    int32_t lo[3], hi[3];
+    int32_t mat, meta;
+};
+static_assert(sizeof(WsEditOp) == 32, "WsEditOp must be 32 B");
+
 }  // namespace ycge
 
 extern "C" {
+// k_ws_edit: the m ops at `ops` (device memory, list order; m <= YCGE_WS_EDIT_OPS_PER_LAUNCH) into the store at `cells`, the later op winning where boxes overlap;
+// max_cells: the largest box among them
+int ycge_launch_world_store_edit(int32_t *cells, const ycge::WsShape *shape, const ycge::WsEditOp *ops, int m, uint64_t max_cells, void *stream);
 // k_ws_occupied over the x-planes [x0, x0 + planes) of the store at `cells` (the whole store's base): occupied[(cx * ncy + cy) * ncz + cz] |= 1 for
 // every chunk with a cell of mat != 0 in those planes.  The words are the caller's to zero, once, before the first slab.
 int ycge_launch_world_store_occupied(const int32_t *cells, const ycge::WsShape *shape, int32_t x0, int32_t planes, uint32_t *occupied, void *stream);

@@ -9,8 +9,10 @@
 //   k_ws_slice      blockIdx.y = chunk of the group: cell i of the destination (ycge_grid.cells order) from the store, by the chunk's record.
 //                   The 8-byte form only: with an odd nz or an odd clipped sz no row pair starts 16-byte aligned, and the aligned worlds gain
 //                   nothing that has been measured.
+//   k_ws_edit       ycge_world_store_edit: one lane per cell of an op's box writes the op's pair (described at the kernel).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "ycge_world_store.h"
@@ -58,7 +60,42 @@ __global__ __launch_bounds__(kBlock) void k_ws_slice(const int2 *__restrict__ ce
     }
 }
 
+// ycge_world_store_edit.  blockIdx.y = op j of the launch, one lane per cell of its box (grid-stride).  The ops of a launch may overlap and the
+// later op wins: a lane walks the ops AFTER its own in list order and leaves its cell alone when one of them covers it - that op's lane
+// writes it - so every cell is written by exactly one lane, that of the last op that covers it, whatever order the workgroups run in.
+// The walk reads the ops at workgroup-uniform addresses (scalar loads) and skips an op whose box misses op j's by a uniform branch.
+// Launches follow each other on one stream, so the rule holds across them.  Plain 8-byte vector stores, no atomics, no LDS, no scratch.
+__global__ __launch_bounds__(kBlock) void k_ws_edit(int2 *__restrict__ cells, WsShape W, const WsEditOp *__restrict__ ops, int m)
+{
+    const int j = (int)blockIdx.y;
+    const WsEditOp E = ops[j];
+    const uint32_t sy = (uint32_t)(E.hi[1] - E.lo[1] + 1), sz = (uint32_t)(E.hi[2] - E.lo[2] + 1);
+    const uint64_t plane = (uint64_t)sy * sz, n = (uint64_t)(uint32_t)(E.hi[0] - E.lo[0] + 1) * plane;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        const int x = E.lo[0] + (int)(i / plane);
+        const uint32_t r = (uint32_t)(i % plane);
+        const int y = E.lo[1] + (int)(r / sz), z = E.lo[2] + (int)(r % sz);
+        bool later = false;
+        for (int k = j + 1; k < m; k++) {
+            const WsEditOp L = ops[k];
+            if (L.hi[0] < E.lo[0] || L.lo[0] > E.hi[0] || L.hi[1] < E.lo[1] || L.lo[1] > E.hi[1] || L.hi[2] < E.lo[2] || L.lo[2] > E.hi[2]) continue;          // (uniform)
+            later |= x >= L.lo[0] && x <= L.hi[0] && y >= L.lo[1] && y <= L.hi[1] && z >= L.lo[2] && z <= L.hi[2];
+        }
+        if (!later) cells[((size_t)x * W.ny + (size_t)y) * W.nz + (size_t)z] = make_int2(E.mat, E.meta);
+    }
+}
+
 }  // namespace
+
+extern "C" int ycge_launch_world_store_edit(int32_t *cells, const WsShape *shape, const WsEditOp *ops, int m, uint64_t max_cells, void *stream)
+{
+    if (m <= 0 || max_cells == 0) return 0;
+    if (m > YCGE_WS_EDIT_OPS_PER_LAUNCH) return (int)hipErrorInvalidValue;
+    const uint64_t per_block = (uint64_t)kBlock * kSliceCellsPerLane;
+    const uint64_t bx = std::min<uint64_t>((max_cells + per_block - 1) / per_block, 65536);
+    hipLaunchKernelGGL(k_ws_edit, dim3((unsigned)bx, (unsigned)m), dim3(kBlock), 0, (hipStream_t)stream, (int2 *)cells, *shape, ops, m);
+    return (int)hipGetLastError();
+}
 
 extern "C" int ycge_launch_world_store_occupied(const int32_t *cells, const WsShape *shape, int32_t x0, int32_t planes, uint32_t *occupied, void *stream)
 {

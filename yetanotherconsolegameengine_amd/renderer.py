@@ -327,6 +327,37 @@ class RaytraceRenderer:
         self._check(rc)
         return [int(out[k]) for k in range(n)]
 
+    # ---------------------------------------------------------------- voxel edits (ycge_scene_edit_voxels / ycge_world_store_edit)
+    @staticmethod
+    def _edit_ops(ops) -> np.ndarray:
+        """int32 [n, 9] = ycge_voxel_edit: {grid_index, lo xyz, hi xyz, mat_id, meta_id} per op (rows of nine, or (grid, lo, hi, mat, meta))."""
+        rows = [np.concatenate([np.atleast_1d(np.asarray(f, np.int64)).ravel() for f in op]) for op in ops] if not isinstance(ops, np.ndarray) else ops
+        arr = np.ascontiguousarray(np.asarray(rows, np.int64).reshape(-1, 9)).astype(np.int32)
+        assert arr.itemsize * 9 == C.sizeof(abi.VoxelEdit)
+        return arr
+
+    def EditVoxels(self, ops) -> dict:
+        """ycge_scene_edit_voxels: every cell of each op's inclusive box lo..hi of resident grid grid_index becomes (mat_id, meta_id), in list
+        order (where boxes overlap the later op wins).  The scene is complete afterwards - the objects are installed again when a held
+        grid's solid box or brick mask changed.  All or nothing: a refused list (YcgeError, the message names the op) changes nothing.
+        Returns {cells_changed, bricks_written, records_changed, objects_installed}."""
+        arr = self._edit_ops(ops)
+        info = (C.c_uint32 * 4)()
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_edit_voxels(self.ctx, arr.ctypes.data if len(arr) else None, len(arr), info)
+        self.stream_call_s["edit"] = time.perf_counter() - t0
+        self._check(rc)
+        return dict(zip(abi.VOXEL_EDIT_INFO, (int(v) for v in info)))
+
+    def EditWorldCells(self, ops) -> None:
+        """ycge_world_store_edit: the same ops in store cell coordinates (grid_index 0) written into the world store as raw pairs; the
+        occupancy of the chunks they touch follows.  No scene is touched: grids attached earlier keep their cells (EditVoxels)."""
+        arr = self._edit_ops(ops)
+        t0 = time.perf_counter()
+        rc = self.L.ycge_world_store_edit(self.ctx, arr.ctypes.data if len(arr) else None, len(arr))
+        self.stream_call_s["edit_world"] = time.perf_counter() - t0
+        self._check(rc)
+
     def ReleaseWorld(self) -> None:
         self._check(self.L.ycge_world_store_release(self.ctx))
 

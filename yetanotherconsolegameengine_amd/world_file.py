@@ -247,6 +247,48 @@ def stream_resident(renderer, proto, center, chunk_size: int, view_distance_chun
     return todo, removed, [i for i in gone if i >= 0]
 
 
+def clip_ops_to_chunks(ops, keys: Iterable[Tuple[int, int, int]], chunk_size: int) -> dict:
+    """World-coordinate edit ops (int [n, 9]: {0, lo xyz, hi xyz, mat_id, meta_id}, ycge_voxel_edit rows with grid_index 0) cut to the chunks
+    `keys`: {key: int32 [m, 8] = {lo xyz, hi xyz, mat_id, meta_id} in the chunk's own cell indices, in list order} for every key a box
+    intersects.  A chunk's far faces need no clipping of their own: a box inside the world ends where the world ends."""
+    ops = np.asarray(ops, np.int64).reshape(-1, 9)
+    out = {}
+    for key in keys:
+        base = np.asarray(key, np.int64) * chunk_size
+        rows = []
+        for op in ops:
+            lo, hi = np.maximum(op[1:4], base), np.minimum(op[4:7], base + chunk_size - 1)
+            if (lo <= hi).all():
+                rows.append([*(lo - base), *(hi - base), op[7], op[8]])
+        if rows:
+            out[tuple(int(v) for v in key)] = np.asarray(rows, np.int32)
+    return out
+
+
+def edit_resident(renderer, ops, loaded: dict, chunk_size: int, proto=None):
+    """The SetBlock a host would write over a world that is resident on the device: the world-coordinate `ops` (int [n, 9], rows of
+    {0, lo xyz, hi xyz, mat_id, meta_id}; list order, the later op wins) go to the world store (RaytraceRenderer.EditWorldCells) and, clipped
+    and translated to chunk-local boxes, to every loaded chunk they intersect (RaytraceRenderer.EditVoxels, one call) - afterwards the
+    resident grids and the store agree, and no cell crossed the bus.  `loaded` is stream_resident's map (key -> device grid index, -1 for
+    a chunk in view that took no slot); a chunk in view that the edit makes occupied is attached from the store when `proto` (the
+    abi.Grid of stream_resident) is given, and its index entered.  Returns (EditVoxels' info or None when no loaded chunk was touched,
+    the keys attached); the caller shows a new chunk with its next object list, as after stream_resident."""
+    ops = np.asarray(ops, np.int64).reshape(-1, 9)
+    renderer.EditWorldCells(ops)
+    local = clip_ops_to_chunks(ops, [k for k, i in loaded.items() if i >= 0], chunk_size)
+    rows = [[loaded[key], *r] for key, boxes in local.items() for r in boxes]
+    info = renderer.EditVoxels(np.asarray(rows, np.int64)) if rows else None
+    attached = []
+    if proto is not None:
+        _, _, occupied = renderer.WorldInfo()
+        inside = lambda k: all(0 <= k[a] < occupied.shape[a] for a in range(3))
+        todo = [k for k in clip_ops_to_chunks(ops, [k for k, i in loaded.items() if i < 0 and inside(k)], chunk_size) if occupied[k]]
+        for key, i in zip(todo, renderer.AttachWorldChunks(todo, proto) if todo else []):
+            loaded[key] = i
+            attached.append(key)
+    return info, attached
+
+
 def load_all_order(dims, chunk_size: int, center, world_min, voxel_size) -> List[Tuple[int, int, int]]:
     """The keys of every chunk of a world of `dims` cells in the order ReloadFromExistingFile queues them (WorldManager.cs:447-480): by
     squared distance of (cx, cz) from the centre column - clamped into the world, :465-468 - then cy.  The C# sort is not stable and starts
