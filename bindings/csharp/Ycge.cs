@@ -255,6 +255,10 @@ namespace ConsoleGame.RayTracing.Native
         // voxel edits of resident grids and of the world store (found by symbol lookup, ABI stays 10); HipVoxelEdits in YcgeWorld.cs
         [DllImport(Lib)] public static extern int ycge_scene_edit_voxels(IntPtr ctx, YVoxelEdit* ops, int n, uint* outInfo);
         [DllImport(Lib)] public static extern int ycge_world_store_edit(IntPtr ctx, YVoxelEdit* ops, int n);
+        // the pool of materialised chunks that lets a fields store take edits (found by symbol lookup, ABI stays 10); HipWorldStore.ReserveEdits in YcgeWorld.cs
+        [DllImport(Lib)] public static extern int ycge_world_store_reserve_edits(IntPtr ctx, int maxChunks);
+        [DllImport(Lib)] public static extern int ycge_world_store_edit_slots(IntPtr ctx, int* capacityOut, int* usedOut);
+        [DllImport(Lib)] public static extern int ycge_world_store_revert_chunks(IntPtr ctx, int* keys, int n);
         [DllImport(Lib)] public static extern int ycge_scene_update_texture(IntPtr ctx, int textureIndex, IntPtr frame, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_resize(IntPtr ctx, int fbWidth, int fbHeight, int superSample);
         [DllImport(Lib)] public static extern int ycge_set_camera(IntPtr ctx, float* pos, float yaw, float pitch, float fovDeg);

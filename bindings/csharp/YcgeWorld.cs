@@ -128,6 +128,26 @@ namespace ConsoleGame.RayTracing.Native
             return index;
         }
 
+        /// <summary>A store generated with Ycge.WorldStoreFields takes edits (HipVoxelEdits.ApplyToStore) only with a pool of materialised
+        /// chunks: maxChunks slots of ChunkSize^3 cells, 8 bytes a cell, on every device.  Every chunk an op touches takes a slot and keeps it
+        /// until RevertChunks; an edit that needs more slots than are free is refused as a whole (YCGE_ERR_OUT_OF_MEMORY).  A later call with a
+        /// larger count grows the pool.  Release, Load and Generate drop it.</summary>
+        public void ReserveEdits(IntPtr ctx, int maxChunks) { Ycge.Check(ctx, Ycge.ycge_world_store_reserve_edits(ctx, maxChunks)); }
+
+        /// <summary>{slots of the pool, slots that hold a chunk}; {0, 0} for a store without a pool.</summary>
+        public int[] EditSlots(IntPtr ctx)
+        {
+            var s = new int[2];
+            fixed (int* p = s) Ycge.Check(ctx, Ycge.ycge_world_store_edit_slots(ctx, p, p + 1));
+            return s;
+        }
+
+        /// <summary>keys: {cx, cy, cz} per chunk.  Their slots are free again and each chunk is the generated chunk once more.</summary>
+        public void RevertChunks(IntPtr ctx, int[] keys)
+        {
+            fixed (int* k = keys) Ycge.Check(ctx, Ycge.ycge_world_store_revert_chunks(ctx, k, keys.Length / 3));
+        }
+
         public void Release(IntPtr ctx) { Ycge.Check(ctx, Ycge.ycge_world_store_release(ctx)); Nx = Ny = Nz = 0; }
     }
 

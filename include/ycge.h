@@ -553,11 +553,44 @@ int ycge_scene_edit_voxels(ycge_ctx *ctx, const ycge_voxel_edit *ops, int32_t n,
  * chunks of the far faces included: a chunk may become empty - an attach of its key then reports -1 - or occupied.  Afterwards the
  * store is what ycge_world_store_load of the edited cells gives, to ycge_world_store_read, ycge_world_store_info and
  * ycge_scene_attach_world_chunks alike.  A device cell store is edited by kernels, a YCGE_WORLD_STORE_HOST store by a host loop; a
- * YCGE_WORLD_STORE_FIELDS store holds no cells and refuses with YCGE_ERR_UNSUPPORTED (generate with YCGE_WORLD_STORE_CELLS instead).
+ * YCGE_WORLD_STORE_FIELDS store holds no cells and refuses with YCGE_ERR_UNSUPPORTED (generate with YCGE_WORLD_STORE_CELLS instead) -
+ * unless it has a pool of materialised chunks (ycge_world_store_reserve_edits, below), which changes nothing else of this contract.
  * No scene is touched: grids attached earlier are encoded copies and keep their cells (edit those with ycge_scene_edit_voxels).  The
  * call waits for frames in flight only where ycge_world_store_read would.  Every device of a multi-device context edits its own copy.
  * Refusals as above, all or nothing, the message names the op; in addition: no store, grid_index != 0, a box that leaves the store. */
 int ycge_world_store_edit(ycge_ctx *ctx, const ycge_voxel_edit *ops, int32_t n);
+/* --- edits on a YCGE_WORLD_STORE_FIELDS store: a pool of materialised chunks beside the fields, copy-on-write at chunk granularity.  A
+ * played world edits a few hundred chunks of thousands, so the fields stay and cells exist only for chunks that were edited.  Found by
+ * symbol lookup; YCGE_ABI_VERSION stays 10, no existing struct changes.
+ * ycge_world_store_reserve_edits gives the context's fields store a pool of max_chunks slots of S^3 cells (S: the chunk size), 8 bytes a
+ * cell in ycge_grid.cells order: max_chunks * S^3 * 8 bytes ON EVERY DEVICE of a one-process multi-device context (each holds its own
+ * pool; a peer context is refused).  A generated store's dimensions are whole chunks, so no slot is clipped.  A later call with another
+ * count resizes the pool and keeps the slots in use.  ycge_world_store_release and a new ycge_world_store_load or _generate drop the
+ * pool with the store.
+ *   Refusals are all or nothing - the store and an earlier pool stay as they were.  YCGE_ERR_INVALID_ARG with a message: no store, a
+ *     store that is not in the fields form (it holds its cells and needs no pool; YCGE_WORLDGEN_HOST and YCGE_WORLD_STORE_HOST make such
+ *     a store whatever the form asked for), max_chunks < 1, above the store's chunk count or below the slots in use.
+ *     YCGE_ERR_OUT_OF_MEMORY: an allocation that fails.
+ * With a pool ycge_world_store_edit makes every check it makes on a cell store, in the same order, on the host before any device work.
+ *   Then EVERY CHUNK AN OP TOUCHES TAKES A SLOT and keeps it - also when the pair written equals what the generator made; nothing
+ *   reclaims a slot but ycge_world_store_revert_chunks.  There are two ways to run out of slots: the pool is smaller than the number of
+ *   distinct chunks the host edits over time (grow it with a larger max_chunks, or revert chunks), or one call's ops touch more chunks
+ *   without a slot than slots are free.  Such a call is refused as a whole with YCGE_ERR_OUT_OF_MEMORY and nothing is written; the message
+ *   names the first op that does not fit and gives both counts.  Otherwise the new slots' chunks are made from the fields (k_wp_fill, a
+ *   launch per batch of chunks), the ops - clipped against the chunks they touch - are applied in list order with the later winning
+ *   (k_ws_pool_edit), the touched slots' occupancy is found again (k_ws_pool_occupied) and one small read-back follows.  YCGE_WS_POOL_BATCH
+ *   at ycge_create (default and most 32768) bounds the records of one such launch.
+ * Every reader sees the pool: to ycge_world_store_read (k_ws_pool_planes over k_wp_planes' slab), ycge_world_store_info and
+ *   ycge_scene_attach_world_chunks (a chunk that holds a slot is copied out of it, in one batch with chunks made from the fields; an
+ *   emptied chunk reports -1, a generated-empty chunk that an edit made solid attaches) the store is what a YCGE_WORLD_STORE_CELLS store
+ *   of the same world and window is after the same ycge_world_store_edit calls. */
+int ycge_world_store_reserve_edits(ycge_ctx *ctx, int32_t max_chunks);
+/* The pool's slots and how many of them hold a chunk (either may be NULL); 0 and 0 for a store without a pool and for no store. */
+int ycge_world_store_edit_slots(ycge_ctx *ctx, int32_t *capacity_out, int32_t *used_out);
+/* Give the slots of these chunks back: each is the generated chunk again, its cells and its occupancy, to every reader.  A key that
+ * holds no slot (or repeats) is not an error, nor is a store without a pool.  No device work.  YCGE_ERR_INVALID_ARG, nothing changed: no
+ * store, a NULL keys with n > 0, n < 0, a key outside the chunk counts (the message names the key), a peer context. */
+int ycge_world_store_revert_chunks(ycge_ctx *ctx, const int32_t *keys /* 3 n */, int32_t n);
 
 /* The argument checks of ycge_scene_upload on their own: pure host code, no device and no context needed
  * (every index in range, counts non-negative, pointers present, material kinds known).  Returns YCGE_OK or the

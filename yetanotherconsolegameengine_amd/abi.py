@@ -261,6 +261,10 @@ _PROTOTYPES = {
     # voxel edits of resident grids and of the world store (ops: an array of abi.VoxelEdit; out_info: uint32 [4] or None)
     "ycge_scene_edit_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]),
     "ycge_world_store_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    # the pool of materialised chunks that lets a fields store take edits (keys: int32 [n, 3])
+    "ycge_world_store_reserve_edits": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ycge_world_store_edit_slots": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ycge_world_store_revert_chunks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "ycge_scene_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "ycge_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ycge_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]),

@@ -238,6 +238,7 @@ struct Knobs {
     bool exposure_serial = false;    // YCGE_EXPOSURE_SERIAL: the one-lane chain instead of the chunked exact evaluation
     bool world_store_host = false;   // YCGE_WORLD_STORE_HOST: ycge_world_store_load keeps the world in host memory; its chunks are sliced by a host loop and go up as an attach's cells do
     size_t world_store_slab_bytes = YCGE_WORLD_STORE_SLAB_BYTES_DEFAULT;   // YCGE_WORLD_STORE_SLAB_BYTES: bytes of whole x-planes staged per slab of a load (one plane at least)
+    int ws_pool_batch = YCGE_WS_POOL_BATCH_DEFAULT;   // YCGE_WS_POOL_BATCH: records (chunks to materialise, clipped ops, slots) in one launch of the edit pool's kernels, 1..32768
     void read()
     {
         auto geti = [](const char *n, int dflt) { const char *e = getenv(n); return e ? atoi(e) : dflt; };
@@ -295,6 +296,8 @@ struct Knobs {
         worldgen_host = getenv("YCGE_WORLDGEN_HOST") != nullptr;
         world_store_host = getenv("YCGE_WORLD_STORE_HOST") != nullptr;
         if (const char *e = getenv("YCGE_WORLD_STORE_SLAB_BYTES")) { const long long v = atoll(e); if (v > 0) world_store_slab_bytes = (size_t)v; }
+        ws_pool_batch = geti("YCGE_WS_POOL_BATCH", YCGE_WS_POOL_BATCH_DEFAULT);
+        if (ws_pool_batch < 1 || ws_pool_batch > YCGE_WS_POOL_BATCH_DEFAULT) ws_pool_batch = YCGE_WS_POOL_BATCH_DEFAULT;
         if (const char *e = getenv("YCGE_ENC_GROUP_BYTES")) { const long long v = atoll(e); if (v > 0) enc_group_bytes = (size_t)v; }
         mesh_emit_host = getenv("YCGE_MESH_EMIT_HOST") != nullptr;
         mesh_emit_device_min = geti("YCGE_MESH_EMIT_DEVICE_MIN", YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT);
@@ -558,6 +561,13 @@ struct WorldStore {
     // microseconds: field kernels, anyLeaves pass loop, occupancy + read-back, plane kernels (CELLS form; stream time), the host generator
     int64_t gen_form = -1, gen_on_host = 0, gen_passes = 0, gen_slabs = 0;
     double gen_us[5] = {0, 0, 0, 0, 0};
+    // ycge_world_store_reserve_edits, a fields store: the pool of materialised chunks.  d_pool is this context's device's; the map is the root's.
+    DevBuf<uint8_t> d_pool;                            // pool_cap slots of pool_stride bytes: a chunk's S^3 cells as k_wp_fill writes them
+    size_t pool_stride = 0;
+    int32_t pool_cap = 0, pool_used = 0;
+    std::vector<int32_t> slot_of;                      // per chunk (occupied's order): its slot, or -1
+    std::vector<int32_t> chunk_in;                     // per slot: its chunk, or -1
+    std::vector<uint8_t> gen_occupied;                 // per chunk: what the generate found (occupied follows the edits)
 };
 
 struct ycge_ctx {
@@ -1011,4 +1021,8 @@ int world_store_generate(ycge_ctx *c, const ycge_world *world, int32_t chunks_x,
 int world_store_read(ycge_ctx *c, int32_t x0, int32_t planes, int32_t *cells_out);
 int world_store_generate_stats(ycge_ctx *c, int64_t *out9);
 int world_store_edit(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n);          // ... and of ycge_world_store_edit
+// ... and of the pool of materialised chunks beside a fields store: ycge_world_store_reserve_edits / _edit_slots / _revert_chunks
+int world_store_reserve_edits(ycge_ctx *c, int32_t max_chunks);
+int world_store_edit_slots(ycge_ctx *c, int32_t *capacity_out, int32_t *used_out);
+int world_store_revert_chunks(ycge_ctx *c, const int32_t *keys, int32_t n);
 } // namespace ycge_host

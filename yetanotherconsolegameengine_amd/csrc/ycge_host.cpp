@@ -722,6 +722,25 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// the pool of materialised chunks that lets a fields store take edits (ycge_world_store.cpp)
+int ycge_world_store_reserve_edits(ycge_ctx *c, int32_t max_chunks)
+try {
+    return world_store_reserve_edits(c, max_chunks);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_world_store_edit_slots(ycge_ctx *c, int32_t *capacity_out, int32_t *used_out)
+try {
+    return world_store_edit_slots(c, capacity_out, used_out);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_world_store_revert_chunks(ycge_ctx *c, const int32_t *keys, int32_t n)
+try {
+    return world_store_revert_chunks(c, keys, n);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 int ycge_debug_world_store_generate_stats(ycge_ctx *c, int64_t *out9)
 try {
     return world_store_generate_stats(c, out9);

@@ -100,6 +100,18 @@ int fields_chunk_to_host(ycge_ctx *c, const WorldStore &st, const std::array<int
     return copy_out(c, out, d.p + 512, bytes);
 }
 
+// ... and as every reader sees it: out of its slot of the edit pool when it holds one, made from the fields otherwise
+int chunk_to_host(ycge_ctx *c, const WorldStore &st, const std::array<int32_t, 3> &key, int32_t *out)
+{
+    const int slot = st.pool_cap ? st.slot_of[chunk_of(st.shape, key[0], key[1], key[2])] : -1;
+    if (slot < 0) return fields_chunk_to_host(c, st, key, out);
+    const size_t S = (size_t)st.shape.S;
+    const DeviceGuard guard(c->device);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return copy_out(c, out, st.d_pool.p + (size_t)slot * st.pool_stride, S * S * S * 8);
+}
+
 // the chunks of one ycge_scene_attach_world_chunks on a fields store: ycge_scene_generate_world's source, filling from the fields the store keeps
 struct FieldCells : WindowCells {
     WorldStore &store;                     // the root's
@@ -107,7 +119,33 @@ struct FieldCells : WindowCells {
     uint8_t *fields_of(ycge_ctx *x) const override { return x->world_store.d_fields.p; }
     std::string where(size_t k, uint32_t cell) const override { return chunk_where(store.shape, keys[k], cell); }
     // for the host encoder (a lookup table k_grid_encode does not take)
-    int write(ycge_ctx *root, size_t k, const ycge_grid &, int32_t *cells) override { return fields_chunk_to_host(root, store, keys[k], cells); }
+    int write(ycge_ctx *root, size_t k, const ycge_grid &, int32_t *cells) override { return chunk_to_host(root, store, keys[k], cells); }
+    int slot_of(size_t k) const { return store.pool_cap ? store.slot_of[chunk_of(store.shape, keys[k][0], keys[k][1], keys[k][2])] : -1; }
+    // the generator's records and `any` words for a group of m, then a copy record for every chunk of the group that holds a slot of the
+    // pool.  fill_chunks sends GeneratedCells::head_bytes(m') bytes for the m' <= m chunks it makes, so it writes inside the generator's
+    // part and never reaches the copy records, which a kernel in flight may still be reading.
+    size_t head_bytes(size_t m) const override { return WindowCells::head_bytes(m) + align_up(m * sizeof(WsPoolCopy), 256); }
+    // a chunk that holds a slot is copied out of it (k_ws_pool_copy, one launch for the group's); the others are made from the fields as ever
+    int fill(ycge_ctx *root, ycge_ctx *x, const std::vector<int> &group, uint8_t *d_head, const std::vector<int32_t *> &d_cells) override
+    {
+        if (!store.pool_used) return WindowCells::fill(root, x, group, d_head, d_cells);
+        std::vector<int> made;
+        std::vector<int32_t *> made_cells;
+        std::vector<WsPoolCopy> copies;
+        for (size_t j = 0; j < group.size(); j++) {
+            const int slot = slot_of((size_t)group[j]);
+            if (slot < 0) { made.push_back(group[j]); made_cells.push_back(d_cells[j]); }
+            else copies.push_back(WsPoolCopy{slot, 0, d_cells[j]});
+        }
+        if (!copies.empty()) {
+            uint8_t *d_copies = d_head + WindowCells::head_bytes(group.size());
+            HIP_TRY(root, hipMemcpy(d_copies, copies.data(), copies.size() * sizeof(WsPoolCopy), hipMemcpyHostToDevice));
+            const WorldStore &xs = x->world_store;
+            const int e = ycge_launch_world_store_pool_copy(xs.d_pool.p, store.pool_stride, store.shape.S, (const WsPoolCopy *)d_copies, (int)copies.size(), x->stream);
+            if (e != 0) return root->fail(YCGE_ERR_DEVICE, "k_ws_pool_copy launch failed: %s", hipGetErrorString((hipError_t)e));
+        }
+        return made.empty() ? YCGE_OK : fill_chunks(root, x, made, d_head, made_cells);
+    }
 };
 
 // the chunks of one ycge_scene_attach_world_chunks: grid k of the attach is chunk keys[k]
@@ -384,7 +422,7 @@ int world_store_chunk(ycge_ctx *c, int32_t cx, int32_t cy, int32_t cz, int32_t *
     if (st.on_host) { slice_host(W, st.host_cells.data(), {{cx, cy, cz}}, cells_out); return YCGE_OK; }
     rc = quiesce(c);          // (copy_out's staging is the frames' too)
     if (rc != YCGE_OK) return rc;
-    if (st.fields) return fields_chunk_to_host(c, st, {{cx, cy, cz}}, cells_out);
+    if (st.fields) return chunk_to_host(c, st, {{cx, cy, cz}}, cells_out);
     return slice_to_host(c, st, {{cx, cy, cz}}, cells_out);
 }
 
@@ -468,6 +506,7 @@ int world_store_generate(ycge_ctx *c, const ycge_world *world, int32_t chunks_x,
     if (form == YCGE_WORLD_STORE_FIELDS) {
         for (WorldStore &s : made) s.fields = true;
         R.bytes = (int64_t)fields_bytes;
+        R.gen_occupied = R.occupied;          // (what ycge_world_store_revert_chunks gives a chunk back)
     } else {
         // the cell store, written where it will lie: x-slabs of k_wp_planes on every device, and on the root k_ws_occupied behind each slab -
         // the loaded store's occupancy kernel on the generated cells, which must find what k_wp_occupied found in the fields
@@ -523,6 +562,44 @@ int world_store_generate(ycge_ctx *c, const ycge_world *world, int32_t chunks_x,
     return YCGE_OK;
 }
 
+// the records at `recs` (m of `bytes_each` bytes) on the current device, ws_pool_batch of them at a time: launch(device records, first, count)
+template <class Launch>
+static int pool_batches(ycge_ctx *c, const void *recs, size_t m, size_t bytes_each, DevBuf<uint8_t> &d_recs, const char *kernel, Launch launch)
+{
+    if (m == 0) return YCGE_OK;
+    HIP_TRY(c, d_recs.alloc(m * bytes_each));
+    HIP_TRY(c, hipMemcpy(d_recs.p, recs, m * bytes_each, hipMemcpyHostToDevice));
+    const size_t per = (size_t)c->knobs.ws_pool_batch;
+    for (size_t first = 0; first < m; first += per) {
+        const int e = launch(d_recs.p + first * bytes_each, first, std::min(per, m - first));
+        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "%s launch failed: %s", kernel, hipGetErrorString((hipError_t)e));
+    }
+    return YCGE_OK;
+}
+
+// behind k_wp_planes on the root's stream: the part of every slot in use that lies in the x-planes [x0, x0 + planes) of a fields store, over the slab's cells (k_ws_pool_planes)
+static int pool_into_slab(ycge_ctx *c, const WorldStore &st, int32_t x0, int32_t planes, int32_t *slab)
+{
+    if (!st.pool_used) return YCGE_OK;
+    const WsShape &W = st.shape;
+    std::vector<WsPoolPlanes> recs;
+    for (int32_t slot = 0; slot < st.pool_cap; slot++) {
+        const int32_t ci = st.chunk_in[(size_t)slot];
+        if (ci < 0) continue;
+        const int32_t cx = ci / (W.ncy * W.ncz), cy = ci / W.ncz % W.ncy, cz = ci % W.ncz;
+        const int32_t lo = std::max(x0, cx * W.S), hi = std::min(x0 + planes, (cx + 1) * W.S);          // [lo, hi)
+        if (lo >= hi) continue;
+        recs.push_back(WsPoolPlanes{slot, lo - cx * W.S, hi - lo, lo - x0, cy, cz, {0, 0}});
+    }
+    DevBuf<uint8_t> d_recs;
+    const int rc = pool_batches(c, recs.data(), recs.size(), sizeof(WsPoolPlanes), d_recs, "k_ws_pool_planes", [&](uint8_t *d, size_t, size_t m) {
+        return ycge_launch_world_store_pool_planes(st.d_pool.p, st.pool_stride, W.S, (const WsPoolPlanes *)d, (int)m, slab, W.ny, W.nz, c->stream);
+    });
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));          // (d_recs goes when this scope ends)
+    return YCGE_OK;
+}
+
 int world_store_read(ycge_ctx *c, int32_t x0, int32_t planes, int32_t *cells_out)
 {
     int rc = need_root(c);
@@ -549,10 +626,129 @@ int world_store_read(ycge_ctx *c, int32_t x0, int32_t planes, int32_t *cells_out
         const size_t px = std::min(per, (size_t)planes - done);
         const int e = ycge_launch_worldpregen_planes(&st.gen_world, &st.gen_window, &F, (int32_t)((size_t)x0 + done), (int32_t)px, slab.p, c->stream);
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wp_planes launch failed: %s", hipGetErrorString((hipError_t)e));
+        rc = pool_into_slab(c, st, (int32_t)((size_t)x0 + done), (int32_t)px, slab.p);          // the edited chunks' cells over the generator's
+        if (rc != YCGE_OK) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         rc = copy_out(c, cells_out + 2 * done * plane_cells, slab.p, px * plane_bytes);
         if (rc != YCGE_OK) return rc;
     }
+    return YCGE_OK;
+}
+
+// ycge_world_store_edit on a fields store with a pool (the ops checked already, one at least): copy-on-write at chunk granularity.
+// Every chunk an op touches takes a slot - refused as a whole when the free slots do not suffice - and is made there by k_wp_fill, a
+// launch per batch of chunks; the ops, clipped against the chunks they touch and sorted by slot, are applied by k_ws_pool_edit;
+// k_ws_pool_occupied finds the touched slots' occupancy again and one read-back brings it home; the new slot map and occupancy are
+// installed in a last step that cannot fail.  Every device of the context materialises and edits its own pool.
+static int pool_edit(ycge_ctx *c, const std::vector<WsEditOp> &list)
+{
+    static const char *const fn = "ycge_world_store_edit";
+    WorldStore &st = c->world_store;
+    const WsShape &W = st.shape;
+    const int S = W.S;
+    auto chunks_of = [&](const WsEditOp &o, auto &&visit) {
+        for (int cx = o.lo[0] / S; cx <= o.hi[0] / S; cx++)
+            for (int cy = o.lo[1] / S; cy <= o.hi[1] / S; cy++)
+                for (int cz = o.lo[2] / S; cz <= o.hi[2] / S; cz++) visit(cx, cy, cz);
+    };
+    // 1. the touched chunks that hold no slot yet, against the free slots
+    const int32_t free_slots = st.pool_cap - st.pool_used;
+    std::vector<uint8_t> counted(st.occupied.size(), 0);
+    int64_t n_fresh = 0;
+    int first_unfit = -1;
+    for (size_t k = 0; k < list.size(); k++)
+        chunks_of(list[k], [&](int cx, int cy, int cz) {
+            const size_t ci = chunk_of(W, cx, cy, cz);
+            if (st.slot_of[ci] >= 0 || counted[ci]) return;
+            counted[ci] = 1;
+            if (++n_fresh > free_slots && first_unfit < 0) first_unfit = (int)k;
+        });
+    if (first_unfit >= 0)
+        return c->fail(YCGE_ERR_OUT_OF_MEMORY, "%s: op %d does not fit the edit pool: the ops touch %lld chunks that hold no slot and %d of its %d slots are free (ycge_world_store_reserve_edits grows the pool, ycge_world_store_revert_chunks gives slots back)",
+                       fn, first_unfit, (long long)n_fresh, free_slots, st.pool_cap);
+    // the new map, the chunks to make, the clipped ops and the touched slots - all on the host, nothing installed yet
+    std::vector<int32_t> slot_of = st.slot_of, chunk_in = st.chunk_in;
+    std::vector<int32_t> fresh_chunk, touched_slots;          // chunk numbers of the new slots, in the order they were given out; every slot an op touches, once
+    std::vector<uint8_t> slot_touched((size_t)st.pool_cap, 0);
+    std::vector<WsPoolEdit> recs;
+    int32_t next_free = 0;
+    for (const WsEditOp &o : list)
+        chunks_of(o, [&](int cx, int cy, int cz) {
+            const size_t ci = chunk_of(W, cx, cy, cz);
+            if (slot_of[ci] < 0) {
+                while (chunk_in[(size_t)next_free] >= 0) next_free++;          // (the lowest free slot: there is one, counted above)
+                slot_of[ci] = next_free; chunk_in[(size_t)next_free] = (int32_t)ci;
+                fresh_chunk.push_back((int32_t)ci);
+            }
+            const int32_t slot = slot_of[ci];
+            if (!slot_touched[(size_t)slot]) { slot_touched[(size_t)slot] = 1; touched_slots.push_back(slot); }
+            const int base[3] = {cx * S, cy * S, cz * S};
+            WsPoolEdit r{};
+            r.slot = slot; r.mat = o.mat; r.meta = o.meta;
+            for (int a = 0; a < 3; a++) { r.lo[a] = std::max(o.lo[a] - base[a], 0); r.hi[a] = std::min(o.hi[a] - base[a], S - 1); }
+            recs.push_back(r);
+        });
+    std::stable_sort(recs.begin(), recs.end(), [](const WsPoolEdit &a, const WsPoolEdit &b) { return a.slot < b.slot; });          // (list order stays inside a slot)
+    const size_t m_fresh = fresh_chunk.size(), per = (size_t)c->knobs.ws_pool_batch;
+    const size_t off_any = align_up(m_fresh * sizeof(WgChunk), 256);
+
+    int rc = quiesce(c);          // (copy_out's staging is the frames' too)
+    if (rc != YCGE_OK) return rc;
+    const DeviceGuard guard(c->device);
+    for (ycge_ctx *x : contexts_of(c)) {
+        HIP_TRY(c, hipSetDevice(x->device));
+        WorldStore &xs = x->world_store;
+        // 2. the new slots' chunks, made where they will lie
+        DevBuf<uint8_t> d_head, d_recs;
+        if (m_fresh) {
+            std::vector<uint8_t> head(off_any + m_fresh * sizeof(uint32_t), 0);          // the chunks' records, then their `any` words, zeroed (not read: step 4 finds the occupancy)
+            for (size_t j = 0; j < m_fresh; j++) {
+                const int32_t ci = fresh_chunk[j];
+                ((WgChunk *)head.data())[j] = WgChunk{ci / (W.ncy * W.ncz), ci / W.ncz % W.ncy, ci % W.ncz, 0, (int32_t *)(xs.d_pool.p + (size_t)slot_of[(size_t)ci] * st.pool_stride)};
+            }
+            HIP_TRY(c, d_head.alloc(head.size()));
+            HIP_TRY(c, hipMemcpy(d_head.p, head.data(), head.size(), hipMemcpyHostToDevice));
+            WpFields F;
+            wp_layout(xs.d_fields.p, (size_t)st.gen_window.nx * st.gen_window.nz, 0, &F);
+            for (size_t first = 0; first < m_fresh; first += per) {
+                const int e = ycge_launch_worldpregen_fill((const WgChunk *)d_head.p + first, (int)std::min(per, m_fresh - first), &st.gen_world, &st.gen_window, &F,
+                                                           (uint32_t *)(d_head.p + off_any) + first, x->stream);
+                if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_wp_fill launch failed: %s", hipGetErrorString((hipError_t)e));
+            }
+        }
+        // 3. the ops
+        rc = pool_batches(c, recs.data(), recs.size(), sizeof(WsPoolEdit), d_recs, "k_ws_pool_edit", [&](uint8_t *d, size_t first, size_t m) {
+            uint64_t max_cells = 0;
+            for (size_t k = first; k < first + m; k++) {
+                const WsPoolEdit &r = recs[k];
+                max_cells = std::max(max_cells, (uint64_t)(r.hi[0] - r.lo[0] + 1) * (uint64_t)(r.hi[1] - r.lo[1] + 1) * (uint64_t)(r.hi[2] - r.lo[2] + 1));
+            }
+            return ycge_launch_world_store_pool_edit(xs.d_pool.p, st.pool_stride, S, (const WsPoolEdit *)d, (int)m, max_cells, x->stream);
+        });
+        if (rc != YCGE_OK) return rc;
+        HIP_TRY(c, hipStreamSynchronize(x->stream));          // (the records go when this scope ends)
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // 4. the touched slots' occupancy, on the root
+    const size_t m_touched = touched_slots.size();
+    std::vector<uint32_t> words(m_touched, 0);
+    {
+        DevBuf<uint8_t> d_slots;
+        DevBuf<uint32_t> d_words;
+        HIP_TRY(c, d_words.alloc(m_touched));
+        HIP_TRY(c, hipMemsetAsync(d_words.p, 0, m_touched * 4, c->stream));
+        rc = pool_batches(c, touched_slots.data(), m_touched, sizeof(int32_t), d_slots, "k_ws_pool_occupied", [&](uint8_t *d, size_t first, size_t m) {
+            return ycge_launch_world_store_pool_occupied(st.d_pool.p, st.pool_stride, S, (const int32_t *)d, (int)m, d_words.p + first, c->stream);
+        });
+        if (rc != YCGE_OK) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        rc = copy_out(c, words.data(), d_words.p, m_touched * 4);
+        if (rc != YCGE_OK) return rc;
+    }
+    // 5. nothing below fails
+    st.slot_of.swap(slot_of); st.chunk_in.swap(chunk_in);
+    st.pool_used += (int32_t)m_fresh;
+    for (size_t j = 0; j < m_touched; j++) st.occupied[(size_t)st.chunk_in[(size_t)touched_slots[j]]] = words[j] != 0;
     return YCGE_OK;
 }
 
@@ -569,8 +765,8 @@ int world_store_edit(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n)
     if (n < 0 || n > YCGE_VOXEL_EDIT_MAX_OPS || (n > 0 && !ops)) return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad op array (n = %d; at most %d ops)", fn, n, YCGE_VOXEL_EDIT_MAX_OPS);
     WorldStore &st = c->world_store;
     if (!st.held) return c->fail(YCGE_ERR_INVALID_ARG, "%s", kNoStore);
-    if (st.fields)
-        return c->fail(YCGE_ERR_UNSUPPORTED, "%s: a fields store holds no cells to edit; generate the store with YCGE_WORLD_STORE_CELLS", fn);
+    if (st.fields && !st.pool_cap)
+        return c->fail(YCGE_ERR_UNSUPPORTED, "%s: a fields store holds no cells to edit; generate the store with YCGE_WORLD_STORE_CELLS, or give this one a pool of materialised chunks (ycge_world_store_reserve_edits)", fn);
     const WsShape &W = st.shape;
     const int dims[3] = {W.nx, W.ny, W.nz};
     std::vector<WsEditOp> list((size_t)n);
@@ -590,6 +786,7 @@ int world_store_edit(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n)
                 for (int cz = e.lo[2] / W.S; cz <= e.hi[2] / W.S; cz++) touched[chunk_of(W, cx, cy, cz)] = 1;
     }
     if (n == 0) return YCGE_OK;
+    if (st.fields) return pool_edit(c, list);
     std::vector<uint8_t> occupied = st.occupied;          // (takes the store's place in a last step that cannot fail)
     const size_t per_cx = (size_t)W.ncy * W.ncz;
 
@@ -664,6 +861,91 @@ int world_store_edit(ycge_ctx *c, const ycge_voxel_edit *ops, int32_t n)
         cx0 = cx1 + 1;
     }
     st.occupied.swap(occupied);
+    return YCGE_OK;
+}
+
+// ycge_world_store_reserve_edits: the pool of a fields store made, or grown - every device's new pool allocated and the slots in use
+// copied into it before any context takes its own, so a refusal or a failure leaves the store and an earlier pool as they were.
+int world_store_reserve_edits(ycge_ctx *c, int32_t max_chunks)
+{
+    static const char *const fn = "ycge_world_store_reserve_edits";
+    int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    WorldStore &st = c->world_store;
+    if (!st.held) return c->fail(YCGE_ERR_INVALID_ARG, "%s", kNoStore);
+    if (!st.fields) return c->fail(YCGE_ERR_INVALID_ARG, "%s: the store is not in the fields form (YCGE_WORLD_STORE_FIELDS): it holds its cells and needs no pool", fn);
+    const size_t n_chunks = st.occupied.size();
+    if (max_chunks < 1 || (size_t)max_chunks > n_chunks) return c->fail(YCGE_ERR_INVALID_ARG, "%s: max_chunks %d is outside 1..%zu, the store's chunks", fn, max_chunks, n_chunks);
+    if (max_chunks < st.pool_used) return c->fail(YCGE_ERR_INVALID_ARG, "%s: max_chunks %d is below the %d slots in use (ycge_world_store_revert_chunks gives slots back)", fn, max_chunks, st.pool_used);
+    if (max_chunks == st.pool_cap) return YCGE_OK;
+    const size_t S = (size_t)st.shape.S, stride = align_up(S * S * S * 8, 16);
+    const std::vector<ycge_ctx *> ctxs = contexts_of(c);
+    if (st.pool_cap) { rc = quiesce(c); if (rc != YCGE_OK) return rc; }          // (an attach in flight may read the old pool)
+    const DeviceGuard guard(c->device);
+    std::vector<DevBuf<uint8_t>> made(ctxs.size());
+    // a smaller pool keeps its slots' numbers only while they fit: the slots in use are packed to the front of the new one
+    std::vector<int32_t> slot_of(n_chunks, -1), chunk_in((size_t)max_chunks, -1);
+    int32_t used = 0;
+    for (int32_t slot = 0; slot < st.pool_cap; slot++) {
+        const int32_t ci = st.chunk_in[(size_t)slot];
+        if (ci < 0) continue;
+        slot_of[(size_t)ci] = used; chunk_in[(size_t)used] = ci;
+        used++;
+    }
+    for (size_t i = 0; i < ctxs.size(); i++) {
+        HIP_TRY(c, hipSetDevice(ctxs[i]->device));
+        HIP_TRY(c, made[i].alloc((size_t)max_chunks * stride));
+        for (int32_t slot = 0; slot < st.pool_cap; slot++) {
+            const int32_t ci = st.chunk_in[(size_t)slot];
+            if (ci >= 0) HIP_TRY(c, hipMemcpyAsync(made[i].p + (size_t)slot_of[(size_t)ci] * stride, ctxs[i]->world_store.d_pool.p + (size_t)slot * stride, stride, hipMemcpyDeviceToDevice, ctxs[i]->stream));
+        }
+        HIP_TRY(c, hipStreamSynchronize(ctxs[i]->stream));
+    }
+    // ---- nothing below fails
+    for (size_t i = 0; i < ctxs.size(); i++) {
+        (void)hipSetDevice(ctxs[i]->device);
+        ctxs[i]->world_store.d_pool = std::move(made[i]);
+        ctxs[i]->world_store.pool_stride = stride;
+    }
+    (void)hipSetDevice(c->device);
+    st.slot_of.swap(slot_of); st.chunk_in.swap(chunk_in);
+    st.pool_cap = max_chunks; st.pool_used = used;
+    return YCGE_OK;
+}
+
+int world_store_edit_slots(ycge_ctx *c, int32_t *capacity_out, int32_t *used_out)
+{
+    const int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    const WorldStore &st = c->world_store;
+    if (capacity_out) *capacity_out = st.held ? st.pool_cap : 0;
+    if (used_out) *used_out = st.held ? st.pool_used : 0;
+    return YCGE_OK;
+}
+
+// ycge_world_store_revert_chunks: host work alone - a chunk without a slot is the generated chunk again to every reader
+int world_store_revert_chunks(ycge_ctx *c, const int32_t *keys, int32_t n)
+{
+    static const char *const fn = "ycge_world_store_revert_chunks";
+    const int rc = need_root(c);
+    if (rc != YCGE_OK) return rc;
+    if (n < 0 || (n > 0 && !keys)) return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad key array (n = %d)", fn, n);
+    WorldStore &st = c->world_store;
+    if (!st.held) return c->fail(YCGE_ERR_INVALID_ARG, "%s", kNoStore);
+    const WsShape &W = st.shape;
+    for (int k = 0; k < n; k++) {
+        const int32_t cx = keys[3 * k], cy = keys[3 * k + 1], cz = keys[3 * k + 2];
+        if (cx < 0 || cy < 0 || cz < 0 || cx >= W.ncx || cy >= W.ncy || cz >= W.ncz)
+            return c->fail(YCGE_ERR_INVALID_ARG, "%s: key %d: no chunk (%d, %d, %d) in a store of %d x %d x %d chunks", fn, k, cx, cy, cz, W.ncx, W.ncy, W.ncz);
+    }
+    if (!st.pool_cap) return YCGE_OK;
+    for (int k = 0; k < n; k++) {
+        const size_t ci = chunk_of(W, keys[3 * k], keys[3 * k + 1], keys[3 * k + 2]);
+        const int32_t slot = st.slot_of[ci];
+        if (slot < 0) continue;
+        st.slot_of[ci] = -1; st.chunk_in[(size_t)slot] = -1; st.pool_used--;
+        st.occupied[ci] = st.gen_occupied[ci];
+    }
     return YCGE_OK;
 }
 

@@ -31,7 +31,7 @@ struct GeneratedCells : CellSource {
     int fill_chunks(ycge_ctx *root, ycge_ctx *x, const std::vector<int> &ks, uint8_t *d_head, const std::vector<int32_t *> &d_cells, bool solid = true)
     {
         const size_t m = ks.size(), off_any = align_up(m * sizeof(WgChunk), 256);
-        std::vector<uint8_t> head(head_bytes(m), 0);
+        std::vector<uint8_t> head(GeneratedCells::head_bytes(m), 0);          // (its own part alone: a derived source may keep records of its own behind it)
         for (size_t j = 0; j < m; j++) { const auto &key = keys[(size_t)ks[j]]; ((WgChunk *)head.data())[j] = WgChunk{key[0], key[1], key[2], col[(size_t)ks[j]], d_cells[j]}; }
         HIP_TRY(root, hipMemcpy(d_head, head.data(), head.size(), hipMemcpyHostToDevice));
         const auto t0 = std::chrono::steady_clock::now();

@@ -358,6 +358,22 @@ class RaytraceRenderer:
         self.stream_call_s["edit_world"] = time.perf_counter() - t0
         self._check(rc)
 
+    def ReserveWorldEdits(self, max_chunks: int) -> None:
+        """ycge_world_store_reserve_edits: a pool of max_chunks materialised chunks (chunk_size^3 * 8 bytes each, on every device) beside a
+        fields store, so EditWorldCells works on it: every chunk an op touches takes a slot until RevertWorldChunks gives it back."""
+        self._check(self.L.ycge_world_store_reserve_edits(self.ctx, int(max_chunks)))
+
+    def WorldEditSlots(self):
+        """ycge_world_store_edit_slots -> (slots of the pool, slots that hold a chunk); (0, 0) without a pool"""
+        cap, used = C.c_int32(-1), C.c_int32(-1)
+        self._check(self.L.ycge_world_store_edit_slots(self.ctx, C.byref(cap), C.byref(used)))
+        return cap.value, used.value
+
+    def RevertWorldChunks(self, keys) -> None:
+        """ycge_world_store_revert_chunks: these chunks (cx, cy, cz) give their slots back and are the generated chunks again"""
+        k = np.ascontiguousarray(np.asarray(keys, np.int32).reshape(-1, 3))
+        self._check(self.L.ycge_world_store_revert_chunks(self.ctx, k.ctypes.data_as(C.POINTER(C.c_int32)) if len(k) else None, len(k)))
+
     def ReleaseWorld(self) -> None:
         self._check(self.L.ycge_world_store_release(self.ctx))
 
@@ -378,7 +394,15 @@ class RaytraceRenderer:
         fn.restype, fn.argtypes = abi.WORLD_STORE_HOOK_PROTOTYPES["ycge_debug_world_store_stats"]
         out = (C.c_int64 * 8)()
         self._check(fn(self.ctx, out))
-        return dict(zip(abi.WORLD_STORE_STATS, (int(v) for v in out)))
+        st = dict(zip(abi.WORLD_STORE_STATS, (int(v) for v in out)))
+        # the pool of materialised chunks beside a fields store: its slots, those in use, its bytes on one device (not part of store_bytes)
+        st["edit_slots"], st["edit_slots_used"] = self.WorldEditSlots()
+        st["edit_pool_bytes"] = 0
+        if st["edit_slots"]:
+            S = C.c_int32(0)
+            self._check(self.L.ycge_world_store_info(self.ctx, None, C.byref(S), None, 0))
+            st["edit_pool_bytes"] = st["edit_slots"] * S.value ** 3 * 8
+        return st
 
     # ---------------------------------------------------------------- OBJ meshes from file bytes (MeshLoader.FromObj on the device)
     def ParseObj(self, data) -> abi.ObjInfo:

@@ -92,11 +92,14 @@ def save_resident(renderer, path, slab_planes: Optional[int] = None) -> Tuple[in
     return nx, ny, nz
 
 
-def pregen_resident(renderer, world, chunks_x: int, chunks_z: int, path=None, origin=(0, 0), form="fields") -> Tuple[int, int, int]:
+def pregen_resident(renderer, world, chunks_x: int, chunks_z: int, path=None, origin=(0, 0), form="fields", edit_chunks: Optional[int] = None) -> Tuple[int, int, int]:
     """pregen_world's counterpart on the device: GenerateAndSaveWorld (WorldManager.cs:510-631) as RaytraceRenderer.GenerateWorldStore - the
     window becomes the renderer's resident world, ready for stream_resident / load_all_resident - written as a VG01 file slab by slab
-    (save_resident) when `path` is given.  No array of the world is made on the host.  Returns (nx, ny, nz)."""
+    (save_resident) when `path` is given.  No array of the world is made on the host.  `edit_chunks`: a fields store is given a pool of
+    that many materialised chunks (RaytraceRenderer.ReserveWorldEdits), so edit_resident works on it.  Returns (nx, ny, nz)."""
     dims = renderer.GenerateWorldStore(world, chunks_x, chunks_z, origin=origin, form=form)
+    if edit_chunks is not None:
+        renderer.ReserveWorldEdits(edit_chunks)
     if path is not None:
         save_resident(renderer, path)
     return dims
