@@ -468,6 +468,9 @@ public partial class RaytraceEntity
         private HipSceneQuery queries;
         /// <summary>Scene.Hit / Scene.Occluded on the device scene of this wrapper (VolumeScene's camera physics; INTEGRATION.md section 6).</summary>
         internal HipSceneQuery SceneQueries => queries ??= new HipSceneQuery(() => ctx);
+        /// <summary>VolumeScene's camera physics on the device scene (HipVolumeCamera): one ycge_volume_camera_tick a tick instead of a query a ray.</summary>
+        internal HipVolumeCamera NewVolumeCamera(Vec3 cameraPos, float worldHeight, float waterLevel, float voxelSizeY, bool autoPlaced)
+            => new HipVolumeCamera(() => ctx, cameraPos, worldHeight, waterLevel, voxelSizeY, autoPlaced);
 
         /// <summary>Forces the next frame to upload the scene again (for a host that edits a scene in ways the signature cannot see).</summary>
         public void Invalidate() { forceUpload = true; }

@@ -182,6 +182,36 @@ namespace ConsoleGame.RayTracing.Native
         public int MatId, MetaId;
     }
 
+    // ycge_camera_body, 40 bytes: what VolumeScene keeps between ticks (passed by address only, as above)
+    public unsafe struct YCameraBody
+    {
+        public fixed float Pos[3];
+        public float VerticalVelocity, ShiftHoldTimer;
+        public fixed float RepelVel[3];
+        public int AutoPlaced, IsGrounded;
+    }
+
+    // ycge_camera_world, 12 bytes: WorldConfig.WorldHeight, WaterLevel, VoxelSize.Y
+    public struct YCameraWorld
+    {
+        public float WorldHeight, WaterLevel, VoxelSizeY;
+    }
+
+    // ycge_camera_move, 16 bytes: one HandleInput call's effect on the body (Kind: Ycge.CameraMove*; A, B: dx, dz or dy)
+    public struct YCameraMove
+    {
+        public int Kind, Shift;
+        public float A, B;
+    }
+
+    // ycge_camera_tick_info, 48 bytes (an out parameter only, as above)
+    public struct YCameraTickInfo
+    {
+        public uint RaysCommitted, RaysWalked, Windows;
+        public uint MicroSteps, BlockedSteps, Slides, PushOuts, EmbeddedResolutions, GroundSnaps, AutoPlacements, FailSafes;
+        public uint Reserved;
+    }
+
     // ycge_obj_ground_info, 64 bytes (an out parameter only, as above)
     public struct YObjGroundInfo
     {
@@ -222,6 +252,8 @@ namespace ConsoleGame.RayTracing.Native
         public const int AbiVersion = 10;
         public const int MaxDevices = 8;
         public const int WorldStoreFields = 0;          // YCGE_WORLD_STORE_FIELDS: the window's 2-D fields stay resident
+        public const int CameraMoveHorizontal = 0, CameraMoveVertical = 1, CameraMoveJump = 2, CameraMoveShift = 3;   // YCGE_CAMERA_MOVE_*
+        public const int CameraMaxMoves = 32;           // YCGE_CAMERA_MAX_MOVES
         public const int WorldStoreCells = 1;           // YCGE_WORLD_STORE_CELLS: the ordinary cell store, written on the device
         private const string Lib = "ycge_hip";       // libycge_hip.so
 
@@ -340,6 +372,9 @@ namespace ConsoleGame.RayTracing.Native
         // scene queries (ABI 10): Scene.Hit / Scene.Occluded for a batch of rays, beside a frame in flight (HipSceneQuery.cs)
         [DllImport(Lib)] public static extern int ycge_scene_hit(IntPtr ctx, float[] rays, int n, float[] hits, int[] ids);
         [DllImport(Lib)] public static extern int ycge_scene_occluded(IntPtr ctx, float[] rays, int n, byte[] occluded);
+        // VolumeScene's camera physics, one launch a tick (found by symbol lookup, ABI stays 10); HipVolumeCamera.cs
+        [DllImport(Lib)] public static extern int ycge_volume_camera_tick(IntPtr ctx, YCameraBody* body, YCameraWorld* world, YCameraMove* moves, int nMoves,
+                                                                          float deltaTimeMs, int runUpdate, YCameraTickInfo* info);
         [DllImport(Lib)] public static extern int ycge_read_buffer(IntPtr ctx, int which, IntPtr dst, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_set_frame_counter(IntPtr ctx, long frameCounter);
         [DllImport(Lib)] public static extern int ycge_read_timed_steps(IntPtr ctx, out ulong laneSteps);

@@ -1028,6 +1028,64 @@ int ycge_scene_hit(ycge_ctx *ctx, const float *rays, int32_t n, float *hits, int
 /* Scene.Occluded / the boolean of Scene.Hit: occluded[i] = 1 when Scene.Hit(ray i, tmin, tmax) would return true, else 0. */
 int ycge_scene_occluded(ycge_ctx *ctx, const float *rays, int32_t n, uint8_t *occluded);
 
+/* --- VolumeScene's camera physics as one call a tick (Scenes/VolumeScenes.cs:51-159 Update, :165-530 HandleInput's moves and the helpers;
+ * kernel k_camera_tick in csrc/ycge_camera.hip, the stepper csrc/ycge_camera_physics.h).  Added after ABI 10 without changing it:
+ * YCGE_ABI_VERSION stays 10, no existing struct changes; a host detects the export by symbol lookup.
+ * The reference's Update and HandleInput are a serial chain of Scene.Hit calls, most of which depend on the one before; through
+ * ycge_scene_hit every one of them is a launch, three copies and a stream synchronise.  Here the chain's control runs on the device: one
+ * launch, one small read-back and one synchronise a tick, and the body that comes back is the reference's, bit for bit.
+ *   body   what VolumeScene keeps between ticks: CameraPos, verticalVelocity, shiftHoldTimer, repelVel, autoPlaced, isGrounded (in, out).
+ *   world  WorldConfig's WorldHeight, WaterLevel and VoxelSize.Y.  EyeHeight ... RepelDamping (:20-39) are the library's.
+ *   moves  one HandleInput call's effect on the body each, in the order the host received them, applied before the update:
+ *            YCGE_CAMERA_MOVE_HORIZONTAL  AttemptMoveHorizontal(new Vec3(a, 0, b)): a, b = x and z of forwardXZ * (moveSpeed * dt) (:198-201)
+ *            YCGE_CAMERA_MOVE_VERTICAL    AttemptMoveVertical(a), a widened to double (:204-205)
+ *            YCGE_CAMERA_MOVE_JUMP        :208-212 - taken only when the body is grounded and `shift` is 0
+ *            YCGE_CAMERA_MOVE_SHIFT       shiftHoldTimer = 0.15f (:177); a key with Shift held is this move, then the key's own
+ *   then, when run_update != 0, Update's physics with delta_time_ms: ResolveIfEmbedded, the one-time auto placement with its early
+ *   return, the shift timer, gravity and the two ground fans, ApplyWallRepulsion(dt), the fail-safe at y < -10.  LoadChunksAround and
+ *   base.Update stay the host's.
+ *   info   (may be NULL) what happened: rays_committed - the Scene.Hit calls of the serial order; rays_walked >= rays_committed - the rays the
+ *          device walked, a window of consecutive rays side by side, those behind a ray that changed the state dropped and asked again;
+ *          windows; micro-steps of the moves, micro-steps that ended a move blocked, slides, push-outs, embedded resolutions, ground
+ *          snaps, auto placements, fail-safes.
+ * The scene is the one of the last successful upload, update_objects, attach or edit, under ycge_scene_hit's contract: the tick runs on the
+ * query stream, waits for the device work of the last scene change and NOT for frames in flight, and changes nothing a frame reads.
+ * YCGE_ERR_NO_SCENE before the first upload.  Refused before any device work with YCGE_ERR_INVALID_ARG, *body untouched, the message
+ * naming the move: a peer context, NULL body or world, n_moves outside 0..YCGE_CAMERA_MAX_MOVES, NULL moves with n_moves > 0, a
+ * non-finite field, a move longer than YCGE_CAMERA_MAX_MOVE_LENGTH, an unknown kind.
+ * Bounded: the reference's AttemptMoveHorizontal adds a slide's residual back to what remains (:275) and has no bound; here a move takes at
+ * most YCGE_CAMERA_MAX_MICRO_STEPS micro-steps.  A tick that reaches that cap, or whose position stops being finite, returns
+ * YCGE_ERR_UNSUPPORTED with *body and *info unchanged; the message says which cap and which move.  *body and *info are written on success
+ * only.  YCGE_CAMERA_HOST=1 in the environment (read at every call) runs the same stepper on the host, a window a ycge_scene_hit batch. */
+#define YCGE_CAMERA_MOVE_HORIZONTAL 0
+#define YCGE_CAMERA_MOVE_VERTICAL 1
+#define YCGE_CAMERA_MOVE_JUMP 2
+#define YCGE_CAMERA_MOVE_SHIFT 3
+#define YCGE_CAMERA_MAX_MOVES 32
+#define YCGE_CAMERA_MAX_MOVE_LENGTH 64.0f
+#define YCGE_CAMERA_MAX_MICRO_STEPS 1024
+typedef struct ycge_camera_body {    /* 40 bytes */
+    float pos[3];
+    float vertical_velocity, shift_hold_timer;
+    float repel_vel[3];
+    int32_t auto_placed, is_grounded;
+} ycge_camera_body;
+typedef struct ycge_camera_world {   /* 12 bytes */
+    float world_height, water_level, voxel_size_y;
+} ycge_camera_world;
+typedef struct ycge_camera_move {    /* 16 bytes */
+    int32_t kind;                    /* YCGE_CAMERA_MOVE_* */
+    int32_t shift;                   /* JUMP: the key came with Shift held */
+    float a, b;                      /* HORIZONTAL: dx, dz; VERTICAL: dy */
+} ycge_camera_move;
+typedef struct ycge_camera_tick_info {   /* 12 uint32, 48 bytes */
+    uint32_t rays_committed, rays_walked, windows;
+    uint32_t micro_steps, blocked_steps, slides, push_outs, embedded_resolutions, ground_snaps, auto_placements, fail_safes;
+    uint32_t reserved;
+} ycge_camera_tick_info;
+int ycge_volume_camera_tick(ycge_ctx *ctx, ycge_camera_body *body /* in, out */, const ycge_camera_world *world, const ycge_camera_move *moves,
+                            int32_t n_moves, float delta_time_ms, int32_t run_update, ycge_camera_tick_info *info /* or NULL */);
+
 /* tests only */
 int ycge_read_buffer(ycge_ctx *ctx, int32_t which /* ycge_buffer */, void *dst, size_t bytes);
 int ycge_set_frame_counter(ycge_ctx *ctx, int64_t frame_counter);

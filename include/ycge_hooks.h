@@ -124,6 +124,15 @@ int ycge_test_taa(ycge_ctx *c, int32_t form, int32_t reset, int32_t w, int32_t h
                   int32_t taa_clamp_radius, float taa_luminance_pad, float *hist_out, float *normal_out, float *depth_out, uint8_t *sky_out,
                   float *slab_out);
 
+/* ---- the camera physics' stepper (csrc/ycge_camera_physics.h) on the host over a caller's Scene.Hit, no context and no device: the
+ * arguments, refusals, caps and results of ycge_volume_camera_tick.  hit answers one ray {o xyz, d xyz, tmin, tmax} (d as handed to
+ * new Ray: the callback normalises) with a non-zero return and rec = {t, p xyz, n xyz} on a hit, 0 on a miss.  windowed = 0: the
+ * reference's serial order, a ray at a time; != 0: the device's window-and-commit order, each window's rays asked before any is folded */
+typedef int (*ycge_camera_hit_fn)(void *user, const float ray[8], float rec[7]);
+int ycge_test_camera_tick_host(ycge_camera_body *body, const ycge_camera_world *world, const ycge_camera_move *moves, int32_t n_moves,
+                               float delta_time_ms, int32_t run_update, ycge_camera_tick_info *info, ycge_camera_hit_fn hit, void *user,
+                               int32_t windowed, char *msg, size_t msg_bytes);
+
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */
 int ycge_debug_device_bvh(const float *bounds, const float *centroids, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *result_out, void *build_out);   /* k_scene_bvh_build alone */

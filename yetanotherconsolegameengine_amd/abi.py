@@ -111,6 +111,38 @@ VOXEL_EDIT_MAX_OPS = 1 << 20
 VOXEL_EDIT_INFO = ("cells_changed", "bricks_written", "records_changed", "objects_installed")
 
 
+class CameraBody(C.Structure):
+    """ycge_camera_body (40 bytes): what VolumeScene keeps between ticks - CameraPos, verticalVelocity, shiftHoldTimer, repelVel, autoPlaced,
+    isGrounded (ycge_volume_camera_tick)."""
+    _fields_ = [("pos", C.c_float * 3), ("vertical_velocity", C.c_float), ("shift_hold_timer", C.c_float), ("repel_vel", C.c_float * 3),
+                ("auto_placed", C.c_int32), ("is_grounded", C.c_int32)]
+
+
+class CameraWorld(C.Structure):
+    """ycge_camera_world (12 bytes): WorldConfig's WorldHeight, WaterLevel and VoxelSize.Y."""
+    _fields_ = [("world_height", C.c_float), ("water_level", C.c_float), ("voxel_size_y", C.c_float)]
+
+
+class CameraMove(C.Structure):
+    """ycge_camera_move (16 bytes): one HandleInput call's effect on the body.  HORIZONTAL: a, b = dx, dz; VERTICAL: a = dy; JUMP: shift = the key
+    came with Shift held; SHIFT: the fly timer is refreshed."""
+    _fields_ = [("kind", C.c_int32), ("shift", C.c_int32), ("a", C.c_float), ("b", C.c_float)]
+
+
+class CameraTickInfo(C.Structure):
+    """ycge_camera_tick_info (12 uint32)"""
+    _fields_ = [(n, C.c_uint32) for n in ("rays_committed", "rays_walked", "windows", "micro_steps", "blocked_steps", "slides", "push_outs",
+                                          "embedded_resolutions", "ground_snaps", "auto_placements", "fail_safes", "reserved")]
+
+
+CAMERA_MOVE_HORIZONTAL, CAMERA_MOVE_VERTICAL, CAMERA_MOVE_JUMP, CAMERA_MOVE_SHIFT = 0, 1, 2, 3
+CAMERA_MAX_MOVES = 32
+CAMERA_MAX_MOVE_LENGTH = 64.0
+CAMERA_MAX_MICRO_STEPS = 1024
+# int hit(void *user, const float ray[8], float rec[7]) of ycge_test_camera_tick_host (include/ycge_hooks.h)
+CAMERA_HIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float))
+
+
 class World(C.Structure):
     """ycge_world: WorldConfig as a chunk depends on it (ycge_worldgen_chunk_cells / ycge_scene_generate_grids)."""
     _fields_ = [("chunk_size", C.c_int32), ("chunks_y", C.c_int32), ("world_seed", C.c_int32), ("world_min", Vec3), ("voxel_size", Vec3)]
@@ -286,6 +318,8 @@ _PROTOTYPES = {
     "ycge_unpack_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ycge_scene_hit": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "ycge_scene_occluded": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_uint8)]),
+    # the camera tick (body / world / moves / info: CameraBody, CameraWorld, CameraMove[n], CameraTickInfo by address)
+    "ycge_volume_camera_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
     "ycge_render_frame_chexels": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                             C.POINTER(FrameStats)]),
     "ycge_render_frame_async_chexels": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
@@ -351,6 +385,11 @@ HOOK_PROTOTYPES = {
     "ycge_debug_grid_pool_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ycge_debug_peer_context": (C.c_void_p, [C.c_void_p, C.c_int32]),
     "ycge_debug_live_resources": (C.c_int, [C.POINTER(C.c_int64)]),
+}
+# the camera physics' stepper on the host over a caller's Scene.Hit (csrc/ycge_camera.cpp), bound where it is used (VolumeCamera.tick_host)
+CAMERA_HOOK_PROTOTYPES = {
+    "ycge_test_camera_tick_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, CAMERA_HIT_FN, C.c_void_p,
+                                             C.c_int32, C.c_char_p, C.c_size_t]),
 }
 # test / profiling hook of chunk generation (csrc/ycge_worldgen_scene.cpp), bound where it is used (RaytraceRenderer.worldgen_stats)
 WORLDGEN_HOOK_PROTOTYPES = {

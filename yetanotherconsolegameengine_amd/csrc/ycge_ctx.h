@@ -154,6 +154,8 @@ int ycge_launch_grid_edit(uint8_t *arena, const void *records, uint32_t n_record
 int ycge_launch_grid_solid(const uint8_t *arena, const void *descs, int n_grids, void *results, uint32_t n_workgroups, hipStream_t stream);
 int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, float *hits, int32_t *ids, uint8_t *occluded, uint32_t *first_bad,
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
+// the camera tick (k_camera_tick, ycge_camera.hip): one wavefront; in / out: ycge_cam::TickIn / TickOut (ycge_camera_physics.h), spill: 64 columns
+int ycge_launch_camera_tick(const ycge::SceneDev *S, const void *in, void *out, void *spill, int has_grid, hipStream_t stream);
 }
 
 using namespace ycge;
@@ -426,6 +428,10 @@ struct QueryState {
     DevBuf<uint64_t> spill;            // [spill levels][resident lanes]
     uint32_t lanes[4] = {0, 0, 0, 0};  // resident lanes of k_query<has_grid, occluded>
     PinnedBuf in_stage, out_stage;
+    // ycge_volume_camera_tick (ycge_camera.cpp): k_camera_tick's {input, result} records, its 64 spill columns, their staging
+    DevBuf<uint8_t> cam_dev;
+    DevBuf<uint64_t> cam_spill;
+    PinnedBuf cam_stage;
 };
 // one ANSI stream call (ycge_ansi.cpp): the colour form, the console, the viewport, the default colours, the clear-screen prefix; delta: a
 // _delta call, which alone reads gap, tolerance (24-bit colour only) and keyframe
@@ -938,6 +944,7 @@ inline double us_since(std::chrono::steady_clock::time_point t0) { return std::c
 // the calling thread's current device goes back to the root's on every way out (a failed step on a peer's device included)
 struct DeviceGuard { int device; explicit DeviceGuard(int d) : device(d) {} ~DeviceGuard() { (void)hipSetDevice(device); } };
 void release_resident(ycge_ctx *c);
+int query_hit_batch(ycge_ctx *c, const char *fn, const float *rays, int32_t n, float *hits, int32_t *ids);   // ycge_query.cpp: ycge_scene_hit's batch under another export's name
 int alloc_tile_buffers(ycge_ctx *c);          // ycge_host.cpp: queue segments, hit records, spill columns (for c->spill_levels) and schedules of the owned tiles
 void snapshot_frame(ycge_ctx *c, FrameState &fs);
 void schedule_policy(const ycge_ctx *c, uint32_t &policy, uint32_t &split_top, int resident_ring = 0, bool batched = false);

@@ -79,6 +79,9 @@ int run_query(ycge_ctx *c, const char *fn, const float *rays, int32_t n, float *
 }
 
 } // namespace
+
+int query_hit_batch(ycge_ctx *c, const char *fn, const float *rays, int32_t n, float *hits, int32_t *ids) { return run_query(c, fn, rays, n, hits, ids, nullptr); }
+
 } // namespace ycge_host
 
 // =========================================================================== C-ABI

@@ -560,6 +560,20 @@ class RaytraceRenderer:
         self._check(self.L.ycge_scene_occluded(self.ctx, rays.ctypes.data_as(C.POINTER(C.c_float)), n, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out.astype(bool)
 
+    # ---------------------------------------------------------------- the camera tick (ycge_volume_camera_tick)
+    def CameraTick(self, body: "abi.CameraBody", world: "abi.CameraWorld", moves, dt_ms: float, run_update: bool = True) -> dict:
+        """VolumeScene.HandleInput's moves, then VolumeScene.Update's physics (Scenes/VolumeScenes.cs:51-159, :165-530), in one launch on the
+        device scene: `body` is updated in place on success and the counters of ycge_camera_tick_info come back.  moves: abi.CameraMove
+        records (or (kind, shift, a, b) tuples) in the order received.  A refusal or a reached cap raises YcgeError and leaves body as it
+        was.  Runs beside frames in flight, as Hit does."""
+        recs = (abi.CameraMove * max(1, len(moves)))()
+        for i, m in enumerate(moves):
+            recs[i] = m if isinstance(m, abi.CameraMove) else abi.CameraMove(int(m[0]), int(m[1]), float(m[2]), float(m[3]))
+        info = abi.CameraTickInfo()
+        self._check(self.L.ycge_volume_camera_tick(self.ctx, C.byref(body), C.byref(world), recs if len(moves) else None, len(moves), float(dt_ms),
+                                                   1 if run_update else 0, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in abi.CameraTickInfo._fields_ if n != "reserved"}
+
     def scene_bvh_stats(self) -> dict:
         """How ycge_scene_update_objects built the scene BVH so far: on the device (csrc/ycge_bvh_build.hip), on the host after the
         kernel declined, on the host outright; microseconds of the last build + install; how often the current tree took the
@@ -1156,3 +1170,65 @@ class VideoRenderer:
         s = np.zeros((fb_height, fb_width, 2, 3), np.float32)
         self._r._check(fn(self.ctx, f.ctypes.data, w, h, bpp, int(fb_width), int(fb_height), int(superSample), s.ctypes.data))
         return s
+
+
+class VolumeCamera:
+    """The player of a voxel world as the host keeps it: the body VolumeScene carries between ticks, WorldConfig's three values, and the
+    moves of the key events since the last tick.  forward / strafe / rise / jump / shift do HandleInput's arithmetic (Scenes/VolumeScenes.cs:
+    169-205: moveSpeed = 6, x ShiftSpeedMult = 30 with Shift held, which also refreshes the fly timer; forwardXZ = (sin yaw, 0, -cos yaw),
+    rightXZ = (cos yaw, 0, sin yaw), each times moveSpeed * dt in binary32) and queue a move; tick() hands them to RaytraceRenderer.CameraTick
+    with Update's delta time and clears the list."""
+
+    MoveSpeed = np.float32(6.0)
+    ShiftSpeedMult = np.float32(30.0)
+
+    def __init__(self, pos, world_height: float, water_level: float, voxel_size_y: float = 1.0, auto_placed: bool = False):
+        self.body = abi.CameraBody()
+        self.body.pos[:] = [float(np.float32(v)) for v in pos]
+        self.body.auto_placed = 1 if auto_placed else 0
+        self.world = abi.CameraWorld(float(world_height), float(water_level), float(voxel_size_y))
+        self.moves: list = []
+
+    def _speed(self, dt: float, shift_down: bool) -> np.float32:
+        dt = max(np.float32(dt), np.float32(0.0))                                   # :167
+        speed = self.MoveSpeed
+        if shift_down:
+            speed = speed * self.ShiftSpeedMult                                        # :175
+            self.shift()
+        return speed * dt
+
+    def shift(self):
+        self.moves.append(abi.CameraMove(abi.CAMERA_MOVE_SHIFT, 0, 0.0, 0.0))
+
+    def forward(self, yaw: float, dt: float, sign: float = 1.0, shift_down: bool = False):
+        """W (sign = 1) / S (sign = -1), :198-199"""
+        k = self._speed(dt, shift_down)
+        sy, cy = np.float32(np.sin(np.float32(yaw))), np.float32(np.cos(np.float32(yaw)))
+        s = np.float32(sign)
+        self.moves.append(abi.CameraMove(abi.CAMERA_MOVE_HORIZONTAL, 0, float((s * sy) * k), float((s * -cy) * k)))
+
+    def strafe(self, yaw: float, dt: float, sign: float = 1.0, shift_down: bool = False):
+        """D (sign = 1) / A (sign = -1), :200-201"""
+        k = self._speed(dt, shift_down)
+        sy, cy = np.float32(np.sin(np.float32(yaw))), np.float32(np.cos(np.float32(yaw)))
+        s = np.float32(sign)
+        self.moves.append(abi.CameraMove(abi.CAMERA_MOVE_HORIZONTAL, 0, float((s * cy) * k), float((s * sy) * k)))
+
+    def rise(self, dt: float, sign: float = 1.0, shift_down: bool = False):
+        """E (sign = 1) / Q (sign = -1), :204-205"""
+        k = self._speed(dt, shift_down)
+        self.moves.append(abi.CameraMove(abi.CAMERA_MOVE_VERTICAL, 0, float(np.float32(sign) * k), 0.0))
+
+    def jump(self, shift_down: bool = False):
+        """Space, :208-212"""
+        if shift_down:
+            self.shift()
+        self.moves.append(abi.CameraMove(abi.CAMERA_MOVE_JUMP, 1 if shift_down else 0, 0.0, 0.0))
+
+    def tick(self, renderer: RaytraceRenderer, dt_ms: float, run_update: bool = True) -> dict:
+        moves, self.moves = self.moves, []
+        return renderer.CameraTick(self.body, self.world, moves, dt_ms, run_update)
+
+    @property
+    def pos(self):
+        return tuple(self.body.pos)
