@@ -471,6 +471,9 @@ public partial class RaytraceEntity
         /// <summary>VolumeScene's camera physics on the device scene (HipVolumeCamera): one ycge_volume_camera_tick a tick instead of a query a ray.</summary>
         internal HipVolumeCamera NewVolumeCamera(Vec3 cameraPos, float worldHeight, float waterLevel, float voxelSizeY, bool autoPlaced)
             => new HipVolumeCamera(() => ctx, cameraPos, worldHeight, waterLevel, voxelSizeY, autoPlaced);
+        /// <summary>The other bodies of a voxel world - mobs, items, projectiles, replicated players - on the device scene (HipVolumeBodies): one ycge_volume_bodies_tick a tick for all of them.</summary>
+        internal HipVolumeBodies NewVolumeBodies(float worldHeight, float waterLevel, float voxelSizeY)
+            => new HipVolumeBodies(() => ctx, worldHeight, waterLevel, voxelSizeY);
 
         /// <summary>Forces the next frame to upload the scene again (for a host that edits a scene in ways the signature cannot see).</summary>
         public void Invalidate() { forceUpload = true; }

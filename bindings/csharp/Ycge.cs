@@ -212,6 +212,19 @@ namespace ConsoleGame.RayTracing.Native
         public uint Reserved;
     }
 
+    // ycge_body_shape, 24 bytes: how big a body is and how it jumps and falls (VolumeScenes.cs:20-39 as data; ycge_volume_bodies_tick)
+    public struct YBodyShape
+    {
+        public float EyeHeight, CollisionRadius, ProbeRadius, GroundClearance, JumpSpeed, GravityAccel;
+        public static YBodyShape Default => new YBodyShape { EyeHeight = 1.7f, CollisionRadius = 0.65f, ProbeRadius = 0.35f, GroundClearance = 0.10f, JumpSpeed = 4.8f, GravityAccel = 9.81f };   // YCGE_BODY_SHAPE_DEFAULT
+    }
+
+    // ycge_body_result, 8 bytes: Status 0 committed, 1 / 2 a horizontal / vertical move reached the micro-step cap, 3 the position stopped being finite
+    public struct YBodyResult
+    {
+        public int Status, BadMove;
+    }
+
     // ycge_obj_ground_info, 64 bytes (an out parameter only, as above)
     public struct YObjGroundInfo
     {
@@ -254,6 +267,7 @@ namespace ConsoleGame.RayTracing.Native
         public const int WorldStoreFields = 0;          // YCGE_WORLD_STORE_FIELDS: the window's 2-D fields stay resident
         public const int CameraMoveHorizontal = 0, CameraMoveVertical = 1, CameraMoveJump = 2, CameraMoveShift = 3;   // YCGE_CAMERA_MOVE_*
         public const int CameraMaxMoves = 32;           // YCGE_CAMERA_MAX_MOVES
+        public const int BodiesMax = 4096;              // YCGE_BODIES_MAX
         public const int WorldStoreCells = 1;           // YCGE_WORLD_STORE_CELLS: the ordinary cell store, written on the device
         private const string Lib = "ycge_hip";       // libycge_hip.so
 
@@ -375,6 +389,9 @@ namespace ConsoleGame.RayTracing.Native
         // VolumeScene's camera physics, one launch a tick (found by symbol lookup, ABI stays 10); HipVolumeCamera.cs
         [DllImport(Lib)] public static extern int ycge_volume_camera_tick(IntPtr ctx, YCameraBody* body, YCameraWorld* world, YCameraMove* moves, int nMoves,
                                                                           float deltaTimeMs, int runUpdate, YCameraTickInfo* info);
+        // many bodies a tick in one launch, each with its own shape (found by symbol lookup, ABI stays 10); HipVolumeBodies.cs
+        [DllImport(Lib)] public static extern int ycge_volume_bodies_tick(IntPtr ctx, YCameraBody* bodies, YBodyShape* shapes, int n, YCameraWorld* world, YCameraMove* moves,
+                                                                          int* moveFirst, float deltaTimeMs, int runUpdate, YBodyResult* results, YCameraTickInfo* info);
         [DllImport(Lib)] public static extern int ycge_read_buffer(IntPtr ctx, int which, IntPtr dst, UIntPtr bytes);
         [DllImport(Lib)] public static extern int ycge_set_frame_counter(IntPtr ctx, long frameCounter);
         [DllImport(Lib)] public static extern int ycge_read_timed_steps(IntPtr ctx, out ulong laneSteps);

@@ -1086,6 +1086,52 @@ typedef struct ycge_camera_tick_info {   /* 12 uint32, 48 bytes */
 int ycge_volume_camera_tick(ycge_ctx *ctx, ycge_camera_body *body /* in, out */, const ycge_camera_world *world, const ycge_camera_move *moves,
                             int32_t n_moves, float delta_time_ms, int32_t run_update, ycge_camera_tick_info *info /* or NULL */);
 
+/* --- many bodies of the voxel world a tick in one launch, each with its own shape (kernel k_bodies_tick in csrc/ycge_camera.hip, the
+ * same stepper).  Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no existing struct changes; a host detects the
+ * export by symbol lookup.
+ * ycge_volume_camera_tick moves one body of one size: a host that also moves mobs, dropped items, projectiles or the other players of a
+ * replicated scene pays one call, one launch, one read-back and one synchronise per body.  Here n independent bodies are one staged copy
+ * up, one launch of n one-wavefront workgroups, one copy back and one synchronise, and every body comes back as the serial stepper leaves
+ * it alone, bit for bit: body i's outcome is a function of its own inputs and the scene only - bodies do not see each other, the
+ * position in the batch and the other bodies do not matter.
+ *   bodies      n bodies (in, out), as ycge_volume_camera_tick's one.
+ *   shapes      n shapes, or NULL: every body has YCGE_BODY_SHAPE_DEFAULT.  A shape is the reference's `const float` values that say how
+ *               big a body is and how it jumps and falls (Scenes/VolumeScenes.cs:20-39): EyeHeight, CollisionRadius, ProbeRadius,
+ *               GroundClearance, JumpSpeed, GravityAccel, read in the reference's types and order of operations.  MaxProbeHeight,
+ *               LocalProbeDepthMin, LocalProbeStart, ExtraFallMargin, StepUpGuardEpsilon and ShiftHoldGraceSeconds stay the library's.
+ *   moves,      body i applies moves[move_first[i] .. move_first[i + 1]) in order (at most YCGE_CAMERA_MAX_MOVES), then, when
+ *   move_first  run_update != 0, Update's physics with delta_time_ms, exactly as ycge_volume_camera_tick does for one body.  move_first
+ *               has n + 1 entries, starts at 0 and does not decrease.
+ *   results     n records, all filled by a call that ran (it returns YCGE_OK): status 0 - bodies[i] and info[i] are the tick's; status
+ *               1 (a horizontal move reached YCGE_CAMERA_MAX_MICRO_STEPS), 2 (a vertical move did), 3 (the position stopped being
+ *               finite) - bodies[i] and info[i] are left as they were and bad_move is the body's own move index, or -1.  The other bodies
+ *               commit all the same: one body in a corner does not cost the rest their tick.
+ *   info        (may be NULL) n records of ycge_camera_tick_info.
+ * The scene and the stream are ycge_volume_camera_tick's: the query stream, waits for the device work of the last scene change and NOT for
+ * frames in flight, changes nothing a frame reads.  YCGE_ERR_NO_SCENE before the first upload; n = 0 with a scene: YCGE_OK.
+ * Refused on the host before any device work with YCGE_ERR_INVALID_ARG, nothing written (results included), the message naming the body
+ * and, where there is one, the move ("body 7: move 2: longer than ..."): a peer context; n outside 0..YCGE_BODIES_MAX; NULL bodies,
+ * world, results or move_first with n > 0; NULL moves while some body has moves; move_first[0] != 0, a decreasing move_first, more than
+ * YCGE_CAMERA_MAX_MOVES moves for one body; whatever ycge_volume_camera_tick refuses for a body, its moves, the world and the time step;
+ * a shape with a field that is not finite, with eye_height, collision_radius, probe_radius or gravity_accel not positive, with
+ * ground_clearance or jump_speed negative, or with eye_height or collision_radius above YCGE_BODY_SHAPE_MAX_SIZE (the caps on moves and
+ * micro-steps keep their meaning).  A device error fails the call and writes nothing.
+ * YCGE_CAMERA_HOST=1 in the environment (read at every call) runs the same stepper on the host: a round collects the next window of every
+ * body still running into one ycge_scene_hit batch and commits body by body. */
+#define YCGE_BODIES_MAX 4096
+#define YCGE_BODY_SHAPE_MAX_SIZE 64.0f
+typedef struct ycge_body_shape {     /* 24 bytes */
+    float eye_height, collision_radius, probe_radius, ground_clearance, jump_speed, gravity_accel;
+} ycge_body_shape;
+#define YCGE_BODY_SHAPE_DEFAULT {1.7f, 0.65f, 0.35f, 0.10f, 4.8f, 9.81f}
+typedef struct ycge_body_result {    /* 8 bytes */
+    int32_t status;                  /* 0 committed; 1 a horizontal move reached YCGE_CAMERA_MAX_MICRO_STEPS; 2 a vertical move did; 3 the position stopped being finite */
+    int32_t bad_move;                /* status 1..3: the body's own move index, or -1 */
+} ycge_body_result;
+int ycge_volume_bodies_tick(ycge_ctx *ctx, ycge_camera_body *bodies /* n, in, out */, const ycge_body_shape *shapes /* n, or NULL: the reference's */,
+                            int32_t n, const ycge_camera_world *world, const ycge_camera_move *moves, const int32_t *move_first /* n + 1 */,
+                            float delta_time_ms, int32_t run_update, ycge_body_result *results /* n */, ycge_camera_tick_info *info /* n, or NULL */);
+
 /* tests only */
 int ycge_read_buffer(ycge_ctx *ctx, int32_t which /* ycge_buffer */, void *dst, size_t bytes);
 int ycge_set_frame_counter(ycge_ctx *ctx, int64_t frame_counter);

@@ -132,6 +132,12 @@ typedef int (*ycge_camera_hit_fn)(void *user, const float ray[8], float rec[7]);
 int ycge_test_camera_tick_host(ycge_camera_body *body, const ycge_camera_world *world, const ycge_camera_move *moves, int32_t n_moves,
                                float delta_time_ms, int32_t run_update, ycge_camera_tick_info *info, ycge_camera_hit_fn hit, void *user,
                                int32_t windowed, char *msg, size_t msg_bytes);
+/* the same for a batch: the arguments, refusals (the text in msg names the body and the move) and per-body results of ycge_volume_bodies_tick,
+ * body after body over the caller's Scene.Hit; no context and no device */
+int ycge_test_bodies_tick_host(ycge_camera_body *bodies, const ycge_body_shape *shapes, int32_t n, const ycge_camera_world *world,
+                               const ycge_camera_move *moves, const int32_t *move_first, float delta_time_ms, int32_t run_update,
+                               ycge_body_result *results, ycge_camera_tick_info *info, ycge_camera_hit_fn hit, void *user, int32_t windowed,
+                               char *msg, size_t msg_bytes);
 
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */

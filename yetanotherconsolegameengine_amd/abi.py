@@ -139,6 +139,23 @@ CAMERA_MOVE_HORIZONTAL, CAMERA_MOVE_VERTICAL, CAMERA_MOVE_JUMP, CAMERA_MOVE_SHIF
 CAMERA_MAX_MOVES = 32
 CAMERA_MAX_MOVE_LENGTH = 64.0
 CAMERA_MAX_MICRO_STEPS = 1024
+
+
+class BodyShape(C.Structure):
+    """ycge_body_shape (24 bytes): how big a body is and how it jumps and falls - the reference's EyeHeight, CollisionRadius, ProbeRadius,
+    GroundClearance, JumpSpeed, GravityAccel (Scenes/VolumeScenes.cs:20-39) as data (ycge_volume_bodies_tick)."""
+    _fields_ = [(n, C.c_float) for n in ("eye_height", "collision_radius", "probe_radius", "ground_clearance", "jump_speed", "gravity_accel")]
+
+
+class BodyResult(C.Structure):
+    """ycge_body_result (8 bytes): status 0 committed, 1 / 2 a horizontal / vertical move reached CAMERA_MAX_MICRO_STEPS, 3 the position stopped
+    being finite; bad_move the body's own move index, or -1."""
+    _fields_ = [("status", C.c_int32), ("bad_move", C.c_int32)]
+
+
+BODIES_MAX = 4096
+BODY_SHAPE_MAX_SIZE = 64.0
+BODY_SHAPE_DEFAULT = (1.7, 0.65, 0.35, 0.10, 4.8, 9.81)          # YCGE_BODY_SHAPE_DEFAULT: the reference's
 # int hit(void *user, const float ray[8], float rec[7]) of ycge_test_camera_tick_host (include/ycge_hooks.h)
 CAMERA_HIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float))
 
@@ -320,6 +337,10 @@ _PROTOTYPES = {
     "ycge_scene_occluded": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_uint8)]),
     # the camera tick (body / world / moves / info: CameraBody, CameraWorld, CameraMove[n], CameraTickInfo by address)
     "ycge_volume_camera_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
+    # many bodies a tick (bodies / shapes / n / world / moves / move_first / dt / run_update / results / info: CameraBody[n], BodyShape[n] or None,
+    # CameraWorld, CameraMove[], int32[n + 1], BodyResult[n], CameraTickInfo[n] or None, by address)
+    "ycge_volume_bodies_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p,
+                                          C.c_void_p]),
     "ycge_render_frame_chexels": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                             C.POINTER(FrameStats)]),
     "ycge_render_frame_async_chexels": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
@@ -390,6 +411,8 @@ HOOK_PROTOTYPES = {
 CAMERA_HOOK_PROTOTYPES = {
     "ycge_test_camera_tick_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, CAMERA_HIT_FN, C.c_void_p,
                                              C.c_int32, C.c_char_p, C.c_size_t]),
+    "ycge_test_bodies_tick_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
+                                             CAMERA_HIT_FN, C.c_void_p, C.c_int32, C.c_char_p, C.c_size_t]),
 }
 # test / profiling hook of chunk generation (csrc/ycge_worldgen_scene.cpp), bound where it is used (RaytraceRenderer.worldgen_stats)
 WORLDGEN_HOOK_PROTOTYPES = {

@@ -22,10 +22,12 @@
 
 namespace ycge_cam {
 
-// VolumeScenes.cs:20-39
-constexpr float kEyeHeight = 1.7f, kGravityAccel = 9.81f, kMaxProbeHeight = 4096.0f, kGroundClearance = 0.10f, kJumpSpeed = 4.8f;
-constexpr float kLocalProbeDepthMin = 3.0f, kLocalProbeStart = 0.6f, kProbeRadius = 0.35f, kExtraFallMargin = 1.0f, kStepUpGuardEpsilon = 0.05f;
-constexpr float kShiftHoldGraceSeconds = 0.15f, kCollisionRadius = 0.65f;
+// VolumeScenes.cs:20-39.  EyeHeight, CollisionRadius, ProbeRadius, GroundClearance, JumpSpeed and GravityAccel are a body's shape
+// (ycge_body_shape, Tick::s): data, read in the types and the order of operations the reference uses its constants in - widened where
+// the C# widens a const float, so a shape of the reference's values gives the reference's bits.
+constexpr float kMaxProbeHeight = 4096.0f;
+constexpr float kLocalProbeDepthMin = 3.0f, kLocalProbeStart = 0.6f, kExtraFallMargin = 1.0f, kStepUpGuardEpsilon = 0.05f;
+constexpr float kShiftHoldGraceSeconds = 0.15f;
 
 struct Ray { float o[3], d[3], tmin, tmax; };      // d as it is handed to `new Ray(o, d)`: whoever walks it normalises (Ray.cs:8-12)
 struct Hit { int32_t hit; float t, nx, ny, nz; };  // the boolean of Scene.Hit, rec.T, rec.N
@@ -38,6 +40,7 @@ constexpr int kMaxWindow = 32;     // the largest group (a push-out call)
 
 struct Tick {
     ycge_camera_body b;
+    ycge_body_shape s;
     ycge_camera_world w;
     const ycge_camera_move *moves;
     int32_t n_moves, run_update;
@@ -82,7 +85,7 @@ YCGE_HD void set_group(Tick &t, int grp, int n, int next_pc) { t.grp = grp; t.gi
 YCGE_HD void heights(Tick &t)          // double eyeY = CameraPos.Y; double torsoY = CameraPos.Y - (EyeHeight * 0.5);
 {
     t.ey = (double)t.b.pos[1];
-    t.ty = (double)t.b.pos[1] - ((double)kEyeHeight * 0.5);
+    t.ty = (double)t.b.pos[1] - ((double)t.s.eye_height * 0.5);
 }
 YCGE_HD void start_push(Tick &t, int next_pc) { heights(t); set_group(t, G_PUSH, 32, next_pc); }     // ApplyWallRepulsion, :418-440
 YCGE_HD void start_fan(Tick &t, double x, double z, double start_y, double max_distance, int next_pc)   // TrySampleGroundYFan, :478-492
@@ -107,7 +110,7 @@ YCGE_HD void cam_control(Tick &t)
             if (m.kind == YCGE_CAMERA_MOVE_SHIFT) {
                 t.b.shift_hold_timer = kShiftHoldGraceSeconds;                                      // :177
             } else if (m.kind == YCGE_CAMERA_MOVE_JUMP) {
-                if (!m.shift && t.b.is_grounded) { t.b.vertical_velocity = kJumpSpeed; t.b.is_grounded = 0; }    // :208-212
+                if (!m.shift && t.b.is_grounded) { t.b.vertical_velocity = t.s.jump_speed; t.b.is_grounded = 0; }    // :208-212
             } else if (m.kind == YCGE_CAMERA_MOVE_HORIZONTAL) {                                   // AttemptMoveHorizontal(delta), :219-227
                 const float dx = m.a, dz = m.b;
                 t.remaining = sqrt((double)(dx * dx + dz * dz));
@@ -130,7 +133,7 @@ YCGE_HD void cam_control(Tick &t)
             if (!(t.remaining > 1e-6)) { t.pc = PC_MOVE_NEXT; break; }
             if (t.micro >= YCGE_CAMERA_MAX_MICRO_STEPS) { fail(t, ST_CAP_HORIZONTAL); return; }
             t.micro++; t.info.micro_steps++;
-            t.step = dmin(t.remaining, dmax(0.1, (double)kCollisionRadius * 0.35));
+            t.step = dmin(t.remaining, dmax(0.1, (double)t.s.collision_radius * 0.35));
             t.best = t.step; t.had = 0; t.bnx = t.bny = t.bnz = 0.0f;
             heights(t);
             set_group(t, G_CAPS, 6, PC_H_END);
@@ -165,7 +168,7 @@ YCGE_HD void cam_control(Tick &t)
             if (!(t.remaining > 1e-6)) { t.pc = PC_MOVE_NEXT; break; }
             if (t.micro >= YCGE_CAMERA_MAX_MICRO_STEPS) { fail(t, ST_CAP_VERTICAL); return; }
             t.micro++; t.info.micro_steps++;
-            t.step = dmin(t.remaining, dmax(0.1, (double)kEyeHeight * 0.25));
+            t.step = dmin(t.remaining, dmax(0.1, (double)t.s.eye_height * 0.25));
             t.vhit = 0; t.vt = 0.0f;
             set_group(t, G_VERT, 1, PC_V_END);
             break;
@@ -189,7 +192,7 @@ YCGE_HD void cam_control(Tick &t)
             dt *= 0.001f;
             t.dts = dt;
             heights(t);
-            t.probe = (float)dmax(0.05, (double)kCollisionRadius * 0.25);
+            t.probe = (float)dmax(0.05, (double)t.s.collision_radius * 0.25);
             t.ebits = 0;
             set_group(t, G_EMBED, 8, PC_EMBED_END);
             break;
@@ -197,7 +200,7 @@ YCGE_HD void cam_control(Tick &t)
         case PC_EMBED_END: {                                                                      // ResolveIfEmbedded, :330-346
             if (!((t.ebits & 15) == 15 || (t.ebits >> 4) == 15)) { t.pc = PC_AFTER_RESOLVE; break; }
             heights(t);
-            t.search_r = (float)dmax((double)kCollisionRadius * 4.0, (double)t.w.voxel_size_y * 4.0);
+            t.search_r = (float)dmax((double)t.s.collision_radius * 4.0, (double)t.w.voxel_size_y * 4.0);
             t.found = 0; t.best_t = (double)YCGE_INF; t.best_dir = 4;
             set_group(t, G_EXIT, 12, PC_EXIT_END);
             break;
@@ -228,7 +231,7 @@ YCGE_HD void cam_control(Tick &t)
             }
             if (t.b.shift_hold_timer > 0.0f) t.b.shift_hold_timer = ycge::cs_max(0.0f, t.b.shift_hold_timer - t.dts);
             if (!(t.b.shift_hold_timer > 0.0f)) {
-                t.b.vertical_velocity -= kGravityAccel * t.dts;
+                t.b.vertical_velocity -= t.s.gravity_accel * t.dts;
                 t.new_y = (double)(pos[1] + t.b.vertical_velocity * t.dts);
                 const double fall = dmax(0.0, (double)pos[1] - t.new_y);
                 const double depth = dmax((double)kLocalProbeDepthMin, fall + (double)kExtraFallMargin);
@@ -240,8 +243,8 @@ YCGE_HD void cam_control(Tick &t)
             break;
         }
         case PC_AUTO_END: {                                                                       // :78-85 (the early return)
-            if (t.fan_has) pos[1] = (float)(t.ground + (double)kEyeHeight + (double)kGroundClearance);
-            else pos[1] = t.w.water_level + kEyeHeight + 4.0f;
+            if (t.fan_has) pos[1] = (float)(t.ground + (double)t.s.eye_height + (double)t.s.ground_clearance);
+            else pos[1] = t.w.water_level + t.s.eye_height + 4.0f;
             t.b.vertical_velocity = 0.0f;
             t.b.auto_placed = 1;
             t.info.auto_placements++;
@@ -251,7 +254,7 @@ YCGE_HD void cam_control(Tick &t)
         case PC_GROUND_END: {                                                                     // :108-132
             t.b.is_grounded = 0;
             if (t.fan_has) {
-                const double floor_y = t.ground + (double)kEyeHeight + (double)kGroundClearance;
+                const double floor_y = t.ground + (double)t.s.eye_height + (double)t.s.ground_clearance;
                 const bool above = floor_y > (double)(pos[1] + kStepUpGuardEpsilon);
                 if (t.new_y <= floor_y && !above) {
                     t.new_y = floor_y;
@@ -268,7 +271,7 @@ YCGE_HD void cam_control(Tick &t)
         }
         case PC_CORR_END: {                                                                       // :132-141
             if (t.fan_has) {
-                const double f2 = t.ground + (double)kEyeHeight + (double)kGroundClearance;
+                const double f2 = t.ground + (double)t.s.eye_height + (double)t.s.ground_clearance;
                 if (f2 <= (double)(pos[1] + kStepUpGuardEpsilon) && ((double)pos[1] - f2) <= 0.5) {
                     pos[1] = (float)f2;
                     t.b.vertical_velocity = 0.0f;
@@ -300,11 +303,11 @@ YCGE_HD void cam_control(Tick &t)
     if (t.pc == PC_DONE && t.status == ST_OK && !finite3(pos)) fail(t, ST_NOT_FINITE);
 }
 
-YCGE_HD void cam_begin(Tick &t, const ycge_camera_body &body, const ycge_camera_world &world, const ycge_camera_move *moves, int32_t n_moves,
-                       float dt_ms, int32_t run_update)
+YCGE_HD void cam_begin(Tick &t, const ycge_camera_body &body, const ycge_body_shape &shape, const ycge_camera_world &world, const ycge_camera_move *moves,
+                       int32_t n_moves, float dt_ms, int32_t run_update)
 {
     t = Tick();
-    t.b = body; t.w = world; t.moves = moves; t.n_moves = n_moves; t.dt_ms = dt_ms; t.run_update = run_update;
+    t.b = body; t.s = shape; t.w = world; t.moves = moves; t.n_moves = n_moves; t.dt_ms = dt_ms; t.run_update = run_update;
     t.pc = PC_MOVE_NEXT; t.grp = G_NONE; t.bad_move = -1;
     cam_control(t);
 }
@@ -326,7 +329,7 @@ YCGE_HD void cam_ray(const Tick &t, int k, Ray &r)
     const float *pos = t.b.pos;
     switch (t.grp) {
     case G_CAPS: {                                   // :243-252: offsets {0, r, -r}, eye then torso; LimitStepByRay, :283-288
-        const double offs[3] = {0.0, (double)kCollisionRadius, -(double)kCollisionRadius};
+        const double offs[3] = {0.0, (double)t.s.collision_radius, -(double)t.s.collision_radius};
         const double o = offs[k >> 1];
         const float ox = (float)((double)t.perpx * o), oz = (float)((double)t.perpz * o);
         r.o[0] = pos[0] + ox; r.o[1] = (float)((k & 1) ? t.ty : t.ey); r.o[2] = pos[2] + oz;
@@ -360,12 +363,12 @@ YCGE_HD void cam_ray(const Tick &t, int k, Ray &r)
         const double len = d < 4 ? 1.0 : 1.4142135623730951;      // Math.Sqrt(dx * dx + dz * dz)
         r.o[0] = pos[0]; r.o[1] = (float)((k & 1) ? t.ty : t.ey); r.o[2] = pos[2];
         r.d[0] = (float)(dx / len); r.d[1] = 0.0f; r.d[2] = (float)(dz / len);
-        r.tmin = 0.001f; r.tmax = kCollisionRadius;
+        r.tmin = 0.001f; r.tmax = t.s.collision_radius;
         break;
     }
     default: {                                       // G_FAN: TrySampleGroundY, :520-525
-        const double ox = k == 1 ? (double)kProbeRadius : k == 2 ? -(double)kProbeRadius : 0.0;
-        const double oz = k == 3 ? (double)kProbeRadius : k == 4 ? -(double)kProbeRadius : 0.0;
+        const double ox = k == 1 ? (double)t.s.probe_radius : k == 2 ? -(double)t.s.probe_radius : 0.0;
+        const double oz = k == 3 ? (double)t.s.probe_radius : k == 4 ? -(double)t.s.probe_radius : 0.0;
         r.o[0] = (float)(t.fx + ox); r.o[1] = (float)t.fstart; r.o[2] = (float)(t.fz + oz);
         r.d[0] = 0.0f; r.d[1] = -1.0f; r.d[2] = 0.0f;
         r.tmin = 0.00001f; r.tmax = (float)t.fmax;
@@ -403,7 +406,7 @@ YCGE_HD void cam_commit(Tick &t, const Hit *hits, int n)
             break;
         case G_PUSH:                                 // ResolvePenetrationAt, :446-463
             if (h.hit) {
-                const float pen = kCollisionRadius - h.t;
+                const float pen = t.s.collision_radius - h.t;
                 if (pen > 0.0f) {
                     const float nl = ycge::cs_sqrt(h.nx * h.nx + h.nz * h.nz);
                     if (nl > 1e-6f) {
@@ -421,7 +424,7 @@ YCGE_HD void cam_commit(Tick &t, const Hit *hits, int n)
             if (h.hit) {
                 const double y = (double)((float)t.fstart + -1.0f * h.t);
                 t.any_hit = 1;
-                const double floor_candidate = y + (double)kEyeHeight + (double)kGroundClearance;
+                const double floor_candidate = y + (double)t.s.eye_height + (double)t.s.ground_clearance;
                 if (floor_candidate <= (double)(pos[1] + kStepUpGuardEpsilon)) {
                     if (!t.any_ok || y > t.best_ok) t.best_ok = y;
                     t.any_ok = 1;
@@ -466,6 +469,20 @@ YCGE_HD const char *cam_refusal(const ycge_camera_body *body, const ycge_camera_
     *bad_move = -1;
     return nullptr;
 }
+// a shape the exports refuse: 0, or the reason.  The sizes are bounded like a move's length, so that a probe (4 radii in the exit
+// search) and a push-out stay within the lengths YCGE_CAMERA_MAX_MOVE_LENGTH and the micro-step cap were set for
+YCGE_HD const char *cam_shape_refusal(const ycge_body_shape &s)
+{
+    if (!isfinite(s.eye_height) || !isfinite(s.collision_radius) || !isfinite(s.probe_radius) || !isfinite(s.ground_clearance) || !isfinite(s.jump_speed) ||
+        !isfinite(s.gravity_accel))
+        return "a field of the shape is not finite";
+    if (!(s.eye_height > 0.0f) || !(s.collision_radius > 0.0f) || !(s.probe_radius > 0.0f) || !(s.gravity_accel > 0.0f))
+        return "eye_height, collision_radius, probe_radius and gravity_accel of a shape must be positive";
+    if (s.ground_clearance < 0.0f || s.jump_speed < 0.0f) return "ground_clearance and jump_speed of a shape must not be negative";
+    if (s.eye_height > YCGE_BODY_SHAPE_MAX_SIZE || s.collision_radius > YCGE_BODY_SHAPE_MAX_SIZE)
+        return "eye_height or collision_radius of a shape above YCGE_BODY_SHAPE_MAX_SIZE (64)";
+    return nullptr;
+}
 YCGE_HD const char *cam_status_text(int status)
 {
     return status == ST_CAP_HORIZONTAL ? "a horizontal move reached the cap of YCGE_CAMERA_MAX_MICRO_STEPS (1024) micro-steps"
@@ -503,6 +520,21 @@ struct TickOut {
     int32_t bad_move;
     int32_t status;               // ST_*, stored last; the host fills the record with 0xff before the launch
 };
+// ---- the records of k_bodies_tick: one header, an input record a body, the moves of all bodies as ONE array (body i's are
+// moves[first_move .. first_move + n_moves)), and a TickOut a body
+struct BodiesHeader {
+    ycge_camera_world world;
+    float dt_ms;
+    int32_t run_update, n, n_moves_total;
+    uint32_t pad;
+};
+struct BodyIn {
+    ycge_camera_body body;
+    ycge_body_shape shape;
+    int32_t first_move, n_moves;
+    uint32_t pad[2];
+};
+static_assert(sizeof(ycge_body_shape) == 24 && sizeof(ycge_body_result) == 8 && sizeof(BodiesHeader) == 32 && sizeof(BodyIn) == 80, "k_bodies_tick's records");
 static_assert(sizeof(ycge_camera_body) == 40 && sizeof(ycge_camera_world) == 12 && sizeof(ycge_camera_move) == 16 && sizeof(ycge_camera_tick_info) == 48, "ycge.h");
 static_assert(sizeof(TickIn) == 80 + 16 * YCGE_CAMERA_MAX_MOVES && sizeof(TickOut) == 96, "k_camera_tick's records");
 

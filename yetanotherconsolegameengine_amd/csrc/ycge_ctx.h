@@ -156,6 +156,10 @@ int ycge_launch_query(const ycge::SceneDev *S, const float *rays, uint32_t n, fl
                       void *spill, uint32_t lanes, int has_grid, hipStream_t stream);
 // the camera tick (k_camera_tick, ycge_camera.hip): one wavefront; in / out: ycge_cam::TickIn / TickOut (ycge_camera_physics.h), spill: 64 columns
 int ycge_launch_camera_tick(const ycge::SceneDev *S, const void *in, void *out, void *spill, int has_grid, hipStream_t stream);
+// many bodies a tick (k_bodies_tick, ycge_camera.hip): n workgroups of one wavefront; header / in / out: ycge_cam::BodiesHeader, n BodyIn, n TickOut;
+// moves: every body's, one array; spill: max(1, spill levels) x 64 * n columns
+int ycge_launch_bodies_tick(const ycge::SceneDev *S, const void *header, const void *in, const void *moves, void *out, void *spill, int n, int has_grid,
+                            hipStream_t stream);
 }
 
 using namespace ycge;
@@ -432,6 +436,10 @@ struct QueryState {
     DevBuf<uint8_t> cam_dev;
     DevBuf<uint64_t> cam_spill;
     PinnedBuf cam_stage;
+    // ycge_volume_bodies_tick: k_bodies_tick's {header, n inputs, moves, n results}, its 64 * n spill columns, their staging; grow-only
+    DevBuf<uint8_t> bodies_dev;
+    DevBuf<uint64_t> bodies_spill;
+    PinnedBuf bodies_stage;
 };
 // one ANSI stream call (ycge_ansi.cpp): the colour form, the console, the viewport, the default colours, the clear-screen prefix; delta: a
 // _delta call, which alone reads gap, tolerance (24-bit colour only) and keyframe

@@ -574,6 +574,30 @@ class RaytraceRenderer:
                                                    1 if run_update else 0, C.byref(info)))
         return {n: int(getattr(info, n)) for n, _ in abi.CameraTickInfo._fields_ if n != "reserved"}
 
+    # ---------------------------------------------------------------- many bodies a tick (ycge_volume_bodies_tick)
+    def BodiesTick(self, bodies, world: "abi.CameraWorld", moves, dt_ms: float, run_update: bool = True, shapes=None):
+        """n independent bodies a tick in one launch: `bodies` is a ctypes array of abi.CameraBody (updated in place, body by body, where the
+        tick committed), `moves` one list of move records (abi.CameraMove or (kind, shift, a, b) tuples) per body, `shapes` a ctypes array
+        of abi.BodyShape or None for the reference's sizes.  Returns (results, infos): per body (status, bad_move) - 0 committed, 1 / 2 a
+        horizontal / vertical move reached the micro-step cap, 3 the position stopped being finite, the body then left as it was - and the
+        counters of ycge_camera_tick_info.  A refusal raises YcgeError and writes nothing.  Runs beside frames in flight, as Hit does."""
+        n = len(bodies)
+        if len(moves) != n or (shapes is not None and len(shapes) != n):
+            raise ValueError("BodiesTick: one list of moves (and one shape) per body")
+        first = (C.c_int32 * (n + 1))()
+        flat = []
+        for i, ms in enumerate(moves):
+            flat.extend(m if isinstance(m, abi.CameraMove) else abi.CameraMove(int(m[0]), int(m[1]), float(m[2]), float(m[3])) for m in ms)
+            first[i + 1] = len(flat)
+        recs = (abi.CameraMove * max(1, len(flat)))(*flat)
+        results = (abi.BodyResult * max(1, n))()
+        info = (abi.CameraTickInfo * max(1, n))()
+        self._check(self.L.ycge_volume_bodies_tick(self.ctx, C.byref(bodies) if n else None, C.byref(shapes) if shapes is not None and n else None, n,
+                                                   C.byref(world), recs if flat else None, first, float(dt_ms), 1 if run_update else 0, results, info))
+        names = [f for f, _ in abi.CameraTickInfo._fields_ if f != "reserved"]
+        return ([(int(results[i].status), int(results[i].bad_move)) for i in range(n)],
+                [{f: int(getattr(info[i], f)) for f in names} for i in range(n)])
+
     def scene_bvh_stats(self) -> dict:
         """How ycge_scene_update_objects built the scene BVH so far: on the device (csrc/ycge_bvh_build.hip), on the host after the
         kernel declined, on the host outright; microseconds of the last build + install; how often the current tree took the
@@ -1232,3 +1256,40 @@ class VolumeCamera:
     @property
     def pos(self):
         return tuple(self.body.pos)
+
+
+class VolumeBodies:
+    """The bodies of a voxel world that are not the player's alone - mobs, dropped items, projectiles, the other players of a replicated
+    scene - ticked together: add() makes a body with its own shape (abi.BodyShape, or None for the reference's 1.7-tall capsule of radius
+    0.65) and hands back a VolumeCamera to queue its moves on (forward / strafe / rise / jump / shift); tick() hands every body, its
+    shape and its moves to RaytraceRenderer.BodiesTick - one launch for all of them - and clears the lists.  A body whose tick reached a
+    cap stays as it was (its moves are dropped with the rest); `results` says which."""
+
+    def __init__(self, world_height: float, water_level: float, voxel_size_y: float = 1.0):
+        self.world = abi.CameraWorld(float(world_height), float(water_level), float(voxel_size_y))
+        self.bodies: list = []          # VolumeCamera: .body, .moves
+        self.shapes: list = []          # abi.BodyShape
+        self.results: list = []         # (status, bad_move) of the last tick
+        self.infos: list = []
+
+    def add(self, pos, shape=None, auto_placed: bool = False) -> VolumeCamera:
+        cam = VolumeCamera(pos, self.world.world_height, self.world.water_level, self.world.voxel_size_y, auto_placed)
+        self.bodies.append(cam)
+        self.shapes.append(abi.BodyShape(*abi.BODY_SHAPE_DEFAULT) if shape is None else shape if isinstance(shape, abi.BodyShape) else abi.BodyShape(*shape))
+        return cam
+
+    def __len__(self):
+        return len(self.bodies)
+
+    def tick(self, renderer: RaytraceRenderer, dt_ms: float, run_update: bool = True):
+        n = len(self.bodies)
+        if n == 0:
+            self.results, self.infos = [], []
+            return self.results, self.infos
+        recs = (abi.CameraBody * n)(*[c.body for c in self.bodies])
+        shapes = (abi.BodyShape * n)(*self.shapes)
+        self.results, self.infos = renderer.BodiesTick(recs, self.world, [c.moves for c in self.bodies], dt_ms, run_update, shapes)
+        for c, r in zip(self.bodies, recs):
+            C.memmove(C.byref(c.body), C.byref(r), C.sizeof(abi.CameraBody))
+            c.moves = []
+        return self.results, self.infos
