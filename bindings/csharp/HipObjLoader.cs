@@ -51,6 +51,27 @@ namespace ConsoleGame.RayTracing
             finally { Ycge.ycge_obj_release(ctx); }
         }
 
+        /// <summary>The OBJ at `path` added to the RESIDENT scene of `ctx` as a mesh of material index `material` (ycge_scene_attach_obj_mesh):
+        /// placed as FromObj places it - or, with autoGround, as AddMeshAutoGround at (tx, ty, tz) - and handed to the tree builder where the
+        /// OBJ kernels wrote it; no triangle comes back.  Returns the device mesh index (ycge_prim.ref of the next ycge_scene_update_objects);
+        /// bounds: min xyz, max xyz.</summary>
+        public static int AttachToScene(IntPtr ctx, string path, int material, out float[] bounds, float scale = 1.0f, float tx = 0.0f, float ty = 0.0f, float tz = 0.0f,
+                                        bool normalize = true, float targetSize = 1.0f, bool autoGround = false)
+        {
+            Parse(ctx, path);
+            try
+            {
+                bounds = new float[6];
+                float* t = stackalloc float[3];
+                t[0] = tx; t[1] = ty; t[2] = tz;
+                int index;
+                fixed (float* pb = bounds)
+                    Ycge.Check(ctx, Ycge.ycge_scene_attach_obj_mesh(ctx, autoGround ? 1 : 0, normalize ? 1 : 0, targetSize, scale, t, material, &index, pb));
+                return index;
+            }
+            finally { Ycge.ycge_obj_release(ctx); }
+        }
+
         private static YObjInfo Parse(IntPtr ctx, string path)
         {
             if (string.IsNullOrWhiteSpace(path)) throw new ArgumentException("path");

@@ -362,6 +362,52 @@ public partial class RaytraceEntity
             return true;
         }
 
+        /// <summary>Meshes of a running scene (an entity whose GetHittables() yields a Mesh, Scene.cs:519-535): the scene's Meshes that the
+        /// device does not hold yet are attached (ycge_scene_attach_meshes: only their own trees are built and their records written), the
+        /// materials they bring appended first (ycge_scene_append_materials).  False when one of them needs a texture the last upload did not hold.</summary>
+        internal bool SyncMeshes(Scene scene)
+        {
+            var fresh = new List<Mesh>();
+            foreach (Hittable o in scene.Objects) if (o is Mesh m && !uploaded.MeshOwners.Contains(m) && !fresh.Contains(m)) fresh.Add(m);
+            if (fresh.Count == 0) return true;
+            using (var scratch = new FlatScene())
+            {
+                var records = new YMesh[fresh.Count];
+                for (int i = 0; i < records.Length; i++)
+                {
+                    if (!SceneFlattener.FlattenMesh(fresh[i], uploaded, scratch, out records[i], out YMaterial[] added)) return false;
+                    if (added.Length == 0) continue;
+                    int first;
+                    fixed (YMaterial* a = added) Ycge.Check(ctx, Ycge.ycge_scene_append_materials(ctx, a, added.Length, &first));
+                    if (first != uploaded.Materials.Length) throw new InvalidOperationException("ycge_scene_append_materials numbered the materials differently");
+                    var longer = new YMaterial[uploaded.Materials.Length + added.Length];
+                    uploaded.Materials.CopyTo(longer, 0); added.CopyTo(longer, uploaded.Materials.Length);
+                    uploaded.Materials = longer;
+                }
+                var index = new int[records.Length];
+                fixed (YMesh* r = records) fixed (int* ix = index) Ycge.Check(ctx, Ycge.ycge_scene_attach_meshes(ctx, r, records.Length, ix));
+                for (int i = 0; i < index.Length; i++)
+                {
+                    while (uploaded.MeshOwners.Count <= index[i]) uploaded.MeshOwners.Add(null);
+                    uploaded.MeshOwners[index[i]] = fresh[i];
+                }
+            }
+            return true;
+        }
+
+        /// <summary>... and the meshes that left Scene.Objects give their indices back (after ycge_scene_update_objects: nothing refers to them).</summary>
+        private void DetachMeshes()
+        {
+            var live = new HashSet<Mesh>();
+            foreach (Hittable o in scene.Objects) if (o is Mesh m) live.Add(m);
+            var gone = new List<int>();
+            for (int i = 0; i < uploaded.MeshOwners.Count; i++) if (uploaded.MeshOwners[i] != null && !live.Contains(uploaded.MeshOwners[i])) gone.Add(i);
+            if (gone.Count == 0) return;
+            int[] ix = gone.ToArray();
+            fixed (int* p = ix) Ycge.Check(ctx, Ycge.ycge_scene_detach_meshes(ctx, p, ix.Length));
+            foreach (int i in gone) uploaded.MeshOwners[i] = null;
+        }
+
         /// <summary>Chunks that came from the generator (HipGeneratedWorld): the desired keys the device does not hold yet are generated ON
         /// THE DEVICE and attached in one call (ycge_scene_generate_grids: keys in, device indices back, -1 for a chunk of nothing but Air,
         /// which gets no object); no cells are made or sent by the host.  False when the lookup needs a material the last upload did not hold.</summary>
@@ -424,11 +470,11 @@ public partial class RaytraceEntity
         {
             if (forceUpload || ObjectsSignature() != objectsSignature || GeneratedChanged())
             {
-                YPrim[] prims = forceUpload || !SyncVolumeGrids(scene) || !SyncGeneratedChunks() ? null : WithGenerated(SceneFlattener.ObjectsAgainst(scene, uploaded));
+                YPrim[] prims = forceUpload || !SyncVolumeGrids(scene) || !SyncMeshes(scene) || !SyncGeneratedChunks() ? null : WithGenerated(SceneFlattener.ObjectsAgainst(scene, uploaded));
                 forceUpload = false;
                 if (prims == null)
                 {
-                    Upload();                       // a new mesh or material: the whole scene again
+                    Upload();                       // a new texture, or a new material on an object that is no mesh: the whole scene again
                     generatedIndex.Clear();         // (an upload forgets every attached grid; the generated chunks are made again)
                     if (generated != null && generated.Desired.Count > 0)
                     {
@@ -443,6 +489,7 @@ public partial class RaytraceEntity
                     fixed (YPrim* p = prims) Ycge.Check(ctx, Ycge.ycge_scene_update_objects(ctx, p, prims.Length));     // only the scene-level BVH is rebuilt, as in the reference
                     uploaded.Prims = prims;
                     DetachVolumeGrids();
+                    DetachMeshes();
                     objectsSignature = ObjectsSignature();
                 }
             }

@@ -409,6 +409,20 @@ namespace ConsoleGame.RayTracing.Native
             return mats.Records.Count == uploaded.Materials.Length && mats.Textures.Count == uploaded.Textures.Count;
         }
 
+        /// <summary>One Mesh as a ycge_mesh against the materials the library holds - for ycge_scene_attach_meshes when an entity brings a new
+        /// model (Scene.cs:519-535).  `scratch` owns the triangles until the call has returned.  newMaterials: the materials the mesh uses that
+        /// the library does not hold yet, in index order behind the held ones (ycge_scene_append_materials first).  False when the mesh needs a
+        /// texture the last upload did not hold: the caller uploads the scene again.</summary>
+        public static bool FlattenMesh(Mesh m, FlatScene uploaded, FlatScene scratch, out YMesh record, out YMaterial[] newMaterials)
+        {
+            var mats = new MaterialTable();
+            foreach (YMaterial r in uploaded.Materials) mats.Records.Add(r);
+            mats.Textures.AddRange(uploaded.Textures);
+            record = MeshRecord(m, mats, scratch);
+            newMaterials = mats.Records.GetRange(uploaded.Materials.Length, mats.Records.Count - uploaded.Materials.Length).ToArray();
+            return mats.Textures.Count == uploaded.Textures.Count;
+        }
+
         /// <summary>The `proto` of ycge_scene_generate_grids for a HipGeneratedWorld: a lookup entry for every (matId, metaId) pair
         /// WorldGenerator.GenerateChunkCells can write (Stone with metas 0..2, StrataMap.cs:8-19; Dirt, Grass, Water, Sand, Wood, Leaves, Snow
         /// with meta 0, WorldGenSettings.cs:8-22), materials numbered against the last upload.  False when the lookup returns one it did not hold.</summary>

@@ -282,6 +282,13 @@ namespace ConsoleGame.RayTracing.Native
         // chunk streaming (found by symbol lookup, ABI stays 10): grids beside those of the last upload, and their slots given back
         [DllImport(Lib)] public static extern int ycge_scene_attach_grids(IntPtr ctx, YGrid* grids, int n, int* outGridIndex);
         [DllImport(Lib)] public static extern int ycge_scene_detach_grids(IntPtr ctx, int* gridIndex, int n);
+        // meshes and materials of a resident scene (found by symbol lookup, ABI stays 10): meshes beside those of the last upload and their indices
+        // given back, materials behind the existing ones, the held OBJ as a resident mesh (translateOrTarget: 3 floats; outBounds: 6 floats or null)
+        [DllImport(Lib)] public static extern int ycge_scene_attach_meshes(IntPtr ctx, YMesh* meshes, int n, int* outMeshIndex);
+        [DllImport(Lib)] public static extern int ycge_scene_detach_meshes(IntPtr ctx, int* meshIndex, int n);
+        [DllImport(Lib)] public static extern int ycge_scene_append_materials(IntPtr ctx, YMaterial* materials, int n, int* outFirstIndex);
+        [DllImport(Lib)] public static extern int ycge_scene_attach_obj_mesh(IntPtr ctx, int autoGround, int normalize, float targetSize, float scale, float* translateOrTarget,
+                                                                             int material, int* outMeshIndex, float* outBounds);
         // chunk generation (found by symbol lookup, ABI stays 10): WorldGenerator.GenerateChunkCells on the host / on the device + attach
         // (YWorld: bindings/csharp/YcgeWorld.cs)
         [DllImport(Lib)] public static extern int ycge_worldgen_chunk_cells(ref YWorld world, int cx, int cy, int cz, int* cellsOut, int* anySolidOut);

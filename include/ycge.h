@@ -336,7 +336,8 @@ int ycge_scene_update_lights(ycge_ctx *ctx, const ycge_light *lights, int32_t n_
 /* Scene.Update() -> RebuildBVH() after an entity moved its geometry (Scenes/Scene.cs:122-127; e.g.
  * BobbingSphereEntity.Update, Scenes/TestScenesRandom.cs:708-714): replaces the Scene.Objects records and
  * rebuilds the scene-level BVH only.  `prims` index the materials and meshes of the last ycge_scene_upload (a Mesh keeps its own
- * BVH in the reference too, Mesh.cs:14) and the RESIDENT grids: those of the upload and of ycge_scene_attach_grids, less the detached.  The tree (Objects/BVH.cs:258-459,
+ * BVH in the reference too, Mesh.cs:14) and the RESIDENT grids: those of the upload and of ycge_scene_attach_grids, less the detached.
+ * Likewise the RESIDENT meshes and the materials appended since (ycge_scene_attach_meshes, ycge_scene_append_materials below).  The tree (Objects/BVH.cs:258-459,
  * same nodes, numbering and leaf order) is built on the device for up to 2 560 objects - the host only flattens the
  * records and their boxes - and by the host builder above that. */
 int ycge_scene_update_objects(ycge_ctx *ctx, const ycge_prim *prims, int32_t n_prims);
@@ -377,6 +378,57 @@ int ycge_scene_attach_grids(ycge_ctx *ctx, const ycge_grid *grids, int32_t n, in
 /* Give n grids' slots back.  Refused (YCGE_ERR_INVALID_ARG, nothing freed) while the current Scene.Objects refer to one of them,
  * for an index that is not resident, or for one named twice. */
 int ycge_scene_detach_grids(ycge_ctx *ctx, const int32_t *grid_index, int32_t n);
+
+/* --- meshes and materials of a resident scene: a host that adds one model to a running scene - a viewer that loads a second .obj, an entity
+ * whose GetHittables() yields a Mesh (Scenes/Scene.cs:519-535) - attaches it, instead of paying for every mesh BVH, the whole arena and every
+ * grid again with ycge_scene_upload.  Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no existing struct changes - a host
+ * detects these exports by symbol lookup.  One tick is: append the materials that are new, attach the meshes that are new,
+ * ycge_scene_update_objects with the new object list, detach what left - or leave it resident and merely unreferenced.  Each step leaves a
+ * complete, renderable scene.
+ *   Same pixels.  After any sequence of append / attach / update_objects / detach, every frame, every ycge_read_buffer buffer, every scene
+ *     query, the counting instances' ycge_frame_stats counters and ycge_read_timed_steps are what the same context gives when each tick is
+ *     instead one ycge_scene_upload of the equivalent scene - bit for bit, TAA history and exposure state included.  The equivalent scene
+ *     holds the same materials in the same order and the same Scene.Objects in the same order; its meshes[i] is the resident mesh of index
+ *     i, a free index a mesh of 0 triangles.  Arena offsets are internal and may differ.
+ *   Indices.  A mesh of the upload keeps its index.  An attached mesh takes the lowest free index; out_mesh_index is written only on
+ *     success.  The next ycge_scene_upload forgets all of it.
+ *   Referencing.  No object refers to an attached mesh until the next ycge_scene_update_objects names it (ycge_prim.ref).  A mesh that
+ *     stays resident and unreferenced changes nothing.
+ *   Materials.  A mesh's `material` and `tri_material` index the materials of the last upload plus everything appended since.
+ *   All or nothing.  A refused or failed attach or append leaves the scene exactly as it was - renderable, no index taken, no range of the
+ *     arena taken, the outputs untouched; every refusal is decided before the pool of resident meshes is changed.  YCGE_ERR_INVALID_ARG:
+ *     n < 0, NULL arrays with n > 0, n_triangles < 0, NULL `triangles` with triangles, a material out of range, a peer context (the
+ *     message names the mesh by its place in the call).  YCGE_ERR_NO_SCENE before the first upload.  A leaf of more than 15 triangles and a
+ *     tree deeper than 64 are refused with the statuses and texts ycge_scene_upload gives.  YCGE_ERR_UNSUPPORTED when the records would pass
+ *     what a pooled arena can address (the message gives the limit in bytes).  YCGE_ERR_OUT_OF_MEMORY for a failed allocation.  n = 0 is
+ *     YCGE_OK.
+ *   Frames in flight.  An attach and an append JOIN the frames in flight, like every other scene call: the arena and the tables may move.
+ *     ycge_scene_detach_meshes changes host state only and joins nothing.  Scene queries see the change with the next query after
+ *     ycge_scene_update_objects.  What the kernels are told about the resident SET - whether any resident mesh has an inner node, the
+ *     deepest resident tree, the flags of the material list - follows it with the next ycge_scene_update_objects, as after an upload of
+ *     the equivalent scene.
+ *   One-process multi-device (n_devices >= 2): the root builds once and forwards - every other device receives the new records and
+ *     treelets by a device copy; a peer context refuses.  Tiled ranks (world_size > 1) each make the same calls.
+ * The trees are built as ycge_scene_upload builds them (the device builder from YCGE_MESH_BVH_DEVICE_MIN triangles on, the host builder
+ * below that and for what the device builder declines); every mesh's records and treelets are written on the device (csrc/ycge_mesh_emit.hip). */
+/* Make n more meshes resident beside those of the last ycge_scene_upload. */
+int ycge_scene_attach_meshes(ycge_ctx *ctx, const ycge_mesh *meshes, int32_t n, int32_t *out_mesh_index /* n */);
+/* Give n meshes' indices and records back.  Refused (YCGE_ERR_INVALID_ARG, nothing freed) while the current Scene.Objects refer to one of
+ * them, for an index that is not resident, or for one named twice. */
+int ycge_scene_detach_meshes(ycge_ctx *ctx, const int32_t *mesh_index, int32_t n);
+/* n more materials behind the existing ones; *out_first_index is the first new index.  A textured material indexes the textures of the last
+ * upload.  The flags derived from the material list (some material is transparent, textured, can mirror - and with that the rounds of the
+ * wavefront path) follow the longer list and are published with the next install of the objects: an append alone changes no frame, and
+ * from the tick's ycge_scene_update_objects on the equivalence above holds.  Grid lookups may name appended materials from the next
+ * ycge_scene_attach_grids on. */
+int ycge_scene_append_materials(ycge_ctx *ctx, const ycge_material *materials, int32_t n, int32_t *out_first_index);
+/* The OBJ held by ycge_obj_parse, placed as ycge_obj_triangles (auto_ground = 0: normalize, target_size, scale, translate) or
+ * ycge_obj_triangles_auto_ground (auto_ground = 1: scale, target; normalize and target_size are not read) places it, becomes a resident
+ * mesh of material `material`: its triangle soup goes from the OBJ kernels' device buffer to the tree builder without crossing the bus
+ * (read back once where the host builder has to build the tree).  The same index, bounds and pixels as that call followed by
+ * ycge_scene_attach_meshes; out_bounds (or NULL) and out_mesh_index are written only on success. */
+int ycge_scene_attach_obj_mesh(ycge_ctx *ctx, int32_t auto_ground, int32_t normalize, float target_size, float scale, const float translate_or_target[3],
+                               int32_t material, int32_t *out_mesh_index, float out_bounds[6] /* or NULL */);
 
 /* --- chunk generation: the chunks ycge_scene_attach_grids receives come from WorldGenerator.GenerateChunkCells on the host's worker threads
  * (WorldManager.cs:754-793, 914; 2 312 calls before the first frame when there is no world file, VolumeScenes.cs:617-624).  The function is

@@ -152,6 +152,8 @@ int ycge_debug_read_walk_tree(ycge_ctx *c, void *gnodes_out, void *walk_out, int
 int ycge_debug_read_grid(ycge_ctx *c, int32_t grid_index, void *record_out /* sizeof GGrid = 112 bytes */, int32_t *materials_out);   /* a resident grid as the device holds it: its record and, per voxel in ycge_grid.cells order, the material of its cell code (-1 = empty) */
 ycge_ctx *ycge_debug_peer_context(ycge_ctx *c, int32_t k);           /* the context of device k + 1 of a one-process multi-device context (NULL: none): the scene calls refuse it */
 int ycge_debug_grid_pool_stats(ycge_ctx *c, int64_t *out12);         /* resident grids, free indices, arena bytes in use, arena capacity, arena growths, slots reused, device encodes, host-fallback encodes; the last attach in us: staging copy, host-to-device copy, encode kernel, read-back */
+int ycge_debug_mesh_pool_stats(ycge_ctx *c, int64_t *out12);         /* the resident meshes (csrc/ycge_mesh_pool.cpp): resident meshes, free indices, units of records in use, capacity in units (before the first attach: the uploaded records), growths of the pooled arena, ranges reused, device builds, host builds of the attaches; the last attach in us: trees, emit, copies (re-homing, growth, other devices); 1 once the arena is pooled */
+int ycge_debug_mesh_ranges(int64_t end0, int32_t n_index0, const int64_t *ops, int32_t n_ops, int64_t *out /* 4 per op */);   /* the pool's allocator alone (csrc/ycge_mesh_pool.h), no context and no device, from end0 units of records and n_index0 indices: n_ops triples {op, a, b} - 0 take a units, 1 give back the b units at unit a, 2 take an index, 3 give back index a; per op {the take's answer, the records' end, free ranges, free units} */
 /* chunk generation, host only (csrc/ycge_worldgen.cpp over csrc/ycge_worldgen.h; tests/test_worldgen_hooks_cpu.py against tests/worldgen_restatement.py) */
 int ycge_host_worldgen_noise(int32_t n, const int32_t *ix, const int32_t *iz, const float *x, const float *z, int32_t seed, uint32_t *hash_out, float *noise_out);   /* FastHash(ix, 0, iz, seed) and GradientNoise2D(x, z, seed) */
 int ycge_host_worldgen_height(const ycge_world *world, int32_t n, const int32_t *gx, const int32_t *gz, int32_t *height_out);                                      /* TerrainNoise.HeightY */

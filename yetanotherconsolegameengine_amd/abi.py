@@ -293,6 +293,11 @@ _PROTOTYPES = {
     "ycge_scene_update_objects": (C.c_int, [C.c_void_p, C.POINTER(Prim), C.c_int32]),
     "ycge_scene_attach_grids": (C.c_int, [C.c_void_p, C.POINTER(Grid), C.c_int32, C.POINTER(C.c_int32)]),
     "ycge_scene_detach_grids": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
+    "ycge_scene_attach_meshes": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.c_int32, C.POINTER(C.c_int32)]),
+    "ycge_scene_detach_meshes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
+    "ycge_scene_append_materials": (C.c_int, [C.c_void_p, C.POINTER(Material), C.c_int32, C.POINTER(C.c_int32)]),
+    # (translate_or_target: 3 floats or None; out_bounds: 6 floats or None)
+    "ycge_scene_attach_obj_mesh": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     # (world: a ycge_world, passed with C.byref(abi.World))
     "ycge_worldgen_chunk_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ycge_scene_generate_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(Grid), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -496,6 +501,14 @@ MESH_EMIT_HOOK_PROTOTYPES = {
 MESH_EMIT_RES_WORDS = 8
 MESH_EMIT_RES = ("tree_built_on_device", "nodes", "record_units", "layout_us", "records_us", "treelets_us")
 MESH_EMIT_STATS = ("device_meshes", "host_meshes", "last_device_emit_us", "arena_bytes")
+# test / profiling hooks of the pool of resident meshes (csrc/ycge_mesh_pool.cpp), bound where they are used (RaytraceRenderer.mesh_pool_stats, mesh_ranges below)
+MESH_POOL_HOOK_PROTOTYPES = {
+    "ycge_debug_mesh_pool_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ycge_debug_mesh_ranges": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+}
+MESH_POOL_STATS = ("resident", "free_indices", "units_in_use", "capacity_units", "growths", "ranges_reused", "device_builds", "host_builds",
+                   "build_us", "emit_us", "copy_us", "pooled")
+MESH_RANGE_TAKE, MESH_RANGE_GIVE, MESH_INDEX_TAKE, MESH_INDEX_GIVE = range(4)
 
 # test / profiling hook of the OBJ parse (csrc/ycge_obj.cpp), bound where it is used (RaytraceRenderer.obj_stats, obj_geometry below)
 OBJ_HOOK_PROTOTYPES = {
@@ -566,6 +579,22 @@ def world_file_info(data, lib: C.CDLL | None = None):
     if rc != 0:
         raise YcgeError(rc, msg.value.decode())
     return tuple(int(v) for v in dims), int(off.value)
+
+
+def mesh_ranges(ops, end0: int = 0, n_index0: int = 0, lib: C.CDLL | None = None):
+    """ycge_debug_mesh_ranges: the mesh pool's allocator alone (no context, no device) run through `ops` - rows {op, a, b} with op one of
+    MESH_RANGE_TAKE (a units), MESH_RANGE_GIVE (the b units at unit a), MESH_INDEX_TAKE, MESH_INDEX_GIVE (index a) -> int64 [n, 4]: per op
+    {the take's answer, the records' end, free ranges, free units}."""
+    import numpy as np
+    L = lib if lib is not None else load_library()
+    fn = L.ycge_debug_mesh_ranges
+    fn.restype, fn.argtypes = MESH_POOL_HOOK_PROTOTYPES["ycge_debug_mesh_ranges"]
+    ops = np.ascontiguousarray(ops, np.int64).reshape(-1, 3)
+    out = np.zeros((len(ops), 4), np.int64)
+    rc = fn(end0, n_index0, ops.ctypes.data, len(ops), out.ctypes.data)
+    if rc != 0:
+        raise YcgeError(rc, "ycge_debug_mesh_ranges refused the arguments")
+    return out
 
 
 def obj_parse_host(data: bytes, lib: C.CDLL | None = None):

@@ -42,6 +42,7 @@
 #include "ycge_ansi_layers.h"
 #include "ycge_device.h"
 #include "ycge_math.h"
+#include "ycge_mesh_pool.h"
 #include "ycge_own.h"
 #include "ycge_world_store.h"
 #include "ycge_worldgen.h"
@@ -232,6 +233,8 @@ struct Knobs {
     bool no_analytic_walk = false;   // YCGE_NO_ANALYTIC_WALK: scenes of analytic objects only are walked by tree_phase's general loop (A/B of analytic_walk; same pixels)
     bool no_walk_tree = false;       // YCGE_NO_WALK_TREE: voxel worlds are walked down the scene tree, leaves and object steps and all (A/B of SceneDev::walk_nodes)
     bool mesh_emit_host = false;     // YCGE_MESH_EMIT_HOST: ycge_scene_upload writes every mesh's records and the treelets on the host, whoever built the trees
+    long long mesh_pool_units = 0;   // YCGE_MESH_POOL_UNITS: the capacity (32-byte units of records) the first ycge_scene_attach_meshes re-homes the arena into (0: twice the uploaded records, at least 1 MiB of them)
+    long long mesh_pool_max_units = 0;   // YCGE_MESH_POOL_MAX_UNITS: a lower cap on that capacity (0: none; tests provoke the refusal at small size)
     int mesh_emit_device_min = YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT;   // YCGE_MESH_EMIT_DEVICE_MIN: ... and also when no tree built on the device has this many triangles (measured crossover of the whole upload, profiles/mesh_build_rate.json)
     bool no_coop = false;            // YCGE_NO_COOP: no treelets are built, sparse wavefronts keep the regular walk (A/B of the cooperative walk)
     size_t enc_group_bytes = (size_t)256 << 20;   // YCGE_ENC_GROUP_BYTES: raw cells staged per encode group (attach / generate sub-batches); a larger grid is a group of its own
@@ -306,6 +309,8 @@ struct Knobs {
         if (ws_pool_batch < 1 || ws_pool_batch > YCGE_WS_POOL_BATCH_DEFAULT) ws_pool_batch = YCGE_WS_POOL_BATCH_DEFAULT;
         if (const char *e = getenv("YCGE_ENC_GROUP_BYTES")) { const long long v = atoll(e); if (v > 0) enc_group_bytes = (size_t)v; }
         mesh_emit_host = getenv("YCGE_MESH_EMIT_HOST") != nullptr;
+        if (const char *e = getenv("YCGE_MESH_POOL_UNITS")) { const long long v = atoll(e); if (v > 0) mesh_pool_units = v; }
+        if (const char *e = getenv("YCGE_MESH_POOL_MAX_UNITS")) { const long long v = atoll(e); if (v > 0) mesh_pool_max_units = v; }
         mesh_emit_device_min = geti("YCGE_MESH_EMIT_DEVICE_MIN", YCGE_MESH_EMIT_DEV_MIN_TRIS_DEFAULT);
         mesh_bvh_device_min = geti("YCGE_MESH_BVH_DEVICE_MIN", YCGE_MESH_BVH_DEV_MIN_TRIS_DEFAULT);
         mesh_bvh_wide_min = geti("YCGE_MESH_BVH_WIDE_MIN", YCGE_BVH_DEV_MAX_ITEMS);
@@ -377,13 +382,22 @@ hipError_t mesh_emit_add(MeshEmit &E, size_t mi, bool built, MeshBvhScratch &S, 
 struct MeshUploadScratch { MeshBvhScratch &s; MeshEmit &e; ~MeshUploadScratch() { s.release(); e.release(); } };
 // One mesh's tree by the builder ycge_scene_upload picks: the device's (the same tree byte for byte) from YCGE_MESH_BVH_DEVICE_MIN triangles on - or always, when asked -
 // and the host's below that, under YCGE_MESH_BVH_HOST and for what the device builder declines (rep.fallback).  on_device: S holds the tree's triangles, nodes and leaf order.
-int build_mesh_tree(const Knobs &knobs, bool always_try_device, MeshBvhScratch &S, const float *tris9, int32_t n, hipStream_t stream, BuiltTree &t, bool &on_device, MeshBvhReport &rep);
+// d_tris9: the same soup where it already lies on the device (ycge_scene_attach_obj_mesh) - the device builder takes it from there by a device copy; with tris9 null the
+// answer is 1, nothing built, wherever the host builder would have to build.
+int build_mesh_tree(const Knobs &knobs, bool always_try_device, MeshBvhScratch &S, const float *tris9, int32_t n, hipStream_t stream, BuiltTree &t, bool &on_device, MeshBvhReport &rep,
+                    const float *d_tris9 = nullptr);
 // The arena of an upload's meshes - records in mesh order, then the treelets unless no_coop - written by the host from the trees (gmeshes[].root_ref), or by the device from
 // E's inputs into d_arena at its exact size (root_refs).  YCGE_OK or the error, its text in msg; the three refusals both share are worded in mesh_refusal alone.
 int emit_arena_on_host(const std::vector<MeshHost> &trees, const ycge_mesh *meshes, int n_materials, bool no_coop, std::vector<uint8_t> &arena, std::vector<GMesh> &gmeshes, uint32_t &tl_offset, std::string &msg);
 int emit_arena_on_device(MeshEmit &E, PinnedBuf &stage, DevBuf<uint8_t> &d_arena, int n_materials, bool no_coop, bool timed, hipStream_t stream, std::vector<uint32_t> &root_refs, uint32_t &tl_offset, std::string &msg);
 enum MeshRefusal { MESH_LEAF_ABOVE_15 = 0, MESH_TRI_MATERIAL = 1, MESH_ARENA_FULL = 2 };
 int mesh_refusal(MeshRefusal why, int mesh, std::string &msg);          // the refusal's code, its text into msg
+// the units of a tree's records as both emits lay them out (a leaf above 15 triangles has none: bad_leaf), and whether its root is a node
+uint32_t mesh_tree_units(const BuiltTree &t, bool &bad_leaf);
+// E's inputs written into a pooled arena of capacity_units units (tl_offset: its treelet region, 0 none): mesh k's records from unit base_units[k] on (units[k] of
+// them, as mesh_tree_units counts), the treelets of exactly these meshes' nodes.  The ranges lie inside the arena and hold zeros.  root_refs on return.
+int emit_meshes_into_arena(MeshEmit &E, PinnedBuf &stage, uint8_t *arena, uint32_t capacity_units, uint32_t tl_offset, const std::vector<uint32_t> &base_units, const std::vector<uint32_t> &units,
+                           int n_materials, hipStream_t stream, std::vector<uint32_t> &root_refs, std::string &msg);
 
 // The resident voxel grids of a scene (ycge_grid_encode.cpp): the grids of the last ycge_scene_upload keep their indices and its packing;
 // ycge_scene_attach_grids takes the lowest free index, a block of the cell arena (size-keyed free list, 256-byte alignment, else the end of
@@ -417,6 +431,24 @@ struct GridPool {
     int64_t n_resident = 0, growths = 0, slots_reused = 0, device_encodes = 0, host_encodes = 0;
     bool streamed = false;                   // an attach or a detach has changed the set since the last upload
     double last_attach_us[4] = {0, 0, 0, 0};  // the last attach: copy into the staging, host-to-device copy, encode kernel, read-back
+};
+
+// The resident meshes of a scene (ycge_mesh_pool.cpp): the meshes of the last ycge_scene_upload keep their indices and their records, laid
+// out exactly as the upload lays them out.  The first ycge_scene_attach_meshes re-homes the arena into an allocation with room -
+// [records: `capacity` units][treelets: capacity * YCGE_TL_BYTES_PER_UNIT bytes at the 512-aligned tl_offset] - where a record keeps its
+// unit and, the map from a node's unit to its treelet being linear, a treelet keeps its place behind tl_offset.  Kept by the root context;
+// every device of a multi-device context holds the same layout.
+struct MeshPool {
+    MeshRanges ranges;                       // units and indices handed out (ycge_mesh_pool.h)
+    std::vector<uint8_t> resident;           // per index: 1 = a mesh lives here (a prim may refer to it)
+    std::vector<uint64_t> first_unit;        // per index: where its records start
+    std::vector<uint32_t> units;             // per index: units of its records (0: a mesh without triangles)
+    bool pooled = false;                     // the arena has been re-homed: capacity / tl_offset describe d_mesh_arena
+    bool treelets = false;                   // a pooled arena has a treelet region (not under YCGE_NO_COOP, not behind an upload too large for one)
+    uint64_t capacity = 0;                   // units of records the pooled arena has room for
+    uint32_t tl_offset = 0;                  // where the treelet region starts: the upload's, then the pooled arena's (0: none)
+    int64_t n_resident = 0, units_in_use = 0, growths = 0, device_builds = 0, host_builds = 0;
+    double last_attach_us[3] = {0, 0, 0};    // the last attach: the trees, the emit (layout, records, treelets, read-backs), the copies (re-homing, growth, peers)
 };
 
 } // namespace ycge_host
@@ -784,6 +816,8 @@ struct ycge_ctx {
     DevBuf<GMesh> d_meshes;
     DevBuf<GGrid> d_grids;
     GridPool grid_pool;                // (root context)
+    MeshPool mesh_pool;                // (root context)
+    bool pending_transparent = false, pending_textured = false;          // (root) of ycge_scene_append_materials: SceneDev's flags follow with the next install of the objects
     std::map<std::string, std::weak_ptr<const LookupTable>> lookup_tables;   // (root) the interned lookup tables of the resident grids, by their bytes
     std::vector<ycge_prim> last_prims;  // (root) the object list the last ycge_scene_upload / ycge_scene_update_objects accepted: an edit that changes a held grid's record installs it again
     // ycge_scene_attach_grids: the batch's descriptors, results, lookup tables and raw cells in page-locked memory (root) and on this
@@ -967,6 +1001,16 @@ void grid_record_solid(GGrid &G, const int lo[3], const int hi[3], uint64_t bric
 std::array<float, 6> grid_world_bounds(const ycge_grid &g);
 int encode_grid_host(ycge_ctx *c, const ycge_grid &g, int gi, int n_materials, const GGrid &G, uint8_t *cells, std::vector<int32_t> &lut, int lo[3], int hi[3],
                      uint64_t &brick_mask, std::vector<std::pair<int32_t, int32_t>> *seen_out = nullptr);   // the host encoder (first-seen codes; seen_out: the pairs in code order)
+// ycge_mesh_pool.cpp: the pool's view of an upload (every mesh of it resident in mesh order, nothing free), what the next install of the objects publishes,
+// and the bodies of ycge_scene_attach_meshes / _detach_meshes / _append_materials / ycge_debug_mesh_pool_stats (arguments checked there)
+void mesh_pool_reset(ycge_ctx *c, uint32_t tl_offset);
+void mesh_pool_publish(ycge_ctx *c);
+int scene_attach_meshes(ycge_ctx *c, const ycge_mesh *meshes, int32_t n, int32_t *out_mesh_index);
+int scene_attach_device_soup(ycge_ctx *c, const float *d_tris9, int32_t n_triangles, int32_t material, int32_t *out_mesh_index);   // one mesh whose soup lies on the root's device
+int scene_detach_meshes(ycge_ctx *c, const int32_t *mesh_index, int32_t n);
+int scene_append_materials(ycge_ctx *c, const ycge_material *materials, int32_t n, int32_t *out_first_index);
+int mesh_pool_stats(ycge_ctx *c, int64_t *out12);
+void flatten_material(const ycge_material &m, GMaterial &g, bool &any_transparent, bool &any_textured);          // ycge_scene.cpp: one material's device record
 void grid_pool_reset(ycge_ctx *c, const std::vector<GGrid> &recs, size_t arena_bytes, size_t lut_entries, std::vector<SlotCodes> codes = {});   // ycge_grid_encode.cpp: after an upload
 // ycge_grid_edit.cpp: how edits code the pairs of grid g (a grid of `root`'s scene; lut: a host-encoded grid's table, entry 0 first), the interned copy of a lookup table,
 // and the bodies of ycge_scene_edit_voxels / ycge_world_store_edit's argument checks
@@ -1021,6 +1065,8 @@ int obj_stats(ycge_ctx *c, int64_t *out6);
 int obj_ground_host(const float *positions, int32_t n_positions, const int32_t *faces, int32_t n_triangles, ycge_obj_ground_info *out);
 int obj_ground(ycge_ctx *c, ycge_obj_ground_info *out);
 int obj_triangles_auto_ground(ycge_ctx *c, float scale, const float target[3], float *out_triangles, float out_bounds[6], ycge_obj_ground_info *out_info);
+int obj_attach_mesh(ycge_ctx *c, int32_t auto_ground, int32_t normalize, float target_size, float scale, const float translate_or_target[3], int32_t material,
+                    int32_t *out_mesh_index, float out_bounds[6]);          // ... and of ycge_scene_attach_obj_mesh
 int obj_ground_stats(ycge_ctx *c, int64_t *out6);
 int obj_ground_phases(ycge_ctx *c, int64_t *out5);
 // ycge_world_store.cpp: the bodies of ycge_world_file_info (no context), ycge_world_store_load / _info / _release, ycge_scene_attach_world_chunks and the hooks

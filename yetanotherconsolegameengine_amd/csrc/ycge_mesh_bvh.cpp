@@ -29,7 +29,7 @@ hipError_t staged_read(PinnedBuf &stage, void *dst, const void *src, size_t byte
 } // namespace
 
 // YCGE_OK: `out` is the host builder's tree of tris9, byte for byte; 1: not built, rep.fallback says why; YCGE_ERR_*: rep.error
-static int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int wide_min, hipStream_t stream, BuiltTree &out, MeshBvhReport &rep)
+static int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t n, int wide_min, hipStream_t stream, BuiltTree &out, MeshBvhReport &rep, bool tris_on_device = false)
 {
     out = BuiltTree{};
     rep = MeshBvhReport{};
@@ -50,7 +50,7 @@ static int mesh_bvh_build_device(MeshBvhScratch &S, const float *tris9, int32_t 
     MESH_TRY(S.node_of.reserve(N)); MESH_TRY(S.level[0].reserve(level_cap)); MESH_TRY(S.level[1].reserve(level_cap)); MESH_TRY(S.jobs.reserve(top_cap));
     MESH_TRY(S.flag.reserve(N)); MESH_TRY(S.top.reserve(top_cap * top_bytes)); MESH_TRY(S.acc.reserve(level_cap * acc_bytes));
     MESH_TRY(S.sub_nodes.reserve(2 * N * sub_bytes)); MESH_TRY(S.nodes.reserve(2 * N * sizeof(RefNode)));
-    MESH_TRY(hipMemcpyAsync(S.tris.p, tris9, 9 * N * sizeof(float), hipMemcpyHostToDevice, stream));
+    MESH_TRY(hipMemcpyAsync(S.tris.p, tris9, 9 * N * sizeof(float), tris_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
     MESH_TRY(hipMemsetAsync(S.hdr.p, 0, MH_WORDS * 4, stream));
     MESH_TRY(hipStreamSynchronize(stream));
     const auto t0 = std::chrono::steady_clock::now();
@@ -102,15 +102,17 @@ static void host_mesh_tree(const float *tris9, int32_t n, BuiltTree &t)
     build_tree(items, TreeFlavour::Mesh, t);
 }
 
-int build_mesh_tree(const Knobs &knobs, bool always_try_device, MeshBvhScratch &S, const float *tris9, int32_t n, hipStream_t stream, BuiltTree &t, bool &on_device, MeshBvhReport &rep)
+int build_mesh_tree(const Knobs &knobs, bool always_try_device, MeshBvhScratch &S, const float *tris9, int32_t n, hipStream_t stream, BuiltTree &t, bool &on_device, MeshBvhReport &rep,
+                    const float *d_tris9)
 {
     rep = MeshBvhReport{};
     on_device = always_try_device || (!knobs.mesh_bvh_host && n >= 1 && n >= knobs.mesh_bvh_device_min);
     if (on_device) {
-        const int rc = mesh_bvh_build_device(S, tris9, n, knobs.mesh_bvh_wide_min, stream, t, rep);
+        const int rc = mesh_bvh_build_device(S, d_tris9 ? d_tris9 : tris9, n, knobs.mesh_bvh_wide_min, stream, t, rep, d_tris9 != nullptr);
         if (rc < 0) return rc;
         on_device = rc == YCGE_OK;
     }
+    if (!on_device && !tris9 && n > 0) return 1;          // (a soup that lives on the device alone: the caller reads it back and asks again)
     if (!on_device) host_mesh_tree(tris9, n, t);
     return YCGE_OK;
 }
@@ -168,8 +170,9 @@ hipError_t mesh_emit_add(MeshEmit &E, size_t mi, bool built, MeshBvhScratch &S, 
     return e;
 }
 
-// every mesh's layout; hdr_host on return (stage: the builder's page-locked staging)
-static hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t stream)
+// every mesh's layout; hdr_host on return (stage: the builder's page-locked staging).  base_units == null: the meshes lie one behind the
+// other from unit 0 (an upload); else mesh mi lies from unit base_units[mi] on (a pooled arena: the header's unit count is preset to it)
+static hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t stream, const uint32_t *base_units = nullptr)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_hdr = EH_MESH0 + EH_MESH_WORDS * E.in.size();
@@ -188,6 +191,7 @@ static hipError_t mesh_emit_layout(MeshEmit &E, PinnedBuf &stage, hipStream_t st
     for (size_t mi = 0; mi < E.in.size(); mi++) {
         const MeshEmit::Input &I = E.in[mi];
         if (I.n_nodes == 0) continue;
+        if (base_units && (e = hipMemsetD32Async((hipDeviceptr_t)(E.hdr.p + EH_UNITS), (int)base_units[mi], 1, stream)) != hipSuccess) return e;
         if ((e = (hipError_t)ycge_launch_mesh_emit_layout(I.nodes.p, I.n_nodes, (uint32_t)mi, E.tiles.p, E.refs.p + I.first_ref, E.hdr.p, stream)) != hipSuccess) return e;
     }
     E.hdr_host.assign(n_hdr, 0u);
@@ -373,6 +377,47 @@ int emit_arena_on_device(MeshEmit &E, PinnedBuf &stage, DevBuf<uint8_t> &d_arena
     return YCGE_OK;
 }
 
+uint32_t mesh_tree_units(const BuiltTree &t, bool &bad_leaf)
+{
+    uint64_t units = 0;
+    bad_leaf = false;
+    if (t.root < 0) return 0;
+    for (const RefNode &nd : t.nodes) {
+        if (nd.count > 15) bad_leaf = true;
+        else units += nd.count > 0 ? 3u * (((uint32_t)nd.count + 1u) / 2u) : 2u;
+    }
+    return units > 0xffffffffull ? 0xffffffffu : (uint32_t)units;
+}
+
+// The meshes E holds written into an arena that exists (ycge_scene_attach_meshes): the same kernels as emit_arena_on_device, each mesh behind
+// its own base unit, the records bounded by the arena's capacity, the treelets of these meshes' nodes alone
+int emit_meshes_into_arena(MeshEmit &E, PinnedBuf &stage, uint8_t *arena, uint32_t capacity_units, uint32_t tl_offset, const std::vector<uint32_t> &base_units, const std::vector<uint32_t> &units,
+                           int n_materials, hipStream_t stream, std::vector<uint32_t> &root_refs, std::string &msg)
+{
+    char buf[256];
+    auto hip_bad = [&](const char *what, hipError_t e) {
+        (void)hipGetLastError();
+        std::snprintf(buf, sizeof buf, "%s failed: %s", what, hipGetErrorString(e)); msg = buf;
+        return e == hipErrorOutOfMemory ? YCGE_ERR_OUT_OF_MEMORY : YCGE_ERR_DEVICE;
+    };
+    const size_t n = E.in.size();
+    root_refs.assign(n, YCGE_REF_NONE_VALUE);
+    hipError_t e = mesh_emit_layout(E, stage, stream, base_units.data());
+    if (e != hipSuccess) return hip_bad("the mesh record layout", e);
+    for (size_t mi = 0; mi < n; mi++) {
+        const MeshEmit::Input &I = E.in[mi];
+        const uint32_t *h = E.hdr_host.data() + EH_MESH0 + EH_MESH_WORDS * mi;
+        if (h[1]) return mesh_refusal(MESH_LEAF_ABOVE_15, (int)mi, msg);
+        if (I.n_nodes == 0) continue;
+        if (h[0] != units[mi] || (uint64_t)base_units[mi] + units[mi] > capacity_units) { msg = "the mesh record layout disagrees with the host's count"; return YCGE_ERR_INTERNAL; }
+        root_refs[mi] = I.root_count > 0 ? YCGE_REF(REF_MESH_LEAF, (base_units[mi] << 4) | (uint32_t)I.root_count) : YCGE_REF(REF_MESH_NODE, base_units[mi] << 4);
+    }
+    if ((e = mesh_emit_write(E, arena, capacity_units, 0, tl_offset, n_materials, false, stage, stream)) != hipSuccess) return hip_bad("the mesh records on the device", e);
+    for (size_t mi = 0; mi < n; mi++)
+        if (E.hdr_host[EH_MESH0 + EH_MESH_WORDS * mi + 2]) return mesh_refusal(MESH_TRI_MATERIAL, (int)mi, msg);
+    return YCGE_OK;
+}
+
 // a hook's read of what c's device holds at src, into dst (null: nothing to read) once the device is idle
 static int read_idle_device(ycge_ctx *c, void *dst, const void *src, size_t bytes)
 {
@@ -533,6 +578,27 @@ try {
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(c); }
+
+// test / profiling hook: the resident meshes of the context's scene - {resident meshes, free indices, units of records in use, capacity in units
+// (before the first attach: the uploaded records), growths of the pooled arena, ranges reused, device builds, host builds of the attaches, then the
+// last attach in microseconds: the trees, the emit, the copies (re-homing, growth, other devices), and 1 once the arena is pooled}
+int ycge_debug_mesh_pool_stats(ycge_ctx *c, int64_t *out12)
+try {
+    if (!c || !out12) return YCGE_ERR_INVALID_ARG;
+    return mesh_pool_stats(c, out12);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook, no context and no device: the pool's allocator of unit ranges and mesh indices (MeshRanges, ycge_mesh_pool.h) run through n_ops
+// triples {op, a, b} from `end0` units of records and `n_index0` indices - 0: take a units, 1: give back the b units at unit a, 2: take an
+// index, 3: give back index a.  out: per op {the take's answer, the records' end, free ranges, free units}
+int ycge_debug_mesh_ranges(int64_t end0, int32_t n_index0, const int64_t *ops, int32_t n_ops, int64_t *out)
+try {
+    if (end0 < 0 || n_index0 < 0 || n_ops < 0 || (n_ops > 0 && (!ops || !out))) return YCGE_ERR_INVALID_ARG;
+    mesh_ranges_run(end0, n_index0, ops, n_ops, out);
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
 
 // ---- host-only helpers exported for the `-m "not gpu"` tests (no device needed) -------------
 // Build a tree over caller-supplied boxes with the product builder: bounds = n*6 (min xyz, max xyz),

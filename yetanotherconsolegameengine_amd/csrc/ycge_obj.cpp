@@ -239,10 +239,9 @@ int obj_read(ycge_ctx *c, float *positions, int32_t *faces)
     return rc;
 }
 
-int obj_triangles(ycge_ctx *c, int32_t normalize, float target_size, float scale, const float translate[3], float *out_triangles, float out_bounds[6])
+// the placed soup of the held OBJ into O.triangles on the device (k_obj_triangles), its box into out_bounds (or NULL)
+static int obj_triangles_on_device(ycge_ctx *c, int32_t normalize, float target_size, float scale, const float translate[3], float out_bounds[6])
 {
-    { const int rc = obj_held(c, "ycge_obj_triangles"); if (rc != YCGE_OK) return rc; }
-    if (!out_triangles) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_obj_triangles: out_triangles is NULL");
     ObjState &O = c->obj;
     const float zero[3] = {0.0f, 0.0f, 0.0f};
     const float *t = translate ? translate : zero;
@@ -269,7 +268,15 @@ int obj_triangles(ycge_ctx *c, int32_t normalize, float target_size, float scale
     { const int rc = read_header(c, h); if (rc != YCGE_OK) return rc; }
     O.last_us[2] = us_since(t0);
     if (out_bounds) decode_box(h.tri_box, out_bounds, out_bounds + 3);
-    return copy_out(c, out_triangles, O.triangles.p, (size_t)9 * O.n_triangles * sizeof(float));
+    return YCGE_OK;
+}
+
+int obj_triangles(ycge_ctx *c, int32_t normalize, float target_size, float scale, const float translate[3], float *out_triangles, float out_bounds[6])
+{
+    { const int rc = obj_held(c, "ycge_obj_triangles"); if (rc != YCGE_OK) return rc; }
+    if (!out_triangles) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_obj_triangles: out_triangles is NULL");
+    { const int rc = obj_triangles_on_device(c, normalize, target_size, scale, translate, out_bounds); if (rc != YCGE_OK) return rc; }
+    return copy_out(c, out_triangles, c->obj.triangles.p, (size_t)9 * c->obj.n_triangles * sizeof(float));
 }
 
 int obj_release(ycge_ctx *c)
@@ -403,11 +410,9 @@ int obj_ground(ycge_ctx *c, ycge_obj_ground_info *out)
     return YCGE_OK;
 }
 
-int obj_triangles_auto_ground(ycge_ctx *c, float scale, const float target[3], float *out_triangles, float out_bounds[6], ycge_obj_ground_info *out_info)
+// AddMeshAutoGround's placement of the held OBJ (the tail, then the soup on the device)
+static int obj_auto_ground_on_device(ycge_ctx *c, float scale, const float target[3], float out_bounds[6], ycge_obj_ground_info *out_info)
 {
-    if (out_info) std::memset(out_info, 0, sizeof *out_info);
-    { const int rc = obj_held(c, "ycge_obj_triangles_auto_ground"); if (rc != YCGE_OK) return rc; }
-    if (!out_triangles || !target) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_obj_triangles_auto_ground: %s is NULL", out_triangles ? "target" : "out_triangles");
     ycge_obj_ground_info g;
     { const int rc = obj_ground(c, &g); if (rc != YCGE_OK) return rc; }
     if (out_info) *out_info = g;
@@ -415,7 +420,37 @@ int obj_triangles_auto_ground(ycge_ctx *c, float scale, const float target[3], f
     const float lifted = g.min[1] * scale;
     const float y_translate = (target[1] - lifted) + 0.01f;
     const float translate[3] = {target[0], y_translate, target[2]};
-    return obj_triangles(c, 1, 1.0f, scale, translate, out_triangles, out_bounds);
+    return obj_triangles_on_device(c, 1, 1.0f, scale, translate, out_bounds);
+}
+
+int obj_triangles_auto_ground(ycge_ctx *c, float scale, const float target[3], float *out_triangles, float out_bounds[6], ycge_obj_ground_info *out_info)
+{
+    if (out_info) std::memset(out_info, 0, sizeof *out_info);
+    { const int rc = obj_held(c, "ycge_obj_triangles_auto_ground"); if (rc != YCGE_OK) return rc; }
+    if (!out_triangles || !target) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_obj_triangles_auto_ground: %s is NULL", out_triangles ? "target" : "out_triangles");
+    { const int rc = obj_auto_ground_on_device(c, scale, target, out_bounds, out_info); if (rc != YCGE_OK) return rc; }
+    return copy_out(c, out_triangles, c->obj.triangles.p, (size_t)9 * c->obj.n_triangles * sizeof(float));
+}
+
+// ycge_scene_attach_obj_mesh: the placed soup stays where k_obj_triangles wrote it and goes to the tree builder from there (ycge_mesh_pool.cpp)
+int obj_attach_mesh(ycge_ctx *c, int32_t auto_ground, int32_t normalize, float target_size, float scale, const float translate_or_target[3], int32_t material,
+                    int32_t *out_mesh_index, float out_bounds[6])
+{
+    { const int rc = obj_held(c, "ycge_scene_attach_obj_mesh"); if (rc != YCGE_OK) return rc; }
+    if (!out_mesh_index || (auto_ground && !translate_or_target))
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_attach_obj_mesh: %s is NULL", out_mesh_index ? "the target" : "out_mesh_index");
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    if (material < 0 || material >= c->n_materials) return c->fail(YCGE_ERR_INVALID_ARG, "mesh 0: material out of range");
+    float bounds[6] = {0, 0, 0, 0, 0, 0};
+    const int prc = auto_ground ? obj_auto_ground_on_device(c, scale, translate_or_target, bounds, nullptr)
+                                : obj_triangles_on_device(c, normalize, target_size, scale, translate_or_target, bounds);
+    if (prc != YCGE_OK) return prc;
+    int32_t index = -1;
+    const int rc = scene_attach_device_soup(c, c->obj.triangles.p, c->obj.n_triangles, material, &index);
+    if (rc != YCGE_OK) return rc;
+    *out_mesh_index = index;
+    if (out_bounds) for (int a = 0; a < 6; a++) out_bounds[a] = bounds[a];
+    return YCGE_OK;
 }
 
 int obj_ground_stats(ycge_ctx *c, int64_t *out6)

@@ -486,30 +486,31 @@ int install_scene(ycge_ctx *c, const SceneArrays &A, const ObjectsHost &oh, cons
 
 // ---- the steps of ycge_scene_upload, in its order: each fills its part of A (the last ones: of the root context) or fails with the error's text on c
 
+void flatten_material(const ycge_material &m, GMaterial &g, bool &any_transparent, bool &any_textured)
+{
+    std::memset(&g, 0, sizeof g);
+    g.kind = m.kind;
+    g.albedo[0] = m.albedo.x; g.albedo[1] = m.albedo.y; g.albedo[2] = m.albedo.z;
+    g.albedo_b[0] = m.albedo_b.x; g.albedo_b[1] = m.albedo_b.y; g.albedo_b[2] = m.albedo_b.z;
+    g.checker_scale = m.checker_scale;
+    g.reflectivity = m.reflectivity;
+    g.emission[0] = m.emission.x; g.emission[1] = m.emission.y; g.emission[2] = m.emission.z;
+    g.transparency = m.transparency; g.ior = m.index_of_refraction;
+    g.trans_color[0] = m.transmission_color.x; g.trans_color[1] = m.transmission_color.y; g.trans_color[2] = m.transmission_color.z;
+    if (m.transparency > 0.0f) any_transparent = true;
+    g.tex = -1;
+    if (m.kind == YCGE_MAT_TEXTURED && m.texture_weight > 0.0) {     // SampleAlbedo, RaytraceRenderer.cs:726-733 (a weight <= 0: the plain albedo)
+        g.tex = m.texture;
+        any_textured = true;
+        g.tex_tiles = (float)(m.uv_scale > 1e-6 ? m.uv_scale : 1e-6);                                            // (float)Math.Max(1e-6, mat.UVScale)
+        g.tex_t = (float)(m.texture_weight < 0.0 ? 0.0 : m.texture_weight > 1.0 ? 1.0 : m.texture_weight);       // (float)Math.Clamp(mat.TextureWeight, 0.0, 1.0)
+    }
+}
+
 int flatten_materials(const ycge_scene *s, SceneArrays &A)
 {
     A.mats.assign(s->n_materials, GMaterial{});
-    for (int i = 0; i < s->n_materials; i++) {
-        const ycge_material &m = s->materials[i];
-        GMaterial &g = A.mats[i];
-        std::memset(&g, 0, sizeof g);
-        g.kind = m.kind;
-        g.albedo[0] = m.albedo.x; g.albedo[1] = m.albedo.y; g.albedo[2] = m.albedo.z;
-        g.albedo_b[0] = m.albedo_b.x; g.albedo_b[1] = m.albedo_b.y; g.albedo_b[2] = m.albedo_b.z;
-        g.checker_scale = m.checker_scale;
-        g.reflectivity = m.reflectivity;
-        g.emission[0] = m.emission.x; g.emission[1] = m.emission.y; g.emission[2] = m.emission.z;
-        g.transparency = m.transparency; g.ior = m.index_of_refraction;
-        g.trans_color[0] = m.transmission_color.x; g.trans_color[1] = m.transmission_color.y; g.trans_color[2] = m.transmission_color.z;
-        if (m.transparency > 0.0f) A.any_transparent = true;
-        g.tex = -1;
-        if (m.kind == YCGE_MAT_TEXTURED && m.texture_weight > 0.0) {     // SampleAlbedo, RaytraceRenderer.cs:726-733 (a weight <= 0: the plain albedo)
-            g.tex = m.texture;
-            A.any_textured = true;
-            g.tex_tiles = (float)(m.uv_scale > 1e-6 ? m.uv_scale : 1e-6);                                            // (float)Math.Max(1e-6, mat.UVScale)
-            g.tex_t = (float)(m.texture_weight < 0.0 ? 0.0 : m.texture_weight > 1.0 ? 1.0 : m.texture_weight);       // (float)Math.Clamp(mat.TextureWeight, 0.0, 1.0)
-        }
-    }
+    for (int i = 0; i < s->n_materials; i++) flatten_material(s->materials[i], A.mats[i], A.any_transparent, A.any_textured);
     return YCGE_OK;
 }
 
@@ -541,6 +542,7 @@ int build_mesh_arena(ycge_ctx *c, const ycge_scene *s, SceneArrays &A)
     MeshEmit &E = c->mesh_emit;
     MeshUploadScratch scratch_of_this_upload{c->mesh_bvh, E};
     c->meshes.assign(s->n_meshes, MeshHost{});
+    c->mesh_pool = MeshPool{};          // (the pool describes c->meshes: nothing is resident until this upload is remembered)
     A.gmeshes.assign(s->n_meshes, GMesh{});
     c->mesh_bvh_sorts = c->mesh_bvh_depth = c->mesh_bvh_wide_nodes = c->mesh_bvh_jobs = 0;
     c->mesh_emit_dev_meshes = c->mesh_emit_host_meshes = c->mesh_emit_arena_bytes = 0; c->mesh_emit_last_us = 0.0;
@@ -644,6 +646,7 @@ int remember_for_updates(ycge_ctx *c, const ycge_scene *s, SceneArrays &A)
     }
     A.has_grid = s->n_grids > 0;
     grid_pool_reset(c, A.ggrids, A.cells.size(), A.lut.size(), std::move(A.codes));          // (ycge_grid_encode.cpp: every grid of the upload is resident, nothing is free)
+    mesh_pool_reset(c, A.tl_offset);                                                         // (ycge_mesh_pool.cpp: likewise every mesh)
     return YCGE_OK;
 }
 
@@ -778,6 +781,48 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// Meshes and materials of a resident scene (the pool and the bodies: ycge_mesh_pool.cpp; the contract: include/ycge.h)
+int ycge_scene_attach_meshes(ycge_ctx *c, const ycge_mesh *meshes, int32_t n, int32_t *out_mesh_index)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    if (n < 0 || (n > 0 && (!meshes || !out_mesh_index))) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_attach_meshes: bad array (n = %d)", n);
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    if (n == 0) return YCGE_OK;
+    return ycge_host::scene_attach_meshes(c, meshes, n, out_mesh_index);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_scene_detach_meshes(ycge_ctx *c, const int32_t *mesh_index, int32_t n)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    if (n < 0 || (n > 0 && !mesh_index)) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_detach_meshes: bad array (n = %d)", n);
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    if (n == 0) return YCGE_OK;
+    return ycge_host::scene_detach_meshes(c, mesh_index, n);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_scene_append_materials(ycge_ctx *c, const ycge_material *materials, int32_t n, int32_t *out_first_index)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (c->parent) return c->fail(YCGE_ERR_INVALID_ARG, "peer contexts are driven by their root");
+    if (n < 0 || (n > 0 && (!materials || !out_first_index))) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_scene_append_materials: bad array (n = %d)", n);
+    if (!c->have_scene) return c->fail(YCGE_ERR_NO_SCENE, "no scene uploaded");
+    if (n == 0) return YCGE_OK;
+    return ycge_host::scene_append_materials(c, materials, n, out_first_index);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_scene_attach_obj_mesh(ycge_ctx *c, int32_t auto_ground, int32_t normalize, float target_size, float scale, const float translate_or_target[3],
+                               int32_t material, int32_t *out_mesh_index, float out_bounds[6])
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return ycge_host::obj_attach_mesh(c, auto_ground, normalize, target_size, scale, translate_or_target, material, out_mesh_index, out_bounds);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 } // extern "C"
 
 // the body of ycge_scene_update_objects, also what ycge_scene_edit_voxels ends with when a held grid's record changed (with the kept list)
@@ -818,6 +863,7 @@ int ycge_host::update_objects(ycge_ctx *c, const ycge_prim *prims, int32_t n_pri
     c->bvh_last_build_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     (void)hipSetDevice(c->device);
     if (rc != YCGE_OK) return rc;
+    mesh_pool_publish(c);          // (what streamed meshes and appended materials change in SceneDev follows here, with the objects that may use them: once they are installed)
     c->grid_pool.owner.swap(oh.grid_owner);
     c->have_scene = true;
     return query_scene_changed(c);

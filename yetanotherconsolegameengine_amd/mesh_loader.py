@@ -165,3 +165,13 @@ def add_mesh_auto_ground_device(renderer, data, scale: float, target_pos) -> np.
     the largest component, its centroid and bounds against the held OBJ and places the triangles - no geometry comes back before them."""
     renderer.ParseObj(data)
     return renderer.ObjTrianglesAutoGround(scale, target_pos)[0]
+
+
+def attach_obj_device(renderer, data, material, scale: float = 1.0, translate=(0.0, 0.0, 0.0), normalize: bool = True, target_size: float = 1.0,
+                      auto_ground: bool = False, target_pos=None):
+    """An OBJ file added to the RESIDENT scene as a mesh of `material` (a Material the library holds, or its index): ParseObj, then one call
+    (RaytraceRenderer.AttachObjMesh) that places the triangles as from_obj_device - or, with auto_ground, add_mesh_auto_ground_device at
+    target_pos - places them and hands them to the tree builder where they lie.  Returns (device mesh index, bounds f32 [6]); the next
+    UpdateObjects may refer to the index."""
+    renderer.ParseObj(data)
+    return renderer.AttachObjMesh(material, scale=scale, translate=translate, normalize=normalize, target_size=target_size, auto_ground=auto_ground, target_pos=target_pos)

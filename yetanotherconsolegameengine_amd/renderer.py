@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import abi
-from .scene import FlatScene, NeedsUpload, Scene, VolumeGrid, flatten, grid_record
+from .scene import FlatScene, Mesh, NeedsUpload, Scene, VolumeGrid, flatten, grid_record, material_record, mesh_record
 
 NODE_DTYPE = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"), ("count", "<i4")])
 
@@ -90,6 +90,7 @@ class RaytraceRenderer:
         self._pos, self._yaw, self._pitch, self._fov = (0.0, 1.0, 0.0), 0.0, 0.0, fovDeg
         self.flat = None
         self._streamed = {}          # id -> VolumeGrid attached by AttachGrids and still resident
+        self._streamed_meshes = {}   # id -> Mesh attached by AttachMeshes and still resident
         self.stream_call_s = {"attach": 0.0, "update": 0.0, "detach": 0.0}          # seconds inside the last library call of each kind (profiles/stream_rate.py)
         self.stats = abi.FrameStats()
         if scene is not None:
@@ -131,6 +132,7 @@ class RaytraceRenderer:
         """scene.RebuildBVH() + upload (RaytraceRenderer.cs:107, RaytraceEntity.cs:244)."""
         self.flat = scene if hasattr(scene, "byref") else flatten(scene)          # (a FlatScene, or a scene file read back: tools/scene_file.py)
         self._streamed = {}          # (the next upload forgets every attached grid)
+        self._streamed_meshes = {}   # (... and every attached mesh)
         self._check(self.L.ycge_scene_upload(self.ctx, self.flat.byref()))
 
     def UpdateLights(self, lights, ambient=None, background_top=None, background_bottom=None):
@@ -163,23 +165,42 @@ class RaytraceRenderer:
         self.flat = f
 
     # ---------------------------------------------------------------- chunk streaming (ycge_scene_attach_grids / ycge_scene_detach_grids)
-    def AttachGrids(self, grids) -> list:
-        """Makes the VolumeGrids resident beside those of the upload and returns their device indices; no object refers to them until
-        the next UpdateObjects / StreamObjects.  Their materials must be materials of the uploaded scene (NeedsUpload otherwise)."""
-        grids = list(grids)
-        if not grids:
-            return []
+    def _material_numbering(self, append_new: bool):
+        """(mat_id, finish): mat_id numbers a Material against those the library holds - one it does not hold raises NeedsUpload, or, with
+        append_new, takes the next index behind them; finish() then appends those, once the records that name them are made."""
         if not hasattr(self.flat, "_mat_index"):
             raise NeedsUpload("the uploaded scene was not flattened from a Scene: its materials cannot be matched")
         mat_index = self.flat._mat_index
+        base, new, provisional = len(mat_index), [], {}
 
         def mat_id(m):
-            if id(m) not in mat_index:
+            if id(m) in mat_index:
+                return mat_index[id(m)]
+            if not append_new:
                 raise NeedsUpload("a material the uploaded scene does not hold")
-            return mat_index[id(m)]
+            if id(m) not in provisional:
+                provisional[id(m)] = base + len(new)
+                new.append(m)
+            return provisional[id(m)]
 
+        def finish():
+            if new:
+                first = self.AppendMaterials(new)
+                assert first == base, (first, base)
+
+        return mat_id, finish
+
+    def AttachGrids(self, grids, append_new_materials: bool = False) -> list:
+        """Makes the VolumeGrids resident beside those of the upload and returns their device indices; no object refers to them until
+        the next UpdateObjects / StreamObjects.  Their materials must be materials the library holds (NeedsUpload otherwise) - or, with
+        append_new_materials, the ones it does not hold are appended first (AppendMaterials), as the records of these grids name them."""
+        grids = list(grids)
+        if not grids:
+            return []
+        mat_id, append_new = self._material_numbering(append_new_materials)
         keep = []
         recs = (abi.Grid * len(grids))(*[grid_record(g, mat_id, keep) for g in grids])
+        append_new()
         out = (C.c_int32 * len(grids))()
         t0 = time.perf_counter()
         rc = self.L.ycge_scene_attach_grids(self.ctx, recs, len(grids), out)
@@ -499,18 +520,137 @@ class RaytraceRenderer:
     def StreamObjects(self, scene: Scene, keep_cached: bool = False):
         """The Scene.Update that follows WorldManager.LoadChunksAround: the scene's VolumeGrid objects (by identity) against the resident
         ones - attach the new, UpdateObjects with the references mapped to device indices, detach what no longer appears (or keep it
-        resident and unreferenced when keep_cached: the reference's chunk cache).  Returns (attached indices, detached indices)."""
+        resident and unreferenced when keep_cached: the reference's chunk cache).  Returns (attached indices, detached indices).
+        Mesh objects are streamed the same way, and Materials the library does not hold yet are appended first - those of the analytic
+        objects, and those the records of the NEW grids and meshes name; a resident grid or mesh is not looked at again (a texture the upload
+        did not hold still raises NeedsUpload); what was attached and detached of them: self.streamed_meshes = (attached, detached)."""
         resident = self.flat._grid_index
-        self.stream_call_s.update(attach=0.0, update=0.0, detach=0.0)
+        resident_meshes = self.flat._mesh_index
+        self.stream_call_s.update(attach=0.0, update=0.0, detach=0.0, attach_meshes=0.0, detach_meshes=0.0)
+        new_mats = self._analytic_materials_not_held(scene)
+        if new_mats:
+            self.AppendMaterials(new_mats)
         wanted = [o for o in scene.Objects if isinstance(o, VolumeGrid)]
-        attached = self.AttachGrids([o for o in wanted if id(o) not in resident])
+        wanted_meshes = [o for o in scene.Objects if isinstance(o, Mesh)]
+        attached = self.AttachGrids([o for o in wanted if id(o) not in resident], append_new_materials=True)
+        new_meshes, seen = [], set()
+        for o in wanted_meshes:
+            if id(o) not in resident_meshes and id(o) not in seen:
+                seen.add(id(o)); new_meshes.append(o)
+        attached_meshes = self.AttachMeshes(new_meshes, append_new_materials=True)
         self.UpdateObjects(scene)
-        detached = []
+        detached, detached_meshes = [], []
         if not keep_cached:
             live = {id(o) for o in wanted}
             detached = sorted(i for k, i in resident.items() if k not in live)
             self.DetachGrids(detached)
+            live = {id(o) for o in wanted_meshes}
+            detached_meshes = sorted(i for k, i in resident_meshes.items() if k not in live)
+            self.DetachMeshes(detached_meshes)
+        self.streamed_meshes = (attached_meshes, detached_meshes)
         return attached, detached
+
+    def _analytic_materials_not_held(self, scene: Scene) -> list:
+        """the Materials of the scene's analytic objects the library does not hold yet, in first-use order (grids and meshes: their
+        records name what they need when they are attached - a resident one is not looked at again)"""
+        held = getattr(self.flat, "_mat_index", None)
+        if held is None:
+            return []
+        out, seen = [], set()
+        for o in scene.Objects:
+            if isinstance(o, (VolumeGrid, Mesh)):
+                continue
+            for m in (getattr(o, "Mat", None), getattr(o, "MaterialFunc", None)):
+                if m is not None and id(m) not in held and id(m) not in seen:
+                    seen.add(id(m)); out.append(m)
+        return out
+
+    # ---------------------------------------------------------------- meshes and materials of a resident scene (ycge_scene_attach_meshes / _detach_meshes / _append_materials)
+    def AppendMaterials(self, materials) -> int:
+        """New Materials behind those of the uploaded scene; returns the first new index (and numbers them in flat._mat_index).  A textured
+        one must use a texture of the uploaded scene (NeedsUpload otherwise).  The next UpdateObjects / StreamObjects publishes what the
+        longer list changes (a transparent, textured or mirroring material)."""
+        materials = list(materials)
+        if not hasattr(self.flat, "_mat_index"):
+            raise NeedsUpload("the uploaded scene was not flattened from a Scene: its materials cannot be matched")
+        if not materials:
+            return len(self.flat._mat_index)
+
+        def texture_id(t) -> int:
+            for i, have in enumerate(self.flat.texture_objects):
+                if have is t:
+                    return i
+            raise NeedsUpload("a texture the uploaded scene does not hold")
+
+        recs = (abi.Material * len(materials))(*[material_record(m, texture_id) for m in materials])
+        first = C.c_int32(-1)
+        self._check(self.L.ycge_scene_append_materials(self.ctx, recs, len(materials), C.byref(first)))
+        for k, m in enumerate(materials):
+            self.flat._mat_index[id(m)] = first.value + k
+            self.flat._keep.append(m)          # (keeps the object, hence its id, alive)
+        return int(first.value)
+
+    def AttachMeshes(self, meshes, append_new_materials: bool = False) -> list:
+        """Makes the Meshes resident beside those of the upload and returns their device indices; no object refers to them until the next
+        UpdateObjects / StreamObjects.  Their materials must be materials the library holds (the upload's, AppendMaterials'; NeedsUpload
+        otherwise) - or, with append_new_materials, the ones it does not hold are appended first, as the records of these meshes name them."""
+        meshes = list(meshes)
+        if not meshes:
+            return []
+        mat_id, append_new = self._material_numbering(append_new_materials)
+        keep = []
+        recs = (abi.Mesh * len(meshes))(*[mesh_record(o, mat_id, keep) for o in meshes])
+        append_new()
+        out = (C.c_int32 * len(meshes))()
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_attach_meshes(self.ctx, recs, len(meshes), out)
+        self.stream_call_s["attach_meshes"] = time.perf_counter() - t0
+        self._check(rc)
+        idx = [int(i) for i in out]
+        for o, i in zip(meshes, idx):
+            self.flat._mesh_index[id(o)] = i
+            self._streamed_meshes[id(o)] = o          # (keeps the object, hence its id, alive while it is resident)
+        return idx
+
+    def DetachMeshes(self, indices) -> None:
+        """Gives the meshes' indices and records back; refused while Scene.Objects (as of the last UpdateObjects) refer to one of them."""
+        indices = [int(i) for i in indices]
+        if not indices:
+            return
+        arr = (C.c_int32 * len(indices))(*indices)
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_detach_meshes(self.ctx, arr, len(indices))
+        self.stream_call_s["detach_meshes"] = time.perf_counter() - t0
+        self._check(rc)
+        gone = set(indices)
+        for key in [k for k, i in self.flat._mesh_index.items() if i in gone]:
+            del self.flat._mesh_index[key]
+            self._streamed_meshes.pop(key, None)
+
+    def AttachObjMesh(self, material, scale: float = 1.0, translate=(0.0, 0.0, 0.0), normalize: bool = True, target_size: float = 1.0, auto_ground: bool = False,
+                      target_pos=None):
+        """ycge_scene_attach_obj_mesh: the held OBJ placed as ObjTriangles (or, with auto_ground, as ObjTrianglesAutoGround at target_pos)
+        places it becomes a resident mesh of `material` (a Material the library holds, or its index) without its triangles crossing the
+        bus -> (device index, bounds f32 [6])."""
+        mi = material if isinstance(material, int) else self.flat._mat_index.get(id(material))
+        if mi is None:
+            raise NeedsUpload("a material the uploaded scene does not hold")
+        t = (C.c_float * 3)(*[float(np.float32(v)) for v in (target_pos if auto_ground else translate)])
+        out, bounds = C.c_int32(-1), np.empty(6, np.float32)
+        t0 = time.perf_counter()
+        rc = self.L.ycge_scene_attach_obj_mesh(self.ctx, int(bool(auto_ground)), int(bool(normalize)), float(np.float32(target_size)), float(np.float32(scale)), t, int(mi),
+                                               C.byref(out), bounds.ctypes.data)
+        self.stream_call_s["attach_meshes"] = time.perf_counter() - t0
+        self._check(rc)
+        return int(out.value), bounds
+
+    def mesh_pool_stats(self) -> dict:
+        """The pool of resident meshes (ycge_debug_mesh_pool_stats) and the last attach's host-side split in microseconds."""
+        out = (C.c_int64 * 12)()
+        fn = self.L.ycge_debug_mesh_pool_stats
+        fn.restype, fn.argtypes = abi.MESH_POOL_HOOK_PROTOTYPES["ycge_debug_mesh_pool_stats"]
+        self._check(fn(self.ctx, out))
+        return {k: int(v) for k, v in zip(abi.MESH_POOL_STATS, out)}
 
     def grid_pool_stats(self) -> dict:
         """The pool of resident grids (ycge_debug_grid_pool_stats) and the last attach's host-side split in microseconds."""

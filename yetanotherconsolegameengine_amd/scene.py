@@ -285,6 +285,45 @@ def grid_record(o: "VolumeGrid", mat_id: Callable[[Material], int], keep: list) 
     return g
 
 
+def material_record(m: Material, texture_id: Callable[[object], int]) -> "abi.Material":
+    """One Material as a ycge_material; `texture_id` numbers its DiffuseTexture."""
+    s = abi.Material()
+    s.kind = m.Kind
+    s.texture, s.texture_weight, s.uv_scale = -1, float(m.TextureWeight), float(m.UVScale)
+    if m.DiffuseTexture is not None:
+        if m.Kind != abi.MAT_CONSTANT:
+            raise ValueError("a texture belongs to a plain Material (the checker delegate builds untextured ones)")
+        s.kind, s.texture = abi.MAT_TEXTURED, texture_id(m.DiffuseTexture)
+    s.albedo = abi.Vec3(*m.Albedo)
+    s.albedo_b = abi.Vec3(*m.AlbedoB)
+    s.checker_scale = m.CheckerScale
+    s.specular = float(f32(m.Specular))
+    s.reflectivity = float(f32(m.Reflectivity))
+    s.emission = abi.Vec3(*m.Emission)
+    s.transparency = float(f32(m.Transparency))
+    s.index_of_refraction = float(f32(m.IndexOfRefraction))
+    s.transmission_color = abi.Vec3(*m.TransmissionColor)
+    return s
+
+
+def mesh_record(o: "Mesh", mat_id: Callable[[Material], int], keep: list) -> "abi.Mesh":
+    """One Mesh as a ycge_mesh, the materials numbered by `mat_id`; `keep` receives what the record points to."""
+    tris = np.ascontiguousarray(o.Triangles, dtype=np.float32).reshape(-1, 9)
+    keep.append(tris)
+    m = abi.Mesh()
+    m.triangles = tris.ctypes.data_as(C.POINTER(C.c_float))
+    m.n_triangles = tris.shape[0]
+    m.material = mat_id(o.Mat)
+    m.tri_material = None
+    if o.TriMaterials is not None:
+        ids = np.array([mat_id(mm) for mm in o.TriMaterials], np.int32)
+        tm = np.ascontiguousarray(ids[np.asarray(o.TriMaterialIndex, np.int64)], dtype=np.int32)
+        assert tm.shape == (tris.shape[0],)
+        keep.append(tm)
+        m.tri_material = tm.ctypes.data_as(C.POINTER(C.c_int32))
+    return m
+
+
 class FlatScene:
     """A `ycge_scene` plus the ctypes/numpy storage that keeps its pointers alive."""
 
@@ -344,19 +383,7 @@ class FlatScene:
                 prim(abi.PRIM_VOLUME_GRID, -1, [], ref=against._grid_index[id(o)])
             elif isinstance(o, Mesh):
                 self._mesh_index[id(o)] = len(meshes)
-                tris = np.ascontiguousarray(o.Triangles, dtype=np.float32).reshape(-1, 9)
-                self._keep.append(tris)
-                m = abi.Mesh()
-                m.triangles = tris.ctypes.data_as(C.POINTER(C.c_float))
-                m.n_triangles = tris.shape[0]
-                m.material = mat_id(o.Mat)
-                m.tri_material = None
-                if o.TriMaterials is not None:
-                    ids = np.array([mat_id(mm) for mm in o.TriMaterials], np.int32)
-                    tm = np.ascontiguousarray(ids[np.asarray(o.TriMaterialIndex, np.int64)], dtype=np.int32)
-                    assert tm.shape == (tris.shape[0],)
-                    self._keep.append(tm)
-                    m.tri_material = tm.ctypes.data_as(C.POINTER(C.c_int32))
+                m = mesh_record(o, mat_id, self._keep)
                 prim(abi.PRIM_MESH, -1, [], ref=len(meshes))
                 meshes.append(m)
             elif isinstance(o, VolumeGrid):
@@ -387,27 +414,15 @@ class FlatScene:
         mat_structs = []
         textures: List[Texture] = []
         tex_index = {}
+
+        def texture_id(t) -> int:
+            if id(t) not in tex_index:
+                tex_index[id(t)] = len(textures)
+                textures.append(t)
+            return tex_index[id(t)]
+
         for m in mats:
-            s = abi.Material()
-            s.kind = m.Kind
-            s.texture, s.texture_weight, s.uv_scale = -1, float(m.TextureWeight), float(m.UVScale)
-            if m.DiffuseTexture is not None:
-                if m.Kind != abi.MAT_CONSTANT:
-                    raise ValueError("a texture belongs to a plain Material (the checker delegate builds untextured ones)")
-                if id(m.DiffuseTexture) not in tex_index:
-                    tex_index[id(m.DiffuseTexture)] = len(textures)
-                    textures.append(m.DiffuseTexture)
-                s.kind, s.texture = abi.MAT_TEXTURED, tex_index[id(m.DiffuseTexture)]
-            s.albedo = abi.Vec3(*m.Albedo)
-            s.albedo_b = abi.Vec3(*m.AlbedoB)
-            s.checker_scale = m.CheckerScale
-            s.specular = float(f32(m.Specular))
-            s.reflectivity = float(f32(m.Reflectivity))
-            s.emission = abi.Vec3(*m.Emission)
-            s.transparency = float(f32(m.Transparency))
-            s.index_of_refraction = float(f32(m.IndexOfRefraction))
-            s.transmission_color = abi.Vec3(*m.TransmissionColor)
-            mat_structs.append(s)
+            mat_structs.append(material_record(m, texture_id))
         lights = []
         for l in scene.Lights:
             s = abi.Light()
