@@ -10,7 +10,10 @@ no Python float takes part in an operation.  Scene.Hit is a callable
 
 which normalises d itself (Ray.cs:8-12), as the oracle's orc_scene_hit and the library's queries do.
 
-What is NOT the reference's: the counters (the same the library reports in ycge_camera_tick_info), the list of moves in place of
+An optional `observer(name, left, right, outcome)` is told of every comparison the physics decide by (tests/camera_seams.py names
+them); it sees values only, the default is none, and nothing the restatement returns depends on it.
+
+What is NOT the reference's: the observer, the counters (the same the library reports in ycge_camera_tick_info), the list of moves in place of
 HandleInput's key decoding (a move is what one HandleInput call does to the body, :165-213), and `max_micro`, the most micro-steps one
 move took - the reference's AttemptMoveHorizontal has no bound (:275 adds the slide's residual back), the library caps it.
 """
@@ -56,25 +59,29 @@ def normalized(v):
 
 
 def dmax(a, b):
-    """Math.Max(double, double)"""
+    """Math.Max(double, double): a NaN wins, +0 is greater than -0"""
     a, b = D(a), D(b)
     if np.isnan(a): return a
     if np.isnan(b): return b
+    if a == b: return b if np.signbit(a) else a
     return a if a > b else b
 
 
 def dmin(a, b):
+    """Math.Min(double, double): a NaN wins, -0 is less than +0"""
     a, b = D(a), D(b)
     if np.isnan(a): return a
     if np.isnan(b): return b
+    if a == b: return a if np.signbit(a) else b
     return a if a < b else b
 
 
 class VolumeCamera:
     """the fields VolumeScene keeps between ticks (:16-43) and WorldConfig's three values its physics read"""
 
-    def __init__(self, hit, pos, world_height, water_level, voxel_size_y, auto_placed=False):
+    def __init__(self, hit, pos, world_height, water_level, voxel_size_y, auto_placed=False, observer=None):
         self.hit = hit
+        self.observer = observer
         self.CameraPos = vec3(*pos)
         self.autoPlaced = bool(auto_placed)
         self.verticalVelocity = F(0.0)
@@ -86,9 +93,18 @@ class VolumeCamera:
         self.max_micro = 0
 
     # ------------------------------------------------------------------------------------------------ Scene.Hit
-    def Hit(self, origin, d, tmin, tmax):
+    def Hit(self, origin, d, tmin, tmax, group="ray"):
         self.counters["rays_committed"] += 1
-        return self.hit([F(origin[0]), F(origin[1]), F(origin[2])], [F(d[0]), F(d[1]), F(d[2])], F(tmin), F(tmax))
+        rec = self.hit([F(origin[0]), F(origin[1]), F(origin[2])], [F(d[0]), F(d[1]), F(d[2])], F(tmin), F(tmax))
+        if self.observer is not None:                            # "hit:<group>": rec.T (None: no hit) against the ray's tMax
+            self.observer("hit:" + group, None if rec is None else F(rec[0]), F(tmax), rec is not None)
+        return rec
+
+    def cmp(self, name, left, right, outcome):
+        """a comparison's outcome, passed through; the observer is told its two sides"""
+        if self.observer is not None:
+            self.observer(name, left, right, bool(outcome))
+        return outcome
 
     # ------------------------------------------------------------------------------------------------ one tick
     def tick(self, moves, delta_time_ms, run_update=True):
@@ -98,7 +114,7 @@ class VolumeCamera:
             if kind == MOVE_SHIFT:
                 self.shiftHoldTimer = ShiftHoldGraceSeconds                                   # :177
             elif kind == MOVE_JUMP:
-                if not shift and self.isGrounded:                                               # :208-212
+                if not shift and self.cmp("jump_grounded", self.isGrounded, True, self.isGrounded):  # :208-212
                     self.verticalVelocity = JumpSpeed
                     self.isGrounded = False
             elif kind == MOVE_HORIZONTAL:
@@ -114,14 +130,15 @@ class VolumeCamera:
     # ------------------------------------------------------------------------------------------------ Update, :51-159
     def Update(self, deltaTimeMS):
         dt = F(deltaTimeMS)
-        if dt < F(0.0): dt = F(0.0)
+        if self.cmp("dt_negative", dt, F(0.0), dt < F(0.0)): dt = F(0.0)
         dt = dt * F(0.001)
         self.ResolveIfEmbedded()                                                                # :72
         P = self.CameraPos
         if not self.autoPlaced:                                                                 # :75-86
+            self.cmp("probe_top", self.WorldHeight + F(16.0), MaxProbeHeight, self.WorldHeight + F(16.0) < MaxProbeHeight)
             probeTop = D(min(self.WorldHeight + F(16.0), MaxProbeHeight))
             ok, g0 = self.TrySampleGroundYFan(D(P[0]), D(P[2]), probeTop, probeTop + D(F(8.0)))
-            if ok:
+            if self.cmp("auto_ground", ok, True, ok):
                 self.CameraPos = vec3(P[0], g0 + D(EyeHeight) + D(GroundClearance), P[2])
             else:
                 self.CameraPos = vec3(P[0], self.WaterLevel + EyeHeight + F(4.0), P[2])
@@ -129,7 +146,8 @@ class VolumeCamera:
             self.autoPlaced = True
             self.counters["auto_placements"] += 1
             return
-        if self.shiftHoldTimer > F(0.0):                                                        # :89-92
+        if self.cmp("timer_running", self.shiftHoldTimer, F(0.0), self.shiftHoldTimer > F(0.0)):       # :89-92
+            self.cmp("timer_left", self.shiftHoldTimer - dt, F(0.0), self.shiftHoldTimer - dt > F(0.0))
             self.shiftHoldTimer = max(F(0.0), self.shiftHoldTimer - dt)
         shiftFlyActive = self.shiftHoldTimer > F(0.0)
         if not shiftFlyActive:                                                                  # :95-142
@@ -142,21 +160,23 @@ class VolumeCamera:
             self.isGrounded = False
             if hasGround:
                 floorY = ground + D(EyeHeight) + D(GroundClearance)
-                floorIsAboveHead = floorY > D(P[1] + StepUpGuardEpsilon)
-                if newY <= floorY and not floorIsAboveHead:
+                floorIsAboveHead = self.cmp("floor_above_head", floorY, D(P[1] + StepUpGuardEpsilon), floorY > D(P[1] + StepUpGuardEpsilon))
+                if self.cmp("snap", newY, floorY, newY <= floorY) and not floorIsAboveHead:
                     newY = floorY
                     self.verticalVelocity = F(0.0)
                     self.isGrounded = True
                     self.counters["ground_snaps"] += 1
                 else:
-                    self.isGrounded = (not floorIsAboveHead) and bool((D(P[1]) - floorY) <= D(StepUpGuardEpsilon))
+                    self.isGrounded = (not floorIsAboveHead) and bool(self.cmp("grounded", D(P[1]) - floorY, D(StepUpGuardEpsilon),
+                                                                               (D(P[1]) - floorY) <= D(StepUpGuardEpsilon)))
             self.CameraPos = P = vec3(P[0], newY, P[2])
             corrStartY = D(P[1] + LocalProbeStart)
             corrDepth = D(LocalProbeStart) + D(1.5)
             ok, g2 = self.TrySampleGroundYFan(D(P[0]), D(P[2]), corrStartY, corrDepth)
             if ok:
                 f2 = g2 + D(EyeHeight) + D(GroundClearance)
-                if f2 <= D(P[1] + StepUpGuardEpsilon) and (D(P[1]) - f2) <= D(0.5):
+                if (self.cmp("corr_accept", f2, D(P[1] + StepUpGuardEpsilon), f2 <= D(P[1] + StepUpGuardEpsilon))
+                        and self.cmp("hover", D(P[1]) - f2, D(0.5), (D(P[1]) - f2) <= D(0.5))):
                     self.CameraPos = P = vec3(P[0], f2, P[2])
                     self.verticalVelocity = F(0.0)
                     self.isGrounded = True
@@ -165,7 +185,7 @@ class VolumeCamera:
             self.verticalVelocity = F(0.0)                                                      # :146
         self.ApplyWallRepulsion(dt)                                                             # :150
         P = self.CameraPos
-        if D(P[1]) < D(-10.0):                                                                  # :153-158
+        if self.cmp("fail_safe", D(P[1]), D(-10.0), D(P[1]) < D(-10.0)):                        # :153-158
             self.CameraPos = vec3(P[0], 200.0, P[2])
             self.verticalVelocity = F(0.0)
             self.repelVel = vec3(0.0, 0.0, 0.0)
@@ -175,14 +195,15 @@ class VolumeCamera:
     def AttemptMoveHorizontal(self, delta):
         maxStep = dmax(D(0.1), D(CollisionRadius) * D(0.35))
         remaining = np.sqrt(D(delta[0] * delta[0] + delta[2] * delta[2]))
-        if remaining <= D(1e-6): return
+        if self.cmp("h_cutoff", remaining, D(1e-6), remaining <= D(1e-6)): return
         dir_ = vec3(D(delta[0]) / remaining, 0.0, D(delta[2]) / remaining)
         perp = vec3(-dir_[2], 0.0, dir_[0])
         micro = 0
-        while remaining > D(1e-6):
+        while self.cmp("h_remaining", remaining, D(1e-6), remaining > D(1e-6)):
             micro += 1
             self.max_micro = max(self.max_micro, micro)
             self.counters["micro_steps"] += 1
+            self.cmp("h_step", remaining, maxStep, remaining < maxStep)
             step = dmin(remaining, maxStep)
             ref = dict(best=step, hadNormal=False, blockNormal=vec3(0.0, 0.0, 0.0))
             P = self.CameraPos
@@ -194,26 +215,26 @@ class VolumeCamera:
                 self.LimitStepByRay(vec3(P[0] + offVec[0], eyeY, P[2] + offVec[2]), dir_, ref)
                 self.LimitStepByRay(vec3(P[0] + offVec[0], torsoY, P[2] + offVec[2]), dir_, ref)
             best = ref["best"]
-            if best <= D(1e-5):
+            if self.cmp("caps_blocked", best, D(1e-5), best <= D(1e-5)):
                 self.counters["blocked_steps"] += 1
                 break
             self.CameraPos = vec3(D(P[0]) + D(dir_[0]) * best, P[1], D(P[2]) + D(dir_[2]) * best)
             remaining = remaining - best
             residual = step - best
-            if residual > D(1e-6) and ref["hadNormal"]:
+            if self.cmp("residual", residual, D(1e-6), residual > D(1e-6)) and ref["hadNormal"]:
                 slide = self.ProjectOntoPlaneXZ(dir_, ref["blockNormal"])
                 length = np.sqrt(slide[0] * slide[0] + slide[2] * slide[2])
-                if length > F(1e-6):
+                if self.cmp("slide_length", length, F(1e-6), length > F(1e-6)):
                     dir_ = vec3(slide[0] / length, 0.0, slide[2] / length)
                     remaining = remaining + residual
                     self.counters["slides"] += 1
 
     def LimitStepByRay(self, origin, dir_, ref):                                               # :283-298
         tmax = F(ref["best"] + D(1e-3))
-        rec = self.Hit(origin, dir_, F(0.001), tmax)
+        rec = self.Hit(origin, dir_, F(0.001), tmax, "caps")
         if rec is not None:
             cand = dmax(D(0.0), D(F(rec[0])) - D(0.01))
-            if cand < ref["best"]:
+            if self.cmp("caps_cand", cand, ref["best"], cand < ref["best"]):
                 ref["best"] = cand
                 ref["hadNormal"] = True
                 ref["blockNormal"] = vec3(*rec[1])
@@ -221,21 +242,22 @@ class VolumeCamera:
     # ------------------------------------------------------------------------------------------------ AttemptMoveVertical, :300-325
     def AttemptMoveVertical(self, dy):
         dy = D(dy)
-        if abs(dy) <= D(1e-6): return
+        if self.cmp("v_cutoff", abs(dy), D(1e-6), abs(dy) <= D(1e-6)): return
         remaining = D(abs(dy))
         stepSign = D(np.sign(dy))
         maxStep = dmax(D(0.1), D(EyeHeight) * D(0.25))
         micro = 0
-        while remaining > D(1e-6):
+        while self.cmp("v_remaining", remaining, D(1e-6), remaining > D(1e-6)):
             micro += 1
             self.max_micro = max(self.max_micro, micro)
             self.counters["micro_steps"] += 1
+            self.cmp("v_step", remaining, maxStep, remaining < maxStep)
             step = dmin(remaining, maxStep)
             P = self.CameraPos
-            rec = self.Hit(vec3(P[0], P[1], P[2]), vec3(0.0, stepSign, 0.0), F(0.001), F(step + D(1e-3)))
+            rec = self.Hit(vec3(P[0], P[1], P[2]), vec3(0.0, stepSign, 0.0), F(0.001), F(step + D(1e-3)), "vert")
             if rec is not None:
                 cand = dmax(D(0.0), D(F(rec[0])) - D(0.01))
-                if cand <= D(1e-5):
+                if self.cmp("vert_blocked", cand, D(1e-5), cand <= D(1e-5)):
                     self.counters["blocked_steps"] += 1
                     break
                 self.CameraPos = vec3(P[0], D(P[1]) + cand * stepSign, P[2])
@@ -254,8 +276,8 @@ class VolumeCamera:
         found, bestT, bestDir = False, D(np.inf), vec3(0.0, 1.0, 0.0)
         for d in dirs:
             for y in (eyeY, torsoY):
-                rec = self.Hit(vec3(P[0], y, P[2]), d, F(0.0), searchR)                         # RayDist, :407-414
-                if rec is not None and D(F(rec[0])) < bestT:
+                rec = self.Hit(vec3(P[0], y, P[2]), d, F(0.0), searchR, "exit")                 # RayDist, :407-414
+                if rec is not None and self.cmp("exit_t", D(F(rec[0])), bestT, D(F(rec[0])) < bestT):
                     bestT, bestDir, found = D(F(rec[0])), d, True
         if found and bestT < D(np.inf):
             eps = dmax(D(0.02), D(self.VoxelSizeY) * D(0.02))
@@ -268,16 +290,17 @@ class VolumeCamera:
         P = self.CameraPos
         eyeY = D(P[1])
         torsoY = D(P[1]) - (D(EyeHeight) * D(0.5))
-        return self.IsLikelyEmbeddedAtY(eyeY) or self.IsLikelyEmbeddedAtY(torsoY)
+        return (self.cmp("embedded_eye", None, None, self.IsLikelyEmbeddedAtY(eyeY))
+                or self.cmp("embedded_torso", None, None, self.IsLikelyEmbeddedAtY(torsoY)))
 
     def IsLikelyEmbeddedAtY(self, y):                                                           # :389-398 (four statements, all evaluated)
         probe = F(dmax(D(0.05), D(CollisionRadius) * D(0.25)))
         P = self.CameraPos
         o = vec3(P[0], y, P[2])
-        xPos = self.Hit(o, vec3(1, 0, 0), F(0.0), probe) is not None                            # RayHitWithin, :400-405
-        xNeg = self.Hit(o, vec3(-1, 0, 0), F(0.0), probe) is not None
-        zPos = self.Hit(o, vec3(0, 0, 1), F(0.0), probe) is not None
-        zNeg = self.Hit(o, vec3(0, 0, -1), F(0.0), probe) is not None
+        xPos = self.Hit(o, vec3(1, 0, 0), F(0.0), probe, "embed") is not None                            # RayHitWithin, :400-405
+        xNeg = self.Hit(o, vec3(-1, 0, 0), F(0.0), probe, "embed") is not None
+        zPos = self.Hit(o, vec3(0, 0, 1), F(0.0), probe, "embed") is not None
+        zNeg = self.Hit(o, vec3(0, 0, -1), F(0.0), probe, "embed") is not None
         return (xPos and xNeg) and (zPos and zNeg)
 
     # ------------------------------------------------------------------------------------------------ ApplyWallRepulsion, :418-464
@@ -295,14 +318,14 @@ class VolumeCamera:
                 self.ResolvePenetrationAt(vec3(self.CameraPos[0], torsoY, self.CameraPos[2]), dirXZ, eps)
 
     def ResolvePenetrationAt(self, origin, dirXZ, eps):
-        rec = self.Hit(origin, dirXZ, F(0.001), CollisionRadius)
+        rec = self.Hit(origin, dirXZ, F(0.001), CollisionRadius, "push")
         if rec is not None:
             pen = CollisionRadius - F(rec[0])
-            if pen > F(0.0):
+            if self.cmp("pen", pen, F(0.0), pen > F(0.0)):
                 n = vec3(*rec[1])
                 nXZ = vec3(n[0], 0.0, n[2])
                 nl = np.sqrt(nXZ[0] * nXZ[0] + nXZ[2] * nXZ[2])
-                if nl > F(1e-6):
+                if self.cmp("push_normal", nl, F(1e-6), nl > F(1e-6)):
                     nXZ = vec3(nXZ[0] / nl, 0.0, nXZ[2] / nl)
                     push = pen + eps
                     P = self.CameraPos
@@ -329,17 +352,18 @@ class VolumeCamera:
             if ok:
                 anyHit = True
                 floorCandidate = y + D(EyeHeight) + D(GroundClearance)
-                if floorCandidate <= D(self.CameraPos[1] + StepUpGuardEpsilon):
-                    if not anyAcceptable or y > bestAcceptable: bestAcceptable = y
+                guard = D(self.CameraPos[1] + StepUpGuardEpsilon)
+                if self.cmp("fan_accept", floorCandidate, guard, floorCandidate <= guard):
+                    if not anyAcceptable or self.cmp("fan_best", y, bestAcceptable, y > bestAcceptable): bestAcceptable = y
                     anyAcceptable = True
-                if not anyAcceptable and (np.isneginf(groundY) or y > groundY): groundY = y
+                if not anyAcceptable and (np.isneginf(groundY) or self.cmp("fan_ground", y, groundY, y > groundY)): groundY = y
         if anyAcceptable:
             return True, bestAcceptable
         return bool(anyHit and not np.isneginf(groundY)), groundY
 
     def TrySampleGroundY(self, x, z, startY, maxDistance):
         origin, d = vec3(x, startY, z), vec3(0.0, -1.0, 0.0)
-        rec = self.Hit(origin, d, F(0.00001), F(maxDistance))
+        rec = self.Hit(origin, d, F(0.00001), F(maxDistance), "fan")
         if rec is None: return False, D(0.0)
         nd = normalized(d)
         t = F(rec[0])
