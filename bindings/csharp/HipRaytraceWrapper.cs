@@ -37,6 +37,12 @@
 //                sRGB8 triples OpenGLTerminalRenderer shows, not the 240 colours of ChexelToAnsi256.  With DeviceAnsiDelta a cell is rewritten
 //                when a channel is more than AnsiRgbTolerance (0..255) away from what the terminal shows for it; 0 is the exact form.  The
 //                library keeps one terminal state per context: a switch of colour form is a keyframe (INTEGRATION.md section 8.2).
+//   QuadrantGlyphs - with DeviceAnsiStream: quadrant block glyphs (ycge_render_frame_ansi_quad / _quad_delta): each cell shows a 2 x 2 grid of
+//                sub-cells in two 24-bit colours, fitted on the device - twice the horizontal detail in the same console.  superSample must
+//                be even; the streams are synchronous (FrameLate is not offered with it) and 24-bit whatever AnsiTrueColor says.  With
+//                DeviceAnsiDelta a cell is rewritten when its glyph differs or a channel is more than AnsiRgbTolerance away;
+//                QuadrantMinContrast (0..255) keeps a cell one colour while its sub-cells lie that close to their mean, so that TAA's +-1
+//                flicker does not flip glyphs in a resting picture (INTEGRATION.md section 8.5).
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -62,6 +68,8 @@ public sealed class HipRaytraceOptions
     public bool AnsiTrueColor = false;                        // DeviceAnsiStream: 24-bit colour streams
     // 0 is the exact form and stays the default until profiles/ansi_rgb_rate.json has numbers that argue otherwise (INTEGRATION.md 8.2).
     public int AnsiRgbTolerance = 0;
+    public bool QuadrantGlyphs = false;                       // DeviceAnsiStream: quadrant block glyphs, 2 x 2 sub-cells a cell (superSample even, no FrameLate)
+    public int QuadrantMinContrast = 0;                       // ... a cell stays one colour while its sub-cell bytes lie this close to their mean (0..255)
     public HipGeneratedWorld GeneratedWorld;                  // chunks that come from the generator are made on the device (ycge_scene_generate_grids)
 }
 
@@ -162,8 +170,10 @@ public partial class RaytraceEntity
         private YAnsiAsyncResult* ansiRec, ansiRecLate;   // FrameLate: the records of the two (page-locked memory of the library)
         private readonly bool ansiDelta;            // DeviceAnsiDelta: delta streams between keyframes
         private readonly int ansiMergeGap;
-        private readonly bool ansiRgb;              // AnsiTrueColor: the 24-bit colour forms of the two calls
+        private bool ansiRgb;                       // AnsiTrueColor: the 24-bit colour forms of the two calls
         private readonly int ansiTolerance;
+        private readonly bool ansiQuad;             // QuadrantGlyphs: the quadrant-glyph forms of the two calls
+        private readonly int ansiMinContrast;
         private bool inFlight;                      // FrameLate: a frame queued by the last TryFlipAndBlit has not been waited for yet
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
         private ulong objectsSignature;
@@ -189,6 +199,10 @@ public partial class RaytraceEntity
             ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
             ansiDelta = ansi != null && options.DeviceAnsiDelta; ansiMergeGap = options != null ? options.AnsiMergeGap : 3;
             ansiRgb = ansi != null && options.AnsiTrueColor; ansiTolerance = options != null ? options.AnsiRgbTolerance : 0;
+            ansiQuad = ansi != null && options.QuadrantGlyphs; ansiMinContrast = options != null ? options.QuadrantMinContrast : 0;
+            if (ansiQuad && (ss & 1) != 0) throw new ArgumentException("QuadrantGlyphs needs an even superSample");
+            if (ansiQuad && options.FrameLate) throw new ArgumentException("QuadrantGlyphs has no FrameLate form");
+            ansiRgb |= ansiQuad;                    // (the quadrant streams are 24-bit ones: their bound is the 24-bit bound)
             frameLate = options != null && options.FrameLate && cfg.NDevices <= 1;      // (frames in flight are the single-device form)
             deviceColors = options != null && options.DeviceChexelColors;
             generated = options?.GeneratedWorld;
@@ -257,7 +271,13 @@ public partial class RaytraceEntity
             }
             HipConsoleLayers.Set(ctx, ansi.FrameBuffers, fb);                   // (the other framebuffers as they stand now; fb is this wrapper's own)
             UIntPtr len;
-            if (ansiRgb && ansiDelta)
+            if (ansiQuad && ansiDelta)
+                Ycge.Check(ctx, Ycge.ycge_render_frame_ansi_quad_delta(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
+                                                                       ansiMergeGap, ansiTolerance, 0, ansiMinContrast, ansiBuf, (UIntPtr)ansiCap, &len, null, null, null));
+            else if (ansiQuad)
+                Ycge.Check(ctx, Ycge.ycge_render_frame_ansi_quad(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
+                                                                 ansiMinContrast, ansiBuf, (UIntPtr)ansiCap, &len, null, null));
+            else if (ansiRgb && ansiDelta)
                 Ycge.Check(ctx, Ycge.ycge_render_frame_ansi_rgb_delta(ctx, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg, ansi.ClearPending ? 1 : 0,
                                                                       ansiMergeGap, ansiTolerance, 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null, null));
             else if (ansiRgb)

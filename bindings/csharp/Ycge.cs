@@ -358,6 +358,17 @@ namespace ConsoleGame.RayTracing.Native
                                                                                  int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, int mergeGap,
                                                                                  int tolerance, int keyframe, byte* outStream, UIntPtr capacity, UIntPtr* outLen,
                                                                                  uint* outInfo, float* outTopBottomSdr);
+        // quadrant-glyph frames (after ABI 10, found by symbol lookup): a chexel's 2 x 2 sub-cell colours (12 floats), the fitted glyph (UTF-16 code
+        // units) and two colours (the RGBA plane, row 2 cy the foreground); the 24-bit streams with them.  superSample must be even; minContrast 0..255
+        [DllImport(Lib)] public static extern int ycge_render_frame_quadrants(IntPtr ctx, float* outTopBottomSdr, float* outQuadSdr, ushort* outGlyphs, byte* outRgba,
+                                                                              int minContrast, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_render_frame_ansi_quad(IntPtr ctx, int consoleW, int consoleH, int viewportX, int viewportY, int defaultFg16,
+                                                                              int defaultBg16, int clearScreen, int minContrast, byte* outStream, UIntPtr capacity,
+                                                                              UIntPtr* outLen, float* outTopBottomSdr, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_render_frame_ansi_quad_delta(IntPtr ctx, int consoleW, int consoleH, int viewportX, int viewportY, int defaultFg16,
+                                                                                    int defaultBg16, int clearScreen, int mergeGap, int tolerance, int keyframe,
+                                                                                    int minContrast, byte* outStream, UIntPtr capacity, UIntPtr* outLen, uint* outInfo,
+                                                                                    float* outTopBottomSdr, YFrameStats* stats);
         // the console's other framebuffers for every stream call above (found by symbol lookup, ABI stays 10); YConsoleLayer, YChexel and
         // HipConsoleLayers: bindings/csharp/YcgeConsole.cs
         [DllImport(Lib)] public static extern int ycge_console_set_layers(IntPtr ctx, YConsoleLayer* layers, int n, int raytraceAt);

@@ -870,6 +870,56 @@ typedef struct ycge_chexel { uint16_t ch; uint16_t pad; float fg[3]; float bg[3]
 typedef struct ycge_console_layer { int32_t x, y, w, h; const ycge_chexel *cells; } ycge_console_layer;
 #define YCGE_CONSOLE_MAX_LAYERS 16
 int ycge_console_set_layers(ycge_ctx *ctx, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at);
+/* --- Quadrant-glyph frames: 2 x 2 sub-cells a chexel, fitted on the device.  Every presenter above ends in '▀' with a top and a bottom
+ * colour: two samples a console cell.  With an even super_sample the frame holds more, and the quadrant block glyphs (U+2596..U+259F, '▌',
+ * '▀': all in the BMP, all 3 UTF-8 bytes) show a 2 x 2 grid in two colours.  The reference has no such presenter, so these rules define the
+ * result; the tone map and LinearToSrgb8 are the frame's own.  Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no existing
+ * struct or prototype changes; a host detects the exports by symbol lookup.
+ *   Sub-cell colours.  super_sample = ss must be even.  Chexel (cx, cy) covers hi-res columns cx ss .. cx ss + ss - 1 and rows 2 cy ss ..
+ *   2 cy ss + 2 ss - 1 of the denoised buffer the tone map reads (YCGE_BUF_DENOISED).  Quadrant k - 0 = TL, 1 = TR, 2 = BL, 3 = BR - is ss / 2
+ *   columns (the left / right half) by ss rows (the top / bottom half-cell's).  Its colour: the binary32 sum of its samples in row-major order
+ *   (rows outer, columns inner, per channel, from 0), times 1.0f / (float)((ss / 2) ss), through the frame's MapPixel with the frame's effective
+ *   exposure (stats.exposure), gamma 2.2, saturation 2.0, vibrance 0.  out_quad_sdr: fbW*fbH*12 f32, {TL rgb, TR rgb, BL rgb, BR rgb} a chexel.
+ *   The fit, all integer from the bytes on, with min_contrast = M in 0..255:
+ *     Q[k][c] = the sRGB8 byte ycge_render_frame_chexels' out_rgba holds for that colour (Clamp01, LinearToSrgb8).
+ *     S0[c] = Q[0][c] + .. + Q[3][c], mean0[c] = (2 S0[c] + 4) / 8 (integer division).
+ *     If the largest |Q[k][c] - mean0[c]| over k, c is <= M the mask is m = 0.  Otherwise, for m in 0..7 - bit 0 = TL, bit 1 = TR, bit 2 = BL
+ *     in the foreground F, the rest and always BR the background B - score(m) = w(|B|) |S_B|^2 + (F empty ? 0 : w(|F|) |S_F|^2), w(1..4) =
+ *     12, 6, 4, 3, |S|^2 the sum over channels of the squared channel sum (int32; below 2^24).  The largest score wins, ties to the smallest
+ *     m: a minimiser of the squared error of the two-colour approximation.
+ *     bg[c] = (2 S_B[c] + |B|) / (2 |B|), fg likewise over F; m = 0: fg = bg.
+ *     The glyph by m: 0 U+2580 (fg == bg), 1 U+2598, 2 U+259D, 3 U+2580, 4 U+2596, 5 U+258C, 6 U+259E, 7 U+259B.  No cell is ever ' ': a
+ *     raytrace cell stays opaque under GetChexelForPoint's rule.
+ *     M is there so that the +-1 flicker TAA leaves in a resting picture does not flip masks, and with them glyphs, every frame.  Default 0.
+ *   ycge_render_frame_quadrants: ycge_render_frame_chexels' frame - the same frame state, the same SDR array bit for bit - with
+ *   out_quad_sdr; out_glyphs, fbW*fbH code units; out_rgba in exactly out_rgba's layout there (fbW x 2 fbH RGBA8, row 2 cy = fg, row 2 cy + 1
+ *   = bg, alpha 255).  Any subset of the four destinations may be NULL, not all; pageable or page-locked as the chexel call handles them.
+ *   ycge_render_frame_ansi_quad: ycge_render_frame_ansi_rgb's stream, rule for rule - clear prefix, per-row cursor move, the three-branch
+ *   escape against the previous cell, the trailer ESC[0m - with a covered cell's character and triples the fitted glyph, fg, bg.  Uncovered
+ *   cells are ' ' in the default colours.  ycge_ansi_rgb_stream_bound stands: every glyph is 3 bytes.
+ *   ycge_render_frame_ansi_quad_delta: the layered 24-bit delta contract above (ycge_console_set_layers), layers or none: shown is a
+ *   console-wide composite of {character, fg, bg}; changed(x, y) where the character differs or the largest channel difference exceeds
+ *   tolerance; emitted cells, run starts, merge_gap, the last-cell rule, out_info and "shown = cur for every emitted cell, its character
+ *   always cur's" as there.  A keyframe is the full quad stream, byte for byte.
+ *   Layers.  With ycge_console_set_layers in force the fitted cells take the raytrace framebuffer's place in the composite - same order, same
+ *   opacity; the other framebuffers behave as they do in the other streams.
+ *   State.  One terminal per context: the quad family is a third beside the 256-colour and 24-bit ones.  A delta of one family is a keyframe
+ *   after any stream of another, and every keyframe cause listed at ycge_render_frame_ansi_rgb_delta applies.  min_contrast is not part of
+ *   the geometry key.  An argument refusal leaves the state untouched.
+ *   Refused before any device work, nothing written then or later, the message naming the value (YCGE_ERR_INVALID_ARG): an odd super_sample;
+ *   min_contrast outside 0..255; everything the corresponding _chexels / _ansi_rgb / _ansi_rgb_delta call refuses - all destinations NULL, a
+ *   NULL stream or length, capacity below the bound, defaults outside 0..15, a peer context, RCCL with lean slabs, tolerance, merge_gap.
+ *   Not offered: 256-colour and console-16 forms, the video blits, frames in flight, sextants and octants, a temporal hysteresis beyond M. */
+int ycge_render_frame_quadrants(ycge_ctx *ctx, float *out_top_bottom_sdr /* may be NULL */, float *out_quad_sdr /* fbW*fbH*12, may be NULL */,
+                                uint16_t *out_glyphs /* fbW*fbH, may be NULL */, uint8_t *out_rgba /* fbW x 2 fbH RGBA8, may be NULL */,
+                                int32_t min_contrast, ycge_frame_stats *stats);
+int ycge_render_frame_ansi_quad(ycge_ctx *ctx, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                                int32_t default_bg16, int32_t clear_screen, int32_t min_contrast, uint8_t *out_stream, size_t capacity,
+                                size_t *out_len, float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+int ycge_render_frame_ansi_quad_delta(ycge_ctx *ctx, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                                      int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance, int32_t keyframe,
+                                      int32_t min_contrast, uint8_t *out_stream, size_t capacity, size_t *out_len,
+                                      uint32_t *out_info /* 4 words or NULL */, float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
 /* --- ANSI streams with frames in flight: the four frame forms above - ycge_render_frame_ansi, _ansi_delta, _ansi_rgb, _ansi_rgb_delta - queued
  * as ycge_render_frame_async_sdr queues a frame.  The synchronous calls read the stream's length on the host and copy exactly that many
  * bytes, which takes a synchronisation inside the call; here a kernel behind the stream's kernels (k_ansi_deliver, csrc/ycge_ansi_flight.hip)

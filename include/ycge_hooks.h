@@ -80,6 +80,25 @@ int ycge_test_ansi_layers(ycge_ctx *c, int32_t rgb, const uint8_t *plane, int32_
                           int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t delta,
                           int32_t merge_gap, int32_t tolerance, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
                           uint8_t *out_colours, uint16_t *out_glyphs);
+/* ---- the quadrant-glyph frames (csrc/ycge_chexel.cpp, csrc/ycge_ansi.cpp; the rules: ycge.h at ycge_render_frame_quadrants).
+ * ycge_test_quadrant_sdr: k_tonemap_quadrants alone on a caller-given hi-res buffer hdr (fbH*2*ss rows of fbW*ss pixels, 3 f32 each) with the
+ * effective exposure `exposure`, whatever the context's framebuffer is; out fbW*fbH*12 f32.  ss even, 2..64.  Touches no frame state.
+ * ycge_test_quadrant_fit: k_fit_quadrants alone on n cells of 12 f32 as an n x 1 framebuffer: out_glyphs n code units, out_rgba n foreground
+ * words then n background words (either NULL, not both).
+ * ycge_test_ansi_quad_stream / _delta: the quadrant streams' kernels alone on caller-given planes of the fbW x fbH framebuffer - glyphs,
+ * fbW*fbH code units (none of them ' '), and rgba, fbW x 2 fbH RGBA8 with row 2 cy the foreground - with the geometry, defaults and refusals
+ * of ycge_render_frame_ansi_quad / _quad_delta and no layers.  The delta hook is stateless: shown_colours (console_w x 2 console_h RGBA8) and
+ * shown_glyphs (console_w*console_h code units) are the composite the terminal shows - either NULL, or clear_screen != 0: the keyframe,
+ * ycge_test_ansi_quad_stream's bytes - and out_shown_colours / out_shown_glyphs (or NULL) receive the next such, every fourth byte 255 */
+int ycge_test_quadrant_sdr(ycge_ctx *c, const float *hdr, int32_t fbW, int32_t fbH, int32_t ss, float exposure, float *out);
+int ycge_test_quadrant_fit(ycge_ctx *c, const float *quad_sdr, int32_t n, int32_t min_contrast, uint16_t *out_glyphs, uint8_t *out_rgba);
+int ycge_test_ansi_quad_stream(ycge_ctx *c, const uint16_t *glyphs, const uint8_t *rgba, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h,
+                               int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream,
+                               size_t capacity, size_t *out_len);
+int ycge_test_ansi_quad_delta(ycge_ctx *c, const uint8_t *shown_colours, const uint16_t *shown_glyphs, const uint16_t *glyphs, const uint8_t *rgba, int32_t fbW,
+                              int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16,
+                              int32_t clear_screen, int32_t merge_gap, int32_t tolerance, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
+                              uint8_t *out_shown_colours, uint16_t *out_shown_glyphs);
 /* ---- the delivery of a stream with frames in flight (csrc/ycge_ansi.cpp, kernel csrc/ycge_ansi_flight.hip): k_ansi_deliver alone.  src
  * (n_src bytes) is uploaded as the device stream and {length, counts[0..3)} as the words the scan writes; the kernel then copies into
  * out_stream (capacity bytes, page-locked, 16-byte aligned) and fills out_result (page-locked, 8-byte aligned), and the call synchronises.

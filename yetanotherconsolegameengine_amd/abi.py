@@ -377,6 +377,15 @@ _PROTOTYPES = {
                                                  C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     # (layers: an array of abi.ConsoleLayer, or None with n = 0)
     "ycge_console_set_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    # the quadrant-glyph frames: the planes (SDR, 12 f32 a chexel, code units, fitted RGBA; min_contrast), the full stream (min_contrast behind
+    # clear_screen) and the delta (min_contrast behind keyframe)
+    "ycge_render_frame_quadrants": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.c_int32,
+                                              C.POINTER(FrameStats)]),
+    "ycge_render_frame_ansi_quad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(FrameStats)]),
+    "ycge_render_frame_ansi_quad_delta": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
+                                                    C.POINTER(C.c_float), C.POINTER(FrameStats)]),
     # (req: C.byref(abi.AnsiAsync); out_result: the address of an abi.AnsiAsyncResult in page-locked memory)
     "ycge_render_frame_async_ansi": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
@@ -474,6 +483,17 @@ ANSI_LAYERS_HOOK_PROTOTYPES = {
     "ycge_test_ansi_layers": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
                                         C.POINTER(C.c_uint16)] + [C.c_int32] * 10 +
                               [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)]),
+}
+# test hooks of the quadrant-glyph frames (csrc/ycge_chexel.cpp, csrc/ycge_ansi.cpp), bound where they are used (tests/test_gpu_quadrants.py):
+# the two kernels alone, and the streams on given glyph (uint16) + RGBA planes; the delta hook starts with the shown composite's colours and
+# glyphs (or None) and ends with the next such (or None)
+QUADRANT_HOOK_PROTOTYPES = {
+    "ycge_test_quadrant_sdr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "ycge_test_quadrant_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ycge_test_ansi_quad_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)] + [C.c_int32] * 9 +
+                                   [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ycge_test_ansi_quad_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)] + [C.c_int32] * 11 +
+                                  [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)]),
 }
 # test hook of the delivery of a stream with frames in flight (csrc/ycge_ansi.cpp), bound where it is used (tests/test_gpu_ansi_flight.py): src,
 # n_src, length, capacity, keyframe, counts (3 uint32), groups, out_stream, out_result (an abi.AnsiAsyncResult in page-locked memory)

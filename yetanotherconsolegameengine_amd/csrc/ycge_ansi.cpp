@@ -21,6 +21,10 @@
 // k_encode_chexels.  While any are set, launch() runs the compose pass in front of the stream kernels, which then walk the console-wide
 // composite; the delta forms keep the last composite's colour and glyph planes in comp_held / glyph_held, flipped with delta_held.
 //
+// The quadrant-glyph forms (ycge_render_frame_ansi_quad, _quad_delta): `quad` set beside `rgb`.  The frame's plane is k_fit_quadrants' and a
+// glyph plane comes with it, so EVERY such stream runs the compose pass - with no layers set, over the raytrace framebuffer alone - and walks
+// the composite with the layered 24-bit kernels; its delta state is the composite's (comp_held / glyph_held), a third family beside the two.
+//
 // The default cell's colours are ansi(palette16[k]): k_encode_chexels run once on the 16 palette colours, so no second formula exists.
 #include "ycge_ctx.h"
 
@@ -93,14 +97,20 @@ static int ensure_ansi(ycge_ctx *c, ChexelState &X, const AnsiRequest &r, unsign
 // otherwise the full stream and its length alone
 // L (or NULL: no layers): the console's other framebuffers and the composite's planes, the compose pass in front; d_prev and d_next are then L's
 // flight (or NULL): the frame in flight whose stream buffer and record k_ansi_deliver fills instead of that copy
+// d_glyph (r.quad alone): the fitted code units beside d_plane; L is then never NULL
 static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiRequest &r, bool delta, const uint8_t *d_plane, const uint8_t *d_prev, uint8_t *d_next,
-                  int fbW, int fbH, const ycge_ansi::LayersRun *L, const FrameOutputs *flight = nullptr)
+                  int fbW, int fbH, const ycge_ansi::LayersRun *L, const FrameOutputs *flight = nullptr, const uint16_t *d_glyph = nullptr)
 {
     const uint8_t *palette = r.rgb ? X.rgb_palette.p : reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48);
     uint8_t *out = X.ansi_stream.p;
     const size_t cap = X.ansi_stream.cap;
     int e;
-    if (L && !delta)
+    if (r.quad && !delta)
+        e = ycge_launch_ansi_quad_stream(L, d_plane, d_glyph, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.clear, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
+    else if (r.quad)
+        e = ycge_launch_ansi_quad_delta(L, d_plane, d_glyph, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, r.tolerance, X.ansi_tiles.p, out, cap, X.ansi_res.p,
+                                        stream);
+    else if (L && !delta)
         e = (r.rgb ? ycge_launch_ansi_rgb_layers_stream : ycge_launch_ansi_layers_stream)(L, d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.clear,
                                                                                         X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
     else if (L && r.rgb)
@@ -117,7 +127,7 @@ static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiReq
     else
         e = ycge_launch_ansi_delta(d_plane, d_prev, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
     if (e != 0)
-        return c->fail(YCGE_ERR_DEVICE, "%sANSI %sstream launch failed: %s", r.rgb ? "24-bit " : "", delta ? "delta " : "", hipGetErrorString((hipError_t)e));
+        return c->fail(YCGE_ERR_DEVICE, "%sANSI %sstream launch failed: %s", r.quad ? "quadrant " : r.rgb ? "24-bit " : "", delta ? "delta " : "", hipGetErrorString((hipError_t)e));
     if (!flight) {
         HIP_TRY(c, hipMemcpyAsync(X.ansi_res_host.p, X.ansi_res.p, (delta ? 4 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
         return YCGE_OK;
@@ -161,7 +171,7 @@ static int ensure_composite(ycge_ctx *c, ChexelState &X, const AnsiRequest &r)
 static int ensure_frame_buffers(ycge_ctx *c, ChexelState &X, const AnsiRequest &r, unsigned long long bound, hipStream_t stream)
 {
     const int rc = ensure_ansi(c, X, r, bound, stream);
-    return rc == YCGE_OK && X.layers.n > 0 ? ensure_composite(c, X, r) : rc;
+    return rc == YCGE_OK && (X.layers.n > 0 || r.quad) ? ensure_composite(c, X, r) : rc;
 }
 
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_pairs)
@@ -171,7 +181,7 @@ int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const
     { const int rc = r.rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
     const bool delta = !out.keyframe;
     const FrameOutputs *flight = out.dev_stream ? &out : nullptr;
-    if (X.layers.n == 0)
+    if (X.layers.n == 0 && !r.quad)
         return launch(c, X, stream, r, delta, d_pairs, X.delta_held[X.delta_prev].p, X.delta_held[1 - X.delta_prev].p, c->fbW, c->fbH, nullptr, flight);
     // (layers: this call's composite goes where the next _delta call finds it; a 24-bit delta's write kernel fills that plane instead)
     ycge_ansi::LayersRun L = layers_run(X.layers, r.rgb);
@@ -180,7 +190,7 @@ int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const
     L.comp_glyph = X.glyph_held[next].p;
     L.prev = X.comp_held[held].p; L.prev_glyph = X.glyph_held[held].p;
     L.next = X.comp_held[next].p;
-    return launch(c, X, stream, r, delta, d_pairs, nullptr, nullptr, c->fbW, c->fbH, &L, flight);
+    return launch(c, X, stream, r, delta, d_pairs, nullptr, nullptr, c->fbW, c->fbH, &L, flight, r.quad ? X.quad_glyphs.p : nullptr);
 }
 
 } // namespace ycge_host
@@ -197,8 +207,9 @@ struct DeltaCall {
     DeltaCall(ycge_ctx *c, const AnsiRequest &r_) : X(c->chexels), r(r_), key{r_.cw, r_.ch, r_.vx, r_.vy, r_.fg, r_.bg, c->fbW, c->fbH}
     {
         if (r.delta)
-            keyframe = !X.delta_valid || X.delta_rgb != r.rgb || !X.delta_held[X.delta_prev].p || std::memcmp(key, X.delta_key, sizeof key) != 0 || r.clear || r.keyframe ||
-                       X.delta_layered != (X.layers.n > 0) || (X.layers.n > 0 && (!X.comp_held[X.delta_prev].p || !X.glyph_held[X.delta_prev].p));
+            keyframe = !X.delta_valid || X.delta_rgb != r.rgb || X.delta_quad != r.quad || (!r.quad && !X.delta_held[X.delta_prev].p) ||
+                       std::memcmp(key, X.delta_key, sizeof key) != 0 || r.clear || r.keyframe || X.delta_layered != (X.layers.n > 0) ||
+                       ((X.layers.n > 0 || r.quad) && (!X.comp_held[X.delta_prev].p || !X.glyph_held[X.delta_prev].p));
         else
             X.delta_valid = false;
     }
@@ -214,7 +225,7 @@ struct DeltaCall {
     void commit()
     {
         if (!r.delta) return;
-        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = r.rgb; X.delta_layered = X.layers.n > 0;
+        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = r.rgb; X.delta_quad = r.quad; X.delta_layered = X.layers.n > 0;
         std::memcpy(X.delta_key, key, sizeof key);
         done = true;
     }
@@ -269,6 +280,7 @@ int frame(ycge_ctx *c, const char *fn, const AnsiRequest &r, uint8_t *out_stream
     if (!c) return YCGE_ERR_INVALID_ARG;
     unsigned long long bound = 0;
     int rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
+    if (rc == YCGE_OK && r.quad) rc = check_quadrant_call(c, fn, r.min_contrast);
     if (rc == YCGE_OK) rc = check_post_frame(c);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -551,33 +563,37 @@ int set_layers(ycge_ctx *c, const ycge_console_layer *layers, int32_t n, int32_t
 // and previous composite, with the geometry, defaults and refusals of the frame calls.  delta: a _delta call's rules - a NULL previous
 // composite or a clear_screen gives the keyframe.  Stateless: layer store and planes of its own; the context's layers, request and delta
 // state are untouched.  out_colours / out_glyphs (or NULL): the next composite - this call's, in a 24-bit delta emitted ? cur : shown
-int test_layers(ycge_ctx *c, const AnsiRequest &r, const uint8_t *plane, int32_t fbW, int32_t fbH, const ycge_console_layer *layers, int32_t n, int32_t raytrace_at,
-                const uint8_t *prev_colours, const uint16_t *prev_glyphs, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
-                uint8_t *out_colours, uint16_t *out_glyphs)
+// The quadrant hooks (r.quad) come through here with frame_glyphs, the framebuffer's fbW * fbH code units, and no layers (n = 0)
+int test_layers(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t *plane, const uint16_t *frame_glyphs, int32_t fbW, int32_t fbH,
+                const ycge_console_layer *layers, int32_t n, int32_t raytrace_at, const uint8_t *prev_colours, const uint16_t *prev_glyphs, uint8_t *out_stream,
+                size_t capacity, size_t *out_len, uint32_t *out_info, uint8_t *out_colours, uint16_t *out_glyphs)
 {
     if (!c) return YCGE_ERR_INVALID_ARG;
-    const char *fn = "ycge_test_ansi_layers";
-    if (!plane || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
-        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (plane %p, %d x %d)", fn, (const void *)plane, fbW, fbH);
+    if (!plane || (r.quad && !frame_glyphs) || fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (plane %p, glyphs %p, %d x %d)", fn, (const void *)plane, (const void *)frame_glyphs, fbW, fbH);
     unsigned long long bound = 0;
     uint64_t cells = 0;
     int rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
     if (rc == YCGE_OK) rc = check_layers(c, fn, layers, n, raytrace_at, cells);
     if (rc != YCGE_OK) return rc;
-    if (n == 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: n = 0 (the unlayered streams have hooks of their own)", fn);
+    if (n == 0 && !r.quad) return c->fail(YCGE_ERR_INVALID_ARG, "%s: n = 0 (the unlayered streams have hooks of their own)", fn);
     HIP_TRY(c, hipSetDevice(c->device));
     ChexelState &X = c->chexels;
     rc = ensure_ansi(c, X, r, bound, c->stream);
     if (rc != YCGE_OK) return rc;
     LayerStore S;
-    rc = build_layers(c, X, layers, n, raytrace_at, cells, S);
+    if (n > 0) rc = build_layers(c, X, layers, n, raytrace_at, cells, S);
     if (rc != YCGE_OK) return rc;
     const bool full = !r.delta || !prev_colours || !prev_glyphs || r.clear;
     const size_t console = (size_t)r.cw * (size_t)r.ch, bytes = (r.rgb ? 8 : 2) * console, fb_bytes = (r.rgb ? 8 : 2) * (size_t)fbW * fbH;
     DevBuf<uint8_t> in, comp, held, next;
-    DevBuf<uint16_t> comp_glyph, held_glyph;
+    DevBuf<uint16_t> comp_glyph, held_glyph, in_glyph;
     HIP_TRY(c, in.alloc(fb_bytes));
     HIP_TRY(c, hipMemcpy(in.p, plane, fb_bytes, hipMemcpyHostToDevice));
+    if (r.quad) {
+        HIP_TRY(c, in_glyph.alloc((size_t)fbW * fbH));
+        HIP_TRY(c, hipMemcpy(in_glyph.p, frame_glyphs, (size_t)fbW * fbH * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
     HIP_TRY(c, comp.alloc(bytes));
     HIP_TRY(c, comp_glyph.alloc(console));
     if (!full) {
@@ -589,7 +605,7 @@ int test_layers(ycge_ctx *c, const AnsiRequest &r, const uint8_t *plane, int32_t
     }
     ycge_ansi::LayersRun L = layers_run(S, r.rgb);
     L.comp = comp.p; L.comp_glyph = comp_glyph.p; L.prev = held.p; L.prev_glyph = held_glyph.p; L.next = next.p;
-    rc = launch(c, X, c->stream, r, !full, in.p, nullptr, nullptr, fbW, fbH, &L);
+    rc = launch(c, X, c->stream, r, !full, in.p, nullptr, nullptr, fbW, fbH, &L, nullptr, in_glyph.p);
     if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     rc = deliver(c, X, fn, full, bound, out_stream, out_len, r.delta ? out_info : nullptr);
@@ -609,6 +625,14 @@ AnsiRequest request(bool rgb, int32_t cw, int32_t ch, int32_t vx, int32_t vy, in
 AnsiRequest with_delta(AnsiRequest r, int32_t merge_gap, int32_t tolerance, int32_t keyframe)
 {
     r.delta = true; r.gap = merge_gap; r.tolerance = tolerance; r.keyframe = keyframe != 0;
+    return r;
+}
+
+// the quadrant-glyph family: 24-bit colour, the fit under min_contrast
+AnsiRequest quad_request(int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear, int32_t min_contrast)
+{
+    AnsiRequest r = request(true, cw, ch, vx, vy, fg, bg, clear);
+    r.quad = true; r.min_contrast = min_contrast;
     return r;
 }
 
@@ -713,6 +737,49 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// The quadrant-glyph forms (the contract: include/ycge.h): the 24-bit calls with the fitted glyph and colours for '▀', top, bottom
+int ycge_render_frame_ansi_quad(ycge_ctx *c, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                                int32_t default_bg16, int32_t clear_screen, int32_t min_contrast, uint8_t *out_stream, size_t capacity, size_t *out_len,
+                                float *out_top_bottom_sdr, ycge_frame_stats *st)
+try {
+    return frame(c, "ycge_render_frame_ansi_quad", quad_request(console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, min_contrast),
+                 out_stream, capacity, out_len, nullptr, out_top_bottom_sdr, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_render_frame_ansi_quad_delta(ycge_ctx *c, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16,
+                                      int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance, int32_t keyframe, int32_t min_contrast,
+                                      uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr, ycge_frame_stats *st)
+try {
+    const AnsiRequest r = quad_request(console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, min_contrast);
+    return frame(c, "ycge_render_frame_ansi_quad_delta", with_delta(r, merge_gap, tolerance, keyframe), out_stream, capacity, out_len, out_info, out_top_bottom_sdr, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hooks: the quadrant streams' kernels alone on caller-given planes of the fbW x fbH framebuffer - glyphs, fbW * fbH code units, and
+// rgba, fbW x 2 fbH RGBA8 with row 2 cy the foreground - with the geometry, defaults and refusals of the frame calls and no layers.  The
+// delta: shown_colours / shown_glyphs are the console-wide composite the terminal shows (cw x 2 ch RGBA8, cw * ch code units; either NULL,
+// or clear_screen: the keyframe), out_shown_colours / out_shown_glyphs (or NULL) receive the next such.  Stateless
+int ycge_test_ansi_quad_stream(ycge_ctx *c, const uint16_t *glyphs, const uint8_t *rgba, int32_t fbW, int32_t fbH, int32_t console_w, int32_t console_h,
+                               int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, uint8_t *out_stream,
+                               size_t capacity, size_t *out_len)
+try {
+    const AnsiRequest r = quad_request(console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, 0);
+    return test_layers(c, "ycge_test_ansi_quad_stream", r, rgba, glyphs, fbW, fbH, nullptr, 0, 0, nullptr, nullptr, out_stream, capacity, out_len, nullptr, nullptr, nullptr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_test_ansi_quad_delta(ycge_ctx *c, const uint8_t *shown_colours, const uint16_t *shown_glyphs, const uint16_t *glyphs, const uint8_t *rgba, int32_t fbW,
+                              int32_t fbH, int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16,
+                              int32_t clear_screen, int32_t merge_gap, int32_t tolerance, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
+                              uint8_t *out_shown_colours, uint16_t *out_shown_glyphs)
+try {
+    const AnsiRequest r = quad_request(console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, 0);
+    return test_layers(c, "ycge_test_ansi_quad_delta", with_delta(r, merge_gap, tolerance, 0), rgba, glyphs, fbW, fbH, nullptr, 0, 0, shown_colours, shown_glyphs,
+                       out_stream, capacity, out_len, out_info, out_shown_colours, out_shown_glyphs);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 // The four frame forms with frames in flight (the contract: include/ycge.h): queued, delivered on the device, the caller's after ycge_wait
 int ycge_render_frame_async_ansi(ycge_ctx *c, const ycge_ansi_async *req, uint8_t *out_stream, size_t capacity, ycge_ansi_async_result *out_result,
                                  float *out_top_bottom_sdr)
@@ -790,7 +857,7 @@ int ycge_test_ansi_layers(ycge_ctx *c, int32_t rgb, const uint8_t *plane, int32_
 try {
     AnsiRequest r = request(rgb != 0, console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen);
     if (delta) r = with_delta(r, merge_gap, rgb ? tolerance : 0, 0);
-    return test_layers(c, r, plane, fbW, fbH, layers, n, raytrace_at, prev_colours, prev_glyphs, out_stream, capacity, out_len, out_info, out_colours, out_glyphs);
+    return test_layers(c, "ycge_test_ansi_layers", r, plane, nullptr, fbW, fbH, layers, n, raytrace_at, prev_colours, prev_glyphs, out_stream, capacity, out_len, out_info, out_colours, out_glyphs);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

@@ -78,6 +78,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "ycge_ansi_layers.h"
 
@@ -122,6 +123,12 @@ struct PlaneGlyph { static constexpr bool kPlane = true; };
 // a colour policy over the composite of a layered console
 template <class C>
 struct Layered : C { using Glyph = PlaneGlyph; };
+
+// A policy derived from FrameGlyphs too: the raytrace framebuffer's chexels carry a glyph of their own (the quadrant fit's, fbW * fbH code
+// units, none of them ' ') where any other policy's are '▀'.  k_compose alone reads them; the streams of such a composite are Layered<C>'s.
+struct FrameGlyphs {};
+template <class C>
+constexpr bool kFrameGlyphs = std::is_base_of<FrameGlyphs, C>::value;
 
 // console cell (x, y) lies on the framebuffer; o: where its colours start in a plane
 template <class C>
@@ -515,7 +522,11 @@ __global__ __launch_bounds__(kAnsiBlock) void k_compose(ComposeArgs<typename C::
     for (int s = g.n_layers; s >= 0 && !found; s--) {
         if (s == g.raytrace_at) {
             size_t o;
-            if (covered_at<C>(g.a, x, y, o)) { C::load(g.a.plane + o, g.a, fg, bg); ch = 0x2580u; found = true; }
+            if (covered_at<C>(g.a, x, y, o)) {
+                C::load(g.a.plane + o, g.a, fg, bg);
+                ch = kFrameGlyphs<C> ? (uint32_t)g.a.glyph[(size_t)((int64_t)y - g.a.vy) * (uint32_t)g.a.fbW + (size_t)((int64_t)x - g.a.vx)] : 0x2580u;
+                found = true;
+            }
             continue;
         }
         const LayerRect &r = g.rect[s < g.raytrace_at ? s : s - 1];
@@ -588,10 +599,11 @@ int launch_delta(typename C::Delta d, const uint8_t *plane, const uint8_t *prev,
 }
 
 // the layered forms: the compose pass into L.comp / L.comp_glyph, then the kernels above over the composite.  false: a LayersRun no kernel may see
+// (frame_only: a composite of the raytrace framebuffer alone is allowed - the quadrant streams', whose every stream is a composite's)
 template <typename T>
-bool fill_compose(ComposeArgs<T> &g, const LayersRun &L, int ch, bool delta)
+bool fill_compose(ComposeArgs<T> &g, const LayersRun &L, int ch, bool delta, bool frame_only = false)
 {
-    if (L.n <= 0 || L.n > kMaxLayers || L.raytrace_at < 0 || L.raytrace_at > L.n || !L.colours || !L.glyphs || !L.comp || !L.comp_glyph ||
+    if (L.n < 0 || (L.n == 0 && !frame_only) || L.n > kMaxLayers || L.raytrace_at < 0 || L.raytrace_at > L.n || (L.n > 0 && (!L.colours || !L.glyphs)) || !L.comp || !L.comp_glyph ||
         (uintptr_t)L.colours % alignof(T) || (uintptr_t)L.comp % alignof(T) || (delta && (!L.prev || !L.prev_glyph || (uintptr_t)L.prev % alignof(T))))
         return false;
     for (int k = 0; k < L.n; k++) {
@@ -606,10 +618,11 @@ bool fill_compose(ComposeArgs<T> &g, const LayersRun &L, int ch, bool delta)
     return true;
 }
 
+// frame_glyph: the raytrace framebuffer's code units, for a policy with FrameGlyphs alone
 template <class C>
-void launch_compose(ComposeArgs<typename C::Plane> &g, hipStream_t stream)
+void launch_compose(ComposeArgs<typename C::Plane> &g, hipStream_t stream, const uint16_t *frame_glyph = nullptr)
 {
-    g.a.glyph = nullptr;
+    g.a.glyph = kFrameGlyphs<C> ? frame_glyph : nullptr;
     hipLaunchKernelGGL(k_compose<C>, dim3((g.a.n + (uint32_t)kAnsiBlock - 1u) / (uint32_t)kAnsiBlock), dim3(kAnsiBlock), 0, stream, g);
 }
 
@@ -621,16 +634,18 @@ void composite_args(StreamArgs<T> &a, const ComposeArgs<T> &g, int ch)
     a.plane = g.out; a.fbW = g.a.cw; a.fbH = ch; a.vx = 0; a.vy = 0; a.glyph = g.out_glyph;
 }
 
-// launch_stream's arguments and the layers: four launches on `stream`
-template <class C>
+// launch_stream's arguments and the layers: four launches on `stream`.  CC: the compose pass's policy, C or one derived from it with
+// FrameGlyphs (frame_glyph: its code units; the layers may then be none)
+template <class C, class CC = C>
 int launch_layered_stream(const LayersRun &L, const uint8_t *plane, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg, int clear,
-                          uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream)
+                          uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream, const uint16_t *frame_glyph = nullptr)
 {
     using T = typename C::Plane;
     ComposeArgs<T> g;
-    if (!fill_args(g.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !fill_compose(g, L, ch, false) || !tiles || !out || !out_len || cap > 0xffffffffull)
+    if (!fill_args(g.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !fill_compose(g, L, ch, false, kFrameGlyphs<CC>) || !tiles || !out || !out_len ||
+        cap > 0xffffffffull || (kFrameGlyphs<CC> && !frame_glyph))
         return (int)hipErrorInvalidValue;
-    launch_compose<C>(g, stream);
+    launch_compose<CC>(g, stream, frame_glyph);
     StreamArgs<T> a;
     composite_args(a, g, ch);
     const uint32_t n_tiles = tiles_of(a.n);
@@ -641,16 +656,17 @@ int launch_layered_stream(const LayersRun &L, const uint8_t *plane, int fbW, int
 }
 
 // launch_delta's arguments and the layers: the composite against L.prev / L.prev_glyph.  Four launches on `stream`
-template <class C>
+template <class C, class CC = C>
 int launch_layered_delta(typename C::Delta d, const LayersRun &L, const uint8_t *plane, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                         int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream)
+                         int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream,
+                         const uint16_t *frame_glyph = nullptr)
 {
     using T = typename C::Plane;
     ComposeArgs<T> g;
-    if (!fill_args(g.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !fill_compose(g, L, ch, true) || gap < 0 || gap > kGapMax || !tiles || !out || !res ||
-        cap > 0xffffffffull)
+    if (!fill_args(g.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !fill_compose(g, L, ch, true, kFrameGlyphs<CC>) || gap < 0 || gap > kGapMax || !tiles ||
+        !out || !res || cap > 0xffffffffull || (kFrameGlyphs<CC> && !frame_glyph))
         return (int)hipErrorInvalidValue;
-    launch_compose<C>(g, stream);
+    launch_compose<CC>(g, stream, frame_glyph);
     composite_args(d.a, g, ch);
     d.prev = reinterpret_cast<const T *>(L.prev); d.prev_glyph = L.prev_glyph; d.gap = gap;
     const uint32_t n_tiles = tiles_of(d.a.n);

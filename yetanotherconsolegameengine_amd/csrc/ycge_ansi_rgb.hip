@@ -104,7 +104,31 @@ struct Rgb {
     }
 };
 
+// the quadrant-glyph streams' compose policy: Rgb, the raytrace framebuffer's chexels carrying the fitted glyph (k_fit_quadrants) for '▀'
+struct RgbQuad : Rgb, FrameGlyphs {};
+
 } // namespace
+
+// The quadrant-glyph forms (ycge_render_frame_ansi_quad / _quad_delta): the layered 24-bit streams above with `glyphs`, the fbW * fbH code
+// units k_fit_quadrants wrote beside the plane `rgba`, as the raytrace framebuffer's characters.  Every such stream is a composite's, so L
+// may hold no layer (n = 0: colours and glyphs unread).  One new instance, k_compose<RgbQuad>; the stream kernels are Layered<Rgb>'s.
+extern "C" int ycge_launch_ansi_quad_stream(const LayersRun *L, const uint8_t *rgba, const uint16_t *glyphs, int fbW, int fbH, int cw, int ch, int vx, int vy,
+                                            const uint8_t *palette, int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap,
+                                            unsigned long long *out_len, hipStream_t stream)
+{
+    if (!L) return (int)hipErrorInvalidValue;
+    return launch_layered_stream<Rgb, RgbQuad>(*L, rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, clear, tiles, out, cap, out_len, stream, glyphs);
+}
+
+extern "C" int ycge_launch_ansi_quad_delta(const LayersRun *L, const uint8_t *rgba, const uint16_t *glyphs, int fbW, int fbH, int cw, int ch, int vx, int vy,
+                                           const uint8_t *palette, int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap,
+                                           unsigned long long *res, hipStream_t stream)
+{
+    if (!L || !L->next || L->next == L->prev || L->next == L->comp || ((uintptr_t)L->next & 3u) || tol < 0 || tol > 255) return (int)hipErrorInvalidValue;
+    Rgb::Delta d{};
+    d.next = reinterpret_cast<uint32_t *>(L->next); d.tol = tol;
+    return launch_layered_delta<Rgb, RgbQuad>(d, *L, rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream, glyphs);
+}
 
 // the 24-bit stream of a cw x ch console over a fbW x 2 fbH RGBA plane at (vx, vy); palette: the 8 x 2 RGBA plane of the 16 palette colours,
 // dfg / dbg their selection (0..15).  tiles: ycge_launch_ansi_tiles(cw * ch) words; out: cap bytes, at least the stream's bound (< 2^32);

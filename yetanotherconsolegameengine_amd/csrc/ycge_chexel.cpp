@@ -77,6 +77,14 @@ struct ChexelLayout {
 
 namespace ycge_host {
 
+int check_quadrant_call(ycge_ctx *c, const char *fn, int32_t min_contrast)
+{
+    if (c->ss < 2 || (c->ss & 1))
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: super_sample %d (the quadrants halve a chexel's columns: it must be even)", fn, c->ss);
+    if (min_contrast < 0 || min_contrast > 255) return c->fail(YCGE_ERR_INVALID_ARG, "%s: min_contrast %d (0..255)", fn, min_contrast);
+    return YCGE_OK;
+}
+
 int ensure_tables(ycge_ctx *c, ChexelState &X)
 {
     if (X.tables.p) return YCGE_OK;
@@ -95,13 +103,26 @@ int chexel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked, co
     ChexelState *X = &c->chexels;
     uint8_t *const *dst = asked.chexels;
     const bool ansi = asked.ansi != nullptr;                                             // (ycge_render_frame_ansi: the pairs stay on the device)
-    if (!dst[0] && !dst[1] && !dst[2] && !ansi) return YCGE_OK;                          // (the SDR alone: nothing to encode)
+    const bool quad = asked.quad || (ansi && asked.ansi->quad);                          // (the quadrant calls: the fit's planes for the encoder's)
+    if (!dst[0] && !dst[1] && !dst[2] && !ansi && !quad) return YCGE_OK;                 // (the SDR alone: nothing to encode)
     // (frames in flight: the stream buffers are one set per context - this frame's encode .. deliver follows the deliver of the frame before)
     if (ansi && X->flight_pending && X->flight_stream != stream) HIP_TRY(c, hipStreamWaitEvent(stream, X->flight_ev, 0));
     const ChexelLayout L((size_t)c->fbW * c->fbH);
     DevBuf<uint8_t> &out = X->out[second ? 1 : 0];
     if (out.cap < L.total) HIP_TRY(c, out.alloc(L.total));
-    if (dst[1] || dst[2] || ansi) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
+    if (dst[1] || dst[2] || ansi || quad) { const int rc = ensure_tables(c, *X); if (rc != YCGE_OK) return rc; }
+    if (quad) {
+        // k_tonemap_quadrants on the buffer and exposure state the tonemap in front of this read, then the fit: the glyph plane, and the RGBA
+        // plane where the encoder's lies.  The held planes of a _quad_delta call are the composite's (ycge_ansi.cpp), so nothing moves here.
+        if (X->quad_sdr.cap < 12 * L.n) HIP_TRY(c, X->quad_sdr.alloc(12 * L.n));
+        if (X->quad_glyphs.cap < L.n) HIP_TRY(c, X->quad_glyphs.alloc(L.n));
+        int e = ycge_launch_tonemap_quadrants(c->denoised, c->hiW, c->fbW, c->fbH, c->ss, 2.2f, 2.0f, 0.0f, c->tone_state.p, X->quad_sdr.p, stream);
+        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_tonemap_quadrants launch failed: %s", hipGetErrorString((hipError_t)e));
+        e = ycge_launch_quadrant_fit(X->quad_sdr.p, c->fbW, c->fbH, X->tables.p, asked.quad ? asked.quad->min_contrast : asked.ansi->min_contrast, X->quad_glyphs.p,
+                                     out.p + L.rgba, c->compute_units, stream);
+        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_fit_quadrants launch failed: %s", hipGetErrorString((hipError_t)e));
+        return YCGE_OK;
+    }
     const bool rgb = ansi && asked.ansi->rgb;                                            // (a 24-bit stream: the RGBA plane stays on the device instead)
     uint8_t *pairs = out.p + L.ansi, *rgba = out.p + L.rgba;
     if (ansi && asked.ansi->delta) {                                                     // (a _delta call: the pairs go where the next call finds them;
@@ -117,10 +138,33 @@ int chexel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked, co
     return YCGE_OK;
 }
 
+// ycge_render_frame_quadrants' copies: the sub-cell colours, the glyph plane, the fitted RGBA plane - pageable destinations staged one
+// behind the other, as below
+static int quadrants_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, bool second)
+{
+    ChexelState *X = &c->chexels;
+    const ChexelLayout L((size_t)c->fbW * c->fbH);
+    void *dst[3] = {out.quad->sdr, out.quad->glyphs, out.quad->rgba};
+    const void *src[3] = {X->quad_sdr.p, X->quad_glyphs.p, X->out[second ? 1 : 0].p + L.rgba};
+    const size_t bytes[3] = {48 * L.n, 2 * L.n, 8 * L.n}, off[3] = {0, 48 * L.n, 56 * L.n};          // (48 n and 56 n: multiples of 8)
+    size_t staged = 0;
+    for (int k = 0; k < 3; k++)
+        if (dst[k] && !host_memory_is_page_locked(dst[k], bytes[k])) staged = off[k] + bytes[k];
+    HIP_TRY(c, X->stage.reserve(staged));
+    for (int k = 0; k < 3; k++) {
+        if (!dst[k]) continue;
+        void *target = dst[k];
+        if (!host_memory_is_page_locked(dst[k], bytes[k])) target = out.redirect(dst[k], X->stage.data() + off[k], bytes[k]);
+        HIP_TRY(c, hipMemcpyAsync(target, src[k], bytes[k], hipMemcpyDeviceToHost, stream));
+    }
+    return YCGE_OK;
+}
+
 int chexel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, bool second)
 {
     ChexelState *X = &c->chexels;
     uint8_t *const *dst = out.chexels;
+    if (out.quad) return quadrants_read_back(c, stream, out, second);
     if (!dst[0] && !dst[1] && !dst[2] && !out.ansi) return YCGE_OK;
     const ChexelLayout L((size_t)c->fbW * c->fbH);
     const size_t off[3] = {L.c16, L.ansi, L.rgba}, bytes[3] = {L.n, 2 * L.n, 8 * L.n};
@@ -138,7 +182,7 @@ int chexel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, bool se
     }
     if (!out.ansi) return YCGE_OK;
     // (ycge_ansi.cpp: the escape stream and its length from the pairs - 24-bit: the RGBA plane - where chexel_encode put them)
-    const bool held = out.ansi->delta && (out.keyframe || !out.ansi->rgb);
+    const bool held = out.ansi->delta && !out.ansi->quad && (out.keyframe || !out.ansi->rgb);
     return ansi_enqueue(c, stream, out, held ? X->delta_held[1 - X->delta_prev].p : src + (out.ansi->rgb ? L.rgba : L.ansi));
 }
 
@@ -165,6 +209,25 @@ try {
     int rc = check_chexel_call(c, "ycge_render_frame_chexels", out);
     if (rc == YCGE_OK) rc = check_post_frame(c);
     return rc == YCGE_OK ? render_frame_sync(c, &out, st) : rc;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// The quadrant-glyph planes (the contract: include/ycge.h): ycge_render_frame_chexels' frame with k_tonemap_quadrants and k_fit_quadrants
+// behind the tonemap for the encoder
+int ycge_render_frame_quadrants(ycge_ctx *c, float *out_top_bottom_sdr, float *out_quad_sdr, uint16_t *out_glyphs, uint8_t *out_rgba, int32_t min_contrast,
+                                ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_render_frame_quadrants";
+    if (!out_top_bottom_sdr && !out_quad_sdr && !out_glyphs && !out_rgba)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, quad_sdr, glyphs, rgba)", fn);
+    int rc = check_quadrant_call(c, fn, min_contrast);
+    if (rc == YCGE_OK) rc = check_post_frame(c);
+    if (rc != YCGE_OK) return rc;
+    const FrameOutputs::Quadrants q{out_quad_sdr, out_glyphs, out_rgba, min_contrast};
+    FrameOutputs out(out_top_bottom_sdr);
+    if (out_quad_sdr || out_glyphs || out_rgba) out.quad = &q;          // (the SDR alone: ycge_render_frame's frame)
+    return render_frame_sync(c, &out, st);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
@@ -239,6 +302,55 @@ try {
     return YCGE_OK;
 }
 catch (...) { return ycge_host::abi_catch(nullptr); }
+
+// test hook: k_tonemap_quadrants alone on a caller-given hi-res buffer (fbH*2*ss rows of fbW*ss pixels) and exposure, whatever the context's
+// framebuffer is.  Buffers and a tone state of its own on the context's device and stream: no frame state is touched
+int ycge_test_quadrant_sdr(ycge_ctx *c, const float *hdr, int32_t fbW, int32_t fbH, int32_t ss, float exposure, float *out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!hdr || !out || fbW <= 0 || fbH <= 0 || ss < 2 || ss > 64 || (ss & 1) || (int64_t)fbW * fbH * ss * ss > ((int64_t)1 << 26))
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_quadrant_sdr: bad arguments (%d x %d chexels, super_sample %d: even, 2..64)", fbW, fbH, ss);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)fbW * fbH, hi = n * 2 * ss * ss;
+    DevBuf<float> in, quad; DevBuf<uint8_t> state;
+    HIP_TRY(c, in.alloc(3 * hi));
+    HIP_TRY(c, quad.alloc(12 * n));
+    HIP_TRY(c, state.alloc(ycge_post_state_bytes()));
+    uint32_t init[6] = {0, 0, 0, 0, 0, 0};
+    if (ycge_post_state_bytes() != sizeof init) return c->fail(YCGE_ERR_INTERNAL, "ycge_test_quadrant_sdr: the tone state is %zu bytes, not %zu", ycge_post_state_bytes(), sizeof init);
+    std::memcpy(&init[0], &exposure, 4); std::memcpy(&init[1], &exposure, 4);          // {aeExposure, effective}: as ycge_test_post_stage
+    HIP_TRY(c, hipMemcpy(state.p, init, sizeof init, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(in.p, hdr, 3 * hi * sizeof(float), hipMemcpyHostToDevice));
+    const int e = ycge_launch_tonemap_quadrants(in.p, fbW * ss, fbW, fbH, ss, 2.2f, 2.0f, 0.0f, state.p, quad.p, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_tonemap_quadrants launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return copy_out(c, out, quad.p, 12 * n * sizeof(float));
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: k_fit_quadrants alone on n caller-given cells of sub-cell colours, as an n x 1 framebuffer: out_rgba gets n foreground words, then
+// n background words.  Either output may be NULL, not both
+int ycge_test_quadrant_fit(ycge_ctx *c, const float *quad_sdr, int32_t n, int32_t min_contrast, uint16_t *out_glyphs, uint8_t *out_rgba)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!quad_sdr || n <= 0 || n > (1 << 26) || (!out_glyphs && !out_rgba) || min_contrast < 0 || min_contrast > 255)
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_quadrant_fit: bad arguments (n = %d, min_contrast = %d)", n, min_contrast);
+    HIP_TRY(c, hipSetDevice(c->device));
+    { const int rc = ensure_tables(c, c->chexels); if (rc != YCGE_OK) return rc; }
+    DevBuf<float> in; DevBuf<uint16_t> glyphs; DevBuf<uint8_t> rgba;
+    HIP_TRY(c, in.alloc(12 * (size_t)n));
+    HIP_TRY(c, glyphs.alloc((size_t)n));
+    HIP_TRY(c, rgba.alloc(8 * (size_t)n));
+    HIP_TRY(c, hipMemcpy(in.p, quad_sdr, 12 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    const int e = ycge_launch_quadrant_fit(in.p, n, 1, c->chexels.tables.p, min_contrast, glyphs.p, rgba.p, c->compute_units, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_fit_quadrants launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = YCGE_OK;
+    if (out_glyphs) rc = copy_out(c, out_glyphs, glyphs.p, 2 * (size_t)n);
+    if (out_rgba && rc == YCGE_OK) rc = copy_out(c, out_rgba, rgba.p, 8 * (size_t)n);
+    return rc;
+}
+catch (...) { return ycge_host::abi_catch(c); }
 
 // test hook: k_encode_chexels on caller-given SDR values (w x h chexels of {top rgb, bottom rgb}); any NULL output is skipped.  On the
 // context's device and stream, with buffers of its own; returns with the bytes in the caller's arrays.

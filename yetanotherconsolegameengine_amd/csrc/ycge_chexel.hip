@@ -122,7 +122,86 @@ __global__ __launch_bounds__(kChexelBlock) void k_encode_chexels(const float *__
     }
 }
 
+// The quadrant-glyph fit (the contract: include/ycge.h at ycge_render_frame_quadrants): one lane a chexel reads its four sub-cell colours
+// {TL, TR, BL, BR} (k_tonemap_quadrants), takes their sRGB8 bytes as half_cell does, and picks the quadrant block glyph and the two colours
+// that approximate the four with the least squared error.  All integer from the bytes on.  Mask m in 0..7: bit 0 = TL, bit 1 = TR, bit 2 = BL
+// in the foreground, BR always background.  With S_F / S_B the channel sums over foreground / background, minimising the error is maximising
+// |S_B|^2 / |B| + |S_F|^2 / |F|; w(n) = 12 / n makes that an int32 (below 2^24).  Ties go to the smallest m.
+__constant__ uint16_t c_quadrant_glyph[8] = {0x2580, 0x2598, 0x259d, 0x2580, 0x2596, 0x258c, 0x259e, 0x259b};
+
+__global__ __launch_bounds__(kChexelBlock) void k_fit_quadrants(const float *__restrict__ quad, uint32_t fbW, uint32_t n, const uint8_t *__restrict__ tables,
+                                                                int32_t min_contrast, uint16_t *__restrict__ glyph_out, uint32_t *__restrict__ rgba_out)
+{
+    __shared__ float t32[256];
+    t32[threadIdx.x] = reinterpret_cast<const float *>(tables)[threadIdx.x];
+    __syncthreads();
+    const uint32_t stride = gridDim.x * kChexelBlock;
+    for (uint32_t i = blockIdx.x * kChexelBlock + threadIdx.x; i < n; i += stride) {
+        const float4 *p = reinterpret_cast<const float4 *>(quad + (size_t)i * 12);
+        const float4 v0 = p[0], v1 = p[1], v2 = p[2];
+        const float x[12] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w};
+        int q[4][3], s0[3] = {0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) { q[k][c] = srgb8(t32, clamp01(x[3 * k + c])); s0[c] += q[k][c]; }
+        int contrast = 0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const int mean = (2 * s0[c] + 4) / 8;
+#pragma unroll
+            for (int k = 0; k < 4; k++) contrast = max(contrast, abs(q[k][c] - mean));
+        }
+        int best = 0;
+        if (contrast > min_contrast) {
+            int best_score = -1;
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const int nf = (m & 1) + (m >> 1 & 1) + (m >> 2 & 1), nb = 4 - nf;
+                int score = 0;
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const int sf = (m & 1 ? q[0][c] : 0) + (m & 2 ? q[1][c] : 0) + (m & 4 ? q[2][c] : 0), sb = s0[c] - sf;
+                    score += (12 / nb) * sb * sb + (nf ? (12 / nf) * sf * sf : 0);
+                }
+                if (score > best_score) { best_score = score; best = m; }
+            }
+        }
+        const int nf = (best & 1) + (best >> 1 & 1) + (best >> 2 & 1), nb = 4 - nf;
+        uint32_t fg = 0, bg = 0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const int sf = (best & 1 ? q[0][c] : 0) + (best & 2 ? q[1][c] : 0) + (best & 4 ? q[2][c] : 0), sb = s0[c] - sf;
+            const int b8 = (2 * sb + nb) / (2 * nb), f8 = nf ? (2 * sf + nf) / (2 * nf) : b8;
+            fg |= (uint32_t)f8 << (8 * c); bg |= (uint32_t)b8 << (8 * c);
+        }
+        if (glyph_out) glyph_out[i] = c_quadrant_glyph[best];
+        if (rgba_out) {
+            const uint32_t cy = i / fbW, cx = i - cy * fbW;
+            const size_t top = (size_t)(2 * cy) * fbW + cx;
+            rgba_out[top] = fg | 0xff000000u;
+            rgba_out[top + fbW] = bg | 0xff000000u;
+        }
+    }
+}
+
 } // namespace
+
+// k_fit_quadrants on the fbW x fbH chexels' sub-cell colours (12 floats a chexel, 16-byte aligned): glyphs fbW*fbH code units, rgba the
+// plane of k_encode_chexels' layout, row 2 cy the foreground and row 2 cy + 1 the background; either may be NULL, not both
+extern "C" int ycge_launch_quadrant_fit(const float *quad, int fbW, int fbH, const uint8_t *tables, int min_contrast, uint16_t *glyphs, uint8_t *rgba,
+                                        int compute_units, hipStream_t stream)
+{
+    if (fbW <= 0 || fbH <= 0 || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 2 || !quad || ((uintptr_t)quad & 15u) || !tables || (!glyphs && !rgba) ||
+        ((uintptr_t)rgba & 3u) || ((uintptr_t)glyphs & 1u) || min_contrast < 0 || min_contrast > 255)
+        return (int)hipErrorInvalidValue;
+    const uint32_t n = (uint32_t)fbW * (uint32_t)fbH;
+    const uint32_t need = (n + kChexelBlock - 1) / kChexelBlock;
+    const uint32_t cap = (uint32_t)(compute_units > 0 ? compute_units : 256) * 8u;
+    hipLaunchKernelGGL(k_fit_quadrants, dim3(need < cap ? need : cap), dim3(kChexelBlock), 0, stream, quad, (uint32_t)fbW, n, tables, (int32_t)min_contrast, glyphs,
+                       reinterpret_cast<uint32_t *>(rgba));
+    return (int)hipGetLastError();
+}
 
 extern "C" int ycge_launch_chexels(const float *sdr, int fbW, int fbH, const uint8_t *tables, uint8_t *c16, uint8_t *ansi, uint8_t *rgba,
                                    int compute_units, hipStream_t stream)

@@ -111,6 +111,10 @@ int ycge_launch_unpermute(const float *all_slabs, size_t slab_floats_per_rank, i
                           int slab_floats, float *hdr, float *albedo, float *normal, float *depth, uint8_t *sky, hipStream_t stream);
 uint32_t ycge_launch_query_lanes(int has_grid, int occluded, int compute_units);
 int ycge_launch_chexels(const float *sdr, int fbW, int fbH, const uint8_t *tables, uint8_t *c16, uint8_t *ansi, uint8_t *rgba, int compute_units, hipStream_t stream);
+int ycge_launch_tonemap_quadrants(const float *hdr, int hiW, int fbW, int fbH, int ss, float gamma, float saturation, float vibrance, const void *state,
+                                  float *out, hipStream_t stream);
+int ycge_launch_quadrant_fit(const float *quad, int fbW, int fbH, const uint8_t *tables, int min_contrast, uint16_t *glyphs, uint8_t *rgba, int compute_units,
+                             hipStream_t stream);
 uint32_t ycge_launch_ansi_tiles(uint32_t cells);
 int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
                             int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
@@ -130,6 +134,12 @@ int ycge_launch_ansi_rgb_layers_stream(const ycge_ansi::LayersRun *L, const uint
 int ycge_launch_ansi_rgb_layers_delta(const ycge_ansi::LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
                                       int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
                                       hipStream_t stream);
+int ycge_launch_ansi_quad_stream(const ycge_ansi::LayersRun *L, const uint8_t *rgba, const uint16_t *glyphs, int fbW, int fbH, int cw, int ch, int vx, int vy,
+                                 const uint8_t *palette, int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap,
+                                 unsigned long long *out_len, hipStream_t stream);
+int ycge_launch_ansi_quad_delta(const ycge_ansi::LayersRun *L, const uint8_t *rgba, const uint16_t *glyphs, int fbW, int fbH, int cw, int ch, int vx, int vy,
+                                const uint8_t *palette, int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap,
+                                unsigned long long *res, hipStream_t stream);
 int ycge_launch_ansi_deliver(const uint8_t *src, const unsigned long long *res, unsigned long long capacity, int full, uint8_t *dst, void *record, uint32_t *sticky,
                              int groups, hipStream_t stream);
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
@@ -475,8 +485,10 @@ struct QueryState {
 };
 // one ANSI stream call (ycge_ansi.cpp): the colour form, the console, the viewport, the default colours, the clear-screen prefix; delta: a
 // _delta call, which alone reads gap, tolerance (24-bit colour only) and keyframe
+// quad: the quadrant-glyph family - 24-bit colour (rgb is set too) with the fitted glyph and colours of k_fit_quadrants under min_contrast
 struct AnsiRequest {
-    bool rgb = false;
+    bool rgb = false, quad = false;
+    int32_t min_contrast = 0;
     int32_t cw = 0, ch = 0, vx = 0, vy = 0, fg = 0, bg = 0;
     bool clear = false, delta = false;
     int32_t gap = 0, tolerance = 0;
@@ -500,6 +512,9 @@ struct LayerStore {
 struct FrameOutputs {
     float *sdr = nullptr;                              // the caller's destinations: the SDR array ...
     uint8_t *chexels[3] = {nullptr, nullptr, nullptr}; // ... c16, ansi pairs, rgba
+    // ycge_render_frame_quadrants: the caller's sub-cell colours (fbW*fbH*12 f32), glyph plane and fitted RGBA plane, any of them NULL
+    struct Quadrants { float *sdr; uint16_t *glyphs; uint8_t *rgba; int32_t min_contrast; };
+    const Quadrants *quad = nullptr;
     const AnsiRequest *ansi = nullptr;                 // the ANSI stream asked for (its encode keeps the pairs - 24-bit colour: the RGBA plane - on the device only)
     bool keyframe = true;                              // ... runs the full stream's kernels (a _delta call: what its DeltaCall decided)
     uint8_t *dev_stream = nullptr;                     // a frame in flight: the device aliases of the caller's page-locked stream buffer (dev_capacity bytes)
@@ -517,6 +532,8 @@ struct FrameOutputs {
 struct ChexelState {
     DevBuf<uint8_t> tables;                            // 256 f32 + 256 f64 thresholds
     DevBuf<uint8_t> out[2];                            // the encoded bytes, per post parity (as d_sdr / d_sdr2)
+    DevBuf<float> quad_sdr;                            // the quadrant calls: k_tonemap_quadrants' 12 floats a chexel ...
+    DevBuf<uint16_t> quad_glyphs;                      // ... and k_fit_quadrants' code units (its RGBA plane lies in out[], where k_encode_chexels' does)
     PinnedBuf stage;                                   // page-locked staging of pageable destinations (synchronous calls only)
     // the ANSI stream calls (ycge_ansi.cpp; kernels: ycge_ansi.hip, ycge_ansi_rgb.hip): the stream's buffers
     DevBuf<uint8_t> ansi_stream;                       // the stream (its bound)
@@ -532,7 +549,7 @@ struct ChexelState {
     // nothing is copied.  Whatever shows the terminal something else (a plain _ansi call, ycge_resize, a failure) clears delta_valid.
     DevBuf<uint8_t> delta_held[2];
     int delta_prev = 0;
-    bool delta_valid = false, delta_rgb = false;
+    bool delta_valid = false, delta_rgb = false, delta_quad = false;       // (delta_quad: the quadrant family, whose held state is the composite's alone)
     int32_t delta_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // {cw, ch, vx, vy, dfg, dbg, fbW, fbH}
     DevBuf<uint8_t> rgb_palette;                       // RGB8 of the 16 palette colours: the encoder's 8 x 2 RGBA plane of ansi_palette's chexels
     bool rgb_palette_ready = false;
@@ -1045,6 +1062,7 @@ int check_in_flight(ycge_ctx *c);                                               
 int check_post_frame(ycge_ctx *c);                                                       // ycge_frame.cpp: ... and a presenter's frame with the post stage
 int render_frame_in_flight(ycge_ctx *c, FrameOutputs *out);                              // ycge_frame.cpp: ycge_render_frame_async(_sdr)
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
+int check_quadrant_call(ycge_ctx *c, const char *fn, int32_t min_contrast);              // ycge_chexel.cpp: what every quadrant call refuses - an odd super_sample, min_contrast outside 0..255
 int ensure_tables(ycge_ctx *c, ChexelState &X);                                           // ycge_chexel.cpp: LinearToSrgb8's thresholds on the device, once
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_pairs);   // ycge_ansi.cpp: out.ansi's stream kernels behind the encode, and the length's copy
 // ycge_video.cpp: Video mode.  The refusals of a source frame; upload + k_video_blit on `stream` for a geometry (*d_sdr: its SDR array);

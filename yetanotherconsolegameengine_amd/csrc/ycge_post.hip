@@ -1112,6 +1112,31 @@ __global__ __launch_bounds__(256) void k_tonemap_downsample(const float *__restr
     o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = b.x; o[4] = b.y; o[5] = b.z;
 }
 
+// The quadrant-glyph presenters' sub-cell colours (no counterpart in the reference; the contract: include/ycge.h at
+// ycge_render_frame_quadrants).  Even ss only: a chexel's four quadrants {TL, TR, BL, BR}, each the box average of ss / 2 columns by ss
+// rows of the same buffer - the left / right half of the chexel's columns, its top / bottom half-cell's rows - summed rows outer, columns
+// inner from 0 as above, times 1 / (ss / 2 * ss), then the same map_pixel.  One lane a quadrant: lane i owns quadrant i & 3 of chexel
+// i >> 2, so a wavefront's stores are one run of 12 floats a chexel.
+__global__ __launch_bounds__(256) void k_tonemap_quadrants(const float *__restrict__ hdr, int hiW, int fbW, int fbH, int ss, float gamma,
+                                                           float saturation, float vibrance, const ToneState *__restrict__ state,
+                                                           float *__restrict__ out /* fbW*fbH*12 */)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)fbW * fbH * 4) return;
+    const int k = (int)(i & 3);
+    const size_t cell = i >> 2;
+    const int cx = (int)(cell % (size_t)fbW), cy = (int)(cell / (size_t)fbW);
+    const int half = ss / 2;
+    const int y0 = (cy * 2 + (k >> 1)) * ss, x0 = cx * ss + (k & 1) * half;
+    F3 sum = f3(0, 0, 0);
+    for (int sy = 0; sy < ss; sy++)
+        for (int sx = 0; sx < half; sx++) sum = sum + ld3(hdr, (size_t)(x0 + sx) + (size_t)(y0 + sy) * hiW);
+    const float inv = 1.0f / (float)(half * ss);
+    const F3 q = map_pixel(f3(sum.x * inv, sum.y * inv, sum.z * inv), state->effective, gamma, saturation, vibrance);
+    float *o = out + i * 3;
+    o[0] = q.x; o[1] = q.y; o[2] = q.z;
+}
+
 } // namespace ycge
 
 template <int G>
@@ -1255,6 +1280,18 @@ int ycge_launch_tonemap(const float *hdr, int hiW, int fbW, int fbH, int ss, flo
     const int n = fbW * fbH;
     hipLaunchKernelGGL(ycge::k_tonemap_downsample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hdr, hiW, fbW, fbH, ss, gamma,
                        saturation, vibrance, (const ycge::ToneState *)state, out);
+    return (int)hipGetLastError();
+}
+
+// k_tonemap_quadrants over the same buffer and state: out is fbW*fbH*12 floats.  ss must be even and positive (the host's refusal; checked again)
+int ycge_launch_tonemap_quadrants(const float *hdr, int hiW, int fbW, int fbH, int ss, float gamma, float saturation, float vibrance, const void *state,
+                                  float *out, hipStream_t stream)
+{
+    if (!hdr || !state || !out || fbW <= 0 || fbH <= 0 || ss < 2 || (ss & 1) || hiW < fbW * ss || (int64_t)fbW * fbH > (int64_t)INT32_MAX / 8)
+        return (int)hipErrorInvalidValue;
+    const size_t n = (size_t)fbW * fbH * 4;
+    hipLaunchKernelGGL(ycge::k_tonemap_quadrants, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hdr, hiW, fbW, fbH, ss, gamma, saturation,
+                       vibrance, (const ycge::ToneState *)state, out);
     return (int)hipGetLastError();
 }
 

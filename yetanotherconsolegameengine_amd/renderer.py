@@ -948,10 +948,11 @@ class RaytraceRenderer:
             buf = self.__dict__["_ansi_buf"] = self._page_locked_zeros((bound,), np.uint8)
         return buf[0]
 
-    def _ansi_call(self, export, head, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr, rgb=False, delta=None, stats=True):
+    def _ansi_call(self, export, head, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr, rgb=False, delta=None, stats=True, extra=()):
         """One stream call on this context: export(ctx, *head, the console, viewport, defaults and clear_screen, *delta, the stream buffer,
         its capacity and length[, info], the SDR array or NULL[, the frame statistics]).  head: a video call's frame arguments; delta: a
-        _delta call's (merge_gap[, tolerance], keyframe), or None.  A plain call returns bytes or (bytes, SDR array), a _delta call
+        _delta call's (merge_gap[, tolerance], keyframe[, min_contrast]), or None; extra: what a plain call takes behind clear_screen (the
+        quadrant stream's min_contrast).  A plain call returns bytes or (bytes, SDR array), a _delta call
         (bytes, info) or (bytes, info, SDR array)."""
         out = self._ansi_out(console_width, console_height, rgb)
         n = C.c_size_t(0)
@@ -960,7 +961,7 @@ class RaytraceRenderer:
         buf = (out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, C.byref(n))
         tail = (s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None,) + ((C.byref(self.stats),) if stats else ())
         if delta is None:
-            self._check(export(self.ctx, *head, *console, *buf, *tail))
+            self._check(export(self.ctx, *head, *console, *(int(v) for v in extra), *buf, *tail))
             stream = out[:n.value].tobytes()
             return (stream, s) if sdr else stream
         info = (C.c_uint32 * 4)()
@@ -1006,6 +1007,41 @@ class RaytraceRenderer:
         form makes the next call a keyframe.  Returns (bytes, info) or (bytes, info, SDR array) with sdr=True."""
         return self._ansi_call(self.L.ycge_render_frame_ansi_rgb_delta, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
                                rgb=True, delta=(merge_gap, tolerance, bool(keyframe)))
+
+    # ---------------------------------------------------------------- quadrant-glyph frames (ycge_render_frame_quadrants / _ansi_quad / _ansi_quad_delta)
+    QUADRANT_GLYPHS = (0x2580, 0x2598, 0x259D, 0x2580, 0x2596, 0x258C, 0x259E, 0x259B)      # by mask: bit 0 = TL, bit 1 = TR, bit 2 = BL in the foreground
+
+    def TryFlipAndBlitQuadrants(self, quad_sdr: bool = False, glyphs: bool = True, rgba: bool = True, sdr: bool = False, min_contrast: int = 0) -> dict:
+        """One frame (ycge_render_frame_quadrants; super_sample must be even): each chexel's 2 x 2 sub-cell colours and the quadrant block
+        glyph and two colours fitted to them on the device - {name: array} for each output asked: "quad_sdr" (fbH, fbW, 4, 3) f32 {TL, TR,
+        BL, BR}; "glyphs" (fbH, fbW) uint16 code units; "rgba" (2 fbH, fbW, 4) uint8, row 2 cy the foreground and row 2 cy + 1 the
+        background; "sdr" as TryFlipAndBlitChexels.  min_contrast (0..255): a chexel whose sub-cell bytes all lie within it of their mean
+        stays one colour.  The SDR and the frame state are those of TryFlipAndBlit(want_sdr=True); the statistics go to self.stats."""
+        shapes = {"sdr": ((self.fbH, self.fbW, 2, 3), np.float32), "quad_sdr": ((self.fbH, self.fbW, 4, 3), np.float32),
+                  "glyphs": ((self.fbH, self.fbW), np.uint16), "rgba": ((2 * self.fbH, self.fbW, 4), np.uint8)}
+        want = {"sdr": sdr, "quad_sdr": quad_sdr, "glyphs": glyphs, "rgba": rgba}
+        arrays = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items() if want[k]}
+        ptr = lambda k, t: arrays[k].ctypes.data_as(C.POINTER(t)) if k in arrays else None
+        self._check(self.L.ycge_render_frame_quadrants(self.ctx, ptr("sdr", C.c_float), ptr("quad_sdr", C.c_float), ptr("glyphs", C.c_uint16), ptr("rgba", C.c_uint8),
+                                                       int(min_contrast), C.byref(self.stats)))
+        return arrays
+
+    def TryFlipAndBlitAnsiQuad(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                               clear_screen: bool = False, min_contrast: int = 0, sdr: bool = False):
+        """TryFlipAndBlitAnsiRgb with quadrant block glyphs (ycge_render_frame_ansi_quad): a covered cell's character and triples are the
+        glyph, foreground and background TryFlipAndBlitQuadrants gives - `bytes`, or (bytes, SDR array) with sdr=True.  The bound is
+        ansi_rgb_stream_bound; super_sample must be even."""
+        return self._ansi_call(self.L.ycge_render_frame_ansi_quad, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr, rgb=True,
+                               extra=(min_contrast,))
+
+    def TryFlipAndBlitAnsiQuadDelta(self, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                                    clear_screen: bool = False, merge_gap: int = 3, tolerance: int = 0, keyframe: bool = False, min_contrast: int = 0,
+                                    sdr: bool = False):
+        """TryFlipAndBlitAnsiRgbDelta with quadrant block glyphs (ycge_render_frame_ansi_quad_delta): a cell is rewritten when its glyph
+        differs from what the terminal shows or a channel is more than `tolerance` away.  A third family beside the 256-colour and 24-bit
+        streams: a stream of another family makes the next call a keyframe.  Returns (bytes, info) or (bytes, info, SDR array)."""
+        return self._ansi_call(self.L.ycge_render_frame_ansi_quad_delta, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
+                               rgb=True, delta=(merge_gap, tolerance, bool(keyframe), min_contrast))
 
     # ---------------------------------------------------------------- ANSI streams with frames in flight (ycge_render_frame_async_ansi)
     def RenderAsyncAnsi(self, slot: int, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
