@@ -166,7 +166,7 @@ def test_the_kernels_live_in_their_own_unit_with_the_bound_proved():
     for k in ("void k_delta_count(", "void k_scan(", "void k_delta_write("):
         assert k in src
     unit = (csrc / "ycge_ansi.hip").read_text()
-    assert '#include "ycge_ansi_cells.hip.h"' in unit and "launch_delta<" in unit
+    assert '#include "ycge_ansi_cells.hip.h"' in unit and "launch<Indexed>(" in unit
 
 
 def test_the_default_merge_gap_is_the_measured_one():

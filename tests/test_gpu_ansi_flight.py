@@ -289,6 +289,38 @@ def test_delta_state_rules_hold_for_queued_calls(product_lib):
         a.close(); b.close()
 
 
+def test_buffers_grow_under_queued_frames(product_lib):
+    """queued calls whose buffers must grow while frames are in flight - each in a slot of its own, no Wait between them: every frame equals
+    the synchronous twin's, whichever buffer its call had to make"""
+    a, b, pose = S.twins(1, 80, 45, 1)
+    try:
+        steps = [(False, False, 41, 23),          # a 256-colour full stream
+                 (False, True, 41, 23),           # its delta form: a keyframe, the held pairs
+                 (False, True, 81, 45),           # the stream and the tiles grow; another geometry: a keyframe
+                 (True, True, 81, 45),            # 24-bit: the triples' palette, a held plane of 8 bytes a cell
+                 (True, True, 81, 45),            # a real delta
+                 (True, True, 81, 45),            # (layers set in front) the composite's planes and the third colour plane
+                 (False, True, 161, 46)]          # a console larger than the framebuffer: the composite grows
+        want = []
+        for k, (rgb, delta, cw, ch) in enumerate(steps):
+            S.move((a, b), pose, k // 2)
+            if k == 5:
+                for g in (a, b):
+                    g.SetConsoleLayers(console_layers(0), 1)
+            kw = dict(merge_gap=3, tolerance=0) if delta else {}
+            want.append(sync_frame(a, rgb, delta, cw, ch, **kw))
+            queue_frame(b, k, rgb, delta, cw, ch, **kw)
+        b.Wait()
+        got = [result(b, k) for k in range(len(steps))]
+        for k in range(len(steps)):
+            assert_frame(got[k], want[k], f"growing buffers, frame {k}")
+        assert [g[1]["keyframe"] for g in got] == [1, 1, 1, 1, 0, 1, 1]
+        assert b"menu__0" in want[5][0] and b"menu__0" in want[6][0]
+        assert pu.bits_equal(a.read(abi.BUF_TAA_HISTORY), b.read(abi.BUF_TAA_HISTORY))
+    finally:
+        a.close(); b.close()
+
+
 def test_interleaved_with_the_other_frames_in_flight(product_lib):
     """RenderAsync(sdr_slot) and RenderAsyncChexels frames between RenderAsyncAnsi frames on one context: every output equals the twin's"""
     a, b, pose = S.twins(2, 160, 45, 1)

@@ -17,6 +17,15 @@
 // against what the terminal shows under a tolerance.  One request, one launch, one delta transaction (DeltaCall) and one delivery serve
 // every form; the delta state belongs to the one terminal, so a stream of either family invalidates it for both.
 //
+// A call is decided in three values.  Its DeltaCall compares ONE key - colour form, family, layers set or not, console, viewport, default
+// colours, framebuffer - with the held one (ChexelState::delta_key) and so decides keyframe or delta.  Its AnsiPlan (plan_of) follows from
+// the request and that decision: every buffer the call reads or writes with the size it must have, and where the frame's colour plane
+// lies.  ensure_frame_buffers grows the buffers to the plan before anything is queued - the held plane a _delta call's encode writes
+// included - and a frame in flight is queued without a join only when frame_buffers_ready finds the same plan met; chexel_encode and
+// chexel_read_back take the plane's place from it (ycge_chexel.cpp, ansi_frame_plane).  launch() then fills one ycge_ansi::StreamJob
+// (ycge_ansi_layers.h) - planes, geometry, defaults, full or delta, the layers and the composite's planes - and hands it to the colour
+// form's one entry point, ycge_launch_ansi_indexed or ycge_launch_ansi_rgb; frames, video and the test hooks all come through it.
+//
 // Layers (ycge_console_set_layers): the console's other framebuffers, kept in ChexelState::layers with their colours encoded once by
 // k_encode_chexels.  While any are set, launch() runs the compose pass in front of the stream kernels, which then walk the console-wide
 // composite; the delta forms keep the last composite's colour and glyph planes in comp_held / glyph_held, flipped with delta_held.
@@ -81,55 +90,84 @@ static int ensure_rgb_palette(ycge_ctx *c, ChexelState &X, hipStream_t stream)
     return YCGE_OK;
 }
 
-// the buffers of r's stream, whose bound is `bound` (kept while large enough), and the default colours (rgb: their triples too)
-static int ensure_ansi(ycge_ctx *c, ChexelState &X, const AnsiRequest &r, unsigned long long bound, hipStream_t stream)
+// The plan of r's call (AnsiPlan, ycge_ctx.h), the one place where its buffers' sizes and its frame plane's place are decided.  bound: its
+// stream's; keyframe: what its DeltaCall decided; fbW x fbH: the framebuffer; layered: layers are set.  A _delta call outside the quadrant
+// family holds the frame's plane for the next call; every layered or quadrant stream composes into the held pairs of console-wide planes
+static AnsiPlan plan_of(const AnsiRequest &r, bool keyframe, unsigned long long bound, int fbW, int fbH, bool layered)
 {
-    if (X.ansi_stream.cap < bound) HIP_TRY(c, X.ansi_stream.alloc(bound));
-    const uint32_t tiles = ycge_launch_ansi_tiles((uint32_t)r.cw * (uint32_t)r.ch);
-    if (X.ansi_tiles.cap < 4 * (size_t)tiles) HIP_TRY(c, X.ansi_tiles.alloc(4 * (size_t)tiles));          // (the delta kernels keep four words a tile)
-    if (!X.ansi_res.p) HIP_TRY(c, X.ansi_res.alloc(4));
-    HIP_TRY(c, X.ansi_res_host.reserve(4 * sizeof(unsigned long long)));
-    return r.rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream);
+    const size_t cells = (size_t)r.cw * (size_t)r.ch, px = r.rgb ? 8 : 2;
+    AnsiPlan p;
+    p.rgb_palette = r.rgb;
+    p.stream = bound;
+    p.tile_words = 4 * (size_t)ycge_launch_ansi_tiles((uint32_t)r.cw * (uint32_t)r.ch);          // (the delta kernels keep four words a tile)
+    if (r.delta && !r.quad) {
+        p.held = px * (size_t)fbW * fbH;
+        p.frame_in_held = keyframe || !r.rgb;          // (a 24-bit delta's write kernel fills the held plane instead)
+    }
+    if (layered || r.quad) {
+        p.comp = px * cells; p.comp_cells = cells;
+        if (r.rgb && r.delta) p.comp_cur = p.comp;
+    }
+    return p;
 }
 
-// r's stream of the fbW x fbH plane d_plane (the pairs; rgb: the RGBA plane), and the copy of what the scan reports.  delta: against d_prev
-// - rgb: what the terminal displays, d_next the plane that receives the next such - with the copy of {length, changed, emitted, run starts};
-// otherwise the full stream and its length alone
-// L (or NULL: no layers): the console's other framebuffers and the composite's planes, the compose pass in front; d_prev and d_next are then L's
-// flight (or NULL): the frame in flight whose stream buffer and record k_ansi_deliver fills instead of that copy
-// d_glyph (r.quad alone): the fitted code units beside d_plane; L is then never NULL
-static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiRequest &r, bool delta, const uint8_t *d_plane, const uint8_t *d_prev, uint8_t *d_next,
-                  int fbW, int fbH, const ycge_ansi::LayersRun *L, const FrameOutputs *flight = nullptr, const uint16_t *d_glyph = nullptr)
+// every buffer of plan p and the elements it must have, handed to `each` until one answers other than YCGE_OK
+template <class F>
+static int each_buffer(ChexelState &X, const AnsiPlan &p, F each)
 {
-    const uint8_t *palette = r.rgb ? X.rgb_palette.p : reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48);
-    uint8_t *out = X.ansi_stream.p;
-    const size_t cap = X.ansi_stream.cap;
-    int e;
-    if (r.quad && !delta)
-        e = ycge_launch_ansi_quad_stream(L, d_plane, d_glyph, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.clear, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
-    else if (r.quad)
-        e = ycge_launch_ansi_quad_delta(L, d_plane, d_glyph, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, r.tolerance, X.ansi_tiles.p, out, cap, X.ansi_res.p,
-                                        stream);
-    else if (L && !delta)
-        e = (r.rgb ? ycge_launch_ansi_rgb_layers_stream : ycge_launch_ansi_layers_stream)(L, d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.clear,
-                                                                                        X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
-    else if (L && r.rgb)
-        e = ycge_launch_ansi_rgb_layers_delta(L, d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, r.tolerance, X.ansi_tiles.p, out, cap, X.ansi_res.p,
-                                              stream);
-    else if (L)
-        e = ycge_launch_ansi_layers_delta(L, d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
-    else if (!delta)
-        e = (r.rgb ? ycge_launch_ansi_rgb_stream : ycge_launch_ansi_stream)(d_plane, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.clear, X.ansi_tiles.p, out,
-                                                                          cap, X.ansi_res.p, stream);
-    else if (r.rgb)
-        e = ycge_launch_ansi_rgb_delta(d_plane, d_prev, d_next, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, r.tolerance, X.ansi_tiles.p, out, cap,
-                                       X.ansi_res.p, stream);
-    else
-        e = ycge_launch_ansi_delta(d_plane, d_prev, fbW, fbH, r.cw, r.ch, r.vx, r.vy, palette, r.fg, r.bg, r.gap, X.ansi_tiles.p, out, cap, X.ansi_res.p, stream);
+    int rc = each(X.ansi_stream, p.stream);
+    if (rc == YCGE_OK) rc = each(X.ansi_tiles, p.tile_words);
+    if (rc == YCGE_OK) rc = each(X.ansi_res, (size_t)4);
+    if (rc == YCGE_OK) rc = each(X.delta_held[1 - X.delta_prev], p.held);
+    for (int k = 0; k < 2 && rc == YCGE_OK; k++) {
+        rc = each(X.comp_held[k], p.comp);
+        if (rc == YCGE_OK) rc = each(X.glyph_held[k], p.comp_cells);
+    }
+    return rc == YCGE_OK ? each(X.comp_cur, p.comp_cur) : rc;
+}
+
+// whether a call of plan p finds every buffer it names as it is: one that has to grow is freed under the frames in flight that read it
+static bool frame_buffers_ready(ChexelState &X, const AnsiPlan &p)
+{
+    if (p.rgb_palette ? !X.rgb_palette_ready : !X.ansi_palette_ready) return false;
+    return each_buffer(X, p, [](auto &b, size_t n) { return b.cap < n ? YCGE_ERR_INTERNAL : YCGE_OK; }) == YCGE_OK;
+}
+
+// what a stream call makes before it queues anything: the buffers of its plan (kept while large enough), the page-locked words of what
+// the scan reports, and the default colours
+static int ensure_frame_buffers(ycge_ctx *c, ChexelState &X, const AnsiPlan &p, hipStream_t stream)
+{
+    const int rc = each_buffer(X, p, [c](auto &b, size_t n) { if (b.cap < n) HIP_TRY(c, b.alloc(n)); return (int)YCGE_OK; });
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, X.ansi_res_host.reserve(4 * sizeof(unsigned long long)));
+    return p.rgb_palette ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream);
+}
+
+// S's layers in the colour form rgb, composed into comp / comp_glyph
+static ycge_ansi::LayersRun layers_run(const LayerStore &S, bool rgb, uint8_t *comp, uint16_t *comp_glyph)
+{
+    ycge_ansi::LayersRun L{};
+    L.n = S.n; L.raytrace_at = S.raytrace_at; L.cells = S.cells;
+    L.colours = rgb ? S.rgba.p : S.pairs.p; L.glyphs = S.glyphs.p;
+    for (int k = 0; k < S.n; k++) L.rect[k] = S.rect[k];
+    L.comp = comp; L.comp_glyph = comp_glyph;
+    return L;
+}
+
+// r's stream as the job j describes it, and the copy of what the scan reports: a delta's {length, changed, emitted, run starts}, otherwise
+// the full stream's length alone.  The caller's part of j: the planes - the framebuffer's with its size, the previous and next ones, the
+// layers and the composite's - and full or delta; the rest is r's and the context's stream buffers
+// flight (or NULL): the frame in flight whose stream buffer and record k_ansi_deliver fills instead of that copy
+static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiRequest &r, ycge_ansi::StreamJob &j, const FrameOutputs *flight = nullptr)
+{
+    j.cw = r.cw; j.ch = r.ch; j.vx = r.vx; j.vy = r.vy; j.dfg = r.fg; j.dbg = r.bg; j.clear = r.clear; j.gap = r.gap; j.tol = r.tolerance;
+    j.palette = r.rgb ? X.rgb_palette.p : reinterpret_cast<const uint8_t *>(X.ansi_palette.p + 48);
+    j.tiles = X.ansi_tiles.p; j.out = X.ansi_stream.p; j.cap = X.ansi_stream.cap; j.res = X.ansi_res.p;
+    int e = (r.rgb ? ycge_launch_ansi_rgb : ycge_launch_ansi_indexed)(&j, stream);
     if (e != 0)
-        return c->fail(YCGE_ERR_DEVICE, "%sANSI %sstream launch failed: %s", r.quad ? "quadrant " : r.rgb ? "24-bit " : "", delta ? "delta " : "", hipGetErrorString((hipError_t)e));
+        return c->fail(YCGE_ERR_DEVICE, "%sANSI %sstream launch failed: %s", r.quad ? "quadrant " : r.rgb ? "24-bit " : "", j.delta ? "delta " : "", hipGetErrorString((hipError_t)e));
     if (!flight) {
-        HIP_TRY(c, hipMemcpyAsync(X.ansi_res_host.p, X.ansi_res.p, (delta ? 4 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(c, hipMemcpyAsync(X.ansi_res_host.p, X.ansi_res.p, (j.delta ? 4 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
         return YCGE_OK;
     }
     // a frame in flight (ycge_render_frame_async_ansi): the exact-length copy and the caller's record by k_ansi_deliver, one workgroup a CU,
@@ -137,7 +175,7 @@ static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiReq
     void *d_sticky = nullptr;
     HIP_TRY(c, hipHostGetDevicePointer(&d_sticky, X.flight_sticky.p, 0));
     // (a length above the device stream's own size is refused as one above the caller's capacity is: no load passes the allocation)
-    e = ycge_launch_ansi_deliver(out, X.ansi_res.p, flight->dev_capacity < cap ? flight->dev_capacity : cap, delta ? 0 : 1, flight->dev_stream, flight->dev_record, static_cast<uint32_t *>(d_sticky), c->compute_units, stream);
+    e = ycge_launch_ansi_deliver(j.out, j.res, flight->dev_capacity < j.cap ? flight->dev_capacity : j.cap, j.delta ? 0 : 1, flight->dev_stream, flight->dev_record, static_cast<uint32_t *>(d_sticky), c->compute_units, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_ansi_deliver launch failed: %s", hipGetErrorString((hipError_t)e));
     HIP_TRY(c, X.flight_ev.ensure());
     HIP_TRY(c, hipEventRecord(X.flight_ev, stream));
@@ -145,52 +183,25 @@ static int launch(ycge_ctx *c, ChexelState &X, hipStream_t stream, const AnsiReq
     return YCGE_OK;
 }
 
-// S's layers in the colour form rgb; the composite's planes are the caller's to set
-static ycge_ansi::LayersRun layers_run(const LayerStore &S, bool rgb)
-{
-    ycge_ansi::LayersRun L{};
-    L.n = S.n; L.raytrace_at = S.raytrace_at; L.cells = S.cells;
-    L.colours = rgb ? S.rgba.p : S.pairs.p; L.glyphs = S.glyphs.p;
-    for (int k = 0; k < S.n; k++) L.rect[k] = S.rect[k];
-    return L;
-}
-
-// the composite's planes of r's console (kept while large enough): both held pairs, and for a 24-bit delta the third colour plane
-static int ensure_composite(ycge_ctx *c, ChexelState &X, const AnsiRequest &r)
-{
-    const size_t cells = (size_t)r.cw * (size_t)r.ch, bytes = (r.rgb ? 8 : 2) * cells;
-    for (int k = 0; k < 2; k++) {
-        if (X.comp_held[k].cap < bytes) HIP_TRY(c, X.comp_held[k].alloc(bytes));
-        if (X.glyph_held[k].cap < cells) HIP_TRY(c, X.glyph_held[k].alloc(cells));
-    }
-    if (r.rgb && r.delta && X.comp_cur.cap < bytes) HIP_TRY(c, X.comp_cur.alloc(bytes));
-    return YCGE_OK;
-}
-
-// what a frame's stream call makes before it queues anything: r's buffers and, while layers are set, the composite's planes
-static int ensure_frame_buffers(ycge_ctx *c, ChexelState &X, const AnsiRequest &r, unsigned long long bound, hipStream_t stream)
-{
-    const int rc = ensure_ansi(c, X, r, bound, stream);
-    return rc == YCGE_OK && (X.layers.n > 0 || r.quad) ? ensure_composite(c, X, r) : rc;
-}
-
-int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_pairs)
+int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_plane)
 {
     ChexelState &X = c->chexels;
     const AnsiRequest &r = *out.ansi;
     { const int rc = r.rgb ? ensure_rgb_palette(c, X, stream) : ensure_palette(c, X, stream); if (rc != YCGE_OK) return rc; }
-    const bool delta = !out.keyframe;
-    const FrameOutputs *flight = out.dev_stream ? &out : nullptr;
-    if (X.layers.n == 0 && !r.quad)
-        return launch(c, X, stream, r, delta, d_pairs, X.delta_held[X.delta_prev].p, X.delta_held[1 - X.delta_prev].p, c->fbW, c->fbH, nullptr, flight);
-    // (layers: this call's composite goes where the next _delta call finds it; a 24-bit delta's write kernel fills that plane instead)
-    ycge_ansi::LayersRun L = layers_run(X.layers, r.rgb);
     const int held = X.delta_prev, next = 1 - X.delta_prev;
-    L.comp = delta && r.rgb ? X.comp_cur.p : X.comp_held[next].p;
-    L.comp_glyph = X.glyph_held[next].p;
-    L.prev = X.comp_held[held].p; L.prev_glyph = X.glyph_held[held].p;
-    L.next = X.comp_held[next].p;
-    return launch(c, X, stream, r, delta, d_pairs, nullptr, nullptr, c->fbW, c->fbH, &L, flight, r.quad ? X.quad_glyphs.p : nullptr);
+    ycge_ansi::StreamJob j{};
+    j.plane = d_plane; j.fbW = c->fbW; j.fbH = c->fbH;
+    j.delta = !out.keyframe;
+    j.compose = X.layers.n > 0 || r.quad;
+    if (!j.compose) {
+        j.prev = X.delta_held[held].p; j.next = X.delta_held[next].p;
+    } else {
+        // (this call's composite goes where the next _delta call finds it; a 24-bit delta's write kernel fills that plane instead)
+        j.frame_glyph = r.quad ? X.quad_glyphs.p : nullptr;
+        j.layers = layers_run(X.layers, r.rgb, j.delta && r.rgb ? X.comp_cur.p : X.comp_held[next].p, X.glyph_held[next].p);
+        j.prev = X.comp_held[held].p; j.prev_glyph = X.glyph_held[held].p; j.next = X.comp_held[next].p;
+    }
+    return launch(c, X, stream, r, j, out.dev_stream ? &out : nullptr);
 }
 
 } // namespace ycge_host
@@ -202,31 +213,35 @@ namespace {
 struct DeltaCall {
     ChexelState &X;
     const AnsiRequest &r;
-    int32_t key[8];
+    const bool layered;
+    const ChexelState::DeltaKey key;
     bool keyframe = true, done = false;
-    DeltaCall(ycge_ctx *c, const AnsiRequest &r_) : X(c->chexels), r(r_), key{r_.cw, r_.ch, r_.vx, r_.vy, r_.fg, r_.bg, c->fbW, c->fbH}
+    AnsiPlan plan;
+    // bound: the stream's (check_stream_args)
+    DeltaCall(ycge_ctx *c, const AnsiRequest &r_, unsigned long long bound)
+        : X(c->chexels), r(r_), layered(X.layers.n > 0), key{{r_.rgb, r_.quad, layered, r_.cw, r_.ch, r_.vx, r_.vy, r_.fg, r_.bg, c->fbW, c->fbH}}
     {
+        const int held = X.delta_prev;
         if (r.delta)
-            keyframe = !X.delta_valid || X.delta_rgb != r.rgb || X.delta_quad != r.quad || (!r.quad && !X.delta_held[X.delta_prev].p) ||
-                       std::memcmp(key, X.delta_key, sizeof key) != 0 || r.clear || r.keyframe || X.delta_layered != (X.layers.n > 0) ||
-                       ((X.layers.n > 0 || r.quad) && (!X.comp_held[X.delta_prev].p || !X.glyph_held[X.delta_prev].p));
+            keyframe = !X.delta_valid || key != X.delta_key || r.clear || r.keyframe || (!r.quad && !X.delta_held[held].p) ||
+                       ((layered || r.quad) && (!X.comp_held[held].p || !X.glyph_held[held].p));
         else
             X.delta_valid = false;
+        plan = plan_of(r, keyframe, bound, c->fbW, c->fbH, layered);
     }
     ~DeltaCall() { if (!done) X.delta_valid = false; }
-    // what the call's frame hands out: r's stream, a keyframe or not as decided here, and the SDR array
+    // what the call's frame hands out: r's stream, a keyframe or not as decided here with the plan that follows from it, and the SDR array
     FrameOutputs outputs(float *sdr) const
     {
         FrameOutputs out(sdr);
-        out.ansi = &r; out.keyframe = keyframe;
+        out.ansi = &r; out.keyframe = keyframe; out.plan = plan;
         return out;
     }
     // a _delta call's stream is with the caller: this frame's pairs are `prev` from now on
     void commit()
     {
         if (!r.delta) return;
-        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_rgb = r.rgb; X.delta_quad = r.quad; X.delta_layered = X.layers.n > 0;
-        std::memcpy(X.delta_key, key, sizeof key);
+        X.delta_prev = 1 - X.delta_prev; X.delta_valid = true; X.delta_key = key;
         done = true;
     }
 };
@@ -284,10 +299,10 @@ int frame(ycge_ctx *c, const char *fn, const AnsiRequest &r, uint8_t *out_stream
     if (rc == YCGE_OK) rc = check_post_frame(c);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    DeltaCall call(c, r);
+    DeltaCall call(c, r, bound);
     FrameOutputs out = call.outputs(out_top_bottom_sdr);
     ChexelState &X = c->chexels;
-    rc = ensure_frame_buffers(c, X, r, bound, c->stream);
+    rc = ensure_frame_buffers(c, X, call.plan, c->stream);
     if (rc != YCGE_OK) return rc;
     rc = render_frame_sync(c, &out, st);          // (its stream synchronisation: the length and the counters have arrived)
     if (rc != YCGE_OK) return rc;
@@ -323,19 +338,6 @@ int ensure_flight(ycge_ctx *c, ChexelState &X)
     return YCGE_OK;
 }
 
-// whether r's queued frame finds every buffer it names as it is: one that has to grow is freed under the frames in flight that read it
-bool flight_buffers_ready(const ycge_ctx *c, const ChexelState &X, const AnsiRequest &r, unsigned long long bound)
-{
-    const size_t tiles = ycge_launch_ansi_tiles((uint32_t)r.cw * (uint32_t)r.ch), cells = (size_t)r.cw * (size_t)r.ch, px = r.rgb ? 8 : 2;
-    if (X.ansi_stream.cap < bound || X.ansi_tiles.cap < 4 * tiles || !X.ansi_res.p || !X.flight_sticky.p) return false;
-    if (r.rgb ? !X.rgb_palette_ready : !X.ansi_palette_ready) return false;
-    if (r.delta && X.delta_held[1 - X.delta_prev].cap < px * (size_t)c->fbW * c->fbH) return false;
-    if (X.layers.n == 0) return true;
-    for (int k = 0; k < 2; k++)
-        if (X.comp_held[k].cap < px * cells || X.glyph_held[k].cap < cells) return false;
-    return !(r.rgb && r.delta && X.comp_cur.cap < px * cells);
-}
-
 AnsiRequest request(bool rgb, int32_t cw, int32_t ch, int32_t vx, int32_t vy, int32_t fg, int32_t bg, int32_t clear);
 AnsiRequest with_delta(AnsiRequest r, int32_t merge_gap, int32_t tolerance, int32_t keyframe);
 
@@ -362,13 +364,13 @@ int frame_async(ycge_ctx *c, const ycge_ansi_async *q, uint8_t *out_stream, size
     if (rc != YCGE_OK) return rc;
     if (!c->taa_stream) return c->fail(YCGE_ERR_INVALID_ARG, "no second stream: frames in flight need a single-device context");
     HIP_TRY(c, hipSetDevice(c->device));
-    DeltaCall call(c, r);
+    DeltaCall call(c, r, bound);
     FrameOutputs out = call.outputs(out_top_bottom_sdr);
     ChexelState &X = c->chexels;
-    if (!flight_buffers_ready(c, X, r, bound)) {
+    if (!frame_buffers_ready(X, call.plan) || !X.flight_sticky.p) {
         // (the first call of a form or a size: the frames in flight are joined, and what the buffers' makers queued on c->stream is waited for)
         rc = join_async(c);
-        if (rc == YCGE_OK) rc = ensure_frame_buffers(c, X, r, bound, c->stream);
+        if (rc == YCGE_OK) rc = ensure_frame_buffers(c, X, call.plan, c->stream);
         if (rc == YCGE_OK) rc = ensure_flight(c, X);
         if (rc != YCGE_OK) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -430,10 +432,10 @@ int video(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t *fram
     rc = join_async(c);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    DeltaCall call(c, r);
+    DeltaCall call(c, r, bound);
     FrameOutputs out = call.outputs(out_top_bottom_sdr);
     ChexelState &X = c->chexels;
-    rc = ensure_frame_buffers(c, X, r, bound, c->stream);
+    rc = ensure_frame_buffers(c, X, call.plan, c->stream);
     const float *d_sdr = nullptr;
     if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
     if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, out, d_sdr, false);
@@ -446,6 +448,32 @@ int video(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t *fram
     out.finish();
     call.commit();
     return YCGE_OK;
+}
+
+// a hook's own device copy of n host elements
+template <class T>
+int upload(ycge_ctx *c, DevBuf<T> &b, const T *src, size_t n)
+{
+    HIP_TRY(c, b.alloc(n));
+    HIP_TRY(c, hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return YCGE_OK;
+}
+
+// what every hook makes first: the context's buffers by the plan of r's full unlayered stream - every plane is the hook's own
+int hook_begin(ycge_ctx *c, AnsiRequest r, unsigned long long bound)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    r.delta = r.quad = false;
+    return ensure_frame_buffers(c, c->chexels, plan_of(r, true, bound, 0, 0, false), c->stream);
+}
+
+// a hook's job: launched, waited for, delivered
+int hook_run(ycge_ctx *c, const char *fn, const AnsiRequest &r, ycge_ansi::StreamJob &j, unsigned long long bound, uint8_t *out_stream, size_t *out_len, uint32_t *out_info)
+{
+    const int rc = launch(c, c->chexels, c->stream, r, j);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return deliver(c, c->chexels, fn, !j.delta, bound, out_stream, out_len, out_info);
 }
 
 // The four test hooks: r's stream kernels alone on caller-given planes of the fbW x fbH framebuffer (`what` names cur in the refusal), with
@@ -461,28 +489,21 @@ int test_stream(ycge_ctx *c, const char *fn, const char *what, const AnsiRequest
         return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad framebuffer (%s %p, %d x %d)", fn, what, (const void *)cur, fbW, fbH);
     unsigned long long bound = 0;
     int rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
-    if (rc != YCGE_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ChexelState &X = c->chexels;
-    rc = ensure_ansi(c, X, r, bound, c->stream);
+    if (rc == YCGE_OK) rc = hook_begin(c, r, bound);
     if (rc != YCGE_OK) return rc;
     const bool full = !r.delta || !prev || r.clear;
     const size_t bytes = (r.rgb ? 8 : 2) * (size_t)fbW * fbH;
     DevBuf<uint8_t> in, held, next;
-    HIP_TRY(c, in.alloc(bytes));
-    HIP_TRY(c, hipMemcpy(in.p, cur, bytes, hipMemcpyHostToDevice));
-    if (!full) {
-        HIP_TRY(c, held.alloc(bytes));
-        HIP_TRY(c, hipMemcpy(held.p, prev, bytes, hipMemcpyHostToDevice));
-    }
+    rc = upload(c, in, cur, bytes);
+    if (rc == YCGE_OK && !full) rc = upload(c, held, prev, bytes);
+    if (rc != YCGE_OK) return rc;
     if (!full && r.rgb) {
         HIP_TRY(c, next.alloc(bytes));
         HIP_TRY(c, hipMemcpy(next.p, held.p, bytes, hipMemcpyDeviceToDevice));      // (framebuffer cells off the console keep what they held)
     }
-    rc = launch(c, X, c->stream, r, !full, in.p, held.p, next.p, fbW, fbH, nullptr);
-    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    rc = deliver(c, X, fn, full, bound, out_stream, out_len, out_info);
+    ycge_ansi::StreamJob j{};
+    j.plane = in.p; j.fbW = fbW; j.fbH = fbH; j.delta = !full; j.prev = held.p; j.next = next.p;
+    rc = hook_run(c, fn, r, j, bound, out_stream, out_len, out_info);
     if (rc != YCGE_OK || !out_shown) return rc;
     rc = copy_out(c, out_shown, full ? in.p : next.p, bytes);
     if (rc != YCGE_OK) return rc;
@@ -577,38 +598,27 @@ int test_layers(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t
     if (rc == YCGE_OK) rc = check_layers(c, fn, layers, n, raytrace_at, cells);
     if (rc != YCGE_OK) return rc;
     if (n == 0 && !r.quad) return c->fail(YCGE_ERR_INVALID_ARG, "%s: n = 0 (the unlayered streams have hooks of their own)", fn);
-    HIP_TRY(c, hipSetDevice(c->device));
-    ChexelState &X = c->chexels;
-    rc = ensure_ansi(c, X, r, bound, c->stream);
-    if (rc != YCGE_OK) return rc;
+    rc = hook_begin(c, r, bound);
     LayerStore S;
-    if (n > 0) rc = build_layers(c, X, layers, n, raytrace_at, cells, S);
+    if (rc == YCGE_OK && n > 0) rc = build_layers(c, c->chexels, layers, n, raytrace_at, cells, S);
     if (rc != YCGE_OK) return rc;
     const bool full = !r.delta || !prev_colours || !prev_glyphs || r.clear;
     const size_t console = (size_t)r.cw * (size_t)r.ch, bytes = (r.rgb ? 8 : 2) * console, fb_bytes = (r.rgb ? 8 : 2) * (size_t)fbW * fbH;
     DevBuf<uint8_t> in, comp, held, next;
     DevBuf<uint16_t> comp_glyph, held_glyph, in_glyph;
-    HIP_TRY(c, in.alloc(fb_bytes));
-    HIP_TRY(c, hipMemcpy(in.p, plane, fb_bytes, hipMemcpyHostToDevice));
-    if (r.quad) {
-        HIP_TRY(c, in_glyph.alloc((size_t)fbW * fbH));
-        HIP_TRY(c, hipMemcpy(in_glyph.p, frame_glyphs, (size_t)fbW * fbH * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
+    rc = upload(c, in, plane, fb_bytes);
+    if (rc == YCGE_OK && r.quad) rc = upload(c, in_glyph, frame_glyphs, (size_t)fbW * fbH);
+    if (rc == YCGE_OK && !full) rc = upload(c, held, prev_colours, bytes);
+    if (rc == YCGE_OK && !full) rc = upload(c, held_glyph, prev_glyphs, console);
+    if (rc != YCGE_OK) return rc;
     HIP_TRY(c, comp.alloc(bytes));
     HIP_TRY(c, comp_glyph.alloc(console));
-    if (!full) {
-        HIP_TRY(c, held.alloc(bytes));
-        HIP_TRY(c, hipMemcpy(held.p, prev_colours, bytes, hipMemcpyHostToDevice));
-        HIP_TRY(c, held_glyph.alloc(console));
-        HIP_TRY(c, hipMemcpy(held_glyph.p, prev_glyphs, console * sizeof(uint16_t), hipMemcpyHostToDevice));
-        if (r.rgb) HIP_TRY(c, next.alloc(bytes));
-    }
-    ycge_ansi::LayersRun L = layers_run(S, r.rgb);
-    L.comp = comp.p; L.comp_glyph = comp_glyph.p; L.prev = held.p; L.prev_glyph = held_glyph.p; L.next = next.p;
-    rc = launch(c, X, c->stream, r, !full, in.p, nullptr, nullptr, fbW, fbH, &L, nullptr, in_glyph.p);
-    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    rc = deliver(c, X, fn, full, bound, out_stream, out_len, r.delta ? out_info : nullptr);
+    if (!full && r.rgb) HIP_TRY(c, next.alloc(bytes));
+    ycge_ansi::StreamJob j{};
+    j.plane = in.p; j.frame_glyph = in_glyph.p; j.fbW = fbW; j.fbH = fbH; j.delta = !full;
+    j.prev = held.p; j.prev_glyph = held_glyph.p; j.next = next.p;
+    j.compose = true; j.layers = layers_run(S, r.rgb, comp.p, comp_glyph.p);
+    rc = hook_run(c, fn, r, j, bound, out_stream, out_len, r.delta ? out_info : nullptr);
     if (rc == YCGE_OK && out_colours) rc = copy_out(c, out_colours, !full && r.rgb ? next.p : comp.p, bytes);
     if (rc == YCGE_OK && out_glyphs) rc = copy_out(c, out_glyphs, comp_glyph.p, console * sizeof(uint16_t));
     return rc;

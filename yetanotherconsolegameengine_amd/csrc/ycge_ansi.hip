@@ -56,42 +56,12 @@ struct Indexed {
 
 } // namespace
 
-// the tiles of a console of `cells` cells: the length of the tile array that ycge_launch_ansi_stream is given
+// the tiles of a console of `cells` cells: the length of the tile array a job is given
 extern "C" uint32_t ycge_launch_ansi_tiles(uint32_t cells) { return tiles_of(cells); }
 
-// the stream of a cw x ch console over a fbW x fbH framebuffer of ANSI pairs at (vx, vy); palette: the 16 default indices on the device,
-// dfg / dbg their selection (0..15).  tiles: ycge_launch_ansi_tiles(cw * ch) words; out: cap bytes, at least the stream's bound (< 2^32);
-// out_len: the stream's length.  Three launches on `stream`.
-extern "C" int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
-                                       int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream)
+// The 256-colour stream of a job (ycge_ansi_layers.h): plane, prev and the composite are pairs, 2 bytes a cell; the palette the 16 default
+// indices on the device.  Full or delta, with the compose pass or without; a job with frame glyphs is the other unit's and is refused.
+extern "C" int ycge_launch_ansi_indexed(const StreamJob *j, hipStream_t stream)
 {
-    return launch_stream<Indexed>(pairs, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, clear, tiles, out, cap, out_len, stream);
-}
-
-// the delta stream of cur against prev (both fbW x fbH pairs) for the geometry of ycge_launch_ansi_stream and merge_gap `gap` (0..8).
-// tiles: 4 * ycge_launch_ansi_tiles(cw * ch) words; out: cap bytes, at least the stream's bound (< 2^32); res: 4 words {the stream's
-// length, changed cells, emitted cells, run starts}.  Three launches on `stream`.
-extern "C" int ycge_launch_ansi_delta(const uint8_t *pairs, const uint8_t *prev, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                      int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
-                                      hipStream_t stream)
-{
-    return launch_delta<Indexed>(Indexed::Delta{}, pairs, prev, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream);
-}
-
-// the two above with the console's other framebuffers (ycge_ansi_layers.h): the compose pass into L->comp / L->comp_glyph - 2 cw ch bytes
-// and cw ch code units - then the stream of that composite; the delta against L->prev / L->prev_glyph.  Four launches on `stream`.
-extern "C" int ycge_launch_ansi_layers_stream(const LayersRun *L, const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                              int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len,
-                                              hipStream_t stream)
-{
-    if (!L) return (int)hipErrorInvalidValue;
-    return launch_layered_stream<Indexed>(*L, pairs, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, clear, tiles, out, cap, out_len, stream);
-}
-
-extern "C" int ycge_launch_ansi_layers_delta(const LayersRun *L, const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                             int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
-                                             hipStream_t stream)
-{
-    if (!L) return (int)hipErrorInvalidValue;
-    return launch_layered_delta<Indexed>(Indexed::Delta{}, *L, pairs, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream);
+    return j ? launch<Indexed>(*j, Indexed::Delta{}, false, stream) : (int)hipErrorInvalidValue;
 }

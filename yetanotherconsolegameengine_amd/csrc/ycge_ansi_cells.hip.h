@@ -545,134 +545,85 @@ __global__ __launch_bounds__(kAnsiBlock) void k_compose(ComposeArgs<typename C::
     g.out_glyph[i] = (uint16_t)ch;
 }
 
-// ------------------------------------------------------------------------------------------------------------------ the launches
+// ------------------------------------------------------------------------------------------------------------------ the launch
+//
+// One StreamJob (ycge_ansi_layers.h), one check, one launcher.  launch<C, CC> runs the optional compose pass k_compose<CC>, then the
+// stream kernels of C - over the framebuffer's plane - or of Layered<C> - over the composite: count, scan, write, or their delta forms.
+// Three launches on `stream`, four with the compose pass.
 
 inline uint32_t tiles_of(uint32_t cells) { return (cells + (uint32_t)kAnsiTile - 1u) / (uint32_t)kAnsiTile; }
 
-// a launcher's geometry into the kernels' arguments; false: an argument no kernel may see
+// whether j is a job every kernel may see, its planes of T.  frame_glyphs: the compose policy reads the framebuffer's code units (the
+// composite may then be of the framebuffer alone); stores_next: the policy's delta writes j.next under j.tol (24-bit colour)
 template <typename T>
-bool fill_args(StreamArgs<T> &a, const uint8_t *plane, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg)
+bool job_ok(const StreamJob &j, bool frame_glyphs, bool stores_next)
 {
-    if (!plane || !palette || fbW <= 0 || fbH <= 0 || cw <= 0 || ch <= 0 || dfg < 0 || dfg > 15 || dbg < 0 || dbg > 15 ||
-        (uint64_t)cw * (uint64_t)ch > 0xffffffffull || (uintptr_t)plane % alignof(T) || (uintptr_t)palette % alignof(T))
+    const auto bad = [](const void *p) { return !p || (uintptr_t)p % alignof(T); };
+    if (bad(j.plane) || bad(j.palette) || j.fbW <= 0 || j.fbH <= 0 || j.cw <= 0 || j.ch <= 0 || j.dfg < 0 || j.dfg > 15 || j.dbg < 0 || j.dbg > 15 ||
+        (uint64_t)j.cw * (uint64_t)j.ch > 0xffffffffull || !j.tiles || !j.out || !j.res || j.cap > 0xffffffffull ||
+        frame_glyphs != (j.frame_glyph != nullptr) || (frame_glyphs && !j.compose))
         return false;
-    a.plane = reinterpret_cast<const T *>(plane); a.palette = reinterpret_cast<const T *>(palette);
-    a.fbW = fbW; a.fbH = fbH; a.cw = cw; a.vx = vx; a.vy = vy; a.dfg = dfg; a.dbg = dbg;
-    a.n = (uint32_t)cw * (uint32_t)ch;
-    a.glyph = nullptr;
+    if (j.delta && (bad(j.prev) || (j.compose && !j.prev_glyph) || j.gap < 0 || j.gap > kGapMax)) return false;
+    if (j.delta && stores_next &&
+        (bad(j.next) || j.next == j.plane || j.next == j.prev || (j.compose && j.next == j.layers.comp) || j.tol < 0 || j.tol > 255))
+        return false;
+    if (!j.compose) return true;
+    const LayersRun &L = j.layers;
+    if (L.n < 0 || (L.n == 0 && !frame_glyphs) || L.n > kMaxLayers || L.raytrace_at < 0 || L.raytrace_at > L.n || (L.n > 0 && (!L.colours || !L.glyphs)) ||
+        (uintptr_t)L.colours % alignof(T) || bad(L.comp) || !L.comp_glyph)
+        return false;
+    for (int k = 0; k < L.n; k++)
+        if (L.rect[k].w <= 0 || L.rect[k].h <= 0 || (uint64_t)L.rect[k].first + (uint64_t)L.rect[k].w * (uint64_t)L.rect[k].h > (uint64_t)L.cells) return false;
     return true;
 }
 
-// the full stream of a cw x ch console over the fbW x fbH framebuffer's plane at (vx, vy); palette: the encoder's output for the 16 palette
-// colours, dfg / dbg their selection (0..15).  tiles: tiles_of(cw * ch) words; out: cap bytes, at least the stream's bound (< 2^32);
-// out_len: the stream's length.  Three launches on `stream`.
-template <class C>
-int launch_stream(const uint8_t *plane, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg, int clear, uint32_t *tiles,
-                  uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream)
+// the stream kernels of policy S over d.a
+template <class S>
+void launch_cells(const StreamJob &j, const typename S::Delta &d, hipStream_t stream)
 {
-    StreamArgs<typename C::Plane> a;
-    if (!fill_args(a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !tiles || !out || !out_len || cap > 0xffffffffull) return (int)hipErrorInvalidValue;
-    const uint32_t n_tiles = tiles_of(a.n);
-    hipLaunchKernelGGL(k_count<C>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, a, tiles);
-    hipLaunchKernelGGL(k_scan<false>, dim3(1), dim3(kAnsiBlock), 0, stream, tiles, n_tiles, clear, out, (uint32_t)cap, out_len);
-    hipLaunchKernelGGL(k_write<C>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, a, (const uint32_t *)tiles, out, (uint32_t)cap);
-    return (int)hipGetLastError();
+    const uint32_t n_tiles = tiles_of(d.a.n), cap = (uint32_t)j.cap;
+    const dim3 grid(n_tiles), block(kAnsiBlock);
+    if (!j.delta) {
+        hipLaunchKernelGGL(k_count<S>, grid, block, 0, stream, d.a, j.tiles);
+        hipLaunchKernelGGL(k_scan<false>, dim3(1), block, 0, stream, j.tiles, n_tiles, j.clear, j.out, cap, j.res);
+        hipLaunchKernelGGL(k_write<S>, grid, block, 0, stream, d.a, (const uint32_t *)j.tiles, j.out, cap);
+    } else {
+        hipLaunchKernelGGL(k_delta_count<S>, grid, block, 0, stream, d, j.tiles);
+        hipLaunchKernelGGL(k_scan<true>, dim3(1), block, 0, stream, j.tiles, n_tiles, 0, j.out, cap, j.res);
+        hipLaunchKernelGGL(k_delta_write<S>, grid, block, 0, stream, d, (const uint32_t *)j.tiles, j.out, cap);
+    }
 }
 
-// the delta stream of `plane` against `prev` (same shape) for that geometry and merge_gap `gap` (0..8); d: the policy's own fields, set and
-// checked by the caller.  tiles: kTileWords * tiles_of(cw * ch) words; res: 4 words {the stream's length, changed cells, emitted cells,
-// run starts}.  Three launches on `stream`.
-template <class C>
-int launch_delta(typename C::Delta d, const uint8_t *plane, const uint8_t *prev, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                 int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream)
+// d: the policy's own delta fields, set by the unit from the job (stores_next: it has them).  CC: the compose pass's policy, C or one
+// derived from it with FrameGlyphs
+template <class C, class CC = C>
+int launch(const StreamJob &j, typename C::Delta d, bool stores_next, hipStream_t stream)
 {
     using T = typename C::Plane;
-    if (!fill_args(d.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !prev || (uintptr_t)prev % alignof(T) || gap < 0 || gap > kGapMax || !tiles ||
-        !out || !res || cap > 0xffffffffull)
-        return (int)hipErrorInvalidValue;
-    d.prev = reinterpret_cast<const T *>(prev); d.gap = gap; d.prev_glyph = nullptr;
-    const uint32_t n_tiles = tiles_of(d.a.n);
-    hipLaunchKernelGGL(k_delta_count<C>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, d, tiles);
-    hipLaunchKernelGGL(k_scan<true>, dim3(1), dim3(kAnsiBlock), 0, stream, tiles, n_tiles, 0, out, (uint32_t)cap, res);
-    hipLaunchKernelGGL(k_delta_write<C>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, d, (const uint32_t *)tiles, out, (uint32_t)cap);
-    return (int)hipGetLastError();
-}
-
-// the layered forms: the compose pass into L.comp / L.comp_glyph, then the kernels above over the composite.  false: a LayersRun no kernel may see
-// (frame_only: a composite of the raytrace framebuffer alone is allowed - the quadrant streams', whose every stream is a composite's)
-template <typename T>
-bool fill_compose(ComposeArgs<T> &g, const LayersRun &L, int ch, bool delta, bool frame_only = false)
-{
-    if (L.n < 0 || (L.n == 0 && !frame_only) || L.n > kMaxLayers || L.raytrace_at < 0 || L.raytrace_at > L.n || (L.n > 0 && (!L.colours || !L.glyphs)) || !L.comp || !L.comp_glyph ||
-        (uintptr_t)L.colours % alignof(T) || (uintptr_t)L.comp % alignof(T) || (delta && (!L.prev || !L.prev_glyph || (uintptr_t)L.prev % alignof(T))))
-        return false;
-    for (int k = 0; k < L.n; k++) {
-        const LayerRect &r = L.rect[k];
-        if (r.w <= 0 || r.h <= 0 || (uint64_t)r.first + (uint64_t)r.w * (uint64_t)r.h > (uint64_t)L.cells) return false;
-        g.rect[k] = r;
+    if (!job_ok<T>(j, kFrameGlyphs<CC>, stores_next)) return (int)hipErrorInvalidValue;
+    StreamArgs<T> &a = d.a;
+    a.plane = reinterpret_cast<const T *>(j.plane); a.palette = reinterpret_cast<const T *>(j.palette);
+    a.fbW = j.fbW; a.fbH = j.fbH; a.cw = j.cw; a.vx = j.vx; a.vy = j.vy; a.dfg = j.dfg; a.dbg = j.dbg;
+    a.n = (uint32_t)j.cw * (uint32_t)j.ch;
+    a.glyph = nullptr;
+    d.prev = reinterpret_cast<const T *>(j.prev); d.gap = j.gap; d.prev_glyph = nullptr;
+    if (!j.compose) {
+        launch_cells<C>(j, d, stream);
+        return (int)hipGetLastError();
     }
-    for (int k = L.n; k < kMaxLayers; k++) g.rect[k] = LayerRect{0, 0, 0, 0, 0};
+    const LayersRun &L = j.layers;
+    ComposeArgs<T> g;
+    g.a = a;
+    g.a.glyph = j.frame_glyph;
+    for (int k = 0; k < kMaxLayers; k++) g.rect[k] = k < L.n ? L.rect[k] : LayerRect{0, 0, 0, 0, 0};
     g.layer_colours = reinterpret_cast<const T *>(L.colours); g.layer_glyphs = L.glyphs; g.layer_cells = L.cells;
     g.n_layers = L.n; g.raytrace_at = L.raytrace_at;
     g.out = reinterpret_cast<T *>(L.comp); g.out_glyph = L.comp_glyph;
-    return true;
-}
-
-// frame_glyph: the raytrace framebuffer's code units, for a policy with FrameGlyphs alone
-template <class C>
-void launch_compose(ComposeArgs<typename C::Plane> &g, hipStream_t stream, const uint16_t *frame_glyph = nullptr)
-{
-    g.a.glyph = kFrameGlyphs<C> ? frame_glyph : nullptr;
-    hipLaunchKernelGGL(k_compose<C>, dim3((g.a.n + (uint32_t)kAnsiBlock - 1u) / (uint32_t)kAnsiBlock), dim3(kAnsiBlock), 0, stream, g);
-}
-
-// the composite as the stream kernels' framebuffer
-template <typename T>
-void composite_args(StreamArgs<T> &a, const ComposeArgs<T> &g, int ch)
-{
-    a = g.a;
-    a.plane = g.out; a.fbW = g.a.cw; a.fbH = ch; a.vx = 0; a.vy = 0; a.glyph = g.out_glyph;
-}
-
-// launch_stream's arguments and the layers: four launches on `stream`.  CC: the compose pass's policy, C or one derived from it with
-// FrameGlyphs (frame_glyph: its code units; the layers may then be none)
-template <class C, class CC = C>
-int launch_layered_stream(const LayersRun &L, const uint8_t *plane, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg, int clear,
-                          uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream, const uint16_t *frame_glyph = nullptr)
-{
-    using T = typename C::Plane;
-    ComposeArgs<T> g;
-    if (!fill_args(g.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !fill_compose(g, L, ch, false, kFrameGlyphs<CC>) || !tiles || !out || !out_len ||
-        cap > 0xffffffffull || (kFrameGlyphs<CC> && !frame_glyph))
-        return (int)hipErrorInvalidValue;
-    launch_compose<CC>(g, stream, frame_glyph);
-    StreamArgs<T> a;
-    composite_args(a, g, ch);
-    const uint32_t n_tiles = tiles_of(a.n);
-    hipLaunchKernelGGL(k_count<Layered<C>>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, a, tiles);
-    hipLaunchKernelGGL(k_scan<false>, dim3(1), dim3(kAnsiBlock), 0, stream, tiles, n_tiles, clear, out, (uint32_t)cap, out_len);
-    hipLaunchKernelGGL(k_write<Layered<C>>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, a, (const uint32_t *)tiles, out, (uint32_t)cap);
-    return (int)hipGetLastError();
-}
-
-// launch_delta's arguments and the layers: the composite against L.prev / L.prev_glyph.  Four launches on `stream`
-template <class C, class CC = C>
-int launch_layered_delta(typename C::Delta d, const LayersRun &L, const uint8_t *plane, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                         int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream,
-                         const uint16_t *frame_glyph = nullptr)
-{
-    using T = typename C::Plane;
-    ComposeArgs<T> g;
-    if (!fill_args(g.a, plane, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg) || !fill_compose(g, L, ch, true, kFrameGlyphs<CC>) || gap < 0 || gap > kGapMax || !tiles ||
-        !out || !res || cap > 0xffffffffull || (kFrameGlyphs<CC> && !frame_glyph))
-        return (int)hipErrorInvalidValue;
-    launch_compose<CC>(g, stream, frame_glyph);
-    composite_args(d.a, g, ch);
-    d.prev = reinterpret_cast<const T *>(L.prev); d.prev_glyph = L.prev_glyph; d.gap = gap;
-    const uint32_t n_tiles = tiles_of(d.a.n);
-    hipLaunchKernelGGL(k_delta_count<Layered<C>>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, d, tiles);
-    hipLaunchKernelGGL(k_scan<true>, dim3(1), dim3(kAnsiBlock), 0, stream, tiles, n_tiles, 0, out, (uint32_t)cap, res);
-    hipLaunchKernelGGL(k_delta_write<Layered<C>>, dim3(n_tiles), dim3(kAnsiBlock), 0, stream, d, (const uint32_t *)tiles, out, (uint32_t)cap);
+    hipLaunchKernelGGL(k_compose<CC>, dim3((a.n + (uint32_t)kAnsiBlock - 1u) / (uint32_t)kAnsiBlock), dim3(kAnsiBlock), 0, stream, g);
+    // the composite as the stream kernels' framebuffer: it fills the console
+    a.plane = g.out; a.fbW = j.cw; a.fbH = j.ch; a.vx = 0; a.vy = 0; a.glyph = g.out_glyph;
+    d.prev_glyph = j.prev_glyph;
+    launch_cells<Layered<C>>(j, d, stream);
     return (int)hipGetLastError();
 }
 

@@ -109,66 +109,16 @@ struct RgbQuad : Rgb, FrameGlyphs {};
 
 } // namespace
 
-// The quadrant-glyph forms (ycge_render_frame_ansi_quad / _quad_delta): the layered 24-bit streams above with `glyphs`, the fbW * fbH code
-// units k_fit_quadrants wrote beside the plane `rgba`, as the raytrace framebuffer's characters.  Every such stream is a composite's, so L
-// may hold no layer (n = 0: colours and glyphs unread).  One new instance, k_compose<RgbQuad>; the stream kernels are Layered<Rgb>'s.
-extern "C" int ycge_launch_ansi_quad_stream(const LayersRun *L, const uint8_t *rgba, const uint16_t *glyphs, int fbW, int fbH, int cw, int ch, int vx, int vy,
-                                            const uint8_t *palette, int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap,
-                                            unsigned long long *out_len, hipStream_t stream)
+// The 24-bit stream of a job (ycge_ansi_layers.h): plane, prev, next and the composite are RGBA planes (w x 2 h words for w x h cells), the
+// palette the 8 x 2 RGBA plane of the 16 palette colours.  Full or delta, with the compose pass or without; a delta's j->next receives
+// emitted ? cur : shown for every covered cell under the tolerance j->tol.
+// The quadrant-glyph forms (ycge_render_frame_ansi_quad / _quad_delta) are the jobs with frame_glyph, the fbW * fbH code units
+// k_fit_quadrants wrote beside the plane, as the raytrace framebuffer's characters.  Every such stream is a composite's, so the job may
+// hold no layer (n = 0: colours and glyphs unread).  One more instance, k_compose<RgbQuad>; the stream kernels are Layered<Rgb>'s.
+extern "C" int ycge_launch_ansi_rgb(const StreamJob *j, hipStream_t stream)
 {
-    if (!L) return (int)hipErrorInvalidValue;
-    return launch_layered_stream<Rgb, RgbQuad>(*L, rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, clear, tiles, out, cap, out_len, stream, glyphs);
-}
-
-extern "C" int ycge_launch_ansi_quad_delta(const LayersRun *L, const uint8_t *rgba, const uint16_t *glyphs, int fbW, int fbH, int cw, int ch, int vx, int vy,
-                                           const uint8_t *palette, int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap,
-                                           unsigned long long *res, hipStream_t stream)
-{
-    if (!L || !L->next || L->next == L->prev || L->next == L->comp || ((uintptr_t)L->next & 3u) || tol < 0 || tol > 255) return (int)hipErrorInvalidValue;
+    if (!j) return (int)hipErrorInvalidValue;
     Rgb::Delta d{};
-    d.next = reinterpret_cast<uint32_t *>(L->next); d.tol = tol;
-    return launch_layered_delta<Rgb, RgbQuad>(d, *L, rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream, glyphs);
-}
-
-// the 24-bit stream of a cw x ch console over a fbW x 2 fbH RGBA plane at (vx, vy); palette: the 8 x 2 RGBA plane of the 16 palette colours,
-// dfg / dbg their selection (0..15).  tiles: ycge_launch_ansi_tiles(cw * ch) words; out: cap bytes, at least the stream's bound (< 2^32);
-// out_len: the stream's length.  Three launches on `stream`.
-extern "C" int ycge_launch_ansi_rgb_stream(const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
-                                           int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream)
-{
-    return launch_stream<Rgb>(rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, clear, tiles, out, cap, out_len, stream);
-}
-
-// the 24-bit delta stream of the plane `rgba` against `shown` for that geometry, merge_gap `gap` (0..8) and tolerance `tol` (0..255); next:
-// a third plane of the same shape, distinct from both, that receives emitted ? cur : shown for every covered cell.  tiles: 4 *
-// ycge_launch_ansi_tiles(cw * ch) words; res: 4 words {the stream's length, changed cells, emitted cells, run starts}.  Three launches.
-extern "C" int ycge_launch_ansi_rgb_delta(const uint8_t *rgba, const uint8_t *shown, uint8_t *next, int fbW, int fbH, int cw, int ch, int vx, int vy,
-                                          const uint8_t *palette, int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap,
-                                          unsigned long long *res, hipStream_t stream)
-{
-    if (!next || next == shown || next == rgba || ((uintptr_t)next & 3u) || tol < 0 || tol > 255) return (int)hipErrorInvalidValue;
-    Rgb::Delta d{};
-    d.next = reinterpret_cast<uint32_t *>(next); d.tol = tol;
-    return launch_delta<Rgb>(d, rgba, shown, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream);
-}
-
-// the two above with the console's other framebuffers (ycge_ansi_layers.h): the compose pass into L->comp / L->comp_glyph - a cw x 2 ch
-// RGBA plane and cw ch code units - then the stream of that composite; the delta against L->prev (`shown`, same shape) / L->prev_glyph,
-// with L->next, distinct from both, receiving emitted ? cur : shown for every console cell.  Four launches on `stream`.
-extern "C" int ycge_launch_ansi_rgb_layers_stream(const LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                                  int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len,
-                                                  hipStream_t stream)
-{
-    if (!L) return (int)hipErrorInvalidValue;
-    return launch_layered_stream<Rgb>(*L, rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, clear, tiles, out, cap, out_len, stream);
-}
-
-extern "C" int ycge_launch_ansi_rgb_layers_delta(const LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                                 int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
-                                                 hipStream_t stream)
-{
-    if (!L || !L->next || L->next == L->prev || L->next == L->comp || ((uintptr_t)L->next & 3u) || tol < 0 || tol > 255) return (int)hipErrorInvalidValue;
-    Rgb::Delta d{};
-    d.next = reinterpret_cast<uint32_t *>(L->next); d.tol = tol;
-    return launch_layered_delta<Rgb>(d, *L, rgba, fbW, fbH, cw, ch, vx, vy, palette, dfg, dbg, gap, tiles, out, cap, res, stream);
+    d.next = reinterpret_cast<uint32_t *>(j->next); d.tol = j->tol;
+    return j->frame_glyph ? launch<Rgb, RgbQuad>(*j, d, true, stream) : launch<Rgb>(*j, d, true, stream);
 }

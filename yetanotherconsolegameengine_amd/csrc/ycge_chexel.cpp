@@ -73,6 +73,14 @@ struct ChexelLayout {
     }
 };
 
+// where the frame's colour plane of asked's stream lies (AnsiPlan::frame_in_held): chexel_encode writes it there - a _delta call's where the
+// next call finds it; 24-bit: a keyframe's plane is the next `shown`, a delta's write kernel fills that - and the stream kernels read it there
+uint8_t *ansi_frame_plane(ChexelState &X, const FrameOutputs &asked,const ChexelLayout &L, bool second)
+{
+    if (asked.plan.frame_in_held) return X.delta_held[1 - X.delta_prev].p;
+    return X.out[second ? 1 : 0].p + (asked.ansi->rgb ? L.rgba : L.ansi);
+}
+
 } // namespace
 
 namespace ycge_host {
@@ -125,13 +133,7 @@ int chexel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked, co
     }
     const bool rgb = ansi && asked.ansi->rgb;                                            // (a 24-bit stream: the RGBA plane stays on the device instead)
     uint8_t *pairs = out.p + L.ansi, *rgba = out.p + L.rgba;
-    if (ansi && asked.ansi->delta) {                                                     // (a _delta call: the pairs go where the next call finds them;
-        DevBuf<uint8_t> &next = X->delta_held[1 - X->delta_prev];                        //  24-bit: a keyframe's plane is the next `shown`, a delta's write kernel fills it)
-        const size_t bytes = (rgb ? 8 : 2) * L.n;
-        if (next.cap < bytes) HIP_TRY(c, next.alloc(bytes));
-        if (!rgb) pairs = next.p;
-        else if (asked.keyframe) rgba = next.p;
-    }
+    if (ansi) (rgb ? rgba : pairs) = ansi_frame_plane(*X, asked, L, second);
     const int e = ycge_launch_chexels(d_sdr, c->fbW, c->fbH, X->tables.p, dst[0] ? out.p + L.c16 : nullptr, dst[1] || (ansi && !rgb) ? pairs : nullptr,
                                       dst[2] || rgb ? rgba : nullptr, c->compute_units, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_encode_chexels launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -182,8 +184,7 @@ int chexel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, bool se
     }
     if (!out.ansi) return YCGE_OK;
     // (ycge_ansi.cpp: the escape stream and its length from the pairs - 24-bit: the RGBA plane - where chexel_encode put them)
-    const bool held = out.ansi->delta && !out.ansi->quad && (out.keyframe || !out.ansi->rgb);
-    return ansi_enqueue(c, stream, out, held ? X->delta_held[1 - X->delta_prev].p : src + (out.ansi->rgb ? L.rgba : L.ansi));
+    return ansi_enqueue(c, stream, out, ansi_frame_plane(*X, out, L, second));
 }
 
 } // namespace ycge_host

@@ -116,30 +116,8 @@ int ycge_launch_tonemap_quadrants(const float *hdr, int hiW, int fbW, int fbH, i
 int ycge_launch_quadrant_fit(const float *quad, int fbW, int fbH, const uint8_t *tables, int min_contrast, uint16_t *glyphs, uint8_t *rgba, int compute_units,
                              hipStream_t stream);
 uint32_t ycge_launch_ansi_tiles(uint32_t cells);
-int ycge_launch_ansi_stream(const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
-                            int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
-int ycge_launch_ansi_delta(const uint8_t *pairs, const uint8_t *prev, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
-                           int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream);
-int ycge_launch_ansi_rgb_stream(const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette, int dfg, int dbg,
-                                int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
-int ycge_launch_ansi_rgb_delta(const uint8_t *rgba, const uint8_t *shown, uint8_t *next, int fbW, int fbH, int cw, int ch, int vx, int vy,
-                               const uint8_t *palette, int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap,
-                               unsigned long long *res, hipStream_t stream);
-int ycge_launch_ansi_layers_stream(const ycge_ansi::LayersRun *L, const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                   int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
-int ycge_launch_ansi_layers_delta(const ycge_ansi::LayersRun *L, const uint8_t *pairs, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                  int dfg, int dbg, int gap, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res, hipStream_t stream);
-int ycge_launch_ansi_rgb_layers_stream(const ycge_ansi::LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                       int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *out_len, hipStream_t stream);
-int ycge_launch_ansi_rgb_layers_delta(const ycge_ansi::LayersRun *L, const uint8_t *rgba, int fbW, int fbH, int cw, int ch, int vx, int vy, const uint8_t *palette,
-                                      int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap, unsigned long long *res,
-                                      hipStream_t stream);
-int ycge_launch_ansi_quad_stream(const ycge_ansi::LayersRun *L, const uint8_t *rgba, const uint16_t *glyphs, int fbW, int fbH, int cw, int ch, int vx, int vy,
-                                 const uint8_t *palette, int dfg, int dbg, int clear, uint32_t *tiles, uint8_t *out, unsigned long long cap,
-                                 unsigned long long *out_len, hipStream_t stream);
-int ycge_launch_ansi_quad_delta(const ycge_ansi::LayersRun *L, const uint8_t *rgba, const uint16_t *glyphs, int fbW, int fbH, int cw, int ch, int vx, int vy,
-                                const uint8_t *palette, int dfg, int dbg, int gap, int tol, uint32_t *tiles, uint8_t *out, unsigned long long cap,
-                                unsigned long long *res, hipStream_t stream);
+int ycge_launch_ansi_indexed(const ycge_ansi::StreamJob *job, hipStream_t stream);
+int ycge_launch_ansi_rgb(const ycge_ansi::StreamJob *job, hipStream_t stream);
 int ycge_launch_ansi_deliver(const uint8_t *src, const unsigned long long *res, unsigned long long capacity, int full, uint8_t *dst, void *record, uint32_t *sticky,
                              int groups, hipStream_t stream);
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
@@ -494,6 +472,17 @@ struct AnsiRequest {
     int32_t gap = 0, tolerance = 0;
     bool keyframe = false;
 };
+// One stream call's plan (ycge_ansi.cpp, plan_of): made once a call from its request, the keyframe decision, the framebuffer and whether
+// layers are set.  Needs: every ChexelState buffer the call reads or writes, with the size it must have (0: not this call's; ansi_res is
+// always 4 words) - ensure_frame_buffers grows the buffers to them, and a frame in flight is queued only onto buffers that meet them already.
+// Placement: where the frame's colour plane lies - chexel_encode writes it there and the stream kernels read it there.
+struct AnsiPlan {
+    bool rgb_palette = false;                          // the default colours' triples (else their indices)
+    size_t stream = 0, tile_words = 0;                 // ansi_stream (the bound), ansi_tiles
+    size_t held = 0;                                   // delta_held[1 - delta_prev], bytes: the held plane a _delta call writes
+    size_t comp = 0, comp_cells = 0, comp_cur = 0;     // each comp_held (bytes), each glyph_held (code units); comp_cur (bytes: a 24-bit layered delta)
+    bool frame_in_held = false;                        // the frame's plane lies in delta_held[1 - delta_prev]; else in ChexelState::out, where k_encode_chexels' lie
+};
 // the console's other framebuffers as the device holds them (ycge_console_set_layers, ycge_ansi.cpp): rect[0..n) bottom first, their cells
 // one behind the other - code units, and the colours as k_encode_chexels wrote them for the cells as a cells x 1 framebuffer, in both forms
 struct LayerStore {
@@ -517,6 +506,7 @@ struct FrameOutputs {
     const Quadrants *quad = nullptr;
     const AnsiRequest *ansi = nullptr;                 // the ANSI stream asked for (its encode keeps the pairs - 24-bit colour: the RGBA plane - on the device only)
     bool keyframe = true;                              // ... runs the full stream's kernels (a _delta call: what its DeltaCall decided)
+    AnsiPlan plan;                                     // ... and its plan (DeltaCall's)
     uint8_t *dev_stream = nullptr;                     // a frame in flight: the device aliases of the caller's page-locked stream buffer (dev_capacity bytes)
     void *dev_record = nullptr;                        // ... and result record - the stream is delivered by k_ansi_deliver instead of the copy of ansi_res
     size_t dev_capacity = 0;
@@ -542,25 +532,27 @@ struct ChexelState {
     DevBuf<float> ansi_palette;                        // the 16 palette colours as 8 SDR chexels, then their 16 ANSI indices (bytes at float 48)
     bool ansi_palette_ready = false;
     PinnedBuf ansi_res_host;                           // page-locked words ansi_res is copied to
-    // The _delta calls: delta_held[delta_prev] holds what the last stream handed out left on the terminal while delta_valid, for the geometry
-    // delta_key and the colour form delta_rgb - the frame's pairs, or in 24-bit colour the plane the terminal displays; a call of the other
-    // form finds no valid state.  The encode of a 256-colour _delta call writes its pairs into delta_held[1 - delta_prev]; in 24-bit colour a
-    // keyframe's encode writes the plane there and a delta's write kernel writes emitted ? cur : shown.  A successful call flips delta_prev -
-    // nothing is copied.  Whatever shows the terminal something else (a plain _ansi call, ycge_resize, a failure) clears delta_valid.
+    // The _delta calls: delta_held[delta_prev] holds what the last stream handed out left on the terminal while delta_valid, for the stream
+    // delta_key names - the frame's pairs, or in 24-bit colour the plane the terminal displays; a call with any other key (the other colour
+    // form, another family, another geometry, layers set or not) finds no valid state.  The encode of a 256-colour _delta call writes its
+    // pairs into delta_held[1 - delta_prev]; in 24-bit colour a keyframe's encode writes the plane there and a delta's write kernel writes
+    // emitted ? cur : shown (AnsiPlan::frame_in_held).  A successful call flips delta_prev - nothing is copied.  Whatever shows the terminal
+    // something else (a plain _ansi call, ycge_resize, a failure) clears delta_valid.
     DevBuf<uint8_t> delta_held[2];
     int delta_prev = 0;
-    bool delta_valid = false, delta_rgb = false, delta_quad = false;       // (delta_quad: the quadrant family, whose held state is the composite's alone)
-    int32_t delta_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // {cw, ch, vx, vy, dfg, dbg, fbW, fbH}
+    bool delta_valid = false;
+    // {rgb, quad (the quadrant family, whose held state is the composite's alone), layered (layers were set), cw, ch, vx, vy, dfg, dbg, fbW, fbH}
+    using DeltaKey = std::array<int32_t, 11>;
+    DeltaKey delta_key{};
     DevBuf<uint8_t> rgb_palette;                       // RGB8 of the 16 palette colours: the encoder's 8 x 2 RGBA plane of ansi_palette's chexels
     bool rgb_palette_ready = false;
     // Layers (ycge_console_set_layers): while layers.n > 0 every stream is that of the console-wide composite.  comp_held / glyph_held
-    // [delta_prev] hold the composite the last _delta stream left on the terminal (delta_layered: that stream was a layered one), the call at
-    // hand composes into [1 - delta_prev] and a successful _delta call flips them with delta_held.  A 24-bit delta composes into comp_cur
-    // instead, and its write kernel fills comp_held[1 - delta_prev] with emitted ? cur : shown.  Kept across ycge_resize and ycge_scene_upload.
+    // [delta_prev] hold the composite the last _delta stream left on the terminal, the call at hand composes into [1 - delta_prev] and a
+    // successful _delta call flips them with delta_held.  A 24-bit delta composes into comp_cur instead, and its write kernel fills
+    // comp_held[1 - delta_prev] with emitted ? cur : shown.  Kept across ycge_resize and ycge_scene_upload.
     LayerStore layers;
     DevBuf<uint8_t> comp_held[2], comp_cur;
     DevBuf<uint16_t> glyph_held[2];
-    bool delta_layered = false;
     // Frames in flight (ycge_render_frame_async_ansi): the stream buffers are one set per context, so a frame's encode .. deliver follows the
     // deliver of the frame before: flight_ev is recorded behind every k_ansi_deliver, on flight_stream, and waited for in front of the next
     // encode on another stream while flight_pending (join_async clears it).  flight_sticky: the word a deliver sets when the stream exceeds
@@ -1064,7 +1056,7 @@ int render_frame_in_flight(ycge_ctx *c, FrameOutputs *out);                     
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
 int check_quadrant_call(ycge_ctx *c, const char *fn, int32_t min_contrast);              // ycge_chexel.cpp: what every quadrant call refuses - an odd super_sample, min_contrast outside 0..255
 int ensure_tables(ycge_ctx *c, ChexelState &X);                                           // ycge_chexel.cpp: LinearToSrgb8's thresholds on the device, once
-int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_pairs);   // ycge_ansi.cpp: out.ansi's stream kernels behind the encode, and the length's copy
+int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_plane);   // ycge_ansi.cpp: out.ansi's stream kernels behind the encode on the frame's plane (where out.plan puts it), and the length's copy
 // ycge_video.cpp: Video mode.  The refusals of a source frame; upload + k_video_blit on `stream` for a geometry (*d_sdr: its SDR array);
 // the SDR read-back (a pageable array: staged as run_post does it); the test hooks' bodies
 int video_check_frame(ycge_ctx *c, const char *fn, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp);
