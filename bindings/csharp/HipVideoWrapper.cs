@@ -11,6 +11,8 @@
 // the user is in Video mode - a blit changes nothing a ray-traced frame reads, so I / U switch back to the frame sequence as it was.
 // The presenter options are HipRaytraceOptions' (HipRaytraceWrapper.cs): DeviceChexelColors reads back one byte a chexel beside the SDR and
 // the host no longer searches the palette; DeviceAnsiStream hands the presenter the bytes ANSITerminalRenderer.Render() would write.
+// QuadrantGlyphs + QuadrantMinContrast: the quadrant-glyph forms (ycge_video_blit_ansi_quad / _quad_delta), so that the mode switch keeps the
+// glyph family and, with DeviceAnsiDelta, the quadrant family's delta state: the first video frame behind a traced one is a delta, not a keyframe.
 // INTEGRATION.md section 9.
 using System;
 using ConsoleGame.RayTracing;
@@ -37,6 +39,8 @@ public partial class RaytraceEntity
         private readonly int ansiMergeGap;
         private readonly bool ansiRgb;              // HipRaytraceOptions.AnsiTrueColor: the 24-bit colour forms
         private readonly int ansiTolerance;
+        private readonly bool ansiQuad;             // HipRaytraceOptions.QuadrantGlyphs: the quadrant-glyph forms (superSample even)
+        private readonly int ansiMinContrast;
 
         /// <summary>sharedContext: the context of the raytrace wrapper of the same console, whose geometry must be fb's and superSample's
         /// (IntPtr.Zero: a context of this wrapper's own).</summary>
@@ -48,6 +52,9 @@ public partial class RaytraceEntity
             ansi = options != null && options.DeviceAnsiStream ? options.AnsiPresenter ?? throw new ArgumentException("DeviceAnsiStream needs an AnsiPresenter") : null;
             ansiDelta = ansi != null && options.DeviceAnsiDelta; ansiMergeGap = options != null ? options.AnsiMergeGap : 3;
             ansiRgb = ansi != null && options.AnsiTrueColor; ansiTolerance = options != null ? options.AnsiRgbTolerance : 0;
+            ansiQuad = ansi != null && options.QuadrantGlyphs; ansiMinContrast = options != null ? options.QuadrantMinContrast : 0;
+            if (ansiQuad && (ss & 1) != 0) throw new ArgumentException("QuadrantGlyphs needs an even superSample");
+            ansiRgb |= ansiQuad;                    // (the quadrant streams are 24-bit ones: their bound is the 24-bit bound)
             deviceColors = options != null && options.DeviceChexelColors;
             if (sharedContext != IntPtr.Zero)
             {
@@ -90,6 +97,7 @@ public partial class RaytraceEntity
         public void Resize(Framebuffer fb, int superSample)
         {
             fbW = fb.Width; fbH = fb.Height; ss = Math.Max(1, superSample);
+            if (ansiQuad && (ss & 1) != 0) throw new ArgumentException("QuadrantGlyphs needs an even superSample");
             Ycge.Check(ctx, Ycge.ycge_resize(ctx, fbW, fbH, ss));
             AllocFrame();
         }
@@ -113,7 +121,14 @@ public partial class RaytraceEntity
                 }
                 HipConsoleLayers.Set(ctx, ansi.FrameBuffers, fb);               // (the presenter's other framebuffers, composed on the device)
                 UIntPtr len;
-                if (ansiRgb && ansiDelta)
+                if (ansiQuad && ansiDelta)
+                    Ycge.Check(ctx, Ycge.ycge_video_blit_ansi_quad_delta(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
+                                                                         ansi.ClearPending ? 1 : 0, ansiMergeGap, ansiTolerance, 0, ansiMinContrast, ansiBuf, (UIntPtr)ansiCap, &len,
+                                                                         null, null));
+                else if (ansiQuad)
+                    Ycge.Check(ctx, Ycge.ycge_video_blit_ansi_quad(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
+                                                                   ansi.ClearPending ? 1 : 0, ansiMinContrast, ansiBuf, (UIntPtr)ansiCap, &len, null));
+                else if (ansiRgb && ansiDelta)
                     Ycge.Check(ctx, Ycge.ycge_video_blit_ansi_rgb_delta(ctx, frame, srcW, srcH, bpp, cw, ch, fb.ViewportX, fb.ViewportY, (int)ansi.DefaultFg, (int)ansi.DefaultBg,
                                                                         ansi.ClearPending ? 1 : 0, ansiMergeGap, ansiTolerance, 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null));
                 else if (ansiRgb)

@@ -369,6 +369,16 @@ namespace ConsoleGame.RayTracing.Native
                                                                                     int defaultBg16, int clearScreen, int mergeGap, int tolerance, int keyframe,
                                                                                     int minContrast, byte* outStream, UIntPtr capacity, UIntPtr* outLen, uint* outInfo,
                                                                                     float* outTopBottomSdr, YFrameStats* stats);
+        // ... and of a video frame: the video calls with minContrast where the frame forms have it; the SDR is ycge_video_blit's bit for bit
+        [DllImport(Lib)] public static extern int ycge_video_blit_quadrants(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, float* outTopBottomSdr,
+                                                                            float* outQuadSdr, ushort* outGlyphs, byte* outRgba, int minContrast);
+        [DllImport(Lib)] public static extern int ycge_video_blit_ansi_quad(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int consoleW, int consoleH,
+                                                                            int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, int minContrast,
+                                                                            byte* outStream, UIntPtr capacity, UIntPtr* outLen, float* outTopBottomSdr);
+        [DllImport(Lib)] public static extern int ycge_video_blit_ansi_quad_delta(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int consoleW, int consoleH,
+                                                                                  int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, int mergeGap,
+                                                                                  int tolerance, int keyframe, int minContrast, byte* outStream, UIntPtr capacity,
+                                                                                  UIntPtr* outLen, uint* outInfo, float* outTopBottomSdr);
         // the console's other framebuffers for every stream call above (found by symbol lookup, ABI stays 10); YConsoleLayer, YChexel and
         // HipConsoleLayers: bindings/csharp/YcgeConsole.cs
         [DllImport(Lib)] public static extern int ycge_console_set_layers(IntPtr ctx, YConsoleLayer* layers, int n, int raytraceAt);

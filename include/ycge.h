@@ -834,6 +834,42 @@ int ycge_video_blit_ansi_rgb_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t 
                                    int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance,
                                    int32_t keyframe, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */,
                                    float *out_top_bottom_sdr /* may be NULL */);
+/* --- Quadrant glyphs in Video mode: the quadrant-glyph family (the rules: below, at ycge_render_frame_quadrants) for the frame a reader
+ * shows, so that a host with quadrant glyphs on keeps the glyph family and the delta state across the switch to a camera or a film.  Added
+ * after ABI 10 without changing it: YCGE_ABI_VERSION stays 10, no existing struct or prototype changes; a host detects the exports by symbol
+ * lookup.  Each call is its video call's argument list with min_contrast where the frame form has it.
+ *   Sub-cell colours.  super_sample = ss must be even.  The hi-res grid, the letterbox geometry, the two weight tables and every sample are
+ *   ycge_video_blit's for the context's (fbW, fbH, ss); a sample is SampleSourceLanczos' value after its per-channel Clamp01
+ *   (VideoRenderer.cs:184-241).  Quadrant k - 0 = TL, 1 = TR, 2 = BL, 3 = BR - of chexel (cx, cy) covers columns cx ss + (k & 1) ss / 2 ..
+ *   + ss / 2 - 1 and rows (2 cy + (k >> 1)) ss .. + ss - 1.  Its colour: the binary32 sum of its samples, rows outer, columns inner, per
+ *   channel, from 0, times 1.0f / (float)((ss / 2) ss), through Clamp01 - the blit's own average-and-saturate (:126-128) over half the columns.
+ *   No tone map: a video frame has none.  out_quad_sdr in the frame call's layout, {TL rgb, TR rgb, BL rgb, BR rgb} a chexel.
+ *   out_top_bottom_sdr is ycge_video_blit's array for the same frame, bit for bit: the serial sy, sx sum, not the quadrant sums' (in binary32
+ *   the left and the right half do not add up to it).
+ *   The fit, the glyph and the RGBA plane: the rules at ycge_render_frame_quadrants on these sub-cell colours, the bytes the chexel encoder's
+ *   Clamp01 / LinearToSrgb8.  Destinations of ycge_video_blit_quadrants as there: any subset may be NULL, not all; pageable or page-locked.
+ *   ycge_video_blit_ansi_quad: ycge_render_frame_ansi_quad's stream for those planes.  ycge_video_blit_ansi_quad_delta: the layered 24-bit
+ *   delta contract with the glyph, as ycge_render_frame_ansi_quad_delta; layers are composed as there.  ycge_ansi_rgb_stream_bound stands.
+ *   State.  One terminal per context: these streams and the frame quad streams share the quadrant family's delta state, as
+ *   ycge_video_blit_ansi_delta shares ycge_render_frame_ansi_delta's - a video _quad_delta behind a frame _quad_delta of the same geometry key
+ *   is a delta, and the other way round; a stream of another family in between makes the next one a keyframe.  min_contrast is not part of
+ *   the key.  A blit changes nothing a traced frame reads, and first joins the frames in flight.
+ *   Refused before any device work, nothing written then or later, the message naming the value, the context usable and the delta state
+ *   untouched (YCGE_ERR_INVALID_ARG): everything the corresponding ycge_video_blit / _ansi_rgb / _ansi_rgb_delta call refuses; an odd or
+ *   < 2 super_sample; min_contrast outside 0..255; all destinations NULL. */
+int ycge_video_blit_quadrants(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                              float *out_top_bottom_sdr /* may be NULL */, float *out_quad_sdr /* fbW*fbH*12, may be NULL */,
+                              uint16_t *out_glyphs /* fbW*fbH, may be NULL */, uint8_t *out_rgba /* fbW x 2 fbH RGBA8, may be NULL */,
+                              int32_t min_contrast);
+int ycge_video_blit_ansi_quad(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                              int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
+                              int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t min_contrast,
+                              uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr /* may be NULL */);
+int ycge_video_blit_ansi_quad_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                                    int32_t console_w, int32_t console_h, int32_t viewport_x, int32_t viewport_y,
+                                    int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance,
+                                    int32_t keyframe, int32_t min_contrast, uint8_t *out_stream, size_t capacity, size_t *out_len,
+                                    uint32_t *out_info /* 4 words or NULL */, float *out_top_bottom_sdr /* may be NULL */);
 /* --- The console's other framebuffers in the device streams: layers, any glyph.  Terminal registers a console-sized entity framebuffer
  * first (Renderer/Terminal.cs:53-55), RaytraceEntity adds its own on top (RaytraceEntity.cs:297-298), any entity may add more, and
  * ANSITerminalRenderer.GetChexelForPoint (:67-84) composes them: the topmost framebuffer whose chexel at the point has Char != ' ' wins,
@@ -909,7 +945,7 @@ int ycge_console_set_layers(ycge_ctx *ctx, const ycge_console_layer *layers, int
  *   Refused before any device work, nothing written then or later, the message naming the value (YCGE_ERR_INVALID_ARG): an odd super_sample;
  *   min_contrast outside 0..255; everything the corresponding _chexels / _ansi_rgb / _ansi_rgb_delta call refuses - all destinations NULL, a
  *   NULL stream or length, capacity below the bound, defaults outside 0..15, a peer context, RCCL with lean slabs, tolerance, merge_gap.
- *   Not offered: 256-colour and console-16 forms, the video blits, frames in flight, sextants and octants, a temporal hysteresis beyond M. */
+ *   Not offered: 256-colour and console-16 forms, frames in flight, sextants and octants, a temporal hysteresis beyond M. */
 int ycge_render_frame_quadrants(ycge_ctx *ctx, float *out_top_bottom_sdr /* may be NULL */, float *out_quad_sdr /* fbW*fbH*12, may be NULL */,
                                 uint16_t *out_glyphs /* fbW*fbH, may be NULL */, uint8_t *out_rgba /* fbW x 2 fbH RGBA8, may be NULL */,
                                 int32_t min_contrast, ycge_frame_stats *stats);

@@ -111,11 +111,14 @@ int ycge_test_ansi_deliver(ycge_ctx *c, const uint8_t *src, size_t n_src, uint64
 /* ---- Video mode (csrc/ycge_video.cpp).  ycge_host_video_tables: host only, no device - for src_w x src_h -> fbW x fbH ss the tables
  * k_video_blit reads, as the library computed them with the C library's sinf: per hi-res column x0 (hiW = fbW*ss entries) and its six
  * normalised weights (6 hiW), per hi-res row y0 (hiH = fbH*2*ss) and weights (6 hiH), and {scale, offX, offY} (VideoRenderer.cs:75-81).
- * ycge_test_video_blit: the kernel alone on a caller-given geometry, whatever the context's framebuffer is; sdr_out fbW*fbH*6 f32 */
+ * ycge_test_video_blit: the kernel alone on a caller-given geometry, whatever the context's framebuffer is; sdr_out fbW*fbH*6 f32.
+ * ycge_test_video_blit_quadrants: k_video_blit_quadrants alone likewise, ss even; sdr_out as there, quad_out fbW*fbH*12 f32 {TL, TR, BL, BR} */
 int ycge_host_video_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0_out, float *wx_out, int32_t *y0_out,
                            float *wy_out, float *geometry_out);
 int ycge_test_video_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t fbW, int32_t fbH, int32_t ss,
                          float *sdr_out);
+int ycge_test_video_blit_quadrants(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t fbW, int32_t fbH,
+                                   int32_t ss, float *sdr_out, float *quad_out);
 /* ---- the post stage (csrc/ycge_post_host.cpp, csrc/ycge_post.hip) on caller-given inputs.  state_out = 6 words: {aeExposure, effective exposure} as
  * binary32, the chunks k_exposure_sum added one by one, 0, the frame's logSum as binary32, its counted samples.
  * ycge_test_post_stage: hist / albedo / normal hiW*hiH*3 f32, depth hiW*hiH f32, sky hiW*hiH u8 are copied over the context's TAA history and

@@ -386,6 +386,14 @@ _PROTOTYPES = {
     "ycge_render_frame_ansi_quad_delta": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                     C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
                                                     C.POINTER(C.c_float), C.POINTER(FrameStats)]),
+    # ... and of a video frame: the video calls' arguments with min_contrast where the frame forms have it
+    "ycge_video_blit_quadrants": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                            C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.c_int32]),
+    "ycge_video_blit_ansi_quad": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    "ycge_video_blit_ansi_quad_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
+                                                  C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     # (req: C.byref(abi.AnsiAsync); out_result: the address of an abi.AnsiAsyncResult in page-locked memory)
     "ycge_render_frame_async_ansi": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
@@ -463,6 +471,7 @@ TAA_FORM_PLANES, TAA_FORM_IN_PLACE, TAA_FORM_KEEP_PLANES, TAA_FORM_IN_FLIGHT, TA
 VIDEO_HOOK_PROTOTYPES = {
     "ycge_host_video_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ycge_test_video_blit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ycge_test_video_blit_quadrants": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 # test hook of the delta ANSI stream (csrc/ycge_ansi.cpp), bound where it is used (tests/test_gpu_ansi_delta.py)
 ANSI_DELTA_HOOK_PROTOTYPES = {

@@ -33,6 +33,8 @@
 // The quadrant-glyph forms (ycge_render_frame_ansi_quad, _quad_delta): `quad` set beside `rgb`.  The frame's plane is k_fit_quadrants' and a
 // glyph plane comes with it, so EVERY such stream runs the compose pass - with no layers set, over the raytrace framebuffer alone - and walks
 // the composite with the layered 24-bit kernels; its delta state is the composite's (comp_held / glyph_held), a third family beside the two.
+// The video forms (ycge_video_blit_ansi_quad, _quad_delta) are video() with the same request: k_video_blit_quadrants makes the sub-cell
+// colours, the encode is the fit alone, and the delta state is the family's one.
 //
 // The default cell's colours are ansi(palette16[k]): k_encode_chexels run once on the 16 palette colours, so no second formula exists.
 #include "ycge_ctx.h"
@@ -428,16 +430,18 @@ int video(ycge_ctx *c, const char *fn, const AnsiRequest &r, const uint8_t *fram
     unsigned long long bound = 0;
     int rc = video_check_frame(c, fn, frame, src_w, src_h, bytes_per_pixel);
     if (rc == YCGE_OK) rc = check_stream_args(c, fn, r, out_stream, capacity, out_len, bound);
+    if (rc == YCGE_OK && r.quad) rc = check_quadrant_call(c, fn, r.min_contrast);
     if (rc != YCGE_OK) return rc;
     rc = join_async(c);
     if (rc != YCGE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     DeltaCall call(c, r, bound);
     FrameOutputs out = call.outputs(out_top_bottom_sdr);
+    out.quad_colours_ready = r.quad;          // (the quadrant family: k_video_blit_quadrants writes the sub-cell colours, the encode is the fit alone)
     ChexelState &X = c->chexels;
     rc = ensure_frame_buffers(c, X, call.plan, c->stream);
     const float *d_sdr = nullptr;
-    if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr);
+    if (rc == YCGE_OK) rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr, r.quad ? &X.quad_sdr : nullptr);
     if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, out, d_sdr, false);
     if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out);
     if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, out, false);          // (the stream kernels and the copy of what they report)
@@ -763,6 +767,27 @@ int ycge_render_frame_ansi_quad_delta(ycge_ctx *c, int32_t console_w, int32_t co
 try {
     const AnsiRequest r = quad_request(console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, min_contrast);
     return frame(c, "ycge_render_frame_ansi_quad_delta", with_delta(r, merge_gap, tolerance, keyframe), out_stream, capacity, out_len, out_info, out_top_bottom_sdr, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// ... and of a video frame, on the quadrant family's delta state: one terminal, whichever renderer the host shows on it
+int ycge_video_blit_ansi_quad(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t console_w, int32_t console_h,
+                              int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t min_contrast,
+                              uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr)
+try {
+    return video(c, "ycge_video_blit_ansi_quad", quad_request(console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, min_contrast), frame,
+                 src_w, src_h, bytes_per_pixel, out_stream, capacity, out_len, nullptr, out_top_bottom_sdr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_video_blit_ansi_quad_delta(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t console_w, int32_t console_h,
+                                    int32_t viewport_x, int32_t viewport_y, int32_t default_fg16, int32_t default_bg16, int32_t clear_screen, int32_t merge_gap,
+                                    int32_t tolerance, int32_t keyframe, int32_t min_contrast, uint8_t *out_stream, size_t capacity, size_t *out_len,
+                                    uint32_t *out_info, float *out_top_bottom_sdr)
+try {
+    const AnsiRequest r = quad_request(console_w, console_h, viewport_x, viewport_y, default_fg16, default_bg16, clear_screen, min_contrast);
+    return video(c, "ycge_video_blit_ansi_quad_delta", with_delta(r, merge_gap, tolerance, keyframe), frame, src_w, src_h, bytes_per_pixel, out_stream, capacity,
+                 out_len, out_info, out_top_bottom_sdr);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

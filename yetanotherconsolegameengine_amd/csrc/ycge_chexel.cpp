@@ -122,10 +122,17 @@ int chexel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked, co
     if (quad) {
         // k_tonemap_quadrants on the buffer and exposure state the tonemap in front of this read, then the fit: the glyph plane, and the RGBA
         // plane where the encoder's lies.  The held planes of a _quad_delta call are the composite's (ycge_ansi.cpp), so nothing moves here.
-        if (X->quad_sdr.cap < 12 * L.n) HIP_TRY(c, X->quad_sdr.alloc(12 * L.n));
+        // A video blit's sub-cell colours are there already (k_video_blit_quadrants, no tone map): the fit alone.
+        if (X->quad_sdr.cap < 12 * L.n) {
+            if (asked.quad_colours_ready) return c->fail(YCGE_ERR_INTERNAL, "chexel_encode: the sub-cell colours of %zu chexels are not on the device", L.n);
+            HIP_TRY(c, X->quad_sdr.alloc(12 * L.n));
+        }
         if (X->quad_glyphs.cap < L.n) HIP_TRY(c, X->quad_glyphs.alloc(L.n));
-        int e = ycge_launch_tonemap_quadrants(c->denoised, c->hiW, c->fbW, c->fbH, c->ss, 2.2f, 2.0f, 0.0f, c->tone_state.p, X->quad_sdr.p, stream);
-        if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_tonemap_quadrants launch failed: %s", hipGetErrorString((hipError_t)e));
+        int e = 0;
+        if (!asked.quad_colours_ready) {
+            e = ycge_launch_tonemap_quadrants(c->denoised, c->hiW, c->fbW, c->fbH, c->ss, 2.2f, 2.0f, 0.0f, c->tone_state.p, X->quad_sdr.p, stream);
+            if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_tonemap_quadrants launch failed: %s", hipGetErrorString((hipError_t)e));
+        }
         e = ycge_launch_quadrant_fit(X->quad_sdr.p, c->fbW, c->fbH, X->tables.p, asked.quad ? asked.quad->min_contrast : asked.ansi->min_contrast, X->quad_glyphs.p,
                                      out.p + L.rgba, c->compute_units, stream);
         if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_fit_quadrants launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -277,6 +284,37 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// The quadrant-glyph planes of a video frame (the contract: include/ycge.h): ycge_video_blit's frame through k_video_blit_quadrants, which
+// writes the sub-cell colours beside the SDR, then the fit and ycge_render_frame_quadrants' read-back.  The SDR alone: ycge_video_blit's launch
+int ycge_video_blit_quadrants(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, float *out_top_bottom_sdr, float *out_quad_sdr,
+                              uint16_t *out_glyphs, uint8_t *out_rgba, int32_t min_contrast)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_video_blit_quadrants";
+    int rc = video_check_frame(c, fn, frame, src_w, src_h, bytes_per_pixel);
+    if (rc != YCGE_OK) return rc;
+    if (!out_top_bottom_sdr && !out_quad_sdr && !out_glyphs && !out_rgba)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, quad_sdr, glyphs, rgba)", fn);
+    rc = check_quadrant_call(c, fn, min_contrast);
+    if (rc != YCGE_OK) return rc;
+    rc = join_async(c);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const FrameOutputs::Quadrants q{out_quad_sdr, out_glyphs, out_rgba, min_contrast};
+    FrameOutputs out(out_top_bottom_sdr);
+    if (out_quad_sdr || out_glyphs || out_rgba) { out.quad = &q; out.quad_colours_ready = true; }
+    const float *d_sdr = nullptr;
+    rc = video_enqueue(c, c->stream, frame, src_w, src_h, bytes_per_pixel, c->fbW, c->fbH, c->ss, &d_sdr, out.quad ? &c->chexels.quad_sdr : nullptr);
+    if (rc == YCGE_OK) rc = chexel_encode(c, c->stream, out, d_sdr, false);
+    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out);
+    if (rc == YCGE_OK) rc = chexel_read_back(c, c->stream, out, false);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }          // (nothing of this call is queued when it returns)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    out.finish();
+    return YCGE_OK;
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 // test hook: the column and row tables of a video geometry as the library computes them (host only; ycge_video.cpp)
 int ycge_host_video_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0_out, float *wx_out, int32_t *y0_out, float *wy_out,
                            float *geometry_out)
@@ -290,6 +328,17 @@ int ycge_test_video_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;
     return video_test_blit(c, frame, src_w, src_h, bytes_per_pixel, fbW, fbH, ss, sdr_out);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// test hook: k_video_blit_quadrants alone on a caller-given geometry (ss even), whatever the context's framebuffer is: the SDR (fbW*fbH*6) and
+// the sub-cell colours (fbW*fbH*12) in the caller's arrays.  The context's quadrant planes are not touched
+int ycge_test_video_blit_quadrants(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t fbW, int32_t fbH, int32_t ss,
+                                   float *sdr_out, float *quad_out)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!quad_out) return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_video_blit_quadrants: quad_out is NULL");
+    return video_test_blit(c, frame, src_w, src_h, bytes_per_pixel, fbW, fbH, ss, sdr_out, quad_out);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

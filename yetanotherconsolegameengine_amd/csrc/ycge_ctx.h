@@ -121,6 +121,8 @@ int ycge_launch_ansi_rgb(const ycge_ansi::StreamJob *job, hipStream_t stream);
 int ycge_launch_ansi_deliver(const uint8_t *src, const unsigned long long *res, unsigned long long capacity, int full, uint8_t *dst, void *record, uint32_t *sticky,
                              int groups, hipStream_t stream);
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
+int ycge_launch_video_blit_quadrants(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, float *quad_sdr,
+                                     hipStream_t stream);
 size_t ycge_launch_obj_sizes(int which);
 int ycge_launch_obj_count_lines(const uint8_t *text, uint32_t n, uint32_t first, uint32_t *tiles, void *header, hipStream_t stream);
 int ycge_launch_obj_classify(const uint8_t *text, uint32_t n, uint32_t first, const uint32_t *tiles, uint32_t *line_start, uint32_t n_lines, uint32_t *add,
@@ -504,6 +506,7 @@ struct FrameOutputs {
     // ycge_render_frame_quadrants: the caller's sub-cell colours (fbW*fbH*12 f32), glyph plane and fitted RGBA plane, any of them NULL
     struct Quadrants { float *sdr; uint16_t *glyphs; uint8_t *rgba; int32_t min_contrast; };
     const Quadrants *quad = nullptr;
+    bool quad_colours_ready = false;                   // a video blit: k_video_blit_quadrants wrote ChexelState::quad_sdr already - the encode is the fit alone
     const AnsiRequest *ansi = nullptr;                 // the ANSI stream asked for (its encode keeps the pairs - 24-bit colour: the RGBA plane - on the device only)
     bool keyframe = true;                              // ... runs the full stream's kernels (a _delta call: what its DeltaCall decided)
     AnsiPlan plan;                                     // ... and its plan (DeltaCall's)
@@ -1060,10 +1063,12 @@ int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const
 // ycge_video.cpp: Video mode.  The refusals of a source frame; upload + k_video_blit on `stream` for a geometry (*d_sdr: its SDR array);
 // the SDR read-back (a pageable array: staged as run_post does it); the test hooks' bodies
 int video_check_frame(ycge_ctx *c, const char *fn, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp);
-int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const float **d_sdr);
+int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const float **d_sdr,
+                  DevBuf<float> *quad_sdr = nullptr);
 int video_read_sdr(ycge_ctx *c, hipStream_t stream, const float *d_sdr, FrameOutputs &out);
 int video_host_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0, float *wx, int32_t *y0, float *wy, float *geom3);
-int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out);
+int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out,
+                    float *quad_out = nullptr);
 // ycge_obj.cpp: MeshLoader.FromObj from file bytes - the bodies of ycge_obj_parse_host (no context), ycge_obj_parse / _read / _triangles / _release and ycge_debug_obj_stats
 int obj_parse_host(const uint8_t *text, size_t bytes, float *positions, int32_t *faces, ycge_obj_info *info, char *msg, size_t msg_bytes);
 int obj_parse(ycge_ctx *c, const uint8_t *text, size_t bytes, ycge_obj_info *info);

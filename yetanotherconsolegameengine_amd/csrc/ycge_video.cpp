@@ -5,6 +5,8 @@
 // this file's own, then what a ray-traced frame's presenters get - ycge_chexel.cpp's encode and read-back and ycge_ansi.cpp's stream on
 // the same stream - and one synchronisation.  It needs no scene and touches nothing a ray-traced frame reads.  The entry points
 // themselves stand beside the calls they mirror (ycge_chexel.cpp, ycge_ansi.cpp: their request guards are private to those files).
+// The quadrant-glyph forms (ycge_video_blit_quadrants, _ansi_quad, _ansi_quad_delta) launch k_video_blit_quadrants instead, which writes the
+// 2 x 2 sub-cell colours into ChexelState::quad_sdr beside the SDR; k_fit_quadrants and the quadrant streams then run as for a traced frame.
 //
 // The Lanczos weights are separable: they depend on the hi-res column alone or on the hi-res row alone.  The host computes them ONCE per
 // geometry with the C library's sinf - the function MathF.Sin calls - in binary32, operation for operation as SampleSourceLanczos
@@ -126,13 +128,17 @@ static int ensure_video_tables(ycge_ctx *c, VideoState &V, int src_w, int src_h,
     return YCGE_OK;
 }
 
-int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const float **d_sdr)
+// quad_sdr (or NULL): the quadrant form - k_video_blit_quadrants writes the sub-cell colours there, fbW * fbH * 12 floats, beside the SDR
+// (ss even: the caller's check_quadrant_call)
+int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const float **d_sdr,
+                  DevBuf<float> *quad_sdr)
 {
     VideoState &V = c->video;
     { const int rc = ensure_video_tables(c, V, src_w, src_h, fbW, fbH, ss); if (rc != YCGE_OK) return rc; }
     const size_t bytes = (size_t)src_w * src_h * bpp;
     HIP_TRY(c, V.frame.reserve(bytes));                // (DevBuf's padding takes the last 3-byte pixel's 32-bit load)
     HIP_TRY(c, V.sdr.reserve((size_t)fbW * fbH * 6));
+    if (quad_sdr) HIP_TRY(c, quad_sdr->reserve((size_t)fbW * fbH * 12));
     const uint8_t *src = frame;
     if (!host_memory_is_page_locked(frame, bytes)) {   // the caller's array is its own again when the call returns: every blit ends synchronised
         HIP_TRY(c, V.stage.reserve(bytes));
@@ -140,8 +146,9 @@ int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src
         src = V.stage.data();
     }
     HIP_TRY(c, hipMemcpyAsync(V.frame.p, src, bytes, hipMemcpyHostToDevice, stream));
-    const int e = ycge_launch_video_blit(V.frame.p, src_w, src_h, bpp, fbW, fbH, ss, V.tables.p, V.sdr.p, stream);
-    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_video_blit launch failed: %s", hipGetErrorString((hipError_t)e));
+    const int e = quad_sdr ? ycge_launch_video_blit_quadrants(V.frame.p, src_w, src_h, bpp, fbW, fbH, ss, V.tables.p, V.sdr.p, quad_sdr->p, stream)
+                           : ycge_launch_video_blit(V.frame.p, src_w, src_h, bpp, fbW, fbH, ss, V.tables.p, V.sdr.p, stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_video_blit%s launch failed: %s", quad_sdr ? "_quadrants" : "", hipGetErrorString((hipError_t)e));
     *d_sdr = V.sdr.p;
     return YCGE_OK;
 }
@@ -174,17 +181,24 @@ int video_host_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, in
     return YCGE_OK;
 }
 
-int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out)
+// quad_out (or NULL): ycge_test_video_blit_quadrants - the quadrant form into a buffer of the hook's own, so the context's planes stay what they were
+int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out, float *quad_out)
 {
+    const char *fn = quad_out ? "ycge_test_video_blit_quadrants" : "ycge_test_video_blit";
     if (!frame || !sdr_out || src_w < 1 || src_h < 1 || (bpp != 3 && bpp != 4) || (int64_t)src_w * src_h * bpp >= ((int64_t)1 << 31) || !geometry_ok(fbW, fbH, ss))
-        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_video_blit: bad arguments (%d x %d x %d -> %d x %d ss %d)", src_w, src_h, bpp, fbW, fbH, ss);
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad arguments (%d x %d x %d -> %d x %d ss %d)", fn, src_w, src_h, bpp, fbW, fbH, ss);
+    if (quad_out && (ss < 2 || (ss & 1)))
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: super_sample %d (the quadrants halve a chexel's columns: it must be even)", fn, ss);
     { const int jr = join_async(c); if (jr != YCGE_OK) return jr; }
     HIP_TRY(c, hipSetDevice(c->device));
     const float *d_sdr = nullptr;
-    const int rc = video_enqueue(c, c->stream, frame, src_w, src_h, bpp, fbW, fbH, ss, &d_sdr);
-    if (rc != YCGE_OK) return rc;
+    DevBuf<float> quad;
+    const int rc = video_enqueue(c, c->stream, frame, src_w, src_h, bpp, fbW, fbH, ss, &d_sdr, quad_out ? &quad : nullptr);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return copy_out(c, sdr_out, d_sdr, (size_t)fbW * fbH * 6 * sizeof(float));
+    const int rs = copy_out(c, sdr_out, d_sdr, (size_t)fbW * fbH * 6 * sizeof(float));
+    if (rs != YCGE_OK || !quad_out) return rs;
+    return copy_out(c, quad_out, quad.p, (size_t)fbW * fbH * 12 * sizeof(float));
 }
 
 } // namespace ycge_host

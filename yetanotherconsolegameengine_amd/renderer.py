@@ -1361,7 +1361,49 @@ class VideoRenderer:
         return self._ansi_call(self.L.ycge_video_blit_ansi_rgb_delta, frame, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
                                rgb=True, delta=(merge_gap, tolerance, bool(keyframe)))
 
+    # ---------------------------------------------------------------- quadrant glyphs (ycge_video_blit_quadrants / _ansi_quad / _ansi_quad_delta)
+    def TryFlipAndBlitQuadrants(self, frame, quad_sdr: bool = False, glyphs: bool = True, rgba: bool = True, sdr: bool = False, min_contrast: int = 0,
+                                out: Optional[dict] = None) -> dict:
+        """RaytraceRenderer.TryFlipAndBlitQuadrants for `frame` (ycge_video_blit_quadrants; super_sample must be even): {name: array} for
+        each output asked - "quad_sdr" (fbH, fbW, 4, 3) f32 {TL, TR, BL, BR}, each the saturated average of its ss / 2 x ss Lanczos samples;
+        "glyphs" (fbH, fbW) uint16; "rgba" (2 fbH, fbW, 4) uint8, row 2 cy the foreground; "sdr" as TryFlipAndBlit's, bit for bit.  `out` =
+        caller's arrays to fill instead (any of those four; pageable or page-locked)."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        if out is None:
+            shapes = {"sdr": ((self.fbH, self.fbW, 2, 3), np.float32), "quad_sdr": ((self.fbH, self.fbW, 4, 3), np.float32),
+                      "glyphs": ((self.fbH, self.fbW), np.uint16), "rgba": ((2 * self.fbH, self.fbW, 4), np.uint8)}
+            want = {"sdr": sdr, "quad_sdr": quad_sdr, "glyphs": glyphs, "rgba": rgba}
+            out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items() if want[k]}
+        p = lambda k, t: out[k].ctypes.data_as(C.POINTER(t)) if out.get(k) is not None else None
+        self._r._check(self.L.ycge_video_blit_quadrants(self.ctx, ptr, w, h, bpp, p("sdr", C.c_float), p("quad_sdr", C.c_float), p("glyphs", C.c_uint16),
+                                                        p("rgba", C.c_uint8), int(min_contrast)))
+        return out
+
+    def TryFlipAndBlitAnsiQuad(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                               clear_screen: bool = False, min_contrast: int = 0, sdr: bool = False):
+        """TryFlipAndBlitAnsiRgb with quadrant block glyphs (ycge_video_blit_ansi_quad): `bytes`, or (bytes, SDR array) with sdr=True."""
+        return self._ansi_call(self.L.ycge_video_blit_ansi_quad, frame, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr, rgb=True,
+                               extra=(min_contrast,))
+
+    def TryFlipAndBlitAnsiQuadDelta(self, frame, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
+                                    clear_screen: bool = False, merge_gap: int = 3, tolerance: int = 0, keyframe: bool = False, min_contrast: int = 0,
+                                    sdr: bool = False):
+        """The delta form of TryFlipAndBlitAnsiQuad (ycge_video_blit_ansi_quad_delta), on the quadrant family's delta state this context shares
+        with RaytraceRenderer.TryFlipAndBlitAnsiQuadDelta: (bytes, info) or (bytes, info, SDR array) with sdr=True."""
+        return self._ansi_call(self.L.ycge_video_blit_ansi_quad_delta, frame, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
+                               rgb=True, delta=(merge_gap, tolerance, bool(keyframe), min_contrast))
+
     # ---------------------------------------------------------------- tests only
+    def blit_quadrants_probe(self, frame, fb_width: int, fb_height: int, superSample: int = 2):
+        """k_video_blit_quadrants alone on a caller-given geometry (ycge_test_video_blit_quadrants): (SDR array, sub-cell colours)."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        fn = self.L.ycge_test_video_blit_quadrants
+        fn.restype, fn.argtypes = abi.VIDEO_HOOK_PROTOTYPES["ycge_test_video_blit_quadrants"]
+        s = np.zeros((fb_height, fb_width, 2, 3), np.float32)
+        q = np.zeros((fb_height, fb_width, 4, 3), np.float32)
+        self._r._check(fn(self.ctx, f.ctypes.data, w, h, bpp, int(fb_width), int(fb_height), int(superSample), s.ctypes.data, q.ctypes.data))
+        return s, q
+
     def blit_probe(self, frame, fb_width: int, fb_height: int, superSample: int = 1) -> np.ndarray:
         """k_video_blit alone on a caller-given geometry (ycge_test_video_blit), whatever this console's size: the SDR array."""
         f, ptr, w, h, bpp = self._frame_args(frame)
