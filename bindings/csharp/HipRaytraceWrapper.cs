@@ -43,6 +43,11 @@
 //                DeviceAnsiDelta a cell is rewritten when its glyph differs or a channel is more than AnsiRgbTolerance away;
 //                QuadrantMinContrast (0..255) keeps a cell one colour while its sub-cells lie that close to their mean, so that TAA's +-1
 //                flicker does not flip glyphs in a resting picture (INTEGRATION.md section 8.5).
+//   SixelGraphics - with DeviceAnsiStream: the frame's bytes are a DEC sixel stream (ycge_render_frame_sixel) of every hi-res sample the frame
+//                traced - fbW * superSample by 2 * fbH * superSample pixels in the 216 colours of a 6 x 6 x 6 cube, SixelDither an ordered
+//                4 x 4 dither - with its top left corner at the framebuffer's viewport cell.  Any superSample; synchronous (no FrameLate), no
+//                delta form, and the other framebuffers are not composed into the picture: the host writes its text cells behind the image.
+//                The stream buffer is pageable memory of the bound's size (INTEGRATION.md section 8.6).
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -70,6 +75,8 @@ public sealed class HipRaytraceOptions
     public int AnsiRgbTolerance = 0;
     public bool QuadrantGlyphs = false;                       // DeviceAnsiStream: quadrant block glyphs, 2 x 2 sub-cells a cell (superSample even, no FrameLate)
     public int QuadrantMinContrast = 0;                       // ... a cell stays one colour while its sub-cell bytes lie this close to their mean (0..255)
+    public bool SixelGraphics = false;                        // DeviceAnsiStream: the frame as a sixel stream, a pixel a hi-res sample (any superSample, no FrameLate, no delta)
+    public bool SixelDither = false;                          // ... with the ordered 4 x 4 dither of the quantiser
     public HipGeneratedWorld GeneratedWorld;                  // chunks that come from the generator are made on the device (ycge_scene_generate_grids)
 }
 
@@ -174,6 +181,8 @@ public partial class RaytraceEntity
         private readonly int ansiTolerance;
         private readonly bool ansiQuad;             // QuadrantGlyphs: the quadrant-glyph forms of the two calls
         private readonly int ansiMinContrast;
+        private readonly bool sixel, sixelDither;   // SixelGraphics: ycge_render_frame_sixel in place of every stream form
+        private bool sixelBufOwned;                 // ... ansiBuf is pageable memory of this wrapper (Marshal), not the library's page-locked memory
         private bool inFlight;                      // FrameLate: a frame queued by the last TryFlipAndBlit has not been waited for yet
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
         private ulong objectsSignature;
@@ -203,6 +212,8 @@ public partial class RaytraceEntity
             if (ansiQuad && (ss & 1) != 0) throw new ArgumentException("QuadrantGlyphs needs an even superSample");
             if (ansiQuad && options.FrameLate) throw new ArgumentException("QuadrantGlyphs has no FrameLate form");
             ansiRgb |= ansiQuad;                    // (the quadrant streams are 24-bit ones: their bound is the 24-bit bound)
+            sixel = ansi != null && options.SixelGraphics; sixelDither = sixel && options.SixelDither;
+            if (sixel && (options.FrameLate || options.DeviceAnsiDelta || options.QuadrantGlyphs)) throw new ArgumentException("SixelGraphics has no FrameLate, delta or quadrant form");
             frameLate = options != null && options.FrameLate && cfg.NDevices <= 1;      // (frames in flight are the single-device form)
             deviceColors = options != null && options.DeviceChexelColors;
             generated = options?.GeneratedWorld;
@@ -255,6 +266,7 @@ public partial class RaytraceEntity
         {
             int cw = ansi.consoleWidth, ch = ansi.consoleHeight;
             UIntPtr bound;
+            if (sixel) { RenderSixel(fb); return; }
             if (ansiRgb) Ycge.Check(ctx, Ycge.ycge_ansi_rgb_stream_bound(cw, ch, out bound));
             else Ycge.Check(ctx, Ycge.ycge_ansi_stream_bound(cw, ch, out bound));
             if (frameLate)
@@ -265,7 +277,7 @@ public partial class RaytraceEntity
             }
             if ((ulong)bound > ansiCap)
             {
-                if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; ansiCap = ansiLen = 0; }
+                FreeAnsiBuf();
                 Ycge.Check(ctx, Ycge.ycge_alloc_host_buffer(bound, out IntPtr p));
                 ansiBuf = (byte*)p; ansiCap = (ulong)bound;
             }
@@ -291,6 +303,29 @@ public partial class RaytraceEntity
                                                             ansiBuf, (UIntPtr)ansiCap, &len, null, null));
             ansiLen = (ulong)len;
             ansi.ClearPending = false;
+        }
+
+        // SixelGraphics: one frame as the sixel stream of its hi-res samples at the framebuffer's viewport.  The bound is large against the streams
+        // (74 MB for 1920 x 1072 pixels, streams of a few hundred KB): the buffer is pageable, so only the pages a stream reaches are ever backed
+        private void RenderSixel(Framebuffer fb)
+        {
+            Ycge.Check(ctx, Ycge.ycge_sixel_stream_bound(fbW * ss, 2 * fbH * ss, out UIntPtr bound));
+            if ((ulong)bound > ansiCap)
+            {
+                FreeAnsiBuf();
+                ansiBuf = (byte*)System.Runtime.InteropServices.Marshal.AllocHGlobal(checked((IntPtr)(long)(ulong)bound)); sixelBufOwned = true; ansiCap = (ulong)bound;
+            }
+            UIntPtr len;
+            Ycge.Check(ctx, Ycge.ycge_render_frame_sixel(ctx, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, sixelDither ? 1 : 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null));
+            ansiLen = (ulong)len;
+            ansi.ClearPending = false;
+        }
+
+        private void FreeAnsiBuf()
+        {
+            if (ansiBuf == null) return;
+            if (sixelBufOwned) System.Runtime.InteropServices.Marshal.FreeHGlobal((IntPtr)ansiBuf); else Ycge.ycge_free_host_buffer((IntPtr)ansiBuf);
+            ansiBuf = null; sixelBufOwned = false; ansiCap = ansiLen = 0;
         }
 
         /// <summary>What the devices' tiles really travel by (the library falls back to the peer push where librccl.so is missing).</summary>
@@ -621,7 +656,7 @@ public partial class RaytraceEntity
             if (sdr != null) { Ycge.ycge_free_host_buffer((IntPtr)sdr); sdr = null; }
             if (sdrLate != null) { Ycge.ycge_free_host_buffer((IntPtr)sdrLate); sdrLate = null; }
             FreeColor16();
-            if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; }
+            FreeAnsiBuf();
             if (ansiBufLate != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBufLate); ansiBufLate = null; }
             if (ansiRec != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiRec); ansiRec = null; }
             if (ansiRecLate != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiRecLate); ansiRecLate = null; }

@@ -55,6 +55,7 @@ public partial class RaytraceEntity
             ansiQuad = ansi != null && options.QuadrantGlyphs; ansiMinContrast = options != null ? options.QuadrantMinContrast : 0;
             if (ansiQuad && (ss & 1) != 0) throw new ArgumentException("QuadrantGlyphs needs an even superSample");
             ansiRgb |= ansiQuad;                    // (the quadrant streams are 24-bit ones: their bound is the 24-bit bound)
+            // (SixelGraphics has no Video mode form - the blit keeps no per-sample plane: a video frame of such a host goes out as a cell stream)
             deviceColors = options != null && options.DeviceChexelColors;
             if (sharedContext != IntPtr.Zero)
             {

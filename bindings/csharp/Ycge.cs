@@ -379,6 +379,15 @@ namespace ConsoleGame.RayTracing.Native
                                                                                   int viewportX, int viewportY, int defaultFg16, int defaultBg16, int clearScreen, int mergeGap,
                                                                                   int tolerance, int keyframe, int minContrast, byte* outStream, UIntPtr capacity,
                                                                                   UIntPtr* outLen, uint* outInfo, float* outTopBottomSdr);
+        // sixel frames (after ABI 10, found by symbol lookup): the picture is the hi-res buffer, fbW * superSample by 2 * fbH * superSample pixels.  The
+        // planes (RGBA8 and the registers of the 6 x 6 x 6 cube, any of them null), the stream at a viewport cell, its bound, and the host encoder of a
+        // register plane (no context); dither 0 or 1
+        [DllImport(Lib)] public static extern int ycge_sixel_stream_bound(int pxW, int pxH, out UIntPtr bytes);
+        [DllImport(Lib)] public static extern int ycge_render_frame_pixels(IntPtr ctx, float* outTopBottomSdr, byte* outRgba, byte* outIndex, int dither, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_render_frame_sixel(IntPtr ctx, int viewportX, int viewportY, int clearScreen, int dither, byte* outStream,
+                                                                          UIntPtr capacity, UIntPtr* outLen, float* outTopBottomSdr, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_sixel_encode_host(byte* index, int pxW, int pxH, int viewportX, int viewportY, int clearScreen, byte* outStream,
+                                                                         UIntPtr capacity, UIntPtr* outLen);
         // the console's other framebuffers for every stream call above (found by symbol lookup, ABI stays 10); YConsoleLayer, YChexel and
         // HipConsoleLayers: bindings/csharp/YcgeConsole.cs
         [DllImport(Lib)] public static extern int ycge_console_set_layers(IntPtr ctx, YConsoleLayer* layers, int n, int raytraceAt);

@@ -956,6 +956,54 @@ int ycge_render_frame_ansi_quad_delta(ycge_ctx *ctx, int32_t console_w, int32_t 
                                       int32_t default_bg16, int32_t clear_screen, int32_t merge_gap, int32_t tolerance, int32_t keyframe,
                                       int32_t min_contrast, uint8_t *out_stream, size_t capacity, size_t *out_len,
                                       uint32_t *out_info /* 4 words or NULL */, float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+/* --- Sixel frames: the traced picture per pixel, as a DEC sixel stream built on the device.  Every presenter above ends in a character cell:
+ * '▀' shows two samples a cell, a quadrant glyph four in two colours, and the box average of the tone map removes the rest of what a frame
+ * at super_sample > 1 traced.  A sixel stream (xterm, foot, WezTerm, Windows Terminal, iTerm2, Konsole, mlterm, tmux 3.4) shows every sample.
+ * The reference has no such presenter, so these rules define the result.  Added after ABI 10 without changing it: YCGE_ABI_VERSION stays 10,
+ * no existing struct or prototype changes; a host detects the exports by symbol lookup.
+ *   Geometry.  The picture is the hi-res buffer: W = fbW ss columns by H = 2 fbH ss rows, row 0 on top.  Any super_sample >= 1.
+ *   Pixel colour.  Pixel (x, y) is the frame's MapPixel of sample (x, y) of the denoised buffer (YCGE_BUF_DENOISED) - no box sum - with the
+ *   frame's effective exposure (stats.exposure), gamma 2.2, saturation 2.0, vibrance 0.  Its sRGB8 bytes are Clamp01 / LinearToSrgb8 of the three
+ *   channels, from the threshold tables ycge_render_frame_chexels uses: at super_sample 1 the RGBA plane is that call's out_rgba plane, byte
+ *   for byte.  The ordinary tone map still runs: the SDR array is ycge_render_frame's, bit for bit, and so is the frame state.
+ *   Palette.  216 registers, a 6 x 6 x 6 cube: register i = 36 r + 6 g + b with levels r, g, b in 0..5 is defined in the stream as
+ *   #i;2;20r;20g;20b (sixel percentages) and stands for the bytes 51 r, 51 g, 51 b.
+ *   Quantiser.  Integer arithmetic on each byte v.  dither = 0: level = (v + 25) / 51, the nearest cube level.  dither = 1:
+ *   level = (32 v + 102 D[y & 3][x & 3] + 51) / 1632 with the 4 x 4 Bayer matrix D = {0,8,2,10; 12,4,14,6; 3,11,1,9; 15,7,13,5} indexed by the
+ *   hi-res pixel.  Both give 0..5 for every byte.
+ *   Stream.  In this order: ESC[2J only if clear_screen is non-zero; ESC[<viewport_y + 1>;<viewport_x + 1>H; ESC P q; "1;1;<W>;<H>; the 216
+ *   register definitions, ascending (3130 bytes, always the same); the bands; ESC \.  Band k holds rows 6 k .. 6 k + 5; rows at or past H
+ *   contribute no bits.  Inside a band the colours present in it come in ascending register order.  Colour c gives one line: #<c>, then the
+ *   line's sixels - sixel x has bit r set where pixel (x, 6 k + r) is c.  Every column after the last non-zero sixel is omitted; the rest is
+ *   cut into maximal runs of equal sixels; a run of n >= 4 is written !<n> and the character 63 + bits, a run of n <= 3 the character n
+ *   times; leading empty columns are runs of '?'.  Between two lines of a band stands '$', behind every band but the last '-'.
+ *   Known answer.  The 5 x 7 picture with the register rows {0 0 0 0 215} {0 7 7 7 7} {0 7 7 7 7} {0 0 0 0 0} x 3 {43 43 43 43 0} at viewport
+ *   (2, 1) with clear has the body #0~xxxw$#7?!4E$#215!4?@-#0!4?@$#43!4@ behind the register definitions, then ESC \: 3190 bytes in all.
+ *   Bound.  ycge_sixel_stream_bound(W, H) = 3200 + ceil(H / 6) min(216, 6 W) (W + 5): a line is at most #ddd, W characters and a separator.
+ *   It refuses (YCGE_ERR_INVALID_ARG) a geometry whose bound does not fit 32 bits.  capacity below the bound is refused before any device
+ *   work, as the ANSI calls do; exactly *out_len bytes are written, no byte at or past them is touched.  The bound is generous - 74 MB for
+ *   1920 x 1072 pixels against streams of a few hundred KB - and a pageable buffer of that size costs nothing it does not use: allocate it
+ *   once, untouched pages are never backed.  More than 6 * 65535 rows are refused.
+ *   ycge_render_frame_pixels: the planes.  out_rgba W x H RGBA8 (alpha 255), out_index W x H registers; any subset of the three destinations
+ *   may be NULL, not all; pageable or page-locked as the chexel call handles them.  It leaves the ANSI delta state alone.
+ *   ycge_render_frame_sixel: the stream of those registers.  The picture paints over the terminal's cells: after a successful call the
+ *   context's ANSI delta state is invalid and the next _delta call of any family is a keyframe.  Layers set with ycge_console_set_layers
+ *   are not composed into the picture: a host writes its text cells behind the image.
+ *   ycge_sixel_encode_host: the same stream in plain C++ from a register plane (values 0..215), no context and no device - the yardstick
+ *   of the kernels, and with YCGE_SIXEL_HOST=1 in the environment the encoder ycge_render_frame_sixel runs on the plane read back.
+ *   Refused before any device work, nothing written, frame and delta state untouched, the message naming the value (YCGE_ERR_INVALID_ARG):
+ *   a NULL stream or length; capacity below the bound; a negative viewport_x or viewport_y; dither outside 0..1; all destinations NULL (the
+ *   planes call); whatever ycge_render_frame_chexels refuses - peer contexts, RCCL with lean slabs.
+ *   Not offered: Video mode (k_video_blit keeps no per-sample plane); frames in flight; partial or delta images; layers composed into the
+ *   picture; a grey ramp or an adaptive palette; pixel replication to scale the image; the kitty graphics protocol (the out_rgba plane of
+ *   ycge_render_frame_pixels is what a host would base64 for it). */
+int ycge_sixel_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes);
+int ycge_render_frame_pixels(ycge_ctx *ctx, float *out_top_bottom_sdr /* may be NULL */, uint8_t *out_rgba /* W x H RGBA8, may be NULL */,
+                             uint8_t *out_index /* W*H registers, may be NULL */, int32_t dither, ycge_frame_stats *stats);
+int ycge_render_frame_sixel(ycge_ctx *ctx, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t dither, uint8_t *out_stream,
+                            size_t capacity, size_t *out_len, float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+int ycge_sixel_encode_host(const uint8_t *index, int32_t px_w, int32_t px_h, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen,
+                           uint8_t *out_stream, size_t capacity, size_t *out_len);
 /* --- ANSI streams with frames in flight: the four frame forms above - ycge_render_frame_ansi, _ansi_delta, _ansi_rgb, _ansi_rgb_delta - queued
  * as ycge_render_frame_async_sdr queues a frame.  The synchronous calls read the stream's length on the host and copy exactly that many
  * bytes, which takes a synchronisation inside the call; here a kernel behind the stream's kernels (k_ansi_deliver, csrc/ycge_ansi_flight.hip)

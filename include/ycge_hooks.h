@@ -161,6 +161,14 @@ int ycge_test_bodies_tick_host(ycge_camera_body *bodies, const ycge_body_shape *
                                ycge_body_result *results, ycge_camera_tick_info *info, ycge_camera_hit_fn hit, void *user, int32_t windowed,
                                char *msg, size_t msg_bytes);
 
+/* the sixel presenter (csrc/ycge_sixel.cpp; tests/test_gpu_sixel.py).  ycge_test_pixels: k_sixel_pixels alone on a caller's hi-res buffer
+ * (2 fbH ss rows of fbW ss samples, 3 f32 each) under `exposure`, whatever the context's framebuffer is: out_rgba W*H RGBA8, out_index W*H
+ * registers, either may be NULL.  ycge_test_sixel_stream: the encoder's kernels alone on a caller's register plane of any W x H whose bound
+ * fits; a value of 216 or more is refused on the host.  Neither touches frame, sixel or delta state */
+int ycge_test_pixels(ycge_ctx *c, const float *hdr, int32_t fbW, int32_t fbH, int32_t ss, float exposure, int32_t dither, uint8_t *out_rgba, uint8_t *out_index);
+int ycge_test_sixel_stream(ycge_ctx *c, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity,
+                           size_t *out_len);
+
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */
 int ycge_debug_device_bvh(const float *bounds, const float *centroids, int32_t n, void *nodes_out, int32_t *leaf_out, uint32_t *result_out, void *build_out);   /* k_scene_bvh_build alone */

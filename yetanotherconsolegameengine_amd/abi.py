@@ -394,6 +394,14 @@ _PROTOTYPES = {
     "ycge_video_blit_ansi_quad_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    # the sixel frames: the bound of a W x H picture; the planes (SDR, W x H RGBA8, W x H registers; dither); the stream (viewport, clear, dither);
+    # the host encoder of a register plane (no context)
+    "ycge_sixel_stream_bound": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "ycge_render_frame_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.POINTER(FrameStats)]),
+    "ycge_render_frame_sixel": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_float), C.POINTER(FrameStats)]),
+    "ycge_sixel_encode_host": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
     # (req: C.byref(abi.AnsiAsync); out_result: the address of an abi.AnsiAsyncResult in page-locked memory)
     "ycge_render_frame_async_ansi": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
@@ -503,6 +511,13 @@ QUADRANT_HOOK_PROTOTYPES = {
                                    [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "ycge_test_ansi_quad_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)] + [C.c_int32] * 11 +
                                   [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)]),
+}
+# test hooks of the sixel frames (csrc/ycge_sixel.cpp), bound where they are used (tests/test_gpu_sixel.py): the pixel stage alone on a hi-res
+# buffer (fbW, fbH, ss, exposure, dither; RGBA and register planes, either None), the encoder alone on a register plane (W, H, vx, vy, clear)
+SIXEL_HOOK_PROTOTYPES = {
+    "ycge_test_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ycge_test_sixel_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
 }
 # test hook of the delivery of a stream with frames in flight (csrc/ycge_ansi.cpp), bound where it is used (tests/test_gpu_ansi_flight.py): src,
 # n_src, length, capacity, keyframe, counts (3 uint32), groups, out_stream, out_result (an abi.AnsiAsyncResult in page-locked memory)

@@ -108,6 +108,7 @@ int ensure_tables(ycge_ctx *c, ChexelState &X)
 
 int chexel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked, const float *d_sdr, bool second)
 {
+    if (asked.pixels) return sixel_encode(c, stream, asked);                             // (the sixel presenter: ycge_sixel.cpp)
     ChexelState *X = &c->chexels;
     uint8_t *const *dst = asked.chexels;
     const bool ansi = asked.ansi != nullptr;                                             // (ycge_render_frame_ansi: the pairs stay on the device)
@@ -173,6 +174,7 @@ int chexel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, bool se
 {
     ChexelState *X = &c->chexels;
     uint8_t *const *dst = out.chexels;
+    if (out.pixels) return sixel_read_back(c, stream, out);
     if (out.quad) return quadrants_read_back(c, stream, out, second);
     if (!dst[0] && !dst[1] && !dst[2] && !out.ansi) return YCGE_OK;
     const ChexelLayout L((size_t)c->fbW * c->fbH);
@@ -236,6 +238,50 @@ try {
     FrameOutputs out(out_top_bottom_sdr);
     if (out_quad_sdr || out_glyphs || out_rgba) out.quad = &q;          // (the SDR alone: ycge_render_frame's frame)
     return render_frame_sync(c, &out, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+// The sixel presenter (the contract: include/ycge.h; the bodies: ycge_sixel.cpp): the bound, the host encoder, the planes of a frame's
+// hi-res samples, their sixel stream, and the two test hooks - the pixel stage and the encoder's kernels alone
+int ycge_sixel_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes)
+try {
+    return sixel_stream_bound(px_w, px_h, bytes);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+int ycge_sixel_encode_host(const uint8_t *index, int32_t px_w, int32_t px_h, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, uint8_t *out_stream,
+                           size_t capacity, size_t *out_len)
+try {
+    return sixel_encode_host(index, px_w, px_h, viewport_x, viewport_y, clear_screen, out_stream, capacity, out_len);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+int ycge_render_frame_pixels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_rgba, uint8_t *out_index, int32_t dither, ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_frame_pixels(c, out_top_bottom_sdr, out_rgba, out_index, dither, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_render_frame_sixel(ycge_ctx *c, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t dither, uint8_t *out_stream, size_t capacity,
+                            size_t *out_len, float *out_top_bottom_sdr, ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_frame_stream(c, viewport_x, viewport_y, clear_screen, dither, out_stream, capacity, out_len, out_top_bottom_sdr, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_test_pixels(ycge_ctx *c, const float *hdr, int32_t fbW, int32_t fbH, int32_t ss, float exposure, int32_t dither, uint8_t *out_rgba, uint8_t *out_index)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_test_pixels(c, hdr, fbW, fbH, ss, exposure, dither, out_rgba, out_index);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_test_sixel_stream(ycge_ctx *c, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity, size_t *out_len)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_test_stream(c, index, W, H, vx, vy, clear, out, capacity, out_len);
 }
 catch (...) { return ycge_host::abi_catch(c); }
 

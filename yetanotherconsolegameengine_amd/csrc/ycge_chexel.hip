@@ -15,6 +15,8 @@
 #include <cfloat>
 #include <cstdint>
 
+#include "ycge_srgb8.hip.h"
+
 namespace {
 
 constexpr int kChexelBlock = 256;
@@ -26,8 +28,8 @@ __constant__ float c_palette16[16][3] = {
     {0.50f, 0.50f, 0.50f}, {0.00f, 0.00f, 1.00f}, {0.00f, 1.00f, 0.00f}, {0.00f, 1.00f, 1.00f},
     {1.00f, 0.00f, 0.00f}, {1.00f, 0.00f, 1.00f}, {1.00f, 1.00f, 0.00f}, {1.00f, 1.00f, 1.00f}};
 
-// Clamp01 (Chexel.cs:92-98): compare in double, NaN and -0.0 pass unchanged; the result is a binary32 again (Vec3's fields)
-__device__ __forceinline__ float clamp01(float x) { return (double)x < 0.0 ? 0.0f : ((double)x > 1.0 ? 1.0f : x); }
+using ycge_chexel::clamp01;          // Clamp01 (Chexel.cs:92-98) and the threshold search: ycge_srgb8.hip.h
+using ycge_chexel::srgb8;
 
 // NearestConsoleColorFrom (Chexel.cs:70-89) on clamped channels: binary32 distances left to right, strict <, ties to the lower index
 __device__ __forceinline__ uint32_t color16(float r, float g, float b)
@@ -41,16 +43,6 @@ __device__ __forceinline__ uint32_t color16(float r, float g, float b)
         if (d < best_d) { best_d = d; best = (uint32_t)i; }
     }
     return best;
-}
-
-// the number of thresholds <= x: a branchless search over the 255 sorted entries (entry 255 is never read)
-template <class T>
-__device__ __forceinline__ int srgb8(const T *t, T x)
-{
-    int pos = 0;
-#pragma unroll
-    for (int s = 128; s >= 1; s >>= 1) pos += t[pos + s - 1] <= x ? s : 0;
-    return pos;
 }
 
 // ToCubeLevelSrgb (ANSITerminalRenderer.cs:276-284)

@@ -115,6 +115,10 @@ int ycge_launch_tonemap_quadrants(const float *hdr, int hiW, int fbW, int fbH, i
                                   float *out, hipStream_t stream);
 int ycge_launch_quadrant_fit(const float *quad, int fbW, int fbH, const uint8_t *tables, int min_contrast, uint16_t *glyphs, uint8_t *rgba, int compute_units,
                              hipStream_t stream);
+int ycge_launch_sixel_pixels(const float *hdr, int W, int H, float gamma, float saturation, float vibrance, const void *state, const uint8_t *tables, int dither,
+                             uint8_t *rgba, uint8_t *index, int compute_units, hipStream_t stream);
+int ycge_launch_sixel_encode(const uint8_t *index, int W, int H, uint32_t *last1, uint32_t *lines, uint32_t *line_bytes, uint32_t max_lines, uint32_t *meta,
+                             const uint8_t *header, uint32_t header_bytes, uint8_t *out, uint32_t cap, unsigned long long *res, int compute_units, hipStream_t stream);
 uint32_t ycge_launch_ansi_tiles(uint32_t cells);
 int ycge_launch_ansi_indexed(const ycge_ansi::StreamJob *job, hipStream_t stream);
 int ycge_launch_ansi_rgb(const ycge_ansi::StreamJob *job, hipStream_t stream);
@@ -507,6 +511,10 @@ struct FrameOutputs {
     struct Quadrants { float *sdr; uint16_t *glyphs; uint8_t *rgba; int32_t min_contrast; };
     const Quadrants *quad = nullptr;
     bool quad_colours_ready = false;                   // a video blit: k_video_blit_quadrants wrote ChexelState::quad_sdr already - the encode is the fit alone
+    // ycge_render_frame_pixels / _sixel (ycge_sixel.cpp): the caller's per-pixel planes (W x H RGBA words, W x H registers), any of them NULL,
+    // and with `stream` set the sixel stream of the registers at the viewport - its bytes are delivered behind the frame's synchronisation
+    struct Pixels { uint8_t *rgba; uint8_t *index; int32_t dither; bool stream; int32_t vx, vy; bool clear; };
+    const Pixels *pixels = nullptr;
     const AnsiRequest *ansi = nullptr;                 // the ANSI stream asked for (its encode keeps the pairs - 24-bit colour: the RGBA plane - on the device only)
     bool keyframe = true;                              // ... runs the full stream's kernels (a _delta call: what its DeltaCall decided)
     AnsiPlan plan;                                     // ... and its plan (DeltaCall's)
@@ -564,6 +572,17 @@ struct ChexelState {
     hipStream_t flight_stream = nullptr;
     bool flight_pending = false;
     PinnedBuf flight_sticky;
+};
+// what the sixel calls of one context hold (ycge_sixel.cpp; kernels: ycge_sixel.hip): made by the first call, grow-only
+struct SixelState {
+    DevBuf<uint8_t> rgba, index;                       // k_sixel_pixels' planes of the frame at hand
+    DevBuf<uint32_t> last1, lines, line_bytes, meta;   // the encoder's per-(band, colour) widths, its line list, the lines' bytes then offsets, the line count
+    DevBuf<uint8_t> header, stream;                    // the stream's parts 1 to 5 as the host built them, and the stream (its bound)
+    std::array<int32_t, 5> header_key{{0, 0, 0, 0, 0}}; // {W, H, vx, vy, clear} the header on the device was built for (W = 0: none)
+    uint32_t header_bytes = 0;
+    DevBuf<unsigned long long> res;                    // the stream's length as k_sixel_scan wrote it ...
+    PinnedBuf res_host;                                // ... and the page-locked word it is copied to
+    PinnedBuf stage;                                   // page-locked staging of pageable destinations
 };
 // what the video blits of one context hold (ycge_video.cpp): made by the first blit, grow-only; nothing a ray-traced frame reads
 struct VideoState {
@@ -879,6 +898,7 @@ struct ycge_ctx {
     // device chexel colours (ycge_render_frame_chexels / _async_chexels, ycge_chexel.cpp): the encoded buffers per post parity, the
     // threshold tables, the staging of pageable destinations
     ChexelState chexels;
+    SixelState sixel;            // the sixel presenter (ycge_render_frame_pixels / _sixel, ycge_sixel.cpp)
     VideoState video;            // Video mode (ycge_video_blit, ycge_video.cpp)
     ObjState obj;                // the parsed OBJ (ycge_obj_parse, ycge_obj.cpp)
     WorldStore world_store;      // the resident VG01 world (ycge_world_store_load, ycge_world_store.cpp)
@@ -1059,6 +1079,16 @@ int render_frame_in_flight(ycge_ctx *c, FrameOutputs *out);                     
 void halo_layout(int hiW, int hiH, int rank, int world, std::vector<int64_t> &send_counts, std::vector<int64_t> &recv_counts, std::vector<uint32_t> &send_px, std::vector<uint32_t> &recv_px);
 int check_quadrant_call(ycge_ctx *c, const char *fn, int32_t min_contrast);              // ycge_chexel.cpp: what every quadrant call refuses - an odd super_sample, min_contrast outside 0..255
 int ensure_tables(ycge_ctx *c, ChexelState &X);                                           // ycge_chexel.cpp: LinearToSrgb8's thresholds on the device, once
+int sixel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked);            // ycge_sixel.cpp: asked.pixels' kernels behind the tonemap (chexel_encode hands them on) ...
+int sixel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out);                 // ... and the copies of its planes and of the stream's length (chexel_read_back)
+// ... the bodies of ycge_sixel_stream_bound, ycge_sixel_encode_host (no context), ycge_render_frame_pixels, ycge_render_frame_sixel and the two hooks
+int sixel_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes);
+int sixel_encode_host(const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity, size_t *out_len);
+int sixel_frame_pixels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_rgba, uint8_t *out_index, int32_t dither, ycge_frame_stats *st);
+int sixel_frame_stream(ycge_ctx *c, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t dither, uint8_t *out_stream, size_t capacity,
+                       size_t *out_len, float *out_top_bottom_sdr, ycge_frame_stats *st);
+int sixel_test_pixels(ycge_ctx *c, const float *hdr, int32_t fbW, int32_t fbH, int32_t ss, float exposure, int32_t dither, uint8_t *out_rgba, uint8_t *out_index);
+int sixel_test_stream(ycge_ctx *c, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity, size_t *out_len);
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_plane);   // ycge_ansi.cpp: out.ansi's stream kernels behind the encode on the frame's plane (where out.plan puts it), and the length's copy
 // ycge_video.cpp: Video mode.  The refusals of a source frame; upload + k_video_blit on `stream` for a geometry (*d_sdr: its SDR array);
 // the SDR read-back (a pageable array: staged as run_post does it); the test hooks' bodies

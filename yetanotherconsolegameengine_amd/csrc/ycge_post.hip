@@ -15,21 +15,13 @@
 #include <hip/hip_runtime.h>
 
 #include "ycge_rt.hip.h"
+#include "ycge_tonemap.hip.h"          // ToneState, map_pixel
 
 namespace ycge {
 
 struct AtrousParams {
     int32_t w, h, step;
     float c_phi, n_phi, z_phi, a_phi;      // already max(1e-6f, phi), :693-696
-};
-
-struct ToneState {                          // ToneMapper fields that change (ToneMapper.cs:13,17)
-    float ae_exposure;
-    float effective;
-    uint32_t count;                         // diagnostics: chunks k_exposure_sum added one by one this frame (0 from the serial form)
-    uint32_t pad;
-    float log_sum;                          // the frame's logSum and cnt (ToneMapper.cs:63-77) as the sum kernels left them: read by the
-    uint32_t samples;                       // test hooks only (ycge_test_post_stage / ycge_test_exposure), nothing on the device reads them
 };
 
 __device__ __forceinline__ F3 ld3(const float *p, size_t i) { return f3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
@@ -1057,37 +1049,7 @@ __global__ __launch_bounds__(1024) void k_exposure_sum(const float *__restrict__
     state->samples = s_total_cnt;
 }
 
-// ToneMapper.ToneMapAndEncode + ApplySaturation, ToneMapper.cs:204-260
-__device__ __forceinline__ float aces_film(float x)
-{
-    const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
-    const float num = x * (a * x + b);
-    const float den = x * (c * x + d) + e;
-    float y = den > 0.0f ? num / den : 0.0f;
-    if (y < 0.0f) y = 0.0f;
-    if (y > 1.0f) y = 1.0f;
-    return y;
-}
-__device__ __forceinline__ F3 map_pixel(F3 hdr, float exposure, float gamma, float saturation, float vibrance)
-{
-    float r = cs_max(0.0f, hdr.x) * exposure;
-    float g = cs_max(0.0f, hdr.y) * exposure;
-    float b = cs_max(0.0f, hdr.z) * exposure;
-    r = aces_film(r); g = aces_film(g); b = aces_film(b);
-    const float inv_gamma = 1.0f / cs_max(0.1f, gamma);
-    const float sr = m_pow(clamp01(r), inv_gamma);
-    const float sg = m_pow(clamp01(g), inv_gamma);
-    const float sb = m_pow(clamp01(b), inv_gamma);
-    r = clamp01(sr); g = clamp01(sg); b = clamp01(sb);
-    const float y = 0.2126f * r + 0.7152f * g + 0.0722f * b;
-    const float maxc = cs_max(r, cs_max(g, b));
-    const float minc = cs_min(r, cs_min(g, b));
-    const float chroma = maxc - minc;
-    const float vib = 1.0f + vibrance * (1.0f - chroma);
-    const float f = saturation * vib;
-    const float rr = y + (r - y) * f, gg = y + (g - y) * f, bb = y + (b - y) * f;
-    return f3(clamp01(rr), clamp01(gg), clamp01(bb));
-}
+// (ToneMapper.MapPixel, ToneMapper.cs:204-260: map_pixel of ycge_tonemap.hip.h)
 
 // step 8, :229-264: per chexel the ss x ss box average of its top and bottom half-cell, then MapPixel
 __global__ __launch_bounds__(256) void k_tonemap_downsample(const float *__restrict__ hdr, int hiW, int fbW, int fbH, int ss, float gamma,

@@ -1,0 +1,348 @@
+// ycge_sixel.cpp - the sixel presenter (ycge_render_frame_pixels, ycge_render_frame_sixel, ycge_sixel_stream_bound, ycge_sixel_encode_host;
+// kernels: ycge_sixel.hip; the contract: include/ycge.h).
+//
+// A frame of these calls is ycge_render_frame's with the post stage, plus k_sixel_pixels behind the tonemap on the same stream - every
+// hi-res sample of the denoised buffer mapped, encoded to sRGB8 and quantised to a register of the 6 x 6 x 6 cube - and for a stream the
+// encoder's launches on that register plane, then the copies of what the caller asked for.  What the caller asked for is the entry point's
+// FrameOutputs::Pixels: chexel_encode and chexel_read_back hand a frame that names it to sixel_encode and sixel_read_back below, and a frame
+// that names none issues no launch or copy of it.  The stream's parts 1 to 5 depend on the geometry and the arguments alone: the host
+// builds them (stream_header) and the context keeps them on the device until another geometry or viewport asks for others.
+//
+// ycge_sixel_encode_host is the same stream in plain C++ from a register plane: the yardstick of the kernels on a machine without a
+// device, and under YCGE_SIXEL_HOST=1 the encoder of ycge_render_frame_sixel and of the stream hook, on the plane read back.
+#include "ycge_ctx.h"
+
+#include <cstdlib>
+#include <string>
+
+namespace {
+
+constexpr unsigned long long kOffsetLimit = 0xffffffffull;          // the kernels' offsets are 32-bit
+constexpr int32_t kMaxRows = 6 * 65535;                              // a band is a row of k_sixel_presence's grid
+
+// 3200 + ceil(H / 6) * min(216, 6 W) * (W + 5); false where W or H is not positive or the bound does not fit 32 bits
+bool stream_bound(int64_t W, int64_t H, unsigned long long &bound)
+{
+    if (W <= 0 || H <= 0) return false;
+    const unsigned __int128 bands = (unsigned __int128)((H + 5) / 6), colours = (unsigned __int128)(6 * W < 216 ? 6 * W : 216);
+    const unsigned __int128 b = 3200 + bands * colours * (unsigned __int128)(W + 5);
+    if (b > kOffsetLimit) return false;
+    bound = (unsigned long long)b;
+    return true;
+}
+
+// parts 1 to 5 of the stream
+std::string stream_header(int32_t W, int32_t H, int32_t vx, int32_t vy, bool clear)
+{
+    std::string s;
+    s.reserve(3200);
+    if (clear) s += "\x1b[2J";
+    s += "\x1b[" + std::to_string((int64_t)vy + 1) + ";" + std::to_string((int64_t)vx + 1) + "H";
+    s += "\x1bPq";
+    s += "\"1;1;" + std::to_string(W) + ";" + std::to_string(H);
+    for (int i = 0; i < 216; i++)
+        s += "#" + std::to_string(i) + ";2;" + std::to_string(20 * (i / 36)) + ";" + std::to_string(20 * (i / 6 % 6)) + ";" + std::to_string(20 * (i % 6));
+    return s;
+}
+
+// the bands and the trailer behind the header, from a plane of values below 216
+void encode_bands(const uint8_t *index, int32_t W, int32_t H, std::string &s)
+{
+    const int32_t bands = (H + 5) / 6;
+    std::vector<uint8_t> six((size_t)W);
+    for (int32_t k = 0; k < bands; k++) {
+        const int32_t rows = H - 6 * k < 6 ? H - 6 * k : 6;
+        const uint8_t *row0 = index + (size_t)6 * k * W;
+        bool present[216] = {};
+        for (int32_t r = 0; r < rows; r++)
+            for (int32_t x = 0; x < W; x++) present[row0[(size_t)r * W + x]] = true;
+        bool first = true;
+        for (int c = 0; c < 216; c++) {
+            if (!present[c]) continue;
+            if (!first) s += '$';
+            first = false;
+            s += '#'; s += std::to_string(c);
+            int32_t width = 0;
+            for (int32_t x = 0; x < W; x++) {
+                uint8_t b = 0;
+                for (int32_t r = 0; r < rows; r++) b |= (uint8_t)((row0[(size_t)r * W + x] == c) << r);
+                six[x] = b;
+                if (b) width = x + 1;
+            }
+            for (int32_t x = 0; x < width;) {
+                int32_t n = 1;
+                while (x + n < width && six[x + n] == six[x]) n++;
+                const char ch = (char)(63 + six[x]);
+                if (n >= 4) { s += '!'; s += std::to_string(n); s += ch; }
+                else s.append((size_t)n, ch);
+                x += n;
+            }
+        }
+        if (k + 1 < bands) s += '-';
+    }
+    s += "\x1b\\";
+}
+
+bool host_encoder_asked()
+{
+    const char *e = std::getenv("YCGE_SIXEL_HOST");
+    return e && e[0] && !(e[0] == '0' && !e[1]);
+}
+
+// the encoder's buffers for a W x H plane, and the header on the device: grown before anything is queued
+int ensure_encoder(ycge_ctx *c, SixelState &S, int32_t W, int32_t H, int32_t vx, int32_t vy, bool clear, unsigned long long bound)
+{
+    const size_t bands = (size_t)(H + 5) / 6, max_lines = bands * (size_t)(6 * (int64_t)W < 216 ? 6 * W : 216);
+    if (S.last1.cap < bands * 216) HIP_TRY(c, S.last1.alloc(bands * 216));
+    if (S.lines.cap < max_lines) HIP_TRY(c, S.lines.alloc(max_lines));
+    if (S.line_bytes.cap < max_lines) HIP_TRY(c, S.line_bytes.alloc(max_lines));
+    if (!S.meta.p) HIP_TRY(c, S.meta.alloc(4));
+    if (!S.res.p) HIP_TRY(c, S.res.alloc(4));
+    if (S.stream.cap < bound) HIP_TRY(c, S.stream.alloc((size_t)bound));
+    HIP_TRY(c, S.res_host.reserve(64));
+    const std::array<int32_t, 5> key{{W, H, vx, vy, clear ? 1 : 0}};
+    if (key != S.header_key || !S.header.p) {
+        const std::string h = stream_header(W, H, vx, vy, clear);
+        if (S.header.cap < h.size()) HIP_TRY(c, S.header.alloc(h.size()));
+        S.header_key = {{0, 0, 0, 0, 0}};
+        HIP_TRY(c, hipMemcpy(S.header.p, h.data(), h.size(), hipMemcpyHostToDevice));
+        S.header_key = key; S.header_bytes = (uint32_t)h.size();
+    }
+    return YCGE_OK;
+}
+
+int launch_encoder(ycge_ctx *c, SixelState &S, const uint8_t *d_index, int32_t W, int32_t H, unsigned long long bound, hipStream_t stream)
+{
+    const size_t bands = (size_t)(H + 5) / 6, max_lines = bands * (size_t)(6 * (int64_t)W < 216 ? 6 * W : 216);
+    const int e = ycge_launch_sixel_encode(d_index, W, H, S.last1.p, S.lines.p, S.line_bytes.p, (uint32_t)max_lines, S.meta.p, S.header.p, S.header_bytes, S.stream.p,
+                                           (uint32_t)bound, S.res.p, c->compute_units, stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "the sixel encoder's launches failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipMemcpyAsync(S.res_host.p, S.res.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    return YCGE_OK;
+}
+
+// behind the stream's synchronisation: the length the device wrote, the bound check, exactly that many bytes into `out` (staged when pageable)
+int deliver(ycge_ctx *c, SixelState &S, const char *fn, unsigned long long bound, uint8_t *out, size_t *out_len)
+{
+    const unsigned long long len = *static_cast<const unsigned long long *>(S.res_host.p);
+    if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
+    uint8_t *target = out;
+    const bool staged = !host_memory_is_page_locked(out, (size_t)len);
+    if (staged) {
+        HIP_TRY(c, S.stage.reserve((size_t)len));
+        target = S.stage.data();
+    }
+    HIP_TRY(c, hipMemcpyAsync(target, S.stream.p, (size_t)len, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (staged) std::memcpy(out, S.stage.p, (size_t)len);
+    *out_len = (size_t)len;
+    return YCGE_OK;
+}
+
+// what both frame calls refuse, before any device work
+int check_pixel_frame(ycge_ctx *c, const char *fn, int32_t dither)
+{
+    if (dither < 0 || dither > 1) return c->fail(YCGE_ERR_INVALID_ARG, "%s: dither %d (0 or 1)", fn, dither);
+    const int rc = check_post_frame(c);
+    if (rc != YCGE_OK) return rc;
+    if (c->hiW != c->fbW * c->ss || c->hiH != 2 * c->fbH * c->ss || (int64_t)c->hiW * c->hiH > (int64_t)INT32_MAX / 2)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: a picture of %d x %d pixels (the hi-res buffer of a %d x %d framebuffer at super_sample %d; at most 2^30 pixels)", fn,
+                       c->hiW, c->hiH, c->fbW, c->fbH, c->ss);
+    return YCGE_OK;
+}
+
+// the planes of the frame at hand and the thresholds, made before the frame is queued
+int ensure_planes(ycge_ctx *c, SixelState &S, bool rgba)
+{
+    const size_t n = (size_t)c->hiW * c->hiH;
+    if (rgba && S.rgba.cap < 4 * n) HIP_TRY(c, S.rgba.alloc(4 * n));
+    if (S.index.cap < n) HIP_TRY(c, S.index.alloc(n));
+    return ensure_tables(c, c->chexels);
+}
+
+} // namespace
+
+namespace ycge_host {
+
+int sixel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked)
+{
+    SixelState &S = c->sixel;
+    const FrameOutputs::Pixels &q = *asked.pixels;
+    const int W = c->hiW, H = c->hiH;
+    if (!S.index.p || S.index.cap < (size_t)W * H || (q.rgba && S.rgba.cap < 4 * (size_t)W * H) || !c->chexels.tables.p)
+        return c->fail(YCGE_ERR_INTERNAL, "sixel_encode: the planes of a %d x %d picture are not on the device", W, H);
+    // k_sixel_pixels on the buffer and exposure state the tonemap in front of this read
+    const int e = ycge_launch_sixel_pixels(c->denoised, W, H, 2.2f, 2.0f, 0.0f, c->tone_state.p, c->chexels.tables.p, q.dither, q.rgba ? S.rgba.p : nullptr, S.index.p,
+                                           c->compute_units, stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_sixel_pixels launch failed: %s", hipGetErrorString((hipError_t)e));
+    return YCGE_OK;
+}
+
+// the planes' copies - pageable destinations staged one behind the other - and for a stream the encoder's launches and the length's copy
+// (YCGE_SIXEL_HOST: the register plane's copy into the staging instead, for the host encoder)
+int sixel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out)
+{
+    SixelState &S = c->sixel;
+    const FrameOutputs::Pixels &q = *out.pixels;
+    const size_t n = (size_t)c->hiW * c->hiH;
+    const bool host_plane = q.stream && host_encoder_asked();
+    void *dst[2] = {q.rgba, q.index};
+    const void *src[2] = {S.rgba.p, S.index.p};
+    const size_t bytes[2] = {4 * n, n}, off[2] = {0, 4 * n};
+    size_t staged = host_plane ? 5 * n + n : 0;                    // (the host encoder's plane: behind both)
+    for (int k = 0; k < 2; k++)
+        if (dst[k] && !host_memory_is_page_locked(dst[k], bytes[k]) && staged < off[k] + bytes[k]) staged = off[k] + bytes[k];
+    HIP_TRY(c, S.stage.reserve(staged));
+    for (int k = 0; k < 2; k++) {
+        if (!dst[k]) continue;
+        void *target = dst[k];
+        if (!host_memory_is_page_locked(dst[k], bytes[k])) target = out.redirect(dst[k], S.stage.data() + off[k], bytes[k]);
+        HIP_TRY(c, hipMemcpyAsync(target, src[k], bytes[k], hipMemcpyDeviceToHost, stream));
+    }
+    if (!q.stream) return YCGE_OK;
+    if (host_plane) { HIP_TRY(c, hipMemcpyAsync(S.stage.data() + 5 * n, S.index.p, n, hipMemcpyDeviceToHost, stream)); return YCGE_OK; }
+    unsigned long long bound = 0;
+    if (!stream_bound(c->hiW, c->hiH, bound)) return c->fail(YCGE_ERR_INTERNAL, "sixel_read_back: no bound for %d x %d pixels", c->hiW, c->hiH);
+    return launch_encoder(c, S, S.index.p, c->hiW, c->hiH, bound, stream);
+}
+
+// ---- the bodies of the exports and hooks (the C-ABI with its exception barrier: ycge_chexel.cpp)
+
+int sixel_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes)
+{
+    unsigned long long b = 0;
+    if (!bytes || !stream_bound(px_w, px_h, b)) return YCGE_ERR_INVALID_ARG;
+    *bytes = (size_t)b;
+    return YCGE_OK;
+}
+
+int sixel_encode_host(const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity, size_t *out_len)
+{
+    unsigned long long bound = 0;
+    if (!index || !out || !out_len || vx < 0 || vy < 0 || !stream_bound(W, H, bound) || capacity < bound) return YCGE_ERR_INVALID_ARG;
+    for (size_t i = 0, n = (size_t)W * H; i < n; i++)
+        if (index[i] >= 216) return YCGE_ERR_INVALID_ARG;
+    std::string s = stream_header(W, H, vx, vy, clear != 0);
+    encode_bands(index, W, H, s);
+    if (s.size() > capacity) return YCGE_ERR_INTERNAL;
+    std::memcpy(out, s.data(), s.size());
+    *out_len = s.size();
+    return YCGE_OK;
+}
+
+int sixel_frame_pixels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_rgba, uint8_t *out_index, int32_t dither, ycge_frame_stats *st)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_render_frame_pixels";
+    if (!out_top_bottom_sdr && !out_rgba && !out_index)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, rgba, index)", fn);
+    int rc = check_pixel_frame(c, fn, dither);
+    if (rc != YCGE_OK) return rc;
+    const FrameOutputs::Pixels q{out_rgba, out_index, dither, false, 0, 0, false};
+    FrameOutputs out(out_top_bottom_sdr);
+    if (out_rgba || out_index) {          // (the SDR alone: ycge_render_frame's frame)
+        out.pixels = &q;
+        rc = join_async(c);
+        if (rc != YCGE_OK) return rc;
+        HIP_TRY(c, hipSetDevice(c->device));
+        rc = ensure_planes(c, c->sixel, out_rgba != nullptr);
+        if (rc != YCGE_OK) return rc;
+    }
+    return render_frame_sync(c, &out, st);
+}
+
+int sixel_frame_stream(ycge_ctx *c, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t dither, uint8_t *out_stream, size_t capacity,
+                            size_t *out_len, float *out_top_bottom_sdr, ycge_frame_stats *st)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_render_frame_sixel";
+    if (!out_stream || !out_len) return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_stream and out_len must not be NULL", fn);
+    if (viewport_x < 0 || viewport_y < 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: viewport (%d, %d) (neither may be negative)", fn, viewport_x, viewport_y);
+    int rc = check_pixel_frame(c, fn, dither);
+    if (rc != YCGE_OK) return rc;
+    unsigned long long bound = 0;
+    if (!stream_bound(c->hiW, c->hiH, bound) || c->hiH > kMaxRows)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: the stream of %d x %d pixels may reach 2^32 bytes (offsets are 32-bit), or has more than %d rows", fn, c->hiW, c->hiH, kMaxRows);
+    if (capacity < bound) return c->fail(YCGE_ERR_INVALID_ARG, "%s: capacity %zu bytes is below the stream's bound %llu (ycge_sixel_stream_bound)", fn, capacity, bound);
+    rc = join_async(c);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SixelState &S = c->sixel;
+    rc = ensure_planes(c, S, false);
+    const bool host_plane = host_encoder_asked();
+    if (rc == YCGE_OK && !host_plane) rc = ensure_encoder(c, S, c->hiW, c->hiH, viewport_x, viewport_y, clear_screen != 0, bound);
+    if (rc != YCGE_OK) return rc;
+    const FrameOutputs::Pixels q{nullptr, nullptr, dither, true, viewport_x, viewport_y, clear_screen != 0};
+    FrameOutputs out(out_top_bottom_sdr);
+    out.pixels = &q;
+    rc = render_frame_sync(c, &out, st);          // (its stream synchronisation: the length has arrived)
+    if (rc != YCGE_OK) return rc;
+    if (host_plane) {
+        const size_t n = (size_t)c->hiW * c->hiH;
+        rc = sixel_encode_host(S.stage.data() + 5 * n, c->hiW, c->hiH, viewport_x, viewport_y, clear_screen, out_stream, capacity, out_len);
+        if (rc != YCGE_OK) return c->fail(rc, "%s: the host encoder refused the frame's register plane", fn);
+    } else {
+        rc = deliver(c, S, fn, bound, out_stream, out_len);
+        if (rc != YCGE_OK) return rc;
+    }
+    c->chexels.delta_valid = false;          // (the picture lies over the terminal's cells: the next _delta call of any family is a keyframe)
+    return YCGE_OK;
+}
+
+// test hook: the pixel stage alone on a caller's hi-res buffer (2 fbH ss rows of fbW ss samples) under `exposure`, whatever the context's
+// framebuffer is.  Buffers and a tone state of its own on the context's device and stream: no frame state is touched.  Either output may be NULL
+int sixel_test_pixels(ycge_ctx *c, const float *hdr, int32_t fbW, int32_t fbH, int32_t ss, float exposure, int32_t dither, uint8_t *out_rgba, uint8_t *out_index)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    if (!hdr || (!out_rgba && !out_index) || fbW <= 0 || fbH <= 0 || ss < 1 || ss > 64 || (int64_t)fbW * fbH * ss * ss > ((int64_t)1 << 26) || dither < 0 || dither > 1)
+        return c->fail(YCGE_ERR_INVALID_ARG, "ycge_test_pixels: bad arguments (%d x %d chexels, super_sample %d: 1..64, dither %d: 0 or 1)", fbW, fbH, ss, dither);
+    HIP_TRY(c, hipSetDevice(c->device));
+    { const int rc = ensure_tables(c, c->chexels); if (rc != YCGE_OK) return rc; }
+    const int W = fbW * ss, H = 2 * fbH * ss;
+    const size_t n = (size_t)W * H;
+    DevBuf<float> in; DevBuf<uint8_t> state, rgba, index;
+    HIP_TRY(c, in.alloc(3 * n));
+    HIP_TRY(c, rgba.alloc(4 * n));
+    HIP_TRY(c, index.alloc(n));
+    HIP_TRY(c, state.alloc(ycge_post_state_bytes()));
+    uint32_t init[6] = {0, 0, 0, 0, 0, 0};
+    if (ycge_post_state_bytes() != sizeof init) return c->fail(YCGE_ERR_INTERNAL, "ycge_test_pixels: the tone state is %zu bytes, not %zu", ycge_post_state_bytes(), sizeof init);
+    std::memcpy(&init[0], &exposure, 4); std::memcpy(&init[1], &exposure, 4);          // {aeExposure, effective}: as ycge_test_post_stage
+    HIP_TRY(c, hipMemcpy(state.p, init, sizeof init, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(in.p, hdr, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    const int e = ycge_launch_sixel_pixels(in.p, W, H, 2.2f, 2.0f, 0.0f, state.p, c->chexels.tables.p, dither, out_rgba ? rgba.p : nullptr, out_index ? index.p : nullptr,
+                                           c->compute_units, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_sixel_pixels launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = YCGE_OK;
+    if (out_rgba) rc = copy_out(c, out_rgba, rgba.p, 4 * n);
+    if (out_index && rc == YCGE_OK) rc = copy_out(c, out_index, index.p, n);
+    return rc;
+}
+
+// test hook: the encoder's kernels alone on a caller's register plane of any W x H whose bound fits (values of 216 or more are refused here,
+// on the host), with buffers of its own: nothing of the context's sixel or delta state is touched.  YCGE_SIXEL_HOST: the host encoder
+int sixel_test_stream(ycge_ctx *c, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity, size_t *out_len)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_test_sixel_stream";
+    unsigned long long bound = 0;
+    if (!index || !out || !out_len || vx < 0 || vy < 0 || !stream_bound(W, H, bound) || H > kMaxRows)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad arguments (%d x %d pixels at (%d, %d))", fn, W, H, vx, vy);
+    if (capacity < bound) return c->fail(YCGE_ERR_INVALID_ARG, "%s: capacity %zu bytes is below the stream's bound %llu (ycge_sixel_stream_bound)", fn, capacity, bound);
+    const size_t n = (size_t)W * H;
+    for (size_t i = 0; i < n; i++)
+        if (index[i] >= 216) return c->fail(YCGE_ERR_INVALID_ARG, "%s: register %d at pixel %zu (0..215)", fn, (int)index[i], i);
+    if (host_encoder_asked()) return sixel_encode_host(index, W, H, vx, vy, clear, out, capacity, out_len);
+    HIP_TRY(c, hipSetDevice(c->device));
+    SixelState S;
+    DevBuf<uint8_t> plane;
+    HIP_TRY(c, plane.alloc(n));
+    { const int rc = ensure_encoder(c, S, W, H, vx, vy, clear != 0, bound); if (rc != YCGE_OK) return rc; }
+    HIP_TRY(c, hipMemcpy(plane.p, index, n, hipMemcpyHostToDevice));
+    { const int rc = launch_encoder(c, S, plane.p, W, H, bound, c->stream); if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; } }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return deliver(c, S, fn, bound, out, out_len);
+}
+
+} // namespace ycge_host

@@ -1043,6 +1043,48 @@ class RaytraceRenderer:
         return self._ansi_call(self.L.ycge_render_frame_ansi_quad_delta, (), console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
                                rgb=True, delta=(merge_gap, tolerance, bool(keyframe), min_contrast))
 
+    # ---------------------------------------------------------------- sixel frames (ycge_render_frame_pixels / _sixel)
+    @staticmethod
+    def sixel_stream_bound(px_width: int, px_height: int, lib=None) -> int:
+        """The most bytes the sixel stream of a px_width x px_height picture can take (ycge_sixel_stream_bound; no GPU needed)."""
+        L = lib if lib is not None else abi.load_library()
+        n = C.c_size_t(0)
+        rc = L.ycge_sixel_stream_bound(int(px_width), int(px_height), C.byref(n))
+        if rc != 0:
+            raise abi.YcgeError(rc, f"no sixel stream bound for a {px_width} x {px_height} picture")
+        return n.value
+
+    def TryFlipAndBlitPixels(self, rgba: bool = True, index: bool = True, dither: bool = False, sdr: bool = False) -> dict:
+        """One frame (ycge_render_frame_pixels): every hi-res sample the frame traced as a pixel - {name: array} for each output asked:
+        "rgba" (2 fbH ss, fbW ss, 4) uint8, the sRGB8 bytes with alpha 255; "index" (2 fbH ss, fbW ss) uint8, its register in the
+        6 x 6 x 6 cube of the sixel stream (ordered 4 x 4 dither on request); "sdr" as TryFlipAndBlitChexels.  The SDR and the frame
+        state are those of TryFlipAndBlit(want_sdr=True); the statistics go to self.stats.  The ANSI delta state is left alone."""
+        W, H = self.fbW * self.ss, 2 * self.fbH * self.ss
+        shapes = {"sdr": ((self.fbH, self.fbW, 2, 3), np.float32), "rgba": ((H, W, 4), np.uint8), "index": ((H, W), np.uint8)}
+        want = {"sdr": sdr, "rgba": rgba, "index": index}
+        arrays = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items() if want[k]}
+        ptr = lambda k, t: arrays[k].ctypes.data_as(C.POINTER(t)) if k in arrays else None
+        self._check(self.L.ycge_render_frame_pixels(self.ctx, ptr("sdr", C.c_float), ptr("rgba", C.c_uint8), ptr("index", C.c_uint8), int(bool(dither)),
+                                                    C.byref(self.stats)))
+        return arrays
+
+    def TryFlipAndBlitSixel(self, viewport=(0, 0), clear_screen: bool = False, dither: bool = False, sdr: bool = False):
+        """One frame (ycge_render_frame_sixel): the DEC sixel stream of TryFlipAndBlitPixels' registers with its top left corner at cell
+        `viewport`, built on the device - `bytes`, or (bytes, SDR array) with sdr=True.  The picture paints over the terminal's cells: the
+        next _delta call of any family returns a keyframe.  The stream is read back into one growable pageable buffer of the renderer of
+        the bound's size, of which only the pages a stream reaches are ever backed."""
+        bound = self.sixel_stream_bound(self.fbW * self.ss, 2 * self.fbH * self.ss, self.L)
+        buf = self.__dict__.get("_sixel_buf")
+        if buf is None or buf.size < bound:
+            buf = self.__dict__["_sixel_buf"] = np.empty(bound, np.uint8)
+        n = C.c_size_t(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._check(self.L.ycge_render_frame_sixel(self.ctx, int(viewport[0]), int(viewport[1]), int(bool(clear_screen)), int(bool(dither)),
+                                                   buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size, C.byref(n),
+                                                   s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
+        stream = buf[:n.value].tobytes()
+        return (stream, s) if sdr else stream
+
     # ---------------------------------------------------------------- ANSI streams with frames in flight (ycge_render_frame_async_ansi)
     def RenderAsyncAnsi(self, slot: int, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                         clear_screen: bool = False, rgb: bool = False, delta: bool = False, merge_gap: int = 3, tolerance: int = 0,
