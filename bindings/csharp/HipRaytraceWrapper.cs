@@ -45,9 +45,11 @@
 //                flicker does not flip glyphs in a resting picture (INTEGRATION.md section 8.5).
 //   SixelGraphics - with DeviceAnsiStream: the frame's bytes are a DEC sixel stream (ycge_render_frame_sixel) of every hi-res sample the frame
 //                traced - fbW * superSample by 2 * fbH * superSample pixels in the 216 colours of a 6 x 6 x 6 cube, SixelDither an ordered
-//                4 x 4 dither - with its top left corner at the framebuffer's viewport cell.  Any superSample; synchronous (no FrameLate), no
-//                delta form, and the other framebuffers are not composed into the picture: the host writes its text cells behind the image.
-//                The stream buffer is pageable memory of the bound's size (INTEGRATION.md section 8.6).
+//                4 x 4 dither - with its top left corner at the framebuffer's viewport cell.  Any superSample; synchronous (no FrameLate),
+//                and the other framebuffers are not composed into the picture: the host writes its text cells behind the image.
+//                The stream buffer is pageable memory of the bound's size (INTEGRATION.md section 8.6).  SixelDelta: the delta form
+//                (ycge_render_frame_sixel_delta) - after the first picture a frame repaints only the bands and columns whose registers
+//                changed, on the delta state the context shares with Video mode (HipVideoWrapper) and the ANSI delta calls.
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -77,6 +79,7 @@ public sealed class HipRaytraceOptions
     public int QuadrantMinContrast = 0;                       // ... a cell stays one colour while its sub-cell bytes lie this close to their mean (0..255)
     public bool SixelGraphics = false;                        // DeviceAnsiStream: the frame as a sixel stream, a pixel a hi-res sample (any superSample, no FrameLate, no delta)
     public bool SixelDither = false;                          // ... with the ordered 4 x 4 dither of the quantiser
+    public bool SixelDelta = false;                           // ... and as delta streams: only the bands and columns that changed are repainted
     public HipGeneratedWorld GeneratedWorld;                  // chunks that come from the generator are made on the device (ycge_scene_generate_grids)
 }
 
@@ -182,6 +185,7 @@ public partial class RaytraceEntity
         private readonly bool ansiQuad;             // QuadrantGlyphs: the quadrant-glyph forms of the two calls
         private readonly int ansiMinContrast;
         private readonly bool sixel, sixelDither;   // SixelGraphics: ycge_render_frame_sixel in place of every stream form
+        private readonly bool sixelDelta;           // ... SixelDelta: ycge_render_frame_sixel_delta
         private bool sixelBufOwned;                 // ... ansiBuf is pageable memory of this wrapper (Marshal), not the library's page-locked memory
         private bool inFlight;                      // FrameLate: a frame queued by the last TryFlipAndBlit has not been waited for yet
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
@@ -212,7 +216,7 @@ public partial class RaytraceEntity
             if (ansiQuad && (ss & 1) != 0) throw new ArgumentException("QuadrantGlyphs needs an even superSample");
             if (ansiQuad && options.FrameLate) throw new ArgumentException("QuadrantGlyphs has no FrameLate form");
             ansiRgb |= ansiQuad;                    // (the quadrant streams are 24-bit ones: their bound is the 24-bit bound)
-            sixel = ansi != null && options.SixelGraphics; sixelDither = sixel && options.SixelDither;
+            sixel = ansi != null && options.SixelGraphics; sixelDither = sixel && options.SixelDither; sixelDelta = sixel && options.SixelDelta;
             if (sixel && (options.FrameLate || options.DeviceAnsiDelta || options.QuadrantGlyphs)) throw new ArgumentException("SixelGraphics has no FrameLate, delta or quadrant form");
             frameLate = options != null && options.FrameLate && cfg.NDevices <= 1;      // (frames in flight are the single-device form)
             deviceColors = options != null && options.DeviceChexelColors;
@@ -316,7 +320,11 @@ public partial class RaytraceEntity
                 ansiBuf = (byte*)System.Runtime.InteropServices.Marshal.AllocHGlobal(checked((IntPtr)(long)(ulong)bound)); sixelBufOwned = true; ansiCap = (ulong)bound;
             }
             UIntPtr len;
-            Ycge.Check(ctx, Ycge.ycge_render_frame_sixel(ctx, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, sixelDither ? 1 : 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null));
+            if (sixelDelta)
+                Ycge.Check(ctx, Ycge.ycge_render_frame_sixel_delta(ctx, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, 0, sixelDither ? 1 : 0, ansiBuf, (UIntPtr)ansiCap, &len,
+                                                                   null, null, null));
+            else
+                Ycge.Check(ctx, Ycge.ycge_render_frame_sixel(ctx, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, sixelDither ? 1 : 0, ansiBuf, (UIntPtr)ansiCap, &len, null, null));
             ansiLen = (ulong)len;
             ansi.ClearPending = false;
         }

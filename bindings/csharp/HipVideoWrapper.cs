@@ -13,7 +13,9 @@
 // the host no longer searches the palette; DeviceAnsiStream hands the presenter the bytes ANSITerminalRenderer.Render() would write.
 // QuadrantGlyphs + QuadrantMinContrast: the quadrant-glyph forms (ycge_video_blit_ansi_quad / _quad_delta), so that the mode switch keeps the
 // glyph family and, with DeviceAnsiDelta, the quadrant family's delta state: the first video frame behind a traced one is a delta, not a keyframe.
-// INTEGRATION.md section 9.
+// SixelGraphics / SixelDither / SixelDelta: the film per pixel (ycge_video_blit_sixel / _sixel_delta), so that a host with SixelGraphics on keeps
+// its presenter through the mode switch; with SixelDelta a paused film costs the header and the trailer, and the first video frame behind a
+// traced one is a delta.  INTEGRATION.md sections 8.6 and 9.
 using System;
 using ConsoleGame.RayTracing;
 using ConsoleGame.RayTracing.Native;
@@ -41,6 +43,8 @@ public partial class RaytraceEntity
         private readonly int ansiTolerance;
         private readonly bool ansiQuad;             // HipRaytraceOptions.QuadrantGlyphs: the quadrant-glyph forms (superSample even)
         private readonly int ansiMinContrast;
+        private readonly bool sixel, sixelDither, sixelDelta;   // HipRaytraceOptions.SixelGraphics: the sixel forms in place of every stream form
+        private bool sixelBufOwned;                 // ... ansiBuf is pageable memory of this wrapper (Marshal), not the library's page-locked memory
 
         /// <summary>sharedContext: the context of the raytrace wrapper of the same console, whose geometry must be fb's and superSample's
         /// (IntPtr.Zero: a context of this wrapper's own).</summary>
@@ -55,7 +59,8 @@ public partial class RaytraceEntity
             ansiQuad = ansi != null && options.QuadrantGlyphs; ansiMinContrast = options != null ? options.QuadrantMinContrast : 0;
             if (ansiQuad && (ss & 1) != 0) throw new ArgumentException("QuadrantGlyphs needs an even superSample");
             ansiRgb |= ansiQuad;                    // (the quadrant streams are 24-bit ones: their bound is the 24-bit bound)
-            // (SixelGraphics has no Video mode form - the blit keeps no per-sample plane: a video frame of such a host goes out as a cell stream)
+            sixel = ansi != null && options.SixelGraphics; sixelDither = sixel && options.SixelDither; sixelDelta = sixel && options.SixelDelta;
+            if (sixel && (options.DeviceAnsiDelta || options.QuadrantGlyphs)) throw new ArgumentException("SixelGraphics has no ANSI delta or quadrant form");
             deviceColors = options != null && options.DeviceChexelColors;
             if (sharedContext != IntPtr.Zero)
             {
@@ -108,6 +113,7 @@ public partial class RaytraceEntity
             if (fb == null) throw new ArgumentNullException(nameof(fb));
             IntPtr frame = reader.GetCurrentFramePtr();                        // VideoRenderer.cs:71-73, 83
             int srcW = reader.Width, srcH = reader.Height, bpp = useRGBA ? 4 : 3;
+            if (sixel) { BlitSixel(fb, frame, srcW, srcH, bpp); return; }
             if (ansi != null)
             {
                 int cw = ansi.consoleWidth, ch = ansi.consoleHeight;
@@ -160,12 +166,40 @@ public partial class RaytraceEntity
                 }
         }
 
+        // SixelGraphics: the frame as the sixel stream of the blit's hi-res samples at the framebuffer's viewport; the buffer is pageable memory of
+        // the bound's size, as HipRaytraceWrapper's
+        private void BlitSixel(Framebuffer fb, IntPtr frame, int srcW, int srcH, int bpp)
+        {
+            Ycge.Check(ctx, Ycge.ycge_sixel_stream_bound(fbW * ss, 2 * fbH * ss, out UIntPtr bound));
+            if ((ulong)bound > ansiCap)
+            {
+                FreeAnsiBuf();
+                ansiBuf = (byte*)System.Runtime.InteropServices.Marshal.AllocHGlobal(checked((IntPtr)(long)(ulong)bound)); sixelBufOwned = true; ansiCap = (ulong)bound;
+            }
+            UIntPtr len;
+            if (sixelDelta)
+                Ycge.Check(ctx, Ycge.ycge_video_blit_sixel_delta(ctx, frame, srcW, srcH, bpp, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, 0, sixelDither ? 1 : 0, ansiBuf,
+                                                                 (UIntPtr)ansiCap, &len, null, null));
+            else
+                Ycge.Check(ctx, Ycge.ycge_video_blit_sixel(ctx, frame, srcW, srcH, bpp, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, sixelDither ? 1 : 0, ansiBuf,
+                                                           (UIntPtr)ansiCap, &len, null));
+            ansiLen = (ulong)len;
+            ansi.ClearPending = false;
+        }
+
+        private void FreeAnsiBuf()
+        {
+            if (ansiBuf == null) return;
+            if (sixelBufOwned) System.Runtime.InteropServices.Marshal.FreeHGlobal((IntPtr)ansiBuf); else Ycge.ycge_free_host_buffer((IntPtr)ansiBuf);
+            ansiBuf = null; sixelBufOwned = false; ansiCap = ansiLen = 0;
+        }
+
         public void Dispose()
         {
             if (ownsContext && ctx != IntPtr.Zero) Ycge.ycge_destroy(ctx);
             ctx = IntPtr.Zero;
             FreeFrame();
-            if (ansiBuf != null) { Ycge.ycge_free_host_buffer((IntPtr)ansiBuf); ansiBuf = null; }
+            FreeAnsiBuf();
             reader?.Dispose();                                                 // VideoRenderer.Dispose (:150-153)
         }
     }

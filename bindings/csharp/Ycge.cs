@@ -388,6 +388,19 @@ namespace ConsoleGame.RayTracing.Native
                                                                           UIntPtr capacity, UIntPtr* outLen, float* outTopBottomSdr, YFrameStats* stats);
         [DllImport(Lib)] public static extern int ycge_sixel_encode_host(byte* index, int pxW, int pxH, int viewportX, int viewportY, int clearScreen, byte* outStream,
                                                                          UIntPtr capacity, UIntPtr* outLen);
+        // sixel in Video mode and the delta sixel streams (found by symbol lookup, ABI stays 10): the blit's hi-res samples as planes or as a stream, and the
+        // streams that repaint only the bands and columns that changed against the last sixel stream handed out (outInfo: keyframe, bands, pixels, lines)
+        [DllImport(Lib)] public static extern int ycge_video_blit_pixels(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, float* outTopBottomSdr, byte* outRgba,
+                                                                         byte* outIndex, int dither);
+        [DllImport(Lib)] public static extern int ycge_video_blit_sixel(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int viewportX, int viewportY,
+                                                                        int clearScreen, int dither, byte* outStream, UIntPtr capacity, UIntPtr* outLen, float* outTopBottomSdr);
+        [DllImport(Lib)] public static extern int ycge_render_frame_sixel_delta(IntPtr ctx, int viewportX, int viewportY, int clearScreen, int keyframe, int dither, byte* outStream,
+                                                                                UIntPtr capacity, UIntPtr* outLen, uint* outInfo, float* outTopBottomSdr, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_video_blit_sixel_delta(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int viewportX, int viewportY,
+                                                                              int clearScreen, int keyframe, int dither, byte* outStream, UIntPtr capacity, UIntPtr* outLen,
+                                                                              uint* outInfo, float* outTopBottomSdr);
+        [DllImport(Lib)] public static extern int ycge_sixel_encode_delta_host(byte* prevIndex, byte* index, int pxW, int pxH, int viewportX, int viewportY, byte* outStream,
+                                                                               UIntPtr capacity, UIntPtr* outLen, uint* outInfo);
         // the console's other framebuffers for every stream call above (found by symbol lookup, ABI stays 10); YConsoleLayer, YChexel and
         // HipConsoleLayers: bindings/csharp/YcgeConsole.cs
         [DllImport(Lib)] public static extern int ycge_console_set_layers(IntPtr ctx, YConsoleLayer* layers, int n, int raytraceAt);

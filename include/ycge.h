@@ -994,7 +994,7 @@ int ycge_render_frame_ansi_quad_delta(ycge_ctx *ctx, int32_t console_w, int32_t 
  *   Refused before any device work, nothing written, frame and delta state untouched, the message naming the value (YCGE_ERR_INVALID_ARG):
  *   a NULL stream or length; capacity below the bound; a negative viewport_x or viewport_y; dither outside 0..1; all destinations NULL (the
  *   planes call); whatever ycge_render_frame_chexels refuses - peer contexts, RCCL with lean slabs.
- *   Not offered: Video mode (k_video_blit keeps no per-sample plane); frames in flight; partial or delta images; layers composed into the
+ *   Not offered: frames in flight; layers composed into the
  *   picture; a grey ramp or an adaptive palette; pixel replication to scale the image; the kitty graphics protocol (the out_rgba plane of
  *   ycge_render_frame_pixels is what a host would base64 for it). */
 int ycge_sixel_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes);
@@ -1004,6 +1004,55 @@ int ycge_render_frame_sixel(ycge_ctx *ctx, int32_t viewport_x, int32_t viewport_
                             size_t capacity, size_t *out_len, float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
 int ycge_sixel_encode_host(const uint8_t *index, int32_t px_w, int32_t px_h, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen,
                            uint8_t *out_stream, size_t capacity, size_t *out_len);
+/* --- Sixel in Video mode, and delta sixel streams.  Added after ABI 10 without changing it, as the block above; found by symbol lookup.
+ *   Video mode's pixel plane (ycge_video_blit_pixels).  Geometry: the blit's hi-res grid, W = fbW ss by H = 2 fbH ss, with the letterbox and
+ *   the tables of ycge_video_blit.  Sample: pixel (x, y) is the per-channel Clamp01 of SampleSourceLanczos at hi-res sample (x, y) - the value
+ *   ycge_video_blit adds into its half-cell sum - with no box sum and no tone map.  Bytes: its sRGB8 bytes from the threshold tables, alpha
+ *   255.  Register: the sixel quantiser above, the Bayer matrix indexed by the hi-res pixel.  SDR: where out_top_bottom_sdr is asked for it is
+ *   ycge_video_blit's, bit for bit.  At super_sample 1 out_rgba is ycge_video_blit's out_rgba, byte for byte.  Any subset of the three
+ *   destinations may be NULL, not all.  The call leaves the frame state and the delta state alone.
+ *   ycge_video_blit_sixel: the stream of that register plane; arguments, bound, refusals and bytes are ycge_render_frame_sixel's for the same
+ *   plane, and ycge_video_blit's refusals of the source frame apply too.  The frame state stays untouched, as for every blit.
+ *   Delta streams (ycge_render_frame_sixel_delta, ycge_video_blit_sixel_delta).  prev is the register plane of the last sixel stream this
+ *   context handed out while its state is valid, cur this call's.  A KEYFRAME - the stream of ycge_render_frame_sixel (ycge_video_blit_sixel)
+ *   for the same arguments, byte for byte - is returned when there is no valid prev, when {W, H, viewport_x, viewport_y} differ from prev's,
+ *   when clear_screen != 0 or when keyframe != 0.  Else, for band k (rows 6 k .. 6 k + 5, cut at H), lo_k is the smallest column in which
+ *   any of the band's rows differs between prev and cur and hi_k the largest such column + 1; the band is unchanged when there is none.
+ *   The delta stream is, in this order: ESC[<viewport_y + 1>;<viewport_x + 1>H; ESC P 0;1 q (P2 = 1: a zero bit leaves its pixel as it is -
+ *   the only difference from the full header); "1;1;<W>;<H>; the 216 register definitions; the body; ESC \.  The body: bands 0 .. the last
+ *   changed band joined by '-', an unchanged band empty, nothing behind the last changed band, empty when no band changed.  A changed band has
+ *   one line per register present in columns lo_k .. hi_k - 1 of the band in cur, ascending, joined by '$': #<c>, then sixel x with bit r set
+ *   where lo_k <= x < hi_k and cur(x, 6 k + r) == c, every other sixel 0, written by the full stream's rules (leading empty columns are runs
+ *   of '?', runs from 4 on !<n>, the empty tail omitted).  When every pixel of every column changed the body is the full stream's body.
+ *   out_info (4 words or NULL): {keyframe returned, changed bands, pixels painted - span width x band rows, summed -, lines}; the three
+ *   counts are 0 on a keyframe.
+ *   Known answers.  prev the 5 x 7 picture above at viewport (2, 1): (2, 6) -> 0 and (3, 6) -> 7 gives the body -#0??@$#7???@, 3165 bytes,
+ *   {0, 1, 2, 2}; (1, 1) -> 0 and (3, 2) -> 215 gives #0?zxx$#7?CEA$#215???C, 3174 bytes, {0, 1, 18, 3}; no change gives the empty body, 3152
+ *   bytes, {0, 0, 0, 0}.
+ *   Bound.  A delta never exceeds ycge_sixel_stream_bound, which stays the capacity to pass: the header is 3 bytes longer (and has no ESC[2J),
+ *   a changed band's lines fit its budget as the full stream's do, and an unchanged band costs one byte out of a band budget of at least 36.
+ *   State.  One terminal, one state a context: the sixel delta is one more family of the ANSI _delta calls' state, shared by frames and
+ *   video.  prev advances only when one of the two delta calls returns YCGE_OK.  The next sixel delta is a keyframe after a failure behind the
+ *   refusals, ycge_resize, a plain _sixel call of either mode, or any ANSI stream of any family; a sixel delta makes the next ANSI _delta
+ *   call a keyframe.  The two planes calls leave the state alone, and a refusal of arguments leaves it as it was.
+ *   Refusals: those of ycge_render_frame_sixel / ycge_video_blit_sixel, decided before any device work.
+ *   ycge_sixel_encode_delta_host: the delta stream in plain C++ from the two planes (never a keyframe), the yardstick of the kernels and with
+ *   YCGE_SIXEL_HOST=1 the encoder of the delta calls on the planes read back.
+ *   Not offered: a tolerance or hysteresis, resending only the registers in use, frames in flight. */
+int ycge_video_blit_pixels(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                           float *out_top_bottom_sdr /* may be NULL */, uint8_t *out_rgba /* W x H RGBA8, may be NULL */,
+                           uint8_t *out_index /* W*H registers, may be NULL */, int32_t dither);
+int ycge_video_blit_sixel(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t viewport_x, int32_t viewport_y,
+                          int32_t clear_screen, int32_t dither, uint8_t *out_stream, size_t capacity, size_t *out_len,
+                          float *out_top_bottom_sdr /* may be NULL */);
+int ycge_render_frame_sixel_delta(ycge_ctx *ctx, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t keyframe, int32_t dither,
+                                  uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */,
+                                  float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+int ycge_video_blit_sixel_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t viewport_x,
+                                int32_t viewport_y, int32_t clear_screen, int32_t keyframe, int32_t dither, uint8_t *out_stream, size_t capacity,
+                                size_t *out_len, uint32_t *out_info /* 4 words or NULL */, float *out_top_bottom_sdr /* may be NULL */);
+int ycge_sixel_encode_delta_host(const uint8_t *prev_index, const uint8_t *index, int32_t px_w, int32_t px_h, int32_t viewport_x, int32_t viewport_y,
+                                 uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */);
 /* --- ANSI streams with frames in flight: the four frame forms above - ycge_render_frame_ansi, _ansi_delta, _ansi_rgb, _ansi_rgb_delta - queued
  * as ycge_render_frame_async_sdr queues a frame.  The synchronous calls read the stream's length on the host and copy exactly that many
  * bytes, which takes a synchronisation inside the call; here a kernel behind the stream's kernels (k_ansi_deliver, csrc/ycge_ansi_flight.hip)

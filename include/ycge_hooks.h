@@ -168,6 +168,13 @@ int ycge_test_bodies_tick_host(ycge_camera_body *bodies, const ycge_body_shape *
 int ycge_test_pixels(ycge_ctx *c, const float *hdr, int32_t fbW, int32_t fbH, int32_t ss, float exposure, int32_t dither, uint8_t *out_rgba, uint8_t *out_index);
 int ycge_test_sixel_stream(ycge_ctx *c, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity,
                            size_t *out_len);
+/* ycge_test_video_pixels: k_video_pixels alone on a caller's source frame and geometry, whatever the context's framebuffer is: out_rgba and
+ * out_index of fbW ss x 2 fbH ss pixels, either may be NULL.  ycge_test_sixel_delta_stream: the delta encoder's kernels alone on two caller's
+ * register planes (prev: what the terminal shows); out_info 4 words or NULL.  Both use buffers of their own and touch no context state */
+int ycge_test_video_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t fbW, int32_t fbH, int32_t ss,
+                           int32_t dither, uint8_t *out_rgba, uint8_t *out_index);
+int ycge_test_sixel_delta_stream(ycge_ctx *c, const uint8_t *prev, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, uint8_t *out,
+                                 size_t capacity, size_t *out_len, uint32_t *out_info);
 
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */

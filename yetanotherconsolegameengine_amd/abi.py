@@ -402,6 +402,18 @@ _PROTOTYPES = {
                                           C.POINTER(C.c_float), C.POINTER(FrameStats)]),
     "ycge_sixel_encode_host": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
                                          C.POINTER(C.c_size_t)]),
+    # sixel in Video mode (the planes; the stream) and the delta sixel streams of frames and video (keyframe; out_info: 4 words or None), and the host
+    # encoder of the delta between two register planes (no context)
+    "ycge_video_blit_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint8),
+                                         C.POINTER(C.c_uint8), C.c_int32]),
+    "ycge_video_blit_sixel": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    "ycge_render_frame_sixel_delta": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(FrameStats)]),
+    "ycge_video_blit_sixel_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "ycge_sixel_encode_delta_host": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
+                                               C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     # (req: C.byref(abi.AnsiAsync); out_result: the address of an abi.AnsiAsyncResult in page-locked memory)
     "ycge_render_frame_async_ansi": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
@@ -518,6 +530,15 @@ SIXEL_HOOK_PROTOTYPES = {
     "ycge_test_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "ycge_test_sixel_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
                                          C.POINTER(C.c_size_t)]),
+}
+# ... and of their Video mode and delta forms (tests/test_gpu_video_sixel.py, tests/test_gpu_sixel_delta.py; a table of its own: the one above
+# is held to its two names by tests/test_sixel_cpu.py): k_video_pixels alone on a source frame and geometry (src_w, src_h, bpp, fbW, fbH, ss,
+# dither; the planes, either None), the delta encoder alone on two register planes (prev, cur, W, H, vx, vy; out_info 4 words or None)
+SIXEL_DELTA_HOOK_PROTOTYPES = {
+    "ycge_test_video_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_void_p]),
+    "ycge_test_sixel_delta_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
+                                               C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
 }
 # test hook of the delivery of a stream with frames in flight (csrc/ycge_ansi.cpp), bound where it is used (tests/test_gpu_ansi_flight.py): src,
 # n_src, length, capacity, keyframe, counts (3 uint32), groups, out_stream, out_result (an abi.AnsiAsyncResult in page-locked memory)

@@ -285,6 +285,65 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// The delta and Video mode forms of the sixel presenter (the bodies: ycge_sixel.cpp, ycge_video.cpp) and their two hooks
+int ycge_sixel_encode_delta_host(const uint8_t *prev_index, const uint8_t *index, int32_t px_w, int32_t px_h, int32_t viewport_x, int32_t viewport_y, uint8_t *out_stream,
+                                 size_t capacity, size_t *out_len, uint32_t *out_info)
+try {
+    return sixel_encode_delta_host(prev_index, index, px_w, px_h, viewport_x, viewport_y, out_stream, capacity, out_len, out_info);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+int ycge_render_frame_sixel_delta(ycge_ctx *c, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t keyframe, int32_t dither, uint8_t *out_stream,
+                                  size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr, ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_frame_stream_delta(c, viewport_x, viewport_y, clear_screen, keyframe, dither, out_stream, capacity, out_len, out_info, out_top_bottom_sdr, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_video_blit_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, float *out_top_bottom_sdr, uint8_t *out_rgba,
+                           uint8_t *out_index, int32_t dither)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_video_pixels(c, frame, src_w, src_h, bytes_per_pixel, out_top_bottom_sdr, out_rgba, out_index, dither);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_video_blit_sixel(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t viewport_x, int32_t viewport_y,
+                          int32_t clear_screen, int32_t dither, uint8_t *out_stream, size_t capacity, size_t *out_len, float *out_top_bottom_sdr)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_video_stream(c, "ycge_video_blit_sixel", frame, src_w, src_h, bytes_per_pixel, viewport_x, viewport_y, clear_screen, -1, dither, out_stream, capacity,
+                              out_len, nullptr, out_top_bottom_sdr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_video_blit_sixel_delta(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t viewport_x, int32_t viewport_y,
+                                int32_t clear_screen, int32_t keyframe, int32_t dither, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
+                                float *out_top_bottom_sdr)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_video_stream(c, "ycge_video_blit_sixel_delta", frame, src_w, src_h, bytes_per_pixel, viewport_x, viewport_y, clear_screen, keyframe != 0 ? 1 : 0, dither,
+                              out_stream, capacity, out_len, out_info, out_top_bottom_sdr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_test_video_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t fbW, int32_t fbH, int32_t ss, int32_t dither,
+                           uint8_t *out_rgba, uint8_t *out_index)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_test_video_pixels(c, frame, src_w, src_h, bytes_per_pixel, fbW, fbH, ss, dither, out_rgba, out_index);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_test_sixel_delta_stream(ycge_ctx *c, const uint8_t *prev, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, uint8_t *out, size_t capacity,
+                                 size_t *out_len, uint32_t *out_info)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_test_delta_stream(c, prev, index, W, H, vx, vy, out, capacity, out_len, out_info);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 int ycge_render_frame_async_chexels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;

@@ -118,7 +118,8 @@ int ycge_launch_quadrant_fit(const float *quad, int fbW, int fbH, const uint8_t 
 int ycge_launch_sixel_pixels(const float *hdr, int W, int H, float gamma, float saturation, float vibrance, const void *state, const uint8_t *tables, int dither,
                              uint8_t *rgba, uint8_t *index, int compute_units, hipStream_t stream);
 int ycge_launch_sixel_encode(const uint8_t *index, int W, int H, uint32_t *last1, uint32_t *lines, uint32_t *line_bytes, uint32_t max_lines, uint32_t *meta,
-                             const uint8_t *header, uint32_t header_bytes, uint8_t *out, uint32_t cap, unsigned long long *res, int compute_units, hipStream_t stream);
+                             const uint8_t *header, uint32_t header_bytes, uint8_t *out, uint32_t cap, unsigned long long *res, int compute_units, hipStream_t stream,
+                             const uint8_t *prev = nullptr, uint32_t *span = nullptr);
 uint32_t ycge_launch_ansi_tiles(uint32_t cells);
 int ycge_launch_ansi_indexed(const ycge_ansi::StreamJob *job, hipStream_t stream);
 int ycge_launch_ansi_rgb(const ycge_ansi::StreamJob *job, hipStream_t stream);
@@ -127,6 +128,8 @@ int ycge_launch_ansi_deliver(const uint8_t *src, const unsigned long long *res, 
 int ycge_launch_video_blit(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, hipStream_t stream);
 int ycge_launch_video_blit_quadrants(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, float *sdr, float *quad_sdr,
                                      hipStream_t stream);
+int ycge_launch_video_pixels(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, const uint8_t *srgb_tables, int dither,
+                             uint8_t *rgba, uint8_t *index, hipStream_t stream);
 size_t ycge_launch_obj_sizes(int which);
 int ycge_launch_obj_count_lines(const uint8_t *text, uint32_t n, uint32_t first, uint32_t *tiles, void *header, hipStream_t stream);
 int ycge_launch_obj_classify(const uint8_t *text, uint32_t n, uint32_t first, const uint32_t *tiles, uint32_t *line_start, uint32_t n_lines, uint32_t *add,
@@ -513,7 +516,9 @@ struct FrameOutputs {
     bool quad_colours_ready = false;                   // a video blit: k_video_blit_quadrants wrote ChexelState::quad_sdr already - the encode is the fit alone
     // ycge_render_frame_pixels / _sixel (ycge_sixel.cpp): the caller's per-pixel planes (W x H RGBA words, W x H registers), any of them NULL,
     // and with `stream` set the sixel stream of the registers at the viewport - its bytes are delivered behind the frame's synchronisation
-    struct Pixels { uint8_t *rgba; uint8_t *index; int32_t dither; bool stream; int32_t vx, vy; bool clear; };
+    // A _sixel_delta call: dev_index, the held plane the registers go to in place of SixelState::index, and with dev_prev the plane the
+    // terminal shows - the stream is the delta against it (dev_prev NULL: the call's keyframe, the full stream)
+    struct Pixels { uint8_t *rgba; uint8_t *index; int32_t dither; bool stream; int32_t vx, vy; bool clear; uint8_t *dev_index = nullptr; const uint8_t *dev_prev = nullptr; };
     const Pixels *pixels = nullptr;
     const AnsiRequest *ansi = nullptr;                 // the ANSI stream asked for (its encode keeps the pairs - 24-bit colour: the RGBA plane - on the device only)
     bool keyframe = true;                              // ... runs the full stream's kernels (a _delta call: what its DeltaCall decided)
@@ -575,7 +580,15 @@ struct ChexelState {
 };
 // what the sixel calls of one context hold (ycge_sixel.cpp; kernels: ycge_sixel.hip): made by the first call, grow-only
 struct SixelState {
-    DevBuf<uint8_t> rgba, index;                       // k_sixel_pixels' planes of the frame at hand
+    DevBuf<uint8_t> rgba, index;                       // k_sixel_pixels' / k_video_pixels' planes of the frame at hand (the planes calls and the plain _sixel calls)
+    // The _sixel_delta calls, frames and video alike: held[held_prev] is the register plane of the last sixel stream handed out, while
+    // ChexelState::delta_valid holds and ChexelState::delta_key names the sixel family ({kSixelFamily, 0, 0, W, H, vx, vy, 0, 0, fbW, fbH}) -
+    // one terminal, one delta state.  A call's registers go to held[1 - held_prev]; a successful call flips held_prev, nothing is copied.
+    // No other call writes either plane
+    DevBuf<uint8_t> held[2];
+    int held_prev = 0;
+    static constexpr int32_t kSixelFamily = 2;         // DeltaKey[0] (the ANSI families: rgb, 0 or 1)
+    DevBuf<uint32_t> span;                             // k_sixel_diff's spans: lo[bands], hi[bands]
     DevBuf<uint32_t> last1, lines, line_bytes, meta;   // the encoder's per-(band, colour) widths, its line list, the lines' bytes then offsets, the line count
     DevBuf<uint8_t> header, stream;                    // the stream's parts 1 to 5 as the host built them, and the stream (its bound)
     std::array<int32_t, 5> header_key{{0, 0, 0, 0, 0}}; // {W, H, vx, vy, clear} the header on the device was built for (W = 0: none)
@@ -1089,12 +1102,27 @@ int sixel_frame_stream(ycge_ctx *c, int32_t viewport_x, int32_t viewport_y, int3
                        size_t *out_len, float *out_top_bottom_sdr, ycge_frame_stats *st);
 int sixel_test_pixels(ycge_ctx *c, const float *hdr, int32_t fbW, int32_t fbH, int32_t ss, float exposure, int32_t dither, uint8_t *out_rgba, uint8_t *out_index);
 int sixel_test_stream(ycge_ctx *c, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity, size_t *out_len);
+// ... and of the delta and video forms: ycge_sixel_encode_delta_host (no context), ycge_render_frame_sixel_delta, ycge_video_blit_pixels, ycge_video_blit_sixel
+// (keyframe < 0) and ycge_video_blit_sixel_delta, and their two hooks
+int sixel_encode_delta_host(const uint8_t *prev, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, uint8_t *out, size_t capacity, size_t *out_len,
+                            uint32_t *out_info);
+int sixel_frame_stream_delta(ycge_ctx *c, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t keyframe, int32_t dither, uint8_t *out_stream,
+                             size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr, ycge_frame_stats *st);
+int sixel_video_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, float *out_top_bottom_sdr, uint8_t *out_rgba, uint8_t *out_index,
+                       int32_t dither);
+int sixel_video_stream(ycge_ctx *c, const char *fn, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t viewport_x, int32_t viewport_y,
+                       int32_t clear_screen, int32_t keyframe, int32_t dither, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
+                       float *out_top_bottom_sdr);
+int sixel_test_video_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, int32_t dither,
+                            uint8_t *out_rgba, uint8_t *out_index);
+int sixel_test_delta_stream(ycge_ctx *c, const uint8_t *prev, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, uint8_t *out, size_t capacity,
+                            size_t *out_len, uint32_t *out_info);
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_plane);   // ycge_ansi.cpp: out.ansi's stream kernels behind the encode on the frame's plane (where out.plan puts it), and the length's copy
 // ycge_video.cpp: Video mode.  The refusals of a source frame; upload + k_video_blit on `stream` for a geometry (*d_sdr: its SDR array);
 // the SDR read-back (a pageable array: staged as run_post does it); the test hooks' bodies
 int video_check_frame(ycge_ctx *c, const char *fn, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp);
 int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const float **d_sdr,
-                  DevBuf<float> *quad_sdr = nullptr);
+                  DevBuf<float> *quad_sdr = nullptr, bool blit = true);          // blit false: the upload and the tables alone (k_video_pixels' frame without an SDR)
 int video_read_sdr(ycge_ctx *c, hipStream_t stream, const float *d_sdr, FrameOutputs &out);
 int video_host_tables(int32_t src_w, int32_t src_h, int32_t fbW, int32_t fbH, int32_t ss, int32_t *x0, float *wx, int32_t *y0, float *wy, float *geom3);
 int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, float *sdr_out,

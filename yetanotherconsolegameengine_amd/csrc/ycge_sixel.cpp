@@ -1,5 +1,5 @@
-// ycge_sixel.cpp - the sixel presenter (ycge_render_frame_pixels, ycge_render_frame_sixel, ycge_sixel_stream_bound, ycge_sixel_encode_host;
-// kernels: ycge_sixel.hip; the contract: include/ycge.h).
+// ycge_sixel.cpp - the sixel presenter (ycge_render_frame_pixels, ycge_render_frame_sixel, ycge_sixel_stream_bound, their delta and Video
+// mode forms; kernels: ycge_sixel.hip, k_video_pixels of ycge_video.hip; the contract: include/ycge.h).
 //
 // A frame of these calls is ycge_render_frame's with the post stage, plus k_sixel_pixels behind the tonemap on the same stream - every
 // hi-res sample of the denoised buffer mapped, encoded to sRGB8 and quantised to a register of the 6 x 6 x 6 cube - and for a stream the
@@ -8,80 +8,26 @@
 // that names none issues no launch or copy of it.  The stream's parts 1 to 5 depend on the geometry and the arguments alone: the host
 // builds them (stream_header) and the context keeps them on the device until another geometry or viewport asks for others.
 //
-// ycge_sixel_encode_host is the same stream in plain C++ from a register plane: the yardstick of the kernels on a machine without a
-// device, and under YCGE_SIXEL_HOST=1 the encoder of ycge_render_frame_sixel and of the stream hook, on the plane read back.
+// ycge_sixel_encode_host and ycge_sixel_encode_delta_host are the same streams in plain C++ from register planes (ycge_sixel_host.cpp, free of
+// HIP and of this context): the yardsticks of the kernels on a machine without a device, and under YCGE_SIXEL_HOST=1 the encoders of the
+// stream calls and of the stream hooks, on the planes read back.
+//
+// A Video mode call (ycge_video_blit_pixels / _sixel / _sixel_delta) is ycge_video_blit's upload, k_video_pixels on the uploaded frame -
+// every hi-res sample of the blit, encoded and quantised - beside k_video_blit where the SDR is asked for, and the same encoder.
+// The _sixel_delta calls hold the register plane of the last stream handed out (SixelState::held) as one more family of the context's
+// delta state (ChexelState::delta_valid / delta_key): SixelDeltaCall below is the transaction, as DeltaCall of ycge_ansi.cpp is the ANSI families'.
 #include "ycge_ctx.h"
+#include "ycge_sixel_host.h"
 
 #include <cstdlib>
 #include <string>
 
 namespace {
 
-constexpr unsigned long long kOffsetLimit = 0xffffffffull;          // the kernels' offsets are 32-bit
 constexpr int32_t kMaxRows = 6 * 65535;                              // a band is a row of k_sixel_presence's grid
 
-// 3200 + ceil(H / 6) * min(216, 6 W) * (W + 5); false where W or H is not positive or the bound does not fit 32 bits
-bool stream_bound(int64_t W, int64_t H, unsigned long long &bound)
-{
-    if (W <= 0 || H <= 0) return false;
-    const unsigned __int128 bands = (unsigned __int128)((H + 5) / 6), colours = (unsigned __int128)(6 * W < 216 ? 6 * W : 216);
-    const unsigned __int128 b = 3200 + bands * colours * (unsigned __int128)(W + 5);
-    if (b > kOffsetLimit) return false;
-    bound = (unsigned long long)b;
-    return true;
-}
-
-// parts 1 to 5 of the stream
-std::string stream_header(int32_t W, int32_t H, int32_t vx, int32_t vy, bool clear)
-{
-    std::string s;
-    s.reserve(3200);
-    if (clear) s += "\x1b[2J";
-    s += "\x1b[" + std::to_string((int64_t)vy + 1) + ";" + std::to_string((int64_t)vx + 1) + "H";
-    s += "\x1bPq";
-    s += "\"1;1;" + std::to_string(W) + ";" + std::to_string(H);
-    for (int i = 0; i < 216; i++)
-        s += "#" + std::to_string(i) + ";2;" + std::to_string(20 * (i / 36)) + ";" + std::to_string(20 * (i / 6 % 6)) + ";" + std::to_string(20 * (i % 6));
-    return s;
-}
-
-// the bands and the trailer behind the header, from a plane of values below 216
-void encode_bands(const uint8_t *index, int32_t W, int32_t H, std::string &s)
-{
-    const int32_t bands = (H + 5) / 6;
-    std::vector<uint8_t> six((size_t)W);
-    for (int32_t k = 0; k < bands; k++) {
-        const int32_t rows = H - 6 * k < 6 ? H - 6 * k : 6;
-        const uint8_t *row0 = index + (size_t)6 * k * W;
-        bool present[216] = {};
-        for (int32_t r = 0; r < rows; r++)
-            for (int32_t x = 0; x < W; x++) present[row0[(size_t)r * W + x]] = true;
-        bool first = true;
-        for (int c = 0; c < 216; c++) {
-            if (!present[c]) continue;
-            if (!first) s += '$';
-            first = false;
-            s += '#'; s += std::to_string(c);
-            int32_t width = 0;
-            for (int32_t x = 0; x < W; x++) {
-                uint8_t b = 0;
-                for (int32_t r = 0; r < rows; r++) b |= (uint8_t)((row0[(size_t)r * W + x] == c) << r);
-                six[x] = b;
-                if (b) width = x + 1;
-            }
-            for (int32_t x = 0; x < width;) {
-                int32_t n = 1;
-                while (x + n < width && six[x + n] == six[x]) n++;
-                const char ch = (char)(63 + six[x]);
-                if (n >= 4) { s += '!'; s += std::to_string(n); s += ch; }
-                else s.append((size_t)n, ch);
-                x += n;
-            }
-        }
-        if (k + 1 < bands) s += '-';
-    }
-    s += "\x1b\\";
-}
+using ycge_sixel_host::stream_bound;
+using ycge_sixel_host::stream_header;
 
 bool host_encoder_asked()
 {
@@ -90,7 +36,7 @@ bool host_encoder_asked()
 }
 
 // the encoder's buffers for a W x H plane, and the header on the device: grown before anything is queued
-int ensure_encoder(ycge_ctx *c, SixelState &S, int32_t W, int32_t H, int32_t vx, int32_t vy, bool clear, unsigned long long bound)
+int ensure_encoder(ycge_ctx *c, SixelState &S, int32_t W, int32_t H, int32_t vx, int32_t vy, bool clear, unsigned long long bound, bool delta = false)
 {
     const size_t bands = (size_t)(H + 5) / 6, max_lines = bands * (size_t)(6 * (int64_t)W < 216 ? 6 * W : 216);
     if (S.last1.cap < bands * 216) HIP_TRY(c, S.last1.alloc(bands * 216));
@@ -100,9 +46,10 @@ int ensure_encoder(ycge_ctx *c, SixelState &S, int32_t W, int32_t H, int32_t vx,
     if (!S.res.p) HIP_TRY(c, S.res.alloc(4));
     if (S.stream.cap < bound) HIP_TRY(c, S.stream.alloc((size_t)bound));
     HIP_TRY(c, S.res_host.reserve(64));
-    const std::array<int32_t, 5> key{{W, H, vx, vy, clear ? 1 : 0}};
+    if (delta && S.span.cap < 2 * bands) HIP_TRY(c, S.span.alloc(2 * bands));
+    const std::array<int32_t, 5> key{{W, H, vx, vy, delta ? 2 : (clear ? 1 : 0)}};
     if (key != S.header_key || !S.header.p) {
-        const std::string h = stream_header(W, H, vx, vy, clear);
+        const std::string h = stream_header(W, H, vx, vy, clear, delta);
         if (S.header.cap < h.size()) HIP_TRY(c, S.header.alloc(h.size()));
         S.header_key = {{0, 0, 0, 0, 0}};
         HIP_TRY(c, hipMemcpy(S.header.p, h.data(), h.size(), hipMemcpyHostToDevice));
@@ -111,20 +58,24 @@ int ensure_encoder(ycge_ctx *c, SixelState &S, int32_t W, int32_t H, int32_t vx,
     return YCGE_OK;
 }
 
-int launch_encoder(ycge_ctx *c, SixelState &S, const uint8_t *d_index, int32_t W, int32_t H, unsigned long long bound, hipStream_t stream)
+// d_prev: the delta against that plane (k_sixel_diff in front, the DELTA instances), the length and the three counts copied
+int launch_encoder(ycge_ctx *c, SixelState &S, const uint8_t *d_index, int32_t W, int32_t H, unsigned long long bound, hipStream_t stream, const uint8_t *d_prev = nullptr)
 {
     const size_t bands = (size_t)(H + 5) / 6, max_lines = bands * (size_t)(6 * (int64_t)W < 216 ? 6 * W : 216);
     const int e = ycge_launch_sixel_encode(d_index, W, H, S.last1.p, S.lines.p, S.line_bytes.p, (uint32_t)max_lines, S.meta.p, S.header.p, S.header_bytes, S.stream.p,
-                                           (uint32_t)bound, S.res.p, c->compute_units, stream);
+                                           (uint32_t)bound, S.res.p, c->compute_units, stream, d_prev, d_prev ? S.span.p : nullptr);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "the sixel encoder's launches failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(c, hipMemcpyAsync(S.res_host.p, S.res.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(c, hipMemcpyAsync(S.res_host.p, S.res.p, (d_prev ? 4 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     return YCGE_OK;
 }
 
 // behind the stream's synchronisation: the length the device wrote, the bound check, exactly that many bytes into `out` (staged when pageable)
-int deliver(ycge_ctx *c, SixelState &S, const char *fn, unsigned long long bound, uint8_t *out, size_t *out_len)
+// info (a delta): {0, changed bands, pixels painted, lines} as k_sixel_scan counted them
+int deliver(ycge_ctx *c, SixelState &S, const char *fn, unsigned long long bound, uint8_t *out, size_t *out_len, uint32_t *info = nullptr)
 {
-    const unsigned long long len = *static_cast<const unsigned long long *>(S.res_host.p);
+    const unsigned long long *res = static_cast<const unsigned long long *>(S.res_host.p);
+    const unsigned long long len = res[0];
+    if (info) { info[0] = 0; info[1] = (uint32_t)res[1]; info[2] = (uint32_t)res[2]; info[3] = (uint32_t)res[3]; }
     if (len > bound) return c->fail(YCGE_ERR_DEVICE, "%s: the device wrote a stream of %llu bytes, above its bound %llu", fn, len, bound);
     uint8_t *target = out;
     const bool staged = !host_memory_is_page_locked(out, (size_t)len);
@@ -169,10 +120,11 @@ int sixel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked)
     SixelState &S = c->sixel;
     const FrameOutputs::Pixels &q = *asked.pixels;
     const int W = c->hiW, H = c->hiH;
-    if (!S.index.p || S.index.cap < (size_t)W * H || (q.rgba && S.rgba.cap < 4 * (size_t)W * H) || !c->chexels.tables.p)
+    uint8_t *plane = q.dev_index ? q.dev_index : S.index.p;
+    if (!plane || (!q.dev_index && S.index.cap < (size_t)W * H) || (q.rgba && S.rgba.cap < 4 * (size_t)W * H) || !c->chexels.tables.p)
         return c->fail(YCGE_ERR_INTERNAL, "sixel_encode: the planes of a %d x %d picture are not on the device", W, H);
     // k_sixel_pixels on the buffer and exposure state the tonemap in front of this read
-    const int e = ycge_launch_sixel_pixels(c->denoised, W, H, 2.2f, 2.0f, 0.0f, c->tone_state.p, c->chexels.tables.p, q.dither, q.rgba ? S.rgba.p : nullptr, S.index.p,
+    const int e = ycge_launch_sixel_pixels(c->denoised, W, H, 2.2f, 2.0f, 0.0f, c->tone_state.p, c->chexels.tables.p, q.dither, q.rgba ? S.rgba.p : nullptr, plane,
                                            c->compute_units, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_sixel_pixels launch failed: %s", hipGetErrorString((hipError_t)e));
     return YCGE_OK;
@@ -180,16 +132,17 @@ int sixel_encode(ycge_ctx *c, hipStream_t stream, const FrameOutputs &asked)
 
 // the planes' copies - pageable destinations staged one behind the other - and for a stream the encoder's launches and the length's copy
 // (YCGE_SIXEL_HOST: the register plane's copy into the staging instead, for the host encoder)
-int sixel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out)
+static int planes_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out, int32_t W, int32_t H)
 {
     SixelState &S = c->sixel;
     const FrameOutputs::Pixels &q = *out.pixels;
-    const size_t n = (size_t)c->hiW * c->hiH;
+    const size_t n = (size_t)W * H;
     const bool host_plane = q.stream && host_encoder_asked();
+    const uint8_t *plane = q.dev_index ? q.dev_index : S.index.p;
     void *dst[2] = {q.rgba, q.index};
-    const void *src[2] = {S.rgba.p, S.index.p};
+    const void *src[2] = {S.rgba.p, plane};
     const size_t bytes[2] = {4 * n, n}, off[2] = {0, 4 * n};
-    size_t staged = host_plane ? 5 * n + n : 0;                    // (the host encoder's plane: behind both)
+    size_t staged = host_plane ? 5 * n + n + (q.dev_prev ? n : 0) : 0;          // (the host encoder's plane, and a delta's prev: behind both)
     for (int k = 0; k < 2; k++)
         if (dst[k] && !host_memory_is_page_locked(dst[k], bytes[k]) && staged < off[k] + bytes[k]) staged = off[k] + bytes[k];
     HIP_TRY(c, S.stage.reserve(staged));
@@ -200,11 +153,17 @@ int sixel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out)
         HIP_TRY(c, hipMemcpyAsync(target, src[k], bytes[k], hipMemcpyDeviceToHost, stream));
     }
     if (!q.stream) return YCGE_OK;
-    if (host_plane) { HIP_TRY(c, hipMemcpyAsync(S.stage.data() + 5 * n, S.index.p, n, hipMemcpyDeviceToHost, stream)); return YCGE_OK; }
+    if (host_plane) {
+        HIP_TRY(c, hipMemcpyAsync(S.stage.data() + 5 * n, plane, n, hipMemcpyDeviceToHost, stream));
+        if (q.dev_prev) HIP_TRY(c, hipMemcpyAsync(S.stage.data() + 6 * n, q.dev_prev, n, hipMemcpyDeviceToHost, stream));
+        return YCGE_OK;
+    }
     unsigned long long bound = 0;
-    if (!stream_bound(c->hiW, c->hiH, bound)) return c->fail(YCGE_ERR_INTERNAL, "sixel_read_back: no bound for %d x %d pixels", c->hiW, c->hiH);
-    return launch_encoder(c, S, S.index.p, c->hiW, c->hiH, bound, stream);
+    if (!stream_bound(W, H, bound)) return c->fail(YCGE_ERR_INTERNAL, "sixel_read_back: no bound for %d x %d pixels", W, H);
+    return launch_encoder(c, S, plane, W, H, bound, stream, q.dev_prev);
 }
+
+int sixel_read_back(ycge_ctx *c, hipStream_t stream, FrameOutputs &out) { return planes_read_back(c, stream, out, c->hiW, c->hiH); }
 
 // ---- the bodies of the exports and hooks (the C-ABI with its exception barrier: ycge_chexel.cpp)
 
@@ -218,16 +177,13 @@ int sixel_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes)
 
 int sixel_encode_host(const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out, size_t capacity, size_t *out_len)
 {
-    unsigned long long bound = 0;
-    if (!index || !out || !out_len || vx < 0 || vy < 0 || !stream_bound(W, H, bound) || capacity < bound) return YCGE_ERR_INVALID_ARG;
-    for (size_t i = 0, n = (size_t)W * H; i < n; i++)
-        if (index[i] >= 216) return YCGE_ERR_INVALID_ARG;
-    std::string s = stream_header(W, H, vx, vy, clear != 0);
-    encode_bands(index, W, H, s);
-    if (s.size() > capacity) return YCGE_ERR_INTERNAL;
-    std::memcpy(out, s.data(), s.size());
-    *out_len = s.size();
-    return YCGE_OK;
+    return ycge_sixel_host::encode(index, W, H, vx, vy, clear, out, capacity, out_len);
+}
+
+int sixel_encode_delta_host(const uint8_t *prev, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, uint8_t *out, size_t capacity, size_t *out_len,
+                            uint32_t *out_info)
+{
+    return ycge_sixel_host::encode_delta(prev, index, W, H, vx, vy, out, capacity, out_len, out_info);
 }
 
 int sixel_frame_pixels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_rgba, uint8_t *out_index, int32_t dither, ycge_frame_stats *st)
@@ -343,6 +299,213 @@ int sixel_test_stream(ycge_ctx *c, const uint8_t *index, int32_t W, int32_t H, i
     { const int rc = launch_encoder(c, S, plane.p, W, H, bound, c->stream); if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; } }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return deliver(c, S, fn, bound, out, out_len);
+}
+
+} // namespace ycge_host
+
+namespace {
+
+// One _sixel_delta call's transaction on the context's delta state, frames and video alike: keyframe or delta is decided here, the call's
+// registers go to held[next], and every way out but commit() leaves the next _delta call of any family a keyframe
+struct SixelDeltaCall {
+    ChexelState &X;
+    SixelState &S;
+    const ChexelState::DeltaKey key;
+    bool keyframe = true;
+    int next = 0;
+    SixelDeltaCall(ycge_ctx *c, int32_t W, int32_t H, int32_t vx, int32_t vy, bool clear, bool asked)
+        : X(c->chexels), S(c->sixel), key{{SixelState::kSixelFamily, 0, 0, W, H, vx, vy, 0, 0, c->fbW, c->fbH}}
+    {
+        const DevBuf<uint8_t> &prev = S.held[S.held_prev];
+        keyframe = !X.delta_valid || key != X.delta_key || clear || asked || !prev.p || prev.cap < (size_t)W * H;
+        next = 1 - S.held_prev;
+        X.delta_valid = false;
+    }
+    const uint8_t *prev() const { return keyframe ? nullptr : S.held[S.held_prev].p; }
+    // the stream is with the caller: this call's plane is `prev` from now on
+    void commit() { S.held_prev = next; X.delta_valid = true; X.delta_key = key; }
+};
+
+// what every stream call refuses beside its frame's own refusals; bound: the stream's
+int check_stream_call(ycge_ctx *c, const char *fn, int32_t W, int32_t H, int32_t vx, int32_t vy, const uint8_t *out_stream, size_t capacity, const size_t *out_len,
+                      unsigned long long &bound)
+{
+    if (!out_stream || !out_len) return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_stream and out_len must not be NULL", fn);
+    if (vx < 0 || vy < 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: viewport (%d, %d) (neither may be negative)", fn, vx, vy);
+    if (!stream_bound(W, H, bound) || H > kMaxRows)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: the stream of %d x %d pixels may reach 2^32 bytes (offsets are 32-bit), or has more than %d rows", fn, W, H, kMaxRows);
+    if (capacity < bound) return c->fail(YCGE_ERR_INVALID_ARG, "%s: capacity %zu bytes is below the stream's bound %llu (ycge_sixel_stream_bound)", fn, capacity, bound);
+    return YCGE_OK;
+}
+
+// behind the synchronisation of a stream call: the host encoder on the planes read back (YCGE_SIXEL_HOST), or the device's stream.  prev:
+// the call is a delta; info: 4 words or NULL
+int finish_stream(ycge_ctx *c, SixelState &S, const char *fn, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, bool delta, unsigned long long bound,
+                  uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *info)
+{
+    uint32_t words[4] = {1, 0, 0, 0};
+    int rc;
+    if (host_encoder_asked()) {
+        const size_t n = (size_t)W * H;
+        const uint8_t *cur = S.stage.data() + 5 * n;
+        rc = delta ? sixel_encode_delta_host(cur + n, cur, W, H, vx, vy, out_stream, capacity, out_len, words) : sixel_encode_host(cur, W, H, vx, vy, clear, out_stream, capacity, out_len);
+        if (rc != YCGE_OK) return c->fail(rc, "%s: the host encoder refused the frame's register plane", fn);
+    } else {
+        rc = deliver(c, S, fn, bound, out_stream, out_len, delta ? words : nullptr);
+        if (rc != YCGE_OK) return rc;
+    }
+    if (info) std::memcpy(info, words, sizeof words);
+    return YCGE_OK;
+}
+
+} // namespace
+
+namespace ycge_host {
+
+int sixel_frame_stream_delta(ycge_ctx *c, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t keyframe, int32_t dither, uint8_t *out_stream,
+                             size_t capacity, size_t *out_len, uint32_t *out_info, float *out_top_bottom_sdr, ycge_frame_stats *st)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_render_frame_sixel_delta";
+    unsigned long long bound = 0;
+    // (the order of ycge_render_frame_sixel's refusals: the stream's pointers and viewport, the frame, the bound)
+    if (!out_stream || !out_len) return c->fail(YCGE_ERR_INVALID_ARG, "%s: out_stream and out_len must not be NULL", fn);
+    if (viewport_x < 0 || viewport_y < 0) return c->fail(YCGE_ERR_INVALID_ARG, "%s: viewport (%d, %d) (neither may be negative)", fn, viewport_x, viewport_y);
+    int rc = check_pixel_frame(c, fn, dither);
+    if (rc == YCGE_OK) rc = check_stream_call(c, fn, c->hiW, c->hiH, viewport_x, viewport_y, out_stream, capacity, out_len, bound);
+    if (rc != YCGE_OK) return rc;
+    rc = join_async(c);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int32_t W = c->hiW, H = c->hiH;
+    SixelState &S = c->sixel;
+    SixelDeltaCall call(c, W, H, viewport_x, viewport_y, clear_screen != 0, keyframe != 0);
+    DevBuf<uint8_t> &plane = S.held[call.next];
+    if (plane.cap < (size_t)W * H) HIP_TRY(c, plane.alloc((size_t)W * H));
+    rc = ensure_tables(c, c->chexels);
+    if (rc == YCGE_OK && !host_encoder_asked()) rc = ensure_encoder(c, S, W, H, viewport_x, viewport_y, clear_screen != 0, bound, !call.keyframe);
+    if (rc != YCGE_OK) return rc;
+    const FrameOutputs::Pixels q{nullptr, nullptr, dither, true, viewport_x, viewport_y, clear_screen != 0, plane.p, call.prev()};
+    FrameOutputs out(out_top_bottom_sdr);
+    out.pixels = &q;
+    rc = render_frame_sync(c, &out, st);          // (its stream synchronisation: the length has arrived)
+    if (rc != YCGE_OK) return rc;
+    c->chexels.delta_valid = false;               // (whatever the frame did to the state: the commit alone makes it valid)
+    rc = finish_stream(c, S, fn, W, H, viewport_x, viewport_y, clear_screen, !call.keyframe, bound, out_stream, capacity, out_len, out_info);
+    if (rc != YCGE_OK) return rc;
+    call.commit();
+    return YCGE_OK;
+}
+
+// the three Video mode calls.  The planes call: no stream.  keyframe < 0: ycge_video_blit_sixel, the full stream and an invalid delta state
+// behind it; else ycge_video_blit_sixel_delta
+static int video_pixels_call(ycge_ctx *c, const char *fn, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, float *out_sdr, uint8_t *out_rgba,
+                             uint8_t *out_index, int32_t dither, bool stream, int32_t vx, int32_t vy, int32_t clear, int32_t keyframe, uint8_t *out_stream,
+                             size_t capacity, size_t *out_len, uint32_t *out_info)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    int rc = video_check_frame(c, fn, frame, src_w, src_h, bpp);
+    if (rc != YCGE_OK) return rc;
+    if (!stream && !out_sdr && !out_rgba && !out_index) return c->fail(YCGE_ERR_INVALID_ARG, "%s: every destination is NULL (ask for at least one of sdr, rgba, index)", fn);
+    if (dither < 0 || dither > 1) return c->fail(YCGE_ERR_INVALID_ARG, "%s: dither %d (0 or 1)", fn, dither);
+    const int64_t W64 = (int64_t)c->fbW * c->ss, H64 = (int64_t)2 * c->fbH * c->ss;
+    if (W64 * H64 > (int64_t)INT32_MAX / 2)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: a picture of %lld x %lld pixels (at most 2^30 pixels)", fn, (long long)W64, (long long)H64);
+    const int32_t W = (int32_t)W64, H = (int32_t)H64;
+    unsigned long long bound = 0;
+    if (stream) { rc = check_stream_call(c, fn, W, H, vx, vy, out_stream, capacity, out_len, bound); if (rc != YCGE_OK) return rc; }
+    rc = join_async(c);
+    if (rc != YCGE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SixelState &S = c->sixel;
+    const size_t n = (size_t)W * H;
+    const bool pixels = stream || out_rgba || out_index, delta = stream && keyframe >= 0;
+    uint8_t *plane = nullptr;
+    const uint8_t *prev = nullptr;
+    bool key = true;
+    int next = 0;
+    if (delta) {
+        SixelDeltaCall call(c, W, H, vx, vy, clear != 0, keyframe != 0);
+        key = call.keyframe; next = call.next; prev = call.prev();
+        if (S.held[next].cap < n) HIP_TRY(c, S.held[next].alloc(n));
+        plane = S.held[next].p;
+    } else if (pixels) {
+        if (S.index.cap < n) HIP_TRY(c, S.index.alloc(n));
+        plane = S.index.p;
+    }
+    if (pixels) {
+        if (out_rgba && S.rgba.cap < 4 * n) HIP_TRY(c, S.rgba.alloc(4 * n));
+        rc = ensure_tables(c, c->chexels);
+        if (rc == YCGE_OK && stream && !host_encoder_asked()) rc = ensure_encoder(c, S, W, H, vx, vy, clear != 0, bound, delta && !key);
+        if (rc != YCGE_OK) return rc;
+    }
+    const FrameOutputs::Pixels q{out_rgba, out_index, dither, stream, vx, vy, clear != 0, plane, prev};
+    FrameOutputs out(out_sdr);
+    if (pixels) out.pixels = &q;
+    const float *d_sdr = nullptr;
+    rc = video_enqueue(c, c->stream, frame, src_w, src_h, bpp, c->fbW, c->fbH, c->ss, &d_sdr, nullptr, out_sdr != nullptr);
+    if (rc == YCGE_OK && pixels) {
+        const int e = ycge_launch_video_pixels(c->video.frame.p, src_w, src_h, bpp, c->fbW, c->fbH, c->ss, c->video.tables.p, c->chexels.tables.p, dither,
+                                               out_rgba ? S.rgba.p : nullptr, plane, c->stream);
+        if (e != 0) rc = c->fail(YCGE_ERR_DEVICE, "k_video_pixels launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    if (rc == YCGE_OK) rc = video_read_sdr(c, c->stream, d_sdr, out);
+    if (rc == YCGE_OK && pixels) rc = planes_read_back(c, c->stream, out, W, H);
+    if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; }          // (nothing of this call is queued when it returns)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    out.finish();
+    if (!stream) return YCGE_OK;
+    rc = finish_stream(c, S, fn, W, H, vx, vy, clear, delta && !key, bound, out_stream, capacity, out_len, out_info);
+    if (rc != YCGE_OK) return rc;
+    // (the picture lies over the terminal's cells: behind the plain call the next _delta call of any family is a keyframe; a delta call commits)
+    c->chexels.delta_valid = false;
+    if (delta) { S.held_prev = next; c->chexels.delta_valid = true; c->chexels.delta_key = ChexelState::DeltaKey{{SixelState::kSixelFamily, 0, 0, W, H, vx, vy, 0, 0, c->fbW, c->fbH}}; }
+    return YCGE_OK;
+}
+
+int sixel_video_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, float *out_top_bottom_sdr, uint8_t *out_rgba, uint8_t *out_index,
+                       int32_t dither)
+{
+    return video_pixels_call(c, "ycge_video_blit_pixels", frame, src_w, src_h, bpp, out_top_bottom_sdr, out_rgba, out_index, dither, false, 0, 0, 0, -1, nullptr, 0,
+                             nullptr, nullptr);
+}
+
+int sixel_video_stream(ycge_ctx *c, const char *fn, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t viewport_x, int32_t viewport_y,
+                       int32_t clear_screen, int32_t keyframe, int32_t dither, uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info,
+                       float *out_top_bottom_sdr)
+{
+    return video_pixels_call(c, fn, frame, src_w, src_h, bpp, out_top_bottom_sdr, nullptr, nullptr, dither, true, viewport_x, viewport_y, clear_screen, keyframe,
+                             out_stream, capacity, out_len, out_info);
+}
+
+// test hook: the delta encoder's kernels alone on two caller's register planes of any W x H whose bound fits (values of 216 or more are
+// refused here, on the host), with buffers of its own: nothing of the context's sixel or delta state is touched.  YCGE_SIXEL_HOST: the host encoder
+int sixel_test_delta_stream(ycge_ctx *c, const uint8_t *prev, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, uint8_t *out, size_t capacity,
+                            size_t *out_len, uint32_t *out_info)
+{
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    static const char fn[] = "ycge_test_sixel_delta_stream";
+    unsigned long long bound = 0;
+    if (!prev || !index || !out || !out_len || vx < 0 || vy < 0 || !stream_bound(W, H, bound) || H > kMaxRows)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad arguments (%d x %d pixels at (%d, %d))", fn, W, H, vx, vy);
+    if (capacity < bound) return c->fail(YCGE_ERR_INVALID_ARG, "%s: capacity %zu bytes is below the stream's bound %llu (ycge_sixel_stream_bound)", fn, capacity, bound);
+    const size_t n = (size_t)W * H;
+    for (size_t i = 0; i < n; i++)
+        if (index[i] >= 216 || prev[i] >= 216) return c->fail(YCGE_ERR_INVALID_ARG, "%s: register %d / %d at pixel %zu (0..215)", fn, (int)prev[i], (int)index[i], i);
+    if (host_encoder_asked()) return sixel_encode_delta_host(prev, index, W, H, vx, vy, out, capacity, out_len, out_info);
+    HIP_TRY(c, hipSetDevice(c->device));
+    SixelState S;
+    DevBuf<uint8_t> planes;
+    HIP_TRY(c, planes.alloc(2 * n));
+    { const int rc = ensure_encoder(c, S, W, H, vx, vy, false, bound, true); if (rc != YCGE_OK) return rc; }
+    HIP_TRY(c, hipMemcpy(planes.p, index, n, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(planes.p + n, prev, n, hipMemcpyHostToDevice));
+    { const int rc = launch_encoder(c, S, planes.p, W, H, bound, c->stream, planes.p + n); if (rc != YCGE_OK) { (void)hipStreamSynchronize(c->stream); return rc; } }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint32_t words[4] = {0, 0, 0, 0};
+    const int rc = deliver(c, S, fn, bound, out, out_len, words);
+    if (rc == YCGE_OK && out_info) std::memcpy(out_info, words, sizeof words);
+    return rc;
 }
 
 } // namespace ycge_host

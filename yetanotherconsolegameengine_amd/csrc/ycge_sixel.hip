@@ -10,6 +10,9 @@
 //   k_sixel_walk<0>    one wavefront a line: its byte count
 //   k_sixel_scan       the exclusive scan of the counts: every line's offset, the header, the trailer, the stream's length
 //   k_sixel_walk<1>    the same walk writes the bytes
+// The delta stream (the contract: include/ycge.h at ycge_render_frame_sixel_delta) is the same five launches in their DELTA instances behind
+// k_sixel_diff, which gives every band the span of columns in which it differs from the plane the terminal shows: presence and the walk keep
+// to the span, the separators in front of a line count the unchanged bands it skips.  The full stream's instances are what they were.
 // The walk takes 64 columns a trip.  Lane x holds the sixel of column x; a lane whose sixel differs from its left neighbour's closes the run
 // that ended there (column `width`, one past the colour's last pixel, closes the last one: the empty tail is never walked).  The ballot of
 // those lanes gives each its run's first column by a bit scan, the run open at a trip's end is carried in a scalar, and a wavefront prefix
@@ -19,6 +22,7 @@
 
 #include <cstdint>
 
+#include "ycge_sixel_quantise.hip.h"
 #include "ycge_srgb8.hip.h"
 #include "ycge_tonemap.hip.h"
 
@@ -28,28 +32,13 @@ constexpr int kSixelBlock = 256;
 constexpr uint32_t kRegisters = 216;
 constexpr uint32_t kPresenceTile = 1024;          // columns a workgroup of k_sixel_presence takes
 
-// the 4 x 4 Bayer matrix of the dithered quantiser, D[y & 3][x & 3]
-__constant__ uint8_t c_bayer[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};
-
-// a byte's cube level 0..5 (the contract's integer rules)
-template <bool DITHER>
-__device__ __forceinline__ uint32_t cube_level(uint32_t v, uint32_t d)
-{
-    return DITHER ? (32u * v + 102u * d + 51u) / 1632u : (v + 25u) / 51u;
-}
-
-// one sample: its sRGB8 bytes and its register
+// one sample: its sRGB8 bytes and its register (the bytes-to-word-and-register tail: ycge_sixel_quantise.hip.h, k_video_pixels' too)
 template <bool DITHER>
 __device__ __forceinline__ void pixel(ycge::F3 hdr, float exposure, float gamma, float saturation, float vibrance, const float *t32, uint32_t x, uint32_t y,
                                       uint32_t &rgba, uint32_t &reg)
 {
     const ycge::F3 m = ycge::map_pixel(hdr, exposure, gamma, saturation, vibrance);
-    const uint32_t r = (uint32_t)ycge_chexel::srgb8(t32, ycge_chexel::clamp01(m.x));
-    const uint32_t g = (uint32_t)ycge_chexel::srgb8(t32, ycge_chexel::clamp01(m.y));
-    const uint32_t b = (uint32_t)ycge_chexel::srgb8(t32, ycge_chexel::clamp01(m.z));
-    const uint32_t d = DITHER ? (uint32_t)c_bayer[(y & 3u) * 4u + (x & 3u)] : 0u;
-    rgba = r | g << 8 | b << 16 | 0xff000000u;
-    reg = 36u * cube_level<DITHER>(r, d) + 6u * cube_level<DITHER>(g, d) + cube_level<DITHER>(b, d);
+    ycge_sixel::word_and_register<DITHER>(ycge_chexel::clamp01(m.x), ycge_chexel::clamp01(m.y), ycge_chexel::clamp01(m.z), t32, x, y, rgba, reg);
 }
 
 // n = W * H samples, rows of W packed (the hi-res buffer's own layout): lane j takes samples 4 j .. 4 j + 3, whichever rows they lie in, so
@@ -115,15 +104,58 @@ __device__ __forceinline__ uint32_t put_int(uint8_t *s, uint32_t cap, uint32_t p
     return p + d;
 }
 
+// The delta stream's spans: span[band] = the smallest column in which any row of the band differs between prev and cur, span[n_bands + band] =
+// the largest such column + 1 (0xffffffff and 0 before the launch, and behind it for a band that did not change).  A workgroup takes
+// kPresenceTile columns of one band: a lane's columns' minimum and maximum, the wavefronts' by shuffles, the workgroup's in LDS, then at
+// most one atomicMin and one atomicMax a workgroup
+__global__ __launch_bounds__(kSixelBlock) void k_sixel_diff(const uint8_t *__restrict__ prev, const uint8_t *__restrict__ cur, uint32_t W, uint32_t H,
+                                                            uint32_t *__restrict__ span)
+{
+    __shared__ uint32_t s_lo[kSixelBlock / 64], s_hi[kSixelBlock / 64];
+    const uint32_t band = blockIdx.y, x0 = blockIdx.x * kPresenceTile;
+    const uint32_t x1 = x0 + kPresenceTile < W ? x0 + kPresenceTile : W;
+    uint32_t lo = 0xffffffffu, hi = 0u;
+    for (uint32_t x = x0 + threadIdx.x; x < x1; x += kSixelBlock) {
+        bool differs = false;
+#pragma unroll
+        for (uint32_t r = 0; r < 6; r++) {
+            const uint32_t y = band * 6u + r;
+            if (y >= H) break;
+            differs |= prev[(size_t)y * W + x] != cur[(size_t)y * W + x];
+        }
+        if (differs) { lo = lo < x ? lo : x; hi = x + 1u; }          // (a lane's columns ascend)
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t l = __shfl_xor(lo, d, 64), h = __shfl_xor(hi, d, 64);
+        lo = l < lo ? l : lo; hi = h > hi ? h : hi;
+    }
+    if ((threadIdx.x & 63u) == 0u) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < kSixelBlock / 64; w++) { lo = s_lo[w] < lo ? s_lo[w] : lo; hi = s_hi[w] > hi ? s_hi[w] : hi; }
+        if (hi) { atomicMin(&span[band], lo); atomicMax(&span[gridDim.y + band], hi); }
+    }
+}
+
 // last1[band * 216 + c]: the column of the last pixel of register c in the band, plus 1 (zero before the launch).  A workgroup takes
-// kPresenceTile columns of one band: the tile's maxima in LDS, then one global atomic a colour present
-__global__ __launch_bounds__(kSixelBlock) void k_sixel_presence(const uint8_t *__restrict__ index, uint32_t W, uint32_t H, uint32_t *__restrict__ last1)
+// kPresenceTile columns of one band: the tile's maxima in LDS, then one global atomic a colour present.  DELTA: of the band's span alone -
+// a register the band holds only outside its span gets no line, an unchanged band none at all
+template <bool DELTA>
+__global__ __launch_bounds__(kSixelBlock) void k_sixel_presence(const uint8_t *__restrict__ index, uint32_t W, uint32_t H, uint32_t *__restrict__ last1,
+                                                                const uint32_t *__restrict__ span)
 {
     __shared__ uint32_t s_last[kRegisters];
     if (threadIdx.x < kRegisters) s_last[threadIdx.x] = 0;
     __syncthreads();
-    const uint32_t band = blockIdx.y, x0 = blockIdx.x * kPresenceTile;
-    const uint32_t x1 = x0 + kPresenceTile < W ? x0 + kPresenceTile : W;
+    const uint32_t band = blockIdx.y;
+    uint32_t x0 = blockIdx.x * kPresenceTile;
+    uint32_t x1 = x0 + kPresenceTile < W ? x0 + kPresenceTile : W;
+    if (DELTA) {
+        const uint32_t lo = span[band], hi = span[gridDim.y + band];          // (unchanged: lo > hi = 0, no column)
+        x0 = x0 > lo ? x0 : lo; x1 = x1 < hi ? x1 : hi;
+    }
     for (uint32_t x = x0 + threadIdx.x; x < x1; x += kSixelBlock) {
         uint32_t before = kRegisters;
 #pragma unroll
@@ -191,10 +223,14 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_lines(const uint32_t *__r
 // One wavefront a line, grid-stride over the meta[0] lines.  WRITE = false: line_bytes[line] = the line's bytes - '#', the register's digits,
 // the runs, and the separator behind it ('$' inside a band, '-' behind a band's last line, none behind the stream's last line).
 // WRITE = true: the same bytes at line_bytes[line], which the scan made the line's offset.
-template <bool WRITE>
+// DELTA: the line's sixels are zero left of its band's span[band] - the trips in front of that column's are not walked, the run of empty
+// columns opens at column 0 all the same - and its separators stand IN FRONT of it: '$' behind a line of the same band, else one '-' for
+// every band between the line before (the stream's first line: band 0) and its own, unchanged bands included; none behind the last line
+template <bool WRITE, bool DELTA>
 __global__ __launch_bounds__(kSixelBlock) void k_sixel_walk(const uint8_t *__restrict__ index, uint32_t W, uint32_t H, const uint32_t *__restrict__ last1,
                                                             const uint32_t *__restrict__ lines, const uint32_t *__restrict__ meta,
-                                                            uint32_t *__restrict__ line_bytes, uint8_t *__restrict__ out, uint32_t cap)
+                                                            uint32_t *__restrict__ line_bytes, uint8_t *__restrict__ out, uint32_t cap,
+                                                            const uint32_t *__restrict__ span)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_lines = meta[0];
@@ -205,6 +241,16 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_walk(const uint8_t *__res
         const uint32_t rows = H - band * 6u < 6u ? H - band * 6u : 6u;
         const uint8_t *row0 = index + (size_t)band * 6u * W;
         uint32_t at = WRITE ? line_bytes[line] : 0u;                                // where the next byte goes (WRITE) / the bytes so far
+        uint32_t lo = 0;
+        if (DELTA) {
+            lo = span[band];
+            const uint32_t before = line ? lines[line - 1u] >> 8 : 0u;
+            const uint32_t lead = line && before == band ? 1u : band - before;    // '$', or the '-' of every band from `before` to this one
+            if (WRITE)
+                for (uint32_t k = lane; k < lead; k += 64u)
+                    if (at + k < cap) out[at + k] = (uint8_t)(line && before == band ? '$' : '-');
+            at += lead;
+        }
         if (WRITE) {
             if (lane == 0) {
                 if (at < cap) out[at] = (uint8_t)'#';
@@ -213,11 +259,12 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_walk(const uint8_t *__res
         }
         at += 1u + digits(colour);
         uint32_t run_first = 0, left_carry = 0;                                    // the open run's first column; the sixel of the column before this trip
-        for (uint32_t base = 0; base <= width; base += 64u) {
+        for (uint32_t base = DELTA ? lo & ~63u : 0u; base <= width; base += 64u) {
             const uint32_t x = base + lane;
             uint32_t six = 0x80u;                                                  // column `width` and beyond: no sixel's value
             if (x < width) {
                 six = 0;
+                if (!DELTA || x >= lo)
                 for (uint32_t r = 0; r < rows; r++) six |= (uint32_t)(row0[(size_t)r * W + x] == colour) << r;
             }
             uint32_t left = __shfl_up(six, 1, 64);
@@ -251,6 +298,10 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_walk(const uint8_t *__res
             left_carry = __shfl(six, 63, 64);
         }
         // the separator: none behind the last line of the stream
+        if (DELTA) {
+            if (!WRITE && lane == 0) line_bytes[line] = at;
+            continue;
+        }
         const bool last_line = line + 1u == n_lines;
         const bool band_ends = last_line || (lines[line + 1u] >> 8) != band;
         if (WRITE) {
@@ -262,9 +313,11 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_walk(const uint8_t *__res
 }
 
 // one workgroup: the lines' byte counts -> their offsets in place, behind the header; the header's bytes and the trailer ESC \ into the
-// stream; res[0] = the stream's length
+// stream; res[0] = the stream's length.  DELTA: and res[1..3] = the changed bands, the pixels painted (span width x band rows, summed) and the lines
+template <bool DELTA>
 __global__ __launch_bounds__(kSixelBlock) void k_sixel_scan(uint32_t *__restrict__ line_bytes, const uint32_t *__restrict__ meta, const uint8_t *__restrict__ header,
-                                                            uint32_t header_bytes, uint8_t *__restrict__ out, uint32_t cap, unsigned long long *__restrict__ res)
+                                                            uint32_t header_bytes, uint8_t *__restrict__ out, uint32_t cap, unsigned long long *__restrict__ res,
+                                                            const uint32_t *__restrict__ span, uint32_t n_bands, uint32_t H)
 {
     __shared__ uint32_t wsum[kSixelBlock / 64];
     const uint32_t n_lines = meta[0];
@@ -281,6 +334,21 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_scan(uint32_t *__restrict
         if (k < cap) out[k] = header[k];
     if (threadIdx.x < 2 && carry + threadIdx.x < cap) out[carry + threadIdx.x] = (uint8_t)"\x1b\\"[threadIdx.x];
     if (threadIdx.x == 0) res[0] = carry + 2ull;
+    if (DELTA) {
+        __shared__ unsigned long long s_info[2];
+        if (threadIdx.x < 2) s_info[threadIdx.x] = 0ull;
+        __syncthreads();
+        unsigned long long changed = 0, painted = 0;
+        for (uint32_t band = threadIdx.x; band < n_bands; band += kSixelBlock) {
+            const uint32_t lo = span[band], hi = span[n_bands + band];
+            if (!hi) continue;
+            const uint32_t rows = H - band * 6u < 6u ? H - band * 6u : 6u;
+            changed++; painted += (unsigned long long)(hi - lo) * rows;
+        }
+        if (changed) { atomicAdd(&s_info[0], changed); atomicAdd(&s_info[1], painted); }
+        __syncthreads();
+        if (threadIdx.x == 0) { res[1] = s_info[0]; res[2] = s_info[1]; res[3] = n_lines; }
+    }
 }
 
 } // namespace
@@ -308,9 +376,13 @@ int ycge_launch_sixel_pixels(const float *hdr, int W, int H, float gamma, float 
 
 // The encoder on a register plane of W x H bytes.  last1: n_bands * 216 words; lines and line_bytes: max_lines words each, max_lines >=
 // n_bands * min(216, 6 W); meta: 1 word; header: the stream's parts 1 to 5; out: cap bytes; res: 1 word of 64 bits, the length
+// prev and span (both or neither): the delta stream against the plane prev - span: 2 * n_bands words, header: the delta's, res: 4 words of 64
+// bits {length, changed bands, pixels painted, lines}
 int ycge_launch_sixel_encode(const uint8_t *index, int W, int H, uint32_t *last1, uint32_t *lines, uint32_t *line_bytes, uint32_t max_lines, uint32_t *meta,
-                             const uint8_t *header, uint32_t header_bytes, uint8_t *out, uint32_t cap, unsigned long long *res, int compute_units, hipStream_t stream)
+                             const uint8_t *header, uint32_t header_bytes, uint8_t *out, uint32_t cap, unsigned long long *res, int compute_units, hipStream_t stream,
+                             const uint8_t *prev, uint32_t *span)
 {
+    if ((prev != nullptr) != (span != nullptr)) return (int)hipErrorInvalidValue;
     if (!index || !last1 || !lines || !line_bytes || !meta || !header || !out || !res || W <= 0 || H <= 0 || H > (1 << 24)) return (int)hipErrorInvalidValue;
     const uint32_t n_bands = ((uint32_t)H + 5u) / 6u;
     const uint64_t colours = 6ull * (uint32_t)W < kRegisters ? 6ull * (uint32_t)W : kRegisters;
@@ -318,14 +390,28 @@ int ycge_launch_sixel_encode(const uint8_t *index, int W, int H, uint32_t *last1
     hipError_t e = hipMemsetAsync(last1, 0, (size_t)n_bands * kRegisters * sizeof(uint32_t), stream);
     if (e != hipSuccess) return (int)e;
     const dim3 tiles(((uint32_t)W + kPresenceTile - 1) / kPresenceTile, n_bands);
-    hipLaunchKernelGGL(k_sixel_presence, tiles, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1);
+    if (prev) {
+        e = hipMemsetAsync(span, 0xff, (size_t)n_bands * sizeof(uint32_t), stream);
+        if (e == hipSuccess) e = hipMemsetAsync(span + n_bands, 0, (size_t)n_bands * sizeof(uint32_t), stream);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(k_sixel_diff, tiles, dim3(kSixelBlock), 0, stream, prev, index, (uint32_t)W, (uint32_t)H, span);
+        hipLaunchKernelGGL(k_sixel_presence<true>, tiles, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, span);
+    } else {
+        hipLaunchKernelGGL(k_sixel_presence<false>, tiles, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, span);
+    }
     hipLaunchKernelGGL(k_sixel_lines, dim3(1), dim3(kSixelBlock), 0, stream, last1, n_bands, max_lines, lines, meta);
     const uint32_t need = (max_lines + kSixelBlock / 64 - 1) / (kSixelBlock / 64);
     const uint32_t limit = (uint32_t)(compute_units > 0 ? compute_units : 256) * 8u;
     const dim3 grid(need < limit ? need : limit);
-    hipLaunchKernelGGL(k_sixel_walk<false>, grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap);
-    hipLaunchKernelGGL(k_sixel_scan, dim3(1), dim3(kSixelBlock), 0, stream, line_bytes, meta, header, header_bytes, out, cap, res);
-    hipLaunchKernelGGL(k_sixel_walk<true>, grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap);
+    if (prev) {
+        hipLaunchKernelGGL((k_sixel_walk<false, true>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
+        hipLaunchKernelGGL(k_sixel_scan<true>, dim3(1), dim3(kSixelBlock), 0, stream, line_bytes, meta, header, header_bytes, out, cap, res, span, n_bands, (uint32_t)H);
+        hipLaunchKernelGGL((k_sixel_walk<true, true>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
+    } else {
+        hipLaunchKernelGGL((k_sixel_walk<false, false>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
+        hipLaunchKernelGGL(k_sixel_scan<false>, dim3(1), dim3(kSixelBlock), 0, stream, line_bytes, meta, header, header_bytes, out, cap, res, span, n_bands, (uint32_t)H);
+        hipLaunchKernelGGL((k_sixel_walk<true, false>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
+    }
     return (int)hipGetLastError();
 }
 

@@ -131,7 +131,7 @@ static int ensure_video_tables(ycge_ctx *c, VideoState &V, int src_w, int src_h,
 // quad_sdr (or NULL): the quadrant form - k_video_blit_quadrants writes the sub-cell colours there, fbW * fbH * 12 floats, beside the SDR
 // (ss even: the caller's check_quadrant_call)
 int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const float **d_sdr,
-                  DevBuf<float> *quad_sdr)
+                  DevBuf<float> *quad_sdr, bool blit)
 {
     VideoState &V = c->video;
     { const int rc = ensure_video_tables(c, V, src_w, src_h, fbW, fbH, ss); if (rc != YCGE_OK) return rc; }
@@ -146,6 +146,8 @@ int video_enqueue(ycge_ctx *c, hipStream_t stream, const uint8_t *frame, int src
         src = V.stage.data();
     }
     HIP_TRY(c, hipMemcpyAsync(V.frame.p, src, bytes, hipMemcpyHostToDevice, stream));
+    *d_sdr = V.sdr.p;
+    if (!blit) return YCGE_OK;
     const int e = quad_sdr ? ycge_launch_video_blit_quadrants(V.frame.p, src_w, src_h, bpp, fbW, fbH, ss, V.tables.p, V.sdr.p, quad_sdr->p, stream)
                            : ycge_launch_video_blit(V.frame.p, src_w, src_h, bpp, fbW, fbH, ss, V.tables.p, V.sdr.p, stream);
     if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_video_blit%s launch failed: %s", quad_sdr ? "_quadrants" : "", hipGetErrorString((hipError_t)e));
@@ -199,6 +201,35 @@ int video_test_blit(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t sr
     const int rs = copy_out(c, sdr_out, d_sdr, (size_t)fbW * fbH * 6 * sizeof(float));
     if (rs != YCGE_OK || !quad_out) return rs;
     return copy_out(c, quad_out, quad.p, (size_t)fbW * fbH * 12 * sizeof(float));
+}
+
+// test hook: k_video_pixels alone on a caller-given geometry, whatever the context's framebuffer is, with tables, frame and planes of its own
+// on the context's device and stream: no video, sixel or delta state is touched.  Either output may be NULL, not both
+int sixel_test_video_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t fbW, int32_t fbH, int32_t ss, int32_t dither,
+                            uint8_t *out_rgba, uint8_t *out_index)
+{
+    static const char fn[] = "ycge_test_video_pixels";
+    if (!frame || (!out_rgba && !out_index) || src_w < 1 || src_h < 1 || (bpp != 3 && bpp != 4) || (int64_t)src_w * src_h * bpp >= ((int64_t)1 << 31) ||
+        !geometry_ok(fbW, fbH, ss) || (int64_t)fbW * fbH * 2 * ss * ss > ((int64_t)1 << 26) || dither < 0 || dither > 1)
+        return c->fail(YCGE_ERR_INVALID_ARG, "%s: bad arguments (%d x %d x %d -> %d x %d ss %d, dither %d)", fn, src_w, src_h, bpp, fbW, fbH, ss, dither);
+    HIP_TRY(c, hipSetDevice(c->device));
+    { const int rc = ensure_tables(c, c->chexels); if (rc != YCGE_OK) return rc; }
+    VideoState V;
+    { const int rc = ensure_video_tables(c, V, src_w, src_h, fbW, fbH, ss); if (rc != YCGE_OK) return rc; }
+    const size_t bytes = (size_t)src_w * src_h * bpp, n = (size_t)fbW * ss * fbH * 2 * ss;
+    DevBuf<uint8_t> rgba, index;
+    HIP_TRY(c, V.frame.reserve(bytes));                // (DevBuf's padding takes the last 3-byte pixel's 32-bit load)
+    HIP_TRY(c, rgba.alloc(4 * n));
+    HIP_TRY(c, index.alloc(n));
+    HIP_TRY(c, hipMemcpy(V.frame.p, frame, bytes, hipMemcpyHostToDevice));
+    const int e = ycge_launch_video_pixels(V.frame.p, src_w, src_h, bpp, fbW, fbH, ss, V.tables.p, c->chexels.tables.p, dither, out_rgba ? rgba.p : nullptr,
+                                           out_index ? index.p : nullptr, c->stream);
+    if (e != 0) return c->fail(YCGE_ERR_DEVICE, "k_video_pixels launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = YCGE_OK;
+    if (out_rgba) rc = copy_out(c, out_rgba, rgba.p, 4 * n);
+    if (out_index && rc == YCGE_OK) rc = copy_out(c, out_index, index.p, n);
+    return rc;
 }
 
 } // namespace ycge_host

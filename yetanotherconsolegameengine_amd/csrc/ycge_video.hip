@@ -20,35 +20,23 @@
 // The quadrant form (k_video_blit_quadrants; the contract: include/ycge.h at ycge_video_blit_quadrants) is the same body with the same
 // mapping: beside the SDR it writes each chexel's 2 x 2 sub-cell colours, the sums of the left and right half of a half-cell row's columns,
 // for k_fit_quadrants (ycge_chexel.hip).  Per lane 3 floats of the SDR and 6 consecutive floats of quad_sdr; no LDS, no atomics, no scratch.
+//
+// The pixel plane (k_video_pixels; the contract: include/ycge.h at ycge_video_blit_pixels) is every hi-res sample as it is - its sRGB8 word and
+// its register of the sixel cube - for the sixel presenter's encoder (ycge_sixel.hip).  The 36-tap sample is ycge_video_sample.hip.h's, the one
+// body of all three kernels.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 
+#include "ycge_sixel_quantise.hip.h"
+#include "ycge_video_sample.hip.h"
+
 namespace {
 
 constexpr int kVideoBlock = 64;
 
-// byte / 255.0f, correctly rounded, without the division's expansion: q = b * fl(1/255) is within an ulp, one Newton step on the exact
-// residual lands on the quotient (Markstein); equal to the division for all 256 bytes (tests/test_video_cpu.py checks the formula)
-__device__ __forceinline__ float unorm8(uint32_t b)
-{
-    const float k = 1.0f / 255.0f;
-    const float x = (float)b;
-    const float q = x * k;
-    const float r = __builtin_fmaf(-255.0f, q, x);
-    return __builtin_fmaf(r, k, q);
-}
-
-// VideoRenderer.Clamp01 (:286-291) = Vec3.Clamp01: -0.0 passes
-__device__ __forceinline__ float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
-
-__device__ __forceinline__ uint32_t load_pixel(const uint8_t *p)
-{
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
+using ycge_video::clamp01;          // unorm8, Clamp01, the pixel load and the 36-tap sample: ycge_video_sample.hip.h
 
 // The blit's body, once for both forms.  Quad: the quadrant form (k_video_blit_quadrants) - beside the serial top / bottom sum, which stays
 // what it is sample for sample, the lane keeps the sums of the left and the right half of its columns: quadrants 2 (hy & 1) and 2 (hy & 1) + 1
@@ -71,41 +59,15 @@ __device__ __forceinline__ void video_blit(const uint8_t *__restrict__ frame, in
     float q[kHalves][3] = {};
     for (int sy = 0; sy < ss; sy++) {
         const uint32_t y = hy * (uint32_t)ss + (uint32_t)sy;
-        const int y0 = ty0[y];
         float wy[6];
         uint32_t row[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-            wy[j] = twy[(size_t)y * 6 + j];
-            const int iy = y0 - 2 + j;
-            row[j] = (uint32_t)(iy < 0 ? 0 : (iy > src_h - 1 ? src_h - 1 : iy)) * pitch;
-        }
+        ycge_video::sample_rows(ty0, twy, y, src_h, pitch, wy, row);
 #pragma unroll
         for (int h = 0; h < kHalves; h++) {
             for (int sx = h * span; sx < (h + 1) * span; sx++) {
                 const uint32_t x = cx * (uint32_t)ss + (uint32_t)sx;
-                const int x0 = tx0[x];
-                float wx[6];
-                uint32_t col[6];
-#pragma unroll
-                for (int i = 0; i < 6; i++) {
-                    wx[i] = twx[(size_t)x * 6 + i];
-                    const int ix = x0 - 2 + i;
-                    col[i] = (uint32_t)(ix < 0 ? 0 : (ix > src_w - 1 ? src_w - 1 : ix)) * (uint32_t)bpp;
-                }
-                float r = 0.0f, g = 0.0f, b = 0.0f;
-#pragma unroll
-                for (int j = 0; j < 6; j++) {
-#pragma unroll
-                    for (int i = 0; i < 6; i++) {
-                        const uint32_t px = load_pixel(frame + row[j] + col[i]);          // B G R [A]
-                        const float wxy = wx[i] * wy[j];
-                        r += unorm8(px >> 16 & 255u) * wxy;
-                        g += unorm8(px >> 8 & 255u) * wxy;
-                        b += unorm8(px & 255u) * wxy;
-                    }
-                }
-                r = clamp01(r); g = clamp01(g); b = clamp01(b);
+                float r, g, b;
+                ycge_video::sample(frame, src_w, bpp, tx0, twx, x, wy, row, r, g, b);
                 sum[0] = sum[0] + r;
                 sum[1] = sum[1] + g;
                 sum[2] = sum[2] + b;
@@ -147,6 +109,40 @@ __global__ __launch_bounds__(kVideoBlock) void k_video_blit_quadrants(const uint
                                                                       float *__restrict__ sdr, float inv_quad, float *__restrict__ quad_sdr)
 {
     video_blit<true>(frame, src_w, src_h, bpp, fbW, ss, groups_x, tx0, twx, ty0, twy, inv, sdr, inv_quad, quad_sdr);
+}
+
+// Video mode's pixel plane (the contract: include/ycge.h at ycge_video_blit_pixels): every hi-res sample of the blit as it is - no box sum -
+// its sRGB8 word and its register of the sixel cube.  One lane a sample; a wavefront takes 64 neighbouring samples of ONE hi-res row, so the
+// row's y0 and six weights are scalar loads (the wavefront's number is made uniform for the compiler) and the lanes' taps of one (j, i) lie
+// side by side in the source, as in k_video_blit; a workgroup is four such wavefronts, which share the 256 thresholds in LDS as
+// k_sixel_pixels' lanes do.  A wavefront stores 64 consecutive words and 64 consecutive bytes.  Four samples a lane (uint4 and word stores)
+// would put four columns' 24 weights and offsets in a lane for stores that are full lines already: the one-sample form is kept.
+constexpr int kPixelsBlock = 256;
+
+template <bool DITHER>
+__global__ __launch_bounds__(kPixelsBlock) void k_video_pixels(const uint8_t *__restrict__ frame, int src_w, int src_h, int bpp, uint32_t hiW, uint32_t chunks_x,
+                                                               uint32_t chunks, const int32_t *__restrict__ tx0, const float *__restrict__ twx,
+                                                               const int32_t *__restrict__ ty0, const float *__restrict__ twy, const uint8_t *__restrict__ tables,
+                                                               uint32_t *__restrict__ rgba_out, uint8_t *__restrict__ index_out)
+{
+    __shared__ float t32[256];
+    t32[threadIdx.x] = reinterpret_cast<const float *>(tables)[threadIdx.x];
+    __syncthreads();
+    const uint32_t chunk = blockIdx.x * (kPixelsBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (chunk >= chunks) return;
+    const uint32_t y = chunk / chunks_x;
+    const uint32_t x = (chunk - y * chunks_x) * 64u + (threadIdx.x & 63u);
+    if (x >= hiW) return;
+    float wy[6];
+    uint32_t row[6];
+    ycge_video::sample_rows(ty0, twy, y, src_h, (uint32_t)src_w * (uint32_t)bpp, wy, row);
+    float r, g, b;
+    ycge_video::sample(frame, src_w, bpp, tx0, twx, x, wy, row, r, g, b);
+    uint32_t word, reg;
+    ycge_sixel::word_and_register<DITHER>(r, g, b, t32, x, y, word, reg);
+    const size_t at = (size_t)y * hiW + x;
+    if (rgba_out) rgba_out[at] = word;
+    if (index_out) index_out[at] = (uint8_t)reg;
 }
 
 } // namespace
@@ -202,5 +198,31 @@ extern "C" int ycge_launch_video_blit_quadrants(const uint8_t *frame, int src_w,
     const float inv_quad = 1.0f / (float)((ss / 2) * ss);
     hipLaunchKernelGGL(k_video_blit_quadrants, dim3(groups), dim3(kVideoBlock), 0, stream, frame, src_w, src_h, bpp, (uint32_t)fbW, ss, groups_x, tx0, twx, ty0, twy, inv,
                        sdr, inv_quad, quad_sdr);
+    return (int)hipGetLastError();
+}
+
+// k_video_pixels: frame and tables as above, srgb_tables the 256 f32 thresholds of LinearToSrgb8; rgba hiW * hiH words (4-byte aligned), index
+// hiW * hiH bytes, either may be NULL, not both
+extern "C" int ycge_launch_video_pixels(const uint8_t *frame, int src_w, int src_h, int bpp, int fbW, int fbH, int ss, const uint8_t *tables, const uint8_t *srgb_tables,
+                                        int dither, uint8_t *rgba, uint8_t *index, hipStream_t stream)
+{
+    uint32_t groups_x = 0, groups = 0;
+    const float *some = reinterpret_cast<const float *>(tables);          // (video_launch_shape's sdr: not this launch's)
+    if (!video_launch_shape(frame, src_w, src_h, bpp, fbW, fbH, ss, tables, some, groups_x, groups) || !srgb_tables || (!rgba && !index) || ((uintptr_t)rgba & 3u) ||
+        dither < 0 || dither > 1)
+        return (int)hipErrorInvalidValue;
+    const uint64_t hiW = (uint64_t)fbW * ss, hiH = (uint64_t)fbH * 2 * ss;
+    if (hiW * hiH > (uint64_t)INT32_MAX / 2) return (int)hipErrorInvalidValue;
+    const uint32_t chunks_x = (uint32_t)((hiW + 63u) / 64u);
+    const uint64_t chunks = (uint64_t)chunks_x * hiH;
+    if (chunks > (uint64_t)INT32_MAX) return (int)hipErrorInvalidValue;
+    const int32_t *tx0 = reinterpret_cast<const int32_t *>(tables);
+    const float *twx = reinterpret_cast<const float *>(tables) + hiW;
+    const int32_t *ty0 = tx0 + 7 * hiW;
+    const float *twy = twx + 6 * hiW + hiH;
+    const dim3 grid((uint32_t)((chunks + kPixelsBlock / 64 - 1) / (kPixelsBlock / 64))), block(kPixelsBlock);
+    uint32_t *r32 = reinterpret_cast<uint32_t *>(rgba);
+    if (dither) hipLaunchKernelGGL(k_video_pixels<true>, grid, block, 0, stream, frame, src_w, src_h, bpp, (uint32_t)hiW, chunks_x, (uint32_t)chunks, tx0, twx, ty0, twy, srgb_tables, r32, index);
+    else hipLaunchKernelGGL(k_video_pixels<false>, grid, block, 0, stream, frame, src_w, src_h, bpp, (uint32_t)hiW, chunks_x, (uint32_t)chunks, tx0, twx, ty0, twy, srgb_tables, r32, index);
     return (int)hipGetLastError();
 }

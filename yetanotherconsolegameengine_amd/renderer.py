@@ -1085,6 +1085,27 @@ class RaytraceRenderer:
         stream = buf[:n.value].tobytes()
         return (stream, s) if sdr else stream
 
+    def _sixel_buffer(self):
+        bound = self.sixel_stream_bound(self.fbW * self.ss, 2 * self.fbH * self.ss, self.L)
+        buf = self.__dict__.get("_sixel_buf")
+        if buf is None or buf.size < bound:
+            buf = self.__dict__["_sixel_buf"] = np.empty(bound, np.uint8)
+        return buf
+
+    def TryFlipAndBlitSixelDelta(self, viewport=(0, 0), clear_screen: bool = False, keyframe: bool = False, dither: bool = False, sdr: bool = False):
+        """One frame (ycge_render_frame_sixel_delta): the sixel stream that repaints only the bands and columns whose registers differ from
+        the last sixel stream this context handed out - or TryFlipAndBlitSixel's bytes, a keyframe, when there is no such stream, the
+        geometry or viewport changed, or clear_screen / keyframe ask for one.  (bytes, info) or (bytes, info, SDR array) with sdr=True;
+        info = (keyframe returned, changed bands, pixels painted, lines).  The state is the one the ANSI _delta calls and
+        VideoRenderer.TryFlipAndBlitSixelDelta share."""
+        buf, n, info = self._sixel_buffer(), C.c_size_t(0), (C.c_uint32 * 4)()
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._check(self.L.ycge_render_frame_sixel_delta(self.ctx, int(viewport[0]), int(viewport[1]), int(bool(clear_screen)), int(bool(keyframe)), int(bool(dither)),
+                                                         buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size, C.byref(n), info,
+                                                         s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
+        stream = buf[:n.value].tobytes()
+        return (stream, tuple(info), s) if sdr else (stream, tuple(info))
+
     # ---------------------------------------------------------------- ANSI streams with frames in flight (ycge_render_frame_async_ansi)
     def RenderAsyncAnsi(self, slot: int, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                         clear_screen: bool = False, rgb: bool = False, delta: bool = False, merge_gap: int = 3, tolerance: int = 0,
@@ -1434,6 +1455,54 @@ class VideoRenderer:
         with RaytraceRenderer.TryFlipAndBlitAnsiQuadDelta: (bytes, info) or (bytes, info, SDR array) with sdr=True."""
         return self._ansi_call(self.L.ycge_video_blit_ansi_quad_delta, frame, console_width, console_height, viewport, default_fg, default_bg, clear_screen, sdr,
                                rgb=True, delta=(merge_gap, tolerance, bool(keyframe), min_contrast))
+
+    # ---------------------------------------------------------------- sixel (ycge_video_blit_pixels / _sixel / _sixel_delta)
+    def TryFlipAndBlitPixels(self, frame, rgba: bool = True, index: bool = True, dither: bool = False, sdr: bool = False) -> dict:
+        """Every hi-res sample of the blit of `frame` as a pixel (ycge_video_blit_pixels): {name: array} for each output asked - "rgba"
+        (2 fbH ss, fbW ss, 4) uint8, the sRGB8 bytes of the Clamp01'd Lanczos sample with alpha 255; "index" (2 fbH ss, fbW ss) uint8, its
+        register in the sixel cube (ordered 4 x 4 dither on request); "sdr" as TryFlipAndBlit's, bit for bit.  No state is touched."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        W, H = self.fbW * self.ss, 2 * self.fbH * self.ss
+        shapes = {"sdr": ((self.fbH, self.fbW, 2, 3), np.float32), "rgba": ((H, W, 4), np.uint8), "index": ((H, W), np.uint8)}
+        want = {"sdr": sdr, "rgba": rgba, "index": index}
+        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items() if want[k]}
+        p = lambda k, t: out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
+        self._r._check(self.L.ycge_video_blit_pixels(self.ctx, ptr, w, h, bpp, p("sdr", C.c_float), p("rgba", C.c_uint8), p("index", C.c_uint8), int(bool(dither))))
+        return out
+
+    def TryFlipAndBlitSixel(self, frame, viewport=(0, 0), clear_screen: bool = False, dither: bool = False, sdr: bool = False):
+        """The sixel stream of TryFlipAndBlitPixels' registers at cell `viewport` (ycge_video_blit_sixel): `bytes`, or (bytes, SDR array)
+        with sdr=True.  The next _delta call of any family returns a keyframe."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        buf, n = self._r._sixel_buffer(), C.c_size_t(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._r._check(self.L.ycge_video_blit_sixel(self.ctx, ptr, w, h, bpp, int(viewport[0]), int(viewport[1]), int(bool(clear_screen)), int(bool(dither)),
+                                                    buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size, C.byref(n), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
+        stream = buf[:n.value].tobytes()
+        return (stream, s) if sdr else stream
+
+    def TryFlipAndBlitSixelDelta(self, frame, viewport=(0, 0), clear_screen: bool = False, keyframe: bool = False, dither: bool = False, sdr: bool = False):
+        """The delta form of TryFlipAndBlitSixel (ycge_video_blit_sixel_delta), on the delta state this context shares with
+        RaytraceRenderer.TryFlipAndBlitSixelDelta: (bytes, info) or (bytes, info, SDR array) with sdr=True.  A still source gives the
+        header and the trailer alone."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        buf, n, info = self._r._sixel_buffer(), C.c_size_t(0), (C.c_uint32 * 4)()
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._r._check(self.L.ycge_video_blit_sixel_delta(self.ctx, ptr, w, h, bpp, int(viewport[0]), int(viewport[1]), int(bool(clear_screen)), int(bool(keyframe)),
+                                                          int(bool(dither)), buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size, C.byref(n), info,
+                                                          s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
+        stream = buf[:n.value].tobytes()
+        return (stream, tuple(info), s) if sdr else (stream, tuple(info))
+
+    def pixels_probe(self, frame, fb_width: int, fb_height: int, superSample: int = 1, dither: bool = False):
+        """k_video_pixels alone on a caller-given geometry (ycge_test_video_pixels), whatever this console's size: (rgba, index)."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        fn = self.L.ycge_test_video_pixels
+        fn.restype, fn.argtypes = abi.SIXEL_DELTA_HOOK_PROTOTYPES["ycge_test_video_pixels"]
+        W, H = fb_width * superSample, 2 * fb_height * superSample
+        rgba, index = np.zeros((H, W, 4), np.uint8), np.zeros((H, W), np.uint8)
+        self._r._check(fn(self.ctx, ptr, w, h, bpp, int(fb_width), int(fb_height), int(superSample), int(bool(dither)), rgba.ctypes.data, index.ctypes.data))
+        return rgba, index
 
     # ---------------------------------------------------------------- tests only
     def blit_quadrants_probe(self, frame, fb_width: int, fb_height: int, superSample: int = 2):
