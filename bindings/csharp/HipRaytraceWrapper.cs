@@ -50,6 +50,9 @@
 //                The stream buffer is pageable memory of the bound's size (INTEGRATION.md section 8.6).  SixelDelta: the delta form
 //                (ycge_render_frame_sixel_delta) - after the first picture a frame repaints only the bands and columns whose registers
 //                changed, on the delta state the context shares with Video mode (HipVideoWrapper) and the ANSI delta calls.
+//                SixelAdaptivePalette: up to 256 median-cut registers built on the device from the picture (ycge_render_frame_sixel_palette)
+//                in place of the cube - no dither, no delta form; SixelHoldPalette keeps the palette of the first frame (hold = 1) so that
+//                a picture at rest does not shimmer, and SixelRebuildPalette() asks the next frame for a new one.
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -80,6 +83,8 @@ public sealed class HipRaytraceOptions
     public bool SixelGraphics = false;                        // DeviceAnsiStream: the frame as a sixel stream, a pixel a hi-res sample (any superSample, no FrameLate, no delta)
     public bool SixelDither = false;                          // ... with the ordered 4 x 4 dither of the quantiser
     public bool SixelDelta = false;                           // ... and as delta streams: only the bands and columns that changed are repainted
+    public bool SixelAdaptivePalette = false;                 // ... under an adaptive palette of up to 256 median-cut registers in place of the cube (no dither, no delta)
+    public bool SixelHoldPalette = false;                     // ... which is kept from frame to frame (hold = 1) until SixelRebuildPalette() asks for a new one
     public HipGeneratedWorld GeneratedWorld;                  // chunks that come from the generator are made on the device (ycge_scene_generate_grids)
 }
 
@@ -186,6 +191,8 @@ public partial class RaytraceEntity
         private readonly int ansiMinContrast;
         private readonly bool sixel, sixelDither;   // SixelGraphics: ycge_render_frame_sixel in place of every stream form
         private readonly bool sixelDelta;           // ... SixelDelta: ycge_render_frame_sixel_delta
+        private readonly bool sixelPalette, sixelHold;   // ... SixelAdaptivePalette / SixelHoldPalette: ycge_render_frame_sixel_palette
+        private bool sixelRebuild;                  // ... the next frame builds its palette whatever sixelHold says
         private bool sixelBufOwned;                 // ... ansiBuf is pageable memory of this wrapper (Marshal), not the library's page-locked memory
         private bool inFlight;                      // FrameLate: a frame queued by the last TryFlipAndBlit has not been waited for yet
         private FlatScene uploaded;                 // what the device holds (records only; its pins are released after the upload)
@@ -218,6 +225,8 @@ public partial class RaytraceEntity
             ansiRgb |= ansiQuad;                    // (the quadrant streams are 24-bit ones: their bound is the 24-bit bound)
             sixel = ansi != null && options.SixelGraphics; sixelDither = sixel && options.SixelDither; sixelDelta = sixel && options.SixelDelta;
             if (sixel && (options.FrameLate || options.DeviceAnsiDelta || options.QuadrantGlyphs)) throw new ArgumentException("SixelGraphics has no FrameLate, delta or quadrant form");
+            sixelPalette = sixel && options.SixelAdaptivePalette; sixelHold = sixelPalette && options.SixelHoldPalette;
+            if (sixelPalette && (sixelDither || sixelDelta)) throw new ArgumentException("SixelAdaptivePalette has no dither and no delta form");
             frameLate = options != null && options.FrameLate && cfg.NDevices <= 1;      // (frames in flight are the single-device form)
             deviceColors = options != null && options.DeviceChexelColors;
             generated = options?.GeneratedWorld;
@@ -309,18 +318,29 @@ public partial class RaytraceEntity
             ansi.ClearPending = false;
         }
 
+        /// <summary>SixelHoldPalette: the next frame builds a new palette from its picture (a cut, a new scene, every N frames)</summary>
+        public void SixelRebuildPalette() { sixelRebuild = true; }
+
         // SixelGraphics: one frame as the sixel stream of its hi-res samples at the framebuffer's viewport.  The bound is large against the streams
         // (74 MB for 1920 x 1072 pixels, streams of a few hundred KB): the buffer is pageable, so only the pages a stream reaches are ever backed
         private void RenderSixel(Framebuffer fb)
         {
-            Ycge.Check(ctx, Ycge.ycge_sixel_stream_bound(fbW * ss, 2 * fbH * ss, out UIntPtr bound));
+            UIntPtr bound;
+            if (sixelPalette) Ycge.Check(ctx, Ycge.ycge_sixel_palette_stream_bound(fbW * ss, 2 * fbH * ss, out bound));
+            else Ycge.Check(ctx, Ycge.ycge_sixel_stream_bound(fbW * ss, 2 * fbH * ss, out bound));
             if ((ulong)bound > ansiCap)
             {
                 FreeAnsiBuf();
                 ansiBuf = (byte*)System.Runtime.InteropServices.Marshal.AllocHGlobal(checked((IntPtr)(long)(ulong)bound)); sixelBufOwned = true; ansiCap = (ulong)bound;
             }
             UIntPtr len;
-            if (sixelDelta)
+            if (sixelPalette)
+            {
+                Ycge.Check(ctx, Ycge.ycge_render_frame_sixel_palette(ctx, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, sixelHold && !sixelRebuild ? 1 : 0, ansiBuf,
+                                                                     (UIntPtr)ansiCap, &len, null, null, null, null));
+                sixelRebuild = false;
+            }
+            else if (sixelDelta)
                 Ycge.Check(ctx, Ycge.ycge_render_frame_sixel_delta(ctx, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, 0, sixelDither ? 1 : 0, ansiBuf, (UIntPtr)ansiCap, &len,
                                                                    null, null, null));
             else

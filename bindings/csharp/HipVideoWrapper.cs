@@ -15,7 +15,8 @@
 // glyph family and, with DeviceAnsiDelta, the quadrant family's delta state: the first video frame behind a traced one is a delta, not a keyframe.
 // SixelGraphics / SixelDither / SixelDelta: the film per pixel (ycge_video_blit_sixel / _sixel_delta), so that a host with SixelGraphics on keeps
 // its presenter through the mode switch; with SixelDelta a paused film costs the header and the trailer, and the first video frame behind a
-// traced one is a delta.  INTEGRATION.md sections 8.6 and 9.
+// traced one is a delta.  SixelAdaptivePalette / SixelHoldPalette: the adaptive palette's form (ycge_video_blit_sixel_palette) on the palette the
+// context's frames share - no dither, no delta.  INTEGRATION.md sections 8.6 and 9.
 using System;
 using ConsoleGame.RayTracing;
 using ConsoleGame.RayTracing.Native;
@@ -45,6 +46,8 @@ public partial class RaytraceEntity
         private readonly int ansiMinContrast;
         private readonly bool sixel, sixelDither, sixelDelta;   // HipRaytraceOptions.SixelGraphics: the sixel forms in place of every stream form
         private bool sixelBufOwned;                 // ... ansiBuf is pageable memory of this wrapper (Marshal), not the library's page-locked memory
+        private readonly bool sixelPalette, sixelHold;   // HipRaytraceOptions.SixelAdaptivePalette / SixelHoldPalette: ycge_video_blit_sixel_palette
+        private bool sixelRebuild;                  // ... the next frame builds its palette whatever sixelHold says
 
         /// <summary>sharedContext: the context of the raytrace wrapper of the same console, whose geometry must be fb's and superSample's
         /// (IntPtr.Zero: a context of this wrapper's own).</summary>
@@ -61,6 +64,8 @@ public partial class RaytraceEntity
             ansiRgb |= ansiQuad;                    // (the quadrant streams are 24-bit ones: their bound is the 24-bit bound)
             sixel = ansi != null && options.SixelGraphics; sixelDither = sixel && options.SixelDither; sixelDelta = sixel && options.SixelDelta;
             if (sixel && (options.DeviceAnsiDelta || options.QuadrantGlyphs)) throw new ArgumentException("SixelGraphics has no ANSI delta or quadrant form");
+            sixelPalette = sixel && options.SixelAdaptivePalette; sixelHold = sixelPalette && options.SixelHoldPalette;
+            if (sixelPalette && (sixelDither || sixelDelta)) throw new ArgumentException("SixelAdaptivePalette has no dither and no delta form");
             deviceColors = options != null && options.DeviceChexelColors;
             if (sharedContext != IntPtr.Zero)
             {
@@ -166,18 +171,29 @@ public partial class RaytraceEntity
                 }
         }
 
+        /// <summary>SixelHoldPalette: the next frame builds a new palette from its picture (a cut in the film, every N frames)</summary>
+        public void SixelRebuildPalette() { sixelRebuild = true; }
+
         // SixelGraphics: the frame as the sixel stream of the blit's hi-res samples at the framebuffer's viewport; the buffer is pageable memory of
         // the bound's size, as HipRaytraceWrapper's
         private void BlitSixel(Framebuffer fb, IntPtr frame, int srcW, int srcH, int bpp)
         {
-            Ycge.Check(ctx, Ycge.ycge_sixel_stream_bound(fbW * ss, 2 * fbH * ss, out UIntPtr bound));
+            UIntPtr bound;
+            if (sixelPalette) Ycge.Check(ctx, Ycge.ycge_sixel_palette_stream_bound(fbW * ss, 2 * fbH * ss, out bound));
+            else Ycge.Check(ctx, Ycge.ycge_sixel_stream_bound(fbW * ss, 2 * fbH * ss, out bound));
             if ((ulong)bound > ansiCap)
             {
                 FreeAnsiBuf();
                 ansiBuf = (byte*)System.Runtime.InteropServices.Marshal.AllocHGlobal(checked((IntPtr)(long)(ulong)bound)); sixelBufOwned = true; ansiCap = (ulong)bound;
             }
             UIntPtr len;
-            if (sixelDelta)
+            if (sixelPalette)
+            {
+                Ycge.Check(ctx, Ycge.ycge_video_blit_sixel_palette(ctx, frame, srcW, srcH, bpp, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, sixelHold && !sixelRebuild ? 1 : 0,
+                                                                   ansiBuf, (UIntPtr)ansiCap, &len, null, null, null));
+                sixelRebuild = false;
+            }
+            else if (sixelDelta)
                 Ycge.Check(ctx, Ycge.ycge_video_blit_sixel_delta(ctx, frame, srcW, srcH, bpp, fb.ViewportX, fb.ViewportY, ansi.ClearPending ? 1 : 0, 0, sixelDither ? 1 : 0, ansiBuf,
                                                                  (UIntPtr)ansiCap, &len, null, null));
             else

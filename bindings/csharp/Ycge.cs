@@ -401,6 +401,22 @@ namespace ConsoleGame.RayTracing.Native
                                                                               uint* outInfo, float* outTopBottomSdr);
         [DllImport(Lib)] public static extern int ycge_sixel_encode_delta_host(byte* prevIndex, byte* index, int pxW, int pxH, int viewportX, int viewportY, byte* outStream,
                                                                                UIntPtr capacity, UIntPtr* outLen, uint* outInfo);
+        // the adaptive sixel palette (found by symbol lookup, ABI stays 10): up to 256 median-cut registers built on the device from the picture at hand
+        // (hold 0) or kept from the last build (hold 1); outPalette 256 x RGBA8 and outCount may be null; the rule and the stream in plain C (no context)
+        [DllImport(Lib)] public static extern int ycge_sixel_palette_stream_bound(int pxW, int pxH, out UIntPtr bytes);
+        [DllImport(Lib)] public static extern int ycge_render_frame_sixel_palette(IntPtr ctx, int viewportX, int viewportY, int clearScreen, int hold, byte* outStream,
+                                                                                  UIntPtr capacity, UIntPtr* outLen, byte* outPalette, int* outCount, float* outTopBottomSdr,
+                                                                                  YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_video_blit_sixel_palette(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, int viewportX, int viewportY,
+                                                                                int clearScreen, int hold, byte* outStream, UIntPtr capacity, UIntPtr* outLen, byte* outPalette,
+                                                                                int* outCount, float* outTopBottomSdr);
+        [DllImport(Lib)] public static extern int ycge_render_frame_pixels_palette(IntPtr ctx, float* outTopBottomSdr, byte* outRgba, byte* outIndex, int hold, byte* outPalette,
+                                                                                   int* outCount, YFrameStats* stats);
+        [DllImport(Lib)] public static extern int ycge_video_blit_pixels_palette(IntPtr ctx, IntPtr frame, int srcW, int srcH, int bytesPerPixel, float* outTopBottomSdr,
+                                                                                 byte* outRgba, byte* outIndex, int hold, byte* outPalette, int* outCount);
+        [DllImport(Lib)] public static extern int ycge_sixel_palette_host(byte* rgba, int pxW, int pxH, byte* outIndex, byte* outPalette, byte* outPct, int* outCount);
+        [DllImport(Lib)] public static extern int ycge_sixel_encode_palette_host(byte* index, byte* pct, int count, int pxW, int pxH, int viewportX, int viewportY, int clearScreen,
+                                                                                 byte* outStream, UIntPtr capacity, UIntPtr* outLen);
         // the console's other framebuffers for every stream call above (found by symbol lookup, ABI stays 10); YConsoleLayer, YChexel and
         // HipConsoleLayers: bindings/csharp/YcgeConsole.cs
         [DllImport(Lib)] public static extern int ycge_console_set_layers(IntPtr ctx, YConsoleLayer* layers, int n, int raytraceAt);

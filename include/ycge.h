@@ -995,7 +995,7 @@ int ycge_render_frame_ansi_quad_delta(ycge_ctx *ctx, int32_t console_w, int32_t 
  *   a NULL stream or length; capacity below the bound; a negative viewport_x or viewport_y; dither outside 0..1; all destinations NULL (the
  *   planes call); whatever ycge_render_frame_chexels refuses - peer contexts, RCCL with lean slabs.
  *   Not offered: frames in flight; layers composed into the
- *   picture; a grey ramp or an adaptive palette; pixel replication to scale the image; the kitty graphics protocol (the out_rgba plane of
+ *   picture; a grey ramp; pixel replication to scale the image; the kitty graphics protocol (the out_rgba plane of
  *   ycge_render_frame_pixels is what a host would base64 for it). */
 int ycge_sixel_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes);
 int ycge_render_frame_pixels(ycge_ctx *ctx, float *out_top_bottom_sdr /* may be NULL */, uint8_t *out_rgba /* W x H RGBA8, may be NULL */,
@@ -1053,6 +1053,67 @@ int ycge_video_blit_sixel_delta(ycge_ctx *ctx, const uint8_t *frame, int32_t src
                                 size_t *out_len, uint32_t *out_info /* 4 words or NULL */, float *out_top_bottom_sdr /* may be NULL */);
 int ycge_sixel_encode_delta_host(const uint8_t *prev_index, const uint8_t *index, int32_t px_w, int32_t px_h, int32_t viewport_x, int32_t viewport_y,
                                  uint8_t *out_stream, size_t capacity, size_t *out_len, uint32_t *out_info /* 4 words or NULL */);
+/* --- Adaptive sixel palette: median-cut registers built on the device, a second palette for the sixel streams of frames and Video mode.  The
+ * cube's levels are 51 apart and need the ordered dither to hide their banding; these registers are cut from the picture at hand.  Added
+ * after ABI 10 without changing it, as the blocks above; found by symbol lookup.  No cube call, struct or stream byte changes.  The reference
+ * has no such presenter, so these rules define the result.  Everything is integer arithmetic on the RGBA8 plane of ycge_render_frame_pixels
+ * (ycge_video_blit_pixels), W x H pixels.
+ *   Bins.  Pixel bytes (r, g, b) fall in bin (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3): 32 768 bins with coordinates 0..31 on three axes.
+ *   A bin holds its pixel count and the three sums of the actual bytes, all uint32: W * H > 2^24 is refused so that the sums fit.
+ *   Boxes.  Boxes partition the whole 32^3 bin cube, empty bins included.  Start with box 0, the whole cube, n = 1.  Eight passes; a pass looks
+ *   at the boxes 0 .. n0 - 1 that exist at its start, in index order.  For box b the occupied extent on an axis is the largest minus the
+ *   smallest coordinate among the box's bins with a count above zero; axis a is the one with the largest extent, ties to the first of r, g,
+ *   b; the box splits if that extent is at least 1.  With omin, omax its occupied bounds on a, m[t] the pixel count at coordinate t and total
+ *   their sum, the cut c is the smallest t in omin .. omax - 1 with 2 (m[omin] + .. + m[t]) >= total, or omax - 1 if there is none.  Bins of
+ *   the box with coordinate <= c stay box b, the others become box n0 + rank, rank the number of boxes below b that split in this pass.
+ *   After the pass n = n0 + the number of splits; both halves hold pixels.  After eight passes n <= 256 is the number of registers.
+ *   Register colour.  Box i with pixel count k and byte sums S has the bytes m = (2 S + k) / (2 k) per channel and the sixel percentages
+ *   (200 m + 255) / 510; it is defined in the stream as #i;2;pr;pg;pb in canonical decimal.  Only registers 0 .. n - 1 are defined, ascending.
+ *   Register plane.  index(x, y) = the box of the pixel's bin.
+ *   Stream.  ycge_render_frame_sixel's, rule for rule - ESC[2J where asked, the cursor, ESC P q, the raster attributes, the bands, their lines in
+ *   ascending register order, the runs, ESC \ - with these register definitions in place of the cube's 216.
+ *   Known answer.  The 6 x 12 picture whose rows 0..5 are (0, 0, 0) and rows 6..11 (255, 255, 255), at viewport (0, 0) without clear:
+ *   ESC[1;1H ESC P q "1;1;6;12 #0;2;0;0;0#1;2;100;100;100 #0!6~-#1!6~ ESC \ (without the spaces).
+ *   Bound.  ycge_sixel_palette_stream_bound(W, H) = 4700 + ceil(H / 6) min(256, 6 W) (W + 5): 256 definitions of at most 18 bytes are 4608
+ *   bytes and the prefix keeps the 70 bytes of slack the cube's 3200 has over its 3130; a line is still #ddd, W characters and a separator.
+ *   Its refusals are ycge_sixel_stream_bound's.
+ *   Hold.  hold = 0 builds the palette from this call's picture and keeps it in the context: the bin-to-box table, the register definitions
+ *   and n.  hold = 1 maps this picture through the kept palette and skips the build - every bin has a box, so the map is total, and the
+ *   colours of a picture at rest do not shimmer with TAA's +-1; with no kept palette hold = 1 builds one.  The palette is independent of
+ *   geometry: ycge_resize keeps it, frames and video share it (as they share the delta state), the hooks of ycge_hooks.h read and replace it
+ *   too.  A failure behind the refusals drops it.
+ *   State.  A stream call paints over the cells and over the cube's picture: it invalidates the context's delta state exactly as a plain
+ *   _sixel call does.  The two planes calls leave the delta state alone.
+ *   ycge_render_frame_sixel_palette / ycge_video_blit_sixel_palette: the stream; out_palette 256 x RGBA8 of the bytes m (alpha 255, unused
+ *   entries zero) and out_count n, either may be NULL.  The SDR and the frame state are ycge_render_frame's (ycge_video_blit's), bit for bit.
+ *   ycge_render_frame_pixels_palette / ycge_video_blit_pixels_palette: the planes.  out_rgba is the cube calls' plane, out_index holds the
+ *   adaptive registers, the palette and count come with it; any subset of the destinations may be NULL, not all.
+ *   ycge_sixel_palette_host (out_pct: 256 x 3 percentages, unused entries zero; any output may be NULL, not all) and
+ *   ycge_sixel_encode_palette_host (registers below count, count 1..256, percentages 0..100): the rule and the stream in plain C++, no
+ *   context and no device - the kernels' yardstick, and with YCGE_SIXEL_HOST=1 what the stream calls run on the RGBA plane read back.
+ *   Refusals: those of the cube calls - decided before any device work, nothing written, the frame state, the delta state and the kept
+ *   palette as they were, the message naming the value - plus hold outside 0..1 and W * H > 2^24.
+ *   Not offered: a dither parameter (the point of the palette is not to need one); the delta form under an adaptive palette (registers
+ *   change meaning between builds, so the diff would have to compare colours); a grey ramp; frames in flight. */
+int ycge_sixel_palette_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes);
+int ycge_render_frame_sixel_palette(ycge_ctx *ctx, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t hold, uint8_t *out_stream,
+                                    size_t capacity, size_t *out_len, uint8_t *out_palette /* 256 x RGBA8, may be NULL */,
+                                    int32_t *out_count /* may be NULL */, float *out_top_bottom_sdr /* may be NULL */, ycge_frame_stats *stats);
+int ycge_video_blit_sixel_palette(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t viewport_x,
+                                  int32_t viewport_y, int32_t clear_screen, int32_t hold, uint8_t *out_stream, size_t capacity, size_t *out_len,
+                                  uint8_t *out_palette /* 256 x RGBA8, may be NULL */, int32_t *out_count /* may be NULL */,
+                                  float *out_top_bottom_sdr /* may be NULL */);
+int ycge_render_frame_pixels_palette(ycge_ctx *ctx, float *out_top_bottom_sdr /* may be NULL */, uint8_t *out_rgba /* W x H RGBA8, may be NULL */,
+                                     uint8_t *out_index /* W*H registers, may be NULL */, int32_t hold, uint8_t *out_palette /* 256 x RGBA8, may be NULL */,
+                                     int32_t *out_count /* may be NULL */, ycge_frame_stats *stats);
+int ycge_video_blit_pixels_palette(ycge_ctx *ctx, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel,
+                                   float *out_top_bottom_sdr /* may be NULL */, uint8_t *out_rgba /* W x H RGBA8, may be NULL */,
+                                   uint8_t *out_index /* W*H registers, may be NULL */, int32_t hold, uint8_t *out_palette /* 256 x RGBA8, may be NULL */,
+                                   int32_t *out_count /* may be NULL */);
+int ycge_sixel_palette_host(const uint8_t *rgba, int32_t px_w, int32_t px_h, uint8_t *out_index, uint8_t *out_palette /* 256 x RGBA8 */,
+                            uint8_t *out_pct /* 256 x 3 */, int32_t *out_count);
+int ycge_sixel_encode_palette_host(const uint8_t *index, const uint8_t *pct /* count x 3 */, int32_t count, int32_t px_w, int32_t px_h, int32_t viewport_x,
+                                   int32_t viewport_y, int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len);
 /* --- ANSI streams with frames in flight: the four frame forms above - ycge_render_frame_ansi, _ansi_delta, _ansi_rgb, _ansi_rgb_delta - queued
  * as ycge_render_frame_async_sdr queues a frame.  The synchronous calls read the stream's length on the host and copy exactly that many
  * bytes, which takes a synchronisation inside the call; here a kernel behind the stream's kernels (k_ansi_deliver, csrc/ycge_ansi_flight.hip)

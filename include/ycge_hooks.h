@@ -175,6 +175,14 @@ int ycge_test_video_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int
                            int32_t dither, uint8_t *out_rgba, uint8_t *out_index);
 int ycge_test_sixel_delta_stream(ycge_ctx *c, const uint8_t *prev, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, uint8_t *out,
                                  size_t capacity, size_t *out_len, uint32_t *out_info);
+/* the adaptive palette (csrc/ycge_sixel_palette.hip; tests/test_gpu_sixel_palette.py).  ycge_test_sixel_palette: the palette stage alone on a
+ * caller's RGBA8 plane of any W x H <= 2^24 pixels: out_index W*H registers, out_palette 256 x RGBA8, out_pct 256 x 3, out_count, any of them
+ * NULL.  ycge_test_sixel_palette_stream: the stage and the 256-register encoder's kernels.  Planes and encoder buffers of their own, no frame
+ * or delta state - but `hold` reads the context's kept palette and a success replaces it, as the _palette calls do */
+int ycge_test_sixel_palette(ycge_ctx *c, const uint8_t *rgba, int32_t W, int32_t H, int32_t hold, uint8_t *out_index, uint8_t *out_palette, uint8_t *out_pct,
+                            int32_t *out_count);
+int ycge_test_sixel_palette_stream(ycge_ctx *c, const uint8_t *rgba, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, int32_t hold, uint8_t *out,
+                                   size_t capacity, size_t *out_len);
 
 /* ---- read-outs for tests and profiles (a context, a destination, a capacity; YCGE_OK or an error code) */
 int ycge_debug_scene_bvh_stats(ycge_ctx *c, int64_t *out6);          /* how ycge_scene_update_objects built the tree: device / fallback / host builds, us, sort fallbacks, depth */

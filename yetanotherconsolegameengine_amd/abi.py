@@ -414,6 +414,20 @@ _PROTOTYPES = {
                                               C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "ycge_sixel_encode_delta_host": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t,
                                                C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    # the adaptive sixel palette: the bound; the stream of a frame / a video source (viewport, clear, hold; palette 256 x RGBA8 and count, either None);
+    # the planes (SDR, RGBA, registers, hold, palette, count); the rule and the stream in plain C++ (no context)
+    "ycge_sixel_palette_stream_bound": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "ycge_render_frame_sixel_palette": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(FrameStats)]),
+    "ycge_video_blit_sixel_palette": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "ycge_render_frame_pixels_palette": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_uint8),
+                                                   C.POINTER(C.c_int32), C.POINTER(FrameStats)]),
+    "ycge_video_blit_pixels_palette": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint8),
+                                                 C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "ycge_sixel_palette_host": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "ycge_sixel_encode_palette_host": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     # (req: C.byref(abi.AnsiAsync); out_result: the address of an abi.AnsiAsyncResult in page-locked memory)
     "ycge_render_frame_async_ansi": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]),
     # (info: a ycge_obj_info, passed with C.byref(abi.ObjInfo))
@@ -539,6 +553,14 @@ SIXEL_DELTA_HOOK_PROTOTYPES = {
                                          C.c_void_p]),
     "ycge_test_sixel_delta_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
                                                C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+}
+# ... and of the adaptive palette (tests/test_gpu_sixel_palette.py): the palette stage alone on an RGBA plane (W, H, hold; registers, palette, percentages,
+# count, any None), and the stage with the 256-register encoder (W, H, vx, vy, clear, hold)
+SIXEL_PALETTE_HOOK_PROTOTYPES = {
+    "ycge_test_sixel_palette": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                          C.POINTER(C.c_int32)]),
+    "ycge_test_sixel_palette_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
+                                                 C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 # test hook of the delivery of a stream with frames in flight (csrc/ycge_ansi.cpp), bound where it is used (tests/test_gpu_ansi_flight.py): src,
 # n_src, length, capacity, keyframe, counts (3 uint32), groups, out_stream, out_result (an abi.AnsiAsyncResult in page-locked memory)

@@ -21,7 +21,7 @@ LIB = LIB_DIR / "libycge_hip.so"
 SOURCES = ["ycge_host.cpp", "ycge_scene.cpp", "ycge_frame.cpp", "ycge_post_host.cpp", "ycge_resident.cpp", "ycge_accel.cpp", "ycge_query.cpp", "ycge_chexel.cpp", "ycge_ansi.cpp", "ycge_kernels.hip", "ycge_post.hip", "ycge_bvh_build.hip", "ycge_query.hip",
            "ycge_chexel.hip", "ycge_ansi.hip", "ycge_ansi_rgb.hip", "ycge_ansi_flight.hip", "ycge_grid_encode.cpp", "ycge_grid_encode.hip", "ycge_video.cpp", "ycge_video.hip", "ycge_mesh_bvh.cpp", "ycge_mesh_pool.cpp", "ycge_mesh_bvh_build.hip", "ycge_mesh_emit.hip",
            "ycge_worldgen.cpp", "ycge_worldgen_scene.cpp", "ycge_worldgen.hip", "ycge_worldpregen.hip", "ycge_obj.cpp", "ycge_obj.hip", "ycge_obj_ground.hip",
-           "ycge_world_store.cpp", "ycge_world_store.hip", "ycge_grid_edit.cpp", "ycge_grid_edit.hip", "ycge_camera.cpp", "ycge_camera.hip", "ycge_sixel.cpp", "ycge_sixel.hip", "ycge_sixel_host.cpp"]
+           "ycge_world_store.cpp", "ycge_world_store.hip", "ycge_grid_edit.cpp", "ycge_grid_edit.hip", "ycge_camera.cpp", "ycge_camera.hip", "ycge_sixel.cpp", "ycge_sixel.hip", "ycge_sixel_host.cpp", "ycge_sixel_palette.hip"]
 HEADERS = ["ycge_ctx.h", "ycge_own.h", "ycge_device.h", "ycge_accel.h", "ycge_math.h", "ycge_mesh_pool.h", "ycge_rt.hip.h", "ycge_coop.hip.h", "ycge_anyhit.hip.h", "ycge_keysort.h", "ycge_grid_encode.h", "ycge_bvh_split.hip.h", "ycge_worldgen.h", "ycge_worldgen_host.h", "ycge_worldgen_cells.h", "ycge_obj.h", "ycge_obj_box.hip.h", "ycge_ansi_cells.hip.h", "ycge_ansi_layers.h", "ycge_world_store.h", "ycge_grid_edit.h", "ycge_camera_physics.h", "ycge_tonemap.hip.h", "ycge_srgb8.hip.h", "ycge_sixel_quantise.hip.h", "ycge_video_sample.hip.h", "ycge_sixel_host.h"]
 ARCH = "gfx950"
 

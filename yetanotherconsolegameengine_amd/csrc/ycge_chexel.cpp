@@ -344,6 +344,79 @@ try {
 }
 catch (...) { return ycge_host::abi_catch(c); }
 
+// The adaptive sixel palette (the bodies: ycge_sixel.cpp; the plain C++: ycge_sixel_host.cpp) and its two hooks
+int ycge_sixel_palette_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes)
+try {
+    return sixel_palette_stream_bound(px_w, px_h, bytes);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+int ycge_sixel_palette_host(const uint8_t *rgba, int32_t px_w, int32_t px_h, uint8_t *out_index, uint8_t *out_palette, uint8_t *out_pct, int32_t *out_count)
+try {
+    return sixel_palette_host(rgba, px_w, px_h, out_index, out_palette, out_pct, out_count);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+int ycge_sixel_encode_palette_host(const uint8_t *index, const uint8_t *pct, int32_t count, int32_t px_w, int32_t px_h, int32_t viewport_x, int32_t viewport_y,
+                                   int32_t clear_screen, uint8_t *out_stream, size_t capacity, size_t *out_len)
+try {
+    return sixel_encode_palette_host(index, pct, count, px_w, px_h, viewport_x, viewport_y, clear_screen, out_stream, capacity, out_len);
+}
+catch (...) { return ycge_host::abi_catch(nullptr); }
+
+int ycge_render_frame_sixel_palette(ycge_ctx *c, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t hold, uint8_t *out_stream, size_t capacity,
+                                    size_t *out_len, uint8_t *out_palette, int32_t *out_count, float *out_top_bottom_sdr, ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_frame_palette(c, "ycge_render_frame_sixel_palette", true, viewport_x, viewport_y, clear_screen, hold, out_stream, capacity, out_len, nullptr, nullptr,
+                               out_palette, out_count, out_top_bottom_sdr, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_render_frame_pixels_palette(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_rgba, uint8_t *out_index, int32_t hold, uint8_t *out_palette, int32_t *out_count,
+                                     ycge_frame_stats *st)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_frame_palette(c, "ycge_render_frame_pixels_palette", false, 0, 0, 0, hold, nullptr, 0, nullptr, out_rgba, out_index, out_palette, out_count,
+                               out_top_bottom_sdr, st);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_video_blit_sixel_palette(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, int32_t viewport_x, int32_t viewport_y,
+                                  int32_t clear_screen, int32_t hold, uint8_t *out_stream, size_t capacity, size_t *out_len, uint8_t *out_palette, int32_t *out_count,
+                                  float *out_top_bottom_sdr)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_video_palette(c, "ycge_video_blit_sixel_palette", true, frame, src_w, src_h, bytes_per_pixel, viewport_x, viewport_y, clear_screen, hold, out_stream,
+                               capacity, out_len, nullptr, nullptr, out_palette, out_count, out_top_bottom_sdr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_video_blit_pixels_palette(ycge_ctx *c, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bytes_per_pixel, float *out_top_bottom_sdr, uint8_t *out_rgba,
+                                   uint8_t *out_index, int32_t hold, uint8_t *out_palette, int32_t *out_count)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_video_palette(c, "ycge_video_blit_pixels_palette", false, frame, src_w, src_h, bytes_per_pixel, 0, 0, 0, hold, nullptr, 0, nullptr, out_rgba, out_index,
+                               out_palette, out_count, out_top_bottom_sdr);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_test_sixel_palette(ycge_ctx *c, const uint8_t *rgba, int32_t W, int32_t H, int32_t hold, uint8_t *out_index, uint8_t *out_palette, uint8_t *out_pct,
+                            int32_t *out_count)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_test_palette(c, rgba, W, H, hold, out_index, out_palette, out_pct, out_count);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
+int ycge_test_sixel_palette_stream(ycge_ctx *c, const uint8_t *rgba, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, int32_t hold, uint8_t *out,
+                                   size_t capacity, size_t *out_len)
+try {
+    if (!c) return YCGE_ERR_INVALID_ARG;
+    return sixel_test_palette_stream(c, rgba, W, H, vx, vy, clear, hold, out, capacity, out_len);
+}
+catch (...) { return ycge_host::abi_catch(c); }
+
 int ycge_render_frame_async_chexels(ycge_ctx *c, float *out_top_bottom_sdr, uint8_t *out_color16, uint8_t *out_ansi, uint8_t *out_rgba)
 try {
     if (!c) return YCGE_ERR_INVALID_ARG;

@@ -117,6 +117,10 @@ int ycge_launch_quadrant_fit(const float *quad, int fbW, int fbH, const uint8_t 
                              hipStream_t stream);
 int ycge_launch_sixel_pixels(const float *hdr, int W, int H, float gamma, float saturation, float vibrance, const void *state, const uint8_t *tables, int dither,
                              uint8_t *rgba, uint8_t *index, int compute_units, hipStream_t stream);
+int ycge_launch_sixel_encode_palette(const uint8_t *index, int W, int H, uint32_t *last1, uint32_t *lines, uint32_t *line_bytes, uint32_t max_lines, uint32_t *meta,
+                                     const uint8_t *prefix, uint32_t prefix_bytes, const uint8_t *defs, const uint32_t *defs_bytes, uint8_t *out, uint32_t cap,
+                                     unsigned long long *res, int compute_units, hipStream_t stream);
+int ycge_launch_sixel_palette(const uint8_t *rgba, int W, int H, int build, uint32_t *hist, uint8_t *block, uint8_t *index, int compute_units, hipStream_t stream);
 int ycge_launch_sixel_encode(const uint8_t *index, int W, int H, uint32_t *last1, uint32_t *lines, uint32_t *line_bytes, uint32_t max_lines, uint32_t *meta,
                              const uint8_t *header, uint32_t header_bytes, uint8_t *out, uint32_t cap, unsigned long long *res, int compute_units, hipStream_t stream,
                              const uint8_t *prev = nullptr, uint32_t *span = nullptr);
@@ -518,7 +522,9 @@ struct FrameOutputs {
     // and with `stream` set the sixel stream of the registers at the viewport - its bytes are delivered behind the frame's synchronisation
     // A _sixel_delta call: dev_index, the held plane the registers go to in place of SixelState::index, and with dev_prev the plane the
     // terminal shows - the stream is the delta against it (dev_prev NULL: the call's keyframe, the full stream)
-    struct Pixels { uint8_t *rgba; uint8_t *index; int32_t dither; bool stream; int32_t vx, vy; bool clear; uint8_t *dev_index = nullptr; const uint8_t *dev_prev = nullptr; };
+    // pal (the _palette calls): 0 the cube's registers; 1 the adaptive palette's, through the palette the context keeps; 2 through a palette
+    // built from this picture - the RGBA plane is always written, the registers are k_pal_remap's
+    struct Pixels { uint8_t *rgba; uint8_t *index; int32_t dither; bool stream; int32_t vx, vy; bool clear; uint8_t *dev_index = nullptr; const uint8_t *dev_prev = nullptr; int32_t pal = 0; };
     const Pixels *pixels = nullptr;
     const AnsiRequest *ansi = nullptr;                 // the ANSI stream asked for (its encode keeps the pairs - 24-bit colour: the RGBA plane - on the device only)
     bool keyframe = true;                              // ... runs the full stream's kernels (a _delta call: what its DeltaCall decided)
@@ -596,6 +602,14 @@ struct SixelState {
     DevBuf<unsigned long long> res;                    // the stream's length as k_sixel_scan wrote it ...
     PinnedBuf res_host;                                // ... and the page-locked word it is copied to
     PinnedBuf stage;                                   // page-locked staging of pageable destinations
+    // The adaptive palette (the _palette calls; kernels: ycge_sixel_palette.hip): the histogram, and the palette block - the kept palette
+    // (bin-to-box table, register definitions, n; layout: ycge_sixel_host.h) while pal_kept.  Independent of geometry: ycge_resize keeps it,
+    // frames and video share it; a failure behind a _palette call's refusals drops it.  pal_prefix: the stream's parts 1 to 4 on the device
+    DevBuf<uint32_t> pal_hist;
+    DevBuf<uint8_t> pal_block, pal_prefix;
+    bool pal_kept = false;
+    std::array<int32_t, 5> pal_prefix_key{{0, 0, 0, 0, 0}};
+    uint32_t pal_prefix_bytes = 0;
 };
 // what the video blits of one context hold (ycge_video.cpp): made by the first blit, grow-only; nothing a ray-traced frame reads
 struct VideoState {
@@ -1117,6 +1131,21 @@ int sixel_test_video_pixels(ycge_ctx *c, const uint8_t *frame, int32_t src_w, in
                             uint8_t *out_rgba, uint8_t *out_index);
 int sixel_test_delta_stream(ycge_ctx *c, const uint8_t *prev, const uint8_t *index, int32_t W, int32_t H, int32_t vx, int32_t vy, uint8_t *out, size_t capacity,
                             size_t *out_len, uint32_t *out_info);
+// ... and of the adaptive palette's: ycge_sixel_palette_stream_bound, the two host functions (no context), the frame and video calls (frame NULL: a
+// traced frame; out_stream NULL: the planes call) and the two hooks
+int sixel_palette_stream_bound(int32_t px_w, int32_t px_h, size_t *bytes);
+int sixel_palette_host(const uint8_t *rgba, int32_t W, int32_t H, uint8_t *out_index, uint8_t *out_palette, uint8_t *out_pct, int32_t *out_count);
+int sixel_encode_palette_host(const uint8_t *index, const uint8_t *pct, int32_t count, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, uint8_t *out,
+                              size_t capacity, size_t *out_len);
+int sixel_frame_palette(ycge_ctx *c, const char *fn, bool stream, int32_t viewport_x, int32_t viewport_y, int32_t clear_screen, int32_t hold, uint8_t *out_stream,
+                        size_t capacity, size_t *out_len, uint8_t *out_rgba, uint8_t *out_index, uint8_t *out_palette, int32_t *out_count, float *out_top_bottom_sdr,
+                        ycge_frame_stats *st);
+int sixel_video_palette(ycge_ctx *c, const char *fn, bool stream, const uint8_t *frame, int32_t src_w, int32_t src_h, int32_t bpp, int32_t viewport_x, int32_t viewport_y,
+                        int32_t clear_screen, int32_t hold, uint8_t *out_stream, size_t capacity, size_t *out_len, uint8_t *out_rgba, uint8_t *out_index,
+                        uint8_t *out_palette, int32_t *out_count, float *out_top_bottom_sdr);
+int sixel_test_palette(ycge_ctx *c, const uint8_t *rgba, int32_t W, int32_t H, int32_t hold, uint8_t *out_index, uint8_t *out_palette, uint8_t *out_pct, int32_t *out_count);
+int sixel_test_palette_stream(ycge_ctx *c, const uint8_t *rgba, int32_t W, int32_t H, int32_t vx, int32_t vy, int32_t clear, int32_t hold, uint8_t *out, size_t capacity,
+                              size_t *out_len);
 int ansi_enqueue(ycge_ctx *c, hipStream_t stream, const FrameOutputs &out, const uint8_t *d_plane);   // ycge_ansi.cpp: out.ansi's stream kernels behind the encode on the frame's plane (where out.plan puts it), and the length's copy
 // ycge_video.cpp: Video mode.  The refusals of a source frame; upload + k_video_blit on `stream` for a geometry (*d_sdr: its SDR array);
 // the SDR read-back (a pageable array: staged as run_post does it); the test hooks' bodies

@@ -10,6 +10,8 @@
 //   k_sixel_walk<0>    one wavefront a line: its byte count
 //   k_sixel_scan       the exclusive scan of the counts: every line's offset, the header, the trailer, the stream's length
 //   k_sixel_walk<1>    the same walk writes the bytes
+// The adaptive palette's streams (ycge_sixel_palette.hip) run the PAL instances of presence, lines and walk - 256 registers a band - and
+// k_sixel_scan_palette, which takes the length of the register definitions from a device word.
 // The delta stream (the contract: include/ycge.h at ycge_render_frame_sixel_delta) is the same five launches in their DELTA instances behind
 // k_sixel_diff, which gives every band the span of columns in which it differs from the plane the terminal shows: presence and the walk keep
 // to the span, the separators in front of a line count the unchanged bands it skips.  The full stream's instances are what they were.
@@ -29,7 +31,8 @@
 namespace {
 
 constexpr int kSixelBlock = 256;
-constexpr uint32_t kRegisters = 216;
+// the cube's 216 registers, or (PAL, the adaptive palette of ycge_sixel_palette.hip) up to 256: the second set of the encoder's instances
+template <bool PAL> __host__ __device__ constexpr uint32_t registers() { return PAL ? 256u : 216u; }
 constexpr uint32_t kPresenceTile = 1024;          // columns a workgroup of k_sixel_presence takes
 
 // one sample: its sRGB8 bytes and its register (the bytes-to-word-and-register tail: ycge_sixel_quantise.hip.h, k_video_pixels' too)
@@ -142,10 +145,11 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_diff(const uint8_t *__res
 // last1[band * 216 + c]: the column of the last pixel of register c in the band, plus 1 (zero before the launch).  A workgroup takes
 // kPresenceTile columns of one band: the tile's maxima in LDS, then one global atomic a colour present.  DELTA: of the band's span alone -
 // a register the band holds only outside its span gets no line, an unchanged band none at all
-template <bool DELTA>
+template <bool DELTA, bool PAL>
 __global__ __launch_bounds__(kSixelBlock) void k_sixel_presence(const uint8_t *__restrict__ index, uint32_t W, uint32_t H, uint32_t *__restrict__ last1,
                                                                 const uint32_t *__restrict__ span)
 {
+    constexpr uint32_t kRegisters = registers<PAL>();
     __shared__ uint32_t s_last[kRegisters];
     if (threadIdx.x < kRegisters) s_last[threadIdx.x] = 0;
     __syncthreads();
@@ -197,9 +201,11 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *w
 
 // one workgroup: lines[] = band << 8 | colour for every colour present, band-major and colour-ascending; meta[0] = how many.  A lane takes a
 // band: its place is the scan of the bands' counts
+template <bool PAL>
 __global__ __launch_bounds__(kSixelBlock) void k_sixel_lines(const uint32_t *__restrict__ last1, uint32_t n_bands, uint32_t max_lines, uint32_t *__restrict__ lines,
                                                              uint32_t *__restrict__ meta)
 {
+    constexpr uint32_t kRegisters = registers<PAL>();
     __shared__ uint32_t wsum[kSixelBlock / 64];
     uint32_t carry = 0;
     for (uint32_t base = 0; base < n_bands; base += kSixelBlock) {
@@ -226,12 +232,13 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_lines(const uint32_t *__r
 // DELTA: the line's sixels are zero left of its band's span[band] - the trips in front of that column's are not walked, the run of empty
 // columns opens at column 0 all the same - and its separators stand IN FRONT of it: '$' behind a line of the same band, else one '-' for
 // every band between the line before (the stream's first line: band 0) and its own, unchanged bands included; none behind the last line
-template <bool WRITE, bool DELTA>
+template <bool WRITE, bool DELTA, bool PAL>
 __global__ __launch_bounds__(kSixelBlock) void k_sixel_walk(const uint8_t *__restrict__ index, uint32_t W, uint32_t H, const uint32_t *__restrict__ last1,
                                                             const uint32_t *__restrict__ lines, const uint32_t *__restrict__ meta,
                                                             uint32_t *__restrict__ line_bytes, uint8_t *__restrict__ out, uint32_t cap,
                                                             const uint32_t *__restrict__ span)
 {
+    constexpr uint32_t kRegisters = registers<PAL>();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_lines = meta[0];
     const uint32_t waves = gridDim.x * (kSixelBlock / 64);
@@ -351,6 +358,31 @@ __global__ __launch_bounds__(kSixelBlock) void k_sixel_scan(uint32_t *__restrict
     }
 }
 
+// k_sixel_scan<false> for the adaptive palette's stream: the header is the host's prefix (parts 1 to 4) and behind it the register
+// definitions k_pal_build wrote on the device, *defs_bytes of them - the host never learns the header's length before the stream's
+__global__ __launch_bounds__(kSixelBlock) void k_sixel_scan_palette(uint32_t *__restrict__ line_bytes, const uint32_t *__restrict__ meta, const uint8_t *__restrict__ prefix,
+                                                                    uint32_t prefix_bytes, const uint8_t *__restrict__ defs, const uint32_t *__restrict__ defs_bytes,
+                                                                    uint8_t *__restrict__ out, uint32_t cap, unsigned long long *__restrict__ res)
+{
+    __shared__ uint32_t wsum[kSixelBlock / 64];
+    const uint32_t n_lines = meta[0], n_defs = defs_bytes[0];
+    unsigned long long carry = (unsigned long long)prefix_bytes + n_defs;
+    for (uint32_t base = 0; base < n_lines; base += kSixelBlock) {
+        const uint32_t t = base + threadIdx.x;
+        const uint32_t v = t < n_lines ? line_bytes[t] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_exclusive_scan(v, wsum, total);
+        if (t < n_lines) line_bytes[t] = (uint32_t)carry + ex;
+        carry += total;
+    }
+    for (uint32_t k = threadIdx.x; k < prefix_bytes; k += kSixelBlock)
+        if (k < cap) out[k] = prefix[k];
+    for (uint32_t k = threadIdx.x; k < n_defs; k += kSixelBlock)
+        if (prefix_bytes + k < cap) out[prefix_bytes + k] = defs[k];
+    if (threadIdx.x < 2 && carry + threadIdx.x < cap) out[carry + threadIdx.x] = (uint8_t)"\x1b\\"[threadIdx.x];
+    if (threadIdx.x == 0) res[0] = carry + 2ull;
+}
+
 } // namespace
 
 extern "C" {
@@ -385,6 +417,7 @@ int ycge_launch_sixel_encode(const uint8_t *index, int W, int H, uint32_t *last1
     if ((prev != nullptr) != (span != nullptr)) return (int)hipErrorInvalidValue;
     if (!index || !last1 || !lines || !line_bytes || !meta || !header || !out || !res || W <= 0 || H <= 0 || H > (1 << 24)) return (int)hipErrorInvalidValue;
     const uint32_t n_bands = ((uint32_t)H + 5u) / 6u;
+    constexpr uint32_t kRegisters = registers<false>();
     const uint64_t colours = 6ull * (uint32_t)W < kRegisters ? 6ull * (uint32_t)W : kRegisters;
     if ((uint64_t)n_bands * colours > max_lines || n_bands > 65535u) return (int)hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(last1, 0, (size_t)n_bands * kRegisters * sizeof(uint32_t), stream);
@@ -395,23 +428,51 @@ int ycge_launch_sixel_encode(const uint8_t *index, int W, int H, uint32_t *last1
         if (e == hipSuccess) e = hipMemsetAsync(span + n_bands, 0, (size_t)n_bands * sizeof(uint32_t), stream);
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL(k_sixel_diff, tiles, dim3(kSixelBlock), 0, stream, prev, index, (uint32_t)W, (uint32_t)H, span);
-        hipLaunchKernelGGL(k_sixel_presence<true>, tiles, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, span);
+        hipLaunchKernelGGL((k_sixel_presence<true, false>), tiles, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, span);
     } else {
-        hipLaunchKernelGGL(k_sixel_presence<false>, tiles, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, span);
+        hipLaunchKernelGGL((k_sixel_presence<false, false>), tiles, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, span);
     }
-    hipLaunchKernelGGL(k_sixel_lines, dim3(1), dim3(kSixelBlock), 0, stream, last1, n_bands, max_lines, lines, meta);
+    hipLaunchKernelGGL(k_sixel_lines<false>, dim3(1), dim3(kSixelBlock), 0, stream, last1, n_bands, max_lines, lines, meta);
     const uint32_t need = (max_lines + kSixelBlock / 64 - 1) / (kSixelBlock / 64);
     const uint32_t limit = (uint32_t)(compute_units > 0 ? compute_units : 256) * 8u;
     const dim3 grid(need < limit ? need : limit);
     if (prev) {
-        hipLaunchKernelGGL((k_sixel_walk<false, true>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
+        hipLaunchKernelGGL((k_sixel_walk<false, true, false>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
         hipLaunchKernelGGL(k_sixel_scan<true>, dim3(1), dim3(kSixelBlock), 0, stream, line_bytes, meta, header, header_bytes, out, cap, res, span, n_bands, (uint32_t)H);
-        hipLaunchKernelGGL((k_sixel_walk<true, true>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
+        hipLaunchKernelGGL((k_sixel_walk<true, true, false>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
     } else {
-        hipLaunchKernelGGL((k_sixel_walk<false, false>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
+        hipLaunchKernelGGL((k_sixel_walk<false, false, false>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
         hipLaunchKernelGGL(k_sixel_scan<false>, dim3(1), dim3(kSixelBlock), 0, stream, line_bytes, meta, header, header_bytes, out, cap, res, span, n_bands, (uint32_t)H);
-        hipLaunchKernelGGL((k_sixel_walk<true, false>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
+        hipLaunchKernelGGL((k_sixel_walk<true, false, false>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap, span);
     }
+    return (int)hipGetLastError();
+}
+
+// The encoder's PAL instances on a register plane of the adaptive palette (values below 256; the full stream alone).  last1: n_bands * 256
+// words; max_lines >= n_bands * min(256, 6 W); prefix: the stream's parts 1 to 4; defs / defs_bytes: the definitions and their length on the
+// device; res: 1 word of 64 bits, the length
+int ycge_launch_sixel_encode_palette(const uint8_t *index, int W, int H, uint32_t *last1, uint32_t *lines, uint32_t *line_bytes, uint32_t max_lines, uint32_t *meta,
+                                     const uint8_t *prefix, uint32_t prefix_bytes, const uint8_t *defs, const uint32_t *defs_bytes, uint8_t *out, uint32_t cap,
+                                     unsigned long long *res, int compute_units, hipStream_t stream)
+{
+    if (!index || !last1 || !lines || !line_bytes || !meta || !prefix || !defs || !defs_bytes || !out || !res || W <= 0 || H <= 0 || H > (1 << 24)) return (int)hipErrorInvalidValue;
+    constexpr uint32_t kRegisters = registers<true>();
+    const uint32_t n_bands = ((uint32_t)H + 5u) / 6u;
+    const uint64_t colours = 6ull * (uint32_t)W < kRegisters ? 6ull * (uint32_t)W : kRegisters;
+    if ((uint64_t)n_bands * colours > max_lines || n_bands > 65535u) return (int)hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(last1, 0, (size_t)n_bands * kRegisters * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return (int)e;
+    const dim3 tiles(((uint32_t)W + kPresenceTile - 1) / kPresenceTile, n_bands);
+    hipLaunchKernelGGL((k_sixel_presence<false, true>), tiles, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, (const uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_sixel_lines<true>, dim3(1), dim3(kSixelBlock), 0, stream, last1, n_bands, max_lines, lines, meta);
+    const uint32_t need = (max_lines + kSixelBlock / 64 - 1) / (kSixelBlock / 64);
+    const uint32_t limit = (uint32_t)(compute_units > 0 ? compute_units : 256) * 8u;
+    const dim3 grid(need < limit ? need : limit);
+    hipLaunchKernelGGL((k_sixel_walk<false, false, true>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap,
+                       (const uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_sixel_scan_palette, dim3(1), dim3(kSixelBlock), 0, stream, line_bytes, meta, prefix, prefix_bytes, defs, defs_bytes, out, cap, res);
+    hipLaunchKernelGGL((k_sixel_walk<true, false, true>), grid, dim3(kSixelBlock), 0, stream, index, (uint32_t)W, (uint32_t)H, last1, lines, meta, line_bytes, out, cap,
+                       (const uint32_t *)nullptr);
     return (int)hipGetLastError();
 }
 

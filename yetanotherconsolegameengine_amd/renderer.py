@@ -1106,6 +1106,52 @@ class RaytraceRenderer:
         stream = buf[:n.value].tobytes()
         return (stream, tuple(info), s) if sdr else (stream, tuple(info))
 
+    # ---------------------------------------------------------------- the adaptive sixel palette (ycge_render_frame_sixel_palette / _pixels_palette)
+    @staticmethod
+    def sixel_palette_stream_bound(px_width: int, px_height: int, lib=None) -> int:
+        """The most bytes the adaptive-palette sixel stream of a px_width x px_height picture can take (ycge_sixel_palette_stream_bound; no GPU needed)."""
+        L = lib if lib is not None else abi.load_library()
+        n = C.c_size_t(0)
+        rc = L.ycge_sixel_palette_stream_bound(int(px_width), int(px_height), C.byref(n))
+        if rc != 0:
+            raise abi.YcgeError(rc, f"no sixel stream bound for a {px_width} x {px_height} picture")
+        return n.value
+
+    def _sixel_palette_buffer(self):
+        bound = self.sixel_palette_stream_bound(self.fbW * self.ss, 2 * self.fbH * self.ss, self.L)
+        buf = self.__dict__.get("_sixel_buf")
+        if buf is None or buf.size < bound:
+            buf = self.__dict__["_sixel_buf"] = np.empty(bound, np.uint8)
+        return buf
+
+    def TryFlipAndBlitSixelPalette(self, viewport=(0, 0), clear_screen: bool = False, hold: bool = False, sdr: bool = False):
+        """One frame (ycge_render_frame_sixel_palette): the sixel stream of the frame's pixels under an adaptive palette - up to 256
+        median-cut registers built on the device from this picture, or with hold=True the palette the context kept from the last build
+        (none kept: built).  (bytes, palette (256, 4) uint8 - the registers' bytes, alpha 255, unused entries zero -, count), and the SDR
+        array behind them with sdr=True.  The next _delta call of any family returns a keyframe."""
+        buf, n = self._sixel_palette_buffer(), C.c_size_t(0)
+        palette, count = np.zeros((256, 4), np.uint8), C.c_int32(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._check(self.L.ycge_render_frame_sixel_palette(self.ctx, int(viewport[0]), int(viewport[1]), int(bool(clear_screen)), int(bool(hold)),
+                                                           buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size, C.byref(n), palette.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                           C.byref(count), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None, C.byref(self.stats)))
+        stream = buf[:n.value].tobytes()
+        return (stream, palette, count.value, s) if sdr else (stream, palette, count.value)
+
+    def TryFlipAndBlitPixelsPalette(self, rgba: bool = True, index: bool = True, hold: bool = False, sdr: bool = False) -> dict:
+        """One frame (ycge_render_frame_pixels_palette): TryFlipAndBlitPixels' planes with the adaptive palette's registers in "index", and
+        "palette" (256, 4) uint8 and "count" with them.  The delta state is left alone; the palette is kept as TryFlipAndBlitSixelPalette keeps it."""
+        W, H = self.fbW * self.ss, 2 * self.fbH * self.ss
+        shapes = {"sdr": ((self.fbH, self.fbW, 2, 3), np.float32), "rgba": ((H, W, 4), np.uint8), "index": ((H, W), np.uint8), "palette": ((256, 4), np.uint8)}
+        want = {"sdr": sdr, "rgba": rgba, "index": index, "palette": True}
+        arrays = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items() if want[k]}
+        ptr = lambda k, t: arrays[k].ctypes.data_as(C.POINTER(t)) if k in arrays else None
+        count = C.c_int32(0)
+        self._check(self.L.ycge_render_frame_pixels_palette(self.ctx, ptr("sdr", C.c_float), ptr("rgba", C.c_uint8), ptr("index", C.c_uint8), int(bool(hold)),
+                                                            ptr("palette", C.c_uint8), C.byref(count), C.byref(self.stats)))
+        arrays["count"] = count.value
+        return arrays
+
     # ---------------------------------------------------------------- ANSI streams with frames in flight (ycge_render_frame_async_ansi)
     def RenderAsyncAnsi(self, slot: int, console_width: int, console_height: int, viewport=(0, 0), default_fg: int = 7, default_bg: int = 0,
                         clear_screen: bool = False, rgb: bool = False, delta: bool = False, merge_gap: int = 3, tolerance: int = 0,
@@ -1493,6 +1539,35 @@ class VideoRenderer:
                                                           s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
         stream = buf[:n.value].tobytes()
         return (stream, tuple(info), s) if sdr else (stream, tuple(info))
+
+    def TryFlipAndBlitSixelPalette(self, frame, viewport=(0, 0), clear_screen: bool = False, hold: bool = False, sdr: bool = False):
+        """The sixel stream of the blit of `frame` under the adaptive palette (ycge_video_blit_sixel_palette), as
+        RaytraceRenderer.TryFlipAndBlitSixelPalette: (bytes, palette, count) or (bytes, palette, count, SDR array).  The kept palette is the
+        one the context's frames share."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        buf, n = self._r._sixel_palette_buffer(), C.c_size_t(0)
+        palette, count = np.zeros((256, 4), np.uint8), C.c_int32(0)
+        s = np.zeros((self.fbH, self.fbW, 2, 3), np.float32) if sdr else None
+        self._r._check(self.L.ycge_video_blit_sixel_palette(self.ctx, ptr, w, h, bpp, int(viewport[0]), int(viewport[1]), int(bool(clear_screen)), int(bool(hold)),
+                                                            buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size, C.byref(n), palette.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                            C.byref(count), s.ctypes.data_as(C.POINTER(C.c_float)) if sdr else None))
+        stream = buf[:n.value].tobytes()
+        return (stream, palette, count.value, s) if sdr else (stream, palette, count.value)
+
+    def TryFlipAndBlitPixelsPalette(self, frame, rgba: bool = True, index: bool = True, hold: bool = False, sdr: bool = False) -> dict:
+        """TryFlipAndBlitPixels' planes with the adaptive palette's registers in "index" (ycge_video_blit_pixels_palette), and "palette"
+        (256, 4) uint8 and "count" with them.  The delta state is left alone."""
+        f, ptr, w, h, bpp = self._frame_args(frame)
+        W, H = self.fbW * self.ss, 2 * self.fbH * self.ss
+        shapes = {"sdr": ((self.fbH, self.fbW, 2, 3), np.float32), "rgba": ((H, W, 4), np.uint8), "index": ((H, W), np.uint8), "palette": ((256, 4), np.uint8)}
+        want = {"sdr": sdr, "rgba": rgba, "index": index, "palette": True}
+        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items() if want[k]}
+        p = lambda k, t: out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
+        count = C.c_int32(0)
+        self._r._check(self.L.ycge_video_blit_pixels_palette(self.ctx, ptr, w, h, bpp, p("sdr", C.c_float), p("rgba", C.c_uint8), p("index", C.c_uint8), int(bool(hold)),
+                                                             p("palette", C.c_uint8), C.byref(count)))
+        out["count"] = count.value
+        return out
 
     def pixels_probe(self, frame, fb_width: int, fb_height: int, superSample: int = 1, dither: bool = False):
         """k_video_pixels alone on a caller-given geometry (ycge_test_video_pixels), whatever this console's size: (rgba, index)."""
